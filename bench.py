@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: BWTS build MB/s (+ inverse MB/s) on synthetic input, bit-exact round trip.
 
-    python bench.py --gpus N --steps K --warmup W [--workload zipf|uniform256|dna|text] [--log2n L]
+    python bench.py --gpus N --steps K --warmup W [--workload zipf|uniform256|dna|text] [--log2n L] [--dump-outputs DIR]
 
 A "step" is one forward transform of one input that is already resident in HBM.  N > 1 runs N independent
 replicas (one input per GPU, seed 1+rank; RCCL is only the barrier and the max-over-ranks of the times): either
@@ -9,7 +9,8 @@ under an outer `python -m torch.distributed.run ... bench.py --gpus N`, or -- wh
 bench.py starts those N ranks itself as a child process before anything here touches a GPU.
 Rank 0 prints ONE JSON line.  At N = 1 the line also carries: the text workload beside the headline one, the
 host-buffer path (bwts_forward / bwts_inverse on unpinned caller memory) and the CLI wall time (`e2e`), and the
-CPU baseline.
+CPU baseline.  --dump-outputs DIR writes what the last timed forward step and the last timed inverse step computed (rank 0) as
+.npy files: the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -156,7 +157,7 @@ def _per_kernel(a):
 
 def _real_text(ctx, d_in, d_out, d_back, cap, big=False):
     """Real text through the device path: best of 5 forwards and inverses (wall time per synchronous call), round trip.  big = False: the
-    53.6 MiB corpus of the gpu suite; True: 1 GiB of the same kind of material from more of the image (tests/realtext.py corpus_big)."""
+    64 MiB corpus of the gpu suite; True: 1 GiB of the same kind of material (tests/realtext.py corpus_big)."""
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from realtext import corpus, corpus_big
@@ -174,12 +175,46 @@ def _real_text(ctx, d_in, d_out, d_back, cap, big=False):
     ctx.inverse_device(d_out, m, d_back)
     for _ in range(5):
         t0 = time.perf_counter(); ctx.inverse_device(d_out, m, d_back); ti.append(time.perf_counter() - t0)
-    return {"workload": ("Python packages, ROCm headers and data files, source and documentation files of this image, concatenated (tests/realtext.py "
-                         "corpus_big)" if big else "source and documentation files of this image, concatenated (tests/realtext.py)"), "bytes": m,
+    return {"workload": "the project's own source and documentation text in overlapping pieces (tests/realtext.py %s)" % (
+                         "corpus_big" if big else "corpus"), "bytes": m,
             "sha256_in": hashlib.sha256(x.tobytes()).hexdigest(),
             "forward_ms": round(1e3 * min(tf), 2), "forward_MBps": round(m / 1e6 / min(tf), 1),
             "inverse_ms": round(1e3 * min(ti), 2), "inverse_MBps": round(m / 1e6 / min(ti), 1),
             "roundtrip_exact": bool(ctx.device_equal(d_in, d_back, m)), "rounds": info["rounds"], "tied_after_round0": info["active_after_round0"]}
+
+
+DUMP_SAMPLE = 1 << 21        # --dump-outputs: positions kept per array (float32 outputs + float64 index: 32 MiB in all at most)
+DUMP_SEED = 20250101
+
+
+def _sample_positions(n):
+    """The positions --dump-outputs keeps: all of them up to DUMP_SAMPLE, else a fixed, seeded, sorted sample of DUMP_SAMPLE."""
+    import numpy as np
+    if n <= DUMP_SAMPLE:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+
+
+def _sample_output(y):
+    idx = _sample_positions(y.size)
+    return (y if idx is None else y[idx]).astype("float32")
+
+
+def _dump_outputs(d, outputs, n):
+    """outputs {name: float32 array} -> d/<name>.npy (+ d/sample_index.npy, float64, when the outputs are samples)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    idx = _sample_positions(n)
+    files = {}
+    for name, a in sorted(outputs.items()):
+        np.save(os.path.join(d, name + ".npy"), a)
+        files[name + ".npy"] = {"dtype": "float32", "shape": list(a.shape)}
+    if idx is not None:
+        np.save(os.path.join(d, "sample_index.npy"), idx.astype(np.float64))
+        files["sample_index.npy"] = {"dtype": "float64", "shape": [int(idx.size)]}
+    return {"dir": d, "files": files, "n": n, "sampled": idx is not None,
+            "what": "output bytes of the last timed forward (bwts) and inverse step of rank 0, as float32%s" % (
+                "" if idx is None else "; positions sample_index.npy (seed %d)" % DUMP_SEED)}
 
 
 _FPS = None
@@ -431,10 +466,17 @@ def main(argv=None):
     ap.add_argument("--no-text", action="store_true", help="skip the text workload reported beside the headline one")
     ap.add_argument("--config5-items", type=int, default=4, help="files per GPU in the host-path leg of an N > 1 run (BASELINE config 5); 0 = skip")
     ap.add_argument("--config5-leg", action="store_true", help="run that leg at N = 1 too")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed forward step (and of the last timed inverse step) of rank 0 to DIR as .npy "
+                         "(float32; above %d bytes a fixed, seeded sample of positions, listed in sample_index.npy)" % DUMP_SAMPLE)
     ap.add_argument("--selftest-sleep-ms", type=float, default=0.0,
                     help="harness self-test (tests/test_dist_cpu.py): no GPU, no transform; every step sleeps "
                          "(rank+1) x this many ms so the rank/barrier/max-reduce/aggregate logic runs under gloo")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.selftest_sleep_ms > 0:
+        ap.error("--dump-outputs needs the real transform (not --selftest-sleep-ms)")
     raw_args = list(sys.argv[1:] if argv is None else argv)
 
     # ---- N > 1 without an outer launcher: start the N ranks as a child, before anything here touches a GPU ----------
@@ -495,8 +537,9 @@ def main(argv=None):
         except Exception as e:
             print("bench.py: CLI leg failed: %r" % (e,), file=sys.stderr)
 
-    def measure(workload, steps, warmup, inverse_steps, breakdown_steps):
-        """K timed forward steps (HIP events only on the dominant kernel), the inverse + round trip, then the breakdown."""
+    def measure(workload, steps, warmup, inverse_steps, breakdown_steps, capture=False):
+        """K timed forward steps (HIP events only on the dominant kernel), the inverse + round trip, then the breakdown.  capture: keep
+        sampled host copies of what the last timed forward and inverse steps wrote (taken outside the timed regions)."""
         ctx.generate(workload, 1 + rank, n, d_in)
         ctx.set_timing(1)
         for _ in range(warmup):
@@ -511,6 +554,9 @@ def main(argv=None):
         barrier()
         fwd_s = time.perf_counter() - t0
         fwd_info = tm.as_dict()
+        outputs = {}
+        if capture:
+            outputs["forward"] = _sample_output(d_out.download(n))
 
         ctx.inverse_device(d_out, n, d_back)            # warm
         roundtrip = ctx.device_equal(d_in, d_back, n)
@@ -524,6 +570,8 @@ def main(argv=None):
         barrier()
         inv_s = time.perf_counter() - t0
         inv_info = ti.as_dict()
+        if capture and inverse_steps > 0:
+            outputs["inverse"] = _sample_output(d_back.download(n))
 
         # every kernel class timed: its own pass, outside the two timed regions
         agg, inv_agg = {}, {}
@@ -535,9 +583,12 @@ def main(argv=None):
             _accumulate(inv_agg, ctx.timings())
         ctx.set_timing(0)
         return {"fwd_s": fwd_s, "inv_s": inv_s, "roundtrip": roundtrip, "fwd_info": fwd_info, "inv_info": inv_info,
-                "main": main_agg, "inv_main": inv_main, "agg": agg, "inv_agg": inv_agg}
+                "main": main_agg, "inv_main": inv_main, "agg": agg, "inv_agg": inv_agg, "outputs": outputs}
 
-    m = measure(args.workload, args.steps, args.warmup, args.inverse_steps, args.breakdown_steps)
+    m = measure(args.workload, args.steps, args.warmup, args.inverse_steps, args.breakdown_steps,
+                capture=bool(args.dump_outputs) and rank == 0)
+    dumped = _dump_outputs(args.dump_outputs, m["outputs"], n) if args.dump_outputs and rank == 0 else None
+    m["outputs"] = None
     # N > 1: the leg that measures config 5's real data flow (files in tmpfs -> bwts_forward_batch -> host buffers), every rank at once
     c5_s, c5_info = 0.0, None
     if (n_gpus > 1 or args.config5_leg) and args.config5_items > 0:
@@ -610,6 +661,8 @@ def main(argv=None):
             c5_bytes = n_gpus * c5_info["items_per_gpu"] * c5_info["bytes_each"]
             line["config5_host_path"] = dict(c5_info, wall_ms=round(1e3 * c5_s, 2), aggregate_MBps=round(c5_bytes / 1e6 / c5_s, 3),
                                              what="per rank: files -> mmap -> bwts_forward_batch -> host buffers, all ranks at once, barrier to barrier, max over ranks")
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if selftest:
             line["data"] = "selftest (no transform executed)"
         if n_gpus == 1 and not selftest:
@@ -639,15 +692,15 @@ def main(argv=None):
                         "HIP events on the engine's stream inside the timed region of the text leg (2 forwards)", per_forward=2)
                 if not t["roundtrip"]:
                     bad = 1.0
-                # real text beside the synthetic one (the reference's own workload is enwik8, Makefile:35-38, which no box has): source and
-                # documentation files of this image, as in the gpu suite (tests/realtext.py builds it; no oracle involved here)
+                # real text beside the synthetic one (the reference's own workload is enwik8, Makefile:35-38, which is not part of the
+                # project): the gpu suite's real-text corpus (tests/realtext.py builds it; no oracle involved here)
                 try:
                     line["text"]["real"] = _real_text(ctx, d_in, d_out, d_back, n)
                     if line["text"]["real"].get("roundtrip_exact") is False:
                         bad = 1.0
                 except Exception as e:
                     line["text"]["real"] = {"error": repr(e)}
-                # ... and 1 GiB of real text, the size the metric is quoted on (no enwik9 on any box; this is what the image itself holds)
+                # ... and 1 GiB of real text, the size the metric is quoted on
                 if n >= (1 << 30):
                     try:
                         line["text"]["real_1GiB"] = _real_text(ctx, d_in, d_out, d_back, n, big=True)

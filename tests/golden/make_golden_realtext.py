@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/realtext.json: sha-256 of the image's real-text corpus (tests/realtext.py, limit 2^26) and of the oracle's
-forward transform of it (oracle/bwts_oracle.c, the pinned CPU restatement of mk_bwts_sa.c:114-195).  ~5 s; run in the build container."""
+"""Generates tests/golden/realtext.json: sha-256 of the real-text corpus (tests/realtext.py, limit 2^26) and of the oracle's
+forward transform of it (oracle/bwts_oracle.c, the pinned CPU restatement of mk_bwts_sa.c:114-195).  ~1 min; needs no GPU."""
 import hashlib, json, os, sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))

@@ -1,79 +1,61 @@
-"""Real text for the repeat-rich regime (the reference's own workload is enwik8, Makefile:35-38, which no box here has): source and
-documentation files of THIS image, concatenated in a fixed order.  Test infrastructure: the corpus is only used when its sha-256 is
-the one on file (tests/golden/realtext.json, made by tests/golden/make_golden_realtext.py in the build container -- same image)."""
+"""Real text for the repeat-rich regime (the reference's own workload is enwik8, Makefile:35-38, which is not part of this project).
+
+The material is the project's own documentation and source text -- the .md, .py, .c, .h, .hip files and Makefiles of the tree, in
+sorted path order, concatenated (1.0 MB, 141 distinct bytes) -- stored once as tests/golden/realtext_seed.xz, so the corpus is
+the same wherever the repository is checked out.  A corpus is a stream of "files": pieces of that text of 256 B .. 64 KiB (log-uniform
+length, uniform offset), each with one byte in about 2 KiB replaced by a byte from elsewhere in the text -- the long but imperfect
+repeats that a directory of related sources and documents has.  Every choice comes from a seeded splitmix64 stream, so the bytes depend
+on nothing but the seed file.  Test infrastructure: the gpu tests hold the corpus to the sha-256 on file (tests/golden/realtext.json and
+realtext_1GiB.json, made by tests/golden/make_golden_realtext.py and make_golden_realtext_big.py)."""
+import lzma
 import os
+
+SEED_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "realtext_seed.xz")
+_M64 = (1 << 64) - 1
+_seed_text = None
+
+
+def seed_text():
+    global _seed_text
+    if _seed_text is None:
+        with open(SEED_FILE, "rb") as f:
+            _seed_text = lzma.decompress(f.read())
+    return _seed_text
+
+
+def _splitmix64(state):
+    while True:
+        state = (state + 0x9E3779B97F4A7C15) & _M64
+        z = state
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+        yield z ^ (z >> 31)
+
+
+def _assemble(limit, stream_seed):
+    text = seed_text()
+    s = len(text)
+    rnd = _splitmix64(stream_seed)
+    out = bytearray(limit)
+    at = 0
+    while at < limit:
+        # length 2^(8 + 8 u), u uniform in [0, 1) on 16 bits: 256 B .. 64 KiB
+        length = min(int(2.0 ** (8.0 + 8.0 * ((next(rnd) >> 48) / 65536.0))), limit - at)
+        src = next(rnd) % (s - length + 1)
+        out[at:at + length] = text[src:src + length]
+        for _ in range(length // 2048 + 1):
+            r = next(rnd)
+            out[at + (r & 0xFFFFFFFF) % length] = text[(r >> 32) % s]
+        at += length
+    return bytes(out)
 
 
 def corpus(limit):
-    out, total = [], 0
-    for root in ("/usr/lib/python3/dist-packages", "/usr/lib/python3.10", "/usr/share/doc", "/usr/include"):
-        for d, _, files in sorted(os.walk(root)):
-            for f in sorted(files):
-                if not f.endswith((".py", ".txt", ".h", ".hpp", ".md", ".rst", ".c", ".json", ".html")):
-                    continue
-                p = os.path.join(d, f)
-                try:
-                    b = open(p, "rb").read()
-                except OSError:
-                    continue
-                out.append(b)
-                total += len(b)
-                if total >= limit:
-                    return b"".join(out)[:limit]
-    return b"".join(out)
-
-
-# what the >= 1 GiB corpus is made of: the four roots of corpus(), the ROCm headers, and forty Python packages by name -- those that the
-# build container and the GPU boxes hold byte for byte alike (the container has more: its offline wheelhouse), largest first
-BIG_ROOTS = ("/usr/lib/python3/dist-packages", "/usr/lib/python3.10", "/usr/share/doc", "/usr/include", "/opt/rocm/include") + tuple(
-    "/usr/local/lib/python3.10/dist-packages/" + pkg for pkg in (
-        "torch", "sympy", "plotly", "scipy", "pandas", "triton", "fontTools", "numpy", "sqlalchemy", "matplotlib", "networkx", "kaleido",
-        "pygments", "libcst", "textual", "dash_svg", "pymongo", "dash", "mpmath", "narwhals", "pydantic", "hypothesis", "_pytest", "rich",
-        "PIL", "torchgen", "dns", "pybind11", "aiohttp", "google", "joblib", "fastapi", "werkzeug", "fsspec", "scikit_build_core",
-        "mpl_toolkits", "anyio", "multiprocess", "jinja2", "typer"))
+    """`limit` bytes of the corpus (the gpu suite's real-text input is 2^26 of them: tests/golden/realtext.json)."""
+    return _assemble(limit, 1)
 
 
 def corpus_big(limit):
-    """The same kind of material, from more of the image (ROCm headers, Python packages: torch's sources and headers are most of it), up
-    to `limit` bytes: the >= 1 GiB real-text input (tests/golden/realtext_1GiB.json).  Directories in sorted order, depth first; symbolic
-    links are not followed."""
-    # (the files are read by a pool of threads, a batch of paths at a time and in order: on a box whose page cache is cold the
-    # hundred thousand small reads took 90 s one after the other)
-    from concurrent.futures import ThreadPoolExecutor
-
-    def paths():
-        for root in BIG_ROOTS:
-            for d, dirs, files in os.walk(root):
-                dirs.sort()
-                for f in sorted(files):
-                    if f.endswith((".py", ".txt", ".h", ".hpp", ".md", ".rst", ".c", ".json", ".html")):
-                        yield os.path.join(d, f)
-
-    def read(p):
-        if os.path.islink(p):
-            return None
-        try:
-            return open(p, "rb").read()
-        except OSError:
-            return None
-
-    out, total, batch = [], 0, []
-    with ThreadPoolExecutor(max_workers=32) as ex:
-        def drain():
-            nonlocal total
-            for b in ex.map(read, batch):
-                if b is None:
-                    continue
-                out.append(b)
-                total += len(b)
-                if total >= limit:
-                    return True
-            batch.clear()
-            return False
-        for p in paths():
-            batch.append(p)
-            if len(batch) >= 4096 and drain():
-                return b"".join(out)[:limit]
-        if batch and drain():
-            return b"".join(out)[:limit]
-    return b"".join(out)
+    """The same kind of material from a stream of its own, up to `limit` bytes: the >= 1 GiB real-text input
+    (tests/golden/realtext_1GiB.json), where every piece of the text recurs about a thousand times."""
+    return _assemble(limit, 2)

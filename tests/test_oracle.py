@@ -177,3 +177,15 @@ def test_live_reference_unbwts_pins_forward():
             y = O.forward(x)
             assert np.array_equal(O.ref_unbwts(y, td), x)
             assert np.array_equal(O.ref_unbwts(x, td), O.inverse(x))
+
+
+def test_realtext_corpus_is_pinned():
+    """The gpu suite's real-text inputs come from tests/golden/realtext_seed.xz alone: the same bytes wherever the repository is, the
+    ones whose oracle output is on file (realtext.json, realtext_1GiB.json)."""
+    import realtext
+    for name, corpus in (("realtext.json", realtext.corpus), ("realtext_1GiB.json", realtext.corpus_big)):
+        gold = json.load(open(os.path.join(GOLD, name)))
+        x = corpus(gold["n"])
+        assert len(x) == gold["n"], name
+        assert np.count_nonzero(np.bincount(np.frombuffer(x, dtype=np.uint8), minlength=256)) == gold["sigma"], name
+        assert hashlib.sha256(x).hexdigest() == gold["sha256_in"], name

@@ -1,5 +1,5 @@
-"""Manual check (GPU box): real text from the image itself (source and documentation files under /usr/lib, /usr/share),
-concatenated up to a size limit.  Forward / inverse timings, round structure, and -- below 64 MiB -- equality with the oracle."""
+"""Manual check (GPU box): the real-text corpus of tests/realtext.py (the project's own source and documentation text in overlapping
+pieces) up to a size limit.  Forward / inverse timings, round structure, and -- below 64 MiB -- equality with the oracle."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np

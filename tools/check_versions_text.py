@@ -1,13 +1,13 @@
 """Manual check (GPU box): four lightly edited copies of the real-text corpus (like versions of the same files):
 very long repeats, many doubling rounds.  Round trip only (the CPU oracle is too slow here)."""
 import os, sys, time
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests"); sys.path.insert(0, "/root/repo/tools")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
 import __graft_entry__ as ge
-import importlib.util
-spec = importlib.util.spec_from_file_location("crt", "/root/repo/tools/check_realtext.py")
-src = open("/root/repo/tools/check_realtext.py").read().split("limit = (1 <<")[0]
-ns = {"__file__": "/root/repo/tools/check_realtext.py"}; exec(src, ns)
+CRT = os.path.join(ROOT, "tools", "check_realtext.py")
+src = open(CRT).read().split("limit = (1 <<")[0]
+ns = {"__file__": CRT}; exec(src, ns)
 base = np.frombuffer(ns["corpus"](1 << 26), dtype=np.uint8)
 rng = np.random.default_rng(7)
 parts = []

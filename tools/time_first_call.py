@@ -1,5 +1,5 @@
-import sys, time
-sys.path.insert(0, "/root/repo")
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as ge
 pkg = ge.load_package()
 t0 = time.time(); ctx = pkg.Context(0); print("ctx create %.0f ms" % (1e3 * (time.time() - t0)))

@@ -37,6 +37,7 @@ EXPORTS = [
     "bwts_forward_device", "bwts_inverse_device", "bwts_last_timings", "bwts_kernel_class_name", "bwts_strerror",
     "bwts_last_hip_error", "bwts_set_timing", "bwts_host_alloc", "bwts_host_free", "bwts_host_cost_name",
     "bwts_forward_batch", "bwts_inverse_batch",
+    "bwts_forward_segments", "bwts_inverse_segments", "bwts_forward_segments_device", "bwts_inverse_segments_device",
 ]
 # ... and include/bwts_test.h (harness and unit-test hooks)
 TEST_EXPORTS = [
@@ -110,6 +111,8 @@ def lib():
         L.bwts_host_free.argtypes = [vp, vp]
         for name in ("bwts_forward_batch", "bwts_inverse_batch"):
             getattr(L, name).argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(vp)]
+        for name in ("bwts_forward_segments", "bwts_inverse_segments", "bwts_forward_segments_device", "bwts_inverse_segments_device"):
+            getattr(L, name).argtypes = [vp, vp, vp, u64, vp]
         for name in ("bwts_forward_sink", "bwts_inverse_sink"):
             getattr(L, name).argtypes = [vp, vp, u64, SINK_FN, vp]
         L.bwts_generate_device.argtypes = [vp, i32, u64, u64, vp]
@@ -268,6 +271,35 @@ class Context:
 
     def inverse_batch(self, arrays):
         return self._batch(lib().bwts_inverse_batch, arrays)
+
+    # -- independent segments in one device pass -----------------------------------------
+    def _segments(self, fn, data, lengths, out=None):
+        a = _u8(data)
+        ls = np.ascontiguousarray(lengths, dtype=np.uint64)
+        if int(ls.sum(dtype=np.uint64)) != a.size or (ls.size and int(ls.max()) > a.size):
+            raise BwtsError(-1, "segment lengths do not add up to the input's size")
+        if out is None:
+            out = np.empty_like(a)
+        elif out.size < a.size:
+            raise BwtsError(-1, "output smaller than the input")
+        self._check(fn(self._h, a.ctypes.data, ls.ctypes.data, ls.size, out.ctypes.data))
+        return out
+
+    def forward_segments(self, data, lengths, out=None):
+        """bwts_forward_segments: data holds len(lengths) consecutive segments; each is transformed on its own, in one device pass.
+        `out` (optional) is a caller-provided uint8 array, which may be `data` itself."""
+        return self._segments(lib().bwts_forward_segments, data, lengths, out)
+
+    def inverse_segments(self, data, lengths, out=None):
+        return self._segments(lib().bwts_inverse_segments, data, lengths, out)
+
+    def forward_segments_device(self, d_in, lengths, d_out):
+        ls = np.ascontiguousarray(lengths, dtype=np.uint64)
+        self._check(lib().bwts_forward_segments_device(self._h, _ptr(d_in), ls.ctypes.data, ls.size, _ptr(d_out)))
+
+    def inverse_segments_device(self, d_in, lengths, d_out):
+        ls = np.ascontiguousarray(lengths, dtype=np.uint64)
+        self._check(lib().bwts_inverse_segments_device(self._h, _ptr(d_in), ls.ctypes.data, ls.size, _ptr(d_out)))
 
     def forward_into(self, a, out):
         """bwts_forward on caller-provided numpy buffers (no allocation inside the call)."""

@@ -341,6 +341,9 @@ extern "C" void bwts_ctx_destroy(bwts_ctx *ctx)
     for (int i = 0; i < BWTS_AUX_SLOTS; i++) if (ctx->aux[i]) (void)ctx_free(ctx, ctx->aux[i]);
     for (char *b : ctx->tied_blk) (void)hipFree(b);
     if (ctx->d_small) (void)ctx_free(ctx, ctx->d_small);
+    if (ctx->d_seg_off) (void)ctx_free(ctx, ctx->d_seg_off);
+    if (ctx->d_seg_scratch) (void)ctx_free(ctx, ctx->d_seg_scratch);
+    if (ctx->h_seg_off) (void)hipHostFree(ctx->h_seg_off);
     for (const auto &b : ctx->guard_freed) (void)hipFree(b.user - ctx->guard);
     ctx->guard_freed.clear();
     if (ctx->h_small) (void)hipHostFree(ctx->h_small);
@@ -374,6 +377,7 @@ extern "C" int bwts_ctx_release_memory(bwts_ctx *ctx)
     ctx->tied_blk.clear();
     for (int i = 0; i < 4; i++)
         if (ctx->d_io[i]) { HIPC(ctx_free(ctx, ctx->d_io[i])); ctx->d_io[i] = nullptr; ctx->d_io_cap[i] = 0; }
+    if (ctx->d_seg_scratch) { HIPC(ctx_free(ctx, ctx->d_seg_scratch)); ctx->d_seg_scratch = nullptr; ctx->d_seg_scratch_cap = 0; }
     return BWTS_OK;
 }
 
@@ -402,7 +406,7 @@ static int run_device(bwts_ctx *ctx, device_impl_fn fn, const void *d_in, u64 n,
     int rc = fn(ctx, (const u8 *)d_in, n, (u8 *)d_out);
     if (ctx->guard) {
         (void)hipStreamSynchronize(ctx->stream);
-        const int grc = guard_check(ctx, fn == forward_device_impl ? "forward" : "inverse");
+        const int grc = guard_check(ctx, fn == forward_device_impl || fn == forward_segments_impl ? "forward" : "inverse");
         if (rc == BWTS_OK) rc = grc;
     }
     if (rc != BWTS_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
@@ -415,6 +419,7 @@ static int run_device(bwts_ctx *ctx, device_impl_fn fn, const void *d_in, u64 n,
     for (int i = 0; i < BWTS_AUX_SLOTS; i++) ctx->tm.device_bytes += ctx->aux_cap[i];
     ctx->tm.device_bytes += ctx->d_io_cap[2] + ctx->d_io_cap[3];
     ctx->tm.device_bytes += ctx->tied_blk.size() * ((size_t)16 << ctx->tied_blk_lg);
+    ctx->tm.device_bytes += ctx->d_seg_cap + ctx->d_seg_scratch_cap;
     return BWTS_OK;
 }
 
@@ -699,7 +704,8 @@ static int ensure_io(bwts_ctx *ctx, u64 n, bool pairs)
 
 static size_t arena_hint(device_impl_fn fn, u64 n)
 {
-    return n <= 0x100000000ull ? (fn == forward_device_impl ? forward_arena_bytes(n) : inverse_arena_bytes(n)) : 0;
+    if (fn == inverse_segments_impl) return n <= 0x100000000ull ? inverse_segments_arena_bytes(n) : 0;
+    return n <= 0x100000000ull ? (fn == forward_device_impl || fn == forward_segments_impl ? forward_arena_bytes(n) : inverse_arena_bytes(n)) : 0;
 }
 
 static int run_host(bwts_ctx *ctx, device_impl_fn fn, const uint8_t *in, uint64_t n, uint8_t *out, bwts_sink_fn sink, void *user)
@@ -707,7 +713,7 @@ static int run_host(bwts_ctx *ctx, device_impl_fn fn, const uint8_t *in, uint64_
     if (!ctx || !in || (!out && !sink) || n == 0) return BWTS_E_ARG;
     HIPC(hipSetDevice(ctx->device));
     BWTS_TRY(ensure_io(ctx, n, false));
-    trace_alloc(ctx, "call    ", fn == forward_device_impl ? "forward: in" : "inverse: in", in, n);
+    trace_alloc(ctx, "call    ", fn == forward_device_impl || fn == forward_segments_impl ? "forward: in" : "inverse: in", in, n);
     if (out) trace_alloc(ctx, "call    ", "out", out, n);
     Stager &sg = ctx->stg[0];
     // A context's first call allocates its arena, which can cost as long as the whole input copy where the driver clears what it
@@ -888,6 +894,114 @@ extern "C" int bwts_inverse_sink(bwts_ctx *ctx, const uint8_t *in, uint64_t n, b
 {
     if (!sink) return BWTS_E_ARG;
     return run_host(ctx, inverse_device_impl, in, n, nullptr, sink, user);
+}
+
+// ------------------------------------------------------------------------------------
+// independent segments in one device pass: the segment table goes to the context, the transform runs through the same host / device
+// plumbing as a single input (staging, pre-faulting, a failed call leaves `out` as it was)
+// ------------------------------------------------------------------------------------
+static int set_segments(bwts_ctx *ctx, const uint64_t *lengths, uint64_t count, u64 *total)
+{
+    if (!ctx || !lengths || count == 0) return BWTS_E_ARG;
+    u64 sum = 0;
+    for (u64 s = 0; s < count; s++) {
+        if (lengths[s] == 0 || lengths[s] > ~0ull - sum) return BWTS_E_ARG;
+        sum += lengths[s];
+    }
+    if (sum > 0x100000000ull) return BWTS_E_RANGE;
+    HIPC(hipSetDevice(ctx->device));
+    ctx->seg_off.resize(count + 1);
+    ctx->seg_off[0] = 0;
+    for (u64 s = 0; s < count; s++) ctx->seg_off[s + 1] = ctx->seg_off[s] + lengths[s];
+    const size_t bytes = (count + 1) * sizeof(u64);
+    const size_t room = 3 * bytes;       // the table, and behind it a second one of up to 2 count + 1 words (seg_upload_extra)
+    if (room > ctx->d_seg_cap) {
+        if (ctx->d_seg_off) { HIPC(hipStreamSynchronize(ctx->stream)); HIPC(ctx_free(ctx, ctx->d_seg_off)); ctx->d_seg_off = nullptr; ctx->d_seg_cap = 0; }
+        void *p = nullptr;
+        const size_t cap = align_up(room, 1 << 16);
+        if (ctx_malloc(ctx, &p, cap, "segment table") != hipSuccess) { (void)hipGetLastError(); return BWTS_E_NOMEM; }
+        ctx->d_seg_off = (u64 *)p;
+        ctx->d_seg_cap = cap;
+    }
+    // the table travels from a pinned block on the context's stream, ahead of the transform (the stream is idle between calls: the wait
+    // only makes sure no earlier copy still reads the block)
+    if (room > ctx->h_seg_cap) {
+        HIPC(hipStreamSynchronize(ctx->stream));
+        if (ctx->h_seg_off) { HIPC(hipHostFree(ctx->h_seg_off)); ctx->h_seg_off = nullptr; ctx->h_seg_cap = 0; }
+        void *p = nullptr;
+        const size_t cap = align_up(room, 1 << 16);
+        if (hipHostMalloc(&p, cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return BWTS_E_NOMEM; }
+        ctx->h_seg_off = (u64 *)p;
+        ctx->h_seg_cap = cap;
+    } else {
+        HIPC(hipStreamSynchronize(ctx->stream));
+    }
+    memcpy(ctx->h_seg_off, ctx->seg_off.data(), bytes);
+    HIPC(hipMemcpyAsync(ctx->d_seg_off, ctx->h_seg_off, bytes, hipMemcpyHostToDevice, ctx->stream));
+    *total = sum;
+    return BWTS_OK;
+}
+
+int seg_upload_extra(bwts_ctx *ctx, const u64 *words, u64 count, u64 **d_words)
+{
+    const u64 at = (u64)ctx->seg_off.size();
+    if ((at + count) * sizeof(u64) > ctx->d_seg_cap || (at + count) * sizeof(u64) > ctx->h_seg_cap) return BWTS_E_INTERNAL;
+    memcpy(ctx->h_seg_off + at, words, count * sizeof(u64));
+    HIPC(hipMemcpyAsync(ctx->d_seg_off + at, ctx->h_seg_off + at, count * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    *d_words = ctx->d_seg_off + at;
+    return BWTS_OK;
+}
+
+int seg_scratch_reserve(bwts_ctx *ctx, size_t bytes, u8 **out)
+{
+    if (bytes > ctx->d_seg_scratch_cap) {
+        if (ctx->d_seg_scratch) { HIPC(hipStreamSynchronize(ctx->stream)); HIPC(ctx_free(ctx, ctx->d_seg_scratch)); ctx->d_seg_scratch = nullptr; ctx->d_seg_scratch_cap = 0; }
+        void *p = nullptr;
+        const size_t cap = align_up(bytes, 1 << 20);
+        if (ctx_malloc(ctx, &p, cap, "segment scratch") != hipSuccess) { (void)hipGetLastError(); return BWTS_E_NOMEM; }
+        ctx->d_seg_scratch = (u8 *)p;
+        ctx->d_seg_scratch_cap = cap;
+    }
+    *out = ctx->d_seg_scratch;
+    return BWTS_OK;
+}
+
+static int run_segments_host(bwts_ctx *ctx, device_impl_fn fn, const uint8_t *in, const uint64_t *lengths, uint64_t count, uint8_t *out)
+{
+    if (!ctx || !in || !out) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(set_segments(ctx, lengths, count, &n));
+    return run_host(ctx, fn, in, n, out, nullptr, nullptr);
+}
+
+static int run_segments_device(bwts_ctx *ctx, device_impl_fn fn, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out)
+{
+    if (!ctx || !d_in || !d_out) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(set_segments(ctx, lengths, count, &n));
+    const char *a = (const char *)d_in, *b = (const char *)d_out;
+    if (a < b + n && b < a + n) return BWTS_E_ARG;
+    return run_device(ctx, fn, d_in, n, d_out);
+}
+
+extern "C" int bwts_forward_segments(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, uint64_t count, uint8_t *out)
+{
+    return run_segments_host(ctx, forward_segments_impl, in, lengths, count, out);
+}
+
+extern "C" int bwts_inverse_segments(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, uint64_t count, uint8_t *out)
+{
+    return run_segments_host(ctx, inverse_segments_impl, in, lengths, count, out);
+}
+
+extern "C" int bwts_forward_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out)
+{
+    return run_segments_device(ctx, forward_segments_impl, d_in, lengths, count, d_out);
+}
+
+extern "C" int bwts_inverse_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out)
+{
+    return run_segments_device(ctx, inverse_segments_impl, d_in, lengths, count, d_out);
 }
 
 extern "C" int bwts_host_alloc(bwts_ctx *ctx, uint64_t bytes, void **h_ptr)

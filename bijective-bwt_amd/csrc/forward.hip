@@ -2002,6 +2002,80 @@ static int lyndon_fast(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, 
     return BWTS_OK;
 }
 
+// ------------------------------------------------------------------------------------
+// Lyndon factors of many independent segments (bwts_forward_segments)
+// ------------------------------------------------------------------------------------
+// One wave per segment runs Duval's algorithm on the segment alone, so a suffix ends at its segment's end (the shorter one is the
+// smaller) whatever the next segment holds.  The scalar state (i, j, k) is the same in every lane; the lanes look at 64 positions at
+// once: while k == i the scan skips every j with T[j] > T[i] (each only resets k to i), otherwise it skips the run of positions where
+// T[k + l] == T[j + l].  A factor start gets flag[p] = 1; the compaction scan of the general path turns the flags into the sorted list.
+// Its work is the segment's length in sequential steps: segments of SEG_FWD_BIG bytes or more never get here (forward_segments_impl).
+__global__ __launch_bounds__(256) void seg_duval_kernel(const u8 *__restrict__ T, const u64 *__restrict__ seg_off, u64 count, u8 *__restrict__ flag)
+{
+    const u64 s = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= count) return;
+    const int lane = lane_id();
+    const u64 base = seg_off[s], L = seg_off[s + 1] - base;
+    const u8 *S = T + base;
+    u64 i = 0;
+    while (i < L) {
+        u64 j = i + 1, k = i;
+        for (;;) {
+            if (k == i) {
+                const u32 si = S[i];
+                for (;;) {
+                    const u64 q = j + (u64)lane;
+                    const bool stop = q >= L || (u32)S[q] <= si;
+                    const u64 m = __ballot(stop);
+                    if (m) { j += (u64)(__ffsll((unsigned long long)m) - 1); break; }
+                    j += 64;
+                }
+                if (j >= L || S[j] < S[k]) break;
+                k++; j++;
+                continue;
+            }
+            for (;;) {
+                const u64 q = j + (u64)lane;
+                const bool stop = q >= L || S[k + lane] != S[q];
+                const u64 m = __ballot(stop);
+                if (m) { const u64 l = (u64)(__ffsll((unsigned long long)m) - 1); k += l; j += l; break; }
+                k += 64; j += 64;
+            }
+            if (j >= L || S[j] < S[k]) break;
+            k = i; j++;                                   // T[k] < T[j]
+        }
+        // factors of length j - k start at i, i + (j - k), ... while <= k
+        const u64 p = j - k, cnt = (k - i) / p + 1;
+        for (u64 t = (u64)lane; t < cnt; t += 64) flag[base + i + t * p] = 1;
+        i += cnt * p;
+    }
+}
+
+static int segment_factors(bwts_ctx *ctx, const u8 *d_T, u64 n, const SegTable &seg, SortSpace &sp, u32 **d_fstart, u64 *k_out)
+{
+    u8 *flag = seg.flag;
+    u32 *starts_tmp = (u32 *)sp.keys[1];
+    u64 *total = ctx->d_small + CNT_TOTAL;
+    {
+        SpanGuard g(ctx, BWTS_K_LYNDON, n, 2 * n);
+        HIPC(hipMemsetAsync(flag, 0, n, ctx->stream));
+        seg_duval_kernel<<<dim3((unsigned)((seg.count + 3) / 4)), dim3(256), 0, ctx->stream>>>(d_T, seg.d_off, seg.count, flag);
+        HIPC(hipGetLastError());
+        FlagIn fin{flag};
+        StartOut sout{flag, starts_tmp, n, total};
+        BWTS_TRY((device_scan<false, u32>(ctx, n, fin, sout, OpAdd(), 0u, sp.scan_temp)));
+    }
+    BWTS_TRY(read_small(ctx, CNT_TOTAL, 1));
+    const u64 k = ctx->h_small[CNT_TOTAL];
+    if (k < seg.count || k > n) return BWTS_E_INTERNAL;
+    char *fl = nullptr;
+    BWTS_TRY(aux_reserve_slot(ctx, 2, (size_t)k * 4, &fl));
+    HIPC(hipMemcpyAsync(fl, starts_tmp, k * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
+    *d_fstart = (u32 *)fl;
+    *k_out = k;
+    return BWTS_OK;
+}
+
 static int lyndon_mode(const bwts_ctx *ctx)
 {
     const char *env = bwts_knob(ctx, "BWTS_LYNDON");     // auto (default) | fast | general
@@ -2012,7 +2086,7 @@ static int lyndon_mode(const bwts_ctx *ctx)
 
 // Finds the factors and leaves the cyclic round-0 keys in sp.keys[0] / identity in sp.vals[0].
 static int factors_and_keys(bwts_ctx *ctx, const u8 *d_T, u64 n, SortSpace &sp, Alphabet *al, u32 **d_fstart, u64 *k_out,
-                            u32 *lyndon_rounds, bool hist_ready = false)
+                            u32 *lyndon_rounds, bool hist_ready = false, const SegTable *seg = nullptr)
 {
     u64 *cand[2];
     u32 *cvals[2];
@@ -2025,10 +2099,18 @@ static int factors_and_keys(bwts_ctx *ctx, const u8 *d_T, u64 n, SortSpace &sp, 
     if (!fast_starts) return BWTS_E_NOMEM;
 
     if (!hist_ready) BWTS_TRY(read_histogram(ctx, d_T, n));
-    const int mode = lyndon_mode(ctx);
+    const int mode = seg ? 3 : lyndon_mode(ctx);
     bool done = false;
     *lyndon_rounds = 0;
-    if (mode != 2) {
+    if (seg) {                  // independent segments: each one's own factors (every segment end is a factor end)
+        BWTS_TRY(segment_factors(ctx, d_T, n, *seg, sp, d_fstart, k_out));
+        STAGE("segment factors");
+        SampleScratch ss{d_T, {sp.keys[0], sp.keys[1]}, {sp.vals[0], sp.vals[1]}, sp.tile_hist, sp.scan_temp};
+        BWTS_TRY(set_alphabet(ctx, false, n, al, &ss));
+        sp.split_keys = sp.want_split && radix_packed_applicable(ctx, n, al->key_bits);
+        BWTS_TRY(launch_keybuild0(ctx, d_T, n, *al, sp, nullptr, sp.split_keys));
+        done = true;
+    } else if (mode != 2) {
         u64 *tile_min = arena_array<u64>(ctx, scan_tiles(n) + 1);
         if (!tile_min) return BWTS_E_NOMEM;
         SampleScratch ss{d_T, {sp.keys[0], sp.keys[1]}, {sp.vals[0], sp.vals[1]}, sp.tile_hist, sp.scan_temp};
@@ -2149,6 +2231,53 @@ __global__ __launch_bounds__(256) void patch_ties_kernel(const u32 *__restrict__
 
 #include "wide_path.h"
 
+// ------------------------------------------------------------------------------------
+// independent segments: the cyclic sort emitted every byte in global rank order; segment s's bytes go to [off_s, off_s + len_s)
+// in that order (a stable partition by the segment of SA[r]).  Key = segment << 8 | byte, LSD passes on the segment bits only.
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void seg_fill_kernel(const u64 *__restrict__ seg_off, u64 count, u32 *__restrict__ segid)
+{
+    const u64 s = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= count) return;
+    const u64 end = seg_off[s + 1];
+    for (u64 p = seg_off[s] + (u64)lane_id(); p < end; p += 64) segid[p] = (u32)s;
+}
+__global__ __launch_bounds__(256) void seg_keys_kernel(const u32 *__restrict__ SA, const u32 *__restrict__ segid, const u8 *__restrict__ bytes, u64 n,
+                                                       u64 *__restrict__ keys)
+{
+    const u64 r = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (r < n) keys[r] = ((u64)segid[SA[r]] << 8) | bytes[r];
+}
+__global__ __launch_bounds__(256) void seg_bytes_kernel(const u64 *__restrict__ keys, u64 n, u8 *__restrict__ out)
+{
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = (u8)keys[i];
+}
+
+static int partition_by_segment(bwts_ctx *ctx, u64 n, const SegTable &seg, SortSpace &sp, const u32 *SA, u8 *d_out)
+{
+    // after the sort only SA (one of the value buffers) and the output are live: the other value buffer takes the segment ids, the
+    // two key buffers the sort
+    u32 *segid = SA == sp.vals[0] ? sp.vals[1] : sp.vals[0];
+    int sbits = bitlen_u64(seg.count - 1);
+    if (sbits < 1) sbits = 1;
+    {
+        SpanGuard g(ctx, BWTS_K_OTHER, n, 4 * n);
+        seg_fill_kernel<<<dim3((unsigned)((seg.count + 3) / 4)), dim3(256), 0, ctx->stream>>>(seg.d_off, seg.count, segid);
+        seg_keys_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream>>>(SA, segid, d_out, n, sp.keys[0]);
+        HIPC(hipGetLastError());
+    }
+    int res = 0;
+    u64 *keys[2] = {sp.keys[0], sp.keys[1]};
+    BWTS_TRY(radix_sort_keys(ctx, keys, sp.tile_hist, sp.scan_temp, n, 8, sbits, &res));
+    {
+        SpanGuard g(ctx, BWTS_K_OTHER, n, 9 * n);
+        seg_bytes_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream>>>(keys[res], n, d_out);
+        HIPC(hipGetLastError());
+    }
+    return BWTS_OK;
+}
+
 size_t forward_arena_bytes(u64 n)
 {
     // candidate buffers + sort space + the round-0 flag words (packed passes; a sort on wide keys keeps the previous-symbol array
@@ -2172,12 +2301,19 @@ int constant_input_probe(bwts_ctx *ctx, const u8 *d_in, u64 n, bool *constant)
     return BWTS_OK;
 }
 
+static int forward_run(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, const SegTable *seg);
+
 int forward_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
+{
+    return forward_run(ctx, d_in, n, d_out, nullptr);
+}
+
+static int forward_run(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, const SegTable *seg)
 {
     // beyond 32-bit indices: the blocked path with 64-bit positions and ranks (wide_path.h).  BWTS_FORCE_WIDE=1 sends every
     // input there, falling back when the wide form cannot take it; =2 does not fall back (tests)
     const int force_wide = [ctx] { const char *e = bwts_knob(ctx, "BWTS_FORCE_WIDE"); return e ? atoi(e) : 0; }();
-    if (n > 0x100000000ull) {
+    if (!seg && n > 0x100000000ull) {
         // one byte value only, beyond 2^32 (every position is a factor and a candidate: the wide path's factor search would refuse it
         // with BWTS_E_RANGE): the identity, as below -- eight probes first, the histogram only if they agree
         bool constant = false;
@@ -2189,7 +2325,7 @@ int forward_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
             return BWTS_OK;
         }
     }
-    if (n > 0x100000000ull || force_wide) {
+    if (!seg && (n > 0x100000000ull || force_wide)) {
         const int rc = forward_wide_impl(ctx, d_in, n, d_out);
         if (n > 0x100000000ull || force_wide == 2 || rc != BWTS_E_RANGE) return rc;
     }
@@ -2217,9 +2353,11 @@ int forward_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
     u64 k = 0;
     u32 lrounds = 0;
     const char *emit_env = bwts_knob(ctx, "BWTS_EMIT");      // carry (default) | gather
-    const bool carry = radix_supports_sym(ctx) && !(emit_env && !strcmp(emit_env, "gather"));
+    // (segments: the partition below needs the whole suffix array, which the sort rebuilds for its tied elements only when no byte
+    // rides on it -- the gather emission)
+    const bool carry = !seg && radix_supports_sym(ctx) && !(emit_env && !strcmp(emit_env, "gather"));
     sp.want_split = carry;                           // the byte stream rides round 0 => the packed passes may take split keys
-    BWTS_TRY(factors_and_keys(ctx, d_in, n, sp, &al, &d_fstart, &k, &lrounds, true));
+    BWTS_TRY(factors_and_keys(ctx, d_in, n, sp, &al, &d_fstart, &k, &lrounds, true, seg));
     ctx->tm.factors = k;
     ctx->tm.lyndon_rounds = lrounds;
     ctx->tm.key_symbols = (u32)al.msym;
@@ -2273,5 +2411,81 @@ int forward_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
         emit_kernel<<<dim3((unsigned)((octs + 255) / 256)), dim3(256), 0, ctx->stream>>>(SA, P, n, d_out);
     }
     HIPC(hipGetLastError());
+    if (seg) BWTS_TRY(partition_by_segment(ctx, n, *seg, sp, SA, d_out));
+    return BWTS_OK;
+}
+
+// one wave per segment moves its bytes between the caller's layout (at src_off[s]) and the packed block of the short segments (at off[s])
+__global__ __launch_bounds__(256) void seg_move_kernel(const u8 *__restrict__ from, u8 *__restrict__ to, const u64 *__restrict__ off,
+                                                       const u64 *__restrict__ src_off, u64 count, int gather)
+{
+    const u64 s = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= count) return;
+    const u64 a = off[s], len = off[s + 1] - a, b = src_off[s];
+    const u64 fb = gather ? b : a, tb = gather ? a : b;
+    for (u64 i = (u64)lane_id(); i < len; i += 64) to[tb + i] = from[fb + i];
+}
+
+int forward_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
+{
+    const std::vector<u64> &off = ctx->seg_off;
+    const u64 count = (u64)off.size() - 1;
+    if (count == 1) return forward_run(ctx, d_in, n, d_out, nullptr);
+    // A segment of `big` bytes or more gains nothing from the shared pass and would cost its length in sequential Duval steps there:
+    // it is transformed alone, straight into its place.  BWTS_SEG_FWD_BIG (test switch) moves the line: 1 = every segment alone.
+    u64 big = SEG_FWD_BIG;
+    if (const char *e = bwts_knob(ctx, "BWTS_SEG_FWD_BIG")) { const long long v = atoll(e); if (v >= 1) big = (u64)v; }
+    u64 nshort = 0, m = 0, factors = 0;
+    u32 rounds = 0;
+    for (u64 s = 0; s < count; s++) {
+        const u64 len = off[s + 1] - off[s];
+        if (len < big) { nshort++; m += len; }
+    }
+    if (nshort == count) {
+        SegTable seg{ctx->d_seg_off, count, nullptr};
+        BWTS_TRY(seg_scratch_reserve(ctx, n, &seg.flag));
+        return forward_run(ctx, d_in, n, d_out, &seg);
+    }
+    for (u64 s = 0; s < count; s++) {
+        const u64 len = off[s + 1] - off[s];
+        if (len < big) continue;
+        BWTS_TRY(forward_run(ctx, d_in + off[s], len, d_out + off[s], nullptr));
+        factors += ctx->tm.factors;
+        if (ctx->tm.rounds > rounds) rounds = ctx->tm.rounds;
+    }
+    if (nshort) {
+        // the short segments, packed into one block: table (nshort + 1 words) and their places in the caller's buffers (nshort words)
+        std::vector<u64> tab(2 * nshort + 1);
+        u64 j = 0;
+        tab[0] = 0;
+        for (u64 s = 0; s < count; s++) {
+            const u64 len = off[s + 1] - off[s];
+            if (len >= big) continue;
+            tab[nshort + 1 + j] = off[s];
+            tab[j + 1] = tab[j] + len;
+            j++;
+        }
+        u64 *d_tab = nullptr;
+        BWTS_TRY(seg_upload_extra(ctx, tab.data(), tab.size(), &d_tab));
+        u8 *scr = nullptr;
+        const size_t m1 = align_up((size_t)m, 256);
+        BWTS_TRY(seg_scratch_reserve(ctx, 3 * m1, &scr));
+        u8 *pin = scr, *pout = scr + m1;
+        const unsigned blocks = (unsigned)((nshort + 3) / 4);
+        seg_move_kernel<<<dim3(blocks), dim3(256), 0, ctx->stream>>>(d_in, pin, d_tab, d_tab + nshort + 1, nshort, 1);
+        HIPC(hipGetLastError());
+        if (nshort == 1) BWTS_TRY(forward_run(ctx, pin, m, pout, nullptr));
+        else {
+            SegTable seg{d_tab, nshort, scr + 2 * m1};
+            BWTS_TRY(forward_run(ctx, pin, m, pout, &seg));
+        }
+        seg_move_kernel<<<dim3(blocks), dim3(256), 0, ctx->stream>>>(pout, d_out, d_tab, d_tab + nshort + 1, nshort, 0);
+        HIPC(hipGetLastError());
+        factors += ctx->tm.factors;
+        if (ctx->tm.rounds > rounds) rounds = ctx->tm.rounds;
+    }
+    ctx->tm.n = n;
+    ctx->tm.factors = factors;
+    ctx->tm.rounds = rounds;
     return BWTS_OK;
 }

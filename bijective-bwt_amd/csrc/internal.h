@@ -120,6 +120,15 @@ struct bwts_ctx {
     int chain_cap;         // ... of the chained packed pass kernel (radix.hip, CHAINED passes)
     int rx_config;         // radix tile shape (BWTS_RX_CONFIG, a tuning knob; 0 = the product shape)
 
+    // segment table of the current segmented call: offsets on the host (count + 1) and their device copy
+    std::vector<u64> seg_off;
+    u64 *d_seg_off = nullptr;
+    size_t d_seg_cap = 0;
+    u64 *h_seg_off = nullptr;           // pinned staging of the table
+    size_t h_seg_cap = 0;
+    u8 *d_seg_scratch = nullptr;        // forward: factor-start flags
+    size_t d_seg_scratch_cap = 0;
+
     bwts_timings tm;
     double host_ms[BWTS_H_COUNT];   // cumulative host-side costs (BWTS_H_*)
     bool launched;                  // a kernel of this context has run (the code object is loaded)
@@ -210,6 +219,15 @@ int radix_sort_keys(bwts_ctx *ctx, u64 *keys[2], u32 *tile_hist, void *scan_temp
 
 // ---- forward / inverse drivers ----------------------------------------------------
 int forward_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
+// independent segments (bwts_forward_segments / bwts_inverse_segments): the table set on the context by the entry point
+// d_off: count + 1 device words, d_off[0] = 0, d_off[count] = n; flag: n bytes of factor-start flags (forward)
+struct SegTable { const u64 *d_off; u64 count; u8 *flag; };
+#define SEG_FWD_BIG (1ull << 21)     // forward: segments of this length or more are transformed alone
+int seg_scratch_reserve(bwts_ctx *ctx, size_t bytes, u8 **p);     // a device block that stays with the context, grown on demand
+int seg_upload_extra(bwts_ctx *ctx, const u64 *words, u64 count, u64 **d_words);   // a second table, behind the segment table
+int forward_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
+int inverse_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
+size_t inverse_segments_arena_bytes(u64 n);
 int inverse_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
 size_t forward_arena_bytes(u64 n);
 size_t inverse_arena_bytes(u64 n);

@@ -1338,3 +1338,166 @@ int inverse_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
     }
     return BWTS_OK;
 }
+
+// ------------------------------------------------------------------------------------
+// independent segments (bwts_inverse_segments)
+// ------------------------------------------------------------------------------------
+// LF per segment: LF[i] = C_s[B[i]] + (occurrences of B[i] in segment s before i), as an index local to the segment.  One wave per
+// segment: byte histogram in LDS, exclusive scan, then 64 positions per step in order -- a lane's rank among the lanes holding the same
+// byte comes from eight ballots, and the last such lane advances the byte's counter.
+#define SEG_INV_VISITED 0xffffffffu
+__global__ __launch_bounds__(256) void seg_lf_kernel(const u8 *__restrict__ B, const u64 *__restrict__ seg_off, u64 count, u64 big, u32 *__restrict__ LF)
+{
+    __shared__ u32 cnt_all[4][256];
+    const u64 s = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= count) return;
+    const u64 base = seg_off[s], L = seg_off[s + 1] - base;
+    if (L >= big) return;
+    const int lane = lane_id();
+    u32 *cnt = cnt_all[threadIdx.x >> 6];
+    const u8 *S = B + base;
+    for (int c = lane; c < 256; c += 64) cnt[c] = 0;
+    __builtin_amdgcn_wave_barrier();
+    for (u64 p = (u64)lane; p < L; p += 64) atomicAdd(&cnt[S[p]], 1u);
+    // the counters are this wave's alone and a wave's LDS operations complete in order; the barriers keep the compiler from moving
+    // one phase's accesses across the next's
+    __builtin_amdgcn_wave_barrier();
+    {
+        const u32 v0 = cnt[4 * lane], v1 = cnt[4 * lane + 1], v2 = cnt[4 * lane + 2], v3 = cnt[4 * lane + 3];
+        const u32 sum = v0 + v1 + v2 + v3;
+        const u32 ex = wave_scan_inclusive(sum, OpAdd()) - sum;
+        cnt[4 * lane] = ex; cnt[4 * lane + 1] = ex + v0; cnt[4 * lane + 2] = ex + v0 + v1; cnt[4 * lane + 3] = ex + v0 + v1 + v2;
+    }
+    __builtin_amdgcn_wave_barrier();
+    for (u64 p0 = 0; p0 < L; p0 += 64) {
+        const u64 p = p0 + (u64)lane;
+        const bool act = p < L;
+        const u32 b = act ? (u32)S[p] : 0u;
+        u64 match = __ballot(act);
+#pragma unroll
+        for (int bit = 0; bit < 8; bit++) {
+            const u64 ones = __ballot((b >> bit) & 1u);
+            match &= ((b >> bit) & 1u) ? ones : ~ones;
+        }
+        if (act) {
+            const u32 at = cnt[b];
+            LF[base + p] = at + (u32)__popcll(match & lanemask_lt());
+            if ((match >> lane) == 1ull) cnt[b] = at + (u32)__popcll(match);      // the group's last lane
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// The cycle walk of unbwts.c:62-86 inside one segment, one lane per segment: cycles by smallest index, each written from the end of
+// what is left of the segment backwards.
+__global__ __launch_bounds__(64) void seg_walk_kernel(const u8 *__restrict__ B, u32 *__restrict__ LF, const u64 *__restrict__ seg_off, u64 count, u64 big,
+                                                       u8 *__restrict__ out, unsigned long long *__restrict__ cycles)
+{
+    const u64 s = (u64)blockIdx.x * 64 + threadIdx.x;       // one wave per workgroup: the chains spread over every CU
+    u64 ncyc = 0;
+    if (s < count) {
+        const u64 base = seg_off[s], L = seg_off[s + 1] - base;
+        if (L < big) {
+            u32 *lf = LF + base;
+            const u8 *b = B + base;
+            u8 *o = out + base;
+            u64 pos = L;
+            u32 start = 0;
+            while (pos > 0) {
+                while (start < L && lf[start] == SEG_INV_VISITED) start++;
+                if (start >= L) break;
+                u32 x = start;
+                do {
+                    const u32 nx = lf[x];
+                    o[--pos] = b[x];
+                    lf[x] = SEG_INV_VISITED;
+                    x = nx;
+                } while (x != start && pos > 0);
+                ncyc++;
+            }
+        }
+    }
+    if (ncyc) atomicAdd(cycles, (unsigned long long)ncyc);
+}
+
+// measured on 1 GiB (profiles/segments_1gib_zipf_text.txt): one step of a walk with 16 384 chains in flight ~5.3 us; 262 144 chains of
+// 4 KiB: 12 G steps/s; a single-input inverse of 64 KiB ~0.3 ms
+#define SEG_WALK_STEP_US 5.0
+#define SEG_WALK_STEPS_PER_US 12000.0
+#define SEG_CALL_US 300.0
+static u64 seg_inverse_threshold(const std::vector<u64> &off)
+{
+    const u64 count = (u64)off.size() - 1;
+    u64 cnt[66] = {0}, bytes[66] = {0}, maxlen[66] = {0};
+    for (u64 s = 0; s < count; s++) {
+        const u64 len = off[s + 1] - off[s];
+        int b = 0; for (u64 x = len; x; x >>= 1) b++;          // len < 2^b
+        cnt[b]++; bytes[b] += len; if (len > maxlen[b]) maxlen[b] = len;
+    }
+    // threshold 2^b: segments with len < 2^b walk, the rest are single calls
+    double best = 1e300;
+    int best_b = 65;
+    u64 small_bytes = 0, small_max = 0, calls = count;
+    for (int b = 0; b <= 65; b++) {
+        if (b > 0) { small_bytes += bytes[b]; if (maxlen[b] > small_max) small_max = maxlen[b]; calls -= cnt[b]; }
+        double walk = 0;
+        if (small_bytes) {
+            walk = (double)small_max * SEG_WALK_STEP_US;
+            const double thr = (double)small_bytes / SEG_WALK_STEPS_PER_US;
+            if (thr > walk) walk = thr;
+        }
+        const double cost = walk + (double)calls * SEG_CALL_US;
+        if (cost < best) { best = cost; best_b = b; }
+    }
+    return best_b >= 64 ? ~0ull : 1ull << best_b;
+}
+
+size_t inverse_segments_arena_bytes(u64 n) { return align_up(n * 4, 256) + (1 << 16); }
+
+int inverse_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
+{
+    const std::vector<u64> &off = ctx->seg_off;
+    const u64 count = (u64)off.size() - 1;
+    if (count == 1) return inverse_device_impl(ctx, d_in, n, d_out);
+    // A segment of `big` bytes or more takes the single-input inverse on its own, the others the per-segment walk below.  The walk costs
+    // its longest segment in dependent steps (or its bytes at the walk's throughput, when many chains share the chip); a single call
+    // costs a fixed latency per segment.  `big` is the power of two that minimises the sum of the two (seg_inverse_threshold), so the
+    // call is never much slower than one single-input call per segment.  BWTS_SEG_INV_BIG (test switch) sets it: 1 = every segment alone.
+    u64 big = seg_inverse_threshold(off);
+    if (const char *e = bwts_knob(ctx, "BWTS_SEG_INV_BIG")) { const long long v = atoll(e); if (v >= 1) big = (u64)v; }
+    u64 cycles = 0, small = 0;
+    u32 attempts = 1;
+    u64 unvisited = 0;
+    for (u64 s = 0; s < count; s++) {
+        const u64 len = off[s + 1] - off[s];
+        if (len < big) { small += len; continue; }
+        BWTS_TRY(inverse_device_impl(ctx, d_in + off[s], len, d_out + off[s]));
+        cycles += ctx->tm.factors;
+        unvisited += ctx->tm.unvisited;
+        if (ctx->tm.attempts > attempts) attempts = ctx->tm.attempts;
+    }
+    if (small) {
+        BWTS_TRY(arena_reserve(ctx, inverse_segments_arena_bytes(n)));
+        u32 *LF = arena_array<u32>(ctx, n);
+        if (!LF) return BWTS_E_NOMEM;
+        unsigned long long *d_cyc = (unsigned long long *)(ctx->d_small + SMI_COUNTERS);
+        HIPC(hipMemsetAsync(d_cyc, 0, sizeof(u64), ctx->stream));
+        {
+            SpanGuard sg(ctx, BWTS_K_LF_BUILD, small, 5 * small);
+            seg_lf_kernel<<<dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx->stream>>>(d_in, ctx->d_seg_off, count, big, LF);
+            HIPC(hipGetLastError());
+        }
+        {
+            SpanGuard sg(ctx, BWTS_K_WALK, small, 10 * small);
+            seg_walk_kernel<<<dim3((unsigned)((count + 63) / 64)), dim3(64), 0, ctx->stream>>>(d_in, LF, ctx->d_seg_off, count, big, d_out, d_cyc);
+            HIPC(hipGetLastError());
+        }
+        BWTS_TRY(read_small(ctx, SMI_COUNTERS, 1));
+        cycles += ctx->h_small[SMI_COUNTERS];
+    }
+    ctx->tm.n = n;
+    ctx->tm.factors = cycles;
+    ctx->tm.unvisited = unvisited;
+    ctx->tm.attempts = attempts;
+    return BWTS_OK;
+}

@@ -133,6 +133,19 @@ int bwts_inverse_sink(bwts_ctx *ctx, const uint8_t *in, uint64_t n, bwts_sink_fn
 int bwts_forward_batch(bwts_ctx *ctx, int count, const uint8_t *const *ins, const uint64_t *ns, uint8_t *const *outs);
 int bwts_inverse_batch(bwts_ctx *ctx, int count, const uint8_t *const *ins, const uint64_t *ns, uint8_t *const *outs);
 
+/* Many independent inputs in one device pass: `in` holds count >= 1 consecutive segments of lengths[0..count) bytes (each >= 1, their
+ * sum <= 2^32), and segment s of `out` -- at the same offset, off_s = sum of the earlier lengths -- receives exactly what
+ * bwts_forward / bwts_inverse give for segment s alone.  A block-sorting compressor's blocks or a dataset's files go through one
+ * factorisation, one cyclic sort and one partition (forward) or one LF build and one set of cycle walks (inverse) instead of count
+ * calls.  lengths: host array.  BWTS_E_ARG on NULL pointers, count == 0, a zero length or a sum that overflows; BWTS_E_RANGE on a sum
+ * above 2^32.  The host forms stage like bwts_forward (out may equal in; a failed call leaves out as it was); the device forms refuse
+ * a d_out that overlaps d_in.  bwts_last_timings: n = the sum, factors = Lyndon factors / LF cycles over all segments.  (No reference
+ * counterpart: mk_bwts_sa.c / unbwts.c transform one file.) */
+int bwts_forward_segments(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, uint64_t count, uint8_t *out);
+int bwts_inverse_segments(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, uint64_t count, uint8_t *out);
+int bwts_forward_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out);
+int bwts_inverse_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out);
+
 /* Device-buffer entry points: d_in/d_out are device pointers on the context's
  * GPU (d_out may not alias d_in).  Synchronous: the call returns after the
  * result is complete in d_out. */

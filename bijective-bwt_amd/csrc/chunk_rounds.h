@@ -1647,7 +1647,10 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
             if (CYCLIC && rounds - 1 < BWTS_MAX_ROUND_STATS) ctx->tm.round_active[rounds - 1] = left;
             if (left == 0) { finished = true; continue; }
             // no group split: the partition is stable under doubling -- what is left are groups of equal infinite words
-            if (CYCLIC && r[CHS_SPLIT] == 0) { finished = true; stable = true; continue; }
+            if (CYCLIC && r[CHS_SPLIT] == 0) {
+                if (round_trace) fprintf(stderr, "[chunks] round %u: no group split, %llu elements left in groups of equal infinite words\n", rounds, (unsigned long long)left);
+                finished = true; stable = true; continue;
+            }
             if (!CYCLIC && hs[b] >= n) CH_FAIL("suffixes still tied at h >= n");      // suffixes are distinct; cannot happen
             if (rounds > 80) CH_FAIL("more than 80 rounds");
         }

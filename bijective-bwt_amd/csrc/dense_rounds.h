@@ -801,7 +801,12 @@ static int dense_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
         if (a == 0 && waiting == 0) break;
         // no group split -- the groups still waiting for their activation round provably do not split either -- so the partition is
         // stable under doubling: what is left are groups of equal infinite words
-        if (CYCLIC && splits == 0) { rest_from = by_rounds ? act_start[act_round + 1 < DG_MAX_ACT ? act_round + 1 : DG_MAX_ACT] : a0; break; }
+        if (CYCLIC && splits == 0) {
+            rest_from = by_rounds ? act_start[act_round + 1 < DG_MAX_ACT ? act_round + 1 : DG_MAX_ACT] : a0;
+            if (round_trace) fprintf(stderr, "[rounds] round %u: no group split, %llu elements left in groups of equal infinite words (%llu of them still waiting for their activation round)\n",
+                                     rounds, (unsigned long long)(a + a0 - rest_from), (unsigned long long)(a0 - rest_from));
+            break;
+        }
         if (!CYCLIC && h >= n) return BWTS_E_INTERNAL;  // suffixes are distinct; cannot happen
         if (rounds > 80) return BWTS_E_INTERNAL;
     }

@@ -215,9 +215,8 @@ def test_deep_repeats_vs_oracle(ctx):
     block = rng.integers(97, 101, size=50000, dtype=np.uint8)
     x = np.concatenate([block, block[:40000], rng.integers(97, 101, size=1000, dtype=np.uint8), block[10000:], block])
     y = ctx.forward(x)
-    # (repeats of 50 000 symbols.  The classic rounds need log4(50 000 / 4) + 1 >= 6 of them; with parked chains -- csrc/chunk_rounds.h --
-    # the copies settle as soon as the END of a repeat does, so fewer are enough; several are still needed)
-    assert ctx.timings().rounds >= 3
+    # (repeats of 50 000 symbols.  The rounds need log4(50 000 / 4) + 1 >= 6 of them)
+    assert ctx.timings().rounds >= 6
     assert np.array_equal(y, O.forward(x))
     assert np.array_equal(ctx.inverse(y), x)
 
@@ -294,7 +293,7 @@ def test_dense_ties_large_vs_oracle(ctx):
     x = np.concatenate([block, block, O.generate("zipf", 1000, 6), block[: 1 << 20], block])      # ~7.3 MiB, long repeats
     y = ctx.forward(x)
     t = ctx.timings()
-    assert t.active_after_round0 > len(x) // 32 and t.rounds >= 3      # (classic rounds: >= 6; parked chains settle a repeat when its end settles)
+    assert t.active_after_round0 > len(x) // 32 and t.rounds >= 6
     assert np.array_equal(y, O.forward(x))
     assert np.array_equal(ctx.inverse(y), x)
 
@@ -1108,7 +1107,7 @@ def test_text_16MiB_vs_oracle(ctx):
     x = O.generate("text", n, 1)
     y = ctx.forward(x)
     t = ctx.timings()
-    assert t.active_after_round0 > n // 4 and t.rounds >= 3
+    assert t.active_after_round0 > n // 4 and t.rounds >= 5
     assert hashlib.sha256(y.tobytes()).hexdigest() == hashlib.sha256(O.forward(x).tobytes()).hexdigest()
     assert np.array_equal(ctx.inverse(y), x)
 
@@ -1123,7 +1122,7 @@ def test_real_text_vs_oracle(ctx):
     assert x.size == gold["n"] and hashlib.sha256(x.tobytes()).hexdigest() == gold["sha256_in"]
     y = ctx.forward(x)
     t = ctx.timings()
-    assert t.active_after_round0 > x.size // 2 and t.rounds >= 3
+    assert t.active_after_round0 > x.size // 2 and t.rounds >= 5
     assert hashlib.sha256(y.tobytes()).hexdigest() == gold["sha256_bwts"]
     assert np.array_equal(y, O.forward(x))
     assert np.array_equal(ctx.inverse(y), x)
@@ -1188,11 +1187,9 @@ _ALT_ENVS = [
     {"BWTS_RX_PACK": "0"},                            # round-0 sort on wide (u64, u32, u8) streams instead of packed ones
     {"BWTS_GROUPSCAN": "keys"},                       # round-0 group scan element-wise over the keys instead of flag words
     {"BWTS_RANKBUILD": "plain"},
-    {"BWTS_DENSE": "tiles", "BWTS_DENSE_RUNS": "1"},  # (tile form) activation rounds from the run structure of the position-ordered list (opt-in)
     {"BWTS_DENSE_STEP": "2"},                         # group-local rounds with plain doubling (one successor rank) instead of the quadrupled step
     {"BWTS_DENSE": "tiles"},                          # the tile form of the group-local rounds (round 2) instead of the chunked one
     {"BWTS_RX_SMALL": "0"},                           # small sorts through the multi-launch passes instead of the one-workgroup kernel
-    {"BWTS_RX_CHAIN": "1"},                           # round-0 packed passes with decoupled look-back instead of histogram sweep + column scan (>= 2^22 elements; opt-in: measured slower)
     {"BWTS_RX_FUSED_SCAN": "0"},                      # column scan of the tile table in five launches instead of the fused kernel
     {"BWTS_K0DIR": "0"},                              # sparse key builder: plain binary searches, no directories                      # dense rank array by two plain scatters instead of the binned one
     {"BWTS_INV_MARK": "log"},                         # inverse logs every visited index (the fallback of the per-range moments)
@@ -1200,8 +1197,6 @@ _ALT_ENVS = [
     {"BWTS_BYTEMARK": "1"},                           # inverse marks in a byte map (the n = 2^32 fallback)
     {"BWTS_SPLIT_LOG2": "0"},                         # inverse: every element a splitter (plain pointer jumping)
     {"BWTS_POISON": "1"},                             # every arena / side block filled with 0xA5 before use: nothing may read what nothing wrote
-    {"BWTS_PARK": "1"},                               # later rounds with PARKED CHAINS (csrc/chunk_rounds.h; opt-in: measured slower than the default rounds)
-    {"BWTS_PARK": "1", "BWTS_PARK_STATIC": "1"},      # ... and long repeats parked before the first round from the sorted group records
     {"BWTS_RESERVE_HELPER": "1"},                     # host path: EVERY arena growth through the helper thread (release on the caller with the stream drained, hipMalloc alone on the helper: DESIGN.md section 9)
 ]
 _alt_pool = {}

@@ -590,10 +590,7 @@ print("ok")
 
 SEG_ALT_ENVS = [
     {"BWTS_DENSE": "tiles"},
-    {"BWTS_DENSE": "tiles", "BWTS_DENSE_RUNS": "1"},
     {"BWTS_DENSE_STEP": "2"},
-    {"BWTS_PARK": "1"},
-    {"BWTS_PARK": "1", "BWTS_PARK_STATIC": "1"},
     {"BWTS_VARLEN": "1", "BWTS_KEY_BITS": "24"},
     {"BWTS_VARLEN": "0", "BWTS_KEY_SYMBOLS": "2"},
     {"BWTS_RX_SMALL": "0"},

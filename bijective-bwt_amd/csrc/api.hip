@@ -230,6 +230,13 @@ int aux_reserve_slot(bwts_ctx *ctx, int slot, size_t bytes, char **base)
     return BWTS_OK;
 }
 
+int aux_release(bwts_ctx *ctx)
+{
+    for (int i = 0; i < BWTS_AUX_SLOTS; i++)
+        if (ctx->aux[i]) { HIPC(hipStreamSynchronize(ctx->stream)); HIPC(ctx_free(ctx, ctx->aux[i])); ctx->aux[i] = nullptr; ctx->aux_cap[i] = 0; }
+    return BWTS_OK;
+}
+
 int ensure_dyn_lds(bwts_ctx *ctx, const void *kernel, size_t bytes)
 {
     for (const void *k : ctx->lds_granted) if (k == kernel) return BWTS_OK;

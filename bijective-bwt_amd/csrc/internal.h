@@ -238,6 +238,7 @@ int byte_histogram_device(bwts_ctx *ctx, const u8 *d_T, u64 n, u64 *d_hist256);
 int constant_input_probe(bwts_ctx *ctx, const u8 *d_in, u64 n, bool *constant);   // one byte value repeated?
 int aux_reserve_slot(bwts_ctx *ctx, int slot, size_t bytes, char **base);   // side arenas, sized on demand
 static inline int aux_reserve(bwts_ctx *ctx, size_t bytes, char **base) { return aux_reserve_slot(ctx, 0, bytes, base); }
+int aux_release(bwts_ctx *ctx);      // gives every side arena back (their contents are dead)
 
 // ---- generators / utilities (gen.hip) ------------------------------------------------
 int generate_device_impl(bwts_ctx *ctx, int kind, u64 seed, u64 n, u8 *d_out);

@@ -5,7 +5,13 @@
 // segment by segment (the tile table's offsets are 32-bit), the unreached elements come from per-range moments (a byte map as the fallback), the reduced list
 // (n / 256 nodes) is ranked by plain pointer jumping, and everything sized by node or cycle counts carries 64-bit positions.
 // Memory at n = 12 GiB: LF 96 GiB + recorded segments 58 + nodes ~6 (+ marks 12 on the fallback).
+//
+// Compact form (taken when the full form's memory cannot be reserved, or forced by BWTS_WIDE_INV=compact): LF as packed 40-bit
+// entries (5 n), segment records of one splitter spacing (slot = G) in a node pool sized by its hard bound, and splitters every
+// 2^WC_G_LOG2 elements so that the node tables stay near 0.3 n, and marks as bits over the ranking tables on the fallback: about
+// 7.35 n in all.
 #define WI_G_LOG2 8
+#define WC_G_LOG2 10
 #define WI_NIL 0xffffffffu
 
 __device__ __forceinline__ u32 symbol_of64(const u64 *Ctab, u64 y)
@@ -19,10 +25,28 @@ __device__ __forceinline__ u32 symbol_of64(const u64 *Ctab, u64 y)
     return lo;
 }
 
+// Every reader of LF in the wide form goes through lf_at(): the full form's u64 array, or the compact form's packed 40-bit entries.
+// Entry x of the packed map is the 5 bytes at byte 5x (little endian), read with the two aligned dwords that hold them: one line
+// fill per step as with the u64 array, except for the 1 in 32 entries that cross a 128-byte line.
+// The kernels shared by both forms take the map as `const W *` and tell the two apart by the word type: u64 for the full form, u32
+// (the dwords of the packed map) for the compact one.
+__device__ __forceinline__ u64 lf_at(const u64 *LF, u64 x) { return LF[x]; }
+__device__ __forceinline__ u64 lf_at(const u32 *LF40, u64 x)
+{
+    const u64 b = 5 * x;
+    const u32 *p = LF40 + (b >> 2);
+    const u32 k = (u32)b & 3u, lo = p[0], hi = p[1];
+    return ((u64)((hi >> (8 * k)) & 0xffu) << 32) | __builtin_amdgcn_alignbyte(hi, lo, k);
+}
+// bytes of the packed map: 5 n, a dword of slack for the reader of the last entry, whole 16-byte stores of the builder's last wave
+static inline size_t lf40_bytes(u64 n) { return align_up(5 * n + 16, 256); }
+
 // LF[p0 + i] for one segment: the segment's scanned tile table gives the rank inside the segment (32-bit), base64[c] turns it
 // into the global one: C[c] + occurrences of c in earlier segments - first slot of c in the segment's own table
-__global__ __launch_bounds__(LF_THREADS) void lf_rank_wide_kernel(const u8 *__restrict__ B, u64 count, const u32 *__restrict__ tile_off,
-                                                                  const u64 *__restrict__ base64, u64 *__restrict__ LF)
+// (emit(j, i, entry) receives item j of the lane: element i of the segment, valid where i < count)
+template <typename Emit>
+__device__ __forceinline__ void lf_rank_wide_body(const u8 *__restrict__ B, u64 count, const u32 *__restrict__ tile_off,
+                                                  const u64 *__restrict__ base64, Emit emit)
 {
     __shared__ u32 whist[LF_WAVES][256];
     __shared__ u64 sbase[256];
@@ -61,209 +85,46 @@ __global__ __launch_bounds__(LF_THREADS) void lf_rank_wide_kernel(const u8 *__re
     }
     __syncthreads();
 #pragma unroll
-    for (int j = 0; j < LF_ITEMS; j++) {
-        const u64 i = wave_base + (u64)j * 64 + lane;
-        if (i < count) LF[i] = sbase[sym[j]] + (u64)(whist[w][sym[j]] + rnk[j]);
-    }
+    for (int j = 0; j < LF_ITEMS; j++) emit(j, wave_base + (u64)j * 64 + lane, sbase[sym[j]] + (u64)(whist[w][sym[j]] + rnk[j]));
+}
+__global__ __launch_bounds__(LF_THREADS) void lf_rank_wide_kernel(const u8 *__restrict__ B, u64 count, const u32 *__restrict__ tile_off,
+                                                                  const u64 *__restrict__ base64, u64 *__restrict__ LF)
+{
+    lf_rank_wide_body(B, count, tile_off, base64, [&](int, u64 i, u64 e) { if (i < count) LF[i] = e; });
+}
+// the same into the packed map (LF points at the segment's first entry, 16-byte aligned: segments and waves start at multiples of
+// 4096 and 1024 elements): a wave stages its 1024 entries in LDS and stores them as whole 16-byte words, never 5-byte pieces, so
+// no two lanes write parts of one dword.  Past the segment's end only the slack behind the last entry is written.
+__global__ __launch_bounds__(LF_THREADS) void lf_rank_c40_kernel(const u8 *__restrict__ B, u64 count, const u32 *__restrict__ tile_off,
+                                                                 const u64 *__restrict__ base64, u8 *__restrict__ LF)
+{
+    constexpr u32 wave_bytes = 5 * 64 * LF_ITEMS;
+    __shared__ __attribute__((aligned(16))) u8 stage[LF_WAVES][wave_bytes];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    lf_rank_wide_body(B, count, tile_off, base64, [&](int j, u64 i, u64 e) {
+        if (i >= count) e = 0;
+        u8 *d = &stage[w][5 * (j * 64 + lane)];
+#pragma unroll
+        for (int q = 0; q < 5; q++) d[q] = (u8)(e >> (8 * q));
+    });
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const u64 wave_base = (u64)blockIdx.x * LF_TILE + (u64)w * (64 * LF_ITEMS);
+    if (wave_base >= count) return;
+    const u64 valid = 5 * (count - wave_base);
+    uint4 *dst = (uint4 *)(LF + 5 * wave_base);
+    const uint4 *src = (const uint4 *)stage[w];
+    for (u32 q = lane; q < wave_bytes / 16; q += 64)
+        if ((u64)q * 16 < valid) dst[q] = src[q];
 }
 
 // node record: where the walk went next, how many symbols it recorded, the smallest element it saw and where
 struct WiNode { u32 nxt, len; u64 mn; u32 off, pad; };
 
-// walk_record_kernel of the main path with 64-bit elements and byte-map marks (see there for the scheme)
-// MOM: no byte map; the unreached elements come from per-range moments (inverse.hip, MARK_MOMENTS) over WMOM_BUCKETS ranges kept in
-// dynamic LDS (80 KB: two workgroups per CU) -- the random byte write per step was what held this walk at half the main path's rate
+// MOM (walk_record_*_kernel in wide_lf_kernels.inc): the unreached elements come from per-range moments over WMOM_BUCKETS ranges
 #define WMOM_LOG2 12
 #define WMOM_BUCKETS (1u << WMOM_LOG2)
-template <bool MOM>
-__global__ __launch_bounds__(256) void walk_record_wide_kernel(const u64 *__restrict__ LF, u8 *__restrict__ marks, u64 s, u64 node_cap, u32 slot,
-                                                               const u64 *__restrict__ Cg, u8 *__restrict__ seg, WiNode *__restrict__ nodes,
-                                                               unsigned long long *__restrict__ ticket, unsigned long long *__restrict__ vcount,
-                                                               unsigned long long *__restrict__ overflow, int mom_shift, unsigned long long *__restrict__ mom)
-{
-    __shared__ u64 Ctab[257];
-    extern __shared__ __attribute__((aligned(16))) unsigned long long wmom_sm[];        // MOM: sums, sums of squares, counts
-    unsigned long long *msum = wmom_sm, *msq = wmom_sm + WMOM_BUCKETS;
-    u32 *mcnt = (u32 *)(wmom_sm + 2 * WMOM_BUCKETS);
-    if (MOM) for (u32 b = threadIdx.x; b < WMOM_BUCKETS; b += 256) { mcnt[b] = 0; msum[b] = 0; msq[b] = 0; }
-    for (int i = threadIdx.x; i < 257; i += 256) Ctab[i] = Cg[i];
-    __syncthreads();
-    const u64 gmask = (1ull << WI_G_LOG2) - 1ull;
-    bool have = false, done = false;
-    u64 my = 0, x = 0, mn = 0;
-    u32 len = 0, mnoff = 0;
-    u32 sb[16];                  // 64 recorded symbols, stored as one 64-byte block (see walk_record_kernel)
-#pragma unroll
-    for (int q = 0; q < 16; q++) sb[q] = 0;
-    u64 bnext = 0, bend = 0;
-    bool exhausted = false;
-    for (;;) {
-        const u64 need = __ballot(!have && !done);
-        if (need) {
-            if (bnext == bend && !exhausted) {
-                const int leader = __ffsll((unsigned long long)need) - 1;
-                unsigned long long basev = 0;
-                if (lane_id() == leader) basev = atomicAdd(ticket, (unsigned long long)WALK_BATCH);
-                basev = shfl_t((u64)basev, leader);
-                bnext = basev;
-                bend = basev + WALK_BATCH < s ? basev + WALK_BATCH : s;
-                if (basev >= s) { exhausted = true; bnext = bend = 0; }
-            }
-            if (!have && !done) {
-                const u64 id = bnext + (u64)__popcll(need & lanemask_lt());
-                if (id < bend) {
-                    have = true; my = id; x = my << WI_G_LOG2; len = 0; mn = x; mnoff = 0;
-#pragma unroll
-                    for (int q = 0; q < 16; q++) sb[q] = 0;
-                }
-                else if (exhausted) done = true;
-            }
-            const u64 taken = bnext + (u64)__popcll(need);
-            bnext = taken < bend ? taken : bend;
-        }
-        if (__ballot(have || !done) == 0) break;
-        if (have) {
-            const u64 y = LF[x];
-            if (MOM) {
-                const u32 b = (u32)x & (WMOM_BUCKETS - 1u);                  // residue classes (see inverse.hip, MARK_MOMENTS)
-                const unsigned long long o = x >> WMOM_LOG2;
-                atomicAdd(&mcnt[b], 1u); atomicAdd(&msum[b], o); atomicAdd(&msq[b], o * o);
-            } else marks[x] = 1;
-            {
-                const u32 sh = symbol_of64(Ctab, y) << (8 * (len & 3u));
-                const u32 w = (len >> 2) & 15u;
-#pragma unroll
-                for (int q = 0; q < 16; q++) sb[q] |= w == (u32)q ? sh : 0u;
-            }
-            if ((len & 63u) == 63u) {
-                uint4 *d = (uint4 *)(seg + my * slot + (len & ~63u));
-#pragma unroll
-                for (int q = 0; q < 4; q++) d[q] = make_uint4(sb[4 * q], sb[4 * q + 1], sb[4 * q + 2], sb[4 * q + 3]);
-#pragma unroll
-                for (int q = 0; q < 16; q++) sb[q] = 0;
-            }
-            len++;
-            x = y;
-            const bool at_splitter = (x & gmask) == 0;
-            if (at_splitter || len == slot) {
-                if (len & 63u) {
-                    uint4 *d = (uint4 *)(seg + my * slot + (len & ~63u));
-                    const u32 rem = len & 63u;
-#pragma unroll
-                    for (int q = 0; q < 4; q++) if ((u32)q * 16u < rem) d[q] = make_uint4(sb[4 * q], sb[4 * q + 1], sb[4 * q + 2], sb[4 * q + 3]);
-                }
-                u64 next_node;
-                if (at_splitter) { next_node = x >> WI_G_LOG2; have = false; }
-                else {
-                    next_node = s + atomicAdd(vcount, 1ull);
-                    if (next_node >= node_cap) { atomicAdd(overflow, 1ull); next_node = node_cap - 1; }
-                }
-                WiNode nd; nd.nxt = (u32)next_node; nd.len = len; nd.mn = mn; nd.off = mnoff; nd.pad = 0;
-                nodes[my] = nd;
-                if (!at_splitter) {
-                    my = next_node; len = 0; mn = x; mnoff = 0;
-#pragma unroll
-                    for (int q = 0; q < 16; q++) sb[q] = 0;
-                }
-            } else if (x < mn) { mn = x; mnoff = len; }
-        }
-    }
-    if (MOM) {
-        __syncthreads();                  // every wave leaves the loop (the pool runs dry for all of them)
-        for (u32 b = threadIdx.x; b < WMOM_BUCKETS; b += 256) {
-            const u32 c = mcnt[b];
-            if (c) { atomicAdd(&mom[b], (unsigned long long)c); atomicAdd(&mom[WMOM_BUCKETS + b], msum[b]); atomicAdd(&mom[2 * WMOM_BUCKETS + b], msq[b]); }
-        }
-    }
-}
-
-// moments_solve_kernel / moments_budget_kernel / moments_chase_kernel of the main path (inverse.hip) with 64-bit elements and WMOM_BUCKETS ranges
-__global__ __launch_bounds__(1024) void moments_solve_wide_kernel(const unsigned long long *__restrict__ mom, u64 n, int shift, const u64 *__restrict__ LF,
-                                                                  u64 *__restrict__ uidx, u64 *__restrict__ ulf, u64 ucap, u32 *__restrict__ def_list,
-                                                                  unsigned long long *__restrict__ counters)
-{
-    const u64 b = (u64)blockIdx.x * 1024 + threadIdx.x;
-    if (b >= WMOM_BUCKETS || b >= n) return;
-    const u64 size = (n - b + WMOM_BUCKETS - 1) >> WMOM_LOG2;
-    const u64 cnt = mom[b];
-    if (cnt > size) { atomicAdd(&counters[11], 1ull); return; }
-    const u64 d = size - cnt;
-    if (d == 0) return;
-    const u64 sall = size * (size - 1) / 2;
-    u64 f[3] = {size - 1, size, 2 * size - 1};
-    { int two = 0, three = 0; for (int i = 0; i < 3; i++) { if (!two && f[i] % 2 == 0) { f[i] /= 2; two = 1; } } for (int i = 0; i < 3; i++) { if (!three && f[i] % 3 == 0) { f[i] /= 3; three = 1; } } }
-    const u64 qall = f[0] * f[1] * f[2];                                     // mod 2^64, like the sums of squares it is compared with
-    const u64 A = sall - mom[WMOM_BUCKETS + b], B = qall - mom[2 * WMOM_BUCKETS + b];
-    if (d == 1) {
-        if (A >= size || A * A != B) { atomicAdd(&counters[11], 1ull); return; }
-        const unsigned long long at = atomicAdd(&counters[1], 1ull);
-        if (at < ucap) { const u64 x = (A << WMOM_LOG2) | b; uidx[at] = x; ulf[at] = LF[x]; }
-    } else if (d == 2) {
-        const u64 D = 2 * B - A * A;
-        u64 r = (u64)sqrt((double)D);
-        while (r * r > D) r--;
-        while ((r + 1) * (r + 1) <= D) r++;
-        const u64 o1 = (A - r) / 2, o2 = (A + r) / 2;
-        if (A >= 2 * size || r * r != D || r == 0 || ((A - r) & 1) || o2 >= size || o1 * o1 + o2 * o2 != B) { atomicAdd(&counters[11], 1ull); return; }
-        const unsigned long long at = atomicAdd(&counters[1], 2ull);
-        if (at < ucap) { const u64 x = (o1 << WMOM_LOG2) | b; uidx[at] = x; ulf[at] = LF[x]; }
-        if (at + 1 < ucap) { const u64 x = (o2 << WMOM_LOG2) | b; uidx[at + 1] = x; ulf[at + 1] = LF[x]; }
-    } else {
-        const unsigned long long at = atomicAdd(&counters[10], 1ull);
-        def_list[at] = (u32)b;
-    }
-}
-__global__ __launch_bounds__(256) void moments_chase_wide_kernel(const u32 *__restrict__ def_list, const unsigned long long *__restrict__ counters_in, u64 n, int shift,
-                                                                 const u64 *__restrict__ LF, u32 cap, u64 *__restrict__ uidx, u64 *__restrict__ ulf, u64 ucap,
-                                                                 unsigned long long *__restrict__ counters)
-{
-    const u64 classes = counters_in[10];
-    const u64 members = (n + WMOM_BUCKETS - 1) >> WMOM_LOG2;
-    const u64 per = (members + 255) / 256;
-    const u64 gmask = (1ull << WI_G_LOG2) - 1ull;
-    (void)shift;
-    for (u64 w = blockIdx.x; w < classes * per; w += gridDim.x) {
-        const u64 x0 = (((w % per) * 256 + threadIdx.x) << WMOM_LOG2) | (u64)def_list[w / per];
-        bool un = false;
-        if (x0 < n) {
-            if ((x0 & gmask) != 0) {
-                u64 y = LF[x0];
-                u32 steps = 0;
-                for (;;) {
-                    if (y == x0) { un = true; break; }
-                    if ((y & gmask) == 0) break;
-                    if (++steps > cap) { atomicAdd(&counters[11], 1ull); break; }
-                    y = LF[y];
-                }
-            }
-        }
-        const u64 m = __ballot(un);
-        if (m) {
-            const int leader = __ffsll((unsigned long long)m) - 1;
-            unsigned long long bse = 0;
-            if (lane_id() == leader) bse = atomicAdd(&counters[1], (unsigned long long)__popcll(m));
-            bse = shfl_t((u64)bse, leader);
-            if (un) { const u64 at = bse + (u64)__popcll(m & lanemask_lt()); if (at < ucap) { uidx[at] = x0; ulf[at] = LF[x0]; } }
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void collect_unvisited_wide_kernel(const u64 *__restrict__ LF, const u8 *__restrict__ marks, u64 n,
-                                                                     u64 *__restrict__ uidx, u64 *__restrict__ ulf, u64 cap, unsigned long long *__restrict__ count)
-{
-    for (u64 base = (u64)blockIdx.x * 256; base < n; base += (u64)gridDim.x * 256) {
-        const u64 i = base + threadIdx.x;
-        const bool un = i < n && marks[i] == 0;
-        const u64 m = __ballot(un);
-        if (m) {
-            const int leader = __ffsll((unsigned long long)m) - 1;
-            unsigned long long b = 0;
-            if (lane_id() == leader) b = atomicAdd(count, (unsigned long long)__popcll(m));
-            b = shfl_t((u64)b, leader);
-            if (un) { const u64 at = b + (u64)__popcll(m & lanemask_lt()); if (at < cap) { uidx[at] = i; ulf[at] = LF[i]; } }
-        }
-    }
-}
 
 // pointer jumping over the nodes: records (leader, hop, smallest element) and (sum of lengths, hop)
 struct WiMin { u32 leader, hop; u64 mn; };
@@ -313,9 +174,10 @@ __global__ __launch_bounds__(256) void wi_finish_kernel(u64 s, const WiMin *__re
     }
 }
 // cycles without a splitter (tiny_cycle_scan_kernel of the main path)
-__global__ __launch_bounds__(256) void tiny_cycle_scan_wide_kernel(const u64 *__restrict__ uidx, const u64 *__restrict__ ulf, u64 nu, const u64 *__restrict__ LF,
-                                                                   u32 cap, WiCycle *__restrict__ cyc, unsigned long long *__restrict__ count,
-                                                                   unsigned long long *__restrict__ overflow)
+template <typename W>
+__device__ __forceinline__ void tiny_cycle_scan_wide_body(const u64 *__restrict__ uidx, const u64 *__restrict__ ulf, u64 nu, const W *__restrict__ LF, u32 cap,
+                                                          WiCycle *__restrict__ cyc, unsigned long long *__restrict__ count,
+                                                          unsigned long long *__restrict__ overflow)
 {
     const u64 q = (u64)blockIdx.x * 256 + threadIdx.x;
     bool ismin = false;
@@ -326,7 +188,7 @@ __global__ __launch_bounds__(256) void tiny_cycle_scan_wide_kernel(const u64 *__
         ismin = true;
         while (y != x) {
             if (y < x) { ismin = false; break; }
-            y = LF[y];
+            y = lf_at(LF, y);
             if (++len > cap) { atomicAdd(overflow, 1ull); ismin = false; break; }
         }
     }
@@ -337,6 +199,18 @@ __global__ __launch_bounds__(256) void tiny_cycle_scan_wide_kernel(const u64 *__
     if (lane_id() == leader) b = atomicAdd(count, (unsigned long long)__popcll(m));
     b = shfl_t((u64)b, leader);
     if (ismin) { WiCycle c; c.minelem = x; c.len = len; c.leader = WI_NIL; c.pad = 0; cyc[b + (u64)__popcll(m & lanemask_lt())] = c; }
+}
+__global__ __launch_bounds__(256) void tiny_cycle_scan_wide_kernel(const u64 *__restrict__ uidx, const u64 *__restrict__ ulf, u64 nu, const u64 *__restrict__ LF,
+                                                                   u32 cap, WiCycle *__restrict__ cyc, unsigned long long *__restrict__ count,
+                                                                   unsigned long long *__restrict__ overflow)
+{
+    tiny_cycle_scan_wide_body(uidx, ulf, nu, LF, cap, cyc, count, overflow);
+}
+__global__ __launch_bounds__(256) void tiny_cycle_scan_c40_kernel(const u64 *__restrict__ uidx, const u64 *__restrict__ ulf, u64 nu, const u32 *__restrict__ LF,
+                                                                  u32 cap, WiCycle *__restrict__ cyc, unsigned long long *__restrict__ count,
+                                                                  unsigned long long *__restrict__ overflow)
+{
+    tiny_cycle_scan_wide_body(uidx, ulf, nu, LF, cap, cyc, count, overflow);
 }
 __global__ __launch_bounds__(256) void wi_cycle_keys_kernel(const WiCycle *__restrict__ cyc, u64 m, u64 *__restrict__ keys, u32 *__restrict__ vals)
 {
@@ -402,23 +276,35 @@ __global__ __launch_bounds__(256) void place_segments_wide_kernel(const u8 *__re
         }
     }
 }
-__global__ __launch_bounds__(256) void tiny_place_wide_kernel(const WiCycle *__restrict__ cyc, u64 m, const u64 *__restrict__ end_of_cyc,
-                                                              const u64 *__restrict__ LF, const u64 *__restrict__ Cg, u8 *__restrict__ out)
-{
-    __shared__ u64 Ctab[257];
-    for (int i = threadIdx.x; i < 257; i += 256) Ctab[i] = Cg[i];
-    __syncthreads();
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    const WiCycle c = cyc[i];
-    if (c.leader != WI_NIL) return;
-    u64 x = c.minelem, pos = end_of_cyc[i];
-    for (u64 t = 0; t < c.len; t++) {
-        const u64 y = LF[x];
-        out[pos--] = (u8)symbol_of64(Ctab, y);
-        x = y;
-    }
-}
+// The kernels that read LF, once per form from one source (wide_lf_kernels.inc): the walk, the searches for unreached elements and
+// the placement of cycles without a splitter.  The full form: u64 LF, splitters every 2^WI_G_LOG2 elements, a byte per mark.
+#define WI_KERNEL(name) name##_wide_kernel
+#define WI_LFW u64
+#define WI_GL WI_G_LOG2
+#define WI_MARKW u8
+#define WI_MARK(m, x) m[x] = 1
+#define WI_UNMARKED(m, i) m[i] == 0
+#include "wide_lf_kernels.inc"
+#undef WI_KERNEL
+#undef WI_LFW
+#undef WI_GL
+#undef WI_MARKW
+#undef WI_MARK
+#undef WI_UNMARKED
+// The compact form: packed 40-bit LF (dwords, see lf_at), splitters every 2^WC_G_LOG2 elements, a bit per mark (n / 8 bytes)
+#define WI_KERNEL(name) name##_c40_kernel
+#define WI_LFW u32
+#define WI_GL WC_G_LOG2
+#define WI_MARKW u32
+#define WI_MARK(m, x) atomicOr(&m[x >> 5], 1u << ((u32)x & 31u))
+#define WI_UNMARKED(m, i) ((m[i >> 5] >> ((u32)i & 31u)) & 1u) == 0
+#include "wide_lf_kernels.inc"
+#undef WI_KERNEL
+#undef WI_LFW
+#undef WI_GL
+#undef WI_MARKW
+#undef WI_MARK
+#undef WI_UNMARKED
 
 // ---- cycles without a splitter that are too long for one lane --------------------------------------------------------------
 // (structured inputs: no regular splitter i * 2^WI_G_LOG2 on a cycle of tens of thousands of elements).  Every unreached
@@ -437,6 +323,26 @@ __global__ __launch_bounds__(256) void wi_unit_nodes_kernel(const IDX *__restric
 {
     const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
     if (i < nu) { WiNode nd; nd.nxt = (u32)LF[ulf[i]]; nd.len = 1; nd.mn = uidx[i]; nd.off = 0; nd.pad = 0; nodes[i] = nd; }
+}
+// the same over the packed map.  Neighbouring entries share dwords, so an entry's 5 bytes are replaced by an atomic and + or on
+// each of the two dwords that hold them (bytes k..3 of the first, 0..k of the second, k = 5x mod 4): other lanes' bytes stay as they are.
+__global__ __launch_bounds__(256) void wi_unit_index_c40_kernel(const u64 *__restrict__ uidx, u64 nu, u32 *__restrict__ LF)
+{
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nu) return;
+    const u64 b = 5 * uidx[i];
+    u32 *p = LF + (b >> 2);
+    const u32 k = (u32)b & 3u, lo = (u32)i, hi = (u32)(i >> 32);
+    const u32 m0 = 0xffffffffu << (8 * k), v0 = lo << (8 * k);
+    const u32 m1 = k == 3 ? 0xffffffffu : (1u << (8 * k + 8)) - 1u, v1 = (k == 0 ? hi : __builtin_amdgcn_alignbyte(hi, lo, 4 - k)) & m1;
+    atomicAnd(&p[0], ~m0); atomicOr(&p[0], v0);
+    atomicAnd(&p[1], ~m1); atomicOr(&p[1], v1);
+}
+__global__ __launch_bounds__(256) void wi_unit_nodes_c40_kernel(const u64 *__restrict__ uidx, const u64 *__restrict__ ulf, u64 nu, const u32 *__restrict__ LF,
+                                                                WiNode *__restrict__ nodes)
+{
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i < nu) { WiNode nd; nd.nxt = (u32)lf_at(LF, ulf[i]); nd.len = 1; nd.mn = uidx[i]; nd.off = 0; nd.pad = 0; nodes[i] = nd; }
 }
 __global__ __launch_bounds__(256) void wi_unit_tag_kernel(WiCycle *__restrict__ cyc, u64 m)
 {
@@ -472,39 +378,67 @@ struct ScopedDeviceBlock {
     ~ScopedDeviceBlock() { if (p) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(p); } }
 };
 
-static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool moments, bool *need_marks);
-static int inverse_wide_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
+static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool moments, bool compact, bool *need_marks);
+static int inverse_wide_form(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool compact)
 {
     // unreached elements from per-range moments; the byte map when too many are missing (or BWTS_INV_MARK=bytemap / BWTS_BYTEMARK=1)
     const char *me = bwts_knob(ctx, "BWTS_INV_MARK");
     bool moments = !((me && !strcmp(me, "bytemap")) || bwts_knob(ctx, "BWTS_BYTEMARK"));
     bool need_marks = false;
     if (moments) {
-        BWTS_TRY(inverse_wide_attempt(ctx, d_in, n, d_out, true, &need_marks));
+        BWTS_TRY(inverse_wide_attempt(ctx, d_in, n, d_out, true, compact, &need_marks));
         if (!need_marks) return BWTS_OK;
     }
-    return inverse_wide_attempt(ctx, d_in, n, d_out, false, &need_marks);
+    return inverse_wide_attempt(ctx, d_in, n, d_out, false, compact, &need_marks);
 }
-static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool moments, bool *need_marks)
+static int inverse_wide_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
+{
+    // the full form where its memory can be had (about 13 n: up to ~16 GiB on one MI355X), the compact form (about 7.5 n) beyond;
+    // BWTS_WIDE_INV=full|compact forces one of them (tests)
+    const char *f = bwts_knob(ctx, "BWTS_WIDE_INV");
+    const bool only_full = f && !strcmp(f, "full"), only_compact = f && !strcmp(f, "compact");
+    if (!only_compact) {
+        const int rc = inverse_wide_form(ctx, d_in, n, d_out, false);
+        if (rc != BWTS_E_NOMEM || only_full) return rc;
+        // nothing of the failed attempt is live: its arena and side blocks go back before the compact form reserves its own
+        BWTS_TRY(arena_release(ctx));
+        BWTS_TRY(aux_release(ctx));
+    }
+    return inverse_wide_form(ctx, d_in, n, d_out, true);
+}
+static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool moments, bool compact, bool *need_marks)
 {
     *need_marks = false;
     if (n > (1ull << 36)) return BWTS_E_RANGE;
     const int mom_shift = WMOM_LOG2;
-    const u64 G = 1ull << WI_G_LOG2;
+    const int g_log2 = compact ? WC_G_LOG2 : WI_G_LOG2;
+    const u64 G = 1ull << g_log2;
     const u64 s = (n + G - 1) / G;
-    const u32 slot = (u32)(4 * G);
-    const u64 node_cap = s + s / 8 + 1024;
+    // compact: one splitter spacing per record (BWTS_WIDE_SLOT, a multiple of 64, for tests), and the pool's hard bound -- every
+    // overflow node follows a node that recorded a full slot, and the walk records each element at most once
+    u32 slot = (u32)(4 * G);
+    if (compact) {
+        slot = (u32)G;
+        if (const char *e = bwts_knob(ctx, "BWTS_WIDE_SLOT")) { const long v = atol(e); if (v >= 64 && v <= (1 << 20) && v % 64 == 0) slot = (u32)v; }
+    }
+    const u64 node_cap = compact ? s + (n + slot - 1) / slot + 1024 : s + s / 8 + 1024;
     if (node_cap > 0xfffffff0ull) return BWTS_E_RANGE;
     int seg_log2 = 31;
     if (const char *e = bwts_knob(ctx, "BWTS_WIDE_SEG_LOG2")) { const int v = atoi(e); if (v >= 12 && v <= 31) seg_log2 = v; }
     const u64 segn = 1ull << seg_log2;
     const u64 nseg = (n + segn - 1) / segn;
-    const size_t need = align_up(n * 8, 256) + align_up(n, 256) + align_up(node_cap * slot, 256) + align_up(node_cap * sizeof(WiNode), 256) +
+    const size_t lf_bytes = compact ? lf40_bytes(n) : align_up(n * 8, 256);
+    // marks: bytes in the full form; bits in the compact one, laid over the ranking tables -- the walk sets them and every collection
+    // (a second one where the first ran out of room) reads them before the ranking writes those tables: the fallback needs no more
+    // memory than the moments
+    const size_t mark_bytes = compact ? (n + 31) / 32 * 4 : n;
+    const size_t need = lf_bytes + (compact ? 0 : align_up(mark_bytes, 256)) + align_up(node_cap * slot, 256) + align_up(node_cap * sizeof(WiNode), 256) +
                         2 * align_up(node_cap * sizeof(WiMin), 256) + 2 * align_up(node_cap * sizeof(WiSum), 256) + 6 * align_up(node_cap * 8, 256) +
                         align_up(node_cap * sizeof(WiCycle), 256) + radix_tile_hist_bytes(segn) + scan_temp_bytes(segn) + (1 << 18);
     BWTS_TRY(arena_reserve(ctx, need));
-    u64 *LF = arena_array<u64>(ctx, n);
-    u8 *marks = moments ? (u8 *)arena_alloc(ctx, 256) : arena_array<u8>(ctx, n);
+    u64 *LF = compact ? nullptr : arena_array<u64>(ctx, n);
+    u32 *LF40 = compact ? (u32 *)arena_alloc(ctx, lf_bytes) : nullptr;
+    u8 *marks = moments || compact ? (u8 *)arena_alloc(ctx, 256) : arena_array<u8>(ctx, mark_bytes);
     unsigned long long *mom = (unsigned long long *)arena_array<u64>(ctx, 3 * WMOM_BUCKETS);
     u32 *def_list = arena_array<u32>(ctx, WMOM_BUCKETS);
     if (!mom || !def_list) return BWTS_E_NOMEM;
@@ -515,9 +449,13 @@ static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out,
     u64 *dist = arena_array<u64>(ctx, node_cap), *min_dist = arena_array<u64>(ctx, node_cap), *end_by_leader = arena_array<u64>(ctx, node_cap);
     u64 *opos = arena_array<u64>(ctx, node_cap), *wrap_at = arena_array<u64>(ctx, node_cap), *cyc_len = arena_array<u64>(ctx, node_cap);
     WiCycle *ncyc = arena_array<WiCycle>(ctx, node_cap);
+    if (compact && !moments && ncyc) {
+        if ((size_t)((char *)(ncyc + node_cap) - (char *)wmin[0]) < mark_bytes) return BWTS_E_INTERNAL;
+        marks = (u8 *)wmin[0];
+    }
     u32 *tile_hist = (u32 *)arena_alloc(ctx, radix_tile_hist_bytes(segn));
     void *scan_temp = arena_alloc(ctx, scan_temp_bytes(segn));
-    if (!LF || !marks || !seg || !nodes || !wmin[1] || !wsum[1] || !dist || !min_dist || !end_by_leader || !opos || !wrap_at || !cyc_len || !ncyc ||
+    if (!(LF || LF40) || !marks || !seg || !nodes || !wmin[1] || !wsum[1] || !dist || !min_dist || !end_by_leader || !opos || !wrap_at || !cyc_len || !ncyc ||
         !tile_hist || !scan_temp)
         return BWTS_E_NOMEM;
 
@@ -551,7 +489,8 @@ static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out,
         HIPC(hipMemcpyAsync(dBase, hBase, 256 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
         lf_hist_kernel<<<dim3((unsigned)tiles), dim3(LF_THREADS), 0, ctx->stream>>>(d_in + p0, c, tile_hist);
         BWTS_TRY(radix_column_scan(ctx, tile_hist, tiles, scan_temp));
-        lf_rank_wide_kernel<<<dim3((unsigned)tiles), dim3(LF_THREADS), 0, ctx->stream>>>(d_in + p0, c, tile_hist, dBase, LF + p0);
+        if (compact) lf_rank_c40_kernel<<<dim3((unsigned)tiles), dim3(LF_THREADS), 0, ctx->stream>>>(d_in + p0, c, tile_hist, dBase, (u8 *)LF40 + 5 * p0);
+        else lf_rank_wide_kernel<<<dim3((unsigned)tiles), dim3(LF_THREADS), 0, ctx->stream>>>(d_in + p0, c, tile_hist, dBase, LF + p0);
         HIPC(hipGetLastError());
         HIPC(hipStreamSynchronize(ctx->stream));            // hBase is rewritten by the next segment
     }
@@ -559,22 +498,31 @@ static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out,
     unsigned long long *ticket = (unsigned long long *)(ctx->d_small + SMI_COUNTERS);
     HIPC(hipMemsetAsync(ticket, 0, 16 * sizeof(u64), ctx->stream));
     if (moments) HIPC(hipMemsetAsync(mom, 0, 3 * WMOM_BUCKETS * sizeof(u64), ctx->stream));
-    else HIPC(hipMemsetAsync(marks, 0, n, ctx->stream));
+    else HIPC(hipMemsetAsync(marks, 0, mark_bytes, ctx->stream));
     {
         SpanGuard sg(ctx, BWTS_K_WALK, n, 10 * n);
         const u64 walkers = s < 524288 ? s : 524288;
-        if (moments) {
-            constexpr size_t lds = (size_t)WMOM_BUCKETS * (8 + 8 + 4);
+        constexpr size_t lds = (size_t)WMOM_BUCKETS * (8 + 8 + 4);
+        const unsigned wgs = (unsigned)((walkers + 255) / 256);
+        if (compact && moments) {
+            BWTS_TRY(ensure_dyn_lds(ctx, (const void *)walk_record_c40_kernel<true>, lds));
+            walk_record_c40_kernel<true><<<dim3(wgs), dim3(256), lds, ctx->stream>>>(LF40, (u32 *)marks, s, node_cap, slot, dC, seg, nodes, ticket, ticket + 3,
+                                                                                    ticket + 4, mom_shift, mom);
+        } else if (compact)
+            walk_record_c40_kernel<false><<<dim3(wgs), dim3(256), 0, ctx->stream>>>(LF40, (u32 *)marks, s, node_cap, slot, dC, seg, nodes, ticket, ticket + 3,
+                                                                                   ticket + 4, 0, nullptr);
+        else if (moments) {
             BWTS_TRY(ensure_dyn_lds(ctx, (const void *)walk_record_wide_kernel<true>, lds));
-            walk_record_wide_kernel<true><<<dim3((unsigned)((walkers + 255) / 256)), dim3(256), lds, ctx->stream>>>(LF, marks, s, node_cap, slot, dC, seg, nodes, ticket,
-                                                                                                                 ticket + 3, ticket + 4, mom_shift, mom);
+            walk_record_wide_kernel<true><<<dim3(wgs), dim3(256), lds, ctx->stream>>>(LF, marks, s, node_cap, slot, dC, seg, nodes, ticket,
+                                                                                     ticket + 3, ticket + 4, mom_shift, mom);
         } else
-            walk_record_wide_kernel<false><<<dim3((unsigned)((walkers + 255) / 256)), dim3(256), 0, ctx->stream>>>(LF, marks, s, node_cap, slot, dC, seg, nodes, ticket,
-                                                                                                                ticket + 3, ticket + 4, 0, nullptr);
+            walk_record_wide_kernel<false><<<dim3(wgs), dim3(256), 0, ctx->stream>>>(LF, marks, s, node_cap, slot, dC, seg, nodes, ticket,
+                                                                                    ticket + 3, ticket + 4, 0, nullptr);
         HIPC(hipGetLastError());
     }
     BWTS_TRY(read_small(ctx, SMI_COUNTERS, 16));
-    if (ctx->h_small[SMI_COUNTERS + 4]) return BWTS_E_NOMEM;          // node pool exhausted (adversarial LF): no fallback in the wide form
+    if (ctx->h_small[SMI_COUNTERS + 4])          // node pool exhausted (adversarial LF): the compact form's pool cannot be
+        return compact ? BWTS_E_INTERNAL : BWTS_E_NOMEM;
     const u64 s_all = s + ctx->h_small[SMI_COUNTERS + 3];
 
     // elements in cycles without a splitter
@@ -599,17 +547,34 @@ static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out,
             HIPC(hipMemsetAsync(ticket + 10, 0, 2 * sizeof(u64), ctx->stream));
             const u64 per_class = (n + WMOM_BUCKETS - 1) >> WMOM_LOG2;
             const u64 budget = (8ull << 20) > per_class ? (8ull << 20) : per_class;        // elements the search may look at (at least one class)
-            moments_solve_wide_kernel<<<dim3(WMOM_BUCKETS / 1024), dim3(1024), 0, ctx->stream>>>(mom, n, mom_shift, LF, uidx, ulf, ucap, def_list, ticket);
+            if (compact) moments_solve_c40_kernel<<<dim3(WMOM_BUCKETS / 1024), dim3(1024), 0, ctx->stream>>>(mom, n, mom_shift, LF40, uidx, ulf, ucap, def_list, ticket);
+            else moments_solve_wide_kernel<<<dim3(WMOM_BUCKETS / 1024), dim3(1024), 0, ctx->stream>>>(mom, n, mom_shift, LF, uidx, ulf, ucap, def_list, ticket);
             moments_budget_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(ticket, per_class, budget);
-            moments_chase_wide_kernel<<<dim3(4096), dim3(256), 0, ctx->stream>>>(def_list, ticket, n, mom_shift, LF, 1u << 16, uidx, ulf, ucap, ticket);
+            if (compact) moments_chase_c40_kernel<<<dim3(4096), dim3(256), 0, ctx->stream>>>(def_list, ticket, n, mom_shift, LF40, 1u << 16, uidx, ulf, ucap, ticket);
+            else moments_chase_wide_kernel<<<dim3(4096), dim3(256), 0, ctx->stream>>>(def_list, ticket, n, mom_shift, LF, 1u << 16, uidx, ulf, ucap, ticket);
         } else {
             u64 blocks = (n + 255) / 256; if (blocks > 16384) blocks = 16384;
-            collect_unvisited_wide_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(LF, marks, n, uidx, ulf, ucap, ticket + 1);
+            if (compact) collect_unvisited_c40_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(LF40, (const u32 *)marks, n, uidx, ulf, ucap, ticket + 1);
+            else collect_unvisited_wide_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(LF, marks, n, uidx, ulf, ucap, ticket + 1);
         }
         HIPC(hipGetLastError());
         return BWTS_OK;
     };
     BWTS_TRY(collect());
+    // how many were found, and a second collection into room for all of them, before the ranking tables below are written: the
+    // compact form's mark bits lie over those tables
+    BWTS_TRY(read_small(ctx, SMI_COUNTERS, 16));
+    if (moments && ctx->h_small[SMI_COUNTERS + 11]) { *need_marks = true; return BWTS_OK; }     // too many unreached elements for the moments: the byte map
+    const u64 nu = ctx->h_small[SMI_COUNTERS + 1];
+    if (nu > n) return BWTS_E_INTERNAL;
+    if (nu > ucap) {
+        ucap = nu;
+        BWTS_TRY(lay_out(ucap));
+        HIPC(hipMemsetAsync(ticket + 1, 0, sizeof(u64), ctx->stream));
+        BWTS_TRY(collect());
+        BWTS_TRY(read_small(ctx, SMI_COUNTERS, 16));
+        if (ctx->h_small[SMI_COUNTERS + 1] != nu) return BWTS_E_INTERNAL;
+    }
     // pointer jumping over the nodes
     const int R = [&] { int b = 0; for (u64 x = s_all; x; x >>= 1) b++; return b; }();
     int cur = 0, sc = 0;
@@ -624,24 +589,17 @@ static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out,
         HIPC(hipGetLastError());
     }
     BWTS_TRY(read_small(ctx, SMI_COUNTERS, 16));
-    const u64 nu = ctx->h_small[SMI_COUNTERS + 1];
     const u64 kc = ctx->h_small[SMI_COUNTERS + 2];
-    if (moments && ctx->h_small[SMI_COUNTERS + 11]) { *need_marks = true; return BWTS_OK; }     // too many unreached elements for the moments: the byte map
     ctx->tm.unvisited = nu;
     ctx->unv_hint = (size_t)nu;
-    if (nu > n || kc == 0 || kc > s_all) return BWTS_E_INTERNAL;
-    if (nu > ucap) {
-        ucap = nu;
-        BWTS_TRY(lay_out(ucap));
-        HIPC(hipMemsetAsync(ticket + 1, 0, sizeof(u64), ctx->stream));
-        BWTS_TRY(collect());
-    }
+    if (kc == 0 || kc > s_all) return BWTS_E_INTERNAL;
     if (nu) {
         SpanGuard sg(ctx, BWTS_K_OTHER, nu, 16 * nu);
         u64 cap = (1ull << 36) / nu;
         if (cap > 64 * G) cap = 64 * G;
         if (cap < 4 * G) cap = 4 * G;
-        tiny_cycle_scan_wide_kernel<<<dim3(grid1(nu)), dim3(256), 0, ctx->stream>>>(uidx, ulf, nu, LF, (u32)cap, cyc, ticket + 7, ticket + 4);
+        if (compact) tiny_cycle_scan_c40_kernel<<<dim3(grid1(nu)), dim3(256), 0, ctx->stream>>>(uidx, ulf, nu, LF40, (u32)cap, cyc, ticket + 7, ticket + 4);
+        else tiny_cycle_scan_wide_kernel<<<dim3(grid1(nu)), dim3(256), 0, ctx->stream>>>(uidx, ulf, nu, LF, (u32)cap, cyc, ticket + 7, ticket + 4);
         HIPC(hipGetLastError());
     }
     BWTS_TRY(read_small(ctx, SMI_COUNTERS, 16));
@@ -666,8 +624,13 @@ static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out,
         const int gb = grid1(nu);
         const int R2 = [&] { int b = 0; for (u64 x = nu; x; x >>= 1) b++; return b; }();
         HIPC(hipMemsetAsync(ticket + 9, 0, sizeof(u64), ctx->stream));
-        wi_unit_index_kernel<u64><<<dim3(gb), dim3(256), 0, ctx->stream>>>(uidx, nu, LF);
-        wi_unit_nodes_kernel<u64><<<dim3(gb), dim3(256), 0, ctx->stream>>>(uidx, ulf, nu, LF, unodes);
+        if (compact) {
+            wi_unit_index_c40_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(uidx, nu, LF40);
+            wi_unit_nodes_c40_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(uidx, ulf, nu, LF40, unodes);
+        } else {
+            wi_unit_index_kernel<u64><<<dim3(gb), dim3(256), 0, ctx->stream>>>(uidx, nu, LF);
+            wi_unit_nodes_kernel<u64><<<dim3(gb), dim3(256), 0, ctx->stream>>>(uidx, ulf, nu, LF, unodes);
+        }
         wi_init_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(nu, unodes, umin[0]);
         for (int r = 0; r < R2; r++, ucur ^= 1) wi_jump_min_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(nu, umin[ucur], umin[ucur ^ 1]);
         wi_cut_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(nu, unodes, umin[ucur], usum[0]);
@@ -705,12 +668,15 @@ static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out,
     }
     {
         SpanGuard sg(ctx, BWTS_K_WALK_EMIT, n, 2 * n);
-        const int tpn_log2 = WI_G_LOG2 - 4;
+        // threads per node: 16 (the full form's records loop over 4 G); in the compact form one per 16 bytes of a slot, at most 64
+        int tpn_log2 = WI_G_LOG2 - 4;
+        if (compact) { tpn_log2 = 2; while (tpn_log2 < 6 && (16u << (tpn_log2 + 1)) <= slot) tpn_log2++; }
         const u64 threads = s_all << tpn_log2;
         place_segments_wide_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream>>>(seg, s_all, slot, tpn_log2, nodes, opos, wrap_at, cyc_len,
                                                                                                            d_out);
         if (unit_rank)
             wi_unit_place_kernel<u64><<<dim3(grid1(nu)), dim3(256), 0, ctx->stream>>>(nu, umin[ucur], usum[usc], udist, umind, uend, ulf, dC, d_out);
+        else if (kt && compact) tiny_place_c40_kernel<<<dim3(grid1(kt)), dim3(256), 0, ctx->stream>>>(cyc, kt, end_of_cyc, LF40, dC, d_out);
         else if (kt) tiny_place_wide_kernel<<<dim3(grid1(kt)), dim3(256), 0, ctx->stream>>>(cyc, kt, end_of_cyc, LF, dC, d_out);
         HIPC(hipGetLastError());
     }

@@ -115,7 +115,9 @@ int bwts_inverse(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out);
  * memory for inputs whose positions the first sort separates (plus 4 n for the rank array and 16-33 bytes per position that stays
  * tied when it does not: text with long repeats; plus 3 n when the first sort runs on keys wider than 40 bits).  Inverse: about
  * 11 n, plus ~110 bytes per element that lies in a long LF cycle without a splitter (sorted or periodic data); its cycle walk runs
- * once on natural inputs and at most five times on adversarial ones (bwts_timings.attempts). */
+ * once on natural inputs and at most five times on adversarial ones (bwts_timings.attempts).  Beyond 2^32 (up to 2^36) the inverse
+ * holds about 13 n where that fits the device and at most 7.5 n + 1 GiB otherwise (40-bit LF entries): about 9.5 n with the device
+ * input and output, so dna(24 GiB) round-trips on one MI355X. */
 
 /* Same transforms, the result handed to a callback in consecutive pieces (in order, together n bytes) straight from the
  * pinned staging buffers: a CLI passes an fwrite wrapper and never holds an n-byte output buffer (mk_bwts_sa.c:60,

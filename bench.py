@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: BWTS build MB/s (+ inverse MB/s) on synthetic input, bit-exact round trip.
 
-    python bench.py --gpus N --steps K --warmup W [--workload zipf|uniform256|dna|text] [--log2n L] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload zipf|uniform256|dna|text] [--log2n L] [--dump-outputs DIR] [--full]
 
 A "step" is one forward transform of one input that is already resident in HBM.  N > 1 runs N independent
 replicas (one input per GPU, seed 1+rank; RCCL is only the barrier and the max-over-ranks of the times): either
 under an outer `python -m torch.distributed.run ... bench.py --gpus N`, or -- when WORLD_SIZE is not set --
 bench.py starts those N ranks itself as a child process before anything here touches a GPU.
-Rank 0 prints ONE JSON line.  At N = 1 the line also carries: the text workload beside the headline one, the
-host-buffer path (bwts_forward / bwts_inverse on unpinned caller memory) and the CLI wall time (`e2e`), and the
-CPU baseline.  --dump-outputs DIR writes what the last timed forward step and the last timed inverse step computed (rank 0) as
+Rank 0 prints ONE JSON line.  A plain run does what the headline needs: the warm-up and the K timed forward steps, then the
+timed inverse of their output (the bit-exact round trip `value` stands on), and the figures those timed regions recorded.
+--full adds every leg that runs transforms of its own: the per-kernel-class breakdown; at N = 1 the text workload beside the
+headline one, the host-buffer path (bwts_forward / bwts_inverse on unpinned caller memory) and the CLI wall time (`e2e`), and
+the CPU baseline; at N > 1 the config-5 host-path leg.
+--dump-outputs DIR writes what the last timed forward step and the last timed inverse step computed (rank 0) as
 .npy files: the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
@@ -459,13 +462,17 @@ def main(argv=None):
     ap.add_argument("--workload", default="zipf", choices=["zipf", "uniform256", "dna", "text"])
     ap.add_argument("--log2n", type=int, default=30)
     ap.add_argument("--inverse-steps", type=int, default=2)
-    ap.add_argument("--breakdown-steps", type=int, default=2, help="extra, untimed-for-the-headline steps with every kernel class timed")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: per-kernel breakdown, text workload, host-buffer / CLI path, CPU "
+                         "baseline (N = 1), config-5 host-path leg (N > 1)")
+    ap.add_argument("--breakdown-steps", type=int, default=2, help="with --full: extra, untimed-for-the-headline steps with every kernel class timed")
     ap.add_argument("--cpu-sample-log2n", type=int, default=26)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-buffer / CLI leg")
-    ap.add_argument("--no-text", action="store_true", help="skip the text workload reported beside the headline one")
-    ap.add_argument("--config5-items", type=int, default=4, help="files per GPU in the host-path leg of an N > 1 run (BASELINE config 5); 0 = skip")
-    ap.add_argument("--config5-leg", action="store_true", help="run that leg at N = 1 too")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the host-buffer / CLI leg")
+    ap.add_argument("--no-text", action="store_true", help="with --full: skip the text workload reported beside the headline one")
+    ap.add_argument("--config5-items", type=int, default=4,
+                    help="files per GPU in the host-path leg of an N > 1 --full run (BASELINE config 5); 0 = skip")
+    ap.add_argument("--config5-leg", action="store_true", help="run that leg in this run, whatever N and --full")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the output of the last timed forward step (and of the last timed inverse step) of rank 0 to DIR as .npy "
                          "(float32; above %d bytes a fixed, seeded sample of positions, listed in sample_index.npy)" % DUMP_SAMPLE)
@@ -500,9 +507,11 @@ def main(argv=None):
     n_gpus = world
 
     helper = None
-    if n_gpus == 1 and not selftest and not args.no_e2e:
+    if args.full and n_gpus == 1 and not selftest and not args.no_e2e:
         helper = subprocess.Popen([sys.executable, "-c", _HELPER], stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
 
+    # torch comes before the engine's library even where it only serves as the barrier: the HIP runtime that torch loads is the one the
+    # engine then binds to, so dropping this import would time the steps on another runtime
     import torch
     dev = "cpu" if selftest else "cuda"
     dist = None
@@ -585,13 +594,15 @@ def main(argv=None):
         return {"fwd_s": fwd_s, "inv_s": inv_s, "roundtrip": roundtrip, "fwd_info": fwd_info, "inv_info": inv_info,
                 "main": main_agg, "inv_main": inv_main, "agg": agg, "inv_agg": inv_agg, "outputs": outputs}
 
-    m = measure(args.workload, args.steps, args.warmup, args.inverse_steps, args.breakdown_steps,
+    breakdown_steps = args.breakdown_steps if args.full else 0
+    m = measure(args.workload, args.steps, args.warmup, args.inverse_steps, breakdown_steps,
                 capture=bool(args.dump_outputs) and rank == 0)
     dumped = _dump_outputs(args.dump_outputs, m["outputs"], n) if args.dump_outputs and rank == 0 else None
     m["outputs"] = None
-    # N > 1: the leg that measures config 5's real data flow (files in tmpfs -> bwts_forward_batch -> host buffers), every rank at once
+    # N > 1 with --full: the leg that measures config 5's real data flow (files in tmpfs -> bwts_forward_batch -> host buffers), every
+    # rank at once
     c5_s, c5_info = 0.0, None
-    if (n_gpus > 1 or args.config5_leg) and args.config5_items > 0:
+    if ((args.full and n_gpus > 1) or args.config5_leg) and args.config5_items > 0:
         c5_s, c5_info = _config5_leg(ctx, rank, n, args.config5_items, args.workload, barrier, selftest)
         if not c5_info["first_item_roundtrip_exact"]:
             m["roundtrip"] = False
@@ -632,16 +643,19 @@ def main(argv=None):
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
                          "alg_bytes_per_launch": sc["alg_bytes"] // max(sc["launches"], 1),
                          "ms_per_launch": round(sc["ms"] / max(sc["launches"], 1), 4), "launches": sc["launches"],
-                         "timed": "HIP events on the engine's stream inside the timed region (this class only; the per-class "
-                                  "breakdown under forward.kernels comes from %d separate steps)" % args.breakdown_steps},
+                         "timed": "HIP events on the engine's stream inside the timed region (this class only%s)" % (
+                             "; the per-class breakdown under forward.kernels comes from %d separate steps" % breakdown_steps
+                             if breakdown_steps else "")},
             "forward": {"factors": fwd_info["factors"], "rounds": fwd_info["rounds"], "lyndon_rounds": fwd_info["lyndon_rounds"],
                         "key_symbols": fwd_info["key_symbols"], "key_bits": fwd_info["key_bits"],
                         "active_after_round0": fwd_info["active_after_round0"], "round_active": fwd_info.get("round_active"),
-                        "device_ms": round(fwd_info["total_ms"], 3), "kernels": _per_kernel(m["agg"])},
+                        "device_ms": round(fwd_info["total_ms"], 3)},
             "inverse": {"cycles": inv_info["factors"], "unvisited": inv_info["unvisited"], "device_ms": round(inv_info["total_ms"], 3),
-                        "walk_ms_timed_region": round(m["inv_main"].get("walk", {}).get("ms", 0.0) / max(args.inverse_steps, 1), 3),
-                        "kernels": _per_kernel(m["inv_agg"])},
+                        "walk_ms_timed_region": round(m["inv_main"].get("walk", {}).get("ms", 0.0) / max(args.inverse_steps, 1), 3)},
         }
+        if breakdown_steps:
+            line["forward"]["kernels"] = _per_kernel(m["agg"])
+            line["inverse"]["kernels"] = _per_kernel(m["inv_agg"])
         # second dominant kernel: the inverse's splitter walk -- bound by line fills, not bytes (one 128-byte fill per 4-byte LF read)
         wk = m["inv_main"].get("walk")
         if wk and wk.get("ms", 0) > 0:
@@ -665,7 +679,7 @@ def main(argv=None):
             line["dump_outputs"] = dumped
         if selftest:
             line["data"] = "selftest (no transform executed)"
-        if n_gpus == 1 and not selftest:
+        if args.full and n_gpus == 1 and not selftest:
             if not args.no_e2e:
                 try:
                     line["e2e"] = _e2e(ctx, helper, d_in, d_out, n, args.workload, cli_pre)

@@ -19,7 +19,7 @@ def _launch(nproc, extra, port, gpus=None):
 
 
 def test_world_size_2_gloo():
-    r = _launch(2, ["--steps", "3", "--warmup", "1", "--log2n", "20", "--selftest-sleep-ms", "20", "--inverse-steps", "1"], 29577)
+    r = _launch(2, ["--steps", "3", "--warmup", "1", "--log2n", "20", "--selftest-sleep-ms", "20", "--inverse-steps", "1", "--full"], 29577)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line, from rank 0"
@@ -31,6 +31,7 @@ def test_world_size_2_gloo():
     expect = 2 * (1 << 20) / 1e6 / (j["ms_per_step"] / 1e3)
     assert abs(j["value"] - expect) / expect < 0.01
     assert j["roundtrip_exact"] is True and "cpu_baseline" not in j
+    assert "kernels" in j["forward"] and "kernels" in j["inverse"]       # --full: the per-class breakdown
     # the config-5 leg (files in tmpfs -> batch entry point -> host buffers): 4 items per rank, the slowest rank sleeps 2 x 20 ms per item;
     # aggregate = all ranks' bytes over the max wall time
     c5 = j["config5_host_path"]
@@ -51,6 +52,18 @@ def test_self_launch_without_outer_torchrun():
     assert len(lines) == 1
     j = json.loads(lines[0])
     assert j["n_gpus"] == 2 and j["steps"] == 2 and 30.0 <= j["ms_per_step"] < 70.0
+
+
+def test_plain_run_leaves_the_other_legs_to_full():
+    """Without --full the line carries the headline and what the timed regions recorded: no breakdown, no config-5 leg."""
+    r = _launch(2, ["--steps", "2", "--warmup", "1", "--log2n", "20", "--selftest-sleep-ms", "10", "--inverse-steps", "1"], 29581)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["n_gpus"] == 2 and j["steps"] == 2 and 20.0 <= j["ms_per_step"] < 60.0 and j["roundtrip_exact"] is True
+    assert "config5_host_path" not in j and "kernels" not in j["forward"] and "kernels" not in j["inverse"]
+    assert "e2e" not in j and "text" not in j and "cpu_baseline" not in j
 
 
 def test_gpus_must_match_world_size():

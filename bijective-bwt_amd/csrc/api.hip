@@ -34,7 +34,6 @@ void bwts_trace_error(const char *file, int line, int rc)
 static const char *const kPublicKnobs[] = {"BWTS_TIMINGS", "BWTS_TRACE_ERRORS", "BWTS_ROUND_TRACE", "BWTS_INV_TRACE", "BWTS_BATCH_TRACE",
                                            "BWTS_COPY_THREADS", "BWTS_H2D", "BWTS_D2H", "BWTS_D2H_SPLIT"};
 extern char **environ;
-int radix_config_count(void);
 
 static void read_knobs(bwts_ctx *ctx)
 {
@@ -49,8 +48,6 @@ static void read_knobs(bwts_ctx *ctx)
         for (const char *k : kPublicKnobs) if (name == k) pub = true;
         if (pub || all) ctx->knobs.emplace_back(name, std::string(eq + 1));
     }
-    ctx->rx_config = 0;
-    if (const char *v = bwts_knob(ctx, "BWTS_RX_CONFIG")) { const int c = atoi(v); if (c >= 0 && c < radix_config_count()) ctx->rx_config = c; }
 }
 
 const char *bwts_knob(const bwts_ctx *ctx, const char *name)

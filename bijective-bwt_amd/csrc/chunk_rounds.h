@@ -51,9 +51,8 @@ static_assert(16 + CH_SLOTS * CH_SLOT_WORDS <= DG_CNT_BIG + DG_CNT_SPREAD, "resu
 
 // WIDE chunks -- those that hold a group of more than CH_CAP members (up to CH_GROUP_MAX: what leaves the big list) -- are handled by a
 // second instantiation of the kernel, which orders every tile with one segmented bitonic sort of the whole workgroup over
-// (group's first slot, rank at h[, ranks at 2h and 3h], slot) instead of counting inside each group: N slots (a power of two >= the
+// (group's first slot, rank at h, ranks at 2h and 3h, slot) instead of counting inside each group: N slots (a power of two >= the
 // tile), the slots behind the tile sort behind it.  pay = group's first slot << 16 | slot.
-template <int NKEYS>
 __device__ __forceinline__ void chunk_bitonic_sort(u32 *key, u64 *key23, u32 *pay, u32 N, int tid)
 {
     for (u32 k = 2; k <= N; k <<= 1)
@@ -63,14 +62,9 @@ __device__ __forceinline__ void chunk_bitonic_sort(u32 *key, u64 *key23, u32 *pa
                 const bool asc = (i & k) == 0;
                 const u32 ka = key[i], kb = key[l], pa = pay[i], pb = pay[l];
                 const u32 ga = pa >> 16, gb = pb >> 16;
-                bool gt;
-                if (NKEYS == 3) {
-                    const u64 xa = key23[NKEYS == 3 ? i : 0], xb = key23[NKEYS == 3 ? l : 0];
-                    gt = ga != gb ? ga > gb : ka != kb ? ka > kb : xa != xb ? xa > xb : pa > pb;
-                    if (gt == asc) { key23[NKEYS == 3 ? i : 0] = xb; key23[NKEYS == 3 ? l : 0] = xa; }
-                } else {
-                    gt = ga != gb ? ga > gb : ka != kb ? ka > kb : pa > pb;
-                }
+                const u64 xa = key23[i], xb = key23[l];
+                const bool gt = ga != gb ? ga > gb : ka != kb ? ka > kb : xa != xb ? xa > xb : pa > pb;
+                if (gt == asc) { key23[i] = xb; key23[l] = xa; }
                 if (gt == asc) { key[i] = kb; key[l] = ka; pay[i] = pb; pay[l] = pa; }
             }
             // a stage with j <= 64 stays inside blocks of 128 slots, and pair q belongs to block q / 64: wave w only ever touches blocks
@@ -97,9 +91,10 @@ __global__ __launch_bounds__(CH_THREADS, WIDE ? 4 : CH_MIN_WAVES) void chunk_rou
                                                                  const u32 *__restrict__ fstart, u64 k,
                                                                  PrevSym prev, u8 *__restrict__ out, unsigned long long *__restrict__ result)
 {
+    static_assert(NKEYS == 3, "the step is always quadrupled; NKEYS stays so the kernel keeps the symbol its PMC records name");
     __shared__ u32 hd[CH_TILE];              // group heads of the tile
     __shared__ u32 key[CH_TILE];             // successor ranks
-    __shared__ u64 key23[NKEYS == 3 ? CH_TILE : 1];
+    __shared__ u64 key23[CH_TILE];           // ... and the ranks two and three steps on
     __shared__ u64 startm[CH_WORDS];         // bit = a group starts at this slot
     __shared__ u64 keepm[CH_WORDS];          // bit = the element sorted into this slot stays tied
     __shared__ u32 kpre[CH_WORDS];
@@ -124,8 +119,8 @@ __global__ __launch_bounds__(CH_THREADS, WIDE ? 4 : CH_MIN_WAVES) void chunk_rou
     if (FSL) {
         for (u32 f = tid0; f < k32; f += CH_THREADS) {
             const u64 s0 = fstart[f], L = (f + 1 < k32 ? (u64)fstart[f + 1] : n) - s0;
-            ftab[f] = make_uint4((u32)s0, (u32)L, (u32)(h < L ? h : h % L), NKEYS == 3 ? (u32)(2 * h < L ? 2 * h : (2 * h) % L) : 0u);
-            fhm3[f] = NKEYS == 3 ? (u32)(3 * h < L ? 3 * h : (3 * h) % L) : 0u;
+            ftab[f] = make_uint4((u32)s0, (u32)L, (u32)(h < L ? h : h % L), (u32)(2 * h < L ? 2 * h : (2 * h) % L));
+            fhm3[f] = (u32)(3 * h < L ? 3 * h : (3 * h) % L);
         }
         { int bl = 0; for (u64 x = n - 1; x; x >>= 1) bl++; dsh = bl > 8 ? bl - 8 : 0; }
         if (tid0 < 256) {
@@ -136,7 +131,7 @@ __global__ __launch_bounds__(CH_THREADS, WIDE ? 4 : CH_MIN_WAVES) void chunk_rou
         }
     } else if (!CYCLIC) {
         nh1 = h < n ? (u32)(n - h) : 0u;            // (h >= 1, so n - h fits)
-        if (NKEYS == 3) { nh2 = 2 * h < n ? (u32)(n - 2 * h) : 0u; nh3 = 3 * h < n ? (u32)(n - 3 * h) : 0u; }
+        nh2 = 2 * h < n ? (u32)(n - 2 * h) : 0u; nh3 = 3 * h < n ? (u32)(n - 3 * h) : 0u;
     }
     u32 rp = 0, wp = 0;                      // read / write cursors inside the chunk (uniform)
 #ifdef CH_PROFILE
@@ -171,16 +166,16 @@ __global__ __launch_bounds__(CH_THREADS, WIDE ? 4 : CH_MIN_WAVES) void chunk_rou
         // (Round 4 tried all twelve gathers of a lane in one straight run of loads -- the compiler drains them item by item, three in
         // flight, because the next item's factor search stands between: 8 % SLOWER, five more spilled registers and no shorter waits.)
         u32 my_key[CH_ITEMS];
-        u64 my_key23[NKEYS == 3 ? CH_ITEMS : 1];
+        u64 my_key23[CH_ITEMS];
         u32 ppos[CH_ITEMS];                      // position of the previous symbol, T[cprev(p)] (mk_bwts_sa.c:172-188), while the factor is at hand
 #pragma unroll
         for (int j = 0; j < CH_ITEMS; j++) {
             my_key[j] = 0; ppos[j] = 0;
-            if (NKEYS == 3) my_key23[NKEYS == 3 ? j : 0] = 0;
+            my_key23[j] = 0;
             if ((u32)j * CH_THREADS + tid >= len) continue;
             const u32 p = myp[j];
             if (CYCLIC) {
-                u32 q1, q2 = 0, q3 = 0;
+                u32 q1, q2, q3;
                 if (FSL) {
                     // offset in the factor + step, minus the factor's length when the sum passes it (a carry out of 32 bits passes
                     // it too; a length of 2^32 is kept as 0: the subtraction then does nothing and the wrapped sum is already right)
@@ -192,27 +187,24 @@ __global__ __launch_bounds__(CH_THREADS, WIDE ? 4 : CH_MIN_WAVES) void chunk_rou
                     u32 o = dd + ft.z;
                     o = (o < dd || o >= L) ? o - L : o;
                     q1 = s0 + o;
-                    if (NKEYS == 3) {
-                        u32 o2 = dd + ft.w, o3 = dd + fhm3[f];
-                        o2 = (o2 < dd || o2 >= L) ? o2 - L : o2;
-                        o3 = (o3 < dd || o3 >= L) ? o3 - L : o3;
-                        q2 = s0 + o2; q3 = s0 + o3;
-                    }
+                    u32 o2 = dd + ft.w, o3 = dd + fhm3[f];
+                    o2 = (o2 < dd || o2 >= L) ? o2 - L : o2;
+                    o3 = (o3 < dd || o3 >= L) ? o3 - L : o3;
+                    q2 = s0 + o2; q3 = s0 + o3;
                 } else {
                     const u64 f = factor_of(fstart, k, (u64)p);
                     const u64 s0 = fstart[f], e1 = factor_end(fstart, k, n, f);
                     ppos[j] = p == s0 ? (u32)(e1 - 1) : p - 1u;
                     q1 = (u32)cyclic_successor(p, s0, e1 - s0, h);
-                    if (NKEYS == 3) { q2 = (u32)cyclic_successor(p, s0, e1 - s0, 2 * h); q3 = (u32)cyclic_successor(p, s0, e1 - s0, 3 * h); }
+                    q2 = (u32)cyclic_successor(p, s0, e1 - s0, 2 * h); q3 = (u32)cyclic_successor(p, s0, e1 - s0, 3 * h);
                 }
                 my_key[j] = rank[q1];
-                if (NKEYS == 3) { const u32 r2 = rank[q2], r3 = rank[q3]; my_key23[NKEYS == 3 ? j : 0] = ((u64)r2 << 32) | r3; }
+                const u32 r2 = rank[q2], r3 = rank[q3];
+                my_key23[j] = ((u64)r2 << 32) | r3;
             } else {
                 my_key[j] = p < nh1 ? rank[p + h32] + 1u : 0u;
-                if (NKEYS == 3) {
-                    const u32 r2 = p < nh2 ? rank[p + 2u * h32] + 1u : 0u, r3 = p < nh3 ? rank[p + 3u * h32] + 1u : 0u;
-                    my_key23[NKEYS == 3 ? j : 0] = ((u64)r2 << 32) | r3;
-                }
+                const u32 r2 = p < nh2 ? rank[p + 2u * h32] + 1u : 0u, r3 = p < nh3 ? rank[p + 3u * h32] + 1u : 0u;
+                my_key23[j] = ((u64)r2 << 32) | r3;
             }
         }
         // group starts: the 64 slots of a wave's item j are exactly word j * 8 + wave of the tile
@@ -267,12 +259,12 @@ __global__ __launch_bounds__(CH_THREADS, WIDE ? 4 : CH_MIN_WAVES) void chunk_rou
                 if (sl < N) {
                     const bool real = sl < plen;
                     key[sl] = real ? my_key[j] : 0xffffffffu;
-                    if (NKEYS == 3) key23[NKEYS == 3 ? sl : 0] = real ? my_key23[NKEYS == 3 ? j : 0] : ~0ull;
+                    key23[sl] = real ? my_key23[j] : ~0ull;
                     hd[sl] = ((real ? gsl[j] : 0xffffu) << 16) | sl;
                 }
             }
             __syncthreads();
-            chunk_bitonic_sort<NKEYS>(key, key23, hd, N, tid);
+            chunk_bitonic_sort(key, key23, hd, N, tid);
             // sorted slot t of this thread: whose element, which group, does a run of equal keys start / end here?
             bool rstart[CH_ITEMS], rend[CH_ITEMS];
             u32 src[CH_ITEMS], gst[CH_ITEMS];
@@ -283,10 +275,10 @@ __global__ __launch_bounds__(CH_THREADS, WIDE ? 4 : CH_MIN_WAVES) void chunk_rou
                 rstart[j] = true; rend[j] = true; src[j] = 0; gst[j] = 0;
                 if (t < plen) {
                     const u32 pt = hd[t], kt = key[t];
-                    const u64 xt = NKEYS == 3 ? key23[NKEYS == 3 ? t : 0] : 0ull;
+                    const u64 xt = key23[t];
                     gst[j] = pt >> 16; src[j] = pt & 0xffffu;
-                    if (t > gst[j]) rstart[j] = key[t - 1] != kt || (NKEYS == 3 && key23[NKEYS == 3 ? t - 1 : 0] != xt);
-                    if (t + 1 < plen && (hd[t + 1] >> 16) == gst[j]) rend[j] = key[t + 1] != kt || (NKEYS == 3 && key23[NKEYS == 3 ? t + 1 : 0] != xt);
+                    if (t > gst[j]) rstart[j] = key[t - 1] != kt || key23[t - 1] != xt;
+                    if (t + 1 < plen && (hd[t + 1] >> 16) == gst[j]) rend[j] = key[t + 1] != kt || key23[t + 1] != xt;
                 }
                 rsm[j] = __ballot(rstart[j]);
             }
@@ -383,7 +375,7 @@ __global__ __launch_bounds__(CH_THREADS, WIDE ? 4 : CH_MIN_WAVES) void chunk_rou
         for (int j = 0; j < CH_ITEMS; j++)
             if (act[j]) {
                 key[j * CH_THREADS + tid] = my_key[j];
-                if (NKEYS == 3) key23[NKEYS == 3 ? j * CH_THREADS + tid : 0] = my_key23[NKEYS == 3 ? j : 0];
+                key23[j * CH_THREADS + tid] = my_key23[j];
             }
         __syncthreads();
         CH_MARK(2);
@@ -395,36 +387,27 @@ __global__ __launch_bounds__(CH_THREADS, WIDE ? 4 : CH_MIN_WAVES) void chunk_rou
             if (!act[j]) continue;
             const u32 g0 = gs[j], gsz = sz[j], mine = key[sl];
             u32 less = 0, eq = 0, eq_before = 0;
-            if (NKEYS == 3) {
-                const u64 mine23 = key23[NKEYS == 3 ? sl : 0];
-                u32 m = 0;
-                for (; m + 4 <= gsz; m += 4) {
-                    u32 ko[4]; u64 ko23[4];
+            const u64 mine23 = key23[sl];
+            u32 m = 0;
+            for (; m + 4 <= gsz; m += 4) {
+                u32 ko[4]; u64 ko23[4];
 #pragma unroll
-                    for (int q = 0; q < 4; q++) { ko[q] = key[g0 + m + q]; ko23[q] = key23[NKEYS == 3 ? g0 + m + q : 0]; }
+                for (int q = 0; q < 4; q++) { ko[q] = key[g0 + m + q]; ko23[q] = key23[g0 + m + q]; }
 #pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const bool same = ko[q] == mine && ko23[q] == mine23;
-                        less += (ko[q] < mine || (ko[q] == mine && ko23[q] < mine23)) ? 1u : 0u;
-                        eq += same ? 1u : 0u;
-                        eq_before += (same && g0 + m + q < sl) ? 1u : 0u;
-                    }
-                }
-                for (; m < gsz; m++) {
-                    const u32 ko = key[g0 + m];
-                    const u64 ko23 = key23[NKEYS == 3 ? g0 + m : 0];
-                    const bool same = ko == mine && ko23 == mine23;
-                    less += (ko < mine || (ko == mine && ko23 < mine23)) ? 1u : 0u;
+                for (int q = 0; q < 4; q++) {
+                    const bool same = ko[q] == mine && ko23[q] == mine23;
+                    less += (ko[q] < mine || (ko[q] == mine && ko23[q] < mine23)) ? 1u : 0u;
                     eq += same ? 1u : 0u;
-                    eq_before += (same && g0 + m < sl) ? 1u : 0u;
+                    eq_before += (same && g0 + m + q < sl) ? 1u : 0u;
                 }
-            } else {
-                for (u32 m = 0; m < gsz; m++) {
-                    const u32 ko = key[g0 + m];
-                    less += ko < mine ? 1u : 0u;
-                    eq += ko == mine ? 1u : 0u;
-                    eq_before += (ko == mine && g0 + m < sl) ? 1u : 0u;
-                }
+            }
+            for (; m < gsz; m++) {
+                const u32 ko = key[g0 + m];
+                const u64 ko23 = key23[g0 + m];
+                const bool same = ko == mine && ko23 == mine23;
+                less += (ko < mine || (ko == mine && ko23 < mine23)) ? 1u : 0u;
+                eq += same ? 1u : 0u;
+                eq_before += (same && g0 + m < sl) ? 1u : 0u;
             }
             dst[j] = g0 + less + eq_before;
             newhead[j] = myh[j] + less;
@@ -781,30 +764,29 @@ template <bool CYCLIC>
 struct BlOut {
     const u32 *head; const u32 *idx; int rb; const u32 *rank; u64 n; u64 h; const u32 *fstart; u64 k;
     u64 *bk; u32 *bv;
-    u64 *k23, *k23_sort; u32 *j_sort;        // quadrupled step (null otherwise): see DgBigOut
+    u64 *k23, *k23_sort; u32 *j_sort;        // see DgBigOut
     __device__ __forceinline__ void operator()(u64 j, u32 before) const
     {
         const u32 st = (j == 0 || head[j] != head[j - 1]) ? 1u : 0u;
         const u64 ord = (u64)before + st - 1;
         const u64 p = idx[j];
-        u64 r1, r2 = 0, r3 = 0;
+        u64 r1, r2, r3;
         if (CYCLIC) {
             const u64 f = factor_of(fstart, k, p);
             const u64 s0 = fstart[f], L = factor_end(fstart, k, n, f) - s0;
             r1 = rank[cyclic_successor(p, s0, L, h)];
-            if (k23) { r2 = rank[cyclic_successor(p, s0, L, 2 * h)]; r3 = rank[cyclic_successor(p, s0, L, 3 * h)]; }
+            r2 = rank[cyclic_successor(p, s0, L, 2 * h)]; r3 = rank[cyclic_successor(p, s0, L, 3 * h)];
         } else {
             const u64 q = p + h;
             r1 = q < n ? (u64)rank[q] + 1ull : 0ull;
-            if (k23) {
-                const u64 q2 = p + 2 * h, q3 = p + 3 * h;
-                r2 = q2 < n ? (u64)rank[q2] + 1ull : 0ull;
-                r3 = q3 < n ? (u64)rank[q3] + 1ull : 0ull;
-            }
+            const u64 q2 = p + 2 * h, q3 = p + 3 * h;
+            r2 = q2 < n ? (u64)rank[q2] + 1ull : 0ull;
+            r3 = q3 < n ? (u64)rank[q3] + 1ull : 0ull;
         }
         bk[j] = (ord << rb) | r1;
         bv[j] = (u32)p;
-        if (k23) { const u64 v = (r2 << rb) | r3; k23[j] = v; k23_sort[j] = v; j_sort[j] = (u32)j; }
+        const u64 v = (r2 << rb) | r3;
+        k23[j] = v; k23_sort[j] = v; j_sort[j] = (u32)j;
     }
 };
 // after the sorts, in sorted order.  bl_flags_kernel looks at every element and its predecessor once -- first of its group (the ordinal
@@ -819,11 +801,11 @@ __global__ __launch_bounds__(256) void bl_flags_kernel(const u64 *__restrict__ b
     const u64 j = (u64)blockIdx.x * 256 + threadIdx.x;
     const bool valid = j < m;
     const u64 key = valid ? bk[j] : 0ull;
-    const u32 s = valid ? (src ? src[j] : (u32)j) : 0u;
-    const u64 q = (valid && k23) ? k23[s] : 0ull;
+    const u32 s = valid ? src[j] : 0u;
+    const u64 q = valid ? k23[s] : 0ull;
     if (valid) t_idx[j] = bv[s];
     u64 kprev = shfl_up_t(key, 1), qprev = shfl_up_t(q, 1);
-    if (lane_id() == 0 && valid && j > 0) { kprev = bk[j - 1]; qprev = k23 ? k23[src ? src[j - 1] : (u32)(j - 1)] : 0ull; }
+    if (lane_id() == 0 && valid && j > 0) { kprev = bk[j - 1]; qprev = k23[src[j - 1]]; }
     if (!valid) return;
     const bool gstart = j == 0 || (kprev >> rb) != (key >> rb);
     const bool sstart = gstart || kprev != key || qprev != q;
@@ -914,7 +896,7 @@ __global__ void bl_diag_flag_kernel(const u64 *__restrict__ bk0, const u64 *__re
     const u64 a = bk0[j], b = bk0[j - 1];
     if ((a >> rb) != (b >> rb)) return;
     if (a != b) f1[a >> rb] = 1;
-    if (k23 && k23[j] != k23[j - 1]) f23[a >> rb] = 1;
+    if (k23[j] != k23[j - 1]) f23[a >> rb] = 1;
 }
 __global__ void bl_diag_count_kernel(const u64 *__restrict__ bk0, u64 m, int rb, const u8 *__restrict__ f1, const u8 *__restrict__ f23, unsigned long long *cnt)
 {
@@ -1075,8 +1057,6 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
 
     // ---- big list buffers (the order sort's block, free again) ----
     const size_t m4 = align_up((size_t)m_big * 4, 256), m8 = align_up((size_t)m_big * 8, 256);
-    const bool step4_ok = [ctx] { const char *e = bwts_knob(ctx, "BWTS_DENSE_STEP"); return !(e && atoi(e) == 2); }();
-    const int nk = step4_ok ? 3 : 1;
     u32 *bl_idx[2] = {nullptr, nullptr}, *bl_head[2] = {nullptr, nullptr}, *t_idx = nullptr, *t_head = nullptr, *bv[2] = {nullptr, nullptr}, *sv1 = nullptr;
     u64 *bk[2] = {nullptr, nullptr}, *k23 = nullptr, *sk1 = nullptr;
     u8 *bflags = nullptr;
@@ -1151,7 +1131,6 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
     }
 
     u64 h = (u64)al.hstep;
-    const int hshift = nk == 3 ? 2 : 1;
     bool finished = false, stable = false;
     while (!finished) {
 #ifdef CH_PROFILE
@@ -1167,15 +1146,13 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
             if (round_trace && nchunks) chunk_diag_sizes(ctx, st_head, cstart, ccount, nchunks, rounds + 1);
             if (nchunks) {
                 SpanGuard g(ctx, BWTS_K_ROUND, 0, 0);          // (elements and bytes are added below, once the round's true size is known)
-#define CH_LAUNCH(NK, FS, WD) chunk_round_kernel<CYCLIC, NK, FS, WD><<<dim3(nchunks), dim3(CH_THREADS), 0, ctx->stream>>>(st_idx, st_head, cstart, ccount, cwide, mv, mvcount, \
+#define CH_LAUNCH(FS, WD) chunk_round_kernel<CYCLIC, 3, FS, WD><<<dim3(nchunks), dim3(CH_THREADS), 0, ctx->stream>>>(st_idx, st_head, cstart, ccount, cwide, mv, mvcount, \
                                                                                                   sp.rank, n, h, d_fstart, k, prev, out, res)
                 const bool fsl = CYCLIC && k <= CH_FS;
-                if (nk == 3) { if (fsl) CH_LAUNCH(3, CYCLIC, false); else CH_LAUNCH(3, false, false); }
-                else { if (fsl) CH_LAUNCH(1, CYCLIC, false); else CH_LAUNCH(1, false, false); }
+                if (fsl) CH_LAUNCH(CYCLIC, false); else CH_LAUNCH(false, false);
                 if (wide_possible) {
                     // (behind the other one: a chunk whose last large group has just split is taken over in the NEXT round)
-                    if (nk == 3) { if (fsl) CH_LAUNCH(3, CYCLIC, true); else CH_LAUNCH(3, false, true); }
-                    else { if (fsl) CH_LAUNCH(1, CYCLIC, true); else CH_LAUNCH(1, false, true); }
+                    if (fsl) CH_LAUNCH(CYCLIC, true); else CH_LAUNCH(false, true);
                 }
 #undef CH_LAUNCH
                 CH_HIP(hipGetLastError());
@@ -1184,8 +1161,7 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
                 // the big list's gathers read the same version of the ranks as the chunks': before the moves are applied
                 SpanGuard g(ctx, BWTS_K_RERANK, m_big, 30 * m_big);
                 BlIn fin{bl_head[blc]};
-                BlOut<CYCLIC> fout{bl_head[blc], bl_idx[blc], rb, sp.rank, n, h, d_fstart, k, bk[0], bv[0],
-                                   nk == 3 ? k23 : nullptr, nk == 3 ? bk[1] : nullptr, nk == 3 ? bv[1] : nullptr};
+                BlOut<CYCLIC> fout{bl_head[blc], bl_idx[blc], rb, sp.rank, n, h, d_fstart, k, bk[0], bv[0], k23, bk[1], bv[1]};
                 CH_TRY((device_scan<false, u32>(ctx, m_big, fin, fout, OpAdd(), 0u, sp.scan_temp)));
                 if (round_trace) {
                     const u64 gcap = m_big / (CH_GROUP_MAX + 1) + 2;
@@ -1194,7 +1170,7 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
                         (void)hipMemsetAsync(df, 0, 2 * gcap + 32, ctx->stream);
                         unsigned long long *dc = (unsigned long long *)(df + ((2 * gcap + 7) & ~7ull));
                         const unsigned gb = (unsigned)((m_big + 255) / 256);
-                        bl_diag_flag_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(bk[0], nk == 3 ? k23 : nullptr, m_big, rb, df, df + gcap);
+                        bl_diag_flag_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(bk[0], k23, m_big, rb, df, df + gcap);
                         bl_diag_count_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(bk[0], m_big, rb, df, df + gcap, dc);
                         (void)hipMemcpyAsync(hc, dc, sizeof(hc), hipMemcpyDeviceToHost, ctx->stream);
                         (void)hipStreamSynchronize(ctx->stream);
@@ -1216,33 +1192,23 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
                 SortPlan bp;
                 bp.tile_hist = sp.tile_hist; bp.scan_temp = sp.scan_temp;
                 int rbig = 0;
-                const u64 *sorted_k1 = nullptr;
-                const u32 *src = nullptr, *positions = nullptr;
-                if (nk == 3) {
-                    // LSD over two key words: stable sort by (rank at 2h, rank at 3h), then by (group ordinal, rank at h)
-                    bp.keys[0] = bk[1]; bp.keys[1] = sk1;
-                    bp.vals[0] = bv[1]; bp.vals[1] = sv1;
-                    int r1 = 0;
-                    CH_TRY(radix_sort_pairs(ctx, bp, m_big, 2 * rb, &r1));
-                    u64 *kin = bp.keys[r1], *kout = bp.keys[r1 ^ 1];
-                    u32 *vin = bp.vals[r1], *vout = bp.vals[r1 ^ 1];
-                    {
-                        SpanGuard g(ctx, BWTS_K_RERANK, m_big, 20 * m_big);
-                        dg_stage2_keys_kernel<<<dim3((unsigned)((m_big + 255) / 256)), dim3(256), 0, ctx->stream>>>(vin, bk[0], m_big, kin);
-                        CH_HIP(hipGetLastError());
-                    }
-                    bp.keys[0] = kin; bp.keys[1] = kout;
-                    bp.vals[0] = vin; bp.vals[1] = vout;
-                    CH_TRY(radix_sort_pairs(ctx, bp, m_big, big_bits, &rbig));
-                    sorted_k1 = bp.keys[rbig]; src = bp.vals[rbig]; positions = bv[0];
-                } else {
-                    bp.keys[0] = bk[0]; bp.keys[1] = bk[1];
-                    bp.vals[0] = bv[0]; bp.vals[1] = bv[1];
-                    CH_TRY(radix_sort_pairs(ctx, bp, m_big, big_bits, &rbig));
-                    sorted_k1 = bk[rbig]; positions = bv[rbig];
+                // LSD over two key words: stable sort by (rank at 2h, rank at 3h), then by (group ordinal, rank at h)
+                bp.keys[0] = bk[1]; bp.keys[1] = sk1;
+                bp.vals[0] = bv[1]; bp.vals[1] = sv1;
+                int r1 = 0;
+                CH_TRY(radix_sort_pairs(ctx, bp, m_big, 2 * rb, &r1));
+                u64 *kin = bp.keys[r1], *kout = bp.keys[r1 ^ 1];
+                u32 *vin = bp.vals[r1], *vout = bp.vals[r1 ^ 1];
+                {
+                    SpanGuard g(ctx, BWTS_K_RERANK, m_big, 20 * m_big);
+                    dg_stage2_keys_kernel<<<dim3((unsigned)((m_big + 255) / 256)), dim3(256), 0, ctx->stream>>>(vin, bk[0], m_big, kin);
+                    CH_HIP(hipGetLastError());
                 }
+                bp.keys[0] = kin; bp.keys[1] = kout;
+                bp.vals[0] = vin; bp.vals[1] = vout;
+                CH_TRY(radix_sort_pairs(ctx, bp, m_big, big_bits, &rbig));
                 SpanGuard g(ctx, BWTS_K_RERANK, m_big, 60 * m_big);
-                bl_flags_kernel<<<dim3((unsigned)((m_big + 255) / 256)), dim3(256), 0, ctx->stream>>>(sorted_k1, src, nk == 3 ? k23 : nullptr, positions, m_big, rb, bflags, t_idx);
+                bl_flags_kernel<<<dim3((unsigned)((m_big + 255) / 256)), dim3(256), 0, ctx->stream>>>(bp.keys[rbig], bp.vals[rbig], k23, bv[0], m_big, rb, bflags, t_idx);
                 CH_HIP(hipGetLastError());
                 // (the sort buffers are free again: subgroup starts and sizes go there)
                 BlFlagIn rin{bflags};
@@ -1253,7 +1219,7 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
                 BlSplitOut sout{bv[0], bv[1], t_idx, t_head, m_big, st_idx + tail, st_head + tail, bl_idx[blc ^ 1], bl_head[blc ^ 1], res};
                 CH_TRY((device_scan<false, u64>(ctx, m_big, sin, sout, OpAdd(), (u64)0, sp.scan_temp)));
             }
-            h = h > (1ull << 60) ? h : h << hshift;
+            h = h > (1ull << 60) ? h : h << 2;        // the step is quadrupled per round
         }
         CH_TRY(read_small(ctx, SM_CHSLOT, CH_SLOTS * CH_SLOT_WORDS));
         for (int b = 0; b < B; b++) {

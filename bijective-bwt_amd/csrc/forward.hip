@@ -675,11 +675,6 @@ __global__ __launch_bounds__(256) void cyclic_patch_vl_kernel(const u8 *__restri
     ks_store(keys, p, vl_key_cyclic(T, vtab, key_bits, p, s, e));
 }
 
-__global__ __launch_bounds__(256) void iota_kernel(u32 *__restrict__ v, u64 n)
-{
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) v[i] = (u32)i;
-}
-
 // first msym symbols of rot(p)^omega for a position of factor [s, e)
 __device__ __forceinline__ u64 cyclic_key(const u8 *__restrict__ T, const u8 *__restrict__ codes, int bits, int msym,
                                           u64 p, u64 s, u64 e)
@@ -888,7 +883,7 @@ struct OpHeadCount {
 struct GroupRaw { u64 k, edge; u32 slot; };
 
 struct GroupIn {
-    const u64 *K; const u32 *S; u64 a; int rb;     // S == nullptr: slot(i) = i (round 0)
+    const u64 *K; const u32 *S; u64 a; int rb;
     __device__ __forceinline__ GroupRaw load(u64 i) const
     {
         GroupRaw r;
@@ -899,7 +894,7 @@ struct GroupIn {
         r.edge = 0;
         if (lane == 0 && i > 0) r.edge = K[i - 1];
         if (lane != 0 && !next_here && i + 1 < a) r.edge = K[i + 1];
-        r.slot = S ? S[i] : (u32)i;
+        r.slot = S[i];
         return r;
     }
     __device__ __forceinline__ u64 make(u64 i, const GroupRaw &r, u32 *note) const
@@ -916,7 +911,7 @@ struct GroupIn {
         if (lane == 0 && !next_here && i + 1 < a) kn = K[i + 1];
         const bool f0 = i == 0 || ki != kp;
         const bool f1 = i + 1 == a || kn != ki;
-        const bool so = rb >= 0 && i > 0 && (ki >> rb) == (kp >> rb);
+        const bool so = i > 0 && (ki >> rb) == (kp >> rb);
         *note = (f0 ? 1u : 0u) | (f1 ? 2u : 0u) | (so ? 4u : 0u);
         return ((u64)(f0 ? r.slot : 0u) << 32) | (u64)((f0 && f1) ? 0u : 1u);
     }
@@ -925,9 +920,8 @@ struct GroupIn {
 };
 
 struct GroupOut {
-    const u32 *S; const u32 *V; u64 a; int rb;     // rb < 0: round 0 (no older groups)
-    const u64 *K;                                   // later rounds: the sorted keys (old head = K[i] >> rb), else nullptr
-    u32 *rank;                                      // dense rank array, or nullptr
+    const u32 *S; const u32 *V; u64 a; int rb;
+    const u64 *K;                                   // the sorted keys (old head = K[i] >> rb)
     const u32 *tpos; u32 *trank; u64 a0;            // sparse rank map (tied positions -> rank), or nullptr
     u32 *SA;
     u32 *n_idx, *n_slot, *n_head;
@@ -938,13 +932,12 @@ struct GroupOut {
         const bool f0 = note & 1u, f1 = note & 2u, same_old = note & 4u;
         const bool keep = !(f0 && f1);
         const u32 head = (u32)(v >> 32);
-        const u32 val = (keep || rank || S) ? V[i] : 0u;     // round 0 touches the suffix array only for tied elements
-        const u32 slot = S ? S[i] : (u32)i;
-        // an element whose group keeps its first slot keeps its rank: no random write (dense) / map search (sparse) for it
-        const bool moved = !K || (u32)(K[i] >> rb) != head;
-        if (rank && moved) rank[val] = head;
+        const u32 val = V[i];
+        const u32 slot = S[i];
+        // an element whose group keeps its first slot keeps its rank: no map search for it
+        const bool moved = (u32)(K[i] >> rb) != head;
         if (tpos && moved) { const u64 j = tied_find(tpos, a0, val); if (j != ~0ull) trank[j] = head; }
-        if (S) SA[slot] = val;
+        SA[slot] = val;
         if (keep) {
             const u32 dst = (u32)v - 1u;
             n_idx[dst] = val; n_slot[dst] = slot; n_head[dst] = head;
@@ -954,12 +947,10 @@ struct GroupOut {
         if (i + 1 == a) *cnt_active = ((u32)v == 0u && keep) ? 0x100000000ull : (u64)(u32)v;
         // "did any group split this round?" is all the driver needs: one plain store per wave, and none once the
         // flag is visibly set (counting with atomics serialised millions of waves on one address in deep rounds)
-        if (rb >= 0) {
-            const u64 ms = __ballot(f0 && same_old);
-            if (ms && lane_id() == __ffsll((unsigned long long)__ballot(true)) - 1 &&
-                __hip_atomic_load(cnt_splits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-                __hip_atomic_store(cnt_splits, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        const u64 ms = __ballot(f0 && same_old);
+        if (ms && lane_id() == __ffsll((unsigned long long)__ballot(true)) - 1 &&
+            __hip_atomic_load(cnt_splits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
+            __hip_atomic_store(cnt_splits, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 };
 
@@ -967,7 +958,7 @@ struct GroupOut {
 // The n-sized round needs the sorted keys only to know where groups start (f0) and which elements sit in a group of more
 // than one (keep).  group_flags_kernel reads the keys once and leaves both as bitmaps (one u64 per 64 slots, straight
 // from __ballot); the scan then runs over n/64 words instead of n elements, and tied_from_flags_kernel turns the set
-// bits into the tied list.  Same outputs as GroupIn/GroupOut with rb < 0, a third of the time.
+// bits into the tied list: a third of the time of an element-wise scan over the keys, as the later rounds run (GroupIn/GroupOut).
 #define GF_WORDS 8      // words (of 64 slots) a wave handles per step: eight key loads in flight per lane
 // A slot starts a group when its key differs from the slot before; it is the last of its group when the NEXT slot starts one: so only
 // the left neighbour's key is fetched (DPP wave_shr:1 on the two halves; lane 0 takes the word before's lane 63 from a scalar), and
@@ -1143,103 +1134,10 @@ static int sort_space_alloc(bwts_ctx *ctx, u64 n, SortSpace *sp)
 
 // ---- dense rank array after round 0, binned -------------------------------------------------------------------------
 // rank[SA[i]] = head(i) is n random 4-byte writes: 24 G/s on this chip, 73-85 G/s when the writes in flight fall into a
-// window of <= 1 MB (tools/micro/window_scatter.hip).  So: (1) partition the pairs (SA[i], head(i)) by destination window
-// -- one tile of RB_CHUNK pairs per workgroup, LDS counts, one global atomic per touched window (counters on separate
-// cache lines), the tile ordered by window in LDS and written out in contiguous runs; (2) scatter window after window,
-// all workgroups in the same few windows at a time.  head(i) comes straight from the round-0 flag words, so the tied
-// elements need no second scatter.  SA is a permutation: every window receives exactly its size.
-#define RB_THREADS 512
-#define RB_PER_THREAD 16
-#define RB_CHUNK (RB_THREADS * RB_PER_THREAD)
-#define RB_MAX_WINDOWS 4096
-#define RB_FILL_STRIDE 32
-#define RB_BLOCKS_PER_WINDOW 64
-static inline size_t rank_partition_lds_bytes(u32 nw) { return (size_t)RB_CHUNK * 8 + 2 * (size_t)nw * 4; }
-
-__global__ __launch_bounds__(RB_THREADS) void rank_partition_kernel(const u32 *__restrict__ SA, u64 n, const u64 *__restrict__ headw,
-                                                                    const u64 *__restrict__ pre, int wlog, u32 nw,
-                                                                    u32 *__restrict__ win_fill, u64 *__restrict__ pairs)
-{
-    extern __shared__ __attribute__((aligned(16))) char rb_lds[];
-    u64 *sorted = (u64 *)rb_lds;                       // RB_CHUNK pairs ordered by window
-    u32 *cnt = (u32 *)(sorted + RB_CHUNK);             // per window: count, then the fill cursor within `sorted`
-    u32 *delta = cnt + nw;                             // per window: (reserved offset in the window) - (start in `sorted`)
-    __shared__ u32 scan_sm[RB_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const u64 base = (u64)blockIdx.x * RB_CHUNK;
-    const u32 clen = n - base < RB_CHUNK ? (u32)(n - base) : (u32)RB_CHUNK;
-    u32 x[RB_PER_THREAD], h[RB_PER_THREAD];
-#pragma unroll
-    for (int q = 0; q < RB_PER_THREAD; q++) {
-        const u32 e = (u32)q * RB_THREADS + tid;
-        x[q] = e < clen ? SA[base + e] : 0u;
-    }
-#pragma unroll
-    for (int q = 0; q < RB_PER_THREAD; q++) {
-        // slot i = base + e; its 64-slot word is the same for the whole wave
-        const u64 i = base + (u32)q * RB_THREADS + tid;
-        const u64 w = i >> 6;
-        u64 hm = 0, pr = 0;
-        if (i < n) { hm = headw[w]; pr = pre[w]; }
-        const u64 below = lane == 63 ? hm : hm & ((2ull << lane) - 1ull);
-        h[q] = below ? (u32)((w << 6) + (u64)(63 - __clzll((long long)below))) : (u32)(pr >> 32);
-    }
-    for (u32 b = tid; b < nw; b += RB_THREADS) cnt[b] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < RB_PER_THREAD; q++)
-        if ((u32)q * RB_THREADS + tid < clen) atomicAdd(&cnt[x[q] >> wlog], 1u);
-    __syncthreads();
-    {
-        const u32 per = (nw + RB_THREADS - 1) / RB_THREADS;      // windows a thread scans (<= 8)
-        u32 c[8], run = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const u32 b = (u32)tid * per + j;
-            c[j] = (u32)j < per && b < nw ? cnt[b] : 0u;
-            run += c[j];
-        }
-        u32 tot;
-        u32 exc = block_scan_exclusive<u32, OpAdd, RB_THREADS / 64>(run, OpAdd(), 0u, scan_sm, &tot);
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const u32 b = (u32)tid * per + j;
-            if ((u32)j < per && b < nw) {
-                const u32 g = c[j] ? atomicAdd(&win_fill[(size_t)b * RB_FILL_STRIDE], c[j]) : 0u;
-                cnt[b] = exc;
-                delta[b] = g - exc;
-                exc += c[j];
-            }
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < RB_PER_THREAD; q++)
-        if ((u32)q * RB_THREADS + tid < clen) ((uint2 *)sorted)[atomicAdd(&cnt[x[q] >> wlog], 1u)] = make_uint2(x[q], h[q]);
-    __syncthreads();
-    for (u32 e = tid; e < clen; e += RB_THREADS) {
-        const uint2 v = ((const uint2 *)sorted)[e];
-        const u32 b = v.x >> wlog;
-        ((uint2 *)pairs)[((u64)b << wlog) + (u32)(delta[b] + e)] = v;
-    }
-}
-
-// window b is written by RB_BLOCKS_PER_WINDOW consecutive workgroups, so the workgroups in flight share a few windows
-__global__ __launch_bounds__(256) void rank_scatter_pairs_kernel(const u64 *__restrict__ pairs, const u32 *__restrict__ win_fill, int wlog,
-                                                                 u32 *__restrict__ rank)
-{
-    const u32 b = blockIdx.x / RB_BLOCKS_PER_WINDOW, s = blockIdx.x % RB_BLOCKS_PER_WINDOW;
-    const u32 fill = win_fill[(size_t)b * RB_FILL_STRIDE];
-    const u32 per = (fill + RB_BLOCKS_PER_WINDOW - 1) / RB_BLOCKS_PER_WINDOW;
-    const u32 lo = s * per, hi = lo + per < fill ? lo + per : fill;
-    const uint2 *src = (const uint2 *)pairs + ((u64)b << wlog);
-    for (u32 e = lo + threadIdx.x; e < hi; e += 256) { const uint2 v = src[e]; rank[v.x] = v.y; }
-}
-
-// Second form of the same build, the one in use: one u64 per slot, (head << 32) | position, sorted on the position's top 16 bits
-// by two keys-only radix passes (16 bytes per element and pass, ballot-ranked like every other pass -- the LDS atomics of
-// rank_partition_kernel made that single pass cost 30 ms at n = 2^30), then rank[position] = head with all writes of a
-// workgroup inside a window of n / 2^16 positions.
+// window of <= 1 MB (tools/micro/window_scatter.hip).  So: one u64 per slot, (head << 32) | position, with head(i) straight from
+// the round-0 flag words (the tied elements need no second scatter), sorted on the position's top 16 bits by two keys-only radix
+// passes (ballot-ranked like every other pass: a partition by LDS atomics cost 30 ms at n = 2^30), then rank[position] = head
+// with all writes of a workgroup inside a window of n / 2^16 positions.
 __global__ __launch_bounds__(256) void rank_keys_kernel(const u32 *__restrict__ SA, u64 n, const u64 *__restrict__ headw,
                                                         const u64 *__restrict__ pre, u64 *__restrict__ keys)
 {
@@ -1410,13 +1308,9 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
     plan.vals[0] = sp.vals[0]; plan.vals[1] = sp.vals[1];
     plan.tile_hist = sp.tile_hist; plan.scan_temp = sp.scan_temp;
     plan.sym_src = sp.carry_src; plan.sym_buf[0] = sp.carry_buf[0]; plan.sym_buf[1] = sp.carry_buf[1]; plan.sym_final = sp.carry_out;
-    plan.vals_identity = radix_supports_sym(ctx);     // keybuild0 writes no value array
-    plan.keys_split = CYCLIC && sp.split_keys && plan.sym_final && plan.vals_identity;
+    plan.vals_identity = true;     // keybuild0 writes no value array
+    plan.keys_split = CYCLIC && sp.split_keys && plan.sym_final;
     if (CYCLIC && sp.split_keys && !plan.keys_split) return BWTS_E_INTERNAL;      // keybuild split the keys for a sort that cannot take them
-    if (!plan.vals_identity) {                     // tuning configs without the identity variant: materialise it
-        u64 blocks = (n + 255) / 256; if (blocks > 8192) blocks = 8192;
-        iota_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(sp.vals[0], n);
-    }
     int res = 0;
     STAGE("cyclic patch (before round 0)");
     BWTS_TRY(radix_sort_pairs(ctx, plan, n, al.key_bits, &res));
@@ -1430,25 +1324,15 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
     cur.head = sp.vals[res ^ 1];
 
     HIPC(hipMemsetAsync(cnt, 0, 4 * sizeof(u64), ctx->stream));
-    const u64 *flag_heads = nullptr, *flag_pre = nullptr;     // set when the round-0 flag words survive outside sp.rank
-    const u64 *flag_heads_any = nullptr, *flag_pre_any = nullptr, *flag_keep = nullptr;   // the flag words wherever they live
-    u64 flag_words = 0;
-    bool rank_early = false;                                  // the dense rank array was built before the tied list
-    const bool scan_by_keys = [ctx] { const char *e = bwts_knob(ctx, "BWTS_GROUPSCAN"); return e && !strcmp(e, "keys"); }();
-    if (scan_by_keys) {             // the element-wise scan the later rounds use (kept selectable for tests)
-        SpanGuard g(ctx, BWTS_K_RERANK, n, 8 * n);
-        GroupIn in{K0, nullptr, n, -1};
-        GroupOut out{nullptr, SA, n, -1, nullptr, nullptr, nullptr, nullptr, 0, SA, cur.idx, cur.slot, cur.head, cnt + 0, cnt + 1};
-        BWTS_TRY((device_scan<true, u64>(ctx, n, in, out, OpHeadCount(), (u64)0, sp.scan_temp)));
-    } else {
+    const u64 words = (n + 63) / 64;
+    u64 *headw, *keepw, *pre;
+    const bool flags_outside_rank = sp.carry_buf[0] && sp.carry_buf[1] && n >= 4096;
+    {
         SpanGuard g(ctx, BWTS_K_RERANK, n, 8 * n);
         // flags and word prefixes (3 * n/8 bytes): in the carried-byte ping-pong buffers when there are any (free once the
         // sort is done), else in sp.rank, which is not needed before the rounds that follow
-        const u64 words = (n + 63) / 64;
-        u64 *headw, *keepw, *pre;
-        if (sp.carry_buf[0] && sp.carry_buf[1] && n >= 4096) {
+        if (flags_outside_rank) {
             headw = (u64 *)sp.carry_buf[0]; keepw = headw + words; pre = (u64 *)sp.carry_buf[1];
-            flag_heads = headw; flag_pre = pre;
         } else {
             BWTS_TRY(ensure_rank(ctx, sp, n));
             headw = (u64 *)sp.rank; keepw = headw + words; pre = keepw + words;
@@ -1462,43 +1346,37 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
         count_tied_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(keepw, pre, words, cnt + 0);
         HIPC(hipGetLastError());
         STAGE("group flags + word scan + count");
-        flag_keep = keepw; flag_words = words;
-        flag_heads_any = headw; flag_pre_any = pre;
     }
     BWTS_TRY(read_small(ctx, SM_COUNTERS, 4));
     u64 a = ctx->h_small[CNT_ACTIVE];
     *active0_out = a;
     if (CYCLIC) ctx->tm.round_active[0] = a;
-    bool rank_valid = false;
-    if (flag_keep) {
-        // Many ties: the dense rank array.  It is built BEFORE the tied list, while the list's future home (the other key
-        // buffer) is still free: the build sorts one u64 per slot between that buffer and the sorted keys' (not needed any
-        // more without the sparse rank map).
-        const bool plain_build = [ctx] { const char *e = bwts_knob(ctx, "BWTS_RANKBUILD"); return e && !strcmp(e, "plain"); }();
-        const bool part_build = [ctx] { const char *e = bwts_knob(ctx, "BWTS_RANKBUILD"); return e && !strcmp(e, "partition"); }();
-        if (a > n / 32 && flag_heads && n >= (1ull << 22) && !plain_build && !part_build) {
-            BWTS_TRY(ensure_rank(ctx, sp, n));
-            SpanGuard g(ctx, BWTS_K_RERANK, n, 28 * n);
-            u64 *rk[2] = {sp.keys[res ^ 1], K0};
-            u64 blocks = (n + 255) / 256; if (blocks > 16384) blocks = 16384;
-            rank_keys_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(SA, n, flag_heads, flag_pre, rk[0]);
-            HIPC(hipGetLastError());
-            // sorted on the position's top 16 bits (24 beyond n = 2^30): windows of at most 2^RA_WLOG_MAX positions
-            const int pb = bitlen_u64(n - 1);
-            const int sbits = pb - 16 <= RA_WLOG_MAX ? 16 : 24;
-            int rres = 0;
-            BWTS_TRY(radix_sort_keys(ctx, rk, sp.tile_hist, sp.scan_temp, n, pb - sbits, sbits, &rres));
-            const int wlog = RA_WLOG_MAX;                   // sorted on at least the bits above 2^14: every 2^14 keys are 2^14 consecutive positions
-            BWTS_TRY(ensure_dyn_lds(ctx, (const void *)rank_apply_kernel, (size_t)4 << RA_WLOG_MAX));
-            rank_apply_kernel<<<dim3((unsigned)((n + (1ull << wlog) - 1) >> wlog)), dim3(1024), (size_t)4 << wlog, ctx->stream>>>(rk[rres], n, wlog, sp.rank);
-            HIPC(hipGetLastError());
-            rank_valid = true;
-            rank_early = true;
-        }
+    // Many ties: the dense rank array.  It is built BEFORE the tied list, while the list's future home (the other key
+    // buffer) is still free: the build sorts one u64 per slot between that buffer and the sorted keys' (not needed any
+    // more without the sparse rank map).
+    const bool rank_early = a > n / 32 && flags_outside_rank && n >= (1ull << 22);
+    if (rank_early) {
+        BWTS_TRY(ensure_rank(ctx, sp, n));
+        SpanGuard g(ctx, BWTS_K_RERANK, n, 28 * n);
+        u64 *rk[2] = {sp.keys[res ^ 1], K0};
+        u64 blocks = (n + 255) / 256; if (blocks > 16384) blocks = 16384;
+        rank_keys_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(SA, n, headw, pre, rk[0]);
+        HIPC(hipGetLastError());
+        // sorted on the position's top 16 bits (24 beyond n = 2^30): windows of at most 2^RA_WLOG_MAX positions
+        const int pb = bitlen_u64(n - 1);
+        const int sbits = pb - 16 <= RA_WLOG_MAX ? 16 : 24;
+        int rres = 0;
+        BWTS_TRY(radix_sort_keys(ctx, rk, sp.tile_hist, sp.scan_temp, n, pb - sbits, sbits, &rres));
+        const int wlog = RA_WLOG_MAX;                   // sorted on at least the bits above 2^14: every 2^14 keys are 2^14 consecutive positions
+        BWTS_TRY(ensure_dyn_lds(ctx, (const void *)rank_apply_kernel, (size_t)4 << RA_WLOG_MAX));
+        rank_apply_kernel<<<dim3((unsigned)((n + (1ull << wlog) - 1) >> wlog)), dim3(1024), (size_t)4 << wlog, ctx->stream>>>(rk[rres], n, wlog, sp.rank);
+        HIPC(hipGetLastError());
+    }
+    {
         SpanGuard g(ctx, BWTS_K_RERANK, a, 12 * a);
-        const u64 waves = (flag_words + 63) / 64;
+        const u64 waves = (words + 63) / 64;
         const unsigned blocks = (unsigned)((waves + 3) / 4 < 16384 ? (waves + 3) / 4 : 16384);
-        tied_from_flags_kernel<<<dim3(blocks), dim3(256), 0, ctx->stream>>>(flag_heads_any, flag_keep, flag_pre_any, n, SA, cur.idx, cur.slot, cur.head, cnt + 0);
+        tied_from_flags_kernel<<<dim3(blocks), dim3(256), 0, ctx->stream>>>(headw, keepw, pre, n, SA, cur.idx, cur.slot, cur.head, cnt + 0);
         HIPC(hipGetLastError());
         STAGE("tied list");
     }
@@ -1543,11 +1421,10 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
             tpos = (u32 *)(base + 2 * e8 + 7 * e4);          // the last two arrays of the aux block
             trank = (u32 *)(base + 2 * e8 + 8 * e4);
             // directory over the sorted keys' top bits for the rank searches of keybuild_sparse_kernel
-            const bool no_dir = [ctx] { const char *e = bwts_knob(ctx, "BWTS_K0DIR"); return e && atoi(e) == 0; }();
             const int kb = al.key_bits;
             dlog = kb < K0_DIR_LOG2_MAX ? kb : K0_DIR_LOG2_MAX;
             if (dlog > bitlen_u64(n)) dlog = bitlen_u64(n);
-            if (!no_dir && dlog >= 8) {
+            if (dlog >= 8) {
                 dir = (u64 *)(base + 2 * e8 + 9 * e4);
                 k0_directory_kernel<<<dim3((unsigned)(((1ull << dlog) + 1 + 255) / 256)), dim3(256), 0, ctx->stream>>>(K0, n, kb, dlog, dir);
             }
@@ -1570,27 +1447,8 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
             }
             HIPC(hipGetLastError());
         } else {
-            const bool plain_build = [ctx] { const char *e = bwts_knob(ctx, "BWTS_RANKBUILD"); return e && !strcmp(e, "plain"); }();
             BWTS_TRY(ensure_rank(ctx, sp, n));
-            if (rank_early) {
-                // built before the tied list (see above)
-            } else if (flag_heads && n >= (1ull << 22) && !plain_build) {
-                // BWTS_RANKBUILD=partition: the first binned form.  Pairs go through the sorted keys' buffer (not needed without the sparse map), counters through the tile table
-                SpanGuard g(ctx, BWTS_K_RERANK, n, 28 * n);
-                int wlog = bitlen_u64(n - 1) - 12;
-                if (wlog < 18) wlog = 18;
-                const u32 nw = (u32)((n + (1ull << wlog) - 1) >> wlog);
-                u32 *win_fill = sp.tile_hist;
-                HIPC(hipMemsetAsync(win_fill, 0, (size_t)nw * RB_FILL_STRIDE * sizeof(u32), ctx->stream));
-                BWTS_TRY(ensure_dyn_lds(ctx, (const void *)rank_partition_kernel, rank_partition_lds_bytes(RB_MAX_WINDOWS)));
-                rank_partition_kernel<<<dim3((unsigned)((n + RB_CHUNK - 1) / RB_CHUNK)), dim3(RB_THREADS), rank_partition_lds_bytes(nw), ctx->stream>>>(
-                    SA, n, flag_heads, flag_pre, wlog, nw, win_fill, K0);
-                rank_scatter_pairs_kernel<<<dim3(nw * RB_BLOCKS_PER_WINDOW), dim3(256), 0, ctx->stream>>>(K0, win_fill, wlog, sp.rank);
-                HIPC(hipGetLastError());
-            } else {
-                BWTS_TRY(build_ranks(ctx, SA, n, cur, a, sp.rank));
-            }
-            rank_valid = true;
+            if (!rank_early) BWTS_TRY(build_ranks(ctx, SA, n, cur, a, sp.rank));      // (else built before the tied list, see above)
             // group-local rounds; SA is only rebuilt when someone reads it afterwards (suffix array requested, or the
             // gather form of the emission)
             const bool need_sa = !CYCLIC || !sp.carry_out;
@@ -1692,7 +1550,7 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
             {
                 SpanGuard g(ctx, BWTS_K_RERANK, a, 24 * a);
                 GroupIn in{AK, cur.slot, a, rb};
-                GroupOut out{cur.slot, AV, a, rb, AK, nullptr, tpos, trank, a0, SA,
+                GroupOut out{cur.slot, AV, a, rb, AK, tpos, trank, a0, SA,
                              sets[nxt].idx, sets[nxt].slot, sets[nxt].head, cnt + 0, cnt + 1};
                 BWTS_TRY((device_scan<true, u64>(ctx, a, in, out, OpHeadCount(), (u64)0, sp.scan_temp)));
             }
@@ -1709,7 +1567,7 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
             if (rounds > 80) return BWTS_E_INTERNAL;
         }
     }
-    if (want_ranks && !rank_valid) { BWTS_TRY(ensure_rank(ctx, sp, n)); BWTS_TRY(build_ranks(ctx, SA, n, a ? cur : none, a, sp.rank)); }
+    if (want_ranks && !rank_early) { BWTS_TRY(ensure_rank(ctx, sp, n)); BWTS_TRY(build_ranks(ctx, SA, n, a ? cur : none, a, sp.rank)); }
     *sa_out = SA;
     *rounds_out = rounds;
     return BWTS_OK;
@@ -2355,7 +2213,7 @@ static int forward_run(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, const Se
     const char *emit_env = bwts_knob(ctx, "BWTS_EMIT");      // carry (default) | gather
     // (segments: the partition below needs the whole suffix array, which the sort rebuilds for its tied elements only when no byte
     // rides on it -- the gather emission)
-    const bool carry = !seg && radix_supports_sym(ctx) && !(emit_env && !strcmp(emit_env, "gather"));
+    const bool carry = !seg && !(emit_env && !strcmp(emit_env, "gather"));
     sp.want_split = carry;                           // the byte stream rides round 0 => the packed passes may take split keys
     BWTS_TRY(factors_and_keys(ctx, d_in, n, sp, &al, &d_fstart, &k, &lrounds, true, seg));
     ctx->tm.factors = k;

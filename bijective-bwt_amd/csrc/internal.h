@@ -117,7 +117,6 @@ struct bwts_ctx {
     // select alternate code paths -- what the test suite drives -- only when BWTS_TEST_KNOBS=1 is set
     std::vector<std::pair<std::string, std::string>> knobs;
     int fused_scan_cap;    // workgroups of radix_column_scan_fused_kernel that are certain to be resident together (0 = not yet asked)
-    int rx_config;         // radix tile shape (BWTS_RX_CONFIG, a tuning knob; 0 = the product shape)
 
     // segment table of the current segmented call: offsets on the host (count + 1) and their device copy
     std::vector<u64> seg_off;
@@ -208,8 +207,6 @@ struct SortPlan {
     bool keys_split = false;
 };
 bool radix_packed_applicable(const bwts_ctx *ctx, u64 m, int key_bits);   // will radix_sort_pairs run its packed-stream passes for such a sort?
-bool radix_supports_sym(const bwts_ctx *ctx);       // the byte stream is compiled for the default tile shape only
-u64    radix_tiles(const bwts_ctx *ctx, u64 m);
 size_t radix_tile_hist_bytes(u64 m);
 // Sorts on key bits [0, key_bits); returns in *result_buf which of keys[]/vals[] holds the output.
 int radix_sort_pairs(bwts_ctx *ctx, const SortPlan &plan, u64 m, int key_bits, int *result_buf);

@@ -192,7 +192,7 @@ __device__ __forceinline__ u32 symbol_of(const u64 *Ctab, u32 y)
 #define MOM_LOG2_SMALL 10                    // classes: 2^10 up to n = 2^30 (20 KB of LDS), 2^12 above (80 KB: a class stays at 2^20 elements)
 #define MOM_LOG2_LARGE 12
 #define MOM_MAX_BUCKETS (1u << MOM_LOG2_LARGE)
-template <int MARK, int SBW = 16 /* registers of recorded symbols per store: 16 = 64-byte blocks, 4 = 16-byte ones (BWTS_WALK_SYMS=16) */>
+template <int MARK, int SBW = 16 /* registers of recorded symbols per store: 16 = 64-byte blocks, 4 = 16-byte ones */>
 __global__ __launch_bounds__(256) void walk_record_kernel(u32 *__restrict__ LF, u8 *__restrict__ marks, u32 *__restrict__ idxlog, u64 s, u64 node_cap, int g, u32 slot,
                                                           const u64 *__restrict__ Cg, u8 *__restrict__ seg,
                                                           uint4 *__restrict__ noderec /* x next node, y segment length, z smallest element, w its offset */,

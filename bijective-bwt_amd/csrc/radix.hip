@@ -32,24 +32,12 @@ __device__ __forceinline__ u64 rx_tile_of_block(u64 tiles)
 }
 static inline u64 rx_grid(u64 tiles) { return (tiles + RX_XCDS - 1) / RX_XCDS * RX_XCDS; }
 
-// tile shapes compiled in; BWTS_RX_CONFIG picks one at first use (tuning knob).  Shape 0 is the product shape:
-// 512 threads x 16 items = 8192 elements, two tiles resident per CU; only it carries the byte stream.
-struct RxConfig { int threads, items; };
-static const RxConfig kRxConfigs[] = {{512, 16}, {512, 12}, {256, 16}, {1024, 8}};
-#define RX_NCONFIGS ((int)(sizeof(kRxConfigs) / sizeof(kRxConfigs[0])))
-#define RX_DEFAULT_CONFIG 0
-
-static int rx_config_index(const bwts_ctx *ctx) { return ctx->rx_config; }      // parsed from BWTS_RX_CONFIG when the context was made (api.hip)
-static u64 rx_tile(const bwts_ctx *ctx) { const RxConfig &c = kRxConfigs[rx_config_index(ctx)]; return (u64)c.threads * c.items; }
-
-int radix_config_count(void) { return RX_NCONFIGS; }
-u64 radix_tiles(const bwts_ctx *ctx, u64 m) { return (m + rx_tile(ctx) - 1) / rx_tile(ctx); }
-
 static inline u64 radix_chunks(u64 tiles) { return (tiles + RX_CHUNK - 1) / RX_CHUNK; }
 
 size_t radix_tile_hist_bytes(u64 m)
 {
-    // sized for the smallest compiled tile so the knob never outgrows a caller's buffer
+    // sized for tiles of 3072 elements, so one size serves every user: the radix passes' 8192-element tiles and the inverse's
+    // 4096-element LF tiles (inverse.hip, wide_inverse.h).  Every arena reservation that holds the table depends on this value.
     const u64 tiles = (m + 3071) / 3072 + 1;
     return align_up((size_t)tiles * 256 * sizeof(u32), 256) +
            align_up((size_t)radix_chunks(tiles) * 256 * sizeof(u32), 256);
@@ -591,7 +579,7 @@ static int launch_scatter_packed(bwts_ctx *ctx, u64 tiles, const PackedIO &io, c
 template <bool HI16>
 static int radix_sort_packed(bwts_ctx *ctx, const SortPlan &plan, u64 m, int passes, int *result_buf)
 {
-    const u64 tiles = (m + 8191) / 8192;
+    const u64 tiles = (m + 8191) / 8192;        // 512 threads x 16 items, two tiles resident per CU
     u32 *tile_hist = plan.tile_hist;
     const size_t lo_bytes = align_up((size_t)m * 4, 256);
     const u64 pass_bytes = HI16 ? 20 : 18;
@@ -735,27 +723,6 @@ static int launch_scatter2_t(bwts_ctx *ctx, u64 tiles, const u64 *kin, const u32
     return BWTS_OK;
 }
 
-static void launch_hist(bwts_ctx *ctx, int cfg, u64 tiles, const u64 *keys, u64 m, int shift, u32 *tile_hist)
-{
-    switch (cfg) {
-    case 0: launch_hist_t<512, 16>(ctx, tiles, keys, m, shift, tile_hist); break;
-    case 1: launch_hist_t<512, 12>(ctx, tiles, keys, m, shift, tile_hist); break;
-    case 2: launch_hist_t<256, 16>(ctx, tiles, keys, m, shift, tile_hist); break;
-    default: launch_hist_t<1024, 8>(ctx, tiles, keys, m, shift, tile_hist); break;
-    }
-}
-
-static int launch_scatter(bwts_ctx *ctx, int cfg, u64 tiles, const u64 *kin, const u32 *vin, u64 *kout, u32 *vout,
-                          const u32 *tile_off, u64 m, int shift)
-{
-    switch (cfg) {
-    case 0: return launch_scatter2_t<512, 16, 4>(ctx, tiles, kin, vin, kout, vout, tile_off, m, shift);
-    case 1: return launch_scatter2_t<512, 12, 4>(ctx, tiles, kin, vin, kout, vout, tile_off, m, shift);
-    case 2: return launch_scatter2_t<256, 16, 4>(ctx, tiles, kin, vin, kout, vout, tile_off, m, shift);
-    default: return launch_scatter2_t<1024, 8, 8>(ctx, tiles, kin, vin, kout, vout, tile_off, m, shift);
-    }
-}
-
 // [tile][digit] counts -> global exclusive offsets in digit-major order, in place.
 // tile_hist must be followed by the chunk table (radix_tile_hist_bytes()).
 // The three steps above in one launch, for tables of at most RX_FUSED_CHUNKS chunks (sorts of up to 2^28 elements): one workgroup
@@ -858,7 +825,7 @@ int radix_column_scan(bwts_ctx *ctx, u32 *tile_hist, u64 tiles, void *scan_temp)
     return BWTS_OK;
 }
 
-// Stable sort of bare u64 keys on bits [lo_bit, lo_bit + bits): 16 bytes per element and pass.  Product tile shape only.
+// Stable sort of bare u64 keys on bits [lo_bit, lo_bit + bits): 16 bytes per element and pass.
 // Returns in *result_buf which of keys[] holds the output.
 int radix_sort_keys(bwts_ctx *ctx, u64 *keys[2], u32 *tile_hist, void *scan_temp, u64 m, int lo_bit, int bits, int *result_buf)
 {
@@ -885,13 +852,11 @@ int radix_sort_keys(bwts_ctx *ctx, u64 *keys[2], u32 *tile_hist, void *scan_temp
     return BWTS_OK;
 }
 
-bool radix_supports_sym(const bwts_ctx *ctx) { return rx_config_index(ctx) == 0; }
-
 bool radix_packed_applicable(const bwts_ctx *ctx, u64 m, int key_bits)
 {
     const bool packed_ok = [ctx] { const char *e = bwts_knob(ctx, "BWTS_RX_PACK"); return !(e && atoi(e) == 0); }();
     const int passes = ((key_bits < 1 ? 1 : key_bits) + 7) / 8;
-    return packed_ok && rx_config_index(ctx) == 0 && passes >= 3 && passes <= 5 && m >= 65536;
+    return packed_ok && passes >= 3 && passes <= 5 && m >= 65536;
 }
 
 int radix_sort_pairs(bwts_ctx *ctx, const SortPlan &plan, u64 m, int key_bits, int *result_buf)
@@ -901,8 +866,7 @@ int radix_sort_pairs(bwts_ctx *ctx, const SortPlan &plan, u64 m, int key_bits, i
     if (key_bits < 1) key_bits = 1;
     if (key_bits > 64) key_bits = 64;
     const int passes = (key_bits + 7) / 8;
-    const u64 tiles = radix_tiles(ctx, m);
-    const int cfg = rx_config_index(ctx);
+    const u64 tiles = (m + 8191) / 8192;        // 512 threads x 16 items, two tiles resident per CU
     u32 *tile_hist = plan.tile_hist;
 
     const bool small_ok = [ctx] { const char *e = bwts_knob(ctx, "BWTS_RX_SMALL"); return !(e && atoi(e) == 0); }();
@@ -923,7 +887,7 @@ int radix_sort_pairs(bwts_ctx *ctx, const SortPlan &plan, u64 m, int key_bits, i
         const int shift = 8 * p;
         {
             SpanGuard g(ctx, BWTS_K_RADIX_HIST, m, 8 * m);
-            launch_hist(ctx, cfg, tiles, plan.keys[cur], m, shift, tile_hist);
+            launch_hist_t<512, 16>(ctx, tiles, plan.keys[cur], m, shift, tile_hist);
         }
         {
             SpanGuard g(ctx, BWTS_K_RADIX_SCAN, tiles * 256, tiles * 256 * 12);
@@ -931,7 +895,6 @@ int radix_sort_pairs(bwts_ctx *ctx, const SortPlan &plan, u64 m, int key_bits, i
         }
         const bool ident = plan.vals_identity && p == 0;
         if (plan.sym_src) {
-            if (cfg != 0) return BWTS_E_INTERNAL;
             const u8 *sin = p == 0 ? plan.sym_src : plan.sym_buf[(p - 1) & 1];
             u8 *sout = p == passes - 1 ? plan.sym_final : plan.sym_buf[p & 1];
             SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, (ident ? 22 : 26) * m);
@@ -945,14 +908,13 @@ int radix_sort_pairs(bwts_ctx *ctx, const SortPlan &plan, u64 m, int key_bits, i
                                                                       plan.vals[cur ^ 1], tile_hist, m, shift, sin, sout)));
             }
         } else if (ident) {
-            if (cfg != 0) return BWTS_E_INTERNAL;
             SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, 20 * m);
             BWTS_TRY((launch_scatter2_t<512, 16, 4, false, true>(ctx, tiles, plan.keys[cur], plan.vals[cur], plan.keys[cur ^ 1], plan.vals[cur ^ 1],
                                                                   tile_hist, m, shift)));
         } else {
             SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, 24 * m);
-            BWTS_TRY(launch_scatter(ctx, cfg, tiles, plan.keys[cur], plan.vals[cur], plan.keys[cur ^ 1], plan.vals[cur ^ 1], tile_hist, m,
-                                    shift));
+            BWTS_TRY((launch_scatter2_t<512, 16, 4>(ctx, tiles, plan.keys[cur], plan.vals[cur], plan.keys[cur ^ 1], plan.vals[cur ^ 1],
+                                                     tile_hist, m, shift)));
         }
         HIPC(hipGetLastError());
         cur ^= 1;

@@ -1185,13 +1185,9 @@ _ALT_ENVS = [
     {"BWTS_LYNDON": "general"},                       # factors from a full suffix sort + prefix minima of ISA
     {"BWTS_EMIT": "gather"},                          # classic bwts[r] = P[sa[r]] gather instead of the carried byte
     {"BWTS_RX_PACK": "0"},                            # round-0 sort on wide (u64, u32, u8) streams instead of packed ones
-    {"BWTS_GROUPSCAN": "keys"},                       # round-0 group scan element-wise over the keys instead of flag words
-    {"BWTS_RANKBUILD": "plain"},
-    {"BWTS_DENSE_STEP": "2"},                         # group-local rounds with plain doubling (one successor rank) instead of the quadrupled step
     {"BWTS_DENSE": "tiles"},                          # the tile form of the group-local rounds (round 2) instead of the chunked one
     {"BWTS_RX_SMALL": "0"},                           # small sorts through the multi-launch passes instead of the one-workgroup kernel
     {"BWTS_RX_FUSED_SCAN": "0"},                      # column scan of the tile table in five launches instead of the fused kernel
-    {"BWTS_K0DIR": "0"},                              # sparse key builder: plain binary searches, no directories                      # dense rank array by two plain scatters instead of the binned one
     {"BWTS_INV_MARK": "log"},                         # inverse logs every visited index (the fallback of the per-range moments)
     {"BWTS_INV_MARK": "sentinel"},                    # inverse marks visited entries in place instead of logging them
     {"BWTS_BYTEMARK": "1"},                           # inverse marks in a byte map (the n = 2^32 fallback)

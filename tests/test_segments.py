@@ -590,14 +590,10 @@ print("ok")
 
 SEG_ALT_ENVS = [
     {"BWTS_DENSE": "tiles"},
-    {"BWTS_DENSE_STEP": "2"},
     {"BWTS_VARLEN": "1", "BWTS_KEY_BITS": "24"},
     {"BWTS_VARLEN": "0", "BWTS_KEY_SYMBOLS": "2"},
     {"BWTS_RX_SMALL": "0"},
     {"BWTS_RX_PACK": "0"},
-    {"BWTS_GROUPSCAN": "keys"},
-    {"BWTS_RANKBUILD": "plain"},
-    {"BWTS_K0DIR": "0"},
     {"BWTS_POISON": "1"},
 ]
 _seg_alt_died = []

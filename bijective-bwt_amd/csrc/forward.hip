@@ -401,9 +401,29 @@ __global__ __launch_bounds__(256) void carried_head_fix_kernel(const u8 *__restr
 // The value array of round 0 is the identity and is never written: the first radix pass uses the element index.
 // pos0 / lim: the launch covers positions [pos0, lim) (pos0 a multiple of KB_TILE) and stores the key of position q at index
 // q - pos0, tile minima at tile - pos0 / KB_TILE: the wide path (n > 2^32) materialises keys one segment at a time.
+// A workgroup builds the KB_SUB tiles of one radix tile (KB_RX_TILE positions) one after the other.  hist0 (may be null; only with
+// pos0 = 0): it also counts the key's bits 0..7 -- the first radix pass's digit -- and leaves the radix tile's row of that pass's
+// [tile][digit] table, so the pass needs no sweep of its own over the keys (SortPlan::first_hist).
+#define KB_RX_TILE 8192                               // = the packed radix passes' tile (radix.hip)
+#define KB_SUB     (KB_RX_TILE / KB_TILE)
+__device__ __forceinline__ void kb_hist_clear(u32 (*bins)[256])
+{
+    for (int i = threadIdx.x; i < KB_THREADS / 64 * 256; i += KB_THREADS) ((u32 *)bins)[i] = 0;
+}
+__device__ __forceinline__ void kb_hist_flush(u32 (*bins)[256], u32 *__restrict__ hist0)
+{
+    __syncthreads();
+    u32 s = 0;
+#pragma unroll
+    for (int w = 0; w < KB_THREADS / 64; w++) s += bins[w][threadIdx.x];
+    hist0[(u64)blockIdx.x * 256 + threadIdx.x] = s;
+}
+static_assert(KB_THREADS == 256, "one thread per digit of the first pass's table row");
+
 __global__ __launch_bounds__(KB_THREADS) void keybuild0_kernel(const u8 *__restrict__ T, u64 n, const u8 *__restrict__ codes_g,
                                                                int bits, int msym, int pad_add,
-                                                               KeyStore keys, u64 *__restrict__ tile_min /* may be null */, u64 pos0, u64 lim)
+                                                               KeyStore keys, u64 *__restrict__ tile_min /* may be null */, u64 pos0, u64 lim,
+                                                               u32 *__restrict__ hist0)
 {
     __shared__ u16 sc[KB_TILE + KB_HALO + 16];
     __shared__ u64 skey[KB_TILE + KB_TILE / 8];     // blocked -> striped transpose (one pad slot per 8)
@@ -411,76 +431,88 @@ __global__ __launch_bounds__(KB_THREADS) void keybuild0_kernel(const u8 *__restr
     __shared__ u64 wmin[KB_THREADS / 64];
     __shared__ __attribute__((aligned(16))) u8 sraw[KB_TILE + KB_HALO + 16];     // the tile's raw bytes (split keys: carried byte = T[q - 1])
     __shared__ u8 before_tile;
+    __shared__ u32 bins[KB_THREADS / 64][256];
 
     const int tid = threadIdx.x;
-    const u64 base = pos0 + (u64)blockIdx.x * KB_TILE;
-    const u64 end = base + KB_TILE < lim ? base + KB_TILE : lim;
     codes[tid] = codes_g[tid];
-    if (tid == 0) before_tile = base ? T[base - 1] : T[n - 1];
-    __syncthreads();
+    if (hist0) kb_hist_clear(bins);
     const int key_bits = bits * msym;
     const u64 mask = key_bits >= 64 ? ~0ull : ((1ull << key_bits) - 1ull);
 
-    // symbol codes of the tile and its halo; past the end of the text the code is 0.  16 bytes per lane
-    // where the text allows it (tile bases are multiples of 2048, device buffers are 16-byte aligned).
-    const u32 span = (u32)(end - base) + (u32)msym;
-    const bool vec_ok = ((uintptr_t)T & 15) == 0;
-    for (u32 c = tid; c * 16 < span; c += KB_THREADS) {
-        const u64 q0 = base + (u64)c * 16;
-        if (vec_ok && q0 + 16 <= n) {
-            const uint4 v = *(const uint4 *)(T + q0);
-            *(uint4 *)(sraw + c * 16) = v;
-            const u32 w[4] = {v.x, v.y, v.z, v.w};
+    for (int sub = 0; sub < KB_SUB; sub++) {
+        const u64 tile = (u64)blockIdx.x * KB_SUB + (u64)sub;
+        const u64 base = pos0 + tile * KB_TILE;
+        if (base >= lim) break;
+        const u64 end = base + KB_TILE < lim ? base + KB_TILE : lim;
+        __syncthreads();                                // (the previous tile's readers of the LDS arrays are done)
+        if (tid == 0) before_tile = base ? T[base - 1] : T[n - 1];
+
+        // symbol codes of the tile and its halo; past the end of the text the code is 0.  16 bytes per lane
+        // where the text allows it (tile bases are multiples of 2048, device buffers are 16-byte aligned).
+        const u32 span = (u32)(end - base) + (u32)msym;
+        const bool vec_ok = ((uintptr_t)T & 15) == 0;
+        for (u32 c = tid; c * 16 < span; c += KB_THREADS) {
+            const u64 q0 = base + (u64)c * 16;
+            if (vec_ok && q0 + 16 <= n) {
+                const uint4 v = *(const uint4 *)(T + q0);
+                *(uint4 *)(sraw + c * 16) = v;
+                const u32 w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-            for (int a = 0; a < 4; a++)
+                for (int a = 0; a < 4; a++)
 #pragma unroll
-                for (int bb = 0; bb < 4; bb++)
-                    sc[c * 16 + a * 4 + bb] = (u16)((u32)codes[(w[a] >> (8 * bb)) & 255u] + (u32)pad_add);
-        } else {
-            for (int bb = 0; bb < 16; bb++) {
-                const u64 q = q0 + bb;
-                const u8 t = q < n ? T[q] : (u8)0;
-                sraw[c * 16 + bb] = t;
-                sc[c * 16 + bb] = q < n ? (u16)((u32)codes[t] + (u32)pad_add) : (u16)0;
+                    for (int bb = 0; bb < 4; bb++)
+                        sc[c * 16 + a * 4 + bb] = (u16)((u32)codes[(w[a] >> (8 * bb)) & 255u] + (u32)pad_add);
+            } else {
+                for (int bb = 0; bb < 16; bb++) {
+                    const u64 q = q0 + bb;
+                    const u8 t = q < n ? T[q] : (u8)0;
+                    sraw[c * 16 + bb] = t;
+                    sc[c * 16 + bb] = q < n ? (u16)((u32)codes[t] + (u32)pad_add) : (u16)0;
+                }
             }
         }
-    }
-    __syncthreads();
-    const u32 o = (u32)tid * KB_ITEMS;
-    u64 lo = ~0ull;
-    if (base + o < end) {
-        u64 key = 0;
-        for (int j = 0; j < msym; j++) key = (key << bits) | sc[o + j];
+        __syncthreads();
+        const u32 o = (u32)tid * KB_ITEMS;
+        u64 lo = ~0ull;
+        if (base + o < end) {
+            u64 key = 0;
+            for (int j = 0; j < msym; j++) key = (key << bits) | sc[o + j];
 #pragma unroll
-        for (int e = 0; e < KB_ITEMS; e++) {
-            if (base + o + e < end) {
-                skey[o + e + ((o + e) >> 3)] = key;
-                lo = key < lo ? key : lo;
-                key = ((key << bits) | sc[o + e + msym]) & mask;   // stays inside the loaded span / halo
+            for (int e = 0; e < KB_ITEMS; e++) {
+                if (base + o + e < end) {
+                    skey[o + e + ((o + e) >> 3)] = key;
+                    lo = key < lo ? key : lo;
+                    key = ((key << bits) | sc[o + e + msym]) & mask;   // stays inside the loaded span / halo
+                }
             }
         }
-    }
-    if (tile_min) {
-        lo = wave_scan_inclusive(lo, OpMin());
-        if (lane_id() == 63) wmin[wave_id()] = lo;
-    }
-    __syncthreads();
-    // lane-consecutive (coalesced) key stores
+        if (tile_min) {
+            lo = wave_scan_inclusive(lo, OpMin());
+            if (lane_id() == 63) wmin[wave_id()] = lo;
+        }
+        __syncthreads();
+        // lane-consecutive (coalesced) key stores
 #pragma unroll
-    for (int j = 0; j < KB_ITEMS; j++) {
-        const u32 e = (u32)j * KB_THREADS + tid;
-        if (base + e < end) {
-            const u64 q = base + e;
-            const u32 prev = e ? (u32)sraw[e - 1] : (u32)before_tile;          // T[q - 1], from the tile already in LDS
-            ks_store_with_prev(keys, q - pos0, skey[e + (e >> 3)], prev);
+        for (int j = 0; j < KB_ITEMS; j++) {
+            const u32 e = (u32)j * KB_THREADS + tid;
+            const bool valid = base + e < end;
+            u64 key = 0;
+            if (valid) {
+                const u64 q = base + e;
+                key = skey[e + (e >> 3)];
+                const u32 prev = e ? (u32)sraw[e - 1] : (u32)before_tile;          // T[q - 1], from the tile already in LDS
+                ks_store_with_prev(keys, q - pos0, key, prev);
+            }
+            if (hist0) hist_add_runs(bins[wave_id()], (u32)key & 255u, valid);
+        }
+        // smallest key of the tile: the Lyndon candidate search starts from these (same tile size as the scan)
+        if (tile_min && tid == 0) {
+            u64 t = wmin[0];
+            for (int w = 1; w < KB_THREADS / 64; w++) t = wmin[w] < t ? wmin[w] : t;
+            tile_min[tile] = t;
         }
     }
-    // smallest key of the tile: the Lyndon candidate search starts from these (same tile size as the scan)
-    if (tile_min && tid == 0) {
-        u64 t = wmin[0];
-        for (int w = 1; w < KB_THREADS / 64; w++) t = wmin[w] < t ? wmin[w] : t;
-        tile_min[blockIdx.x] = t;
-    }
+    if (hist0) kb_hist_flush(bins, hist0);
 }
 
 // ---- variable-length codes -------------------------------------------------------------------------------------
@@ -570,7 +602,8 @@ __global__ __launch_bounds__(256) void count_prefix_matches_kernel(const u64 *__
 #define KB_SYM_PER   ((KB_SYMS + KB_THREADS - 1) / KB_THREADS)      // symbols a thread lays out: 9
 #define KB_BS_WORDS  ((KB_SYMS * VL_MAXLEN + 31) / 32 + 4)   // stream words incl. zero padding for the last windows
 __global__ __launch_bounds__(KB_THREADS) void keybuild0v_kernel(const u8 *__restrict__ T, u64 n, const u64 *__restrict__ vtab_g,
-                                                                int key_bits, KeyStore keys, u64 *__restrict__ tile_min, u64 pos0, u64 lim)
+                                                                int key_bits, KeyStore keys, u64 *__restrict__ tile_min, u64 pos0, u64 lim,
+                                                                u32 *__restrict__ hist0)
 {
     __shared__ u64 vtab[256];
     __shared__ __attribute__((aligned(16))) u8 sb[KB_SYMS + 16];
@@ -579,92 +612,118 @@ __global__ __launch_bounds__(KB_THREADS) void keybuild0v_kernel(const u8 *__rest
     __shared__ u64 wmin[KB_THREADS / 64];
     __shared__ u32 scan_sm[KB_THREADS / 64];
     __shared__ u8 before_tile;                      // T[base - 1]: the carried byte of the tile's first position
+    __shared__ u32 bins[KB_THREADS / 64][256];      // hist0: per-wave counts of the keys' bits 0..7
 
     const int tid = threadIdx.x;
-    const u64 base = pos0 + (u64)blockIdx.x * KB_TILE;
-    const u64 end = base + KB_TILE < lim ? base + KB_TILE : lim;
     vtab[tid] = vtab_g[tid];
-    if (tid == 0) before_tile = base ? T[base - 1] : T[n - 1];
-    const u32 span = KB_SYMS;
-    const u64 avail = n - base;                                 // symbols of the text from the tile's start
-    const u32 nvalid = avail < span ? (u32)avail : span;
-    const bool vec_ok = ((uintptr_t)T & 15) == 0;
-    for (u32 c = tid; c * 16 < span; c += KB_THREADS) {
-        const u64 q0 = base + (u64)c * 16;
-        if (vec_ok && q0 + 16 <= n) {
-            *(uint4 *)(sb + c * 16) = *(const uint4 *)(T + q0);
-        } else {
-            for (int bb = 0; bb < 16; bb++) sb[c * 16 + bb] = q0 + bb < n ? T[q0 + bb] : (u8)0;
-        }
-    }
-    for (u32 i = tid; i < KB_BS_WORDS; i += KB_THREADS) bs[i] = 0;
-    __syncthreads();
-
-    // lay out symbols [s0, s0 + KB_SYM_PER)
-    const u32 s0 = (u32)tid * KB_SYM_PER;
-    u32 ent_len[KB_SYM_PER], ent_code[KB_SYM_PER];
-    u32 mine = 0;
-#pragma unroll
-    for (int i = 0; i < KB_SYM_PER; i++) {
-        const u32 sidx = s0 + i;
-        u64 ent = 0;
-        if (sidx < nvalid) ent = vtab[sb[sidx]];            // past the text (or past the halo): length 0
-        ent_len[i] = (u32)(ent >> 32);
-        ent_code[i] = (u32)ent;
-        mine += ent_len[i];
-    }
-    u32 total;
-    u32 off = block_scan_exclusive<u32, OpAdd, KB_THREADS / 64>(mine, OpAdd(), 0u, scan_sm, &total);
-#pragma unroll
-    for (int i = 0; i < KB_SYM_PER; i++) {
-        const u32 sidx = s0 + i;
-        if (sidx < KB_SYMS) symoff[sidx] = (u16)off;
-        const u32 l = ent_len[i];
-        if (l) {
-            const u32 wd = off >> 5, r = off & 31u;
-            if (r + l <= 32) atomicOr(&bs[wd], ent_code[i] << (32 - r - l));
-            else {
-                atomicOr(&bs[wd], ent_code[i] >> (r + l - 32));
-                atomicOr(&bs[wd + 1], ent_code[i] << (64 - r - l));
+    if (hist0) kb_hist_clear(bins);
+    for (int sub = 0; sub < KB_SUB; sub++) {
+        const u64 tile = (u64)blockIdx.x * KB_SUB + (u64)sub;
+        const u64 base = pos0 + tile * KB_TILE;
+        if (base >= lim) break;
+        const u64 end = base + KB_TILE < lim ? base + KB_TILE : lim;
+        __syncthreads();                                // (the previous tile's readers of the LDS arrays are done)
+        if (tid == 0) before_tile = base ? T[base - 1] : T[n - 1];
+        const u32 span = KB_SYMS;
+        const u64 avail = n - base;                                 // symbols of the text from the tile's start
+        const u32 nvalid = avail < span ? (u32)avail : span;
+        const bool vec_ok = ((uintptr_t)T & 15) == 0;
+        for (u32 c = tid; c * 16 < span; c += KB_THREADS) {
+            const u64 q0 = base + (u64)c * 16;
+            if (vec_ok && q0 + 16 <= n) {
+                *(uint4 *)(sb + c * 16) = *(const uint4 *)(T + q0);
+            } else {
+                for (int bb = 0; bb < 16; bb++) sb[c * 16 + bb] = q0 + bb < n ? T[q0 + bb] : (u8)0;
             }
         }
-        off += l;
-    }
-    __syncthreads();
-
-    // keys, lane-consecutive over the tile's positions (any thread can cut any position's window out of the stream):
-    // coalesced stores straight from registers
-    u64 lo = ~0ull;
-#pragma unroll
-    for (int j = 0; j < KB_ITEMS; j++) {
-        const u32 e = (u32)j * KB_THREADS + tid;
-        if (base + e < end) {
-            const u32 bo = symoff[e];
-            const u32 wd = bo >> 5, r = bo & 31u;
-            const u64 hi64 = ((u64)bs[wd] << 32) | (u64)bs[wd + 1];
-            const u64 win = r ? (hi64 << r) | ((u64)bs[wd + 2] >> (32 - r)) : hi64;      // 64 stream bits from bo
-            const u64 key = win >> (64 - key_bits);
-            lo = key < lo ? key : lo;
-            const u32 prev = e ? (u32)sb[e - 1] : (u32)before_tile;            // T[q - 1], from the tile already in LDS
-            ks_store_with_prev(keys, base + e - pos0, key, prev);
-        }
-    }
-    if (tile_min) {
-        lo = wave_scan_inclusive(lo, OpMin());
-        if (lane_id() == 63) wmin[wave_id()] = lo;
+        for (u32 i = tid; i < KB_BS_WORDS; i += KB_THREADS) bs[i] = 0;
         __syncthreads();
-        // smallest key of the tile: the Lyndon candidate search starts from these (same tile size as the scan)
-        if (tid == 0) {
-            u64 t = wmin[0];
-            for (int w = 1; w < KB_THREADS / 64; w++) t = wmin[w] < t ? wmin[w] : t;
-            tile_min[blockIdx.x] = t;
+
+        // lay out symbols [s0, s0 + KB_SYM_PER)
+        const u32 s0 = (u32)tid * KB_SYM_PER;
+        u32 ent_len[KB_SYM_PER], ent_code[KB_SYM_PER];
+        u32 mine = 0;
+#pragma unroll
+        for (int i = 0; i < KB_SYM_PER; i++) {
+            const u32 sidx = s0 + i;
+            u64 ent = 0;
+            if (sidx < nvalid) ent = vtab[sb[sidx]];            // past the text (or past the halo): length 0
+            ent_len[i] = (u32)(ent >> 32);
+            ent_code[i] = (u32)ent;
+            mine += ent_len[i];
+        }
+        u32 total;
+        u32 off = block_scan_exclusive<u32, OpAdd, KB_THREADS / 64>(mine, OpAdd(), 0u, scan_sm, &total);
+#pragma unroll
+        for (int i = 0; i < KB_SYM_PER; i++) {
+            const u32 sidx = s0 + i;
+            if (sidx < KB_SYMS) symoff[sidx] = (u16)off;
+            const u32 l = ent_len[i];
+            if (l) {
+                const u32 wd = off >> 5, r = off & 31u;
+                if (r + l <= 32) atomicOr(&bs[wd], ent_code[i] << (32 - r - l));
+                else {
+                    atomicOr(&bs[wd], ent_code[i] >> (r + l - 32));
+                    atomicOr(&bs[wd + 1], ent_code[i] << (64 - r - l));
+                }
+            }
+            off += l;
+        }
+        __syncthreads();
+
+        // keys, lane-consecutive over the tile's positions (any thread can cut any position's window out of the stream):
+        // coalesced stores straight from registers
+        u64 lo = ~0ull;
+#pragma unroll
+        for (int j = 0; j < KB_ITEMS; j++) {
+            const u32 e = (u32)j * KB_THREADS + tid;
+            const bool valid = base + e < end;
+            u64 key = 0;
+            if (valid) {
+                const u32 bo = symoff[e];
+                const u32 wd = bo >> 5, r = bo & 31u;
+                const u64 hi64 = ((u64)bs[wd] << 32) | (u64)bs[wd + 1];
+                const u64 win = r ? (hi64 << r) | ((u64)bs[wd + 2] >> (32 - r)) : hi64;      // 64 stream bits from bo
+                key = win >> (64 - key_bits);
+                lo = key < lo ? key : lo;
+                const u32 prev = e ? (u32)sb[e - 1] : (u32)before_tile;            // T[q - 1], from the tile already in LDS
+                ks_store_with_prev(keys, base + e - pos0, key, prev);
+            }
+            if (hist0) hist_add_runs(bins[wave_id()], (u32)key & 255u, valid);
+        }
+        if (tile_min) {
+            lo = wave_scan_inclusive(lo, OpMin());
+            if (lane_id() == 63) wmin[wave_id()] = lo;
+            __syncthreads();
+            // smallest key of the tile: the Lyndon candidate search starts from these (same tile size as the scan)
+            if (tid == 0) {
+                u64 t = wmin[0];
+                for (int w = 1; w < KB_THREADS / 64; w++) t = wmin[w] < t ? wmin[w] : t;
+                tile_min[tile] = t;
+            }
         }
     }
+    if (hist0) kb_hist_flush(bins, hist0);
+}
+
+// A patch rewrites a key the key builder counted into the first radix pass's table (hist0, may be null): the count moves from
+// the old key's bits 0..7 to the new one's.  (Every position is rewritten at most once, so the old key is the counted one.)
+__device__ __forceinline__ void ks_patch(const KeyStore &ks, u64 p, u64 key, u32 *__restrict__ hist0)
+{
+    if (hist0) {
+        const u32 od = (u32)ks_load(ks, p) & 255u, nd = (u32)key & 255u;
+        if (od != nd) {
+            u32 *row = hist0 + p / KB_RX_TILE * 256;
+            atomicSub(&row[od], 1u);
+            atomicAdd(&row[nd], 1u);
+        }
+    }
+    ks_store(ks, p, key);
 }
 
 // keys of the (up to 64) positions in front of each factor end wrap around inside the factor
 __global__ __launch_bounds__(256) void cyclic_patch_vl_kernel(const u8 *__restrict__ T, u64 n, const u64 *__restrict__ vtab, int key_bits,
-                                                              const u32 *__restrict__ fstart, u64 k, KeyStore keys)
+                                                              const u32 *__restrict__ fstart, u64 k, KeyStore keys, u32 *__restrict__ hist0)
 {
     const u64 t = (u64)blockIdx.x * 256 + threadIdx.x;
     if (t >= k * 64) return;
@@ -672,7 +731,7 @@ __global__ __launch_bounds__(256) void cyclic_patch_vl_kernel(const u8 *__restri
     const u64 s = fstart[f], e = factor_end(fstart, k, n, f);
     if (j >= e - s) return;
     const u64 p = e - 1 - j;
-    ks_store(keys, p, vl_key_cyclic(T, vtab, key_bits, p, s, e));
+    ks_patch(keys, p, vl_key_cyclic(T, vtab, key_bits, p, s, e), hist0);
 }
 
 // first msym symbols of rot(p)^omega for a position of factor [s, e)
@@ -690,7 +749,7 @@ __device__ __forceinline__ u64 cyclic_key(const u8 *__restrict__ T, const u8 *__
 // positions closer than msym to their factor's end wrap around: rewrite their round-0 keys
 __global__ __launch_bounds__(256) void cyclic_patch_kernel(const u8 *__restrict__ T, u64 n, const u8 *__restrict__ codes,
                                                            int bits, int msym, const u32 *__restrict__ fstart, u64 k,
-                                                           KeyStore keys)
+                                                           KeyStore keys, u32 *__restrict__ hist0)
 {
     const u64 t = (u64)blockIdx.x * 256 + threadIdx.x;
     const u64 per = (u64)(msym - 1);
@@ -699,7 +758,7 @@ __global__ __launch_bounds__(256) void cyclic_patch_kernel(const u8 *__restrict_
     const u64 s = fstart[f], e = factor_end(fstart, k, n, f);
     if (j >= e - s) return;
     const u64 p = e - 1 - j;
-    ks_store(keys, p, cyclic_key(T, codes, bits, msym, p, s, e));
+    ks_patch(keys, p, cyclic_key(T, codes, bits, msym, p, s, e), hist0);
 }
 
 // ------------------------------------------------------------------------------------
@@ -750,7 +809,14 @@ __global__ __launch_bounds__(256) void tpos_directory_kernel(const u32 *__restri
     }
     pdir[k] = (u32)lo;
 }
-__global__ __launch_bounds__(256) void k0_directory_kernel(const u64 *__restrict__ K0, u64 n, int key_bits, int dlog, u64 *__restrict__ dir)
+// The sorted round-0 keys: u64 each, or split as the packed passes leave them (SortPlan::keys_split) -- u32 low words, and for keys
+// of more than 32 bits their bits 32..39 in a byte array of their own (hi; null for keys of <= 32 bits).
+struct K0Keys {
+    const u64 *wide; const u32 *lo; const u8 *hi;
+    __device__ __forceinline__ u64 at(u64 i) const { return wide ? wide[i] : ((u64)lo[i] | (hi ? (u64)hi[i] << 32 : 0ull)); }
+    __device__ __forceinline__ u32 low(u64 i) const { return wide ? (u32)wide[i] : lo[i]; }
+};
+__global__ __launch_bounds__(256) void k0_directory_kernel(const K0Keys K0, u64 n, int key_bits, int dlog, u64 *__restrict__ dir)
 {
     const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
     if (k > (1ull << dlog)) return;
@@ -759,15 +825,20 @@ __global__ __launch_bounds__(256) void k0_directory_kernel(const u64 *__restrict
     u64 lo = 0, hi = n;
     while (lo < hi) {
         const u64 mid = (lo + hi) >> 1;
-        if (K0[mid] < want) lo = mid + 1; else hi = mid;
+        if (K0.at(mid) < want) lo = mid + 1; else hi = mid;
     }
     dir[k] = lo;
 }
-__device__ __forceinline__ u64 k0_lower_bound(const u64 *__restrict__ K0, u64 n, u64 want, const u64 *__restrict__ dir, int dlog, int key_bits)
+// Inside a directory bucket every key has want's top dlog bits; when those include all bits above 32 (key_bits - dlog <= 32) the
+// low words alone decide, and a probe of split keys stays one random read.
+__device__ __forceinline__ u64 k0_lower_bound(const K0Keys &K0, u64 n, u64 want, const u64 *__restrict__ dir, int dlog, int key_bits)
 {
     u64 lo = 0, hi = n;
+    bool low_only = false;
+    auto below = [&](u64 p) { return low_only ? K0.low(p) < (u32)want : K0.at(p) < want; };
     if (dir) {
         const int sh = key_bits - dlog;
+        low_only = !K0.wide && sh <= 32;
         const u64 k = want >> sh;
         lo = dir[k]; hi = dir[k + 1];
         if (lo == hi) return lo;
@@ -777,26 +848,26 @@ __device__ __forceinline__ u64 k0_lower_bound(const u64 *__restrict__ K0, u64 n,
             g = lo + (u64)(frac * (double)(hi - lo));
         }
         if (g >= hi) g = hi - 1;
-        if (K0[g] < want) {                     // the answer lies in (g, hi]
+        if (below(g)) {                         // the answer lies in (g, hi]
             lo = g + 1;
             for (u64 st = 1; lo < hi; st <<= 1) {
                 const u64 p = g + st;
                 if (p >= hi) break;
-                if (K0[p] < want) lo = p + 1; else { hi = p; break; }
+                if (below(p)) lo = p + 1; else { hi = p; break; }
             }
         } else {                                // the answer lies in [lo, g]
             hi = g;
             for (u64 st = 1; lo < hi; st <<= 1) {
                 if (st > g - lo) break;
                 const u64 p = g - st;
-                if (K0[p] < want) { lo = p + 1; break; }
+                if (below(p)) { lo = p + 1; break; }
                 hi = p;
             }
         }
     }
     while (lo < hi) {
         const u64 mid = (lo + hi) >> 1;
-        if (K0[mid] < want) lo = mid + 1; else hi = mid;
+        if (below(mid)) lo = mid + 1; else hi = mid;
     }
     return lo;
 }
@@ -804,7 +875,7 @@ __device__ __forceinline__ u64 k0_lower_bound(const u64 *__restrict__ K0, u64 n,
 template <bool CYCLIC>
 __global__ __launch_bounds__(256) void keybuild_sparse_kernel(const u32 *__restrict__ a_idx, const u32 *__restrict__ a_head, u64 a,
                                                               const u8 *__restrict__ T, u64 n, const u8 *__restrict__ codes,
-                                                              int bits, int msym, int pad_add, u64 h, const u64 *__restrict__ K0, int rb,
+                                                              int bits, int msym, int pad_add, u64 h, const K0Keys K0, int rb,
                                                               const u32 *__restrict__ fstart, u64 k, u64 *__restrict__ keys,
                                                               const u64 *__restrict__ vtab /* variable-length codes, or null */, int key_bits,
                                                               const u32 *__restrict__ tpos, const u32 *__restrict__ trank, u64 a0,
@@ -964,8 +1035,19 @@ struct GroupOut {
 // the left neighbour's key is fetched (DPP wave_shr:1 on the two halves; lane 0 takes the word before's lane 63 from a scalar), and
 // "last of its group" is the start mask shifted by one, as scalar arithmetic on the ballot words.  (The first version brought both
 // neighbours through the LDS crossbar, eight ds_bpermute per element: 2.45 ms at 2^30 where the keys stream in 1.7.)
-__global__ __launch_bounds__(256) void group_flags_kernel(const u64 *__restrict__ K, u64 n, u64 *__restrict__ headw, u64 *__restrict__ keepw,
-                                                          u64 mask = ~0ull /* key bits that count (the 64-bit path parks position bits above them) */)
+// The keys come through a loader: GfWide (u64 keys; mask = the key bits that count -- the 64-bit path parks position bits above
+// them) or GfSplit (the split form of the packed round-0 sort, K0Keys: 5 or 4 bytes per slot instead of 8).
+struct GfWide {
+    const u64 *k; u64 mask;
+    __device__ __forceinline__ u64 operator()(u64 i) const { return k[i] & mask; }
+};
+template <bool HI>
+struct GfSplit {
+    const u32 *lo; const u8 *hi;
+    __device__ __forceinline__ u64 operator()(u64 i) const { return (u64)lo[i] | (HI ? (u64)hi[i] << 32 : 0ull); }
+};
+template <class KL>
+__global__ __launch_bounds__(256) void group_flags_kernel(const KL K, u64 n, u64 *__restrict__ headw, u64 *__restrict__ keepw)
 {
     const int lane = lane_id();
     const u64 words = (n + 63) / 64;
@@ -978,11 +1060,11 @@ __global__ __launch_bounds__(256) void group_flags_kernel(const u64 *__restrict_
 #pragma unroll
         for (int q = 0; q < GF_WORDS; q++) {
             const u64 i = (w0 + q) * 64 + lane;
-            k[q] = K[i < n ? i : n - 1] & mask;
+            k[q] = K(i < n ? i : n - 1);
         }
         const u64 first = w0 * 64, after = (w0 + GF_WORDS) * 64;          // the chunk's outer neighbours: slots first - 1 and after
-        const u64 before_key = K[first > 0 ? first - 1 : 0] & mask;          // (uniform addresses: scalar loads)
-        const u64 after_key = K[after < n ? after : n - 1] & mask;
+        const u64 before_key = K(first > 0 ? first - 1 : 0);                 // (uniform addresses: scalar loads)
+        const u64 after_key = K(after < n ? after : n - 1);
         u64 hm[GF_WORDS], vm[GF_WORDS];        // per word: slots that start a group (slots past the end count as starts), valid slots
         u64 prev63 = before_key;
 #pragma unroll
@@ -1098,6 +1180,10 @@ struct SortSpace {
     u64 tie_count = 0;
     // the cyclic sort will carry the byte stream (=> the packed passes may apply); keys[0] currently holds split keys
     bool want_split = false, split_keys = false;
+    // split keys only, may be null: the first packed pass's table as the key builder counted it (SortPlan::first_hist).  It lives in
+    // vals[0]: round 0's values are the identity, which the first pass does not read, and nothing else uses vals[0] before that
+    // pass has scanned the table.
+    u32 *first_hist = nullptr;
     // set by the sort when the later rounds wrote the bytes of the tied elements themselves (dense rounds)
     bool ties_emitted = false;
 };
@@ -1310,12 +1396,15 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
     plan.sym_src = sp.carry_src; plan.sym_buf[0] = sp.carry_buf[0]; plan.sym_buf[1] = sp.carry_buf[1]; plan.sym_final = sp.carry_out;
     plan.vals_identity = true;     // keybuild0 writes no value array
     plan.keys_split = CYCLIC && sp.split_keys && plan.sym_final;
+    plan.first_hist = plan.keys_split ? sp.first_hist : nullptr;
     if (CYCLIC && sp.split_keys && !plan.keys_split) return BWTS_E_INTERNAL;      // keybuild split the keys for a sort that cannot take them
     int res = 0;
     STAGE("cyclic patch (before round 0)");
     BWTS_TRY(radix_sort_pairs(ctx, plan, n, al.key_bits, &res));
     STAGE("round-0 sort");
     u64 *K0 = sp.keys[res];
+    K0Keys k0v{K0, nullptr, nullptr};
+    if (plan.keys_split) k0v = K0Keys{nullptr, (const u32 *)K0, al.key_bits > 32 ? (const u8 *)K0 + align_up((size_t)n * 4, 256) : nullptr};
     u32 *SA = sp.vals[res];
     // the other key buffer (8n bytes) and value buffer (4n) are free: first active list goes there
     ActiveList cur;
@@ -1328,7 +1417,7 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
     u64 *headw, *keepw, *pre;
     const bool flags_outside_rank = sp.carry_buf[0] && sp.carry_buf[1] && n >= 4096;
     {
-        SpanGuard g(ctx, BWTS_K_RERANK, n, 8 * n);
+        SpanGuard g(ctx, BWTS_K_RERANK, n, (k0v.wide ? 8 : k0v.hi ? 5 : 4) * n);
         // flags and word prefixes (3 * n/8 bytes): in the carried-byte ping-pong buffers when there are any (free once the
         // sort is done), else in sp.rank, which is not needed before the rounds that follow
         if (flags_outside_rank) {
@@ -1339,7 +1428,9 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
         }
         u64 waves = (words + GF_WORDS - 1) / GF_WORDS;
         unsigned blocks = (unsigned)((waves + 3) / 4 < 16384 ? (waves + 3) / 4 : 16384);
-        group_flags_kernel<<<dim3(blocks), dim3(256), 0, ctx->stream>>>(K0, n, headw, keepw);
+        if (k0v.wide) group_flags_kernel<GfWide><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(GfWide{K0, ~0ull}, n, headw, keepw);
+        else if (k0v.hi) group_flags_kernel<GfSplit<true>><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(GfSplit<true>{k0v.lo, k0v.hi}, n, headw, keepw);
+        else group_flags_kernel<GfSplit<false>><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(GfSplit<false>{k0v.lo, nullptr}, n, headw, keepw);
         WordIn in{headw, keepw};
         ScanStoreArr<u64> out{pre};
         BWTS_TRY((device_scan<false, u64>(ctx, words, in, out, OpHeadCount(), (u64)0, sp.scan_temp)));
@@ -1426,8 +1517,10 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
             if (dlog > bitlen_u64(n)) dlog = bitlen_u64(n);
             if (dlog >= 8) {
                 dir = (u64 *)(base + 2 * e8 + 9 * e4);
-                k0_directory_kernel<<<dim3((unsigned)(((1ull << dlog) + 1 + 255) / 256)), dim3(256), 0, ctx->stream>>>(K0, n, kb, dlog, dir);
+                k0_directory_kernel<<<dim3((unsigned)(((1ull << dlog) + 1 + 255) / 256)), dim3(256), 0, ctx->stream>>>(k0v, n, kb, dlog, dir);
             }
+            // split keys with a high byte: the rank searches compare low words alone (k0_lower_bound)
+            if (k0v.hi && (!dir || kb - dlog > 32)) return BWTS_E_INTERNAL;
             tied_map_keys_kernel<<<dim3((unsigned)((a + 255) / 256)), dim3(256), 0, ctx->stream>>>(cur.idx, a, akeys[0]);
             HIPC(hipMemcpyAsync(scratch, cur.head, a * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
             SortPlan mp;
@@ -1472,7 +1565,7 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
                 SpanGuard g(ctx, BWTS_K_KEYBUILD, a, 20 * a);
                 const unsigned blocks = (unsigned)((a + 255) / 256);
                 keybuild_sparse_kernel<CYCLIC><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(
-                    cur.idx, cur.head, a, d_T, n, d_codes, al.bits, al.msym, al.pad_add, h, K0, rb, d_fstart, k, akeys[0],
+                    cur.idx, cur.head, a, d_T, n, d_codes, al.bits, al.msym, al.pad_add, h, k0v, rb, d_fstart, k, akeys[0],
                     al.varlen ? ctx->d_small + SM_VTAB : nullptr, al.key_bits, tpos, trank, a0, dir, dlog, pdir, psh);
                 HIPC(hipGetLastError());
             }
@@ -1576,27 +1669,30 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
 static_assert(KB_TILE == SCAN_TILE, "keybuild0's tile minima feed the scan's final sweep");
 
 // keys of positions [pos0, pos0 + count) into keys0 (index q - pos0), tile minima into tile_min[0 ..)
+// hist0 (may be null; pos0 = 0 only): the first packed radix pass's table (SortPlan::first_hist)
 static int launch_keybuild0_seg(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, u64 *keys0, u64 *tile_min, bool split, u64 pos0, u64 count,
-                                u8 *wprev = nullptr /* wide keys only: T[q - 1] of every position beside its key */)
+                                u8 *wprev = nullptr /* wide keys only: T[q - 1] of every position beside its key */, u32 *hist0 = nullptr)
 {
+    if (hist0 && (pos0 != 0 || !split)) return BWTS_E_INTERNAL;
     SpanGuard g(ctx, BWTS_K_KEYBUILD, count, count + (split ? 5 : 8) * count);
-    const u64 blocks = (count + KB_TILE - 1) / KB_TILE;
+    const u64 blocks = (count + KB_RX_TILE - 1) / KB_RX_TILE;
     KeyStore ks = key_store_of(keys0, count, split, al.key_bits);
     ks.wprev = split ? nullptr : wprev;
     if (al.varlen) {
         keybuild0v_kernel<<<dim3((unsigned)blocks), dim3(KB_THREADS), 0, ctx->stream>>>(d_T, n, ctx->d_small + SM_VTAB, al.key_bits,
-                                                                                        ks, tile_min, pos0, pos0 + count);
+                                                                                        ks, tile_min, pos0, pos0 + count, hist0);
         HIPC(hipGetLastError());
         return BWTS_OK;
     }
     keybuild0_kernel<<<dim3((unsigned)blocks), dim3(KB_THREADS), 0, ctx->stream>>>(
-        d_T, n, (const u8 *)(ctx->d_small + SM_CODES), al.bits, al.msym, al.pad_add, ks, tile_min, pos0, pos0 + count);
+        d_T, n, (const u8 *)(ctx->d_small + SM_CODES), al.bits, al.msym, al.pad_add, ks, tile_min, pos0, pos0 + count, hist0);
     HIPC(hipGetLastError());
     return BWTS_OK;
 }
-static int launch_keybuild0(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, SortSpace &sp, u64 *tile_min, bool split)
+static int launch_keybuild0(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, SortSpace &sp, u64 *tile_min, bool split,
+                            u32 *hist0 = nullptr)
 {
-    return launch_keybuild0_seg(ctx, d_T, n, al, sp.keys[0], tile_min, split, 0, n);
+    return launch_keybuild0_seg(ctx, d_T, n, al, sp.keys[0], tile_min, split, 0, n, nullptr, hist0);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1975,7 +2071,8 @@ static int factors_and_keys(bwts_ctx *ctx, const u8 *d_T, u64 n, SortSpace &sp, 
         BWTS_TRY(set_alphabet(ctx, false, n, al, &ss));
         sp.split_keys = sp.want_split && radix_packed_applicable(ctx, n, al->key_bits);
         STAGE("histogram + alphabet");
-        BWTS_TRY(launch_keybuild0(ctx, d_T, n, *al, sp, tile_min, sp.split_keys));
+        if (sp.split_keys && radix_tile_hist_bytes(n) <= (size_t)n * 4) sp.first_hist = sp.vals[0];
+        BWTS_TRY(launch_keybuild0(ctx, d_T, n, *al, sp, tile_min, sp.split_keys, sp.first_hist));
         STAGE("keybuild0");
         BWTS_TRY(lyndon_fast(ctx, d_T, n, *al, sp, tile_min, cand, cvals, fast_starts, k_out, &done));
         STAGE("lyndon_fast");
@@ -1983,6 +2080,7 @@ static int factors_and_keys(bwts_ctx *ctx, const u8 *d_T, u64 n, SortSpace &sp, 
         else if (mode == 1) return BWTS_E_INTERNAL;
     }
     if (!done) {
+        sp.first_hist = nullptr;           // (the general path's suffix sort uses vals[0]; its key build below counts nothing)
         BWTS_TRY(lyndon_general(ctx, d_T, n, sp, d_fstart, k_out, lyndon_rounds));
         SampleScratch ss{d_T, {sp.keys[0], sp.keys[1]}, {sp.vals[0], sp.vals[1]}, sp.tile_hist, sp.scan_temp};
         BWTS_TRY(set_alphabet(ctx, false, n, al, &ss));
@@ -2000,13 +2098,13 @@ static int factors_and_keys(bwts_ctx *ctx, const u8 *d_T, u64 n, SortSpace &sp, 
         SpanGuard g(ctx, BWTS_K_KEYBUILD, *k_out * 64, 0);
         const u64 threads = *k_out * 64;
         cyclic_patch_vl_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream>>>(
-            d_T, n, ctx->d_small + SM_VTAB, al->key_bits, *d_fstart, *k_out, ks);
+            d_T, n, ctx->d_small + SM_VTAB, al->key_bits, *d_fstart, *k_out, ks, sp.first_hist);
         HIPC(hipGetLastError());
     } else if (al->msym > 1) {
         SpanGuard g(ctx, BWTS_K_KEYBUILD, *k_out * (u64)(al->msym - 1), 0);
         const u64 threads = *k_out * (u64)(al->msym - 1);
         cyclic_patch_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream>>>(
-            d_T, n, (const u8 *)(ctx->d_small + SM_CODES), al->bits, al->msym, *d_fstart, *k_out, ks);
+            d_T, n, (const u8 *)(ctx->d_small + SM_CODES), al->bits, al->msym, *d_fstart, *k_out, ks, sp.first_hist);
         HIPC(hipGetLastError());
     }
     return BWTS_OK;

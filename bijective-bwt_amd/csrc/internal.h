@@ -203,8 +203,12 @@ struct SortPlan {
     bool vals_identity = false;      // vals[0] is not read: the first pass uses value = element index
     // keys[0] holds the keys split for the packed sort (radix_packed_applicable()): u32 low words at keys[0], and at
     // (u8 *)keys[0] + align_up(4 m, 256) the c stream: u16 (key bits 32..39 | carried byte << 8) for keys of more than 32
-    // bits, else u8 (the carried byte).  sym_src is not read; needs sym_final and vals_identity.
+    // bits, else u8 (the carried byte).  sym_src is not read; needs sym_final and vals_identity.  The sorted keys come out split
+    // too: u32 low words at keys[res], and for keys of more than 32 bits their bits 32..39 as u8 at (u8 *)keys[res] + align_up(4 m, 256).
     bool keys_split = false;
+    // keys_split only, may be null: the first pass's [tile][digit] table (8192-element tiles, digit = key bits 0..7), counted
+    // already, in a block of radix_tile_hist_bytes(m) that no pass writes but the first one's scan; that pass's histogram sweep is skipped
+    u32 *first_hist = nullptr;
 };
 bool radix_packed_applicable(const bwts_ctx *ctx, u64 m, int key_bits);   // will radix_sort_pairs run its packed-stream passes for such a sort?
 size_t radix_tile_hist_bytes(u64 m);

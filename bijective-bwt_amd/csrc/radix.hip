@@ -61,27 +61,6 @@ int exclusive_sum_u32(bwts_ctx *ctx, u32 *data, u64 n, void *temp)
 // ------------------------------------------------------------------------------------
 // pass kernels
 // ------------------------------------------------------------------------------------
-// One wave's 64 consecutive digits into its LDS bins.  Sorted and repetitive input (every pass but the first of a sort over text or
-// over ranks with many equal values) puts runs of equal digits into neighbouring lanes, and same-address LDS atomics are served one
-// lane at a time: a pass over such keys ran at 2.4 TB/s where unsorted keys reach 5.6.  So the lanes of a run elect their first one, and
-// it adds the run's length (valid lanes are a prefix of the wave).  The neighbour's digit comes through DPP (row_shr:1 -- no trip
-// through the LDS crossbar, which cost the 2-byte sweep over random digits 0.15 ms of 0.45); a row's first lane has no neighbour
-// there and starts a run of its own: runs are at most 16 long.
-__device__ __forceinline__ void hist_add_runs(u32 *wave_bins, u32 d, bool valid)
-{
-    const int lane = lane_id();
-    const u32 dprev = (u32)__builtin_amdgcn_update_dpp((int)d, (int)d, 0x111 /* row_shr:1 */, 0xf, 0xf, false);
-    const bool head = valid && ((lane & 15) == 0 || d != dprev);
-    const u64 hm = __ballot(head), vm = __ballot(valid);
-    if (hm == vm) {                              // (no two neighbours alike -- three waves in four on random digits: nothing to add up)
-        if (valid) atomicAdd(&wave_bins[d], 1u);
-    } else if (head) {
-        const u64 above = lane == 63 ? 0ull : hm >> (lane + 1);
-        const u32 next = above ? (u32)lane + (u32)__ffsll((unsigned long long)above) : (u32)__popcll(vm);
-        atomicAdd(&wave_bins[d], next - (u32)lane);
-    }
-}
-
 template <int RX_THREADS, int RX_ITEMS>
 __global__ __launch_bounds__(RX_THREADS) void radix_hist_kernel(const u64 *__restrict__ keys, u64 m, int shift,
                                                                  u32 *__restrict__ tile_hist)
@@ -328,9 +307,11 @@ __global__ __launch_bounds__(RX_THREADS, MINW) void radix_scatter2_kernel(const 
 //     val u32   the position
 //     c   u16   key bits 32..39 | carried byte << 8        (HI16)   -- or u8: the carried byte alone (keys <= 32 bits)
 // = 10 (9) bytes, and a histogram sweep reads only the stream that holds its digit (4 or 2 bytes, not 8).
-// keybuild leaves lo and c in exactly this form (forward.hip, KeyStore), the first pass supplies value = index, and the
-// last pass writes wide keys, so everything downstream sees sorted u64 keys.  Ranking, LDS staging and XCD mapping are those of
-// radix_scatter2_kernel; the LDS tile carries the digit's stream on its first trip and the other two on its second.
+// keybuild leaves lo and c in exactly this form (forward.hip, KeyStore) and counts the first pass's digits while it writes them
+// (SortPlan::first_hist), the first pass supplies value = index, and the last pass leaves the sorted keys split as well: lo, and
+// for keys of more than 32 bits their bits 32..39 as one byte (5 bytes per key instead of a u64's 8; K0Split in forward.hip reads
+// them).  Ranking, LDS staging and XCD mapping are those of radix_scatter2_kernel; the LDS tile carries the digit's stream on its
+// first trip and the other two on its second.
 template <typename T>
 __global__ __launch_bounds__(512) void radix_hist_packed_kernel(const T *__restrict__ src, u64 m, int shift, u32 *__restrict__ tile_hist)
 {
@@ -363,12 +344,13 @@ __global__ __launch_bounds__(512) void radix_hist_packed_kernel(const T *__restr
 struct PackedIO {
     const u32 *lo_in; const void *c_in;                    // c: u16 if HI16 else u8
     const u32 *val_in;                                     // not read by the first pass (value = index)
-    u64 *kout_wide; u8 *sym_out;                           // OUT_WIDE
-    u32 *lo_out; void *c_out;                              // !OUT_WIDE
+    u32 *lo_out;
+    void *c_out;                                           // !LAST
+    u8 *hi_out, *sym_out;                                  // LAST: key bits 32..39 (HI16), carried byte
     u32 *val_out;
 };
 
-template <bool FIRST, bool OUT_WIDE, bool HI16>
+template <bool FIRST, bool LAST, bool HI16>
 __global__ __launch_bounds__(512, 4) void radix_scatter_packed_kernel(PackedIO io, const u32 *__restrict__ tile_off, u64 m, int shift)
 {
     constexpr int RX_THREADS = 512, RX_ITEMS = 16, RX_WAVES = 8, RX_TILE = 8192;
@@ -401,7 +383,7 @@ __global__ __launch_bounds__(512, 4) void radix_scatter_packed_kernel(PackedIO i
     // Only the stream that holds this pass's digit is loaded before the ranking and makes the first LDS trip alone;
     // the other two are loaded while the first trip is written out and share the second trip.
     // With 40-bit keys the fifth (= last) pass sorts by the byte that travels in c.
-    constexpr bool DIG_C = HI16 && OUT_WIDE;
+    constexpr bool DIG_C = HI16 && LAST;
     u32 dsrc[RX_ITEMS];
     u32 posp[RX_ITEMS / 2];
     {
@@ -511,7 +493,6 @@ __global__ __launch_bounds__(512, 4) void radix_scatter_packed_kernel(PackedIO i
             if (s < tile_count) {
                 const u32 dst = g[jj] + s;
                 if (DIG_C) io.sym_out[dst] = (u8)(x[jj] >> 8);
-                else if (OUT_WIDE) io.kout_wide[dst] = (u64)x[jj];
                 else io.lo_out[dst] = x[jj];
             }
         }
@@ -548,11 +529,12 @@ __global__ __launch_bounds__(512, 4) void radix_scatter_packed_kernel(PackedIO i
             if (s < tile_count) {
                 const u32 dst = g[jj] + s;
                 if (DIG_C) {
-                    io.kout_wide[dst] = (u64)e[jj].x | ((u64)hi_s[j0 + jj] << 32);
+                    io.lo_out[dst] = e[jj].x;
+                    io.hi_out[dst] = (u8)hi_s[j0 + jj];
                     io.val_out[dst] = e[jj].y;
                 } else {
                     io.val_out[dst] = e[jj].x;
-                    if (OUT_WIDE) io.sym_out[dst] = (u8)e[jj].y;
+                    if (LAST) io.sym_out[dst] = (u8)e[jj].y;
                     else if (HI16) ((u16 *)io.c_out)[dst] = (u16)e[jj].y;
                     else ((u8 *)io.c_out)[dst] = (u8)e[jj].y;
                 }
@@ -566,21 +548,20 @@ __global__ __launch_bounds__(512, 4) void radix_scatter_packed_kernel(PackedIO i
 }
 
 #define RX_PACKED_LDS ((size_t)8192 * 9 + 2048 + 64 + (size_t)8 * 512)
-template <bool FIRST, bool OUT_WIDE, bool HI16>
+template <bool FIRST, bool LAST, bool HI16>
 static int launch_scatter_packed(bwts_ctx *ctx, u64 tiles, const PackedIO &io, const u32 *tile_off, u64 m, int shift)
 {
     constexpr size_t lds = RX_PACKED_LDS;
-    BWTS_TRY(ensure_dyn_lds(ctx, (const void *)radix_scatter_packed_kernel<FIRST, OUT_WIDE, HI16>, lds));
-    radix_scatter_packed_kernel<FIRST, OUT_WIDE, HI16><<<dim3((unsigned)rx_grid(tiles)), dim3(512), lds, ctx->stream>>>(io, tile_off, m, shift);
+    BWTS_TRY(ensure_dyn_lds(ctx, (const void *)radix_scatter_packed_kernel<FIRST, LAST, HI16>, lds));
+    radix_scatter_packed_kernel<FIRST, LAST, HI16><<<dim3((unsigned)rx_grid(tiles)), dim3(512), lds, ctx->stream>>>(io, tile_off, m, shift);
     return BWTS_OK;
 }
 
-// round 0 with the byte stream and identity values, keys of 17..40 bits: split -> packed ... packed -> wide
+// round 0 with the byte stream and identity values, keys of 17..40 bits: split -> packed ... packed -> split
 template <bool HI16>
 static int radix_sort_packed(bwts_ctx *ctx, const SortPlan &plan, u64 m, int passes, int *result_buf)
 {
     const u64 tiles = (m + 8191) / 8192;        // 512 threads x 16 items, two tiles resident per CU
-    u32 *tile_hist = plan.tile_hist;
     const size_t lo_bytes = align_up((size_t)m * 4, 256);
     const u64 pass_bytes = HI16 ? 20 : 18;
     int cur = 0;
@@ -590,9 +571,11 @@ static int radix_sort_packed(bwts_ctx *ctx, const SortPlan &plan, u64 m, int pas
         char *src = (char *)plan.keys[cur], *dst = (char *)plan.keys[cur ^ 1];
         PackedIO io{};
         io.lo_in = (const u32 *)src; io.c_in = src + lo_bytes; io.val_in = plan.vals[cur];
-        io.kout_wide = plan.keys[cur ^ 1]; io.sym_out = plan.sym_final;
         io.lo_out = (u32 *)dst; io.c_out = dst + lo_bytes; io.val_out = plan.vals[cur ^ 1];
-        {
+        io.hi_out = (u8 *)dst + lo_bytes; io.sym_out = plan.sym_final;
+        // the first pass's table may have been counted already (the key builder's)
+        u32 *tile_hist = first && plan.first_hist ? plan.first_hist : plan.tile_hist;
+        if (tile_hist == plan.tile_hist) {
             SpanGuard g(ctx, BWTS_K_RADIX_HIST, m, ((HI16 && shift >= 32) ? 2 : 4) * m);
             if (HI16 && shift >= 32) radix_hist_packed_kernel<u16><<<dim3((unsigned)tiles), dim3(512), 0, ctx->stream>>>((const u16 *)io.c_in, m, 0, tile_hist);
             else radix_hist_packed_kernel<u32><<<dim3((unsigned)tiles), dim3(512), 0, ctx->stream>>>(io.lo_in, m, shift, tile_hist);
@@ -607,7 +590,7 @@ static int radix_sort_packed(bwts_ctx *ctx, const SortPlan &plan, u64 m, int pas
             SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, (pass_bytes / 2 - 4 + pass_bytes / 2) * m);
             BWTS_TRY((launch_scatter_packed<true, false, HI16>(ctx, tiles, io, tile_hist, m, shift)));
         } else if (last) {
-            SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, (pass_bytes / 2 + 13) * m);
+            SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, (pass_bytes / 2 + (HI16 ? 10 : 9)) * m);
             BWTS_TRY((launch_scatter_packed<false, true, HI16>(ctx, tiles, io, tile_hist, m, shift)));
         } else {
             // timed a second time under its own class: the roofline kernel (one template variant, n-sized launches)

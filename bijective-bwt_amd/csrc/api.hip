@@ -1141,11 +1141,10 @@ extern "C" int bwts_debug_sort_pairs(bwts_ctx *ctx, uint64_t *h_keys, uint32_t *
     spans_reset(ctx);
     const size_t need = 2 * align_up(m * 8, 256) + 2 * align_up(m * 4, 256) + radix_tile_hist_bytes(m) + scan_temp_bytes(m) + 4096;
     BWTS_TRY(arena_reserve(ctx, need));
-    SortPlan plan;
-    plan.keys[0] = arena_array<u64>(ctx, m); plan.keys[1] = arena_array<u64>(ctx, m);
-    plan.vals[0] = arena_array<u32>(ctx, m); plan.vals[1] = arena_array<u32>(ctx, m);
-    plan.tile_hist = (u32 *)arena_alloc(ctx, radix_tile_hist_bytes(m));
-    plan.scan_temp = arena_alloc(ctx, scan_temp_bytes(m));
+    u64 *k0 = arena_array<u64>(ctx, m), *k1 = arena_array<u64>(ctx, m);
+    u32 *v0 = arena_array<u32>(ctx, m), *v1 = arena_array<u32>(ctx, m);
+    u32 *tile_hist = (u32 *)arena_alloc(ctx, radix_tile_hist_bytes(m));
+    const SortPlan plan = sort_plan(k0, k1, v0, v1, tile_hist, arena_alloc(ctx, scan_temp_bytes(m)));
     if (!plan.keys[0] || !plan.keys[1] || !plan.vals[0] || !plan.vals[1] || !plan.tile_hist || !plan.scan_temp) return BWTS_E_NOMEM;
     HIPC(hipMemcpyAsync(plan.keys[0], h_keys, m * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPC(hipMemcpyAsync(plan.vals[0], h_vals, m * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1165,6 +1164,14 @@ static int upload_text(bwts_ctx *ctx, const uint8_t *in, uint64_t n, u8 **d_T)
         hipStreamSynchronize(ctx->stream) != hipSuccess) { (void)hipFree(p); return BWTS_E_HIP; }
     *d_T = (u8 *)p;
     return BWTS_OK;
+}
+
+// the chunk tables' arithmetic for a tied list of a0 elements of which a_chunks are left at a compaction: no context, no device
+extern "C" int bwts_debug_chunk_plan(uint64_t a0, uint64_t a_chunks, uint64_t out[4])
+{
+    const ChunkRecut re = chunk_recut_plan(a0, a_chunks);
+    out[0] = chunk_nominal_size(a0); out[1] = chunk_table_capacity(a0); out[2] = re.S; out[3] = re.nc;
+    return re.allowed ? 1 : 0;
 }
 
 extern "C" int bwts_debug_suffix_array(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint32_t *h_sa)

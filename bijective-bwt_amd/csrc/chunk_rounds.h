@@ -957,13 +957,265 @@ static void chunk_diag_sizes(bwts_ctx *ctx, const u32 *head, const u32 *cstart, 
     fprintf(stderr, "[chunks] before round %u, chunk elements by group size: 2: %llu  3-4: %llu  5-16: %llu  17-64: %llu  65-256: %llu  257-2048: %llu\n", round, hh[0], hh[1], hh[2], hh[3], hh[4], hh[5]);
 }
 
-static u32 chunk_nominal_size(u64 a)
+// ---- the chunk tables as plain arithmetic (declared in internal.h: the bwts_debug_chunk_plan test hook asks them too) ----
+u32 chunk_nominal_size(u64 a)
 {
     // about 16 K chunks, between one and eight tiles each
     u64 s = (a / 16384 + 1023) / 1024 * 1024;
     if (s < CH_TILE) s = CH_TILE;
     if (s > 8 * CH_TILE) s = 8 * CH_TILE;
     return (u32)s;
+}
+// Entries of cstart/ccount/mvcount/cwide/coff, fixed when their block is reserved: the first cut's chunks, and one ragged chunk per
+// append (rounds are capped at 80).  After a compaction the nominal size is up to 8x smaller, so a list that the big list dominates
+// may append more chunks than this budgets: that ends in "chunk table full" (BWTS_E_INTERNAL), a clean failure and never an overrun.
+u64 chunk_table_capacity(u64 a0) { return a0 / chunk_nominal_size(a0) + 1024; }
+// A compaction re-cuts the a_chunks elements left by their own nominal size, which is allowed only when the new chunks fit the tables
+// (S is rounded up to whole K, so a0 / S(a0) can fall to about 14 K while the re-cut makes up to 16 K chunks).
+ChunkRecut chunk_recut_plan(u64 a0, u64 a_chunks)
+{
+    ChunkRecut r;
+    r.S = chunk_nominal_size(a_chunks);
+    r.nc = (a_chunks + r.S - 1) / r.S;
+    r.allowed = r.nc <= chunk_table_capacity(a0);
+    return r;
+}
+
+// The big list: idx/head ping-pong (cur = the side that holds it), the regrouped copy, two pairs of sort buffers, the second key word.
+struct BigList {
+    u32 *idx[2], *head[2], *t_idx, *t_head, *bv[2], *sv1;
+    u64 *bk[2], *k23, *sk1;
+    u8 *flags;
+    u64 m = 0, groups = 0;          // elements; groups: the ordinals of a round's sort key lie below it
+    int cur = 0;
+};
+// What the stages of chunk_rounds share: the list store with its chunk tables, and the big list
+struct ChunkRun {
+    bool trace;                     // BWTS_ROUND_TRACE=1
+    u32 rounds;
+    int rb;
+    PrevSym prev;
+    u8 *out;
+    u64 *slots;                     // CH_SLOTS result slots in d_small
+    u32 *st_idx, *st_head, *alt_idx, *alt_head;     // the store, and its other pair of arrays (chunk_compact_kernel)
+    u64 *mv;
+    u32 *cstart, *ccount, *mvcount, *coff;          // (coff: the chunks' offsets in the dense list of a compaction)
+    u8 *cwide;
+    u32 S, nchunks = 0;             // nominal chunk size; chunks in the tables
+    u64 maxchunks, tail = 0;        // chunk_table_capacity(); slots of the store in use: chunks leaving the big list are appended there
+    bool wide_possible = false;     // some chunk may be flagged WIDE: the second instantiation is launched as well
+    BigList b;
+};
+
+#define CH_TRY(call) do { const int rc__ = (call); if (rc__ != BWTS_OK) { if (c.trace) fprintf(stderr, "[chunks] line %d: rc %d\n", __LINE__, rc__); return rc__; } } while (0)
+#define CH_HIP(call) do { const hipError_t e__ = (call); if (e__ != hipSuccess) { ctx->last_hip = (int)e__; if (c.trace) fprintf(stderr, "[chunks] line %d: hip error %d\n", __LINE__, (int)e__); return BWTS_E_HIP; } } while (0)
+#define CH_FAIL(why) do { if (c.trace) fprintf(stderr, "[chunks] invariant: %s (round %u)\n", why, c.rounds); return BWTS_E_INTERNAL; } while (0)
+
+// Every launch of chunk_init_kernel: list slots [lo, hi) of the store become chunks first_chunk, first_chunk + 1, ... of the nominal size
+// (the first cut and the re-cut after a compaction start the tables over at 0; an append goes behind the last chunk).
+// wide: the new chunks may hold groups of up to CH_GROUP_MAX members.
+static int cut_chunks(bwts_ctx *ctx, ChunkRun &c, u64 lo, u64 hi, u32 first_chunk, bool wide)
+{
+    const u32 add = (u32)((hi - lo + c.S - 1) / c.S);
+    if ((u64)first_chunk + add > c.maxchunks) CH_FAIL("chunk table full");
+    chunk_init_kernel<<<dim3((add + 3) / 4), dim3(256), 0, ctx->stream>>>(c.st_head, lo, hi, c.S, first_chunk, add, c.cstart, c.ccount, c.mvcount, c.cwide, wide);
+    if (wide) c.wide_possible = true;
+    CH_HIP(hipGetLastError());
+    c.nchunks = first_chunk + add;
+    c.tail = hi;
+    return BWTS_OK;
+}
+
+// The one-off order: group records sorted by the group's smallest position, members copied to their places in the store; the larger
+// groups' members compacted behind them (see go_write_kernel).  ob: the order block of ob_bytes, cut here as group records.
+// *a_small: elements of the smaller groups.
+static int chunk_order(bwts_ctx *ctx, ChunkRun &c, u64 n, SortSpace &sp, const ActiveList &cur, u64 a0, u32 *SA, char *ob, size_t ob_bytes, u64 *a_small)
+{
+    const u64 tiles = (a0 + DG_OWN - 1) / DG_OWN;
+    const bool pairs = n <= 0x80000000ull;                        // (positions and list indices below 2^31)
+    const u64 gmax = a0 / 2 + 1;                                  // a group has at least two members
+    // records and their sort buffers (2 x 8 + 3 x 4 bytes per group <= 14 bytes per element), tile counts behind
+    u64 *rk[2], *tcount;
+    u32 *rv[2], *doff;
+    BlockLayout G;
+    G.array(&rk[0], gmax); G.array(&rk[1], gmax); G.array(&rv[0], gmax); G.array(&rv[1], gmax); G.array(&doff, gmax); G.array(&tcount, tiles + 1);
+    if (!G.place_within(ob, ob_bytes)) CH_FAIL("order block too small");
+    {
+        SpanGuard g(ctx, BWTS_K_RERANK, a0, 14 * a0);
+        go_count_kernel<<<dim3((unsigned)tiles), dim3(DG_THREADS), 0, ctx->stream>>>(cur.idx, cur.head, a0, tcount);
+        CH_HIP(hipMemsetAsync(tcount + tiles, 0, sizeof(u64), ctx->stream));
+        ScanLoadArr<u64> tin{tcount};
+        ScanStoreArr<u64> tout{tcount};
+        CH_TRY((device_scan<false, u64>(ctx, tiles + 1, tin, tout, OpAdd(), (u64)0, sp.scan_temp)));
+        CH_HIP(hipMemcpyAsync(c.slots + CHS_TOTAL, tcount + tiles, sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
+        go_write_kernel<<<dim3((unsigned)tiles), dim3(DG_THREADS), 0, ctx->stream>>>(cur.idx, cur.head, a0, tcount, tiles, rk[0], rv[0], c.st_idx, c.st_head, pairs);
+        CH_HIP(hipGetLastError());
+    }
+    CH_TRY(read_small(ctx, SM_CHSLOT, CH_SLOT_WORDS));
+    const u64 tot = ctx->h_small[SM_CHSLOT + CHS_TOTAL];
+    const u64 groups = (u32)tot, bigs = tot >> 32;
+    if (bigs > a0 || groups > gmax) CH_FAIL("group records");
+    *a_small = a0 - bigs;
+    if (groups) {
+        const SortPlan op = sort_plan(rk[0], rk[1], rv[0], rv[1], sp.tile_hist, sp.scan_temp);
+        int ores = 0;
+        const int pb = bitlen_u64(n - 1);
+        CH_TRY(radix_sort_pairs(ctx, op, groups, pb < 1 ? 1 : pb, &ores));
+        SpanGuard g(ctx, BWTS_K_RERANK, *a_small, 20 * *a_small);
+        const unsigned gblocks = (unsigned)((groups + 255) / 256);
+        GoSizeIn zin{rk[ores], rv[ores], pairs};
+        ScanStoreArr<u32> zout{doff};
+        CH_TRY((device_scan<false, u32>(ctx, groups, zin, zout, OpAdd(), 0u, sp.scan_temp)));
+        go_expand_kernel<<<dim3(gblocks), dim3(256), 0, ctx->stream>>>(rk[ores], rv[ores], doff, groups, SA, c.st_idx, c.st_head, pairs);
+        CH_HIP(hipGetLastError());
+    }
+    return BWTS_OK;
+}
+
+// The big list's buffers, in side arena 1 (the order sort's block, free again), and the list itself: the m elements that
+// go_write_kernel left behind the smaller groups.  BWTS_E_NOMEM: no room (nothing was written).
+static int big_list_setup(bwts_ctx *ctx, ChunkRun &c, u64 m, u64 a_small)
+{
+    BigList &b = c.b;
+    char *bb = nullptr;
+    BlockLayout L;
+    for (int i = 0; i < 2; i++) { L.array(&b.idx[i], m); L.array(&b.head[i], m); }
+    L.array(&b.t_idx, m); L.array(&b.t_head, m); L.array(&b.bv[0], m); L.array(&b.bv[1], m); L.array(&b.sv1, m);
+    L.array(&b.bk[0], m); L.array(&b.bk[1], m); L.array(&b.k23, m); L.array(&b.sk1, m); L.array(&b.flags, m);
+    const bool deny = [ctx] { const char *e = bwts_knob(ctx, "BWTS_BIGLIST_NOMEM"); return e && atoi(e) == 1; }();      // (test switch)
+    const int rc = deny ? BWTS_E_NOMEM : aux_reserve_slot(ctx, 1, L.bytes(), &bb);
+    if (rc == BWTS_E_NOMEM) return rc;
+    CH_TRY(rc);
+    L.place(bb);
+    b.m = m;
+    CH_HIP(hipMemcpyAsync(b.idx[0], c.st_idx + a_small, m * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
+    CH_HIP(hipMemcpyAsync(b.head[0], c.st_head + a_small, m * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
+    return BWTS_OK;
+}
+
+// The one-off order left every group of more than CH_CAP members in the big list; those of up to CH_GROUP_MAX go to chunks right
+// away (unordered, like everything that leaves the big list later): their chunks are flagged WIDE and take the sorting instantiation of the round kernel
+static int big_list_first_split(bwts_ctx *ctx, ChunkRun &c, SortSpace &sp, u64 a0, u64 *a_chunks)
+{
+    BigList &b = c.b;
+    CH_HIP(hipMemsetAsync(c.slots, 0, CH_SLOT_WORDS * sizeof(u64), ctx->stream));
+    {
+        SpanGuard g(ctx, BWTS_K_RERANK, b.m, 28 * b.m);
+        BlRunIn nin{b.head[0]};
+        BlRunOut nout{b.head[0], b.m, b.bv[0], b.bv[1]};
+        CH_TRY((device_scan<true, u32>(ctx, b.m, nin, nout, OpMax(), 0u, sp.scan_temp)));
+        if (c.trace) bl_diag_sizes(ctx, b.bv[0], b.bv[1], b.m, "groups of more than 256 after round 0");
+        BlSplitIn sin{b.bv[0], b.bv[1]};
+        BlSplitOut sout{b.bv[0], b.bv[1], b.idx[0], b.head[0], b.m, c.st_idx + c.tail, c.st_head + c.tail, b.idx[1], b.head[1], (unsigned long long *)c.slots};
+        CH_TRY((device_scan<false, u64>(ctx, b.m, sin, sout, OpAdd(), (u64)0, sp.scan_temp)));
+    }
+    CH_TRY(read_small(ctx, SM_CHSLOT, CH_SLOT_WORDS));
+    const u64 m_exit = ctx->h_small[SM_CHSLOT + CHS_EXIT], m_stay = ctx->h_small[SM_CHSLOT + CHS_STAY];
+    b.groups = ctx->h_small[SM_CHSLOT + CHS_BIGGROUPS];
+    if (m_exit + m_stay != b.m || c.tail + m_exit > a0 || b.groups * (CH_GROUP_MAX + 1) > m_stay) CH_FAIL("first split of the big list");
+    if (m_exit) {
+        CH_TRY(cut_chunks(ctx, c, c.tail, c.tail + m_exit, c.nchunks, true));
+        *a_chunks += m_exit;
+    }
+    b.cur = 1;
+    b.m = m_stay;
+    if (c.trace) fprintf(stderr, "[chunks] groups of up to %d members leave the big list at once: %llu elements, %llu stay\n", (int)CH_GROUP_MAX,
+                         (unsigned long long)m_exit, (unsigned long long)m_stay);
+    return BWTS_OK;
+}
+
+// A round of the big list, first half: its gathers read the same version of the ranks as the chunks', before the moves are applied
+template <bool CYCLIC>
+static int big_list_gather(bwts_ctx *ctx, ChunkRun &c, SortSpace &sp, u64 n, u64 h, const u32 *d_fstart, u64 k)
+{
+    BigList &b = c.b;
+    SpanGuard g(ctx, BWTS_K_RERANK, b.m, 30 * b.m);
+    BlIn fin{b.head[b.cur]};
+    BlOut<CYCLIC> fout{b.head[b.cur], b.idx[b.cur], c.rb, sp.rank, n, h, d_fstart, k, b.bk[0], b.bv[0], b.k23, b.bk[1], b.bv[1]};
+    CH_TRY((device_scan<false, u32>(ctx, b.m, fin, fout, OpAdd(), 0u, sp.scan_temp)));
+    if (c.trace) {
+        const u64 gcap = b.m / (CH_GROUP_MAX + 1) + 2;
+        u8 *df = nullptr; unsigned long long hc[3] = {0, 0, 0};
+        if (hipMalloc((void **)&df, 2 * gcap + 32) == hipSuccess) {
+            (void)hipMemsetAsync(df, 0, 2 * gcap + 32, ctx->stream);
+            unsigned long long *dc = (unsigned long long *)(df + ((2 * gcap + 7) & ~7ull));
+            const unsigned gb = (unsigned)((b.m + 255) / 256);
+            bl_diag_flag_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(b.bk[0], b.k23, b.m, c.rb, df, df + gcap);
+            bl_diag_count_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(b.bk[0], b.m, c.rb, df, df + gcap, dc);
+            (void)hipMemcpyAsync(hc, dc, sizeof(hc), hipMemcpyDeviceToHost, ctx->stream);
+            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipFree(df);
+            fprintf(stderr, "[chunks] big list at h %llu: %llu elements in %llu groups; in groups with one rank at h: %llu, with one rank triple (cannot split): %llu\n",
+                    (unsigned long long)h, (unsigned long long)b.m, hc[2], hc[0], hc[1]);
+        }
+    }
+    return BWTS_OK;
+}
+
+// ... second half: the two-word sort, subgroup flags, regrouping (ranks, emission), and the split into what stays (the list's other
+// side) and what leaves for the store's tail
+static int big_list_sort_split(bwts_ctx *ctx, ChunkRun &c, SortSpace &sp, unsigned long long *res)
+{
+    BigList &b = c.b;
+    const int big_bits = (b.groups > 1 ? bitlen_u64(b.groups - 1) : 1) + c.rb;          // ordinals < groups
+    if (big_bits > 64) return BWTS_E_RANGE;
+    const u64 *sorted_keys = nullptr;
+    const u32 *src = nullptr;
+    CH_TRY(two_word_sort(ctx, sp, b.bk, b.bv[1], b.sk1, b.sv1, b.m, c.rb, big_bits, &sorted_keys, &src));
+    SpanGuard g(ctx, BWTS_K_RERANK, b.m, 60 * b.m);
+    bl_flags_kernel<<<dim3((unsigned)((b.m + 255) / 256)), dim3(256), 0, ctx->stream>>>(sorted_keys, src, b.k23, b.bv[0], b.m, c.rb, b.flags, b.t_idx);
+    CH_HIP(hipGetLastError());
+    // (the sort buffers are free again: subgroup starts and sizes go there)
+    BlFlagIn rin{b.flags};
+    BlRegroupOut rout{b.flags, b.head[b.cur], b.m, b.t_idx, b.t_head, sp.rank, c.prev, c.out, res, b.bv[0], b.bv[1]};
+    CH_TRY((device_scan<true, u64>(ctx, b.m, rin, rout, OpMax2(), (u64)0, sp.scan_temp)));
+    if (c.trace) bl_diag_sizes(ctx, b.bv[0], b.bv[1], b.m, "big list regrouped");
+    BlSplitIn sin{b.bv[0], b.bv[1]};
+    BlSplitOut sout{b.bv[0], b.bv[1], b.t_idx, b.t_head, b.m, c.st_idx + c.tail, c.st_head + c.tail, b.idx[b.cur ^ 1], b.head[b.cur ^ 1], res};
+    CH_TRY((device_scan<false, u64>(ctx, b.m, sin, sout, OpAdd(), (u64)0, sp.scan_temp)));
+    return BWTS_OK;
+}
+
+// The chunks are two thirds empty: a dense list in the store's other pair of arrays, cut into new chunks (chunk_compact_kernel).
+// Skipped, as whenever the chunks are fuller than that, when the new chunks would not fit the tables.
+static int compact_chunks(bwts_ctx *ctx, ChunkRun &c, u64 a0, u64 a_chunks)
+{
+    const ChunkRecut re = chunk_recut_plan(a0, a_chunks);
+    if (!re.allowed) {
+        if (c.trace) fprintf(stderr, "[chunks] list not compacted: %llu elements would make %llu chunks (nominal chunk %u), the tables hold %llu\n",
+                             (unsigned long long)a_chunks, (unsigned long long)re.nc, re.S, (unsigned long long)c.maxchunks);
+        return BWTS_OK;
+    }
+    SpanGuard g(ctx, BWTS_K_ROUND, 0, 0);
+    chunk_total_kernel<<<dim3(1), dim3(1024), 0, ctx->stream>>>(c.ccount, c.nchunks, (unsigned long long *)(c.slots + 3 * CH_SLOT_WORDS), c.coff);
+    chunk_compact_kernel<<<dim3(c.nchunks), dim3(256), 0, ctx->stream>>>(c.st_idx, c.st_head, c.cstart, c.ccount, c.coff, c.alt_idx, c.alt_head);
+    { u32 *t = c.st_idx; c.st_idx = c.alt_idx; c.alt_idx = t; t = c.st_head; c.st_head = c.alt_head; c.alt_head = t; }
+    if (c.trace) fprintf(stderr, "[chunks] list compacted: %llu elements of %llu slots, %u chunks -> %u (nominal chunk %u)\n", (unsigned long long)a_chunks,
+                         (unsigned long long)c.tail, c.nchunks, (u32)re.nc, re.S);
+    c.S = re.S;
+    return cut_chunks(ctx, c, 0, a_chunks, 0, c.wide_possible);
+}
+
+// After the last round: the suffix array when someone reads it, and with a stable partition the groups of equal infinite words
+static int chunk_finish(bwts_ctx *ctx, ChunkRun &c, SortSpace &sp, u64 n, u32 *SA, bool need_sa, bool stable, u64 a_chunks)
+{
+    BigList &b = c.b;
+    if (need_sa) CH_TRY(sa_from_ranks(ctx, sp.rank, n, SA));
+    if (stable) {
+        // (a round enqueued behind the stable one has split nothing either: the lists are what they were)
+        SpanGuard g(ctx, BWTS_K_EMIT, a_chunks + b.m, 10 * (a_chunks + b.m));
+        if (c.nchunks && a_chunks) {
+            chunk_rest_records_kernel<<<dim3(c.nchunks), dim3(256), 0, ctx->stream>>>(c.st_idx, c.st_head, c.cstart, c.ccount, c.mv, c.mvcount);
+            chunk_apply_records_kernel<1><<<dim3(c.nchunks), dim3(256), 0, ctx->stream>>>(c.mv, c.cstart, c.mvcount, RecordTargets{sp.rank, c.prev, c.out, need_sa ? SA : nullptr});
+            CH_HIP(hipGetLastError());
+        }
+        if (b.m) {
+            DgRestIn rin{b.head[b.cur]};
+            DgRestOut rout{b.idx[b.cur], b.head[b.cur], c.prev, c.out, need_sa ? SA : nullptr};
+            CH_TRY((device_scan<true, u32>(ctx, b.m, rin, rout, OpMax(), 0u, sp.scan_temp)));
+        }
+    }
+    return BWTS_OK;
 }
 
 // Same contract as dense_rounds().  *handled = false: this form does not apply (short list, no room) and nothing was changed.
@@ -973,162 +1225,50 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
 {
     *handled = false;
     if (a0 > 0xffffffffull || a0 < CH_MIN_LIST) return BWTS_OK;
-    const bool round_trace = [ctx] { const char *e = bwts_knob(ctx, "BWTS_ROUND_TRACE"); return e && atoi(e) == 1; }();
-#define CH_TRY(call) do { const int rc__ = (call); if (rc__ != BWTS_OK) { if (round_trace) fprintf(stderr, "[chunks] line %d: rc %d\n", __LINE__, rc__); return rc__; } } while (0)
-#define CH_HIP(call) do { const hipError_t e__ = (call); if (e__ != hipSuccess) { ctx->last_hip = (int)e__; if (round_trace) fprintf(stderr, "[chunks] line %d: hip error %d\n", __LINE__, (int)e__); return BWTS_E_HIP; } } while (0)
-#define CH_FAIL(why) do { if (round_trace) fprintf(stderr, "[chunks] invariant: %s (round %u)\n", why, rounds); return BWTS_E_INTERNAL; } while (0)
-    const size_t e4 = align_up((size_t)a0 * 4, 256), e8 = align_up((size_t)a0 * 8, 256);
-    u32 S = chunk_nominal_size(a0);
-    const u64 maxchunks = a0 / S + 1024;                 // every append adds at most one ragged chunk; rounds are capped at 80
-    const size_t ct4 = align_up((size_t)(maxchunks + 1) * 4, 256);
+    ChunkRun c{[ctx] { const char *e = bwts_knob(ctx, "BWTS_ROUND_TRACE"); return e && atoi(e) == 1; }(), *rounds_io,
+               CYCLIC ? bitlen_u64(n - 1) : bitlen_u64(n), PrevSym{sp.carry_src, d_T, n, d_fstart, k}, CYCLIC ? sp.carry_out : nullptr,
+               ctx->d_small + SM_CHSLOT};
+    BigList &b = c.b;
+    c.S = chunk_nominal_size(a0);
+    c.maxchunks = chunk_table_capacity(a0);
     char *base = nullptr, *ob = nullptr;
-    const size_t ct1 = align_up((size_t)(maxchunks + 1), 256);
-    int rc = aux_reserve(ctx, 4 * e4 + e8 + 4 * ct4 + ct1, &base);
+    BlockLayout L;
+    L.array(&c.st_idx, a0); L.array(&c.st_head, a0); L.array(&c.mv, a0);
+    L.array(&c.cstart, c.maxchunks + 1); L.array(&c.ccount, c.maxchunks + 1); L.array(&c.mvcount, c.maxchunks + 1); L.array(&c.cwide, c.maxchunks + 1);
+    L.array(&c.coff, c.maxchunks + 1); L.array(&c.alt_idx, a0); L.array(&c.alt_head, a0);
+    int rc = aux_reserve(ctx, L.bytes(), &base);
     if (rc == BWTS_E_NOMEM) return BWTS_OK;
     CH_TRY(rc);
-    rc = aux_reserve_slot(ctx, 1, 2 * e8 + 2 * e4, &ob);
+    // the order block: what the order sort of dense_rounds takes, two key and two value buffers of the whole list
+    const size_t ob_bytes = 2 * BlockLayout::padded<u64>(a0) + 2 * BlockLayout::padded<u32>(a0);
+    rc = aux_reserve_slot(ctx, 1, ob_bytes, &ob);
     if (rc == BWTS_E_NOMEM) return BWTS_OK;
     CH_TRY(rc);
     *handled = true;
-    u32 *st_idx = (u32 *)base, *st_head = (u32 *)(base + e4);
-    u64 *mv = (u64 *)(base + 2 * e4);
-    u32 *cstart = (u32 *)(base + 2 * e4 + e8), *ccount = (u32 *)(base + 2 * e4 + e8 + ct4), *mvcount = (u32 *)(base + 2 * e4 + e8 + 2 * ct4);
-    u8 *cwide = (u8 *)(base + 2 * e4 + e8 + 3 * ct4);
-    // (chunk_compact_kernel: the chunks' offsets in the dense list, and the list's other pair of arrays)
-    u32 *coff = (u32 *)(base + 2 * e4 + e8 + 3 * ct4 + ct1);
-    u32 *alt_idx = (u32 *)(base + 2 * e4 + e8 + 4 * ct4 + ct1), *alt_head = (u32 *)(base + 3 * e4 + e8 + 4 * ct4 + ct1);
-    u64 *slots = ctx->d_small + SM_CHSLOT;
-    const int rb = CYCLIC ? bitlen_u64(n - 1) : bitlen_u64(n);
-    PrevSym prev{sp.carry_src, d_T, n, d_fstart, k};
-    u8 *out = CYCLIC ? sp.carry_out : nullptr;
-    u32 rounds = *rounds_io;
+    L.place(base);
 
-    // ---- one-off order: group records sorted by the group's smallest position, members copied to their places; the larger groups'
-    // members compacted behind them (see go_write_kernel) ----
-    u64 a_small = 0;                         // elements of the smaller groups
-    {
-        const u64 tiles = (a0 + DG_OWN - 1) / DG_OWN;
-        const bool pairs = n <= 0x80000000ull;                        // (positions and list indices below 2^31)
-        const u64 gmax = a0 / 2 + 1;                                  // a group has at least two members
-        const size_t g8 = align_up((size_t)gmax * 8, 256), g4 = align_up((size_t)gmax * 4, 256);
-        // records and their sort buffers inside the order block (2 x 8 + 3 x 4 bytes per group <= 14 bytes per element), tile counts behind
-        u64 *rk[2] = {(u64 *)ob, (u64 *)(ob + g8)};
-        u32 *rv[2] = {(u32 *)(ob + 2 * g8), (u32 *)(ob + 2 * g8 + g4)};
-        u32 *doff = (u32 *)(ob + 2 * g8 + 2 * g4);
-        u64 *tcount = (u64 *)(ob + 2 * g8 + 3 * g4);
-        const size_t tc_bytes = align_up((size_t)(tiles + 1) * 8, 256);
-        if (2 * g8 + 3 * g4 + tc_bytes > 2 * e8 + 2 * e4) CH_FAIL("order block too small");
-        {
-            SpanGuard g(ctx, BWTS_K_RERANK, a0, 14 * a0);
-            go_count_kernel<<<dim3((unsigned)tiles), dim3(DG_THREADS), 0, ctx->stream>>>(cur.idx, cur.head, a0, tcount);
-            CH_HIP(hipMemsetAsync(tcount + tiles, 0, sizeof(u64), ctx->stream));
-            ScanLoadArr<u64> tin{tcount};
-            ScanStoreArr<u64> tout{tcount};
-            CH_TRY((device_scan<false, u64>(ctx, tiles + 1, tin, tout, OpAdd(), (u64)0, sp.scan_temp)));
-            CH_HIP(hipMemcpyAsync(slots + CHS_TOTAL, tcount + tiles, sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
-            go_write_kernel<<<dim3((unsigned)tiles), dim3(DG_THREADS), 0, ctx->stream>>>(cur.idx, cur.head, a0, tcount, tiles, rk[0], rv[0], st_idx, st_head, pairs);
-            CH_HIP(hipGetLastError());
-        }
-        CH_TRY(read_small(ctx, SM_CHSLOT, CH_SLOT_WORDS));
-        const u64 tot = ctx->h_small[SM_CHSLOT + CHS_TOTAL];
-        const u64 groups = (u32)tot, bigs = tot >> 32;
-        if (bigs > a0 || groups > gmax) CH_FAIL("group records");
-        a_small = a0 - bigs;
-        if (groups) {
-            SortPlan op;
-            op.keys[0] = rk[0]; op.keys[1] = rk[1];
-            op.vals[0] = rv[0]; op.vals[1] = rv[1];
-            op.tile_hist = sp.tile_hist; op.scan_temp = sp.scan_temp;
-            int ores = 0;
-            const int pb = bitlen_u64(n - 1);
-            CH_TRY(radix_sort_pairs(ctx, op, groups, pb < 1 ? 1 : pb, &ores));
-            SpanGuard g(ctx, BWTS_K_RERANK, a_small, 20 * a_small);
-            const unsigned gblocks = (unsigned)((groups + 255) / 256);
-            GoSizeIn zin{rk[ores], rv[ores], pairs};
-            ScanStoreArr<u32> zout{doff};
-            CH_TRY((device_scan<false, u32>(ctx, groups, zin, zout, OpAdd(), 0u, sp.scan_temp)));
-            go_expand_kernel<<<dim3(gblocks), dim3(256), 0, ctx->stream>>>(rk[ores], rv[ores], doff, groups, SA, st_idx, st_head, pairs);
-            CH_HIP(hipGetLastError());
-        }
-    }
-    u64 m_big = a0 - a_small;
-    if (round_trace) fprintf(stderr, "[chunks] list %llu: in chunks %llu (nominal chunk %u), big list %llu\n", (unsigned long long)a0,
-                             (unsigned long long)a_small, S, (unsigned long long)m_big);
-
-    // ---- big list buffers (the order sort's block, free again) ----
-    const size_t m4 = align_up((size_t)m_big * 4, 256), m8 = align_up((size_t)m_big * 8, 256);
-    u32 *bl_idx[2] = {nullptr, nullptr}, *bl_head[2] = {nullptr, nullptr}, *t_idx = nullptr, *t_head = nullptr, *bv[2] = {nullptr, nullptr}, *sv1 = nullptr;
-    u64 *bk[2] = {nullptr, nullptr}, *k23 = nullptr, *sk1 = nullptr;
-    u8 *bflags = nullptr;
-    u64 big_groups = 0;                     // groups in the big list: the ordinals of a round's sort key lie below it
-    int blc = 0;
-    if (m_big) {
-        char *bb = nullptr;
+    u64 a_small = 0;
+    CH_TRY(chunk_order(ctx, c, n, sp, cur, a0, SA, ob, ob_bytes, &a_small));
+    if (c.trace) fprintf(stderr, "[chunks] list %llu: in chunks %llu (nominal chunk %u), big list %llu\n", (unsigned long long)a0,
+                         (unsigned long long)a_small, c.S, (unsigned long long)(a0 - a_small));
+    if (a0 - a_small) {
         // (nothing outside this function's own buffers has been written so far: without room for the big list the tile form takes over,
         // as it does when the first two blocks do not fit)
-        const bool deny = [ctx] { const char *e = bwts_knob(ctx, "BWTS_BIGLIST_NOMEM"); return e && atoi(e) == 1; }();      // (test switch)
-        rc = deny ? BWTS_E_NOMEM : aux_reserve_slot(ctx, 1, 4 * m8 + 9 * m4 + align_up((size_t)m_big, 256), &bb);
+        rc = big_list_setup(ctx, c, a0 - a_small, a_small);
         if (rc == BWTS_E_NOMEM) {
-            if (round_trace) fprintf(stderr, "[chunks] no room for the big list (%llu elements): the tile form takes over\n", (unsigned long long)m_big);
+            if (c.trace) fprintf(stderr, "[chunks] no room for the big list (%llu elements): the tile form takes over\n", (unsigned long long)(a0 - a_small));
             *handled = false;
             return BWTS_OK;
         }
-        CH_TRY(rc);
-        char *q = bb;
-        for (int i = 0; i < 2; i++) { bl_idx[i] = (u32 *)q; q += m4; bl_head[i] = (u32 *)q; q += m4; }
-        t_idx = (u32 *)q; q += m4; t_head = (u32 *)q; q += m4;
-        bv[0] = (u32 *)q; q += m4; bv[1] = (u32 *)q; q += m4; sv1 = (u32 *)q; q += m4;
-        bk[0] = (u64 *)q; q += m8; bk[1] = (u64 *)q; q += m8; k23 = (u64 *)q; q += m8; sk1 = (u64 *)q; q += m8;
-        bflags = (u8 *)q;
-        CH_HIP(hipMemcpyAsync(bl_idx[0], st_idx + a_small, m_big * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
-        CH_HIP(hipMemcpyAsync(bl_head[0], st_head + a_small, m_big * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
+        if (rc != BWTS_OK) return rc;
     }
     // ---- chunks over the smaller groups ----
-    u32 nchunks = 0;
     // (the larger groups' members, which go_write_kernel left at [a_small, a0), are in the big list's own buffers by now: the store
     // behind the smaller groups is free, chunks leaving the big list are appended there)
-    u64 tail = a_small;
-    if (a_small) {
-        nchunks = (u32)((a_small + S - 1) / S);
-        chunk_init_kernel<<<dim3((nchunks + 3) / 4), dim3(256), 0, ctx->stream>>>(st_head, 0, a_small, S, 0, nchunks, cstart, ccount, mvcount, cwide, false);
-        CH_HIP(hipGetLastError());
-    }
-
+    c.tail = a_small;
+    if (a_small) CH_TRY(cut_chunks(ctx, c, 0, a_small, 0, false));
     u64 a_chunks = a_small;                 // elements in chunks after the last evaluated round
-    bool wide_possible = false;             // some chunk may be flagged WIDE: the second instantiation is launched as well
-    if (m_big) {
-        // the one-off order left every group of more than CH_CAP members in the big list; those of up to CH_GROUP_MAX go to chunks right
-        // away (unordered, like everything that leaves the big list later): their chunks are flagged WIDE and take the sorting instantiation of the round kernel
-        CH_HIP(hipMemsetAsync(slots, 0, CH_SLOT_WORDS * sizeof(u64), ctx->stream));
-        {
-            SpanGuard g(ctx, BWTS_K_RERANK, m_big, 28 * m_big);
-            BlRunIn nin{bl_head[0]};
-            BlRunOut nout{bl_head[0], m_big, bv[0], bv[1]};
-            CH_TRY((device_scan<true, u32>(ctx, m_big, nin, nout, OpMax(), 0u, sp.scan_temp)));
-            if (round_trace) bl_diag_sizes(ctx, bv[0], bv[1], m_big, "groups of more than 256 after round 0");
-            BlSplitIn sin{bv[0], bv[1]};
-            BlSplitOut sout{bv[0], bv[1], bl_idx[0], bl_head[0], m_big, st_idx + tail, st_head + tail, bl_idx[1], bl_head[1], (unsigned long long *)slots};
-            CH_TRY((device_scan<false, u64>(ctx, m_big, sin, sout, OpAdd(), (u64)0, sp.scan_temp)));
-        }
-        CH_TRY(read_small(ctx, SM_CHSLOT, CH_SLOT_WORDS));
-        const u64 m_exit = ctx->h_small[SM_CHSLOT + CHS_EXIT], m_stay = ctx->h_small[SM_CHSLOT + CHS_STAY];
-        big_groups = ctx->h_small[SM_CHSLOT + CHS_BIGGROUPS];
-        if (m_exit + m_stay != m_big || tail + m_exit > a0 || big_groups * (CH_GROUP_MAX + 1) > m_stay) CH_FAIL("first split of the big list");
-        if (m_exit) {
-            const u32 add = (u32)((m_exit + S - 1) / S);
-            if ((u64)nchunks + add > maxchunks) CH_FAIL("chunk table full");
-            chunk_init_kernel<<<dim3((add + 3) / 4), dim3(256), 0, ctx->stream>>>(st_head, tail, tail + m_exit, S, nchunks, add, cstart, ccount, mvcount, cwide, true);
-            CH_HIP(hipGetLastError());
-            nchunks += add;
-            tail += m_exit;
-            a_chunks += m_exit;
-            wide_possible = true;
-        }
-        blc = 1;
-        m_big = m_stay;
-        if (round_trace) fprintf(stderr, "[chunks] groups of up to %d members leave the big list at once: %llu elements, %llu stay\n", (int)CH_GROUP_MAX,
-                                 (unsigned long long)m_exit, (unsigned long long)m_stay);
-    }
+    if (b.m) CH_TRY(big_list_first_split(ctx, c, sp, a0, &a_chunks));
 
     u64 h = (u64)al.hstep;
     bool finished = false, stable = false;
@@ -1136,186 +1276,91 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
 #ifdef CH_PROFILE
         const int B = 1;
 #else
-        const int B = m_big ? 1 : 2;        // rounds per host round trip
+        const int B = b.m ? 1 : 2;        // rounds per host round trip
 #endif
-        CH_HIP(hipMemsetAsync(slots, 0, CH_SLOTS * CH_SLOT_WORDS * sizeof(u64), ctx->stream));
+        CH_HIP(hipMemsetAsync(c.slots, 0, CH_SLOTS * CH_SLOT_WORDS * sizeof(u64), ctx->stream));
         u64 hs[CH_SLOTS];
-        for (int b = 0; b < B; b++) {
-            unsigned long long *res = (unsigned long long *)(slots + b * CH_SLOT_WORDS);
-            hs[b] = h;
-            if (round_trace && nchunks) chunk_diag_sizes(ctx, st_head, cstart, ccount, nchunks, rounds + 1);
-            if (nchunks) {
+        for (int r = 0; r < B; r++) {
+            unsigned long long *res = (unsigned long long *)(c.slots + r * CH_SLOT_WORDS);
+            hs[r] = h;
+            if (c.trace && c.nchunks) chunk_diag_sizes(ctx, c.st_head, c.cstart, c.ccount, c.nchunks, c.rounds + 1);
+            if (c.nchunks) {
                 SpanGuard g(ctx, BWTS_K_ROUND, 0, 0);          // (elements and bytes are added below, once the round's true size is known)
-#define CH_LAUNCH(FS, WD) chunk_round_kernel<CYCLIC, 3, FS, WD><<<dim3(nchunks), dim3(CH_THREADS), 0, ctx->stream>>>(st_idx, st_head, cstart, ccount, cwide, mv, mvcount, \
-                                                                                                  sp.rank, n, h, d_fstart, k, prev, out, res)
+#define CH_LAUNCH(FS, WD) chunk_round_kernel<CYCLIC, 3, FS, WD><<<dim3(c.nchunks), dim3(CH_THREADS), 0, ctx->stream>>>(c.st_idx, c.st_head, c.cstart, c.ccount, c.cwide, c.mv, c.mvcount, \
+                                                                                                  sp.rank, n, h, d_fstart, k, c.prev, c.out, res)
                 const bool fsl = CYCLIC && k <= CH_FS;
                 if (fsl) CH_LAUNCH(CYCLIC, false); else CH_LAUNCH(false, false);
-                if (wide_possible) {
+                if (c.wide_possible) {
                     // (behind the other one: a chunk whose last large group has just split is taken over in the NEXT round)
                     if (fsl) CH_LAUNCH(CYCLIC, true); else CH_LAUNCH(false, true);
                 }
 #undef CH_LAUNCH
                 CH_HIP(hipGetLastError());
             }
-            if (m_big) {
-                // the big list's gathers read the same version of the ranks as the chunks': before the moves are applied
-                SpanGuard g(ctx, BWTS_K_RERANK, m_big, 30 * m_big);
-                BlIn fin{bl_head[blc]};
-                BlOut<CYCLIC> fout{bl_head[blc], bl_idx[blc], rb, sp.rank, n, h, d_fstart, k, bk[0], bv[0], k23, bk[1], bv[1]};
-                CH_TRY((device_scan<false, u32>(ctx, m_big, fin, fout, OpAdd(), 0u, sp.scan_temp)));
-                if (round_trace) {
-                    const u64 gcap = m_big / (CH_GROUP_MAX + 1) + 2;
-                    u8 *df = nullptr; unsigned long long hc[3] = {0, 0, 0};
-                    if (hipMalloc((void **)&df, 2 * gcap + 32) == hipSuccess) {
-                        (void)hipMemsetAsync(df, 0, 2 * gcap + 32, ctx->stream);
-                        unsigned long long *dc = (unsigned long long *)(df + ((2 * gcap + 7) & ~7ull));
-                        const unsigned gb = (unsigned)((m_big + 255) / 256);
-                        bl_diag_flag_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(bk[0], k23, m_big, rb, df, df + gcap);
-                        bl_diag_count_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(bk[0], m_big, rb, df, df + gcap, dc);
-                        (void)hipMemcpyAsync(hc, dc, sizeof(hc), hipMemcpyDeviceToHost, ctx->stream);
-                        (void)hipStreamSynchronize(ctx->stream);
-                        (void)hipFree(df);
-                        fprintf(stderr, "[chunks] big list at h %llu: %llu elements in %llu groups; in groups with one rank at h: %llu, with one rank triple (cannot split): %llu\n",
-                                (unsigned long long)h, (unsigned long long)m_big, hc[2], hc[0], hc[1]);
-                    }
-                }
-            }
-            if (nchunks) {
+            if (b.m) CH_TRY((big_list_gather<CYCLIC>(ctx, c, sp, n, h, d_fstart, k)));
+            if (c.nchunks) {
                 SpanGuard g(ctx, BWTS_K_ROUND, 0, 0);
-                chunk_apply_records_kernel<0><<<dim3(nchunks), dim3(256), 0, ctx->stream>>>(mv, cstart, mvcount, RecordTargets{sp.rank, prev, out, nullptr});
-                chunk_total_kernel<<<dim3(1), dim3(1024), 0, ctx->stream>>>(ccount, nchunks, res, nullptr);
+                chunk_apply_records_kernel<0><<<dim3(c.nchunks), dim3(256), 0, ctx->stream>>>(c.mv, c.cstart, c.mvcount, RecordTargets{sp.rank, c.prev, c.out, nullptr});
+                chunk_total_kernel<<<dim3(1), dim3(1024), 0, ctx->stream>>>(c.ccount, c.nchunks, res, nullptr);
                 CH_HIP(hipGetLastError());
             }
-            if (m_big) {
-                const int big_bits = (big_groups > 1 ? bitlen_u64(big_groups - 1) : 1) + rb;          // ordinals < big_groups
-                if (big_bits > 64) return BWTS_E_RANGE;
-                SortPlan bp;
-                bp.tile_hist = sp.tile_hist; bp.scan_temp = sp.scan_temp;
-                int rbig = 0;
-                // LSD over two key words: stable sort by (rank at 2h, rank at 3h), then by (group ordinal, rank at h)
-                bp.keys[0] = bk[1]; bp.keys[1] = sk1;
-                bp.vals[0] = bv[1]; bp.vals[1] = sv1;
-                int r1 = 0;
-                CH_TRY(radix_sort_pairs(ctx, bp, m_big, 2 * rb, &r1));
-                u64 *kin = bp.keys[r1], *kout = bp.keys[r1 ^ 1];
-                u32 *vin = bp.vals[r1], *vout = bp.vals[r1 ^ 1];
-                {
-                    SpanGuard g(ctx, BWTS_K_RERANK, m_big, 20 * m_big);
-                    dg_stage2_keys_kernel<<<dim3((unsigned)((m_big + 255) / 256)), dim3(256), 0, ctx->stream>>>(vin, bk[0], m_big, kin);
-                    CH_HIP(hipGetLastError());
-                }
-                bp.keys[0] = kin; bp.keys[1] = kout;
-                bp.vals[0] = vin; bp.vals[1] = vout;
-                CH_TRY(radix_sort_pairs(ctx, bp, m_big, big_bits, &rbig));
-                SpanGuard g(ctx, BWTS_K_RERANK, m_big, 60 * m_big);
-                bl_flags_kernel<<<dim3((unsigned)((m_big + 255) / 256)), dim3(256), 0, ctx->stream>>>(bp.keys[rbig], bp.vals[rbig], k23, bv[0], m_big, rb, bflags, t_idx);
-                CH_HIP(hipGetLastError());
-                // (the sort buffers are free again: subgroup starts and sizes go there)
-                BlFlagIn rin{bflags};
-                BlRegroupOut rout{bflags, bl_head[blc], m_big, t_idx, t_head, sp.rank, prev, out, res, bv[0], bv[1]};
-                CH_TRY((device_scan<true, u64>(ctx, m_big, rin, rout, OpMax2(), (u64)0, sp.scan_temp)));
-                if (round_trace) bl_diag_sizes(ctx, bv[0], bv[1], m_big, "big list regrouped");
-                BlSplitIn sin{bv[0], bv[1]};
-                BlSplitOut sout{bv[0], bv[1], t_idx, t_head, m_big, st_idx + tail, st_head + tail, bl_idx[blc ^ 1], bl_head[blc ^ 1], res};
-                CH_TRY((device_scan<false, u64>(ctx, m_big, sin, sout, OpAdd(), (u64)0, sp.scan_temp)));
-            }
+            if (b.m) CH_TRY(big_list_sort_split(ctx, c, sp, res));
             h = h > (1ull << 60) ? h : h << 2;        // the step is quadrupled per round
         }
         CH_TRY(read_small(ctx, SM_CHSLOT, CH_SLOTS * CH_SLOT_WORDS));
-        for (int b = 0; b < B; b++) {
-            const u64 *r = ctx->h_small + SM_CHSLOT + b * CH_SLOT_WORDS;
+        for (int q = 0; q < B; q++) {
+            const u64 *r = ctx->h_small + SM_CHSLOT + q * CH_SLOT_WORDS;
             // 32 algorithmic bytes per list element and round: position + head in, three successor ranks, position + head out, rank update
-            if (nchunks) { ctx->tm.k[BWTS_K_ROUND].elems += a_chunks; ctx->tm.k[BWTS_K_ROUND].alg_bytes += 32 * a_chunks; }
+            if (c.nchunks) { ctx->tm.k[BWTS_K_ROUND].elems += a_chunks; ctx->tm.k[BWTS_K_ROUND].alg_bytes += 32 * a_chunks; }
             if (finished) continue;          // (a round enqueued behind the last one: it ran, over what was left, and changed nothing)
-            rounds++;
+            c.rounds++;
             if (r[CHS_ERR]) {
-                if (round_trace) fprintf(stderr, "[chunks] chunk %llu of %u: group [%d, %d) plen %llu len %llu rp %llu slot %llu\n", (unsigned long long)r[5] - 1, nchunks,
-                                         (int)(r[6] >> 32), (int)(u32)r[6], (unsigned long long)(r[7] >> 48), (unsigned long long)((r[7] >> 32) & 0xffff),
-                                         (unsigned long long)((r[7] >> 16) & 0xffff), (unsigned long long)(r[7] & 0xffff));
+                if (c.trace) fprintf(stderr, "[chunks] chunk %llu of %u: group [%d, %d) plen %llu len %llu rp %llu slot %llu\n", (unsigned long long)r[5] - 1, c.nchunks,
+                                     (int)(r[6] >> 32), (int)(u32)r[6], (unsigned long long)(r[7] >> 48), (unsigned long long)((r[7] >> 32) & 0xffff),
+                                     (unsigned long long)((r[7] >> 16) & 0xffff), (unsigned long long)(r[7] & 0xffff));
                 CH_FAIL("a chunk met a group larger than it may hold");
             }
-            const u64 in_chunks = nchunks ? r[CHS_TOTAL] : 0;
+            const u64 in_chunks = c.nchunks ? r[CHS_TOTAL] : 0;
             u64 m_exit = 0, m_stay = 0;
-            if (m_big) {
+            if (b.m) {
                 m_exit = r[CHS_EXIT]; m_stay = r[CHS_STAY];
-                big_groups = r[CHS_BIGGROUPS];
-                if (m_exit + m_stay > m_big || tail + m_exit > a0 || big_groups * (CH_GROUP_MAX + 1) > m_stay) CH_FAIL("big list split counts");
+                b.groups = r[CHS_BIGGROUPS];
+                if (m_exit + m_stay > b.m || c.tail + m_exit > a0 || b.groups * (CH_GROUP_MAX + 1) > m_stay) CH_FAIL("big list split counts");
             }
             if (in_chunks > a_chunks) CH_FAIL("chunks grew");
 #ifdef CH_PROFILE
-            if (round_trace && b == 0) {
+            if (c.trace && q == 0) {
                 (void)hipMemcpy(ctx->h_small + SM_CHSLOT + 64, ctx->d_small + SM_CHSLOT + 64, 64 * 8 * sizeof(u64), hipMemcpyDeviceToHost);
                 double ph[6] = {0, 0, 0, 0, 0, 0}, tot = 0;
-                for (int q = 0; q < 64; q++) for (int i = 0; i < 6; i++) ph[i] += (double)ctx->h_small[SM_CHSLOT + 64 + 8 * q + i];
+                for (int w = 0; w < 64; w++) for (int i = 0; i < 6; i++) ph[i] += (double)ctx->h_small[SM_CHSLOT + 64 + 8 * w + i];
                 for (int i = 0; i < 6; i++) tot += ph[i];
                 fprintf(stderr, "[chunks] phase shares: load %.1f%% detect %.1f%% gather %.1f%% count %.1f%% emit/moves %.1f%% write %.1f%%  (cycles per element %.2f)\n", 100 * ph[0] / tot, 100 * ph[1] / tot,
                         100 * ph[2] / tot, 100 * ph[3] / tot, 100 * ph[4] / tot, 100 * ph[5] / tot, tot / (double)(a_chunks ? a_chunks : 1));
                 (void)hipMemset(ctx->d_small + SM_CHSLOT + 64, 0, 64 * 8 * sizeof(u64));
             }
 #endif
-            if (round_trace) fprintf(stderr, "[chunks] round %u h %llu: chunks %llu -> %llu, big list %llu -> stays %llu, leaves %llu\n", rounds,
-                                     (unsigned long long)hs[b], (unsigned long long)a_chunks, (unsigned long long)in_chunks, (unsigned long long)m_big, (unsigned long long)m_stay, (unsigned long long)m_exit);
-            if (m_exit) {
-                const u32 add = (u32)((m_exit + S - 1) / S);
-                if ((u64)nchunks + add > maxchunks) CH_FAIL("chunk table full");
-                chunk_init_kernel<<<dim3((add + 3) / 4), dim3(256), 0, ctx->stream>>>(st_head, tail, tail + m_exit, S, nchunks, add, cstart, ccount, mvcount, cwide, true);
-                wide_possible = true;
-                CH_HIP(hipGetLastError());
-                nchunks += add;
-                tail += m_exit;
-            }
-            if (m_big) { blc ^= 1; m_big = m_stay; }
+            if (c.trace) fprintf(stderr, "[chunks] round %u h %llu: chunks %llu -> %llu, big list %llu -> stays %llu, leaves %llu\n", c.rounds,
+                                 (unsigned long long)hs[q], (unsigned long long)a_chunks, (unsigned long long)in_chunks, (unsigned long long)b.m, (unsigned long long)m_stay, (unsigned long long)m_exit);
+            if (m_exit) CH_TRY(cut_chunks(ctx, c, c.tail, c.tail + m_exit, c.nchunks, true));
+            if (b.m) { b.cur ^= 1; b.m = m_stay; }
             a_chunks = in_chunks + m_exit;
-            const u64 left = a_chunks + m_big;
-            if (CYCLIC && rounds - 1 < BWTS_MAX_ROUND_STATS) ctx->tm.round_active[rounds - 1] = left;
+            const u64 left = a_chunks + b.m;
+            if (CYCLIC && c.rounds - 1 < BWTS_MAX_ROUND_STATS) ctx->tm.round_active[c.rounds - 1] = left;
             if (left == 0) { finished = true; continue; }
             // no group split: the partition is stable under doubling -- what is left are groups of equal infinite words
             if (CYCLIC && r[CHS_SPLIT] == 0) {
-                if (round_trace) fprintf(stderr, "[chunks] round %u: no group split, %llu elements left in groups of equal infinite words\n", rounds, (unsigned long long)left);
+                if (c.trace) fprintf(stderr, "[chunks] round %u: no group split, %llu elements left in groups of equal infinite words\n", c.rounds, (unsigned long long)left);
                 finished = true; stable = true; continue;
             }
-            if (!CYCLIC && hs[b] >= n) CH_FAIL("suffixes still tied at h >= n");      // suffixes are distinct; cannot happen
-            if (rounds > 80) CH_FAIL("more than 80 rounds");
+            if (!CYCLIC && hs[q] >= n) CH_FAIL("suffixes still tied at h >= n");      // suffixes are distinct; cannot happen
+            if (c.rounds > 80) CH_FAIL("more than 80 rounds");
         }
-        if (!finished && nchunks >= 64 && a_chunks > 0 && a_chunks * 3 < tail) {
-            // the chunks are two thirds empty: a dense list, new chunks (chunk_compact_kernel)
-            SpanGuard g(ctx, BWTS_K_ROUND, 0, 0);
-            chunk_total_kernel<<<dim3(1), dim3(1024), 0, ctx->stream>>>(ccount, nchunks, (unsigned long long *)(slots + 3 * CH_SLOT_WORDS), coff);
-            chunk_compact_kernel<<<dim3(nchunks), dim3(256), 0, ctx->stream>>>(st_idx, st_head, cstart, ccount, coff, alt_idx, alt_head);
-            { u32 *t = st_idx; st_idx = alt_idx; alt_idx = t; t = st_head; st_head = alt_head; alt_head = t; }
-            S = chunk_nominal_size(a_chunks);
-            const u32 nc = (u32)((a_chunks + S - 1) / S);
-            if (round_trace) fprintf(stderr, "[chunks] list compacted: %llu elements of %llu slots, %u chunks -> %u (nominal chunk %u)\n", (unsigned long long)a_chunks,
-                                     (unsigned long long)tail, nchunks, nc, S);
-            nchunks = nc;
-            chunk_init_kernel<<<dim3((nchunks + 3) / 4), dim3(256), 0, ctx->stream>>>(st_head, 0, a_chunks, S, 0, nchunks, cstart, ccount, mvcount, cwide, wide_possible);
-            CH_HIP(hipGetLastError());
-            tail = a_chunks;
-        }
+        if (!finished && c.nchunks >= 64 && a_chunks > 0 && a_chunks * 3 < c.tail) CH_TRY(compact_chunks(ctx, c, a0, a_chunks));
     }
-    if (need_sa) {
-        SpanGuard g(ctx, BWTS_K_RERANK, n, 8 * n);
-        u64 blocks = (n + 255) / 256; if (blocks > 16384) blocks = 16384;
-        sa_from_rank_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(sp.rank, n, SA);
-        CH_HIP(hipGetLastError());
-    }
-    if (stable) {
-        // (a round enqueued behind the stable one has split nothing either: the lists are what they were)
-        SpanGuard g(ctx, BWTS_K_EMIT, a_chunks + m_big, 10 * (a_chunks + m_big));
-        if (nchunks && a_chunks) {
-            chunk_rest_records_kernel<<<dim3(nchunks), dim3(256), 0, ctx->stream>>>(st_idx, st_head, cstart, ccount, mv, mvcount);
-            chunk_apply_records_kernel<1><<<dim3(nchunks), dim3(256), 0, ctx->stream>>>(mv, cstart, mvcount, RecordTargets{sp.rank, prev, out, need_sa ? SA : nullptr});
-            CH_HIP(hipGetLastError());
-        }
-        if (m_big) {
-            DgRestIn rin{bl_head[blc]};
-            DgRestOut rout{bl_idx[blc], bl_head[blc], prev, out, need_sa ? SA : nullptr};
-            CH_TRY((device_scan<true, u32>(ctx, m_big, rin, rout, OpMax(), 0u, sp.scan_temp)));
-        }
-    }
-    *rounds_io = rounds;
+    CH_TRY(chunk_finish(ctx, c, sp, n, SA, need_sa, stable, a_chunks));
+    *rounds_io = c.rounds;
     return BWTS_OK;
+}
 #undef CH_FAIL
 #undef CH_TRY
 #undef CH_HIP
-}

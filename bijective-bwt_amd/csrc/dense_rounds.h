@@ -480,6 +480,35 @@ static int build_ranks(bwts_ctx *ctx, const u32 *SA, u64 n, const ActiveList &l,
     return BWTS_OK;
 }
 
+static int sa_from_ranks(bwts_ctx *ctx, const u32 *rank, u64 n, u32 *SA)
+{
+    SpanGuard g(ctx, BWTS_K_RERANK, n, 8 * n);
+    u64 blocks = (n + 255) / 256; if (blocks > 16384) blocks = 16384;
+    sa_from_rank_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(rank, n, SA);
+    HIPC(hipGetLastError());
+    return BWTS_OK;
+}
+
+// The larger groups' sort, LSD over two key words: stable by (rank at 2h, rank at 3h) -- the second keys' copy in bk[1], the element
+// index in bv1 --, then by (group ordinal, rank at h), the first keys in bk[0], fetched through the index.  sk1, sv1: the second buffers.
+static int two_word_sort(bwts_ctx *ctx, const SortSpace &sp, u64 *const bk[2], u32 *bv1, u64 *sk1, u32 *sv1, u64 m, int rb, int big_bits,
+                         const u64 **sorted_keys, const u32 **sorted_src)
+{
+    SortPlan bp = sort_plan(bk[1], sk1, bv1, sv1, sp.tile_hist, sp.scan_temp);
+    int r1 = 0, r2 = 0;
+    BWTS_TRY(radix_sort_pairs(ctx, bp, m, 2 * rb, &r1));
+    {
+        SpanGuard g(ctx, BWTS_K_RERANK, m, 20 * m);
+        dg_stage2_keys_kernel<<<dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream>>>(bp.vals[r1], bk[0], m, bp.keys[r1]);
+        HIPC(hipGetLastError());
+    }
+    bp = sort_plan(bp.keys[r1], bp.keys[r1 ^ 1], bp.vals[r1], bp.vals[r1 ^ 1], sp.tile_hist, sp.scan_temp);
+    BWTS_TRY(radix_sort_pairs(ctx, bp, m, big_bits, &r2));
+    *sorted_keys = bp.keys[r2];
+    *sorted_src = bp.vals[r2];
+    return BWTS_OK;
+}
+
 // The rounds after round 0 when many elements are tied (dense rank array in sp.rank): see dense_round_kernel.
 // cur: the tied list left by round 0 (group-contiguous).  On return the ranks in sp.rank are final (members of a group
 // of equal infinite words share their group's first slot); with need_sa the suffix array is rebuilt from them.
@@ -489,19 +518,16 @@ static int dense_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
 {
     if (a > 0xffffffffull) return BWTS_E_NOMEM;     // every position tied at n = 2^32: beyond what the side buffers hold
     u64 *cnt = ctx->d_small + SM_DGCNT;
-    const size_t e4 = align_up((size_t)a * 4, 256), e1 = align_up((size_t)a, 256);
     char *base = nullptr;
-    const size_t tb4 = align_up(((size_t)a / DG_OWN + 3) * 4, 256);
-    BWTS_TRY(aux_reserve(ctx, 6 * e4 + e1 + tb4, &base));
-    u32 *tile_big = (u32 *)(base + 6 * e4 + e1);
-    u32 *t_idx = (u32 *)base, *t_head = (u32 *)(base + e4);
-    u8 *state = (u8 *)(base + 2 * e4);
-    ActiveList sets[2];        // the rounds' working lists
-    for (int i = 0; i < 2; i++) {
-        sets[i].idx = (u32 *)(base + 2 * e4 + e1 + (size_t)(2 * i) * e4);
-        sets[i].head = (u32 *)(base + 2 * e4 + e1 + (size_t)(2 * i + 1) * e4);
-        sets[i].slot = nullptr;
-    }
+    u32 *tile_big, *t_idx, *t_head;
+    u8 *state;
+    ActiveList sets[2] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};        // the rounds' working lists
+    BlockLayout L;
+    L.array(&t_idx, a); L.array(&t_head, a); L.array(&state, a);
+    for (int i = 0; i < 2; i++) { L.array(&sets[i].idx, a); L.array(&sets[i].head, a); }
+    L.array(&tile_big, a / DG_OWN + 3);
+    BWTS_TRY(aux_reserve(ctx, L.bytes(), &base));
+    L.place(base);
     const int rb = CYCLIC ? bitlen_u64(n - 1) : bitlen_u64(n);
     PrevSym prev{sp.carry_src, d_T, n, d_fstart, k};
     u8 *out = CYCLIC ? sp.carry_out : nullptr;
@@ -511,14 +537,13 @@ static int dense_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
     if (a >= (1ull << 16)) {
         // groups in the order of their smallest position (see dg_minpos_kernel); the sorted list lands in sets[0]
         char *ob = nullptr;
-        const size_t a8 = align_up((size_t)a * 8, 256);
-        const int orc = aux_reserve_slot(ctx, 1, 2 * a8 + 2 * e4, &ob);
+        SortPlan op = sort_plan(nullptr, nullptr, nullptr, nullptr, sp.tile_hist, sp.scan_temp);
+        BlockLayout O;
+        O.array(&op.keys[0], a); O.array(&op.keys[1], a); O.array(&op.vals[0], a); O.array(&op.vals[1], a);
+        const int orc = aux_reserve_slot(ctx, 1, O.bytes(), &ob);
         if (orc != BWTS_OK && orc != BWTS_E_NOMEM) return orc;
         if (orc == BWTS_OK) {      // (no room for the sort buffers, e.g. text at n = 2^32: the rounds run on the list as it is)
-            SortPlan op;
-            op.keys[0] = (u64 *)ob; op.keys[1] = (u64 *)(ob + a8);
-            op.vals[0] = (u32 *)(ob + 2 * a8); op.vals[1] = (u32 *)(ob + 2 * a8 + e4);
-            op.tile_hist = sp.tile_hist; op.scan_temp = sp.scan_temp;
+            O.place(ob);
             {
                 SpanGuard g(ctx, BWTS_K_RERANK, a, 20 * a);
                 dg_minpos_kernel<<<dim3((unsigned)((a + DG_OWN - 1) / DG_OWN)), dim3(DG_THREADS), 0, ctx->stream>>>(cur.idx, cur.head, a, n, kb, op.keys[0], op.vals[0]);
@@ -558,14 +583,14 @@ static int dense_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
         if (m_big) {
             // larger groups: compact (with the successor ranks), radix sort by (group ordinal, successor rank), regroup, put back
             char *bb = nullptr;
-            const size_t m8 = align_up((size_t)m_big * 8, 256), m4 = align_up((size_t)m_big * 4, 256);
-            BWTS_TRY(aux_reserve_slot(ctx, 1, 4 * m8 + 4 * m4, &bb));
             // [first keys | second buffer] [positions | second buffer] [list slots] [second keys] [sort buffer] [index buffer]
-            u64 *bk[2] = {(u64 *)bb, (u64 *)(bb + m8)};
-            u32 *bv[2] = {(u32 *)(bb + 2 * m8), (u32 *)(bb + 2 * m8 + m4)};
-            u32 *bpos = (u32 *)(bb + 2 * m8 + 2 * m4);
-            u64 *k23 = (u64 *)(bb + 2 * m8 + 3 * m4), *sk1 = (u64 *)(bb + 3 * m8 + 3 * m4);
-            u32 *sv1 = (u32 *)(bb + 4 * m8 + 3 * m4);
+            u64 *bk[2], *k23, *sk1;
+            u32 *bv[2], *bpos, *sv1;
+            BlockLayout B;
+            B.array(&bk[0], m_big); B.array(&bk[1], m_big); B.array(&bv[0], m_big); B.array(&bv[1], m_big); B.array(&bpos, m_big);
+            B.array(&k23, m_big); B.array(&sk1, m_big); B.array(&sv1, m_big);
+            BWTS_TRY(aux_reserve_slot(ctx, 1, B.bytes(), &bb));
+            B.place(bb);
             {
                 SpanGuard g(ctx, BWTS_K_RERANK, m_big, 4 * (a / DG_OWN) + 30 * m_big);
                 BWTS_TRY(exclusive_sum_u32(ctx, tile_big, rtiles + 1, sp.scan_temp));
@@ -577,26 +602,9 @@ static int dense_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
             }
             int big_bits = bitlen_u64(m_big / (DG_CAP + 1)) + rb;          // ordinals < m_big / (DG_CAP + 1)
             if (big_bits > 64) return BWTS_E_RANGE;
-            SortPlan bp;
-            bp.tile_hist = sp.tile_hist; bp.scan_temp = sp.scan_temp;
-            int rbig = 0;
-            // LSD over two key words: stable sort by (rank at 2h, rank at 3h), then by (group ordinal, rank at h)
-            bp.keys[0] = bk[1]; bp.keys[1] = sk1;
-            bp.vals[0] = bv[1]; bp.vals[1] = sv1;
-            int r1 = 0;
-            BWTS_TRY(radix_sort_pairs(ctx, bp, m_big, 2 * rb, &r1));
-            u64 *kin = bp.keys[r1], *kout = bp.keys[r1 ^ 1];
-            u32 *vin = bp.vals[r1], *vout = bp.vals[r1 ^ 1];
-            {
-                SpanGuard g(ctx, BWTS_K_RERANK, m_big, 20 * m_big);
-                dg_stage2_keys_kernel<<<dim3((unsigned)((m_big + 255) / 256)), dim3(256), 0, ctx->stream>>>(vin, bk[0], m_big, kin);
-                HIPC(hipGetLastError());
-            }
-            bp.keys[0] = kin; bp.keys[1] = kout;
-            bp.vals[0] = vin; bp.vals[1] = vout;
-            BWTS_TRY(radix_sort_pairs(ctx, bp, m_big, big_bits, &rbig));
-            const u64 *sorted_k1 = bp.keys[rbig];
-            const u32 *src = bp.vals[rbig], *positions = bv[0];
+            const u64 *sorted_k1 = nullptr;
+            const u32 *src = nullptr, *positions = bv[0];
+            BWTS_TRY(two_word_sort(ctx, sp, bk, bv[1], sk1, sv1, m_big, rb, big_bits, &sorted_k1, &src));
             {
                 SpanGuard g(ctx, BWTS_K_RERANK, m_big, 36 * m_big);
                 DgRegroupIn rin{sorted_k1, m_big, rb, src, k23};
@@ -631,12 +639,7 @@ static int dense_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
         if (!CYCLIC && h >= n) return BWTS_E_INTERNAL;  // suffixes are distinct; cannot happen
         if (rounds > 80) return BWTS_E_INTERNAL;
     }
-    if (need_sa) {
-        SpanGuard g(ctx, BWTS_K_RERANK, n, 8 * n);
-        u64 blocks = (n + 255) / 256; if (blocks > 16384) blocks = 16384;
-        sa_from_rank_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(sp.rank, n, SA);
-        HIPC(hipGetLastError());
-    }
+    if (need_sa) BWTS_TRY(sa_from_ranks(ctx, sp.rank, n, SA));
     if (a) {
         // groups of equal infinite words: their members take the group's slots in list order
         SpanGuard g(ctx, BWTS_K_EMIT, a, 10 * a);

@@ -274,10 +274,7 @@ static int set_alphabet(bwts_ctx *ctx, bool reserve_pad, u64 n, Alphabet *al, co
                     HIPC(hipMemsetAsync(ctx->d_small + CNT_SAMPLE, 0, 8 * sizeof(u64), ctx->stream));
                     SpanGuard g(ctx, BWTS_K_KEYBUILD, KEY_SAMPLES, 0);
                     sample_keys_kernel<<<dim3(KEY_SAMPLES / 256), dim3(256), 0, ctx->stream>>>(ss->T, n, ctx->d_small + SM_VTAB, KEY_SAMPLES, ss->k[0]);
-                    SortPlan spn;
-                    spn.keys[0] = ss->k[0]; spn.keys[1] = ss->k[1];
-                    spn.vals[0] = ss->v[0]; spn.vals[1] = ss->v[1];
-                    spn.tile_hist = ss->tile_hist; spn.scan_temp = ss->scan_temp;
+                    SortPlan spn = sort_plan(ss->k[0], ss->k[1], ss->v[0], ss->v[1], ss->tile_hist, ss->scan_temp);
                     int sres = 0;
                     BWTS_TRY(radix_sort_pairs(ctx, spn, KEY_SAMPLES, 64, &sres));
                     count_prefix_matches_kernel<<<dim3(KEY_SAMPLES / 256), dim3(256), 0, ctx->stream>>>(
@@ -1379,20 +1376,22 @@ __global__ __launch_bounds__(256) void seg_writeback_kernel(const u64 *__restric
 #include "dense_rounds.h"
 #include "chunk_rounds.h"
 
-// Sorts all positions by their (cyclic | suffix) word.  sp.keys[0]/sp.vals[0] hold the round-0
-// keys and the identity on entry.  want_ranks: leave final ranks in sp.rank (ISA for the suffix sort).
-template <bool CYCLIC>
-static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, const u32 *d_fstart, u64 k,
-                         SortSpace &sp, bool want_ranks, u32 **sa_out, u32 *rounds_out, u64 *active0_out)
-{
-    const u8 *d_codes = (const u8 *)(ctx->d_small + SM_CODES);
-    u64 *cnt = ctx->d_small + SM_COUNTERS;
+// What round 0 leaves for the stages after it
+struct Round0 {
+    int res;                        // which of sp.keys[] / sp.vals[] holds the sorted keys and the suffix array
+    K0Keys k0v;                     // the sorted keys: u64 each, or split as the packed passes leave them
+    u32 *SA;
+    u64 *headw, *keepw, *pre;       // group flags (64 slots per word) and the word scan
+    bool flags_outside_rank;        // the flag words lie in the carried-byte buffers, not in sp.rank
+    u64 a;                          // tied elements
+};
 
-    // ---- round 0 ------------------------------------------------------------------
-    SortPlan plan;
-    plan.keys[0] = sp.keys[0]; plan.keys[1] = sp.keys[1];
-    plan.vals[0] = sp.vals[0]; plan.vals[1] = sp.vals[1];
-    plan.tile_hist = sp.tile_hist; plan.scan_temp = sp.scan_temp;
+// Round 0: the radix sort of the keys that keybuild0 left in sp.keys[0] (values: the identity), group flags, their word scan, the tied count
+template <bool CYCLIC>
+static int round0_sort(bwts_ctx *ctx, u64 n, const Alphabet &al, SortSpace &sp, Round0 *r0)
+{
+    u64 *cnt = ctx->d_small + SM_COUNTERS;
+    SortPlan plan = sort_plan(sp.keys[0], sp.keys[1], sp.vals[0], sp.vals[1], sp.tile_hist, sp.scan_temp);
     plan.sym_src = sp.carry_src; plan.sym_buf[0] = sp.carry_buf[0]; plan.sym_buf[1] = sp.carry_buf[1]; plan.sym_final = sp.carry_out;
     plan.vals_identity = true;     // keybuild0 writes no value array
     plan.keys_split = CYCLIC && sp.split_keys && plan.sym_final;
@@ -1405,12 +1404,6 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
     u64 *K0 = sp.keys[res];
     K0Keys k0v{K0, nullptr, nullptr};
     if (plan.keys_split) k0v = K0Keys{nullptr, (const u32 *)K0, al.key_bits > 32 ? (const u8 *)K0 + align_up((size_t)n * 4, 256) : nullptr};
-    u32 *SA = sp.vals[res];
-    // the other key buffer (8n bytes) and value buffer (4n) are free: first active list goes there
-    ActiveList cur;
-    cur.idx = (u32 *)sp.keys[res ^ 1];
-    cur.slot = cur.idx + n;
-    cur.head = sp.vals[res ^ 1];
 
     HIPC(hipMemsetAsync(cnt, 0, 4 * sizeof(u64), ctx->stream));
     const u64 words = (n + 63) / 64;
@@ -1439,226 +1432,250 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
         STAGE("group flags + word scan + count");
     }
     BWTS_TRY(read_small(ctx, SM_COUNTERS, 4));
-    u64 a = ctx->h_small[CNT_ACTIVE];
+    *r0 = Round0{res, k0v, sp.vals[res], headw, keepw, pre, flags_outside_rank, ctx->h_small[CNT_ACTIVE]};
+    return BWTS_OK;
+}
+
+// Many ties: the dense rank array.  It is built BEFORE the tied list, while the list's future home (the other key
+// buffer) is still free: the build sorts one u64 per slot between that buffer and the sorted keys' (not needed any
+// more without the sparse rank map).
+static int early_ranks(bwts_ctx *ctx, u64 n, SortSpace &sp, const Round0 &r0)
+{
+    BWTS_TRY(ensure_rank(ctx, sp, n));
+    SpanGuard g(ctx, BWTS_K_RERANK, n, 28 * n);
+    u64 *rk[2] = {sp.keys[r0.res ^ 1], sp.keys[r0.res]};
+    u64 blocks = (n + 255) / 256; if (blocks > 16384) blocks = 16384;
+    rank_keys_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(r0.SA, n, r0.headw, r0.pre, rk[0]);
+    HIPC(hipGetLastError());
+    // sorted on the position's top 16 bits (24 beyond n = 2^30): windows of at most 2^RA_WLOG_MAX positions
+    const int pb = bitlen_u64(n - 1);
+    const int sbits = pb - 16 <= RA_WLOG_MAX ? 16 : 24;
+    int rres = 0;
+    BWTS_TRY(radix_sort_keys(ctx, rk, sp.tile_hist, sp.scan_temp, n, pb - sbits, sbits, &rres));
+    const int wlog = RA_WLOG_MAX;                   // sorted on at least the bits above 2^14: every 2^14 keys are 2^14 consecutive positions
+    BWTS_TRY(ensure_dyn_lds(ctx, (const void *)rank_apply_kernel, (size_t)4 << RA_WLOG_MAX));
+    rank_apply_kernel<<<dim3((unsigned)((n + (1ull << wlog) - 1) >> wlog)), dim3(1024), (size_t)4 << wlog, ctx->stream>>>(rk[rres], n, wlog, sp.rank);
+    HIPC(hipGetLastError());
+    return BWTS_OK;
+}
+
+// The tied list, in the key and value buffers that round 0 left free (8n + 4n bytes)
+static int tied_list(bwts_ctx *ctx, u64 n, SortSpace &sp, const Round0 &r0, ActiveList *cur)
+{
+    u64 *cnt = ctx->d_small + SM_COUNTERS;
+    cur->idx = (u32 *)sp.keys[r0.res ^ 1];
+    cur->slot = cur->idx + n;
+    cur->head = sp.vals[r0.res ^ 1];
+    SpanGuard g(ctx, BWTS_K_RERANK, r0.a, 12 * r0.a);
+    const u64 waves = ((n + 63) / 64 + 63) / 64;
+    const unsigned blocks = (unsigned)((waves + 3) / 4 < 16384 ? (waves + 3) / 4 : 16384);
+    tied_from_flags_kernel<<<dim3(blocks), dim3(256), 0, ctx->stream>>>(r0.headw, r0.keepw, r0.pre, n, r0.SA, cur->idx, cur->slot, cur->head, cnt + 0);
+    HIPC(hipGetLastError());
+    STAGE("tied list");
+    sp.tie_slots = cur->slot;        // stays untouched by the later rounds
+    sp.tie_count = r0.a;
+    return BWTS_OK;
+}
+
+// the buffers of the sparse rounds' small-groups path: flags, compacted keys x2, values x2, slots of the larger groups
+struct SegBufs { u8 *big; u64 *bk[2]; u32 *bv[2], *bpos; };
+
+// Groups of <= SEG_CAP sort in place, the rest go through the radix sort (see seg_small_sort_kernel).  *whole = true: the larger
+// groups hold nearly all of the list and nothing more was done -- the caller sorts everything; else K, V hold the sorted round.
+static int seg_sort_round(bwts_ctx *ctx, SortSpace &sp, const SegBufs &sb, const u32 *head, u64 *K, u32 *V, u64 a, int rb, int round_key_bits,
+                          bool *whole, bool *skip_next)
+{
+    u64 *cnt = ctx->d_small + SM_COUNTERS;
+    u64 m_big = 0;
+    {
+        SpanGuard g(ctx, BWTS_K_RERANK, a, 20 * a);
+        u64 *segcnt = ctx->d_small + SM_SEGCNT;
+        HIPC(hipMemsetAsync(segcnt, 0, 256 * sizeof(u64), ctx->stream));
+        const u64 waves = (a + SEG_OWN - 1) / SEG_OWN;
+        seg_small_sort_kernel<<<dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, ctx->stream>>>(head, K, V, a, sb.big, segcnt);
+        HIPC(hipGetLastError());
+    }
+    BWTS_TRY(read_small(ctx, SM_SEGCNT, 256));
+    for (int c = 0; c < 256; c++) m_big += ctx->h_small[SM_SEGCNT + c];
+    if (m_big > a) return BWTS_E_INTERNAL;
+    *skip_next = m_big * 10 > a * 9;
+    // larger groups hold nearly all of the list: sorting everything costs less than compacting them
+    // (by bytes moved the break-even is near 85 %)
+    *whole = m_big * 5 > a * 4;
+    if (*whole || !m_big) return BWTS_OK;
+    {
+        SpanGuard g(ctx, BWTS_K_RERANK, a, 20 * a);
+        SegFlagIn fin{sb.big, head};
+        SegBigOut fout{sb.big, head, K, V, a, rb, sb.bk[0], sb.bv[0], sb.bpos, cnt + 3};
+        BWTS_TRY((device_scan<false, u64>(ctx, a, fin, fout, OpAdd(), (u64)0, sp.scan_temp)));
+    }
+    const SortPlan bp = sort_plan(sb.bk[0], sb.bk[1], sb.bv[0], sb.bv[1], sp.tile_hist, sp.scan_temp);
+    int rbig = 0;
+    const int big_bits = bitlen_u64(m_big / (SEG_CAP + 1)) + rb;       // ordinals < m_big / (SEG_CAP + 1)
+    BWTS_TRY(radix_sort_pairs(ctx, bp, m_big, big_bits < round_key_bits ? big_bits : round_key_bits, &rbig));
+    SpanGuard g(ctx, BWTS_K_RERANK, m_big, 28 * m_big);
+    seg_writeback_kernel<<<dim3((unsigned)((m_big + 255) / 256)), dim3(256), 0, ctx->stream>>>(sb.bk[rbig], sb.bv[rbig], sb.bpos, m_big, head, rb, K, V);
+    HIPC(hipGetLastError());
+    return BWTS_OK;
+}
+
+// The rounds after round 0 when few elements are tied: sparse ranks (a map from the tied positions to their heads, everything else
+// ranked by a search in the sorted round-0 keys), the list in SA order, a sort per round.  cur, *a_io: the tied list; on return what is
+// still tied (groups of equal infinite words).
+template <bool CYCLIC>
+static int sparse_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, const u32 *d_fstart, u64 k, SortSpace &sp,
+                         const Round0 &r0, ActiveList *cur_io, u64 *a_io, u32 *rounds_io)
+{
+    const u8 *d_codes = (const u8 *)(ctx->d_small + SM_CODES);
+    u64 *cnt = ctx->d_small + SM_COUNTERS;
+    const K0Keys &k0v = r0.k0v;
+    ActiveList cur = *cur_io;
+    u64 a = *a_io;
+    u32 rounds = *rounds_io;
+    const u64 a0 = a;
+    // aux: two key buffers, one value scratch, two list sets, the tied map, the two directories, the small-groups path's buffers
+    char *base = nullptr;
+    u64 *akeys[2], *dir_at;
+    u32 *scratch, *tpos, *trank, *pdir_at;
+    ActiveList sets[2];
+    SegBufs sb;
+    BlockLayout L;
+    L.array(&akeys[0], a); L.array(&akeys[1], a); L.array(&scratch, a);
+    for (int s = 0; s < 2; s++) { L.array(&sets[s].idx, a); L.array(&sets[s].slot, a); L.array(&sets[s].head, a); }
+    L.array(&tpos, a); L.array(&trank, a);
+    L.array(&dir_at, ((u64)1 << K0_DIR_LOG2_MAX) + 1); L.array(&pdir_at, ((u64)1 << K0_DIR_LOG2_MAX) + 2);
+    L.array(&sb.big, a); L.array(&sb.bk[0], a); L.array(&sb.bk[1], a); L.array(&sb.bv[0], a); L.array(&sb.bv[1], a); L.array(&sb.bpos, a);
+    BWTS_TRY(aux_reserve(ctx, L.bytes(), &base));
+    L.place(base);
+    const int rb = CYCLIC ? bitlen_u64(n - 1) : bitlen_u64(n);
+    if (2 * rb > 64) return BWTS_E_RANGE;
+    const int round_key_bits = 2 * rb > 1 ? 2 * rb : 1;
+    int nxt = 0;
+    u64 *dir = nullptr;
+    u32 *pdir = nullptr;
+    int dlog = 0, psh = 0;
+    {
+        SpanGuard g(ctx, BWTS_K_RERANK, a, 24 * a);
+        // directory over the sorted keys' top bits for the rank searches of keybuild_sparse_kernel
+        const int kb = al.key_bits;
+        dlog = kb < K0_DIR_LOG2_MAX ? kb : K0_DIR_LOG2_MAX;
+        if (dlog > bitlen_u64(n)) dlog = bitlen_u64(n);
+        if (dlog >= 8) {
+            dir = dir_at;
+            k0_directory_kernel<<<dim3((unsigned)(((1ull << dlog) + 1 + 255) / 256)), dim3(256), 0, ctx->stream>>>(k0v, n, kb, dlog, dir);
+        }
+        // split keys with a high byte: the rank searches compare low words alone (k0_lower_bound)
+        if (k0v.hi && (!dir || kb - dlog > 32)) return BWTS_E_INTERNAL;
+        tied_map_keys_kernel<<<dim3((unsigned)((a + 255) / 256)), dim3(256), 0, ctx->stream>>>(cur.idx, a, akeys[0]);
+        HIPC(hipMemcpyAsync(scratch, cur.head, a * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
+        const SortPlan mp = sort_plan(akeys[0], akeys[1], scratch, trank, sp.tile_hist, sp.scan_temp);
+        int mr = 0;
+        BWTS_TRY(radix_sort_pairs(ctx, mp, a, bitlen_u64(n - 1) > 0 ? bitlen_u64(n - 1) : 1, &mr));
+        tied_map_finish_kernel<<<dim3((unsigned)((a + 255) / 256)), dim3(256), 0, ctx->stream>>>(akeys[mr], a, tpos);
+        if (mr == 0) HIPC(hipMemcpyAsync(trank, scratch, a * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
+        if (dir) {          // same switch as the key directory: a directory over the map's positions
+            const int pb = bitlen_u64(n - 1);
+            psh = pb > K0_DIR_LOG2_MAX ? pb - K0_DIR_LOG2_MAX : 0;
+            const u64 buckets = ((n - 1) >> psh) + 1;
+            pdir = pdir_at;
+            tpos_directory_kernel<<<dim3((unsigned)((buckets + 1 + 255) / 256)), dim3(256), 0, ctx->stream>>>(tpos, a, psh, buckets, pdir);
+        }
+        HIPC(hipGetLastError());
+    }
+
+    bool seg_skip_next = false;
+    for (u64 h = (u64)al.hstep;; h <<= 1) {
+        rounds++;
+        {
+            SpanGuard g(ctx, BWTS_K_KEYBUILD, a, 20 * a);
+            const unsigned blocks = (unsigned)((a + 255) / 256);
+            keybuild_sparse_kernel<CYCLIC><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(
+                cur.idx, cur.head, a, d_T, n, d_codes, al.bits, al.msym, al.pad_add, h, k0v, rb, d_fstart, k, akeys[0],
+                al.varlen ? ctx->d_small + SM_VTAB : nullptr, al.key_bits, tpos, trank, a0, dir, dlog, pdir, psh);
+            HIPC(hipGetLastError());
+        }
+        const u64 *AK = akeys[0];
+        const u32 *AV = cur.idx;
+        // (large groups dominating one round dominate the next one too: then the classification is skipped every other round)
+        const bool seg_probe = !seg_skip_next;
+        seg_skip_next = false;
+        bool whole = true;
+        if (a > 4096 && seg_probe) BWTS_TRY(seg_sort_round(ctx, sp, sb, cur.head, akeys[0], cur.idx, a, rb, round_key_bits, &whole, &seg_skip_next));
+        if (whole) {
+            const SortPlan ap = sort_plan(akeys[0], akeys[1], cur.idx, scratch, sp.tile_hist, sp.scan_temp);
+            int r2 = 0;
+            BWTS_TRY(radix_sort_pairs(ctx, ap, a, round_key_bits, &r2));
+            AK = akeys[r2];
+            AV = r2 ? scratch : cur.idx;
+        }
+
+        HIPC(hipMemsetAsync(cnt, 0, 4 * sizeof(u64), ctx->stream));
+        {
+            SpanGuard g(ctx, BWTS_K_RERANK, a, 24 * a);
+            GroupIn in{AK, cur.slot, a, rb};
+            GroupOut out{cur.slot, AV, a, rb, AK, tpos, trank, a0, r0.SA,
+                         sets[nxt].idx, sets[nxt].slot, sets[nxt].head, cnt + 0, cnt + 1};
+            BWTS_TRY((device_scan<true, u64>(ctx, a, in, out, OpHeadCount(), (u64)0, sp.scan_temp)));
+        }
+        BWTS_TRY(read_small(ctx, SM_COUNTERS, 4));
+        const u64 a_new = ctx->h_small[CNT_ACTIVE];
+        const u64 splits = ctx->h_small[CNT_SPLITS];
+        cur = sets[nxt];
+        nxt ^= 1;
+        a = a_new;
+        if (CYCLIC && rounds - 1 < BWTS_MAX_ROUND_STATS) ctx->tm.round_active[rounds - 1] = a;
+        if (a == 0) break;
+        if (CYCLIC && splits == 0) break;               // partition stable under doubling: equal infinite words
+        if (!CYCLIC && h >= n) return BWTS_E_INTERNAL;  // suffixes are distinct; cannot happen
+        if (rounds > 80) return BWTS_E_INTERNAL;
+    }
+    *cur_io = cur;
+    *a_io = a;
+    *rounds_io = rounds;
+    return BWTS_OK;
+}
+
+// Sorts all positions by their (cyclic | suffix) word.  sp.keys[0]/sp.vals[0] hold the round-0
+// keys and the identity on entry.  want_ranks: leave final ranks in sp.rank (ISA for the suffix sort).
+// Round 0, the dense ranks when many elements are tied, the tied list, then the later rounds in one of three forms: sparse_rounds,
+// chunk_rounds, dense_rounds (tiles).
+template <bool CYCLIC>
+static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, const u32 *d_fstart, u64 k,
+                         SortSpace &sp, bool want_ranks, u32 **sa_out, u32 *rounds_out, u64 *active0_out)
+{
+    Round0 r0;
+    BWTS_TRY((round0_sort<CYCLIC>(ctx, n, al, sp, &r0)));
+    u64 a = r0.a;
+    u32 *SA = r0.SA;
     *active0_out = a;
     if (CYCLIC) ctx->tm.round_active[0] = a;
-    // Many ties: the dense rank array.  It is built BEFORE the tied list, while the list's future home (the other key
-    // buffer) is still free: the build sorts one u64 per slot between that buffer and the sorted keys' (not needed any
-    // more without the sparse rank map).
-    const bool rank_early = a > n / 32 && flags_outside_rank && n >= (1ull << 22);
-    if (rank_early) {
-        BWTS_TRY(ensure_rank(ctx, sp, n));
-        SpanGuard g(ctx, BWTS_K_RERANK, n, 28 * n);
-        u64 *rk[2] = {sp.keys[res ^ 1], K0};
-        u64 blocks = (n + 255) / 256; if (blocks > 16384) blocks = 16384;
-        rank_keys_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(SA, n, headw, pre, rk[0]);
-        HIPC(hipGetLastError());
-        // sorted on the position's top 16 bits (24 beyond n = 2^30): windows of at most 2^RA_WLOG_MAX positions
-        const int pb = bitlen_u64(n - 1);
-        const int sbits = pb - 16 <= RA_WLOG_MAX ? 16 : 24;
-        int rres = 0;
-        BWTS_TRY(radix_sort_keys(ctx, rk, sp.tile_hist, sp.scan_temp, n, pb - sbits, sbits, &rres));
-        const int wlog = RA_WLOG_MAX;                   // sorted on at least the bits above 2^14: every 2^14 keys are 2^14 consecutive positions
-        BWTS_TRY(ensure_dyn_lds(ctx, (const void *)rank_apply_kernel, (size_t)4 << RA_WLOG_MAX));
-        rank_apply_kernel<<<dim3((unsigned)((n + (1ull << wlog) - 1) >> wlog)), dim3(1024), (size_t)4 << wlog, ctx->stream>>>(rk[rres], n, wlog, sp.rank);
-        HIPC(hipGetLastError());
-    }
-    {
-        SpanGuard g(ctx, BWTS_K_RERANK, a, 12 * a);
-        const u64 waves = (words + 63) / 64;
-        const unsigned blocks = (unsigned)((waves + 3) / 4 < 16384 ? (waves + 3) / 4 : 16384);
-        tied_from_flags_kernel<<<dim3(blocks), dim3(256), 0, ctx->stream>>>(headw, keepw, pre, n, SA, cur.idx, cur.slot, cur.head, cnt + 0);
-        HIPC(hipGetLastError());
-        STAGE("tied list");
-    }
-    sp.tie_slots = cur.slot;        // stays untouched by the later rounds
-    sp.tie_count = a;
+    const bool rank_early = a > n / 32 && r0.flags_outside_rank && n >= (1ull << 22);
+    if (rank_early) BWTS_TRY(early_ranks(ctx, n, sp, r0));
+    ActiveList cur, none{nullptr, nullptr, nullptr};
+    BWTS_TRY(tied_list(ctx, n, sp, r0, &cur));
     u32 rounds = 1;
-    ActiveList none{nullptr, nullptr, nullptr};
 
-    if (a > 0) {
-        // every position tied at n = 2^32 (a constant or a two-symbol periodic input of exactly 4 GiB): the side buffers of the
-        // later rounds are sized by the tied count and do not fit next to the 36 n bytes of round 0
-        if (a > 0xffffffffull) return BWTS_E_NOMEM;
-        // few tied elements: sparse rank map; many (real text ties most m-grams): the dense rank array
-        const bool sparse = a <= n / 32;
-        // aux: two key buffers, one value scratch, two list sets (the group-local dense rounds lay out their own, smaller block)
-        char *base = nullptr;
-        const size_t e4 = align_up((size_t)a * 4, 256), e8 = align_up((size_t)a * 8, 256);
-        const size_t dir_bytes = align_up(((size_t)1 << K0_DIR_LOG2_MAX) * 8 + 8, 256) + align_up(((size_t)1 << K0_DIR_LOG2_MAX) * 4 + 8, 256);
-        const size_t e1 = align_up((size_t)a, 256);
-        const size_t seg_bytes = e1 + 2 * e8 + 3 * e4;            // flags, compacted keys x2, values x2, slots of the larger groups
-        if (sparse) BWTS_TRY(aux_reserve(ctx, 2 * e8 + 9 * e4 + dir_bytes + seg_bytes, &base));
-        u64 *akeys[2] = {(u64 *)base, (u64 *)(base + e8)};
-        char *q = base + 2 * e8;
-        u32 *scratch = (u32 *)q; q += e4;
-        ActiveList sets[2];
-        for (int s = 0; s < 2; s++) {
-            sets[s].idx = (u32 *)q; q += e4;
-            sets[s].slot = (u32 *)q; q += e4;
-            sets[s].head = (u32 *)q; q += e4;
-        }
-        const int rb = CYCLIC ? bitlen_u64(n - 1) : bitlen_u64(n);
-        if (2 * rb > 64) return BWTS_E_RANGE;
-        const int round_key_bits = 2 * rb > 1 ? 2 * rb : 1;
-        int nxt = 0;
-        u32 *tpos = nullptr, *trank = nullptr;
-        u64 *dir = nullptr;
-        u32 *pdir = nullptr;
-        int dlog = 0, psh = 0;
-        const u64 a0 = a;
-        if (sparse) {
-            SpanGuard g(ctx, BWTS_K_RERANK, a, 24 * a);
-            tpos = (u32 *)(base + 2 * e8 + 7 * e4);          // the last two arrays of the aux block
-            trank = (u32 *)(base + 2 * e8 + 8 * e4);
-            // directory over the sorted keys' top bits for the rank searches of keybuild_sparse_kernel
-            const int kb = al.key_bits;
-            dlog = kb < K0_DIR_LOG2_MAX ? kb : K0_DIR_LOG2_MAX;
-            if (dlog > bitlen_u64(n)) dlog = bitlen_u64(n);
-            if (dlog >= 8) {
-                dir = (u64 *)(base + 2 * e8 + 9 * e4);
-                k0_directory_kernel<<<dim3((unsigned)(((1ull << dlog) + 1 + 255) / 256)), dim3(256), 0, ctx->stream>>>(k0v, n, kb, dlog, dir);
-            }
-            // split keys with a high byte: the rank searches compare low words alone (k0_lower_bound)
-            if (k0v.hi && (!dir || kb - dlog > 32)) return BWTS_E_INTERNAL;
-            tied_map_keys_kernel<<<dim3((unsigned)((a + 255) / 256)), dim3(256), 0, ctx->stream>>>(cur.idx, a, akeys[0]);
-            HIPC(hipMemcpyAsync(scratch, cur.head, a * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
-            SortPlan mp;
-            mp.keys[0] = akeys[0]; mp.keys[1] = akeys[1];
-            mp.vals[0] = scratch; mp.vals[1] = trank;
-            mp.tile_hist = sp.tile_hist; mp.scan_temp = sp.scan_temp;
-            int mr = 0;
-            BWTS_TRY(radix_sort_pairs(ctx, mp, a, bitlen_u64(n - 1) > 0 ? bitlen_u64(n - 1) : 1, &mr));
-            tied_map_finish_kernel<<<dim3((unsigned)((a + 255) / 256)), dim3(256), 0, ctx->stream>>>(akeys[mr], a, tpos);
-            if (mr == 0) HIPC(hipMemcpyAsync(trank, scratch, a * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
-            if (dir) {          // same switch as the key directory: a directory over the map's positions
-                const int pb = bitlen_u64(n - 1);
-                psh = pb > K0_DIR_LOG2_MAX ? pb - K0_DIR_LOG2_MAX : 0;
-                const u64 buckets = ((n - 1) >> psh) + 1;
-                pdir = (u32 *)(base + 2 * e8 + 9 * e4 + align_up(((size_t)1 << K0_DIR_LOG2_MAX) * 8 + 8, 256));
-                tpos_directory_kernel<<<dim3((unsigned)((buckets + 1 + 255) / 256)), dim3(256), 0, ctx->stream>>>(tpos, a, psh, buckets, pdir);
-            }
-            HIPC(hipGetLastError());
-        } else {
-            BWTS_TRY(ensure_rank(ctx, sp, n));
-            if (!rank_early) BWTS_TRY(build_ranks(ctx, SA, n, cur, a, sp.rank));      // (else built before the tied list, see above)
-            // group-local rounds; SA is only rebuilt when someone reads it afterwards (suffix array requested, or the
-            // gather form of the emission)
-            const bool need_sa = !CYCLIC || !sp.carry_out;
-            // chunks (chunk_rounds.h) unless BWTS_DENSE=tiles asks for the tile form (dense_rounds.h), the list is short or memory is
-            const bool tiles_only = [ctx] { const char *e = bwts_knob(ctx, "BWTS_DENSE"); return e && !strcmp(e, "tiles"); }();
-            bool handled = false;
-            if (!tiles_only) BWTS_TRY((chunk_rounds<CYCLIC>(ctx, d_T, n, al, d_fstart, k, sp, cur, a, SA, need_sa, &rounds, &handled)));
-            if (!handled) BWTS_TRY((dense_rounds<CYCLIC>(ctx, d_T, n, al, d_fstart, k, sp, cur, a, SA, need_sa, &rounds)));
-            sp.ties_emitted = CYCLIC && sp.carry_out;
-            *sa_out = SA;
-            *rounds_out = rounds;
-            return BWTS_OK;
-        }
-
-        // ---- few ties: sparse ranks, the list in SA order, a sort per round ----
-
-        bool seg_skip_next = false;
-        for (u64 h = (u64)al.hstep;; h <<= 1) {
-            rounds++;
-            {
-                SpanGuard g(ctx, BWTS_K_KEYBUILD, a, 20 * a);
-                const unsigned blocks = (unsigned)((a + 255) / 256);
-                keybuild_sparse_kernel<CYCLIC><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(
-                    cur.idx, cur.head, a, d_T, n, d_codes, al.bits, al.msym, al.pad_add, h, k0v, rb, d_fstart, k, akeys[0],
-                    al.varlen ? ctx->d_small + SM_VTAB : nullptr, al.key_bits, tpos, trank, a0, dir, dlog, pdir, psh);
-                HIPC(hipGetLastError());
-            }
-            const u64 *AK;
-            const u32 *AV;
-            // (large groups dominating one round dominate the next one too: then the classification is skipped every other round)
-            const bool seg_probe = !seg_skip_next;
-            seg_skip_next = false;
-            if (a > 4096 && seg_probe) {
-                // groups of <= SEG_CAP in place, the rest through the radix sort (see seg_small_sort_kernel)
-                char *sb = base + 2 * e8 + 9 * e4 + dir_bytes;
-                u8 *big = (u8 *)sb;
-                u64 *bk[2] = {(u64 *)(sb + e1), (u64 *)(sb + e1 + e8)};
-                u32 *bv[2] = {(u32 *)(sb + e1 + 2 * e8), (u32 *)(sb + e1 + 2 * e8 + e4)};
-                u32 *bpos = (u32 *)(sb + e1 + 2 * e8 + 2 * e4);
-                u64 m_big = 0;
-                {
-                    SpanGuard g(ctx, BWTS_K_RERANK, a, 20 * a);
-                    u64 *segcnt = ctx->d_small + SM_SEGCNT;
-                    HIPC(hipMemsetAsync(segcnt, 0, 256 * sizeof(u64), ctx->stream));
-                    const u64 waves = (a + SEG_OWN - 1) / SEG_OWN;
-                    seg_small_sort_kernel<<<dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, ctx->stream>>>(cur.head, akeys[0], cur.idx, a, big, segcnt);
-                    HIPC(hipGetLastError());
-                }
-                BWTS_TRY(read_small(ctx, SM_SEGCNT, 256));
-                for (int c = 0; c < 256; c++) m_big += ctx->h_small[SM_SEGCNT + c];
-                if (m_big > a) return BWTS_E_INTERNAL;
-                seg_skip_next = m_big * 10 > a * 9;
-                if (m_big * 5 > a * 4) {
-                    // larger groups hold nearly all of the list: sorting everything costs less than compacting them
-                    // (by bytes moved the break-even is near 85 %)
-                    SortPlan ap;
-                    ap.keys[0] = akeys[0]; ap.keys[1] = akeys[1];
-                    ap.vals[0] = cur.idx; ap.vals[1] = scratch;
-                    ap.tile_hist = sp.tile_hist; ap.scan_temp = sp.scan_temp;
-                    int r2 = 0;
-                    BWTS_TRY(radix_sort_pairs(ctx, ap, a, round_key_bits, &r2));
-                    AK = akeys[r2];
-                    AV = r2 ? scratch : cur.idx;
-                } else {
-                    if (m_big) {
-                        {
-                            SpanGuard g(ctx, BWTS_K_RERANK, a, 20 * a);
-                            SegFlagIn fin{big, cur.head};
-                            SegBigOut fout{big, cur.head, akeys[0], cur.idx, a, rb, bk[0], bv[0], bpos, cnt + 3};
-                            BWTS_TRY((device_scan<false, u64>(ctx, a, fin, fout, OpAdd(), (u64)0, sp.scan_temp)));
-                        }
-                        SortPlan bp;
-                        bp.keys[0] = bk[0]; bp.keys[1] = bk[1];
-                        bp.vals[0] = bv[0]; bp.vals[1] = bv[1];
-                        bp.tile_hist = sp.tile_hist; bp.scan_temp = sp.scan_temp;
-                        int rbig = 0;
-                        const int big_bits = bitlen_u64(m_big / (SEG_CAP + 1)) + rb;       // ordinals < m_big / (SEG_CAP + 1)
-                        BWTS_TRY(radix_sort_pairs(ctx, bp, m_big, big_bits < round_key_bits ? big_bits : round_key_bits, &rbig));
-                        SpanGuard g(ctx, BWTS_K_RERANK, m_big, 28 * m_big);
-                        seg_writeback_kernel<<<dim3((unsigned)((m_big + 255) / 256)), dim3(256), 0, ctx->stream>>>(bk[rbig], bv[rbig], bpos, m_big, cur.head, rb,
-                                                                                                                 akeys[0], cur.idx);
-                        HIPC(hipGetLastError());
-                    }
-                    AK = akeys[0];
-                    AV = cur.idx;
-                }
-            } else {
-                SortPlan ap;
-                ap.keys[0] = akeys[0]; ap.keys[1] = akeys[1];
-                ap.vals[0] = cur.idx; ap.vals[1] = scratch;
-                ap.tile_hist = sp.tile_hist; ap.scan_temp = sp.scan_temp;
-                int r2 = 0;
-                BWTS_TRY(radix_sort_pairs(ctx, ap, a, round_key_bits, &r2));
-                AK = akeys[r2];
-                AV = r2 ? scratch : cur.idx;
-            }
-
-            HIPC(hipMemsetAsync(cnt, 0, 4 * sizeof(u64), ctx->stream));
-            {
-                SpanGuard g(ctx, BWTS_K_RERANK, a, 24 * a);
-                GroupIn in{AK, cur.slot, a, rb};
-                GroupOut out{cur.slot, AV, a, rb, AK, tpos, trank, a0, SA,
-                             sets[nxt].idx, sets[nxt].slot, sets[nxt].head, cnt + 0, cnt + 1};
-                BWTS_TRY((device_scan<true, u64>(ctx, a, in, out, OpHeadCount(), (u64)0, sp.scan_temp)));
-            }
-            BWTS_TRY(read_small(ctx, SM_COUNTERS, 4));
-            const u64 a_new = ctx->h_small[CNT_ACTIVE];
-            const u64 splits = ctx->h_small[CNT_SPLITS];
-            cur = sets[nxt];
-            nxt ^= 1;
-            a = a_new;
-            if (CYCLIC && rounds - 1 < BWTS_MAX_ROUND_STATS) ctx->tm.round_active[rounds - 1] = a;
-            if (a == 0) break;
-            if (CYCLIC && splits == 0) break;               // partition stable under doubling: equal infinite words
-            if (!CYCLIC && h >= n) return BWTS_E_INTERNAL;  // suffixes are distinct; cannot happen
-            if (rounds > 80) return BWTS_E_INTERNAL;
-        }
+    // every position tied at n = 2^32 (a constant or a two-symbol periodic input of exactly 4 GiB): the side buffers of the
+    // later rounds are sized by the tied count and do not fit next to the 36 n bytes of round 0
+    if (a > 0xffffffffull) return BWTS_E_NOMEM;
+    // few tied elements: sparse rank map; many (real text ties most m-grams): the dense rank array
+    if (a > 0 && a <= n / 32) {
+        BWTS_TRY((sparse_rounds<CYCLIC>(ctx, d_T, n, al, d_fstart, k, sp, r0, &cur, &a, &rounds)));
+    } else if (a > 0) {
+        BWTS_TRY(ensure_rank(ctx, sp, n));
+        if (!rank_early) BWTS_TRY(build_ranks(ctx, SA, n, cur, a, sp.rank));      // (else built before the tied list, see above)
+        // group-local rounds; SA is only rebuilt when someone reads it afterwards (suffix array requested, or the
+        // gather form of the emission)
+        const bool need_sa = !CYCLIC || !sp.carry_out;
+        // chunks (chunk_rounds.h) unless BWTS_DENSE=tiles asks for the tile form (dense_rounds.h), the list is short or memory is
+        const bool tiles_only = [ctx] { const char *e = bwts_knob(ctx, "BWTS_DENSE"); return e && !strcmp(e, "tiles"); }();
+        bool handled = false;
+        if (!tiles_only) BWTS_TRY((chunk_rounds<CYCLIC>(ctx, d_T, n, al, d_fstart, k, sp, cur, a, SA, need_sa, &rounds, &handled)));
+        if (!handled) BWTS_TRY((dense_rounds<CYCLIC>(ctx, d_T, n, al, d_fstart, k, sp, cur, a, SA, need_sa, &rounds)));
+        sp.ties_emitted = CYCLIC && sp.carry_out;
+        *sa_out = SA;
+        *rounds_out = rounds;
+        return BWTS_OK;
     }
     if (want_ranks && !rank_early) { BWTS_TRY(ensure_rank(ctx, sp, n)); BWTS_TRY(build_ranks(ctx, SA, n, a ? cur : none, a, sp.rank)); }
     *sa_out = SA;
@@ -1902,10 +1919,7 @@ static int lyndon_fast(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, 
     if (cnt_c == 0) return BWTS_E_INTERNAL;
     if (cnt_c > LYN_CAND_CAP) return BWTS_OK;
     // candidates arrive in arbitrary order: sort by position
-    SortPlan cp;
-    cp.keys[0] = cand[0]; cp.keys[1] = cand[1];
-    cp.vals[0] = cvals[0]; cp.vals[1] = cvals[1];
-    cp.tile_hist = sp.tile_hist; cp.scan_temp = sp.scan_temp;
+    SortPlan cp = sort_plan(cand[0], cand[1], cvals[0], cvals[1], sp.tile_hist, sp.scan_temp);
     int res = 0;
     BWTS_TRY(radix_sort_pairs(ctx, cp, cnt_c, bitlen_u64(n) + 1, &res));
     // resumable resolver: long comparisons are decided by a grid-wide kernel between two of its launches

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <assert.h>
 #include <string>
 #include <vector>
 #include <condition_variable>
@@ -210,6 +211,13 @@ struct SortPlan {
     // already, in a block of radix_tile_hist_bytes(m) that no pass writes but the first one's scan; that pass's histogram sweep is skipped
     u32 *first_hist = nullptr;
 };
+// a plain pair sort over two key and two value buffers (the optional fields stay as above)
+static inline SortPlan sort_plan(u64 *k0, u64 *k1, u32 *v0, u32 *v1, u32 *tile_hist, void *scan_temp)
+{
+    SortPlan p;
+    p.keys[0] = k0; p.keys[1] = k1; p.vals[0] = v0; p.vals[1] = v1; p.tile_hist = tile_hist; p.scan_temp = scan_temp;
+    return p;
+}
 bool radix_packed_applicable(const bwts_ctx *ctx, u64 m, int key_bits);   // will radix_sort_pairs run its packed-stream passes for such a sort?
 size_t radix_tile_hist_bytes(u64 m);
 // Sorts on key bits [0, key_bits); returns in *result_buf which of keys[]/vals[] holds the output.
@@ -232,6 +240,13 @@ int inverse_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
 size_t forward_arena_bytes(u64 n);
 size_t inverse_arena_bytes(u64 n);
 
+// chunk tables of the forward's later rounds (chunk_rounds.h) as plain arithmetic: nominal chunk size of a list, the tables' capacity
+// for a tied list of a0, and the re-cut of the a_chunks elements left at a compaction (allowed = the new chunks fit the tables)
+struct ChunkRecut { u32 S; u64 nc; bool allowed; };
+u32 chunk_nominal_size(u64 a);
+u64 chunk_table_capacity(u64 a0);
+ChunkRecut chunk_recut_plan(u64 a0, u64 a_chunks);
+
 // non-cyclic suffix sort: leaves the suffix array in *d_sa (arena memory) and ranks in *d_rank
 int suffix_sort_device(bwts_ctx *ctx, const u8 *d_T, u64 n, u32 **d_sa, u32 **d_rank, u32 *rounds);
 int lyndon_factors_device(bwts_ctx *ctx, const u8 *d_T, u64 n, u32 **d_fstart, u64 *k, u32 *rounds);
@@ -240,6 +255,28 @@ int constant_input_probe(bwts_ctx *ctx, const u8 *d_in, u64 n, bool *constant); 
 int aux_reserve_slot(bwts_ctx *ctx, int slot, size_t bytes, char **base);   // side arenas, sized on demand
 static inline int aux_reserve(bwts_ctx *ctx, size_t bytes, char **base) { return aux_reserve_slot(ctx, 0, bytes, base); }
 int aux_release(bwts_ctx *ctx);      // gives every side arena back (their contents are dead)
+
+// The arrays of one side block, declared once and in order, each rounded up to 256 bytes: bytes() is what to reserve, place()
+// points every declared array into the block.  No allocator and no ownership: the pointers named must outlive place().
+struct BlockLayout {
+    struct Field { void *var; size_t off; void (*set)(void *var, char *p); };
+    Field f[24];
+    int count = 0;
+    size_t total = 0;
+    template <typename T> static size_t padded(u64 n) { return align_up((size_t)n * sizeof(T), 256); }
+    template <typename T> void array(T **var, u64 n) { raw(var, padded<T>(n)); }
+    template <typename T> void raw(T **var, size_t bytes)         // a field of exactly `bytes` (sizes that come rounded already)
+    {
+        assert(count < 24);
+        f[count++] = Field{var, total, [](void *v, char *p) { *(T **)v = (T *)p; }};
+        total += bytes;
+    }
+    void pad(size_t bytes) { total += bytes; }
+    size_t bytes() const { return total; }
+    void place(char *base) const { for (int i = 0; i < count; i++) f[i].set(f[i].var, base + f[i].off); }
+    // a second layout over a block of `cap` bytes that is reserved already: false, and nothing placed, when it does not fit
+    bool place_within(char *base, size_t cap) const { if (bytes() > cap) return false; place(base); return true; }
+};
 
 // ---- generators / utilities (gen.hip) ------------------------------------------------
 int generate_device_impl(bwts_ctx *ctx, int kind, u64 seed, u64 n, u8 *d_out);

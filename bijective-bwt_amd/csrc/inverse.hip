@@ -949,6 +949,19 @@ size_t inverse_arena_bytes(u64 n)
 
 static int grid1(u64 m) { return (int)((m + 255) / 256); }
 
+// the cycle sort's buffers, a whole pair sort of m elements in side arena 1: keys, values, the radix tables, scan scratch, and the
+// 4 KiB of slack that every such block carries
+static int cycle_sort_plan(bwts_ctx *ctx, u64 m, SortPlan *cp)
+{
+    char *sb = nullptr;
+    BlockLayout L;
+    L.array(&cp->keys[0], m); L.array(&cp->keys[1], m); L.array(&cp->vals[0], m); L.array(&cp->vals[1], m);
+    L.raw(&cp->tile_hist, radix_tile_hist_bytes(m)); L.raw(&cp->scan_temp, scan_temp_bytes(m)); L.pad(4096);
+    BWTS_TRY(aux_reserve_slot(ctx, 1, L.bytes(), &sb));
+    L.place(sb);
+    return BWTS_OK;
+}
+
 #include "wide_inverse.h"         // the 64-bit form; its node-ranking kernels also serve the unit-node ranking below
 
 // wi_finish_kernel for the main path: the cycles of the unit-node ranking go straight into the record form of the cycles
@@ -1100,11 +1113,10 @@ static int inverse_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, int 
     auto lay_out_lists = [&](size_t cap) -> int {
         // uidx, ulf: cap entries; records of the cycles without a splitter and their ends: at most cap
         char *ub = nullptr;
-        const size_t e4 = align_up(cap * 4, 256), e8 = align_up(cap * 8, 256);
-        BWTS_TRY(aux_reserve_slot(ctx, 0, 3 * e4 + e8, &ub));
-        uidx = (u32 *)ub; ulf = (u32 *)(ub + e4);
-        tiny = (uint2 *)(ub + 2 * e4);
-        end_of_tiny = (u32 *)(ub + 2 * e4 + e8);
+        BlockLayout L;
+        L.array(&uidx, cap); L.array(&ulf, cap); L.array(&tiny, cap); L.array(&end_of_tiny, cap);
+        BWTS_TRY(aux_reserve_slot(ctx, 0, L.bytes(), &ub));
+        L.place(ub);
         return BWTS_OK;
     };
     BWTS_TRY(lay_out_lists(ucap));
@@ -1244,14 +1256,8 @@ static int inverse_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, int 
     {
         SpanGuard sg(ctx, BWTS_K_LISTRANK, kall, 0);
         const CycleList cl{tiny, kt, d_recs2, kc};
-        char *sb = nullptr;
-        const size_t k8 = align_up(kall * 8, 256), k4 = align_up(kall * 4, 256);
-        BWTS_TRY(aux_reserve_slot(ctx, 1, 2 * k8 + 2 * k4 + radix_tile_hist_bytes(kall) + scan_temp_bytes(kall) + 4096, &sb));
         SortPlan cp;
-        cp.keys[0] = (u64 *)sb; cp.keys[1] = (u64 *)(sb + k8);
-        cp.vals[0] = (u32 *)(sb + 2 * k8); cp.vals[1] = (u32 *)(sb + 2 * k8 + k4);
-        cp.tile_hist = (u32 *)(sb + 2 * k8 + 2 * k4);
-        cp.scan_temp = sb + 2 * k8 + 2 * k4 + radix_tile_hist_bytes(kall);
+        BWTS_TRY(cycle_sort_plan(ctx, kall, &cp));
         cycle_keys_kernel<<<dim3(grid1(kall)), dim3(256), 0, ctx->stream>>>(cl, cp.keys[0], cp.vals[0]);
         int res = 0;
         int kbits = 0; for (u64 x = n - 1; x; x >>= 1) kbits++;

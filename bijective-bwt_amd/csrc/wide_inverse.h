@@ -532,12 +532,10 @@ static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out,
     WiCycle *cyc = nullptr;
     auto lay_out = [&](u64 cap) -> int {
         char *ub = nullptr;
-        const size_t e8 = align_up((size_t)cap * 8, 256), c24 = align_up((size_t)(node_cap + cap) * sizeof(WiCycle), 256),
-                     c8 = align_up((size_t)(node_cap + cap) * 8, 256);
-        BWTS_TRY(aux_reserve_slot(ctx, 0, 2 * e8 + c24 + c8, &ub));
-        uidx = (u64 *)ub; ulf = (u64 *)(ub + e8);
-        cyc = (WiCycle *)(ub + 2 * e8);
-        end_of_cyc = (u64 *)(ub + 2 * e8 + c24);
+        BlockLayout L;
+        L.array(&uidx, cap); L.array(&ulf, cap); L.array(&cyc, node_cap + cap); L.array(&end_of_cyc, node_cap + cap);
+        BWTS_TRY(aux_reserve_slot(ctx, 0, L.bytes(), &ub));
+        L.place(ub);
         return BWTS_OK;
     };
     BWTS_TRY(lay_out(ucap));
@@ -648,14 +646,8 @@ static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out,
     {
         SpanGuard sg(ctx, BWTS_K_LISTRANK, kall, 0);
         HIPC(hipMemcpyAsync(cyc + kt, ncyc, kc * sizeof(WiCycle), hipMemcpyDeviceToDevice, ctx->stream));
-        char *sb = nullptr;
-        const size_t k8 = align_up(kall * 8, 256), k4 = align_up(kall * 4, 256);
-        BWTS_TRY(aux_reserve_slot(ctx, 1, 2 * k8 + 2 * k4 + radix_tile_hist_bytes(kall) + scan_temp_bytes(kall) + 4096, &sb));
         SortPlan cp;
-        cp.keys[0] = (u64 *)sb; cp.keys[1] = (u64 *)(sb + k8);
-        cp.vals[0] = (u32 *)(sb + 2 * k8); cp.vals[1] = (u32 *)(sb + 2 * k8 + k4);
-        cp.tile_hist = (u32 *)(sb + 2 * k8 + 2 * k4);
-        cp.scan_temp = sb + 2 * k8 + 2 * k4 + radix_tile_hist_bytes(kall);
+        BWTS_TRY(cycle_sort_plan(ctx, kall, &cp));
         wi_cycle_keys_kernel<<<dim3(grid1(kall)), dim3(256), 0, ctx->stream>>>(cyc, kall, cp.keys[0], cp.vals[0]);
         int res = 0, kbits = 0;
         for (u64 x = n - 1; x; x >>= 1) kbits++;

@@ -536,10 +536,7 @@ static int forward_wide_run(bwts_ctx *ctx, const u8 *d_T, u64 n, u8 *d_out, Wide
             HIPC(hipMemsetAsync(cnt + 27, 0, sizeof(u64), ctx->stream));
             wide_sample_keys_kernel<<<dim3((m + 255) / 256), dim3(256), 0, ctx->stream>>>(segkeys, c, m, bk[0], bv[0]);
             HIPC(hipGetLastError());
-            SortPlan spn;
-            spn.keys[0] = bk[0]; spn.keys[1] = bk[1];
-            spn.vals[0] = bv[0]; spn.vals[1] = bv[1];
-            spn.tile_hist = tile_hist; spn.scan_temp = scan_temp;
+            SortPlan spn = sort_plan(bk[0], bk[1], bv[0], bv[1], tile_hist, scan_temp);
             int sres = 0;
             BWTS_TRY(radix_sort_pairs(ctx, spn, m, al.key_bits, &sres));
             wide_sample_ties_kernel<<<dim3((m + 255) / 256), dim3(256), 0, ctx->stream>>>(spn.keys[sres], m, cnt + 27);
@@ -573,10 +570,7 @@ static int forward_wide_run(bwts_ctx *ctx, const u8 *d_T, u64 n, u8 *d_out, Wide
         if (cnt_c == 0) return BWTS_E_INTERNAL;
         if (cnt_c > LYN_CAND_CAP) { *redo = WIDE_NEED_SUFFIX; return BWTS_OK; }      // (runs of the smallest byte, a^n, (ab)^n ...)
         {
-            SortPlan cp;
-            cp.keys[0] = cand[0]; cp.keys[1] = cand[1];
-            cp.vals[0] = cvals[0]; cp.vals[1] = cvals[1];
-            cp.tile_hist = tile_hist; cp.scan_temp = scan_temp;
+            SortPlan cp = sort_plan(cand[0], cand[1], cvals[0], cvals[1], tile_hist, scan_temp);
             int res = 0;
             BWTS_TRY(radix_sort_pairs(ctx, cp, cnt_c, bitlen_u64(n) + 1, &res));
             LynState *d_st = (LynState *)(ctx->d_small + CNT_LYN_K);
@@ -709,10 +703,7 @@ static int forward_wide_run(bwts_ctx *ctx, const u8 *d_T, u64 n, u8 *d_out, Wide
             off += share;
         }
         if (off != m) return BWTS_E_INTERNAL;
-        SortPlan sp;
-        sp.keys[0] = bk[0]; sp.keys[1] = bk[1];
-        sp.vals[0] = bv[0]; sp.vals[1] = bv[1];
-        sp.tile_hist = tile_hist; sp.scan_temp = scan_temp;
+        SortPlan sp = sort_plan(bk[0], bk[1], bv[0], bv[1], tile_hist, scan_temp);
         sp.sym_src = bs_src; sp.sym_buf[0] = bs_buf[0]; sp.sym_buf[1] = bs_buf[1]; sp.sym_final = bs_fin;
         int res = 0;
         BWTS_TRY(radix_sort_pairs(ctx, sp, m, al.key_bits, &res));
@@ -831,10 +822,7 @@ static int forward_wide_run(bwts_ctx *ctx, const u8 *d_T, u64 n, u8 *d_out, Wide
             BWTS_TRY(read_small(ctx, SM_COUNTERS + 3, 1));
             const u64 groups = ctx->h_small[SM_COUNTERS + 3];
             if (bitlen_u64(groups) + rb > 64) return BWTS_E_RANGE;
-            SortPlan tp;
-            tp.keys[0] = bk[0]; tp.keys[1] = bk[1];
-            tp.vals[0] = bv[0]; tp.vals[1] = bv[1];
-            tp.tile_hist = tile_hist; tp.scan_temp = scan_temp;
+            SortPlan tp = sort_plan(bk[0], bk[1], bv[0], bv[1], tile_hist, scan_temp);
             int tres = 0;
             BWTS_TRY(radix_sort_pairs(ctx, tp, m, bitlen_u64(groups) + rb, &tres));
             {

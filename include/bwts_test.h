@@ -29,6 +29,10 @@ int bwts_device_equal(bwts_ctx *ctx, const void *d_a, const void *d_b, uint64_t 
 int bwts_debug_sort_pairs(bwts_ctx *ctx, uint64_t *h_keys, uint32_t *h_vals, uint64_t m, int key_bits);
 int bwts_debug_suffix_array(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint32_t *h_sa);
 int bwts_debug_lyndon(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint64_t *h_starts, uint64_t cap, uint64_t *count);
+/* Pure arithmetic, no context and no device: the chunk tables of the forward's later rounds for a tied list of a0 elements, and the
+ * re-cut of the a_chunks elements left at a compaction.  out = {nominal chunk size of a0, table capacity, nominal size of a_chunks,
+ * chunks of the re-cut}; returns 1 when the compaction is allowed (the re-cut fits the tables), else 0. */
+int bwts_debug_chunk_plan(uint64_t a0, uint64_t a_chunks, uint64_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -43,7 +43,7 @@ EXPORTS = [
 TEST_EXPORTS = [
     "bwts_generate_device", "bwts_device_alloc", "bwts_device_free", "bwts_copy_to_device", "bwts_copy_to_host",
     "bwts_device_equal", "bwts_debug_sort_pairs", "bwts_debug_suffix_array", "bwts_debug_lyndon",
-    "bwts_debug_chunk_plan",
+    "bwts_debug_chunk_plan", "bwts_debug_inverse_arena",
 ]
 
 
@@ -126,6 +126,7 @@ def lib():
         L.bwts_debug_suffix_array.argtypes = [vp, vp, u64, vp]
         L.bwts_debug_lyndon.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
         L.bwts_debug_chunk_plan.argtypes = [u64, u64, ctypes.POINTER(u64)]
+        L.bwts_debug_inverse_arena.argtypes = [u64, i32, i32, ctypes.POINTER(u64)]
         _lib = L
     return _lib
 

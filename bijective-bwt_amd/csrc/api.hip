@@ -1174,6 +1174,15 @@ extern "C" int bwts_debug_chunk_plan(uint64_t a0, uint64_t a_chunks, uint64_t ou
     return re.allowed ? 1 : 0;
 }
 
+// the narrow inverse's arena as plain arithmetic: no context, no device
+extern "C" int bwts_debug_inverse_arena(uint64_t n, int g, int mark, uint64_t out[2])
+{
+    if (n == 0 || n > 0x100000000ull || g > 20 || mark < 0 || mark > 3) return -1;
+    if (g < 0) g = inverse_splitter_log2(n);
+    out[0] = inverse_attempt_bytes(n, g, mark); out[1] = inverse_arena_bytes(n);
+    return g;
+}
+
 extern "C" int bwts_debug_suffix_array(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint32_t *h_sa)
 {
     if (!ctx || !in || !h_sa || n == 0) return BWTS_E_ARG;

@@ -238,6 +238,10 @@ int inverse_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
 size_t inverse_segments_arena_bytes(u64 n);
 int inverse_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
 size_t forward_arena_bytes(u64 n);
+// the inverse's arena as plain arithmetic (the bwts_debug_inverse_arena test hook asks them too): the splitter spacing the narrow
+// form picks, what one attempt reserves (mark: 0 index log, 1 sentinel, 2 byte map, 3 moments), what the host path allocates ahead
+int    inverse_splitter_log2(u64 n);
+size_t inverse_attempt_bytes(u64 n, int g, int mark);
 size_t inverse_arena_bytes(u64 n);
 
 // chunk tables of the forward's later rounds (chunk_rounds.h) as plain arithmetic: nominal chunk size of a list, the tables' capacity
@@ -260,14 +264,15 @@ int aux_release(bwts_ctx *ctx);      // gives every side arena back (their conte
 // points every declared array into the block.  No allocator and no ownership: the pointers named must outlive place().
 struct BlockLayout {
     struct Field { void *var; size_t off; void (*set)(void *var, char *p); };
-    Field f[24];
+    Field f[32];
     int count = 0;
     size_t total = 0;
     template <typename T> static size_t padded(u64 n) { return align_up((size_t)n * sizeof(T), 256); }
     template <typename T> void array(T **var, u64 n) { raw(var, padded<T>(n)); }
+    template <typename... T> void arrays(u64 n, T **...vars) { (array(vars, n), ...); }      // several arrays of n elements each
     template <typename T> void raw(T **var, size_t bytes)         // a field of exactly `bytes` (sizes that come rounded already)
     {
-        assert(count < 24);
+        assert(count < (int)(sizeof f / sizeof f[0]));
         f[count++] = Field{var, total, [](void *v, char *p) { *(T **)v = (T *)p; }};
         total += bytes;
     }

@@ -8,8 +8,8 @@
 //              placement of the recorded segments
 // The reference follows ONE cycle at a time (n dependent loads).  Here every G-th index is a splitter; a lane walks
 // from its splitter to the next one, so ~n/G walks run concurrently, and LF is chased exactly once.  Cycles that contain
-// no splitter are found from the walk's index log (or, in the alternative modes, from visited marks) and resolved
-// separately.
+// no splitter are found from per-class moments of the indices the walk visited (or, in the alternative modes, from the walk's
+// index log or from visited marks) and resolved separately.
 #include "internal.h"
 #include "device_utils.h"
 #include "scan_templ.h"
@@ -24,8 +24,18 @@
 #define LF_TILE    (LF_THREADS * LF_ITEMS)
 #define LF_VISITED 0xffffffffu     // written over an entry once the walk has read it (LF is chased exactly once)
 
-
 #define SMI_COUNTERS 320
+// The used words of the inverse's counter block, d_small[SMI_COUNTERS ..] (IC_WORDS words, cleared before every walk; both forms)
+enum InvCounter {
+    IC_TICKET = 0, IC_VIRTUAL = 3, IC_LOG_CHUNKS = 5,           // the walk: next batch of splitter ids, virtual nodes (segments cut at `slot` symbols), log chunks handed out
+    IC_OVERFLOW = 4,                                            // the walk: node pool exhausted; the one-lane scan: a cycle too long for one lane
+    IC_UNREACHED = 1, IC_UNREACHED_NODES = 6,                   // elements no walk visited; nodes no level-2 walk reached
+    IC_LIST_CYCLES = 2, IC_FREE_CYCLES = 7, IC_UNIT_CYCLES = 9, // cycles of the reduced list; without a splitter by the one-lane scan, or by the unit-node ranking
+    IC_LISTED_CLASSES = 10, IC_MOM_FALLBACK = 11,               // moments: classes handed to the element-by-element search; the moments do not name the unreached elements
+    IC_LENGTH_SUM = 13, IC_WORDS = 16                           // sum of all cycle lengths: n when every element has its place
+};
+static inline unsigned long long *inv_counter(bwts_ctx *ctx, int c) { return (unsigned long long *)(ctx->d_small + SMI_COUNTERS + c); }
+static inline u64 inv_count(const bwts_ctx *ctx, int c) { return ctx->h_small[SMI_COUNTERS + c]; }
 
 // ------------------------------------------------------------------------------------
 // stable LF map
@@ -169,7 +179,7 @@ __device__ __forceinline__ u32 symbol_of(const u64 *Ctab, u32 y)
 //                     else that is random: measured 58 -> 35 ms at n = 2^30 against sentinel marks.
 //   1  sentinel    -- the entry is overwritten with LF_VISITED (one extra random 32-byte write per step)
 //   2  byte map    -- marks[x] = 1 (when LF_VISITED could be a real entry: n = 2^32)
-// WALK_PROFILE (compile-time) stamps wall-clock times of first start / pool exhausted / wave ends into ticket[8..12]:
+// WALK_PROFILE (compile-time; no build defines it and no host code primes or prints the stamps any more) put wall-clock times of first start / pool exhausted / wave ends into ticket[8..12]:
 // at n = 2^30 the pool runs dry at ~29 ms whatever the walker count (64 K .. 512 K lanes) and batch size, and the
 // longest residual chain (~G ln(walkers) dependent steps) adds ~5 ms; only a smaller G shortens that tail.
 #define IDX_RANGE_LOG2 20
@@ -212,7 +222,7 @@ __global__ __launch_bounds__(256) void walk_record_kernel(u32 *__restrict__ LF, 
     // (Round 3 tried two things here and measured both worse: fetching the next LF entry before the current step's symbol search and
     // moments -- the walk is bound by the memory system's line-fill rate, not by a lane's dependency chain, and the second read in
     // flight per lane only lengthens the queues: dna 2^32 119.7 -> 129.5 ms, zipf 2^30 27.4 -> 27.8 ms -- and count + sum in one
-    // 64-bit LDS atomic, which changed nothing measurable.  tools/sessions/r03y.sh, r03af.sh.)
+    // 64-bit LDS atomic, which changed nothing measurable.  profiles/history/NOTES.md.)
     // MARK_LOG: how many indices of each 2^IDX_RANGE_LOG2-range this workgroup visited.  A range that ends up with all of
     // its indices counted holds nothing unvisited, and its log entries need not be looked at again.
     __shared__ u32 bseen[MARK == MARK_LOG ? IDX_MAX_BUCKETS : 1];
@@ -921,48 +931,45 @@ __global__ __launch_bounds__(256) void tiny_place_kernel(const uint2 *__restrict
 // ------------------------------------------------------------------------------------
 // driver
 // ------------------------------------------------------------------------------------
+static int grid1(u64 m) { return (int)((m + 255) / 256); }
+static int bit_length(u64 x) { int b = 0; for (; x; x >>= 1) b++; return b; }
+int inverse_splitter_log2(u64 n) { const int g = bit_length(n) - 24; return g < 4 ? 4 : g > 8 ? 8 : g; }
 static int splitter_log2(const bwts_ctx *ctx, u64 n)
 {
-    int bl = 0; for (u64 x = n; x; x >>= 1) bl++;
-    int g = bl - 24;
-    if (g < 4) g = 4;
-    if (g > 8) g = 8;
     const char *env = bwts_knob(ctx, "BWTS_SPLIT_LOG2");
-    if (env) { int v = atoi(env); if (v >= 0 && v <= 20) g = v; }
-    return g;
+    const int v = env ? atoi(env) : -1;
+    return v >= 0 && v <= 20 ? v : inverse_splitter_log2(n);
 }
-
 #define UNV_CAP0 (1ull << 20)     // room for unreached elements before their number is known
-
-static size_t inverse_node_bytes(u64 node_cap, u32 slot)
-{
-    const u64 l2cap = node_cap / L2_H + 2 + node_cap;        // worst case: no node is reached by a level-2 walk
-    return align_up(node_cap * 16, 256) + 5 * align_up(node_cap * 4, 256) + align_up(node_cap, 256) + align_up(node_cap * slot, 256) +
-           4 * align_up(l2cap * 16, 256) + 2 * align_up(l2cap * 8, 256) + 3 * align_up(l2cap * 4, 256) + align_up(l2cap * sizeof(CycleRec), 256);
-}
-
-size_t inverse_arena_bytes(u64 n)
-{
-    const u64 s = (n >> 4) + 2;   // upper bound on splitters (g >= 4)
-    return align_up(n * 4, 256) + radix_tile_hist_bytes(n) + scan_temp_bytes(n) + inverse_node_bytes(s + s / 8 + 1024, 64) + (1 << 16);
-}
-
-static int grid1(u64 m) { return (int)((m + 255) / 256); }
-
+// Spare bytes behind the last array of an attempt's arena block (both forms).  No kernel is known to need them: they are what the
+// anonymous 256 KiB of the former hand-made sums left over once the moments tables, which lived off it, were declared.
+#define INV_ARENA_SLACK ((size_t)1 << 15)
+// the error of the launches queued since the last check, as a return code
+static int launched(bwts_ctx *ctx) { HIPC(hipGetLastError()); return BWTS_OK; }
 // the cycle sort's buffers, a whole pair sort of m elements in side arena 1: keys, values, the radix tables, scan scratch, and the
 // 4 KiB of slack that every such block carries
 static int cycle_sort_plan(bwts_ctx *ctx, u64 m, SortPlan *cp)
 {
-    char *sb = nullptr;
-    BlockLayout L;
-    L.array(&cp->keys[0], m); L.array(&cp->keys[1], m); L.array(&cp->vals[0], m); L.array(&cp->vals[1], m);
+    char *sb = nullptr; BlockLayout L;
+    L.arrays(m, &cp->keys[0], &cp->keys[1], &cp->vals[0], &cp->vals[1]);
     L.raw(&cp->tile_hist, radix_tile_hist_bytes(m)); L.raw(&cp->scan_temp, scan_temp_bytes(m)); L.pad(4096);
     BWTS_TRY(aux_reserve_slot(ctx, 1, L.bytes(), &sb));
     L.place(sb);
     return BWTS_OK;
 }
+// the one block an attempt (InvRun, WideRun) holds in the arena: reserved by its declared size, taken whole, every declared array pointed into it
+template <typename RUN> static int arena_place(bwts_ctx *ctx, RUN &r)
+{
+    BlockLayout L; r.declare(L);
+    BWTS_TRY(arena_reserve(ctx, L.bytes()));
+    char *base = (char *)arena_alloc(ctx, L.bytes());
+    if (!base) return BWTS_E_NOMEM;
+    L.place(base);
+    r.dC = ctx->d_small + 1024;         // symbol boundaries C[0..256] (unbwts.c:38-43)
+    return BWTS_OK;
+}
 
-#include "wide_inverse.h"         // the 64-bit form; its node-ranking kernels also serve the unit-node ranking below
+#include "wide_inverse.h"         // the 64-bit form; its node ranking (WiRanking, UnitRank) also serves the unit-node route below
 
 // wi_finish_kernel for the main path: the cycles of the unit-node ranking go straight into the record form of the cycles
 // without a splitter (smallest element, length) plus their leader
@@ -988,310 +995,285 @@ __global__ __launch_bounds__(256) void unit_ends_kernel(const u32 *__restrict__ 
     if (i < m) end_by_leader[leader[i]] = end_of_tiny[i];
 }
 
-// One attempt with splitter spacing 2^g.  *retry is set when the node pool overflows (adversarial LF) or the unreached
-// elements are too many for the unit-node ranking; the caller then repeats with g = 0 (every element a splitter).
-static int inverse_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, int g, int mark, bool *retry, bool *ambiguous, bool *need_log = nullptr)
+// ---- what one attempt holds in the arena: every group declares its arrays once, into the attempt's one BlockLayout ----
+struct LfTables {           // the LF map and what builds it
+    u32 *LF = nullptr, *tile_hist = nullptr; void *scan_temp = nullptr;
+    void declare(BlockLayout &L, u64 n) { L.array(&LF, n); L.raw(&tile_hist, radix_tile_hist_bytes(n)); L.raw(&scan_temp, scan_temp_bytes(n)); }
+};
+struct NodeTables {         // per node of the reduced list (splitters and virtual nodes): record, recorded symbols, place in the text
+    uint4 *noderec = nullptr; u32 *opos = nullptr, *wrap = nullptr, *clen = nullptr, *id2of = nullptr, *U = nullptr; u8 *visited2 = nullptr, *seg = nullptr;
+    void declare(BlockLayout &L, u64 node_cap, u32 slot) { L.arrays(node_cap, &noderec, &opos, &wrap, &clen, &id2of, &U, &visited2); L.array(&seg, node_cap * slot); }
+};
+struct Level2Tables {       // the level-2 list: its records, the two ping-pong pairs of the ranking, the cycles of the reduced list
+    uint4 *rec2 = nullptr, *place2 = nullptr; LrMin *lrmin[2] = {nullptr, nullptr}; LrSum *lrsum[2] = {nullptr, nullptr};
+    u32 *dist = nullptr, *min_dist = nullptr, *end_by_leader = nullptr; CycleRec *recs2 = nullptr;
+    void declare(BlockLayout &L, u64 l2cap) { L.arrays(l2cap, &rec2, &place2, &lrmin[0], &lrmin[1], &lrsum[0], &lrsum[1], &dist, &min_dist, &end_by_leader, &recs2); }
+};
+struct MomentTables {       // MARK_MOMENTS: the classes' moments, the copy moments_resolve_kernel adds to, listed classes, class states
+    unsigned long long *mom = nullptr, *work = nullptr; u32 *def_list = nullptr, *cstat = nullptr;
+    void declare(BlockLayout &L) { L.arrays(3 * MOM_MAX_BUCKETS, &mom, &work); L.arrays(MOM_MAX_BUCKETS, &def_list, &cstat); }
+};
+struct LogTables {          // MARK_LOG: the index log in chunks, the indices of deficient ranges by range, per-range counters
+    u32 *idxlog = nullptr, *chunk_fill = nullptr, *bucket_data = nullptr, *bucket_fill = nullptr, *bucket_seen = nullptr;
+    u32 *deficient() const { return bucket_seen + IDX_MAX_BUCKETS; }       // bucket_seen: counts, then deficit flags
+    void declare(BlockLayout &L, u64 log_chunks, u32 nbuckets)
+    {
+        L.array(&idxlog, log_chunks * IDX_CHUNK); L.array(&chunk_fill, log_chunks); L.array(&bucket_data, (u64)nbuckets << IDX_RANGE_LOG2);
+        L.array(&bucket_fill, (u64)IDX_MAX_BUCKETS * IDX_FILL_STRIDE); L.array(&bucket_seen, 2 * IDX_MAX_BUCKETS);
+    }
+};
+// One attempt with splitter spacing 2^g and one way of marking: its sizes (plain arithmetic), its arrays, what one stage hands to the next
+struct InvRun {
+    u64 n, G, s, tiles, node_cap, l2cap, log_chunks, mom_classes;
+    int g, mark, mom_shift; u32 slot, nbuckets; unsigned wblocks;
+    LfTables lf; NodeTables nd; Level2Tables l2; MomentTables mt; LogTables lg;
+    u8 *marks = nullptr; u64 *dC = nullptr;                     // the byte map (MARK_BYTEMAP); symbol boundaries
+    u64 ucap = 0; u32 *uidx = nullptr, *ulf = nullptr, *end_of_tiny = nullptr; uint2 *tiny = nullptr;       // side block 0: the unreached elements and their cycles
+    u64 s_all = 0, s2 = 0, nu = 0, nu2 = 0, s2all = 0, kc = 0, kt = 0;
+    int cur = 0, sc = 0;                                        // which side of lrmin[] / lrsum[] holds the ranking
+    bool unit_rank = false;                                     // the unit-node route: its block, taken from the device for the call
+    UnitRank unit; u32 *uend = nullptr, *uleader = nullptr; ScopedDeviceBlock ub;
+    InvRun(bwts_ctx *ctx /* null: sizes only */, u64 n_, int g_, int mark_) : n(n_), g(g_), mark(mark_), ub(ctx)
+    {
+        u64 walker_cap = 524288;                                // lanes of the walk
+        if (const char *e = ctx ? bwts_knob(ctx, "BWTS_WALKERS") : nullptr) { const long v = atol(e); if (v >= 256 && v <= (1 << 22)) walker_cap = (u64)v; }
+        mom_shift = n > (1ull << 30) ? MOM_LOG2_LARGE : MOM_LOG2_SMALL; mom_classes = 1ull << mom_shift;      // residue classes, and their log2
+        G = 1ull << g; s = (n + G - 1) / G; tiles = (n + LF_TILE - 1) / LF_TILE;
+        // a segment longer than `slot` steps is cut into virtual nodes; room for s/8 of them (natural data needs ~2 %)
+        slot = (u32)(4 * G < 16 ? 16 : 4 * G);
+        node_cap = g == 0 ? s : s + s / 8 + 1024;
+        l2cap = node_cap / L2_H + 2 + node_cap;                 // worst case: no node is reached by a level-2 walk
+        wblocks = (unsigned)(((s < walker_cap ? s : walker_cap) + 255) / 256);
+        log_chunks = n / (IDX_CHUNK - 64) + (u64)wblocks * 4 + 2;     // a closed chunk wastes < 64 entries; every wave may leave one open
+        nbuckets = (u32)((n + (1ull << IDX_RANGE_LOG2) - 1) >> IDX_RANGE_LOG2);
+    }
+    void declare(BlockLayout &L)            // the mark-specific buffers only for the mark that runs
+    {
+        lf.declare(L, n);
+        if (mark == MARK_MOMENTS) mt.declare(L);
+        if (mark == MARK_BYTEMAP) L.array(&marks, n);
+        if (mark == MARK_LOG) lg.declare(L, log_chunks, nbuckets);
+        nd.declare(L, node_cap, slot); l2.declare(L, l2cap); L.pad(INV_ARENA_SLACK);
+    }
+};
+enum InvOutcome { INV_DONE,
+    INV_RETRY_DENSE,    // the node pool overflowed (adversarial LF), or too many unreached elements for the unit-node ranking: g = 0
+    INV_AMBIGUOUS,      // sentinel marks at n = 2^32: the one entry equal to LF_VISITED sat in a cycle without a splitter
+    INV_NEED_LOG        // the moments do not name the unreached elements: the index log does
+};
+// bytes the narrow attempt (n, g, mark) reserves: no context, no device (bwts_debug_inverse_arena asks too)
+size_t inverse_attempt_bytes(u64 n, int g, int mark) { InvRun r(nullptr, n, g, mark); BlockLayout L; r.declare(L); return L.bytes(); }
+// What the host path's helper thread allocates before the transform runs: the default attempt at the closest splitter spacing the
+// narrow form picks (g = 4, slot 64, moments) -- the node tables shrink faster with g than the records grow, so it bounds every g >= 4.
+size_t inverse_arena_bytes(u64 n) { return inverse_attempt_bytes(n, 4, MARK_MOMENTS); }
+// stable LF map (unbwts.c:50-52) and C; the byte map starts clear
+static int inv_build_lf(bwts_ctx *ctx, InvRun &r, const u8 *d_in)
 {
-    *retry = false;
-    *ambiguous = false;
-    if (need_log) *need_log = false;
-    const bool moments = mark == MARK_MOMENTS;
-    const int mom_shift = n > (1ull << 30) ? MOM_LOG2_LARGE : MOM_LOG2_SMALL;       // log2 of the number of residue classes
-    const u64 mom_classes = 1ull << mom_shift;
-    const u64 G = 1ull << g;
-    const u64 s = (n + G - 1) / G;
-    const u64 tiles = (n + LF_TILE - 1) / LF_TILE;
-
-    // a segment longer than `slot` steps is cut into virtual nodes; room for s/8 of them (natural data needs ~2 %)
-    const u32 slot = (u32)(4 * G < 16 ? 16 : 4 * G);
-    const u64 node_cap = g == 0 ? s : s + s / 8 + 1024;
-    const u64 l2cap = node_cap / L2_H + 2 + node_cap;
-    u64 walker_cap = 524288;
-    if (const char *e = bwts_knob(ctx, "BWTS_WALKERS")) { const long v = atol(e); if (v >= 256 && v <= (1 << 22)) walker_cap = (u64)v; }
-    const u64 walkers = s < walker_cap ? s : walker_cap;
-    const unsigned wblocks = (unsigned)((walkers + 255) / 256);
-    const u64 log_chunks = n / (IDX_CHUNK - 64) + (u64)wblocks * 4 + 2;     // a closed chunk wastes < 64 entries; every wave may leave one open
-    BWTS_TRY(arena_reserve(ctx, align_up(n * 4, 256) + radix_tile_hist_bytes(n) + scan_temp_bytes(n) + inverse_node_bytes(node_cap, slot) +
-                                    align_up(n, 256) +
-                                    (mark == MARK_LOG ? align_up(log_chunks * IDX_CHUNK * 4, 256) + align_up(log_chunks * 4, 256) + align_up(n * 4 + (4ull << IDX_RANGE_LOG2), 256) + (1 << 20) : 0) +
-                                    (1 << 18)));
-    u32 *LF = arena_array<u32>(ctx, n);
-    unsigned long long *mom = moments ? (unsigned long long *)arena_array<u64>(ctx, 3 * MOM_MAX_BUCKETS) : nullptr;
-    unsigned long long *mom_work = moments ? (unsigned long long *)arena_array<u64>(ctx, 3 * MOM_MAX_BUCKETS) : nullptr;   // (moments_resolve_kernel adds to its copy)
-    u32 *def_list = moments ? arena_array<u32>(ctx, MOM_MAX_BUCKETS) : nullptr, *cstat = moments ? arena_array<u32>(ctx, MOM_MAX_BUCKETS) : nullptr;
-    if (moments && (!mom || !mom_work || !def_list || !cstat)) return BWTS_E_NOMEM;
-    u32 *tile_hist = (u32 *)arena_alloc(ctx, radix_tile_hist_bytes(n));
-    void *scan_temp = arena_alloc(ctx, scan_temp_bytes(n));
-    uint4 *noderec = arena_array<uint4>(ctx, node_cap);
-    u32 *d_opos = arena_array<u32>(ctx, node_cap), *d_wrap = arena_array<u32>(ctx, node_cap), *d_clen = arena_array<u32>(ctx, node_cap);
-    u32 *id2of = arena_array<u32>(ctx, node_cap), *U = arena_array<u32>(ctx, node_cap);
-    u8 *visited2 = arena_array<u8>(ctx, node_cap);
-    u8 *seg = arena_array<u8>(ctx, node_cap * slot);
-    uint4 *rec2 = arena_array<uint4>(ctx, l2cap), *place2 = arena_array<uint4>(ctx, l2cap);
-    LrMin *lrmin[2] = {arena_array<LrMin>(ctx, l2cap), arena_array<LrMin>(ctx, l2cap)};
-    LrSum *lrsum[2] = {arena_array<LrSum>(ctx, l2cap), arena_array<LrSum>(ctx, l2cap)};
-    u32 *dist = arena_array<u32>(ctx, l2cap), *min_dist = arena_array<u32>(ctx, l2cap), *end_by_leader = arena_array<u32>(ctx, l2cap);
-    CycleRec *d_recs2 = (CycleRec *)arena_alloc(ctx, l2cap * sizeof(CycleRec));      // cycles of the reduced list (copied next to the others later)
-    const bool bytemark = mark == MARK_BYTEMAP;
-    u8 *marks = bytemark ? arena_array<u8>(ctx, n) : nullptr;
-    const u32 nbuckets = (u32)((n + (1ull << IDX_RANGE_LOG2) - 1) >> IDX_RANGE_LOG2);
-    u32 *idxlog = mark == MARK_LOG ? arena_array<u32>(ctx, log_chunks * IDX_CHUNK) : nullptr;
-    u32 *chunk_fill = mark == MARK_LOG ? arena_array<u32>(ctx, log_chunks) : nullptr;
-    u32 *bucket_data = mark == MARK_LOG ? arena_array<u32>(ctx, (u64)nbuckets << IDX_RANGE_LOG2) : nullptr;
-    u32 *bucket_fill = mark == MARK_LOG ? arena_array<u32>(ctx, (u64)IDX_MAX_BUCKETS * IDX_FILL_STRIDE) : nullptr;
-    u32 *bucket_seen = mark == MARK_LOG ? arena_array<u32>(ctx, 2 * IDX_MAX_BUCKETS) : nullptr;   // counts, then deficit flags
-    u32 *deficient = bucket_seen ? bucket_seen + IDX_MAX_BUCKETS : nullptr;
-    if (!LF || !tile_hist || !scan_temp || !noderec || !d_opos || !d_wrap || !d_clen || !id2of || !U || !visited2 || !seg || !rec2 || !place2 ||
-        !lrmin[0] || !lrmin[1] || !lrsum[0] || !lrsum[1] || !dist || !min_dist || !end_by_leader || !d_recs2 || (bytemark && !marks) ||
-        (mark == MARK_LOG && (!idxlog || !chunk_fill || !bucket_data || !bucket_fill || !bucket_seen)))
-        return BWTS_E_NOMEM;
-    if (bytemark) HIPC(hipMemsetAsync(marks, 0, n, ctx->stream));
-
-    u64 *dC = ctx->d_small + 1024;          // symbol boundaries C[0..256] (unbwts.c:38-43); filled below
-
-    // stable LF map (unbwts.c:50-52)
+    if (r.mark == MARK_BYTEMAP) HIPC(hipMemsetAsync(r.marks, 0, r.n, ctx->stream));
+    SpanGuard sg(ctx, BWTS_K_LF_BUILD, r.n, 5 * r.n);
+    lf_hist_kernel<<<dim3((unsigned)r.tiles), dim3(LF_THREADS), 0, ctx->stream>>>(d_in, r.n, r.lf.tile_hist);
+    BWTS_TRY(radix_column_scan(ctx, r.lf.tile_hist, r.tiles, r.lf.scan_temp));
+    // the scanned table's first row is C itself: no separate histogram sweep, no host round trip before the walk
+    ctab_from_tiles_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(r.lf.tile_hist, r.n, d_in, r.dC);
+    lf_rank_kernel<<<dim3((unsigned)r.tiles), dim3(LF_THREADS), 0, ctx->stream>>>(d_in, r.n, r.lf.tile_hist, r.lf.LF);
+    return launched(ctx);
+}
+template <int MARK> static int launch_walk(bwts_ctx *ctx, const InvRun &r)
+{
+    constexpr bool mom = MARK == MARK_MOMENTS;
+    if (mom) BWTS_TRY(ensure_dyn_lds(ctx, (const void *)walk_record_kernel<MARK>, (size_t)MOM_MAX_BUCKETS * 20));
+    walk_record_kernel<MARK><<<dim3(r.wblocks), dim3(256), mom ? (size_t)r.mom_classes * 20 : 0, ctx->stream>>>(
+        r.lf.LF, r.marks, r.lg.idxlog, r.s, r.node_cap, r.g, r.slot, r.dC, r.nd.seg, r.nd.noderec, inv_counter(ctx, IC_TICKET), inv_counter(ctx, IC_VIRTUAL),
+        inv_counter(ctx, IC_OVERFLOW), inv_counter(ctx, IC_LOG_CHUNKS), r.lg.chunk_fill, r.log_chunks, r.nbuckets, r.lg.bucket_seen, mom ? r.mom_shift : 0, r.mt.mom);
+    return launched(ctx);
+}
+// the walk: marks, segment symbols, reduced list.  Virtual nodes join the reduced list: its size is only known afterwards.
+static int inv_walk(bwts_ctx *ctx, InvRun &r, InvOutcome *out)
+{
+    HIPC(hipMemsetAsync(inv_counter(ctx, 0), 0, IC_WORDS * sizeof(u64), ctx->stream));
+    if (r.mark == MARK_LOG) {
+        HIPC(hipMemsetAsync(r.lg.chunk_fill, 0, r.log_chunks * sizeof(u32), ctx->stream));
+        HIPC(hipMemsetAsync(r.lg.bucket_seen, 0, IDX_MAX_BUCKETS * sizeof(u32), ctx->stream));
+    }
+    if (r.mark == MARK_MOMENTS) HIPC(hipMemsetAsync(r.mt.mom, 0, 3 * r.mom_classes * sizeof(u64), ctx->stream));
     {
-        SpanGuard sg(ctx, BWTS_K_LF_BUILD, n, 5 * n);
-        lf_hist_kernel<<<dim3((unsigned)tiles), dim3(LF_THREADS), 0, ctx->stream>>>(d_in, n, tile_hist);
-        BWTS_TRY(radix_column_scan(ctx, tile_hist, tiles, scan_temp));
-        // the scanned table's first row is C itself: no separate histogram sweep, no host round trip before the walk
-        ctab_from_tiles_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(tile_hist, n, d_in, dC);
-        lf_rank_kernel<<<dim3((unsigned)tiles), dim3(LF_THREADS), 0, ctx->stream>>>(d_in, n, tile_hist, LF);
+        SpanGuard sg(ctx, BWTS_K_WALK, r.n, 6 * r.n);
+        int (*const launch[4])(bwts_ctx *, const InvRun &) = {launch_walk<MARK_LOG>, launch_walk<MARK_SENTINEL>, launch_walk<MARK_BYTEMAP>, launch_walk<MARK_MOMENTS>};
+        BWTS_TRY(launch[r.mark](ctx, r));
+    }
+    BWTS_TRY(read_small(ctx, SMI_COUNTERS, IC_WORDS));
+    if (inv_count(ctx, IC_OVERFLOW)) { *out = INV_RETRY_DENSE; return BWTS_OK; }   // node pool exhausted (adversarial LF): plain pointer jumping
+    r.s_all = r.s + inv_count(ctx, IC_VIRTUAL); r.s2 = (r.s_all + L2_H - 1) / L2_H;
+    return BWTS_OK;
+}
+static int inv_collect(bwts_ctx *ctx, InvRun &r, bool first_time)
+{
+    SpanGuard sg(ctx, BWTS_K_OTHER, r.n, 4 * r.n);
+    unsigned long long *ctr = inv_counter(ctx, 0), *found = inv_counter(ctx, IC_UNREACHED);
+    u32 *LF = r.lf.LF; u64 blocks = (r.n + 255) / 256; if (blocks > 8192) blocks = 8192;
+    if (r.mark == MARK_MOMENTS) {
+        if (!first_time) HIPC(hipMemsetAsync(inv_counter(ctx, IC_LISTED_CLASSES), 0, 2 * sizeof(u64), ctx->stream));    // ... and IC_MOM_FALLBACK
+        const u64 per_class = (r.n + r.mom_classes - 1) >> r.mom_shift;
+        const u64 budget = (4ull << 20) > per_class ? (4ull << 20) : per_class;        // elements the search may look at (at least one class)
+        HIPC(hipMemcpyAsync(r.mt.work, r.mt.mom, 3 * r.mom_classes * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
+        moments_resolve_kernel<<<dim3(1), dim3(1024), 0, ctx->stream>>>(r.mt.work, r.mt.cstat, r.n, r.mom_shift, LF, r.uidx, r.ulf, r.ucap, r.mt.def_list, ctr, 1u << 16);
+        moments_budget_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(ctr, per_class, budget);
+        moments_chase_kernel<<<dim3(2048), dim3(256), 0, ctx->stream>>>(r.mt.def_list, ctr, r.n, r.mom_shift, r.g, LF, 1u << 16, r.uidx, r.ulf, r.ucap, ctr, r.mt.cstat);
+    } else if (r.mark == MARK_LOG) {
+        const int bm_bytes = (int)((1u << IDX_RANGE_LOG2) / 8);
+        if (first_time) {
+            HIPC(hipMemsetAsync(r.lg.bucket_fill, 0, (size_t)r.nbuckets * IDX_FILL_STRIDE * sizeof(u32), ctx->stream));
+            BWTS_TRY(ensure_dyn_lds(ctx, (const void *)unvisited_from_buckets_kernel, (size_t)bm_bytes));
+            BWTS_TRY(ensure_dyn_lds(ctx, (const void *)bucket_indices_kernel, bucket_indices_lds_bytes(IDX_MAX_BUCKETS)));
+            bucket_deficit_kernel<<<dim3((r.nbuckets + 255) / 256), dim3(256), 0, ctx->stream>>>(r.lg.bucket_seen, r.nbuckets, r.n, r.lg.deficient());
+            bucket_indices_kernel<<<dim3((unsigned)r.log_chunks), dim3(IDX_THREADS), bucket_indices_lds_bytes(r.nbuckets), ctx->stream>>>(
+                r.lg.idxlog, r.lg.chunk_fill, r.nbuckets, r.lg.deficient(), r.lg.bucket_fill, r.lg.bucket_data);
+        }
+        unvisited_from_buckets_kernel<<<dim3(r.nbuckets), dim3(1024), bm_bytes, ctx->stream>>>(r.lg.deficient(), r.lg.bucket_fill, r.lg.bucket_data, LF, r.n, r.uidx, r.ulf,
+                                                                                              r.ucap, found);
+    } else if (r.mark == MARK_BYTEMAP)
+        collect_unvisited_kernel<MARK_BYTEMAP><<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(LF, r.marks, r.n, r.uidx, r.ulf, r.ucap, found);
+    else
+        collect_unvisited_kernel<MARK_SENTINEL><<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(LF, r.marks, r.n, r.uidx, r.ulf, r.ucap, found);
+    return launched(ctx);
+}
+// Elements in cycles without a splitter, in lists sized by their number: count first, and where the first room was too small lay the lists out
+// again and collect again.  The level-2 walk over the node list is queued in between: one read-back brings both counts (elements, nodes).
+static int inv_find_unreached(bwts_ctx *ctx, InvRun &r, InvOutcome *out)
+{
+    const size_t ucap = ctx->unv_hint > UNV_CAP0 ? ctx->unv_hint : UNV_CAP0;
+    BWTS_TRY(lay_out_unreached(ctx, r, ucap > r.n ? (size_t)r.n : ucap, 0, &r.tiny, &r.end_of_tiny));
+    BWTS_TRY(inv_collect(ctx, r, true));
+    {
+        SpanGuard sg(ctx, BWTS_K_LISTRANK, r.s_all, 32 * r.s_all);
+        HIPC(hipMemsetAsync(r.nd.visited2, 0, r.s_all, ctx->stream));
+        lr2_walk_kernel<<<dim3(grid1(r.s2)), dim3(256), 0, ctx->stream>>>(r.nd.noderec, r.s2, r.nd.visited2, r.l2.rec2);
+        lr2_collect_kernel<<<dim3(grid1(r.s_all)), dim3(256), 0, ctx->stream>>>(r.nd.visited2, r.s_all, r.s2, r.nd.U, r.nd.id2of, inv_counter(ctx, IC_UNREACHED_NODES));
         HIPC(hipGetLastError());
     }
-
-    // the walk: marks, segment symbols, reduced list
-    // counters: [0] ticket, [1] unreached elements, [2] cycles of the reduced list, [3] virtual nodes, [4] overflow, [5] log chunks,
-    //           [6] unreached nodes, [7] cycles without a splitter, [13] sum of all cycle lengths ([8..12]: WALK_PROFILE stamps)
-    unsigned long long *ticket = (unsigned long long *)(ctx->d_small + SMI_COUNTERS);
-    HIPC(hipMemsetAsync(ticket, 0, 16 * sizeof(u64), ctx->stream));
-#ifdef WALK_PROFILE
-    HIPC(hipMemsetAsync(ticket + 8, 0xff, 2 * sizeof(u64), ctx->stream));
-    HIPC(hipMemsetAsync(ticket + 12, 0xff, 1 * sizeof(u64), ctx->stream));
-#endif
-    if (mark == MARK_LOG) {
-        HIPC(hipMemsetAsync(chunk_fill, 0, log_chunks * sizeof(u32), ctx->stream));
-        HIPC(hipMemsetAsync(bucket_seen, 0, IDX_MAX_BUCKETS * sizeof(u32), ctx->stream));
-    }
-    if (moments) HIPC(hipMemsetAsync(mom, 0, 3 * mom_classes * sizeof(u64), ctx->stream));
-    {
-        SpanGuard sg(ctx, BWTS_K_WALK, n, 6 * n);
-        if (moments) {
-            BWTS_TRY(ensure_dyn_lds(ctx, (const void *)walk_record_kernel<MARK_MOMENTS>, (size_t)MOM_MAX_BUCKETS * 20));
-            walk_record_kernel<MARK_MOMENTS><<<dim3(wblocks), dim3(256), (size_t)mom_classes * 20, ctx->stream>>>(LF, marks, idxlog, s, node_cap, g, slot, dC, seg, noderec,
-                                                                                          ticket, ticket + 3, ticket + 4, ticket + 5, chunk_fill, log_chunks, nbuckets, bucket_seen,
-                                                                                          mom_shift, mom);
-        } else if (mark == MARK_BYTEMAP)
-            walk_record_kernel<MARK_BYTEMAP><<<dim3(wblocks), dim3(256), 0, ctx->stream>>>(LF, marks, idxlog, s, node_cap, g, slot, dC, seg, noderec,
-                                                                                          ticket, ticket + 3, ticket + 4, ticket + 5, chunk_fill, log_chunks, nbuckets, bucket_seen);
-        else if (mark == MARK_SENTINEL)
-            walk_record_kernel<MARK_SENTINEL><<<dim3(wblocks), dim3(256), 0, ctx->stream>>>(LF, marks, idxlog, s, node_cap, g, slot, dC, seg, noderec,
-                                                                                           ticket, ticket + 3, ticket + 4, ticket + 5, chunk_fill, log_chunks, nbuckets, bucket_seen);
-        else
-            walk_record_kernel<MARK_LOG><<<dim3(wblocks), dim3(256), 0, ctx->stream>>>(LF, marks, idxlog, s, node_cap, g, slot, dC, seg, noderec,
-                                                                                      ticket, ticket + 3, ticket + 4, ticket + 5, chunk_fill, log_chunks, nbuckets, bucket_seen);
-        HIPC(hipGetLastError());
-    }
-    // virtual nodes join the reduced list: its size is only known now
-    BWTS_TRY(read_small(ctx, SMI_COUNTERS, 16));
-#ifdef WALK_PROFILE
-    {
-        const u64 *pf = ctx->h_small + SMI_COUNTERS + 8;
-        fprintf(stderr, "walk profile (ms from first wave start): first-exhausted %.2f  last-exhausted %.2f  first-wave-end %.2f  last-wave-end %.2f\n",
-                (pf[1] - pf[0]) / 1e5, (pf[3] - pf[0]) / 1e5, (pf[4] - pf[0]) / 1e5, (pf[2] - pf[0]) / 1e5);
-    }
-#endif
-    if (ctx->h_small[SMI_COUNTERS + 4]) { *retry = true; return BWTS_OK; }   // node pool exhausted (adversarial LF): plain pointer jumping
-    const u64 s_all = s + ctx->h_small[SMI_COUNTERS + 3];
-    const u64 s2 = (s_all + L2_H - 1) / L2_H;
-
-    // elements in cycles without a splitter: collected into lists sized by their number (a second pass if the first room is too small)
-    size_t ucap = ctx->unv_hint > UNV_CAP0 ? ctx->unv_hint : UNV_CAP0;
-    if (ucap > n) ucap = (size_t)n;
-    u32 *uidx = nullptr, *ulf = nullptr, *end_of_tiny = nullptr;
-    uint2 *tiny = nullptr;
-    auto lay_out_lists = [&](size_t cap) -> int {
-        // uidx, ulf: cap entries; records of the cycles without a splitter and their ends: at most cap
-        char *ub = nullptr;
-        BlockLayout L;
-        L.array(&uidx, cap); L.array(&ulf, cap); L.array(&tiny, cap); L.array(&end_of_tiny, cap);
-        BWTS_TRY(aux_reserve_slot(ctx, 0, L.bytes(), &ub));
-        L.place(ub);
-        return BWTS_OK;
-    };
-    BWTS_TRY(lay_out_lists(ucap));
-    auto collect_unreached = [&](bool first_time) -> int {
-        u64 blocks = (n + 255) / 256; if (blocks > 8192) blocks = 8192;
-        if (moments) {
-            if (!first_time) HIPC(hipMemsetAsync(ticket + 10, 0, 2 * sizeof(u64), ctx->stream));
-            const u64 per_class = (n + mom_classes - 1) >> mom_shift;
-            const u64 budget = (4ull << 20) > per_class ? (4ull << 20) : per_class;        // elements the search may look at (at least one class)
-            HIPC(hipMemcpyAsync(mom_work, mom, 3 * mom_classes * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
-            moments_resolve_kernel<<<dim3(1), dim3(1024), 0, ctx->stream>>>(mom_work, cstat, n, mom_shift, LF, uidx, ulf, ucap, def_list, ticket, 1u << 16);
-            moments_budget_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(ticket, per_class, budget);
-            moments_chase_kernel<<<dim3(2048), dim3(256), 0, ctx->stream>>>(def_list, ticket, n, mom_shift, g, LF, 1u << 16, uidx, ulf, ucap, ticket, cstat);
-        } else if (mark == MARK_LOG) {
-            const int bm_bytes = (int)((1u << IDX_RANGE_LOG2) / 8);
-            if (first_time) {
-                HIPC(hipMemsetAsync(bucket_fill, 0, (size_t)nbuckets * IDX_FILL_STRIDE * sizeof(u32), ctx->stream));
-                BWTS_TRY(ensure_dyn_lds(ctx, (const void *)unvisited_from_buckets_kernel, (size_t)bm_bytes));
-                BWTS_TRY(ensure_dyn_lds(ctx, (const void *)bucket_indices_kernel, bucket_indices_lds_bytes(IDX_MAX_BUCKETS)));
-                bucket_deficit_kernel<<<dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream>>>(bucket_seen, nbuckets, n, deficient);
-                bucket_indices_kernel<<<dim3((unsigned)log_chunks), dim3(IDX_THREADS), bucket_indices_lds_bytes(nbuckets), ctx->stream>>>(
-                    idxlog, chunk_fill, nbuckets, deficient, bucket_fill, bucket_data);
-            }
-            unvisited_from_buckets_kernel<<<dim3(nbuckets), dim3(1024), bm_bytes, ctx->stream>>>(deficient, bucket_fill, bucket_data, LF, n, uidx, ulf, ucap,
-                                                                                                ticket + 1);
-        } else if (mark == MARK_BYTEMAP)
-            collect_unvisited_kernel<MARK_BYTEMAP><<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(LF, marks, n, uidx, ulf, ucap, ticket + 1);
-        else
-            collect_unvisited_kernel<MARK_SENTINEL><<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(LF, marks, n, uidx, ulf, ucap, ticket + 1);
-        HIPC(hipGetLastError());
-        return BWTS_OK;
-    };
-    {
-        SpanGuard sg(ctx, BWTS_K_OTHER, n, 4 * n);
-        BWTS_TRY(collect_unreached(true));
-    }
-    // level-2 walk over the node list, and the nodes it does not reach
-    {
-        SpanGuard sg(ctx, BWTS_K_LISTRANK, s_all, 32 * s_all);
-        HIPC(hipMemsetAsync(visited2, 0, s_all, ctx->stream));
-        lr2_walk_kernel<<<dim3(grid1(s2)), dim3(256), 0, ctx->stream>>>(noderec, s2, visited2, rec2);
-        lr2_collect_kernel<<<dim3(grid1(s_all)), dim3(256), 0, ctx->stream>>>(visited2, s_all, s2, U, id2of, ticket + 6);
-        HIPC(hipGetLastError());
-    }
-    BWTS_TRY(read_small(ctx, SMI_COUNTERS, 16));
-    const u64 nu = ctx->h_small[SMI_COUNTERS + 1];
-    const u64 nu2 = ctx->h_small[SMI_COUNTERS + 6];
+    BWTS_TRY(read_small(ctx, SMI_COUNTERS, IC_WORDS));
+    r.nu = inv_count(ctx, IC_UNREACHED); r.nu2 = inv_count(ctx, IC_UNREACHED_NODES);
     const bool inv_trace = [ctx] { const char *e = bwts_knob(ctx, "BWTS_INV_TRACE"); return e && atoi(e) == 1; }();
-    if (inv_trace && moments)
-        fprintf(stderr, "[inverse] moments: shift %d, unreached found %llu, ranges searched %llu, fallback flag %llu\n", mom_shift,
-                (unsigned long long)ctx->h_small[SMI_COUNTERS + 1], (unsigned long long)ctx->h_small[SMI_COUNTERS + 10], (unsigned long long)ctx->h_small[SMI_COUNTERS + 11]);
-    if (moments && ctx->h_small[SMI_COUNTERS + 11]) {          // the ranges' moments do not name the unreached elements: the index log does
-        if (need_log) *need_log = true;
-        return BWTS_OK;
+    if (inv_trace && r.mark == MARK_MOMENTS)
+        fprintf(stderr, "[inverse] moments: shift %d, unreached found %llu, ranges searched %llu, fallback flag %llu\n", r.mom_shift, (unsigned long long)r.nu,
+                (unsigned long long)inv_count(ctx, IC_LISTED_CLASSES), (unsigned long long)inv_count(ctx, IC_MOM_FALLBACK));
+    if (r.mark == MARK_MOMENTS && inv_count(ctx, IC_MOM_FALLBACK)) { *out = INV_NEED_LOG; return BWTS_OK; }
+    ctx->tm.unvisited = r.nu;
+    if (r.nu > r.n || r.nu2 > r.s_all) return BWTS_E_INTERNAL;
+    ctx->unv_hint = (size_t)r.nu;
+    if (r.nu > r.ucap) {
+        BWTS_TRY(lay_out_unreached(ctx, r, r.nu, 0, &r.tiny, &r.end_of_tiny));
+        HIPC(hipMemsetAsync(inv_counter(ctx, IC_UNREACHED), 0, sizeof(u64), ctx->stream));
+        BWTS_TRY(inv_collect(ctx, r, false));
     }
-    ctx->tm.unvisited = nu;
-    if (nu > n || nu2 > s_all) return BWTS_E_INTERNAL;
-    ctx->unv_hint = (size_t)nu;
-    if (nu > ucap) {
-        ucap = (size_t)nu;
-        BWTS_TRY(lay_out_lists(ucap));
-        HIPC(hipMemsetAsync(ticket + 1, 0, sizeof(u64), ctx->stream));
-        SpanGuard sg(ctx, BWTS_K_OTHER, n, 4 * n);
-        BWTS_TRY(collect_unreached(false));
-    }
-    const u64 s2all = s2 + nu2;
-
-    // level-2 list ranking by pointer jumping; cycle records of the reduced list; cycles without a splitter
-    const int R = [&] { int b = 0; for (u64 x = s2all; x; x >>= 1) b++; return b; }();   // 2^R > s2all >= any cycle's entry count
-    int cur = 0, sc = 0;
-    {
-        SpanGuard sg(ctx, BWTS_K_LISTRANK, s2all, 0);
-        const int gb = grid1(s2all);
-        if (nu2) lr2_fill_kernel<<<dim3(grid1(nu2)), dim3(256), 0, ctx->stream>>>(U, nu2, s2, noderec, id2of, rec2);
-        lr_init_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(s2all, rec2, lrmin[0]);
-        for (int r = 0; r < R; r++, cur ^= 1)
-            lr_jump_min_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(s2all, lrmin[cur], lrmin[cur ^ 1]);
-        lr_cut_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(s2all, rec2, lrmin[cur], lrsum[0]);
-        for (int r = 0; r < R; r++, sc ^= 1)
-            lr_jump_sum_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(s2all, lrsum[sc], lrsum[sc ^ 1]);
-        lr_finish_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(s2all, lrmin[cur], lrsum[sc], rec2, dist, min_dist, d_recs2, ticket + 2);
+    r.s2all = r.s2 + r.nu2;
+    return BWTS_OK;
+}
+// level-2 list ranking by pointer jumping; cycle records of the reduced list
+static int inv_rank_node_list(bwts_ctx *ctx, InvRun &r)
+{
+    SpanGuard sg(ctx, BWTS_K_LISTRANK, r.s2all, 0);
+    const int R = bit_length(r.s2all), gb = grid1(r.s2all);      // 2^R > s2all >= any cycle's entry count
+    Level2Tables &t = r.l2;
+    if (r.nu2) lr2_fill_kernel<<<dim3(grid1(r.nu2)), dim3(256), 0, ctx->stream>>>(r.nd.U, r.nu2, r.s2, r.nd.noderec, r.nd.id2of, t.rec2);
+    lr_init_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(r.s2all, t.rec2, t.lrmin[0]);
+    for (int i = 0; i < R; i++, r.cur ^= 1) lr_jump_min_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(r.s2all, t.lrmin[r.cur], t.lrmin[r.cur ^ 1]);
+    lr_cut_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(r.s2all, t.rec2, t.lrmin[r.cur], t.lrsum[0]);
+    for (int i = 0; i < R; i++, r.sc ^= 1) lr_jump_sum_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(r.s2all, t.lrsum[r.sc], t.lrsum[r.sc ^ 1]);
+    lr_finish_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(r.s2all, t.lrmin[r.cur], t.lrsum[r.sc], t.rec2, t.dist, t.min_dist, t.recs2, inv_counter(ctx, IC_LIST_CYCLES));
+    return launched(ctx);
+}
+// cycles without a splitter: one lane per unreached element follows its cycle; where one is too long for that, the unit-node ranking
+static int inv_free_cycles(bwts_ctx *ctx, InvRun &r, InvOutcome *out)
+{
+    if (r.nu) {
+        SpanGuard sg(ctx, BWTS_K_OTHER, r.nu, 8 * r.nu);
+        tiny_cycle_scan_kernel<<<dim3(grid1(r.nu)), dim3(256), 0, ctx->stream>>>(r.uidx, r.ulf, r.nu, r.lf.LF, one_lane_cap(r.nu, r.G), r.tiny, inv_counter(ctx, IC_FREE_CYCLES),
+                                                                                inv_counter(ctx, IC_OVERFLOW));
         HIPC(hipGetLastError());
     }
-    if (nu) {
-        SpanGuard sg(ctx, BWTS_K_OTHER, nu, 8 * nu);
-        // one lane follows at most `cap` elements: bounds the work of an adversarial LF (many long cycles that dodge every splitter)
-        u64 cap = (1ull << 36) / nu;
-        if (cap > 64 * G) cap = 64 * G;
-        if (cap < 4 * G) cap = 4 * G;
-        tiny_cycle_scan_kernel<<<dim3(grid1(nu)), dim3(256), 0, ctx->stream>>>(uidx, ulf, nu, LF, (u32)(cap > 0xfffffff0ull ? 0xfffffff0ull : cap),
-                                                                              tiny, ticket + 7, ticket + 4);
-        HIPC(hipGetLastError());
-    }
-    BWTS_TRY(read_small(ctx, SMI_COUNTERS, 16));
-    const u64 kc = ctx->h_small[SMI_COUNTERS + 2];
-    u64 kt = ctx->h_small[SMI_COUNTERS + 7];
-    if (kc == 0 || kc > s2all || kt > nu) return BWTS_E_INTERNAL;
+    BWTS_TRY(read_small(ctx, SMI_COUNTERS, IC_WORDS));
+    r.kc = inv_count(ctx, IC_LIST_CYCLES); r.kt = inv_count(ctx, IC_FREE_CYCLES);
+    if (r.kc == 0 || r.kc > r.s2all || r.kt > r.nu) return BWTS_E_INTERNAL;
+    r.unit_rank = inv_count(ctx, IC_OVERFLOW) != 0;
+    if (!r.unit_rank) return BWTS_OK;
     // A cycle without a splitter too long for one lane (sorted or periodic data: 1^b 0^c with n = 2^k, c = 2 * odd has a cycle of
     // n / 2 odd elements): every unreached element becomes a node of one symbol and the pointer-jumping kernels of the 64-bit
     // form rank that list -- memory and work by the number of unreached elements, not by n (wide_inverse.h).
-    const bool unit_rank = ctx->h_small[SMI_COUNTERS + 4] != 0;
-    ScopedDeviceBlock ub(ctx);
-    WiMin *umin[2] = {nullptr, nullptr};
-    WiSum *usum[2] = {nullptr, nullptr};
-    u64 *udist = nullptr, *umind = nullptr;
-    u32 *uend = nullptr, *uleader = nullptr;
-    int ucur = 0, usc = 0;
-    if (unit_rank) {
-        if (nu >= 0x7ffffff0ull) { *retry = true; return BWTS_OK; }
-        SpanGuard sg(ctx, BWTS_K_LISTRANK, nu, 0);
-        const size_t a24 = align_up(nu * sizeof(WiNode), 256), a16 = align_up(nu * 16, 256), a8 = align_up(nu * 8, 256), a4 = align_up(nu * 4, 256);
-        if (ub.take(a24 + 4 * a16 + 2 * a8 + 2 * a4) != BWTS_OK) { *retry = true; return BWTS_OK; }      // 112 bytes per unreached element
-        WiNode *unodes = (WiNode *)ub.p;
-        umin[0] = (WiMin *)(ub.p + a24); umin[1] = (WiMin *)(ub.p + a24 + a16);
-        usum[0] = (WiSum *)(ub.p + a24 + 2 * a16); usum[1] = (WiSum *)(ub.p + a24 + 3 * a16);
-        udist = (u64 *)(ub.p + a24 + 4 * a16); umind = (u64 *)(ub.p + a24 + 4 * a16 + a8);
-        uend = (u32 *)(ub.p + a24 + 4 * a16 + 2 * a8); uleader = (u32 *)(ub.p + a24 + 4 * a16 + 2 * a8 + a4);
-        const int gb = grid1(nu);
-        const int R2 = [&] { int b = 0; for (u64 x = nu; x; x >>= 1) b++; return b; }();
-        HIPC(hipMemsetAsync(ticket + 9, 0, sizeof(u64), ctx->stream));
-        wi_unit_index_kernel<u32><<<dim3(gb), dim3(256), 0, ctx->stream>>>(uidx, nu, LF);        // LF[x] of an unreached x lives on in ulf
-        wi_unit_nodes_kernel<u32><<<dim3(gb), dim3(256), 0, ctx->stream>>>(uidx, ulf, nu, LF, unodes);
-        wi_init_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(nu, unodes, umin[0]);
-        for (int r = 0; r < R2; r++, ucur ^= 1) wi_jump_min_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(nu, umin[ucur], umin[ucur ^ 1]);
-        wi_cut_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(nu, unodes, umin[ucur], usum[0]);
-        for (int r = 0; r < R2; r++, usc ^= 1) wi_jump_sum_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(nu, usum[usc], usum[usc ^ 1]);
-        unit_finish_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(nu, umin[ucur], usum[usc], unodes, udist, umind, tiny, uleader, ticket + 9);
-        HIPC(hipGetLastError());
-        BWTS_TRY(read_small(ctx, SMI_COUNTERS + 9, 1));
-        kt = ctx->h_small[SMI_COUNTERS + 9];              // these cycles take the place of the one-lane scan's
-        if (kt == 0 || kt > nu) return BWTS_E_INTERNAL;
-    }
-    const u64 kall = kc + kt;
+    if (r.nu >= 0x7ffffff0ull) { *out = INV_RETRY_DENSE; return BWTS_OK; }
+    SpanGuard sg(ctx, BWTS_K_LISTRANK, r.nu, 0);
+    BlockLayout L; r.unit.declare(L, r.nu); L.array(&r.uend, r.nu); L.array(&r.uleader, r.nu);
+    if (r.ub.take(L.bytes()) != BWTS_OK) { *out = INV_RETRY_DENSE; return BWTS_OK; }      // 112 bytes per unreached element
+    L.place(r.ub.p);
+    const int gb = grid1(r.nu);
+    HIPC(hipMemsetAsync(inv_counter(ctx, IC_UNIT_CYCLES), 0, sizeof(u64), ctx->stream));
+    wi_unit_index_kernel<u32><<<dim3(gb), dim3(256), 0, ctx->stream>>>(r.uidx, r.nu, r.lf.LF);        // LF[x] of an unreached x lives on in ulf
+    wi_unit_nodes_kernel<u32><<<dim3(gb), dim3(256), 0, ctx->stream>>>(r.uidx, r.ulf, r.nu, r.lf.LF, r.unit.nodes);
+    wi_rank_nodes(ctx, r.nu, r.unit.nodes, r.unit.rk);
+    unit_finish_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(r.nu, r.unit.rk.min_of(), r.unit.rk.sum_of(), r.unit.nodes, r.unit.dist, r.unit.min_dist, r.tiny, r.uleader,
+                                                               inv_counter(ctx, IC_UNIT_CYCLES));
+    HIPC(hipGetLastError());
+    BWTS_TRY(read_small(ctx, SMI_COUNTERS + IC_UNIT_CYCLES, 1));
+    r.kt = inv_count(ctx, IC_UNIT_CYCLES);              // these cycles take the place of the one-lane scan's
+    return r.kt == 0 || r.kt > r.nu ? BWTS_E_INTERNAL : BWTS_OK;
+}
+// order the cycles by smallest element on the device: sort (minelem, record), prefix sums of the lengths; then every node's place
+static int inv_order_cycles(bwts_ctx *ctx, InvRun &r)
+{
+    const u64 kall = r.kc + r.kt;
     ctx->tm.factors = kall;
-
-    // order the cycles by smallest element on the device: sort (minelem, record), prefix sums of the lengths
+    SpanGuard sg(ctx, BWTS_K_LISTRANK, kall, 0);
+    const CycleList cl{r.tiny, r.kt, r.l2.recs2, r.kc};
+    SortPlan cp;
+    BWTS_TRY(cycle_sort_plan(ctx, kall, &cp));
+    cycle_keys_kernel<<<dim3(grid1(kall)), dim3(256), 0, ctx->stream>>>(cl, cp.keys[0], cp.vals[0]);
+    int res = 0, kbits = bit_length(r.n - 1);
+    BWTS_TRY(radix_sort_pairs(ctx, cp, kall, kbits < 1 ? 1 : kbits, &res));
+    CycleLenIn lin{cl, cp.vals[res]};
+    CycleEndOut lout{cl, cp.vals[res], (u32)(r.n - 1), r.l2.end_by_leader, r.end_of_tiny, ctx->d_small + SMI_COUNTERS + IC_LENGTH_SUM};
+    BWTS_TRY((device_scan<false, u32>(ctx, kall, lin, lout, OpAdd(), 0u, cp.scan_temp)));
+    if (r.unit_rank) unit_ends_kernel<<<dim3(grid1(r.kt)), dim3(256), 0, ctx->stream>>>(r.uleader, r.end_of_tiny, r.kt, r.uend);
+    lr_place2_kernel<<<dim3(grid1(r.s2all)), dim3(256), 0, ctx->stream>>>(r.s2all, r.l2.lrmin[r.cur], r.l2.lrsum[r.sc], r.l2.dist, r.l2.min_dist, r.l2.end_by_leader, r.l2.place2);
+    lr2_distribute_kernel<<<dim3(grid1(r.s2all)), dim3(256), 0, ctx->stream>>>(r.nd.noderec, r.s2, r.s2all, r.nd.U, r.l2.place2, r.nd.opos, r.nd.wrap, r.nd.clen);
+    return launched(ctx);
+}
+// the recorded segments go to their places in the text (unbwts.c:73-82); the sum of the cycle lengths says whether every element was placed
+static int inv_place(bwts_ctx *ctx, InvRun &r, u8 *d_out, InvOutcome *out)
+{
     {
-        SpanGuard sg(ctx, BWTS_K_LISTRANK, kall, 0);
-        const CycleList cl{tiny, kt, d_recs2, kc};
-        SortPlan cp;
-        BWTS_TRY(cycle_sort_plan(ctx, kall, &cp));
-        cycle_keys_kernel<<<dim3(grid1(kall)), dim3(256), 0, ctx->stream>>>(cl, cp.keys[0], cp.vals[0]);
-        int res = 0;
-        int kbits = 0; for (u64 x = n - 1; x; x >>= 1) kbits++;
-        BWTS_TRY(radix_sort_pairs(ctx, cp, kall, kbits < 1 ? 1 : kbits, &res));
-        CycleLenIn lin{cl, cp.vals[res]};
-        CycleEndOut lout{cl, cp.vals[res], (u32)(n - 1), end_by_leader, end_of_tiny, ctx->d_small + SMI_COUNTERS + 13};
-        BWTS_TRY((device_scan<false, u32>(ctx, kall, lin, lout, OpAdd(), 0u, cp.scan_temp)));
-        if (unit_rank) unit_ends_kernel<<<dim3(grid1(kt)), dim3(256), 0, ctx->stream>>>(uleader, end_of_tiny, kt, uend);
-        lr_place2_kernel<<<dim3(grid1(s2all)), dim3(256), 0, ctx->stream>>>(s2all, lrmin[cur], lrsum[sc], dist, min_dist, end_by_leader, place2);
-        lr2_distribute_kernel<<<dim3(grid1(s2all)), dim3(256), 0, ctx->stream>>>(noderec, s2, s2all, U, place2, d_opos, d_wrap, d_clen);
+        SpanGuard sg(ctx, BWTS_K_WALK_EMIT, r.n, 2 * r.n);
+        const int tpn_log2 = r.g < 4 ? 0 : r.g > 12 ? 8 : r.g - 4;      // one 16-symbol chunk per thread at the expected segment length (G)
+        const u64 threads = r.s_all << tpn_log2;
+        place_segments_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream>>>(r.nd.seg, r.s_all, r.slot, tpn_log2, r.nd.noderec, r.nd.opos, r.nd.wrap,
+                                                                                                      r.nd.clen, d_out);
+        if (r.unit_rank)
+            wi_unit_place_kernel<u32><<<dim3(grid1(r.nu)), dim3(256), 0, ctx->stream>>>(r.nu, r.unit.rk.min_of(), r.unit.rk.sum_of(), r.unit.dist, r.unit.min_dist, r.uend, r.ulf,
+                                                                                        r.dC, d_out);
+        else if (r.kt) tiny_place_kernel<<<dim3(grid1(r.kt)), dim3(256), 0, ctx->stream>>>(r.tiny, r.kt, r.end_of_tiny, r.lf.LF, r.dC, d_out);
         HIPC(hipGetLastError());
     }
-
-    // the recorded segments go to their places in the text (unbwts.c:73-82)
-    {
-        SpanGuard sg(ctx, BWTS_K_WALK_EMIT, n, 2 * n);
-        int tpn_log2 = g - 4;                           // one 16-symbol chunk per thread at the expected segment length (G)
-        if (tpn_log2 < 0) tpn_log2 = 0;
-        if (tpn_log2 > 8) tpn_log2 = 8;
-        const u64 threads = s_all << tpn_log2;
-        place_segments_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream>>>(seg, s_all, slot, tpn_log2, noderec,
-                                                                                                      d_opos, d_wrap, d_clen, d_out);
-        if (unit_rank)
-            wi_unit_place_kernel<u32><<<dim3(grid1(nu)), dim3(256), 0, ctx->stream>>>(nu, umin[ucur], usum[usc], udist, umind, uend, ulf, dC, d_out);
-        else if (kt) tiny_place_kernel<<<dim3(grid1(kt)), dim3(256), 0, ctx->stream>>>(tiny, kt, end_of_tiny, LF, dC, d_out);
-        HIPC(hipGetLastError());
-    }
-    BWTS_TRY(read_small(ctx, SMI_COUNTERS + 13, 1));
-    if ((u32)ctx->h_small[SMI_COUNTERS + 13] != (u32)n) {
-        // n = 2^32 only: the one entry whose value equals LF_VISITED sat in a cycle without a splitter and was taken for visited
-        if (mark == MARK_SENTINEL && n == 0x100000000ull) { *ambiguous = true; return BWTS_OK; }
-        return BWTS_E_INTERNAL;
-    }
-    return BWTS_OK;
+    BWTS_TRY(read_small(ctx, SMI_COUNTERS + IC_LENGTH_SUM, 1));
+    if ((u32)inv_count(ctx, IC_LENGTH_SUM) == (u32)r.n) return BWTS_OK;
+    // n = 2^32 only: the one entry whose value equals LF_VISITED sat in a cycle without a splitter and was taken for visited
+    if (r.mark == MARK_SENTINEL && r.n == 0x100000000ull) { *out = INV_AMBIGUOUS; return BWTS_OK; }
+    return BWTS_E_INTERNAL;
+}
+// One attempt with splitter spacing 2^g: the stages in order; one that sets *out to anything but INV_DONE ends the attempt there.
+static int inverse_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, int g, int mark, InvOutcome *out)
+{
+    InvRun r(ctx, n, g, mark);
+    *out = INV_DONE;
+    BWTS_TRY(arena_place(ctx, r));
+    BWTS_TRY(inv_build_lf(ctx, r, d_in));
+    BWTS_TRY(inv_walk(ctx, r, out));
+    if (*out != INV_DONE) return BWTS_OK;
+    BWTS_TRY(inv_find_unreached(ctx, r, out));
+    if (*out != INV_DONE) return BWTS_OK;
+    BWTS_TRY(inv_rank_node_list(ctx, r));
+    BWTS_TRY(inv_free_cycles(ctx, r, out));
+    if (*out != INV_DONE) return BWTS_OK;
+    BWTS_TRY(inv_order_cycles(ctx, r));
+    return inv_place(ctx, r, d_out, out);
 }
 
 int inverse_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
@@ -1312,37 +1294,30 @@ int inverse_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
         }
     }
     if (n > 0x100000000ull || force_wide) return inverse_wide_impl(ctx, d_in, n, d_out);
-    bool retry = false, ambiguous = false;
-    // how the unreached elements are found: per-range moments (default; falls back to the index log when too many are missing),
-    // the index log, or the two mark forms (BWTS_INV_MARK=log|sentinel|bytemap, BWTS_BYTEMARK=1: tests, and the fallback chain below)
+    // how the unreached elements are found: per-class moments (default), the index log, or the two mark forms
+    // (BWTS_INV_MARK=log|sentinel|bytemap, BWTS_BYTEMARK=1: tests, and the fallback chain below)
     int mark = MARK_MOMENTS;
     const char *me = bwts_knob(ctx, "BWTS_INV_MARK");
     if (me && !strcmp(me, "log")) mark = MARK_LOG;
     if (me && !strcmp(me, "sentinel")) mark = MARK_SENTINEL;
     if ((me && !strcmp(me, "bytemap")) || bwts_knob(ctx, "BWTS_BYTEMARK")) mark = MARK_BYTEMAP;
-    bool need_log = false;
-    // Worst case: the walk runs up to five times (moments -> index log -> byte map at n = 2^32 -> every element a splitter, with
-    // sentinel and then byte-map marks); natural inputs take one.  bwts_timings.attempts says how many it was.
-    ctx->tm.attempts = 1;
-    BWTS_TRY(inverse_attempt(ctx, d_in, n, d_out, splitter_log2(ctx, n), mark, &retry, &ambiguous, &need_log));
-    if (need_log) {             // many unreached elements (low-entropy input): the walk again, this time logging every index it visits
-        mark = MARK_LOG;
-        ctx->tm.attempts++;
-        BWTS_TRY(inverse_attempt(ctx, d_in, n, d_out, splitter_log2(ctx, n), mark, &retry, &ambiguous));
+    // The fallback chain: every outcome but INV_DONE names the next (g, mark).  Worst case the walk runs five times (moments -> index
+    // log -> byte map at n = 2^32 -> every element a splitter, with sentinel and then byte-map marks); natural inputs take one.
+    // bwts_timings.attempts says how many it was.
+    int g = splitter_log2(ctx, n);
+    bool dense = false;
+    for (;; ctx->tm.attempts++) {
+        InvOutcome out;
+        BWTS_TRY(inverse_attempt(ctx, d_in, n, d_out, g, mark, &out));
+        if (out == INV_DONE) return BWTS_OK;
+        if (out == INV_NEED_LOG) mark = MARK_LOG;           // many unreached elements (low-entropy input): the walk again, logging every index it visits
+        else if (out == INV_AMBIGUOUS) mark = MARK_BYTEMAP; // sentinel marks only
+        else {                                              // INV_RETRY_DENSE, once: on the simplest marks
+            if (dense) return BWTS_E_INTERNAL;
+            dense = true; g = 0;
+            if (mark == MARK_LOG || mark == MARK_MOMENTS) mark = MARK_SENTINEL;
+        }
     }
-    if (ambiguous) {            // sentinel marks only, n = 2^32: 0xffffffff was a real entry of a cycle without a splitter
-        mark = MARK_BYTEMAP;
-        ctx->tm.attempts++;
-        BWTS_TRY(inverse_attempt(ctx, d_in, n, d_out, splitter_log2(ctx, n), mark, &retry, &ambiguous));
-    }
-    if (retry) {
-        if (mark == MARK_LOG || mark == MARK_MOMENTS) mark = MARK_SENTINEL;        // adversarial LF: keep the retry on the simplest marks
-        ctx->tm.attempts++;
-        BWTS_TRY(inverse_attempt(ctx, d_in, n, d_out, 0, mark, &retry, &ambiguous));
-        if (ambiguous) { ctx->tm.attempts++; BWTS_TRY(inverse_attempt(ctx, d_in, n, d_out, 0, MARK_BYTEMAP, &retry, &ambiguous)); }
-        if (retry || ambiguous) return BWTS_E_INTERNAL;
-    }
-    return BWTS_OK;
 }
 
 // ------------------------------------------------------------------------------------

@@ -377,8 +377,303 @@ struct ScopedDeviceBlock {
     }
     ~ScopedDeviceBlock() { if (p) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(p); } }
 };
-
-static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool moments, bool compact, bool *need_marks);
+// The pointer jumping over a node list (the wide node list, and the unit nodes of both forms): its two ping-pong pairs, declared
+// into the caller's layout, and which side of each holds the result
+struct WiRanking {
+    WiMin *mn[2] = {nullptr, nullptr}; WiSum *sum[2] = {nullptr, nullptr}; int cur = 0, sc = 0;
+    void declare(BlockLayout &L, u64 count) { L.arrays(count, &mn[0], &mn[1], &sum[0], &sum[1]); }
+    const WiMin *min_of() const { return mn[cur]; } const WiSum *sum_of() const { return sum[sc]; }
+};
+// wi_init -> R x wi_jump_min -> wi_cut -> R x wi_jump_sum, 2^R > count >= any cycle's node count.  The finish kernel is the caller's.
+static void wi_rank_nodes(bwts_ctx *ctx, u64 count, const WiNode *nodes, WiRanking &k)
+{
+    const int gb = grid1(count), R = bit_length(count);
+    wi_init_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(count, nodes, k.mn[0]);
+    for (int r = 0; r < R; r++, k.cur ^= 1) wi_jump_min_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(count, k.mn[k.cur], k.mn[k.cur ^ 1]);
+    wi_cut_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(count, nodes, k.mn[k.cur], k.sum[0]);
+    for (int r = 0; r < R; r++, k.sc ^= 1) wi_jump_sum_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(count, k.sum[k.sc], k.sum[k.sc ^ 1]);
+}
+// Side block 0 of an attempt (InvRun, WideRun): room for `cap` unreached elements (uidx, ulf), and for the records and ends of cap +
+// `more` cycles -- the cycles without a splitter (at most cap), in the wide form next to those of the node list
+template <typename RUN, typename CYC, typename END> static int lay_out_unreached(bwts_ctx *ctx, RUN &r, u64 cap, u64 more, CYC **cyc, END **ends)
+{
+    char *ub = nullptr; BlockLayout L;
+    L.arrays(cap, &r.uidx, &r.ulf); L.array(cyc, cap + more); L.array(ends, cap + more);
+    BWTS_TRY(aux_reserve_slot(ctx, 0, L.bytes(), &ub));
+    L.place(ub);
+    r.ucap = cap;
+    return BWTS_OK;
+}
+// one lane of the scan for cycles without a splitter follows at most so many elements: bounds the work of an adversarial LF (many long cycles that dodge every splitter)
+static u32 one_lane_cap(u64 nu, u64 G) { const u64 cap = (1ull << 36) / nu; return (u32)(cap > 64 * G ? 64 * G : cap < 4 * G ? 4 * G : cap); }
+// The unit-node route's tables, in a block taken from the device for the call (about 110 bytes per unreached element): the caller
+// declares its own ends (and leaders) behind them -- u64 here, u32 on the main path
+struct UnitRank {
+    WiNode *nodes = nullptr; WiRanking rk; u64 *dist = nullptr, *min_dist = nullptr;
+    void declare(BlockLayout &L, u64 nu) { L.array(&nodes, nu); rk.declare(L, nu); L.arrays(nu, &dist, &min_dist); }
+};
+// One attempt of the 64-bit form: its sizes, its arrays in the arena, and what one stage hands to the next
+struct WideRun {
+    u64 n, G, s, node_cap, segn, nseg; u32 slot; bool moments, compact;
+    size_t lf_bytes, mark_bytes, overlay_bytes = 0;
+    u64 *LF = nullptr; u32 *LF40 = nullptr;             // the map: full form, compact form
+    u8 *marks = nullptr, *seg = nullptr; unsigned long long *mom = nullptr; u32 *def_list = nullptr, *tile_hist = nullptr; void *scan_temp = nullptr;
+    WiNode *nodes = nullptr; WiRanking rk; WiCycle *ncyc = nullptr;
+    u64 *dist = nullptr, *min_dist = nullptr, *end_by_leader = nullptr, *opos = nullptr, *wrap_at = nullptr, *cyc_len = nullptr, *dC = nullptr;
+    u64 ucap = 0, *uidx = nullptr, *ulf = nullptr, *end_of_cyc = nullptr; WiCycle *cyc = nullptr;      // side block 0: the unreached elements; all cycles and their ends
+    u64 s_all = 0, nu = 0, kc = 0, kt = 0; bool unit_rank = false;     // ... the unit-node route: its block, taken from the device for the call
+    UnitRank unit; u64 *uend = nullptr; ScopedDeviceBlock ub;
+    WideRun(bwts_ctx *ctx, u64 n_, bool moments_, bool compact_) : n(n_), moments(moments_), compact(compact_), ub(ctx)
+    {
+        G = 1ull << (compact ? WC_G_LOG2 : WI_G_LOG2); s = (n + G - 1) / G;
+        // compact: one splitter spacing per record (BWTS_WIDE_SLOT, a multiple of 64, for tests), and the pool's hard bound -- every
+        // overflow node follows a node that recorded a full slot, and the walk records each element at most once
+        slot = (u32)(compact ? G : 4 * G);
+        if (const char *e = compact ? bwts_knob(ctx, "BWTS_WIDE_SLOT") : nullptr) { const long v = atol(e); if (v >= 64 && v <= (1 << 20) && v % 64 == 0) slot = (u32)v; }
+        node_cap = compact ? s + (n + slot - 1) / slot + 1024 : s + s / 8 + 1024;
+        int seg_log2 = 31;
+        if (const char *e = bwts_knob(ctx, "BWTS_WIDE_SEG_LOG2")) { const int v = atoi(e); if (v >= 12 && v <= 31) seg_log2 = v; }
+        segn = 1ull << seg_log2; nseg = (n + segn - 1) / segn;
+        lf_bytes = compact ? lf40_bytes(n) : BlockLayout::padded<u64>(n);
+        // marks: bytes in the full form; bits in the compact one, laid over the ranking tables -- the walk sets them and every collection
+        // (a second one where the first ran out of room) reads them before the ranking writes those tables: the fallback needs no more
+        // memory than the moments
+        mark_bytes = compact ? (n + 31) / 32 * 4 : n;
+    }
+    void declare(BlockLayout &L)
+    {
+        if (compact) L.raw(&LF40, lf_bytes); else L.raw(&LF, lf_bytes);
+        L.raw(&marks, moments || compact ? 256 : align_up(mark_bytes, 256));      // no byte map kept: a token block (the kernels take a pointer)
+        L.array(&mom, 3 * WMOM_BUCKETS); L.array(&def_list, WMOM_BUCKETS); L.array(&seg, node_cap * slot); L.array(&nodes, node_cap);
+        const size_t ranking_from = L.bytes(); rk.declare(L, node_cap);
+        L.arrays(node_cap, &dist, &min_dist, &end_by_leader, &opos, &wrap_at, &cyc_len); L.array(&ncyc, node_cap);
+        overlay_bytes = L.bytes() - ranking_from;       // rk.mn[0] .. the end of ncyc: where the compact form's mark bits go
+        L.raw(&tile_hist, radix_tile_hist_bytes(segn)); L.raw(&scan_temp, scan_temp_bytes(segn)); L.pad(INV_ARENA_SLACK);
+    }
+};
+static int wide_reserve(bwts_ctx *ctx, WideRun &r)
+{
+    BWTS_TRY(arena_place(ctx, r));
+    if (r.compact && !r.moments) {
+        if (r.overlay_bytes < r.mark_bytes) return BWTS_E_INTERNAL;
+        r.marks = (u8 *)r.rk.mn[0];
+    }
+    return BWTS_OK;
+}
+// symbol boundaries C (unbwts.c:34-43), 64-bit, and the stable LF map (unbwts.c:50-52), segment by segment
+static int wide_build_lf(bwts_ctx *ctx, WideRun &r, const u8 *d_in)
+{
+    const u64 n = r.n;
+    u64 *hC = ctx->h_small + 1024, *dBase = ctx->d_small + 1536, *hBase = ctx->h_small + 1536, *dHist = ctx->d_small + 2048, *hHist = ctx->h_small + 2048;
+    BWTS_TRY(byte_histogram_device(ctx, d_in, n, dHist));
+    BWTS_TRY(read_small(ctx, 2048, 256));
+    {
+        u64 run = 0;
+        for (int c = 0; c < 256; c++) { hC[c] = run; run += hHist[c]; }
+        hC[256] = n;
+        if (run != n) return BWTS_E_INTERNAL;
+    }
+    HIPC(hipMemcpyAsync(r.dC, hC, 257 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    u64 before[256] = {0};
+    for (u64 sg = 0; sg < r.nseg; sg++) {
+        const u64 p0 = sg * r.segn, c = n - p0 < r.segn ? n - p0 : r.segn;
+        const u64 tiles = (c + LF_TILE - 1) / LF_TILE;
+        SpanGuard g(ctx, BWTS_K_LF_BUILD, c, 10 * c);
+        BWTS_TRY(byte_histogram_device(ctx, d_in + p0, c, dHist));
+        BWTS_TRY(read_small(ctx, 2048, 256));
+        {
+            u64 run = 0;
+            for (int q = 0; q < 256; q++) { hBase[q] = hC[q] + before[q] - run; run += hHist[q]; before[q] += hHist[q]; }
+        }
+        HIPC(hipMemcpyAsync(dBase, hBase, 256 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+        lf_hist_kernel<<<dim3((unsigned)tiles), dim3(LF_THREADS), 0, ctx->stream>>>(d_in + p0, c, r.tile_hist);
+        BWTS_TRY(radix_column_scan(ctx, r.tile_hist, tiles, r.scan_temp));
+        if (r.compact) lf_rank_c40_kernel<<<dim3((unsigned)tiles), dim3(LF_THREADS), 0, ctx->stream>>>(d_in + p0, c, r.tile_hist, dBase, (u8 *)r.LF40 + 5 * p0);
+        else lf_rank_wide_kernel<<<dim3((unsigned)tiles), dim3(LF_THREADS), 0, ctx->stream>>>(d_in + p0, c, r.tile_hist, dBase, r.LF + p0);
+        HIPC(hipGetLastError());
+        HIPC(hipStreamSynchronize(ctx->stream));            // hBase is rewritten by the next segment
+    }
+    return BWTS_OK;
+}
+template <typename K, typename LFW, typename MARKW> static int launch_wide_walk(bwts_ctx *ctx, const WideRun &r, K kernel, const LFW *LF, MARKW *marks)
+{
+    const u64 walkers = r.s < 524288 ? r.s : 524288;
+    const size_t lds = r.moments ? (size_t)WMOM_BUCKETS * (8 + 8 + 4) : 0;
+    if (r.moments) BWTS_TRY(ensure_dyn_lds(ctx, (const void *)kernel, lds));
+    kernel<<<dim3((unsigned)((walkers + 255) / 256)), dim3(256), lds, ctx->stream>>>(LF, marks, r.s, r.node_cap, r.slot, r.dC, r.seg, r.nodes, inv_counter(ctx, IC_TICKET),
+                                                                                     inv_counter(ctx, IC_VIRTUAL), inv_counter(ctx, IC_OVERFLOW), r.moments ? WMOM_LOG2 : 0,
+                                                                                     r.moments ? r.mom : nullptr);
+    return launched(ctx);
+}
+static int wide_walk(bwts_ctx *ctx, WideRun &r)
+{
+    HIPC(hipMemsetAsync(inv_counter(ctx, 0), 0, IC_WORDS * sizeof(u64), ctx->stream));
+    if (r.moments) HIPC(hipMemsetAsync(r.mom, 0, 3 * WMOM_BUCKETS * sizeof(u64), ctx->stream));
+    else HIPC(hipMemsetAsync(r.marks, 0, r.mark_bytes, ctx->stream));
+    {
+        SpanGuard sg(ctx, BWTS_K_WALK, r.n, 10 * r.n);
+        if (r.compact && r.moments) BWTS_TRY(launch_wide_walk(ctx, r, walk_record_c40_kernel<true>, r.LF40, (u32 *)r.marks));
+        else if (r.compact) BWTS_TRY(launch_wide_walk(ctx, r, walk_record_c40_kernel<false>, r.LF40, (u32 *)r.marks));
+        else if (r.moments) BWTS_TRY(launch_wide_walk(ctx, r, walk_record_wide_kernel<true>, r.LF, r.marks));
+        else BWTS_TRY(launch_wide_walk(ctx, r, walk_record_wide_kernel<false>, r.LF, r.marks));
+    }
+    BWTS_TRY(read_small(ctx, SMI_COUNTERS, IC_WORDS));
+    if (inv_count(ctx, IC_OVERFLOW)) return r.compact ? BWTS_E_INTERNAL : BWTS_E_NOMEM;     // node pool exhausted (adversarial LF): the compact form's pool cannot be
+    r.s_all = r.s + inv_count(ctx, IC_VIRTUAL);
+    return BWTS_OK;
+}
+static int wide_collect(bwts_ctx *ctx, WideRun &r)
+{
+    SpanGuard sg(ctx, BWTS_K_OTHER, r.n, r.n);
+    const u64 n = r.n; unsigned long long *ctr = inv_counter(ctx, 0);
+    if (r.moments) {
+        HIPC(hipMemsetAsync(inv_counter(ctx, IC_LISTED_CLASSES), 0, 2 * sizeof(u64), ctx->stream));      // ... and IC_MOM_FALLBACK
+        const u64 per_class = (n + WMOM_BUCKETS - 1) >> WMOM_LOG2;
+        const u64 budget = (8ull << 20) > per_class ? (8ull << 20) : per_class;        // elements the search may look at (at least one class)
+        if (r.compact) moments_solve_c40_kernel<<<dim3(WMOM_BUCKETS / 1024), dim3(1024), 0, ctx->stream>>>(r.mom, n, WMOM_LOG2, r.LF40, r.uidx, r.ulf, r.ucap, r.def_list, ctr);
+        else moments_solve_wide_kernel<<<dim3(WMOM_BUCKETS / 1024), dim3(1024), 0, ctx->stream>>>(r.mom, n, WMOM_LOG2, r.LF, r.uidx, r.ulf, r.ucap, r.def_list, ctr);
+        moments_budget_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(ctr, per_class, budget);
+        if (r.compact) moments_chase_c40_kernel<<<dim3(4096), dim3(256), 0, ctx->stream>>>(r.def_list, ctr, n, WMOM_LOG2, r.LF40, 1u << 16, r.uidx, r.ulf, r.ucap, ctr);
+        else moments_chase_wide_kernel<<<dim3(4096), dim3(256), 0, ctx->stream>>>(r.def_list, ctr, n, WMOM_LOG2, r.LF, 1u << 16, r.uidx, r.ulf, r.ucap, ctr);
+    } else {
+        u64 blocks = (n + 255) / 256; if (blocks > 16384) blocks = 16384;
+        unsigned long long *found = inv_counter(ctx, IC_UNREACHED);
+        if (r.compact) collect_unvisited_c40_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(r.LF40, (const u32 *)r.marks, n, r.uidx, r.ulf, r.ucap, found);
+        else collect_unvisited_wide_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(r.LF, r.marks, n, r.uidx, r.ulf, r.ucap, found);
+    }
+    return launched(ctx);
+}
+// collect, count, and collect again where the first room was too small -- before the ranking writes its tables: the compact form's mark bits lie over them
+static int wide_collect_unreached(bwts_ctx *ctx, WideRun &r, bool *need_marks)
+{
+    const u64 ucap = ctx->unv_hint > (1ull << 20) ? ctx->unv_hint : (1ull << 20);
+    BWTS_TRY(lay_out_unreached(ctx, r, ucap > r.n ? r.n : ucap, r.node_cap, &r.cyc, &r.end_of_cyc));
+    BWTS_TRY(wide_collect(ctx, r));
+    BWTS_TRY(read_small(ctx, SMI_COUNTERS, IC_WORDS));
+    if (r.moments && inv_count(ctx, IC_MOM_FALLBACK)) { *need_marks = true; return BWTS_OK; }     // too many unreached elements for the moments: the byte map
+    r.nu = inv_count(ctx, IC_UNREACHED);
+    if (r.nu > r.n) return BWTS_E_INTERNAL;
+    if (r.nu > r.ucap) {
+        BWTS_TRY(lay_out_unreached(ctx, r, r.nu, r.node_cap, &r.cyc, &r.end_of_cyc));
+        HIPC(hipMemsetAsync(inv_counter(ctx, IC_UNREACHED), 0, sizeof(u64), ctx->stream));
+        BWTS_TRY(wide_collect(ctx, r));
+        BWTS_TRY(read_small(ctx, SMI_COUNTERS, IC_WORDS));
+        if (inv_count(ctx, IC_UNREACHED) != r.nu) return BWTS_E_INTERNAL;
+    }
+    return BWTS_OK;
+}
+// pointer jumping over the nodes; cycle records of the node list
+static int wide_rank_node_list(bwts_ctx *ctx, WideRun &r)
+{
+    {
+        SpanGuard sg(ctx, BWTS_K_LISTRANK, r.s_all, 0);
+        wi_rank_nodes(ctx, r.s_all, r.nodes, r.rk);
+        wi_finish_kernel<<<dim3(grid1(r.s_all)), dim3(256), 0, ctx->stream>>>(r.s_all, r.rk.min_of(), r.rk.sum_of(), r.nodes, r.dist, r.min_dist, r.ncyc,
+                                                                             inv_counter(ctx, IC_LIST_CYCLES));
+        HIPC(hipGetLastError());
+    }
+    BWTS_TRY(read_small(ctx, SMI_COUNTERS, IC_WORDS));
+    r.kc = inv_count(ctx, IC_LIST_CYCLES);
+    ctx->tm.unvisited = r.nu; ctx->unv_hint = (size_t)r.nu;
+    return r.kc == 0 || r.kc > r.s_all ? BWTS_E_INTERNAL : BWTS_OK;
+}
+// cycles without a splitter: the one-lane scan, or the unit-node ranking
+static int wide_free_cycles(bwts_ctx *ctx, WideRun &r)
+{
+    if (r.nu) {
+        SpanGuard sg(ctx, BWTS_K_OTHER, r.nu, 16 * r.nu);
+        const u32 cap = one_lane_cap(r.nu, r.G);
+        unsigned long long *count = inv_counter(ctx, IC_FREE_CYCLES), *overflow = inv_counter(ctx, IC_OVERFLOW);
+        if (r.compact) tiny_cycle_scan_c40_kernel<<<dim3(grid1(r.nu)), dim3(256), 0, ctx->stream>>>(r.uidx, r.ulf, r.nu, r.LF40, cap, r.cyc, count, overflow);
+        else tiny_cycle_scan_wide_kernel<<<dim3(grid1(r.nu)), dim3(256), 0, ctx->stream>>>(r.uidx, r.ulf, r.nu, r.LF, cap, r.cyc, count, overflow);
+        HIPC(hipGetLastError());
+    }
+    BWTS_TRY(read_small(ctx, SMI_COUNTERS, IC_WORDS));
+    r.kt = inv_count(ctx, IC_FREE_CYCLES);
+    if (r.kt > r.nu) return BWTS_E_INTERNAL;
+    r.unit_rank = inv_count(ctx, IC_OVERFLOW) != 0;
+    if (!r.unit_rank) return BWTS_OK;
+    // a cycle without a splitter too long for one lane: all unreached elements are ranked as nodes of one symbol instead
+    SpanGuard sg(ctx, BWTS_K_LISTRANK, r.nu, 0);
+    if (r.nu >= 0x7ffffff0ull) return BWTS_E_NOMEM;
+    BlockLayout L; r.unit.declare(L, r.nu); L.array(&r.uend, r.nu);
+    BWTS_TRY(r.ub.take(L.bytes()));
+    L.place(r.ub.p);
+    const int gb = grid1(r.nu);
+    HIPC(hipMemsetAsync(inv_counter(ctx, IC_UNIT_CYCLES), 0, sizeof(u64), ctx->stream));
+    if (r.compact) {
+        wi_unit_index_c40_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(r.uidx, r.nu, r.LF40);
+        wi_unit_nodes_c40_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(r.uidx, r.ulf, r.nu, r.LF40, r.unit.nodes);
+    } else {
+        wi_unit_index_kernel<u64><<<dim3(gb), dim3(256), 0, ctx->stream>>>(r.uidx, r.nu, r.LF);
+        wi_unit_nodes_kernel<u64><<<dim3(gb), dim3(256), 0, ctx->stream>>>(r.uidx, r.ulf, r.nu, r.LF, r.unit.nodes);
+    }
+    wi_rank_nodes(ctx, r.nu, r.unit.nodes, r.unit.rk);
+    wi_finish_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(r.nu, r.unit.rk.min_of(), r.unit.rk.sum_of(), r.unit.nodes, r.unit.dist, r.unit.min_dist, r.cyc,
+                                                             inv_counter(ctx, IC_UNIT_CYCLES));
+    HIPC(hipGetLastError());
+    BWTS_TRY(read_small(ctx, SMI_COUNTERS + IC_UNIT_CYCLES, 1));
+    r.kt = inv_count(ctx, IC_UNIT_CYCLES);          // these cycles take the place of the one-lane scan's
+    if (r.kt == 0 || r.kt > r.nu) return BWTS_E_INTERNAL;
+    wi_unit_tag_kernel<<<dim3(grid1(r.kt)), dim3(256), 0, ctx->stream>>>(r.cyc, r.kt);
+    return launched(ctx);
+}
+// all cycles by smallest element, the ends of their stretches of text, every node's place
+static int wide_order_cycles(bwts_ctx *ctx, WideRun &r)
+{
+    const u64 kall = r.kc + r.kt;
+    ctx->tm.factors = kall;
+    SpanGuard sg(ctx, BWTS_K_LISTRANK, kall, 0);
+    HIPC(hipMemcpyAsync(r.cyc + r.kt, r.ncyc, r.kc * sizeof(WiCycle), hipMemcpyDeviceToDevice, ctx->stream));
+    SortPlan cp;
+    BWTS_TRY(cycle_sort_plan(ctx, kall, &cp));
+    wi_cycle_keys_kernel<<<dim3(grid1(kall)), dim3(256), 0, ctx->stream>>>(r.cyc, kall, cp.keys[0], cp.vals[0]);
+    int res = 0, kbits = bit_length(r.n - 1);
+    BWTS_TRY(radix_sort_pairs(ctx, cp, kall, kbits < 1 ? 1 : kbits, &res));
+    WiLenIn lin{r.cyc, cp.vals[res]};
+    WiEndOut lout{r.cyc, cp.vals[res], kall, r.n - 1, r.end_by_leader, r.end_of_cyc, ctx->d_small + SMI_COUNTERS + IC_LENGTH_SUM, r.uend};
+    BWTS_TRY((device_scan<false, u64>(ctx, kall, lin, lout, OpAdd(), (u64)0, cp.scan_temp)));
+    wi_place_kernel<<<dim3(grid1(r.s_all)), dim3(256), 0, ctx->stream>>>(r.s_all, r.rk.min_of(), r.rk.sum_of(), r.dist, r.min_dist, r.end_by_leader, r.opos, r.wrap_at, r.cyc_len);
+    return launched(ctx);
+}
+static int wide_place(bwts_ctx *ctx, WideRun &r, u8 *d_out)
+{
+    {
+        SpanGuard sg(ctx, BWTS_K_WALK_EMIT, r.n, 2 * r.n);
+        // threads per node: 16 (the full form's records loop over 4 G); in the compact form one per 16 bytes of a slot, at most 64
+        int tpn_log2 = WI_G_LOG2 - 4;
+        if (r.compact) { tpn_log2 = 2; while (tpn_log2 < 6 && (16u << (tpn_log2 + 1)) <= r.slot) tpn_log2++; }
+        const u64 threads = r.s_all << tpn_log2;
+        place_segments_wide_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream>>>(r.seg, r.s_all, r.slot, tpn_log2, r.nodes, r.opos, r.wrap_at,
+                                                                                                           r.cyc_len, d_out);
+        if (r.unit_rank)
+            wi_unit_place_kernel<u64><<<dim3(grid1(r.nu)), dim3(256), 0, ctx->stream>>>(r.nu, r.unit.rk.min_of(), r.unit.rk.sum_of(), r.unit.dist, r.unit.min_dist, r.uend, r.ulf,
+                                                                                        r.dC, d_out);
+        else if (r.kt && r.compact) tiny_place_c40_kernel<<<dim3(grid1(r.kt)), dim3(256), 0, ctx->stream>>>(r.cyc, r.kt, r.end_of_cyc, r.LF40, r.dC, d_out);
+        else if (r.kt) tiny_place_wide_kernel<<<dim3(grid1(r.kt)), dim3(256), 0, ctx->stream>>>(r.cyc, r.kt, r.end_of_cyc, r.LF, r.dC, d_out);
+        HIPC(hipGetLastError());
+    }
+    BWTS_TRY(read_small(ctx, SMI_COUNTERS + IC_LENGTH_SUM, 1));
+    return inv_count(ctx, IC_LENGTH_SUM) == r.n ? BWTS_OK : BWTS_E_INTERNAL;
+}
+// One attempt of one form with one way of finding the unreached elements: the stages in order
+static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool moments, bool compact, bool *need_marks)
+{
+    *need_marks = false;
+    if (n > (1ull << 36)) return BWTS_E_RANGE;
+    WideRun r(ctx, n, moments, compact);
+    if (r.node_cap > 0xfffffff0ull) return BWTS_E_RANGE;
+    BWTS_TRY(wide_reserve(ctx, r));
+    BWTS_TRY(wide_build_lf(ctx, r, d_in));
+    BWTS_TRY(wide_walk(ctx, r));
+    BWTS_TRY(wide_collect_unreached(ctx, r, need_marks));
+    if (*need_marks) return BWTS_OK;
+    BWTS_TRY(wide_rank_node_list(ctx, r));
+    BWTS_TRY(wide_free_cycles(ctx, r));
+    BWTS_TRY(wide_order_cycles(ctx, r));
+    return wide_place(ctx, r, d_out);
+}
 static int inverse_wide_form(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool compact)
 {
     // unreached elements from per-range moments; the byte map when too many are missing (or BWTS_INV_MARK=bytemap / BWTS_BYTEMARK=1)
@@ -405,274 +700,4 @@ static int inverse_wide_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
         BWTS_TRY(aux_release(ctx));
     }
     return inverse_wide_form(ctx, d_in, n, d_out, true);
-}
-static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool moments, bool compact, bool *need_marks)
-{
-    *need_marks = false;
-    if (n > (1ull << 36)) return BWTS_E_RANGE;
-    const int mom_shift = WMOM_LOG2;
-    const int g_log2 = compact ? WC_G_LOG2 : WI_G_LOG2;
-    const u64 G = 1ull << g_log2;
-    const u64 s = (n + G - 1) / G;
-    // compact: one splitter spacing per record (BWTS_WIDE_SLOT, a multiple of 64, for tests), and the pool's hard bound -- every
-    // overflow node follows a node that recorded a full slot, and the walk records each element at most once
-    u32 slot = (u32)(4 * G);
-    if (compact) {
-        slot = (u32)G;
-        if (const char *e = bwts_knob(ctx, "BWTS_WIDE_SLOT")) { const long v = atol(e); if (v >= 64 && v <= (1 << 20) && v % 64 == 0) slot = (u32)v; }
-    }
-    const u64 node_cap = compact ? s + (n + slot - 1) / slot + 1024 : s + s / 8 + 1024;
-    if (node_cap > 0xfffffff0ull) return BWTS_E_RANGE;
-    int seg_log2 = 31;
-    if (const char *e = bwts_knob(ctx, "BWTS_WIDE_SEG_LOG2")) { const int v = atoi(e); if (v >= 12 && v <= 31) seg_log2 = v; }
-    const u64 segn = 1ull << seg_log2;
-    const u64 nseg = (n + segn - 1) / segn;
-    const size_t lf_bytes = compact ? lf40_bytes(n) : align_up(n * 8, 256);
-    // marks: bytes in the full form; bits in the compact one, laid over the ranking tables -- the walk sets them and every collection
-    // (a second one where the first ran out of room) reads them before the ranking writes those tables: the fallback needs no more
-    // memory than the moments
-    const size_t mark_bytes = compact ? (n + 31) / 32 * 4 : n;
-    const size_t need = lf_bytes + (compact ? 0 : align_up(mark_bytes, 256)) + align_up(node_cap * slot, 256) + align_up(node_cap * sizeof(WiNode), 256) +
-                        2 * align_up(node_cap * sizeof(WiMin), 256) + 2 * align_up(node_cap * sizeof(WiSum), 256) + 6 * align_up(node_cap * 8, 256) +
-                        align_up(node_cap * sizeof(WiCycle), 256) + radix_tile_hist_bytes(segn) + scan_temp_bytes(segn) + (1 << 18);
-    BWTS_TRY(arena_reserve(ctx, need));
-    u64 *LF = compact ? nullptr : arena_array<u64>(ctx, n);
-    u32 *LF40 = compact ? (u32 *)arena_alloc(ctx, lf_bytes) : nullptr;
-    u8 *marks = moments || compact ? (u8 *)arena_alloc(ctx, 256) : arena_array<u8>(ctx, mark_bytes);
-    unsigned long long *mom = (unsigned long long *)arena_array<u64>(ctx, 3 * WMOM_BUCKETS);
-    u32 *def_list = arena_array<u32>(ctx, WMOM_BUCKETS);
-    if (!mom || !def_list) return BWTS_E_NOMEM;
-    u8 *seg = arena_array<u8>(ctx, node_cap * slot);
-    WiNode *nodes = arena_array<WiNode>(ctx, node_cap);
-    WiMin *wmin[2] = {arena_array<WiMin>(ctx, node_cap), arena_array<WiMin>(ctx, node_cap)};
-    WiSum *wsum[2] = {arena_array<WiSum>(ctx, node_cap), arena_array<WiSum>(ctx, node_cap)};
-    u64 *dist = arena_array<u64>(ctx, node_cap), *min_dist = arena_array<u64>(ctx, node_cap), *end_by_leader = arena_array<u64>(ctx, node_cap);
-    u64 *opos = arena_array<u64>(ctx, node_cap), *wrap_at = arena_array<u64>(ctx, node_cap), *cyc_len = arena_array<u64>(ctx, node_cap);
-    WiCycle *ncyc = arena_array<WiCycle>(ctx, node_cap);
-    if (compact && !moments && ncyc) {
-        if ((size_t)((char *)(ncyc + node_cap) - (char *)wmin[0]) < mark_bytes) return BWTS_E_INTERNAL;
-        marks = (u8 *)wmin[0];
-    }
-    u32 *tile_hist = (u32 *)arena_alloc(ctx, radix_tile_hist_bytes(segn));
-    void *scan_temp = arena_alloc(ctx, scan_temp_bytes(segn));
-    if (!(LF || LF40) || !marks || !seg || !nodes || !wmin[1] || !wsum[1] || !dist || !min_dist || !end_by_leader || !opos || !wrap_at || !cyc_len || !ncyc ||
-        !tile_hist || !scan_temp)
-        return BWTS_E_NOMEM;
-
-    // symbol boundaries C (unbwts.c:34-43), 64-bit
-    u64 *dC = ctx->d_small + 1024, *hC = ctx->h_small + 1024;
-    u64 *dBase = ctx->d_small + 1536, *hBase = ctx->h_small + 1536;
-    u64 *dHist = ctx->d_small + 2048, *hHist = ctx->h_small + 2048;
-    BWTS_TRY(byte_histogram_device(ctx, d_in, n, dHist));
-    BWTS_TRY(read_small(ctx, 2048, 256));
-    {
-        u64 run = 0;
-        for (int c = 0; c < 256; c++) { hC[c] = run; run += hHist[c]; }
-        hC[256] = n;
-        if (run != n) return BWTS_E_INTERNAL;
-    }
-    HIPC(hipMemcpyAsync(dC, hC, 257 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-    HIPC(hipStreamSynchronize(ctx->stream));
-    // stable LF map (unbwts.c:50-52), segment by segment
-    u64 before[256];
-    for (int c = 0; c < 256; c++) before[c] = 0;
-    for (u64 sg = 0; sg < nseg; sg++) {
-        const u64 p0 = sg * segn, c = n - p0 < segn ? n - p0 : segn;
-        const u64 tiles = (c + LF_TILE - 1) / LF_TILE;
-        SpanGuard g(ctx, BWTS_K_LF_BUILD, c, 10 * c);
-        BWTS_TRY(byte_histogram_device(ctx, d_in + p0, c, dHist));
-        BWTS_TRY(read_small(ctx, 2048, 256));
-        {
-            u64 run = 0;
-            for (int q = 0; q < 256; q++) { hBase[q] = hC[q] + before[q] - run; run += hHist[q]; before[q] += hHist[q]; }
-        }
-        HIPC(hipMemcpyAsync(dBase, hBase, 256 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-        lf_hist_kernel<<<dim3((unsigned)tiles), dim3(LF_THREADS), 0, ctx->stream>>>(d_in + p0, c, tile_hist);
-        BWTS_TRY(radix_column_scan(ctx, tile_hist, tiles, scan_temp));
-        if (compact) lf_rank_c40_kernel<<<dim3((unsigned)tiles), dim3(LF_THREADS), 0, ctx->stream>>>(d_in + p0, c, tile_hist, dBase, (u8 *)LF40 + 5 * p0);
-        else lf_rank_wide_kernel<<<dim3((unsigned)tiles), dim3(LF_THREADS), 0, ctx->stream>>>(d_in + p0, c, tile_hist, dBase, LF + p0);
-        HIPC(hipGetLastError());
-        HIPC(hipStreamSynchronize(ctx->stream));            // hBase is rewritten by the next segment
-    }
-
-    unsigned long long *ticket = (unsigned long long *)(ctx->d_small + SMI_COUNTERS);
-    HIPC(hipMemsetAsync(ticket, 0, 16 * sizeof(u64), ctx->stream));
-    if (moments) HIPC(hipMemsetAsync(mom, 0, 3 * WMOM_BUCKETS * sizeof(u64), ctx->stream));
-    else HIPC(hipMemsetAsync(marks, 0, mark_bytes, ctx->stream));
-    {
-        SpanGuard sg(ctx, BWTS_K_WALK, n, 10 * n);
-        const u64 walkers = s < 524288 ? s : 524288;
-        constexpr size_t lds = (size_t)WMOM_BUCKETS * (8 + 8 + 4);
-        const unsigned wgs = (unsigned)((walkers + 255) / 256);
-        if (compact && moments) {
-            BWTS_TRY(ensure_dyn_lds(ctx, (const void *)walk_record_c40_kernel<true>, lds));
-            walk_record_c40_kernel<true><<<dim3(wgs), dim3(256), lds, ctx->stream>>>(LF40, (u32 *)marks, s, node_cap, slot, dC, seg, nodes, ticket, ticket + 3,
-                                                                                    ticket + 4, mom_shift, mom);
-        } else if (compact)
-            walk_record_c40_kernel<false><<<dim3(wgs), dim3(256), 0, ctx->stream>>>(LF40, (u32 *)marks, s, node_cap, slot, dC, seg, nodes, ticket, ticket + 3,
-                                                                                   ticket + 4, 0, nullptr);
-        else if (moments) {
-            BWTS_TRY(ensure_dyn_lds(ctx, (const void *)walk_record_wide_kernel<true>, lds));
-            walk_record_wide_kernel<true><<<dim3(wgs), dim3(256), lds, ctx->stream>>>(LF, marks, s, node_cap, slot, dC, seg, nodes, ticket,
-                                                                                     ticket + 3, ticket + 4, mom_shift, mom);
-        } else
-            walk_record_wide_kernel<false><<<dim3(wgs), dim3(256), 0, ctx->stream>>>(LF, marks, s, node_cap, slot, dC, seg, nodes, ticket,
-                                                                                    ticket + 3, ticket + 4, 0, nullptr);
-        HIPC(hipGetLastError());
-    }
-    BWTS_TRY(read_small(ctx, SMI_COUNTERS, 16));
-    if (ctx->h_small[SMI_COUNTERS + 4])          // node pool exhausted (adversarial LF): the compact form's pool cannot be
-        return compact ? BWTS_E_INTERNAL : BWTS_E_NOMEM;
-    const u64 s_all = s + ctx->h_small[SMI_COUNTERS + 3];
-
-    // elements in cycles without a splitter
-    u64 ucap = ctx->unv_hint > (1ull << 20) ? ctx->unv_hint : (1ull << 20);
-    if (ucap > n) ucap = n;
-    u64 *uidx = nullptr, *ulf = nullptr, *end_of_cyc = nullptr;
-    WiCycle *cyc = nullptr;
-    auto lay_out = [&](u64 cap) -> int {
-        char *ub = nullptr;
-        BlockLayout L;
-        L.array(&uidx, cap); L.array(&ulf, cap); L.array(&cyc, node_cap + cap); L.array(&end_of_cyc, node_cap + cap);
-        BWTS_TRY(aux_reserve_slot(ctx, 0, L.bytes(), &ub));
-        L.place(ub);
-        return BWTS_OK;
-    };
-    BWTS_TRY(lay_out(ucap));
-    auto collect = [&]() -> int {
-        SpanGuard sg(ctx, BWTS_K_OTHER, n, n);
-        if (moments) {
-            HIPC(hipMemsetAsync(ticket + 10, 0, 2 * sizeof(u64), ctx->stream));
-            const u64 per_class = (n + WMOM_BUCKETS - 1) >> WMOM_LOG2;
-            const u64 budget = (8ull << 20) > per_class ? (8ull << 20) : per_class;        // elements the search may look at (at least one class)
-            if (compact) moments_solve_c40_kernel<<<dim3(WMOM_BUCKETS / 1024), dim3(1024), 0, ctx->stream>>>(mom, n, mom_shift, LF40, uidx, ulf, ucap, def_list, ticket);
-            else moments_solve_wide_kernel<<<dim3(WMOM_BUCKETS / 1024), dim3(1024), 0, ctx->stream>>>(mom, n, mom_shift, LF, uidx, ulf, ucap, def_list, ticket);
-            moments_budget_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(ticket, per_class, budget);
-            if (compact) moments_chase_c40_kernel<<<dim3(4096), dim3(256), 0, ctx->stream>>>(def_list, ticket, n, mom_shift, LF40, 1u << 16, uidx, ulf, ucap, ticket);
-            else moments_chase_wide_kernel<<<dim3(4096), dim3(256), 0, ctx->stream>>>(def_list, ticket, n, mom_shift, LF, 1u << 16, uidx, ulf, ucap, ticket);
-        } else {
-            u64 blocks = (n + 255) / 256; if (blocks > 16384) blocks = 16384;
-            if (compact) collect_unvisited_c40_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(LF40, (const u32 *)marks, n, uidx, ulf, ucap, ticket + 1);
-            else collect_unvisited_wide_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(LF, marks, n, uidx, ulf, ucap, ticket + 1);
-        }
-        HIPC(hipGetLastError());
-        return BWTS_OK;
-    };
-    BWTS_TRY(collect());
-    // how many were found, and a second collection into room for all of them, before the ranking tables below are written: the
-    // compact form's mark bits lie over those tables
-    BWTS_TRY(read_small(ctx, SMI_COUNTERS, 16));
-    if (moments && ctx->h_small[SMI_COUNTERS + 11]) { *need_marks = true; return BWTS_OK; }     // too many unreached elements for the moments: the byte map
-    const u64 nu = ctx->h_small[SMI_COUNTERS + 1];
-    if (nu > n) return BWTS_E_INTERNAL;
-    if (nu > ucap) {
-        ucap = nu;
-        BWTS_TRY(lay_out(ucap));
-        HIPC(hipMemsetAsync(ticket + 1, 0, sizeof(u64), ctx->stream));
-        BWTS_TRY(collect());
-        BWTS_TRY(read_small(ctx, SMI_COUNTERS, 16));
-        if (ctx->h_small[SMI_COUNTERS + 1] != nu) return BWTS_E_INTERNAL;
-    }
-    // pointer jumping over the nodes
-    const int R = [&] { int b = 0; for (u64 x = s_all; x; x >>= 1) b++; return b; }();
-    int cur = 0, sc = 0;
-    {
-        SpanGuard sg(ctx, BWTS_K_LISTRANK, s_all, 0);
-        const int gb = grid1(s_all);
-        wi_init_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(s_all, nodes, wmin[0]);
-        for (int r = 0; r < R; r++, cur ^= 1) wi_jump_min_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(s_all, wmin[cur], wmin[cur ^ 1]);
-        wi_cut_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(s_all, nodes, wmin[cur], wsum[0]);
-        for (int r = 0; r < R; r++, sc ^= 1) wi_jump_sum_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(s_all, wsum[sc], wsum[sc ^ 1]);
-        wi_finish_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(s_all, wmin[cur], wsum[sc], nodes, dist, min_dist, ncyc, ticket + 2);
-        HIPC(hipGetLastError());
-    }
-    BWTS_TRY(read_small(ctx, SMI_COUNTERS, 16));
-    const u64 kc = ctx->h_small[SMI_COUNTERS + 2];
-    ctx->tm.unvisited = nu;
-    ctx->unv_hint = (size_t)nu;
-    if (kc == 0 || kc > s_all) return BWTS_E_INTERNAL;
-    if (nu) {
-        SpanGuard sg(ctx, BWTS_K_OTHER, nu, 16 * nu);
-        u64 cap = (1ull << 36) / nu;
-        if (cap > 64 * G) cap = 64 * G;
-        if (cap < 4 * G) cap = 4 * G;
-        if (compact) tiny_cycle_scan_c40_kernel<<<dim3(grid1(nu)), dim3(256), 0, ctx->stream>>>(uidx, ulf, nu, LF40, (u32)cap, cyc, ticket + 7, ticket + 4);
-        else tiny_cycle_scan_wide_kernel<<<dim3(grid1(nu)), dim3(256), 0, ctx->stream>>>(uidx, ulf, nu, LF, (u32)cap, cyc, ticket + 7, ticket + 4);
-        HIPC(hipGetLastError());
-    }
-    BWTS_TRY(read_small(ctx, SMI_COUNTERS, 16));
-    u64 kt = ctx->h_small[SMI_COUNTERS + 7];
-    if (kt > nu) return BWTS_E_INTERNAL;
-    // a cycle without a splitter too long for one lane: all unreached elements are ranked as nodes of one symbol instead
-    const bool unit_rank = ctx->h_small[SMI_COUNTERS + 4] != 0;
-    ScopedDeviceBlock ub(ctx);
-    WiMin *umin[2] = {nullptr, nullptr};
-    WiSum *usum[2] = {nullptr, nullptr};
-    u64 *udist = nullptr, *umind = nullptr, *uend = nullptr;
-    int ucur = 0, usc = 0;
-    if (unit_rank) {
-        SpanGuard sg(ctx, BWTS_K_LISTRANK, nu, 0);
-        if (nu >= 0x7ffffff0ull) return BWTS_E_NOMEM;
-        const size_t a24 = align_up(nu * sizeof(WiNode), 256), a16 = align_up(nu * 16, 256), a8 = align_up(nu * 8, 256);
-        BWTS_TRY(ub.take(a24 + 4 * a16 + 3 * a8));
-        WiNode *unodes = (WiNode *)ub.p;
-        umin[0] = (WiMin *)(ub.p + a24); umin[1] = (WiMin *)(ub.p + a24 + a16);
-        usum[0] = (WiSum *)(ub.p + a24 + 2 * a16); usum[1] = (WiSum *)(ub.p + a24 + 3 * a16);
-        udist = (u64 *)(ub.p + a24 + 4 * a16); umind = udist + a8 / 8; uend = umind + a8 / 8;
-        const int gb = grid1(nu);
-        const int R2 = [&] { int b = 0; for (u64 x = nu; x; x >>= 1) b++; return b; }();
-        HIPC(hipMemsetAsync(ticket + 9, 0, sizeof(u64), ctx->stream));
-        if (compact) {
-            wi_unit_index_c40_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(uidx, nu, LF40);
-            wi_unit_nodes_c40_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(uidx, ulf, nu, LF40, unodes);
-        } else {
-            wi_unit_index_kernel<u64><<<dim3(gb), dim3(256), 0, ctx->stream>>>(uidx, nu, LF);
-            wi_unit_nodes_kernel<u64><<<dim3(gb), dim3(256), 0, ctx->stream>>>(uidx, ulf, nu, LF, unodes);
-        }
-        wi_init_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(nu, unodes, umin[0]);
-        for (int r = 0; r < R2; r++, ucur ^= 1) wi_jump_min_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(nu, umin[ucur], umin[ucur ^ 1]);
-        wi_cut_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(nu, unodes, umin[ucur], usum[0]);
-        for (int r = 0; r < R2; r++, usc ^= 1) wi_jump_sum_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(nu, usum[usc], usum[usc ^ 1]);
-        wi_finish_kernel<<<dim3(gb), dim3(256), 0, ctx->stream>>>(nu, umin[ucur], usum[usc], unodes, udist, umind, cyc, ticket + 9);
-        HIPC(hipGetLastError());
-        BWTS_TRY(read_small(ctx, SMI_COUNTERS + 9, 1));
-        kt = ctx->h_small[SMI_COUNTERS + 9];          // these cycles take the place of the one-lane scan's
-        if (kt == 0 || kt > nu) return BWTS_E_INTERNAL;
-        wi_unit_tag_kernel<<<dim3(grid1(kt)), dim3(256), 0, ctx->stream>>>(cyc, kt);
-        HIPC(hipGetLastError());
-    }
-    const u64 kall = kc + kt;
-    ctx->tm.factors = kall;
-    {
-        SpanGuard sg(ctx, BWTS_K_LISTRANK, kall, 0);
-        HIPC(hipMemcpyAsync(cyc + kt, ncyc, kc * sizeof(WiCycle), hipMemcpyDeviceToDevice, ctx->stream));
-        SortPlan cp;
-        BWTS_TRY(cycle_sort_plan(ctx, kall, &cp));
-        wi_cycle_keys_kernel<<<dim3(grid1(kall)), dim3(256), 0, ctx->stream>>>(cyc, kall, cp.keys[0], cp.vals[0]);
-        int res = 0, kbits = 0;
-        for (u64 x = n - 1; x; x >>= 1) kbits++;
-        BWTS_TRY(radix_sort_pairs(ctx, cp, kall, kbits < 1 ? 1 : kbits, &res));
-        WiLenIn lin{cyc, cp.vals[res]};
-        WiEndOut lout{cyc, cp.vals[res], kall, n - 1, end_by_leader, end_of_cyc, ctx->d_small + SMI_COUNTERS + 13, uend};
-        BWTS_TRY((device_scan<false, u64>(ctx, kall, lin, lout, OpAdd(), (u64)0, cp.scan_temp)));
-        wi_place_kernel<<<dim3(grid1(s_all)), dim3(256), 0, ctx->stream>>>(s_all, wmin[cur], wsum[sc], dist, min_dist, end_by_leader, opos, wrap_at, cyc_len);
-        HIPC(hipGetLastError());
-    }
-    {
-        SpanGuard sg(ctx, BWTS_K_WALK_EMIT, n, 2 * n);
-        // threads per node: 16 (the full form's records loop over 4 G); in the compact form one per 16 bytes of a slot, at most 64
-        int tpn_log2 = WI_G_LOG2 - 4;
-        if (compact) { tpn_log2 = 2; while (tpn_log2 < 6 && (16u << (tpn_log2 + 1)) <= slot) tpn_log2++; }
-        const u64 threads = s_all << tpn_log2;
-        place_segments_wide_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream>>>(seg, s_all, slot, tpn_log2, nodes, opos, wrap_at, cyc_len,
-                                                                                                           d_out);
-        if (unit_rank)
-            wi_unit_place_kernel<u64><<<dim3(grid1(nu)), dim3(256), 0, ctx->stream>>>(nu, umin[ucur], usum[usc], udist, umind, uend, ulf, dC, d_out);
-        else if (kt && compact) tiny_place_c40_kernel<<<dim3(grid1(kt)), dim3(256), 0, ctx->stream>>>(cyc, kt, end_of_cyc, LF40, dC, d_out);
-        else if (kt) tiny_place_wide_kernel<<<dim3(grid1(kt)), dim3(256), 0, ctx->stream>>>(cyc, kt, end_of_cyc, LF, dC, d_out);
-        HIPC(hipGetLastError());
-    }
-    BWTS_TRY(read_small(ctx, SMI_COUNTERS + 13, 1));
-    if (ctx->h_small[SMI_COUNTERS + 13] != n) return BWTS_E_INTERNAL;
-    return BWTS_OK;
 }

@@ -43,8 +43,14 @@ EXPORTS = [
 TEST_EXPORTS = [
     "bwts_generate_device", "bwts_device_alloc", "bwts_device_free", "bwts_copy_to_device", "bwts_copy_to_host",
     "bwts_device_equal", "bwts_debug_sort_pairs", "bwts_debug_suffix_array", "bwts_debug_lyndon",
-    "bwts_debug_chunk_plan", "bwts_debug_inverse_arena",
+    "bwts_debug_chunk_plan", "bwts_debug_inverse_arena", "bwts_debug_inverse_report",
 ]
+# bwts_debug_inverse_report: the words of one attempt's record, and what marks, outcomes and forms are called
+INV_REPORT_FIELDS = ["g", "mark", "outcome", "s", "virtual", "node_cap", "nu", "nu2", "ucap_first", "second_collect",
+                     "listed_classes", "mom_fallback", "unit_rank", "kc", "kt", "form"]
+INV_MARKS = {0: "log", 1: "sentinel", 2: "bytemap", 3: "moments"}
+INV_OUTCOMES = {0: "DONE", 1: "RETRY_DENSE", 2: "AMBIGUOUS", 3: "NEED_LOG", 255: "ERROR"}
+INV_FORMS = {0: "narrow", 1: "wide", 2: "wide_compact"}
 
 
 class BwtsError(RuntimeError):
@@ -127,6 +133,7 @@ def lib():
         L.bwts_debug_lyndon.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
         L.bwts_debug_chunk_plan.argtypes = [u64, u64, ctypes.POINTER(u64)]
         L.bwts_debug_inverse_arena.argtypes = [u64, i32, i32, ctypes.POINTER(u64)]
+        L.bwts_debug_inverse_report.argtypes = [vp, ctypes.POINTER(u64), u64, ctypes.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -347,6 +354,25 @@ class Context:
         cnt = ctypes.c_uint64(0)
         self._check(lib().bwts_debug_lyndon(self._h, a.ctypes.data, a.size, st.ctypes.data, st.size, ctypes.byref(cnt)))
         return st[: cnt.value].copy()
+
+    def debug_inverse_report(self):
+        """One dict per attempt of the most recent inverse call on this context (INV_REPORT_FIELDS; mark, outcome and form by name,
+        the three flags as bool), oldest first."""
+        words = len(INV_REPORT_FIELDS)
+        buf = (ctypes.c_uint64 * (8 * words))()
+        made = ctypes.c_uint64(0)
+        got = lib().bwts_debug_inverse_report(self._h, buf, len(buf), ctypes.byref(made))
+        if got < 0:
+            self._check(got)
+        assert got == made.value, "more attempts than records: %d" % made.value
+        out = []
+        for a in range(got):
+            d = {f: int(buf[a * words + i]) for i, f in enumerate(INV_REPORT_FIELDS)}
+            d["mark"], d["outcome"], d["form"] = INV_MARKS[d["mark"]], INV_OUTCOMES[d["outcome"]], INV_FORMS[d["form"]]
+            for f in ("second_collect", "unit_rank"):
+                d[f] = bool(d[f])
+            out.append(d)
+        return out
 
 
 def _ptr(x):

@@ -1183,6 +1183,17 @@ extern "C" int bwts_debug_inverse_arena(uint64_t n, int g, int mark, uint64_t ou
     return g;
 }
 
+// what the attempts of the most recent inverse call on this context did: no device, the records are host memory
+extern "C" int bwts_debug_inverse_report(bwts_ctx *ctx, uint64_t *out, uint64_t cap_words, uint64_t *attempts)
+{
+    if (!ctx || !attempts || (!out && cap_words)) return BWTS_E_ARG;
+    *attempts = ctx->inv_attempts_made;
+    int copied = 0;
+    for (u32 a = 0; a < ctx->inv_attempts_made && a < INV_REPORT_MAX && (u64)(a + 1) * INV_REPORT_WORDS <= cap_words; a++, copied++)
+        memcpy(out + (size_t)a * INV_REPORT_WORDS, ctx->inv_report[a], INV_REPORT_WORDS * sizeof(u64));
+    return copied;
+}
+
 extern "C" int bwts_debug_suffix_array(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint32_t *h_sa)
 {
     if (!ctx || !in || !h_sa || n == 0) return BWTS_E_ARG;

@@ -51,6 +51,8 @@ struct CopyPool {
     void part(int i);
 };
 
+#define INV_REPORT_MAX 8         // (the narrow inverse's fallback chain has at most five attempts, the wide one four)
+#define INV_REPORT_WORDS 16
 #define STAGE_SLOTS 4
 #define BWTS_AUX_SLOTS 5
 
@@ -80,6 +82,10 @@ struct bwts_ctx {
     char  *aux[BWTS_AUX_SLOTS];
     size_t aux_cap[BWTS_AUX_SLOTS];
     size_t unv_hint;       // inverse: unreached elements seen by the previous call (sizes the first collection pass)
+    // inverse: one record per attempt of the most recent call, from values its stages hold on the host anyway (a few stores per
+    // attempt); bwts_debug_inverse_report is the only reader and include/bwts_test.h names the words
+    u64 inv_report[INV_REPORT_MAX][INV_REPORT_WORDS];
+    u32 inv_attempts_made = 0;          // attempts of that call (the records of those past INV_REPORT_MAX are dropped)
     // tied list of the forward transform beyond 2^32 positions (wide_path.h): blocks of 2^tied_blk_lg (position, head) pairs, taken as the
     // list grows and kept for the next call
     std::vector<char *> tied_blk;

@@ -969,6 +969,27 @@ template <typename RUN> static int arena_place(bwts_ctx *ctx, RUN &r)
     return BWTS_OK;
 }
 
+enum InvOutcome { INV_DONE,
+    INV_RETRY_DENSE,    // the node pool overflowed (adversarial LF), or too many unreached elements for the unit-node ranking: g = 0
+    INV_AMBIGUOUS,      // sentinel marks at n = 2^32: the one entry equal to LF_VISITED sat in a cycle without a splitter
+    INV_NEED_LOG        // the moments do not name the unreached elements: the index log does
+};
+// The record of one attempt (ctx->inv_report, read by bwts_debug_inverse_report; include/bwts_test.h names the words): values the stages
+// hold on the host anyway, stored as they become known.  An attempt that ends with an error code keeps IR_ERROR as its outcome.
+enum InvReportWord { IR_G, IR_MARK, IR_OUTCOME, IR_S, IR_VIRTUAL, IR_NODE_CAP, IR_NU, IR_NU2, IR_UCAP_FIRST, IR_SECOND_COLLECT,
+                     IR_LISTED, IR_MOM_FALLBACK, IR_UNIT_RANK, IR_KC, IR_KT, IR_FORM };
+enum InvReportForm { IR_FORM_NARROW, IR_FORM_WIDE, IR_FORM_WIDE_COMPACT };
+#define IR_ERROR 255
+static_assert(IR_FORM < INV_REPORT_WORDS, "the record's words");
+static u64 *inv_report_open(bwts_ctx *ctx /* null: sizes only */, u64 *spill)
+{
+    u64 *w = ctx && ctx->inv_attempts_made < INV_REPORT_MAX ? ctx->inv_report[ctx->inv_attempts_made] : spill;
+    if (ctx) ctx->inv_attempts_made++;
+    memset(w, 0, INV_REPORT_WORDS * sizeof(u64));
+    w[IR_OUTCOME] = IR_ERROR;
+    return w;
+}
+
 #include "wide_inverse.h"         // the 64-bit form; its node ranking (WiRanking, UnitRank) also serves the unit-node route below
 
 // wi_finish_kernel for the main path: the cycles of the unit-node ranking go straight into the record form of the cycles
@@ -1033,6 +1054,7 @@ struct InvRun {
     int cur = 0, sc = 0;                                        // which side of lrmin[] / lrsum[] holds the ranking
     bool unit_rank = false;                                     // the unit-node route: its block, taken from the device for the call
     UnitRank unit; u32 *uend = nullptr, *uleader = nullptr; ScopedDeviceBlock ub;
+    u64 rep_spill[INV_REPORT_WORDS], *rep;                      // this attempt's record
     InvRun(bwts_ctx *ctx /* null: sizes only */, u64 n_, int g_, int mark_) : n(n_), g(g_), mark(mark_), ub(ctx)
     {
         u64 walker_cap = 524288;                                // lanes of the walk
@@ -1046,6 +1068,8 @@ struct InvRun {
         wblocks = (unsigned)(((s < walker_cap ? s : walker_cap) + 255) / 256);
         log_chunks = n / (IDX_CHUNK - 64) + (u64)wblocks * 4 + 2;     // a closed chunk wastes < 64 entries; every wave may leave one open
         nbuckets = (u32)((n + (1ull << IDX_RANGE_LOG2) - 1) >> IDX_RANGE_LOG2);
+        rep = inv_report_open(ctx, rep_spill);
+        rep[IR_G] = (u64)g; rep[IR_MARK] = (u64)mark; rep[IR_S] = s; rep[IR_NODE_CAP] = node_cap; rep[IR_FORM] = IR_FORM_NARROW;
     }
     void declare(BlockLayout &L)            // the mark-specific buffers only for the mark that runs
     {
@@ -1055,11 +1079,6 @@ struct InvRun {
         if (mark == MARK_LOG) lg.declare(L, log_chunks, nbuckets);
         nd.declare(L, node_cap, slot); l2.declare(L, l2cap); L.pad(INV_ARENA_SLACK);
     }
-};
-enum InvOutcome { INV_DONE,
-    INV_RETRY_DENSE,    // the node pool overflowed (adversarial LF), or too many unreached elements for the unit-node ranking: g = 0
-    INV_AMBIGUOUS,      // sentinel marks at n = 2^32: the one entry equal to LF_VISITED sat in a cycle without a splitter
-    INV_NEED_LOG        // the moments do not name the unreached elements: the index log does
 };
 // bytes the narrow attempt (n, g, mark) reserves: no context, no device (bwts_debug_inverse_arena asks too)
 size_t inverse_attempt_bytes(u64 n, int g, int mark) { InvRun r(nullptr, n, g, mark); BlockLayout L; r.declare(L); return L.bytes(); }
@@ -1102,6 +1121,7 @@ static int inv_walk(bwts_ctx *ctx, InvRun &r, InvOutcome *out)
         BWTS_TRY(launch[r.mark](ctx, r));
     }
     BWTS_TRY(read_small(ctx, SMI_COUNTERS, IC_WORDS));
+    r.rep[IR_VIRTUAL] = inv_count(ctx, IC_VIRTUAL);
     if (inv_count(ctx, IC_OVERFLOW)) { *out = INV_RETRY_DENSE; return BWTS_OK; }   // node pool exhausted (adversarial LF): plain pointer jumping
     r.s_all = r.s + inv_count(ctx, IC_VIRTUAL); r.s2 = (r.s_all + L2_H - 1) / L2_H;
     return BWTS_OK;
@@ -1144,6 +1164,7 @@ static int inv_find_unreached(bwts_ctx *ctx, InvRun &r, InvOutcome *out)
     const size_t ucap = ctx->unv_hint > UNV_CAP0 ? ctx->unv_hint : UNV_CAP0;
     BWTS_TRY(lay_out_unreached(ctx, r, ucap > r.n ? (size_t)r.n : ucap, 0, &r.tiny, &r.end_of_tiny));
     BWTS_TRY(inv_collect(ctx, r, true));
+    r.rep[IR_UCAP_FIRST] = r.ucap;
     {
         SpanGuard sg(ctx, BWTS_K_LISTRANK, r.s_all, 32 * r.s_all);
         HIPC(hipMemsetAsync(r.nd.visited2, 0, r.s_all, ctx->stream));
@@ -1153,6 +1174,7 @@ static int inv_find_unreached(bwts_ctx *ctx, InvRun &r, InvOutcome *out)
     }
     BWTS_TRY(read_small(ctx, SMI_COUNTERS, IC_WORDS));
     r.nu = inv_count(ctx, IC_UNREACHED); r.nu2 = inv_count(ctx, IC_UNREACHED_NODES);
+    r.rep[IR_NU] = r.nu; r.rep[IR_NU2] = r.nu2; r.rep[IR_LISTED] = inv_count(ctx, IC_LISTED_CLASSES); r.rep[IR_MOM_FALLBACK] = inv_count(ctx, IC_MOM_FALLBACK);
     const bool inv_trace = [ctx] { const char *e = bwts_knob(ctx, "BWTS_INV_TRACE"); return e && atoi(e) == 1; }();
     if (inv_trace && r.mark == MARK_MOMENTS)
         fprintf(stderr, "[inverse] moments: shift %d, unreached found %llu, ranges searched %llu, fallback flag %llu\n", r.mom_shift, (unsigned long long)r.nu,
@@ -1165,6 +1187,7 @@ static int inv_find_unreached(bwts_ctx *ctx, InvRun &r, InvOutcome *out)
         BWTS_TRY(lay_out_unreached(ctx, r, r.nu, 0, &r.tiny, &r.end_of_tiny));
         HIPC(hipMemsetAsync(inv_counter(ctx, IC_UNREACHED), 0, sizeof(u64), ctx->stream));
         BWTS_TRY(inv_collect(ctx, r, false));
+        r.rep[IR_SECOND_COLLECT] = 1;
     }
     r.s2all = r.s2 + r.nu2;
     return BWTS_OK;
@@ -1194,8 +1217,10 @@ static int inv_free_cycles(bwts_ctx *ctx, InvRun &r, InvOutcome *out)
     }
     BWTS_TRY(read_small(ctx, SMI_COUNTERS, IC_WORDS));
     r.kc = inv_count(ctx, IC_LIST_CYCLES); r.kt = inv_count(ctx, IC_FREE_CYCLES);
+    r.rep[IR_KC] = r.kc; r.rep[IR_KT] = r.kt;
     if (r.kc == 0 || r.kc > r.s2all || r.kt > r.nu) return BWTS_E_INTERNAL;
     r.unit_rank = inv_count(ctx, IC_OVERFLOW) != 0;
+    r.rep[IR_UNIT_RANK] = r.unit_rank;
     if (!r.unit_rank) return BWTS_OK;
     // A cycle without a splitter too long for one lane (sorted or periodic data: 1^b 0^c with n = 2^k, c = 2 * odd has a cycle of
     // n / 2 odd elements): every unreached element becomes a node of one symbol and the pointer-jumping kernels of the 64-bit
@@ -1215,6 +1240,7 @@ static int inv_free_cycles(bwts_ctx *ctx, InvRun &r, InvOutcome *out)
     HIPC(hipGetLastError());
     BWTS_TRY(read_small(ctx, SMI_COUNTERS + IC_UNIT_CYCLES, 1));
     r.kt = inv_count(ctx, IC_UNIT_CYCLES);              // these cycles take the place of the one-lane scan's
+    r.rep[IR_KT] = r.kt;
     return r.kt == 0 || r.kt > r.nu ? BWTS_E_INTERNAL : BWTS_OK;
 }
 // order the cycles by smallest element on the device: sort (minelem, record), prefix sums of the lengths; then every node's place
@@ -1259,10 +1285,8 @@ static int inv_place(bwts_ctx *ctx, InvRun &r, u8 *d_out, InvOutcome *out)
     return BWTS_E_INTERNAL;
 }
 // One attempt with splitter spacing 2^g: the stages in order; one that sets *out to anything but INV_DONE ends the attempt there.
-static int inverse_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, int g, int mark, InvOutcome *out)
+static int inverse_stages(bwts_ctx *ctx, InvRun &r, const u8 *d_in, u8 *d_out, InvOutcome *out)
 {
-    InvRun r(ctx, n, g, mark);
-    *out = INV_DONE;
     BWTS_TRY(arena_place(ctx, r));
     BWTS_TRY(inv_build_lf(ctx, r, d_in));
     BWTS_TRY(inv_walk(ctx, r, out));
@@ -1275,12 +1299,21 @@ static int inverse_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, int 
     BWTS_TRY(inv_order_cycles(ctx, r));
     return inv_place(ctx, r, d_out, out);
 }
+static int inverse_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, int g, int mark, InvOutcome *out)
+{
+    InvRun r(ctx, n, g, mark);
+    *out = INV_DONE;
+    BWTS_TRY(inverse_stages(ctx, r, d_in, d_out, out));
+    r.rep[IR_OUTCOME] = (u64)*out;
+    return BWTS_OK;
+}
 
 int inverse_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
 {
     // beyond 32-bit indices: the 64-bit form (wide_inverse.h); BWTS_FORCE_WIDE sends every input there (tests)
     const int force_wide = [ctx] { const char *e = bwts_knob(ctx, "BWTS_FORCE_WIDE"); return e ? atoi(e) : 0; }();
     ctx->tm.attempts = 1;
+    ctx->inv_attempts_made = 0;
     if (n > 0x80000000ull) {
         // one byte value only: LF is the identity, n cycles of one element, the text is the input (unbwts.c:66-86 walks each of them
         // in one step).  The general route holds ~110 bytes per element of cycles that meet no splitter -- all of them here --, which

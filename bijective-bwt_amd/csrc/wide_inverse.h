@@ -423,6 +423,7 @@ struct WideRun {
     u64 ucap = 0, *uidx = nullptr, *ulf = nullptr, *end_of_cyc = nullptr; WiCycle *cyc = nullptr;      // side block 0: the unreached elements; all cycles and their ends
     u64 s_all = 0, nu = 0, kc = 0, kt = 0; bool unit_rank = false;     // ... the unit-node route: its block, taken from the device for the call
     UnitRank unit; u64 *uend = nullptr; ScopedDeviceBlock ub;
+    u64 rep_spill[INV_REPORT_WORDS], *rep;              // this attempt's record (the fields the wide form has)
     WideRun(bwts_ctx *ctx, u64 n_, bool moments_, bool compact_) : n(n_), moments(moments_), compact(compact_), ub(ctx)
     {
         G = 1ull << (compact ? WC_G_LOG2 : WI_G_LOG2); s = (n + G - 1) / G;
@@ -439,6 +440,8 @@ struct WideRun {
         // (a second one where the first ran out of room) reads them before the ranking writes those tables: the fallback needs no more
         // memory than the moments
         mark_bytes = compact ? (n + 31) / 32 * 4 : n;
+        rep = inv_report_open(ctx, rep_spill);
+        rep[IR_G] = compact ? WC_G_LOG2 : WI_G_LOG2; rep[IR_MARK] = moments ? MARK_MOMENTS : MARK_BYTEMAP; rep[IR_S] = s; rep[IR_NODE_CAP] = node_cap; rep[IR_FORM] = compact ? IR_FORM_WIDE_COMPACT : IR_FORM_WIDE;
     }
     void declare(BlockLayout &L)
     {
@@ -519,6 +522,7 @@ static int wide_walk(bwts_ctx *ctx, WideRun &r)
         else BWTS_TRY(launch_wide_walk(ctx, r, walk_record_wide_kernel<false>, r.LF, r.marks));
     }
     BWTS_TRY(read_small(ctx, SMI_COUNTERS, IC_WORDS));
+    r.rep[IR_VIRTUAL] = inv_count(ctx, IC_VIRTUAL);
     if (inv_count(ctx, IC_OVERFLOW)) return r.compact ? BWTS_E_INTERNAL : BWTS_E_NOMEM;     // node pool exhausted (adversarial LF): the compact form's pool cannot be
     r.s_all = r.s + inv_count(ctx, IC_VIRTUAL);
     return BWTS_OK;
@@ -551,6 +555,8 @@ static int wide_collect_unreached(bwts_ctx *ctx, WideRun &r, bool *need_marks)
     BWTS_TRY(lay_out_unreached(ctx, r, ucap > r.n ? r.n : ucap, r.node_cap, &r.cyc, &r.end_of_cyc));
     BWTS_TRY(wide_collect(ctx, r));
     BWTS_TRY(read_small(ctx, SMI_COUNTERS, IC_WORDS));
+    r.rep[IR_UCAP_FIRST] = r.ucap; r.rep[IR_NU] = inv_count(ctx, IC_UNREACHED);
+    r.rep[IR_LISTED] = inv_count(ctx, IC_LISTED_CLASSES); r.rep[IR_MOM_FALLBACK] = inv_count(ctx, IC_MOM_FALLBACK);
     if (r.moments && inv_count(ctx, IC_MOM_FALLBACK)) { *need_marks = true; return BWTS_OK; }     // too many unreached elements for the moments: the byte map
     r.nu = inv_count(ctx, IC_UNREACHED);
     if (r.nu > r.n) return BWTS_E_INTERNAL;
@@ -560,6 +566,7 @@ static int wide_collect_unreached(bwts_ctx *ctx, WideRun &r, bool *need_marks)
         BWTS_TRY(wide_collect(ctx, r));
         BWTS_TRY(read_small(ctx, SMI_COUNTERS, IC_WORDS));
         if (inv_count(ctx, IC_UNREACHED) != r.nu) return BWTS_E_INTERNAL;
+        r.rep[IR_SECOND_COLLECT] = 1;
     }
     return BWTS_OK;
 }
@@ -575,6 +582,7 @@ static int wide_rank_node_list(bwts_ctx *ctx, WideRun &r)
     }
     BWTS_TRY(read_small(ctx, SMI_COUNTERS, IC_WORDS));
     r.kc = inv_count(ctx, IC_LIST_CYCLES);
+    r.rep[IR_KC] = r.kc;
     ctx->tm.unvisited = r.nu; ctx->unv_hint = (size_t)r.nu;
     return r.kc == 0 || r.kc > r.s_all ? BWTS_E_INTERNAL : BWTS_OK;
 }
@@ -593,6 +601,7 @@ static int wide_free_cycles(bwts_ctx *ctx, WideRun &r)
     r.kt = inv_count(ctx, IC_FREE_CYCLES);
     if (r.kt > r.nu) return BWTS_E_INTERNAL;
     r.unit_rank = inv_count(ctx, IC_OVERFLOW) != 0;
+    r.rep[IR_UNIT_RANK] = r.unit_rank; r.rep[IR_KT] = r.kt;
     if (!r.unit_rank) return BWTS_OK;
     // a cycle without a splitter too long for one lane: all unreached elements are ranked as nodes of one symbol instead
     SpanGuard sg(ctx, BWTS_K_LISTRANK, r.nu, 0);
@@ -615,6 +624,7 @@ static int wide_free_cycles(bwts_ctx *ctx, WideRun &r)
     HIPC(hipGetLastError());
     BWTS_TRY(read_small(ctx, SMI_COUNTERS + IC_UNIT_CYCLES, 1));
     r.kt = inv_count(ctx, IC_UNIT_CYCLES);          // these cycles take the place of the one-lane scan's
+    r.rep[IR_KT] = r.kt;
     if (r.kt == 0 || r.kt > r.nu) return BWTS_E_INTERNAL;
     wi_unit_tag_kernel<<<dim3(grid1(r.kt)), dim3(256), 0, ctx->stream>>>(r.cyc, r.kt);
     return launched(ctx);
@@ -668,11 +678,13 @@ static int inverse_wide_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out,
     BWTS_TRY(wide_build_lf(ctx, r, d_in));
     BWTS_TRY(wide_walk(ctx, r));
     BWTS_TRY(wide_collect_unreached(ctx, r, need_marks));
-    if (*need_marks) return BWTS_OK;
+    if (*need_marks) { r.rep[IR_OUTCOME] = INV_NEED_LOG; return BWTS_OK; }       // the moments gave up: in this form the marks come next (bwts_test.h says so for outcome 3)
     BWTS_TRY(wide_rank_node_list(ctx, r));
     BWTS_TRY(wide_free_cycles(ctx, r));
     BWTS_TRY(wide_order_cycles(ctx, r));
-    return wide_place(ctx, r, d_out);
+    BWTS_TRY(wide_place(ctx, r, d_out));
+    r.rep[IR_OUTCOME] = INV_DONE;
+    return BWTS_OK;
 }
 static int inverse_wide_form(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool compact)
 {

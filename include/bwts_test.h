@@ -37,6 +37,19 @@ int bwts_debug_chunk_plan(uint64_t a0, uint64_t a_chunks, uint64_t out[4]);
  * splitter spacing 2^g (g < 0: the spacing the engine picks for n) and mark 0 index log, 1 sentinel, 2 byte map, 3 moments (the
  * default) reserves; out[1] = bytes the host path allocates before the transform runs.  Returns the g used, -1 on a bad argument. */
 int bwts_debug_inverse_arena(uint64_t n, int g, int mark, uint64_t out[2]);
+/* What the most recent inverse call on the context did, one record of 16 words per attempt of its fallback chain, oldest first
+ * (no device work: the engine keeps the records on the host as it goes).  Word 0 g: log2 of the splitter spacing; 1 mark: 0 index
+ * log, 1 sentinel, 2 byte map, 3 moments; 2 outcome: 0 done, 1 retry with every element a splitter (node pool overflow, or the unit
+ * nodes refused), 2 ambiguous sentinel (n = 2^32), 3 the moments do not name the unreached elements (next: the index log; wide form:
+ * the marks), 255 the attempt ended with an error code; 3 s: splitters; 4 virtual nodes handed out by the walk (s_all - s; counted
+ * past the pool's end when it overflows); 5 node_cap; 6 nu: elements no walk reached; 7 nu2: nodes no level-2 walk reached;
+ * 8 room for unreached elements at the first collection; 9 a second collection ran; 10 moments: classes listed for the search, as
+ * read back after the first collection; 11 moments: the fallback flag, likewise; 12 the unit-node route ranked the cycles without a
+ * splitter; 13 kc: cycles of the node list; 14 kt: cycles without a splitter; 15 form: 0 narrow, 1 wide, 2 wide compact.  A stage
+ * that did not run leaves its words 0; the wide form has no level 2 (word 7 stays 0).
+ * out receives whole records while they fit into cap_words; *attempts = attempts the call made (records exist for the first 8; 0
+ * after the constant-input shortcut beyond 2^31, and before any call).  Returns the number of records written, < 0 on a bad argument. */
+int bwts_debug_inverse_report(bwts_ctx *ctx, uint64_t *out, uint64_t cap_words, uint64_t *attempts);
 
 #ifdef __cplusplus
 }

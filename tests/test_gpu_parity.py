@@ -138,13 +138,22 @@ def test_large_reference_unbwts_hashes(ctx, rec):
     assert np.array_equal(ctx.forward(x), y)
 
 
-def test_inverse_attempts_reported(ctx):
+def test_inverse_attempts_reported(ctx, pkg):
     """bwts_timings.attempts: the cycle walk runs once on natural inputs; a constant input (every element its own LF cycle, nearly all
-    of them unreached by any splitter walk) needs the index log: two attempts."""
+    of them unreached by any splitter walk) needs the index log: two attempts.  On a fresh context (no room for unreached elements
+    remembered from an earlier call) the chain is exactly that, by the engine's own report."""
     x = O.generate("zipf", 3 << 20, 5)
     assert np.array_equal(ctx.inverse(x), O.inverse(x)) and ctx.timings().attempts == 1
     z = np.full(6 << 20, 7, dtype=np.uint8)
     assert np.array_equal(ctx.inverse(z), z) and 1 <= ctx.timings().attempts <= 5
+    with pkg.Context(0) as fresh:
+        assert np.array_equal(fresh.inverse(x), O.inverse(x))
+        assert [(a["g"], a["mark"], a["outcome"]) for a in fresh.debug_inverse_report()] == [(4, "moments", "DONE")]
+    with pkg.Context(0) as fresh:
+        assert np.array_equal(fresh.inverse(z), z) and fresh.timings().attempts == 2
+        rep = fresh.debug_inverse_report()
+        assert [(a["g"], a["mark"], a["outcome"]) for a in rep] == [(4, "moments", "NEED_LOG"), (4, "log", "DONE")]
+        assert rep[1]["nu"] == z.size - z.size // 16 and rep[1]["second_collect"]
 
 
 @pytest.mark.parametrize("kind,n,seed", [("zipf", 4 << 20, 11), ("dna", 3000017, 12), ("uniform256", (2 << 20) + 5, 13)])
@@ -1198,10 +1207,19 @@ _ALT_ENVS = [
 _alt_pool = {}
 
 
+# the inverse's own inputs (Theta(n) tiny cycles, hundreds of unreached elements in short cycles, long cycles without a splitter,
+# constant and sorted inputs) for the children that change how the inverse marks what it visited.  (Not for BWTS_SPLIT_LOG2=0:
+# with every element a splitter nothing is unreached, which those tests assert otherwise; tests/test_inverse_paths.py runs
+# their input families at g = 0.)
+_ALT_INVERSE_TESTS = " or inverse_many_tiny_cycles or inverse_unreached_named or inverse_long_cycle or inverse_low_entropy"
+
+
 def _alt_child(env):
+    marks = "BWTS_INV_MARK" in env or "BWTS_BYTEMARK" in env
     # (-s: the child must not capture its tests' stderr -- what the HIP runtime says when it aborts the process would stay in the capture file)
     cmd = [sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-m", "gpu", "-x", "-q", "-s",
-           "-k", "(small or mid_size or deep_repeats or dense_ties or dense_rounds or chunk_rounds or text_16MiB or reference_unbwts_vectors_through_cabi) and not alternate"]
+           "-k", "(small or mid_size or deep_repeats or dense_ties or dense_rounds or chunk_rounds or text_16MiB or reference_unbwts_vectors_through_cabi"
+                 + (_ALT_INVERSE_TESTS if marks else "") + ") and not alternate"]
     # (-k matches case-insensitively and looks at parameter ids too: without the exclusion, an id like BWTS_RX_SMALL=0
     # makes the child select this very test and start a child of its own.)
     proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,

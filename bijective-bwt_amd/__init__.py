@@ -43,7 +43,7 @@ EXPORTS = [
 TEST_EXPORTS = [
     "bwts_generate_device", "bwts_device_alloc", "bwts_device_free", "bwts_copy_to_device", "bwts_copy_to_host",
     "bwts_device_equal", "bwts_debug_sort_pairs", "bwts_debug_suffix_array", "bwts_debug_lyndon",
-    "bwts_debug_chunk_plan", "bwts_debug_inverse_arena", "bwts_debug_inverse_report",
+    "bwts_debug_chunk_plan", "bwts_debug_inverse_arena", "bwts_debug_inverse_report", "bwts_debug_forward_report",
 ]
 # bwts_debug_inverse_report: the words of one attempt's record, and what marks, outcomes and forms are called
 INV_REPORT_FIELDS = ["g", "mark", "outcome", "s", "virtual", "node_cap", "nu", "nu2", "ucap_first", "second_collect",
@@ -51,6 +51,23 @@ INV_REPORT_FIELDS = ["g", "mark", "outcome", "s", "virtual", "node_cap", "nu", "
 INV_MARKS = {0: "log", 1: "sentinel", 2: "bytemap", 3: "moments"}
 INV_OUTCOMES = {0: "DONE", 1: "RETRY_DENSE", 2: "AMBIGUOUS", 3: "NEED_LOG", 255: "ERROR"}
 INV_FORMS = {0: "narrow", 1: "wide", 2: "wide_compact"}
+# bwts_debug_forward_report: the header words of one sort's record (chunk words from 24 on), the words of a round's record by
+# form, and what forms, reasons and ends are called
+FWD_HEADER_WORDS, FWD_ROUND_WORDS = 48, 12
+FWD_SORT_WORDS = FWD_HEADER_WORDS + MAX_ROUND_STATS * FWD_ROUND_WORDS
+FWD_HEADER_FIELDS = ["cyclic", "n", "k", "sigma", "bits", "msym", "key_bits", "varlen", "hstep", "keys", "flags_outside_rank", "tied0",
+                     "rank_early", "form", "no_chunks", "need_sa", "end", "rest_chunks", "rest_big", "rest_tiles", "rounds", "directory",
+                     "order_sort", "left"]
+FWD_CHUNK_FIELDS = ["S", "maxchunks", "a_small", "big0", "m_exit", "m_stay", "groups", "wide_possible", "fsl", "compactions",
+                    "compactions_skipped", "enqueued_behind_last"]
+FWD_ROUND_FIELDS = {"sparse": ["form", "h", "in", "out", "splits", "probe", "m_big", "whole", "skip_next"],
+                    "chunks": ["form", "h", "in", "out", "splits", "chunks_in", "chunks_out", "big_in", "big_stays", "big_leaves", "nchunks"],
+                    "tiles": ["form", "h", "in", "out", "splits", "m_big"]}
+FWD_FORMS = {0: "none", 1: "sparse", 2: "chunks", 3: "tiles"}
+FWD_KEYS = {0: "wide", 1: "split32", 2: "split40"}
+FWD_NO_CHUNKS = {0: None, 1: "short_list", 2: "knob", 3: "no_room_store", 4: "no_room_order", 5: "no_room_biglist"}
+FWD_ENDS = {0: "none", 1: "empty", 2: "stable"}
+FWD_PROBES = {0: "short_list", 1: "ran", 2: "skipped"}
 
 
 class BwtsError(RuntimeError):
@@ -134,6 +151,7 @@ def lib():
         L.bwts_debug_chunk_plan.argtypes = [u64, u64, ctypes.POINTER(u64)]
         L.bwts_debug_inverse_arena.argtypes = [u64, i32, i32, ctypes.POINTER(u64)]
         L.bwts_debug_inverse_report.argtypes = [vp, ctypes.POINTER(u64), u64, ctypes.POINTER(u64)]
+        L.bwts_debug_forward_report.argtypes = [vp, ctypes.POINTER(u64), u64, ctypes.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -371,6 +389,38 @@ class Context:
             d["mark"], d["outcome"], d["form"] = INV_MARKS[d["mark"]], INV_OUTCOMES[d["outcome"]], INV_FORMS[d["form"]]
             for f in ("second_collect", "unit_rank"):
                 d[f] = bool(d[f])
+            out.append(d)
+        return out
+
+    def debug_forward_report(self):
+        """One dict per doubling sort of the most recent forward call on this context (also debug_suffix_array / debug_lyndon), in the
+        order they ran: the header (FWD_HEADER_FIELDS; form, keys, no_chunks and end by name, flags as bool), "chunks" (FWD_CHUNK_FIELDS)
+        when the chunk form ran, and "round": one dict per recorded round after round 0 (FWD_ROUND_FIELDS of its form)."""
+        buf = (ctypes.c_uint64 * (2 * FWD_SORT_WORDS))()
+        made = ctypes.c_uint64(0)
+        got = lib().bwts_debug_forward_report(self._h, buf, len(buf), ctypes.byref(made))
+        if got < 0:
+            self._check(got)
+        out = []
+        for a in range(got):
+            w = [int(v) for v in buf[a * FWD_SORT_WORDS:(a + 1) * FWD_SORT_WORDS]]
+            d = {f: w[i] for i, f in enumerate(FWD_HEADER_FIELDS)}
+            d["form"], d["keys"], d["no_chunks"], d["end"] = FWD_FORMS[d["form"]], FWD_KEYS[d["keys"]], FWD_NO_CHUNKS[d["no_chunks"]], FWD_ENDS[d["end"]]
+            for f in ("cyclic", "varlen", "flags_outside_rank", "rank_early", "need_sa", "order_sort"):
+                d[f] = bool(d[f])
+            if d["form"] == "chunks":
+                d["chunks"] = {f: w[24 + i] for i, f in enumerate(FWD_CHUNK_FIELDS)}
+                for f in ("wide_possible", "fsl", "enqueued_behind_last"):
+                    d["chunks"][f] = bool(d["chunks"][f])
+            d["round"] = []
+            for r in range(min(max(d["rounds"] - 1, 0), MAX_ROUND_STATS)):
+                rw = w[FWD_HEADER_WORDS + r * FWD_ROUND_WORDS:FWD_HEADER_WORDS + (r + 1) * FWD_ROUND_WORDS]
+                form = FWD_FORMS[rw[0]]
+                rd = {f: rw[i] for i, f in enumerate(FWD_ROUND_FIELDS[form])}
+                rd["form"] = form
+                if form == "sparse":
+                    rd["probe"], rd["whole"], rd["skip_next"] = FWD_PROBES[rd["probe"]], bool(rd["whole"]), bool(rd["skip_next"])
+                d["round"].append(rd)
             out.append(d)
         return out
 

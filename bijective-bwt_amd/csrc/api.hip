@@ -1194,6 +1194,18 @@ extern "C" int bwts_debug_inverse_report(bwts_ctx *ctx, uint64_t *out, uint64_t 
     return copied;
 }
 
+// what the doubling sorts of the most recent forward call on this context did: no device, the records are host memory
+extern "C" int bwts_debug_forward_report(bwts_ctx *ctx, uint64_t *out, uint64_t cap_words, uint64_t *sorts)
+{
+    static_assert(FWD_HEADER_WORDS == BWTS_FWD_HEADER_WORDS && FWD_ROUND_WORDS == BWTS_FWD_ROUND_WORDS, "the record layout bwts_test.h states");
+    if (!ctx || !sorts || (!out && cap_words)) return BWTS_E_ARG;
+    *sorts = ctx->fwd_sorts_made;
+    int copied = 0;
+    for (u32 a = 0; a < ctx->fwd_sorts_made && a < FWD_REPORT_SORTS && (u64)(a + 1) * FWD_SORT_WORDS <= cap_words; a++, copied++)
+        memcpy(out + (size_t)a * FWD_SORT_WORDS, ctx->fwd_report[a], FWD_SORT_WORDS * sizeof(u64));
+    return copied;
+}
+
 extern "C" int bwts_debug_suffix_array(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint32_t *h_sa)
 {
     if (!ctx || !in || !h_sa || n == 0) return BWTS_E_ARG;

@@ -1112,6 +1112,7 @@ static int big_list_first_split(bwts_ctx *ctx, ChunkRun &c, SortSpace &sp, u64 a
     CH_TRY(read_small(ctx, SM_CHSLOT, CH_SLOT_WORDS));
     const u64 m_exit = ctx->h_small[SM_CHSLOT + CHS_EXIT], m_stay = ctx->h_small[SM_CHSLOT + CHS_STAY];
     b.groups = ctx->h_small[SM_CHSLOT + CHS_BIGGROUPS];
+    { u64 *rep = fwd_report_of(ctx); rep[FC_M_EXIT] = m_exit; rep[FC_M_STAY] = m_stay; rep[FC_GROUPS] = b.groups; }
     if (m_exit + m_stay != b.m || c.tail + m_exit > a0 || b.groups * (CH_GROUP_MAX + 1) > m_stay) CH_FAIL("first split of the big list");
     if (m_exit) {
         CH_TRY(cut_chunks(ctx, c, c.tail, c.tail + m_exit, c.nchunks, true));
@@ -1184,8 +1185,10 @@ static int compact_chunks(bwts_ctx *ctx, ChunkRun &c, u64 a0, u64 a_chunks)
     if (!re.allowed) {
         if (c.trace) fprintf(stderr, "[chunks] list not compacted: %llu elements would make %llu chunks (nominal chunk %u), the tables hold %llu\n",
                              (unsigned long long)a_chunks, (unsigned long long)re.nc, re.S, (unsigned long long)c.maxchunks);
+        fwd_report_of(ctx)[FC_COMPACTIONS_SKIPPED]++;
         return BWTS_OK;
     }
+    fwd_report_of(ctx)[FC_COMPACTIONS]++;
     SpanGuard g(ctx, BWTS_K_ROUND, 0, 0);
     chunk_total_kernel<<<dim3(1), dim3(1024), 0, ctx->stream>>>(c.ccount, c.nchunks, (unsigned long long *)(c.slots + 3 * CH_SLOT_WORDS), c.coff);
     chunk_compact_kernel<<<dim3(c.nchunks), dim3(256), 0, ctx->stream>>>(c.st_idx, c.st_head, c.cstart, c.ccount, c.coff, c.alt_idx, c.alt_head);
@@ -1204,6 +1207,8 @@ static int chunk_finish(bwts_ctx *ctx, ChunkRun &c, SortSpace &sp, u64 n, u32 *S
     if (stable) {
         // (a round enqueued behind the stable one has split nothing either: the lists are what they were)
         SpanGuard g(ctx, BWTS_K_EMIT, a_chunks + b.m, 10 * (a_chunks + b.m));
+        fwd_report_of(ctx)[FR_REST_CHUNKS] = c.nchunks ? a_chunks : 0;
+        fwd_report_of(ctx)[FR_REST_BIG] = b.m;
         if (c.nchunks && a_chunks) {
             chunk_rest_records_kernel<<<dim3(c.nchunks), dim3(256), 0, ctx->stream>>>(c.st_idx, c.st_head, c.cstart, c.ccount, c.mv, c.mvcount);
             chunk_apply_records_kernel<1><<<dim3(c.nchunks), dim3(256), 0, ctx->stream>>>(c.mv, c.cstart, c.mvcount, RecordTargets{sp.rank, c.prev, c.out, need_sa ? SA : nullptr});
@@ -1224,7 +1229,8 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
                         ActiveList cur, u64 a0, u32 *SA, bool need_sa, u32 *rounds_io, bool *handled)
 {
     *handled = false;
-    if (a0 > 0xffffffffull || a0 < CH_MIN_LIST) return BWTS_OK;
+    u64 *rep = fwd_report_of(ctx);
+    if (a0 > 0xffffffffull || a0 < CH_MIN_LIST) { rep[FR_NO_CHUNKS] = FR_NC_SHORT; return BWTS_OK; }
     ChunkRun c{[ctx] { const char *e = bwts_knob(ctx, "BWTS_ROUND_TRACE"); return e && atoi(e) == 1; }(), *rounds_io,
                CYCLIC ? bitlen_u64(n - 1) : bitlen_u64(n), PrevSym{sp.carry_src, d_T, n, d_fstart, k}, CYCLIC ? sp.carry_out : nullptr,
                ctx->d_small + SM_CHSLOT};
@@ -1237,13 +1243,14 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
     L.array(&c.cstart, c.maxchunks + 1); L.array(&c.ccount, c.maxchunks + 1); L.array(&c.mvcount, c.maxchunks + 1); L.array(&c.cwide, c.maxchunks + 1);
     L.array(&c.coff, c.maxchunks + 1); L.array(&c.alt_idx, a0); L.array(&c.alt_head, a0);
     int rc = aux_reserve(ctx, L.bytes(), &base);
-    if (rc == BWTS_E_NOMEM) return BWTS_OK;
+    if (rc == BWTS_E_NOMEM) { rep[FR_NO_CHUNKS] = FR_NC_STORE; return BWTS_OK; }
     CH_TRY(rc);
     // the order block: what the order sort of dense_rounds takes, two key and two value buffers of the whole list
     const size_t ob_bytes = 2 * BlockLayout::padded<u64>(a0) + 2 * BlockLayout::padded<u32>(a0);
     rc = aux_reserve_slot(ctx, 1, ob_bytes, &ob);
-    if (rc == BWTS_E_NOMEM) return BWTS_OK;
+    if (rc == BWTS_E_NOMEM) { rep[FR_NO_CHUNKS] = FR_NC_ORDER; return BWTS_OK; }
     CH_TRY(rc);
+    rep[FR_NO_CHUNKS] = FR_NC_NA;
     *handled = true;
     L.place(base);
 
@@ -1251,6 +1258,8 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
     CH_TRY(chunk_order(ctx, c, n, sp, cur, a0, SA, ob, ob_bytes, &a_small));
     if (c.trace) fprintf(stderr, "[chunks] list %llu: in chunks %llu (nominal chunk %u), big list %llu\n", (unsigned long long)a0,
                          (unsigned long long)a_small, c.S, (unsigned long long)(a0 - a_small));
+    rep[FC_S] = c.S; rep[FC_MAXCHUNKS] = c.maxchunks; rep[FC_A_SMALL] = a_small; rep[FC_BIG0] = a0 - a_small;
+    rep[FC_FSL] = CYCLIC && k <= CH_FS;
     if (a0 - a_small) {
         // (nothing outside this function's own buffers has been written so far: without room for the big list the tile form takes over,
         // as it does when the first two blocks do not fit)
@@ -1258,6 +1267,8 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
         if (rc == BWTS_E_NOMEM) {
             if (c.trace) fprintf(stderr, "[chunks] no room for the big list (%llu elements): the tile form takes over\n", (unsigned long long)(a0 - a_small));
             *handled = false;
+            rep[FR_NO_CHUNKS] = FR_NC_BIGLIST;
+            memset(rep + FC_S, 0, (FWD_HEADER_WORDS - FC_S) * sizeof(u64));       // (the chunk words describe a chunk run: this is none)
             return BWTS_OK;
         }
         if (rc != BWTS_OK) return rc;
@@ -1312,7 +1323,7 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
             const u64 *r = ctx->h_small + SM_CHSLOT + q * CH_SLOT_WORDS;
             // 32 algorithmic bytes per list element and round: position + head in, three successor ranks, position + head out, rank update
             if (c.nchunks) { ctx->tm.k[BWTS_K_ROUND].elems += a_chunks; ctx->tm.k[BWTS_K_ROUND].alg_bytes += 32 * a_chunks; }
-            if (finished) continue;          // (a round enqueued behind the last one: it ran, over what was left, and changed nothing)
+            if (finished) { rep[FC_ENQUEUED_BEHIND_LAST] = 1; continue; }        // (a round enqueued behind the last one: it ran, over what was left, and changed nothing)
             c.rounds++;
             if (r[CHS_ERR]) {
                 if (c.trace) fprintf(stderr, "[chunks] chunk %llu of %u: group [%d, %d) plen %llu len %llu rp %llu slot %llu\n", (unsigned long long)r[5] - 1, c.nchunks,
@@ -1341,10 +1352,17 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
 #endif
             if (c.trace) fprintf(stderr, "[chunks] round %u h %llu: chunks %llu -> %llu, big list %llu -> stays %llu, leaves %llu\n", c.rounds,
                                  (unsigned long long)hs[q], (unsigned long long)a_chunks, (unsigned long long)in_chunks, (unsigned long long)b.m, (unsigned long long)m_stay, (unsigned long long)m_exit);
+            if (u64 *rr = fwd_report_round(ctx, c.rounds)) {
+                rr[FRR_FORM] = FR_FORM_CHUNKS; rr[FRR_H] = hs[q]; rr[FRR_IN] = a_chunks + b.m; rr[FRR_OUT] = in_chunks + m_exit + (b.m ? m_stay : 0);
+                rr[FRR_SPLITS] = r[CHS_SPLIT]; rr[FRR_CHUNKS_IN] = a_chunks; rr[FRR_CHUNKS_OUT] = in_chunks; rr[FRR_BIG_IN] = b.m;
+                rr[FRR_BIG_STAYS] = m_stay; rr[FRR_BIG_LEAVES] = m_exit; rr[FRR_NCHUNKS] = c.nchunks;
+            }
             if (m_exit) CH_TRY(cut_chunks(ctx, c, c.tail, c.tail + m_exit, c.nchunks, true));
             if (b.m) { b.cur ^= 1; b.m = m_stay; }
             a_chunks = in_chunks + m_exit;
             const u64 left = a_chunks + b.m;
+            rep[FR_LEFT] = left;
+            rep[FR_END] = left == 0 ? FR_END_EMPTY : CYCLIC && r[CHS_SPLIT] == 0 ? FR_END_STABLE : FR_END_NONE;
             if (CYCLIC && c.rounds - 1 < BWTS_MAX_ROUND_STATS) ctx->tm.round_active[c.rounds - 1] = left;
             if (left == 0) { finished = true; continue; }
             // no group split: the partition is stable under doubling -- what is left are groups of equal infinite words
@@ -1357,6 +1375,7 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
         }
         if (!finished && c.nchunks >= 64 && a_chunks > 0 && a_chunks * 3 < c.tail) CH_TRY(compact_chunks(ctx, c, a0, a_chunks));
     }
+    rep[FC_WIDE_POSSIBLE] = c.wide_possible;
     CH_TRY(chunk_finish(ctx, c, sp, n, SA, need_sa, stable, a_chunks));
     *rounds_io = c.rounds;
     return BWTS_OK;

@@ -560,6 +560,7 @@ static int dense_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
             }
             cur = sets[0];
             nxt = 1;
+            fwd_report_of(ctx)[FR_ORDER_SORT] = 1;
         }
     }
     // the step is quadrupled per round (three successor ranks per element)
@@ -626,6 +627,10 @@ static int dense_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
         const u64 a_new = ctx->h_small[SM_DGCNT + 0];
         const u64 splits = ctx->h_small[SM_DGCNT + 2];
         if (a_new > a) return BWTS_E_INTERNAL;
+        if (u64 *rr = fwd_report_round(ctx, rounds)) {
+            rr[FRR_FORM] = FR_FORM_TILES; rr[FRR_H] = h; rr[FRR_IN] = a; rr[FRR_OUT] = a_new; rr[FRR_SPLITS] = splits; rr[FRR_TILE_MBIG] = m_big;
+        }
+        fwd_report_of(ctx)[FR_END] = a_new == 0 ? FR_END_EMPTY : CYCLIC && splits == 0 ? FR_END_STABLE : FR_END_NONE;
         cur = sets[nxt];
         nxt ^= 1;
         a = a_new;
@@ -639,8 +644,10 @@ static int dense_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
         if (!CYCLIC && h >= n) return BWTS_E_INTERNAL;  // suffixes are distinct; cannot happen
         if (rounds > 80) return BWTS_E_INTERNAL;
     }
+    fwd_report_of(ctx)[FR_LEFT] = a;
     if (need_sa) BWTS_TRY(sa_from_ranks(ctx, sp.rank, n, SA));
     if (a) {
+        fwd_report_of(ctx)[FR_REST_TILES] = a;
         // groups of equal infinite words: their members take the group's slots in list order
         SpanGuard g(ctx, BWTS_K_EMIT, a, 10 * a);
         DgRestIn rin{cur.head};

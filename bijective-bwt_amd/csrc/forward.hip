@@ -1373,6 +1373,34 @@ __global__ __launch_bounds__(256) void seg_writeback_kernel(const u64 *__restric
     }
 }
 
+// The record of one doubling sort (ctx->fwd_report, read by bwts_debug_forward_report; include/bwts_test.h names the words): values the
+// stages hold on the host anyway.
+enum FwdReportWord { FR_CYCLIC, FR_N, FR_K, FR_SIGMA, FR_BITS, FR_MSYM, FR_KEY_BITS, FR_VARLEN, FR_HSTEP, FR_KEYS, FR_FLAGS_OUTSIDE_RANK,
+                     FR_TIED0, FR_RANK_EARLY, FR_FORM, FR_NO_CHUNKS, FR_NEED_SA, FR_END, FR_REST_CHUNKS, FR_REST_BIG, FR_REST_TILES,
+                     FR_ROUNDS, FR_DIRECTORY, FR_ORDER_SORT, FR_LEFT,
+                     FC_S = 24, FC_MAXCHUNKS, FC_A_SMALL, FC_BIG0, FC_M_EXIT, FC_M_STAY, FC_GROUPS, FC_WIDE_POSSIBLE, FC_FSL, FC_COMPACTIONS,
+                     FC_COMPACTIONS_SKIPPED, FC_ENQUEUED_BEHIND_LAST };
+enum FwdRoundWord { FRR_FORM, FRR_H, FRR_IN, FRR_OUT, FRR_SPLITS, FRR_PROBE = 5, FRR_MBIG, FRR_WHOLE, FRR_SKIP_NEXT,
+                    FRR_CHUNKS_IN = 5, FRR_CHUNKS_OUT, FRR_BIG_IN, FRR_BIG_STAYS, FRR_BIG_LEAVES, FRR_NCHUNKS, FRR_TILE_MBIG = 5 };
+enum FwdForm { FR_FORM_NONE, FR_FORM_SPARSE, FR_FORM_CHUNKS, FR_FORM_TILES };
+enum FwdNoChunks { FR_NC_NA, FR_NC_SHORT, FR_NC_KNOB, FR_NC_STORE, FR_NC_ORDER, FR_NC_BIGLIST };
+enum FwdEnd { FR_END_NONE, FR_END_EMPTY, FR_END_STABLE };
+static_assert(FC_ENQUEUED_BEHIND_LAST < FWD_HEADER_WORDS && FRR_NCHUNKS < FWD_ROUND_WORDS && FR_LEFT < FC_S, "the forward report's layout");
+static u64 *fwd_report_open(bwts_ctx *ctx)
+{
+    u64 *w = ctx->fwd_report[ctx->fwd_sorts_made < FWD_REPORT_SORTS ? ctx->fwd_sorts_made : FWD_REPORT_SORTS - 1];
+    memset(w, 0, FWD_SORT_WORDS * sizeof(u64));
+    ctx->fwd_sorts_made++;
+    return w;
+}
+// the record of the sort that is running: fwd_report_open() has run (only the stages under doubling_sort may ask)
+static inline u64 *fwd_report_of(bwts_ctx *ctx) { assert(ctx->fwd_sorts_made > 0); return ctx->fwd_report[ctx->fwd_sorts_made < FWD_REPORT_SORTS ? ctx->fwd_sorts_made - 1 : FWD_REPORT_SORTS - 1]; }
+// the record of the round that made the round counter `rounds` (round 0 made it 1); null past the records there are
+static inline u64 *fwd_report_round(bwts_ctx *ctx, u32 rounds)
+{
+    return rounds >= 2 && rounds - 2 < BWTS_MAX_ROUND_STATS ? fwd_report_of(ctx) + FWD_HEADER_WORDS + (size_t)(rounds - 2) * FWD_ROUND_WORDS : nullptr;
+}
+
 #include "dense_rounds.h"
 #include "chunk_rounds.h"
 
@@ -1483,7 +1511,7 @@ struct SegBufs { u8 *big; u64 *bk[2]; u32 *bv[2], *bpos; };
 // Groups of <= SEG_CAP sort in place, the rest go through the radix sort (see seg_small_sort_kernel).  *whole = true: the larger
 // groups hold nearly all of the list and nothing more was done -- the caller sorts everything; else K, V hold the sorted round.
 static int seg_sort_round(bwts_ctx *ctx, SortSpace &sp, const SegBufs &sb, const u32 *head, u64 *K, u32 *V, u64 a, int rb, int round_key_bits,
-                          bool *whole, bool *skip_next)
+                          bool *whole, bool *skip_next, u64 *m_big_out)
 {
     u64 *cnt = ctx->d_small + SM_COUNTERS;
     u64 m_big = 0;
@@ -1498,6 +1526,7 @@ static int seg_sort_round(bwts_ctx *ctx, SortSpace &sp, const SegBufs &sb, const
     BWTS_TRY(read_small(ctx, SM_SEGCNT, 256));
     for (int c = 0; c < 256; c++) m_big += ctx->h_small[SM_SEGCNT + c];
     if (m_big > a) return BWTS_E_INTERNAL;
+    *m_big_out = m_big;
     *skip_next = m_big * 10 > a * 9;
     // larger groups hold nearly all of the list: sorting everything costs less than compacting them
     // (by bytes moved the break-even is near 85 %)
@@ -1573,6 +1602,7 @@ static int sparse_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
         BWTS_TRY(radix_sort_pairs(ctx, mp, a, bitlen_u64(n - 1) > 0 ? bitlen_u64(n - 1) : 1, &mr));
         tied_map_finish_kernel<<<dim3((unsigned)((a + 255) / 256)), dim3(256), 0, ctx->stream>>>(akeys[mr], a, tpos);
         if (mr == 0) HIPC(hipMemcpyAsync(trank, scratch, a * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
+        fwd_report_of(ctx)[FR_DIRECTORY] = dir ? (u64)dlog : 0;
         if (dir) {          // same switch as the key directory: a directory over the map's positions
             const int pb = bitlen_u64(n - 1);
             psh = pb > K0_DIR_LOG2_MAX ? pb - K0_DIR_LOG2_MAX : 0;
@@ -1600,7 +1630,13 @@ static int sparse_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
         const bool seg_probe = !seg_skip_next;
         seg_skip_next = false;
         bool whole = true;
-        if (a > 4096 && seg_probe) BWTS_TRY(seg_sort_round(ctx, sp, sb, cur.head, akeys[0], cur.idx, a, rb, round_key_bits, &whole, &seg_skip_next));
+        u64 m_big = 0;
+        if (a > 4096 && seg_probe) BWTS_TRY(seg_sort_round(ctx, sp, sb, cur.head, akeys[0], cur.idx, a, rb, round_key_bits, &whole, &seg_skip_next, &m_big));
+        u64 *rr = fwd_report_round(ctx, rounds);
+        if (rr) {
+            rr[FRR_FORM] = FR_FORM_SPARSE; rr[FRR_H] = h; rr[FRR_IN] = a;
+            rr[FRR_PROBE] = a <= 4096 ? 0 : seg_probe ? 1 : 2; rr[FRR_MBIG] = m_big; rr[FRR_WHOLE] = whole; rr[FRR_SKIP_NEXT] = seg_skip_next;
+        }
         if (whole) {
             const SortPlan ap = sort_plan(akeys[0], akeys[1], cur.idx, scratch, sp.tile_hist, sp.scan_temp);
             int r2 = 0;
@@ -1624,6 +1660,8 @@ static int sparse_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
         nxt ^= 1;
         a = a_new;
         if (CYCLIC && rounds - 1 < BWTS_MAX_ROUND_STATS) ctx->tm.round_active[rounds - 1] = a;
+        if (rr) { rr[FRR_OUT] = a; rr[FRR_SPLITS] = splits; }
+        fwd_report_of(ctx)[FR_END] = a == 0 ? FR_END_EMPTY : CYCLIC && splits == 0 ? FR_END_STABLE : FR_END_NONE;
         if (a == 0) break;
         if (CYCLIC && splits == 0) break;               // partition stable under doubling: equal infinite words
         if (!CYCLIC && h >= n) return BWTS_E_INTERNAL;  // suffixes are distinct; cannot happen
@@ -1650,6 +1688,11 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
     *active0_out = a;
     if (CYCLIC) ctx->tm.round_active[0] = a;
     const bool rank_early = a > n / 32 && r0.flags_outside_rank && n >= (1ull << 22);
+    u64 *rep = fwd_report_open(ctx);
+    rep[FR_CYCLIC] = CYCLIC; rep[FR_N] = n; rep[FR_K] = k; rep[FR_SIGMA] = (u64)al.sigma; rep[FR_BITS] = (u64)al.bits; rep[FR_MSYM] = (u64)al.msym;
+    rep[FR_KEY_BITS] = (u64)al.key_bits; rep[FR_VARLEN] = al.varlen; rep[FR_HSTEP] = (u64)al.hstep;
+    rep[FR_KEYS] = r0.k0v.wide ? 0 : r0.k0v.hi ? 2 : 1; rep[FR_FLAGS_OUTSIDE_RANK] = r0.flags_outside_rank; rep[FR_TIED0] = a;
+    rep[FR_RANK_EARLY] = rank_early; rep[FR_ROUNDS] = 1;
     if (rank_early) BWTS_TRY(early_ranks(ctx, n, sp, r0));
     ActiveList cur, none{nullptr, nullptr, nullptr};
     BWTS_TRY(tied_list(ctx, n, sp, r0, &cur));
@@ -1660,7 +1703,9 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
     if (a > 0xffffffffull) return BWTS_E_NOMEM;
     // few tied elements: sparse rank map; many (real text ties most m-grams): the dense rank array
     if (a > 0 && a <= n / 32) {
+        rep[FR_FORM] = FR_FORM_SPARSE;
         BWTS_TRY((sparse_rounds<CYCLIC>(ctx, d_T, n, al, d_fstart, k, sp, r0, &cur, &a, &rounds)));
+        rep[FR_ROUNDS] = rounds; rep[FR_LEFT] = a;
     } else if (a > 0) {
         BWTS_TRY(ensure_rank(ctx, sp, n));
         if (!rank_early) BWTS_TRY(build_ranks(ctx, SA, n, cur, a, sp.rank));      // (else built before the tied list, see above)
@@ -1670,8 +1715,12 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
         // chunks (chunk_rounds.h) unless BWTS_DENSE=tiles asks for the tile form (dense_rounds.h), the list is short or memory is
         const bool tiles_only = [ctx] { const char *e = bwts_knob(ctx, "BWTS_DENSE"); return e && !strcmp(e, "tiles"); }();
         bool handled = false;
+        rep[FR_NEED_SA] = need_sa;
+        if (tiles_only) rep[FR_NO_CHUNKS] = FR_NC_KNOB;
         if (!tiles_only) BWTS_TRY((chunk_rounds<CYCLIC>(ctx, d_T, n, al, d_fstart, k, sp, cur, a, SA, need_sa, &rounds, &handled)));
+        rep[FR_FORM] = handled ? FR_FORM_CHUNKS : FR_FORM_TILES;
         if (!handled) BWTS_TRY((dense_rounds<CYCLIC>(ctx, d_T, n, al, d_fstart, k, sp, cur, a, SA, need_sa, &rounds)));
+        rep[FR_ROUNDS] = rounds;
         sp.ties_emitted = CYCLIC && sp.carry_out;
         *sa_out = SA;
         *rounds_out = rounds;
@@ -1743,6 +1792,7 @@ static int suffix_sort_in(bwts_ctx *ctx, const u8 *d_T, u64 n, SortSpace &sp, bo
 
 int suffix_sort_device(bwts_ctx *ctx, const u8 *d_T, u64 n, u32 **d_sa, u32 **d_rank, u32 *rounds)
 {
+    ctx->fwd_sorts_made = 0;
     BWTS_TRY(read_histogram(ctx, d_T, n));
     SortSpace sp;
     BWTS_TRY(sort_space_alloc(ctx, n, &sp));
@@ -2126,6 +2176,7 @@ static int factors_and_keys(bwts_ctx *ctx, const u8 *d_T, u64 n, SortSpace &sp, 
 
 int lyndon_factors_device(bwts_ctx *ctx, const u8 *d_T, u64 n, u32 **d_fstart, u64 *k_out, u32 *rounds)
 {
+    ctx->fwd_sorts_made = 0;
     SortSpace sp;
     BWTS_TRY(sort_space_alloc(ctx, n, &sp));
     Alphabet al;
@@ -2280,6 +2331,7 @@ int forward_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
 
 static int forward_run(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, const SegTable *seg)
 {
+    ctx->fwd_sorts_made = 0;
     // beyond 32-bit indices: the blocked path with 64-bit positions and ranks (wide_path.h).  BWTS_FORCE_WIDE=1 sends every
     // input there, falling back when the wide form cannot take it; =2 does not fall back (tests)
     const int force_wide = [ctx] { const char *e = bwts_knob(ctx, "BWTS_FORCE_WIDE"); return e ? atoi(e) : 0; }();

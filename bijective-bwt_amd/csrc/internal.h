@@ -53,6 +53,11 @@ struct CopyPool {
 
 #define INV_REPORT_MAX 8         // (the narrow inverse's fallback chain has at most five attempts, the wide one four)
 #define INV_REPORT_WORDS 16
+// the forward's report (bwts_debug_forward_report; include/bwts_test.h names the words): a header, then one record per later round
+#define FWD_REPORT_SORTS 2       // (the suffix sort of the general Lyndon path, then the cyclic sort)
+#define FWD_HEADER_WORDS 48
+#define FWD_ROUND_WORDS 12
+#define FWD_SORT_WORDS (FWD_HEADER_WORDS + BWTS_MAX_ROUND_STATS * FWD_ROUND_WORDS)
 #define STAGE_SLOTS 4
 #define BWTS_AUX_SLOTS 5
 
@@ -86,6 +91,10 @@ struct bwts_ctx {
     // attempt); bwts_debug_inverse_report is the only reader and include/bwts_test.h names the words
     u64 inv_report[INV_REPORT_MAX][INV_REPORT_WORDS];
     u32 inv_attempts_made = 0;          // attempts of that call (the records of those past INV_REPORT_MAX are dropped)
+    // forward: one record per doubling sort of the most recent call, likewise from values the stages read back anyway;
+    // bwts_debug_forward_report is the only reader
+    u64 fwd_report[FWD_REPORT_SORTS][FWD_SORT_WORDS];
+    u32 fwd_sorts_made = 0;             // sorts of that call (a third one and later overwrite the last record)
     // tied list of the forward transform beyond 2^32 positions (wide_path.h): blocks of 2^tied_blk_lg (position, head) pairs, taken as the
     // list grows and kept for the next call
     std::vector<char *> tied_blk;

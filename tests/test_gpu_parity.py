@@ -180,8 +180,40 @@ def test_dense_ties_at_bin_threshold_vs_oracle(ctx):
     assert len(x) == 1 << 22
     y = ctx.forward(x)
     assert ctx.timings().active_after_round0 > len(x) // 32
+    # (more than n/32 tied at n = 2^22, whatever the key: the dense ranks are built ahead of the tied list wherever the flags lie
+    # outside sp.rank, and the later rounds take a dense form)
+    rep = _sort_report(ctx)
+    assert rep["n"] == 1 << 22 and rep["tied0"] == ctx.timings().active_after_round0, rep
+    assert rep["rank_early"] == (not _gather_forced()) and rep["flags_outside_rank"] == (not _gather_forced()) and rep["form"] == _dense_form(), rep
     assert np.array_equal(y, O.forward(x))
     assert np.array_equal(ctx.inverse(y), x)
+
+
+def _sort_report(ctx):
+    """The cyclic sort's record of the forward that has just run (Context.debug_forward_report)."""
+    rep = ctx.debug_forward_report()[-1]
+    assert rep["cyclic"]
+    return rep
+
+
+def _tile_form_forced():
+    """Inside the BWTS_DENSE=tiles child of test_alternate_paths the tile form runs where chunks would."""
+    return os.environ.get("BWTS_TEST_KNOBS") == "1" and os.environ.get("BWTS_DENSE") == "tiles"
+
+
+def _gather_forced():
+    """Inside the BWTS_EMIT=gather child of test_alternate_paths no byte rides on round 0: its flags lie in sp.rank, and the dense
+    ranks cannot be built ahead of the tied list."""
+    return os.environ.get("BWTS_TEST_KNOBS") == "1" and os.environ.get("BWTS_EMIT") == "gather"
+
+
+def _dense_form():
+    return "tiles" if _tile_form_forced() else "chunks"
+
+
+def _key_forced():
+    """Inside a child of test_alternate_paths that forces the round-0 key."""
+    return os.environ.get("BWTS_TEST_KNOBS") == "1" and any(k in os.environ for k in ("BWTS_KEY_SYMBOLS", "BWTS_KEY_BITS"))
 
 
 def _structured_input(seed):
@@ -226,6 +258,12 @@ def test_deep_repeats_vs_oracle(ctx):
     y = ctx.forward(x)
     # (repeats of 50 000 symbols.  The rounds need log4(50 000 / 4) + 1 >= 6 of them)
     assert ctx.timings().rounds >= 6
+    # (every position of a copy is tied with its twin for as long as the depth stays inside the copy: about 180 000 of 181 000 after
+    # round 0, whatever the key -- a dense form; below 2^22 bytes the ranks are not built ahead)
+    rep = _sort_report(ctx)
+    assert rep["rounds"] == ctx.timings().rounds and len(rep["round"]) == rep["rounds"] - 1, rep
+    assert rep["tied0"] >= 170000 and not rep["rank_early"] and rep["form"] == _dense_form(), rep
+    assert [r["out"] for r in rep["round"]] == [int(v) for v in ctx.timings().round_active[1:rep["rounds"]]], rep
     assert np.array_equal(y, O.forward(x))
     assert np.array_equal(ctx.inverse(y), x)
 
@@ -255,6 +293,12 @@ def test_dense_rounds_repeated_material(ctx, kind):
             L = int(2 ** rng.uniform(6, 18)); at = int(rng.integers(0, n - L)); x[at:at + L] = np.resize(per, L)
     y = ctx.forward(x)
     assert ctx.timings().active_after_round0 > n // 64
+    # (written for the tile form; lists of 65 536 elements and more go to chunks now, and the tile form on inputs like these is
+    # the BWTS_DENSE=tiles cells of tests/test_forward_paths.py and the child of test_alternate_paths)
+    rep = _sort_report(ctx)
+    # (by tests/forward_model.py the four kinds still have 1.09 .. 2.79 Mi elements tied at depth 64, and no key holds more than 64
+    # symbols: more than n/32 = 131 072 are tied after round 0 under any key, so a dense form it is)
+    assert rep["tied0"] > n // 32 and rep["form"] == _dense_form(), rep
     assert np.array_equal(y, O.forward(x))
     assert np.array_equal(ctx.inverse(y), x)
 
@@ -273,6 +317,10 @@ def test_chunk_rounds_many_factors_equal_rotations(ctx):
     y = ctx.forward(x)
     t = ctx.timings()
     assert t.factors == 402 and t.active_after_round0 == len(x)
+    rep = _sort_report(ctx)
+    assert rep["end"] == "stable" and rep["left"] == len(x), rep
+    if not _tile_form_forced():
+        assert rep["form"] == "chunks" and not rep["chunks"]["fsl"] and rep["rest_chunks"] + rep["rest_big"] == len(x) and rep["rest_chunks"] > 0, rep
     assert np.array_equal(y, O.forward(x))
     assert np.array_equal(ctx.inverse(y), x)
 
@@ -292,6 +340,18 @@ def test_chunk_rounds_groups_of_hundreds_and_thousands(ctx):
         y = ctx.forward(x)
         t = ctx.timings()
         assert t.active_after_round0 >= 1 << 16                   # (the chunk form takes lists from 65 536 elements on)
+        rep = _sort_report(ctx)
+        if not _tile_form_forced():
+            ch = rep["chunks"]
+            left_big = ch["m_exit"] + sum(r["big_leaves"] for r in rep["round"])
+            # whatever the key: groups of more than 256 (a big list), pieces of it that leave for WIDE chunks, and nothing left in it
+            assert rep["form"] == "chunks" and ch["big0"] > 0 and ch["wide_possible"] and left_big > 0, rep
+            assert rep["round"][-1]["big_stays"] == 0 and rep["rest_big"] == 0, rep
+            # the key the heuristics pick is shorter than the phrases, so round 0 itself leaves groups of 257 .. 2048 (they go at the first
+            # split) beside larger ones (they stay).  A forced key of two symbols (a child of test_alternate_paths) ties everything into
+            # sigma^2 groups of far more than 2048: there the first split lets nothing go, and only the general claim holds.
+            if not _key_forced():
+                assert ch["m_exit"] > 0 and ch["m_stay"] > 0 and any(r["big_leaves"] > 0 for r in rep["round"]), rep
         assert np.array_equal(y, O.forward(x)), (seed, n, sigma)
         assert np.array_equal(ctx.inverse(y), x)
 
@@ -303,6 +363,10 @@ def test_dense_ties_large_vs_oracle(ctx):
     y = ctx.forward(x)
     t = ctx.timings()
     assert t.active_after_round0 > len(x) // 32 and t.rounds >= 6
+    rep = _sort_report(ctx)
+    assert rep["rounds"] == t.rounds and len(rep["round"]) == t.rounds - 1 and rep["tied0"] == t.active_after_round0, rep
+    assert rep["rank_early"] == (not _gather_forced()) and rep["form"] == _dense_form(), rep
+    assert all(r["form"] == _dense_form() for r in rep["round"]), rep
     assert np.array_equal(y, O.forward(x))
     assert np.array_equal(ctx.inverse(y), x)
 
@@ -322,7 +386,7 @@ def test_inverse_many_tiny_cycles(ctx):
     assert np.array_equal(ctx.forward(ctx.inverse(z)), z)
 
 
-def test_no_room_for_the_big_list_falls_back_to_the_tile_form(pkg, capfd):
+def test_no_room_for_the_big_list_falls_back_to_the_tile_form(pkg):
     """Groups of thousands of members go to the chunk rounds' big list, whose buffers are reserved once the list's size is known -- after
     the first two blocks.  Without room for them the tile form takes over, as it does when the first blocks do not fit (nothing but
     the function's own buffers has been written by then): same bytes, no error.  BWTS_BIGLIST_NOMEM=1 refuses that reservation."""
@@ -330,20 +394,25 @@ def test_no_room_for_the_big_list_falls_back_to_the_tile_form(pkg, capfd):
     phrase = rng.integers(97, 123, 200, dtype=np.uint8)
     x = np.concatenate([np.tile(phrase, 5000), O.generate("zipf", 1 << 20, 4)])
     want = O.forward(x)
-    saved = {k: os.environ.get(k) for k in ("BWTS_TEST_KNOBS", "BWTS_BIGLIST_NOMEM", "BWTS_ROUND_TRACE")}
+    saved = {k: os.environ.get(k) for k in ("BWTS_TEST_KNOBS", "BWTS_BIGLIST_NOMEM", "BWTS_DENSE")}
     try:
-        os.environ.update(BWTS_TEST_KNOBS="1", BWTS_BIGLIST_NOMEM="1", BWTS_ROUND_TRACE="1")
+        os.environ.pop("BWTS_DENSE", None)
+        os.environ.update(BWTS_TEST_KNOBS="1", BWTS_BIGLIST_NOMEM="1")
         with pkg.Context(0) as ctx:                      # (a context reads its switches when it is made)
             got = ctx.forward(x)
-            assert "no room for the big list" in capfd.readouterr().err          # (the input does have one, and it was refused)
+            rep = _sort_report(ctx)                      # (the input does have a big list, and it was refused)
+            assert rep["form"] == "tiles" and rep["no_chunks"] == "no_room_biglist", rep
             assert np.array_equal(got, want)
             assert np.array_equal(ctx.inverse(got), x)
+        os.environ.pop("BWTS_BIGLIST_NOMEM")
+        with pkg.Context(0) as ctx:                      # ... and with room the chunk form keeps it
+            assert np.array_equal(ctx.forward(x), want)
+            rep = _sort_report(ctx)
+            assert rep["form"] == "chunks" and rep["chunks"]["big0"] > 0, rep
     finally:
         for k, v in saved.items():
             if v is None: os.environ.pop(k, None)
             else: os.environ[k] = v
-    with pkg.Context(0) as ctx:
-        assert np.array_equal(ctx.forward(x), want)
 
 
 def _short_factors_text(words, length, tail, seed):

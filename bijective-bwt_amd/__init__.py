@@ -43,7 +43,8 @@ EXPORTS = [
 TEST_EXPORTS = [
     "bwts_generate_device", "bwts_device_alloc", "bwts_device_free", "bwts_copy_to_device", "bwts_copy_to_host",
     "bwts_device_equal", "bwts_debug_sort_pairs", "bwts_debug_suffix_array", "bwts_debug_lyndon",
-    "bwts_debug_chunk_plan", "bwts_debug_inverse_arena", "bwts_debug_inverse_report", "bwts_debug_forward_report",
+    "bwts_debug_chunk_plan", "bwts_debug_inverse_arena", "bwts_debug_forward_arena", "bwts_debug_inverse_report",
+    "bwts_debug_forward_report",
 ]
 # bwts_debug_inverse_report: the words of one attempt's record, and what marks, outcomes and forms are called
 INV_REPORT_FIELDS = ["g", "mark", "outcome", "s", "virtual", "node_cap", "nu", "nu2", "ucap_first", "second_collect",
@@ -150,6 +151,7 @@ def lib():
         L.bwts_debug_lyndon.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
         L.bwts_debug_chunk_plan.argtypes = [u64, u64, ctypes.POINTER(u64)]
         L.bwts_debug_inverse_arena.argtypes = [u64, i32, i32, ctypes.POINTER(u64)]
+        L.bwts_debug_forward_arena.argtypes = [u64, ctypes.POINTER(u64)]
         L.bwts_debug_inverse_report.argtypes = [vp, ctypes.POINTER(u64), u64, ctypes.POINTER(u64)]
         L.bwts_debug_forward_report.argtypes = [vp, ctypes.POINTER(u64), u64, ctypes.POINTER(u64)]
         _lib = L

@@ -1139,13 +1139,14 @@ extern "C" int bwts_debug_sort_pairs(bwts_ctx *ctx, uint64_t *h_keys, uint32_t *
     if (!ctx || !h_keys || !h_vals) return BWTS_E_ARG;
     HIPC(hipSetDevice(ctx->device));
     spans_reset(ctx);
-    const size_t need = 2 * align_up(m * 8, 256) + 2 * align_up(m * 4, 256) + radix_tile_hist_bytes(m) + scan_temp_bytes(m) + 4096;
-    BWTS_TRY(arena_reserve(ctx, need));
-    u64 *k0 = arena_array<u64>(ctx, m), *k1 = arena_array<u64>(ctx, m);
-    u32 *v0 = arena_array<u32>(ctx, m), *v1 = arena_array<u32>(ctx, m);
-    u32 *tile_hist = (u32 *)arena_alloc(ctx, radix_tile_hist_bytes(m));
-    const SortPlan plan = sort_plan(k0, k1, v0, v1, tile_hist, arena_alloc(ctx, scan_temp_bytes(m)));
-    if (!plan.keys[0] || !plan.keys[1] || !plan.vals[0] || !plan.vals[1] || !plan.tile_hist || !plan.scan_temp) return BWTS_E_NOMEM;
+    SortBufs sb;
+    BlockLayout L;
+    sb.declare(L, m);
+    BWTS_TRY(arena_reserve(ctx, L.bytes()));
+    char *base = (char *)arena_alloc(ctx, L.bytes());
+    if (!base) return BWTS_E_NOMEM;
+    L.place(base);
+    const SortPlan plan = sb.plan();
     HIPC(hipMemcpyAsync(plan.keys[0], h_keys, m * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPC(hipMemcpyAsync(plan.vals[0], h_vals, m * 4, hipMemcpyHostToDevice, ctx->stream));
     int res = 0;
@@ -1181,6 +1182,14 @@ extern "C" int bwts_debug_inverse_arena(uint64_t n, int g, int mark, uint64_t ou
     if (g < 0) g = inverse_splitter_log2(n);
     out[0] = inverse_attempt_bytes(n, g, mark); out[1] = inverse_arena_bytes(n);
     return g;
+}
+
+// the narrow forward's arena, likewise: the bytes its declared layout takes
+extern "C" int bwts_debug_forward_arena(uint64_t n, uint64_t out[1])
+{
+    if (n == 0 || n > 0x100000000ull || !out) return -1;
+    out[0] = forward_arena_bytes(n);
+    return 0;
 }
 
 // what the attempts of the most recent inverse call on this context did: no device, the records are host memory

@@ -102,8 +102,7 @@ int byte_histogram_device(bwts_ctx *ctx, const u8 *d_T, u64 n, u64 *d_hist256)
     return BWTS_OK;
 }
 
-// builds the byte->code table from the histogram in h_small: the cyclic sort uses codes
-// 0..sigma-1; the suffix (non-cyclic) sort reserves code 0 for "past the end" and uses 1..sigma
+// the byte histogram of the text, in h_small[SM_HIST ..]
 static int read_histogram(bwts_ctx *ctx, const u8 *d_T, u64 n)
 {
     BWTS_TRY(byte_histogram_device(ctx, d_T, n, ctx->d_small + SM_HIST));
@@ -130,8 +129,6 @@ static int pick_key_symbols(const u64 *hist, u64 n, int bits, int max_sym)
     return m;
 }
 
-// scratch the key-width sampler may use (round-0 sort buffers, free at that point)
-struct SampleScratch { const u8 *T; u64 *k[2]; u32 *v[2]; u32 *tile_hist; void *scan_temp; };
 #define KEY_SAMPLES (1u << 17)
 #define CNT_SAMPLE (SM_COUNTERS + 16)      // 5 words: adjacent sample keys agreeing on their first 24/32/40/48/56 bits
 __global__ void sample_keys_kernel(const u8 *T, u64 n, const u64 *vtab, u32 samples, u64 *out);
@@ -199,131 +196,129 @@ static int build_alphabetic_code(const u64 *hist, u64 n, u32 *code, u8 *len, dou
     return lmax;
 }
 
-static int set_alphabet(bwts_ctx *ctx, bool reserve_pad, u64 n, Alphabet *al, const SampleScratch *ss = nullptr)
+// Fixed-width codes: the byte -> code table, sigma, bits per code.  The cyclic sort uses codes 0..sigma-1; the suffix (non-cyclic)
+// sort reserves code 0 for "past the end" and uses 1..sigma (reserve_pad).
+static void fixed_codes(const u64 *hist, bool reserve_pad, u8 codes[256], Alphabet *al)
 {
-    u8 codes[256];
     int sigma = 0;
-    for (int c = 0; c < 256; c++) {
-        codes[c] = 0;
-        if (ctx->h_small[SM_HIST + c]) {
-            codes[c] = (u8)(sigma + (reserve_pad ? 1 : 0));   // sigma == 256 with pad handled below
-            sigma++;
-        }
-    }
-    int ncodes = sigma + (reserve_pad ? 1 : 0);
-    int bits = bitlen_u64((u64)(ncodes > 1 ? ncodes - 1 : 1));
+    for (int c = 0; c < 256; c++) codes[c] = hist[c] ? (u8)(sigma++ + (reserve_pad ? 1 : 0)) : (u8)0;   // sigma == 256 with pad handled below
+    const int ncodes = sigma + (reserve_pad ? 1 : 0);
+    al->sigma = sigma;
+    al->bits = bitlen_u64((u64)(ncodes > 1 ? ncodes - 1 : 1));
     al->pad_add = 0;
-    if (bits > 8) {
+    if (al->bits > 8) {
         // 256 symbols + pad: 9-bit codes; the u8 table cannot hold code 256, so the kernels add
         // the +1 themselves (the table then holds 0..255)
-        for (int c = 0, s = 0; c < 256; c++) if (ctx->h_small[SM_HIST + c]) codes[c] = (u8)(s++);
+        for (int c = 0, s = 0; c < 256; c++) if (hist[c]) codes[c] = (u8)(s++);
         al->pad_add = 1;
     }
-    al->sigma = sigma;
-    al->bits = bits;
-    al->msym = pick_key_symbols(ctx->h_small + SM_HIST, n, bits, 64 / bits);
+}
+
+// Width of a variable-length key: the smallest whole number of bytes B for which an i.i.d. source with this histogram leaves at most
+// ~0.8 % of the positions tied.  share[b] = probability that two independent positions agree on the first b
+// bits of their code streams: both start with the same symbol and agree on the rest, or their first code
+// words are both longer than b bits and agree on those b bits.  Host arithmetic only; share[0..64] is left for the caller.
+static int iid_key_bits(const u64 *hist, const u8 *vlen, const u32 *vcode, u64 n, double share[65])
+{
+    double p[256];
+    for (int c = 0; c < 256; c++) p[c] = (double)hist[c] / (double)n;
+    share[0] = 1.0;
+    for (int b = 1; b <= 64; b++) {
+        double s = 0.0;
+        for (int c = 0; c < 256; c++)
+            if (vlen[c] && vlen[c] <= b) s += p[c] * p[c] * share[b - vlen[c]];
+        // code words longer than b bits that share their first b bits are neighbours in symbol order
+        // (alphabetic and prefix-free), so the partial term is a sum of squared run masses
+        double mass = 0.0; u32 cur = 0; bool open = false;
+        for (int c = 0; c < 256; c++) {
+            if (!vlen[c] || vlen[c] <= b) continue;
+            const u32 pc = vcode[c] >> (vlen[c] - b);
+            if (open && pc == cur) mass += p[c];
+            else { s += mass * mass; mass = p[c]; cur = pc; open = true; }
+        }
+        s += mass * mass;
+        share[b] = s;
+    }
+    for (int b = 32; b <= 64; b += 8)
+        if ((double)n * share[b] <= 1.0 / 128.0) return b;
+    return 64;
+}
+
+// The model knows nothing about repeated phrases.  Where the input is large enough to matter, sort the keys
+// of 2^17 sampled positions and count neighbours that agree on their first B bits: if the sample shows
+// clearly more ties than the model allows, take the empirical figure (real text wants the full 64 bits).
+// scratch: the round-0 sort buffers, free at that point; vtab: the code table in h_small.  The only part that launches kernels.
+static int sampled_key_bits(bwts_ctx *ctx, const u8 *d_T, u64 n, const SortBufs &scratch, const u64 *vtab, const double share[65], int *kb_emp)
+{
+    HIPC(hipMemcpyAsync(ctx->d_small + SM_VTAB, vtab, 256 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    HIPC(hipMemsetAsync(ctx->d_small + CNT_SAMPLE, 0, 8 * sizeof(u64), ctx->stream));
+    SpanGuard g(ctx, BWTS_K_KEYBUILD, KEY_SAMPLES, 0);
+    sample_keys_kernel<<<dim3(KEY_SAMPLES / 256), dim3(256), 0, ctx->stream>>>(d_T, n, ctx->d_small + SM_VTAB, KEY_SAMPLES, scratch.keys[0]);
+    int sres = 0;
+    BWTS_TRY(radix_sort_pairs(ctx, scratch.plan(), KEY_SAMPLES, 64, &sres));
+    count_prefix_matches_kernel<<<dim3(KEY_SAMPLES / 256), dim3(256), 0, ctx->stream>>>(
+        scratch.keys[sres], KEY_SAMPLES, (unsigned long long *)(ctx->d_small + CNT_SAMPLE));
+    HIPC(hipGetLastError());
+    BWTS_TRY(read_small(ctx, CNT_SAMPLE, 5));
+    const double pairs = 0.5 * (double)KEY_SAMPLES * (double)KEY_SAMPLES;
+    *kb_emp = 64;
+    for (int b = 32, w = 1; b <= 56; b += 8, w++) {
+        const double m = (double)ctx->h_small[CNT_SAMPLE + w];
+        const double partners = m >= 8.0 ? (double)n * m / pairs : (double)n * share[b];   // few hits: trust the model
+        if (1.0 - exp(-partners) <= 1.0 / 64.0) { *kb_emp = b; break; }
+    }
+    return BWTS_OK;
+}
+
+// The alphabet and the round-0 key of a sort, from the histogram in h_small.  The sampled measurement needs both d_T and scratch.
+static int set_alphabet(bwts_ctx *ctx, bool reserve_pad, u64 n, Alphabet *al, const u8 *d_T = nullptr, const SortBufs *scratch = nullptr)
+{
+    const u64 *hist = ctx->h_small + SM_HIST;
+    u8 codes[256];
+    fixed_codes(hist, reserve_pad, codes, al);
+    const int bits = al->bits;
+    int msym = pick_key_symbols(hist, n, bits, 64 / bits);
     const char *env = bwts_knob(ctx, "BWTS_KEY_SYMBOLS");              // tuning / test knob: force the symbol count (0 = maximum)
-    if (env) { int v = atoi(env); if (v >= 1 && v <= 64 / bits) al->msym = v; else if (v == 0) al->msym = 64 / bits; }
-    al->key_bits = al->bits * al->msym;
-    al->varlen = false;
-    al->hstep = al->msym;
-    al->patch_span = al->msym - 1;
+    if (env) { int v = atoi(env); if (v >= 1 && v <= 64 / bits) msym = v; else if (v == 0) msym = 64 / bits; }
+    al->msym = al->hstep = msym; al->key_bits = bits * msym; al->varlen = false; al->patch_span = msym - 1;
     // variable-length codes when they save whole radix passes (skewed alphabets: text); the suffix sort of the general
     // Lyndon path keeps fixed-width codes with the pad symbol
     const char *vl = bwts_knob(ctx, "BWTS_VARLEN");                    // 0 = never, 1 = always (tests), unset = when it pays
-    if (!reserve_pad && sigma > 1 && !(vl && vl[0] == '0') && !(env && !vl)) {
-        u32 vcode[256]; u8 vlen[256];
-        double avg = 0, ent = 0;
-        const int lmax = build_alphabetic_code(ctx->h_small + SM_HIST, n, vcode, vlen, &avg, &ent);
-        int lmax_eff = lmax;
-        if (lmax <= VL_MAXLEN) {
-            // Width: the smallest whole number of bytes B for which an i.i.d. source with this histogram leaves at most
-            // ~0.8 % of the positions tied.  share[b] = probability that two independent positions agree on the first b
-            // bits of their code streams: both start with the same symbol and agree on the rest, or their first code
-            // words are both longer than b bits and agree on those b bits.
-            int kb = 64;
-            {
-                double p[256], share[65];
-                for (int c = 0; c < 256; c++) p[c] = (double)ctx->h_small[SM_HIST + c] / (double)n;
-                share[0] = 1.0;
-                for (int b = 1; b <= 64; b++) {
-                    double s = 0.0;
-                    for (int c = 0; c < 256; c++)
-                        if (vlen[c] && vlen[c] <= b) s += p[c] * p[c] * share[b - vlen[c]];
-                    // code words longer than b bits that share their first b bits are neighbours in symbol order
-                    // (alphabetic and prefix-free), so the partial term is a sum of squared run masses
-                    double mass = 0.0; u32 cur = 0; bool open = false;
-                    for (int c = 0; c < 256; c++) {
-                        if (!vlen[c] || vlen[c] <= b) continue;
-                        const u32 pc = vcode[c] >> (vlen[c] - b);
-                        if (open && pc == cur) mass += p[c];
-                        else { s += mass * mass; mass = p[c]; cur = pc; open = true; }
-                    }
-                    s += mass * mass;
-                    share[b] = s;
-                }
-                for (int b = 32; b <= 64; b += 8)
-                    if ((double)n * share[b] <= 1.0 / 128.0) { kb = b; break; }
-                // The model knows nothing about repeated phrases.  Where the input is large enough to matter, sort the keys
-                // of 2^17 sampled positions and count neighbours that agree on their first B bits: if the sample shows
-                // clearly more ties than the model allows, take the empirical figure (real text wants the full 64 bits).
-                if (ss && n >= (1ull << 22)) {
-                    u64 *tab = ctx->h_small + SM_VTAB;
-                    for (int c = 0; c < 256; c++) tab[c] = ((u64)vlen[c] << 32) | vcode[c];
-                    HIPC(hipMemcpyAsync(ctx->d_small + SM_VTAB, tab, 256 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-                    HIPC(hipMemsetAsync(ctx->d_small + CNT_SAMPLE, 0, 8 * sizeof(u64), ctx->stream));
-                    SpanGuard g(ctx, BWTS_K_KEYBUILD, KEY_SAMPLES, 0);
-                    sample_keys_kernel<<<dim3(KEY_SAMPLES / 256), dim3(256), 0, ctx->stream>>>(ss->T, n, ctx->d_small + SM_VTAB, KEY_SAMPLES, ss->k[0]);
-                    SortPlan spn = sort_plan(ss->k[0], ss->k[1], ss->v[0], ss->v[1], ss->tile_hist, ss->scan_temp);
-                    int sres = 0;
-                    BWTS_TRY(radix_sort_pairs(ctx, spn, KEY_SAMPLES, 64, &sres));
-                    count_prefix_matches_kernel<<<dim3(KEY_SAMPLES / 256), dim3(256), 0, ctx->stream>>>(
-                        ss->k[sres], KEY_SAMPLES, (unsigned long long *)(ctx->d_small + CNT_SAMPLE));
-                    HIPC(hipGetLastError());
-                    BWTS_TRY(read_small(ctx, CNT_SAMPLE, 5));
-                    const double pairs = 0.5 * (double)KEY_SAMPLES * (double)KEY_SAMPLES;
-                    int kb_emp = 64;
-                    for (int b = 32, w = 1; b <= 56; b += 8, w++) {
-                        const double m = (double)ctx->h_small[CNT_SAMPLE + w];
-                        const double partners = m >= 8.0 ? (double)n * m / pairs : (double)n * share[b];   // few hits: trust the model
-                        if (1.0 - exp(-partners) <= 1.0 / 64.0) { kb_emp = b; break; }
-                    }
-                    if (kb_emp > kb) {
-                        // Repeats, not entropy, tie these positions, and no key width separates the copies of a long repeat: the
-                        // rounds on the tied list will.  Wider keys then only pay where they lengthen the first step (key bits /
-                        // longest code word) -- with short code words five digits (the packed passes) already give a step
-                        // of four symbols, and three fewer n-sized passes beat the few per cent of extra list elements (text 2^30,
-                        // longest code 9 bits: 64 / 48 / 40 / 32 key bits = 169 / 160 / 143 / 159 ms); with long code words (real
-                        // text: 205 symbols, 16 bits) every key bit counts (53.6 MiB: 16.1 / 18.5 / 20.6 / 23.3 ms).
-                        // (five packed digits whatever the model asks for at this n: text 2^31 / 2^32 with 48 against 40 bits = 334 / 660
-                        // against 295 / 590 ms)
-                        const int keep = 40;
-                        if (keep / lmax >= 4) kb = keep;
-                        else {
-                            kb = kb_emp;
-                            // the fixed-width alternative was sized by the same model: let it use every symbol that fits
-                            al->msym = 64 / bits;
-                            al->key_bits = al->bits * al->msym;
-                            al->hstep = al->msym;
-                            al->patch_span = al->msym - 1;
-                        }
-                    }
-                }
+    u32 vcode[256]; u8 vlen[256];
+    double avg = 0, ent = 0;
+    const bool try_vl = !reserve_pad && al->sigma > 1 && !(vl && vl[0] == '0') && !(env && !vl);
+    const int lmax = try_vl ? build_alphabetic_code(hist, n, vcode, vlen, &avg, &ent) : 0;
+    if (try_vl && lmax <= VL_MAXLEN) {
+        u64 *vtab = ctx->h_small + SM_VTAB;          // (length << 32) | code of each byte value
+        for (int c = 0; c < 256; c++) vtab[c] = ((u64)vlen[c] << 32) | vcode[c];
+        double share[65];
+        int kb = iid_key_bits(hist, vlen, vcode, n, share), kb_emp = 0;
+        if (d_T && scratch && n >= (1ull << 22)) BWTS_TRY(sampled_key_bits(ctx, d_T, n, *scratch, vtab, share, &kb_emp));
+        if (kb_emp > kb) {
+            // Repeats, not entropy, tie these positions, and no key width separates the copies of a long repeat: the
+            // rounds on the tied list will.  Wider keys then only pay where they lengthen the first step (key bits /
+            // longest code word) -- with short code words five digits (the packed passes) already give a step
+            // of four symbols, and three fewer n-sized passes beat the few per cent of extra list elements (text 2^30,
+            // longest code 9 bits: 64 / 48 / 40 / 32 key bits = 169 / 160 / 143 / 159 ms); with long code words (real
+            // text: 205 symbols, 16 bits) every key bit counts (53.6 MiB: 16.1 / 18.5 / 20.6 / 23.3 ms).
+            // (five packed digits whatever the model asks for at this n: text 2^31 / 2^32 with 48 against 40 bits = 334 / 660
+            // against 295 / 590 ms)
+            const int keep = 40;
+            if (keep / lmax >= 4) kb = keep;
+            else {
+                kb = kb_emp;
+                // the fixed-width alternative was sized by the same model: let it use every symbol that fits
+                al->msym = al->hstep = 64 / bits; al->key_bits = bits * al->msym; al->patch_span = al->msym - 1;
             }
-            const char *kbe = bwts_knob(ctx, "BWTS_KEY_BITS");
-            if (kbe) { int v = atoi(kbe); if (v >= 8 && v >= lmax && v <= 64) kb = v; }       // (a key must hold its first symbol whole: the first step is >= 1)
-            const int passes_fixed = (al->key_bits + 7) / 8, passes_var = (kb + 7) / 8;
-            // equal pass counts: the variable-length key still holds more symbols when its words are shorter on average
-            if ((vl && vl[0] == '1') || passes_var < passes_fixed || (passes_var == passes_fixed && avg < (double)bits - 0.25)) {
-                al->varlen = true;
-                al->key_bits = kb;
-                al->hstep = kb / lmax_eff < 1 ? 1 : kb / lmax_eff;
-                al->patch_span = 64;
-                al->msym = al->hstep;
-                u64 *tab = ctx->h_small + SM_VTAB;
-                for (int c = 0; c < 256; c++) tab[c] = ((u64)vlen[c] << 32) | vcode[c];
-                HIPC(hipMemcpyAsync(ctx->d_small + SM_VTAB, tab, 256 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-            }
+        }
+        const char *kbe = bwts_knob(ctx, "BWTS_KEY_BITS");
+        if (kbe) { int v = atoi(kbe); if (v >= 8 && v >= lmax && v <= 64) kb = v; }       // (a key must hold its first symbol whole: the first step is >= 1)
+        const int passes_fixed = (al->key_bits + 7) / 8, passes_var = (kb + 7) / 8;
+        // equal pass counts: the variable-length key still holds more symbols when its words are shorter on average
+        if ((vl && vl[0] == '1') || passes_var < passes_fixed || (passes_var == passes_fixed && avg < (double)bits - 0.25)) {
+            al->varlen = true; al->key_bits = kb; al->patch_span = 64;
+            al->msym = al->hstep = kb / lmax < 1 ? 1 : kb / lmax;
+            HIPC(hipMemcpyAsync(ctx->d_small + SM_VTAB, vtab, 256 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
         }
     }
     memcpy(ctx->h_small + SM_CODES, codes, 256);
@@ -1161,34 +1156,24 @@ __global__ __launch_bounds__(256) void rank_from_list_kernel(const u32 *__restri
 // ------------------------------------------------------------------------------------
 // the doubling sort
 // ------------------------------------------------------------------------------------
-struct SortSpace {
-    u64 *keys[2];     // n each
-    u32 *vals[2];     // n each
-    u32 *rank;        // n
-    u32 *tile_hist;
-    void *scan_temp;
-    // emission riding on round 0 (cyclic sort only): P[p] = T[cprev(p)] travels with the pairs and the last
-    // pass writes it straight into the output; null = gather after the sort instead
+// What a doubling sort works in and what its stages tell each other: three kinds of field, each with one writer
+struct SortSpace : SortBufs {               // 1. buffers: keys, vals (n each), tile_hist, scan_temp, placed by the arena's layout (FwdArena)
+    u32 *rank = nullptr;                    //    rank (n): ensure_rank()
+    // 2. inputs of the cyclic sort, set by forward_run before it.  Emission riding on round 0: P[p] = T[cprev(p)] travels with the
+    // pairs and the last pass writes it straight into the output; carry_out null = gather after the sort instead
     const u8 *carry_src = nullptr;
     u8 *carry_buf[2] = {nullptr, nullptr};
     u8 *carry_out = nullptr;
-    // the round-0 tie list (slots), for patching the carried bytes of elements that later rounds reorder
-    const u32 *tie_slots = nullptr;
-    u64 tie_count = 0;
-    // the cyclic sort will carry the byte stream (=> the packed passes may apply); keys[0] currently holds split keys
-    bool want_split = false, split_keys = false;
-    // split keys only, may be null: the first packed pass's table as the key builder counted it (SortPlan::first_hist).  It lives in
-    // vals[0]: round 0's values are the identity, which the first pass does not read, and nothing else uses vals[0] before that
-    // pass has scanned the table.
+    bool want_split = false;                // the sort will carry the byte stream (=> the packed passes may apply, the keys may be split)
+    // 3. handed on by one stage to those after it.  round0_keys(): keys[0] holds split keys; first_hist (split keys only, may be null):
+    // the first packed pass's table as the key builder counted it (SortPlan::first_hist).  It lives in vals[0]: round 0's values are
+    // the identity, which the first pass does not read, and nothing else uses vals[0] before that pass has scanned the table.
+    bool split_keys = false;
     u32 *first_hist = nullptr;
-    // set by the sort when the later rounds wrote the bytes of the tied elements themselves (dense rounds)
-    bool ties_emitted = false;
+    const u32 *tie_slots = nullptr;         // tied_list(): the round-0 tie list (slots), for patching the carried bytes of elements
+    u64 tie_count = 0;                      // that later rounds reorder
+    bool ties_emitted = false;              // doubling_sort(): the later rounds wrote the bytes of the tied elements themselves (dense rounds)
 };
-
-static size_t sort_space_bytes(u64 n)
-{
-    return 2 * align_up(n * 8, 256) + 2 * align_up(n * 4, 256) + radix_tile_hist_bytes(n) + scan_temp_bytes(n) + 4096;
-}
 
 // the dense rank array (4 n bytes) exists only for inputs that need it: many ties after round 0, a suffix array with ranks, or a
 // sort without the carried-byte buffers (whose space the round-0 flag words otherwise use)
@@ -1198,20 +1183,6 @@ static int ensure_rank(bwts_ctx *ctx, SortSpace &sp, u64 n)
     char *p = nullptr;
     BWTS_TRY(aux_reserve_slot(ctx, 4, align_up((size_t)n * 4, 256), &p));
     sp.rank = (u32 *)p;
-    return BWTS_OK;
-}
-
-static int sort_space_alloc(bwts_ctx *ctx, u64 n, SortSpace *sp)
-{
-    sp->keys[0] = arena_array<u64>(ctx, n);
-    sp->keys[1] = arena_array<u64>(ctx, n);
-    sp->vals[0] = arena_array<u32>(ctx, n);
-    sp->vals[1] = arena_array<u32>(ctx, n);
-    sp->rank = nullptr;            // ensure_rank()
-    sp->tile_hist = (u32 *)arena_alloc(ctx, radix_tile_hist_bytes(n));
-    sp->scan_temp = arena_alloc(ctx, scan_temp_bytes(n));
-    if (!sp->keys[0] || !sp->keys[1] || !sp->vals[0] || !sp->vals[1] || !sp->tile_hist || !sp->scan_temp)
-        return BWTS_E_NOMEM;
     return BWTS_OK;
 }
 
@@ -1419,7 +1390,7 @@ template <bool CYCLIC>
 static int round0_sort(bwts_ctx *ctx, u64 n, const Alphabet &al, SortSpace &sp, Round0 *r0)
 {
     u64 *cnt = ctx->d_small + SM_COUNTERS;
-    SortPlan plan = sort_plan(sp.keys[0], sp.keys[1], sp.vals[0], sp.vals[1], sp.tile_hist, sp.scan_temp);
+    SortPlan plan = sp.plan();
     plan.sym_src = sp.carry_src; plan.sym_buf[0] = sp.carry_buf[0]; plan.sym_buf[1] = sp.carry_buf[1]; plan.sym_final = sp.carry_out;
     plan.vals_identity = true;     // keybuild0 writes no value array
     plan.keys_split = CYCLIC && sp.split_keys && plan.sym_final;
@@ -1549,127 +1520,143 @@ static int seg_sort_round(bwts_ctx *ctx, SortSpace &sp, const SegBufs &sb, const
 }
 
 // The rounds after round 0 when few elements are tied: sparse ranks (a map from the tied positions to their heads, everything else
-// ranked by a search in the sorted round-0 keys), the list in SA order, a sort per round.  cur, *a_io: the tied list; on return what is
-// still tied (groups of equal infinite words).
-template <bool CYCLIC>
-static int sparse_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, const u32 *d_fstart, u64 k, SortSpace &sp,
-                         const Round0 &r0, ActiveList *cur_io, u64 *a_io, u32 *rounds_io)
-{
-    const u8 *d_codes = (const u8 *)(ctx->d_small + SM_CODES);
-    u64 *cnt = ctx->d_small + SM_COUNTERS;
-    const K0Keys &k0v = r0.k0v;
-    ActiveList cur = *cur_io;
-    u64 a = *a_io;
-    u32 rounds = *rounds_io;
-    const u64 a0 = a;
-    // aux: two key buffers, one value scratch, two list sets, the tied map, the two directories, the small-groups path's buffers
-    char *base = nullptr;
+// ranked by a search in the sorted round-0 keys), the list in SA order, a sort per round.
+struct SparseRun {
+    // side block 0: two key buffers, one value scratch, two list sets, the tied map, the two directories, the small-groups path's buffers
     u64 *akeys[2], *dir_at;
     u32 *scratch, *tpos, *trank, *pdir_at;
     ActiveList sets[2];
     SegBufs sb;
-    BlockLayout L;
-    L.array(&akeys[0], a); L.array(&akeys[1], a); L.array(&scratch, a);
-    for (int s = 0; s < 2; s++) { L.array(&sets[s].idx, a); L.array(&sets[s].slot, a); L.array(&sets[s].head, a); }
-    L.array(&tpos, a); L.array(&trank, a);
-    L.array(&dir_at, ((u64)1 << K0_DIR_LOG2_MAX) + 1); L.array(&pdir_at, ((u64)1 << K0_DIR_LOG2_MAX) + 2);
-    L.array(&sb.big, a); L.array(&sb.bk[0], a); L.array(&sb.bk[1], a); L.array(&sb.bv[0], a); L.array(&sb.bv[1], a); L.array(&sb.bpos, a);
-    BWTS_TRY(aux_reserve(ctx, L.bytes(), &base));
-    L.place(base);
-    const int rb = CYCLIC ? bitlen_u64(n - 1) : bitlen_u64(n);
-    if (2 * rb > 64) return BWTS_E_RANGE;
-    const int round_key_bits = 2 * rb > 1 ? 2 * rb : 1;
-    int nxt = 0;
-    u64 *dir = nullptr;
-    u32 *pdir = nullptr;
-    int dlog = 0, psh = 0;
+    void declare(BlockLayout &L, u64 a)
     {
-        SpanGuard g(ctx, BWTS_K_RERANK, a, 24 * a);
-        // directory over the sorted keys' top bits for the rank searches of keybuild_sparse_kernel
-        const int kb = al.key_bits;
-        dlog = kb < K0_DIR_LOG2_MAX ? kb : K0_DIR_LOG2_MAX;
-        if (dlog > bitlen_u64(n)) dlog = bitlen_u64(n);
-        if (dlog >= 8) {
-            dir = dir_at;
-            k0_directory_kernel<<<dim3((unsigned)(((1ull << dlog) + 1 + 255) / 256)), dim3(256), 0, ctx->stream>>>(k0v, n, kb, dlog, dir);
-        }
-        // split keys with a high byte: the rank searches compare low words alone (k0_lower_bound)
-        if (k0v.hi && (!dir || kb - dlog > 32)) return BWTS_E_INTERNAL;
-        tied_map_keys_kernel<<<dim3((unsigned)((a + 255) / 256)), dim3(256), 0, ctx->stream>>>(cur.idx, a, akeys[0]);
-        HIPC(hipMemcpyAsync(scratch, cur.head, a * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
-        const SortPlan mp = sort_plan(akeys[0], akeys[1], scratch, trank, sp.tile_hist, sp.scan_temp);
-        int mr = 0;
-        BWTS_TRY(radix_sort_pairs(ctx, mp, a, bitlen_u64(n - 1) > 0 ? bitlen_u64(n - 1) : 1, &mr));
-        tied_map_finish_kernel<<<dim3((unsigned)((a + 255) / 256)), dim3(256), 0, ctx->stream>>>(akeys[mr], a, tpos);
-        if (mr == 0) HIPC(hipMemcpyAsync(trank, scratch, a * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
-        fwd_report_of(ctx)[FR_DIRECTORY] = dir ? (u64)dlog : 0;
-        if (dir) {          // same switch as the key directory: a directory over the map's positions
-            const int pb = bitlen_u64(n - 1);
-            psh = pb > K0_DIR_LOG2_MAX ? pb - K0_DIR_LOG2_MAX : 0;
-            const u64 buckets = ((n - 1) >> psh) + 1;
-            pdir = pdir_at;
-            tpos_directory_kernel<<<dim3((unsigned)((buckets + 1 + 255) / 256)), dim3(256), 0, ctx->stream>>>(tpos, a, psh, buckets, pdir);
-        }
+        L.arrays(a, &akeys[0], &akeys[1]); L.array(&scratch, a);
+        for (int s = 0; s < 2; s++) L.arrays(a, &sets[s].idx, &sets[s].slot, &sets[s].head);
+        L.arrays(a, &tpos, &trank);
+        L.array(&dir_at, ((u64)1 << K0_DIR_LOG2_MAX) + 1); L.array(&pdir_at, ((u64)1 << K0_DIR_LOG2_MAX) + 2);
+        L.array(&sb.big, a); L.arrays(a, &sb.bk[0], &sb.bk[1]); L.arrays(a, &sb.bv[0], &sb.bv[1], &sb.bpos);
+    }
+    u64 a0;                         // tied after round 0: the map's size
+    int rb, round_key_bits;
+    u64 *dir = nullptr;             // sparse_map(): the directories over the sorted keys and the map's positions (null: plain
+    u32 *pdir = nullptr;            // binary searches)
+    int dlog = 0, psh = 0;
+    ActiveList cur;                 // sparse_round(): the tied list and its size, the groups the round split, the set the next
+    u64 a, splits = 0;              // round writes, the round counter
+    int nxt = 0;
+    u32 rounds;                     // (of the whole sort: round 0 counted)
+    bool seg_skip_next = false;
+};
+
+// the tied map (tpos = the tied positions, sorted; trank = their ranks) and the two directories
+static int sparse_map(bwts_ctx *ctx, SparseRun &r, u64 n, const Alphabet &al, SortSpace &sp, const K0Keys &k0v)
+{
+    const u64 a = r.a0;
+    SpanGuard g(ctx, BWTS_K_RERANK, a, 24 * a);
+    // directory over the sorted keys' top bits for the rank searches of keybuild_sparse_kernel
+    const int kb = al.key_bits;
+    r.dlog = kb < K0_DIR_LOG2_MAX ? kb : K0_DIR_LOG2_MAX;
+    if (r.dlog > bitlen_u64(n)) r.dlog = bitlen_u64(n);
+    if (r.dlog >= 8) {
+        r.dir = r.dir_at;
+        k0_directory_kernel<<<dim3((unsigned)(((1ull << r.dlog) + 1 + 255) / 256)), dim3(256), 0, ctx->stream>>>(k0v, n, kb, r.dlog, r.dir);
+    }
+    // split keys with a high byte: the rank searches compare low words alone (k0_lower_bound)
+    if (k0v.hi && (!r.dir || kb - r.dlog > 32)) return BWTS_E_INTERNAL;
+    tied_map_keys_kernel<<<dim3((unsigned)((a + 255) / 256)), dim3(256), 0, ctx->stream>>>(r.cur.idx, a, r.akeys[0]);
+    HIPC(hipMemcpyAsync(r.scratch, r.cur.head, a * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
+    const SortPlan mp = sort_plan(r.akeys[0], r.akeys[1], r.scratch, r.trank, sp.tile_hist, sp.scan_temp);
+    int mr = 0;
+    BWTS_TRY(radix_sort_pairs(ctx, mp, a, bitlen_u64(n - 1) > 0 ? bitlen_u64(n - 1) : 1, &mr));
+    tied_map_finish_kernel<<<dim3((unsigned)((a + 255) / 256)), dim3(256), 0, ctx->stream>>>(r.akeys[mr], a, r.tpos);
+    if (mr == 0) HIPC(hipMemcpyAsync(r.trank, r.scratch, a * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
+    fwd_report_of(ctx)[FR_DIRECTORY] = r.dir ? (u64)r.dlog : 0;
+    if (r.dir) {          // same switch as the key directory: a directory over the map's positions
+        const int pb = bitlen_u64(n - 1);
+        r.psh = pb > K0_DIR_LOG2_MAX ? pb - K0_DIR_LOG2_MAX : 0;
+        const u64 buckets = ((n - 1) >> r.psh) + 1;
+        r.pdir = r.pdir_at;
+        tpos_directory_kernel<<<dim3((unsigned)((buckets + 1 + 255) / 256)), dim3(256), 0, ctx->stream>>>(r.tpos, a, r.psh, buckets, r.pdir);
+    }
+    HIPC(hipGetLastError());
+    return BWTS_OK;
+}
+
+// one round at step h: keys (head, rank of the h-th successor), the sort, the re-rank scan; leaves the new list in r.cur / r.a
+template <bool CYCLIC>
+static int sparse_round(bwts_ctx *ctx, SparseRun &r, const u8 *d_T, u64 n, const Alphabet &al, const u32 *d_fstart, u64 k, SortSpace &sp, const Round0 &r0, u64 h)
+{
+    u64 *cnt = ctx->d_small + SM_COUNTERS;
+    const u64 a = r.a;
+    ActiveList &cur = r.cur;
+    r.rounds++;
+    {
+        SpanGuard g(ctx, BWTS_K_KEYBUILD, a, 20 * a);
+        const unsigned blocks = (unsigned)((a + 255) / 256);
+        keybuild_sparse_kernel<CYCLIC><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(
+            cur.idx, cur.head, a, d_T, n, (const u8 *)(ctx->d_small + SM_CODES), al.bits, al.msym, al.pad_add, h, r0.k0v, r.rb, d_fstart, k, r.akeys[0],
+            al.varlen ? ctx->d_small + SM_VTAB : nullptr, al.key_bits, r.tpos, r.trank, r.a0, r.dir, r.dlog, r.pdir, r.psh);
         HIPC(hipGetLastError());
     }
-
-    bool seg_skip_next = false;
-    for (u64 h = (u64)al.hstep;; h <<= 1) {
-        rounds++;
-        {
-            SpanGuard g(ctx, BWTS_K_KEYBUILD, a, 20 * a);
-            const unsigned blocks = (unsigned)((a + 255) / 256);
-            keybuild_sparse_kernel<CYCLIC><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(
-                cur.idx, cur.head, a, d_T, n, d_codes, al.bits, al.msym, al.pad_add, h, k0v, rb, d_fstart, k, akeys[0],
-                al.varlen ? ctx->d_small + SM_VTAB : nullptr, al.key_bits, tpos, trank, a0, dir, dlog, pdir, psh);
-            HIPC(hipGetLastError());
-        }
-        const u64 *AK = akeys[0];
-        const u32 *AV = cur.idx;
-        // (large groups dominating one round dominate the next one too: then the classification is skipped every other round)
-        const bool seg_probe = !seg_skip_next;
-        seg_skip_next = false;
-        bool whole = true;
-        u64 m_big = 0;
-        if (a > 4096 && seg_probe) BWTS_TRY(seg_sort_round(ctx, sp, sb, cur.head, akeys[0], cur.idx, a, rb, round_key_bits, &whole, &seg_skip_next, &m_big));
-        u64 *rr = fwd_report_round(ctx, rounds);
-        if (rr) {
-            rr[FRR_FORM] = FR_FORM_SPARSE; rr[FRR_H] = h; rr[FRR_IN] = a;
-            rr[FRR_PROBE] = a <= 4096 ? 0 : seg_probe ? 1 : 2; rr[FRR_MBIG] = m_big; rr[FRR_WHOLE] = whole; rr[FRR_SKIP_NEXT] = seg_skip_next;
-        }
-        if (whole) {
-            const SortPlan ap = sort_plan(akeys[0], akeys[1], cur.idx, scratch, sp.tile_hist, sp.scan_temp);
-            int r2 = 0;
-            BWTS_TRY(radix_sort_pairs(ctx, ap, a, round_key_bits, &r2));
-            AK = akeys[r2];
-            AV = r2 ? scratch : cur.idx;
-        }
-
-        HIPC(hipMemsetAsync(cnt, 0, 4 * sizeof(u64), ctx->stream));
-        {
-            SpanGuard g(ctx, BWTS_K_RERANK, a, 24 * a);
-            GroupIn in{AK, cur.slot, a, rb};
-            GroupOut out{cur.slot, AV, a, rb, AK, tpos, trank, a0, r0.SA,
-                         sets[nxt].idx, sets[nxt].slot, sets[nxt].head, cnt + 0, cnt + 1};
-            BWTS_TRY((device_scan<true, u64>(ctx, a, in, out, OpHeadCount(), (u64)0, sp.scan_temp)));
-        }
-        BWTS_TRY(read_small(ctx, SM_COUNTERS, 4));
-        const u64 a_new = ctx->h_small[CNT_ACTIVE];
-        const u64 splits = ctx->h_small[CNT_SPLITS];
-        cur = sets[nxt];
-        nxt ^= 1;
-        a = a_new;
-        if (CYCLIC && rounds - 1 < BWTS_MAX_ROUND_STATS) ctx->tm.round_active[rounds - 1] = a;
-        if (rr) { rr[FRR_OUT] = a; rr[FRR_SPLITS] = splits; }
-        fwd_report_of(ctx)[FR_END] = a == 0 ? FR_END_EMPTY : CYCLIC && splits == 0 ? FR_END_STABLE : FR_END_NONE;
-        if (a == 0) break;
-        if (CYCLIC && splits == 0) break;               // partition stable under doubling: equal infinite words
-        if (!CYCLIC && h >= n) return BWTS_E_INTERNAL;  // suffixes are distinct; cannot happen
-        if (rounds > 80) return BWTS_E_INTERNAL;
+    const u64 *AK = r.akeys[0];
+    const u32 *AV = cur.idx;
+    // (large groups dominating one round dominate the next one too: then the classification is skipped every other round)
+    const bool seg_probe = !r.seg_skip_next;
+    r.seg_skip_next = false;
+    bool whole = true;
+    u64 m_big = 0;
+    if (a > 4096 && seg_probe) BWTS_TRY(seg_sort_round(ctx, sp, r.sb, cur.head, r.akeys[0], cur.idx, a, r.rb, r.round_key_bits, &whole, &r.seg_skip_next, &m_big));
+    u64 *rr = fwd_report_round(ctx, r.rounds);
+    if (rr) {
+        rr[FRR_FORM] = FR_FORM_SPARSE; rr[FRR_H] = h; rr[FRR_IN] = a;
+        rr[FRR_PROBE] = a <= 4096 ? 0 : seg_probe ? 1 : 2; rr[FRR_MBIG] = m_big; rr[FRR_WHOLE] = whole; rr[FRR_SKIP_NEXT] = r.seg_skip_next;
     }
-    *cur_io = cur;
-    *a_io = a;
-    *rounds_io = rounds;
+    if (whole) {
+        const SortPlan ap = sort_plan(r.akeys[0], r.akeys[1], cur.idx, r.scratch, sp.tile_hist, sp.scan_temp);
+        int r2 = 0;
+        BWTS_TRY(radix_sort_pairs(ctx, ap, a, r.round_key_bits, &r2));
+        AK = r.akeys[r2];
+        AV = r2 ? r.scratch : cur.idx;
+    }
+    HIPC(hipMemsetAsync(cnt, 0, 4 * sizeof(u64), ctx->stream));
+    {
+        SpanGuard g(ctx, BWTS_K_RERANK, a, 24 * a);
+        const ActiveList &to = r.sets[r.nxt];
+        GroupIn in{AK, cur.slot, a, r.rb};
+        GroupOut out{cur.slot, AV, a, r.rb, AK, r.tpos, r.trank, r.a0, r0.SA, to.idx, to.slot, to.head, cnt + 0, cnt + 1};
+        BWTS_TRY((device_scan<true, u64>(ctx, a, in, out, OpHeadCount(), (u64)0, sp.scan_temp)));
+    }
+    BWTS_TRY(read_small(ctx, SM_COUNTERS, 4));
+    r.a = ctx->h_small[CNT_ACTIVE]; r.splits = ctx->h_small[CNT_SPLITS];
+    cur = r.sets[r.nxt]; r.nxt ^= 1;
+    if (CYCLIC && r.rounds - 1 < BWTS_MAX_ROUND_STATS) ctx->tm.round_active[r.rounds - 1] = r.a;
+    if (rr) { rr[FRR_OUT] = r.a; rr[FRR_SPLITS] = r.splits; }
+    return BWTS_OK;
+}
+
+// cur, *a_io: the tied list; on return what is still tied (groups of equal infinite words).
+template <bool CYCLIC>
+static int sparse_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, const u32 *d_fstart, u64 k, SortSpace &sp,
+                         const Round0 &r0, ActiveList *cur_io, u64 *a_io, u32 *rounds_io)
+{
+    SparseRun r;
+    BlockLayout L;
+    r.cur = *cur_io; r.a = r.a0 = *a_io; r.rounds = *rounds_io; r.declare(L, r.a0);
+    char *base = nullptr;
+    BWTS_TRY(aux_reserve(ctx, L.bytes(), &base));
+    L.place(base);
+    r.rb = CYCLIC ? bitlen_u64(n - 1) : bitlen_u64(n);
+    if (2 * r.rb > 64) return BWTS_E_RANGE;
+    r.round_key_bits = 2 * r.rb > 1 ? 2 * r.rb : 1;
+    BWTS_TRY(sparse_map(ctx, r, n, al, sp, r0.k0v));
+    for (u64 h = (u64)al.hstep;; h <<= 1) {
+        BWTS_TRY((sparse_round<CYCLIC>(ctx, r, d_T, n, al, d_fstart, k, sp, r0, h)));
+        fwd_report_of(ctx)[FR_END] = r.a == 0 ? FR_END_EMPTY : CYCLIC && r.splits == 0 ? FR_END_STABLE : FR_END_NONE;
+        if (r.a == 0) break;
+        if (CYCLIC && r.splits == 0) break;             // partition stable under doubling: equal infinite words
+        if (!CYCLIC && h >= n) return BWTS_E_INTERNAL;  // suffixes are distinct; cannot happen
+        if (r.rounds > 80) return BWTS_E_INTERNAL;
+    }
+    *cur_io = r.cur; *a_io = r.a; *rounds_io = r.rounds;
     return BWTS_OK;
 }
 
@@ -1755,11 +1742,6 @@ static int launch_keybuild0_seg(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alpha
     HIPC(hipGetLastError());
     return BWTS_OK;
 }
-static int launch_keybuild0(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, SortSpace &sp, u64 *tile_min, bool split,
-                            u32 *hist0 = nullptr)
-{
-    return launch_keybuild0_seg(ctx, d_T, n, al, sp.keys[0], tile_min, split, 0, n, nullptr, hist0);
-}
 
 // ------------------------------------------------------------------------------------
 // Lyndon factors, general path: strict prefix minima of the suffix ranks (mk_bwts_sa.c:126-129)
@@ -1785,19 +1767,22 @@ static int suffix_sort_in(bwts_ctx *ctx, const u8 *d_T, u64 n, SortSpace &sp, bo
     if (n > 0xffffffffull) return BWTS_E_RANGE;
     Alphabet al;
     BWTS_TRY(set_alphabet(ctx, true, n, &al));
-    BWTS_TRY(launch_keybuild0(ctx, d_T, n, al, sp, nullptr, false));
+    BWTS_TRY(launch_keybuild0_seg(ctx, d_T, n, al, sp.keys[0], nullptr, false, 0, n));
     u64 active0 = 0;
     return doubling_sort<false>(ctx, d_T, n, al, nullptr, 0, sp, want_ranks, d_sa, rounds, &active0);
 }
 
-int suffix_sort_device(bwts_ctx *ctx, const u8 *d_T, u64 n, u32 **d_sa, u32 **d_rank, u32 *rounds)
+// The shared tail of the general and the segment path, after their compaction scan left the sorted factor starts in keys[1] (free at
+// both) and their number in CNT_TOTAL: read k, refuse one outside [k_min, n], move the list to side slot 2.
+static int take_factor_list(bwts_ctx *ctx, u64 n, u64 k_min, SortSpace &sp, u32 **d_fstart, u64 *k_out)
 {
-    ctx->fwd_sorts_made = 0;
-    BWTS_TRY(read_histogram(ctx, d_T, n));
-    SortSpace sp;
-    BWTS_TRY(sort_space_alloc(ctx, n, &sp));
-    BWTS_TRY(suffix_sort_in(ctx, d_T, n, sp, true, d_sa, rounds));
-    *d_rank = sp.rank;
+    BWTS_TRY(read_small(ctx, CNT_TOTAL, 1));
+    const u64 k = ctx->h_small[CNT_TOTAL];
+    if (k < k_min || k > n) return BWTS_E_INTERNAL;
+    char *fl = nullptr;
+    BWTS_TRY(aux_reserve_slot(ctx, 2, (size_t)k * 4, &fl));
+    HIPC(hipMemcpyAsync(fl, sp.keys[1], k * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
+    *d_fstart = (u32 *)fl; *k_out = k;
     return BWTS_OK;
 }
 
@@ -1807,27 +1792,16 @@ static int lyndon_general(bwts_ctx *ctx, const u8 *d_T, u64 n, SortSpace &sp, u3
     BWTS_TRY(suffix_sort_in(ctx, d_T, n, sp, true, &sa, rounds));
     // the sort's key buffers are free again: flags and the compacted starts live there
     u8 *flag = (u8 *)sp.keys[0];
-    u32 *starts_tmp = (u32 *)sp.keys[1];
-    u64 *total = ctx->d_small + CNT_TOTAL;
     {
         SpanGuard g(ctx, BWTS_K_LYNDON, n, 8 * n);
         RankIn in{sp.rank};
         MinFlagOut out{sp.rank, flag};
         BWTS_TRY((device_scan<false, u32>(ctx, n, in, out, OpMin(), 0xffffffffu, sp.scan_temp)));
         FlagIn fin{flag};
-        StartOut sout{flag, starts_tmp, n, total};
+        StartOut sout{flag, (u32 *)sp.keys[1], n, ctx->d_small + CNT_TOTAL};
         BWTS_TRY((device_scan<false, u32>(ctx, n, fin, sout, OpAdd(), 0u, sp.scan_temp)));
     }
-    BWTS_TRY(read_small(ctx, CNT_TOTAL, 1));
-    const u64 k = ctx->h_small[CNT_TOTAL];
-    if (k == 0 || k > n) return BWTS_E_INTERNAL;
-    char *fl = nullptr;
-    BWTS_TRY(aux_reserve_slot(ctx, 2, (size_t)k * 4, &fl));
-    u32 *dst = (u32 *)fl;
-    HIPC(hipMemcpyAsync(dst, starts_tmp, k * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
-    *d_fstart = dst;
-    *k_out = k;
-    return BWTS_OK;
+    return take_factor_list(ctx, n, 1, sp, d_fstart, k_out);
 }
 
 // ------------------------------------------------------------------------------------
@@ -2071,27 +2045,16 @@ __global__ __launch_bounds__(256) void seg_duval_kernel(const u8 *__restrict__ T
 
 static int segment_factors(bwts_ctx *ctx, const u8 *d_T, u64 n, const SegTable &seg, SortSpace &sp, u32 **d_fstart, u64 *k_out)
 {
-    u8 *flag = seg.flag;
-    u32 *starts_tmp = (u32 *)sp.keys[1];
-    u64 *total = ctx->d_small + CNT_TOTAL;
     {
         SpanGuard g(ctx, BWTS_K_LYNDON, n, 2 * n);
-        HIPC(hipMemsetAsync(flag, 0, n, ctx->stream));
-        seg_duval_kernel<<<dim3((unsigned)((seg.count + 3) / 4)), dim3(256), 0, ctx->stream>>>(d_T, seg.d_off, seg.count, flag);
+        HIPC(hipMemsetAsync(seg.flag, 0, n, ctx->stream));
+        seg_duval_kernel<<<dim3((unsigned)((seg.count + 3) / 4)), dim3(256), 0, ctx->stream>>>(d_T, seg.d_off, seg.count, seg.flag);
         HIPC(hipGetLastError());
-        FlagIn fin{flag};
-        StartOut sout{flag, starts_tmp, n, total};
+        FlagIn fin{seg.flag};
+        StartOut sout{seg.flag, (u32 *)sp.keys[1], n, ctx->d_small + CNT_TOTAL};
         BWTS_TRY((device_scan<false, u32>(ctx, n, fin, sout, OpAdd(), 0u, sp.scan_temp)));
     }
-    BWTS_TRY(read_small(ctx, CNT_TOTAL, 1));
-    const u64 k = ctx->h_small[CNT_TOTAL];
-    if (k < seg.count || k > n) return BWTS_E_INTERNAL;
-    char *fl = nullptr;
-    BWTS_TRY(aux_reserve_slot(ctx, 2, (size_t)k * 4, &fl));
-    HIPC(hipMemcpyAsync(fl, starts_tmp, k * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
-    *d_fstart = (u32 *)fl;
-    *k_out = k;
-    return BWTS_OK;
+    return take_factor_list(ctx, n, seg.count, sp, d_fstart, k_out);
 }
 
 static int lyndon_mode(const bwts_ctx *ctx)
@@ -2102,20 +2065,69 @@ static int lyndon_mode(const bwts_ctx *ctx)
     return 0;
 }
 
-// Finds the factors and leaves the cyclic round-0 keys in sp.keys[0] / identity in sp.vals[0].
-static int factors_and_keys(bwts_ctx *ctx, const u8 *d_T, u64 n, SortSpace &sp, Alphabet *al, u32 **d_fstart, u64 *k_out,
+// The arena of a narrow forward call: every array it holds, declared once, on every call -- which path runs (fast or general factors,
+// split or wide keys) is known only after the arena is reserved.  Side slots 2 (factor list of the general path), 3 (previous symbols +
+// carried bytes of a sort on wide keys) and 4 (dense rank array) stay on demand: the headline path does not pay for them.
+struct FwdArena {
+    SortSpace sp;                           // the sort buffers (SortBufs): keys x2, vals x2, tile_hist, scan_temp
+    u64 *cand[2];                           // Lyndon candidates, LYN_CAND_CAP each: the set, its sort's values, the factor starts found
+    u32 *cvals[2], *fast_starts;
+    u64 *tile_min;                          // smallest round-0 key of every scan tile
+    u8  *flag_words[2];                     // round 0's group flags (2 x n/8 bytes) and their word scan (n/8) beside split keys
+    void declare(BlockLayout &L, u64 n)
+    {
+        sp.declare(L, n);
+        L.arrays(LYN_CAND_CAP, &cand[0], &cand[1]); L.arrays(LYN_CAND_CAP, &cvals[0], &cvals[1], &fast_starts);
+        L.array(&tile_min, scan_tiles(n) + 1);
+        L.array(&flag_words[0], n / 4 + 64); L.array(&flag_words[1], n / 8 + 64);
+    }
+};
+size_t forward_arena_bytes(u64 n) { FwdArena A; BlockLayout L; A.declare(L, n); return L.bytes(); }
+// points A's arrays into the arena, which the caller has reserved with forward_arena_bytes(n)
+static int fwd_arena_place(bwts_ctx *ctx, u64 n, FwdArena &A)
+{
+    BlockLayout L;
+    A.declare(L, n);
+    char *base = (char *)arena_alloc(ctx, L.bytes());
+    if (base) L.place(base);
+    return base ? BWTS_OK : BWTS_E_NOMEM;
+}
+
+// Alphabet, split decision, round-0 keys in sp.keys[0] (values: the identity, unwritten).  tile_min (may be null): for the tiles' smallest
+// keys.  count_first: the key builder may count the first packed pass's table into vals[0] -- only where no sort comes before the cyclic one.
+static int round0_keys(bwts_ctx *ctx, const u8 *d_T, u64 n, SortSpace &sp, Alphabet *al, u64 *tile_min, bool count_first)
+{
+    BWTS_TRY(set_alphabet(ctx, false, n, al, d_T, &sp));
+    sp.split_keys = sp.want_split && radix_packed_applicable(ctx, n, al->key_bits);
+    STAGE("histogram + alphabet");
+    sp.first_hist = count_first && sp.split_keys && radix_tile_hist_bytes(n) <= (size_t)n * 4 ? sp.vals[0] : nullptr;
+    BWTS_TRY(launch_keybuild0_seg(ctx, d_T, n, *al, sp.keys[0], tile_min, sp.split_keys, 0, n, nullptr, sp.first_hist));
+    STAGE("keybuild0");
+    return BWTS_OK;
+}
+
+// wrap the keys of positions near their factor's end
+static int cyclic_patch(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, const KeyStore &ks, u32 *first_hist, const u32 *d_fstart, u64 k)
+{
+    const u64 threads = k * (u64)(al.varlen ? 64 : al.msym - 1);
+    if (!threads) return BWTS_OK;
+    SpanGuard g(ctx, BWTS_K_KEYBUILD, threads, 0);
+    if (al.varlen)
+        cyclic_patch_vl_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream>>>(
+            d_T, n, ctx->d_small + SM_VTAB, al.key_bits, d_fstart, k, ks, first_hist);
+    else
+        cyclic_patch_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream>>>(
+            d_T, n, (const u8 *)(ctx->d_small + SM_CODES), al.bits, al.msym, d_fstart, k, ks, first_hist);
+    HIPC(hipGetLastError());
+    return BWTS_OK;
+}
+
+// Finds the factors and leaves the cyclic round-0 keys in sp.keys[0] / identity in sp.vals[0]:
+// factors (segments | fast | general), keys, head fix, patch.
+static int factors_and_keys(bwts_ctx *ctx, const u8 *d_T, u64 n, FwdArena &A, Alphabet *al, u32 **d_fstart, u64 *k_out,
                             u32 *lyndon_rounds, bool hist_ready = false, const SegTable *seg = nullptr)
 {
-    u64 *cand[2];
-    u32 *cvals[2];
-    for (int i = 0; i < 2; i++) {
-        cand[i] = arena_array<u64>(ctx, LYN_CAND_CAP);
-        cvals[i] = arena_array<u32>(ctx, LYN_CAND_CAP);
-        if (!cand[i] || !cvals[i]) return BWTS_E_NOMEM;
-    }
-    u32 *fast_starts = arena_array<u32>(ctx, LYN_CAND_CAP);
-    if (!fast_starts) return BWTS_E_NOMEM;
-
+    SortSpace &sp = A.sp;
     if (!hist_ready) BWTS_TRY(read_histogram(ctx, d_T, n));
     const int mode = seg ? 3 : lyndon_mode(ctx);
     bool done = false;
@@ -2123,64 +2135,44 @@ static int factors_and_keys(bwts_ctx *ctx, const u8 *d_T, u64 n, SortSpace &sp, 
     if (seg) {                  // independent segments: each one's own factors (every segment end is a factor end)
         BWTS_TRY(segment_factors(ctx, d_T, n, *seg, sp, d_fstart, k_out));
         STAGE("segment factors");
-        SampleScratch ss{d_T, {sp.keys[0], sp.keys[1]}, {sp.vals[0], sp.vals[1]}, sp.tile_hist, sp.scan_temp};
-        BWTS_TRY(set_alphabet(ctx, false, n, al, &ss));
-        sp.split_keys = sp.want_split && radix_packed_applicable(ctx, n, al->key_bits);
-        BWTS_TRY(launch_keybuild0(ctx, d_T, n, *al, sp, nullptr, sp.split_keys));
-        done = true;
-    } else if (mode != 2) {
-        u64 *tile_min = arena_array<u64>(ctx, scan_tiles(n) + 1);
-        if (!tile_min) return BWTS_E_NOMEM;
-        SampleScratch ss{d_T, {sp.keys[0], sp.keys[1]}, {sp.vals[0], sp.vals[1]}, sp.tile_hist, sp.scan_temp};
-        BWTS_TRY(set_alphabet(ctx, false, n, al, &ss));
-        sp.split_keys = sp.want_split && radix_packed_applicable(ctx, n, al->key_bits);
-        STAGE("histogram + alphabet");
-        if (sp.split_keys && radix_tile_hist_bytes(n) <= (size_t)n * 4) sp.first_hist = sp.vals[0];
-        BWTS_TRY(launch_keybuild0(ctx, d_T, n, *al, sp, tile_min, sp.split_keys, sp.first_hist));
-        STAGE("keybuild0");
-        BWTS_TRY(lyndon_fast(ctx, d_T, n, *al, sp, tile_min, cand, cvals, fast_starts, k_out, &done));
+    } else if (mode != 2) {     // the fast path reads the keys (and their tile minima): they come first
+        BWTS_TRY(round0_keys(ctx, d_T, n, sp, al, A.tile_min, true));
+        BWTS_TRY(lyndon_fast(ctx, d_T, n, *al, sp, A.tile_min, A.cand, A.cvals, A.fast_starts, k_out, &done));
         STAGE("lyndon_fast");
-        if (done) *d_fstart = fast_starts;
+        if (done) *d_fstart = A.fast_starts;
         else if (mode == 1) return BWTS_E_INTERNAL;
     }
-    if (!done) {
-        sp.first_hist = nullptr;           // (the general path's suffix sort uses vals[0]; its key build below counts nothing)
-        BWTS_TRY(lyndon_general(ctx, d_T, n, sp, d_fstart, k_out, lyndon_rounds));
-        SampleScratch ss{d_T, {sp.keys[0], sp.keys[1]}, {sp.vals[0], sp.vals[1]}, sp.tile_hist, sp.scan_temp};
-        BWTS_TRY(set_alphabet(ctx, false, n, al, &ss));
-        sp.split_keys = sp.want_split && radix_packed_applicable(ctx, n, al->key_bits);
-        BWTS_TRY(launch_keybuild0(ctx, d_T, n, *al, sp, nullptr, sp.split_keys));
-    }
+    // (the general path's suffix sort uses vals[0] and keys[0]: the keys are built after it, and count nothing.  After a fast path that
+    // gave up, split_keys and first_hist stay set through that sort: only a cyclic sort reads them, and round0_keys() then sets both anew)
+    if (!seg && !done) BWTS_TRY(lyndon_general(ctx, d_T, n, sp, d_fstart, k_out, lyndon_rounds));
+    if (!done) BWTS_TRY(round0_keys(ctx, d_T, n, sp, al, nullptr, false));
     const KeyStore ks = key_store_of(sp.keys[0], n, sp.split_keys, al->key_bits);
     if (sp.split_keys) {
         carried_head_fix_kernel<<<dim3((unsigned)((*k_out + 255) / 256)), dim3(256), 0, ctx->stream>>>(d_T, n, *d_fstart, *k_out, ks);
         HIPC(hipGetLastError());
         STAGE("carried_head_fix");
     }
-    // wrap the keys of positions near their factor's end
-    if (al->varlen) {
-        SpanGuard g(ctx, BWTS_K_KEYBUILD, *k_out * 64, 0);
-        const u64 threads = *k_out * 64;
-        cyclic_patch_vl_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream>>>(
-            d_T, n, ctx->d_small + SM_VTAB, al->key_bits, *d_fstart, *k_out, ks, sp.first_hist);
-        HIPC(hipGetLastError());
-    } else if (al->msym > 1) {
-        SpanGuard g(ctx, BWTS_K_KEYBUILD, *k_out * (u64)(al->msym - 1), 0);
-        const u64 threads = *k_out * (u64)(al->msym - 1);
-        cyclic_patch_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream>>>(
-            d_T, n, (const u8 *)(ctx->d_small + SM_CODES), al->bits, al->msym, *d_fstart, *k_out, ks, sp.first_hist);
-        HIPC(hipGetLastError());
-    }
-    return BWTS_OK;
+    return cyclic_patch(ctx, d_T, n, *al, ks, sp.first_hist, *d_fstart, *k_out);
 }
 
+// the test hooks' entries: their caller has reserved forward_arena_bytes(n)
+int suffix_sort_device(bwts_ctx *ctx, const u8 *d_T, u64 n, u32 **d_sa, u32 **d_rank, u32 *rounds)
+{
+    ctx->fwd_sorts_made = 0;
+    BWTS_TRY(read_histogram(ctx, d_T, n));
+    FwdArena A;
+    BWTS_TRY(fwd_arena_place(ctx, n, A));
+    BWTS_TRY(suffix_sort_in(ctx, d_T, n, A.sp, true, d_sa, rounds));
+    *d_rank = A.sp.rank;
+    return BWTS_OK;
+}
 int lyndon_factors_device(bwts_ctx *ctx, const u8 *d_T, u64 n, u32 **d_fstart, u64 *k_out, u32 *rounds)
 {
     ctx->fwd_sorts_made = 0;
-    SortSpace sp;
-    BWTS_TRY(sort_space_alloc(ctx, n, &sp));
+    FwdArena A;
+    BWTS_TRY(fwd_arena_place(ctx, n, A));
     Alphabet al;
-    return factors_and_keys(ctx, d_T, n, sp, &al, d_fstart, k_out, rounds);
+    return factors_and_keys(ctx, d_T, n, A, &al, d_fstart, k_out, rounds);
 }
 
 // ------------------------------------------------------------------------------------
@@ -2299,13 +2291,6 @@ static int partition_by_segment(bwts_ctx *ctx, u64 n, const SegTable &seg, SortS
     return BWTS_OK;
 }
 
-size_t forward_arena_bytes(u64 n)
-{
-    // candidate buffers + sort space + the round-0 flag words (packed passes; a sort on wide keys keeps the previous-symbol array
-    // and two carried-byte buffers in a side block instead, like the general path's factor list and the dense rank array)
-    return 8 * align_up(LYN_CAND_CAP * 8, 256) + sort_space_bytes(n) + 2 * align_up(n / 4 + 64, 256) + align_up(n / 256 + 64, 256) + (1 << 16);
-}
-
 // is the input one byte value repeated?  Eight probes, then -- only if they agree -- the byte histogram.
 int constant_input_probe(bwts_ctx *ctx, const u8 *d_in, u64 n, bool *constant)
 {
@@ -2322,11 +2307,54 @@ int constant_input_probe(bwts_ctx *ctx, const u8 *d_in, u64 n, bool *constant)
     return BWTS_OK;
 }
 
-static int forward_run(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, const SegTable *seg);
-
-int forward_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
+// One byte value only: n factors of one symbol, every rotation equal -- the transform is the identity (mk_bwts_sa.c:172-188 emits
+// each factor's own last byte).
+static int emit_identity(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, hipMemcpyKind kind)
 {
-    return forward_run(ctx, d_in, n, d_out, nullptr);
+    HIPC(hipMemcpyAsync(d_out, d_in, n, kind, ctx->stream));
+    ctx->tm.factors = n; ctx->tm.rounds = 1; ctx->tm.lyndon_rounds = 0; ctx->tm.active_after_round0 = 0;
+    ctx->tm.key_symbols = 1; ctx->tm.key_bits = 1;
+    return BWTS_OK;
+}
+
+// The sort's inputs (SortSpace, section 2).  P[p] = T[cprev(p)] (mk_bwts_sa.c:172-188): a factor's head takes the factor's last byte.
+// With split keys the byte already travels in the keys' c stream and no array is built: P stays null, and the carried-byte
+// buffers only hold the round-0 flag words.  Else side slot 3 holds P and, when the bytes ride on the sort, the two buffers.
+static int carry_setup(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, FwdArena &A, bool carry, const u32 *d_fstart, u64 k, u8 *&P)
+{
+    SortSpace &sp = A.sp;
+    const size_t n1 = align_up((size_t)n, 256);
+    if (!sp.split_keys) {
+        char *pc = nullptr;
+        BWTS_TRY(aux_reserve_slot(ctx, 3, carry ? 3 * n1 : n1, &pc));
+        P = (u8 *)pc;
+        SpanGuard g(ctx, BWTS_K_OTHER, n, 2 * n);
+        u64 blocks = (n / 16 + 255) / 256 + 1; if (blocks > 8192) blocks = 8192;
+        prevsym_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(d_in, n, P);
+        prevsym_fix_kernel<<<dim3((unsigned)((k + 255) / 256)), dim3(256), 0, ctx->stream>>>(d_in, n, d_fstart, k, P);
+        HIPC(hipGetLastError());
+    }
+    if (carry) {
+        sp.carry_src = P;
+        sp.carry_buf[0] = sp.split_keys ? A.flag_words[0] : P + n1;
+        sp.carry_buf[1] = sp.split_keys ? A.flag_words[1] : P + 2 * n1;
+        sp.carry_out = d_out;
+    }
+    return BWTS_OK;
+}
+
+// emission: either it rode on the sort (only the tied elements are patched), or a gather
+static int emit(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, const SortSpace &sp, const u32 *SA, const u8 *P, const u32 *d_fstart, u64 k)
+{
+    if (sp.carry_out && sp.tie_count && !sp.ties_emitted) {
+        SpanGuard g(ctx, BWTS_K_EMIT, sp.tie_count, 6 * sp.tie_count);
+        patch_ties_kernel<<<dim3((unsigned)((sp.tie_count + 255) / 256)), dim3(256), 0, ctx->stream>>>(sp.tie_slots, sp.tie_count, SA, P, d_in, n, d_fstart, k, d_out);
+    } else if (!sp.carry_out) {
+        SpanGuard g(ctx, BWTS_K_EMIT, n, 6 * n);
+        emit_kernel<<<dim3((unsigned)(((n + 7) / 8 + 255) / 256)), dim3(256), 0, ctx->stream>>>(SA, P, n, d_out);
+    }
+    HIPC(hipGetLastError());
+    return BWTS_OK;
 }
 
 static int forward_run(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, const SegTable *seg)
@@ -2340,102 +2368,50 @@ static int forward_run(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, const Se
         // with BWTS_E_RANGE): the identity, as below -- eight probes first, the histogram only if they agree
         bool constant = false;
         BWTS_TRY(constant_input_probe(ctx, d_in, n, &constant));
-        if (constant) {
-            HIPC(hipMemcpyAsync(d_out, d_in, n, hipMemcpyDefault, ctx->stream));
-            ctx->tm.factors = n; ctx->tm.rounds = 1; ctx->tm.lyndon_rounds = 0; ctx->tm.active_after_round0 = 0;
-            ctx->tm.key_symbols = 1; ctx->tm.key_bits = 1;
-            return BWTS_OK;
-        }
+        if (constant) return emit_identity(ctx, d_in, n, d_out, hipMemcpyDefault);
     }
     if (!seg && (n > 0x100000000ull || force_wide)) {
         const int rc = forward_wide_impl(ctx, d_in, n, d_out);
         if (n > 0x100000000ull || force_wide == 2 || rc != BWTS_E_RANGE) return rc;
     }
-    // one byte value only: n factors of one symbol, every rotation equal -- the transform is the identity (mk_bwts_sa.c:172-188 emits
-    // each factor's own last byte).  Taken before anything is allocated: at n = 2^32 this is the input on which every position stays
+    // One byte value only.  Taken before anything is allocated: at n = 2^32 this is the input on which every position stays
     // tied, which the tied-list buffers (32-bit slots) cannot hold.
     BWTS_TRY(read_histogram(ctx, d_in, n));
-    {
-        int present = 0;
-        for (int c = 0; c < 256; c++) present += ctx->h_small[SM_HIST + c] ? 1 : 0;
-        if (present == 1) {
-            HIPC(hipMemcpyAsync(d_out, d_in, n, hipMemcpyDeviceToDevice, ctx->stream));
-            ctx->tm.factors = n; ctx->tm.rounds = 1; ctx->tm.lyndon_rounds = 0; ctx->tm.active_after_round0 = 0;
-            ctx->tm.key_symbols = 1; ctx->tm.key_bits = 1;
-            return BWTS_OK;
-        }
-    }
+    int present = 0;
+    for (int c = 0; c < 256; c++) present += ctx->h_small[SM_HIST + c] ? 1 : 0;
+    if (present == 1) return emit_identity(ctx, d_in, n, d_out, hipMemcpyDeviceToDevice);
     BWTS_TRY(arena_reserve(ctx, forward_arena_bytes(n)));
-    SortSpace sp;
-    BWTS_TRY(sort_space_alloc(ctx, n, &sp));
+    FwdArena A;
+    BWTS_TRY(fwd_arena_place(ctx, n, A));
+    SortSpace &sp = A.sp;
 
     // 1. Lyndon factors + round-0 keys
     Alphabet al;
-    u32 *d_fstart = nullptr;
+    u32 *d_fstart = nullptr, lrounds = 0;
     u64 k = 0;
-    u32 lrounds = 0;
     const char *emit_env = bwts_knob(ctx, "BWTS_EMIT");      // carry (default) | gather
     // (segments: the partition below needs the whole suffix array, which the sort rebuilds for its tied elements only when no byte
     // rides on it -- the gather emission)
     const bool carry = !seg && !(emit_env && !strcmp(emit_env, "gather"));
     sp.want_split = carry;                           // the byte stream rides round 0 => the packed passes may take split keys
-    BWTS_TRY(factors_and_keys(ctx, d_in, n, sp, &al, &d_fstart, &k, &lrounds, true, seg));
-    ctx->tm.factors = k;
-    ctx->tm.lyndon_rounds = lrounds;
-    ctx->tm.key_symbols = (u32)al.msym;
-    ctx->tm.key_bits = (u32)al.key_bits;
-
-    // P[p] = T[cprev(p)] (mk_bwts_sa.c:172-188): a factor's head takes the factor's last byte.  With split keys the
-    // byte already travels in the keys' c stream and no array is built.
+    BWTS_TRY(factors_and_keys(ctx, d_in, n, A, &al, &d_fstart, &k, &lrounds, true, seg));
+    ctx->tm.factors = k; ctx->tm.lyndon_rounds = lrounds; ctx->tm.key_symbols = (u32)al.msym; ctx->tm.key_bits = (u32)al.key_bits;
     u8 *P = nullptr;
-    char *pc = nullptr;                 // side block of a sort on wide keys: P, then the two carried-byte buffers
-    const size_t n1 = align_up((size_t)n, 256);
-    if (!sp.split_keys) {
-        BWTS_TRY(aux_reserve_slot(ctx, 3, carry ? 3 * n1 : n1, &pc));
-        P = (u8 *)pc;
-        SpanGuard g(ctx, BWTS_K_OTHER, n, 2 * n);
-        u64 blocks = (n / 16 + 255) / 256 + 1; if (blocks > 8192) blocks = 8192;
-        prevsym_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(d_in, n, P);
-        prevsym_fix_kernel<<<dim3((unsigned)((k + 255) / 256)), dim3(256), 0, ctx->stream>>>(d_in, n, d_fstart, k, P);
-        HIPC(hipGetLastError());
-    }
-    if (carry) {
-        sp.carry_src = P;
-        if (sp.split_keys) {
-            // the byte travels in the keys' c stream: these two only hold the round-0 flag words (2 x n/8 and n/8 bytes)
-            sp.carry_buf[0] = (u8 *)arena_alloc(ctx, (size_t)n / 4 + 64);
-            sp.carry_buf[1] = (u8 *)arena_alloc(ctx, (size_t)n / 8 + 64);
-        } else {
-            sp.carry_buf[0] = (u8 *)pc + n1;
-            sp.carry_buf[1] = (u8 *)pc + 2 * n1;
-        }
-        sp.carry_out = d_out;
-        if (!sp.carry_buf[0] || !sp.carry_buf[1]) return BWTS_E_NOMEM;
-    }
+    BWTS_TRY(carry_setup(ctx, d_in, n, d_out, A, carry, d_fstart, k, P));
 
     // 2. cyclic sort
-    u32 *SA = nullptr;
-    u32 rounds = 0;
+    u32 *SA = nullptr, rounds = 0;
     u64 active0 = 0;
     BWTS_TRY((doubling_sort<true>(ctx, d_in, n, al, d_fstart, k, sp, false, &SA, &rounds, &active0)));
-    ctx->tm.rounds = rounds;
-    ctx->tm.active_after_round0 = active0;
+    ctx->tm.rounds = rounds; ctx->tm.active_after_round0 = active0;
 
-    // 3. emission: either it rode on the sort (only the tied elements are patched), or a gather
-    if (carry) {
-        if (active0 && !sp.ties_emitted) {
-            SpanGuard g(ctx, BWTS_K_EMIT, active0, 6 * active0);
-            patch_ties_kernel<<<dim3((unsigned)((active0 + 255) / 256)), dim3(256), 0, ctx->stream>>>(sp.tie_slots, active0, SA, P, d_in, n, d_fstart, k, d_out);
-        }
-    } else {
-        SpanGuard g(ctx, BWTS_K_EMIT, n, 6 * n);
-        const u64 octs = (n + 7) / 8;
-        emit_kernel<<<dim3((unsigned)((octs + 255) / 256)), dim3(256), 0, ctx->stream>>>(SA, P, n, d_out);
-    }
-    HIPC(hipGetLastError());
+    // 3. emission, and the segments' bytes to their places
+    BWTS_TRY(emit(ctx, d_in, n, d_out, sp, SA, P, d_fstart, k));
     if (seg) BWTS_TRY(partition_by_segment(ctx, n, *seg, sp, SA, d_out));
     return BWTS_OK;
 }
+
+int forward_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out) { return forward_run(ctx, d_in, n, d_out, nullptr); }
 
 // one wave per segment moves its bytes between the caller's layout (at src_off[s]) and the packed block of the short segments (at off[s])
 __global__ __launch_bounds__(256) void seg_move_kernel(const u8 *__restrict__ from, u8 *__restrict__ to, const u64 *__restrict__ off,

@@ -298,6 +298,20 @@ struct BlockLayout {
     bool place_within(char *base, size_t cap) const { if (bytes() > cap) return false; place(base); return true; }
 };
 
+// The buffers of a pair sort of up to m elements as one group of a layout: key and value ping-pong, the passes' [tile][digit] table
+// (with its chunk table behind it) and the scans' partials
+struct SortBufs {
+    u64  *keys[2];
+    u32  *vals[2], *tile_hist;
+    void *scan_temp;
+    void declare(BlockLayout &L, u64 m)
+    {
+        L.arrays(m, &keys[0], &keys[1]); L.arrays(m, &vals[0], &vals[1]);
+        L.raw(&tile_hist, radix_tile_hist_bytes(m)); L.raw(&scan_temp, scan_temp_bytes(m));
+    }
+    SortPlan plan() const { return sort_plan(keys[0], keys[1], vals[0], vals[1], tile_hist, scan_temp); }
+};
+
 // ---- generators / utilities (gen.hip) ------------------------------------------------
 int generate_device_impl(bwts_ctx *ctx, int kind, u64 seed, u64 n, u8 *d_out);
 int device_equal_impl(bwts_ctx *ctx, const u8 *a, const u8 *b, u64 bytes, int *equal);

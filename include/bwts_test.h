@@ -37,6 +37,9 @@ int bwts_debug_chunk_plan(uint64_t a0, uint64_t a_chunks, uint64_t out[4]);
  * splitter spacing 2^g (g < 0: the spacing the engine picks for n) and mark 0 index log, 1 sentinel, 2 byte map, 3 moments (the
  * default) reserves; out[1] = bytes the host path allocates before the transform runs.  Returns the g used, -1 on a bad argument. */
 int bwts_debug_inverse_arena(uint64_t n, int g, int mark, uint64_t out[2]);
+/* Likewise for the narrow forward (1 <= n <= 2^32): out[0] = bytes of the arena a call declares and the host path allocates ahead.
+ * Returns 0, -1 on a bad argument. */
+int bwts_debug_forward_arena(uint64_t n, uint64_t out[1]);
 /* What the most recent inverse call on the context did, one record of 16 words per attempt of its fallback chain, oldest first
  * (no device work: the engine keeps the records on the host as it goes).  Word 0 g: log2 of the splitter spacing; 1 mark: 0 index
  * log, 1 sentinel, 2 byte map, 3 moments; 2 outcome: 0 done, 1 retry with every element a splitter (node pool overflow, or the unit

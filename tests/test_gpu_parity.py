@@ -62,6 +62,9 @@ def _inputs_small():
     for sigma in (1, 2, 3, 4, 256):
         for n in (1, 2, 7, 64, 65, 199, 2049, 4097):
             out.append(("rand-s%d-n%d" % (sigma, n), rng.integers(0, sigma, size=n, dtype=np.uint8)))
+    # around one 256-thread block, and around 4096 (where a sort's round-0 flag words move between the rank array and the carry buffers)
+    for n in (255, 256, 257, 4095, 4096):
+        out.append(("rand-s4-n%d" % n, rng.integers(0, 4, size=n, dtype=np.uint8)))
     for kind in ("uniform256", "zipf", "dna"):
         for n in (1000, 70001):
             out.append(("%s-%d" % (kind, n), O.generate(kind, n, 3)))
@@ -1271,6 +1274,7 @@ _ALT_ENVS = [
     {"BWTS_BYTEMARK": "1"},                           # inverse marks in a byte map (the n = 2^32 fallback)
     {"BWTS_SPLIT_LOG2": "0"},                         # inverse: every element a splitter (plain pointer jumping)
     {"BWTS_POISON": "1"},                             # every arena / side block filled with 0xA5 before use: nothing may read what nothing wrote
+    {"BWTS_GUARD": "1", "BWTS_POISON": "1"},          # ... and a guard band around every block, checked after every transform: a write past a block is named
     {"BWTS_RESERVE_HELPER": "1"},                     # host path: EVERY arena growth through the helper thread (release on the caller with the stream drained, hipMalloc alone on the helper: DESIGN.md section 9)
 ]
 _alt_pool = {}

@@ -44,14 +44,17 @@ TEST_EXPORTS = [
     "bwts_generate_device", "bwts_device_alloc", "bwts_device_free", "bwts_copy_to_device", "bwts_copy_to_host",
     "bwts_device_equal", "bwts_debug_sort_pairs", "bwts_debug_suffix_array", "bwts_debug_lyndon",
     "bwts_debug_chunk_plan", "bwts_debug_inverse_arena", "bwts_debug_forward_arena", "bwts_debug_inverse_report",
-    "bwts_debug_forward_report",
+    "bwts_debug_forward_report", "bwts_debug_segments_plan", "bwts_debug_segments_report",
 ]
 # bwts_debug_inverse_report: the words of one attempt's record, and what marks, outcomes and forms are called
 INV_REPORT_FIELDS = ["g", "mark", "outcome", "s", "virtual", "node_cap", "nu", "nu2", "ucap_first", "second_collect",
                      "listed_classes", "mom_fallback", "unit_rank", "kc", "kt", "form"]
 INV_MARKS = {0: "log", 1: "sentinel", 2: "bytemap", 3: "moments"}
 INV_OUTCOMES = {0: "DONE", 1: "RETRY_DENSE", 2: "AMBIGUOUS", 3: "NEED_LOG", 255: "ERROR"}
-INV_FORMS = {0: "narrow", 1: "wide", 2: "wide_compact"}
+INV_FORMS = {0: "narrow", 1: "wide", 2: "wide_compact", 3: "segmented"}
+# bwts_debug_segments_plan / bwts_debug_segments_report: the plans by name ("shared_nomem": the shared plan was refused for memory and
+# the lane plan ran), and the route the plan's own segments take
+SEG_PLANS = {0: "lane", 1: "shared", 2: "shared_nomem"}
 # bwts_debug_forward_report: the header words of one sort's record (chunk words from 24 on), the words of a round's record by
 # form, and what forms, reasons and ends are called
 FWD_HEADER_WORDS, FWD_ROUND_WORDS = 48, 12
@@ -154,6 +157,8 @@ def lib():
         L.bwts_debug_forward_arena.argtypes = [u64, ctypes.POINTER(u64)]
         L.bwts_debug_inverse_report.argtypes = [vp, ctypes.POINTER(u64), u64, ctypes.POINTER(u64)]
         L.bwts_debug_forward_report.argtypes = [vp, ctypes.POINTER(u64), u64, ctypes.POINTER(u64)]
+        L.bwts_debug_segments_plan.argtypes = [vp, u64, ctypes.POINTER(u64)]
+        L.bwts_debug_segments_report.argtypes = [vp, ctypes.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -394,6 +399,15 @@ class Context:
             out.append(d)
         return out
 
+    def debug_segments_report(self):
+        """What the most recent inverse_segments call on this context did (bwts_debug_segments_report): plan ("lane", "shared", or
+        "shared_nomem"), big, runs, segments and bytes by route (lane / shared / single), and the largest attempt count."""
+        buf = (ctypes.c_uint64 * 8)()
+        self._check(lib().bwts_debug_segments_report(self._h, buf))
+        d = _segments_words(buf)
+        d["attempts"] = int(buf[7])
+        return d
+
     def debug_forward_report(self):
         """One dict per doubling sort of the most recent forward call on this context (also debug_suffix_array / debug_lyndon), in the
         order they ran: the header (FWD_HEADER_FIELDS; form, keys, no_chunks and end by name, flags as bool), "chunks" (FWD_CHUNK_FIELDS)
@@ -425,6 +439,28 @@ class Context:
                 d["round"].append(rd)
             out.append(d)
         return out
+
+
+def _segments_words(w):
+    """Words 0 .. 6 of bwts_debug_segments_plan / _report as a dict: the plan by name, and segments and bytes by route."""
+    plan = SEG_PLANS[int(w[0])]
+    own = "shared" if plan == "shared" else "lane"
+    d = {"plan": plan, "big": int(w[1]), "runs": int(w[2]), "lane_segments": 0, "lane_bytes": 0, "shared_segments": 0, "shared_bytes": 0,
+         "single_segments": int(w[5]), "single_bytes": int(w[6])}
+    d[own + "_segments"], d[own + "_bytes"] = int(w[3]), int(w[4])
+    return d
+
+
+def debug_segments_plan(lengths):
+    """What inverse_segments would do with segments of these lengths (bwts_debug_segments_plan: host arithmetic, no context, no device):
+    the dict of Context.debug_segments_report without "attempts", plus "arena_bytes"."""
+    ls = np.ascontiguousarray(lengths, dtype=np.uint64)
+    buf = (ctypes.c_uint64 * 8)()
+    if lib().bwts_debug_segments_plan(ls.ctypes.data, ls.size, buf) < 0:
+        raise BwtsError(-1, "bad segment lengths")
+    d = _segments_words(buf)
+    d["arena_bytes"] = int(buf[7])
+    return d
 
 
 def _ptr(x):

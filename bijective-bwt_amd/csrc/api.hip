@@ -706,9 +706,9 @@ static int ensure_io(bwts_ctx *ctx, u64 n, bool pairs)
     return BWTS_OK;
 }
 
-static size_t arena_hint(device_impl_fn fn, u64 n)
+static size_t arena_hint(const bwts_ctx *ctx, device_impl_fn fn, u64 n)
 {
-    if (fn == inverse_segments_impl) return n <= 0x100000000ull ? inverse_segments_arena_bytes(n) : 0;
+    if (fn == inverse_segments_impl) return n <= 0x100000000ull ? inverse_segments_arena_bytes(ctx, n) : 0;
     return n <= 0x100000000ull ? (fn == forward_device_impl || fn == forward_segments_impl ? forward_arena_bytes(n) : inverse_arena_bytes(n)) : 0;
 }
 
@@ -727,7 +727,7 @@ static int run_host(bwts_ctx *ctx, device_impl_fn fn, const uint8_t *in, uint64_
     //    smaller arena first does everything on this thread -- arena_release() drains the stream, then frees -- before staging starts;
     //  * the helper touches no context state: it allocates into a local, this thread installs the block after join().
     // BWTS_RESERVE_HELPER=1 (a test switch) sends EVERY growth through the helper, after the release on this thread.
-    const size_t want = arena_hint(fn, n);
+    const size_t want = arena_hint(ctx, fn, n);
     std::thread reserve;
     void *fresh = nullptr;
     double reserve_ms = 0;
@@ -804,7 +804,7 @@ static int run_batch(bwts_ctx *ctx, device_impl_fn fn, int count, const uint8_t 
     BWTS_TRY(ensure_io(ctx, nmax, true));
     BWTS_TRY(ensure_staging(ctx, ctx->stg[1]));
     BWTS_TRY(ensure_staging(ctx, ctx->stg[2]));
-    BWTS_TRY(arena_reserve(ctx, arena_hint(fn, nmax) > ctx->arena_cap ? arena_hint(fn, nmax) : ctx->arena_cap));
+    BWTS_TRY(arena_reserve(ctx, arena_hint(ctx, fn, nmax) > ctx->arena_cap ? arena_hint(ctx, fn, nmax) : ctx->arena_cap));
     BatchState st;
     double busy[3] = {0, 0, 0};          // time the three stages spent working (BWTS_BATCH_TRACE=1 prints them)
     auto fail = [&st](int rc) { std::lock_guard<std::mutex> lk(st.mu); if (st.error == BWTS_OK) st.error = rc; st.cv.notify_all(); };
@@ -1173,6 +1173,23 @@ extern "C" int bwts_debug_chunk_plan(uint64_t a0, uint64_t a_chunks, uint64_t ou
     const ChunkRecut re = chunk_recut_plan(a0, a_chunks);
     out[0] = chunk_nominal_size(a0); out[1] = chunk_table_capacity(a0); out[2] = re.S; out[3] = re.nc;
     return re.allowed ? 1 : 0;
+}
+
+// what a segmented inverse would do with segments of these lengths (the cost estimate's choice; test switches do not apply): no
+// context, no device
+extern "C" int bwts_debug_segments_plan(const uint64_t *lengths, uint64_t count, uint64_t out[8])
+{
+    if (!lengths || !out || count == 0) return -1;
+    return inverse_segments_plan_words(lengths, count, out);
+}
+
+// what the most recent segmented inverse on this context did: no device, the record is host memory
+extern "C" int bwts_debug_segments_report(bwts_ctx *ctx, uint64_t out[8])
+{
+    static_assert(SEG_REPORT_WORDS == 8, "the record layout bwts_test.h states");
+    if (!ctx || !out) return BWTS_E_ARG;
+    memcpy(out, ctx->seg_report, sizeof ctx->seg_report);
+    return BWTS_OK;
 }
 
 // the narrow inverse's arena as plain arithmetic: no context, no device

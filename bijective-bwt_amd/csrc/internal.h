@@ -53,6 +53,8 @@ struct CopyPool {
 
 #define INV_REPORT_MAX 8         // (the narrow inverse's fallback chain has at most five attempts, the wide one four)
 #define INV_REPORT_WORDS 16
+#define SEG_REPORT_WORDS 8
+enum SegReportWord { SR_PLAN, SR_BIG, SR_RUNS, SR_OWN_SEGS, SR_OWN_BYTES, SR_SINGLE_SEGS, SR_SINGLE_BYTES, SR_ATTEMPTS };
 // the forward's report (bwts_debug_forward_report; include/bwts_test.h names the words): a header, then one record per later round
 #define FWD_REPORT_SORTS 2       // (the suffix sort of the general Lyndon path, then the cyclic sort)
 #define FWD_HEADER_WORDS 48
@@ -141,6 +143,8 @@ struct bwts_ctx {
     u64 *h_seg_off = nullptr;           // pinned staging of the table
     size_t h_seg_cap = 0;
     u8 *d_seg_scratch = nullptr;        // forward: factor-start flags
+    // inverse: what the most recent segmented inverse did (bwts_debug_segments_report; include/bwts_test.h names the words)
+    u64 seg_report[SEG_REPORT_WORDS] = {0};
     size_t d_seg_scratch_cap = 0;
 
     bwts_timings tm;
@@ -250,7 +254,8 @@ int seg_scratch_reserve(bwts_ctx *ctx, size_t bytes, u8 **p);     // a device bl
 int seg_upload_extra(bwts_ctx *ctx, const u64 *words, u64 count, u64 **d_words);   // a second table, behind the segment table
 int forward_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
 int inverse_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
-size_t inverse_segments_arena_bytes(u64 n);
+size_t inverse_segments_arena_bytes(const bwts_ctx *ctx, u64 n);   // for the context's current segment table, by the plan the call will take
+int inverse_segments_plan_words(const u64 *lengths, u64 count, u64 out[8]);   // bwts_debug_segments_plan: no context, no device
 int inverse_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
 size_t forward_arena_bytes(u64 n);
 // the inverse's arena as plain arithmetic (the bwts_debug_inverse_arena test hook asks them too): the splitter spacing the narrow

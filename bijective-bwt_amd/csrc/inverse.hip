@@ -202,18 +202,23 @@ __device__ __forceinline__ u32 symbol_of(const u64 *Ctab, u32 y)
 #define MOM_LOG2_SMALL 10                    // classes: 2^10 up to n = 2^30 (20 KB of LDS), 2^12 above (80 KB: a class stays at 2^20 elements)
 #define MOM_LOG2_LARGE 12
 #define MOM_MAX_BUCKETS (1u << MOM_LOG2_LARGE)
-template <int MARK, int SBW = 16 /* registers of recorded symbols per store: 16 = 64-byte blocks, 4 = 16-byte ones */>
-__global__ __launch_bounds__(256) void walk_record_kernel(u32 *__restrict__ LF, u8 *__restrict__ marks, u32 *__restrict__ idxlog, u64 s, u64 node_cap, int g, u32 slot,
-                                                          const u64 *__restrict__ Cg, u8 *__restrict__ seg,
-                                                          uint4 *__restrict__ noderec /* x next node, y segment length, z smallest element, w its offset */,
-                                                          unsigned long long *__restrict__ ticket,
-                                                          unsigned long long *__restrict__ vcount,
-                                                          unsigned long long *__restrict__ overflow,
-                                                          unsigned long long *__restrict__ chunk_ctr, u32 *__restrict__ chunk_fill, u64 log_chunks,
-                                                          u32 nbuckets, u32 *__restrict__ bucket_seen,
-                                                          int mom_shift = 0, unsigned long long *__restrict__ mom = nullptr /* [3][2^mom_shift]: counts, sums, sums of squares */)
+// SYM: where the symbol of x comes from.  SYM_FROM_C: B[x] is the symbol whose C-range holds LF[x] (one BWT, one C table: nothing but LF is
+// read).  SYM_FROM_INPUT: B[x] itself, loaded beside LF[x] -- the shared pass over independent segments, whose LF is built per segment
+// with one C table each (inv_build_lf), so no single table names the symbol.
+#define SYM_FROM_C 0
+#define SYM_FROM_INPUT 1
+template <int MARK, int SBW /* registers of recorded symbols per store: 16 = 64-byte blocks, 4 = 16-byte ones */, int SYM>
+__device__ __forceinline__ void walk_record_body(u32 *LF, u8 *marks, u32 *idxlog, u64 s, u64 node_cap, int g, u32 slot,
+                                                 const u64 *Cg, const u8 *Bsym, u8 *seg,
+                                                 uint4 *noderec /* x next node, y segment length, z smallest element, w its offset */,
+                                                 unsigned long long *ticket,
+                                                 unsigned long long *vcount,
+                                                 unsigned long long *overflow,
+                                                 unsigned long long *chunk_ctr, u32 *chunk_fill, u64 log_chunks,
+                                                 u32 nbuckets, u32 *bucket_seen,
+                                                 int mom_shift, unsigned long long *mom /* [3][2^mom_shift]: counts, sums, sums of squares */)
 {
-    __shared__ u64 Ctab[257];
+    __shared__ u64 Ctab[SYM == SYM_FROM_C ? 257 : 1];
     extern __shared__ __attribute__((aligned(16))) unsigned long long walk_mom_sm[];     // MARK_MOMENTS: 2^mom_shift sums, sums of squares, counts
     const u32 mom_classes = MARK == MARK_MOMENTS ? 1u << mom_shift : 0u;
     unsigned long long *msum = walk_mom_sm, *msq = walk_mom_sm + mom_classes;
@@ -227,7 +232,7 @@ __global__ __launch_bounds__(256) void walk_record_kernel(u32 *__restrict__ LF, 
     // its indices counted holds nothing unvisited, and its log entries need not be looked at again.
     __shared__ u32 bseen[MARK == MARK_LOG ? IDX_MAX_BUCKETS : 1];
     if (MARK == MARK_LOG) for (u32 b = threadIdx.x; b < nbuckets; b += 256) bseen[b] = 0;
-    for (int i = threadIdx.x; i < 257; i += 256) Ctab[i] = Cg[i];
+    if (SYM == SYM_FROM_C) for (int i = threadIdx.x; i < 257; i += 256) Ctab[i] = Cg[i];
     __syncthreads();
     const u32 gmask = (1u << g) - 1u;
     bool have = false, done = false;
@@ -304,10 +309,11 @@ __global__ __launch_bounds__(256) void walk_record_kernel(u32 *__restrict__ LF, 
         }
         if (have) {
             const u32 y = LF[x];
+            const u32 bx = SYM == SYM_FROM_INPUT ? (u32)Bsym[x] : 0u;  // (depends on x alone: in flight together with LF[x])
             if (MARK == MARK_BYTEMAP) marks[x] = 1;
             else if (MARK == MARK_SENTINEL) LF[x] = LF_VISITED;       // the entry is not needed again
             {
-                const u32 sh = symbol_of(Ctab, y) << (8 * (len & 3u));
+                const u32 sh = (SYM == SYM_FROM_INPUT ? bx : symbol_of(Ctab, y)) << (8 * (len & 3u));
                 const u32 w = (len >> 2) & (u32)(SBW - 1);
 #pragma unroll
                 for (int q = 0; q < SBW; q++) sb[q] |= w == (u32)q ? sh : 0u;
@@ -361,6 +367,33 @@ __global__ __launch_bounds__(256) void walk_record_kernel(u32 *__restrict__ LF, 
 #ifdef WALK_PROFILE
     if (lane_id() == 0) { atomicMax(&prof[2], (unsigned long long)wall_clock64()); atomicMin(&prof[4], (unsigned long long)wall_clock64()); }
 #endif
+}
+template <int MARK, int SBW = 16>
+__global__ __launch_bounds__(256) void walk_record_kernel(u32 *__restrict__ LF, u8 *__restrict__ marks, u32 *__restrict__ idxlog, u64 s, u64 node_cap, int g, u32 slot,
+                                                          const u64 *__restrict__ Cg, u8 *__restrict__ seg, uint4 *__restrict__ noderec,
+                                                          unsigned long long *__restrict__ ticket,
+                                                          unsigned long long *__restrict__ vcount,
+                                                          unsigned long long *__restrict__ overflow,
+                                                          unsigned long long *__restrict__ chunk_ctr, u32 *__restrict__ chunk_fill, u64 log_chunks,
+                                                          u32 nbuckets, u32 *__restrict__ bucket_seen,
+                                                          int mom_shift = 0, unsigned long long *__restrict__ mom = nullptr)
+{
+    walk_record_body<MARK, SBW, SYM_FROM_C>(LF, marks, idxlog, s, node_cap, g, slot, Cg, nullptr, seg, noderec, ticket, vcount, overflow, chunk_ctr, chunk_fill, log_chunks,
+                                            nbuckets, bucket_seen, mom_shift, mom);
+}
+// the same walk over the shared pass's LF (cycles that each lie inside one segment): symbols from the input
+template <int MARK, int SBW = 16>
+__global__ __launch_bounds__(256) void walk_record_seg_kernel(u32 *__restrict__ LF, u8 *__restrict__ marks, u32 *__restrict__ idxlog, u64 s, u64 node_cap, int g, u32 slot,
+                                                              const u8 *__restrict__ B, u8 *__restrict__ seg, uint4 *__restrict__ noderec,
+                                                              unsigned long long *__restrict__ ticket,
+                                                              unsigned long long *__restrict__ vcount,
+                                                              unsigned long long *__restrict__ overflow,
+                                                              unsigned long long *__restrict__ chunk_ctr, u32 *__restrict__ chunk_fill, u64 log_chunks,
+                                                              u32 nbuckets, u32 *__restrict__ bucket_seen,
+                                                              int mom_shift = 0, unsigned long long *__restrict__ mom = nullptr)
+{
+    walk_record_body<MARK, SBW, SYM_FROM_INPUT>(LF, marks, idxlog, s, node_cap, g, slot, nullptr, B, seg, noderec, ticket, vcount, overflow, chunk_ctr, chunk_fill, log_chunks,
+                                                nbuckets, bucket_seen, mom_shift, mom);
 }
 
 // out[end_c - t] = B[LF^t(min_c)] (unbwts.c:73-82): node v's recorded symbols go to out[opos - i], wrapping to the
@@ -910,22 +943,50 @@ struct CycleEndOut {
     }
 };
 
+// The shared pass over a run of independent segments (offsets off[0 .. count], run-relative once `base` is taken off): a cycle lies
+// inside one segment, so the cycles of earlier segments are ordered first and their lengths sum to that segment's start.  The cycle
+// with smallest element m ends at  off[s + 1] - 1 - (used - off[s]),  s = the segment that holds m.
+struct SegCycleEndOut {
+    CycleList cl; const u32 *order; const u64 *off; u64 count, base; u32 *end_by_leader; u32 *end_of_tiny; u64 *total;
+    __device__ __forceinline__ void operator()(u64 j, u32 used) const
+    {
+        const u32 i = order[j];
+        const u64 m = (u64)cl.minelem(i) + base;
+        u64 lo = 0, hi = count;                         // largest s with off[s] <= m  (off[0] = base <= m < off[count])
+        while (hi - lo > 1) { const u64 mid = (lo + hi) >> 1; if (off[mid] <= m) lo = mid; else hi = mid; }
+        const u32 end = (u32)(off[lo + 1] - base) - 1u - (used - (u32)(off[lo] - base));     // (mod 2^32, like the whole-input form)
+        if (i < cl.kt) end_of_tiny[i] = end;
+        else end_by_leader[cl.recs[i - cl.kt].leader] = end;
+        if (j + 1 == cl.kt + cl.kc) *total = (u64)used + cl.len(i);
+    }
+};
+
 // out[end - t] = B[LF^t(min)] for a cycle without a splitter: unbwts.c:73-82, one lane per cycle
-__global__ __launch_bounds__(256) void tiny_place_kernel(const uint2 *__restrict__ tiny, u64 kt, const u32 *__restrict__ end_of_tiny,
-                                                         const u32 *__restrict__ LF, const u64 *__restrict__ Cg, u8 *__restrict__ out)
+template <int SYM>
+__device__ __forceinline__ void tiny_place_body(const uint2 *tiny, u64 kt, const u32 *end_of_tiny, const u32 *LF, const u64 *Ctab /* in LDS */, const u8 *Bsym, u8 *out)
 {
-    __shared__ u64 Ctab[257];
-    for (int i = threadIdx.x; i < 257; i += 256) Ctab[i] = Cg[i];
-    __syncthreads();
     const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
     if (i >= kt) return;
     const uint2 c = tiny[i];
     u32 x = c.x, pos = end_of_tiny[i];
     for (u32 t = 0; t < c.y; t++) {
         const u32 y = LF[x];
-        out[pos--] = (u8)symbol_of(Ctab, y);
+        out[pos--] = SYM == SYM_FROM_INPUT ? Bsym[x] : (u8)symbol_of(Ctab, y);
         x = y;
     }
+}
+__global__ __launch_bounds__(256) void tiny_place_kernel(const uint2 *__restrict__ tiny, u64 kt, const u32 *__restrict__ end_of_tiny,
+                                                         const u32 *__restrict__ LF, const u64 *__restrict__ Cg, u8 *__restrict__ out)
+{
+    __shared__ u64 Ctab[257];
+    for (int i = threadIdx.x; i < 257; i += 256) Ctab[i] = Cg[i];
+    __syncthreads();
+    tiny_place_body<SYM_FROM_C>(tiny, kt, end_of_tiny, LF, Ctab, nullptr, out);
+}
+__global__ __launch_bounds__(256) void tiny_place_seg_kernel(const uint2 *__restrict__ tiny, u64 kt, const u32 *__restrict__ end_of_tiny,
+                                                             const u32 *__restrict__ LF, const u8 *__restrict__ B, u8 *__restrict__ out)
+{
+    tiny_place_body<SYM_FROM_INPUT>(tiny, kt, end_of_tiny, LF, nullptr, B, out);
 }
 
 // ------------------------------------------------------------------------------------
@@ -978,7 +1039,7 @@ enum InvOutcome { INV_DONE,
 // hold on the host anyway, stored as they become known.  An attempt that ends with an error code keeps IR_ERROR as its outcome.
 enum InvReportWord { IR_G, IR_MARK, IR_OUTCOME, IR_S, IR_VIRTUAL, IR_NODE_CAP, IR_NU, IR_NU2, IR_UCAP_FIRST, IR_SECOND_COLLECT,
                      IR_LISTED, IR_MOM_FALLBACK, IR_UNIT_RANK, IR_KC, IR_KT, IR_FORM };
-enum InvReportForm { IR_FORM_NARROW, IR_FORM_WIDE, IR_FORM_WIDE_COMPACT };
+enum InvReportForm { IR_FORM_NARROW, IR_FORM_WIDE, IR_FORM_WIDE_COMPACT, IR_FORM_NARROW_SEGMENTED };
 #define IR_ERROR 255
 static_assert(IR_FORM < INV_REPORT_WORDS, "the record's words");
 static u64 *inv_report_open(bwts_ctx *ctx /* null: sizes only */, u64 *spill)
@@ -1043,9 +1104,15 @@ struct LogTables {          // MARK_LOG: the index log in chunks, the indices of
         L.array(&bucket_fill, (u64)IDX_MAX_BUCKETS * IDX_FILL_STRIDE); L.array(&bucket_seen, 2 * IDX_MAX_BUCKETS);
     }
 };
+// A run of consecutive segments that one shared pass inverts: its slice off[0 .. count] of the call's device offset table (absolute
+// offsets; off[0] = base, the run's first byte, which the pass's indices are relative to)
+struct InvSegs { const u64 *off; u64 count, base; };
+#define SEG_MOMENTS_MAX_SEGMENTS 128    // a pass over more segments than this looks for its unreached elements with the index log first
 // One attempt with splitter spacing 2^g and one way of marking: its sizes (plain arithmetic), its arrays, what one stage hands to the next
 struct InvRun {
     u64 n, G, s, tiles, node_cap, l2cap, log_chunks, mom_classes;
+    const InvSegs *segs;                                        // the shared pass over segments, or null: the input is one BWT
+    const u8 *B = nullptr;                                      // ... whose symbols the walk and the placement read from the input
     int g, mark, mom_shift; u32 slot, nbuckets; unsigned wblocks;
     LfTables lf; NodeTables nd; Level2Tables l2; MomentTables mt; LogTables lg;
     u8 *marks = nullptr; u64 *dC = nullptr;                     // the byte map (MARK_BYTEMAP); symbol boundaries
@@ -1055,7 +1122,7 @@ struct InvRun {
     bool unit_rank = false;                                     // the unit-node route: its block, taken from the device for the call
     UnitRank unit; u32 *uend = nullptr, *uleader = nullptr; ScopedDeviceBlock ub;
     u64 rep_spill[INV_REPORT_WORDS], *rep;                      // this attempt's record
-    InvRun(bwts_ctx *ctx /* null: sizes only */, u64 n_, int g_, int mark_) : n(n_), g(g_), mark(mark_), ub(ctx)
+    InvRun(bwts_ctx *ctx /* null: sizes only */, u64 n_, int g_, int mark_, const InvSegs *segs_ = nullptr) : n(n_), segs(segs_), g(g_), mark(mark_), ub(ctx)
     {
         u64 walker_cap = 524288;                                // lanes of the walk
         if (const char *e = ctx ? bwts_knob(ctx, "BWTS_WALKERS") : nullptr) { const long v = atol(e); if (v >= 256 && v <= (1 << 22)) walker_cap = (u64)v; }
@@ -1069,7 +1136,7 @@ struct InvRun {
         log_chunks = n / (IDX_CHUNK - 64) + (u64)wblocks * 4 + 2;     // a closed chunk wastes < 64 entries; every wave may leave one open
         nbuckets = (u32)((n + (1ull << IDX_RANGE_LOG2) - 1) >> IDX_RANGE_LOG2);
         rep = inv_report_open(ctx, rep_spill);
-        rep[IR_G] = (u64)g; rep[IR_MARK] = (u64)mark; rep[IR_S] = s; rep[IR_NODE_CAP] = node_cap; rep[IR_FORM] = IR_FORM_NARROW;
+        rep[IR_G] = (u64)g; rep[IR_MARK] = (u64)mark; rep[IR_S] = s; rep[IR_NODE_CAP] = node_cap; rep[IR_FORM] = segs ? IR_FORM_NARROW_SEGMENTED : IR_FORM_NARROW;
     }
     void declare(BlockLayout &L)            // the mark-specific buffers only for the mark that runs
     {
@@ -1085,11 +1152,17 @@ size_t inverse_attempt_bytes(u64 n, int g, int mark) { InvRun r(nullptr, n, g, m
 // What the host path's helper thread allocates before the transform runs: the default attempt at the closest splitter spacing the
 // narrow form picks (g = 4, slot 64, moments) -- the node tables shrink faster with g than the records grow, so it bounds every g >= 4.
 size_t inverse_arena_bytes(u64 n) { return inverse_attempt_bytes(n, 4, MARK_MOMENTS); }
-// stable LF map (unbwts.c:50-52) and C; the byte map starts clear
+__global__ __launch_bounds__(256) void seg_lf_shared_kernel(const u8 *__restrict__ B, const u64 *__restrict__ seg_off, u64 count, u64 run_base, u32 *__restrict__ LF);   // (with seg_lf_kernel, below)
+// stable LF map (unbwts.c:50-52) and C; the byte map starts clear.  Over segments: the stable LF map of every segment, as indices of the run; no C
 static int inv_build_lf(bwts_ctx *ctx, InvRun &r, const u8 *d_in)
 {
+    r.B = d_in;
     if (r.mark == MARK_BYTEMAP) HIPC(hipMemsetAsync(r.marks, 0, r.n, ctx->stream));
     SpanGuard sg(ctx, BWTS_K_LF_BUILD, r.n, 5 * r.n);
+    if (r.segs) {
+        seg_lf_shared_kernel<<<dim3((unsigned)((r.segs->count + 3) / 4)), dim3(256), 0, ctx->stream>>>(d_in, r.segs->off, r.segs->count, r.segs->base, r.lf.LF);
+        return launched(ctx);
+    }
     lf_hist_kernel<<<dim3((unsigned)r.tiles), dim3(LF_THREADS), 0, ctx->stream>>>(d_in, r.n, r.lf.tile_hist);
     BWTS_TRY(radix_column_scan(ctx, r.lf.tile_hist, r.tiles, r.lf.scan_temp));
     // the scanned table's first row is C itself: no separate histogram sweep, no host round trip before the walk
@@ -1100,6 +1173,13 @@ static int inv_build_lf(bwts_ctx *ctx, InvRun &r, const u8 *d_in)
 template <int MARK> static int launch_walk(bwts_ctx *ctx, const InvRun &r)
 {
     constexpr bool mom = MARK == MARK_MOMENTS;
+    if (r.segs) {
+        if (mom) BWTS_TRY(ensure_dyn_lds(ctx, (const void *)walk_record_seg_kernel<MARK>, (size_t)MOM_MAX_BUCKETS * 20));
+        walk_record_seg_kernel<MARK><<<dim3(r.wblocks), dim3(256), mom ? (size_t)r.mom_classes * 20 : 0, ctx->stream>>>(
+            r.lf.LF, r.marks, r.lg.idxlog, r.s, r.node_cap, r.g, r.slot, r.B, r.nd.seg, r.nd.noderec, inv_counter(ctx, IC_TICKET), inv_counter(ctx, IC_VIRTUAL),
+            inv_counter(ctx, IC_OVERFLOW), inv_counter(ctx, IC_LOG_CHUNKS), r.lg.chunk_fill, r.log_chunks, r.nbuckets, r.lg.bucket_seen, mom ? r.mom_shift : 0, r.mt.mom);
+        return launched(ctx);
+    }
     if (mom) BWTS_TRY(ensure_dyn_lds(ctx, (const void *)walk_record_kernel<MARK>, (size_t)MOM_MAX_BUCKETS * 20));
     walk_record_kernel<MARK><<<dim3(r.wblocks), dim3(256), mom ? (size_t)r.mom_classes * 20 : 0, ctx->stream>>>(
         r.lf.LF, r.marks, r.lg.idxlog, r.s, r.node_cap, r.g, r.slot, r.dC, r.nd.seg, r.nd.noderec, inv_counter(ctx, IC_TICKET), inv_counter(ctx, IC_VIRTUAL),
@@ -1256,8 +1336,14 @@ static int inv_order_cycles(bwts_ctx *ctx, InvRun &r)
     int res = 0, kbits = bit_length(r.n - 1);
     BWTS_TRY(radix_sort_pairs(ctx, cp, kall, kbits < 1 ? 1 : kbits, &res));
     CycleLenIn lin{cl, cp.vals[res]};
-    CycleEndOut lout{cl, cp.vals[res], (u32)(r.n - 1), r.l2.end_by_leader, r.end_of_tiny, ctx->d_small + SMI_COUNTERS + IC_LENGTH_SUM};
-    BWTS_TRY((device_scan<false, u32>(ctx, kall, lin, lout, OpAdd(), 0u, cp.scan_temp)));
+    u64 *total = ctx->d_small + SMI_COUNTERS + IC_LENGTH_SUM;
+    if (r.segs) {
+        SegCycleEndOut lout{cl, cp.vals[res], r.segs->off, r.segs->count, r.segs->base, r.l2.end_by_leader, r.end_of_tiny, total};
+        BWTS_TRY((device_scan<false, u32>(ctx, kall, lin, lout, OpAdd(), 0u, cp.scan_temp)));
+    } else {
+        CycleEndOut lout{cl, cp.vals[res], (u32)(r.n - 1), r.l2.end_by_leader, r.end_of_tiny, total};
+        BWTS_TRY((device_scan<false, u32>(ctx, kall, lin, lout, OpAdd(), 0u, cp.scan_temp)));
+    }
     if (r.unit_rank) unit_ends_kernel<<<dim3(grid1(r.kt)), dim3(256), 0, ctx->stream>>>(r.uleader, r.end_of_tiny, r.kt, r.uend);
     lr_place2_kernel<<<dim3(grid1(r.s2all)), dim3(256), 0, ctx->stream>>>(r.s2all, r.l2.lrmin[r.cur], r.l2.lrsum[r.sc], r.l2.dist, r.l2.min_dist, r.l2.end_by_leader, r.l2.place2);
     lr2_distribute_kernel<<<dim3(grid1(r.s2all)), dim3(256), 0, ctx->stream>>>(r.nd.noderec, r.s2, r.s2all, r.nd.U, r.l2.place2, r.nd.opos, r.nd.wrap, r.nd.clen);
@@ -1272,9 +1358,13 @@ static int inv_place(bwts_ctx *ctx, InvRun &r, u8 *d_out, InvOutcome *out)
         const u64 threads = r.s_all << tpn_log2;
         place_segments_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream>>>(r.nd.seg, r.s_all, r.slot, tpn_log2, r.nd.noderec, r.nd.opos, r.nd.wrap,
                                                                                                       r.nd.clen, d_out);
-        if (r.unit_rank)
+        if (r.unit_rank && r.segs)
+            wi_unit_place_seg_kernel<u32><<<dim3(grid1(r.nu)), dim3(256), 0, ctx->stream>>>(r.nu, r.unit.rk.min_of(), r.unit.rk.sum_of(), r.unit.dist, r.unit.min_dist, r.uend,
+                                                                                            r.uidx, r.B, d_out);
+        else if (r.unit_rank)
             wi_unit_place_kernel<u32><<<dim3(grid1(r.nu)), dim3(256), 0, ctx->stream>>>(r.nu, r.unit.rk.min_of(), r.unit.rk.sum_of(), r.unit.dist, r.unit.min_dist, r.uend, r.ulf,
                                                                                         r.dC, d_out);
+        else if (r.kt && r.segs) tiny_place_seg_kernel<<<dim3(grid1(r.kt)), dim3(256), 0, ctx->stream>>>(r.tiny, r.kt, r.end_of_tiny, r.lf.LF, r.B, d_out);
         else if (r.kt) tiny_place_kernel<<<dim3(grid1(r.kt)), dim3(256), 0, ctx->stream>>>(r.tiny, r.kt, r.end_of_tiny, r.lf.LF, r.dC, d_out);
         HIPC(hipGetLastError());
     }
@@ -1299,13 +1389,48 @@ static int inverse_stages(bwts_ctx *ctx, InvRun &r, const u8 *d_in, u8 *d_out, I
     BWTS_TRY(inv_order_cycles(ctx, r));
     return inv_place(ctx, r, d_out, out);
 }
-static int inverse_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, int g, int mark, InvOutcome *out)
+static int inverse_attempt(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, int g, int mark, const InvSegs *segs, InvOutcome *out)
 {
-    InvRun r(ctx, n, g, mark);
+    InvRun r(ctx, n, g, mark, segs);
     *out = INV_DONE;
     BWTS_TRY(inverse_stages(ctx, r, d_in, d_out, out));
     r.rep[IR_OUTCOME] = (u64)*out;
     return BWTS_OK;
+}
+
+// The narrow form's chain of attempts over [0, n), n <= 2^32: one BWT (segs null), or the shared pass over a run of segments.  The caller
+// has set tm.attempts = 1 and cleared the attempt records.
+static int inverse_narrow_chain(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, const InvSegs *segs)
+{
+    // how the unreached elements are found: per-class moments (default), the index log, or the two mark forms
+    // (BWTS_INV_MARK=log|sentinel|bytemap, BWTS_BYTEMARK=1: tests, and the fallback chain below)
+    // (A shared pass over many segments starts with the index log: every segment of a transform ends in short Lyndon factors, about 15
+    // unreached elements each, and beyond a few thousand of them the moments' classes all miss more than the arithmetic names.  Measured,
+    // profiles/segments_shared_inverse_1gib.txt: with the moments first, passes over 8 .. 128 segments of 64 KiB and of 1 MiB took one
+    // attempt, 256 x 1 MiB and every 1 GiB set (1 024 to 262 144 segments) ran the walk twice.)
+    int mark = segs && segs->count > SEG_MOMENTS_MAX_SEGMENTS ? MARK_LOG : MARK_MOMENTS;
+    const char *me = bwts_knob(ctx, "BWTS_INV_MARK");
+    if (me && !strcmp(me, "moments")) mark = MARK_MOMENTS;
+    if (me && !strcmp(me, "log")) mark = MARK_LOG;
+    if (me && !strcmp(me, "sentinel")) mark = MARK_SENTINEL;
+    if ((me && !strcmp(me, "bytemap")) || bwts_knob(ctx, "BWTS_BYTEMARK")) mark = MARK_BYTEMAP;
+    // The fallback chain: every outcome but INV_DONE names the next (g, mark).  Worst case the walk runs five times (moments -> index
+    // log -> byte map at n = 2^32 -> every element a splitter, with sentinel and then byte-map marks); natural inputs take one.
+    // bwts_timings.attempts says how many it was.
+    int g = splitter_log2(ctx, n);
+    bool dense = false;
+    for (;; ctx->tm.attempts++) {
+        InvOutcome out;
+        BWTS_TRY(inverse_attempt(ctx, d_in, n, d_out, g, mark, segs, &out));
+        if (out == INV_DONE) return BWTS_OK;
+        if (out == INV_NEED_LOG) mark = MARK_LOG;           // many unreached elements (low-entropy input): the walk again, logging every index it visits
+        else if (out == INV_AMBIGUOUS) mark = MARK_BYTEMAP; // sentinel marks only
+        else {                                              // INV_RETRY_DENSE, once: on the simplest marks
+            if (dense) return BWTS_E_INTERNAL;
+            dense = true; g = 0;
+            if (mark == MARK_LOG || mark == MARK_MOMENTS) mark = MARK_SENTINEL;
+        }
+    }
 }
 
 int inverse_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
@@ -1327,30 +1452,7 @@ int inverse_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
         }
     }
     if (n > 0x100000000ull || force_wide) return inverse_wide_impl(ctx, d_in, n, d_out);
-    // how the unreached elements are found: per-class moments (default), the index log, or the two mark forms
-    // (BWTS_INV_MARK=log|sentinel|bytemap, BWTS_BYTEMARK=1: tests, and the fallback chain below)
-    int mark = MARK_MOMENTS;
-    const char *me = bwts_knob(ctx, "BWTS_INV_MARK");
-    if (me && !strcmp(me, "log")) mark = MARK_LOG;
-    if (me && !strcmp(me, "sentinel")) mark = MARK_SENTINEL;
-    if ((me && !strcmp(me, "bytemap")) || bwts_knob(ctx, "BWTS_BYTEMARK")) mark = MARK_BYTEMAP;
-    // The fallback chain: every outcome but INV_DONE names the next (g, mark).  Worst case the walk runs five times (moments -> index
-    // log -> byte map at n = 2^32 -> every element a splitter, with sentinel and then byte-map marks); natural inputs take one.
-    // bwts_timings.attempts says how many it was.
-    int g = splitter_log2(ctx, n);
-    bool dense = false;
-    for (;; ctx->tm.attempts++) {
-        InvOutcome out;
-        BWTS_TRY(inverse_attempt(ctx, d_in, n, d_out, g, mark, &out));
-        if (out == INV_DONE) return BWTS_OK;
-        if (out == INV_NEED_LOG) mark = MARK_LOG;           // many unreached elements (low-entropy input): the walk again, logging every index it visits
-        else if (out == INV_AMBIGUOUS) mark = MARK_BYTEMAP; // sentinel marks only
-        else {                                              // INV_RETRY_DENSE, once: on the simplest marks
-            if (dense) return BWTS_E_INTERNAL;
-            dense = true; g = 0;
-            if (mark == MARK_LOG || mark == MARK_MOMENTS) mark = MARK_SENTINEL;
-        }
-    }
+    return inverse_narrow_chain(ctx, d_in, n, d_out, nullptr);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1360,16 +1462,10 @@ int inverse_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
 // segment: byte histogram in LDS, exclusive scan, then 64 positions per step in order -- a lane's rank among the lanes holding the same
 // byte comes from eight ballots, and the last such lane advances the byte's counter.
 #define SEG_INV_VISITED 0xffffffffu
-__global__ __launch_bounds__(256) void seg_lf_kernel(const u8 *__restrict__ B, const u64 *__restrict__ seg_off, u64 count, u64 big, u32 *__restrict__ LF)
+// one wave, one segment S[0 .. L): LFseg[p] = add + C[S[p]] + occ(S[p], p); cnt: the wave's 256 counters in LDS
+__device__ __forceinline__ void seg_lf_wave(const u8 *__restrict__ S, u64 L, u32 add, u32 *__restrict__ LFseg, u32 *cnt)
 {
-    __shared__ u32 cnt_all[4][256];
-    const u64 s = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (s >= count) return;
-    const u64 base = seg_off[s], L = seg_off[s + 1] - base;
-    if (L >= big) return;
     const int lane = lane_id();
-    u32 *cnt = cnt_all[threadIdx.x >> 6];
-    const u8 *S = B + base;
     for (int c = lane; c < 256; c += 64) cnt[c] = 0;
     __builtin_amdgcn_wave_barrier();
     for (u64 p = (u64)lane; p < L; p += 64) atomicAdd(&cnt[S[p]], 1u);
@@ -1383,23 +1479,50 @@ __global__ __launch_bounds__(256) void seg_lf_kernel(const u8 *__restrict__ B, c
         cnt[4 * lane] = ex; cnt[4 * lane + 1] = ex + v0; cnt[4 * lane + 2] = ex + v0 + v1; cnt[4 * lane + 3] = ex + v0 + v1 + v2;
     }
     __builtin_amdgcn_wave_barrier();
-    for (u64 p0 = 0; p0 < L; p0 += 64) {
-        const u64 p = p0 + (u64)lane;
-        const bool act = p < L;
-        const u32 b = act ? (u32)S[p] : 0u;
-        u64 match = __ballot(act);
+    // (the steps are serial -- a step's ranks start from the counters the one before left -- but their bytes are not: four steps' loads
+    // are in flight together, else every step waits out a memory round trip: 0.8 us a step at 1 MiB segments)
+    for (u64 q0 = 0; q0 < L; q0 += 256) {
+        u32 bs[4];
 #pragma unroll
-        for (int bit = 0; bit < 8; bit++) {
-            const u64 ones = __ballot((b >> bit) & 1u);
-            match &= ((b >> bit) & 1u) ? ones : ~ones;
+        for (int k = 0; k < 4; k++) { const u64 p = q0 + 64 * k + (u64)lane; bs[k] = p < L ? (u32)S[p] : 0u; }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const u64 p = q0 + 64 * k + (u64)lane;
+            const bool act = p < L;
+            const u32 b = bs[k];
+            u64 match = __ballot(act);
+#pragma unroll
+            for (int bit = 0; bit < 8; bit++) {
+                const u64 ones = __ballot((b >> bit) & 1u);
+                match &= ((b >> bit) & 1u) ? ones : ~ones;
+            }
+            if (act) {
+                const u32 at = cnt[b];
+                LFseg[p] = add + at + (u32)__popcll(match & lanemask_lt());
+                if ((match >> lane) == 1ull) cnt[b] = at + (u32)__popcll(match);      // the group's last lane
+            }
+            __builtin_amdgcn_wave_barrier();
         }
-        if (act) {
-            const u32 at = cnt[b];
-            LF[base + p] = at + (u32)__popcll(match & lanemask_lt());
-            if ((match >> lane) == 1ull) cnt[b] = at + (u32)__popcll(match);      // the group's last lane
-        }
-        __builtin_amdgcn_wave_barrier();
     }
+}
+__global__ __launch_bounds__(256) void seg_lf_kernel(const u8 *__restrict__ B, const u64 *__restrict__ seg_off, u64 count, u64 big, u32 *__restrict__ LF)
+{
+    __shared__ u32 cnt_all[4][256];
+    const u64 s = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= count) return;
+    const u64 base = seg_off[s], L = seg_off[s + 1] - base;
+    if (L >= big) return;
+    seg_lf_wave(B + base, L, 0u, LF + base, cnt_all[threadIdx.x >> 6]);
+}
+// The shared pass's LF: the same per segment, as indices of the run -- a permutation of the run's [0, n) whose cycles each lie inside one
+// segment.  seg_off: the run's slice of the offset table (absolute offsets, seg_off[0] = run_base); B and LF start at the run.
+__global__ __launch_bounds__(256) void seg_lf_shared_kernel(const u8 *__restrict__ B, const u64 *__restrict__ seg_off, u64 count, u64 run_base, u32 *__restrict__ LF)
+{
+    __shared__ u32 cnt_all[4][256];
+    const u64 s = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= count) return;
+    const u64 base = seg_off[s] - run_base, L = seg_off[s + 1] - seg_off[s];
+    seg_lf_wave(B + base, L, (u32)base, LF + base, cnt_all[threadIdx.x >> 6]);
 }
 
 // The cycle walk of unbwts.c:62-86 inside one segment, one lane per segment: cycles by smallest index, each written from the end of
@@ -1439,13 +1562,27 @@ __global__ __launch_bounds__(64) void seg_walk_kernel(const u8 *__restrict__ B, 
 #define SEG_WALK_STEP_US 5.0
 #define SEG_WALK_STEPS_PER_US 12000.0
 #define SEG_CALL_US 300.0
-static u64 seg_inverse_threshold(const std::vector<u64> &off)
+// the shared pass (plan B), measured (profiles/segments_shared_inverse_1gib.txt): a pass of two 100 000-byte segments takes 0.9 ms, 0.5 of
+// them in the LF builder; 1 GiB goes at 19 000 bytes/us (55 .. 59 ms for segments of 4 KiB .. 1 MiB), 64 MiB at 14 000 -- the lower rate is
+// the one used, so that the lane walk keeps the sets where the two plans are close; the LF builder gives a segment one wave, 64 positions
+// a step, so the longest segment of a run adds its steps (1 MiB: 16 384 steps, 10.2 - 3.1 ms); and every segment leaves about min(length,
+// 15) elements that no walk reaches, 0.5 .. 0.9 ns each through the index log and the second collection (64 MiB of 8 .. 256-byte segments:
+// 48.8 .. 7.2 ms, where the lane walk takes 31.3 .. 4.9).  A single call's bytes go at the whole-input rate (1 GiB in 32.6 ms).
+#define SEG_SHARED_PASS_US 400.0
+#define SEG_SHARED_BYTES_PER_US 14000.0
+#define SEG_SHARED_UNREACHED_PER_US 1400.0
+#define SEG_SHARED_UNREACHED_PER_SEGMENT 16
+#define SEG_SHARED_LF_STEP_US 0.45
+#define SEG_SINGLE_BYTES_PER_US 33000.0
+static int length_bits(u64 len) { int b = 0; for (u64 x = len; x; x >>= 1) b++; return b; }          // len < 2^b
+// Plan A: the power of two `big` that minimises (lane walk of the segments below it) + (a single call for each of the others)
+static u64 seg_inverse_threshold(const std::vector<u64> &off, double *cost_out = nullptr)
 {
     const u64 count = (u64)off.size() - 1;
     u64 cnt[66] = {0}, bytes[66] = {0}, maxlen[66] = {0};
     for (u64 s = 0; s < count; s++) {
         const u64 len = off[s + 1] - off[s];
-        int b = 0; for (u64 x = len; x; x >>= 1) b++;          // len < 2^b
+        const int b = length_bits(len);
         cnt[b]++; bytes[b] += len; if (len > maxlen[b]) maxlen[b] = len;
     }
     // threshold 2^b: segments with len < 2^b walk, the rest are single calls
@@ -1463,35 +1600,140 @@ static u64 seg_inverse_threshold(const std::vector<u64> &off)
         const double cost = walk + (double)calls * SEG_CALL_US;
         if (cost < best) { best = cost; best_b = b; }
     }
+    if (cost_out) {
+        // (for the comparison with plan B, which counts them: the single calls' bytes)
+        u64 single_bytes = 0;
+        for (int b = best_b + 1; b <= 65; b++) single_bytes += bytes[b];
+        *cost_out = best + (double)single_bytes / SEG_SINGLE_BYTES_PER_US;
+    }
+    return best_b >= 64 ? ~0ull : 1ull << best_b;
+}
+// Plan B: the power of two `big` that minimises (one shared pass per maximal run of segments below it) + (a single call for each of the others)
+static u64 seg_shared_threshold(const std::vector<u64> &off, double *cost_out)
+{
+    const u64 count = (u64)off.size() - 1;
+    u64 cnt[67] = {0}, bytes[67] = {0}, maxlen[67] = {0}, unreached[67] = {0};     // unreached: the estimate, min(length, 16) a segment
+    long long run_starts[67] = {0};          // difference array over b: segment s starts a run at threshold 2^b for bits(s) <= b < bits(s - 1)
+    int prev = 66;
+    for (u64 s = 0; s < count; s++) {
+        const u64 len = off[s + 1] - off[s];
+        const int b = length_bits(len);
+        cnt[b]++; bytes[b] += len; if (len > maxlen[b]) maxlen[b] = len;
+        unreached[b] += len < SEG_SHARED_UNREACHED_PER_SEGMENT ? len : SEG_SHARED_UNREACHED_PER_SEGMENT;
+        if (b < prev) { run_starts[b]++; run_starts[prev]--; }
+        prev = b;
+    }
+    double best = 1e300;
+    int best_b = 65;
+    u64 shared_bytes = 0, shared_unreached = 0, shared_max = 0, calls = count, single_bytes = off[count];
+    long long runs = 0;
+    for (int b = 0; b <= 65; b++) {
+        runs += run_starts[b];
+        if (b > 0) {
+            shared_bytes += bytes[b]; single_bytes -= bytes[b]; calls -= cnt[b];
+            shared_unreached += unreached[b];
+            if (maxlen[b] > shared_max) shared_max = maxlen[b];
+        }
+        const double cost = (double)runs * SEG_SHARED_PASS_US + (double)shared_bytes / SEG_SHARED_BYTES_PER_US + (double)shared_unreached / SEG_SHARED_UNREACHED_PER_US +
+                            (double)((shared_max + 63) / 64) * SEG_SHARED_LF_STEP_US + (double)calls * SEG_CALL_US + (double)single_bytes / SEG_SINGLE_BYTES_PER_US;
+        if (cost < best) { best = cost; best_b = b; }
+    }
+    *cost_out = best;
     return best_b >= 64 ? ~0ull : 1ull << best_b;
 }
 
-size_t inverse_segments_arena_bytes(u64 n) { return align_up(n * 4, 256) + (1 << 16); }
-
-int inverse_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
+// What a segmented inverse does with a set of segments.  Plan A (SEG_PLAN_LANE): segments below `big` are walked one lane each, in one
+// pass over the call.  Plan B (SEG_PLAN_SHARED): every maximal run of consecutive segments below `big` goes through one shared pass of
+// the splitter walk.  In both the segments of `big` bytes or more take a single-input call each.
+enum { SEG_PLAN_LANE = 0, SEG_PLAN_SHARED = 1, SEG_PLAN_SHARED_NOMEM = 2 /* (reports only) plan B refused for memory: plan A ran */ };
+struct SegInvPlan { int plan; u64 big, runs, own_segs, own_bytes, single_segs, single_bytes, longest_run, longest_run_segs; };
+// the routes of the set under (plan, big)
+static SegInvPlan seg_plan_routes(const std::vector<u64> &off, int plan, u64 big)
 {
-    const std::vector<u64> &off = ctx->seg_off;
+    SegInvPlan p = {plan, big, 0, 0, 0, 0, 0, 0, 0};
     const u64 count = (u64)off.size() - 1;
-    if (count == 1) return inverse_device_impl(ctx, d_in, n, d_out);
-    // A segment of `big` bytes or more takes the single-input inverse on its own, the others the per-segment walk below.  The walk costs
-    // its longest segment in dependent steps (or its bytes at the walk's throughput, when many chains share the chip); a single call
-    // costs a fixed latency per segment.  `big` is the power of two that minimises the sum of the two (seg_inverse_threshold), so the
-    // call is never much slower than one single-input call per segment.  BWTS_SEG_INV_BIG (test switch) sets it: 1 = every segment alone.
-    u64 big = seg_inverse_threshold(off);
-    if (const char *e = bwts_knob(ctx, "BWTS_SEG_INV_BIG")) { const long long v = atoll(e); if (v >= 1) big = (u64)v; }
-    u64 cycles = 0, small = 0;
-    u32 attempts = 1;
-    u64 unvisited = 0;
+    u64 run = 0, run_segs = 0;
     for (u64 s = 0; s < count; s++) {
         const u64 len = off[s + 1] - off[s];
-        if (len < big) { small += len; continue; }
-        BWTS_TRY(inverse_device_impl(ctx, d_in + off[s], len, d_out + off[s]));
-        cycles += ctx->tm.factors;
-        unvisited += ctx->tm.unvisited;
-        if (ctx->tm.attempts > attempts) attempts = ctx->tm.attempts;
+        if (len >= big) { p.single_segs++; p.single_bytes += len; run = run_segs = 0; continue; }
+        if (run == 0) p.runs++;
+        run += len; run_segs++; p.own_segs++; p.own_bytes += len;
+        if (run > p.longest_run) { p.longest_run = run; p.longest_run_segs = run_segs; }
     }
+    if (plan == SEG_PLAN_LANE) p.runs = p.own_segs ? 1 : 0;            // one lane walk over the whole call
+    return p;
+}
+// force_plan: -1 the cost estimate chooses, else the plan; force_big: 0 the plan's own threshold, else `big`
+static SegInvPlan seg_inverse_plan(const std::vector<u64> &off, int force_plan, u64 force_big)
+{
+    double cost_a = 0, cost_b = 0;
+    const u64 big_a = seg_inverse_threshold(off, &cost_a), big_b = seg_shared_threshold(off, &cost_b);
+    const int plan = force_plan >= 0 ? force_plan : cost_b < cost_a ? SEG_PLAN_SHARED : SEG_PLAN_LANE;
+    return seg_plan_routes(off, plan, force_big ? force_big : plan == SEG_PLAN_SHARED ? big_b : big_a);
+}
+// ... with the context's test switches: BWTS_SEG_INV_PLAN=lane|shared forces the plan, BWTS_SEG_INV_BIG sets `big` (1 = every segment alone)
+static SegInvPlan seg_inverse_plan(const bwts_ctx *ctx)
+{
+    int force_plan = -1; u64 force_big = 0;
+    if (const char *e = bwts_knob(ctx, "BWTS_SEG_INV_PLAN")) force_plan = !strcmp(e, "shared") ? SEG_PLAN_SHARED : !strcmp(e, "lane") ? SEG_PLAN_LANE : -1;
+    if (const char *e = bwts_knob(ctx, "BWTS_SEG_INV_BIG")) { const long long v = atoll(e); if (v >= 1) force_big = (u64)v; }
+    return seg_inverse_plan(ctx->seg_off, force_plan, force_big);
+}
+static size_t seg_lane_arena_bytes(u64 n) { return align_up(n * 4, 256) + (1 << 16); }
+// a shared pass's first attempt over a run of n bytes in `segs` segments: the default spacing, and the marks inverse_narrow_chain starts with
+static size_t seg_pass_arena_bytes(u64 n, u64 segs)
+{
+    return n == 0 ? 0 : segs > SEG_MOMENTS_MAX_SEGMENTS ? inverse_attempt_bytes(n, inverse_splitter_log2(n), MARK_LOG) : inverse_arena_bytes(n);
+}
+static size_t seg_plan_arena_bytes(const SegInvPlan &p, u64 n)
+{
+    return p.plan == SEG_PLAN_SHARED ? seg_pass_arena_bytes(p.longest_run, p.longest_run_segs) : seg_lane_arena_bytes(n);
+}
+// what the host path reserves ahead for the context's current segment table: by the plan the call will take
+size_t inverse_segments_arena_bytes(const bwts_ctx *ctx, u64 n)
+{
+    if (ctx->seg_off.size() <= 2) return inverse_arena_bytes(n);
+    return seg_plan_arena_bytes(seg_inverse_plan(ctx), n);
+}
+// bwts_debug_segments_plan: the plan for a set of lengths, no context and no device (so no test switch either)
+int inverse_segments_plan_words(const u64 *lengths, u64 count, u64 out[8])
+{
+    std::vector<u64> off(count + 1);
+    off[0] = 0;
+    for (u64 s = 0; s < count; s++) {
+        if (lengths[s] == 0 || lengths[s] > 0x100000000ull - off[s]) return -1;
+        off[s + 1] = off[s] + lengths[s];
+    }
+    const SegInvPlan p = seg_inverse_plan(off, -1, 0);
+    const u64 w[8] = {(u64)p.plan, p.big, p.runs, p.own_segs, p.own_bytes, p.single_segs, p.single_bytes, (u64)seg_plan_arena_bytes(p, off[count])};
+    memcpy(out, w, sizeof w);
+    return p.plan;
+}
+
+// the sums a segmented call reports in bwts_timings: all cycles, the unreached elements summed over the passes, the largest attempt count
+struct SegTotals {
+    u64 cycles = 0, unvisited = 0; u32 attempts = 1;
+    void add_last_pass(const bwts_ctx *ctx) { cycles += ctx->tm.factors; unvisited += ctx->tm.unvisited; if (ctx->tm.attempts > attempts) attempts = ctx->tm.attempts; }
+};
+static int seg_single_calls(bwts_ctx *ctx, const u8 *d_in, u8 *d_out, u64 big, SegTotals &t)
+{
+    const std::vector<u64> &off = ctx->seg_off;
+    for (u64 s = 0; s + 1 < (u64)off.size(); s++) {
+        const u64 len = off[s + 1] - off[s];
+        if (len < big) continue;
+        BWTS_TRY(inverse_device_impl(ctx, d_in + off[s], len, d_out + off[s]));
+        t.add_last_pass(ctx);
+    }
+    return BWTS_OK;
+}
+// Plan A.  The walk costs its longest segment in dependent steps (or its bytes at the walk's throughput, when many chains share the
+// chip); a single call costs a fixed latency per segment.
+static int inverse_segments_lane(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, const SegInvPlan &pl, SegTotals &t)
+{
+    const u64 count = (u64)ctx->seg_off.size() - 1, big = pl.big, small = pl.own_bytes;
+    BWTS_TRY(seg_single_calls(ctx, d_in, d_out, big, t));
     if (small) {
-        BWTS_TRY(arena_reserve(ctx, inverse_segments_arena_bytes(n)));
+        BWTS_TRY(arena_reserve(ctx, seg_lane_arena_bytes(n)));
         u32 *LF = arena_array<u32>(ctx, n);
         if (!LF) return BWTS_E_NOMEM;
         unsigned long long *d_cyc = (unsigned long long *)(ctx->d_small + SMI_COUNTERS);
@@ -1507,11 +1749,62 @@ int inverse_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
             HIPC(hipGetLastError());
         }
         BWTS_TRY(read_small(ctx, SMI_COUNTERS, 1));
-        cycles += ctx->h_small[SMI_COUNTERS];
+        t.cycles += ctx->h_small[SMI_COUNTERS];
     }
+    return BWTS_OK;
+}
+// Plan B.  Every run's pass is the narrow form's chain of attempts over the run (LF per segment as indices of the run, symbols from the
+// input, cycle ends per segment); it holds about what a single-input inverse of the run holds, reserved for the longest run before
+// anything runs, so that a refusal (BWTS_E_NOMEM) leaves the call to plan A.
+static int inverse_segments_shared(bwts_ctx *ctx, const u8 *d_in, u8 *d_out, const SegInvPlan &pl, SegTotals &t)
+{
+    const std::vector<u64> &off = ctx->seg_off;
+    const u64 count = (u64)off.size() - 1, big = pl.big;
+    if (pl.longest_run) BWTS_TRY(arena_reserve(ctx, seg_pass_arena_bytes(pl.longest_run, pl.longest_run_segs)));
+    for (u64 a = 0; a < count;) {
+        if (off[a + 1] - off[a] >= big) { a++; continue; }
+        u64 b = a + 1;
+        while (b < count && off[b + 1] - off[b] < big) b++;
+        const InvSegs run = {ctx->d_seg_off + a, b - a, off[a]};
+        ctx->tm.attempts = 1;
+        ctx->inv_attempts_made = 0;
+        BWTS_TRY(inverse_narrow_chain(ctx, d_in + off[a], off[b] - off[a], d_out + off[a], &run));
+        t.add_last_pass(ctx);
+        a = b;
+    }
+    return seg_single_calls(ctx, d_in, d_out, big, t);          // (after the passes: bwts_debug_inverse_report describes the last pass that ran)
+}
+
+int inverse_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
+{
+    const u64 count = (u64)ctx->seg_off.size() - 1;
+    u64 *rep = ctx->seg_report;
+    memset(rep, 0, sizeof ctx->seg_report);
+    SegTotals t;
+    if (count == 1) {
+        BWTS_TRY(inverse_device_impl(ctx, d_in, n, d_out));
+        rep[SR_SINGLE_SEGS] = 1; rep[SR_SINGLE_BYTES] = n; rep[SR_ATTEMPTS] = ctx->tm.attempts;
+        return BWTS_OK;
+    }
+    SegInvPlan pl = seg_inverse_plan(ctx);
+    int rc = BWTS_E_NOMEM, taken = pl.plan;
+    if (pl.plan == SEG_PLAN_SHARED) {
+        rc = inverse_segments_shared(ctx, d_in, d_out, pl, t);
+        if (rc == BWTS_E_NOMEM) {                                   // no room for a pass: today's plan, from the start
+            u64 big = 0;
+            if (const char *e = bwts_knob(ctx, "BWTS_SEG_INV_BIG")) { const long long v = atoll(e); if (v >= 1) big = (u64)v; }
+            pl = seg_inverse_plan(ctx->seg_off, SEG_PLAN_LANE, big);
+            taken = SEG_PLAN_SHARED_NOMEM;
+            t = SegTotals();
+        }
+    }
+    if (pl.plan == SEG_PLAN_LANE) rc = inverse_segments_lane(ctx, d_in, n, d_out, pl, t);
+    BWTS_TRY(rc);
+    rep[SR_PLAN] = (u64)taken; rep[SR_BIG] = pl.big; rep[SR_RUNS] = pl.runs; rep[SR_OWN_SEGS] = pl.own_segs; rep[SR_OWN_BYTES] = pl.own_bytes;
+    rep[SR_SINGLE_SEGS] = pl.single_segs; rep[SR_SINGLE_BYTES] = pl.single_bytes; rep[SR_ATTEMPTS] = t.attempts;
     ctx->tm.n = n;
-    ctx->tm.factors = cycles;
-    ctx->tm.unvisited = unvisited;
-    ctx->tm.attempts = attempts;
+    ctx->tm.factors = t.cycles;
+    ctx->tm.unvisited = t.unvisited;
+    ctx->tm.attempts = t.attempts;
     return BWTS_OK;
 }

@@ -350,20 +350,36 @@ __global__ __launch_bounds__(256) void wi_unit_tag_kernel(WiCycle *__restrict__ 
     if (i < m) cyc[i].leader |= WI_UNIT_TAG;
 }
 // wi_place_kernel + place_segments_wide_kernel for nodes of one symbol
-template <typename IDX>
-__global__ __launch_bounds__(256) void wi_unit_place_kernel(u64 nu, const WiMin *__restrict__ rec, const WiSum *__restrict__ sh, const u64 *__restrict__ dist,
-                                                            const u64 *__restrict__ min_dist, const IDX *__restrict__ end_by_leader,
-                                                            const IDX *__restrict__ ulf, const u64 *__restrict__ Cg, u8 *__restrict__ out)
+// FROM_INPUT (the narrow form's shared pass over segments, inverse.hip): the unit node's symbol is B[uidx[v]], not looked up from its LF value
+template <typename IDX, bool FROM_INPUT>
+__device__ __forceinline__ void wi_unit_place_body(u64 nu, const WiMin *rec, const WiSum *sh, const u64 *dist,
+                                                   const u64 *min_dist, const IDX *end_by_leader,
+                                                   const IDX *ulf, const u64 *Cg, const IDX *uidx, const u8 *Bsym,
+                                                   u8 *out)
 {
-    __shared__ u64 Ctab[257];
-    for (int i = threadIdx.x; i < 257; i += 256) Ctab[i] = Cg[i];
+    __shared__ u64 Ctab[FROM_INPUT ? 1 : 257];
+    if (!FROM_INPUT) for (int i = threadIdx.x; i < 257; i += 256) Ctab[i] = Cg[i];
     __syncthreads();
     const u64 v = (u64)blockIdx.x * 256 + threadIdx.x;
     if (v >= nu) return;
     const u32 l = rec[v].leader;
     const u64 L = sh[l].sum, dm = min_dist[l], d = dist[v];
     const u64 t = d >= dm ? d - dm : d + L - dm;
-    out[(u64)end_by_leader[l] - t] = (u8)symbol_of64(Ctab, (u64)ulf[v]);
+    out[(u64)end_by_leader[l] - t] = FROM_INPUT ? Bsym[uidx[v]] : (u8)symbol_of64(Ctab, (u64)ulf[v]);
+}
+template <typename IDX>
+__global__ __launch_bounds__(256) void wi_unit_place_kernel(u64 nu, const WiMin *__restrict__ rec, const WiSum *__restrict__ sh, const u64 *__restrict__ dist,
+                                                            const u64 *__restrict__ min_dist, const IDX *__restrict__ end_by_leader,
+                                                            const IDX *__restrict__ ulf, const u64 *__restrict__ Cg, u8 *__restrict__ out)
+{
+    wi_unit_place_body<IDX, false>(nu, rec, sh, dist, min_dist, end_by_leader, ulf, Cg, nullptr, nullptr, out);
+}
+template <typename IDX>
+__global__ __launch_bounds__(256) void wi_unit_place_seg_kernel(u64 nu, const WiMin *__restrict__ rec, const WiSum *__restrict__ sh, const u64 *__restrict__ dist,
+                                                                const u64 *__restrict__ min_dist, const IDX *__restrict__ end_by_leader,
+                                                                const IDX *__restrict__ uidx, const u8 *__restrict__ B, u8 *__restrict__ out)
+{
+    wi_unit_place_body<IDX, true>(nu, rec, sh, dist, min_dist, end_by_leader, nullptr, nullptr, uidx, B, out);
 }
 // device memory for one call (the rare paths): released when the call returns
 struct ScopedDeviceBlock {

@@ -48,11 +48,25 @@ int bwts_debug_forward_arena(uint64_t n, uint64_t out[1]);
  * past the pool's end when it overflows); 5 node_cap; 6 nu: elements no walk reached; 7 nu2: nodes no level-2 walk reached;
  * 8 room for unreached elements at the first collection; 9 a second collection ran; 10 moments: classes listed for the search, as
  * read back after the first collection; 11 moments: the fallback flag, likewise; 12 the unit-node route ranked the cycles without a
- * splitter; 13 kc: cycles of the node list; 14 kt: cycles without a splitter; 15 form: 0 narrow, 1 wide, 2 wide compact.  A stage
+ * splitter; 13 kc: cycles of the node list; 14 kt: cycles without a splitter; 15 form: 0 narrow, 1 wide, 2 wide compact, 3 narrow,
+ * segmented (the shared pass of bwts_inverse_segments over a run of segments: after such a call the records are those of the last
+ * pass that ran).  A stage
  * that did not run leaves its words 0; the wide form has no level 2 (word 7 stays 0).
  * out receives whole records while they fit into cap_words; *attempts = attempts the call made (records exist for the first 8; 0
  * after the constant-input shortcut beyond 2^31, and before any call).  Returns the number of records written, < 0 on a bad argument. */
 int bwts_debug_inverse_report(bwts_ctx *ctx, uint64_t *out, uint64_t cap_words, uint64_t *attempts);
+/* Pure arithmetic, no context and no device (so no test switch applies): what bwts_inverse_segments would do with `count` segments of
+ * these lengths.  out: 0 plan: 0 = A, segments below `big` are walked one lane each in one pass; 1 = B, every maximal run of consecutive
+ * segments below `big` goes through one shared pass of the splitter walk; 1 big: segments of this length or more take a single-input
+ * call each (2^64 - 1: none); 2 runs: shared passes (plan A: 1 when a segment is walked, else 0); 3, 4 segments and bytes on the plan's
+ * own route (lane walk or shared pass); 5, 6 segments and bytes that go single; 7 arena bytes the call reserves for its own route.
+ * Returns the plan, -1 on a bad argument (no lengths, a zero length, a sum beyond 2^32). */
+int bwts_debug_segments_plan(const uint64_t *lengths, uint64_t count, uint64_t out[8]);
+/* What the most recent segmented inverse (host or device entry) on the context did (host memory, no device work).  Words as for
+ * bwts_debug_segments_plan with the test switches applied, except: 0 plan: also 2 = B was chosen, its arena was refused
+ * (BWTS_E_NOMEM) and plan A ran instead; 7 the largest attempt count of the call's passes and single calls.  A call with one segment
+ * is a single call (words 5 and 6).  All 0 before any call. */
+int bwts_debug_segments_report(bwts_ctx *ctx, uint64_t out[8]);
 /* What the doubling sorts of the most recent forward call on the context did (also bwts_debug_suffix_array and bwts_debug_lyndon;
  * no device work: the engine keeps the records on the host as it goes, from values its stages read back anyway).  One record of
  * BWTS_FWD_SORT_WORDS words per sort, in the order they ran: a forward that found its factors by the general Lyndon path has the

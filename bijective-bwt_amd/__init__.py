@@ -39,12 +39,18 @@ EXPORTS = [
     "bwts_forward_batch", "bwts_inverse_batch",
     "bwts_forward_segments", "bwts_inverse_segments", "bwts_forward_segments_device", "bwts_inverse_segments_device",
 ]
+# ... include/bwts_mtf.h (move-to-front, the stage behind the transform) ...
+MTF_EXPORTS = [
+    "bwts_mtf_forward_device", "bwts_mtf_inverse_device", "bwts_mtf_forward", "bwts_mtf_inverse",
+    "bwts_mtf_forward_segments_device", "bwts_mtf_inverse_segments_device", "bwts_mtf_forward_segments", "bwts_mtf_inverse_segments",
+]
 # ... and include/bwts_test.h (harness and unit-test hooks)
 TEST_EXPORTS = [
     "bwts_generate_device", "bwts_device_alloc", "bwts_device_free", "bwts_copy_to_device", "bwts_copy_to_host",
     "bwts_device_equal", "bwts_debug_sort_pairs", "bwts_debug_suffix_array", "bwts_debug_lyndon",
     "bwts_debug_chunk_plan", "bwts_debug_inverse_arena", "bwts_debug_forward_arena", "bwts_debug_inverse_report",
     "bwts_debug_forward_report", "bwts_debug_segments_plan", "bwts_debug_segments_report",
+    "bwts_debug_mtf_plan", "bwts_debug_last_spans",
 ]
 # bwts_debug_inverse_report: the words of one attempt's record, and what marks, outcomes and forms are called
 INV_REPORT_FIELDS = ["g", "mark", "outcome", "s", "virtual", "node_cap", "nu", "nu2", "ucap_first", "second_collect",
@@ -141,6 +147,12 @@ def lib():
             getattr(L, name).argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(vp)]
         for name in ("bwts_forward_segments", "bwts_inverse_segments", "bwts_forward_segments_device", "bwts_inverse_segments_device"):
             getattr(L, name).argtypes = [vp, vp, vp, u64, vp]
+        for name in ("bwts_mtf_forward", "bwts_mtf_inverse", "bwts_mtf_forward_device", "bwts_mtf_inverse_device"):
+            getattr(L, name).argtypes = [vp, vp, u64, vp]
+        for name in ("bwts_mtf_forward_segments", "bwts_mtf_inverse_segments", "bwts_mtf_forward_segments_device", "bwts_mtf_inverse_segments_device"):
+            getattr(L, name).argtypes = [vp, vp, vp, u64, vp]
+        L.bwts_debug_mtf_plan.argtypes = [u64, ctypes.POINTER(u64)]
+        L.bwts_debug_last_spans.argtypes = [vp, ctypes.POINTER(ctypes.c_double), u64]
         for name in ("bwts_forward_sink", "bwts_inverse_sink"):
             getattr(L, name).argtypes = [vp, vp, u64, SINK_FN, vp]
         L.bwts_generate_device.argtypes = [vp, i32, u64, u64, vp]
@@ -336,6 +348,35 @@ class Context:
         ls = np.ascontiguousarray(lengths, dtype=np.uint64)
         self._check(lib().bwts_inverse_segments_device(self._h, _ptr(d_in), ls.ctypes.data, ls.size, _ptr(d_out)))
 
+    # -- move-to-front behind the transform (include/bwts_mtf.h) ------------------------------
+    def mtf_forward(self, data):
+        """bwts_mtf_forward: the move-to-front ranks of a byte string (host buffers, staged like forward())."""
+        return self._host(lib().bwts_mtf_forward, data)
+
+    def mtf_inverse(self, data):
+        return self._host(lib().bwts_mtf_inverse, data)
+
+    def mtf_forward_device(self, d_in, n, d_out):
+        self._check(lib().bwts_mtf_forward_device(self._h, _ptr(d_in), int(n), _ptr(d_out)))
+
+    def mtf_inverse_device(self, d_in, n, d_out):
+        self._check(lib().bwts_mtf_inverse_device(self._h, _ptr(d_in), int(n), _ptr(d_out)))
+
+    def mtf_forward_segments(self, data, lengths, out=None):
+        """bwts_mtf_forward_segments: the list starts afresh at every segment; `out` may be `data` itself."""
+        return self._segments(lib().bwts_mtf_forward_segments, data, lengths, out)
+
+    def mtf_inverse_segments(self, data, lengths, out=None):
+        return self._segments(lib().bwts_mtf_inverse_segments, data, lengths, out)
+
+    def mtf_forward_segments_device(self, d_in, lengths, d_out):
+        ls = np.ascontiguousarray(lengths, dtype=np.uint64)
+        self._check(lib().bwts_mtf_forward_segments_device(self._h, _ptr(d_in), ls.ctypes.data, ls.size, _ptr(d_out)))
+
+    def mtf_inverse_segments_device(self, d_in, lengths, d_out):
+        ls = np.ascontiguousarray(lengths, dtype=np.uint64)
+        self._check(lib().bwts_mtf_inverse_segments_device(self._h, _ptr(d_in), ls.ctypes.data, ls.size, _ptr(d_out)))
+
     def forward_into(self, a, out):
         """bwts_forward on caller-provided numpy buffers (no allocation inside the call)."""
         self._check(lib().bwts_forward(self._h, a.ctypes.data, a.size, out.ctypes.data))
@@ -379,6 +420,14 @@ class Context:
         cnt = ctypes.c_uint64(0)
         self._check(lib().bwts_debug_lyndon(self._h, a.ctypes.data, a.size, st.ctypes.data, st.size, ctypes.byref(cnt)))
         return st[: cnt.value].copy()
+
+    def debug_last_spans(self, cap=4096):
+        """Device ms of every timed launch of the most recent call, in launch order (set_timing(2): every launch)."""
+        buf = (ctypes.c_double * cap)()
+        got = lib().bwts_debug_last_spans(self._h, buf, cap)
+        if got < 0:
+            self._check(got)
+        return [float(buf[i]) for i in range(got)]
 
     def debug_inverse_report(self):
         """One dict per attempt of the most recent inverse call on this context (INV_REPORT_FIELDS; mark, outcome and form by name,
@@ -461,6 +510,14 @@ def debug_segments_plan(lengths):
     d = _segments_words(buf)
     d["arena_bytes"] = int(buf[7])
     return d
+
+
+def debug_mtf_plan(n):
+    """How the move-to-front stage cuts one input of n bytes (bwts_debug_mtf_plan: host arithmetic, no context, no device)."""
+    buf = (ctypes.c_uint64 * 4)()
+    if lib().bwts_debug_mtf_plan(int(n), buf) < 0:
+        raise BwtsError(-1, "bad length")
+    return {"T": int(buf[0]), "G": int(buf[1]), "tiles": int(buf[2]), "groups": int(buf[3])}
 
 
 def _ptr(x):

@@ -1,6 +1,7 @@
 // api.hip -- the C-ABI of include/bwts.h: context, arenas, staging, timing, test hooks.
 #include "internal.h"
 #include "../../include/bwts_test.h"
+#include "../../include/bwts_mtf.h"
 
 #include <new>
 #include <stdio.h>
@@ -391,6 +392,15 @@ extern "C" int bwts_ctx_release_memory(bwts_ctx *ctx)
 typedef int (*device_impl_fn)(bwts_ctx *, const u8 *, u64, u8 *);
 __global__ void pcie_copy_kernel(uint4 *__restrict__ dst, const uint4 *__restrict__ src, u64 vecs, u8 *__restrict__ dst_tail, const u8 *__restrict__ src_tail, u32 tail);
 
+static bool is_mtf(device_impl_fn fn) { return fn == mtf_forward_impl || fn == mtf_inverse_impl || fn == mtf_forward_segments_impl || fn == mtf_inverse_segments_impl; }
+static bool is_forward(device_impl_fn fn) { return fn == forward_device_impl || fn == forward_segments_impl; }
+// what a call is called in the guard report and the allocation trace
+static const char *impl_name(device_impl_fn fn)
+{
+    if (is_mtf(fn)) return fn == mtf_forward_impl || fn == mtf_forward_segments_impl ? "mtf forward" : "mtf inverse";
+    return is_forward(fn) ? "forward" : "inverse";
+}
+
 static int run_device(bwts_ctx *ctx, device_impl_fn fn, const void *d_in, u64 n, void *d_out)
 {
     if (!ctx || !d_in || !d_out || n == 0) return BWTS_E_ARG;
@@ -410,7 +420,7 @@ static int run_device(bwts_ctx *ctx, device_impl_fn fn, const void *d_in, u64 n,
     int rc = fn(ctx, (const u8 *)d_in, n, (u8 *)d_out);
     if (ctx->guard) {
         (void)hipStreamSynchronize(ctx->stream);
-        const int grc = guard_check(ctx, fn == forward_device_impl || fn == forward_segments_impl ? "forward" : "inverse");
+        const int grc = guard_check(ctx, impl_name(fn));
         if (rc == BWTS_OK) rc = grc;
     }
     if (rc != BWTS_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
@@ -708,6 +718,7 @@ static int ensure_io(bwts_ctx *ctx, u64 n, bool pairs)
 
 static size_t arena_hint(const bwts_ctx *ctx, device_impl_fn fn, u64 n)
 {
+    if (is_mtf(fn)) return mtf_arena_bytes(ctx, n, fn == mtf_forward_segments_impl || fn == mtf_inverse_segments_impl);
     if (fn == inverse_segments_impl) return n <= 0x100000000ull ? inverse_segments_arena_bytes(ctx, n) : 0;
     return n <= 0x100000000ull ? (fn == forward_device_impl || fn == forward_segments_impl ? forward_arena_bytes(n) : inverse_arena_bytes(n)) : 0;
 }
@@ -717,7 +728,7 @@ static int run_host(bwts_ctx *ctx, device_impl_fn fn, const uint8_t *in, uint64_
     if (!ctx || !in || (!out && !sink) || n == 0) return BWTS_E_ARG;
     HIPC(hipSetDevice(ctx->device));
     BWTS_TRY(ensure_io(ctx, n, false));
-    trace_alloc(ctx, "call    ", fn == forward_device_impl || fn == forward_segments_impl ? "forward: in" : "inverse: in", in, n);
+    trace_alloc(ctx, "call    ", is_mtf(fn) ? "mtf: in" : is_forward(fn) ? "forward: in" : "inverse: in", in, n);
     if (out) trace_alloc(ctx, "call    ", "out", out, n);
     Stager &sg = ctx->stg[0];
     // A context's first call allocates its arena, which can cost as long as the whole input copy where the driver clears what it
@@ -1008,6 +1019,49 @@ extern "C" int bwts_inverse_segments_device(bwts_ctx *ctx, const void *d_in, con
     return run_segments_device(ctx, inverse_segments_impl, d_in, lengths, count, d_out);
 }
 
+// ------------------------------------------------------------------------------------
+// move-to-front behind the transform (include/bwts_mtf.h): the same four plumbing routes, the kernels in mtf.hip
+// ------------------------------------------------------------------------------------
+extern "C" int bwts_mtf_forward_device(bwts_ctx *ctx, const void *d_in, uint64_t n, void *d_out)
+{
+    return run_device(ctx, mtf_forward_impl, d_in, n, d_out);
+}
+
+extern "C" int bwts_mtf_inverse_device(bwts_ctx *ctx, const void *d_in, uint64_t n, void *d_out)
+{
+    return run_device(ctx, mtf_inverse_impl, d_in, n, d_out);
+}
+
+extern "C" int bwts_mtf_forward(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out)
+{
+    return run_host(ctx, mtf_forward_impl, in, n, out, nullptr, nullptr);
+}
+
+extern "C" int bwts_mtf_inverse(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out)
+{
+    return run_host(ctx, mtf_inverse_impl, in, n, out, nullptr, nullptr);
+}
+
+extern "C" int bwts_mtf_forward_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out)
+{
+    return run_segments_device(ctx, mtf_forward_segments_impl, d_in, lengths, count, d_out);
+}
+
+extern "C" int bwts_mtf_inverse_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out)
+{
+    return run_segments_device(ctx, mtf_inverse_segments_impl, d_in, lengths, count, d_out);
+}
+
+extern "C" int bwts_mtf_forward_segments(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, uint64_t count, uint8_t *out)
+{
+    return run_segments_host(ctx, mtf_forward_segments_impl, in, lengths, count, out);
+}
+
+extern "C" int bwts_mtf_inverse_segments(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, uint64_t count, uint8_t *out)
+{
+    return run_segments_host(ctx, mtf_inverse_segments_impl, in, lengths, count, out);
+}
+
 extern "C" int bwts_host_alloc(bwts_ctx *ctx, uint64_t bytes, void **h_ptr)
 {
     if (!ctx || !h_ptr) return BWTS_E_ARG;
@@ -1173,6 +1227,29 @@ extern "C" int bwts_debug_chunk_plan(uint64_t a0, uint64_t a_chunks, uint64_t ou
     const ChunkRecut re = chunk_recut_plan(a0, a_chunks);
     out[0] = chunk_nominal_size(a0); out[1] = chunk_table_capacity(a0); out[2] = re.S; out[3] = re.nc;
     return re.allowed ? 1 : 0;
+}
+
+// the move-to-front stage's cut of one input of n bytes: tile size, tiles per group, tiles, groups.  No context, no device
+extern "C" int bwts_debug_mtf_plan(uint64_t n, uint64_t out[4])
+{
+    if (n == 0 || !out) return -1;
+    bwts_mtf_plan(n, out);
+    return 0;
+}
+
+// the device time of every timed launch of the most recent call, in launch order (timing level 2: every launch has a span; the events
+// stay with the context until the next call)
+extern "C" int bwts_debug_last_spans(bwts_ctx *ctx, double *ms, uint64_t cap)
+{
+    if (!ctx || (!ms && cap)) return BWTS_E_ARG;
+    int k = 0;
+    for (const TimedSpan &sp : ctx->spans) {
+        if ((u64)k >= cap) break;
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, sp.a, sp.b) != hipSuccess) { (void)hipGetLastError(); t = -1.f; }
+        ms[k++] = t;
+    }
+    return k;
 }
 
 // what a segmented inverse would do with segments of these lengths (the cost estimate's choice; test switches do not apply): no

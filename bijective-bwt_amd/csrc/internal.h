@@ -264,6 +264,14 @@ int    inverse_splitter_log2(u64 n);
 size_t inverse_attempt_bytes(u64 n, int g, int mark);
 size_t inverse_arena_bytes(u64 n);
 
+// ---- move-to-front, the stage behind the transform (mtf.hip; include/bwts_mtf.h) ----
+int mtf_forward_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
+int mtf_inverse_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
+int mtf_forward_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);       // the context's segment table, like the transform's
+int mtf_inverse_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
+size_t mtf_arena_bytes(const bwts_ctx *ctx, u64 n, bool segments);     // what a call reserves: 256 bytes per tile and a little per group
+void bwts_mtf_plan(u64 n, u64 out[4]);                                  // tile size, tiles per group, tiles and groups of one input of n bytes
+
 // chunk tables of the forward's later rounds (chunk_rounds.h) as plain arithmetic: nominal chunk size of a list, the tables' capacity
 // for a tied list of a0, and the re-cut of the a_chunks elements left at a compaction (allowed = the new chunks fit the tables)
 struct ChunkRecut { u32 S; u64 nc; bool allowed; };

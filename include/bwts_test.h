@@ -33,6 +33,14 @@ int bwts_debug_lyndon(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint64_t *h_
  * re-cut of the a_chunks elements left at a compaction.  out = {nominal chunk size of a0, table capacity, nominal size of a_chunks,
  * chunks of the re-cut}; returns 1 when the compaction is allowed (the re-cut fits the tables), else 0. */
 int bwts_debug_chunk_plan(uint64_t a0, uint64_t a_chunks, uint64_t out[4]);
+/* Pure arithmetic, no context and no device: how the move-to-front stage (bwts_mtf.h) cuts one input of n >= 1 bytes.  out = {T, the
+ * tile size in bytes; G, the tiles one wave composes in the scan's first level; tiles = ceil(n / T); groups = ceil(tiles / G)}.
+ * Returns 0, -1 on a bad argument. */
+int bwts_debug_mtf_plan(uint64_t n, uint64_t out[4]);
+/* Device time in ms of every timed launch of the most recent call on the context, in launch order, into ms[0 .. cap): with
+ * bwts_set_timing level 2 every launch is timed, so this is the per-kernel split that bwts_timings sums by class.  Returns the
+ * number written (0 with timing off), < 0 on a bad argument. */
+int bwts_debug_last_spans(bwts_ctx *ctx, double *ms, uint64_t cap);
 /* Pure arithmetic, no context and no device: the arena of the inverse for n <= 2^32 elements.  out[0] = bytes one attempt with
  * splitter spacing 2^g (g < 0: the spacing the engine picks for n) and mark 0 index log, 1 sentinel, 2 byte map, 3 moments (the
  * default) reserves; out[1] = bytes the host path allocates before the transform runs.  Returns the g used, -1 on a bad argument. */

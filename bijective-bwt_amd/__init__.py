@@ -44,13 +44,19 @@ MTF_EXPORTS = [
     "bwts_mtf_forward_device", "bwts_mtf_inverse_device", "bwts_mtf_forward", "bwts_mtf_inverse",
     "bwts_mtf_forward_segments_device", "bwts_mtf_inverse_segments_device", "bwts_mtf_forward_segments", "bwts_mtf_inverse_segments",
 ]
+# ... include/bwts_ec.h (entropy coding of the ranks, the stage behind move-to-front) ...
+EC_EXPORTS = [
+    "bwts_ec_bound", "bwts_ec_bound_segments", "bwts_ec_decoded_size", "bwts_ec_encode_device", "bwts_ec_decode_device",
+    "bwts_ec_encode", "bwts_ec_decode", "bwts_ec_encode_segments_device", "bwts_ec_decode_segments_device",
+]
+E_FORMAT, E_SPACE = -8, -9
 # ... and include/bwts_test.h (harness and unit-test hooks)
 TEST_EXPORTS = [
     "bwts_generate_device", "bwts_device_alloc", "bwts_device_free", "bwts_copy_to_device", "bwts_copy_to_host",
     "bwts_device_equal", "bwts_debug_sort_pairs", "bwts_debug_suffix_array", "bwts_debug_lyndon",
     "bwts_debug_chunk_plan", "bwts_debug_inverse_arena", "bwts_debug_forward_arena", "bwts_debug_inverse_report",
     "bwts_debug_forward_report", "bwts_debug_segments_plan", "bwts_debug_segments_report",
-    "bwts_debug_mtf_plan", "bwts_debug_last_spans",
+    "bwts_debug_mtf_plan", "bwts_debug_last_spans", "bwts_debug_ec_plan",
 ]
 # bwts_debug_inverse_report: the words of one attempt's record, and what marks, outcomes and forms are called
 INV_REPORT_FIELDS = ["g", "mark", "outcome", "s", "virtual", "node_cap", "nu", "nu2", "ucap_first", "second_collect",
@@ -153,6 +159,15 @@ def lib():
             getattr(L, name).argtypes = [vp, vp, vp, u64, vp]
         L.bwts_debug_mtf_plan.argtypes = [u64, ctypes.POINTER(u64)]
         L.bwts_debug_last_spans.argtypes = [vp, ctypes.POINTER(ctypes.c_double), u64]
+        L.bwts_ec_bound.argtypes = [u64]
+        L.bwts_ec_bound.restype = u64
+        L.bwts_ec_bound_segments.argtypes = [vp, u64, ctypes.POINTER(u64)]
+        L.bwts_ec_decoded_size.argtypes = [vp, u64, ctypes.POINTER(u64)]
+        for name in ("bwts_ec_encode_device", "bwts_ec_decode_device", "bwts_ec_encode", "bwts_ec_decode"):
+            getattr(L, name).argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
+        L.bwts_ec_encode_segments_device.argtypes = [vp, vp, vp, u64, vp, u64, vp]
+        L.bwts_ec_decode_segments_device.argtypes = [vp, vp, vp, vp, u64, vp]
+        L.bwts_debug_ec_plan.argtypes = [u64, ctypes.POINTER(u64)]
         for name in ("bwts_forward_sink", "bwts_inverse_sink"):
             getattr(L, name).argtypes = [vp, vp, u64, SINK_FN, vp]
         L.bwts_generate_device.argtypes = [vp, i32, u64, u64, vp]
@@ -377,6 +392,52 @@ class Context:
         ls = np.ascontiguousarray(lengths, dtype=np.uint64)
         self._check(lib().bwts_mtf_inverse_segments_device(self._h, _ptr(d_in), ls.ctypes.data, ls.size, _ptr(d_out)))
 
+    # -- entropy coding behind move-to-front (include/bwts_ec.h) ------------------------------------
+    def ec_encode(self, data, out_cap=None):
+        """bwts_ec_encode: the rANS stream of a byte string (host buffers); out_cap defaults to the bound."""
+        a = _u8(data)
+        if a.size == 0:
+            raise BwtsError(-1, "empty input")
+        out = np.empty(ec_bound(a.size) if out_cap is None else int(out_cap), dtype=np.uint8)
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_ec_encode(self._h, a.ctypes.data, a.size, out.ctypes.data, out.size, ctypes.byref(got)))
+        return out[:got.value].copy()
+
+    def ec_decode(self, stream):
+        """bwts_ec_decode: the bytes a stream holds (host buffers); the output is sized from the stream's header."""
+        a = _u8(stream)
+        n = ec_decoded_size(a)
+        out = np.empty(n, dtype=np.uint8)
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_ec_decode(self._h, a.ctypes.data, a.size, out.ctypes.data, out.size, ctypes.byref(got)))
+        return out[:got.value]
+
+    def ec_encode_device(self, d_in, n, d_out, out_cap):
+        """bwts_ec_encode_device: returns the stream's size in bytes."""
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_ec_encode_device(self._h, _ptr(d_in), int(n), _ptr(d_out), int(out_cap), ctypes.byref(got)))
+        return int(got.value)
+
+    def ec_decode_device(self, d_in, in_bytes, d_out, out_cap):
+        """bwts_ec_decode_device: returns the number of bytes decoded."""
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_ec_decode_device(self._h, _ptr(d_in), int(in_bytes), _ptr(d_out), int(out_cap), ctypes.byref(got)))
+        return int(got.value)
+
+    def ec_encode_segments_device(self, d_in, lengths, d_out, out_cap):
+        """bwts_ec_encode_segments_device: one stream per segment, concatenated; returns their sizes (uint64 array)."""
+        ls = np.ascontiguousarray(lengths, dtype=np.uint64)
+        sizes = np.zeros(ls.size, dtype=np.uint64)
+        self._check(lib().bwts_ec_encode_segments_device(self._h, _ptr(d_in), ls.ctypes.data, ls.size, _ptr(d_out), int(out_cap), sizes.ctypes.data))
+        return sizes
+
+    def ec_decode_segments_device(self, d_in, stream_bytes, lengths, d_out):
+        ls = np.ascontiguousarray(lengths, dtype=np.uint64)
+        sb = np.ascontiguousarray(stream_bytes, dtype=np.uint64)
+        if sb.size != ls.size:
+            raise BwtsError(-1, "one stream size per segment")
+        self._check(lib().bwts_ec_decode_segments_device(self._h, _ptr(d_in), sb.ctypes.data, ls.ctypes.data, ls.size, _ptr(d_out)))
+
     def forward_into(self, a, out):
         """bwts_forward on caller-provided numpy buffers (no allocation inside the call)."""
         self._check(lib().bwts_forward(self._h, a.ctypes.data, a.size, out.ctypes.data))
@@ -518,6 +579,43 @@ def debug_mtf_plan(n):
     if lib().bwts_debug_mtf_plan(int(n), buf) < 0:
         raise BwtsError(-1, "bad length")
     return {"T": int(buf[0]), "G": int(buf[1]), "tiles": int(buf[2]), "groups": int(buf[3])}
+
+
+def debug_ec_plan(n):
+    """How the entropy coder cuts one input of n bytes (bwts_debug_ec_plan: host arithmetic, no context, no device)."""
+    buf = (ctypes.c_uint64 * 5)()
+    if lib().bwts_debug_ec_plan(int(n), buf) < 0:
+        raise BwtsError(-1, "bad length")
+    return {"T": int(buf[0]), "K": int(buf[1]), "tiles": int(buf[2]), "blocks": int(buf[3]), "bound": int(buf[4])}
+
+
+def ec_bound(n):
+    """bwts_ec_bound: the largest stream an input of n bytes can have."""
+    b = int(lib().bwts_ec_bound(int(n)))
+    if b == 0:
+        raise BwtsError(-5 if int(n) > 0 else -1, "no bound for this length")
+    return b
+
+
+def ec_bound_segments(lengths):
+    ls = np.ascontiguousarray(lengths, dtype=np.uint64)
+    got = ctypes.c_uint64(0)
+    rc = lib().bwts_ec_bound_segments(ls.ctypes.data, ls.size, ctypes.byref(got))
+    if rc != 0:
+        raise BwtsError(rc, lib().bwts_strerror(rc).decode())
+    return int(got.value)
+
+
+def ec_decoded_size(stream):
+    """bwts_ec_decoded_size: the n a stream's header names, checked against the stream's length."""
+    a = _u8(stream)
+    head = np.zeros(16, dtype=np.uint8)
+    head[:min(a.size, 16)] = a[:16]
+    got = ctypes.c_uint64(0)
+    rc = lib().bwts_ec_decoded_size(head.ctypes.data, a.size, ctypes.byref(got))
+    if rc != 0:
+        raise BwtsError(rc, lib().bwts_strerror(rc).decode())
+    return int(got.value)
 
 
 def _ptr(x):

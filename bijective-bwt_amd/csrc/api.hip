@@ -2,6 +2,8 @@
 #include "internal.h"
 #include "../../include/bwts_test.h"
 #include "../../include/bwts_mtf.h"
+#include "../../include/bwts_ec.h"
+#include "ec_plan.h"
 
 #include <new>
 #include <stdio.h>
@@ -1062,6 +1064,169 @@ extern "C" int bwts_mtf_inverse_segments(bwts_ctx *ctx, const uint8_t *in, const
     return run_segments_host(ctx, mtf_inverse_segments_impl, in, lengths, count, out);
 }
 
+// ------------------------------------------------------------------------------------
+// entropy coding behind move-to-front (include/bwts_ec.h): calls whose output is not as long as their input, the kernels in ec.hip
+// ------------------------------------------------------------------------------------
+// run_device's bracket around such a call (code object loaded outside the timing, spans, guard check, total_ms); what the body needs
+// beyond the context travels in its closure.  n: the uncoded bytes, where the caller knows them already.
+template <typename Body>
+static int run_sized(bwts_ctx *ctx, u64 n, const char *what, Body body)
+{
+    HIPC(hipSetDevice(ctx->device));
+    spans_reset(ctx);
+    ctx->tm.n = n;
+    ctx->call_block_bytes = 0;
+    if (!ctx->launched) {
+        const double t0 = wall_ms();
+        pcie_copy_kernel<<<dim3(1), dim3(256), 0, ctx->stream>>>(nullptr, nullptr, 0, nullptr, nullptr, 0);
+        HIPC(hipStreamSynchronize(ctx->stream));
+        ctx->host_ms[BWTS_H_MODULE] += wall_ms() - t0;
+        ctx->launched = true;
+    }
+    HIPC(hipEventRecord(ctx->ev_begin, ctx->stream));
+    int rc = body();
+    if (ctx->guard) {
+        (void)hipStreamSynchronize(ctx->stream);
+        const int grc = guard_check(ctx, what);
+        if (rc == BWTS_OK) rc = grc;
+    }
+    if (rc != BWTS_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    HIPC(hipEventRecord(ctx->ev_end, ctx->stream));
+    BWTS_TRY(spans_resolve(ctx));
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
+    ctx->tm.total_ms = ms;
+    ctx->tm.device_bytes = ctx->arena_cap + ctx->d_seg_cap + ctx->d_seg_scratch_cap + ctx->call_block_bytes;
+    for (int i = 0; i < 4; i++) ctx->tm.device_bytes += ctx->d_io_cap[i];
+    for (int i = 0; i < BWTS_AUX_SLOTS; i++) ctx->tm.device_bytes += ctx->aux_cap[i];
+    ctx->tm.device_bytes += ctx->tied_blk.size() * ((size_t)16 << ctx->tied_blk_lg);
+    return BWTS_OK;
+}
+
+static bool ranges_overlap(const void *a, u64 na, const void *b, u64 nb)
+{
+    // by subtraction: a length as large as 2^64 - 1 must not wrap the comparison
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x <= y ? y - x < na : x - y < nb;
+}
+
+extern "C" uint64_t bwts_ec_bound(uint64_t n)
+{
+    return n == 0 || n > EC_MAX_N ? 0 : ec_bound_bytes(n);
+}
+
+extern "C" int bwts_ec_bound_segments(const uint64_t *lengths, uint64_t count, uint64_t *bound)
+{
+    if (!lengths || !bound || count == 0) return BWTS_E_ARG;
+    u64 sum = 0, total = 0;
+    for (u64 s = 0; s < count; s++) {
+        if (lengths[s] == 0 || lengths[s] > ~0ull - sum) return BWTS_E_ARG;
+        sum += lengths[s];
+        if (sum > 0x100000000ull) return BWTS_E_RANGE;
+        total += ec_bound_bytes(lengths[s]);
+    }
+    *bound = total;
+    return BWTS_OK;
+}
+
+extern "C" int bwts_ec_decoded_size(const uint8_t header[16], uint64_t in_bytes, uint64_t *n)
+{
+    if (!header || !n) return BWTS_E_ARG;
+    u64 v = 0;
+    if (in_bytes < EC_HEADER_BYTES || (in_bytes & 15) || ec_header_parse(header, &v) != 0) return BWTS_E_FORMAT;
+    if (v > EC_MAX_N) return BWTS_E_RANGE;
+    if (in_bytes < ec_least_bytes(v) || in_bytes > ec_bound_bytes(v)) return BWTS_E_FORMAT;
+    *n = v;
+    return BWTS_OK;
+}
+
+extern "C" int bwts_ec_encode_device(bwts_ctx *ctx, const void *d_in, uint64_t n, void *d_out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!ctx || !d_in || !d_out || !out_bytes || n == 0 || ((uintptr_t)d_out & 15)) return BWTS_E_ARG;
+    if (n > EC_MAX_N) return BWTS_E_RANGE;
+    if (ranges_overlap(d_in, n, d_out, out_cap)) return BWTS_E_ARG;
+    return run_sized(ctx, n, "ec encode", [&] { return ec_encode_impl(ctx, (const u8 *)d_in, n, (u8 *)d_out, out_cap, out_bytes, nullptr); });
+}
+
+extern "C" int bwts_ec_decode_device(bwts_ctx *ctx, const void *d_in, uint64_t in_bytes, void *d_out, uint64_t out_cap, uint64_t *n)
+{
+    if (!ctx || !d_in || !d_out || !n || in_bytes == 0 || ((uintptr_t)d_in & 15)) return BWTS_E_ARG;
+    if (in_bytes > ec_bound_bytes(EC_MAX_N)) return BWTS_E_RANGE;
+    if (ranges_overlap(d_in, in_bytes, d_out, out_cap)) return BWTS_E_ARG;
+    return run_sized(ctx, 0, "ec decode", [&] { return ec_decode_impl(ctx, (const u8 *)d_in, in_bytes, (u8 *)d_out, out_cap, n, nullptr); });
+}
+
+extern "C" int bwts_ec_encode_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out, uint64_t out_cap,
+                                              uint64_t *stream_bytes)
+{
+    if (!ctx || !d_in || !d_out || !stream_bytes || ((uintptr_t)d_out & 15)) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(set_segments(ctx, lengths, count, &n));
+    if (ranges_overlap(d_in, n, d_out, out_cap)) return BWTS_E_ARG;
+    return run_sized(ctx, n, "ec encode", [&] { return ec_encode_impl(ctx, (const u8 *)d_in, n, (u8 *)d_out, out_cap, nullptr, stream_bytes); });
+}
+
+extern "C" int bwts_ec_decode_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *stream_bytes, const uint64_t *lengths, uint64_t count,
+                                              void *d_out)
+{
+    if (!ctx || !d_in || !d_out || !stream_bytes || ((uintptr_t)d_in & 15)) return BWTS_E_ARG;
+    u64 n = 0, in_bytes = 0;
+    BWTS_TRY(set_segments(ctx, lengths, count, &n));
+    for (u64 s = 0; s < count; s++) {
+        if (stream_bytes[s] > ec_bound_bytes(lengths[s])) return BWTS_E_FORMAT;       // (so the sum cannot overflow)
+        in_bytes += stream_bytes[s];
+    }
+    if (ranges_overlap(d_in, in_bytes, d_out, n)) return BWTS_E_ARG;
+    return run_sized(ctx, n, "ec decode", [&] { return ec_decode_impl(ctx, (const u8 *)d_in, n, (u8 *)d_out, n, nullptr, stream_bytes); });
+}
+
+// Host buffers, staged simply: the input goes to the device, the device form runs, what it made comes back.  Nothing is written to out
+// before the device form has succeeded.
+extern "C" int bwts_ec_encode(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!ctx || !in || !out || !out_bytes || n == 0) return BWTS_E_ARG;
+    if (n > EC_MAX_N) return BWTS_E_RANGE;
+    const u64 cap = out_cap < ec_bound_bytes(n) ? out_cap : ec_bound_bytes(n);
+    if (cap < ec_least_bytes(n)) return BWTS_E_SPACE;
+    HIPC(hipSetDevice(ctx->device));
+    BWTS_TRY(ensure_io(ctx, n > cap ? n : cap, false));
+    Stager &sg = ctx->stg[0];
+    double t0 = wall_ms();
+    BWTS_TRY(staged_h2d(ctx, sg, ctx->d_io[0], in, n));
+    const double h2d = wall_ms() - t0;
+    u64 bytes = 0;
+    BWTS_TRY(bwts_ec_encode_device(ctx, ctx->d_io[0], n, ctx->d_io[2], cap, &bytes));
+    t0 = wall_ms();
+    BWTS_TRY(staged_d2h(ctx, sg, out, ctx->d_io[2], bytes, nullptr, nullptr));
+    ctx->tm.d2h_ms = wall_ms() - t0;
+    ctx->tm.h2d_ms = h2d;
+    *out_bytes = bytes;
+    return BWTS_OK;
+}
+
+extern "C" int bwts_ec_decode(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n)
+{
+    if (!ctx || !in || !out || !n || in_bytes == 0) return BWTS_E_ARG;
+    if (in_bytes > ec_bound_bytes(EC_MAX_N)) return BWTS_E_RANGE;
+    u64 v = 0;
+    BWTS_TRY(bwts_ec_decoded_size(in, in_bytes, &v));
+    if (v > out_cap) return BWTS_E_SPACE;
+    HIPC(hipSetDevice(ctx->device));
+    BWTS_TRY(ensure_io(ctx, in_bytes > v ? in_bytes : v, false));
+    Stager &sg = ctx->stg[0];
+    double t0 = wall_ms();
+    BWTS_TRY(staged_h2d(ctx, sg, ctx->d_io[0], in, in_bytes));
+    const double h2d = wall_ms() - t0;
+    u64 got = 0;
+    BWTS_TRY(bwts_ec_decode_device(ctx, ctx->d_io[0], in_bytes, ctx->d_io[2], v, &got));
+    t0 = wall_ms();
+    BWTS_TRY(staged_d2h(ctx, sg, out, ctx->d_io[2], got, nullptr, nullptr));
+    ctx->tm.d2h_ms = wall_ms() - t0;
+    ctx->tm.h2d_ms = h2d;
+    *n = got;
+    return BWTS_OK;
+}
+
 extern "C" int bwts_host_alloc(bwts_ctx *ctx, uint64_t bytes, void **h_ptr)
 {
     if (!ctx || !h_ptr) return BWTS_E_ARG;
@@ -1130,6 +1295,8 @@ extern "C" const char *bwts_strerror(int code)
     case BWTS_E_RANGE: return "input length beyond the engine's index range";
     case BWTS_E_INTERNAL: return "internal invariant violated";
     case BWTS_E_SINK: return "the caller's output sink reported an error";
+    case BWTS_E_FORMAT: return "not a valid entropy-coded stream";
+    case BWTS_E_SPACE: return "the result does not fit into the output buffer";
     default: return "unknown error";
     }
 }
@@ -1234,6 +1401,14 @@ extern "C" int bwts_debug_mtf_plan(uint64_t n, uint64_t out[4])
 {
     if (n == 0 || !out) return -1;
     bwts_mtf_plan(n, out);
+    return 0;
+}
+
+// the entropy coder's cut of one input of n bytes: tile size, tiles per block, tiles, blocks, the bound.  No context, no device
+extern "C" int bwts_debug_ec_plan(uint64_t n, uint64_t out[5])
+{
+    if (n == 0 || n > EC_MAX_N || !out) return -1;
+    bwts_ec_plan(n, out);
     return 0;
 }
 

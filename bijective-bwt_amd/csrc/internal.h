@@ -64,6 +64,9 @@ enum SegReportWord { SR_PLAN, SR_BIG, SR_RUNS, SR_OWN_SEGS, SR_OWN_BYTES, SR_SIN
 #define BWTS_AUX_SLOTS 5
 
 #define SM_RX_SYNC 4090          // d_small word holding the two 32-bit counters of radix_column_scan_fused_kernel (zero between launches)
+#define SM_EC_TOTAL 4020         // entropy coder (ec.hip): d_small word for the bytes of all payloads of an encode
+#define SM_EC_FLAG  4021         // ... d_small word for what a decode found wrong (0: nothing)
+#define SM_EC_HEAD  4022         // ... h_small, two words: the header of a single stream
 
 struct Stager {
     hipStream_t stream;             // the queue its copies (and copy kernels) are issued on
@@ -271,6 +274,12 @@ int mtf_forward_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out); 
 int mtf_inverse_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
 size_t mtf_arena_bytes(const bwts_ctx *ctx, u64 n, bool segments);     // what a call reserves: 256 bytes per tile and a little per group
 void bwts_mtf_plan(u64 n, u64 out[4]);                                  // tile size, tiles per group, tiles and groups of one input of n bytes
+
+// ---- entropy coding behind move-to-front (ec.hip) -----------------------------------
+// stream_bytes == null: one input / one stream; else the context's segment table, one stream size per segment (written / read)
+int ec_encode_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, u64 out_cap, u64 *out_bytes, u64 *stream_bytes);
+int ec_decode_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out, const u64 *stream_bytes);
+void bwts_ec_plan(u64 n, u64 out[5]);                                   // tile size, tiles per block, tiles, blocks and the bound of one input
 
 // chunk tables of the forward's later rounds (chunk_rounds.h) as plain arithmetic: nominal chunk size of a list, the tables' capacity
 // for a tied list of a0, and the re-cut of the a_chunks elements left at a compaction (allowed = the new chunks fit the tables)

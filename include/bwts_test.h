@@ -103,6 +103,11 @@ int bwts_debug_segments_report(bwts_ctx *ctx, uint64_t out[8]);
 #define BWTS_FWD_SORT_WORDS (BWTS_FWD_HEADER_WORDS + BWTS_MAX_ROUND_STATS * BWTS_FWD_ROUND_WORDS)
 int bwts_debug_forward_report(bwts_ctx *ctx, uint64_t *out, uint64_t cap_words, uint64_t *sorts);
 
+/* Pure arithmetic, no context and no device: how the entropy coder (bwts_ec.h) cuts one input of 1 <= n <= 2^36 bytes.  out = {T, the
+ * tile size in bytes; K, the tiles that share one frequency table; tiles = ceil(n / T); blocks = ceil(tiles / K); the bound of the
+ * stream in bytes}.  Returns 0, -1 on a bad argument. */
+int bwts_debug_ec_plan(uint64_t n, uint64_t out[5]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,12 +74,15 @@ FWD_SORT_WORDS = FWD_HEADER_WORDS + MAX_ROUND_STATS * FWD_ROUND_WORDS
 FWD_HEADER_FIELDS = ["cyclic", "n", "k", "sigma", "bits", "msym", "key_bits", "varlen", "hstep", "keys", "flags_outside_rank", "tied0",
                      "rank_early", "form", "no_chunks", "need_sa", "end", "rest_chunks", "rest_big", "rest_tiles", "rounds", "directory",
                      "order_sort", "left"]
+FWD_DIRECT_WORD = 36            # header word: what became of the direct form
+FWD_DIRECT = {0: "not_tried", 1: "settled", 2: "fallback_group", 3: "fallback_depth"}
 FWD_CHUNK_FIELDS = ["S", "maxchunks", "a_small", "big0", "m_exit", "m_stay", "groups", "wide_possible", "fsl", "compactions",
                     "compactions_skipped", "enqueued_behind_last"]
 FWD_ROUND_FIELDS = {"sparse": ["form", "h", "in", "out", "splits", "probe", "m_big", "whole", "skip_next"],
                     "chunks": ["form", "h", "in", "out", "splits", "chunks_in", "chunks_out", "big_in", "big_stays", "big_leaves", "nchunks"],
-                    "tiles": ["form", "h", "in", "out", "splits", "m_big"]}
-FWD_FORMS = {0: "none", 1: "sparse", 2: "chunks", 3: "tiles"}
+                    "tiles": ["form", "h", "in", "out", "splits", "m_big"],
+                    "direct": ["form", "h", "in", "out", "splits"]}
+FWD_FORMS = {0: "none", 1: "sparse", 2: "chunks", 3: "tiles", 4: "direct"}
 FWD_KEYS = {0: "wide", 1: "split32", 2: "split40"}
 FWD_NO_CHUNKS = {0: None, 1: "short_list", 2: "knob", 3: "no_room_store", 4: "no_room_order", 5: "no_room_biglist"}
 FWD_ENDS = {0: "none", 1: "empty", 2: "stable"}
@@ -520,7 +523,8 @@ class Context:
 
     def debug_forward_report(self):
         """One dict per doubling sort of the most recent forward call on this context (also debug_suffix_array / debug_lyndon), in the
-        order they ran: the header (FWD_HEADER_FIELDS; form, keys, no_chunks and end by name, flags as bool), "chunks" (FWD_CHUNK_FIELDS)
+        order they ran: the header (FWD_HEADER_FIELDS; form, keys, no_chunks and end by name, flags as bool; "direct" / "direct_word": header
+        word 36 by name and as the number), "chunks" (FWD_CHUNK_FIELDS)
         when the chunk form ran, and "round": one dict per recorded round after round 0 (FWD_ROUND_FIELDS of its form)."""
         buf = (ctypes.c_uint64 * (2 * FWD_SORT_WORDS))()
         made = ctypes.c_uint64(0)
@@ -532,6 +536,7 @@ class Context:
             w = [int(v) for v in buf[a * FWD_SORT_WORDS:(a + 1) * FWD_SORT_WORDS]]
             d = {f: w[i] for i, f in enumerate(FWD_HEADER_FIELDS)}
             d["form"], d["keys"], d["no_chunks"], d["end"] = FWD_FORMS[d["form"]], FWD_KEYS[d["keys"]], FWD_NO_CHUNKS[d["no_chunks"]], FWD_ENDS[d["end"]]
+            d["direct"], d["direct_word"] = FWD_DIRECT[w[FWD_DIRECT_WORD]], w[FWD_DIRECT_WORD]
             for f in ("cyclic", "varlen", "flags_outside_rank", "rank_early", "need_sa", "order_sort"):
                 d[f] = bool(d[f])
             if d["form"] == "chunks":

@@ -1172,7 +1172,7 @@ struct SortSpace : SortBufs {               // 1. buffers: keys, vals (n each), 
     u32 *first_hist = nullptr;
     const u32 *tie_slots = nullptr;         // tied_list(): the round-0 tie list (slots), for patching the carried bytes of elements
     u64 tie_count = 0;                      // that later rounds reorder
-    bool ties_emitted = false;              // doubling_sort(): the later rounds wrote the bytes of the tied elements themselves (dense rounds)
+    bool ties_emitted = false;              // doubling_sort(): the later rounds wrote the bytes of the tied elements themselves (direct, dense)
 };
 
 // the dense rank array (4 n bytes) exists only for inputs that need it: many ties after round 0, a suffix array with ranks, or a
@@ -1350,13 +1350,14 @@ enum FwdReportWord { FR_CYCLIC, FR_N, FR_K, FR_SIGMA, FR_BITS, FR_MSYM, FR_KEY_B
                      FR_TIED0, FR_RANK_EARLY, FR_FORM, FR_NO_CHUNKS, FR_NEED_SA, FR_END, FR_REST_CHUNKS, FR_REST_BIG, FR_REST_TILES,
                      FR_ROUNDS, FR_DIRECTORY, FR_ORDER_SORT, FR_LEFT,
                      FC_S = 24, FC_MAXCHUNKS, FC_A_SMALL, FC_BIG0, FC_M_EXIT, FC_M_STAY, FC_GROUPS, FC_WIDE_POSSIBLE, FC_FSL, FC_COMPACTIONS,
-                     FC_COMPACTIONS_SKIPPED, FC_ENQUEUED_BEHIND_LAST };
+                     FC_COMPACTIONS_SKIPPED, FC_ENQUEUED_BEHIND_LAST,
+                     FR_DIRECT = 36 /* FwdDirect: what became of the direct form */ };
 enum FwdRoundWord { FRR_FORM, FRR_H, FRR_IN, FRR_OUT, FRR_SPLITS, FRR_PROBE = 5, FRR_MBIG, FRR_WHOLE, FRR_SKIP_NEXT,
                     FRR_CHUNKS_IN = 5, FRR_CHUNKS_OUT, FRR_BIG_IN, FRR_BIG_STAYS, FRR_BIG_LEAVES, FRR_NCHUNKS, FRR_TILE_MBIG = 5 };
-enum FwdForm { FR_FORM_NONE, FR_FORM_SPARSE, FR_FORM_CHUNKS, FR_FORM_TILES };
+enum FwdForm { FR_FORM_NONE, FR_FORM_SPARSE, FR_FORM_CHUNKS, FR_FORM_TILES, FR_FORM_DIRECT };
 enum FwdNoChunks { FR_NC_NA, FR_NC_SHORT, FR_NC_KNOB, FR_NC_STORE, FR_NC_ORDER, FR_NC_BIGLIST };
 enum FwdEnd { FR_END_NONE, FR_END_EMPTY, FR_END_STABLE };
-static_assert(FC_ENQUEUED_BEHIND_LAST < FWD_HEADER_WORDS && FRR_NCHUNKS < FWD_ROUND_WORDS && FR_LEFT < FC_S, "the forward report's layout");
+static_assert(FC_ENQUEUED_BEHIND_LAST < FR_DIRECT && FR_DIRECT < FWD_HEADER_WORDS && FRR_NCHUNKS < FWD_ROUND_WORDS && FR_LEFT < FC_S, "the forward report's layout");
 static u64 *fwd_report_open(bwts_ctx *ctx)
 {
     u64 *w = ctx->fwd_report[ctx->fwd_sorts_made < FWD_REPORT_SORTS ? ctx->fwd_sorts_made : FWD_REPORT_SORTS - 1];
@@ -1474,6 +1475,126 @@ static int tied_list(bwts_ctx *ctx, u64 n, SortSpace &sp, const Round0 &r0, Acti
     sp.tie_slots = cur->slot;        // stays untouched by the later rounds
     sp.tie_count = r0.a;
     return BWTS_OK;
+}
+
+// ---- few ties, shallow: every tied group ordered by comparing its members' rotations --------------------------------------
+// After round 0 on an i.i.d.-like input the tied positions are a fraction of a percent of n, nearly all in pairs, and two tied
+// rotations differ a few symbols behind what the key covered.  Ordering them needs no rank of any other position: the thread at a
+// group's first list element (the list is in slot order, so a group is a run of equal heads) sorts the members by insertion,
+// comparing their rotations inside their own Lyndon factors from symbol `skip` (al.hstep: what every key covers) on, sixteen bytes
+// at a time away from the factors' wraps, and writes the members' carried bytes T[cprev(p)] into the group's slots.  SA, the list
+// and the sorted keys stay as they are, so when any group does not fit -- more than DIRECT_GROUP members, or two rotations still
+// equal after DIRECT_DEPTH symbols whose periods sum to more than that (below it, Fine and Wilf: equal for ever, the same byte
+// either way) -- the flag is raised, every thread leaves at its next look at it, and the sparse rounds run as if nothing had been.
+#define DIRECT_GROUP 8          // SEG_CAP: the groups the sparse rounds sort in place
+#define DIRECT_DEPTH 640u       // symbols compared before a pair is given up: every thread resident with the first to get there has read
+                                // as many by then, which is what a fallback costs (0.1 ms at 2^28 positions with 2^20 tied)
+#define DIRECT_POLL  64u        // compared symbols between two looks at the flag
+#define CNT_DIRECT   (SM_COUNTERS + 28)
+enum FwdDirect { FR_DIRECT_NONE, FR_DIRECT_SETTLED, FR_DIRECT_GROUP, FR_DIRECT_DEEP };
+static_assert(DIRECT_GROUP >= SEG_CAP, "the direct form takes every group the small-groups sort takes");
+
+enum RotCmp { ROT_LESS, ROT_NOT_LESS, ROT_DEEP, ROT_STOP };
+// the rotation at offset op of factor [ps, ps + pl) against the one at offset oq of [qs, qs + ql)
+__device__ __forceinline__ RotCmp rotation_less(const u8 *__restrict__ T, u64 ps, u64 pl, u64 op, u64 qs, u64 ql, u64 oq, const u64 *flag)
+{
+    const u64 lim = pl + ql < DIRECT_DEPTH ? pl + ql : DIRECT_DEPTH;
+    u64 next_poll = DIRECT_POLL;
+    for (u64 d = 0; d < lim;) {
+        if (pl - op >= 16 && ql - oq >= 16) {
+            u64 x[2], y[2];
+            __builtin_memcpy(x, T + ps + op, 16);
+            __builtin_memcpy(y, T + qs + oq, 16);
+            const int w = x[0] != y[0] ? 0 : 1;
+            if (x[w] != y[w]) {
+                const int sh = (__ffsll((unsigned long long)(x[w] ^ y[w])) - 1) & ~7;
+                return ((x[w] >> sh) & 255u) < ((y[w] >> sh) & 255u) ? ROT_LESS : ROT_NOT_LESS;
+            }
+            op += 16; oq += 16; d += 16;
+        } else {
+            const u8 cp = T[ps + op], cq = T[qs + oq];
+            if (cp != cq) return cp < cq ? ROT_LESS : ROT_NOT_LESS;
+            op++; oq++; d++;
+        }
+        if (op == pl) op = 0;
+        if (oq == ql) oq = 0;
+        if (d >= next_poll) {
+            if (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return ROT_STOP;
+            next_poll += DIRECT_POLL;
+        }
+    }
+    return pl + ql > DIRECT_DEPTH ? ROT_DEEP : ROT_NOT_LESS;
+}
+
+__global__ __launch_bounds__(256) void direct_ties_kernel(const u32 *__restrict__ idx, const u32 *__restrict__ head, u64 a,
+                                                          const u8 *__restrict__ T, u64 n, const u32 *__restrict__ fstart, u64 k, u64 skip,
+                                                          u8 *__restrict__ out, u64 *flag)
+{
+    // a member: its position, its factor's first and last position (the length itself may be 2^32)
+    __shared__ u32 s_pos[DIRECT_GROUP][256], s_first[DIRECT_GROUP][256], s_last[DIRECT_GROUP][256];
+    const int t = threadIdx.x;
+    const u64 i = (u64)blockIdx.x * 256 + t;
+    if (i >= a) return;
+    const u32 h0 = head[i];
+    if (i > 0 && head[i - 1] == h0) return;
+    if (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+    u32 cnt = 1;
+    while (cnt <= DIRECT_GROUP && i + cnt < a && head[i + cnt] == h0) cnt++;
+    if (cnt > DIRECT_GROUP) { atomicCAS((unsigned long long *)flag, 0ull, (unsigned long long)FR_DIRECT_GROUP); return; }
+    for (u32 j = 0; j < cnt; j++) {
+        const u32 p = idx[i + j];
+        const u64 f = factor_of(fstart, k, p);
+        s_pos[j][t] = p; s_first[j][t] = fstart[f]; s_last[j][t] = (u32)(factor_end(fstart, k, n, f) - 1);
+    }
+    for (u32 m = 1; m < cnt; m++) {
+        const u32 p = s_pos[m][t], pf = s_first[m][t], pe = s_last[m][t];
+        const u64 ps = pf, pl = (u64)pe - pf + 1, op = ((u64)p - pf + skip) % pl;
+        u32 j = m;
+        while (j > 0) {
+            const u32 q = s_pos[j - 1][t], qf = s_first[j - 1][t], qe = s_last[j - 1][t];
+            const u64 ql = (u64)qe - qf + 1;
+            const RotCmp c = rotation_less(T, ps, pl, op, qf, ql, ((u64)q - qf + skip) % ql, flag);
+            if (c == ROT_STOP) return;
+            if (c == ROT_DEEP) { atomicCAS((unsigned long long *)flag, 0ull, (unsigned long long)FR_DIRECT_DEEP); return; }
+            if (c != ROT_LESS) break;
+            s_pos[j][t] = q; s_first[j][t] = qf; s_last[j][t] = qe;
+            j--;
+        }
+        s_pos[j][t] = p; s_first[j][t] = pf; s_last[j][t] = pe;
+    }
+    // the carried byte, as patch_ties_kernel finds it: a factor's first position takes the factor's last byte
+    for (u32 j = 0; j < cnt; j++) {
+        const u32 p = s_pos[j][t];
+        out[(u64)h0 + j] = T[p == s_first[j][t] ? s_last[j][t] : p - 1];
+    }
+}
+
+// Runs the kernel and reads its flag: FR_DIRECT_SETTLED when every tied slot now holds its byte, else why the list goes to the sparse rounds
+static int direct_ties(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, const u32 *d_fstart, u64 k, const SortSpace &sp,
+                       const ActiveList &cur, u64 a, u64 *outcome)
+{
+    u64 *flag = ctx->d_small + CNT_DIRECT;
+    HIPC(hipMemsetAsync(flag, 0, sizeof(u64), ctx->stream));
+    {
+        SpanGuard g(ctx, BWTS_K_RERANK, a, 24 * a);
+        direct_ties_kernel<<<dim3((unsigned)((a + 255) / 256)), dim3(256), 0, ctx->stream>>>(cur.idx, cur.head, a, d_T, n, d_fstart, k, (u64)al.hstep,
+                                                                                             sp.carry_out, flag);
+        HIPC(hipGetLastError());
+        STAGE("direct ties");
+    }
+    BWTS_TRY(read_small(ctx, CNT_DIRECT, 1));
+    const u64 f = ctx->h_small[CNT_DIRECT];
+    if (f != 0 && f != FR_DIRECT_GROUP && f != FR_DIRECT_DEEP) return BWTS_E_INTERNAL;
+    *outcome = f ? f : (u64)FR_DIRECT_SETTLED;
+    return BWTS_OK;
+}
+// positions from which the direct form is the default (BWTS_DIRECT_MIN_LOG2, a test switch, moves the line; 64: never)
+static bool direct_ties_allowed(const bwts_ctx *ctx, u64 n)
+{
+    int lg = 24;
+    if (const char *e = bwts_knob(ctx, "BWTS_DIRECT_MIN_LOG2")) lg = atoi(e);
+    if (lg < 0) lg = 0;
+    return lg < 64 && n >= (1ull << lg);
 }
 
 // the buffers of the sparse rounds' small-groups path: flags, compacted keys x2, values x2, slots of the larger groups
@@ -1662,8 +1783,8 @@ static int sparse_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
 
 // Sorts all positions by their (cyclic | suffix) word.  sp.keys[0]/sp.vals[0] hold the round-0
 // keys and the identity on entry.  want_ranks: leave final ranks in sp.rank (ISA for the suffix sort).
-// Round 0, the dense ranks when many elements are tied, the tied list, then the later rounds in one of three forms: sparse_rounds,
-// chunk_rounds, dense_rounds (tiles).
+// Round 0, the dense ranks when many elements are tied, the tied list, then the later rounds in one of four forms: direct_ties (few
+// ties, the byte rode round 0; a list it cannot settle goes on to the next), sparse_rounds, chunk_rounds, dense_rounds (tiles).
 template <bool CYCLIC>
 static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, const u32 *d_fstart, u64 k,
                          SortSpace &sp, bool want_ranks, u32 **sa_out, u32 *rounds_out, u64 *active0_out)
@@ -1690,8 +1811,22 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
     if (a > 0xffffffffull) return BWTS_E_NOMEM;
     // few tied elements: sparse rank map; many (real text ties most m-grams): the dense rank array
     if (a > 0 && a <= n / 32) {
-        rep[FR_FORM] = FR_FORM_SPARSE;
-        BWTS_TRY((sparse_rounds<CYCLIC>(ctx, d_T, n, al, d_fstart, k, sp, r0, &cur, &a, &rounds)));
+        // the cyclic sort whose bytes rode round 0 (only the tied slots are left to write) first tries to settle every group by
+        // comparing rotations; all or nothing: a list it cannot settle goes to the sparse rounds untouched
+        u64 direct = FR_DIRECT_NONE;
+        if (CYCLIC && sp.carry_out && !want_ranks && direct_ties_allowed(ctx, n)) BWTS_TRY(direct_ties(ctx, d_T, n, al, d_fstart, k, sp, cur, a, &direct));
+        rep[FR_DIRECT] = direct;
+        if (direct == FR_DIRECT_SETTLED) {
+            rounds++;
+            if (u64 *rr = fwd_report_round(ctx, rounds)) { rr[FRR_FORM] = FR_FORM_DIRECT; rr[FRR_H] = (u64)al.hstep; rr[FRR_IN] = a; rr[FRR_OUT] = 0; rr[FRR_SPLITS] = 1; }
+            if (rounds - 1 < BWTS_MAX_ROUND_STATS) ctx->tm.round_active[rounds - 1] = 0;
+            rep[FR_FORM] = FR_FORM_DIRECT; rep[FR_END] = FR_END_EMPTY;
+            sp.ties_emitted = true;
+            a = 0;
+        } else {
+            rep[FR_FORM] = FR_FORM_SPARSE;
+            BWTS_TRY((sparse_rounds<CYCLIC>(ctx, d_T, n, al, d_fstart, k, sp, r0, &cur, &a, &rounds)));
+        }
         rep[FR_ROUNDS] = rounds; rep[FR_LEFT] = a;
     } else if (a > 0) {
         BWTS_TRY(ensure_rank(ctx, sp, n));

@@ -82,18 +82,19 @@ int bwts_debug_segments_report(bwts_ctx *ctx, uint64_t out[8]);
  * segmented call's shared pass before its last sort.
  * Header, words 0..47: 0 cyclic (1) or suffix form (0); 1 n; 2 factors k (0: suffix form); 3 sigma; 4 bits per symbol; 5 msym;
  * 6 key_bits; 7 varlen; 8 hstep; 9 keys: 0 one u64 each, 1 split without the high byte, 2 split with it; 10 flags_outside_rank;
- * 11 tied after round 0; 12 rank_early; 13 form of the later rounds: 0 none, 1 sparse, 2 chunks, 3 tiles; 14 why chunks did not
- * apply (form 3 only): 1 list shorter than CH_MIN_LIST, 2 BWTS_DENSE=tiles, 3 no room for the store, 4 no room for the order block,
+ * 11 tied after round 0; 12 rank_early; 13 form of the later rounds: 0 none, 1 sparse, 2 chunks, 3 tiles, 4 direct (every tied group
+ * ordered by comparing its members' rotations: one round, no rank of any other position); 14 why chunks did not apply (form 3 only): 1 list shorter than CH_MIN_LIST, 2 BWTS_DENSE=tiles, 3 no room for the store, 4 no room for the order block,
  * 5 no room for the big list; 15 need_sa (forms 2 and 3; else 0); 16 how the rounds ended: 0 there were none, 1 list empty, 2 no group split; 17, 18, 19
  * elements the stable finish laid out from chunks, from the big list, from the tile list; 20 rounds, round 0 included; 21 sparse:
  * log2 of the key directory's size, 0 without one; 22 tiles: the one-off order sort ran; 23 tied when the rounds ended.
  * Chunks, words 24..35: 24 S, the nominal chunk size at the start; 25 maxchunks; 26 a_small, elements of groups of at most 256;
  * 27 the big list's first size; 28, 29, 30 m_exit, m_stay and groups staying of the first split; 31 wide_possible; 32 factor
  * starts in LDS (1) or the general instantiation (0); 33 compactions done; 34 compactions chunk_recut_plan refused; 35 a round was
- * enqueued behind the last one.  Words 36..47 stay 0; so do all of 24..47 when the chunk form did not run to its end (form 3
- * after a hand-over included).
+ * enqueued behind the last one.  All of 24..35 stay 0 when the chunk form did not run to its end (form 3 after a hand-over included).
+ * 36 the direct form: 0 not tried, 1 all groups settled (form 4), 2 fell back to the sparse rounds on a group above its cap, 3 fell
+ * back on two rotations equal beyond its depth.  Words 37..47 stay 0.
  * Rounds, BWTS_FWD_ROUND_WORDS words each, the first BWTS_MAX_ROUND_STATS rounds after round 0 (those past that are counted in word 20
- * and leave no record): 0 form, as header word 13; 1 h; 2 list going in; 3 list coming out; 4 a group split in this round (1) or none did (0); then sparse: 5 probe: 0 list of at most 4096, 1 ran, 2 skipped after skip_next; 6 m_big; 7 whole; 8 skip_next;
+ * and leave no record): 0 form, as header word 13; 1 h; 2 list going in; 3 list coming out; 4 a group split in this round (1) or none did (0; direct: always 1); then sparse: 5 probe: 0 list of at most 4096, 1 ran, 2 skipped after skip_next; 6 m_big; 7 whole; 8 skip_next;
  * chunks: 5, 6 elements in chunks before and after; 7, 8, 9 big list before, stays, leaves; 10 chunks in the tables;
  * tiles: 5 m_big.
  * out receives whole records while they fit into cap_words; *sorts = sorts the call made.  Returns the records written, < 0 on a

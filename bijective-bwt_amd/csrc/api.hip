@@ -1,10 +1,11 @@
-// api.hip -- the C-ABI of include/bwts.h: context, arenas, staging, timing, test hooks.
+// api.hip -- the C-ABI of include/bwts.h: context, staging, timing, test hooks (the context's device memory: ctx_memory.hip).
 #include "internal.h"
 #include "../../include/bwts_test.h"
 #include "../../include/bwts_mtf.h"
 #include "../../include/bwts_ec.h"
 #include "ec_plan.h"
 
+#include <algorithm>
 #include <new>
 #include <stdio.h>
 #include <time.h>
@@ -59,97 +60,6 @@ const char *bwts_knob(const bwts_ctx *ctx, const char *name)
     return nullptr;
 }
 
-// ------------------------------------------------------------------------------------
-// arenas
-// ------------------------------------------------------------------------------------
-// BWTS_POISON=1 (a test switch): every block handed to a transform is filled with 0xA5 first, so that a kernel which reads memory
-// nothing has written yet does so reproducibly -- whatever an earlier call or process left there -- instead of once in a blue moon
-static bool poison_on(const bwts_ctx *ctx) { const char *e = bwts_knob(ctx, "BWTS_POISON"); return e && e[0] == '1'; }
-
-// device blocks of the context, with guard bands when BWTS_GUARD=1
-#define GUARD_BYTE 0x5C
-#define GUARD_FREED 0x5D
-// BWTS_TRACE_ALLOC=1: every block the context takes or gives up, with its address range, on stderr -- the map a GPU memory fault's
-// address is read against
-static void trace_alloc(const bwts_ctx *ctx, const char *what, const char *name, const void *p, size_t bytes)
-{
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("BWTS_TRACE_ALLOC"); on = (e && e[0] == '1') ? 1 : 0; }
-    if (on) fprintf(stderr, "[bwts alloc] ctx %p %s %-16s [%p, %p) %zu bytes\n", (const void *)ctx, what, name, p, (const void *)((const char *)p + bytes), bytes);
-}
-static hipError_t ctx_malloc(bwts_ctx *ctx, void **out, size_t bytes, const char *name)
-{
-    if (!ctx->guard) { const hipError_t e0 = hipMalloc(out, bytes); if (e0 == hipSuccess) trace_alloc(ctx, "device +", name, *out, bytes); return e0; }
-    void *p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes + 2 * ctx->guard);
-    if (e != hipSuccess) return e;
-    e = hipMemset(p, GUARD_BYTE, ctx->guard);
-    if (e == hipSuccess) e = hipMemset((char *)p + ctx->guard + bytes, GUARD_BYTE, ctx->guard);
-    if (e != hipSuccess) { (void)hipFree(p); return e; }
-    *out = (char *)p + ctx->guard;
-    ctx->guard_blocks.push_back({(char *)*out, bytes, name});
-    return hipSuccess;
-}
-static hipError_t ctx_free(bwts_ctx *ctx, void *user)
-{
-    trace_alloc(ctx, "device -", "", user, 0);
-    if (!ctx->guard) return hipFree(user);
-    for (size_t i = 0; i < ctx->guard_blocks.size(); i++)
-        if (ctx->guard_blocks[i].user == (char *)user) {
-            const bwts_ctx::GuardBlock b = ctx->guard_blocks[i];
-            ctx->guard_blocks.erase(ctx->guard_blocks.begin() + (long)i);
-            // blocks of up to 64 MiB are not handed back: they stay mapped, filled with a pattern that guard_check() looks at
-            if (b.bytes <= ((size_t)64 << 20) && hipDeviceSynchronize() == hipSuccess &&
-                hipMemset((char *)user - ctx->guard, GUARD_FREED, b.bytes + 2 * ctx->guard) == hipSuccess) {
-                ctx->guard_freed.push_back(b);
-                return hipSuccess;
-            }
-            break;
-        }
-    return hipFree((char *)user - ctx->guard);
-}
-// after a transform: are all guard bands intact?
-static int guard_check(bwts_ctx *ctx, const char *what)
-{
-    if (!ctx->guard) return BWTS_OK;
-    std::vector<unsigned char> h(ctx->guard);
-    int bad = 0;
-    for (const auto &b : ctx->guard_blocks)
-        for (int side = 0; side < 2; side++) {
-            const char *src = side == 0 ? b.user - ctx->guard : b.user + b.bytes;
-            HIPC(hipMemcpy(h.data(), src, ctx->guard, hipMemcpyDeviceToHost));
-            size_t first = ctx->guard, last = 0, count = 0;
-            for (size_t i = 0; i < ctx->guard; i++)
-                if (h[i] != GUARD_BYTE) { if (first == ctx->guard) first = i; last = i; count++; }
-            if (count) {
-                bad++;
-                fprintf(stderr, "[bwts guard] %s: block '%s' (%zu bytes): %zu byte(s) written %s it, offsets %ld .. %ld relative to the block's %s; first bytes:", what,
-                        b.name, b.bytes, count, side == 0 ? "IN FRONT OF" : "BEHIND", side == 0 ? (long)first - (long)ctx->guard : (long)first,
-                        side == 0 ? (long)last - (long)ctx->guard : (long)last, side == 0 ? "start" : "end");
-                for (size_t i = first; i < first + 16 && i < ctx->guard; i++) fprintf(stderr, " %02x", h[i]);
-                fprintf(stderr, "\n");
-                HIPC(hipMemset((void *)src, GUARD_BYTE, ctx->guard));
-            }
-        }
-    for (const auto &b : ctx->guard_freed) {
-        const size_t total = b.bytes + 2 * ctx->guard;
-        std::vector<unsigned char> f(total);
-        HIPC(hipMemcpy(f.data(), b.user - ctx->guard, total, hipMemcpyDeviceToHost));
-        size_t first = total, last = 0, count = 0;
-        for (size_t i = 0; i < total; i++)
-            if (f[i] != GUARD_FREED) { if (first == total) first = i; last = i; count++; }
-        if (count) {
-            bad++;
-            fprintf(stderr, "[bwts guard] %s: GIVEN-UP block '%s' (%zu bytes) was written after the context let go of it: %zu byte(s), offsets %ld .. %ld from its start; first bytes:",
-                    what, b.name, b.bytes, count, (long)first - (long)ctx->guard, (long)last - (long)ctx->guard);
-            for (size_t i = first; i < first + 16 && i < total; i++) fprintf(stderr, " %02x", f[i]);
-            fprintf(stderr, "\n");
-            HIPC(hipMemset(b.user - ctx->guard, GUARD_FREED, total));
-        }
-    }
-    return bad ? BWTS_E_INTERNAL : BWTS_OK;
-}
-
 void bwts_stage_mark(bwts_ctx *ctx, const char *name)
 {
     static int on = -1;
@@ -158,83 +68,6 @@ void bwts_stage_mark(bwts_ctx *ctx, const char *name)
     const hipError_t e = hipStreamSynchronize(ctx->stream);
     fprintf(stderr, "[bwts stage] %s %s\n", name, e == hipSuccess ? "ok" : "FAILED");
     fflush(stderr);
-}
-
-// The arena changes hands on the thread that owns the context, and only with the context's stream drained: nothing that was
-// enqueued can still use the block that is given up.
-int arena_release(bwts_ctx *ctx)
-{
-    if (!ctx->arena) return BWTS_OK;
-    HIPC(hipStreamSynchronize(ctx->stream));
-    HIPC(ctx_free(ctx, ctx->arena));
-    ctx->arena = nullptr;
-    ctx->arena_cap = 0;
-    ctx->arena_off = 0;
-    return BWTS_OK;
-}
-
-void arena_install(bwts_ctx *ctx, void *block, size_t bytes, double alloc_ms)
-{
-    trace_alloc(ctx, "device +", "arena", block, bytes);
-    ctx->arena = (char *)block;
-    ctx->arena_cap = bytes;
-    ctx->arena_off = 0;
-    ctx->host_ms[BWTS_H_ARENA_ALLOC] += alloc_ms;
-}
-
-int arena_reserve(bwts_ctx *ctx, size_t bytes)
-{
-    bytes = align_up(bytes, 1 << 20);
-    if (bytes > ctx->arena_cap) {
-        const double t0 = wall_ms();
-        BWTS_TRY(arena_release(ctx));
-        void *p = nullptr;
-        if (ctx_malloc(ctx, &p, bytes, "arena") != hipSuccess) { (void)hipGetLastError(); return BWTS_E_NOMEM; }
-        ctx->arena = (char *)p;
-        ctx->arena_cap = bytes;
-        ctx->host_ms[BWTS_H_ARENA_ALLOC] += wall_ms() - t0;
-    }
-    ctx->arena_off = 0;
-    if (ctx->arena && poison_on(ctx)) HIPC(hipMemsetAsync(ctx->arena, 0xA5, ctx->arena_cap, ctx->stream));
-    return BWTS_OK;
-}
-
-void arena_reset(bwts_ctx *ctx) { ctx->arena_off = 0; }
-
-void *arena_alloc(bwts_ctx *ctx, size_t bytes)
-{
-    bytes = align_up(bytes ? bytes : 1, 256);
-    if (ctx->arena_off + bytes > ctx->arena_cap) return nullptr;
-    void *p = ctx->arena + ctx->arena_off;
-    trace_alloc(ctx, "  arena:", "array", p, bytes);
-    ctx->arena_off += bytes;
-    return p;
-}
-
-int aux_reserve_slot(bwts_ctx *ctx, int slot, size_t bytes, char **base)
-{
-    bytes = align_up(bytes, 1 << 20);
-    if (bytes > ctx->aux_cap[slot]) {
-        const double t0 = wall_ms();
-        // contents of a previous, smaller block are never live across this call
-        if (ctx->aux[slot]) { HIPC(hipStreamSynchronize(ctx->stream)); HIPC(ctx_free(ctx, ctx->aux[slot])); ctx->aux[slot] = nullptr; ctx->aux_cap[slot] = 0; }
-        void *p = nullptr;
-        static const char *const aux_names[BWTS_AUX_SLOTS] = {"side block 0", "side block 1", "side block 2", "side block 3", "side block 4"};
-        if (ctx_malloc(ctx, &p, bytes, aux_names[slot]) != hipSuccess) { (void)hipGetLastError(); return BWTS_E_NOMEM; }
-        ctx->aux[slot] = (char *)p;
-        ctx->aux_cap[slot] = bytes;
-        ctx->host_ms[BWTS_H_ARENA_ALLOC] += wall_ms() - t0;
-    }
-    *base = ctx->aux[slot];
-    if (ctx->aux[slot] && poison_on(ctx)) HIPC(hipMemsetAsync(ctx->aux[slot], 0xA5, ctx->aux_cap[slot], ctx->stream));
-    return BWTS_OK;
-}
-
-int aux_release(bwts_ctx *ctx)
-{
-    for (int i = 0; i < BWTS_AUX_SLOTS; i++)
-        if (ctx->aux[i]) { HIPC(hipStreamSynchronize(ctx->stream)); HIPC(ctx_free(ctx, ctx->aux[i])); ctx->aux[i] = nullptr; ctx->aux_cap[i] = 0; }
-    return BWTS_OK;
 }
 
 int ensure_dyn_lds(bwts_ctx *ctx, const void *kernel, size_t bytes)
@@ -344,12 +177,9 @@ extern "C" void bwts_ctx_destroy(bwts_ctx *ctx)
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
-    if (ctx->arena) (void)ctx_free(ctx, ctx->arena);
-    for (int i = 0; i < BWTS_AUX_SLOTS; i++) if (ctx->aux[i]) (void)ctx_free(ctx, ctx->aux[i]);
-    for (char *b : ctx->tied_blk) (void)hipFree(b);
+    for (KeptBlock &b : ctx->kept) (void)kept_give_up(ctx, b);
+    (void)tied_release(ctx);
     if (ctx->d_small) (void)ctx_free(ctx, ctx->d_small);
-    if (ctx->d_seg_off) (void)ctx_free(ctx, ctx->d_seg_off);
-    if (ctx->d_seg_scratch) (void)ctx_free(ctx, ctx->d_seg_scratch);
     if (ctx->h_seg_off) (void)hipHostFree(ctx->h_seg_off);
     for (const auto &b : ctx->guard_freed) (void)hipFree(b.user - ctx->guard);
     ctx->guard_freed.clear();
@@ -364,28 +194,23 @@ extern "C" void bwts_ctx_destroy(bwts_ctx *ctx)
         if (sg.copy_stream) (void)hipStreamDestroy(sg.copy_stream);
         if (sg.own_stream && sg.stream) (void)hipStreamDestroy(sg.stream);
     }
-    for (int i = 0; i < 4; i++) if (ctx->d_io[i]) (void)ctx_free(ctx, ctx->d_io[i]);
     for (const auto &b : ctx->host_blocks) (void)hipHostFree(b.first);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
 
 // A context keeps what its last calls allocated on the device (a 12 GiB input leaves ~100-200 GiB there) so that the next call starts at
-// once; a caller who wants the memory back without giving up the context asks for it here.  Pinned staging and the small blocks stay.
+// once; a caller who wants the memory back without giving up the context asks for it here.  Pinned staging and the small blocks (the
+// small words, the segment table) stay.
 extern "C" int bwts_ctx_release_memory(bwts_ctx *ctx)
 {
     if (!ctx) return BWTS_E_ARG;
     HIPC(hipSetDevice(ctx->device));
     HIPC(hipStreamSynchronize(ctx->stream));
-    BWTS_TRY(arena_release(ctx));
-    for (int i = 0; i < BWTS_AUX_SLOTS; i++)
-        if (ctx->aux[i]) { HIPC(ctx_free(ctx, ctx->aux[i])); ctx->aux[i] = nullptr; ctx->aux_cap[i] = 0; }
-    for (char *b : ctx->tied_blk) HIPC(hipFree(b));
-    ctx->tied_blk.clear();
-    for (int i = 0; i < 4; i++)
-        if (ctx->d_io[i]) { HIPC(ctx_free(ctx, ctx->d_io[i])); ctx->d_io[i] = nullptr; ctx->d_io_cap[i] = 0; }
-    if (ctx->d_seg_scratch) { HIPC(ctx_free(ctx, ctx->d_seg_scratch)); ctx->d_seg_scratch = nullptr; ctx->d_seg_scratch_cap = 0; }
-    return BWTS_OK;
+    ctx->arena_off = 0;
+    for (int i = 0; i < KB_COUNT; i++)
+        if (i != KB_SEG_TABLE) BWTS_TRY(kept_give_up(ctx, ctx->kept[i]));
+    return tied_release(ctx);
 }
 
 // ------------------------------------------------------------------------------------
@@ -394,18 +219,30 @@ extern "C" int bwts_ctx_release_memory(bwts_ctx *ctx)
 typedef int (*device_impl_fn)(bwts_ctx *, const u8 *, u64, u8 *);
 __global__ void pcie_copy_kernel(uint4 *__restrict__ dst, const uint4 *__restrict__ src, u64 vecs, u8 *__restrict__ dst_tail, const u8 *__restrict__ src_tail, u32 tail);
 
-static bool is_mtf(device_impl_fn fn) { return fn == mtf_forward_impl || fn == mtf_inverse_impl || fn == mtf_forward_segments_impl || fn == mtf_inverse_segments_impl; }
-static bool is_forward(device_impl_fn fn) { return fn == forward_device_impl || fn == forward_segments_impl; }
-// what a call is called in the guard report and the allocation trace
-static const char *impl_name(device_impl_fn fn)
-{
-    if (is_mtf(fn)) return fn == mtf_forward_impl || fn == mtf_forward_segments_impl ? "mtf forward" : "mtf inverse";
-    return is_forward(fn) ? "forward" : "inverse";
-}
+// The eight transforms that map n bytes to n bytes.  name: what a call is called in the guard report; in_label: its input in the
+// allocation trace; arena_hint: what the host path reserves ahead of the call (0: the call's own reservation decides).  The transform
+// and its inverse allocate ahead only up to 2^32 positions; the wide forms size their arenas themselves.
+struct Transform {
+    device_impl_fn fn;
+    const char *name, *in_label;
+    size_t (*arena_hint)(const bwts_ctx *ctx, u64 n);
+};
+#define NARROW_N 0x100000000ull
+static const Transform kForward = {forward_device_impl, "forward", "forward: in", [](const bwts_ctx *, u64 n) { return n <= NARROW_N ? forward_arena_bytes(n) : 0; }};
+static const Transform kInverse = {inverse_device_impl, "inverse", "inverse: in", [](const bwts_ctx *, u64 n) { return n <= NARROW_N ? inverse_arena_bytes(n) : 0; }};
+static const Transform kForwardSegments = {forward_segments_impl, "forward", "forward: in", kForward.arena_hint};
+static const Transform kInverseSegments = {inverse_segments_impl, "inverse", "inverse: in",
+                                           [](const bwts_ctx *ctx, u64 n) { return n <= NARROW_N ? inverse_segments_arena_bytes(ctx, n) : 0; }};
+static const Transform kMtfForward = {mtf_forward_impl, "mtf forward", "mtf: in", [](const bwts_ctx *ctx, u64 n) { return mtf_arena_bytes(ctx, n, false); }};
+static const Transform kMtfInverse = {mtf_inverse_impl, "mtf inverse", "mtf: in", kMtfForward.arena_hint};
+static const Transform kMtfForwardSegments = {mtf_forward_segments_impl, "mtf forward", "mtf: in", [](const bwts_ctx *ctx, u64 n) { return mtf_arena_bytes(ctx, n, true); }};
+static const Transform kMtfInverseSegments = {mtf_inverse_segments_impl, "mtf inverse", "mtf: in", kMtfForwardSegments.arena_hint};
 
-static int run_device(bwts_ctx *ctx, device_impl_fn fn, const void *d_in, u64 n, void *d_out)
+// The bracket around every device call: code object loaded outside the timing, spans, guard check, total_ms, device_bytes.  What the
+// body needs beyond the context travels in its closure.  n: the uncoded bytes, where the caller knows them already.
+template <typename Body>
+static int run_sized(bwts_ctx *ctx, u64 n, const char *what, Body body)
 {
-    if (!ctx || !d_in || !d_out || n == 0) return BWTS_E_ARG;
     HIPC(hipSetDevice(ctx->device));
     spans_reset(ctx);
     ctx->tm.n = n;
@@ -419,10 +256,10 @@ static int run_device(bwts_ctx *ctx, device_impl_fn fn, const void *d_in, u64 n,
         ctx->launched = true;
     }
     HIPC(hipEventRecord(ctx->ev_begin, ctx->stream));
-    int rc = fn(ctx, (const u8 *)d_in, n, (u8 *)d_out);
+    int rc = body();
     if (ctx->guard) {
         (void)hipStreamSynchronize(ctx->stream);
-        const int grc = guard_check(ctx, impl_name(fn));
+        const int grc = guard_check(ctx, what);
         if (rc == BWTS_OK) rc = grc;
     }
     if (rc != BWTS_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
@@ -431,22 +268,24 @@ static int run_device(bwts_ctx *ctx, device_impl_fn fn, const void *d_in, u64 n,
     float ms = 0.f;
     HIPC(hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
     ctx->tm.total_ms = ms;
-    ctx->tm.device_bytes = ctx->arena_cap + ctx->d_io_cap[0] + ctx->d_io_cap[1] + ctx->call_block_bytes;
-    for (int i = 0; i < BWTS_AUX_SLOTS; i++) ctx->tm.device_bytes += ctx->aux_cap[i];
-    ctx->tm.device_bytes += ctx->d_io_cap[2] + ctx->d_io_cap[3];
-    ctx->tm.device_bytes += ctx->tied_blk.size() * ((size_t)16 << ctx->tied_blk_lg);
-    ctx->tm.device_bytes += ctx->d_seg_cap + ctx->d_seg_scratch_cap;
+    ctx->tm.device_bytes = ctx_device_bytes(ctx);
     return BWTS_OK;
+}
+
+static int run_device(bwts_ctx *ctx, const Transform &t, const void *d_in, u64 n, void *d_out)
+{
+    if (!ctx || !d_in || !d_out || n == 0) return BWTS_E_ARG;
+    return run_sized(ctx, n, t.name, [&] { return t.fn(ctx, (const u8 *)d_in, n, (u8 *)d_out); });
 }
 
 extern "C" int bwts_forward_device(bwts_ctx *ctx, const void *d_in, uint64_t n, void *d_out)
 {
-    return run_device(ctx, forward_device_impl, d_in, n, d_out);
+    return run_device(ctx, kForward, d_in, n, d_out);
 }
 
 extern "C" int bwts_inverse_device(bwts_ctx *ctx, const void *d_in, uint64_t n, void *d_out)
 {
-    return run_device(ctx, inverse_device_impl, d_in, n, d_out);
+    return run_device(ctx, kInverse, d_in, n, d_out);
 }
 
 // ------------------------------------------------------------------------------------
@@ -698,55 +537,38 @@ static int staged_d2h(bwts_ctx *ctx, Stager &sg, u8 *h_dst, const u8 *d_src, u64
 }
 
 
-// device-side copies of the caller's input and output stay with the context (grown, never shrunk): d_io[0], d_io[1] inputs,
-// d_io[2], d_io[3] outputs; the single calls use the first of each pair
+// device-side copies of the caller's input and output stay with the context (grown, never shrunk): d_io(ctx, 0), d_io(ctx, 1) inputs,
+// d_io(ctx, 2), d_io(ctx, 3) outputs; the single calls use the first of each pair
 static int ensure_io(bwts_ctx *ctx, u64 n, bool pairs)
 {
-    const double t0 = wall_ms();
-    for (int i = 0; i < 4; i++) {
-        if (!pairs && (i & 1)) continue;
-        if (ctx->d_io_cap[i] >= n) continue;
-        if (ctx->d_io[i]) { HIPC(hipStreamSynchronize(ctx->stream)); HIPC(ctx_free(ctx, ctx->d_io[i])); ctx->d_io[i] = nullptr; ctx->d_io_cap[i] = 0; }
-        void *p = nullptr;
-        const size_t cap = align_up((size_t)n, 1 << 20);
-        static const char *const io_names[4] = {"device input 0", "device input 1", "device output 0", "device output 1"};
-        if (ctx_malloc(ctx, &p, cap, io_names[i]) != hipSuccess) { (void)hipGetLastError(); return BWTS_E_NOMEM; }
-        ctx->d_io[i] = (u8 *)p;
-        ctx->d_io_cap[i] = cap;
-    }
-    ctx->host_ms[BWTS_H_IO_ALLOC] += wall_ms() - t0;
+    for (int i = 0; i < 4; i++)
+        if (pairs || !(i & 1)) BWTS_TRY(kept_grow(ctx, ctx->kept[KB_IO + i], (size_t)n, 1 << 20, BWTS_H_IO_ALLOC));
     return BWTS_OK;
 }
 
-static size_t arena_hint(const bwts_ctx *ctx, device_impl_fn fn, u64 n)
-{
-    if (is_mtf(fn)) return mtf_arena_bytes(ctx, n, fn == mtf_forward_segments_impl || fn == mtf_inverse_segments_impl);
-    if (fn == inverse_segments_impl) return n <= 0x100000000ull ? inverse_segments_arena_bytes(ctx, n) : 0;
-    return n <= 0x100000000ull ? (fn == forward_device_impl || fn == forward_segments_impl ? forward_arena_bytes(n) : inverse_arena_bytes(n)) : 0;
-}
-
-static int run_host(bwts_ctx *ctx, device_impl_fn fn, const uint8_t *in, uint64_t n, uint8_t *out, bwts_sink_fn sink, void *user)
+static int run_host(bwts_ctx *ctx, const Transform &t, const uint8_t *in, uint64_t n, uint8_t *out, bwts_sink_fn sink, void *user)
 {
     if (!ctx || !in || (!out && !sink) || n == 0) return BWTS_E_ARG;
     HIPC(hipSetDevice(ctx->device));
     BWTS_TRY(ensure_io(ctx, n, false));
-    trace_alloc(ctx, "call    ", is_mtf(fn) ? "mtf: in" : is_forward(fn) ? "forward: in" : "inverse: in", in, n);
+    trace_alloc(ctx, "call    ", t.in_label, in, n);
     if (out) trace_alloc(ctx, "call    ", "out", out, n);
     Stager &sg = ctx->stg[0];
     // A context's first call allocates its arena, which can cost as long as the whole input copy where the driver clears what it
     // hands out: a helper thread does the hipMalloc -- and nothing else -- while this thread stages the input.  Rules (DESIGN.md
-    // section 9: a GPU memory fault followed four arena re-reservations that an earlier form did wholly on the helper):
+    // section 10: a GPU memory fault followed four arena re-reservations that an earlier form did wholly on the helper):
     //  * only a context that holds NO arena takes the helper (the one-shot CLI it was built for); a context that has to give up a
     //    smaller arena first does everything on this thread -- arena_release() drains the stream, then frees -- before staging starts;
     //  * the helper touches no context state: it allocates into a local, this thread installs the block after join().
     // BWTS_RESERVE_HELPER=1 (a test switch) sends EVERY growth through the helper, after the release on this thread.
-    const size_t want = arena_hint(ctx, fn, n);
+    const size_t want = t.arena_hint(ctx, n);
+    const KeptBlock &arena = ctx->kept[KB_ARENA];
     std::thread reserve;
     void *fresh = nullptr;
     double reserve_ms = 0;
-    if (want > ctx->arena_cap) {
+    if (want > arena.cap) {
         const char *force = bwts_knob(ctx, "BWTS_RESERVE_HELPER");
-        const bool helper = !ctx->guard && (force ? force[0] == '1' : (ctx->arena == nullptr && want >= ((size_t)256 << 20)));
+        const bool helper = !ctx->guard && (force ? force[0] == '1' : (arena.p == nullptr && want >= ((size_t)256 << 20)));
         if (helper) {
             BWTS_TRY(arena_release(ctx));
             const size_t bytes = align_up(want, 1 << 20);
@@ -761,7 +583,7 @@ static int run_host(bwts_ctx *ctx, device_impl_fn fn, const uint8_t *in, uint64_
         }
     }
     double t0 = wall_ms();
-    const int h2d_rc = staged_h2d(ctx, sg, ctx->d_io[0], in, n);
+    const int h2d_rc = staged_h2d(ctx, sg, d_io(ctx, 0), in, n);
     if (reserve.joinable()) {
         reserve.join();
         if (fresh) arena_install(ctx, fresh, align_up(want, 1 << 20), reserve_ms);     // (no block: the transform's own reservation reports it)
@@ -773,12 +595,12 @@ static int run_host(bwts_ctx *ctx, device_impl_fn fn, const uint8_t *in, uint64_
     // untouched: a call that fails leaves the buffer as it was, like the reference, which writes only after success: mk_bwts_sa.c:52-60)
     const bool touch = !sink && !is_pinned_block(ctx, out, n) && ensure_staging(ctx, sg) == BWTS_OK;
     if (touch) sg.pool->touch_async(out, n);
-    const int rcd = run_device(ctx, fn, ctx->d_io[0], n, ctx->d_io[2]);
+    const int rcd = run_device(ctx, t, d_io(ctx, 0), n, d_io(ctx, 2));
     if (touch) sg.pool->wait();
     BWTS_TRY(rcd);
     STAGE("host path: transform done");
     t0 = wall_ms();
-    const int rc = staged_d2h(ctx, sg, out, ctx->d_io[2], n, sink, user);
+    const int rc = staged_d2h(ctx, sg, out, d_io(ctx, 2), n, sink, user);
     ctx->tm.d2h_ms = wall_ms() - t0;
     ctx->tm.h2d_ms = h2d;
     return rc;
@@ -798,7 +620,7 @@ struct BatchState {
     int error = BWTS_OK;
 };
 
-static int run_batch(bwts_ctx *ctx, device_impl_fn fn, int count, const uint8_t *const *ins, const uint64_t *ns, uint8_t *const *outs)
+static int run_batch(bwts_ctx *ctx, const Transform &t, int count, const uint8_t *const *ins, const uint64_t *ns, uint8_t *const *outs)
 {
     if (!ctx || count < 0 || (count && (!ins || !ns || !outs))) return BWTS_E_ARG;
     u64 nmax = 0;
@@ -817,7 +639,7 @@ static int run_batch(bwts_ctx *ctx, device_impl_fn fn, int count, const uint8_t 
     BWTS_TRY(ensure_io(ctx, nmax, true));
     BWTS_TRY(ensure_staging(ctx, ctx->stg[1]));
     BWTS_TRY(ensure_staging(ctx, ctx->stg[2]));
-    BWTS_TRY(arena_reserve(ctx, arena_hint(ctx, fn, nmax) > ctx->arena_cap ? arena_hint(ctx, fn, nmax) : ctx->arena_cap));
+    BWTS_TRY(arena_reserve(ctx, std::max(t.arena_hint(ctx, nmax), ctx->kept[KB_ARENA].cap)));
     BatchState st;
     double busy[3] = {0, 0, 0};          // time the three stages spent working (BWTS_BATCH_TRACE=1 prints them)
     auto fail = [&st](int rc) { std::lock_guard<std::mutex> lk(st.mu); if (st.error == BWTS_OK) st.error = rc; st.cv.notify_all(); };
@@ -831,7 +653,7 @@ static int run_batch(bwts_ctx *ctx, device_impl_fn fn, int count, const uint8_t 
                 if (st.error != BWTS_OK) return;
             }
             const double t0 = wall_ms();
-            const int rc = staged_h2d(ctx, ctx->stg[1], ctx->d_io[k & 1], ins[k], ns[k]);
+            const int rc = staged_h2d(ctx, ctx->stg[1], d_io(ctx, k & 1), ins[k], ns[k]);
             busy[0] += wall_ms() - t0;
             if (rc != BWTS_OK) { fail(rc); return; }
             { std::lock_guard<std::mutex> lk(st.mu); st.staged = k; }
@@ -852,7 +674,7 @@ static int run_batch(bwts_ctx *ctx, device_impl_fn fn, int count, const uint8_t 
                 if (st.error != BWTS_OK) return;
             }
             const double t0 = wall_ms();
-            const int rc = staged_d2h(ctx, ctx->stg[2], outs[k], ctx->d_io[2 + (k & 1)], ns[k], nullptr, nullptr);
+            const int rc = staged_d2h(ctx, ctx->stg[2], outs[k], d_io(ctx, 2 + (k & 1)), ns[k], nullptr, nullptr);
             busy[2] += wall_ms() - t0;
             if (rc != BWTS_OK) { fail(rc); return; }
             { std::lock_guard<std::mutex> lk(st.mu); st.drained = k; }
@@ -866,7 +688,7 @@ static int run_batch(bwts_ctx *ctx, device_impl_fn fn, int count, const uint8_t 
             if (st.error != BWTS_OK) break;
         }
         const double t0 = wall_ms();
-        const int rc = run_device(ctx, fn, ctx->d_io[k & 1], ns[k], ctx->d_io[2 + (k & 1)]);
+        const int rc = run_device(ctx, t, d_io(ctx, k & 1), ns[k], d_io(ctx, 2 + (k & 1)));
         busy[1] += wall_ms() - t0;
         if (rc != BWTS_OK) { fail(rc); break; }
         { std::lock_guard<std::mutex> lk(st.mu); st.transformed = k; }
@@ -883,34 +705,34 @@ static int run_batch(bwts_ctx *ctx, device_impl_fn fn, int count, const uint8_t 
 
 extern "C" int bwts_forward_batch(bwts_ctx *ctx, int count, const uint8_t *const *ins, const uint64_t *ns, uint8_t *const *outs)
 {
-    return run_batch(ctx, forward_device_impl, count, ins, ns, outs);
+    return run_batch(ctx, kForward, count, ins, ns, outs);
 }
 
 extern "C" int bwts_inverse_batch(bwts_ctx *ctx, int count, const uint8_t *const *ins, const uint64_t *ns, uint8_t *const *outs)
 {
-    return run_batch(ctx, inverse_device_impl, count, ins, ns, outs);
+    return run_batch(ctx, kInverse, count, ins, ns, outs);
 }
 
 extern "C" int bwts_forward(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out)
 {
-    return run_host(ctx, forward_device_impl, in, n, out, nullptr, nullptr);
+    return run_host(ctx, kForward, in, n, out, nullptr, nullptr);
 }
 
 extern "C" int bwts_inverse(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out)
 {
-    return run_host(ctx, inverse_device_impl, in, n, out, nullptr, nullptr);
+    return run_host(ctx, kInverse, in, n, out, nullptr, nullptr);
 }
 
 extern "C" int bwts_forward_sink(bwts_ctx *ctx, const uint8_t *in, uint64_t n, bwts_sink_fn sink, void *user)
 {
     if (!sink) return BWTS_E_ARG;
-    return run_host(ctx, forward_device_impl, in, n, nullptr, sink, user);
+    return run_host(ctx, kForward, in, n, nullptr, sink, user);
 }
 
 extern "C" int bwts_inverse_sink(bwts_ctx *ctx, const uint8_t *in, uint64_t n, bwts_sink_fn sink, void *user)
 {
     if (!sink) return BWTS_E_ARG;
-    return run_host(ctx, inverse_device_impl, in, n, nullptr, sink, user);
+    return run_host(ctx, kInverse, in, n, nullptr, sink, user);
 }
 
 // ------------------------------------------------------------------------------------
@@ -932,14 +754,7 @@ static int set_segments(bwts_ctx *ctx, const uint64_t *lengths, uint64_t count, 
     for (u64 s = 0; s < count; s++) ctx->seg_off[s + 1] = ctx->seg_off[s] + lengths[s];
     const size_t bytes = (count + 1) * sizeof(u64);
     const size_t room = 3 * bytes;       // the table, and behind it a second one of up to 2 count + 1 words (seg_upload_extra)
-    if (room > ctx->d_seg_cap) {
-        if (ctx->d_seg_off) { HIPC(hipStreamSynchronize(ctx->stream)); HIPC(ctx_free(ctx, ctx->d_seg_off)); ctx->d_seg_off = nullptr; ctx->d_seg_cap = 0; }
-        void *p = nullptr;
-        const size_t cap = align_up(room, 1 << 16);
-        if (ctx_malloc(ctx, &p, cap, "segment table") != hipSuccess) { (void)hipGetLastError(); return BWTS_E_NOMEM; }
-        ctx->d_seg_off = (u64 *)p;
-        ctx->d_seg_cap = cap;
-    }
+    BWTS_TRY(kept_grow(ctx, ctx->kept[KB_SEG_TABLE], room, 1 << 16, -1));
     // the table travels from a pinned block on the context's stream, ahead of the transform (the stream is idle between calls: the wait
     // only makes sure no earlier copy still reads the block)
     if (room > ctx->h_seg_cap) {
@@ -954,7 +769,7 @@ static int set_segments(bwts_ctx *ctx, const uint64_t *lengths, uint64_t count, 
         HIPC(hipStreamSynchronize(ctx->stream));
     }
     memcpy(ctx->h_seg_off, ctx->seg_off.data(), bytes);
-    HIPC(hipMemcpyAsync(ctx->d_seg_off, ctx->h_seg_off, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(hipMemcpyAsync(d_seg_off(ctx), ctx->h_seg_off, bytes, hipMemcpyHostToDevice, ctx->stream));
     *total = sum;
     return BWTS_OK;
 }
@@ -962,63 +777,56 @@ static int set_segments(bwts_ctx *ctx, const uint64_t *lengths, uint64_t count, 
 int seg_upload_extra(bwts_ctx *ctx, const u64 *words, u64 count, u64 **d_words)
 {
     const u64 at = (u64)ctx->seg_off.size();
-    if ((at + count) * sizeof(u64) > ctx->d_seg_cap || (at + count) * sizeof(u64) > ctx->h_seg_cap) return BWTS_E_INTERNAL;
+    if ((at + count) * sizeof(u64) > ctx->kept[KB_SEG_TABLE].cap || (at + count) * sizeof(u64) > ctx->h_seg_cap) return BWTS_E_INTERNAL;
     memcpy(ctx->h_seg_off + at, words, count * sizeof(u64));
-    HIPC(hipMemcpyAsync(ctx->d_seg_off + at, ctx->h_seg_off + at, count * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-    *d_words = ctx->d_seg_off + at;
+    HIPC(hipMemcpyAsync(d_seg_off(ctx) + at, ctx->h_seg_off + at, count * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    *d_words = d_seg_off(ctx) + at;
     return BWTS_OK;
 }
 
 int seg_scratch_reserve(bwts_ctx *ctx, size_t bytes, u8 **out)
 {
-    if (bytes > ctx->d_seg_scratch_cap) {
-        if (ctx->d_seg_scratch) { HIPC(hipStreamSynchronize(ctx->stream)); HIPC(ctx_free(ctx, ctx->d_seg_scratch)); ctx->d_seg_scratch = nullptr; ctx->d_seg_scratch_cap = 0; }
-        void *p = nullptr;
-        const size_t cap = align_up(bytes, 1 << 20);
-        if (ctx_malloc(ctx, &p, cap, "segment scratch") != hipSuccess) { (void)hipGetLastError(); return BWTS_E_NOMEM; }
-        ctx->d_seg_scratch = (u8 *)p;
-        ctx->d_seg_scratch_cap = cap;
-    }
-    *out = ctx->d_seg_scratch;
+    BWTS_TRY(kept_grow(ctx, ctx->kept[KB_SEG_SCRATCH], bytes, 1 << 20, -1));
+    *out = (u8 *)ctx->kept[KB_SEG_SCRATCH].p;
     return BWTS_OK;
 }
 
-static int run_segments_host(bwts_ctx *ctx, device_impl_fn fn, const uint8_t *in, const uint64_t *lengths, uint64_t count, uint8_t *out)
+static int run_segments_host(bwts_ctx *ctx, const Transform &t, const uint8_t *in, const uint64_t *lengths, uint64_t count, uint8_t *out)
 {
     if (!ctx || !in || !out) return BWTS_E_ARG;
     u64 n = 0;
     BWTS_TRY(set_segments(ctx, lengths, count, &n));
-    return run_host(ctx, fn, in, n, out, nullptr, nullptr);
+    return run_host(ctx, t, in, n, out, nullptr, nullptr);
 }
 
-static int run_segments_device(bwts_ctx *ctx, device_impl_fn fn, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out)
+static int run_segments_device(bwts_ctx *ctx, const Transform &t, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out)
 {
     if (!ctx || !d_in || !d_out) return BWTS_E_ARG;
     u64 n = 0;
     BWTS_TRY(set_segments(ctx, lengths, count, &n));
     const char *a = (const char *)d_in, *b = (const char *)d_out;
     if (a < b + n && b < a + n) return BWTS_E_ARG;
-    return run_device(ctx, fn, d_in, n, d_out);
+    return run_device(ctx, t, d_in, n, d_out);
 }
 
 extern "C" int bwts_forward_segments(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, uint64_t count, uint8_t *out)
 {
-    return run_segments_host(ctx, forward_segments_impl, in, lengths, count, out);
+    return run_segments_host(ctx, kForwardSegments, in, lengths, count, out);
 }
 
 extern "C" int bwts_inverse_segments(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, uint64_t count, uint8_t *out)
 {
-    return run_segments_host(ctx, inverse_segments_impl, in, lengths, count, out);
+    return run_segments_host(ctx, kInverseSegments, in, lengths, count, out);
 }
 
 extern "C" int bwts_forward_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out)
 {
-    return run_segments_device(ctx, forward_segments_impl, d_in, lengths, count, d_out);
+    return run_segments_device(ctx, kForwardSegments, d_in, lengths, count, d_out);
 }
 
 extern "C" int bwts_inverse_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out)
 {
-    return run_segments_device(ctx, inverse_segments_impl, d_in, lengths, count, d_out);
+    return run_segments_device(ctx, kInverseSegments, d_in, lengths, count, d_out);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1026,83 +834,47 @@ extern "C" int bwts_inverse_segments_device(bwts_ctx *ctx, const void *d_in, con
 // ------------------------------------------------------------------------------------
 extern "C" int bwts_mtf_forward_device(bwts_ctx *ctx, const void *d_in, uint64_t n, void *d_out)
 {
-    return run_device(ctx, mtf_forward_impl, d_in, n, d_out);
+    return run_device(ctx, kMtfForward, d_in, n, d_out);
 }
 
 extern "C" int bwts_mtf_inverse_device(bwts_ctx *ctx, const void *d_in, uint64_t n, void *d_out)
 {
-    return run_device(ctx, mtf_inverse_impl, d_in, n, d_out);
+    return run_device(ctx, kMtfInverse, d_in, n, d_out);
 }
 
 extern "C" int bwts_mtf_forward(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out)
 {
-    return run_host(ctx, mtf_forward_impl, in, n, out, nullptr, nullptr);
+    return run_host(ctx, kMtfForward, in, n, out, nullptr, nullptr);
 }
 
 extern "C" int bwts_mtf_inverse(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out)
 {
-    return run_host(ctx, mtf_inverse_impl, in, n, out, nullptr, nullptr);
+    return run_host(ctx, kMtfInverse, in, n, out, nullptr, nullptr);
 }
 
 extern "C" int bwts_mtf_forward_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out)
 {
-    return run_segments_device(ctx, mtf_forward_segments_impl, d_in, lengths, count, d_out);
+    return run_segments_device(ctx, kMtfForwardSegments, d_in, lengths, count, d_out);
 }
 
 extern "C" int bwts_mtf_inverse_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out)
 {
-    return run_segments_device(ctx, mtf_inverse_segments_impl, d_in, lengths, count, d_out);
+    return run_segments_device(ctx, kMtfInverseSegments, d_in, lengths, count, d_out);
 }
 
 extern "C" int bwts_mtf_forward_segments(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, uint64_t count, uint8_t *out)
 {
-    return run_segments_host(ctx, mtf_forward_segments_impl, in, lengths, count, out);
+    return run_segments_host(ctx, kMtfForwardSegments, in, lengths, count, out);
 }
 
 extern "C" int bwts_mtf_inverse_segments(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, uint64_t count, uint8_t *out)
 {
-    return run_segments_host(ctx, mtf_inverse_segments_impl, in, lengths, count, out);
+    return run_segments_host(ctx, kMtfInverseSegments, in, lengths, count, out);
 }
 
 // ------------------------------------------------------------------------------------
 // entropy coding behind move-to-front (include/bwts_ec.h): calls whose output is not as long as their input, the kernels in ec.hip
 // ------------------------------------------------------------------------------------
-// run_device's bracket around such a call (code object loaded outside the timing, spans, guard check, total_ms); what the body needs
-// beyond the context travels in its closure.  n: the uncoded bytes, where the caller knows them already.
-template <typename Body>
-static int run_sized(bwts_ctx *ctx, u64 n, const char *what, Body body)
-{
-    HIPC(hipSetDevice(ctx->device));
-    spans_reset(ctx);
-    ctx->tm.n = n;
-    ctx->call_block_bytes = 0;
-    if (!ctx->launched) {
-        const double t0 = wall_ms();
-        pcie_copy_kernel<<<dim3(1), dim3(256), 0, ctx->stream>>>(nullptr, nullptr, 0, nullptr, nullptr, 0);
-        HIPC(hipStreamSynchronize(ctx->stream));
-        ctx->host_ms[BWTS_H_MODULE] += wall_ms() - t0;
-        ctx->launched = true;
-    }
-    HIPC(hipEventRecord(ctx->ev_begin, ctx->stream));
-    int rc = body();
-    if (ctx->guard) {
-        (void)hipStreamSynchronize(ctx->stream);
-        const int grc = guard_check(ctx, what);
-        if (rc == BWTS_OK) rc = grc;
-    }
-    if (rc != BWTS_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    HIPC(hipEventRecord(ctx->ev_end, ctx->stream));
-    BWTS_TRY(spans_resolve(ctx));
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
-    ctx->tm.total_ms = ms;
-    ctx->tm.device_bytes = ctx->arena_cap + ctx->d_seg_cap + ctx->d_seg_scratch_cap + ctx->call_block_bytes;
-    for (int i = 0; i < 4; i++) ctx->tm.device_bytes += ctx->d_io_cap[i];
-    for (int i = 0; i < BWTS_AUX_SLOTS; i++) ctx->tm.device_bytes += ctx->aux_cap[i];
-    ctx->tm.device_bytes += ctx->tied_blk.size() * ((size_t)16 << ctx->tied_blk_lg);
-    return BWTS_OK;
-}
-
 static bool ranges_overlap(const void *a, u64 na, const void *b, u64 nb)
 {
     // by subtraction: a length as large as 2^64 - 1 must not wrap the comparison
@@ -1192,12 +964,12 @@ extern "C" int bwts_ec_encode(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint
     BWTS_TRY(ensure_io(ctx, n > cap ? n : cap, false));
     Stager &sg = ctx->stg[0];
     double t0 = wall_ms();
-    BWTS_TRY(staged_h2d(ctx, sg, ctx->d_io[0], in, n));
+    BWTS_TRY(staged_h2d(ctx, sg, d_io(ctx, 0), in, n));
     const double h2d = wall_ms() - t0;
     u64 bytes = 0;
-    BWTS_TRY(bwts_ec_encode_device(ctx, ctx->d_io[0], n, ctx->d_io[2], cap, &bytes));
+    BWTS_TRY(bwts_ec_encode_device(ctx, d_io(ctx, 0), n, d_io(ctx, 2), cap, &bytes));
     t0 = wall_ms();
-    BWTS_TRY(staged_d2h(ctx, sg, out, ctx->d_io[2], bytes, nullptr, nullptr));
+    BWTS_TRY(staged_d2h(ctx, sg, out, d_io(ctx, 2), bytes, nullptr, nullptr));
     ctx->tm.d2h_ms = wall_ms() - t0;
     ctx->tm.h2d_ms = h2d;
     *out_bytes = bytes;
@@ -1215,12 +987,12 @@ extern "C" int bwts_ec_decode(bwts_ctx *ctx, const uint8_t *in, uint64_t in_byte
     BWTS_TRY(ensure_io(ctx, in_bytes > v ? in_bytes : v, false));
     Stager &sg = ctx->stg[0];
     double t0 = wall_ms();
-    BWTS_TRY(staged_h2d(ctx, sg, ctx->d_io[0], in, in_bytes));
+    BWTS_TRY(staged_h2d(ctx, sg, d_io(ctx, 0), in, in_bytes));
     const double h2d = wall_ms() - t0;
     u64 got = 0;
-    BWTS_TRY(bwts_ec_decode_device(ctx, ctx->d_io[0], in_bytes, ctx->d_io[2], v, &got));
+    BWTS_TRY(bwts_ec_decode_device(ctx, d_io(ctx, 0), in_bytes, d_io(ctx, 2), v, &got));
     t0 = wall_ms();
-    BWTS_TRY(staged_d2h(ctx, sg, out, ctx->d_io[2], got, nullptr, nullptr));
+    BWTS_TRY(staged_d2h(ctx, sg, out, d_io(ctx, 2), got, nullptr, nullptr));
     ctx->tm.d2h_ms = wall_ms() - t0;
     ctx->tm.h2d_ms = h2d;
     *n = got;

@@ -471,10 +471,10 @@ static int ec_prepare(bwts_ctx *ctx, const EcPlan &p, bool encode, bool segments
     if (segments) {
         u64 *d_words = nullptr;
         BWTS_TRY(seg_upload_extra(ctx, p.words.data(), 2 * p.count + 1, &d_words));
-        S.seg_off = ctx->d_seg_off; S.first = d_words; S.base = d_words + p.count; S.bseg = b.bseg;
+        S.seg_off = d_seg_off(ctx); S.first = d_words; S.base = d_words + p.count; S.bseg = b.bseg;
         SpanGuard sp(ctx, BWTS_K_OTHER, p.blocks, 4 * p.blocks);
         const u64 wgs = (p.count + 3) / 4;
-        ec_block_table_kernel<<<dim3((unsigned)(wgs < (1u << 20) ? wgs : (1u << 20))), dim3(256), 0, ctx->stream>>>(ctx->d_seg_off, S.first, p.count, b.bseg);
+        ec_block_table_kernel<<<dim3((unsigned)(wgs < (1u << 20) ? wgs : (1u << 20))), dim3(256), 0, ctx->stream>>>(d_seg_off(ctx), S.first, p.count, b.bseg);
     }
     return BWTS_OK;
 }
@@ -519,7 +519,7 @@ int ec_encode_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, u64 out_cap,
     if (segments) {
         {
             SpanGuard sp(ctx, BWTS_K_OTHER, p.count, 24 * p.count);
-            ec_stream_sizes_kernel<<<dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, ctx->stream>>>(ctx->d_seg_off, S.first, p.count, b.offs, b.ssize);
+            ec_stream_sizes_kernel<<<dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, ctx->stream>>>(d_seg_off(ctx), S.first, p.count, b.offs, b.ssize);
         }
         HIPC(hipMemcpyAsync(stream_bytes, b.ssize, p.count * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
         HIPC(hipStreamSynchronize(ctx->stream));

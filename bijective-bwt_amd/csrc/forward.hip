@@ -2575,7 +2575,7 @@ int forward_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out)
         if (len < big) { nshort++; m += len; }
     }
     if (nshort == count) {
-        SegTable seg{ctx->d_seg_off, count, nullptr};
+        SegTable seg{d_seg_off(ctx), count, nullptr};
         BWTS_TRY(seg_scratch_reserve(ctx, n, &seg.flag));
         return forward_run(ctx, d_in, n, d_out, &seg);
     }

@@ -63,6 +63,12 @@ enum SegReportWord { SR_PLAN, SR_BIG, SR_RUNS, SR_OWN_SEGS, SR_OWN_BYTES, SR_SIN
 #define STAGE_SLOTS 4
 #define BWTS_AUX_SLOTS 5
 
+// A device block that stays with the context: grown when a call needs more, never shrunk, given up by bwts_ctx_release_memory and
+// bwts_ctx_destroy (ctx_memory.hip).  name: what the allocation trace and the guard report call it.
+struct KeptBlock { char *p; size_t cap; const char *name; };
+// every kept block of a context, in bwts_ctx::kept
+enum { KB_ARENA, KB_AUX, KB_IO = KB_AUX + BWTS_AUX_SLOTS, KB_SEG_TABLE = KB_IO + 4, KB_SEG_SCRATCH, KB_COUNT };
+
 #define SM_RX_SYNC 4090          // d_small word holding the two 32-bit counters of radix_column_scan_fused_kernel (zero between launches)
 #define SM_EC_TOTAL 4020         // entropy coder (ec.hip): d_small word for the bytes of all payloads of an encode
 #define SM_EC_FLAG  4021         // ... d_small word for what a decode found wrong (0: nothing)
@@ -83,14 +89,19 @@ struct bwts_ctx {
     size_t call_block_bytes = 0;        // device memory taken for one call only (rare paths), largest of the last call
     int last_hip;
 
-    // device arena: one allocation, bump-allocated per call, grown between calls
-    char  *arena;
-    size_t arena_cap, arena_off;
-    // side arenas sized on demand.  0, 1: forward: tied-set buffers; inverse: unreached-element lists, cycle sort.  2: factor list of
-    // the general Lyndon path.  3: previous-symbol array + carried-byte buffers (rounds-0 sorts on wide keys).  4: dense rank array.
+    // KB_ARENA: the device arena: one allocation, bump-allocated per call (arena_off), grown between calls.
+    // KB_AUX + i: side arenas sized on demand.  0, 1: forward: tied-set buffers; inverse: unreached-element lists, cycle sort.  2: factor
+    // list of the general Lyndon path.  3: previous-symbol array + carried-byte buffers (rounds-0 sorts on wide keys).  4: dense rank array.
     // (What the headline path does not touch is not allocated: the driver clears device memory it hands out, ~27 ms per GiB.)
-    char  *aux[BWTS_AUX_SLOTS];
-    size_t aux_cap[BWTS_AUX_SLOTS];
+    // KB_IO + i: the host-buffer entry points' device-side in/out buffers (below).  KB_SEG_TABLE: the device copy of the segment table.
+    // KB_SEG_SCRATCH: segmented forward: factor-start flags.
+    KeptBlock kept[KB_COUNT] = {{nullptr, 0, "arena"},
+                                {nullptr, 0, "side block 0"}, {nullptr, 0, "side block 1"}, {nullptr, 0, "side block 2"},
+                                {nullptr, 0, "side block 3"}, {nullptr, 0, "side block 4"},
+                                {nullptr, 0, "device input 0"}, {nullptr, 0, "device input 1"},
+                                {nullptr, 0, "device output 0"}, {nullptr, 0, "device output 1"},
+                                {nullptr, 0, "segment table"}, {nullptr, 0, "segment scratch"}};
+    size_t arena_off;
     size_t unv_hint;       // inverse: unreached elements seen by the previous call (sizes the first collection pass)
     // inverse: one record per attempt of the most recent call, from values its stages hold on the host anyway (a few stores per
     // attempt); bwts_debug_inverse_report is the only reader and include/bwts_test.h names the words
@@ -118,10 +129,8 @@ struct bwts_ctx {
     // host-buffer entry points: staging (a ring of pinned slots with one event each, copy workers, a queue of its own), device-side
     // in/out buffers that stay with the context, and the pinned blocks handed out by bwts_host_alloc.  stg[0] serves the single
     // calls on the context's own stream; the batch entry points move the neighbouring items' data on stg[1] (in) and stg[2] (out)
-    // while the current item is transformed, between two pairs of device buffers (d_io[0..1] in, d_io[2..3] out).
+    // while the current item is transformed, between two pairs of device buffers (d_io(ctx, 0..1) in, d_io(ctx, 2..3) out).
     Stager stg[3];
-    u8    *d_io[4];
-    size_t d_io_cap[4];
     std::vector<std::pair<char *, size_t>> host_blocks;
 
     // event pool + spans of the current call
@@ -139,16 +148,12 @@ struct bwts_ctx {
     std::vector<std::pair<std::string, std::string>> knobs;
     int fused_scan_cap;    // workgroups of radix_column_scan_fused_kernel that are certain to be resident together (0 = not yet asked)
 
-    // segment table of the current segmented call: offsets on the host (count + 1) and their device copy
+    // segment table of the current segmented call: offsets on the host (count + 1); their device copy is d_seg_off(ctx)
     std::vector<u64> seg_off;
-    u64 *d_seg_off = nullptr;
-    size_t d_seg_cap = 0;
     u64 *h_seg_off = nullptr;           // pinned staging of the table
     size_t h_seg_cap = 0;
-    u8 *d_seg_scratch = nullptr;        // forward: factor-start flags
     // inverse: what the most recent segmented inverse did (bwts_debug_segments_report; include/bwts_test.h names the words)
     u64 seg_report[SEG_REPORT_WORDS] = {0};
-    size_t d_seg_scratch_cap = 0;
 
     bwts_timings tm;
     double host_ms[BWTS_H_COUNT];   // cumulative host-side costs (BWTS_H_*)
@@ -179,9 +184,24 @@ const char *bwts_knob(const bwts_ctx *ctx, const char *name);    // value of an 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 double wall_ms(void);
 
+// ---- the context's device memory (ctx_memory.hip) -------------------------------
+hipError_t ctx_malloc(bwts_ctx *ctx, void **out, size_t bytes, const char *name);   // with guard bands under BWTS_GUARD
+hipError_t ctx_free(bwts_ctx *ctx, void *user);
+int  guard_check(bwts_ctx *ctx, const char *what);      // after a transform: are all guard bands intact?
+void trace_alloc(const bwts_ctx *ctx, const char *what, const char *name, const void *p, size_t bytes);   // BWTS_TRACE_ALLOC=1
+bool poison_on(const bwts_ctx *ctx);
+// room for `bytes`, rounded up to a multiple of `round`, in a kept block; host_cost: the BWTS_H_* the wall time of a growth is
+// booked to, or -1.  A block that is large enough is left alone; one that is refused is left empty (BWTS_E_NOMEM).
+int  kept_grow(bwts_ctx *ctx, KeptBlock &b, size_t bytes, size_t round, int host_cost);
+int  kept_give_up(bwts_ctx *ctx, KeptBlock &b);         // drains the context's stream, then frees (calling thread only)
+size_t ctx_device_bytes(const bwts_ctx *ctx);           // what the context holds on the device: bwts_timings::device_bytes
+int  tied_release(bwts_ctx *ctx);                       // the wide forward's tied-list blocks (wide_path.h): drains, then frees
+static inline u8 *d_io(const bwts_ctx *ctx, int i) { return (u8 *)ctx->kept[KB_IO + i].p; }
+static inline u64 *d_seg_off(const bwts_ctx *ctx) { return (u64 *)ctx->kept[KB_SEG_TABLE].p; }
+
 // ---- arena -------------------------------------------------------------------
 int  arena_reserve(bwts_ctx *ctx, size_t bytes);        // (re)allocates when too small; resets
-int  arena_release(bwts_ctx *ctx);                      // drains the context's stream, then gives the arena up (calling thread only)
+int  arena_release(bwts_ctx *ctx);                      // gives the arena up (calling thread only)
 void arena_install(bwts_ctx *ctx, void *block, size_t bytes, double alloc_ms);
 void arena_reset(bwts_ctx *ctx);
 void *arena_alloc(bwts_ctx *ctx, size_t bytes);         // NULL when exhausted

@@ -1740,12 +1740,12 @@ static int inverse_segments_lane(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out
         HIPC(hipMemsetAsync(d_cyc, 0, sizeof(u64), ctx->stream));
         {
             SpanGuard sg(ctx, BWTS_K_LF_BUILD, small, 5 * small);
-            seg_lf_kernel<<<dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx->stream>>>(d_in, ctx->d_seg_off, count, big, LF);
+            seg_lf_kernel<<<dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx->stream>>>(d_in, d_seg_off(ctx), count, big, LF);
             HIPC(hipGetLastError());
         }
         {
             SpanGuard sg(ctx, BWTS_K_WALK, small, 10 * small);
-            seg_walk_kernel<<<dim3((unsigned)((count + 63) / 64)), dim3(64), 0, ctx->stream>>>(d_in, LF, ctx->d_seg_off, count, big, d_out, d_cyc);
+            seg_walk_kernel<<<dim3((unsigned)((count + 63) / 64)), dim3(64), 0, ctx->stream>>>(d_in, LF, d_seg_off(ctx), count, big, d_out, d_cyc);
             HIPC(hipGetLastError());
         }
         BWTS_TRY(read_small(ctx, SMI_COUNTERS, 1));
@@ -1765,7 +1765,7 @@ static int inverse_segments_shared(bwts_ctx *ctx, const u8 *d_in, u8 *d_out, con
         if (off[a + 1] - off[a] >= big) { a++; continue; }
         u64 b = a + 1;
         while (b < count && off[b + 1] - off[b] < big) b++;
-        const InvSegs run = {ctx->d_seg_off + a, b - a, off[a]};
+        const InvSegs run = {d_seg_off(ctx) + a, b - a, off[a]};
         ctx->tm.attempts = 1;
         ctx->inv_attempts_made = 0;
         BWTS_TRY(inverse_narrow_chain(ctx, d_in + off[a], off[b] - off[a], d_out + off[a], &run));

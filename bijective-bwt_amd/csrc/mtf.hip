@@ -472,7 +472,7 @@ static int mtf_run(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool inverse
         u64 *d_first = nullptr;
         BWTS_TRY(seg_upload_extra(ctx, first.data(), count, &d_first));
         SpanGuard sp(ctx, BWTS_K_OTHER, p.tiles, 8 * p.tiles);
-        mtf_tile_table_kernel<<<dim3(mtf_grid((count + 3) / 4)), dim3(256), 0, ctx->stream>>>(ctx->d_seg_off, d_first, count, n, b.tile_off);
+        mtf_tile_table_kernel<<<dim3(mtf_grid((count + 3) / 4)), dim3(256), 0, ctx->stream>>>(d_seg_off(ctx), d_first, count, n, b.tile_off);
     }
     const unsigned tile_blocks = mtf_grid(p.tiles);
     if (!inverse) {

@@ -374,12 +374,7 @@ __global__ __launch_bounds__(64) void wide_direct_groups_kernel(TiedList tl, con
 // room for `elements` list entries; the block table goes to the device whenever it has changed (or `push` asks)
 static int wide_tied_ensure(bwts_ctx *ctx, u64 elements, int lg, u64 **d_tab, bool push)
 {
-    if (!ctx->tied_blk.empty() && lg > ctx->tied_blk_lg) {
-        // (blocks of an earlier, smaller call: nothing in them is live)
-        HIPC(hipStreamSynchronize(ctx->stream));
-        for (char *b : ctx->tied_blk) HIPC(hipFree(b));
-        ctx->tied_blk.clear();
-    }
+    if (lg > ctx->tied_blk_lg) BWTS_TRY(tied_release(ctx));     // (blocks of an earlier, smaller call: nothing in them is live)
     if (ctx->tied_blk.empty()) { ctx->tied_blk.reserve(WIDE_TB_MAX); if (lg > ctx->tied_blk_lg) ctx->tied_blk_lg = lg; }
     const int L = ctx->tied_blk_lg;
     const u64 want = (elements + (1ull << L) - 1ull) >> L;

@@ -33,7 +33,7 @@ def test_header_symbols_exported(built, pkg):
 def test_strerror_and_names(pkg):
     L = pkg.lib()
     assert L.bwts_strerror(0) == b"ok"
-    for code in range(-7, 0):
+    for code in range(-9, 0):
         assert L.bwts_strerror(code) and L.bwts_strerror(code) != b"unknown error"
     assert [L.bwts_kernel_class_name(i).decode() for i in range(pkg.K_COUNT)] == pkg.K_NAMES
 

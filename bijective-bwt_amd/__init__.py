@@ -54,7 +54,7 @@ E_FORMAT, E_SPACE = -8, -9
 TEST_EXPORTS = [
     "bwts_generate_device", "bwts_device_alloc", "bwts_device_free", "bwts_copy_to_device", "bwts_copy_to_host",
     "bwts_device_equal", "bwts_debug_sort_pairs", "bwts_debug_suffix_array", "bwts_debug_lyndon",
-    "bwts_debug_chunk_plan", "bwts_debug_inverse_arena", "bwts_debug_forward_arena", "bwts_debug_inverse_report",
+    "bwts_debug_chunk_plan", "bwts_debug_inverse_arena", "bwts_debug_forward_arena", "bwts_debug_wide_forward_arena", "bwts_debug_inverse_report",
     "bwts_debug_forward_report", "bwts_debug_segments_plan", "bwts_debug_segments_report",
     "bwts_debug_mtf_plan", "bwts_debug_last_spans", "bwts_debug_ec_plan",
 ]
@@ -185,6 +185,7 @@ def lib():
         L.bwts_debug_chunk_plan.argtypes = [u64, u64, ctypes.POINTER(u64)]
         L.bwts_debug_inverse_arena.argtypes = [u64, i32, i32, ctypes.POINTER(u64)]
         L.bwts_debug_forward_arena.argtypes = [u64, ctypes.POINTER(u64)]
+        L.bwts_debug_wide_forward_arena.argtypes = [u64, i32, i32, u64, ctypes.POINTER(u64)]
         L.bwts_debug_inverse_report.argtypes = [vp, ctypes.POINTER(u64), u64, ctypes.POINTER(u64)]
         L.bwts_debug_forward_report.argtypes = [vp, ctypes.POINTER(u64), u64, ctypes.POINTER(u64)]
         L.bwts_debug_segments_plan.argtypes = [vp, u64, ctypes.POINTER(u64)]

@@ -1233,6 +1233,12 @@ extern "C" int bwts_debug_forward_arena(uint64_t n, uint64_t out[1])
     return 0;
 }
 
+// the wide forward's arena (wide_path.h), likewise
+extern "C" int bwts_debug_wide_forward_arena(uint64_t n, int mode, int seg_log2, uint64_t bucket_cap, uint64_t out[1])
+{
+    return forward_wide_arena_probe(n, mode, seg_log2, bucket_cap, out);
+}
+
 // what the attempts of the most recent inverse call on this context did: no device, the records are host memory
 extern "C" int bwts_debug_inverse_report(bwts_ctx *ctx, uint64_t *out, uint64_t cap_words, uint64_t *attempts)
 {

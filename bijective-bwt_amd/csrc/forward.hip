@@ -2053,32 +2053,15 @@ __global__ __launch_bounds__(256) void suffix_mismatch_grid_kernel(const u8 *__r
     }
 }
 
-// returns BWTS_OK with *done = false when the input needs the general path
-static int lyndon_fast(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, SortSpace &sp, const u64 *tile_min, u64 *cand[2],
-                       u32 *cvals[2], u32 *fstart, u64 *k_out, bool *done)
+// The cnt_c candidates in cand[0] become the factor starts fstart[0 .. *k): sorted by position, then walked by the resolver.
+// BWTS_OK with *settled = false: too much sequential work, and the caller takes its other route to the factors.
+template <typename IDX>
+static int lyndon_resolve_candidates(bwts_ctx *ctx, const u8 *d_T, u64 n, u64 *const cand[2], u32 *const cvals[2], u32 *tile_hist, void *scan_temp, u64 cnt_c,
+                                     IDX *fstart, u64 *k, bool *settled)
 {
-    *done = false;
-    u64 *cnt = ctx->d_small + SM_COUNTERS;
-    HIPC(hipMemsetAsync(cnt + 4, 0, 4 * sizeof(u64), ctx->stream));
-    {
-        // keybuild0 left every tile's smallest key in tile_min; after the exclusive min-scan of those, a tile can
-        // hold a candidate only if its own minimum does not exceed the minimum of everything before it
-        SpanGuard g(ctx, BWTS_K_LYNDON, n, 0);
-        const u64 tiles = scan_tiles(n);
-        HIPC(hipMemcpyAsync(sp.scan_temp, tile_min, tiles * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
-        BWTS_TRY((device_scan_partials<u64, OpMin>(ctx, tiles, OpMin(), ~0ull, sp.scan_temp)));
-        const KeyStore ks = key_store_of(sp.keys[0], n, sp.split_keys, al.key_bits);
-        KeyIn in{ks};
-        CandOut out{ks, n, al.varlen ? 64 : al.msym, cand[0], LYN_CAND_CAP, ctx->d_small + CNT_CAND};
-        TileMayHoldCandidate filter{tile_min};
-        BWTS_TRY((device_scan_final<false, u64>(ctx, n, in, out, OpMin(), ~0ull, sp.scan_temp, filter)));
-    }
-    BWTS_TRY(read_small(ctx, CNT_CAND, 1));
-    const u64 cnt_c = ctx->h_small[CNT_CAND];
-    if (cnt_c == 0) return BWTS_E_INTERNAL;
-    if (cnt_c > LYN_CAND_CAP) return BWTS_OK;
+    *settled = false;
     // candidates arrive in arbitrary order: sort by position
-    SortPlan cp = sort_plan(cand[0], cand[1], cvals[0], cvals[1], sp.tile_hist, sp.scan_temp);
+    SortPlan cp = sort_plan(cand[0], cand[1], cvals[0], cvals[1], tile_hist, scan_temp);
     int res = 0;
     BWTS_TRY(radix_sort_pairs(ctx, cp, cnt_c, bitlen_u64(n) + 1, &res));
     // resumable resolver: long comparisons are decided by a grid-wide kernel between two of its launches
@@ -2089,12 +2072,12 @@ static int lyndon_fast(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, 
     for (int iter = 0;; iter++) {
         {
             SpanGuard g(ctx, BWTS_K_LYNDON, cnt_c, 0);
-            lyndon_resolve_kernel<u32><<<dim3(1), dim3(256), 0, ctx->stream>>>(d_T, n, cand[res], cnt_c, fstart, d_st, LYN_WORK_CAP);
+            lyndon_resolve_kernel<IDX><<<dim3(1), dim3(256), 0, ctx->stream>>>(d_T, n, cand[res], cnt_c, fstart, d_st, LYN_WORK_CAP);
             HIPC(hipGetLastError());
         }
         BWTS_TRY(read_small(ctx, CNT_LYN_K, 8));
         if (h_st->status == 0) break;
-        if (h_st->status == 2 || iter > 4096) return BWTS_OK;       // too much sequential work: general path
+        if (h_st->status == 2 || iter > 4096) return BWTS_OK;       // too much sequential work
         // status 1: compare suffix(p) with suffix(cur) on the whole chip
         u64 e = 0;
         HIPC(hipMemcpyAsync(&e, cand[res] + h_st->next, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
@@ -2123,10 +2106,37 @@ static int lyndon_fast(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, 
         HIPC(hipMemcpyAsync(d_st, h_st, sizeof(LynState), hipMemcpyHostToDevice, ctx->stream));
         HIPC(hipStreamSynchronize(ctx->stream));
     }
-    *k_out = h_st->k;
-    if (*k_out == 0) return BWTS_E_INTERNAL;
-    *done = true;
+    *k = h_st->k;
+    if (*k == 0) return BWTS_E_INTERNAL;
+    *settled = true;
     return BWTS_OK;
+}
+
+// returns BWTS_OK with *done = false when the input needs the general path
+static int lyndon_fast(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, SortSpace &sp, const u64 *tile_min, u64 *cand[2],
+                       u32 *cvals[2], u32 *fstart, u64 *k_out, bool *done)
+{
+    *done = false;
+    u64 *cnt = ctx->d_small + SM_COUNTERS;
+    HIPC(hipMemsetAsync(cnt + 4, 0, 4 * sizeof(u64), ctx->stream));
+    {
+        // keybuild0 left every tile's smallest key in tile_min; after the exclusive min-scan of those, a tile can
+        // hold a candidate only if its own minimum does not exceed the minimum of everything before it
+        SpanGuard g(ctx, BWTS_K_LYNDON, n, 0);
+        const u64 tiles = scan_tiles(n);
+        HIPC(hipMemcpyAsync(sp.scan_temp, tile_min, tiles * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
+        BWTS_TRY((device_scan_partials<u64, OpMin>(ctx, tiles, OpMin(), ~0ull, sp.scan_temp)));
+        const KeyStore ks = key_store_of(sp.keys[0], n, sp.split_keys, al.key_bits);
+        KeyIn in{ks};
+        CandOut out{ks, n, al.varlen ? 64 : al.msym, cand[0], LYN_CAND_CAP, ctx->d_small + CNT_CAND};
+        TileMayHoldCandidate filter{tile_min};
+        BWTS_TRY((device_scan_final<false, u64>(ctx, n, in, out, OpMin(), ~0ull, sp.scan_temp, filter)));
+    }
+    BWTS_TRY(read_small(ctx, CNT_CAND, 1));
+    const u64 cnt_c = ctx->h_small[CNT_CAND];
+    if (cnt_c == 0) return BWTS_E_INTERNAL;
+    if (cnt_c > LYN_CAND_CAP) return BWTS_OK;
+    return lyndon_resolve_candidates<u32>(ctx, d_T, n, cand, cvals, sp.tile_hist, sp.scan_temp, cnt_c, fstart, k_out, done);
 }
 
 // ------------------------------------------------------------------------------------

@@ -281,6 +281,7 @@ size_t inverse_segments_arena_bytes(const bwts_ctx *ctx, u64 n);   // for the co
 int inverse_segments_plan_words(const u64 *lengths, u64 count, u64 out[8]);   // bwts_debug_segments_plan: no context, no device
 int inverse_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
 size_t forward_arena_bytes(u64 n);
+int forward_wide_arena_probe(u64 n, int mode, int seg_log2, u64 bucket_cap, u64 *bytes);   // wide_path.h, for bwts_debug_wide_forward_arena
 // the inverse's arena as plain arithmetic (the bwts_debug_inverse_arena test hook asks them too): the splitter spacing the narrow
 // form picks, what one attempt reserves (mark: 0 index log, 1 sentinel, 2 byte map, 3 moments), what the host path allocates ahead
 int    inverse_splitter_log2(u64 n);

@@ -392,10 +392,10 @@ static int wide_tied_ensure(bwts_ctx *ctx, u64 elements, int lg, u64 **d_tab, bo
     return BWTS_OK;
 }
 
-struct WideKnobs { int seg_log2; u64 bucket_cap; u64 part; int tblock_log2; int direct; };
+struct WideKnobs { int seg_log2; u64 bucket_cap; u64 part; int tblock_log2; int direct; bool bucket_given /* BWTS_WIDE_BUCKET is set */; };
 static WideKnobs wide_knobs(const bwts_ctx *ctx)
 {
-    WideKnobs kn{30, 1ull << 30, 0, 0, -1};
+    WideKnobs kn{30, 1ull << 30, 0, 0, -1, bwts_knob(ctx, "BWTS_WIDE_BUCKET") != nullptr};
     if (const char *e = bwts_knob(ctx, "BWTS_WIDE_DIRECT")) kn.direct = atoi(e) ? 1 : 0;     // 1: ties by direct comparison only, 0: rank array at once
     if (const char *e = bwts_knob(ctx, "BWTS_WIDE_PART")) { const long long v = atoll(e); if (v >= 64) kn.part = (u64)v; }             // elements per part of a round
     if (const char *e = bwts_knob(ctx, "BWTS_WIDE_TBLOCK_LOG2")) { const int v = atoi(e); if (v >= 6 && v <= 30) kn.tblock_log2 = v; } // tied-list block size
@@ -445,429 +445,465 @@ static int wide_suffix_heads(bwts_ctx *ctx, u64 n, u64 *rank64, void *temp, u32 
     return BWTS_OK;
 }
 
-static int forward_wide_run(bwts_ctx *ctx, const u8 *d_T, u64 n, u8 *d_out, WideMode mode, WideFactors *fac, int *redo)
+// The words of the counter block d_small[SM_COUNTERS ..] that the wide forward uses, cleared where they are used.  forward.hip owns words
+// 2 (CNT_TOTAL), 4-8 (CNT_CAND, and from CNT_LYN_K the resolver's state, which runs on to word 13), 16-20 (CNT_SAMPLE) and 28 (CNT_DIRECT).
+enum WideCounter {
+    WC_KEPT = 0, WC_SPLIT = 1, WC_GROUPS = 3,     // a part of a round: elements it keeps; some group split; its groups (also: the direct form's)
+    WC_UNRESOLVED = WC_SPLIT, WC_ROUND_WORDS = 4, // direct form: a group too large, or rotations equal too far; (no word: 0..3 are cleared and read together)
+    WC_TIED = 24, WC_OVERFLOW = 25,               // tied elements of the buckets so far; the finish kernel's error (1 list full, 2 bad position)
+    WC_WRITE = 26, WC_SAMPLE_TIES = 27            // where a round's next part writes its survivors; equal neighbours in the key sample
+};
+static inline u64 *wide_counter(bwts_ctx *ctx, int c) { return ctx->d_small + SM_COUNTERS + c; }
+static inline u64 wide_count(const bwts_ctx *ctx, int c) { return ctx->h_small[SM_COUNTERS + c]; }
+// Sizes of one run: pure host arithmetic over n, the mode and the knobs
+struct WideShape {
+    u64 n; WideMode mode; WideKnobs kn;
+    u64 seg, nseg, tiles, M /* elements a bucket may hold */, Mb, mwords, sort_max;
+    u64 seg_count(u64 s) const { const u64 p0 = s * seg; return n - p0 < seg ? n - p0 : seg; }
+};
+static WideShape wide_shape(WideKnobs kn, u64 n, WideMode mode)
 {
-    *redo = WIDE_DONE;
-    if (n > (1ull << 36)) return BWTS_E_RANGE;
-    const bool direct = mode == WIDE_DIRECT, suffix = mode == WIDE_SUFFIX;
-    const bool search = !suffix && !fac->fstart;                   // candidate search for the factors
-    WideKnobs kn = wide_knobs(ctx);
     // larger buckets (fewer collection passes over the text) while rank array + bucket buffers + in/out leave room: 12 GiB of DNA
     // take 2.03 s with buckets of 2^30 elements (before the carried byte), 1.86 s with 2^31, 1.62 s with 3 * 2^30 (203 GiB on the device)
-    if (!bwts_knob(ctx, "BWTS_WIDE_BUCKET")) {
+    if (!kn.bucket_given) {
         // (without the rank array there is room for the largest bucket the 32-bit sort indices allow: 4 instead of 5 passes over the
         // text at 12 GiB, 7 instead of 9 at 24 GiB)
-        if (direct && n <= (48ull << 30)) kn.bucket_cap = 0xff000000ull;
+        if (mode == WIDE_DIRECT && n <= (48ull << 30)) kn.bucket_cap = 0xff000000ull;
         else if (n <= (13ull << 30)) kn.bucket_cap = 3ull << 30;
-        else if (n <= (14ull << 30) || direct) kn.bucket_cap = 1ull << 31;
+        else if (n <= (14ull << 30) || mode == WIDE_DIRECT) kn.bucket_cap = 1ull << 31;
     }
-    const u64 seg = 1ull << kn.seg_log2;
-    const u64 nseg = (n + seg - 1) / seg;
-    const u64 tiles = scan_tiles(n);
-    const u64 M = kn.bucket_cap;                                   // elements a bucket may hold
+    WideShape sh{n, mode, kn};
+    sh.seg = 1ull << kn.seg_log2; sh.nseg = (n + sh.seg - 1) / sh.seg;
+    sh.tiles = scan_tiles(n); sh.M = kn.bucket_cap;
     // the buckets' sort buffers also serve the rounds over the tied list, which take it in parts of half a buffer (the other half
     // holds the part's regrouped elements): short inputs (the forced runs of the tests) keep room for the whole list in one part
     const u64 whole = 2 * n < (1ull << 29) ? 2 * n : (1ull << 29);
-    const u64 Mb = M > whole ? M : whole;
-    const u64 mwords = (Mb + 63) / 64 + 1;
-    u64 sort_max = Mb > seg ? Mb : seg;                            // largest sort or scan through tile_hist / scan_temp:
-    if (sort_max < LYN_CAND_CAP) sort_max = LYN_CAND_CAP;          // a bucket, a segment, or the factor candidates
-    // ---- arena layout -------------------------------------------------------------------------------------------------
-    const size_t need = (direct ? 0 : align_up(n * 8, 256)) + align_up(seg * 8, 256) + align_up(seg, 256) + align_up((tiles + 1) * 8, 256) + scan_temp_bytes(n) +
-                        2 * align_up(Mb * 8, 256) + 2 * align_up(Mb * 4, 256) + 4 * align_up(Mb, 256) + radix_tile_hist_bytes(sort_max) +
-                        scan_temp_bytes(sort_max) + 3 * align_up(mwords * 8, 256) + 8 * align_up(LYN_CAND_CAP * 8, 256) +
-                        align_up(nseg * WIDE_PREFIXES * 4, 256) + align_up((WIDE_MAX_PARTS + 2) * 8, 256) + (1 << 16);
-    BWTS_TRY(arena_reserve(ctx, need));
-    u64 *rank64 = direct ? nullptr : arena_array<u64>(ctx, n);
-    u64 *segkeys = arena_array<u64>(ctx, seg);
-    u8 *segprev = arena_array<u8>(ctx, seg);
-    u64 *tile_min = arena_array<u64>(ctx, tiles + 1);
-    void *pre_temp = arena_alloc(ctx, scan_temp_bytes(n));
-    u64 *bk[2] = {arena_array<u64>(ctx, Mb), arena_array<u64>(ctx, Mb)};
-    u32 *bv[2] = {arena_array<u32>(ctx, Mb), arena_array<u32>(ctx, Mb)};
-    u8 *bs_src = arena_array<u8>(ctx, Mb), *bs_buf[2] = {arena_array<u8>(ctx, Mb), arena_array<u8>(ctx, Mb)}, *bs_fin = arena_array<u8>(ctx, Mb);
-    u32 *tile_hist = (u32 *)arena_alloc(ctx, radix_tile_hist_bytes(sort_max));
-    void *scan_temp = arena_alloc(ctx, scan_temp_bytes(sort_max));
-    u64 *headw = arena_array<u64>(ctx, mwords), *keepw = arena_array<u64>(ctx, mwords), *prew = arena_array<u64>(ctx, mwords);
-    u64 *cand[2] = {arena_array<u64>(ctx, LYN_CAND_CAP), arena_array<u64>(ctx, LYN_CAND_CAP)};
-    u32 *cvals[2] = {arena_array<u32>(ctx, LYN_CAND_CAP), arena_array<u32>(ctx, LYN_CAND_CAP)};
-    u64 *fstart = arena_array<u64>(ctx, LYN_CAND_CAP);
-    u32 *d_hist = arena_array<u32>(ctx, nseg * WIDE_PREFIXES);
-    u64 *d_cuts = arena_array<u64>(ctx, WIDE_MAX_PARTS + 2);
-    u64 **d_tab = (u64 **)arena_array<u64>(ctx, WIDE_TB_MAX);
-    if (!d_cuts || !d_tab) return BWTS_E_NOMEM;
-    if ((!direct && !rank64) || !segkeys || !segprev || !tile_min || !pre_temp || !bk[1] || !bv[1] || !bs_src || !bs_buf[1] || !bs_fin || !tile_hist || !scan_temp ||
-        !headw || !keepw || !prew || !cand[1] || !cvals[1] || !fstart || !d_hist)
-        return BWTS_E_NOMEM;
-
-    // ---- alphabet and key format ---------------------------------------------------------------------------------------
-    BWTS_TRY(read_histogram(ctx, d_T, n));
-    Alphabet al;
-    BWTS_TRY(set_alphabet(ctx, suffix, n, &al));          // (suffixes: code 0 is "past the end", fixed-width codes)
-    if (!suffix) {
-        ctx->tm.key_symbols = (u32)al.msym;
-        ctx->tm.key_bits = (u32)al.key_bits;
+    sh.Mb = sh.M > whole ? sh.M : whole;
+    sh.mwords = (sh.Mb + 63) / 64 + 1;
+    sh.sort_max = sh.Mb > sh.seg ? sh.Mb : sh.seg;                    // largest sort or scan through tile_hist / scan_temp:
+    if (sh.sort_max < LYN_CAND_CAP) sh.sort_max = LYN_CAND_CAP;       // a bucket, a segment, or the factor candidates
+    return sh;
+}
+// The arena of one run: every array it holds, declared once and in the order the code meets them
+struct WideArena {
+    u64 *rank64 = nullptr;                        // global rank of every position (absent in WIDE_DIRECT)
+    u64 *segkeys; u8 *segprev;                    // one segment: round-0 keys, output bytes
+    u64 *tile_min; void *pre_temp;                // smallest key of every scan tile; partials of a scan over n elements
+    u64 *bk[2]; u32 *bv[2];                       // a bucket's (or a part's) sort buffers: keys, position low words ...
+    u8  *bs_src, *bs_buf[2], *bs_fin;             // ... and the byte stream that travels with them: source, ping-pong, result
+    u32 *tile_hist; void *scan_temp;              // of sorts and scans up to sort_max elements
+    u64 *headw, *keepw, *prew;                    // a sorted bucket's flag words: group heads, tied elements, their word scan
+    u64 *cand[2]; u32 *cvals[2]; u64 *fstart;     // Lyndon candidates, LYN_CAND_CAP each: the set, its sort's values, the factor starts found
+    u32 *d_hist; u64 *d_cuts; u64 **d_tab;        // key-prefix histogram of every segment; part cuts of a round; block table of the tied list
+    void declare(BlockLayout &L, const WideShape &sh)
+    {
+        if (sh.mode != WIDE_DIRECT) L.array(&rank64, sh.n);
+        L.array(&segkeys, sh.seg); L.array(&segprev, sh.seg);
+        L.array(&tile_min, sh.tiles + 1); L.raw(&pre_temp, scan_temp_bytes(sh.n));
+        L.arrays(sh.Mb, &bk[0], &bk[1]); L.arrays(sh.Mb, &bv[0], &bv[1]); L.arrays(sh.Mb, &bs_src, &bs_buf[0], &bs_buf[1], &bs_fin);
+        L.raw(&tile_hist, radix_tile_hist_bytes(sh.sort_max)); L.raw(&scan_temp, scan_temp_bytes(sh.sort_max));
+        L.arrays(sh.mwords, &headw, &keepw, &prew);
+        L.arrays(LYN_CAND_CAP, &cand[0], &cand[1]); L.arrays(LYN_CAND_CAP, &cvals[0], &cvals[1]); L.array(&fstart, LYN_CAND_CAP);
+        L.array(&d_hist, sh.nseg * WIDE_PREFIXES); L.array(&d_cuts, WIDE_MAX_PARTS + 2); L.array(&d_tab, WIDE_TB_MAX);
     }
-    const int pbits = al.key_bits < WIDE_PREFIX_BITS ? al.key_bits : WIDE_PREFIX_BITS;
-    const int pshift = al.key_bits - pbits;
-    const u64 *d_vtab = al.varlen ? ctx->d_small + SM_VTAB : nullptr;
-    const u8 *d_codes = (const u8 *)(ctx->d_small + SM_CODES);
-    auto seg_count = [&](u64 s) -> u64 { const u64 p0 = s * seg; return n - p0 < seg ? n - p0 : seg; };
+    SortPlan plan() const { return sort_plan(bk[0], bk[1], bv[0], bv[1], tile_hist, scan_temp); }
+};
+static size_t forward_wide_arena_bytes(const WideShape &sh) { WideArena A; BlockLayout L; A.declare(L, sh); return L.bytes(); }
+// bwts_debug_wide_forward_arena: no context, no device; 0 for a knob means the engine's own choice
+int forward_wide_arena_probe(u64 n, int mode, int seg_log2, u64 bucket_cap, u64 *bytes)
+{
+    if (n == 0 || n > (1ull << 36) || mode < WIDE_DIRECT || mode > WIDE_SUFFIX || !bytes) return -1;
+    if ((seg_log2 && (seg_log2 < 11 || seg_log2 > 31)) || (bucket_cap && (bucket_cap < 256 || bucket_cap > 0xff000000ull))) return -1;
+    const WideKnobs kn{seg_log2 ? seg_log2 : 30, bucket_cap ? bucket_cap : 1ull << 30, 0, 0, -1, bucket_cap != 0};
+    *bytes = forward_wide_arena_bytes(wide_shape(kn, n, (WideMode)mode));
+    return 0;
+}
+// reserves the arena and points A's arrays into it
+static int wide_arena_place(bwts_ctx *ctx, const WideShape &sh, WideArena &A)
+{
+    BlockLayout L;
+    A.declare(L, sh);
+    BWTS_TRY(arena_reserve(ctx, L.bytes()));
+    char *base = (char *)arena_alloc(ctx, L.bytes());
+    if (base) L.place(base);
+    return base ? BWTS_OK : BWTS_E_NOMEM;
+}
+// One run.  The inputs and the shape are set when it is made; every other member is written by the one stage named beside it.
+struct WideRun {
+    bwts_ctx *ctx; const u8 *d_T; u64 n; u8 *d_out; WideFactors *fac;
+    const bool direct, suffix, search;            // search: the candidate search for the factors runs here
+    const WideShape sh; WideArena A;              // wide_shape; wide_arena_place
+    Alphabet al; int pbits, pshift;               // wide_alphabet: the alphabet, and the key's prefix that names the bucket
+    const u64 *fs; u64 k; PrevSym64 prev;         // wide_candidate_factors: the factors (found, or handed in by the suffix route) ...
+    bool carry;                                   // ... and whether the output byte travels with the sort (see WideFilterOut)
+    std::vector<u32> h_hist, cut;                 // wide_bucket_plan: segment histograms; bucket b = prefixes [cut[b], cut[b + 1]);
+    std::vector<u64> ptotal; int tlg; TiedList tl; //                  positions per prefix; the tied list
+    u64 tied_total = 0, base = 0;                 // wide_bucket: tied elements so far; first rank of the next bucket
+    u64 a = 0;                                    // wide_buckets_done, then wide_rounds: tied elements left
+    u32 rounds = 1; int rb; u64 P;                // wide_rounds: rounds made; rank bits and part size of its sort keys
+    std::vector<u64> h_cuts;                      // wide_cut_parts: cuts of the latest call
+    int &redo;                                    // any stage: the run cannot finish in this mode, and what it needs (WIDE_NEED_*)
+    WideRun(bwts_ctx *c, const u8 *T, u64 n_, u8 *out, WideMode mode, WideFactors *f, int &rd)
+        : ctx(c), d_T(T), n(n_), d_out(out), fac(f), direct(mode == WIDE_DIRECT), suffix(mode == WIDE_SUFFIX),
+          search(mode != WIDE_SUFFIX && !f->fstart), sh(wide_shape(wide_knobs(c), n_, mode)), redo(rd) {}
+};
 
-    // ---- Lyndon factors (mk_bwts_sa.c:126-129): candidate search as on the main path, segment by segment -- or the list the
-    // suffix route made (which itself sorts suffixes and needs none) ------------------------------------------------------------
-    if (search)
-        for (u64 s = 0; s < nseg; s++)
-            BWTS_TRY(launch_keybuild0_seg(ctx, d_T, n, al, segkeys, tile_min + s * (seg / KB_TILE), false, s * seg, seg_count(s)));
-    else if (direct && kn.direct < 0)
-        BWTS_TRY(launch_keybuild0_seg(ctx, d_T, n, al, segkeys, nullptr, false, (nseg - 1) * seg, seg_count(nseg - 1)));     // (the sample's)
-    u64 *cnt = ctx->d_small + SM_COUNTERS;
-    if (direct && kn.direct < 0) {
-        // is this an input with few ties at all?  2^20 of the last segment's keys (still in segkeys), sorted: text shows 10^5 equal
-        // neighbours, i.i.d. data none.  Two or more: the rank array is needed, and the caller is told before a bucket is sorted.
-        const u64 c = seg_count(nseg - 1);
-        const u32 m = c >= (1u << 20) ? (1u << 20) : (u32)c;
-        if (m >= 4096 && m <= Mb) {
-            HIPC(hipMemsetAsync(cnt + 27, 0, sizeof(u64), ctx->stream));
-            wide_sample_keys_kernel<<<dim3((m + 255) / 256), dim3(256), 0, ctx->stream>>>(segkeys, c, m, bk[0], bv[0]);
-            HIPC(hipGetLastError());
-            SortPlan spn = sort_plan(bk[0], bk[1], bv[0], bv[1], tile_hist, scan_temp);
-            int sres = 0;
-            BWTS_TRY(radix_sort_pairs(ctx, spn, m, al.key_bits, &sres));
-            wide_sample_ties_kernel<<<dim3((m + 255) / 256), dim3(256), 0, ctx->stream>>>(spn.keys[sres], m, cnt + 27);
-            HIPC(hipGetLastError());
-            BWTS_TRY(read_small(ctx, SM_COUNTERS + 27, 1));
-            if (ctx->h_small[SM_COUNTERS + 27] >= 2) { *redo = WIDE_NEED_RANKS; return BWTS_OK; }
-        }
-    }
-    const u64 *fs = fac->fstart;
-    u64 k = fac->k;
-    if (search) {
-        HIPC(hipMemsetAsync(cnt + 4, 0, 4 * sizeof(u64), ctx->stream));
+static int wide_alphabet(WideRun &r)
+{
+    BWTS_TRY(read_histogram(r.ctx, r.d_T, r.n));
+    BWTS_TRY(set_alphabet(r.ctx, r.suffix, r.n, &r.al));          // (suffixes: code 0 is "past the end", fixed-width codes)
+    if (!r.suffix) { r.ctx->tm.key_symbols = (u32)r.al.msym; r.ctx->tm.key_bits = (u32)r.al.key_bits; }
+    r.pbits = r.al.key_bits < WIDE_PREFIX_BITS ? r.al.key_bits : WIDE_PREFIX_BITS;
+    r.pshift = r.al.key_bits - r.pbits;
+    return BWTS_OK;
+}
+// the key builds in front of the factor search: every segment with its tile minima when the factors are searched, else the last segment for the sample
+static int wide_first_keys(WideRun &r)
+{
+    const WideShape &sh = r.sh;
+    if (r.search)
+        for (u64 s = 0; s < sh.nseg; s++)
+            BWTS_TRY(launch_keybuild0_seg(r.ctx, r.d_T, r.n, r.al, r.A.segkeys, r.A.tile_min + s * (sh.seg / KB_TILE), false, s * sh.seg, sh.seg_count(s)));
+    else if (r.direct && sh.kn.direct < 0)
+        BWTS_TRY(launch_keybuild0_seg(r.ctx, r.d_T, r.n, r.al, r.A.segkeys, nullptr, false, (sh.nseg - 1) * sh.seg, sh.seg_count(sh.nseg - 1)));
+    return BWTS_OK;
+}
+// is this an input with few ties at all?  2^20 of the last segment's keys (still in segkeys), sorted: text shows 10^5 equal
+// neighbours, i.i.d. data none.  Two or more: the rank array is needed, and the caller is told before a bucket is sorted.
+static int wide_sample_ties(WideRun &r)
+{
+    bwts_ctx *ctx = r.ctx; const WideArena &A = r.A;
+    if (!r.direct || r.sh.kn.direct >= 0) return BWTS_OK;
+    const u64 c = r.sh.seg_count(r.sh.nseg - 1);
+    const u32 m = c >= (1u << 20) ? (1u << 20) : (u32)c;
+    if (m < 4096 || m > r.sh.Mb) return BWTS_OK;
+    HIPC(hipMemsetAsync(wide_counter(ctx, WC_SAMPLE_TIES), 0, sizeof(u64), ctx->stream));
+    wide_sample_keys_kernel<<<dim3((m + 255) / 256), dim3(256), 0, ctx->stream>>>(A.segkeys, c, m, A.bk[0], A.bv[0]);
+    HIPC(hipGetLastError());
+    SortPlan spn = A.plan();
+    int sres = 0;
+    BWTS_TRY(radix_sort_pairs(ctx, spn, m, r.al.key_bits, &sres));
+    wide_sample_ties_kernel<<<dim3((m + 255) / 256), dim3(256), 0, ctx->stream>>>(spn.keys[sres], m, wide_counter(ctx, WC_SAMPLE_TIES));
+    HIPC(hipGetLastError());
+    BWTS_TRY(read_small(ctx, SM_COUNTERS + WC_SAMPLE_TIES, 1));
+    if (wide_count(ctx, WC_SAMPLE_TIES) >= 2) r.redo = WIDE_NEED_RANKS;
+    return BWTS_OK;
+}
+// The Lyndon factors (mk_bwts_sa.c:126-129): the list the suffix route made (which itself sorts suffixes and needs none), or the candidate search
+// of the main path, segment by segment over the global prefix minima of the tile minima; then what hangs on them
+static int wide_candidate_factors(WideRun &r)
+{
+    bwts_ctx *ctx = r.ctx; const WideShape &sh = r.sh; WideArena &A = r.A;
+    r.fs = r.fac->fstart; r.k = r.fac->k;
+    if (r.search) {
+        HIPC(hipMemsetAsync(ctx->d_small + CNT_CAND, 0, 4 * sizeof(u64), ctx->stream));
         {
-            SpanGuard g(ctx, BWTS_K_LYNDON, n, 0);
+            SpanGuard g(ctx, BWTS_K_LYNDON, r.n, 0);
             // exclusive prefix minima of the tile minima, in pre_temp (laid out like the partials of a scan over n elements)
-            HIPC(hipMemcpyAsync(pre_temp, tile_min, tiles * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
-            BWTS_TRY((device_scan_partials<u64, OpMin>(ctx, tiles, OpMin(), ~0ull, pre_temp)));
+            HIPC(hipMemcpyAsync(A.pre_temp, A.tile_min, sh.tiles * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
+            BWTS_TRY((device_scan_partials<u64, OpMin>(ctx, sh.tiles, OpMin(), ~0ull, A.pre_temp)));
         }
-        for (u64 s = 0; s < nseg; s++) {
-            const u64 p0 = s * seg, c = seg_count(s), t0 = p0 / KB_TILE;
-            BWTS_TRY(launch_keybuild0_seg(ctx, d_T, n, al, segkeys, nullptr, false, p0, c));
+        for (u64 s = 0; s < sh.nseg; s++) {
+            const u64 p0 = s * sh.seg, c = sh.seg_count(s), t0 = p0 / KB_TILE;
+            BWTS_TRY(launch_keybuild0_seg(ctx, r.d_T, r.n, r.al, A.segkeys, nullptr, false, p0, c));
             SpanGuard g(ctx, BWTS_K_LYNDON, c, 8 * c);
-            const KeyStore ks = key_store_of(segkeys, c, false, al.key_bits);
+            const KeyStore ks = key_store_of(A.segkeys, c, false, r.al.key_bits);
             KeyIn in{ks};
-            CandOut out{ks, n, al.varlen ? 64 : al.msym, cand[0], LYN_CAND_CAP, ctx->d_small + CNT_CAND, p0};
-            TileMayHoldCandidate filter{tile_min + t0};
-            BWTS_TRY((device_scan_final<false, u64>(ctx, c, in, out, OpMin(), ~0ull, (u64 *)pre_temp + t0, filter)));
+            CandOut out{ks, r.n, r.al.varlen ? 64 : r.al.msym, A.cand[0], LYN_CAND_CAP, ctx->d_small + CNT_CAND, p0};
+            TileMayHoldCandidate filter{A.tile_min + t0};
+            BWTS_TRY((device_scan_final<false, u64>(ctx, c, in, out, OpMin(), ~0ull, (u64 *)A.pre_temp + t0, filter)));
         }
         BWTS_TRY(read_small(ctx, CNT_CAND, 1));
         const u64 cnt_c = ctx->h_small[CNT_CAND];
         if (cnt_c == 0) return BWTS_E_INTERNAL;
-        if (cnt_c > LYN_CAND_CAP) { *redo = WIDE_NEED_SUFFIX; return BWTS_OK; }      // (runs of the smallest byte, a^n, (ab)^n ...)
-        {
-            SortPlan cp = sort_plan(cand[0], cand[1], cvals[0], cvals[1], tile_hist, scan_temp);
-            int res = 0;
-            BWTS_TRY(radix_sort_pairs(ctx, cp, cnt_c, bitlen_u64(n) + 1, &res));
-            LynState *d_st = (LynState *)(ctx->d_small + CNT_LYN_K);
-            LynState *h_st = (LynState *)(ctx->h_small + CNT_LYN_K);
-            unsigned long long *d_mis = (unsigned long long *)(ctx->d_small + CNT_LYN_K + 8);
-            HIPC(hipMemsetAsync(d_st, 0, sizeof(LynState), ctx->stream));
-            for (int iter = 0;; iter++) {
-                {
-                    SpanGuard g(ctx, BWTS_K_LYNDON, cnt_c, 0);
-                    lyndon_resolve_kernel<u64><<<dim3(1), dim3(256), 0, ctx->stream>>>(d_T, n, cand[res], cnt_c, fstart, d_st, LYN_WORK_CAP);
-                    HIPC(hipGetLastError());
-                }
-                BWTS_TRY(read_small(ctx, CNT_LYN_K, 8));
-                if (h_st->status == 0) break;
-                if (h_st->status == 2 || iter > 4096) { *redo = WIDE_NEED_SUFFIX; return BWTS_OK; }      // too much sequential work
-                u64 e = 0;
-                HIPC(hipMemcpyAsync(&e, cand[res] + h_st->next, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-                HIPC(hipStreamSynchronize(ctx->stream));
-                const u64 pp = e >> 1, qq = h_st->cur;
-                const u64 len = n - pp;
-                HIPC(hipMemcpyAsync(d_mis, &len, sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-                {
-                    SpanGuard g(ctx, BWTS_K_LYNDON, len, 2 * len);
-                    u64 blocks = (len + 255) / 256; if (blocks > 4096) blocks = 4096;
-                    suffix_mismatch_grid_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(d_T, n, pp, qq, d_mis);
-                    HIPC(hipGetLastError());
-                }
-                BWTS_TRY(read_small(ctx, CNT_LYN_K + 8, 1));
-                const u64 at = ctx->h_small[CNT_LYN_K + 8];
-                bool less;
-                if (at >= len) less = true;
-                else {
-                    u8 ab[2];
-                    HIPC(hipMemcpyAsync(&ab[0], d_T + pp + at, 1, hipMemcpyDeviceToHost, ctx->stream));
-                    HIPC(hipMemcpyAsync(&ab[1], d_T + qq + at, 1, hipMemcpyDeviceToHost, ctx->stream));
-                    HIPC(hipStreamSynchronize(ctx->stream));
-                    less = ab[0] < ab[1];
-                }
-                h_st->forced = 1; h_st->forced_less = less ? 1 : 0; h_st->status = 0;
-                HIPC(hipMemcpyAsync(d_st, h_st, sizeof(LynState), hipMemcpyHostToDevice, ctx->stream));
-                HIPC(hipStreamSynchronize(ctx->stream));
-            }
-            k = h_st->k;
-            if (k == 0) return BWTS_E_INTERNAL;
-        }
-        fs = fstart;
+        bool settled = false;      // (more candidates than the set holds: runs of the smallest byte, a^n, (ab)^n ...)
+        if (cnt_c <= LYN_CAND_CAP)
+            BWTS_TRY(lyndon_resolve_candidates<u64>(ctx, r.d_T, r.n, A.cand, A.cvals, A.tile_hist, A.scan_temp, cnt_c, A.fstart, &r.k, &settled));
+        if (!settled) { r.redo = WIDE_NEED_SUFFIX; return BWTS_OK; }
+        r.fs = A.fstart;
     }
-    if (!suffix) ctx->tm.factors = k;
-    const PrevSym64 prev{d_T, n, fs, k};
-    const bool carry_ok = [ctx] { const char *e = bwts_knob(ctx, "BWTS_WIDE_CARRY"); return !(e && atoi(e) == 0); }();
+    if (!r.suffix) ctx->tm.factors = r.k;
+    r.prev = PrevSym64{r.d_T, r.n, r.fs, r.k};
+    const char *e = bwts_knob(ctx, "BWTS_WIDE_CARRY");
     // the output byte travels with the sort (see WideFilterOut): the passes cover whole bytes of the key, so the parked bits must lie above them
     // (the suffix sort emits nothing: its byte stream carries the position bits)
-    const bool carry = !suffix && carry_ok && 8 * ((al.key_bits + 7) / 8) <= WIDE_HI_SHIFT;
-
-    // round-0 keys of one segment: keybuild, and for rotations the wrap-around patch near the factor ends (suffixes end in code 0)
-    auto seg_keys = [&](u64 s) -> int {
-        const u64 p0 = s * seg, c = seg_count(s);
-        BWTS_TRY(launch_keybuild0_seg(ctx, d_T, n, al, segkeys, nullptr, false, p0, c, carry ? segprev : nullptr));
-        const int span = al.varlen ? 64 : al.msym - 1;
-        if (!suffix && span > 0) {
-            u64 blocks = (k * (u64)span + 255) / 256; if (blocks > 4096) blocks = 4096;
-            cyclic_patch_wide_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(
-                d_T, n, d_codes, al.bits, al.msym, d_vtab, al.key_bits, span, fs, k, segkeys, p0, p0 + c);
-            HIPC(hipGetLastError());
-        }
-        if (carry) {
-            u64 blocks = (k + 255) / 256; if (blocks > 4096) blocks = 4096;
-            wide_head_prev_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(d_T, n, fs, k, segprev, p0, p0 + c);
-            HIPC(hipGetLastError());
-        }
-        return BWTS_OK;
-    };
-
-    // ---- bucket sizes: histogram of the key prefixes, per segment --------------------------------------------------------
-    HIPC(hipMemsetAsync(d_hist, 0, nseg * WIDE_PREFIXES * sizeof(u32), ctx->stream));
-    for (u64 s = 0; s < nseg; s++) {
-        BWTS_TRY(seg_keys(s));
-        const u64 c = seg_count(s);
+    r.carry = !r.suffix && !(e && atoi(e) == 0) && 8 * ((r.al.key_bits + 7) / 8) <= WIDE_HI_SHIFT;
+    return BWTS_OK;
+}
+// round-0 keys of one segment: keybuild, and for rotations the wrap-around patch near the factor ends (suffixes end in code 0)
+static int wide_seg_keys(WideRun &r, u64 s)
+{
+    bwts_ctx *ctx = r.ctx; const Alphabet &al = r.al; const WideArena &A = r.A;
+    const u64 p0 = s * r.sh.seg, c = r.sh.seg_count(s);
+    BWTS_TRY(launch_keybuild0_seg(ctx, r.d_T, r.n, al, A.segkeys, nullptr, false, p0, c, r.carry ? A.segprev : nullptr));
+    const int span = al.varlen ? 64 : al.msym - 1;
+    if (!r.suffix && span > 0) {
+        u64 blocks = (r.k * (u64)span + 255) / 256; if (blocks > 4096) blocks = 4096;
+        cyclic_patch_wide_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(
+            r.d_T, r.n, (const u8 *)(ctx->d_small + SM_CODES), al.bits, al.msym, al.varlen ? ctx->d_small + SM_VTAB : nullptr, al.key_bits, span, r.fs, r.k, A.segkeys, p0, p0 + c);
+        HIPC(hipGetLastError());
+    }
+    if (r.carry) {
+        u64 blocks = (r.k + 255) / 256; if (blocks > 4096) blocks = 4096;
+        wide_head_prev_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(r.d_T, r.n, r.fs, r.k, A.segprev, p0, p0 + c);
+        HIPC(hipGetLastError());
+    }
+    return BWTS_OK;
+}
+// greedy: consecutive prefixes while the bucket stays within M.  false: one key prefix holds more positions than a bucket may (no finer cut in this form)
+static bool wide_greedy_cut(const std::vector<u64> &ptotal, u64 M, std::vector<u32> &cut)
+{
+    u64 run = 0;
+    cut.assign(1, 0);
+    for (u32 q = 0; q < ptotal.size(); q++) {
+        if (ptotal[q] > M) return false;
+        if (run + ptotal[q] > M) { cut.push_back(q); run = 0; }
+        run += ptotal[q];
+    }
+    cut.push_back((u32)ptotal.size());
+    return true;
+}
+// bucket sizes: histogram of the key prefixes, per segment; their totals on the host; the cut into buckets; the empty tied list
+static int wide_bucket_plan(WideRun &r)
+{
+    bwts_ctx *ctx = r.ctx; const WideShape &sh = r.sh; const WideArena &A = r.A;
+    HIPC(hipMemsetAsync(A.d_hist, 0, sh.nseg * WIDE_PREFIXES * sizeof(u32), ctx->stream));
+    for (u64 s = 0; s < sh.nseg; s++) {
+        BWTS_TRY(wide_seg_keys(r, s));
+        const u64 c = sh.seg_count(s);
         u64 blocks = (c + 255) / 256; if (blocks > 2048) blocks = 2048;
         SpanGuard g(ctx, BWTS_K_HISTOGRAM, c, 8 * c);
-        wide_prefix_hist_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(segkeys, c, pshift, d_hist + s * WIDE_PREFIXES);
+        wide_prefix_hist_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(A.segkeys, c, r.pshift, A.d_hist + s * WIDE_PREFIXES);
         HIPC(hipGetLastError());
     }
-    std::vector<u32> h_hist((size_t)nseg * WIDE_PREFIXES);
-    HIPC(hipMemcpyAsync(h_hist.data(), d_hist, h_hist.size() * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+    r.h_hist.resize((size_t)sh.nseg * WIDE_PREFIXES);
+    HIPC(hipMemcpyAsync(r.h_hist.data(), A.d_hist, r.h_hist.size() * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
-    const u32 nprefix = 1u << pbits;
-    std::vector<u64> ptotal(nprefix, 0);
-    for (u64 s = 0; s < nseg; s++) for (u32 q = 0; q < nprefix; q++) ptotal[q] += h_hist[(size_t)s * WIDE_PREFIXES + q];
-    // greedy: consecutive prefixes while the bucket stays within M
-    std::vector<u32> cut;                 // bucket b = prefixes [cut[b], cut[b + 1])
+    r.ptotal.assign(1u << r.pbits, 0);
+    for (u64 s = 0; s < sh.nseg; s++) for (u32 q = 0; q < r.ptotal.size(); q++) r.ptotal[q] += r.h_hist[(size_t)s * WIDE_PREFIXES + q];
+    if (!wide_greedy_cut(r.ptotal, sh.M, r.cut)) return BWTS_E_RANGE;
+    // the tied list: blocks taken as it grows
+    r.tlg = sh.kn.tblock_log2;
+    if (!r.tlg) { r.tlg = bitlen_u64(r.n - 1); if (r.tlg < 8) r.tlg = 8; if (r.tlg > 28) r.tlg = 28; }
+    BWTS_TRY(wide_tied_ensure(ctx, 1, r.tlg, A.d_tab, true));
+    r.tl = TiedList{A.d_tab, ctx->tied_blk_lg};
+    HIPC(hipMemsetAsync(wide_counter(ctx, WC_TIED), 0, 2 * sizeof(u64), ctx->stream));       // (WC_TIED and WC_OVERFLOW)
+    return BWTS_OK;
+}
+// one bucket, prefixes [plo, phi): collect its members segment by segment (stable), sort, flag groups and ties, make room in the tied
+// list, finish (the kernel instantiation by mode)
+static int wide_bucket(WideRun &r, u32 plo, u32 phi)
+{
+    bwts_ctx *ctx = r.ctx; const WideShape &sh = r.sh; const WideArena &A = r.A;
+    u64 m = 0;
+    for (u32 q = plo; q < phi; q++) m += r.ptotal[q];
+    if (m == 0) return BWTS_OK;
+    u64 off = 0;
+    for (u64 s = 0; s < sh.nseg; s++) {
+        u64 share = 0;
+        for (u32 q = plo; q < phi; q++) share += r.h_hist[(size_t)s * WIDE_PREFIXES + q];
+        if (share == 0) continue;
+        BWTS_TRY(wide_seg_keys(r, s));
+        const u64 c = sh.seg_count(s);
+        SpanGuard g(ctx, BWTS_K_RERANK, c, 9 * c + 13 * share);
+        WideFilterIn fin{A.segkeys, r.pshift, plo, phi};
+        WideFilterOut fout{A.segkeys, r.pshift, plo, phi, s * sh.seg, A.bk[0] + off, A.bv[0] + off, A.bs_src + off, r.carry ? A.segprev : nullptr};
+        BWTS_TRY((device_scan<false, u32>(ctx, c, fin, fout, OpAdd(), 0u, A.scan_temp)));
+        off += share;
+    }
+    if (off != m) return BWTS_E_INTERNAL;
+    SortPlan sp = A.plan();
+    sp.sym_src = A.bs_src; sp.sym_buf[0] = A.bs_buf[0]; sp.sym_buf[1] = A.bs_buf[1]; sp.sym_final = A.bs_fin;
+    int res = 0;
+    BWTS_TRY(radix_sort_pairs(ctx, sp, m, r.al.key_bits, &res));
+    const u64 words = (m + 63) / 64;
     {
-        u64 run = 0;
-        cut.push_back(0);
-        for (u32 q = 0; q < nprefix; q++) {
-            if (ptotal[q] > M) return BWTS_E_RANGE;        // one key prefix holds more positions than a bucket may: no finer cut in this form
-            if (run + ptotal[q] > M) { cut.push_back(q); run = 0; }
-            run += ptotal[q];
-        }
-        cut.push_back(nprefix);
+        SpanGuard g(ctx, BWTS_K_RERANK, m, 8 * m);
+        u64 waves = (words + GF_WORDS - 1) / GF_WORDS;
+        unsigned blocks = (unsigned)((waves + 3) / 4 < 16384 ? (waves + 3) / 4 : 16384);
+        group_flags_kernel<GfWide><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(GfWide{sp.keys[res], r.carry ? (1ull << WIDE_HI_SHIFT) - 1ull : ~0ull},
+                                                                                m, A.headw, A.keepw);
+        WordIn win{A.headw, A.keepw};
+        ScanStoreArr<u64> wout{A.prew};
+        BWTS_TRY((device_scan<false, u64>(ctx, words, win, wout, OpHeadCount(), (u64)0, A.scan_temp)));
     }
-
-    // ---- tied list: blocks taken as it grows ---------------------------------------------------------------------------------
-    int tlg = kn.tblock_log2;
-    if (!tlg) { tlg = bitlen_u64(n - 1); if (tlg < 8) tlg = 8; if (tlg > 28) tlg = 28; }
-    BWTS_TRY(wide_tied_ensure(ctx, 1, tlg, d_tab, true));
-    TiedList tl{d_tab, ctx->tied_blk_lg};
-    u64 *d_tied = cnt + 24, *d_over = cnt + 25;
-    HIPC(hipMemsetAsync(cnt + 24, 0, 2 * sizeof(u64), ctx->stream));
-    u64 tied_total = 0;
-
-    // ---- bucket by bucket ----------------------------------------------------------------------------------------------------
-    u64 base = 0;
-    for (size_t b = 0; b + 1 < cut.size(); b++) {
-        const u32 plo = cut[b], phi = cut[b + 1];
-        u64 m = 0;
-        for (u32 q = plo; q < phi; q++) m += ptotal[q];
-        if (m == 0) continue;
-        u64 off = 0;
-        for (u64 s = 0; s < nseg; s++) {
-            u64 share = 0;
-            for (u32 q = plo; q < phi; q++) share += h_hist[(size_t)s * WIDE_PREFIXES + q];
-            if (share == 0) continue;
-            BWTS_TRY(seg_keys(s));
-            const u64 c = seg_count(s);
-            SpanGuard g(ctx, BWTS_K_RERANK, c, 9 * c + 13 * share);
-            WideFilterIn fin{segkeys, pshift, plo, phi};
-            WideFilterOut fout{segkeys, pshift, plo, phi, s * seg, bk[0] + off, bv[0] + off, bs_src + off, carry ? segprev : nullptr};
-            BWTS_TRY((device_scan<false, u32>(ctx, c, fin, fout, OpAdd(), 0u, scan_temp)));
-            off += share;
-        }
-        if (off != m) return BWTS_E_INTERNAL;
-        SortPlan sp = sort_plan(bk[0], bk[1], bv[0], bv[1], tile_hist, scan_temp);
-        sp.sym_src = bs_src; sp.sym_buf[0] = bs_buf[0]; sp.sym_buf[1] = bs_buf[1]; sp.sym_final = bs_fin;
-        int res = 0;
-        BWTS_TRY(radix_sort_pairs(ctx, sp, m, al.key_bits, &res));
-        const u64 words = (m + 63) / 64;
-        {
-            SpanGuard g(ctx, BWTS_K_RERANK, m, 8 * m);
-            u64 waves = (words + GF_WORDS - 1) / GF_WORDS;
-            unsigned blocks = (unsigned)((waves + 3) / 4 < 16384 ? (waves + 3) / 4 : 16384);
-            group_flags_kernel<GfWide><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(GfWide{sp.keys[res], carry ? (1ull << WIDE_HI_SHIFT) - 1ull : ~0ull},
-                                                                                    m, headw, keepw);
-            WordIn win{headw, keepw};
-            ScanStoreArr<u64> wout{prew};
-            BWTS_TRY((device_scan<false, u64>(ctx, words, win, wout, OpHeadCount(), (u64)0, scan_temp)));
-        }
-        // the bucket's tied elements are counted before they are written: the list takes another block when they need one
-        wide_add_tied_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(keepw, prew, words, d_tied);
+    // the bucket's tied elements are counted before they are written: the list takes another block when they need one
+    wide_add_tied_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(A.keepw, A.prew, words, wide_counter(ctx, WC_TIED));
+    HIPC(hipGetLastError());
+    BWTS_TRY(read_small(ctx, SM_COUNTERS + WC_TIED, 1));
+    const u64 tied_before = r.tied_total;
+    r.tied_total = wide_count(ctx, WC_TIED);
+    if (r.tied_total < tied_before || r.tied_total - tied_before > m) return BWTS_E_INTERNAL;
+    if (r.direct && r.tied_total > WIDE_DIRECT_MAX) { r.redo = WIDE_NEED_RANKS; return BWTS_OK; }        // many ties: this input needs the ranks
+    BWTS_TRY(wide_tied_ensure(ctx, r.tied_total ? r.tied_total : 1, r.tlg, A.d_tab, false));
+    {
+        SpanGuard g(ctx, BWTS_K_EMIT, m, 15 * m);
+        u64 blocks = (m + 255) / 256; if (blocks > 16384) blocks = 16384;
+        const auto finish = r.suffix ? wide_bucket_finish_kernel<false, false> : r.carry ? wide_bucket_finish_kernel<true, true> : wide_bucket_finish_kernel<false, true>;
+        finish<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(sp.keys[res], sp.vals[res], A.bs_fin, m, r.base, A.headw, A.keepw, A.prew, A.rank64, r.prev,
+                                                                      r.suffix ? nullptr : r.d_out, tied_before, r.tied_total, r.tl, wide_counter(ctx, WC_OVERFLOW), r.n);
         HIPC(hipGetLastError());
-        BWTS_TRY(read_small(ctx, SM_COUNTERS + 24, 1));
-        const u64 tied_before = tied_total;
-        tied_total = ctx->h_small[SM_COUNTERS + 24];
-        if (tied_total < tied_before || tied_total - tied_before > m) return BWTS_E_INTERNAL;
-        if (direct && tied_total > WIDE_DIRECT_MAX) { *redo = WIDE_NEED_RANKS; return BWTS_OK; }        // many ties: this input needs the ranks
-        BWTS_TRY(wide_tied_ensure(ctx, tied_total ? tied_total : 1, tlg, d_tab, false));
-        {
-            SpanGuard g(ctx, BWTS_K_EMIT, m, 15 * m);
-            u64 blocks = (m + 255) / 256; if (blocks > 16384) blocks = 16384;
-            if (suffix)
-                wide_bucket_finish_kernel<false, false><<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(sp.keys[res], sp.vals[res], bs_fin, m, base, headw, keepw,
-                                                                                                              prew, rank64, prev, nullptr, tied_before, tied_total, tl, d_over, n);
-            else if (carry)
-                wide_bucket_finish_kernel<true, true><<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(sp.keys[res], sp.vals[res], bs_fin, m, base, headw, keepw,
-                                                                                                             prew, rank64, prev, d_out, tied_before, tied_total, tl, d_over, n);
-            else
-                wide_bucket_finish_kernel<false, true><<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(sp.keys[res], sp.vals[res], bs_fin, m, base, headw, keepw,
-                                                                                                              prew, rank64, prev, d_out, tied_before, tied_total, tl, d_over, n);
-            HIPC(hipGetLastError());
-        }
-        base += m;
     }
-    if (base != n) return BWTS_E_INTERNAL;
-    BWTS_TRY(read_small(ctx, SM_COUNTERS + 24, 2));
-    u64 a = ctx->h_small[SM_COUNTERS + 24];
-    if (ctx->h_small[SM_COUNTERS + 25] == 2) return BWTS_E_INTERNAL;              // a sorted element carried a position outside the text
-    if (ctx->h_small[SM_COUNTERS + 25] || a != tied_total) return BWTS_E_INTERNAL; // (the list had room for every count read above)
-    if (!suffix) {
-        ctx->tm.active_after_round0 = a;
-        ctx->tm.round_active[0] = a;
-    }
-    if (direct) {
-        if (a) {
-            if (a > WIDE_DIRECT_MAX) { *redo = WIDE_NEED_RANKS; return BWTS_OK; }
-            SpanGuard g(ctx, BWTS_K_RERANK, a, 40 * a);
-            u32 *gstart = bv[0];                         // (a <= WIDE_DIRECT_MAX <= the buffers' size)
-            if (a > Mb) return BWTS_E_INTERNAL;
-            HIPC(hipMemsetAsync(cnt, 0, 4 * sizeof(u64), ctx->stream));
-            WideGroupIn gin{tl};
-            WideGroupOut gout{tl, gstart, a, cnt + 3};
-            BWTS_TRY((device_scan<false, u32>(ctx, a, gin, gout, OpAdd(), 0u, scan_temp)));
-            BWTS_TRY(read_small(ctx, SM_COUNTERS, 4));
-            const u64 ngroups = ctx->h_small[SM_COUNTERS + 3];
-            if (ngroups == 0 || ngroups > a) return BWTS_E_INTERNAL;
-            wide_direct_groups_kernel<<<dim3((unsigned)((ngroups + 63) / 64)), dim3(64), 0, ctx->stream>>>(tl, gstart, ngroups, a, d_T, n, fs, k, (u64)al.hstep, prev,
-                                                                                                          d_out, cnt + 1);
-            HIPC(hipGetLastError());
-            BWTS_TRY(read_small(ctx, SM_COUNTERS, 4));
-            if (ctx->h_small[SM_COUNTERS + 1]) { *redo = WIDE_NEED_RANKS; return BWTS_OK; }     // a large group, or rotations equal for thousands of symbols
-        }
-        ctx->tm.rounds = a ? 2 : 1;
-        if (a && 1 < BWTS_MAX_ROUND_STATS) ctx->tm.round_active[1] = 0;
-        return BWTS_OK;
-    }
-
-    // ---- rounds over the tied list, part by part ----------------------------------------------------------------------------
-    u32 rounds = 1;
-    const int rb = bitlen_u64(suffix ? n : n - 1);               // (suffix ranks run from 1 to n)
-    u64 P = kn.part ? kn.part : Mb / 2;
-    if (P > Mb / 2) P = Mb / 2;
-    while (P > 64 && bitlen_u64(P / 2) + rb > 64) P >>= 1;       // (group ordinal, rank) must fit a 64-bit sort key
-    u64 *npos = bk[0] + (Mb - Mb / 2), *nhead = bk[1] + (Mb - Mb / 2);       // the buffers' second halves
-    u8 *tstate = bs_src;
-    u64 *d_wp = cnt + 26, *d_cnt = cnt + 0, *d_split = cnt + 1, *d_groups = cnt + 3;
-    std::vector<u64> h_cuts(WIDE_MAX_PARTS + 2);
-    auto cut_parts = [&](u64 count, u64 *nparts) -> int {
-        wide_cuts_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(tl, count, P, d_cuts, WIDE_MAX_PARTS);
+    r.base += m;
+    return BWTS_OK;
+}
+// every bucket is finished: the tied list as the device counted it
+static int wide_buckets_done(WideRun &r)
+{
+    if (r.base != r.n) return BWTS_E_INTERNAL;
+    BWTS_TRY(read_small(r.ctx, SM_COUNTERS + WC_TIED, 2));
+    r.a = wide_count(r.ctx, WC_TIED);
+    if (wide_count(r.ctx, WC_OVERFLOW) == 2) return BWTS_E_INTERNAL;                       // a sorted element carried a position outside the text
+    if (wide_count(r.ctx, WC_OVERFLOW) || r.a != r.tied_total) return BWTS_E_INTERNAL;     // (the list had room for every count read above)
+    if (!r.suffix) { r.ctx->tm.active_after_round0 = r.a; r.ctx->tm.round_active[0] = r.a; }
+    return BWTS_OK;
+}
+// WIDE_DIRECT: every tied group ordered by comparing its members' rotations (wide_direct_groups_kernel), or "needs ranks"
+static int wide_direct_groups(WideRun &r)
+{
+    bwts_ctx *ctx = r.ctx; const WideArena &A = r.A;
+    const u64 a = r.a;
+    if (a) {
+        if (a > WIDE_DIRECT_MAX) { r.redo = WIDE_NEED_RANKS; return BWTS_OK; }
+        SpanGuard g(ctx, BWTS_K_RERANK, a, 40 * a);
+        u32 *gstart = A.bv[0];                         // (a <= WIDE_DIRECT_MAX <= the buffers' size)
+        if (a > r.sh.Mb) return BWTS_E_INTERNAL;
+        HIPC(hipMemsetAsync(wide_counter(ctx, WC_KEPT), 0, WC_ROUND_WORDS * sizeof(u64), ctx->stream));
+        WideGroupIn gin{r.tl};
+        WideGroupOut gout{r.tl, gstart, a, wide_counter(ctx, WC_GROUPS)};
+        BWTS_TRY((device_scan<false, u32>(ctx, a, gin, gout, OpAdd(), 0u, A.scan_temp)));
+        BWTS_TRY(read_small(ctx, SM_COUNTERS + WC_KEPT, WC_ROUND_WORDS));
+        const u64 ngroups = wide_count(ctx, WC_GROUPS);
+        if (ngroups == 0 || ngroups > a) return BWTS_E_INTERNAL;
+        wide_direct_groups_kernel<<<dim3((unsigned)((ngroups + 63) / 64)), dim3(64), 0, ctx->stream>>>(r.tl, gstart, ngroups, a, r.d_T, r.n, r.fs, r.k, (u64)r.al.hstep,
+                                                                                                      r.prev, r.d_out, wide_counter(ctx, WC_UNRESOLVED));
         HIPC(hipGetLastError());
-        HIPC(hipMemcpyAsync(h_cuts.data(), d_cuts, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-        HIPC(hipStreamSynchronize(ctx->stream));
-        if (h_cuts[0] == ~0ull) return BWTS_E_RANGE;               // a group of more elements than a part holds
-        *nparts = h_cuts[0];
-        HIPC(hipMemcpyAsync(h_cuts.data() + 1, d_cuts + 1, (size_t)*nparts * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-        HIPC(hipStreamSynchronize(ctx->stream));
-        return BWTS_OK;
-    };
-    for (u64 h = (u64)al.hstep; a > 0; h <<= 1) {
-        rounds++;
+        BWTS_TRY(read_small(ctx, SM_COUNTERS + WC_KEPT, WC_ROUND_WORDS));
+        if (wide_count(ctx, WC_UNRESOLVED)) { r.redo = WIDE_NEED_RANKS; return BWTS_OK; }     // a large group, or rotations equal for thousands of symbols
+    }
+    ctx->tm.rounds = a ? 2 : 1;
+    if (a && 1 < BWTS_MAX_ROUND_STATS) ctx->tm.round_active[1] = 0;
+    return BWTS_OK;
+}
+// the first `count` list elements cut into parts of whole groups: *nparts ends in h_cuts[1 ..]
+static int wide_cut_parts(WideRun &r, u64 count, u64 *nparts)
+{
+    bwts_ctx *ctx = r.ctx; u64 *d_cuts = r.A.d_cuts;
+    r.h_cuts.resize(WIDE_MAX_PARTS + 2);
+    wide_cuts_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(r.tl, count, r.P, d_cuts, WIDE_MAX_PARTS);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(r.h_cuts.data(), d_cuts, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    if (r.h_cuts[0] == ~0ull) return BWTS_E_RANGE;               // a group of more elements than a part holds
+    *nparts = r.h_cuts[0];
+    HIPC(hipMemcpyAsync(r.h_cuts.data() + 1, d_cuts + 1, (size_t)*nparts * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    return BWTS_OK;
+}
+// one part [lo, lo + m) of a round at depth h: sort keys (group ordinal, rank of the h-th successor), sort, regroup, new ranks, survivors to
+// the front of the list.  SUFFIX picks the two functors' instantiations.
+template <bool SUFFIX> static int wide_round_part(WideRun &r, u64 lo, u64 m, u64 h)
+{
+    bwts_ctx *ctx = r.ctx; const WideArena &A = r.A;
+    u64 *npos = A.bk[0] + (r.sh.Mb - r.sh.Mb / 2), *nhead = A.bk[1] + (r.sh.Mb - r.sh.Mb / 2);       // the buffers' second halves
+    u8 *tstate = A.bs_src;
+    {
+        SpanGuard g(ctx, BWTS_K_KEYBUILD, m, 36 * m);
+        WideOrdIn oin{r.tl, lo};
+        WideOrdOut<SUFFIX> oout{r.tl, lo, A.rank64, r.n, h, SUFFIX ? nullptr : r.fs, SUFFIX ? 0 : r.k, r.rb, A.bk[0], A.bv[0], m, wide_counter(ctx, WC_GROUPS)};
+        BWTS_TRY((device_scan<false, u32>(ctx, m, oin, oout, OpAdd(), 0u, A.scan_temp)));
+    }
+    BWTS_TRY(read_small(ctx, SM_COUNTERS + WC_GROUPS, 1));
+    const u64 groups = wide_count(ctx, WC_GROUPS);
+    if (bitlen_u64(groups) + r.rb > 64) return BWTS_E_RANGE;
+    SortPlan tp = A.plan();
+    int tres = 0;
+    BWTS_TRY(radix_sort_pairs(ctx, tp, m, bitlen_u64(groups) + r.rb, &tres));
+    SpanGuard g(ctx, BWTS_K_RERANK, m, 48 * m);
+    DgRegroupIn rin{A.bk[tres], m, r.rb};
+    WideRegroupOut<!SUFFIX> rout{A.bk[tres], A.bv[tres], m, r.tl, lo, npos, nhead, tstate, r.prev, SUFFIX ? nullptr : r.d_out, wide_counter(ctx, WC_SPLIT)};
+    BWTS_TRY((device_scan<true, u64>(ctx, m, rin, rout, OpMax2(), (u64)0, A.scan_temp)));
+    WideKeepIn kin{tstate};
+    WideKeepOut kout{tstate, npos, nhead, A.rank64, r.tl, wide_counter(ctx, WC_WRITE), m, wide_counter(ctx, WC_KEPT)};
+    BWTS_TRY((device_scan<false, u32>(ctx, m, kin, kout, OpAdd(), 0u, A.scan_temp)));
+    wide_advance_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(wide_counter(ctx, WC_WRITE), wide_counter(ctx, WC_KEPT));
+    HIPC(hipGetLastError());
+    return BWTS_OK;
+}
+// rounds over the tied list, part by part, until no group splits
+static int wide_rounds(WideRun &r)
+{
+    bwts_ctx *ctx = r.ctx; const u64 Mb = r.sh.Mb;
+    r.rb = bitlen_u64(r.suffix ? r.n : r.n - 1);                   // (suffix ranks run from 1 to n)
+    r.P = r.sh.kn.part ? r.sh.kn.part : Mb / 2;
+    if (r.P > Mb / 2) r.P = Mb / 2;
+    while (r.P > 64 && bitlen_u64(r.P / 2) + r.rb > 64) r.P >>= 1;       // (group ordinal, rank) must fit a 64-bit sort key
+    for (u64 h = (u64)r.al.hstep; r.a > 0; h <<= 1) {
+        r.rounds++;
         u64 nparts = 0;
-        BWTS_TRY(cut_parts(a, &nparts));
-        HIPC(hipMemsetAsync(cnt, 0, 4 * sizeof(u64), ctx->stream));
-        HIPC(hipMemsetAsync(d_wp, 0, sizeof(u64), ctx->stream));
+        BWTS_TRY(wide_cut_parts(r, r.a, &nparts));
+        HIPC(hipMemsetAsync(wide_counter(ctx, WC_KEPT), 0, WC_ROUND_WORDS * sizeof(u64), ctx->stream));
+        HIPC(hipMemsetAsync(wide_counter(ctx, WC_WRITE), 0, sizeof(u64), ctx->stream));
         u64 lo = 0;
         for (u64 part = 0; part < nparts; part++) {
-            const u64 e = h_cuts[1 + part];
-            if (e <= lo || e > a || e - lo > P) return BWTS_E_INTERNAL;
-            const u64 m = e - lo;
-            {
-                SpanGuard g(ctx, BWTS_K_KEYBUILD, m, 36 * m);
-                WideOrdIn oin{tl, lo};
-                if (suffix) {
-                    WideOrdOut<true> oout{tl, lo, rank64, n, h, nullptr, 0, rb, bk[0], bv[0], m, d_groups};
-                    BWTS_TRY((device_scan<false, u32>(ctx, m, oin, oout, OpAdd(), 0u, scan_temp)));
-                } else {
-                    WideOrdOut<false> oout{tl, lo, rank64, n, h, fs, k, rb, bk[0], bv[0], m, d_groups};
-                    BWTS_TRY((device_scan<false, u32>(ctx, m, oin, oout, OpAdd(), 0u, scan_temp)));
-                }
-            }
-            BWTS_TRY(read_small(ctx, SM_COUNTERS + 3, 1));
-            const u64 groups = ctx->h_small[SM_COUNTERS + 3];
-            if (bitlen_u64(groups) + rb > 64) return BWTS_E_RANGE;
-            SortPlan tp = sort_plan(bk[0], bk[1], bv[0], bv[1], tile_hist, scan_temp);
-            int tres = 0;
-            BWTS_TRY(radix_sort_pairs(ctx, tp, m, bitlen_u64(groups) + rb, &tres));
-            {
-                SpanGuard g(ctx, BWTS_K_RERANK, m, 48 * m);
-                DgRegroupIn rin{bk[tres], m, rb};
-                if (suffix) {
-                    WideRegroupOut<false> rout{bk[tres], bv[tres], m, tl, lo, npos, nhead, tstate, prev, nullptr, d_split};
-                    BWTS_TRY((device_scan<true, u64>(ctx, m, rin, rout, OpMax2(), (u64)0, scan_temp)));
-                } else {
-                    WideRegroupOut<true> rout{bk[tres], bv[tres], m, tl, lo, npos, nhead, tstate, prev, d_out, d_split};
-                    BWTS_TRY((device_scan<true, u64>(ctx, m, rin, rout, OpMax2(), (u64)0, scan_temp)));
-                }
-                WideKeepIn kin{tstate};
-                WideKeepOut kout{tstate, npos, nhead, rank64, tl, d_wp, m, d_cnt};
-                BWTS_TRY((device_scan<false, u32>(ctx, m, kin, kout, OpAdd(), 0u, scan_temp)));
-                wide_advance_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(d_wp, d_cnt);
-                HIPC(hipGetLastError());
-            }
+            const u64 e = r.h_cuts[1 + part];
+            if (e <= lo || e > r.a || e - lo > r.P) return BWTS_E_INTERNAL;
+            BWTS_TRY(r.suffix ? wide_round_part<true>(r, lo, e - lo, h) : wide_round_part<false>(r, lo, e - lo, h));
             lo = e;
         }
-        if (lo != a) return BWTS_E_INTERNAL;
-        BWTS_TRY(read_small(ctx, SM_COUNTERS, 4));
-        BWTS_TRY(read_small(ctx, SM_COUNTERS + 26, 1));
-        const u64 a_new = ctx->h_small[SM_COUNTERS + 26], splits = ctx->h_small[SM_COUNTERS + 1];
-        if (a_new > a) return BWTS_E_INTERNAL;
-        a = a_new;
-        if (!suffix && rounds - 1 < BWTS_MAX_ROUND_STATS) ctx->tm.round_active[rounds - 1] = a;
-        if (a == 0) break;
+        if (lo != r.a) return BWTS_E_INTERNAL;
+        BWTS_TRY(read_small(ctx, SM_COUNTERS + WC_KEPT, WC_ROUND_WORDS));
+        BWTS_TRY(read_small(ctx, SM_COUNTERS + WC_WRITE, 1));
+        const u64 a_new = wide_count(ctx, WC_WRITE), splits = wide_count(ctx, WC_SPLIT);
+        if (a_new > r.a) return BWTS_E_INTERNAL;
+        r.a = a_new;
+        if (!r.suffix && r.rounds - 1 < BWTS_MAX_ROUND_STATS) ctx->tm.round_active[r.rounds - 1] = r.a;
+        if (r.a == 0) break;
         if (splits == 0) {
-            if (suffix) return BWTS_E_INTERNAL;             // suffixes are distinct: a round without a split cannot happen
+            if (r.suffix) return BWTS_E_INTERNAL;           // suffixes are distinct: a round without a split cannot happen
             break;                                          // no group split: equal infinite words
         }
-        if (rounds > 80) return BWTS_E_INTERNAL;
+        if (r.rounds > 80) return BWTS_E_INTERNAL;
     }
-    if (suffix) return wide_suffix_heads(ctx, n, rank64, pre_temp, rounds, fac);
-    if (a) {
+    return BWTS_OK;
+}
+// what the rounds left tied are equal infinite words: their bytes, in list order
+static int wide_emit_rest(WideRun &r)
+{
+    if (r.a) {
         u64 nparts = 0;
-        BWTS_TRY(cut_parts(a, &nparts));
+        BWTS_TRY(wide_cut_parts(r, r.a, &nparts));
         u64 lo = 0;
         for (u64 part = 0; part < nparts; part++) {
-            const u64 e = h_cuts[1 + part], m = e - lo;
-            SpanGuard g(ctx, BWTS_K_EMIT, m, 20 * m);
-            WideRestIn rin{tl, lo};
-            WideRestOut rout{tl, lo, prev, d_out};
-            BWTS_TRY((device_scan<true, u32>(ctx, m, rin, rout, OpMax(), 0u, scan_temp)));
+            const u64 e = r.h_cuts[1 + part], m = e - lo;
+            SpanGuard g(r.ctx, BWTS_K_EMIT, m, 20 * m);
+            WideRestIn rin{r.tl, lo};
+            WideRestOut rout{r.tl, lo, r.prev, r.d_out};
+            BWTS_TRY((device_scan<true, u32>(r.ctx, m, rin, rout, OpMax(), 0u, r.A.scan_temp)));
             lo = e;
         }
     }
-    ctx->tm.rounds = rounds;
+    r.ctx->tm.rounds = r.rounds;
     return BWTS_OK;
+}
+// the stages in order; one that sets r.redo ends the run, and the caller reads what it needs
+#define WIDE_STAGE(call) do { BWTS_TRY(call); if (r.redo != WIDE_DONE) return BWTS_OK; } while (0)
+static int forward_wide_run(bwts_ctx *ctx, const u8 *d_T, u64 n, u8 *d_out, WideMode mode, WideFactors *fac, int *redo)
+{
+    *redo = WIDE_DONE;
+    if (n > (1ull << 36)) return BWTS_E_RANGE;
+    WideRun r(ctx, d_T, n, d_out, mode, fac, *redo);
+    BWTS_TRY(wide_arena_place(ctx, r.sh, r.A));
+    BWTS_TRY(wide_alphabet(r));
+    BWTS_TRY(wide_first_keys(r));
+    WIDE_STAGE(wide_sample_ties(r));
+    WIDE_STAGE(wide_candidate_factors(r));
+    BWTS_TRY(wide_bucket_plan(r));
+    for (size_t b = 0; b + 1 < r.cut.size(); b++) WIDE_STAGE(wide_bucket(r, r.cut[b], r.cut[b + 1]));
+    BWTS_TRY(wide_buckets_done(r));
+    if (r.direct) return wide_direct_groups(r);
+    BWTS_TRY(wide_rounds(r));
+    return r.suffix ? wide_suffix_heads(ctx, n, r.A.rank64, r.A.pre_temp, r.rounds, fac) : wide_emit_rest(r);
 }
 
 static int forward_wide_impl(bwts_ctx *ctx, const u8 *d_T, u64 n, u8 *d_out)

@@ -48,6 +48,11 @@ int bwts_debug_inverse_arena(uint64_t n, int g, int mark, uint64_t out[2]);
 /* Likewise for the narrow forward (1 <= n <= 2^32): out[0] = bytes of the arena a call declares and the host path allocates ahead.
  * Returns 0, -1 on a bad argument. */
 int bwts_debug_forward_arena(uint64_t n, uint64_t out[1]);
+/* Likewise for one run of the forward beyond 2^32 (1 <= n <= 2^36; the forced runs of the tests take it below 2^32 too): out[0] =
+ * bytes of the arena a run in mode 0 direct (no rank array), 1 ranks, 2 suffix (the route to the Lyndon factors) declares, with
+ * segments of 2^seg_log2 positions (11..31) and buckets of bucket_cap elements (256..0xff000000); 0 for either means the engine's own
+ * choice for n.  Returns 0, -1 on a bad argument. */
+int bwts_debug_wide_forward_arena(uint64_t n, int mode, int seg_log2, uint64_t bucket_cap, uint64_t out[1]);
 /* What the most recent inverse call on the context did, one record of 16 words per attempt of its fallback chain, oldest first
  * (no device work: the engine keeps the records on the host as it goes).  Word 0 g: log2 of the splitter spacing; 1 mark: 0 index
  * log, 1 sentinel, 2 byte map, 3 moments; 2 outcome: 0 done, 1 retry with every element a splitter (node pool overflow, or the unit

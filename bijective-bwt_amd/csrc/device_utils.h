@@ -98,6 +98,46 @@ __device__ __forceinline__ u64 match_digit8(u32 digit, bool valid)
     return ((u64)phi << 32) | plo;
 }
 
+// One item's step of the stable ranking every radix and LF kernel uses: the lanes of a wave that hold digit d take consecutive
+// ranks, in lane order, from the wave's counter wave_hist[d] (u16 or u32), and the first lane of the run moves the counter past
+// them.  rank(r) receives the item's rank among the wave's elements with its digit BEFORE the first fence, so the caller's
+// store of it is not ordered behind the counter update.  The two wavefront fences are what makes the next item's read of the
+// counter see this item's update: the lanes run in lockstep, but without them the compiler may move the LDS read of item j+1
+// above the write of item j.  No atomics, no barrier.
+template <typename C, typename Rank>
+__device__ __forceinline__ void wave_rank_step(C *wave_hist, u32 d, bool valid, Rank rank)
+{
+    const u64 peers = match_digit8(d, valid);
+    const u32 before = (u32)__popcll(peers & lanemask_lt());
+    const u32 cnt = (u32)__popcll(peers);
+    const u32 prev = wave_hist[d];
+    rank(prev + before);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    if (valid && before == 0) wave_hist[d] = (C)(prev + cnt);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+// After the ranking: thread d < 256 turns column d of the waves' counters into each wave's start inside the digit (exclusive, in
+// wave order), and the column totals are scanned over the workgroup.  Returns the calling thread's exclusive base: for d < 256 the
+// number of the tile's elements with a smaller digit.  Contains block_scan_exclusive's two barriers; the caller stores the base
+// where it needs it and synchronises before anyone reads it.
+template <int NWAVES, typename C>
+__device__ __forceinline__ u32 digit_bases(C (*whist)[256], u32 *scan_sm)
+{
+    const int tid = threadIdx.x;
+    u32 run = 0;
+    if (tid < 256) {
+#pragma unroll
+        for (int ww = 0; ww < NWAVES; ww++) {
+            const u32 c = whist[ww][tid];
+            whist[ww][tid] = (C)run;
+            run += c;
+        }
+    }
+    u32 total;
+    return block_scan_exclusive<u32, OpAdd, NWAVES>(run, OpAdd(), 0u, scan_sm, &total);
+}
+
 // One wave's 64 consecutive digits into its LDS bins.  Sorted and repetitive input (every pass but the first of a sort over text or
 // over ranks with many equal values) puts runs of equal digits into neighbouring lanes, and same-address LDS atomics are served one
 // lane at a time: a pass over such keys ran at 2.4 TB/s where unsorted keys reach 5.6.  So the lanes of a run elect their first one, and

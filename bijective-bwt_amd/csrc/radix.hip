@@ -7,10 +7,12 @@
 //   column scan           exclusive scan of the [tile][digit] table in digit-major order
 //   scatter kernel        per-wave ballot ranking, LDS-staged tile sort, coalesced scatter
 // Two families of pass kernels:
-//   radix_hist_kernel / radix_scatter2_kernel                wide streams: u64 key, u32 value (+ u8 byte); 2*(8+4[+1]) bytes
-//                                                            per element and pass.  Later rounds, keys wider than 40 bits.
-//   radix_hist_packed_kernel / radix_scatter_packed_kernel   round 0 of the forward transform with keys of <= 40 bits:
-//                                                            packed streams, 2*(4+4+2) bytes (see "packed streams" below).
+//   radix_scatter2_kernel         wide streams: u64 key, u32 value (+ u8 byte); 2*(8+4[+1]) bytes per element and pass.
+//                                 Later rounds, keys wider than 40 bits.
+//   radix_scatter_packed_kernel   round 0 of the forward transform with keys of <= 40 bits: packed streams, 2*(4+4+2) bytes
+//                                 (see "packed streams" below).
+// Both are built from the same blocks: RxTile (the tile's place and its LDS), wave_rank_step and digit_bases (device_utils.h),
+// Pos16; radix_hist_kernel<T> counts the digits of whichever stream holds them.
 #include "internal.h"
 #include "device_utils.h"
 #include "scan_templ.h"
@@ -19,6 +21,9 @@
 
 #define RX_CHUNK   128          // tiles per column-scan chunk
 #define RX_XCDS    8
+// the one tile shape: 512 threads x 16 items, at least 4 waves per SIMD -- two 8192-element tiles resident per CU
+constexpr int RX_THREADS = 512, RX_ITEMS = 16, RX_MINW = 4, RX_WAVES = RX_THREADS / 64, RX_TILE = RX_THREADS * RX_ITEMS;
+constexpr u64 RX_HIST_TILE = 3072;      // radix_tile_hist_bytes() sizes the table for tiles of this many elements
 
 // Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share one), and each XCD has its own
 // non-coherent L2.  Tile t's run for digit d is followed in memory by tile t+1's run, so the two share a
@@ -32,13 +37,14 @@ __device__ __forceinline__ u64 rx_tile_of_block(u64 tiles)
 }
 static inline u64 rx_grid(u64 tiles) { return (tiles + RX_XCDS - 1) / RX_XCDS * RX_XCDS; }
 
+static inline u64 rx_tiles(u64 m) { return (m + RX_TILE - 1) / RX_TILE; }
 static inline u64 radix_chunks(u64 tiles) { return (tiles + RX_CHUNK - 1) / RX_CHUNK; }
 
 size_t radix_tile_hist_bytes(u64 m)
 {
-    // sized for tiles of 3072 elements, so one size serves every user: the radix passes' 8192-element tiles and the inverse's
+    // sized for tiles of RX_HIST_TILE elements, so one size serves every user: the radix passes' 8192-element tiles and the inverse's
     // 4096-element LF tiles (inverse.hip, wide_inverse.h).  Every arena reservation that holds the table depends on this value.
-    const u64 tiles = (m + 3071) / 3072 + 1;
+    const u64 tiles = (m + RX_HIST_TILE - 1) / RX_HIST_TILE + 1;
     return align_up((size_t)tiles * 256 * sizeof(u32), 256) +
            align_up((size_t)radix_chunks(tiles) * 256 * sizeof(u32), 256);
 }
@@ -61,23 +67,21 @@ int exclusive_sum_u32(bwts_ctx *ctx, u32 *data, u64 n, void *temp)
 // ------------------------------------------------------------------------------------
 // pass kernels
 // ------------------------------------------------------------------------------------
-template <int RX_THREADS, int RX_ITEMS>
-__global__ __launch_bounds__(RX_THREADS) void radix_hist_kernel(const u64 *__restrict__ keys, u64 m, int shift,
-                                                                 u32 *__restrict__ tile_hist)
+// per-tile digit counts of one stream: the u64 keys, or the packed passes' lo (u32) / c (u16) streams
+template <typename T>
+__global__ __launch_bounds__(RX_THREADS) void radix_hist_kernel(const T *__restrict__ src, u64 m, int shift, u32 *__restrict__ tile_hist)
 {
-    constexpr int RX_WAVES = RX_THREADS / 64;
-    constexpr int RX_TILE = RX_THREADS * RX_ITEMS;
     __shared__ u32 bins[RX_WAVES][256];
     const int tid = threadIdx.x, w = tid >> 6;
     for (int i = tid; i < RX_WAVES * 256; i += RX_THREADS) ((u32 *)bins)[i] = 0;
     __syncthreads();
     const u64 base = (u64)blockIdx.x * RX_TILE;
-    // all loads first (one register pair each), then the LDS atomics: keeps 16 loads in flight per lane
-    u64 k[RX_ITEMS];
+    // all loads first (one register (pair) each), then the LDS atomics: keeps 16 loads in flight per lane
+    T k[RX_ITEMS];
 #pragma unroll
     for (int j = 0; j < RX_ITEMS; j++) {
         const u64 i = base + (u64)j * RX_THREADS + tid;
-        k[j] = i < m ? keys[i] : 0ull;
+        k[j] = i < m ? src[i] : (T)0;
     }
 #pragma unroll
     for (int j = 0; j < RX_ITEMS; j++) {
@@ -120,72 +124,89 @@ __global__ __launch_bounds__(256) void radix_chunk_apply_kernel(u32 *__restrict_
     }
 }
 
-// The LDS tile holds the keys first and is then reused for the values (and, optionally, a third
-// one-byte stream), the per-wave digit counters are 16-bit and each slot's digit is kept in a byte table, so
-// the destination of a slot is re-derived instead of living in a register: 9 B of LDS per element instead
+// The scatter kernels' dynamic LDS: the six arrays, each at its byte offset from the dynamic base, and their total.  Kernels take
+// the pointers from here and launches the byte count, so the two cannot drift apart.  (The pointers are handed out one by one and
+// kept in locals: held in an object, or with the tile's place computed in a shared function, the same arithmetic cost some
+// instantiations a VGPR more or less.)  The LDS tile holds the keys first and is then
+// reused for the values (and, optionally, a third one-byte stream), the per-wave digit counters are 16-bit and each slot's digit is
+// kept in a byte table, so the destination of a slot is re-derived instead of living in a register: 9 B of LDS per element instead
 // of 12, two 8192-element tiles fit a CU and one tile's loads overlap the other's ranking.
-template <int RX_THREADS, int RX_ITEMS, int MINW, bool HAS_SYM, bool IDENT, bool KEYS_ONLY = false>
-__global__ __launch_bounds__(RX_THREADS, MINW) void radix_scatter2_kernel(const u64 *__restrict__ kin, const u32 *__restrict__ vin,
+template <int THREADS, int ITEMS>
+struct RxTile {
+    static constexpr int WAVES = THREADS / 64, TILE = THREADS * ITEMS;
+    static constexpr size_t off_dbase = (size_t)TILE * sizeof(u64), off_gbase = off_dbase + 256 * sizeof(u32),
+                            off_scan = off_gbase + 256 * sizeof(u32), off_whist = off_scan + 16 * sizeof(u32),
+                            off_sdig = off_whist + (size_t)WAVES * 256 * sizeof(u16), bytes = off_sdig + TILE;
+    // TILE slots: the first stream (keys; the packed passes' u32 digit stream), then the others (values; uint2 pairs)
+    static __device__ __forceinline__ u64 *stage(char *smem) { return (u64 *)smem; }
+    // 256 each: the digit's first slot in the tile; its run's global start minus that slot
+    static __device__ __forceinline__ u32 *dbase(char *smem) { return (u32 *)(smem + off_dbase); }
+    static __device__ __forceinline__ u32 *gbase(char *smem) { return (u32 *)(smem + off_gbase); }
+    // WAVES words (padded to 16) for block_scan_exclusive
+    static __device__ __forceinline__ u32 *scan_sm(char *smem) { return (u32 *)(smem + off_scan); }
+    // WAVES x 256: the waves' digit counters, then each wave's start inside the digit
+    static __device__ __forceinline__ u16 (*whist(char *smem))[256] { return (u16 (*)[256])(smem + off_whist); }
+    // TILE: digit of the element in slot s
+    static __device__ __forceinline__ u8 *sdig(char *smem) { return (u8 *)(smem + off_sdig); }
+};
+static_assert(RxTile<RX_THREADS, RX_ITEMS>::bytes == 79936, "9 B per element + 6208: two tiles per CU");
+
+// the items' 16-bit tile positions, two per register
+template <int ITEMS>
+struct Pos16 {
+    static_assert(ITEMS % 2 == 0, "positions are packed as 16-bit pairs");
+    u32 p[ITEMS / 2];
+    __device__ __forceinline__ u32 get(int j) const { return (j & 1) ? p[j >> 1] >> 16 : p[j >> 1] & 0xffffu; }
+    __device__ __forceinline__ void set(int j, u32 v)
+    {
+        if (j & 1) p[j >> 1] = (p[j >> 1] & 0xffffu) | (v << 16); else p[j >> 1] = (p[j >> 1] & 0xffff0000u) | v;
+    }
+    // the first write of a pair: the even item sets the register, the odd one joins it
+    __device__ __forceinline__ void init(int j, u32 v) { if (j & 1) p[j >> 1] |= v << 16; else p[j >> 1] = v; }
+};
+
+template <int TH, int IT, int MINW, bool HAS_SYM, bool IDENT, bool KEYS_ONLY = false>
+__global__ __launch_bounds__(TH, MINW) void radix_scatter2_kernel(const u64 *__restrict__ kin, const u32 *__restrict__ vin,
                                                                      u64 *__restrict__ kout, u32 *__restrict__ vout,
                                                                      const u32 *__restrict__ tile_off, u64 m, int shift,
                                                                      const u8 *__restrict__ sin, u8 *__restrict__ sout)
 {
-    constexpr int RX_WAVES = RX_THREADS / 64;
-    constexpr int RX_TILE = RX_THREADS * RX_ITEMS;
-    static_assert(RX_TILE <= 65536 && RX_ITEMS % 2 == 0, "positions are packed as 16-bit pairs");
+    using L = RxTile<TH, IT>;
+    constexpr int WAVES = L::WAVES, TILE = L::TILE;
+    static_assert(TILE <= 65536, "positions are 16-bit");
     extern __shared__ __attribute__((aligned(16))) char rx_smem[];
-    u64 *stage = (u64 *)rx_smem;                                   // RX_TILE keys, later values, later bytes
-    u32 *dbase = (u32 *)(stage + RX_TILE);                         // 256
-    u32 *gbase = dbase + 256;                                      // 256
-    u32 *scan_sm = gbase + 256;                                    // RX_WAVES (padded to 16)
-    u16 (*whist)[256] = (u16 (*)[256])(scan_sm + 16);              // RX_WAVES x 256
-    u8 *sdig = (u8 *)(whist + RX_WAVES);                           // RX_TILE: digit of the element in slot s
-
+    u64 *stage = L::stage(rx_smem);
+    u32 *dbase = L::dbase(rx_smem), *gbase = L::gbase(rx_smem), *scan_sm = L::scan_sm(rx_smem);
+    u16 (*whist)[256] = L::whist(rx_smem);
+    u8 *sdig = L::sdig(rx_smem);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const u64 tile = rx_tile_of_block((m + RX_TILE - 1) / RX_TILE);
-    const u64 tile_base = tile * RX_TILE;
+    const u64 tile = rx_tile_of_block((m + TILE - 1) / TILE);
+    const u64 tile_base = tile * TILE;
     if (tile_base >= m) return;                                   // padding block of the XCD-aligned grid
-    const u64 wave_base = tile_base + (u64)w * (64 * RX_ITEMS);
+    const u64 wave_base = tile_base + (u64)w * (64 * IT);
     const u64 remain = m - tile_base;
-    const u32 tile_count = remain < RX_TILE ? (u32)remain : (u32)RX_TILE;
+    const u32 tile_count = remain < TILE ? (u32)remain : (u32)TILE;
 
-    for (int i = tid; i < RX_WAVES * 128; i += RX_THREADS) ((u32 *)whist)[i] = 0;
+    for (int i = tid; i < WAVES * 128; i += TH) ((u32 *)whist)[i] = 0;
 
-    u64 key[RX_ITEMS];
-    u32 posp[RX_ITEMS / 2];                                        // two 16-bit tile positions per register
+    u64 key[IT];
+    Pos16<IT> pos;
 #pragma unroll
-    for (int j = 0; j < RX_ITEMS; j++) {
+    for (int j = 0; j < IT; j++) {
         const u64 i = wave_base + (u64)j * 64 + lane;
         key[j] = i < m ? kin[i] : ~0ull;
     }
     __syncthreads();
 
 #pragma unroll
-    for (int j = 0; j < RX_ITEMS; j++) {
+    for (int j = 0; j < IT; j++) {
         const bool valid = wave_base + (u64)j * 64 + lane < m;
         const u32 d = (u32)(key[j] >> shift) & 255u;
-        const u64 peers = match_digit8(d, valid);
-        const u32 before = (u32)__popcll(peers & lanemask_lt());
-        const u32 cnt = (u32)__popcll(peers);
-        const u32 prev = whist[w][d];
-        if (j & 1) posp[j >> 1] |= (prev + before) << 16; else posp[j >> 1] = prev + before;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (valid && before == 0) whist[w][d] = (u16)(prev + cnt);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        wave_rank_step(whist[w], d, valid, [&](u32 r) { pos.init(j, r); });
     }
     __syncthreads();
     {
-        u32 run = 0;
-        if (tid < 256) {
-#pragma unroll
-            for (int ww = 0; ww < RX_WAVES; ww++) {
-                const u32 c = whist[ww][tid];
-                whist[ww][tid] = (u16)run;
-                run += c;
-            }
-        }
-        u32 total;
-        const u32 exc = block_scan_exclusive<u32, OpAdd, RX_WAVES>(run, OpAdd(), 0u, scan_sm, &total);
+        const u32 exc = digit_bases<WAVES>(whist, scan_sm);
         if (tid < 256) {
             dbase[tid] = exc;
             gbase[tid] = tile_off[tile * 256 + tid] - exc;
@@ -196,12 +217,9 @@ __global__ __launch_bounds__(RX_THREADS, MINW) void radix_scatter2_kernel(const 
     // From here on every loop is split into "all LDS reads", then "all dependent work": inside one loop body the
     // compiler keeps a read, its s_waitcnt and the dependent LDS/global operation together, which serialises sixteen
     // LDS round trips per phase (seen in the ISA); batched, a phase costs about one.
-#define POS_GET(j) (((j) & 1) ? posp[(j) >> 1] >> 16 : posp[(j) >> 1] & 0xffffu)
-#define POS_SET(j, v) do { if ((j) & 1) posp[(j) >> 1] = (posp[(j) >> 1] & 0xffffu) | ((v) << 16); \
-                           else posp[(j) >> 1] = (posp[(j) >> 1] & 0xffff0000u) | (v); } while (0)
-    constexpr int HB = RX_ITEMS % 8 == 0 ? 8 : 4;                  // LDS reads batched per phase step
+    constexpr int HB = IT % 8 == 0 ? 8 : 4;                  // LDS reads batched per phase step
 #pragma unroll
-    for (int j0 = 0; j0 < RX_ITEMS; j0 += HB) {
+    for (int j0 = 0; j0 < IT; j0 += HB) {
         u32 add[HB];
 #pragma unroll
         for (int jj = 0; jj < HB; jj++) {
@@ -212,17 +230,17 @@ __global__ __launch_bounds__(RX_THREADS, MINW) void radix_scatter2_kernel(const 
         for (int jj = 0; jj < HB; jj++) {
             const int j = j0 + jj;
             const bool valid = wave_base + (u64)j * 64 + lane < m;
-            const u32 p = POS_GET(j) + add[jj];
-            POS_SET(j, p);
+            const u32 p = pos.get(j) + add[jj];
+            pos.set(j, p);
             if (valid) stage[p] = key[j];
         }
     }
     // the keys' registers are free: the value (and byte) loads overlap the key write-out
-    u32 val[KEYS_ONLY ? 1 : RX_ITEMS];
-    u32 sym[HAS_SYM ? RX_ITEMS : 1];
+    u32 val[KEYS_ONLY ? 1 : IT];
+    u32 sym[HAS_SYM ? IT : 1];
     if (!KEYS_ONLY) {
 #pragma unroll
-        for (int j = 0; j < RX_ITEMS; j++) {
+        for (int j = 0; j < IT; j++) {
             const u64 i = wave_base + (u64)j * 64 + lane;
             val[KEYS_ONLY ? 0 : j] = IDENT ? (u32)i : (i < m ? vin[i] : 0u);          // first pass of a sort over positions: value = index
         }
@@ -231,26 +249,26 @@ __global__ __launch_bounds__(RX_THREADS, MINW) void radix_scatter2_kernel(const 
         // one register per byte and no arithmetic on them here: the 16 loads issue back to back (packing them
         // on arrival made the compiler wait for memory after every two or three loads)
 #pragma unroll
-        for (int j = 0; j < RX_ITEMS; j++) {
+        for (int j = 0; j < IT; j++) {
             const u64 i = wave_base + (u64)j * 64 + lane;
             sym[j] = i < m ? (u32)sin[i] : 0u;
         }
     }
     __syncthreads();
 #pragma unroll
-    for (int j0 = 0; j0 < RX_ITEMS; j0 += HB) {
+    for (int j0 = 0; j0 < IT; j0 += HB) {
         u64 k[HB];
         u32 g[HB];
 #pragma unroll
         for (int jj = 0; jj < HB; jj++) {
-            const u32 s = (u32)(j0 + jj) * RX_THREADS + tid;
+            const u32 s = (u32)(j0 + jj) * TH + tid;
             k[jj] = s < tile_count ? stage[s] : 0ull;
         }
 #pragma unroll
         for (int jj = 0; jj < HB; jj++) g[jj] = gbase[(u32)(k[jj] >> shift) & 255u];
 #pragma unroll
         for (int jj = 0; jj < HB; jj++) {
-            const u32 s = (u32)(j0 + jj) * RX_THREADS + tid;
+            const u32 s = (u32)(j0 + jj) * TH + tid;
             if (s < tile_count) {
                 sdig[s] = (u8)((u32)(k[jj] >> shift) & 255u);
                 kout[g[jj] + s] = k[jj];
@@ -261,9 +279,9 @@ __global__ __launch_bounds__(RX_THREADS, MINW) void radix_scatter2_kernel(const 
     __syncthreads();
     // second trip through the same LDS: the value, with the travelling byte in the upper half of the slot
 #pragma unroll
-    for (int j = 0; j < RX_ITEMS; j++) {
+    for (int j = 0; j < IT; j++) {
         const bool valid = wave_base + (u64)j * 64 + lane < m;
-        const u32 p = POS_GET(j);
+        const u32 p = pos.get(j);
         if (valid) {
             if (HAS_SYM) stage[p] = (u64)val[KEYS_ONLY ? 0 : j] | ((u64)sym[j] << 32);
             else ((u32 *)stage)[p] = val[KEYS_ONLY ? 0 : j];
@@ -271,13 +289,13 @@ __global__ __launch_bounds__(RX_THREADS, MINW) void radix_scatter2_kernel(const 
     }
     __syncthreads();
 #pragma unroll
-    for (int j0 = 0; j0 < RX_ITEMS; j0 += HB) {
+    for (int j0 = 0; j0 < IT; j0 += HB) {
         u64 e[HAS_SYM ? HB : 1];
         u32 v32[HAS_SYM ? 1 : HB];
         u32 g[HB];
 #pragma unroll
         for (int jj = 0; jj < HB; jj++) {
-            const u32 s = (u32)(j0 + jj) * RX_THREADS + tid;
+            const u32 s = (u32)(j0 + jj) * TH + tid;
             const u32 sc = s < tile_count ? s : 0u;
             if (HAS_SYM) e[jj] = stage[sc]; else v32[jj] = ((u32 *)stage)[sc];
             g[jj] = sdig[sc];
@@ -286,7 +304,7 @@ __global__ __launch_bounds__(RX_THREADS, MINW) void radix_scatter2_kernel(const 
         for (int jj = 0; jj < HB; jj++) g[jj] = gbase[g[jj]];
 #pragma unroll
         for (int jj = 0; jj < HB; jj++) {
-            const u32 s = (u32)(j0 + jj) * RX_THREADS + tid;
+            const u32 s = (u32)(j0 + jj) * TH + tid;
             if (s < tile_count) {
                 const u32 dst = g[jj] + s;
                 if (HAS_SYM) { vout[dst] = (u32)e[jj]; sout[dst] = (u8)(e[jj] >> 32); }
@@ -294,8 +312,6 @@ __global__ __launch_bounds__(RX_THREADS, MINW) void radix_scatter2_kernel(const 
             }
         }
     }
-#undef POS_GET
-#undef POS_SET
 }
 
 // ------------------------------------------------------------------------------------
@@ -312,35 +328,6 @@ __global__ __launch_bounds__(RX_THREADS, MINW) void radix_scatter2_kernel(const 
 // for keys of more than 32 bits their bits 32..39 as one byte (5 bytes per key instead of a u64's 8; K0Split in forward.hip reads
 // them).  Ranking, LDS staging and XCD mapping are those of radix_scatter2_kernel; the LDS tile carries the digit's stream on its
 // first trip and the other two on its second.
-template <typename T>
-__global__ __launch_bounds__(512) void radix_hist_packed_kernel(const T *__restrict__ src, u64 m, int shift, u32 *__restrict__ tile_hist)
-{
-    constexpr int RX_THREADS = 512, RX_ITEMS = 16, RX_WAVES = 8, RX_TILE = 8192;
-    __shared__ u32 bins[RX_WAVES][256];
-    const int tid = threadIdx.x, w = tid >> 6;
-    for (int i = tid; i < RX_WAVES * 256; i += RX_THREADS) ((u32 *)bins)[i] = 0;
-    __syncthreads();
-    const u64 base = (u64)blockIdx.x * RX_TILE;
-    T k[RX_ITEMS];
-#pragma unroll
-    for (int j = 0; j < RX_ITEMS; j++) {
-        const u64 i = base + (u64)j * RX_THREADS + tid;
-        k[j] = i < m ? src[i] : (T)0;
-    }
-#pragma unroll
-    for (int j = 0; j < RX_ITEMS; j++) {
-        const u64 i = base + (u64)j * RX_THREADS + tid;
-        hist_add_runs(bins[w], (u32)(k[j] >> shift) & 255u, i < m);
-    }
-    __syncthreads();
-    if (tid < 256) {
-        u32 s = 0;
-#pragma unroll
-        for (int ww = 0; ww < RX_WAVES; ww++) s += bins[ww][tid];
-        tile_hist[(u64)blockIdx.x * 256 + tid] = s;
-    }
-}
-
 struct PackedIO {
     const u32 *lo_in; const void *c_in;                    // c: u16 if HI16 else u8
     const u32 *val_in;                                     // not read by the first pass (value = index)
@@ -351,17 +338,14 @@ struct PackedIO {
 };
 
 template <bool FIRST, bool LAST, bool HI16>
-__global__ __launch_bounds__(512, 4) void radix_scatter_packed_kernel(PackedIO io, const u32 *__restrict__ tile_off, u64 m, int shift)
+__global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_packed_kernel(PackedIO io, const u32 *__restrict__ tile_off, u64 m, int shift)
 {
-    constexpr int RX_THREADS = 512, RX_ITEMS = 16, RX_WAVES = 8, RX_TILE = 8192;
     extern __shared__ __attribute__((aligned(16))) char rx_smem[];
-    u64 *stage = (u64 *)rx_smem;                                   // RX_TILE x u32 (first trip), RX_TILE x uint2 (second)
-    u32 *dbase = (u32 *)(stage + RX_TILE);                         // 256
-    u32 *gbase = dbase + 256;                                      // 256
-    u32 *scan_sm = gbase + 256;                                    // RX_WAVES (padded to 16)
-    u16 (*whist)[256] = (u16 (*)[256])(scan_sm + 16);              // RX_WAVES x 256
-    u8 *sdig = (u8 *)(whist + RX_WAVES);                           // RX_TILE: digit of the element in slot s
-
+    using L = RxTile<RX_THREADS, RX_ITEMS>;
+    u64 *stage = L::stage(rx_smem);
+    u32 *dbase = L::dbase(rx_smem), *gbase = L::gbase(rx_smem), *scan_sm = L::scan_sm(rx_smem);
+    u16 (*whist)[256] = L::whist(rx_smem);
+    u8 *sdig = L::sdig(rx_smem);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const u64 tile = rx_tile_of_block((m + RX_TILE - 1) / RX_TILE);
     const u64 tile_base = tile * RX_TILE;
@@ -385,7 +369,7 @@ __global__ __launch_bounds__(512, 4) void radix_scatter_packed_kernel(PackedIO i
     // With 40-bit keys the fifth (= last) pass sorts by the byte that travels in c.
     constexpr bool DIG_C = HI16 && LAST;
     u32 dsrc[RX_ITEMS];
-    u32 posp[RX_ITEMS / 2];
+    Pos16<RX_ITEMS> pos;
     {
         const u16 *c16 = (const u16 *)io.c_in + i0;
         const u32 *lop = io.lo_in + i0;
@@ -402,28 +386,11 @@ __global__ __launch_bounds__(512, 4) void radix_scatter_packed_kernel(PackedIO i
     for (int j = 0; j < RX_ITEMS; j++) {
         const bool valid = PK_VALID(j);
         const u32 d = PK_DIGIT(j);
-        const u64 peers = match_digit8(d, valid);
-        const u32 before = (u32)__popcll(peers & lanemask_lt());
-        const u32 cnt = (u32)__popcll(peers);
-        const u32 prev = whist[w][d];
-        if (j & 1) posp[j >> 1] |= (prev + before) << 16; else posp[j >> 1] = prev + before;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (valid && before == 0) whist[w][d] = (u16)(prev + cnt);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        wave_rank_step(whist[w], d, valid, [&](u32 r) { pos.init(j, r); });
     }
     __syncthreads();
     {
-        u32 run = 0;
-        if (tid < 256) {
-#pragma unroll
-            for (int ww = 0; ww < RX_WAVES; ww++) {
-                const u32 cc = whist[ww][tid];
-                whist[ww][tid] = (u16)run;
-                run += cc;
-            }
-        }
-        u32 total;
-        const u32 exc = block_scan_exclusive<u32, OpAdd, RX_WAVES>(run, OpAdd(), 0u, scan_sm, &total);
+        const u32 exc = digit_bases<RX_WAVES>(whist, scan_sm);
         if (tid < 256) {
             dbase[tid] = exc;
             gbase[tid] = tile_off[tile * 256 + tid] - exc;
@@ -431,9 +398,6 @@ __global__ __launch_bounds__(512, 4) void radix_scatter_packed_kernel(PackedIO i
     }
     __syncthreads();
 
-#define POS_GET(j) (((j) & 1) ? posp[(j) >> 1] >> 16 : posp[(j) >> 1] & 0xffffu)
-#define POS_SET(j, v) do { if ((j) & 1) posp[(j) >> 1] = (posp[(j) >> 1] & 0xffffu) | ((v) << 16); \
-                           else posp[(j) >> 1] = (posp[(j) >> 1] & 0xffff0000u) | (v); } while (0)
     constexpr int HB = 8;
     u32 *stage32 = (u32 *)stage;
     // first trip: the digit's stream into its slot, the slot's digit into the byte table
@@ -449,8 +413,8 @@ __global__ __launch_bounds__(512, 4) void radix_scatter_packed_kernel(PackedIO i
         for (int jj = 0; jj < HB; jj++) {
             const int j = j0 + jj;
             const bool valid = PK_VALID(j);
-            const u32 p = POS_GET(j) + add[jj];
-            POS_SET(j, p);
+            const u32 p = pos.get(j) + add[jj];
+            pos.set(j, p);
             if (valid) { stage32[p] = dsrc[j]; sdig[p] = (u8)PK_DIGIT(j); }
         }
     }
@@ -507,7 +471,7 @@ __global__ __launch_bounds__(512, 4) void radix_scatter_packed_kernel(PackedIO i
         const bool valid = PK_VALID(j);
         const u32 second = sb[j];
         const u32 firstw = FIRST ? idx_base + (u32)j * 64u : sa[j];
-        if (valid) ((uint2 *)stage)[POS_GET(j)] = make_uint2(firstw, second);
+        if (valid) ((uint2 *)stage)[pos.get(j)] = make_uint2(firstw, second);
     }
     __syncthreads();
 #pragma unroll
@@ -541,19 +505,47 @@ __global__ __launch_bounds__(512, 4) void radix_scatter_packed_kernel(PackedIO i
             }
         }
     }
-#undef POS_GET
-#undef POS_SET
 #undef PK_DIGIT
 #undef PK_VALID
 }
 
-#define RX_PACKED_LDS ((size_t)8192 * 9 + 2048 + 64 + (size_t)8 * 512)
-template <bool FIRST, bool LAST, bool HI16>
-static int launch_scatter_packed(bwts_ctx *ctx, u64 tiles, const PackedIO &io, const u32 *tile_off, u64 m, int shift)
+// ------------------------------------------------------------------------------------
+// host side of a pass
+// ------------------------------------------------------------------------------------
+static bool knob_off(const bwts_ctx *ctx, const char *name) { const char *e = bwts_knob(ctx, name); return e && atoi(e) == 0; }
+
+// This pass's offsets: the per-tile digit counts of `src` (unless tile_hist holds them already), then their column scan.
+template <typename T>
+static int radix_pass_offsets(bwts_ctx *ctx, const T *src, u64 m, int shift, u32 *tile_hist, bool counted, void *scan_temp)
 {
-    constexpr size_t lds = RX_PACKED_LDS;
-    BWTS_TRY(ensure_dyn_lds(ctx, (const void *)radix_scatter_packed_kernel<FIRST, LAST, HI16>, lds));
-    radix_scatter_packed_kernel<FIRST, LAST, HI16><<<dim3((unsigned)rx_grid(tiles)), dim3(512), lds, ctx->stream>>>(io, tile_off, m, shift);
+    const u64 tiles = rx_tiles(m);
+    if (!counted) {
+        SpanGuard g(ctx, BWTS_K_RADIX_HIST, m, sizeof(T) * m);
+        radix_hist_kernel<T><<<dim3((unsigned)tiles), dim3(RX_THREADS), 0, ctx->stream>>>(src, m, shift, tile_hist);
+    }
+    SpanGuard g(ctx, BWTS_K_RADIX_SCAN, tiles * 256, tiles * 256 * 12);
+    STAGE("radix pass: histogram");
+    BWTS_TRY(radix_column_scan(ctx, tile_hist, tiles, scan_temp));
+    STAGE("radix pass: column scan");
+    return BWTS_OK;
+}
+
+// One scatter launch of either family; `kernel` is the instantiation its caller picked.  roofline: the launch is timed a second time
+// under its own class -- the roofline kernel (one template variant, n-sized launches).
+template <typename... P, typename... A>
+static int launch_scatter(bwts_ctx *ctx, void (*kernel)(P...), u64 m, u64 alg_bytes, bool roofline, A... args)
+{
+    constexpr size_t lds = RxTile<RX_THREADS, RX_ITEMS>::bytes;
+    {
+        SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, alg_bytes);
+        const int gm = roofline ? span_begin(ctx, BWTS_K_RADIX_SCATTER_MAIN, m, alg_bytes) : -1;
+        const int rc = ensure_dyn_lds(ctx, (const void *)kernel, lds);
+        if (rc == BWTS_OK) kernel<<<dim3((unsigned)rx_grid(rx_tiles(m))), dim3(RX_THREADS), lds, ctx->stream>>>(args...);
+        span_end(ctx, gm);
+        BWTS_TRY(rc);
+    }
+    HIPC(hipGetLastError());
+    STAGE("radix pass: scatter");
     return BWTS_OK;
 }
 
@@ -561,7 +553,6 @@ static int launch_scatter_packed(bwts_ctx *ctx, u64 tiles, const PackedIO &io, c
 template <bool HI16>
 static int radix_sort_packed(bwts_ctx *ctx, const SortPlan &plan, u64 m, int passes, int *result_buf)
 {
-    const u64 tiles = (m + 8191) / 8192;        // 512 threads x 16 items, two tiles resident per CU
     const size_t lo_bytes = align_up((size_t)m * 4, 256);
     const u64 pass_bytes = HI16 ? 20 : 18;
     int cur = 0;
@@ -575,31 +566,14 @@ static int radix_sort_packed(bwts_ctx *ctx, const SortPlan &plan, u64 m, int pas
         io.hi_out = (u8 *)dst + lo_bytes; io.sym_out = plan.sym_final;
         // the first pass's table may have been counted already (the key builder's)
         u32 *tile_hist = first && plan.first_hist ? plan.first_hist : plan.tile_hist;
-        if (tile_hist == plan.tile_hist) {
-            SpanGuard g(ctx, BWTS_K_RADIX_HIST, m, ((HI16 && shift >= 32) ? 2 : 4) * m);
-            if (HI16 && shift >= 32) radix_hist_packed_kernel<u16><<<dim3((unsigned)tiles), dim3(512), 0, ctx->stream>>>((const u16 *)io.c_in, m, 0, tile_hist);
-            else radix_hist_packed_kernel<u32><<<dim3((unsigned)tiles), dim3(512), 0, ctx->stream>>>(io.lo_in, m, shift, tile_hist);
-        }
-        {
-            SpanGuard g(ctx, BWTS_K_RADIX_SCAN, tiles * 256, tiles * 256 * 12);
-            STAGE("packed pass: histogram");
-            BWTS_TRY(radix_column_scan(ctx, tile_hist, tiles, plan.scan_temp));
-            STAGE("packed pass: column scan");
-        }
-        if (first) {
-            SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, (pass_bytes / 2 - 4 + pass_bytes / 2) * m);
-            BWTS_TRY((launch_scatter_packed<true, false, HI16>(ctx, tiles, io, tile_hist, m, shift)));
-        } else if (last) {
-            SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, (pass_bytes / 2 + (HI16 ? 10 : 9)) * m);
-            BWTS_TRY((launch_scatter_packed<false, true, HI16>(ctx, tiles, io, tile_hist, m, shift)));
-        } else {
-            // timed a second time under its own class: the roofline kernel (one template variant, n-sized launches)
-            SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, pass_bytes * m);
-            SpanGuard gm(ctx, BWTS_K_RADIX_SCATTER_MAIN, m, pass_bytes * m);
-            BWTS_TRY((launch_scatter_packed<false, false, HI16>(ctx, tiles, io, tile_hist, m, shift)));
-        }
-        HIPC(hipGetLastError());
-        STAGE("packed pass: scatter");
+        const bool counted = tile_hist != plan.tile_hist;
+        if (HI16 && shift >= 32) BWTS_TRY(radix_pass_offsets(ctx, (const u16 *)io.c_in, m, 0, tile_hist, counted, plan.scan_temp));
+        else BWTS_TRY(radix_pass_offsets(ctx, io.lo_in, m, shift, tile_hist, counted, plan.scan_temp));
+        // the first pass reads no values; the last writes the keys split and the byte alone
+        const u64 bytes = first ? pass_bytes - 4 : last ? pass_bytes / 2 + (HI16 ? 10 : 9) : pass_bytes;
+        const auto kernel = first ? radix_scatter_packed_kernel<true, false, HI16>
+                          : last  ? radix_scatter_packed_kernel<false, true, HI16> : radix_scatter_packed_kernel<false, false, HI16>;
+        BWTS_TRY(launch_scatter(ctx, kernel, m, bytes * m, !first && !last, io, tile_hist, m, shift));
         cur ^= 1;
     }
     *result_buf = cur;
@@ -646,28 +620,11 @@ __global__ __launch_bounds__(RS_THREADS) void radix_sort_small_kernel(const u64 
         for (int j = 0; j < RS_ITEMS; j++) {
             const bool valid = wbase + (u32)j * 64 + lane < m;
             const u32 d = (u32)(key[j] >> shift) & 255u;
-            const u64 peers = match_digit8(d, valid);
-            const u32 before = (u32)__popcll(peers & lanemask_lt());
-            const u32 cnt = (u32)__popcll(peers);
-            const u32 prev = whist[w][d];
-            pos[j] = prev + before;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            if (valid && before == 0) whist[w][d] = (u16)(prev + cnt);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            wave_rank_step(whist[w], d, valid, [&](u32 r) { pos[j] = r; });
         }
         __syncthreads();
         {
-            u32 run = 0;
-            if (tid < 256) {
-#pragma unroll
-                for (int ww = 0; ww < RS_WAVES; ww++) {
-                    const u32 c = whist[ww][tid];
-                    whist[ww][tid] = (u16)run;
-                    run += c;
-                }
-            }
-            u32 total;
-            const u32 exc = block_scan_exclusive<u32, OpAdd, RS_WAVES>(run, OpAdd(), 0u, scan_sm, &total);
+            const u32 exc = digit_bases<RS_WAVES>(whist, scan_sm);
             if (tid < 256) dbase[tid] = exc;
         }
         __syncthreads();
@@ -688,24 +645,8 @@ __global__ __launch_bounds__(RS_THREADS) void radix_sort_small_kernel(const u64 
 }
 
 // ------------------------------------------------------------------------------------
-// host driver
+// column scan and the sort drivers
 // ------------------------------------------------------------------------------------
-template <int TH, int IT>
-static void launch_hist_t(bwts_ctx *ctx, u64 tiles, const u64 *keys, u64 m, int shift, u32 *tile_hist)
-{
-    radix_hist_kernel<TH, IT><<<dim3((unsigned)tiles), dim3(TH), 0, ctx->stream>>>(keys, m, shift, tile_hist);
-}
-
-template <int TH, int IT, int MINW, bool HAS_SYM = false, bool IDENT = false>
-static int launch_scatter2_t(bwts_ctx *ctx, u64 tiles, const u64 *kin, const u32 *vin, u64 *kout, u32 *vout, const u32 *tile_off,
-                             u64 m, int shift, const u8 *sin = nullptr, u8 *sout = nullptr)
-{
-    constexpr size_t lds = (size_t)TH * IT * 9 + 2048 + 64 + (size_t)(TH / 64) * 512;
-    BWTS_TRY(ensure_dyn_lds(ctx, (const void *)radix_scatter2_kernel<TH, IT, MINW, HAS_SYM, IDENT>, lds));
-    radix_scatter2_kernel<TH, IT, MINW, HAS_SYM, IDENT><<<dim3((unsigned)rx_grid(tiles)), dim3(TH), lds, ctx->stream>>>(kin, vin, kout, vout, tile_off, m, shift, sin, sout);
-    return BWTS_OK;
-}
-
 // [tile][digit] counts -> global exclusive offsets in digit-major order, in place.
 // tile_hist must be followed by the chunk table (radix_tile_hist_bytes()).
 // The three steps above in one launch, for tables of at most RX_FUSED_CHUNKS chunks (sorts of up to 2^28 elements): one workgroup
@@ -786,7 +727,7 @@ int radix_column_scan(bwts_ctx *ctx, u32 *tile_hist, u64 tiles, void *scan_temp)
 {
     const u64 chunks = radix_chunks(tiles);
     u32 *chunk_sum = (u32 *)((char *)tile_hist + align_up((size_t)tiles * 256 * sizeof(u32), 256));
-    const bool fused_ok = [ctx] { const char *e = bwts_knob(ctx, "BWTS_RX_FUSED_SCAN"); return !(e && atoi(e) == 0); }();
+    const bool fused_ok = !knob_off(ctx, "BWTS_RX_FUSED_SCAN");
     if (ctx->fused_scan_cap == 0) {
         // every workgroup of the fused kernel waits for all the others: it may only be used with as many workgroups as the device
         // is certain to hold at once (a whole MI355X: 256 CUs x 8; a partition of it, or a CU-masked queue, fewer)
@@ -813,22 +754,11 @@ int radix_column_scan(bwts_ctx *ctx, u32 *tile_hist, u64 tiles, void *scan_temp)
 int radix_sort_keys(bwts_ctx *ctx, u64 *keys[2], u32 *tile_hist, void *scan_temp, u64 m, int lo_bit, int bits, int *result_buf)
 {
     int cur = 0;
-    const u64 tiles = (m + 8191) / 8192;
-    constexpr size_t lds = (size_t)512 * 16 * 9 + 2048 + 64 + (size_t)8 * 512;
-    BWTS_TRY(ensure_dyn_lds(ctx, (const void *)radix_scatter2_kernel<512, 16, 4, false, false, true>, lds));
     for (int shift = lo_bit; shift < lo_bit + bits; shift += 8) {
-        {
-            SpanGuard g(ctx, BWTS_K_RADIX_HIST, m, 8 * m);
-            launch_hist_t<512, 16>(ctx, tiles, keys[cur], m, shift, tile_hist);
-        }
-        {
-            SpanGuard g(ctx, BWTS_K_RADIX_SCAN, tiles * 256, tiles * 256 * 12);
-            BWTS_TRY(radix_column_scan(ctx, tile_hist, tiles, scan_temp));
-        }
-        SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, 16 * m);
-        radix_scatter2_kernel<512, 16, 4, false, false, true><<<dim3((unsigned)rx_grid(tiles)), dim3(512), lds, ctx->stream>>>(
-            keys[cur], nullptr, keys[cur ^ 1], nullptr, tile_hist, m, shift, nullptr, nullptr);
-        HIPC(hipGetLastError());
+        BWTS_TRY(radix_pass_offsets(ctx, keys[cur], m, shift, tile_hist, false, scan_temp));
+        BWTS_TRY(launch_scatter(ctx, radix_scatter2_kernel<RX_THREADS, RX_ITEMS, RX_MINW, false, false, true>, m, 16 * m, false,
+                                keys[cur], nullptr, keys[cur ^ 1], nullptr, tile_hist, m, shift,
+                                nullptr, nullptr));
         cur ^= 1;
     }
     *result_buf = cur;
@@ -837,9 +767,8 @@ int radix_sort_keys(bwts_ctx *ctx, u64 *keys[2], u32 *tile_hist, void *scan_temp
 
 bool radix_packed_applicable(const bwts_ctx *ctx, u64 m, int key_bits)
 {
-    const bool packed_ok = [ctx] { const char *e = bwts_knob(ctx, "BWTS_RX_PACK"); return !(e && atoi(e) == 0); }();
     const int passes = ((key_bits < 1 ? 1 : key_bits) + 7) / 8;
-    return packed_ok && passes >= 3 && passes <= 5 && m >= 65536;
+    return !knob_off(ctx, "BWTS_RX_PACK") && passes >= 3 && passes <= 5 && m >= 65536;
 }
 
 int radix_sort_pairs(bwts_ctx *ctx, const SortPlan &plan, u64 m, int key_bits, int *result_buf)
@@ -849,11 +778,8 @@ int radix_sort_pairs(bwts_ctx *ctx, const SortPlan &plan, u64 m, int key_bits, i
     if (key_bits < 1) key_bits = 1;
     if (key_bits > 64) key_bits = 64;
     const int passes = (key_bits + 7) / 8;
-    const u64 tiles = (m + 8191) / 8192;        // 512 threads x 16 items, two tiles resident per CU
-    u32 *tile_hist = plan.tile_hist;
 
-    const bool small_ok = [ctx] { const char *e = bwts_knob(ctx, "BWTS_RX_SMALL"); return !(e && atoi(e) == 0); }();
-    if (small_ok && m <= RS_MAX && !plan.sym_src && !plan.vals_identity && !plan.keys_split) {
+    if (!knob_off(ctx, "BWTS_RX_SMALL") && m <= RS_MAX && !plan.sym_src && !plan.vals_identity && !plan.keys_split) {
         SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, 24 * m);
         radix_sort_small_kernel<<<dim3(1), dim3(RS_THREADS), 0, ctx->stream>>>(plan.keys[0], plan.vals[0], plan.keys[1], plan.vals[1], (u32)m, passes);
         HIPC(hipGetLastError());
@@ -868,38 +794,18 @@ int radix_sort_pairs(bwts_ctx *ctx, const SortPlan &plan, u64 m, int key_bits, i
 
     for (int p = 0; p < passes; p++) {
         const int shift = 8 * p;
-        {
-            SpanGuard g(ctx, BWTS_K_RADIX_HIST, m, 8 * m);
-            launch_hist_t<512, 16>(ctx, tiles, plan.keys[cur], m, shift, tile_hist);
-        }
-        {
-            SpanGuard g(ctx, BWTS_K_RADIX_SCAN, tiles * 256, tiles * 256 * 12);
-            BWTS_TRY(radix_column_scan(ctx, tile_hist, tiles, plan.scan_temp));
-        }
-        const bool ident = plan.vals_identity && p == 0;
-        if (plan.sym_src) {
-            const u8 *sin = p == 0 ? plan.sym_src : plan.sym_buf[(p - 1) & 1];
-            u8 *sout = p == passes - 1 ? plan.sym_final : plan.sym_buf[p & 1];
-            SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, (ident ? 22 : 26) * m);
-            if (ident)
-                BWTS_TRY((launch_scatter2_t<512, 16, 4, true, true>(ctx, tiles, plan.keys[cur], plan.vals[cur], plan.keys[cur ^ 1],
-                                                                     plan.vals[cur ^ 1], tile_hist, m, shift, sin, sout)));
-            else {
-                // timed a second time under its own class: the roofline kernel (one template variant, n-sized launches)
-                SpanGuard gm(ctx, BWTS_K_RADIX_SCATTER_MAIN, m, 26 * m);
-                BWTS_TRY((launch_scatter2_t<512, 16, 4, true, false>(ctx, tiles, plan.keys[cur], plan.vals[cur], plan.keys[cur ^ 1],
-                                                                      plan.vals[cur ^ 1], tile_hist, m, shift, sin, sout)));
-            }
-        } else if (ident) {
-            SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, 20 * m);
-            BWTS_TRY((launch_scatter2_t<512, 16, 4, false, true>(ctx, tiles, plan.keys[cur], plan.vals[cur], plan.keys[cur ^ 1], plan.vals[cur ^ 1],
-                                                                  tile_hist, m, shift)));
-        } else {
-            SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, 24 * m);
-            BWTS_TRY((launch_scatter2_t<512, 16, 4>(ctx, tiles, plan.keys[cur], plan.vals[cur], plan.keys[cur ^ 1], plan.vals[cur ^ 1],
-                                                     tile_hist, m, shift)));
-        }
-        HIPC(hipGetLastError());
+        BWTS_TRY(radix_pass_offsets(ctx, plan.keys[cur], m, shift, plan.tile_hist, false, plan.scan_temp));
+        // the first pass of a sort over positions reads no values (value = index); the byte stream, if any, rides along
+        const bool ident = plan.vals_identity && p == 0, has_sym = plan.sym_src != nullptr;
+        const u8 *sin = !has_sym ? nullptr : p == 0 ? plan.sym_src : plan.sym_buf[(p - 1) & 1];
+        u8 *sout = !has_sym ? nullptr : p == passes - 1 ? plan.sym_final : plan.sym_buf[p & 1];
+        const auto kernel = has_sym ? (ident ? radix_scatter2_kernel<RX_THREADS, RX_ITEMS, RX_MINW, true, true>
+                                             : radix_scatter2_kernel<RX_THREADS, RX_ITEMS, RX_MINW, true, false>)
+                                    : (ident ? radix_scatter2_kernel<RX_THREADS, RX_ITEMS, RX_MINW, false, true>
+                                             : radix_scatter2_kernel<RX_THREADS, RX_ITEMS, RX_MINW, false, false>);
+        BWTS_TRY(launch_scatter(ctx, kernel, m, ((has_sym ? 26 : 24) - (ident ? 4 : 0)) * m, has_sym && !ident,
+                                plan.keys[cur], plan.vals[cur], plan.keys[cur ^ 1], plan.vals[cur ^ 1],
+                                plan.tile_hist, m, shift, sin, sout));
         cur ^= 1;
     }
     *result_buf = cur;

@@ -64,14 +64,7 @@ __device__ __forceinline__ void lf_rank_wide_body(const u8 *__restrict__ B, u64 
 #pragma unroll
     for (int j = 0; j < LF_ITEMS; j++) {
         const bool valid = wave_base + (u64)j * 64 + lane < count;
-        const u64 peers = match_digit8(sym[j], valid);
-        const u32 before = (u32)__popcll(peers & lanemask_lt());
-        const u32 cnt = (u32)__popcll(peers);
-        const u32 prev = whist[w][sym[j]];
-        rnk[j] = prev + before;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (valid && before == 0) whist[w][sym[j]] = prev + cnt;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        wave_rank_step(whist[w], sym[j], valid, [&](u32 r) { rnk[j] = r; });
     }
     __syncthreads();
     {

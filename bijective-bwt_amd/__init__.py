@@ -50,13 +50,19 @@ EC_EXPORTS = [
     "bwts_ec_encode", "bwts_ec_decode", "bwts_ec_encode_segments_device", "bwts_ec_decode_segments_device",
 ]
 E_FORMAT, E_SPACE = -8, -9
+# ... include/bwts_pack.h (the chain as one call: a checksummed frame) ...
+PACK_EXPORTS = [
+    "bwts_crc32_device", "bwts_crc32_segments_device", "bwts_pack_bound", "bwts_unpack_size",
+    "bwts_pack_device", "bwts_unpack_device", "bwts_pack", "bwts_unpack",
+]
+E_CHECKSUM = -10
 # ... and include/bwts_test.h (harness and unit-test hooks)
 TEST_EXPORTS = [
     "bwts_generate_device", "bwts_device_alloc", "bwts_device_free", "bwts_copy_to_device", "bwts_copy_to_host",
     "bwts_device_equal", "bwts_debug_sort_pairs", "bwts_debug_suffix_array", "bwts_debug_lyndon",
     "bwts_debug_chunk_plan", "bwts_debug_inverse_arena", "bwts_debug_forward_arena", "bwts_debug_wide_forward_arena", "bwts_debug_inverse_report",
     "bwts_debug_forward_report", "bwts_debug_segments_plan", "bwts_debug_segments_report",
-    "bwts_debug_mtf_plan", "bwts_debug_last_spans", "bwts_debug_ec_plan",
+    "bwts_debug_mtf_plan", "bwts_debug_last_spans", "bwts_debug_ec_plan", "bwts_debug_crc_plan",
 ]
 # bwts_debug_inverse_report: the words of one attempt's record, and what marks, outcomes and forms are called
 INV_REPORT_FIELDS = ["g", "mark", "outcome", "s", "virtual", "node_cap", "nu", "nu2", "ucap_first", "second_collect",
@@ -171,6 +177,16 @@ def lib():
         L.bwts_ec_encode_segments_device.argtypes = [vp, vp, vp, u64, vp, u64, vp]
         L.bwts_ec_decode_segments_device.argtypes = [vp, vp, vp, vp, u64, vp]
         L.bwts_debug_ec_plan.argtypes = [u64, ctypes.POINTER(u64)]
+        L.bwts_crc32_device.argtypes = [vp, vp, u64, ctypes.POINTER(ctypes.c_uint32)]
+        L.bwts_crc32_segments_device.argtypes = [vp, vp, vp, u64, vp]
+        L.bwts_pack_bound.argtypes = [u64, u64]
+        L.bwts_pack_bound.restype = u64
+        L.bwts_unpack_size.argtypes = [vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+        for name in ("bwts_pack_device", "bwts_pack"):
+            getattr(L, name).argtypes = [vp, vp, u64, u64, vp, u64, ctypes.POINTER(u64)]
+        for name in ("bwts_unpack_device", "bwts_unpack"):
+            getattr(L, name).argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
+        L.bwts_debug_crc_plan.argtypes = [u64, ctypes.POINTER(u64)]
         for name in ("bwts_forward_sink", "bwts_inverse_sink"):
             getattr(L, name).argtypes = [vp, vp, u64, SINK_FN, vp]
         L.bwts_generate_device.argtypes = [vp, i32, u64, u64, vp]
@@ -442,6 +458,51 @@ class Context:
             raise BwtsError(-1, "one stream size per segment")
         self._check(lib().bwts_ec_decode_segments_device(self._h, _ptr(d_in), sb.ctypes.data, ls.ctypes.data, ls.size, _ptr(d_out)))
 
+    # -- the chain as one call: a checksummed frame (include/bwts_pack.h) -----------------------------
+    def crc32_device(self, d_in, n):
+        """bwts_crc32_device: zlib's CRC-32 of n device bytes."""
+        got = ctypes.c_uint32(0)
+        self._check(lib().bwts_crc32_device(self._h, _ptr(d_in), int(n), ctypes.byref(got)))
+        return int(got.value)
+
+    def crc32_segments_device(self, d_in, lengths):
+        """bwts_crc32_segments_device: one CRC-32 per segment (uint32 array)."""
+        ls = np.ascontiguousarray(lengths, dtype=np.uint64)
+        crcs = np.zeros(ls.size, dtype=np.uint32)
+        self._check(lib().bwts_crc32_segments_device(self._h, _ptr(d_in), ls.ctypes.data, ls.size, crcs.ctypes.data))
+        return crcs
+
+    def pack(self, data, block_bytes=0, out_cap=None):
+        """bwts_pack: the frame of a byte string (host buffers); out_cap defaults to the bound."""
+        a = _u8(data)
+        if a.size == 0:
+            raise BwtsError(-1, "empty input")
+        out = np.empty(pack_bound(a.size, block_bytes) if out_cap is None else int(out_cap), dtype=np.uint8)
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_pack(self._h, a.ctypes.data, a.size, int(block_bytes), out.ctypes.data, out.size, ctypes.byref(got)))
+        return out[:got.value].copy()
+
+    def unpack(self, frame, out=None):
+        """bwts_unpack: the bytes a frame holds (host buffers); the output is sized from the frame's header unless `out` is given."""
+        a = _u8(frame)
+        if out is None:
+            out = np.empty(unpack_size(a)[0], dtype=np.uint8)
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_unpack(self._h, a.ctypes.data, a.size, out.ctypes.data, out.size, ctypes.byref(got)))
+        return out[:got.value]
+
+    def pack_device(self, d_in, n, block_bytes, d_out, out_cap):
+        """bwts_pack_device: returns the frame's size in bytes."""
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_pack_device(self._h, _ptr(d_in), int(n), int(block_bytes), _ptr(d_out), int(out_cap), ctypes.byref(got)))
+        return int(got.value)
+
+    def unpack_device(self, d_in, in_bytes, d_out, out_cap):
+        """bwts_unpack_device: returns the number of bytes unpacked."""
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_unpack_device(self._h, _ptr(d_in), int(in_bytes), _ptr(d_out), int(out_cap), ctypes.byref(got)))
+        return int(got.value)
+
     def forward_into(self, a, out):
         """bwts_forward on caller-provided numpy buffers (no allocation inside the call)."""
         self._check(lib().bwts_forward(self._h, a.ctypes.data, a.size, out.ctypes.data))
@@ -593,6 +654,32 @@ def debug_ec_plan(n):
     if lib().bwts_debug_ec_plan(int(n), buf) < 0:
         raise BwtsError(-1, "bad length")
     return {"T": int(buf[0]), "K": int(buf[1]), "tiles": int(buf[2]), "blocks": int(buf[3]), "bound": int(buf[4])}
+
+
+def debug_crc_plan(n):
+    """How the checksum cuts one input of n bytes (bwts_debug_crc_plan: host arithmetic, no context, no device)."""
+    buf = (ctypes.c_uint64 * 4)()
+    if lib().bwts_debug_crc_plan(int(n), buf) < 0:
+        raise BwtsError(-1, "bad length")
+    return {"T": int(buf[0]), "G": int(buf[1]), "tiles": int(buf[2]), "groups": int(buf[3])}
+
+
+def pack_bound(n, block_bytes=0):
+    """bwts_pack_bound: the largest frame an input of n bytes cut at block_bytes can have."""
+    b = int(lib().bwts_pack_bound(int(n), int(block_bytes)))
+    if b == 0:
+        raise BwtsError(-5 if int(n) > (1 << 32) else -1, "no bound for these arguments")
+    return b
+
+
+def unpack_size(frame):
+    """bwts_unpack_size: (n, frame_bytes) of the frame at the start of a byte string, from its header and directory."""
+    a = _u8(frame)
+    n, fb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = lib().bwts_unpack_size(a.ctypes.data, a.size, ctypes.byref(n), ctypes.byref(fb))
+    if rc != 0:
+        raise BwtsError(rc, lib().bwts_strerror(rc).decode())
+    return int(n.value), int(fb.value)
 
 
 def ec_bound(n):

@@ -3,7 +3,9 @@
 #include "../../include/bwts_test.h"
 #include "../../include/bwts_mtf.h"
 #include "../../include/bwts_ec.h"
+#include "../../include/bwts_pack.h"
 #include "ec_plan.h"
+#include "pack_plan.h"
 
 #include <algorithm>
 #include <new>
@@ -739,7 +741,7 @@ extern "C" int bwts_inverse_sink(bwts_ctx *ctx, const uint8_t *in, uint64_t n, b
 // independent segments in one device pass: the segment table goes to the context, the transform runs through the same host / device
 // plumbing as a single input (staging, pre-faulting, a failed call leaves `out` as it was)
 // ------------------------------------------------------------------------------------
-static int set_segments(bwts_ctx *ctx, const uint64_t *lengths, uint64_t count, u64 *total)
+int seg_table_set(bwts_ctx *ctx, const uint64_t *lengths, uint64_t count, u64 *total)
 {
     if (!ctx || !lengths || count == 0) return BWTS_E_ARG;
     u64 sum = 0;
@@ -795,7 +797,7 @@ static int run_segments_host(bwts_ctx *ctx, const Transform &t, const uint8_t *i
 {
     if (!ctx || !in || !out) return BWTS_E_ARG;
     u64 n = 0;
-    BWTS_TRY(set_segments(ctx, lengths, count, &n));
+    BWTS_TRY(seg_table_set(ctx, lengths, count, &n));
     return run_host(ctx, t, in, n, out, nullptr, nullptr);
 }
 
@@ -803,7 +805,7 @@ static int run_segments_device(bwts_ctx *ctx, const Transform &t, const void *d_
 {
     if (!ctx || !d_in || !d_out) return BWTS_E_ARG;
     u64 n = 0;
-    BWTS_TRY(set_segments(ctx, lengths, count, &n));
+    BWTS_TRY(seg_table_set(ctx, lengths, count, &n));
     const char *a = (const char *)d_in, *b = (const char *)d_out;
     if (a < b + n && b < a + n) return BWTS_E_ARG;
     return run_device(ctx, t, d_in, n, d_out);
@@ -933,7 +935,7 @@ extern "C" int bwts_ec_encode_segments_device(bwts_ctx *ctx, const void *d_in, c
 {
     if (!ctx || !d_in || !d_out || !stream_bytes || ((uintptr_t)d_out & 15)) return BWTS_E_ARG;
     u64 n = 0;
-    BWTS_TRY(set_segments(ctx, lengths, count, &n));
+    BWTS_TRY(seg_table_set(ctx, lengths, count, &n));
     if (ranges_overlap(d_in, n, d_out, out_cap)) return BWTS_E_ARG;
     return run_sized(ctx, n, "ec encode", [&] { return ec_encode_impl(ctx, (const u8 *)d_in, n, (u8 *)d_out, out_cap, nullptr, stream_bytes); });
 }
@@ -943,7 +945,7 @@ extern "C" int bwts_ec_decode_segments_device(bwts_ctx *ctx, const void *d_in, c
 {
     if (!ctx || !d_in || !d_out || !stream_bytes || ((uintptr_t)d_in & 15)) return BWTS_E_ARG;
     u64 n = 0, in_bytes = 0;
-    BWTS_TRY(set_segments(ctx, lengths, count, &n));
+    BWTS_TRY(seg_table_set(ctx, lengths, count, &n));
     for (u64 s = 0; s < count; s++) {
         if (stream_bytes[s] > ec_bound_bytes(lengths[s])) return BWTS_E_FORMAT;       // (so the sum cannot overflow)
         in_bytes += stream_bytes[s];
@@ -991,6 +993,106 @@ extern "C" int bwts_ec_decode(bwts_ctx *ctx, const uint8_t *in, uint64_t in_byte
     const double h2d = wall_ms() - t0;
     u64 got = 0;
     BWTS_TRY(bwts_ec_decode_device(ctx, d_io(ctx, 0), in_bytes, d_io(ctx, 2), v, &got));
+    t0 = wall_ms();
+    BWTS_TRY(staged_d2h(ctx, sg, out, d_io(ctx, 2), got, nullptr, nullptr));
+    ctx->tm.d2h_ms = wall_ms() - t0;
+    ctx->tm.h2d_ms = h2d;
+    *n = got;
+    return BWTS_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// checksum and the packed frame (include/bwts_pack.h): the chain of the three stages as one call, the kernel in crc.hip, the drivers
+// in pack.hip
+// ------------------------------------------------------------------------------------
+extern "C" int bwts_crc32_device(bwts_ctx *ctx, const void *d_in, uint64_t n, uint32_t *crc)
+{
+    if (!ctx || !d_in || !crc || n == 0) return BWTS_E_ARG;
+    if (n > CRC_MAX_N) return BWTS_E_RANGE;
+    return run_sized(ctx, n, "crc32", [&] { return crc_impl(ctx, (const u8 *)d_in, n, false, crc); });
+}
+
+extern "C" int bwts_crc32_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, uint32_t *crcs)
+{
+    if (!ctx || !d_in || !crcs) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(seg_table_set(ctx, lengths, count, &n));
+    return run_sized(ctx, n, "crc32", [&] { return crc_impl(ctx, (const u8 *)d_in, n, true, crcs); });
+}
+
+extern "C" uint64_t bwts_pack_bound(uint64_t n, uint64_t block_bytes)
+{
+    const u64 B = pack_block_len(n, block_bytes);
+    return B ? pack_bound_bytes(n, B) : 0;
+}
+
+extern "C" int bwts_unpack_size(const uint8_t *frame, uint64_t in_bytes, uint64_t *n, uint64_t *frame_bytes)
+{
+    if (!frame || !n || !frame_bytes) return BWTS_E_ARG;
+    PackHeader H;
+    BWTS_TRY(pack_header_check(frame, in_bytes, &H));
+    BWTS_TRY(pack_directory_check(frame + PACK_HEADER_BYTES, H, in_bytes, false, frame_bytes));
+    *n = H.n;
+    return BWTS_OK;
+}
+
+extern "C" int bwts_pack_device(bwts_ctx *ctx, const void *d_in, uint64_t n, uint64_t block_bytes, void *d_out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!ctx || !d_in || !d_out || !out_bytes || n == 0 || ((uintptr_t)d_out & 15)) return BWTS_E_ARG;
+    if (n > PACK_MAX_N) return BWTS_E_RANGE;
+    const u64 B = pack_block_len(n, block_bytes);
+    if (B == 0 || ranges_overlap(d_in, n, d_out, out_cap)) return BWTS_E_ARG;
+    return run_sized(ctx, n, "pack", [&] { return pack_device_impl(ctx, (const u8 *)d_in, n, B, (u8 *)d_out, out_cap, out_bytes); });
+}
+
+extern "C" int bwts_unpack_device(bwts_ctx *ctx, const void *d_in, uint64_t in_bytes, void *d_out, uint64_t out_cap, uint64_t *n)
+{
+    if (!ctx || !d_in || !d_out || !n || in_bytes == 0 || ((uintptr_t)d_in & 15)) return BWTS_E_ARG;
+    if (ranges_overlap(d_in, in_bytes, d_out, out_cap)) return BWTS_E_ARG;
+    return run_sized(ctx, 0, "unpack", [&] { return unpack_device_impl(ctx, (const u8 *)d_in, in_bytes, (u8 *)d_out, out_cap, n); });
+}
+
+// Host buffers, staged like the coder's: in goes to the device, the device form runs, what it made comes back.  Nothing is written
+// to out before the device form has succeeded.
+extern "C" int bwts_pack(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint64_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!ctx || !in || !out || !out_bytes || n == 0) return BWTS_E_ARG;
+    if (n > PACK_MAX_N) return BWTS_E_RANGE;
+    const u64 B = pack_block_len(n, block_bytes);
+    if (B == 0) return BWTS_E_ARG;
+    const u64 cap = out_cap < pack_bound_bytes(n, B) ? out_cap : pack_bound_bytes(n, B);
+    if (cap < pack_least_bytes(n, B)) return BWTS_E_SPACE;
+    HIPC(hipSetDevice(ctx->device));
+    BWTS_TRY(ensure_io(ctx, n > cap ? n : cap, false));
+    Stager &sg = ctx->stg[0];
+    double t0 = wall_ms();
+    BWTS_TRY(staged_h2d(ctx, sg, d_io(ctx, 0), in, n));
+    const double h2d = wall_ms() - t0;
+    u64 bytes = 0;
+    BWTS_TRY(bwts_pack_device(ctx, d_io(ctx, 0), n, block_bytes, d_io(ctx, 2), cap, &bytes));
+    t0 = wall_ms();
+    BWTS_TRY(staged_d2h(ctx, sg, out, d_io(ctx, 2), bytes, nullptr, nullptr));
+    ctx->tm.d2h_ms = wall_ms() - t0;
+    ctx->tm.h2d_ms = h2d;
+    *out_bytes = bytes;
+    return BWTS_OK;
+}
+
+extern "C" int bwts_unpack(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n)
+{
+    if (!ctx || !in || !out || !n || in_bytes == 0) return BWTS_E_ARG;
+    u64 v = 0, frame = 0;
+    BWTS_TRY(bwts_unpack_size(in, in_bytes, &v, &frame));
+    if (frame != in_bytes) return BWTS_E_FORMAT;
+    if (v > out_cap) return BWTS_E_SPACE;
+    HIPC(hipSetDevice(ctx->device));
+    BWTS_TRY(ensure_io(ctx, in_bytes > v ? in_bytes : v, false));
+    Stager &sg = ctx->stg[0];
+    double t0 = wall_ms();
+    BWTS_TRY(staged_h2d(ctx, sg, d_io(ctx, 0), in, in_bytes));
+    const double h2d = wall_ms() - t0;
+    u64 got = 0;
+    BWTS_TRY(bwts_unpack_device(ctx, d_io(ctx, 0), in_bytes, d_io(ctx, 2), v, &got));
     t0 = wall_ms();
     BWTS_TRY(staged_d2h(ctx, sg, out, d_io(ctx, 2), got, nullptr, nullptr));
     ctx->tm.d2h_ms = wall_ms() - t0;
@@ -1069,6 +1171,7 @@ extern "C" const char *bwts_strerror(int code)
     case BWTS_E_SINK: return "the caller's output sink reported an error";
     case BWTS_E_FORMAT: return "not a valid entropy-coded stream";
     case BWTS_E_SPACE: return "the result does not fit into the output buffer";
+    case BWTS_E_CHECKSUM: return "checksum mismatch: the unpacked bytes are not the ones that were packed";
     default: return "unknown error";
     }
 }
@@ -1181,6 +1284,14 @@ extern "C" int bwts_debug_ec_plan(uint64_t n, uint64_t out[5])
 {
     if (n == 0 || n > EC_MAX_N || !out) return -1;
     bwts_ec_plan(n, out);
+    return 0;
+}
+
+// the checksum's cut of one input of n bytes: tile size, tiles per fold group, tiles, groups.  No context, no device
+extern "C" int bwts_debug_crc_plan(uint64_t n, uint64_t out[4])
+{
+    if (n == 0 || n > CRC_MAX_N || !out) return -1;
+    bwts_crc_plan(n, out);
     return 0;
 }
 

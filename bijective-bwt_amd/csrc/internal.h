@@ -67,12 +67,14 @@ enum SegReportWord { SR_PLAN, SR_BIG, SR_RUNS, SR_OWN_SEGS, SR_OWN_BYTES, SR_SIN
 // bwts_ctx_destroy (ctx_memory.hip).  name: what the allocation trace and the guard report call it.
 struct KeptBlock { char *p; size_t cap; const char *name; };
 // every kept block of a context, in bwts_ctx::kept
-enum { KB_ARENA, KB_AUX, KB_IO = KB_AUX + BWTS_AUX_SLOTS, KB_SEG_TABLE = KB_IO + 4, KB_SEG_SCRATCH, KB_COUNT };
+enum { KB_ARENA, KB_AUX, KB_IO = KB_AUX + BWTS_AUX_SLOTS, KB_SEG_TABLE = KB_IO + 4, KB_SEG_SCRATCH, KB_PACK, KB_COUNT = KB_PACK + 2 };
 
 #define SM_RX_SYNC 4090          // d_small word holding the two 32-bit counters of radix_column_scan_fused_kernel (zero between launches)
 #define SM_EC_TOTAL 4020         // entropy coder (ec.hip): d_small word for the bytes of all payloads of an encode
 #define SM_EC_FLAG  4021         // ... d_small word for what a decode found wrong (0: nothing)
 #define SM_EC_HEAD  4022         // ... h_small, two words: the header of a single stream
+#define SM_CRC_OUT  4024         // checksum (crc.hip): h_small word for the value of a single input
+#define SM_PACK_HEAD 4026        // packed frame (pack.hip): h_small, six words: the header and a one-block directory on their way in or out
 
 struct Stager {
     hipStream_t stream;             // the queue its copies (and copy kernels) are issued on
@@ -94,13 +96,14 @@ struct bwts_ctx {
     // list of the general Lyndon path.  3: previous-symbol array + carried-byte buffers (rounds-0 sorts on wide keys).  4: dense rank array.
     // (What the headline path does not touch is not allocated: the driver clears device memory it hands out, ~27 ms per GiB.)
     // KB_IO + i: the host-buffer entry points' device-side in/out buffers (below).  KB_SEG_TABLE: the device copy of the segment table.
-    // KB_SEG_SCRATCH: segmented forward: factor-start flags.
+    // KB_SEG_SCRATCH: segmented forward: factor-start flags.  KB_PACK + i: pack / unpack: the bytes between two stages of the chain.
     KeptBlock kept[KB_COUNT] = {{nullptr, 0, "arena"},
                                 {nullptr, 0, "side block 0"}, {nullptr, 0, "side block 1"}, {nullptr, 0, "side block 2"},
                                 {nullptr, 0, "side block 3"}, {nullptr, 0, "side block 4"},
                                 {nullptr, 0, "device input 0"}, {nullptr, 0, "device input 1"},
                                 {nullptr, 0, "device output 0"}, {nullptr, 0, "device output 1"},
-                                {nullptr, 0, "segment table"}, {nullptr, 0, "segment scratch"}};
+                                {nullptr, 0, "segment table"}, {nullptr, 0, "segment scratch"},
+                                {nullptr, 0, "pack stage 0"}, {nullptr, 0, "pack stage 1"}};
     size_t arena_off;
     size_t unv_hint;       // inverse: unreached elements seen by the previous call (sizes the first collection pass)
     // inverse: one record per attempt of the most recent call, from values its stages hold on the host anyway (a few stores per
@@ -154,6 +157,7 @@ struct bwts_ctx {
     size_t h_seg_cap = 0;
     // inverse: what the most recent segmented inverse did (bwts_debug_segments_report; include/bwts_test.h names the words)
     u64 seg_report[SEG_REPORT_WORDS] = {0};
+    bool crc_tables = false;            // the checksum's tables (crc.hip) have been made on this context's device
 
     bwts_timings tm;
     double host_ms[BWTS_H_COUNT];   // cumulative host-side costs (BWTS_H_*)
@@ -301,6 +305,14 @@ void bwts_mtf_plan(u64 n, u64 out[4]);                                  // tile 
 int ec_encode_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, u64 out_cap, u64 *out_bytes, u64 *stream_bytes);
 int ec_decode_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out, const u64 *stream_bytes);
 void bwts_ec_plan(u64 n, u64 out[5]);                                   // tile size, tiles per block, tiles, blocks and the bound of one input
+
+// ---- checksum and the packed frame (crc.hip, pack.hip; include/bwts_pack.h) ------------
+// one input of n bytes, or the segments of the context's table: one value each, to the host
+int crc_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, bool segments, u32 *crcs);
+void bwts_crc_plan(u64 n, u64 out[4]);                                  // tile size, tiles per fold group, tiles and groups of one input
+int seg_table_set(bwts_ctx *ctx, const uint64_t *lengths, uint64_t count, u64 *total);     // the segment table of the calls that follow (api.hip)
+int pack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes);
+int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out);
 
 // chunk tables of the forward's later rounds (chunk_rounds.h) as plain arithmetic: nominal chunk size of a list, the tables' capacity
 // for a tied list of a0, and the re-cut of the a_chunks elements left at a compaction (allowed = the new chunks fit the tables)

@@ -1,0 +1,155 @@
+// pack_plan.h -- the arithmetic of the packed frame (include/bwts_pack.h, version 1) and of its checksum that host and device share:
+// CRC-32 as polynomial arithmetic over GF(2), how an input is cut into blocks, the bound, and what makes a header and a directory
+// valid.  Plain C++ with no dependency but ec_plan.h: crc.hip, pack.hip, the host side of the calls and a stand-alone host program
+// (tests/pack_plan_check.cc, built with the sanitizers) all compile this file.
+#pragma once
+#include <stdint.h>
+#include "ec_plan.h"
+
+#define PACK_MAGIC 0x5A545742u           // "BWTZ"
+#define PACK_VERSION 1u
+#define PACK_HEADER_BYTES 32u
+#define PACK_ENTRY_BYTES 16u
+#define PACK_MIN_BLOCK 4096u
+#define PACK_MAX_N (1ull << 32)
+#define PACK_LEAST_FRAME 48u             // header and one directory entry
+// what the predicates answer (the values of BWTS_OK, BWTS_E_RANGE and BWTS_E_FORMAT; pack.hip asserts that they are)
+#define PACK_OK 0
+#define PACK_RANGE -5
+#define PACK_FORMAT -8
+
+// ---- CRC-32 (zlib, gzip, PNG): reflected polynomial, a register's bit 31 is the coefficient of x^0 ----
+#define CRC_POLY 0xEDB88320u
+#define CRC_ONE 0x80000000u              // the polynomial 1
+#define CRC_MAX_N (1ull << 36)
+#define CRC_LOG_T 16u                    // tile: T = 65536 bytes, one wave
+#define CRC_T (1u << CRC_LOG_T)
+#define CRC_G 256u                       // tiles whose values one wave folds at the second level
+#define CRC_ROW 1024u                    // a lane owns 16 consecutive bytes of every row
+
+EC_HD uint64_t crc_tiles(uint64_t n) { return (n + CRC_T - 1u) >> CRC_LOG_T; }
+EC_HD uint64_t crc_groups(uint64_t tiles) { return (tiles + CRC_G - 1u) / CRC_G; }
+
+EC_HD uint32_t crc_times_x(uint32_t a) { return (a >> 1) ^ ((a & 1u) ? CRC_POLY : 0u); }
+// a / x mod P: P has the constant term 1, so x is invertible
+EC_HD uint32_t crc_over_x(uint32_t a) { return (a & CRC_ONE) ? ((a ^ CRC_POLY) << 1) | 1u : a << 1; }
+// a b mod P
+EC_HD uint32_t crc_mul(uint32_t a, uint32_t b)
+{
+    uint32_t p = 0;
+    for (int i = 0; i < 32; i++) {
+        p ^= (a & (CRC_ONE >> i)) ? b : 0u;
+        b = crc_times_x(b);
+    }
+    return p;
+}
+// x^(8 bytes) mod P, by squaring
+EC_HD uint32_t crc_xpow8(uint64_t bytes)
+{
+    uint32_t r = CRC_ONE, sq = CRC_ONE >> 8;
+    for (; bytes; bytes >>= 1) {
+        if (bytes & 1u) r = crc_mul(r, sq);
+        sq = crc_mul(sq, sq);
+    }
+    return r;
+}
+// the register after one more byte
+EC_HD uint32_t crc_step_byte(uint32_t r, uint32_t byte)
+{
+    r ^= byte;
+    for (int i = 0; i < 8; i++) r = crc_times_x(r);
+    return r;
+}
+// crc(A B) from crc(A), crc(B) and the length of B (both finished values: the initial and final terms cancel)
+EC_HD uint32_t crc_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return crc_mul(crc_a, crc_xpow8(len_b)) ^ crc_b; }
+// the checksum of a few bytes on the host (header and directory): four bits at a time
+EC_HD uint32_t crc32_bytes(const uint8_t *p, uint64_t len)
+{
+    uint32_t nib[16];
+    for (uint32_t v = 0; v < 16; v++) {
+        uint32_t r = v;
+        for (int i = 0; i < 4; i++) r = crc_times_x(r);
+        nib[v] = r;
+    }
+    uint32_t r = 0xFFFFFFFFu;
+    for (uint64_t i = 0; i < len; i++) {
+        r ^= p[i];
+        r = nib[r & 15u] ^ (r >> 4);
+        r = nib[r & 15u] ^ (r >> 4);
+    }
+    return ~r;
+}
+
+// ---- the frame ----
+EC_HD uint64_t pack_le64(const uint8_t *p) { return (uint64_t)ec_le32(p) | (uint64_t)ec_le32(p + 4) << 32; }
+EC_HD void pack_put64(uint8_t *p, uint64_t v) { ec_put32(p, (uint32_t)v); ec_put32(p + 4, (uint32_t)(v >> 32)); }
+
+// the block length a pack of n bytes stores for the caller's block_bytes; 0: bad arguments
+EC_HD uint64_t pack_block_len(uint64_t n, uint64_t block_bytes)
+{
+    if (n == 0 || n > PACK_MAX_N) return 0;
+    if (block_bytes == 0 || block_bytes >= n) return n;
+    return block_bytes < PACK_MIN_BLOCK ? 0 : block_bytes;
+}
+EC_HD uint64_t pack_blocks(uint64_t n, uint64_t B) { return (n + B - 1u) / B; }
+EC_HD uint64_t pack_block_at(uint64_t n, uint64_t B, uint64_t b) { return n - b * B < B ? n - b * B : B; }      // bytes of block b
+EC_HD uint64_t pack_fixed_bytes(uint64_t nblk) { return PACK_HEADER_BYTES + (uint64_t)PACK_ENTRY_BYTES * nblk; }
+// all blocks but the last are B long: the coder's bound and least size, summed over the blocks, behind header and directory
+EC_HD uint64_t pack_bound_bytes(uint64_t n, uint64_t B)
+{
+    const uint64_t nblk = pack_blocks(n, B);
+    return pack_fixed_bytes(nblk) + (nblk - 1u) * ec_bound_bytes(B) + ec_bound_bytes(n - (nblk - 1u) * B);
+}
+EC_HD uint64_t pack_least_bytes(uint64_t n, uint64_t B)
+{
+    const uint64_t nblk = pack_blocks(n, B);
+    return pack_fixed_bytes(nblk) + (nblk - 1u) * ec_least_bytes(B) + ec_least_bytes(n - (nblk - 1u) * B);
+}
+
+EC_HD void pack_entry_write(uint8_t e[16], uint64_t stream_bytes, uint32_t crc)
+{
+    pack_put64(e, stream_bytes); ec_put32(e + 8, crc); ec_put32(e + 12, 0u);
+}
+// the header of a frame whose directory (nblk entries) is complete
+EC_HD void pack_header_write(uint8_t h[32], uint64_t n, uint64_t B, const uint8_t *dir)
+{
+    ec_put32(h, PACK_MAGIC); ec_put32(h + 4, PACK_VERSION); pack_put64(h + 8, n); pack_put64(h + 16, B);
+    ec_put32(h + 24, crc32_bytes(dir, (uint64_t)PACK_ENTRY_BYTES * pack_blocks(n, B)));
+    ec_put32(h + 28, crc32_bytes(h, 28));
+}
+
+struct PackHeader { uint64_t n, B, nblk; uint32_t dir_crc; };
+
+// The header of a frame of which in_bytes bytes are at hand (h: the first 32 of them, read only when in_bytes allows a frame at all).
+// PACK_OK and *H, PACK_FORMAT, or PACK_RANGE for a sound header that names more than 2^32 bytes.
+EC_HD int pack_header_check(const uint8_t *h, uint64_t in_bytes, PackHeader *H)
+{
+    if (in_bytes < PACK_LEAST_FRAME || (in_bytes & 15u)) return PACK_FORMAT;
+    if (ec_le32(h) != PACK_MAGIC || ec_le32(h + 4) != PACK_VERSION) return PACK_FORMAT;
+    if (ec_le32(h + 28) != crc32_bytes(h, 28)) return PACK_FORMAT;
+    const uint64_t n = pack_le64(h + 8), B = pack_le64(h + 16);
+    if (n == 0) return PACK_FORMAT;
+    if (n > PACK_MAX_N) return PACK_RANGE;
+    if (B == 0 || B > n || (B < PACK_MIN_BLOCK && B != n)) return PACK_FORMAT;
+    H->n = n; H->B = B; H->nblk = pack_blocks(n, B); H->dir_crc = ec_le32(h + 24);
+    if (pack_fixed_bytes(H->nblk) > in_bytes) return PACK_FORMAT;
+    return PACK_OK;
+}
+
+// The directory behind a header that passed (dir: H.nblk entries, which in_bytes holds).  exact: the frame must be all of in_bytes
+// (an unpack), else it may end earlier (stepping through concatenated frames).  PACK_OK and *frame_bytes, or PACK_FORMAT.
+EC_HD int pack_directory_check(const uint8_t *dir, const PackHeader &H, uint64_t in_bytes, bool exact, uint64_t *frame_bytes)
+{
+    if (crc32_bytes(dir, (uint64_t)PACK_ENTRY_BYTES * H.nblk) != H.dir_crc) return PACK_FORMAT;
+    uint64_t total = pack_fixed_bytes(H.nblk);
+    for (uint64_t b = 0; b < H.nblk; b++) {
+        const uint8_t *e = dir + (uint64_t)PACK_ENTRY_BYTES * b;
+        const uint64_t sb = pack_le64(e), len = pack_block_at(H.n, H.B, b);
+        if (ec_le32(e + 12) != 0u || (sb & 15u)) return PACK_FORMAT;
+        if (sb < ec_least_bytes(len) || sb > ec_bound_bytes(len)) return PACK_FORMAT;      // (so the sum cannot overflow)
+        total += sb;
+    }
+    if (exact ? total != in_bytes : total > in_bytes) return PACK_FORMAT;
+    *frame_bytes = total;
+    return PACK_OK;
+}

@@ -30,7 +30,8 @@
  *
  * The format has no checksum.  The decoder refuses what it can see is malformed (BWTS_E_FORMAT) and forms every address from values
  * it has checked or clamped, so a hostile stream cannot make it read or write outside its buffers; but a changed payload bit that
- * still brings every lane back to 2^16 yields wrong bytes, in bounds, and BWTS_OK.  Callers that need integrity add their own check.
+ * still brings every lane back to 2^16 yields wrong bytes, in bounds, and BWTS_OK.  Callers that need integrity add their own check
+ * (bwts_pack.h does: a CRC-32 per block, computed on the device).
  *
  * Semantics are those of bwts_mtf.h: the calls run on the context's stream and are synchronous; BWTS_E_ARG on NULL pointers, n == 0,
  * in_bytes == 0, count == 0, a zero length, or device buffers that overlap; single inputs up to 2^36 bytes and segment sums up to

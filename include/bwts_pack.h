@@ -1,0 +1,77 @@
+/*
+ * bwts_pack.h -- the three device stages as a compressor: pack runs transform (bwts.h), move-to-front (bwts_mtf.h) and entropy coder
+ * (bwts_ec.h) over the blocks of an input and writes one self-describing frame with a CRC-32 per block; unpack checks the frame,
+ * runs the chain backwards and checks every block's bytes.  The checksum kernel is a call of its own too.
+ *
+ * Not part of the drop-in surface of the two reference programs (include/bwts.h is, and stays as it is).
+ *
+ * CRC-32 is the one of zlib, gzip and PNG: reflected polynomial 0xEDB88320, initial value and final xor 0xFFFFFFFF.
+ *
+ * The frame, version 1 (all integers little-endian).  An input of n bytes, 1 <= n <= 2^32, is cut into nblk = ceil(n / B) blocks of
+ * B bytes; the last may be shorter.
+ *   1. Header, 32 bytes:
+ *        offset  0  u32 magic 0x5A545742 ("BWTZ")
+ *        offset  4  u32 version = 1
+ *        offset  8  u64 n
+ *        offset 16  u64 B
+ *        offset 24  u32 CRC-32 of the directory bytes
+ *        offset 28  u32 CRC-32 of header bytes 0 .. 27
+ *   2. Directory, nblk x 16 bytes: u64 stream_bytes, u32 CRC-32 of the block's original (untransformed) bytes, u32 zero.
+ *   3. Streams: the version-1 stream of bwts_ec.h of MTF(BWTS(block)) for every block, in order; each a multiple of 16 bytes, together
+ *      exactly what bwts_ec_encode_segments_device writes for these lengths.
+ * B is always the real block length: block_bytes == 0 on the way in means one block, B = n; otherwise block_bytes >= 4096, and a
+ * value >= n is stored as n (a nonzero block_bytes below 4096 is BWTS_E_ARG).  So B = n or 4096 <= B < n.
+ * Bound: 32 + 16 nblk + the sum of bwts_ec_bound over the blocks.
+ *
+ * A frame is not trusted.  Unpack refuses with BWTS_E_FORMAT, in this order: in_bytes < 48 or not a multiple of 16; wrong magic or
+ * version; a wrong header CRC; n = 0 (n > 2^32 is BWTS_E_RANGE); B = 0, B > n, or B < 4096 with B != n; a directory longer than the
+ * frame; a wrong directory CRC; an entry with a nonzero reserved word, or a stream_bytes that is not a multiple of 16 or outside
+ * what the coder can make of the block's length; 32 + 16 nblk + the sum of stream_bytes != in_bytes.  Then a header n > out_cap is
+ * BWTS_E_SPACE.  After the checks: decode (the coder's own BWTS_E_FORMAT passes through, and a stream whose header names another
+ * length than its block's is BWTS_E_FORMAT), inverse move-to-front, inverse transform, and the CRC-32 of every block of the result
+ * against the directory: a difference is BWTS_E_CHECKSUM.
+ *
+ * Semantics are those of bwts_ec.h: the calls run on the context's stream and are synchronous; BWTS_E_ARG on NULL pointers, n == 0,
+ * in_bytes == 0, count == 0 or a zero length; the device forms refuse buffers that overlap, and a coded side (d_out of a pack, d_in of
+ * an unpack) that is not 16-byte aligned.  The checksum calls take single inputs up to 2^36 bytes and segment sums up to 2^32
+ * (BWTS_E_RANGE above, decided before the data is touched) at any alignment of d_in and of the segment starts; pack takes up to
+ * 2^32 bytes (BWTS_E_RANGE above).
+ * Pack never fails with BWTS_E_SPACE for out_cap >= bwts_pack_bound; with less it returns BWTS_E_SPACE as soon as the frame is known
+ * not to fit, and has then written nothing at all (header and directory are written last).  A device unpack that fails may have
+ * written part of d_out; the host forms leave out as it was after any failure.
+ * Cost: pack is one checksum pass and the three stages; between them the bytes stay in two n-byte blocks that the context keeps
+ * (unpack: one; it decodes into d_out), counted in bwts_timings::device_bytes and given up by bwts_ctx_release_memory.  The checksum
+ * takes four bytes per 64 KiB tile from the context's arena.  bwts_last_timings: n (the unpacked bytes) and total_ms are filled,
+ * the kernels are accounted under BWTS_K_OTHER.
+ */
+#ifndef BWTS_PACK_H
+#define BWTS_PACK_H
+
+#include "bwts_ec.h"
+
+#define BWTS_E_CHECKSUM -10   /* a block decoded in bounds but its bytes are not the ones that were packed */
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* crc: one value; crcs: host array of count entries */
+int bwts_crc32_device(bwts_ctx *ctx, const void *d_in, uint64_t n, uint32_t *crc);
+int bwts_crc32_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, uint32_t *crcs);
+
+/* host arithmetic only: the largest frame of n bytes cut at block_bytes (0 on bad arguments), and what header and directory of a
+ * frame say, of which in_bytes bytes are at hand (the frame may end before them: concatenated frames are stepped through by
+ * frame_bytes; BWTS_E_FORMAT also for a frame that does not end within in_bytes) */
+uint64_t bwts_pack_bound(uint64_t n, uint64_t block_bytes);
+int bwts_unpack_size(const uint8_t *frame, uint64_t in_bytes, uint64_t *n, uint64_t *frame_bytes);
+
+int bwts_pack_device(bwts_ctx *ctx, const void *d_in, uint64_t n, uint64_t block_bytes, void *d_out, uint64_t out_cap, uint64_t *out_bytes);
+int bwts_unpack_device(bwts_ctx *ctx, const void *d_in, uint64_t in_bytes, void *d_out, uint64_t out_cap, uint64_t *n);
+/* host buffers */
+int bwts_pack(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint64_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes);
+int bwts_unpack(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -113,6 +113,10 @@ int bwts_debug_forward_report(bwts_ctx *ctx, uint64_t *out, uint64_t cap_words, 
  * tile size in bytes; K, the tiles that share one frequency table; tiles = ceil(n / T); blocks = ceil(tiles / K); the bound of the
  * stream in bytes}.  Returns 0, -1 on a bad argument. */
 int bwts_debug_ec_plan(uint64_t n, uint64_t out[5]);
+/* Pure arithmetic, no context and no device: how the checksum (bwts_pack.h) cuts one input of 1 <= n <= 2^36 bytes.  out = {T, the tile
+ * size in bytes; G, the tile values one wave folds at the second level; tiles = ceil(n / T); groups = ceil(tiles / G)}.  Returns 0, -1
+ * on a bad argument. */
+int bwts_debug_crc_plan(uint64_t n, uint64_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,243 @@
+// api_test.hip -- what include/bwts_test.h declares: the harness utilities (generate, device buffers, compare) and the bwts_debug_*
+// hooks the test suite drives.  No product path calls into this file.
+#include "internal.h"
+#include "../../include/bwts_test.h"
+#include "ec_plan.h"
+#include "pack_plan.h"
+
+#include <stdlib.h>
+#include <string.h>
+
+extern "C" int bwts_generate_device(bwts_ctx *ctx, int kind, uint64_t seed, uint64_t n, void *d_out)
+{
+    if (!ctx || !d_out) return BWTS_E_ARG;
+    HIPC(hipSetDevice(ctx->device));
+    return generate_device_impl(ctx, kind, seed, n, (u8 *)d_out);
+}
+
+extern "C" int bwts_device_alloc(bwts_ctx *ctx, uint64_t bytes, void **d_ptr)
+{
+    if (!ctx || !d_ptr) return BWTS_E_ARG;
+    HIPC(hipSetDevice(ctx->device));
+    if (hipMalloc(d_ptr, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); return BWTS_E_NOMEM; }
+    return BWTS_OK;
+}
+
+extern "C" int bwts_device_free(bwts_ctx *ctx, void *d_ptr)
+{
+    if (!ctx) return BWTS_E_ARG;
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipFree(d_ptr));
+    return BWTS_OK;
+}
+
+extern "C" int bwts_copy_to_device(bwts_ctx *ctx, void *d_dst, const void *h_src, uint64_t bytes)
+{
+    if (!ctx || (bytes && (!d_dst || !h_src))) return BWTS_E_ARG;
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipMemcpy(d_dst, h_src, bytes, hipMemcpyHostToDevice));
+    return BWTS_OK;
+}
+
+extern "C" int bwts_copy_to_host(bwts_ctx *ctx, void *h_dst, const void *d_src, uint64_t bytes)
+{
+    if (!ctx || (bytes && (!h_dst || !d_src))) return BWTS_E_ARG;
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipMemcpy(h_dst, d_src, bytes, hipMemcpyDeviceToHost));
+    return BWTS_OK;
+}
+
+extern "C" int bwts_device_equal(bwts_ctx *ctx, const void *d_a, const void *d_b, uint64_t bytes, int *equal)
+{
+    if (!ctx || !equal) return BWTS_E_ARG;
+    HIPC(hipSetDevice(ctx->device));
+    return device_equal_impl(ctx, (const u8 *)d_a, (const u8 *)d_b, bytes, equal);
+}
+
+// ---- unit-test hooks ----
+extern "C" int bwts_debug_sort_pairs(bwts_ctx *ctx, uint64_t *h_keys, uint32_t *h_vals, uint64_t m, int key_bits)
+{
+    if (!ctx || !h_keys || !h_vals) return BWTS_E_ARG;
+    HIPC(hipSetDevice(ctx->device));
+    spans_reset(ctx);
+    SortBufs sb;
+    BlockLayout L;
+    sb.declare(L, m);
+    BWTS_TRY(arena_reserve(ctx, L.bytes()));
+    char *base = (char *)arena_alloc(ctx, L.bytes());
+    if (!base) return BWTS_E_NOMEM;
+    L.place(base);
+    const SortPlan plan = sb.plan();
+    HIPC(hipMemcpyAsync(plan.keys[0], h_keys, m * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(hipMemcpyAsync(plan.vals[0], h_vals, m * 4, hipMemcpyHostToDevice, ctx->stream));
+    int res = 0;
+    BWTS_TRY(radix_sort_pairs(ctx, plan, m, key_bits, &res));
+    HIPC(hipMemcpyAsync(h_keys, plan.keys[res], m * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipMemcpyAsync(h_vals, plan.vals[res], m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    BWTS_TRY(spans_resolve(ctx));
+    return BWTS_OK;
+}
+
+static int upload_text(bwts_ctx *ctx, const uint8_t *in, uint64_t n, u8 **d_T)
+{
+    void *p = nullptr;
+    if (hipMalloc(&p, n) != hipSuccess) { (void)hipGetLastError(); return BWTS_E_NOMEM; }
+    if (hipMemcpyAsync(p, in, n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess) { (void)hipFree(p); return BWTS_E_HIP; }
+    *d_T = (u8 *)p;
+    return BWTS_OK;
+}
+
+// the chunk tables' arithmetic for a tied list of a0 elements of which a_chunks are left at a compaction: no context, no device
+extern "C" int bwts_debug_chunk_plan(uint64_t a0, uint64_t a_chunks, uint64_t out[4])
+{
+    const ChunkRecut re = chunk_recut_plan(a0, a_chunks);
+    out[0] = chunk_nominal_size(a0); out[1] = chunk_table_capacity(a0); out[2] = re.S; out[3] = re.nc;
+    return re.allowed ? 1 : 0;
+}
+
+// the move-to-front stage's cut of one input of n bytes: tile size, tiles per group, tiles, groups.  No context, no device
+extern "C" int bwts_debug_mtf_plan(uint64_t n, uint64_t out[4])
+{
+    if (n == 0 || !out) return -1;
+    bwts_mtf_plan(n, out);
+    return 0;
+}
+
+// the entropy coder's cut of one input of n bytes: tile size, tiles per block, tiles, blocks, the bound.  No context, no device
+extern "C" int bwts_debug_ec_plan(uint64_t n, uint64_t out[5])
+{
+    if (n == 0 || n > EC_MAX_N || !out) return -1;
+    bwts_ec_plan(n, out);
+    return 0;
+}
+
+// the checksum's cut of one input of n bytes: tile size, tiles per fold group, tiles, groups.  No context, no device
+extern "C" int bwts_debug_crc_plan(uint64_t n, uint64_t out[4])
+{
+    if (n == 0 || n > CRC_MAX_N || !out) return -1;
+    bwts_crc_plan(n, out);
+    return 0;
+}
+
+// the device time of every timed launch of the most recent call, in launch order (timing level 2: every launch has a span; the events
+// stay with the context until the next call)
+extern "C" int bwts_debug_last_spans(bwts_ctx *ctx, double *ms, uint64_t cap)
+{
+    if (!ctx || (!ms && cap)) return BWTS_E_ARG;
+    int k = 0;
+    for (const TimedSpan &sp : ctx->spans) {
+        if ((u64)k >= cap) break;
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, sp.a, sp.b) != hipSuccess) { (void)hipGetLastError(); t = -1.f; }
+        ms[k++] = t;
+    }
+    return k;
+}
+
+// what a segmented inverse would do with segments of these lengths (the cost estimate's choice; test switches do not apply): no
+// context, no device
+extern "C" int bwts_debug_segments_plan(const uint64_t *lengths, uint64_t count, uint64_t out[8])
+{
+    if (!lengths || !out || count == 0) return -1;
+    return inverse_segments_plan_words(lengths, count, out);
+}
+
+// what the most recent segmented inverse on this context did: no device, the record is host memory
+extern "C" int bwts_debug_segments_report(bwts_ctx *ctx, uint64_t out[8])
+{
+    static_assert(SEG_REPORT_WORDS == 8, "the record layout bwts_test.h states");
+    if (!ctx || !out) return BWTS_E_ARG;
+    memcpy(out, ctx->seg_report, sizeof ctx->seg_report);
+    return BWTS_OK;
+}
+
+// the narrow inverse's arena as plain arithmetic: no context, no device
+extern "C" int bwts_debug_inverse_arena(uint64_t n, int g, int mark, uint64_t out[2])
+{
+    if (n == 0 || n > NARROW_N || g > 20 || mark < 0 || mark > 3) return -1;
+    if (g < 0) g = inverse_splitter_log2(n);
+    out[0] = inverse_attempt_bytes(n, g, mark); out[1] = inverse_arena_bytes(n);
+    return g;
+}
+
+// the narrow forward's arena, likewise: the bytes its declared layout takes
+extern "C" int bwts_debug_forward_arena(uint64_t n, uint64_t out[1])
+{
+    if (n == 0 || n > NARROW_N || !out) return -1;
+    out[0] = forward_arena_bytes(n);
+    return 0;
+}
+
+// the wide forward's arena (wide_path.h), likewise
+extern "C" int bwts_debug_wide_forward_arena(uint64_t n, int mode, int seg_log2, uint64_t bucket_cap, uint64_t out[1])
+{
+    return forward_wide_arena_probe(n, mode, seg_log2, bucket_cap, out);
+}
+
+// what the attempts of the most recent inverse call on this context did: no device, the records are host memory
+extern "C" int bwts_debug_inverse_report(bwts_ctx *ctx, uint64_t *out, uint64_t cap_words, uint64_t *attempts)
+{
+    if (!ctx || !attempts || (!out && cap_words)) return BWTS_E_ARG;
+    *attempts = ctx->inv_attempts_made;
+    int copied = 0;
+    for (u32 a = 0; a < ctx->inv_attempts_made && a < INV_REPORT_MAX && (u64)(a + 1) * INV_REPORT_WORDS <= cap_words; a++, copied++)
+        memcpy(out + (size_t)a * INV_REPORT_WORDS, ctx->inv_report[a], INV_REPORT_WORDS * sizeof(u64));
+    return copied;
+}
+
+// what the doubling sorts of the most recent forward call on this context did: no device, the records are host memory
+extern "C" int bwts_debug_forward_report(bwts_ctx *ctx, uint64_t *out, uint64_t cap_words, uint64_t *sorts)
+{
+    static_assert(FWD_HEADER_WORDS == BWTS_FWD_HEADER_WORDS && FWD_ROUND_WORDS == BWTS_FWD_ROUND_WORDS, "the record layout bwts_test.h states");
+    if (!ctx || !sorts || (!out && cap_words)) return BWTS_E_ARG;
+    *sorts = ctx->fwd_sorts_made;
+    int copied = 0;
+    for (u32 a = 0; a < ctx->fwd_sorts_made && a < FWD_REPORT_SORTS && (u64)(a + 1) * FWD_SORT_WORDS <= cap_words; a++, copied++)
+        memcpy(out + (size_t)a * FWD_SORT_WORDS, ctx->fwd_report[a], FWD_SORT_WORDS * sizeof(u64));
+    return copied;
+}
+
+extern "C" int bwts_debug_suffix_array(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint32_t *h_sa)
+{
+    if (!ctx || !in || !h_sa || n == 0) return BWTS_E_ARG;
+    HIPC(hipSetDevice(ctx->device));
+    spans_reset(ctx);
+    u8 *d_T = nullptr;
+    BWTS_TRY(upload_text(ctx, in, n, &d_T));
+    int rc = arena_reserve(ctx, forward_arena_bytes(n));
+    u32 *sa = nullptr, *rank = nullptr, rounds = 0;
+    if (rc == BWTS_OK) rc = suffix_sort_device(ctx, d_T, n, &sa, &rank, &rounds);
+    if (rc == BWTS_OK && hipMemcpyAsync(h_sa, sa, n * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = BWTS_E_HIP;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == BWTS_OK) rc = BWTS_E_HIP;
+    (void)hipFree(d_T);
+    return rc;
+}
+
+extern "C" int bwts_debug_lyndon(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint64_t *h_starts, uint64_t cap, uint64_t *count)
+{
+    if (!ctx || !in || !h_starts || !count || n == 0) return BWTS_E_ARG;
+    HIPC(hipSetDevice(ctx->device));
+    spans_reset(ctx);
+    u8 *d_T = nullptr;
+    BWTS_TRY(upload_text(ctx, in, n, &d_T));
+    int rc = arena_reserve(ctx, forward_arena_bytes(n));
+    u32 *fstart = nullptr, rounds = 0;
+    u64 k = 0;
+    if (rc == BWTS_OK) rc = lyndon_factors_device(ctx, d_T, n, &fstart, &k, &rounds);
+    if (rc == BWTS_OK) {
+        const u64 take = k < cap ? k : cap;
+        u32 *tmp = (u32 *)malloc((size_t)(take ? take : 1) * 4);
+        if (!tmp) rc = BWTS_E_NOMEM;
+        else {
+            // on the context's stream: it is non-blocking, so the null stream would not wait for the factor list's last copy
+            if (hipMemcpyAsync(tmp, fstart, take * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                hipStreamSynchronize(ctx->stream) != hipSuccess) rc = BWTS_E_HIP;
+            for (u64 i = 0; i < take; i++) h_starts[i] = tmp[i];
+            free(tmp);
+        }
+        *count = k;
+    }
+    (void)hipFree(d_T);
+    return rc;
+}

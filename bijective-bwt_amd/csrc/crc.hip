@@ -257,13 +257,10 @@ int crc_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, bool segments, u32 *crcs)
         crc_fold_kernel<<<dim3(1), dim3(256), 0, ctx->stream>>>(vals, nvals, nullptr, nvals, 1, nullptr, n, 1, b.out);
     }
     HIPC(hipGetLastError());
-    // the values come back through pinned memory: the small block, or for segments the staging of the segment table behind its tables
+    // the values come back through pinned memory: the small block, or for segments the read-back region behind the segment table,
+    // which begins where the upload of `first` ends (seg_layout.h)
     u32 *h = (u32 *)(ctx->h_small + SM_CRC_OUT);
-    if (segments) {
-        const u64 at = 2 * (count + 1);
-        if ((at + (count + 1) / 2) * sizeof(u64) > ctx->h_seg_cap) return BWTS_E_INTERNAL;
-        h = (u32 *)(ctx->h_seg_off + at);
-    }
+    if (segments) BWTS_TRY(seg_pinned_region(ctx, seg_readback_at(count), seg_readback_words(count), (void **)&h));
     HIPC(hipMemcpyAsync(h, b.out, count * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
     memcpy(crcs, h, count * sizeof(u32));

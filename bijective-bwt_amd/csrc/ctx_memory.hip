@@ -1,8 +1,9 @@
-// ctx_memory.hip -- every byte of device memory a context owns: guarded allocation, the kept blocks, the arena, the side blocks.
+// ctx_memory.hip -- every byte of device memory a context owns: guarded allocation, kept blocks, arena, side blocks, the segment table and its pinned copy.
 #include "internal.h"
 
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 // BWTS_POISON=1 (a test switch): every block handed to a transform is filled with 0xA5 first, so that a kernel which reads memory
 // nothing has written yet does so reproducibly -- whatever an earlier call or process left there -- instead of once in a blue moon
@@ -138,6 +139,68 @@ size_t ctx_device_bytes(const bwts_ctx *ctx)
     size_t sum = ctx->call_block_bytes + ctx->tied_blk.size() * ((size_t)16 << ctx->tied_blk_lg);
     for (const KeptBlock &b : ctx->kept) sum += b.cap;
     return sum;
+}
+
+// ------------------------------------------------------------------------------------
+// the segment table and its pinned copy (layout: seg_layout.h), the segment scratch
+// ------------------------------------------------------------------------------------
+int seg_table_set(bwts_ctx *ctx, const uint64_t *lengths, uint64_t count, u64 *total)
+{
+    if (!ctx || !lengths || count == 0) return BWTS_E_ARG;
+    u64 sum = 0;
+    for (u64 s = 0; s < count; s++) {
+        if (lengths[s] == 0 || lengths[s] > ~0ull - sum) return BWTS_E_ARG;
+        sum += lengths[s];
+    }
+    if (sum > NARROW_N) return BWTS_E_RANGE;
+    HIPC(hipSetDevice(ctx->device));
+    ctx->seg_off.resize(count + 1);
+    ctx->seg_off[0] = 0;
+    for (u64 s = 0; s < count; s++) ctx->seg_off[s + 1] = ctx->seg_off[s] + lengths[s];
+    const size_t bytes = seg_offset_words(count) * sizeof(u64), room = seg_room_bytes(count);
+    BWTS_TRY(kept_grow(ctx, ctx->kept[KB_SEG_TABLE], room, 1 << 16, -1));
+    // the table travels from a pinned block on the context's stream, ahead of the transform (the stream is idle between calls: the wait
+    // only makes sure no earlier copy still reads the block)
+    HIPC(hipStreamSynchronize(ctx->stream));
+    if (room > ctx->h_seg_cap) {
+        if (ctx->h_seg_off) { HIPC(hipHostFree(ctx->h_seg_off)); ctx->h_seg_off = nullptr; ctx->h_seg_cap = 0; }
+        void *p = nullptr;
+        if (hipHostMalloc(&p, room, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return BWTS_E_NOMEM; }
+        ctx->h_seg_off = (u64 *)p;
+        ctx->h_seg_cap = room;
+    }
+    memcpy(ctx->h_seg_off, ctx->seg_off.data(), bytes);
+    HIPC(hipMemcpyAsync(d_seg_off(ctx), ctx->h_seg_off, bytes, hipMemcpyHostToDevice, ctx->stream));
+    *total = sum;
+    return BWTS_OK;
+}
+
+void seg_pinned_free(bwts_ctx *ctx) { if (ctx->h_seg_off) (void)hipHostFree(ctx->h_seg_off); }      // (bwts_ctx_destroy)
+
+// `words` u64 from word `at` of the pinned copy (a region of seg_layout.h), for the host to read or write
+int seg_pinned_region(bwts_ctx *ctx, u64 at, u64 words, void **p)
+{
+    if ((at + words) * sizeof(u64) > ctx->h_seg_cap) return BWTS_E_INTERNAL;
+    *p = ctx->h_seg_off + at;
+    return BWTS_OK;
+}
+
+int seg_upload_extra(bwts_ctx *ctx, const u64 *words, u64 count, u64 **d_words)
+{
+    const u64 at = seg_upload_at(ctx->seg_off.size() - 1);
+    void *h = nullptr;
+    if ((at + count) * sizeof(u64) > ctx->kept[KB_SEG_TABLE].cap || seg_pinned_region(ctx, at, count, &h) != BWTS_OK) return BWTS_E_INTERNAL;
+    memcpy(h, words, count * sizeof(u64));
+    HIPC(hipMemcpyAsync(d_seg_off(ctx) + at, h, count * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    *d_words = d_seg_off(ctx) + at;
+    return BWTS_OK;
+}
+
+int seg_scratch_reserve(bwts_ctx *ctx, size_t bytes, u8 **out)
+{
+    BWTS_TRY(kept_grow(ctx, ctx->kept[KB_SEG_SCRATCH], bytes, 1 << 20, -1));
+    *out = (u8 *)ctx->kept[KB_SEG_SCRATCH].p;
+    return BWTS_OK;
 }
 
 static int poison(bwts_ctx *ctx, const KeptBlock &b)

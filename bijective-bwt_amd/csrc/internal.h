@@ -7,12 +7,10 @@
 #include <assert.h>
 #include <string>
 #include <vector>
-#include <condition_variable>
-#include <mutex>
-#include <thread>
-#include <atomic>
+#include <functional>
 
 #include "../../include/bwts.h"
+#include "seg_layout.h"
 
 typedef uint64_t u64;
 typedef uint32_t u32;
@@ -24,32 +22,7 @@ struct TimedSpan {
     hipEvent_t a, b;
 };
 
-// Host-side copy workers for the host-buffer entry points: a chunk is cut into page-aligned parts and every worker (and the
-// caller) memcpy's one.  One thread moves ~10 GB/s into or out of pinned staging -- and pays every first-touch page fault
-// of a fresh output buffer alone -- which is below what the PCIe link carries.
-struct CopyPool {
-    std::vector<std::thread> workers;
-    std::mutex mu;
-    std::condition_variable cv_work, cv_done;
-    u64 generation = 0;
-    int pending = 0;
-    bool stop = false;
-    char *dst = nullptr;
-    const char *src = nullptr;
-    size_t len = 0;
-    int parts = 1;
-    bool touching = false;  // the current job pre-faults the pages of dst (madvise, contents untouched) instead of copying
-    std::atomic<bool> touch_failed{false};
-    void start(int threads);
-    void copy(void *dst, const void *src, size_t len);      // returns when all parts are done
-    // The workers alone fault in the pages of a fresh buffer (MADV_POPULATE_WRITE: mapped writable, contents as they were) while
-    // the caller goes on: the first-touch faults of a caller's output buffer are paid while the GPU transforms.  wait() before the
-    // next job.
-    void touch_async(void *dst, size_t len);
-    void wait();
-    void shutdown();
-    void part(int i);
-};
+struct CopyPool;                 // the copy workers of a staging ring (copy_pool.h)
 
 #define INV_REPORT_MAX 8         // (the narrow inverse's fallback chain has at most five attempts, the wide one four)
 #define INV_REPORT_WORDS 16
@@ -153,7 +126,7 @@ struct bwts_ctx {
 
     // segment table of the current segmented call: offsets on the host (count + 1); their device copy is d_seg_off(ctx)
     std::vector<u64> seg_off;
-    u64 *h_seg_off = nullptr;           // pinned staging of the table
+    u64 *h_seg_off = nullptr;           // pinned copy of the table and what lies behind it: ctx_memory.hip alone reads these two
     size_t h_seg_cap = 0;
     // inverse: what the most recent segmented inverse did (bwts_debug_segments_report; include/bwts_test.h names the words)
     u64 seg_report[SEG_REPORT_WORDS] = {0};
@@ -187,6 +160,42 @@ const char *bwts_knob(const bwts_ctx *ctx, const char *name);    // value of an 
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 double wall_ms(void);
+#define NARROW_N 0x100000000ull  // the narrow limit: up to this many positions an index is 32 bits wide (host code; kernels spell it out)
+// do [a, a + na) and [b, b + nb) share a byte?  By subtraction: a length as large as 2^64 - 1 must not wrap the comparison
+static inline bool ranges_overlap(const void *a, u64 na, const void *b, u64 nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x <= y ? y - x < na : x - y < nb;
+}
+
+// ---- the call bracket and the transform table (api.hip) ---------------------------
+// One of the eight transforms that map n bytes to n bytes.  name: what a call is called in the guard report; in_label: its input in
+// the allocation trace; arena_hint: what the host path reserves ahead of the call (0: the call's own reservation decides).
+struct Transform {
+    int (*fn)(bwts_ctx *, const u8 *, u64, u8 *);
+    const char *name, *in_label;
+    size_t (*arena_hint)(const bwts_ctx *ctx, u64 n);
+};
+int run_device(bwts_ctx *ctx, const Transform &t, const void *d_in, u64 n, void *d_out);    // the bracket around one row's device form
+// the first launch of a context is this kernel with nothing to copy: it loads the library's code object outside the timing
+__global__ void pcie_copy_kernel(uint4 *__restrict__ dst, const uint4 *__restrict__ src, u64 vecs, u8 *__restrict__ dst_tail, const u8 *__restrict__ src_tail, u32 tail);
+
+// ---- between caller memory and HBM (staging.hip) -----------------------------------
+// One host call: `in` to the device, the device form, what it made back to `out` (or to `sink`, piece by piece), the copy times
+// booked in h2d_ms / d2h_ms.  Nothing reaches out, sink or *out_bytes unless the device form succeeded.
+struct HostTrip {
+    const u8 *in; u64 in_bytes;
+    u64 io_bytes;                           // room in the device-side input and output buffer
+    u8 *out; u64 *out_bytes;
+    bwts_sink_fn sink = nullptr; void *user = nullptr;
+    // the n -> n transforms only (out is in_bytes long): the arena reserved ahead of the call where the rules in staging.hip allow
+    // it, the pages of a fresh `out` faulted in while the device works, and the call's two lines in the allocation trace
+    const Transform *ahead = nullptr;
+};
+// device_form(d_in, d_out, &bytes): the public _device entry point, which says how many bytes it made
+int host_round_trip(bwts_ctx *ctx, const HostTrip &trip, const std::function<int(const u8 *, u8 *, u64 *)> &device_form);
+int run_batch(bwts_ctx *ctx, const Transform &t, int count, const uint8_t *const *ins, const uint64_t *ns, uint8_t *const *outs);
+void staging_destroy(bwts_ctx *ctx);        // bwts_ctx_destroy: workers, pinned slots, events and queues of the three stagers
 
 // ---- the context's device memory (ctx_memory.hip) -------------------------------
 hipError_t ctx_malloc(bwts_ctx *ctx, void **out, size_t bytes, const char *name);   // with guard bands under BWTS_GUARD
@@ -202,6 +211,12 @@ size_t ctx_device_bytes(const bwts_ctx *ctx);           // what the context hold
 int  tied_release(bwts_ctx *ctx);                       // the wide forward's tied-list blocks (wide_path.h): drains, then frees
 static inline u8 *d_io(const bwts_ctx *ctx, int i) { return (u8 *)ctx->kept[KB_IO + i].p; }
 static inline u64 *d_seg_off(const bwts_ctx *ctx) { return (u64 *)ctx->kept[KB_SEG_TABLE].p; }
+// the segment table, and the regions behind it in its pinned copy (seg_layout.h); a region the block has no room for: BWTS_E_INTERNAL
+int  seg_table_set(bwts_ctx *ctx, const uint64_t *lengths, uint64_t count, u64 *total);     // the segment table of the calls that follow
+int  seg_upload_extra(bwts_ctx *ctx, const u64 *words, u64 count, u64 **d_words);   // a second table, behind the segment table
+int  seg_pinned_region(bwts_ctx *ctx, u64 at, u64 words, void **p);                 // a region behind the table, in the pinned copy, with its capacity check
+void seg_pinned_free(bwts_ctx *ctx);
+int  seg_scratch_reserve(bwts_ctx *ctx, size_t bytes, u8 **p);     // a device block that stays with the context, grown on demand
 
 // ---- arena -------------------------------------------------------------------
 int  arena_reserve(bwts_ctx *ctx, size_t bytes);        // (re)allocates when too small; resets
@@ -277,8 +292,6 @@ int forward_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
 // d_off: count + 1 device words, d_off[0] = 0, d_off[count] = n; flag: n bytes of factor-start flags (forward)
 struct SegTable { const u64 *d_off; u64 count; u8 *flag; };
 #define SEG_FWD_BIG (1ull << 21)     // forward: segments of this length or more are transformed alone
-int seg_scratch_reserve(bwts_ctx *ctx, size_t bytes, u8 **p);     // a device block that stays with the context, grown on demand
-int seg_upload_extra(bwts_ctx *ctx, const u64 *words, u64 count, u64 **d_words);   // a second table, behind the segment table
 int forward_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
 int inverse_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
 size_t inverse_segments_arena_bytes(const bwts_ctx *ctx, u64 n);   // for the context's current segment table, by the plan the call will take
@@ -310,7 +323,6 @@ void bwts_ec_plan(u64 n, u64 out[5]);                                   // tile 
 // one input of n bytes, or the segments of the context's table: one value each, to the host
 int crc_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, bool segments, u32 *crcs);
 void bwts_crc_plan(u64 n, u64 out[4]);                                  // tile size, tiles per fold group, tiles and groups of one input
-int seg_table_set(bwts_ctx *ctx, const uint64_t *lengths, uint64_t count, u64 *total);     // the segment table of the calls that follow (api.hip)
 int pack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes);
 int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out);
 

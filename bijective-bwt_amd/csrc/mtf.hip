@@ -441,7 +441,7 @@ static int mtf_scan(bwts_ctx *ctx, const MtfBufs &b, const MtfPlan &p)
 static int mtf_run(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool inverse, bool segments)
 {
     if (n > MTF_MAX_N) return BWTS_E_RANGE;
-    if (d_in < d_out + n && d_out < d_in + n) return BWTS_E_ARG;
+    if (ranges_overlap(d_in, n, d_out, n)) return BWTS_E_ARG;
     const bool table = segments && ctx->seg_off.size() > 2;
     const MtfPlan p = mtf_plan_tiles(mtf_call_tiles(ctx, n, segments));
     if (p.groups > 0x7fffffffull) return BWTS_E_RANGE;

@@ -5,8 +5,8 @@
 // A frame of one block goes through the single-input stages, one of several blocks through the segment forms (the bytes are the
 // same by the segment forms' contract).  The stages share the context's arena, and the segment forms the pinned staging of their
 // tables: the stream is drained between two stages, so that no table copy of the stage before is still to come when the next stage
-// writes its own.  Header and directory travel through pinned memory too: the small block, and for several blocks the staging
-// behind the segment table.
+// writes its own (seg_layout.h: the regions, and who overlaps whom).  Header and directory travel through pinned memory too: the
+// small block, and for several blocks the directory region behind the segment table.
 #include "internal.h"
 #include "pack_plan.h"
 #include "../../include/bwts_pack.h"
@@ -34,13 +34,11 @@ static int pack_blocks_set(bwts_ctx *ctx, u64 n, u64 B, u64 nblk)
     return total == n ? BWTS_OK : BWTS_E_INTERNAL;
 }
 
-// pinned room for a directory of nblk entries: the small block behind the header, or the staging behind the segment table
+// pinned room for a directory of nblk entries: the small block behind the header, or the directory region behind the segment table
 static int pack_dir_staging(bwts_ctx *ctx, u64 nblk, u8 **dir)
 {
     if (nblk == 1) { *dir = (u8 *)(ctx->h_small + SM_PACK_HEAD) + PACK_HEADER_BYTES; return BWTS_OK; }
-    if ((3 * nblk + 1) * sizeof(u64) > ctx->h_seg_cap) return BWTS_E_INTERNAL;
-    *dir = (u8 *)(ctx->h_seg_off + nblk + 1);
-    return BWTS_OK;
+    return seg_pinned_region(ctx, seg_dir_at(nblk), seg_dir_words(nblk), (void **)dir);
 }
 
 int pack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes)

@@ -211,10 +211,15 @@ static const Transform kInverse = {inverse_device_impl, "inverse", "inverse: in"
 static const Transform kForwardSegments = {forward_segments_impl, "forward", "forward: in", kForward.arena_hint};
 static const Transform kInverseSegments = {inverse_segments_impl, "inverse", "inverse: in",
                                            [](const bwts_ctx *ctx, u64 n) { return n <= NARROW_N ? inverse_segments_arena_bytes(ctx, n) : 0; }};
-static const Transform kMtfForward = {mtf_forward_impl, "mtf forward", "mtf: in", [](const bwts_ctx *ctx, u64 n) { return mtf_arena_bytes(ctx, n, false); }};
-static const Transform kMtfInverse = {mtf_inverse_impl, "mtf inverse", "mtf: in", kMtfForward.arena_hint};
-static const Transform kMtfForwardSegments = {mtf_forward_segments_impl, "mtf forward", "mtf: in", [](const bwts_ctx *ctx, u64 n) { return mtf_arena_bytes(ctx, n, true); }};
-static const Transform kMtfInverseSegments = {mtf_inverse_segments_impl, "mtf inverse", "mtf: in", kMtfForwardSegments.arena_hint};
+// (move-to-front is one function: its four rows say which direction, and whether the context's table is meant)
+static const Transform kMtfForward = {[](bwts_ctx *ctx, const u8 *in, u64 n, u8 *out) { return mtf_impl(ctx, in, n, out, false, SEG_SINGLE); }, "mtf forward", "mtf: in",
+                                      [](const bwts_ctx *ctx, u64 n) { return mtf_arena_bytes(ctx, n, SEG_SINGLE); }};
+static const Transform kMtfInverse = {[](bwts_ctx *ctx, const u8 *in, u64 n, u8 *out) { return mtf_impl(ctx, in, n, out, true, SEG_SINGLE); }, "mtf inverse", "mtf: in",
+                                      kMtfForward.arena_hint};
+static const Transform kMtfForwardSegments = {[](bwts_ctx *ctx, const u8 *in, u64 n, u8 *out) { return mtf_impl(ctx, in, n, out, false, seg_mode(ctx)); }, "mtf forward",
+                                              "mtf: in", [](const bwts_ctx *ctx, u64 n) { return mtf_arena_bytes(ctx, n, seg_mode(ctx)); }};
+static const Transform kMtfInverseSegments = {[](bwts_ctx *ctx, const u8 *in, u64 n, u8 *out) { return mtf_impl(ctx, in, n, out, true, seg_mode(ctx)); }, "mtf inverse",
+                                              "mtf: in", kMtfForwardSegments.arena_hint};
 
 // The bracket around every device call: code object loaded outside the timing, spans, guard check, total_ms, device_bytes.  What the
 // body needs beyond the context travels in its closure.  n: the uncoded bytes, where the caller knows them already.
@@ -427,7 +432,7 @@ extern "C" int bwts_ec_encode_device(bwts_ctx *ctx, const void *d_in, uint64_t n
     if (!ctx || !d_in || !d_out || !out_bytes || n == 0 || ((uintptr_t)d_out & 15)) return BWTS_E_ARG;
     if (n > EC_MAX_N) return BWTS_E_RANGE;
     if (ranges_overlap(d_in, n, d_out, out_cap)) return BWTS_E_ARG;
-    return run_sized(ctx, n, "ec encode", [&] { return ec_encode_impl(ctx, (const u8 *)d_in, n, (u8 *)d_out, out_cap, out_bytes, nullptr); });
+    return run_sized(ctx, n, "ec encode", [&] { return ec_encode_impl(ctx, (const u8 *)d_in, n, (u8 *)d_out, out_cap, SEG_SINGLE, out_bytes); });
 }
 
 extern "C" int bwts_ec_decode_device(bwts_ctx *ctx, const void *d_in, uint64_t in_bytes, void *d_out, uint64_t out_cap, uint64_t *n)
@@ -435,7 +440,7 @@ extern "C" int bwts_ec_decode_device(bwts_ctx *ctx, const void *d_in, uint64_t i
     if (!ctx || !d_in || !d_out || !n || in_bytes == 0 || ((uintptr_t)d_in & 15)) return BWTS_E_ARG;
     if (in_bytes > ec_bound_bytes(EC_MAX_N)) return BWTS_E_RANGE;
     if (ranges_overlap(d_in, in_bytes, d_out, out_cap)) return BWTS_E_ARG;
-    return run_sized(ctx, 0, "ec decode", [&] { return ec_decode_impl(ctx, (const u8 *)d_in, in_bytes, (u8 *)d_out, out_cap, n, nullptr); });
+    return run_sized(ctx, 0, "ec decode", [&] { return ec_decode_impl(ctx, (const u8 *)d_in, in_bytes, (u8 *)d_out, out_cap, n, SEG_SINGLE, nullptr); });
 }
 
 extern "C" int bwts_ec_encode_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out, uint64_t out_cap,
@@ -445,7 +450,7 @@ extern "C" int bwts_ec_encode_segments_device(bwts_ctx *ctx, const void *d_in, c
     u64 n = 0;
     BWTS_TRY(seg_table_set(ctx, lengths, count, &n));
     if (ranges_overlap(d_in, n, d_out, out_cap)) return BWTS_E_ARG;
-    return run_sized(ctx, n, "ec encode", [&] { return ec_encode_impl(ctx, (const u8 *)d_in, n, (u8 *)d_out, out_cap, nullptr, stream_bytes); });
+    return run_sized(ctx, n, "ec encode", [&] { return ec_encode_impl(ctx, (const u8 *)d_in, n, (u8 *)d_out, out_cap, seg_mode(ctx), stream_bytes); });
 }
 
 extern "C" int bwts_ec_decode_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *stream_bytes, const uint64_t *lengths, uint64_t count,
@@ -459,7 +464,7 @@ extern "C" int bwts_ec_decode_segments_device(bwts_ctx *ctx, const void *d_in, c
         in_bytes += stream_bytes[s];
     }
     if (ranges_overlap(d_in, in_bytes, d_out, n)) return BWTS_E_ARG;
-    return run_sized(ctx, n, "ec decode", [&] { return ec_decode_impl(ctx, (const u8 *)d_in, n, (u8 *)d_out, n, nullptr, stream_bytes); });
+    return run_sized(ctx, n, "ec decode", [&] { return ec_decode_impl(ctx, (const u8 *)d_in, n, (u8 *)d_out, n, nullptr, seg_mode(ctx), stream_bytes); });
 }
 
 // Host buffers: the checks that need no device, then one host_round_trip around the device form.
@@ -492,7 +497,7 @@ extern "C" int bwts_crc32_device(bwts_ctx *ctx, const void *d_in, uint64_t n, ui
 {
     if (!ctx || !d_in || !crc || n == 0) return BWTS_E_ARG;
     if (n > CRC_MAX_N) return BWTS_E_RANGE;
-    return run_sized(ctx, n, "crc32", [&] { return crc_impl(ctx, (const u8 *)d_in, n, false, crc); });
+    return run_sized(ctx, n, "crc32", [&] { return crc_impl(ctx, (const u8 *)d_in, n, SEG_SINGLE, crc); });
 }
 
 extern "C" int bwts_crc32_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, uint32_t *crcs)
@@ -500,7 +505,7 @@ extern "C" int bwts_crc32_segments_device(bwts_ctx *ctx, const void *d_in, const
     if (!ctx || !d_in || !crcs) return BWTS_E_ARG;
     u64 n = 0;
     BWTS_TRY(seg_table_set(ctx, lengths, count, &n));
-    return run_sized(ctx, n, "crc32", [&] { return crc_impl(ctx, (const u8 *)d_in, n, true, crcs); });
+    return run_sized(ctx, n, "crc32", [&] { return crc_impl(ctx, (const u8 *)d_in, n, seg_mode(ctx), crcs); });
 }
 
 extern "C" uint64_t bwts_pack_bound(uint64_t n, uint64_t block_bytes)

@@ -64,13 +64,6 @@ __device__ __forceinline__ u32 crc_xpow8_wave(u64 bytes, int lane)
     return (u32)__builtin_amdgcn_readfirstlane((int)f);
 }
 
-__device__ __forceinline__ u32 crc_wave_xor(u32 v)
-{
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v ^= (u32)__shfl_xor((int)v, d, 64);
-    return v;
-}
-
 // one piece into a lane's register
 __device__ __forceinline__ u32 crc_absorb(const u32 *__restrict__ slice, u32 st, uint4 q)
 {
@@ -95,15 +88,14 @@ __device__ __forceinline__ uint4 crc_piece(const u8 *__restrict__ base, u32 j, u
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// tseg of a segmented call: one wave per segment writes the segment's number over its tiles
-__global__ __launch_bounds__(256) void crc_tile_table_kernel(const u64 *__restrict__ seg_off, const u64 *__restrict__ first, u64 count, u32 *__restrict__ tseg)
-{
-    const u64 lane = (u64)lane_id();
-    for (u64 s = (u64)blockIdx.x * 4 + (u64)wave_id(); s < count; s += (u64)gridDim.x * 4) {
-        const u64 f = first[s], nt = first[s + 1] - f;
-        for (u64 j = lane; j < nt; j += 64) tseg[f + j] = (u32)s;
-    }
-}
+// tseg of a segmented call (unit_table_kernel): the segment's number over its tiles
+struct CrcTileTable {
+    const u64 *first_tile;
+    u32 *tseg;
+    __device__ u64 first(u64 s) const { return first_tile[s]; }
+    __device__ u64 units(u64 s) const { return first_tile[s + 1] - first_tile[s]; }
+    __device__ void store(u64 s, u64 first, u64, u64 j) const { tseg[first + j] = (u32)s; }
+};
 
 // every tile's register, moved to the end of its segment.  seg_off == null: one input of n bytes.  (Left alone the compiler takes 89
 // VGPRs for the four pieces in flight and their lookups: five waves per SIMD; held to eight it needs 62 and no scratch.)
@@ -155,7 +147,7 @@ void crc_tile_kernel(const u8 *__restrict__ in, const u64 *__restrict__ seg_off,
         const u32 last = any ? (u32)lane + 64u * ((np - 1u - (u32)lane) >> 6) : 0u;
         const u32 back = any ? 16u * last + CRC_ROW - 16u * np + z : 0u;
         u32 v = crc_mul(st, g_crc_tab[CRC_TAB_BACK + back]);
-        v = crc_wave_xor(any ? v : 0u);
+        v = wave_reduce(any ? v : 0u, OpXor());
         const u64 behind = seg_end - end;
         if (behind) v = crc_mul(v, crc_xpow8_wave(behind, lane));
         if (lane == 0) tilecrc[t] = v;
@@ -175,7 +167,7 @@ __global__ __launch_bounds__(256) void crc_fold_kernel(const u32 *__restrict__ v
         if (b > count_vals) b = count_vals;
         u32 x = 0;
         for (u64 i = a + (u64)lane; i < b; i += 64) x ^= vals[i];
-        x = crc_wave_xor(x);
+        x = wave_reduce(x, OpXor());
         if (finish) {
             const u64 len = seg_off ? seg_off[r + 1] - seg_off[r] : n;
             x ^= crc_mul(0xFFFFFFFFu, crc_xpow8_wave(len, lane)) ^ 0xFFFFFFFFu;
@@ -189,7 +181,8 @@ __global__ __launch_bounds__(256) void crc_fold_kernel(const u32 *__restrict__ v
 // ------------------------------------------------------------------------------------
 void bwts_crc_plan(u64 n, u64 out[4])
 {
-    out[0] = CRC_T; out[1] = CRC_G; out[2] = crc_tiles(n); out[3] = crc_groups(crc_tiles(n));
+    const u64 tiles = stage_cut_single(n, CRC_T).units[0];
+    out[0] = CRC_T; out[1] = CRC_G; out[2] = tiles; out[3] = crc_groups(tiles);
 }
 
 struct CrcBufs {
@@ -202,28 +195,16 @@ struct CrcBufs {
     }
 };
 
-static unsigned crc_grid(u64 waves) { const u64 wgs = (waves + 3) / 4; return (unsigned)(wgs < 2048 ? wgs : 2048); }      // (eight workgroups a CU)
-
 // crcs: one word (one input of n bytes) or one per segment of the context's table, on the host
-int crc_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, bool segments, u32 *crcs)
+int crc_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, SegMode segs, u32 *crcs)
 {
-    const u64 count = segments ? (u64)ctx->seg_off.size() - 1 : 1;
-    std::vector<u64> first;
-    u64 tiles = 0;
-    if (segments) {
-        first.resize((size_t)count + 1);
-        for (u64 s = 0; s < count; s++) { first[s] = tiles; tiles += crc_tiles(ctx->seg_off[s + 1] - ctx->seg_off[s]); }
-        first[count] = tiles;
-    } else {
-        tiles = crc_tiles(n);
-    }
+    const StageCut cut = stage_cut_call(ctx, segs, n, CRC_T);
+    const u64 count = cut.count, tiles = cut.units[0];
+    const bool segments = segs.table();
     CrcBufs b;
     BlockLayout L;
     b.declare(L, tiles, count, segments);
-    BWTS_TRY(arena_reserve(ctx, L.bytes()));
-    char *base = (char *)arena_alloc(ctx, L.bytes());
-    if (!base) return BWTS_E_NOMEM;
-    L.place(base);
+    BWTS_TRY(arena_take(ctx, L));
     if (!ctx->crc_tables) {
         SpanGuard sp(ctx, BWTS_K_OTHER, CRC_TAB_WORDS, 4 * CRC_TAB_WORDS);
         crc_tables_kernel<<<dim3((CRC_TAB_WORDS + 255) / 256), dim3(256), 0, ctx->stream>>>();
@@ -232,25 +213,25 @@ int crc_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, bool segments, u32 *crcs)
     const u64 *d_first = nullptr;
     if (segments) {
         u64 *d_words = nullptr;
-        BWTS_TRY(seg_upload_extra(ctx, first.data(), count + 1, &d_words));
+        BWTS_TRY(seg_upload_extra(ctx, cut.first[0].data(), count + 1, &d_words));
         d_first = d_words;
         SpanGuard sp(ctx, BWTS_K_OTHER, tiles, 4 * tiles);
-        crc_tile_table_kernel<<<dim3(crc_grid(count)), dim3(256), 0, ctx->stream>>>(d_seg_off(ctx), d_first, count, b.tseg);
+        unit_table_launch(ctx->stream, count, CrcTileTable{d_first, b.tseg});
     }
     {
         SpanGuard sp(ctx, BWTS_K_OTHER, n, n);
-        crc_tile_kernel<<<dim3(crc_grid(tiles)), dim3(256), 0, ctx->stream>>>(d_in, segments ? d_seg_off(ctx) : nullptr, d_first, b.tseg, n, tiles, b.tilecrc);
+        crc_tile_kernel<<<dim3(wave_grid(tiles)), dim3(256), 0, ctx->stream>>>(d_in, segments ? d_seg_off(ctx) : nullptr, d_first, b.tseg, n, tiles, b.tilecrc);
     }
     if (segments) {
         SpanGuard sp(ctx, BWTS_K_OTHER, tiles, 4 * tiles + 4 * count);
-        crc_fold_kernel<<<dim3(crc_grid(count)), dim3(256), 0, ctx->stream>>>(b.tilecrc, tiles, d_first, 0, count, d_seg_off(ctx), n, 1, b.out);
+        crc_fold_kernel<<<dim3(wave_grid(count)), dim3(256), 0, ctx->stream>>>(b.tilecrc, tiles, d_first, 0, count, d_seg_off(ctx), n, 1, b.out);
     } else {
         const u32 *vals = b.tilecrc;
         u64 nvals = tiles;
         if (tiles > CRC_G) {
             SpanGuard sp(ctx, BWTS_K_OTHER, tiles, 4 * tiles);
             nvals = crc_groups(tiles);
-            crc_fold_kernel<<<dim3(crc_grid(nvals)), dim3(256), 0, ctx->stream>>>(b.tilecrc, tiles, nullptr, CRC_G, nvals, nullptr, n, 0, b.gvals);
+            crc_fold_kernel<<<dim3(wave_grid(nvals)), dim3(256), 0, ctx->stream>>>(b.tilecrc, tiles, nullptr, CRC_G, nvals, nullptr, n, 0, b.gvals);
             vals = b.gvals;
         }
         SpanGuard sp(ctx, BWTS_K_OTHER, nvals, 4 * nvals);
@@ -258,7 +239,7 @@ int crc_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, bool segments, u32 *crcs)
     }
     HIPC(hipGetLastError());
     // the values come back through pinned memory: the small block, or for segments the read-back region behind the segment table,
-    // which begins where the upload of `first` ends (seg_layout.h)
+    // which begins where the upload of the cut's first tiles ends (seg_layout.h)
     u32 *h = (u32 *)(ctx->h_small + SM_CRC_OUT);
     if (segments) BWTS_TRY(seg_pinned_region(ctx, seg_readback_at(count), seg_readback_words(count), (void **)&h));
     HIPC(hipMemcpyAsync(h, b.out, count * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));

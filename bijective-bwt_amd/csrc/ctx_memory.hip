@@ -247,6 +247,16 @@ void *arena_alloc(bwts_ctx *ctx, size_t bytes)
     return p;
 }
 
+// the one block a call holds in the arena: reserved by its declared size, taken whole, every declared array pointed into it
+int arena_take(bwts_ctx *ctx, const BlockLayout &L)
+{
+    BWTS_TRY(arena_reserve(ctx, L.bytes()));
+    char *base = (char *)arena_alloc(ctx, L.bytes());
+    if (!base) return BWTS_E_NOMEM;
+    L.place(base);
+    return BWTS_OK;
+}
+
 int aux_reserve_slot(bwts_ctx *ctx, int slot, size_t bytes, char **base)
 {
     KeptBlock &b = ctx->kept[KB_AUX + slot];

@@ -21,6 +21,7 @@ __device__ __forceinline__ u64 lanemask_lt()
 struct OpAdd { template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; } };
 struct OpMax { template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a > b ? a : b; } };
 struct OpMin { template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a < b ? a : b; } };
+struct OpXor { template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a ^ b; } };
 
 __device__ __forceinline__ u32 shfl_up_t(u32 v, int d) { return (u32)__shfl_up((int)v, d, 64); }
 __device__ __forceinline__ u64 shfl_up_t(u64 v, int d)
@@ -54,6 +55,42 @@ __device__ __forceinline__ T wave_scan_inclusive(T v, Op op)
         if (lane >= d) v = op(o, v);
     }
     return v;
+}
+
+// op over the 64 lanes of a wave, the result in every lane (commutative op)
+template <typename Op>
+__device__ __forceinline__ u32 wave_reduce(u32 v, Op op)
+{
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v = op((u32)__shfl_xor((int)v, d, 64), v);
+    return v;
+}
+
+// The per-unit table of a segmented stage call (stage_cut.h: a unit is a tile or a block): one wave per segment, the lanes over
+// the segment's units.  f.first(s): the segment's first unit, counted over the call; f.units(s): how many it has; f.store(s, first,
+// units, j): writes what the stage keeps for the segment's unit j.
+template <typename F>
+__global__ __launch_bounds__(256) void unit_table_kernel(u64 count, F f)
+{
+    const u64 lane = (u64)lane_id();
+    for (u64 s = (u64)blockIdx.x * 4 + (u64)wave_id(); s < count; s += (u64)gridDim.x * 4) {
+        const u64 first = f.first(s), units = f.units(s);
+        for (u64 j = lane; j < units; j += 64) f.store(s, first, units, j);
+    }
+}
+
+// Workgroups of four waves for kernels that stride over their work by the grid, one wave an item: at most 2048, eight a CU.  (Of the
+// three caps the table launches had -- 2^30, 2^20 and this one -- the tightest: a strided kernel covers every count under any cap.)
+static inline unsigned wave_grid(u64 waves)
+{
+    const u64 wgs = (waves + 3) / 4;
+    return (unsigned)(wgs < 2048 ? wgs : 2048);
+}
+
+template <typename F>
+static inline void unit_table_launch(hipStream_t stream, u64 count, F f)
+{
+    unit_table_kernel<<<dim3(wave_grid(count)), dim3(256), 0, stream>>>(count, f);
 }
 
 // Workgroup-wide scan of one value per thread.  NWAVES = blockDim.x / 64.

@@ -50,32 +50,17 @@ __device__ __forceinline__ EcBlock ec_block(const EcSegs &S, u64 b)
 // lanes below mine among those of mask
 __device__ __forceinline__ u32 ec_rank_in(u64 mask) { return __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u)); }
 
-__device__ __forceinline__ u32 ec_wave_add(u32 v)
-{
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v += (u32)__shfl_xor((int)v, d, 64);
-    return v;
-}
-
-__device__ __forceinline__ u32 ec_wave_max(u32 v)
-{
-#pragma unroll
-    for (int d = 32; d; d >>= 1) { const u32 o = (u32)__shfl_xor((int)v, d, 64); v = o > v ? o : v; }
-    return v;
-}
-
 // ------------------------------------------------------------------------------------
 // tables
 // ------------------------------------------------------------------------------------
-// bseg of a segmented call: one wave per segment writes the segment's number over its blocks
-__global__ __launch_bounds__(256) void ec_block_table_kernel(const u64 *__restrict__ seg_off, const u64 *__restrict__ first, u64 count, u32 *__restrict__ bseg)
-{
-    const u64 lane = (u64)lane_id();
-    for (u64 s = (u64)blockIdx.x * 4 + (u64)wave_id(); s < count; s += (u64)gridDim.x * 4) {
-        const u64 nb = ec_blocks(ec_tiles(seg_off[s + 1] - seg_off[s])), fb = first[s] >> 32;
-        for (u64 j = lane; j < nb; j += 64) bseg[fb + j] = (u32)s;
-    }
-}
+// bseg of a segmented call (unit_table_kernel): the segment's number over its blocks
+struct EcBlockTable {
+    const u64 *seg_off, *first_words;
+    u32 *bseg;
+    __device__ u64 first(u64 s) const { return first_words[s] >> 32; }
+    __device__ u64 units(u64 s) const { return ec_blocks(ec_tiles(seg_off[s + 1] - seg_off[s])); }
+    __device__ void store(u64 s, u64 first, u64, u64 j) const { bseg[first + j] = (u32)s; }
+};
 
 // Byte counts of one block (256 KiB of one segment) per workgroup.  Ranks are mostly zeros: every thread adds a run's length when
 // the run ends, not one per byte, into its wave's own 256 counters.
@@ -125,14 +110,14 @@ __global__ __launch_bounds__(64) void ec_normalise_kernel(const u32 *__restrict_
     const u32 lane = (u32)lane_id();
     const uint4 hv = ((const uint4 *)(hist + b * 256))[lane];
     const u32 h[4] = {hv.x, hv.y, hv.z, hv.w};
-    const u32 m = ec_wave_add(h[0] + h[1] + h[2] + h[3]);        // at most 2^18: h << 12 fits 32 bits
+    const u32 m = wave_reduce(h[0] + h[1] + h[2] + h[3], OpAdd());      // at most 2^18: h << 12 fits 32 bits
     u32 f[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const u32 v = h[i] ? (h[i] << EC_PROB_BITS) / m : 0u;
         f[i] = h[i] && v == 0 ? 1u : v;
     }
-    int d = (int)EC_M - (int)ec_wave_add(f[0] + f[1] + f[2] + f[3]);
+    int d = (int)EC_M - (int)wave_reduce(f[0] + f[1] + f[2] + f[3], OpAdd());
     while (d != 0) {
         u32 key = 0;
 #pragma unroll
@@ -140,7 +125,7 @@ __global__ __launch_bounds__(64) void ec_normalise_kernel(const u32 *__restrict_
             const u32 k = f[i] << 8 | (255u - (4u * lane + (u32)i));
             key = k > key ? k : key;
         }
-        const u32 s = 255u - (ec_wave_max(key) & 255u);
+        const u32 s = 255u - (wave_reduce(key, OpMax()) & 255u);
         const int step = d > 0 ? d : -1;
 #pragma unroll
         for (int i = 0; i < 4; i++)
@@ -407,18 +392,20 @@ struct EcPlan {
     std::vector<u64> words;      // segmented: first[count], then base[count + 1]
 };
 
+// The cut at the coder's two units (a block of K tiles of one segment is the same cut at K T bytes), and the byte arithmetic over it.
 // base: encode: the fixed parts of the earlier segments; decode: the streams' starts (stream_bytes given)
-static int ec_plan_call(const bwts_ctx *ctx, u64 n, bool segments, const u64 *stream_bytes, EcPlan &p)
+static int ec_plan_call(const bwts_ctx *ctx, u64 n, SegMode segs, const u64 *stream_bytes, EcPlan &p)
 {
-    p.count = segments ? (u64)ctx->seg_off.size() - 1 : 1;
-    p.tiles = p.blocks = p.fixed = p.least = 0;
-    if (segments) p.words.resize((size_t)(2 * p.count + 1));
+    const StageCut cut = stage_cut_call(ctx, segs, n, EC_T, (u64)EC_T << EC_LOG_K);
+    const std::vector<u64> &tile = cut.first[0], &block = cut.first[1];
+    p.count = cut.count; p.tiles = cut.units[0]; p.blocks = cut.units[1];
+    p.fixed = p.least = 0;
+    if (segs.table()) p.words.resize((size_t)(2 * p.count + 1));
     u64 at = 0;
     for (u64 s = 0; s < p.count; s++) {
-        const u64 len = segments ? ctx->seg_off[s + 1] - ctx->seg_off[s] : n;
-        const u64 nt = ec_tiles(len);
-        if (segments) {
-            p.words[s] = p.tiles | p.blocks << 32;
+        const u64 len = segs.table() ? ctx->seg_off[s + 1] - ctx->seg_off[s] : n;
+        if (segs.table()) {
+            p.words[s] = tile[s] | block[s] << 32;
             p.words[p.count + s] = stream_bytes ? at : p.fixed;
         }
         if (stream_bytes) {
@@ -426,13 +413,11 @@ static int ec_plan_call(const bwts_ctx *ctx, u64 n, bool segments, const u64 *st
             if ((sb & 15) || sb < ec_least_bytes(len) || sb > ec_bound_bytes(len)) return BWTS_E_FORMAT;
             at += sb;
         }
-        p.tiles += nt;
-        p.blocks += ec_blocks(nt);
         p.fixed += ec_fixed_bytes(len);
         p.least += ec_least_bytes(len);
-        if (p.tiles >= (1ull << 31) || p.blocks >= (1ull << 29)) return BWTS_E_RANGE;
+        if (tile[s + 1] >= (1ull << 31) || block[s + 1] >= (1ull << 29)) return BWTS_E_RANGE;
     }
-    if (segments) p.words[2 * p.count] = stream_bytes ? at : p.fixed;
+    if (segs.table()) p.words[2 * p.count] = stream_bytes ? at : p.fixed;
     return BWTS_OK;
 }
 
@@ -453,7 +438,8 @@ struct EcBufs {
 
 void bwts_ec_plan(u64 n, u64 out[5])
 {
-    out[0] = EC_T; out[1] = EC_K; out[2] = ec_tiles(n); out[3] = ec_blocks(ec_tiles(n)); out[4] = ec_bound_bytes(n);
+    const StageCut cut = stage_cut_single(n, EC_T, (u64)EC_T << EC_LOG_K);
+    out[0] = EC_T; out[1] = EC_K; out[2] = cut.units[0]; out[3] = cut.units[1]; out[4] = ec_bound_bytes(n);
 }
 
 static unsigned ec_grid(u64 blocks) { return (unsigned)blocks; }      // (ec_plan_call keeps 4 blocks below 2^31)
@@ -463,18 +449,14 @@ static int ec_prepare(bwts_ctx *ctx, const EcPlan &p, bool encode, bool segments
 {
     BlockLayout L;
     b.declare(L, p, encode, segments);
-    BWTS_TRY(arena_reserve(ctx, L.bytes()));
-    char *base = (char *)arena_alloc(ctx, L.bytes());
-    if (!base) return BWTS_E_NOMEM;
-    L.place(base);
+    BWTS_TRY(arena_take(ctx, L));
     S = EcSegs{nullptr, nullptr, nullptr, nullptr, n, 0};
     if (segments) {
         u64 *d_words = nullptr;
         BWTS_TRY(seg_upload_extra(ctx, p.words.data(), 2 * p.count + 1, &d_words));
         S.seg_off = d_seg_off(ctx); S.first = d_words; S.base = d_words + p.count; S.bseg = b.bseg;
         SpanGuard sp(ctx, BWTS_K_OTHER, p.blocks, 4 * p.blocks);
-        const u64 wgs = (p.count + 3) / 4;
-        ec_block_table_kernel<<<dim3((unsigned)(wgs < (1u << 20) ? wgs : (1u << 20))), dim3(256), 0, ctx->stream>>>(d_seg_off(ctx), S.first, p.count, b.bseg);
+        unit_table_launch(ctx->stream, p.count, EcBlockTable{S.seg_off, S.first, b.bseg});
     }
     return BWTS_OK;
 }
@@ -485,12 +467,12 @@ static int ec_scan_sizes(bwts_ctx *ctx, const EcPlan &p, const EcBufs &b, bool w
     return device_scan<false, u64>(ctx, p.tiles + 1, EcSizeIn{b.per_tile, p.tiles, words}, EcOffOut{b.offs, p.tiles, d_total}, OpAdd(), (u64)0, b.scan_temp);
 }
 
-// one input (stream_bytes == null: *out_bytes) or the context's segments (stream_bytes[count])
-int ec_encode_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, u64 out_cap, u64 *out_bytes, u64 *stream_bytes)
+// sizes: the bytes of the one input's stream, or of every segment's (sizes[count])
+int ec_encode_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, u64 out_cap, SegMode segs, u64 *sizes)
 {
-    const bool segments = stream_bytes != nullptr;
+    const bool segments = segs.table();
     EcPlan p;
-    BWTS_TRY(ec_plan_call(ctx, n, segments, nullptr, p));
+    BWTS_TRY(ec_plan_call(ctx, n, segs, nullptr, p));
     if (out_cap < p.least) return BWTS_E_SPACE;
     EcBufs b;
     EcSegs S;
@@ -521,20 +503,20 @@ int ec_encode_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, u64 out_cap,
             SpanGuard sp(ctx, BWTS_K_OTHER, p.count, 24 * p.count);
             ec_stream_sizes_kernel<<<dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, ctx->stream>>>(d_seg_off(ctx), S.first, p.count, b.offs, b.ssize);
         }
-        HIPC(hipMemcpyAsync(stream_bytes, b.ssize, p.count * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+        HIPC(hipMemcpyAsync(sizes, b.ssize, p.count * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
         HIPC(hipStreamSynchronize(ctx->stream));
     } else {
-        *out_bytes = total;
+        *sizes = total;
     }
     HIPC(hipGetLastError());
     return BWTS_OK;
 }
 
-// one stream of in_bytes (stream_bytes == null; its n goes to *n_out, and must not exceed out_cap) or one per segment of the context's
-// table, whose lengths the headers must repeat
-int ec_decode_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out, const u64 *stream_bytes)
+// one stream of in_bytes (its n goes to *n_out, and must not exceed out_cap; stream_bytes is not read) or one per segment of the
+// context's table, stream_bytes[count], whose lengths the headers must repeat
+int ec_decode_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out, SegMode segs, const u64 *stream_bytes)
 {
-    const bool segments = stream_bytes != nullptr;
+    const bool segments = segs.table();
     u64 n = in_bytes;       // segmented: the sum of the lengths
     if (!segments) {
         if (in_bytes < EC_HEADER_BYTES || (in_bytes & 15)) return BWTS_E_FORMAT;
@@ -547,7 +529,7 @@ int ec_decode_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 o
         ctx->tm.n = n;
     }
     EcPlan p;
-    BWTS_TRY(ec_plan_call(ctx, n, segments, stream_bytes, p));
+    BWTS_TRY(ec_plan_call(ctx, n, segs, segments ? stream_bytes : nullptr, p));
     EcBufs b;
     EcSegs S;
     BWTS_TRY(ec_prepare(ctx, p, false, segments, n, b, S));

@@ -11,6 +11,7 @@
 
 #include "../../include/bwts.h"
 #include "seg_layout.h"
+#include "stage_cut.h"
 
 typedef uint64_t u64;
 typedef uint32_t u32;
@@ -224,6 +225,8 @@ int  arena_release(bwts_ctx *ctx);                      // gives the arena up (c
 void arena_install(bwts_ctx *ctx, void *block, size_t bytes, double alloc_ms);
 void arena_reset(bwts_ctx *ctx);
 void *arena_alloc(bwts_ctx *ctx, size_t bytes);         // NULL when exhausted
+struct BlockLayout;
+int  arena_take(bwts_ctx *ctx, const BlockLayout &L);   // reserves a declared layout's bytes(), takes them whole and places the layout; BWTS_E_NOMEM
 template <typename T> static inline T *arena_array(bwts_ctx *ctx, u64 count)
 {
     return (T *)arena_alloc(ctx, (size_t)count * sizeof(T));
@@ -305,23 +308,27 @@ int    inverse_splitter_log2(u64 n);
 size_t inverse_attempt_bytes(u64 n, int g, int mark);
 size_t inverse_arena_bytes(u64 n);
 
-// ---- move-to-front, the stage behind the transform (mtf.hip; include/bwts_mtf.h) ----
-int mtf_forward_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
-int mtf_inverse_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
-int mtf_forward_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);       // the context's segment table, like the transform's
-int mtf_inverse_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out);
-size_t mtf_arena_bytes(const bwts_ctx *ctx, u64 n, bool segments);     // what a call reserves: 256 bytes per tile and a little per group
+// ---- the stages behind the transform: which input a call works on, and its cut (stage_cut.h) ----
+static inline SegMode seg_mode(const bwts_ctx *ctx) { return SegMode{ctx->seg_off.empty() ? 0 : (u64)ctx->seg_off.size() - 1}; }     // the context's table
+static inline StageCut stage_cut_call(const bwts_ctx *ctx, SegMode segs, u64 n, u64 unit_a, u64 unit_b = 0)
+{
+    return stage_cut_call(ctx->seg_off, segs, n, unit_a, unit_b);
+}
+
+// ---- move-to-front (mtf.hip; include/bwts_mtf.h) ----
+int mtf_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool inverse, SegMode segs);
+size_t mtf_arena_bytes(const bwts_ctx *ctx, u64 n, SegMode segs);      // what a call reserves: 256 bytes per tile and a little per group
 void bwts_mtf_plan(u64 n, u64 out[4]);                                  // tile size, tiles per group, tiles and groups of one input of n bytes
 
 // ---- entropy coding behind move-to-front (ec.hip) -----------------------------------
-// stream_bytes == null: one input / one stream; else the context's segment table, one stream size per segment (written / read)
-int ec_encode_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, u64 out_cap, u64 *out_bytes, u64 *stream_bytes);
-int ec_decode_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out, const u64 *stream_bytes);
+// sizes: the stream's bytes, or one per segment; decode: the one stream of in_bytes, or stream_bytes[count] (in_bytes: the lengths' sum)
+int ec_encode_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, u64 out_cap, SegMode segs, u64 *sizes);
+int ec_decode_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out, SegMode segs, const u64 *stream_bytes);
 void bwts_ec_plan(u64 n, u64 out[5]);                                   // tile size, tiles per block, tiles, blocks and the bound of one input
 
 // ---- checksum and the packed frame (crc.hip, pack.hip; include/bwts_pack.h) ------------
-// one input of n bytes, or the segments of the context's table: one value each, to the host
-int crc_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, bool segments, u32 *crcs);
+// one value for the input of n bytes, or one per segment, to the host
+int crc_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, SegMode segs, u32 *crcs);
 void bwts_crc_plan(u64 n, u64 out[4]);                                  // tile size, tiles per fold group, tiles and groups of one input
 int pack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes);
 int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out);

@@ -1011,14 +1011,11 @@ static int cycle_sort_plan(bwts_ctx *ctx, u64 m, SortPlan *cp)
     L.place(sb);
     return BWTS_OK;
 }
-// the one block an attempt (InvRun, WideRun) holds in the arena: reserved by its declared size, taken whole, every declared array pointed into it
+// the one block an attempt (InvRun, WideRun) holds in the arena
 template <typename RUN> static int arena_place(bwts_ctx *ctx, RUN &r)
 {
     BlockLayout L; r.declare(L);
-    BWTS_TRY(arena_reserve(ctx, L.bytes()));
-    char *base = (char *)arena_alloc(ctx, L.bytes());
-    if (!base) return BWTS_E_NOMEM;
-    L.place(base);
+    BWTS_TRY(arena_take(ctx, L));
     r.dC = ctx->d_small + 1024;         // symbol boundaries C[0..256] (unbwts.c:38-43)
     return BWTS_OK;
 }

@@ -351,18 +351,19 @@ __global__ __launch_bounds__(256) void mtf_remap_kernel(u8 *out, const u64 *__re
     }
 }
 
-// The tile table of a segmented call, from the segment table: segment s owns the tiles first[s] ... (one wave per segment); a
-// segment's first tile is marked, the last entry is n.
-__global__ __launch_bounds__(256) void mtf_tile_table_kernel(const u64 *__restrict__ seg_off, const u64 *__restrict__ first, u64 count, u64 n,
-                                                             u64 *__restrict__ tile_off)
-{
-    const u64 lane = (u64)lane_id();
-    for (u64 s = (u64)blockIdx.x * 4 + (u64)wave_id(); s < count; s += (u64)gridDim.x * 4) {
-        const u64 a = seg_off[s], f = first[s], nt = (seg_off[s + 1] - a + MTF_T - 1) / MTF_T;
-        for (u64 j = lane; j < nt; j += 64) tile_off[f + j] = (a + j * MTF_T) | (j == 0 ? MTF_RESET : 0ull);
-        if (s + 1 == count && lane == 0) tile_off[f + nt] = n;
+// The tile table of a segmented call (unit_table_kernel): where every tile starts, a segment's first tile marked; the last entry is n.
+struct MtfTileTable {
+    const u64 *seg_off, *first_tile;
+    u64 count, n;
+    u64 *tile_off;
+    __device__ u64 first(u64 s) const { return first_tile[s]; }
+    __device__ u64 units(u64 s) const { return (seg_off[s + 1] - seg_off[s] + MTF_T - 1) / MTF_T; }
+    __device__ void store(u64 s, u64 first, u64 units, u64 j) const
+    {
+        tile_off[first + j] = (seg_off[s] + j * MTF_T) | (j == 0 ? MTF_RESET : 0ull);
+        if (s + 1 == count && j + 1 == units) tile_off[first + units] = n;
     }
-}
+};
 
 // ------------------------------------------------------------------------------------
 // host side
@@ -375,17 +376,6 @@ static MtfPlan mtf_plan_tiles(u64 tiles)
     p.tiles = tiles;
     p.groups = (tiles + MTF_G - 1) / MTF_G;
     return p;
-}
-
-static u64 mtf_tiles_of(u64 len) { return (len + MTF_T - 1) / MTF_T; }
-
-// tiles of the call: of the one input, or of the context's segment table (every segment is cut on its own)
-static u64 mtf_call_tiles(const bwts_ctx *ctx, u64 n, bool segments)
-{
-    if (!segments || ctx->seg_off.size() <= 2) return mtf_tiles_of(n);
-    u64 tiles = 0;
-    for (size_t s = 0; s + 1 < ctx->seg_off.size(); s++) tiles += mtf_tiles_of(ctx->seg_off[s + 1] - ctx->seg_off[s]);
-    return tiles;
 }
 
 struct MtfBufs {
@@ -403,17 +393,18 @@ struct MtfBufs {
 
 void bwts_mtf_plan(u64 n, u64 out[4])
 {
-    const MtfPlan p = mtf_plan_tiles(mtf_tiles_of(n));
+    const MtfPlan p = mtf_plan_tiles(stage_cut_single(n, MTF_T).units[0]);
     out[0] = MTF_T; out[1] = MTF_G; out[2] = p.tiles; out[3] = p.groups;
 }
 
-size_t mtf_arena_bytes(const bwts_ctx *ctx, u64 n, bool segments)
+size_t mtf_arena_bytes(const bwts_ctx *ctx, u64 n, SegMode segs)
 {
     if (n == 0 || n > MTF_MAX_N) return 0;
-    const MtfPlan p = mtf_plan_tiles(mtf_call_tiles(ctx, n, segments));
+    segs = segs.one_as_single();
+    const MtfPlan p = mtf_plan_tiles(stage_cut_call(ctx, segs, n, MTF_T).units[0]);
     MtfBufs b;
     BlockLayout L;
-    b.declare(L, p, segments && ctx->seg_off.size() > 2);
+    b.declare(L, p, segs.table());
     return L.bytes();
 }
 
@@ -438,12 +429,13 @@ static int mtf_scan(bwts_ctx *ctx, const MtfBufs &b, const MtfPlan &p)
     return BWTS_OK;
 }
 
-static int mtf_run(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool inverse, bool segments)
+int mtf_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool inverse, SegMode segs)
 {
     if (n > MTF_MAX_N) return BWTS_E_RANGE;
     if (ranges_overlap(d_in, n, d_out, n)) return BWTS_E_ARG;
-    const bool table = segments && ctx->seg_off.size() > 2;
-    const MtfPlan p = mtf_plan_tiles(mtf_call_tiles(ctx, n, segments));
+    segs = segs.one_as_single();
+    const StageCut cut = stage_cut_call(ctx, segs, n, MTF_T);
+    const MtfPlan p = mtf_plan_tiles(cut.units[0]);
     if (p.groups > 0x7fffffffull) return BWTS_E_RANGE;
     const unsigned wave_blocks = mtf_grid((p.tiles + 3) / 4);
     if ((u64)wave_blocks * 4 < p.tiles) return BWTS_E_RANGE;
@@ -457,22 +449,14 @@ static int mtf_run(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool inverse
     }
     MtfBufs b;
     BlockLayout L;
-    b.declare(L, p, table);
-    BWTS_TRY(arena_reserve(ctx, L.bytes()));
-    char *base = (char *)arena_alloc(ctx, L.bytes());
-    if (!base) return BWTS_E_NOMEM;
-    L.place(base);
-    if (table) {
+    b.declare(L, p, segs.table());
+    BWTS_TRY(arena_take(ctx, L));
+    if (segs.table()) {
         // every segment's first tile goes up behind the segment table (pinned, on the stream); the table itself is made on the device
-        const u64 count = (u64)ctx->seg_off.size() - 1;
-        std::vector<u64> first((size_t)count);
-        u64 at = 0;
-        for (u64 sgm = 0; sgm < count; sgm++) { first[sgm] = at; at += mtf_tiles_of(ctx->seg_off[sgm + 1] - ctx->seg_off[sgm]); }
-        if (at != p.tiles) return BWTS_E_INTERNAL;
         u64 *d_first = nullptr;
-        BWTS_TRY(seg_upload_extra(ctx, first.data(), count, &d_first));
+        BWTS_TRY(seg_upload_extra(ctx, cut.first[0].data(), cut.count, &d_first));
         SpanGuard sp(ctx, BWTS_K_OTHER, p.tiles, 8 * p.tiles);
-        mtf_tile_table_kernel<<<dim3(mtf_grid((count + 3) / 4)), dim3(256), 0, ctx->stream>>>(d_seg_off(ctx), d_first, count, n, b.tile_off);
+        unit_table_launch(ctx->stream, cut.count, MtfTileTable{d_seg_off(ctx), d_first, cut.count, n, b.tile_off});
     }
     const unsigned tile_blocks = mtf_grid(p.tiles);
     if (!inverse) {
@@ -495,8 +479,3 @@ static int mtf_run(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, bool inverse
     HIPC(hipGetLastError());
     return BWTS_OK;
 }
-
-int mtf_forward_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out) { return mtf_run(ctx, d_in, n, d_out, false, false); }
-int mtf_inverse_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out) { return mtf_run(ctx, d_in, n, d_out, true, false); }
-int mtf_forward_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out) { return mtf_run(ctx, d_in, n, d_out, false, true); }
-int mtf_inverse_segments_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out) { return mtf_run(ctx, d_in, n, d_out, true, true); }

@@ -47,18 +47,19 @@ int pack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64
     const bool seg = nblk > 1;
     if (out_cap < pack_least_bytes(n, B)) return BWTS_E_SPACE;
     BWTS_TRY(pack_blocks_set(ctx, n, B, nblk));
+    const SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
     std::vector<u32> crcs((size_t)nblk);
     std::vector<u64> sizes((size_t)nblk);
-    BWTS_TRY(crc_impl(ctx, d_in, n, seg, crcs.data()));
+    BWTS_TRY(crc_impl(ctx, d_in, n, segs, crcs.data()));
     u8 *a = nullptr, *b = nullptr;
     BWTS_TRY(pack_stage(ctx, 0, n, &a));
     BWTS_TRY(pack_stage(ctx, 1, n, &b));
     BWTS_TRY(seg ? forward_segments_impl(ctx, d_in, n, a) : forward_device_impl(ctx, d_in, n, a));
     HIPC(hipStreamSynchronize(ctx->stream));
-    BWTS_TRY(seg ? mtf_forward_segments_impl(ctx, a, n, b) : mtf_forward_impl(ctx, a, n, b));
+    BWTS_TRY(mtf_impl(ctx, a, n, b, false, segs));
     HIPC(hipStreamSynchronize(ctx->stream));
     // the streams go straight to their place; a frame that does not fit is refused by the coder before it writes anything
-    BWTS_TRY(ec_encode_impl(ctx, b, n, d_out + fixed, out_cap - fixed, seg ? nullptr : &sizes[0], seg ? sizes.data() : nullptr));
+    BWTS_TRY(ec_encode_impl(ctx, b, n, d_out + fixed, out_cap - fixed, segs, sizes.data()));
     HIPC(hipStreamSynchronize(ctx->stream));
     u8 *head = (u8 *)(ctx->h_small + SM_PACK_HEAD), *dir = nullptr;
     BWTS_TRY(pack_dir_staging(ctx, nblk, &dir));
@@ -89,6 +90,7 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
     const bool seg = H.nblk > 1;
     const u64 fixed = pack_fixed_bytes(H.nblk);
     BWTS_TRY(pack_blocks_set(ctx, H.n, H.B, H.nblk));
+    const SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
     BWTS_TRY(pack_dir_staging(ctx, H.nblk, &dir));
     if (seg) {
         HIPC(hipMemcpyAsync(dir, d_in + PACK_HEADER_BYTES, PACK_ENTRY_BYTES * H.nblk, hipMemcpyDeviceToHost, ctx->stream));
@@ -107,21 +109,21 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
     }
     // ranks into d_out, bytes of the transform into the stage block, the input's bytes into d_out
     if (seg) {
-        BWTS_TRY(ec_decode_impl(ctx, d_in + fixed, H.n, d_out, H.n, nullptr, sizes.data()));
+        BWTS_TRY(ec_decode_impl(ctx, d_in + fixed, H.n, d_out, H.n, nullptr, segs, sizes.data()));
     } else {
         u64 m = 0;
-        const int rc = ec_decode_impl(ctx, d_in + fixed, sizes[0], d_out, H.n, &m, nullptr);
+        const int rc = ec_decode_impl(ctx, d_in + fixed, sizes[0], d_out, H.n, &m, segs, nullptr);
         // (room for the frame's n is what the coder was given: a stream that names more, or less, is not this frame's)
         if (rc == BWTS_E_SPACE || (rc == BWTS_OK && m != H.n)) return BWTS_E_FORMAT;
         BWTS_TRY(rc);
     }
     u8 *a = nullptr;
     BWTS_TRY(pack_stage(ctx, 0, H.n, &a));
-    BWTS_TRY(seg ? mtf_inverse_segments_impl(ctx, d_out, H.n, a) : mtf_inverse_impl(ctx, d_out, H.n, a));
+    BWTS_TRY(mtf_impl(ctx, d_out, H.n, a, true, segs));
     HIPC(hipStreamSynchronize(ctx->stream));
     BWTS_TRY(seg ? inverse_segments_impl(ctx, a, H.n, d_out) : inverse_device_impl(ctx, a, H.n, d_out));
     HIPC(hipStreamSynchronize(ctx->stream));
-    BWTS_TRY(crc_impl(ctx, d_out, H.n, seg, got.data()));
+    BWTS_TRY(crc_impl(ctx, d_out, H.n, segs, got.data()));
     if (memcmp(got.data(), want.data(), (size_t)H.nblk * sizeof(u32)) != 0) return BWTS_E_CHECKSUM;
     *n_out = H.n;
     return BWTS_OK;

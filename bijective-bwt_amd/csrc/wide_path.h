@@ -523,10 +523,7 @@ static int wide_arena_place(bwts_ctx *ctx, const WideShape &sh, WideArena &A)
 {
     BlockLayout L;
     A.declare(L, sh);
-    BWTS_TRY(arena_reserve(ctx, L.bytes()));
-    char *base = (char *)arena_alloc(ctx, L.bytes());
-    if (base) L.place(base);
-    return base ? BWTS_OK : BWTS_E_NOMEM;
+    return arena_take(ctx, L);
 }
 // One run.  The inputs and the shape are set when it is made; every other member is written by the one stage named beside it.
 struct WideRun {

@@ -1,7 +1,8 @@
 """GPU suite of the checksum kernel (include/bwts_pack.h, csrc/crc.hip): bwts_crc32_device and its segment form against zlib.crc32 at
 sizes taken from the engine's own plan (tile T, fold group G): the 16-byte piece, the tile ends, the group boundary and past two
 groups; on uniform bytes, all zeros (the classic catch for a wrong length in the combine) and all 0xFF, from an aligned and an
-unaligned start; the error contract; and one input beyond 2^32 bytes whose value the model's combine predicts."""
+unaligned start; the error contract; one input beyond 2^32 bytes whose value the model's combine predicts; and one segment table
+through all three stages that share the segment cut and its table kernel (checksum, move-to-front, coder)."""
 import ctypes
 import zlib
 
@@ -9,6 +10,8 @@ import numpy as np
 import pytest
 
 import big_cases as B
+import ec_model as E
+import mtf_model as M
 import pack_model as P
 
 pytestmark = pytest.mark.gpu
@@ -88,6 +91,57 @@ def test_segments(ctx, plan, room, references):
     _segments_checked(ctx, room, x[:sum(many)], many)
     # the single call after a segmented one, and the other way round, on one context
     assert ctx.crc32_device(room, T + 5) == zlib.crc32(x[:T + 5])
+
+
+WAVE_GRID_CAP = 2048        # workgroups of four waves the stages' shared table launch uses at most (csrc/device_utils.h, wave_grid)
+
+
+def test_one_table_through_every_stage(pkg, ctx):
+    """One segment table through the checksum, move-to-front and the coder on one context: the three stages cut it with one function
+    (csrc/stage_cut.h) and write their per-unit tables with one kernel.  More segments than four times the launch's workgroup cap,
+    and not a multiple of four, so the kernel's stride over segments runs and its last workgroup is not full; almost all of 1 to 17
+    bytes; one of exactly 64 of the largest unit (the coder's block) and one, behind the stride, of 65, so the lanes' loop over a
+    segment's units wraps for every stage."""
+    mtf_T, crc_T, ec = pkg.debug_mtf_plan(1)["T"], pkg.debug_crc_plan(1)["T"], pkg.debug_ec_plan(1)
+    unit = max(mtf_T, crc_T, ec["T"] * ec["K"])
+    count = 4 * WAVE_GRID_CAP + 7
+    assert unit == ec["T"] * ec["K"] == E.T * E.K and count % 4 != 0 and count > 4 * WAVE_GRID_CAP
+    rng = np.random.default_rng(2024)
+    lengths = 1 + rng.integers(0, 17, count)
+    long64, long65 = 77, 4 * WAVE_GRID_CAP + 3
+    lengths[long64], lengths[long65] = 64 * unit, 64 * unit + 1
+    short = [s for s in range(count) if s not in (long64, long65)]
+    assert min(lengths) == 1 and max(lengths[short]) == 17
+    n = int(lengths.sum())
+    offs = np.concatenate(([0], np.cumsum(lengths))).astype(np.int64)
+    x = (rng.integers(0, 256, n, dtype=np.uint8) & rng.integers(0, 256, n, dtype=np.uint8))       # skewed: the ranks get a table worth coding
+    cap = pkg.ec_bound_segments(lengths)
+    a, b, c, coded = ctx.alloc(n), ctx.alloc(n), ctx.alloc(n), ctx.alloc(cap)
+    try:
+        a.upload(x)
+        crcs = ctx.crc32_segments_device(a, lengths)
+        bad = [s for s in range(count) if int(crcs[s]) != zlib.crc32(x[offs[s]:offs[s + 1]])]
+        assert not bad, "checksum of segments %s ..." % bad[:8]
+        # move-to-front: the model on every short segment, the round trip on all
+        ctx.mtf_forward_segments_device(a, lengths, b)
+        y = b.download(n)
+        bad = [s for s in short if y[offs[s]:offs[s + 1]].tobytes() != M.forward(x[offs[s]:offs[s + 1]].tobytes())]
+        assert not bad, "ranks of segments %s ..." % bad[:8]
+        ctx.mtf_inverse_segments_device(b, lengths, c)
+        assert np.array_equal(c.download(n), x)
+        # the coder: the model's stream, and its size, on a handful of short segments; the round trip on all
+        sizes = ctx.ec_encode_segments_device(b, lengths, coded, cap)
+        soffs = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+        assert int(soffs[-1]) <= cap
+        streams = coded.download(int(soffs[-1]))
+        for s in (0, 1, long64 - 1, long64 + 1, 4 * WAVE_GRID_CAP - 1, 4 * WAVE_GRID_CAP, long65 - 1, long65 + 1, count - 1):
+            want = E.encode(y[offs[s]:offs[s + 1]])
+            assert int(sizes[s]) == len(want) and streams[soffs[s]:soffs[s + 1]].tobytes() == want, s
+        ctx.ec_decode_segments_device(coded, sizes, lengths, c)
+        assert np.array_equal(c.download(n), y)
+    finally:
+        for d in (a, b, c, coded):
+            d.free()
 
 
 def test_error_contract(pkg, ctx, room):

@@ -1,5 +1,7 @@
 """The host layer's plain C++ under the sanitizers, as a program of its own (no GPU, nothing loaded into Python): the copy workers
-of csrc/copy_pool.h and the segment table's region arithmetic of csrc/seg_layout.h, driven by tests/host_layer_check.cc."""
+of csrc/copy_pool.h and the segment table's region arithmetic of csrc/seg_layout.h, driven by tests/host_layer_check.cc; and the cut
+of a stage call into units of csrc/stage_cut.h, driven by tests/stage_cut_check.cc (its single-input cuts are then compared with the
+library's plan hooks, which are host arithmetic)."""
 import os
 import shutil
 import subprocess
@@ -10,21 +12,42 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bijective-bwt_amd", "csrc")
 
 
-@pytest.mark.parametrize("name,flags", [("thread", ["-fsanitize=thread"]),
-                                        ("address", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])])
-def test_copy_pool_and_segment_layout_under_sanitizers(tmp_path, name, flags):
+ASAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+
+
+def _built_and_run(tmp_path, source, name, flags):
+    """Builds tests/<source>.cc with `flags`, runs it as a child process and returns what it printed."""
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     assert cxx, "no host C++ compiler"
-    exe = str(tmp_path / ("host_layer_check_" + name))
+    exe = str(tmp_path / (source + "_" + name))
     subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-pthread"] + flags +
-                          ["-I", CSRC, os.path.join(ROOT, "tests", "host_layer_check.cc"), "-o", exe])
+                          ["-I", CSRC, os.path.join(ROOT, "tests", source + ".cc"), "-o", exe])
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env={"PATH": os.environ.get("PATH", "")})
     assert r.returncode == 0, (r.stdout.decode(errors="replace")[-1000:], r.stderr.decode(errors="replace")[-3000:])
     assert r.stdout.decode().strip().endswith("checks ok")
+    return r.stdout.decode()
+
+
+@pytest.mark.parametrize("name,flags", [("thread", ["-fsanitize=thread"]), ("address", ASAN)])
+def test_copy_pool_and_segment_layout_under_sanitizers(tmp_path, name, flags):
+    _built_and_run(tmp_path, "host_layer_check", name, flags)
+
+
+def test_stage_cut_under_sanitizers(tmp_path, pkg):
+    """csrc/stage_cut.h against its serial definition (tests/stage_cut_check.cc), and the library's three plan hooks -- which are
+    built on the same cut -- against what the program prints for single inputs."""
+    singles = [line.split() for line in _built_and_run(tmp_path, "stage_cut_check", "address", ASAN).splitlines() if line.startswith("single ")]
+    assert len(singles) >= 10 and max(int(f[1]) for f in singles) == 1 << 36
+    for _, n, mtf_tiles, crc_tiles, ec_tiles, ec_blocks in singles:
+        n = int(n)
+        assert pkg.debug_mtf_plan(n)["tiles"] == int(mtf_tiles), n
+        assert pkg.debug_crc_plan(n)["tiles"] == int(crc_tiles), n
+        ec = pkg.debug_ec_plan(n)
+        assert (ec["tiles"], ec["blocks"]) == (int(ec_tiles), int(ec_blocks)), n
 
 
 def test_headers_are_plain_cxx():
-    """Neither header may pull in the device runtime: the program above has to build with a host compiler alone."""
-    for h in ("copy_pool.h", "seg_layout.h"):
+    """None of the headers may pull in the device runtime: the programs above have to build with a host compiler alone."""
+    for h in ("copy_pool.h", "seg_layout.h", "stage_cut.h"):
         includes = [line for line in open(os.path.join(CSRC, h)).read().splitlines() if line.startswith("#include")]
         assert includes and not [line for line in includes if "hip" in line or "internal.h" in line], h

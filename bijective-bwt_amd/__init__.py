@@ -50,10 +50,16 @@ EC_EXPORTS = [
     "bwts_ec_encode", "bwts_ec_decode", "bwts_ec_encode_segments_device", "bwts_ec_decode_segments_device",
 ]
 E_FORMAT, E_SPACE = -8, -9
+# ... include/bwts_zrl.h (zero-run coding of the ranks, between move-to-front and the entropy coder) ...
+ZRL_EXPORTS = [
+    "bwts_zrl_bound", "bwts_zrl_encode_device", "bwts_zrl_decode_device", "bwts_zrl_encode", "bwts_zrl_decode",
+    "bwts_zrl_encode_segments_device", "bwts_zrl_decode_segments_device",
+]
 # ... include/bwts_pack.h (the chain as one call: a checksummed frame) ...
 PACK_EXPORTS = [
     "bwts_crc32_device", "bwts_crc32_segments_device", "bwts_pack_bound", "bwts_unpack_size",
     "bwts_pack_device", "bwts_unpack_device", "bwts_pack", "bwts_unpack",
+    "bwts_pack_bound_v", "bwts_pack_device_v", "bwts_pack_v",
 ]
 E_CHECKSUM = -10
 # ... and include/bwts_test.h (harness and unit-test hooks)
@@ -63,6 +69,7 @@ TEST_EXPORTS = [
     "bwts_debug_chunk_plan", "bwts_debug_inverse_arena", "bwts_debug_forward_arena", "bwts_debug_wide_forward_arena", "bwts_debug_inverse_report",
     "bwts_debug_forward_report", "bwts_debug_segments_plan", "bwts_debug_segments_report",
     "bwts_debug_mtf_plan", "bwts_debug_last_spans", "bwts_debug_ec_plan", "bwts_debug_crc_plan",
+    "bwts_debug_zrl_plan",
 ]
 # bwts_debug_inverse_report: the words of one attempt's record, and what marks, outcomes and forms are called
 INV_REPORT_FIELDS = ["g", "mark", "outcome", "s", "virtual", "node_cap", "nu", "nu2", "ucap_first", "second_collect",
@@ -177,6 +184,15 @@ def lib():
         L.bwts_ec_encode_segments_device.argtypes = [vp, vp, vp, u64, vp, u64, vp]
         L.bwts_ec_decode_segments_device.argtypes = [vp, vp, vp, vp, u64, vp]
         L.bwts_debug_ec_plan.argtypes = [u64, ctypes.POINTER(u64)]
+        L.bwts_zrl_bound.argtypes = [u64]
+        L.bwts_zrl_bound.restype = u64
+        for name in ("bwts_zrl_encode_device", "bwts_zrl_encode"):
+            getattr(L, name).argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
+        for name in ("bwts_zrl_decode_device", "bwts_zrl_decode"):
+            getattr(L, name).argtypes = [vp, vp, u64, vp, u64]
+        L.bwts_zrl_encode_segments_device.argtypes = [vp, vp, vp, u64, vp, u64, vp]
+        L.bwts_zrl_decode_segments_device.argtypes = [vp, vp, vp, vp, u64, vp]
+        L.bwts_debug_zrl_plan.argtypes = [u64, ctypes.POINTER(u64)]
         L.bwts_crc32_device.argtypes = [vp, vp, u64, ctypes.POINTER(ctypes.c_uint32)]
         L.bwts_crc32_segments_device.argtypes = [vp, vp, vp, u64, vp]
         L.bwts_pack_bound.argtypes = [u64, u64]
@@ -184,6 +200,11 @@ def lib():
         L.bwts_unpack_size.argtypes = [vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]
         for name in ("bwts_pack_device", "bwts_pack"):
             getattr(L, name).argtypes = [vp, vp, u64, u64, vp, u64, ctypes.POINTER(u64)]
+        u32 = ctypes.c_uint32
+        L.bwts_pack_bound_v.argtypes = [u32, u64, u64]
+        L.bwts_pack_bound_v.restype = u64
+        for name in ("bwts_pack_device_v", "bwts_pack_v"):
+            getattr(L, name).argtypes = [vp, u32, vp, u64, u64, vp, u64, ctypes.POINTER(u64)]
         for name in ("bwts_unpack_device", "bwts_unpack"):
             getattr(L, name).argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
         L.bwts_debug_crc_plan.argtypes = [u64, ctypes.POINTER(u64)]
@@ -458,6 +479,48 @@ class Context:
             raise BwtsError(-1, "one stream size per segment")
         self._check(lib().bwts_ec_decode_segments_device(self._h, _ptr(d_in), sb.ctypes.data, ls.ctypes.data, ls.size, _ptr(d_out)))
 
+    # -- zero-run coding between move-to-front and the entropy coder (include/bwts_zrl.h) -----------
+    def zrl_encode(self, data, out_cap=None):
+        """bwts_zrl_encode: the zero-run coded form of a byte string, or the string itself where that is no shorter (host buffers);
+        out_cap defaults to the bound, the input's length."""
+        a = _u8(data)
+        if a.size == 0:
+            raise BwtsError(-1, "empty input")
+        out = np.empty(a.size if out_cap is None else int(out_cap), dtype=np.uint8)
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_zrl_encode(self._h, a.ctypes.data, a.size, out.ctypes.data, out.size, ctypes.byref(got)))
+        return out[:got.value].copy()
+
+    def zrl_decode(self, coded, n):
+        """bwts_zrl_decode: the n bytes a coded form stands for (host buffers)."""
+        a = _u8(coded)
+        out = np.empty(int(n), dtype=np.uint8)
+        self._check(lib().bwts_zrl_decode(self._h, a.ctypes.data, a.size, out.ctypes.data, out.size))
+        return out
+
+    def zrl_encode_device(self, d_in, n, d_out, out_cap):
+        """bwts_zrl_encode_device: returns the bytes written (below n: coded; n: stored)."""
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_zrl_encode_device(self._h, _ptr(d_in), int(n), _ptr(d_out), int(out_cap), ctypes.byref(got)))
+        return int(got.value)
+
+    def zrl_decode_device(self, d_in, in_bytes, d_out, n):
+        self._check(lib().bwts_zrl_decode_device(self._h, _ptr(d_in), int(in_bytes), _ptr(d_out), int(n)))
+
+    def zrl_encode_segments_device(self, d_in, lengths, d_out, out_cap):
+        """bwts_zrl_encode_segments_device: one output per segment, concatenated; returns their lengths (uint64 array)."""
+        ls = np.ascontiguousarray(lengths, dtype=np.uint64)
+        sizes = np.zeros(ls.size, dtype=np.uint64)
+        self._check(lib().bwts_zrl_encode_segments_device(self._h, _ptr(d_in), ls.ctypes.data, ls.size, _ptr(d_out), int(out_cap), sizes.ctypes.data))
+        return sizes
+
+    def zrl_decode_segments_device(self, d_in, in_lengths, lengths, d_out):
+        ls = np.ascontiguousarray(lengths, dtype=np.uint64)
+        il = np.ascontiguousarray(in_lengths, dtype=np.uint64)
+        if il.size != ls.size:
+            raise BwtsError(-1, "one coded length per segment")
+        self._check(lib().bwts_zrl_decode_segments_device(self._h, _ptr(d_in), il.ctypes.data, ls.ctypes.data, ls.size, _ptr(d_out)))
+
     # -- the chain as one call: a checksummed frame (include/bwts_pack.h) -----------------------------
     def crc32_device(self, d_in, n):
         """bwts_crc32_device: zlib's CRC-32 of n device bytes."""
@@ -472,14 +535,15 @@ class Context:
         self._check(lib().bwts_crc32_segments_device(self._h, _ptr(d_in), ls.ctypes.data, ls.size, crcs.ctypes.data))
         return crcs
 
-    def pack(self, data, block_bytes=0, out_cap=None):
-        """bwts_pack: the frame of a byte string (host buffers); out_cap defaults to the bound."""
+    def pack(self, data, block_bytes=0, out_cap=None, version=1):
+        """bwts_pack_v: the frame of a byte string (host buffers); out_cap defaults to the bound; version 2: zero-run coding in front
+        of the coder."""
         a = _u8(data)
         if a.size == 0:
             raise BwtsError(-1, "empty input")
-        out = np.empty(pack_bound(a.size, block_bytes) if out_cap is None else int(out_cap), dtype=np.uint8)
+        out = np.empty(pack_bound(a.size, block_bytes, version) if out_cap is None else int(out_cap), dtype=np.uint8)
         got = ctypes.c_uint64(0)
-        self._check(lib().bwts_pack(self._h, a.ctypes.data, a.size, int(block_bytes), out.ctypes.data, out.size, ctypes.byref(got)))
+        self._check(lib().bwts_pack_v(self._h, int(version), a.ctypes.data, a.size, int(block_bytes), out.ctypes.data, out.size, ctypes.byref(got)))
         return out[:got.value].copy()
 
     def unpack(self, frame, out=None):
@@ -491,10 +555,10 @@ class Context:
         self._check(lib().bwts_unpack(self._h, a.ctypes.data, a.size, out.ctypes.data, out.size, ctypes.byref(got)))
         return out[:got.value]
 
-    def pack_device(self, d_in, n, block_bytes, d_out, out_cap):
-        """bwts_pack_device: returns the frame's size in bytes."""
+    def pack_device(self, d_in, n, block_bytes, d_out, out_cap, version=1):
+        """bwts_pack_device_v: returns the frame's size in bytes."""
         got = ctypes.c_uint64(0)
-        self._check(lib().bwts_pack_device(self._h, _ptr(d_in), int(n), int(block_bytes), _ptr(d_out), int(out_cap), ctypes.byref(got)))
+        self._check(lib().bwts_pack_device_v(self._h, int(version), _ptr(d_in), int(n), int(block_bytes), _ptr(d_out), int(out_cap), ctypes.byref(got)))
         return int(got.value)
 
     def unpack_device(self, d_in, in_bytes, d_out, out_cap):
@@ -664,9 +728,25 @@ def debug_crc_plan(n):
     return {"T": int(buf[0]), "G": int(buf[1]), "tiles": int(buf[2]), "groups": int(buf[3])}
 
 
-def pack_bound(n, block_bytes=0):
-    """bwts_pack_bound: the largest frame an input of n bytes cut at block_bytes can have."""
-    b = int(lib().bwts_pack_bound(int(n), int(block_bytes)))
+def debug_zrl_plan(n):
+    """How the zero-run stage cuts one input of n bytes (bwts_debug_zrl_plan: host arithmetic, no context, no device)."""
+    buf = (ctypes.c_uint64 * 2)()
+    if lib().bwts_debug_zrl_plan(int(n), buf) < 0:
+        raise BwtsError(-1, "bad length")
+    return {"T": int(buf[0]), "tiles": int(buf[1])}
+
+
+def zrl_bound(n):
+    """bwts_zrl_bound: the most bytes the zero-run stage writes for an input of n bytes: n."""
+    b = int(lib().bwts_zrl_bound(int(n)))
+    if b == 0:
+        raise BwtsError(-5 if int(n) > 0 else -1, "no bound for this length")
+    return b
+
+
+def pack_bound(n, block_bytes=0, version=1):
+    """bwts_pack_bound_v: the largest frame of the given version an input of n bytes cut at block_bytes can have."""
+    b = int(lib().bwts_pack_bound_v(int(version), int(n), int(block_bytes)))
     if b == 0:
         raise BwtsError(-5 if int(n) > (1 << 32) else -1, "no bound for these arguments")
     return b

@@ -2,8 +2,9 @@
  * bwts_pack -- compress a file on the GPU: bijective BWT, move-to-front and rANS over blocks, one checksummed frame
  * (include/bwts_pack.h) per 2^32 input bytes.
  *
- *   bwts_pack [-b <KiB>] <infile> [<outfile>]
+ *   bwts_pack [-z] [-b <KiB>] <infile> [<outfile>]
  *   -b <KiB>: block size in KiB, at least 4 (default: every frame is one block)
+ *   -z: frames of version 2, zero-run coding between move-to-front and the coder (before or behind -b)
  *   no outfile: the frames go to standard output
  *   any error: a message on stderr, exit 1
  * The output is opened once the first frame exists, so a failing run leaves no truncated destination behind.
@@ -22,8 +23,9 @@
 
 static void usage(void)
 {
-	fprintf(stderr, "Usage: bwts_pack [-b <KiB>] <infile> [<outfile>]\n");
+	fprintf(stderr, "Usage: bwts_pack [-z] [-b <KiB>] <infile> [<outfile>]\n");
 	fprintf(stderr, "-b: block size in KiB, at least 4 (default: one block per frame)\n");
+	fprintf(stderr, "-z: zero-run coding in front of the coder (frame version 2)\n");
 	fprintf(stderr, "If unspecified, output is written to standard output\n");
 	exit(1);
 }
@@ -43,6 +45,7 @@ int main(int argc, char **argv)
 	FILE *fp = NULL;
 	int rc, arg = 1;
 	uint64_t block_bytes = 0, at, in_total, out_total = 0, cap;
+	uint32_t version = 1;
 	double device_ms = 0.0;
 	const char *dev = getenv("BWTS_DEVICE"), *show_env = getenv("BWTS_TIMINGS"), *out_name;
 	const int show = show_env && show_env[0] == '1';
@@ -50,19 +53,24 @@ int main(int argc, char **argv)
 
 	marks.main_start = cli_now_s();
 	marks.write_s = 0.0;
-	if (argc > 1 && strcmp(argv[1], "-b") == 0) {
+	while (arg < argc && (strcmp(argv[arg], "-b") == 0 || strcmp(argv[arg], "-z") == 0)) {
 		char *end = NULL;
 		unsigned long long kib;
 
-		if (argc < 3)
+		if (argv[arg][1] == 'z') {
+			version = 2;
+			arg++;
+			continue;
+		}
+		if (argc < arg + 2)
 			usage();
-		kib = strtoull(argv[2], &end, 10);
+		kib = strtoull(argv[arg + 1], &end, 10);
 		if (!end || *end || kib < 4 || kib > (1ull << 22)) {
 			fprintf(stderr, "bwts_pack: block size must be 4 .. 4194304 KiB\n");
 			exit(1);
 		}
 		block_bytes = (uint64_t)kib << 10;
-		arg = 3;
+		arg += 2;
 	}
 	if (argc - arg < 1 || argc - arg > 2)
 		usage();
@@ -74,7 +82,7 @@ int main(int argc, char **argv)
 	if ((rc = bwts_ctx_create(&ctx, dev ? atoi(dev) : 0)) != BWTS_OK)
 		fail("cannot open GPU context", rc);
 	marks.ctx_ready = cli_now_s();
-	cap = bwts_pack_bound(in_total < FRAME_INPUT_MAX ? in_total : FRAME_INPUT_MAX, block_bytes);
+	cap = bwts_pack_bound_v(version, in_total < FRAME_INPUT_MAX ? in_total : FRAME_INPUT_MAX, block_bytes);
 	out = cap ? malloc(cap) : NULL;
 	if (!out) {
 		fprintf(stderr, "bwts_pack: no memory for a frame of up to %llu bytes\n", (unsigned long long)cap);
@@ -85,7 +93,7 @@ int main(int argc, char **argv)
 		uint64_t bytes = 0;
 		double t0;
 
-		if ((rc = bwts_pack(ctx, text + at, n, block_bytes, out, cap, &bytes)) != BWTS_OK)
+		if ((rc = bwts_pack_v(ctx, version, text + at, n, block_bytes, out, cap, &bytes)) != BWTS_OK)
 			fail("packing failed", rc);
 		bwts_last_timings(ctx, &t);
 		device_ms += t.total_ms;

@@ -3,8 +3,10 @@
 #include "internal.h"
 #include "../../include/bwts_mtf.h"
 #include "../../include/bwts_ec.h"
+#include "../../include/bwts_zrl.h"
 #include "../../include/bwts_pack.h"
 #include "ec_plan.h"
+#include "zrl_plan.h"
 #include "pack_plan.h"
 
 #include <new>
@@ -490,6 +492,77 @@ extern "C" int bwts_ec_decode(bwts_ctx *ctx, const uint8_t *in, uint64_t in_byte
 }
 
 // ------------------------------------------------------------------------------------
+// zero-run coding between move-to-front and the entropy coder (include/bwts_zrl.h): the same routes as the coder's, the kernels in
+// zrl.hip
+// ------------------------------------------------------------------------------------
+extern "C" uint64_t bwts_zrl_bound(uint64_t n)
+{
+    return n == 0 || n > ZRL_MAX_N ? 0 : n;
+}
+
+extern "C" int bwts_zrl_encode_device(bwts_ctx *ctx, const void *d_in, uint64_t n, void *d_out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!ctx || !d_in || !d_out || !out_bytes || n == 0) return BWTS_E_ARG;
+    if (n > ZRL_MAX_N) return BWTS_E_RANGE;
+    if (ranges_overlap(d_in, n, d_out, out_cap)) return BWTS_E_ARG;
+    return run_sized(ctx, n, "zrl encode", [&] { return zrl_encode_impl(ctx, (const u8 *)d_in, n, (u8 *)d_out, out_cap, SEG_SINGLE, out_bytes); });
+}
+
+extern "C" int bwts_zrl_decode_device(bwts_ctx *ctx, const void *d_in, uint64_t in_bytes, void *d_out, uint64_t n)
+{
+    if (!ctx || !d_in || !d_out || in_bytes == 0 || n == 0) return BWTS_E_ARG;
+    if (n > ZRL_MAX_N) return BWTS_E_RANGE;
+    if (in_bytes > n) return BWTS_E_FORMAT;
+    if (ranges_overlap(d_in, in_bytes, d_out, n)) return BWTS_E_ARG;
+    return run_sized(ctx, n, "zrl decode", [&] { return zrl_decode_impl(ctx, (const u8 *)d_in, in_bytes, (u8 *)d_out, n, SEG_SINGLE, nullptr); });
+}
+
+extern "C" int bwts_zrl_encode_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, void *d_out, uint64_t out_cap,
+                                               uint64_t *out_lengths)
+{
+    if (!ctx || !d_in || !d_out || !out_lengths) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(seg_table_set(ctx, lengths, count, &n));
+    if (ranges_overlap(d_in, n, d_out, out_cap)) return BWTS_E_ARG;
+    return run_sized(ctx, n, "zrl encode", [&] { return zrl_encode_impl(ctx, (const u8 *)d_in, n, (u8 *)d_out, out_cap, seg_mode(ctx), out_lengths); });
+}
+
+extern "C" int bwts_zrl_decode_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *in_lengths, const uint64_t *lengths, uint64_t count,
+                                               void *d_out)
+{
+    if (!ctx || !d_in || !d_out || !in_lengths) return BWTS_E_ARG;
+    u64 n = 0, in_bytes = 0;
+    BWTS_TRY(seg_table_set(ctx, lengths, count, &n));
+    for (u64 s = 0; s < count; s++) {
+        if (in_lengths[s] == 0) return BWTS_E_ARG;
+        if (in_lengths[s] > lengths[s]) return BWTS_E_FORMAT;       // (so the sum cannot overflow)
+        in_bytes += in_lengths[s];
+    }
+    if (ranges_overlap(d_in, in_bytes, d_out, n)) return BWTS_E_ARG;
+    return run_sized(ctx, n, "zrl decode", [&] { return zrl_decode_impl(ctx, (const u8 *)d_in, in_bytes, (u8 *)d_out, n, seg_mode(ctx), in_lengths); });
+}
+
+extern "C" int bwts_zrl_encode(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!ctx || !in || !out || !out_bytes || n == 0) return BWTS_E_ARG;
+    if (n > ZRL_MAX_N) return BWTS_E_RANGE;
+    if (out_cap == 0) return BWTS_E_SPACE;
+    const u64 cap = out_cap < n ? out_cap : n;
+    const HostTrip trip = {in, n, n, out, out_bytes};
+    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *bytes) { return bwts_zrl_encode_device(ctx, d_in, n, d_out, cap, bytes); });
+}
+
+extern "C" int bwts_zrl_decode(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, uint8_t *out, uint64_t n)
+{
+    if (!ctx || !in || !out || in_bytes == 0 || n == 0) return BWTS_E_ARG;
+    if (n > ZRL_MAX_N) return BWTS_E_RANGE;
+    if (in_bytes > n) return BWTS_E_FORMAT;
+    u64 made = 0;
+    const HostTrip trip = {in, in_bytes, n, out, &made};
+    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *got) { *got = n; return bwts_zrl_decode_device(ctx, d_in, in_bytes, d_out, n); });
+}
+
+// ------------------------------------------------------------------------------------
 // checksum and the packed frame (include/bwts_pack.h): the chain of the three stages as one call, the kernel in crc.hip, the drivers
 // in pack.hip
 // ------------------------------------------------------------------------------------
@@ -508,10 +581,16 @@ extern "C" int bwts_crc32_segments_device(bwts_ctx *ctx, const void *d_in, const
     return run_sized(ctx, n, "crc32", [&] { return crc_impl(ctx, (const u8 *)d_in, n, seg_mode(ctx), crcs); });
 }
 
-extern "C" uint64_t bwts_pack_bound(uint64_t n, uint64_t block_bytes)
+extern "C" uint64_t bwts_pack_bound_v(uint32_t version, uint64_t n, uint64_t block_bytes)
 {
     const u64 B = pack_block_len(n, block_bytes);
-    return B ? pack_bound_bytes(n, B) : 0;
+    if (!B || !pack_version_ok(version)) return 0;
+    return version == PACK_VERSION_2 ? pack_bound_bytes_v2(n, B) : pack_bound_bytes(n, B);
+}
+
+extern "C" uint64_t bwts_pack_bound(uint64_t n, uint64_t block_bytes)
+{
+    return bwts_pack_bound_v(PACK_VERSION, n, block_bytes);
 }
 
 extern "C" int bwts_unpack_size(const uint8_t *frame, uint64_t in_bytes, uint64_t *n, uint64_t *frame_bytes)
@@ -524,13 +603,19 @@ extern "C" int bwts_unpack_size(const uint8_t *frame, uint64_t in_bytes, uint64_
     return BWTS_OK;
 }
 
-extern "C" int bwts_pack_device(bwts_ctx *ctx, const void *d_in, uint64_t n, uint64_t block_bytes, void *d_out, uint64_t out_cap, uint64_t *out_bytes)
+extern "C" int bwts_pack_device_v(bwts_ctx *ctx, uint32_t version, const void *d_in, uint64_t n, uint64_t block_bytes, void *d_out, uint64_t out_cap,
+                                  uint64_t *out_bytes)
 {
-    if (!ctx || !d_in || !d_out || !out_bytes || n == 0 || ((uintptr_t)d_out & 15)) return BWTS_E_ARG;
+    if (!ctx || !d_in || !d_out || !out_bytes || n == 0 || ((uintptr_t)d_out & 15) || !pack_version_ok(version)) return BWTS_E_ARG;
     if (n > PACK_MAX_N) return BWTS_E_RANGE;
     const u64 B = pack_block_len(n, block_bytes);
     if (B == 0 || ranges_overlap(d_in, n, d_out, out_cap)) return BWTS_E_ARG;
-    return run_sized(ctx, n, "pack", [&] { return pack_device_impl(ctx, (const u8 *)d_in, n, B, (u8 *)d_out, out_cap, out_bytes); });
+    return run_sized(ctx, n, "pack", [&] { return pack_device_impl(ctx, version, (const u8 *)d_in, n, B, (u8 *)d_out, out_cap, out_bytes); });
+}
+
+extern "C" int bwts_pack_device(bwts_ctx *ctx, const void *d_in, uint64_t n, uint64_t block_bytes, void *d_out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    return bwts_pack_device_v(ctx, PACK_VERSION, d_in, n, block_bytes, d_out, out_cap, out_bytes);
 }
 
 extern "C" int bwts_unpack_device(bwts_ctx *ctx, const void *d_in, uint64_t in_bytes, void *d_out, uint64_t out_cap, uint64_t *n)
@@ -540,16 +625,24 @@ extern "C" int bwts_unpack_device(bwts_ctx *ctx, const void *d_in, uint64_t in_b
     return run_sized(ctx, 0, "unpack", [&] { return unpack_device_impl(ctx, (const u8 *)d_in, in_bytes, (u8 *)d_out, out_cap, n); });
 }
 
-extern "C" int bwts_pack(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint64_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes)
+extern "C" int bwts_pack_v(bwts_ctx *ctx, uint32_t version, const uint8_t *in, uint64_t n, uint64_t block_bytes, uint8_t *out, uint64_t out_cap,
+                           uint64_t *out_bytes)
 {
-    if (!ctx || !in || !out || !out_bytes || n == 0) return BWTS_E_ARG;
+    if (!ctx || !in || !out || !out_bytes || n == 0 || !pack_version_ok(version)) return BWTS_E_ARG;
     if (n > PACK_MAX_N) return BWTS_E_RANGE;
     const u64 B = pack_block_len(n, block_bytes);
     if (B == 0) return BWTS_E_ARG;
-    const u64 cap = out_cap < pack_bound_bytes(n, B) ? out_cap : pack_bound_bytes(n, B);
-    if (cap < pack_least_bytes(n, B)) return BWTS_E_SPACE;
+    const bool v2 = version == PACK_VERSION_2;
+    const u64 bound = v2 ? pack_bound_bytes_v2(n, B) : pack_bound_bytes(n, B);
+    const u64 cap = out_cap < bound ? out_cap : bound;
+    if (cap < (v2 ? pack_least_bytes_v2(n, B) : pack_least_bytes(n, B))) return BWTS_E_SPACE;
     const HostTrip trip = {in, n, n > cap ? n : cap, out, out_bytes};
-    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *bytes) { return bwts_pack_device(ctx, d_in, n, block_bytes, d_out, cap, bytes); });
+    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *bytes) { return bwts_pack_device_v(ctx, version, d_in, n, block_bytes, d_out, cap, bytes); });
+}
+
+extern "C" int bwts_pack(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint64_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    return bwts_pack_v(ctx, PACK_VERSION, in, n, block_bytes, out, out_cap, out_bytes);
 }
 
 extern "C" int bwts_unpack(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n)

@@ -3,6 +3,7 @@
 #include "internal.h"
 #include "../../include/bwts_test.h"
 #include "ec_plan.h"
+#include "zrl_plan.h"
 #include "pack_plan.h"
 
 #include <stdlib.h>
@@ -117,6 +118,14 @@ extern "C" int bwts_debug_crc_plan(uint64_t n, uint64_t out[4])
 {
     if (n == 0 || n > CRC_MAX_N || !out) return -1;
     bwts_crc_plan(n, out);
+    return 0;
+}
+
+// the zero-run stage's cut of one input of n bytes: tile size, tiles.  No context, no device
+extern "C" int bwts_debug_zrl_plan(uint64_t n, uint64_t out[2])
+{
+    if (n == 0 || n > ZRL_MAX_N || !out) return -1;
+    bwts_zrl_plan(n, out);
     return 0;
 }
 

@@ -48,7 +48,9 @@ enum { KB_ARENA, KB_AUX, KB_IO = KB_AUX + BWTS_AUX_SLOTS, KB_SEG_TABLE = KB_IO +
 #define SM_EC_FLAG  4021         // ... d_small word for what a decode found wrong (0: nothing)
 #define SM_EC_HEAD  4022         // ... h_small, two words: the header of a single stream
 #define SM_CRC_OUT  4024         // checksum (crc.hip): h_small word for the value of a single input
-#define SM_PACK_HEAD 4026        // packed frame (pack.hip): h_small, six words: the header and a one-block directory on their way in or out
+#define SM_PACK_HEAD 4026        // packed frame (pack.hip): h_small, eight words: the header and a one-block directory (version 2: 32 bytes) on their way in or out
+#define SM_ZRL_TOTAL 4034        // zero-run coding (zrl.hip): d_small word for the bytes of an encode, or the weights' sum of a decode
+#define SM_ZRL_FLAG  4035        // ... d_small word, right behind it, for what a decode found wrong (0: nothing)
 
 struct Stager {
     hipStream_t stream;             // the queue its copies (and copy kernels) are issued on
@@ -326,11 +328,17 @@ int ec_encode_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, u64 out_cap,
 int ec_decode_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out, SegMode segs, const u64 *stream_bytes);
 void bwts_ec_plan(u64 n, u64 out[5]);                                   // tile size, tiles per block, tiles, blocks and the bound of one input
 
+// ---- zero-run coding between move-to-front and the entropy coder (zrl.hip; include/bwts_zrl.h) ----
+// sizes: the bytes the input becomes, or one per segment; decode: the one coded input of in_bytes, or in_lengths[count] (in_bytes: their sum)
+int zrl_encode_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, u64 out_cap, SegMode segs, u64 *sizes);
+int zrl_decode_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 n, SegMode segs, const u64 *in_lengths);
+void bwts_zrl_plan(u64 n, u64 out[2]);                                  // tile size and tiles of one input of n bytes
+
 // ---- checksum and the packed frame (crc.hip, pack.hip; include/bwts_pack.h) ------------
 // one value for the input of n bytes, or one per segment, to the host
 int crc_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, SegMode segs, u32 *crcs);
 void bwts_crc_plan(u64 n, u64 out[4]);                                  // tile size, tiles per fold group, tiles and groups of one input
-int pack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes);
+int pack_device_impl(bwts_ctx *ctx, u32 version, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes);
 int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out);
 
 // chunk tables of the forward's later rounds (chunk_rounds.h) as plain arithmetic: nominal chunk size of a list, the tables' capacity

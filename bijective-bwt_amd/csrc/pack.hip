@@ -1,12 +1,15 @@
-// pack.hip -- the chain as one call (include/bwts_pack.h): checksums, transform, move-to-front and entropy coder over the blocks of
-// a frame, and the way back.  No kernel of its own: the stages are the ones behind the single calls, run one after the other inside
+// pack.hip -- the chain as one call (include/bwts_pack.h): checksums, transform, move-to-front, zero-run coding (frame version 2) and
+// entropy coder over the blocks of a frame, and the way back.  No kernel of its own: the stages are the ones behind the single calls, run one after the other inside
 // one call bracket; the frame's arithmetic and the checks of an untrusted frame are in pack_plan.h.
 //
 // A frame of one block goes through the single-input stages, one of several blocks through the segment forms (the bytes are the
 // same by the segment forms' contract).  The stages share the context's arena, and the segment forms the pinned staging of their
 // tables: the stream is drained between two stages, so that no table copy of the stage before is still to come when the next stage
 // writes its own (seg_layout.h: the regions, and who overlaps whom).  Header and directory travel through pinned memory too: the
-// small block, and for several blocks the directory region behind the segment table.
+// small block, and for several blocks the directory region behind the segment table (version 1; the 32-byte entries of version 2 do
+// not fit that region and travel through a host block of the call's own).
+// Version 2 changes the segment table on the way: the coder's segments are the blocks' zero-run coded bytes, every other stage's
+// the blocks themselves.
 #include "internal.h"
 #include "pack_plan.h"
 #include "../../include/bwts_pack.h"
@@ -34,22 +37,36 @@ static int pack_blocks_set(bwts_ctx *ctx, u64 n, u64 B, u64 nblk)
     return total == n ? BWTS_OK : BWTS_E_INTERNAL;
 }
 
-// pinned room for a directory of nblk entries: the small block behind the header, or the directory region behind the segment table
-static int pack_dir_staging(bwts_ctx *ctx, u64 nblk, u8 **dir)
+// room on the host for a directory of nblk entries: the small block behind the header, or for several blocks the directory region
+// behind the segment table (pinned; version 1) or `own` (version 2)
+static int pack_dir_staging(bwts_ctx *ctx, u32 version, u64 nblk, std::vector<u8> &own, u8 **dir)
 {
     if (nblk == 1) { *dir = (u8 *)(ctx->h_small + SM_PACK_HEAD) + PACK_HEADER_BYTES; return BWTS_OK; }
+    if (version == PACK_VERSION_2) {
+        own.resize((size_t)(PACK_ENTRY_BYTES_V2 * nblk));
+        *dir = own.data();
+        return BWTS_OK;
+    }
     return seg_pinned_region(ctx, seg_dir_at(nblk), seg_dir_words(nblk), (void **)dir);
 }
 
-int pack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes)
+// the coder's segments of a version-2 frame of several blocks: the blocks' coded bytes
+static int pack_coded_set(bwts_ctx *ctx, const std::vector<u64> &coded, u64 *total)
 {
-    const u64 nblk = pack_blocks(n, B), fixed = pack_fixed_bytes(nblk);
+    if (coded.size() == 1) { *total = coded[0]; return BWTS_OK; }
+    return seg_table_set(ctx, coded.data(), coded.size(), total);
+}
+
+int pack_device_impl(bwts_ctx *ctx, u32 version, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes)
+{
+    const bool v2 = version == PACK_VERSION_2;
+    const u64 nblk = pack_blocks(n, B), fixed = pack_fixed_bytes_v(version, nblk), entry = pack_entry_bytes(version);
     const bool seg = nblk > 1;
-    if (out_cap < pack_least_bytes(n, B)) return BWTS_E_SPACE;
+    if (out_cap < (v2 ? pack_least_bytes_v2(n, B) : pack_least_bytes(n, B))) return BWTS_E_SPACE;
     BWTS_TRY(pack_blocks_set(ctx, n, B, nblk));
-    const SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
+    SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
     std::vector<u32> crcs((size_t)nblk);
-    std::vector<u64> sizes((size_t)nblk);
+    std::vector<u64> sizes((size_t)nblk), coded((size_t)nblk);
     BWTS_TRY(crc_impl(ctx, d_in, n, segs, crcs.data()));
     u8 *a = nullptr, *b = nullptr;
     BWTS_TRY(pack_stage(ctx, 0, n, &a));
@@ -58,19 +75,31 @@ int pack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64
     HIPC(hipStreamSynchronize(ctx->stream));
     BWTS_TRY(mtf_impl(ctx, a, n, b, false, segs));
     HIPC(hipStreamSynchronize(ctx->stream));
+    const u8 *ranks = b;
+    u64 m = n;
+    if (v2) {
+        // the ranks' coded bytes go back into the first block, one block's behind the other's: the coder's segments
+        BWTS_TRY(zrl_encode_impl(ctx, b, n, a, n, segs, coded.data()));
+        HIPC(hipStreamSynchronize(ctx->stream));
+        BWTS_TRY(pack_coded_set(ctx, coded, &m));
+        if (seg) segs = seg_mode(ctx);
+        ranks = a;
+    }
     // the streams go straight to their place; a frame that does not fit is refused by the coder before it writes anything
-    BWTS_TRY(ec_encode_impl(ctx, b, n, d_out + fixed, out_cap - fixed, segs, sizes.data()));
+    BWTS_TRY(ec_encode_impl(ctx, ranks, m, d_out + fixed, out_cap - fixed, segs, sizes.data()));
     HIPC(hipStreamSynchronize(ctx->stream));
     u8 *head = (u8 *)(ctx->h_small + SM_PACK_HEAD), *dir = nullptr;
-    BWTS_TRY(pack_dir_staging(ctx, nblk, &dir));
+    std::vector<u8> own;
+    BWTS_TRY(pack_dir_staging(ctx, version, nblk, own, &dir));
     u64 total = fixed;
     for (u64 k = 0; k < nblk; k++) {
-        pack_entry_write(dir + PACK_ENTRY_BYTES * k, sizes[(size_t)k], crcs[(size_t)k]);
+        if (v2) pack_entry_write_v2(dir + entry * k, sizes[(size_t)k], crcs[(size_t)k], coded[(size_t)k]);
+        else pack_entry_write(dir + entry * k, sizes[(size_t)k], crcs[(size_t)k]);
         total += sizes[(size_t)k];
     }
     if (total > out_cap) return BWTS_E_INTERNAL;
-    pack_header_write(head, n, B, dir);
-    HIPC(hipMemcpyAsync(d_out + PACK_HEADER_BYTES, dir, PACK_ENTRY_BYTES * nblk, hipMemcpyHostToDevice, ctx->stream));
+    pack_header_write_v(head, version, n, B, dir);
+    HIPC(hipMemcpyAsync(d_out + PACK_HEADER_BYTES, dir, entry * nblk, hipMemcpyHostToDevice, ctx->stream));
     HIPC(hipMemcpyAsync(d_out, head, PACK_HEADER_BYTES, hipMemcpyHostToDevice, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
     *out_bytes = total;
@@ -78,22 +107,24 @@ int pack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64
 }
 
 // The frame is not trusted: header, then directory, are brought to the host and judged by the predicates of pack_plan.h before
-// anything is made of them; the coder judges its streams itself.
+// anything is made of them; the coder and the zero-run decoder judge their inputs themselves.
 int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out)
 {
     if (in_bytes < PACK_LEAST_FRAME || (in_bytes & 15u)) return BWTS_E_FORMAT;
     u8 *head = (u8 *)(ctx->h_small + SM_PACK_HEAD), *dir = nullptr;
-    HIPC(hipMemcpyAsync(head, d_in, PACK_LEAST_FRAME, hipMemcpyDeviceToHost, ctx->stream));
+    const u64 first = in_bytes < PACK_HEADER_BYTES + PACK_ENTRY_BYTES_V2 ? in_bytes : PACK_HEADER_BYTES + PACK_ENTRY_BYTES_V2;
+    HIPC(hipMemcpyAsync(head, d_in, first, hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
     PackHeader H;
     BWTS_TRY(pack_header_check(head, in_bytes, &H));
-    const bool seg = H.nblk > 1;
-    const u64 fixed = pack_fixed_bytes(H.nblk);
+    const bool seg = H.nblk > 1, v2 = H.version == PACK_VERSION_2;
+    const u64 fixed = pack_fixed_bytes_v(H.version, H.nblk), entry = pack_entry_bytes(H.version);
     BWTS_TRY(pack_blocks_set(ctx, H.n, H.B, H.nblk));
     const SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
-    BWTS_TRY(pack_dir_staging(ctx, H.nblk, &dir));
+    std::vector<u8> own;
+    BWTS_TRY(pack_dir_staging(ctx, H.version, H.nblk, own, &dir));
     if (seg) {
-        HIPC(hipMemcpyAsync(dir, d_in + PACK_HEADER_BYTES, PACK_ENTRY_BYTES * H.nblk, hipMemcpyDeviceToHost, ctx->stream));
+        HIPC(hipMemcpyAsync(dir, d_in + PACK_HEADER_BYTES, entry * H.nblk, hipMemcpyDeviceToHost, ctx->stream));
         HIPC(hipStreamSynchronize(ctx->stream));
     }
     u64 frame = 0;
@@ -101,24 +132,40 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
     if (H.n > out_cap) return BWTS_E_SPACE;
     ctx->tm.n = H.n;
     // (the staging is the next stage's: what the directory says is kept here)
-    std::vector<u64> sizes((size_t)H.nblk);
+    std::vector<u64> sizes((size_t)H.nblk), coded((size_t)H.nblk);
     std::vector<u32> want((size_t)H.nblk), got((size_t)H.nblk);
     for (u64 k = 0; k < H.nblk; k++) {
-        sizes[(size_t)k] = pack_le64(dir + PACK_ENTRY_BYTES * k);
-        want[(size_t)k] = ec_le32(dir + PACK_ENTRY_BYTES * k + 8);
+        sizes[(size_t)k] = pack_le64(dir + entry * k);
+        want[(size_t)k] = ec_le32(dir + entry * k + 8);
+        coded[(size_t)k] = v2 ? pack_le64(dir + entry * k + 16) : pack_block_at(H.n, H.B, k);
     }
-    // ranks into d_out, bytes of the transform into the stage block, the input's bytes into d_out
-    if (seg) {
-        BWTS_TRY(ec_decode_impl(ctx, d_in + fixed, H.n, d_out, H.n, nullptr, segs, sizes.data()));
-    } else {
-        u64 m = 0;
-        const int rc = ec_decode_impl(ctx, d_in + fixed, sizes[0], d_out, H.n, &m, segs, nullptr);
-        // (room for the frame's n is what the coder was given: a stream that names more, or less, is not this frame's)
-        if (rc == BWTS_E_SPACE || (rc == BWTS_OK && m != H.n)) return BWTS_E_FORMAT;
-        BWTS_TRY(rc);
-    }
+    // version 1: ranks into d_out, bytes of the transform into the stage block, the input's bytes into d_out.  Version 2: the ranks'
+    // coded bytes into the stage block first, and from there the ranks into d_out.
     u8 *a = nullptr;
     BWTS_TRY(pack_stage(ctx, 0, H.n, &a));
+    u8 *ranks = v2 ? a : d_out;
+    u64 m = H.n;
+    SegMode csegs = segs;
+    if (v2) {
+        BWTS_TRY(pack_coded_set(ctx, coded, &m));
+        if (seg) csegs = seg_mode(ctx);
+    }
+    if (seg) {
+        BWTS_TRY(ec_decode_impl(ctx, d_in + fixed, m, ranks, m, nullptr, csegs, sizes.data()));
+    } else {
+        u64 named = 0;
+        const int rc = ec_decode_impl(ctx, d_in + fixed, sizes[0], ranks, m, &named, csegs, nullptr);
+        // (room for the bytes the directory names is what the coder was given: a stream that names more, or less, is not this frame's)
+        if (rc == BWTS_E_SPACE || (rc == BWTS_OK && named != m)) return BWTS_E_FORMAT;
+        BWTS_TRY(rc);
+    }
+    if (v2) {
+        HIPC(hipStreamSynchronize(ctx->stream));
+        ctx->tm.n = H.n;        // (the coder has put its own n there: the coded bytes)
+        BWTS_TRY(pack_blocks_set(ctx, H.n, H.B, H.nblk));
+        BWTS_TRY(zrl_decode_impl(ctx, a, m, d_out, H.n, segs, coded.data()));
+        HIPC(hipStreamSynchronize(ctx->stream));
+    }
     BWTS_TRY(mtf_impl(ctx, d_out, H.n, a, true, segs));
     HIPC(hipStreamSynchronize(ctx->stream));
     BWTS_TRY(seg ? inverse_segments_impl(ctx, a, H.n, d_out) : inverse_device_impl(ctx, a, H.n, d_out));

@@ -1,4 +1,4 @@
-// pack_plan.h -- the arithmetic of the packed frame (include/bwts_pack.h, version 1) and of its checksum that host and device share:
+// pack_plan.h -- the arithmetic of the packed frame (include/bwts_pack.h, versions 1 and 2) and of its checksum that host and device share:
 // CRC-32 as polynomial arithmetic over GF(2), how an input is cut into blocks, the bound, and what makes a header and a directory
 // valid.  Plain C++ with no dependency but ec_plan.h: crc.hip, pack.hip, the host side of the calls and a stand-alone host program
 // (tests/pack_plan_check.cc, built with the sanitizers) all compile this file.
@@ -8,8 +8,10 @@
 
 #define PACK_MAGIC 0x5A545742u           // "BWTZ"
 #define PACK_VERSION 1u
+#define PACK_VERSION_2 2u                // zero-run coding between the ranks and the coder: a directory entry names the coded bytes too
 #define PACK_HEADER_BYTES 32u
 #define PACK_ENTRY_BYTES 16u
+#define PACK_ENTRY_BYTES_V2 32u
 #define PACK_MIN_BLOCK 4096u
 #define PACK_MAX_N (1ull << 32)
 #define PACK_LEAST_FRAME 48u             // header and one directory entry
@@ -106,33 +108,56 @@ EC_HD uint64_t pack_least_bytes(uint64_t n, uint64_t B)
     return pack_fixed_bytes(nblk) + (nblk - 1u) * ec_least_bytes(B) + ec_least_bytes(n - (nblk - 1u) * B);
 }
 
+// ---- version 2: the same header with version = 2, entries of 32 bytes, the coder's streams over the zero-run coded bytes ----
+EC_HD bool pack_version_ok(uint32_t version) { return version == PACK_VERSION || version == PACK_VERSION_2; }
+EC_HD uint32_t pack_entry_bytes(uint32_t version) { return version == PACK_VERSION_2 ? PACK_ENTRY_BYTES_V2 : PACK_ENTRY_BYTES; }
+EC_HD uint64_t pack_fixed_bytes_v(uint32_t version, uint64_t nblk) { return PACK_HEADER_BYTES + (uint64_t)pack_entry_bytes(version) * nblk; }
+// the zero-run stage never expands, and the coder's bound grows with its input: the version-1 streams' bound holds
+EC_HD uint64_t pack_bound_bytes_v2(uint64_t n, uint64_t B)
+{
+    const uint64_t nblk = pack_blocks(n, B);
+    return pack_bound_bytes(n, B) + (uint64_t)(PACK_ENTRY_BYTES_V2 - PACK_ENTRY_BYTES) * nblk;
+}
+// every block at least one coded byte
+EC_HD uint64_t pack_least_bytes_v2(uint64_t n, uint64_t B)
+{
+    const uint64_t nblk = pack_blocks(n, B);
+    return pack_fixed_bytes_v(PACK_VERSION_2, nblk) + nblk * ec_least_bytes(1u);
+}
+
 EC_HD void pack_entry_write(uint8_t e[16], uint64_t stream_bytes, uint32_t crc)
 {
     pack_put64(e, stream_bytes); ec_put32(e + 8, crc); ec_put32(e + 12, 0u);
 }
-// the header of a frame whose directory (nblk entries) is complete
-EC_HD void pack_header_write(uint8_t h[32], uint64_t n, uint64_t B, const uint8_t *dir)
+EC_HD void pack_entry_write_v2(uint8_t e[32], uint64_t stream_bytes, uint32_t crc, uint64_t coded_bytes)
 {
-    ec_put32(h, PACK_MAGIC); ec_put32(h + 4, PACK_VERSION); pack_put64(h + 8, n); pack_put64(h + 16, B);
-    ec_put32(h + 24, crc32_bytes(dir, (uint64_t)PACK_ENTRY_BYTES * pack_blocks(n, B)));
+    pack_entry_write(e, stream_bytes, crc);
+    pack_put64(e + 16, coded_bytes); pack_put64(e + 24, 0u);
+}
+// the header of a frame whose directory (nblk entries) is complete
+EC_HD void pack_header_write_v(uint8_t h[32], uint32_t version, uint64_t n, uint64_t B, const uint8_t *dir)
+{
+    ec_put32(h, PACK_MAGIC); ec_put32(h + 4, version); pack_put64(h + 8, n); pack_put64(h + 16, B);
+    ec_put32(h + 24, crc32_bytes(dir, (uint64_t)pack_entry_bytes(version) * pack_blocks(n, B)));
     ec_put32(h + 28, crc32_bytes(h, 28));
 }
+EC_HD void pack_header_write(uint8_t h[32], uint64_t n, uint64_t B, const uint8_t *dir) { pack_header_write_v(h, PACK_VERSION, n, B, dir); }
 
-struct PackHeader { uint64_t n, B, nblk; uint32_t dir_crc; };
+struct PackHeader { uint64_t n, B, nblk; uint32_t dir_crc, version; };
 
 // The header of a frame of which in_bytes bytes are at hand (h: the first 32 of them, read only when in_bytes allows a frame at all).
 // PACK_OK and *H, PACK_FORMAT, or PACK_RANGE for a sound header that names more than 2^32 bytes.
 EC_HD int pack_header_check(const uint8_t *h, uint64_t in_bytes, PackHeader *H)
 {
     if (in_bytes < PACK_LEAST_FRAME || (in_bytes & 15u)) return PACK_FORMAT;
-    if (ec_le32(h) != PACK_MAGIC || ec_le32(h + 4) != PACK_VERSION) return PACK_FORMAT;
+    if (ec_le32(h) != PACK_MAGIC || !pack_version_ok(ec_le32(h + 4))) return PACK_FORMAT;
     if (ec_le32(h + 28) != crc32_bytes(h, 28)) return PACK_FORMAT;
     const uint64_t n = pack_le64(h + 8), B = pack_le64(h + 16);
     if (n == 0) return PACK_FORMAT;
     if (n > PACK_MAX_N) return PACK_RANGE;
     if (B == 0 || B > n || (B < PACK_MIN_BLOCK && B != n)) return PACK_FORMAT;
-    H->n = n; H->B = B; H->nblk = pack_blocks(n, B); H->dir_crc = ec_le32(h + 24);
-    if (pack_fixed_bytes(H->nblk) > in_bytes) return PACK_FORMAT;
+    H->n = n; H->B = B; H->nblk = pack_blocks(n, B); H->dir_crc = ec_le32(h + 24); H->version = ec_le32(h + 4);
+    if (pack_fixed_bytes_v(H->version, H->nblk) > in_bytes) return PACK_FORMAT;      // (judged with the version's entry size, before the directory is read)
     return PACK_OK;
 }
 
@@ -140,12 +165,20 @@ EC_HD int pack_header_check(const uint8_t *h, uint64_t in_bytes, PackHeader *H)
 // (an unpack), else it may end earlier (stepping through concatenated frames).  PACK_OK and *frame_bytes, or PACK_FORMAT.
 EC_HD int pack_directory_check(const uint8_t *dir, const PackHeader &H, uint64_t in_bytes, bool exact, uint64_t *frame_bytes)
 {
-    if (crc32_bytes(dir, (uint64_t)PACK_ENTRY_BYTES * H.nblk) != H.dir_crc) return PACK_FORMAT;
-    uint64_t total = pack_fixed_bytes(H.nblk);
+    const uint64_t entry = pack_entry_bytes(H.version);
+    if (crc32_bytes(dir, entry * H.nblk) != H.dir_crc) return PACK_FORMAT;
+    uint64_t total = pack_fixed_bytes_v(H.version, H.nblk);
     for (uint64_t b = 0; b < H.nblk; b++) {
-        const uint8_t *e = dir + (uint64_t)PACK_ENTRY_BYTES * b;
-        const uint64_t sb = pack_le64(e), len = pack_block_at(H.n, H.B, b);
+        const uint8_t *e = dir + entry * b;
+        const uint64_t sb = pack_le64(e);
+        uint64_t len = pack_block_at(H.n, H.B, b);
         if (ec_le32(e + 12) != 0u || (sb & 15u)) return PACK_FORMAT;
+        if (H.version == PACK_VERSION_2) {
+            // the stream is the coder's over the zero-run coded bytes: 1 <= coded_bytes <= the block's length
+            const uint64_t coded = pack_le64(e + 16);
+            if (pack_le64(e + 24) != 0u || coded == 0u || coded > len) return PACK_FORMAT;
+            len = coded;
+        }
         if (sb < ec_least_bytes(len) || sb > ec_bound_bytes(len)) return PACK_FORMAT;      // (so the sum cannot overflow)
         total += sb;
     }

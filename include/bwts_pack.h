@@ -23,13 +23,25 @@
  * value >= n is stored as n (a nonzero block_bytes below 4096 is BWTS_E_ARG).  So B = n or 4096 <= B < n.
  * Bound: 32 + 16 nblk + the sum of bwts_ec_bound over the blocks.
  *
- * A frame is not trusted.  Unpack refuses with BWTS_E_FORMAT, in this order: in_bytes < 48 or not a multiple of 16; wrong magic or
- * version; a wrong header CRC; n = 0 (n > 2^32 is BWTS_E_RANGE); B = 0, B > n, or B < 4096 with B != n; a directory longer than the
+ * The frame, version 2: zero-run coding (bwts_zrl.h) between the ranks and the coder.  Asked for with the _v calls; unpack takes both.
+ *   1. Header: as above, with version = 2.
+ *   2. Directory, nblk x 32 bytes: u64 stream_bytes, u32 CRC-32 of the block's original bytes, u32 zero, u64 coded_bytes (the zero-run
+ *      stage's out_bytes for the block: 1 <= coded_bytes <= the block's length), u64 zero.
+ *   3. Streams: the version-1 stream of bwts_ec.h of ZRL(MTF(BWTS(block))) for every block, in order; its header names coded_bytes;
+ *      together exactly what bwts_ec_encode_segments_device writes for the coded_bytes lengths.
+ * Bound: 32 + 32 nblk + the sum of bwts_ec_bound over the blocks' lengths (the zero-run stage never expands).
+ *
+ * A frame is not trusted.  Unpack refuses with BWTS_E_FORMAT, in this order: in_bytes < 48 or not a multiple of 16; wrong magic, or
+ * a version that is neither 1 nor 2; a wrong header CRC; n = 0 (n > 2^32 is BWTS_E_RANGE); B = 0, B > n, or B < 4096 with B != n; a directory longer than the
  * frame; a wrong directory CRC; an entry with a nonzero reserved word, or a stream_bytes that is not a multiple of 16 or outside
  * what the coder can make of the block's length; 32 + 16 nblk + the sum of stream_bytes != in_bytes.  Then a header n > out_cap is
  * BWTS_E_SPACE.  After the checks: decode (the coder's own BWTS_E_FORMAT passes through, and a stream whose header names another
  * length than its block's is BWTS_E_FORMAT), inverse move-to-front, inverse transform, and the CRC-32 of every block of the result
  * against the directory: a difference is BWTS_E_CHECKSUM.
+ * Version 2 keeps that order with its own entries: the directory is judged to lie inside the frame with 32 bytes per block, before
+ * its CRC is read; both reserved words must be zero, coded_bytes in range, and stream_bytes what the coder can make of coded_bytes.
+ * After the checks: decode against coded_bytes (a stream whose header names another length is BWTS_E_FORMAT), zero-run decode of
+ * every block against its length (its BWTS_E_FORMAT passes through), inverse move-to-front, inverse transform, the CRC check.
  *
  * Semantics are those of bwts_ec.h: the calls run on the context's stream and are synchronous; BWTS_E_ARG on NULL pointers, n == 0,
  * in_bytes == 0, count == 0 or a zero length; the device forms refuse buffers that overlap, and a coded side (d_out of a pack, d_in of
@@ -39,15 +51,15 @@
  * Pack never fails with BWTS_E_SPACE for out_cap >= bwts_pack_bound; with less it returns BWTS_E_SPACE as soon as the frame is known
  * not to fit, and has then written nothing at all (header and directory are written last).  A device unpack that fails may have
  * written part of d_out; the host forms leave out as it was after any failure.
- * Cost: pack is one checksum pass and the three stages; between them the bytes stay in two n-byte blocks that the context keeps
- * (unpack: one; it decodes into d_out), counted in bwts_timings::device_bytes and given up by bwts_ctx_release_memory.  The checksum
+ * Cost: pack is one checksum pass and the three stages (version 2: four); between them the bytes stay in two n-byte blocks that the
+ * context keeps (unpack: one; it decodes into d_out, version 2 into the block and from there into d_out), counted in bwts_timings::device_bytes and given up by bwts_ctx_release_memory.  The checksum
  * takes four bytes per 64 KiB tile from the context's arena.  bwts_last_timings: n (the unpacked bytes) and total_ms are filled,
  * the kernels are accounted under BWTS_K_OTHER.
  */
 #ifndef BWTS_PACK_H
 #define BWTS_PACK_H
 
-#include "bwts_ec.h"
+#include "bwts_zrl.h"
 
 #define BWTS_E_CHECKSUM -10   /* a block decoded in bounds but its bytes are not the ones that were packed */
 
@@ -70,6 +82,13 @@ int bwts_unpack_device(bwts_ctx *ctx, const void *d_in, uint64_t in_bytes, void 
 /* host buffers */
 int bwts_pack(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint64_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes);
 int bwts_unpack(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, uint8_t *out, uint64_t out_cap, uint64_t *n);
+/* the frame's version chosen by the caller: with version 1 these are the calls above, byte for byte; 2: zero-run coding in front of
+ * the coder; any other version: BWTS_E_ARG (the bound: 0) */
+uint64_t bwts_pack_bound_v(uint32_t version, uint64_t n, uint64_t block_bytes);
+int bwts_pack_device_v(bwts_ctx *ctx, uint32_t version, const void *d_in, uint64_t n, uint64_t block_bytes, void *d_out, uint64_t out_cap,
+                       uint64_t *out_bytes);
+int bwts_pack_v(bwts_ctx *ctx, uint32_t version, const uint8_t *in, uint64_t n, uint64_t block_bytes, uint8_t *out, uint64_t out_cap,
+                uint64_t *out_bytes);
 
 #ifdef __cplusplus
 }

@@ -117,6 +117,9 @@ int bwts_debug_ec_plan(uint64_t n, uint64_t out[5]);
  * size in bytes; G, the tile values one wave folds at the second level; tiles = ceil(n / T); groups = ceil(tiles / G)}.  Returns 0, -1
  * on a bad argument. */
 int bwts_debug_crc_plan(uint64_t n, uint64_t out[4]);
+/* Pure arithmetic, no context and no device: how the zero-run stage (bwts_zrl.h) cuts one input of 1 <= n <= 2^36 bytes.  out = {T, the
+ * tile size in bytes the kernels use; tiles = ceil(n / T)}.  Returns 0, -1 on a bad argument. */
+int bwts_debug_zrl_plan(uint64_t n, uint64_t out[2]);
 
 #ifdef __cplusplus
 }

@@ -89,6 +89,8 @@ FWD_HEADER_FIELDS = ["cyclic", "n", "k", "sigma", "bits", "msym", "key_bits", "v
                      "order_sort", "left"]
 FWD_DIRECT_WORD = 36            # header word: what became of the direct form
 FWD_DIRECT = {0: "not_tried", 1: "settled", 2: "fallback_group", 3: "fallback_depth"}
+FWD_LEAN_WORD = 37              # header word: what became of round 0's lean last pass (flags and tied positions, no sorted keys)
+FWD_LEAN = {0: "not_tried", 1: "held", 2: "gave_up_seam", 3: "gave_up_count", 4: "gave_up_direct"}
 FWD_CHUNK_FIELDS = ["S", "maxchunks", "a_small", "big0", "m_exit", "m_stay", "groups", "wide_possible", "fsl", "compactions",
                     "compactions_skipped", "enqueued_behind_last"]
 FWD_ROUND_FIELDS = {"sparse": ["form", "h", "in", "out", "splits", "probe", "m_big", "whole", "skip_next"],
@@ -650,7 +652,7 @@ class Context:
     def debug_forward_report(self):
         """One dict per doubling sort of the most recent forward call on this context (also debug_suffix_array / debug_lyndon), in the
         order they ran: the header (FWD_HEADER_FIELDS; form, keys, no_chunks and end by name, flags as bool; "direct" / "direct_word": header
-        word 36 by name and as the number), "chunks" (FWD_CHUNK_FIELDS)
+        word 36 by name and as the number; "lean" / "lean_word": likewise header word 37), "chunks" (FWD_CHUNK_FIELDS)
         when the chunk form ran, and "round": one dict per recorded round after round 0 (FWD_ROUND_FIELDS of its form)."""
         buf = (ctypes.c_uint64 * (2 * FWD_SORT_WORDS))()
         made = ctypes.c_uint64(0)
@@ -663,6 +665,7 @@ class Context:
             d = {f: w[i] for i, f in enumerate(FWD_HEADER_FIELDS)}
             d["form"], d["keys"], d["no_chunks"], d["end"] = FWD_FORMS[d["form"]], FWD_KEYS[d["keys"]], FWD_NO_CHUNKS[d["no_chunks"]], FWD_ENDS[d["end"]]
             d["direct"], d["direct_word"] = FWD_DIRECT[w[FWD_DIRECT_WORD]], w[FWD_DIRECT_WORD]
+            d["lean"], d["lean_word"] = FWD_LEAN[w[FWD_LEAN_WORD]], w[FWD_LEAN_WORD]
             for f in ("cyclic", "varlen", "flags_outside_rank", "rank_early", "need_sa", "order_sort"):
                 d[f] = bool(d[f])
             if d["form"] == "chunks":

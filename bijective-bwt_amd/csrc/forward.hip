@@ -15,6 +15,7 @@
 #include "internal.h"
 #include "device_utils.h"
 #include "scan_templ.h"
+#include "../../include/bwts_test.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -44,6 +45,7 @@ struct Alphabet {
     bool varlen;    // order-preserving variable-length codes (optimal alphabetic tree) instead of fixed-width ones
     int hstep;      // symbols every key is guaranteed to cover: the step of round 1 (msym, or key_bits / longest code)
     int patch_span; // positions in front of a factor's end whose key wraps around (msym - 1, or 64)
+    bool few_ties;  // the model of this key, and the key sample where one was taken, expect at most n / 64 positions tied after round 0
 };
 #define SM_DGCNT  2816      // 8 + 1024 words: counters of the group-local dense rounds (dense_round_kernel)
 #define SM_SEGCNT 2560      // 256 words: large-group element counts of seg_small_sort_kernel (spread: one address would serialise)
@@ -248,7 +250,9 @@ static int iid_key_bits(const u64 *hist, const u8 *vlen, const u32 *vcode, u64 n
 // of 2^17 sampled positions and count neighbours that agree on their first B bits: if the sample shows
 // clearly more ties than the model allows, take the empirical figure (real text wants the full 64 bits).
 // scratch: the round-0 sort buffers, free at that point; vtab: the code table in h_small.  The only part that launches kernels.
-static int sampled_key_bits(bwts_ctx *ctx, const u8 *d_T, u64 n, const SortBufs &scratch, const u64 *vtab, const double share[65], int *kb_emp)
+// partners_of[b] (b = 32, 40, 48, 56): the equal keys of b bits a position is expected to meet, by the sample where it saw enough, else by the model.
+static int sampled_key_bits(bwts_ctx *ctx, const u8 *d_T, u64 n, const SortBufs &scratch, const u64 *vtab, const double share[65], int *kb_emp,
+                            double partners_of[65])
 {
     HIPC(hipMemcpyAsync(ctx->d_small + SM_VTAB, vtab, 256 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
     HIPC(hipMemsetAsync(ctx->d_small + CNT_SAMPLE, 0, 8 * sizeof(u64), ctx->stream));
@@ -265,7 +269,8 @@ static int sampled_key_bits(bwts_ctx *ctx, const u8 *d_T, u64 n, const SortBufs 
     for (int b = 32, w = 1; b <= 56; b += 8, w++) {
         const double m = (double)ctx->h_small[CNT_SAMPLE + w];
         const double partners = m >= 8.0 ? (double)n * m / pairs : (double)n * share[b];   // few hits: trust the model
-        if (1.0 - exp(-partners) <= 1.0 / 64.0) { *kb_emp = b; break; }
+        partners_of[b] = partners;
+        if (*kb_emp == 64 && 1.0 - exp(-partners) <= 1.0 / 64.0) *kb_emp = b;
     }
     return BWTS_OK;
 }
@@ -281,6 +286,14 @@ static int set_alphabet(bwts_ctx *ctx, bool reserve_pad, u64 n, Alphabet *al, co
     const char *env = bwts_knob(ctx, "BWTS_KEY_SYMBOLS");              // tuning / test knob: force the symbol count (0 = maximum)
     if (env) { int v = atoi(env); if (v >= 1 && v <= 64 / bits) msym = v; else if (v == 0) msym = 64 / bits; }
     al->msym = al->hstep = msym; al->key_bits = bits * msym; al->varlen = false; al->patch_span = msym - 1;
+    // tied after round 0, as pick_key_symbols models it: a position meets n * (sum of p^2)^msym others with its key
+    const auto few = [](double partners) { return 1.0 - exp(-partners) <= 1.0 / 64.0; };
+    const auto fixed_partners = [&](int m) {
+        double sum2 = 0.0;
+        for (int c = 0; c < 256; c++) { const double p = (double)hist[c] / (double)n; sum2 += p * p; }
+        return (double)n * pow(sum2, (double)m);
+    };
+    al->few_ties = few(fixed_partners(msym));
     // variable-length codes when they save whole radix passes (skewed alphabets: text); the suffix sort of the general
     // Lyndon path keeps fixed-width codes with the pad symbol
     const char *vl = bwts_knob(ctx, "BWTS_VARLEN");                    // 0 = never, 1 = always (tests), unset = when it pays
@@ -291,9 +304,10 @@ static int set_alphabet(bwts_ctx *ctx, bool reserve_pad, u64 n, Alphabet *al, co
     if (try_vl && lmax <= VL_MAXLEN) {
         u64 *vtab = ctx->h_small + SM_VTAB;          // (length << 32) | code of each byte value
         for (int c = 0; c < 256; c++) vtab[c] = ((u64)vlen[c] << 32) | vcode[c];
-        double share[65];
+        double share[65], partners_of[65];
+        for (int b = 0; b <= 64; b++) partners_of[b] = -1.0;              // (no sample, or none at this width: the model)
         int kb = iid_key_bits(hist, vlen, vcode, n, share), kb_emp = 0;
-        if (d_T && scratch && n >= (1ull << 22)) BWTS_TRY(sampled_key_bits(ctx, d_T, n, *scratch, vtab, share, &kb_emp));
+        if (d_T && scratch && n >= (1ull << 22)) BWTS_TRY(sampled_key_bits(ctx, d_T, n, *scratch, vtab, share, &kb_emp, partners_of));
         if (kb_emp > kb) {
             // Repeats, not entropy, tie these positions, and no key width separates the copies of a long repeat: the
             // rounds on the tied list will.  Wider keys then only pay where they lengthen the first step (key bits /
@@ -309,6 +323,7 @@ static int set_alphabet(bwts_ctx *ctx, bool reserve_pad, u64 n, Alphabet *al, co
                 kb = kb_emp;
                 // the fixed-width alternative was sized by the same model: let it use every symbol that fits
                 al->msym = al->hstep = 64 / bits; al->key_bits = bits * al->msym; al->patch_span = al->msym - 1;
+                al->few_ties = few(fixed_partners(al->msym));
             }
         }
         const char *kbe = bwts_knob(ctx, "BWTS_KEY_BITS");
@@ -317,6 +332,7 @@ static int set_alphabet(bwts_ctx *ctx, bool reserve_pad, u64 n, Alphabet *al, co
         // equal pass counts: the variable-length key still holds more symbols when its words are shorter on average
         if ((vl && vl[0] == '1') || passes_var < passes_fixed || (passes_var == passes_fixed && avg < (double)bits - 0.25)) {
             al->varlen = true; al->key_bits = kb; al->patch_span = 64;
+            al->few_ties = few(partners_of[kb] >= 0.0 ? partners_of[kb] : (double)n * share[kb]);
             al->msym = al->hstep = kb / lmax < 1 ? 1 : kb / lmax;
             HIPC(hipMemcpyAsync(ctx->d_small + SM_VTAB, vtab, 256 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
         }
@@ -1351,13 +1367,16 @@ enum FwdReportWord { FR_CYCLIC, FR_N, FR_K, FR_SIGMA, FR_BITS, FR_MSYM, FR_KEY_B
                      FR_ROUNDS, FR_DIRECTORY, FR_ORDER_SORT, FR_LEFT,
                      FC_S = 24, FC_MAXCHUNKS, FC_A_SMALL, FC_BIG0, FC_M_EXIT, FC_M_STAY, FC_GROUPS, FC_WIDE_POSSIBLE, FC_FSL, FC_COMPACTIONS,
                      FC_COMPACTIONS_SKIPPED, FC_ENQUEUED_BEHIND_LAST,
-                     FR_DIRECT = 36 /* FwdDirect: what became of the direct form */ };
+                     FR_DIRECT = 36 /* FwdDirect: what became of the direct form */,
+                     FR_LEAN = 37 /* FwdLean: what became of the lean last pass of round 0 */ };
 enum FwdRoundWord { FRR_FORM, FRR_H, FRR_IN, FRR_OUT, FRR_SPLITS, FRR_PROBE = 5, FRR_MBIG, FRR_WHOLE, FRR_SKIP_NEXT,
                     FRR_CHUNKS_IN = 5, FRR_CHUNKS_OUT, FRR_BIG_IN, FRR_BIG_STAYS, FRR_BIG_LEAVES, FRR_NCHUNKS, FRR_TILE_MBIG = 5 };
 enum FwdForm { FR_FORM_NONE, FR_FORM_SPARSE, FR_FORM_CHUNKS, FR_FORM_TILES, FR_FORM_DIRECT };
 enum FwdNoChunks { FR_NC_NA, FR_NC_SHORT, FR_NC_KNOB, FR_NC_STORE, FR_NC_ORDER, FR_NC_BIGLIST };
 enum FwdEnd { FR_END_NONE, FR_END_EMPTY, FR_END_STABLE };
-static_assert(FC_ENQUEUED_BEHIND_LAST < FR_DIRECT && FR_DIRECT < FWD_HEADER_WORDS && FRR_NCHUNKS < FWD_ROUND_WORDS && FR_LEFT < FC_S, "the forward report's layout");
+enum FwdLean { FR_LEAN_NONE, FR_LEAN_HELD, FR_LEAN_SEAM, FR_LEAN_COUNT, FR_LEAN_DIRECT };
+static_assert(FR_LEAN == BWTS_FWD_LEAN_WORD, "include/bwts_test.h names the word");
+static_assert(FC_ENQUEUED_BEHIND_LAST < FR_DIRECT && FR_LEAN < FWD_HEADER_WORDS && FRR_NCHUNKS < FWD_ROUND_WORDS && FR_LEFT < FC_S, "the forward report's layout");
 static u64 *fwd_report_open(bwts_ctx *ctx)
 {
     u64 *w = ctx->fwd_report[ctx->fwd_sorts_made < FWD_REPORT_SORTS ? ctx->fwd_sorts_made : FWD_REPORT_SORTS - 1];
@@ -1384,56 +1403,117 @@ struct Round0 {
     u64 *headw, *keepw, *pre;       // group flags (64 slots per word) and the word scan
     bool flags_outside_rank;        // the flag words lie in the carried-byte buffers, not in sp.rank
     u64 a;                          // tied elements
+    // the last pass ran lean (SortPlan::lean_last): the flags are its own, SA holds the tied slots' positions only, the sorted keys
+    // were not written; seam: it raised its give-up flag, and flags and count mean nothing
+    bool lean, seam;
 };
+#define CNT_SEAM (SM_COUNTERS + 3)      // the lean pass's give-up flag: read back with the tied count
+// the bits of headw's last word past n: no slots, no group starts.  (One launch of 5 us per forward.  Done inside the lean pass, one
+// atomic AND by its first tile, it changed that kernel's code enough to cost 0.65 ms per forward at 2^30, measured; a copy of the
+// word from the host or two 32-bit fills are launches too.)
+__global__ void flag_tail_kernel(u64 *headw, u64 n)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0 && (n & 63)) headw[n >> 6] = (1ull << (n & 63)) - 1ull;
+}
 
-// Round 0: the radix sort of the keys that keybuild0 left in sp.keys[0] (values: the identity), group flags, their word scan, the tied count
-template <bool CYCLIC>
-static int round0_sort(bwts_ctx *ctx, u64 n, const Alphabet &al, SortSpace &sp, Round0 *r0)
+// Where round 0's group flags and their word scan go (3 * n/8 bytes): the carried-byte ping-pong buffers when there are any (the
+// packed passes never use them, the others are done with them when the flags are made), else sp.rank, which is not needed before the
+// rounds that follow.  Every sort decides this, takes sp.rank where it needs it and clears the counters BEFORE its radix passes, not
+// behind them: the lean last pass writes flags and give-up word while it sorts, and one order serves all (no pass touches either)
+static int round0_flag_words(bwts_ctx *ctx, u64 n, SortSpace &sp, Round0 *r0)
+{
+    const u64 words = (n + 63) / 64;
+    r0->flags_outside_rank = sp.carry_buf[0] && sp.carry_buf[1] && n >= 4096;
+    if (r0->flags_outside_rank) {
+        r0->headw = (u64 *)sp.carry_buf[0]; r0->keepw = r0->headw + words; r0->pre = (u64 *)sp.carry_buf[1];
+    } else {
+        BWTS_TRY(ensure_rank(ctx, sp, n));
+        r0->headw = (u64 *)sp.rank; r0->keepw = r0->headw + words; r0->pre = r0->keepw + words;
+    }
+    return BWTS_OK;
+}
+
+// The group flags of the sorted keys (unless the lean last pass left them already), their word scan and the tied count, read back
+// together with the lean pass's give-up flag
+static int round0_flags(bwts_ctx *ctx, u64 n, SortSpace &sp, Round0 *r0)
 {
     u64 *cnt = ctx->d_small + SM_COUNTERS;
+    const u64 words = (n + 63) / 64;
+    const K0Keys &k0v = r0->k0v;
+    u64 *K0 = sp.keys[r0->res];
+    {
+        SpanGuard g(ctx, BWTS_K_RERANK, n, r0->lean ? 16 * words : (k0v.wide ? 8 : k0v.hi ? 5 : 4) * n);
+        if (!r0->lean) {
+            u64 waves = (words + GF_WORDS - 1) / GF_WORDS;
+            unsigned blocks = (unsigned)((waves + 3) / 4 < 16384 ? (waves + 3) / 4 : 16384);
+            if (k0v.wide) group_flags_kernel<GfWide><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(GfWide{K0, ~0ull}, n, r0->headw, r0->keepw);
+            else if (k0v.hi) group_flags_kernel<GfSplit<true>><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(GfSplit<true>{k0v.lo, k0v.hi}, n, r0->headw, r0->keepw);
+            else group_flags_kernel<GfSplit<false>><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(GfSplit<false>{k0v.lo, nullptr}, n, r0->headw, r0->keepw);
+        }
+        WordIn in{r0->headw, r0->keepw};
+        ScanStoreArr<u64> out{r0->pre};
+        BWTS_TRY((device_scan<false, u64>(ctx, words, in, out, OpHeadCount(), (u64)0, sp.scan_temp)));
+        count_tied_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(r0->keepw, r0->pre, words, cnt + 0);
+        HIPC(hipGetLastError());
+        STAGE("group flags + word scan + count");
+    }
+    BWTS_TRY(read_small(ctx, SM_COUNTERS, 4));
+    r0->a = ctx->h_small[CNT_ACTIVE];
+    r0->seam = r0->lean && ctx->h_small[CNT_SEAM] != 0;
+    return BWTS_OK;
+}
+
+static SortPlan round0_plan(const SortSpace &sp, bool cyclic)
+{
     SortPlan plan = sp.plan();
     plan.sym_src = sp.carry_src; plan.sym_buf[0] = sp.carry_buf[0]; plan.sym_buf[1] = sp.carry_buf[1]; plan.sym_final = sp.carry_out;
     plan.vals_identity = true;     // keybuild0 writes no value array
-    plan.keys_split = CYCLIC && sp.split_keys && plan.sym_final;
+    plan.keys_split = cyclic && sp.split_keys && plan.sym_final;
     plan.first_hist = plan.keys_split ? sp.first_hist : nullptr;
+    return plan;
+}
+
+// Round 0: the radix sort of the keys that keybuild0 left in sp.keys[0] (values: the identity), group flags, their word scan, the tied count.
+// lean_ok: nobody behind this sort reads the sorted keys or the whole suffix array unless many positions stay tied, and few are
+// expected to: five packed passes then end in the lean one, which leaves the flags itself
+template <bool CYCLIC>
+static int round0_sort(bwts_ctx *ctx, u64 n, const Alphabet &al, SortSpace &sp, bool lean_ok, Round0 *r0)
+{
+    u64 *cnt = ctx->d_small + SM_COUNTERS;
+    SortPlan plan = round0_plan(sp, CYCLIC);
     if (CYCLIC && sp.split_keys && !plan.keys_split) return BWTS_E_INTERNAL;      // keybuild split the keys for a sort that cannot take them
+    BWTS_TRY(round0_flag_words(ctx, n, sp, r0));
+    r0->lean = lean_ok && plan.keys_split && al.key_bits > 32 && al.key_bits <= 40;
+    HIPC(hipMemsetAsync(cnt, 0, 4 * sizeof(u64), ctx->stream));
+    if (r0->lean) {
+        const u64 words = (n + 63) / 64;
+        HIPC(hipMemsetAsync(r0->headw, 0xff, words * sizeof(u64), ctx->stream));
+        HIPC(hipMemsetAsync(r0->keepw, 0, words * sizeof(u64), ctx->stream));
+        flag_tail_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(r0->headw, n);
+        HIPC(hipGetLastError());
+        plan.lean_last = true; plan.headw = r0->headw; plan.keepw = r0->keepw; plan.seam_giveup = ctx->d_small + CNT_SEAM;
+    }
     int res = 0;
     STAGE("cyclic patch (before round 0)");
     BWTS_TRY(radix_sort_pairs(ctx, plan, n, al.key_bits, &res));
     STAGE("round-0 sort");
     u64 *K0 = sp.keys[res];
-    K0Keys k0v{K0, nullptr, nullptr};
-    if (plan.keys_split) k0v = K0Keys{nullptr, (const u32 *)K0, al.key_bits > 32 ? (const u8 *)K0 + align_up((size_t)n * 4, 256) : nullptr};
+    r0->res = res;
+    r0->k0v = K0Keys{K0, nullptr, nullptr};
+    if (plan.keys_split) r0->k0v = K0Keys{nullptr, (const u32 *)K0, al.key_bits > 32 ? (const u8 *)K0 + align_up((size_t)n * 4, 256) : nullptr};
+    r0->SA = sp.vals[res];
+    return round0_flags(ctx, n, sp, r0);
+}
 
-    HIPC(hipMemsetAsync(cnt, 0, 4 * sizeof(u64), ctx->stream));
-    const u64 words = (n + 63) / 64;
-    u64 *headw, *keepw, *pre;
-    const bool flags_outside_rank = sp.carry_buf[0] && sp.carry_buf[1] && n >= 4096;
-    {
-        SpanGuard g(ctx, BWTS_K_RERANK, n, (k0v.wide ? 8 : k0v.hi ? 5 : 4) * n);
-        // flags and word prefixes (3 * n/8 bytes): in the carried-byte ping-pong buffers when there are any (free once the
-        // sort is done), else in sp.rank, which is not needed before the rounds that follow
-        if (flags_outside_rank) {
-            headw = (u64 *)sp.carry_buf[0]; keepw = headw + words; pre = (u64 *)sp.carry_buf[1];
-        } else {
-            BWTS_TRY(ensure_rank(ctx, sp, n));
-            headw = (u64 *)sp.rank; keepw = headw + words; pre = keepw + words;
-        }
-        u64 waves = (words + GF_WORDS - 1) / GF_WORDS;
-        unsigned blocks = (unsigned)((waves + 3) / 4 < 16384 ? (waves + 3) / 4 : 16384);
-        if (k0v.wide) group_flags_kernel<GfWide><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(GfWide{K0, ~0ull}, n, headw, keepw);
-        else if (k0v.hi) group_flags_kernel<GfSplit<true>><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(GfSplit<true>{k0v.lo, k0v.hi}, n, headw, keepw);
-        else group_flags_kernel<GfSplit<false>><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(GfSplit<false>{k0v.lo, nullptr}, n, headw, keepw);
-        WordIn in{headw, keepw};
-        ScanStoreArr<u64> out{pre};
-        BWTS_TRY((device_scan<false, u64>(ctx, words, in, out, OpHeadCount(), (u64)0, sp.scan_temp)));
-        count_tied_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(keepw, pre, words, cnt + 0);
-        HIPC(hipGetLastError());
-        STAGE("group flags + word scan + count");
-    }
-    BWTS_TRY(read_small(ctx, SM_COUNTERS, 4));
-    *r0 = Round0{res, k0v, sp.vals[res], headw, keepw, pre, flags_outside_rank, ctx->h_small[CNT_ACTIVE]};
-    return BWTS_OK;
+// Behind a lean last pass that did not stand (a seam it could not decide, more ties than the tied list has room for beside the
+// untouched streams, a list the direct form gave back): the classic last pass from the same input, and the flags from its keys
+static int round0_redo_classic(bwts_ctx *ctx, u64 n, SortSpace &sp, Round0 *r0)
+{
+    HIPC(hipMemsetAsync(ctx->d_small + SM_COUNTERS, 0, 4 * sizeof(u64), ctx->stream));
+    BWTS_TRY(radix_packed_last_pass(ctx, round0_plan(sp, true), n));
+    STAGE("round-0 sort: classic last pass");
+    r0->lean = false;
+    return round0_flags(ctx, n, sp, r0);
 }
 
 // Many ties: the dense rank array.  It is built BEFORE the tied list, while the list's future home (the other key
@@ -1460,12 +1540,22 @@ static int early_ranks(bwts_ctx *ctx, u64 n, SortSpace &sp, const Round0 &r0)
 }
 
 // The tied list, in the key and value buffers that round 0 left free (8n + 4n bytes)
+// (behind a lean last pass those still hold the pass's input, which a fallback sorts again: the list, of at most n / 32 elements
+// then, goes where the sorted keys would have gone)
 static int tied_list(bwts_ctx *ctx, u64 n, SortSpace &sp, const Round0 &r0, ActiveList *cur)
 {
     u64 *cnt = ctx->d_small + SM_COUNTERS;
-    cur->idx = (u32 *)sp.keys[r0.res ^ 1];
-    cur->slot = cur->idx + n;
-    cur->head = sp.vals[r0.res ^ 1];
+    if (r0.lean) {
+        if (r0.a > n / 32) return BWTS_E_INTERNAL;
+        const u64 cap = n / 32 + 1;                 // 3 * cap * 4 <= 8 n: the packed sort runs from 65 536 elements
+        cur->idx = (u32 *)sp.keys[r0.res];
+        cur->slot = cur->idx + cap;
+        cur->head = cur->slot + cap;
+    } else {
+        cur->idx = (u32 *)sp.keys[r0.res ^ 1];
+        cur->slot = cur->idx + n;
+        cur->head = sp.vals[r0.res ^ 1];
+    }
     SpanGuard g(ctx, BWTS_K_RERANK, r0.a, 12 * r0.a);
     const u64 waves = ((n + 63) / 64 + 63) / 64;
     const unsigned blocks = (unsigned)((waves + 3) / 4 < 16384 ? (waves + 3) / 4 : 16384);
@@ -1789,8 +1879,29 @@ template <bool CYCLIC>
 static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al, const u32 *d_fstart, u64 k,
                          SortSpace &sp, bool want_ranks, u32 **sa_out, u32 *rounds_out, u64 *active0_out)
 {
+    // the lean last pass: behind a cyclic sort whose byte rode round 0 only the ranks and the sparse and dense forms read the sorted
+    // keys or the whole suffix array.  (A call that works on a segment table is no such sort: its partition reads the suffix array,
+    // so no byte rides and carry_out is null.  The context's own table says nothing here: it stays set between calls, and a
+    // segmented call transforms its large segments alone, byte riding.)  BWTS_RX_LEAN=0 (a test switch): never
+    const bool direct_ok = CYCLIC && sp.carry_out && !want_ranks && direct_ties_allowed(ctx, n);
+    const bool lean_off = [ctx] { const char *e = bwts_knob(ctx, "BWTS_RX_LEAN"); return e && atoi(e) == 0; }();
+    const bool lean_ok = direct_ok && al.few_ties && !lean_off;
     Round0 r0;
-    BWTS_TRY((round0_sort<CYCLIC>(ctx, n, al, sp, &r0)));
+    BWTS_TRY((round0_sort<CYCLIC>(ctx, n, al, sp, lean_ok, &r0)));
+    // lean is all or nothing: it stands when the direct form settles every tied group from the list alone
+    u64 lean = FR_LEAN_NONE, direct = FR_DIRECT_NONE;
+    ActiveList cur, none{nullptr, nullptr, nullptr};
+    bool listed = false;
+    if (r0.lean) {
+        lean = r0.seam ? FR_LEAN_SEAM : r0.a > n / 32 ? FR_LEAN_COUNT : FR_LEAN_HELD;
+        if (lean == FR_LEAN_HELD) {
+            BWTS_TRY(tied_list(ctx, n, sp, r0, &cur));
+            listed = true;
+            if (r0.a > 0) BWTS_TRY(direct_ties(ctx, d_T, n, al, d_fstart, k, sp, cur, r0.a, &direct));
+            if (r0.a > 0 && direct != FR_DIRECT_SETTLED) lean = FR_LEAN_DIRECT;
+        }
+        if (lean != FR_LEAN_HELD) { BWTS_TRY(round0_redo_classic(ctx, n, sp, &r0)); listed = false; }
+    }
     u64 a = r0.a;
     u32 *SA = r0.SA;
     *active0_out = a;
@@ -1800,10 +1911,9 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
     rep[FR_CYCLIC] = CYCLIC; rep[FR_N] = n; rep[FR_K] = k; rep[FR_SIGMA] = (u64)al.sigma; rep[FR_BITS] = (u64)al.bits; rep[FR_MSYM] = (u64)al.msym;
     rep[FR_KEY_BITS] = (u64)al.key_bits; rep[FR_VARLEN] = al.varlen; rep[FR_HSTEP] = (u64)al.hstep;
     rep[FR_KEYS] = r0.k0v.wide ? 0 : r0.k0v.hi ? 2 : 1; rep[FR_FLAGS_OUTSIDE_RANK] = r0.flags_outside_rank; rep[FR_TIED0] = a;
-    rep[FR_RANK_EARLY] = rank_early; rep[FR_ROUNDS] = 1;
+    rep[FR_RANK_EARLY] = rank_early; rep[FR_ROUNDS] = 1; rep[FR_LEAN] = lean;
     if (rank_early) BWTS_TRY(early_ranks(ctx, n, sp, r0));
-    ActiveList cur, none{nullptr, nullptr, nullptr};
-    BWTS_TRY(tied_list(ctx, n, sp, r0, &cur));
+    if (!listed) BWTS_TRY(tied_list(ctx, n, sp, r0, &cur));
     u32 rounds = 1;
 
     // every position tied at n = 2^32 (a constant or a two-symbol periodic input of exactly 4 GiB): the side buffers of the
@@ -1813,8 +1923,8 @@ static int doubling_sort(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al
     if (a > 0 && a <= n / 32) {
         // the cyclic sort whose bytes rode round 0 (only the tied slots are left to write) first tries to settle every group by
         // comparing rotations; all or nothing: a list it cannot settle goes to the sparse rounds untouched
-        u64 direct = FR_DIRECT_NONE;
-        if (CYCLIC && sp.carry_out && !want_ranks && direct_ties_allowed(ctx, n)) BWTS_TRY(direct_ties(ctx, d_T, n, al, d_fstart, k, sp, cur, a, &direct));
+        // (a lean round 0 has asked already; what made the direct form give up is still what it is)
+        if (direct_ok && direct == FR_DIRECT_NONE) BWTS_TRY(direct_ties(ctx, d_T, n, al, d_fstart, k, sp, cur, a, &direct));
         rep[FR_DIRECT] = direct;
         if (direct == FR_DIRECT_SETTLED) {
             rounds++;

@@ -276,6 +276,12 @@ struct SortPlan {
     // keys_split only, may be null: the first pass's [tile][digit] table (8192-element tiles, digit = key bits 0..7), counted
     // already, in a block of radix_tile_hist_bytes(m) that no pass writes but the first one's scan; that pass's histogram sweep is skipped
     u32 *first_hist = nullptr;
+    // keys_split with five passes only: the last pass writes the byte stream and, instead of the sorted keys and the values, the group
+    // flags of its output (radix.hip, radix_scatter_lean_last_kernel): headw, keepw of (m + 63) / 64 words each, which the caller has
+    // filled with ones (up to m) and zeros; vals[res] at the tied slots only; *seam_giveup (zero before) set when the flags cannot be
+    // trusted.  keys[res ^ 1] and vals[res ^ 1] stay as the fourth pass left them (radix_packed_last_pass), keys[res] is not written.
+    bool lean_last = false;
+    u64 *headw = nullptr, *keepw = nullptr, *seam_giveup = nullptr;
 };
 // a plain pair sort over two key and two value buffers (the optional fields stay as above)
 static inline SortPlan sort_plan(u64 *k0, u64 *k1, u32 *v0, u32 *v1, u32 *tile_hist, void *scan_temp)
@@ -288,6 +294,7 @@ bool radix_packed_applicable(const bwts_ctx *ctx, u64 m, int key_bits);   // wil
 size_t radix_tile_hist_bytes(u64 m);
 // Sorts on key bits [0, key_bits); returns in *result_buf which of keys[]/vals[] holds the output.
 int radix_sort_pairs(bwts_ctx *ctx, const SortPlan &plan, u64 m, int key_bits, int *result_buf);
+int radix_packed_last_pass(bwts_ctx *ctx, const SortPlan &plan, u64 m);   // the classic fifth pass behind a lean one that gave up
 int radix_column_scan(bwts_ctx *ctx, u32 *tile_hist, u64 tiles, void *scan_temp);
 int radix_sort_keys(bwts_ctx *ctx, u64 *keys[2], u32 *tile_hist, void *scan_temp, u64 m, int lo_bit, int bits, int *result_buf);
 

@@ -11,7 +11,9 @@
 //                                 Later rounds, keys wider than 40 bits.
 //   radix_scatter_packed_kernel   round 0 of the forward transform with keys of <= 40 bits: packed streams, 2*(4+4+2) bytes
 //                                 (see "packed streams" below).
-// Both are built from the same blocks: RxTile (the tile's place and its LDS), wave_rank_step and digit_bases (device_utils.h),
+//   radix_scatter_lean_last_kernel  the last of five packed passes when few positions are expected to stay tied: the byte out,
+//                                 and the group flags of its own output instead of sorted keys and values; 7 bytes per element.
+// All are built from the same blocks: RxTile (the tile's place and its LDS), wave_rank_step and digit_bases (device_utils.h),
 // Pos16; radix_hist_kernel<T> counts the digits of whichever stream holds them.
 #include "internal.h"
 #include "device_utils.h"
@@ -509,6 +511,190 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_packed_kern
 #undef PK_VALID
 }
 
+// The lean last pass of a five-pass sort (SortPlan::lean_last): the carried byte goes out as above, and of the keys only what the
+// stages after round 0 ask of them when few positions stay tied: which output slots start a group of equal keys (headw) and which sit
+// in a group of more than one (keepw) -- the two bitmaps group_flags_kernel (forward.hip) makes from the sorted keys -- and the
+// positions of the tied slots.  Neither lo, the key byte nor the other positions are written: 7 bytes per element instead of 20.
+//
+// The pass's input is sorted by lo (passes 0..3 covered its 32 bits, stably), so the elements of one lo form a run of the input, and
+// the pass is stable: the output neighbour of an element in front, inside its digit, is the nearest element with its digit before it
+// in the input, and the two keys are equal iff that one lies in the same run.  Inside the tile that is the slot before it (same
+// digit, same lo).  The first slot of a digit's run in the tile has its neighbour in an earlier tile: it can have the same lo only
+// when this lo is that of the tile's first element and the run of that value reaches back over the tile's start; then the key is
+// equal iff the digit occurs in the part of the run before the tile.  Mirrored for the last slot of a digit's run and the run that
+// goes on behind the tile.  Wave 0 looks at LEAN_SEAM elements on either side and keeps, per side, the set of digits in the
+// neighbouring run (2 x 256 bits, in its own row of the waves' digit counters, once it has read that for the last time); a run
+// that fills them -- one tile in thousands on random keys -- is followed further, LEAN_SEAM elements at a time.  A run of
+// LEAN_REACH elements that has not ended (nor the array there) is not decided from here: *giveup is raised, the flags are then
+// worthless and the host sorts the classic way (radix_packed_last_pass).  Below that the flags are exact.  (The reach is what lets
+// a phrase pasted a few hundred times -- a run of as many equal lo -- through to the stage whose business large groups are.)
+// headw comes in all ones (its last word up to m: masking it in here cost the pass 0.6 ms at 2^30), keepw all zeros: a tied slot -- one in
+// 250 on the inputs this is chosen for -- sets its keepw bit, clears its headw bit if it equals the slot before, and fetches and
+// stores its position.
+// With only the byte to write the tile makes one LDS trip where the other passes make two: c and lo are both loaded before the
+// ranking and staged together (lo | c with the element's place in the tile, 8 B per slot as ever), and one sweep over the slots
+// writes the bytes and looks for equal neighbours: two barriers and a write-out loop fewer (zipf 2^30: 4.10 -> 3.60 ms).  The
+// slots' byte table, 8 KB of RxTile, is not used (the digit is c's low byte); the layout is kept whole: it is what fits two
+// tiles on a CU.
+#define LEAN_SEAM 64
+#define LEAN_REACH 1024
+static_assert(LEAN_REACH % LEAN_SEAM == 0 && LEAN_REACH <= RX_TILE, "the elements before a tile that is not the first are all there");
+struct LeanIO {
+    const u32 *lo_in; const u16 *c_in; const u32 *val_in;
+    u8 *sym_out;
+    u32 *val_out;                                          // written at tied slots only
+    u64 *headw, *keepw, *giveup;
+};
+
+__global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_lean_last_kernel(LeanIO io, const u32 *__restrict__ tile_off, u64 m)
+{
+    extern __shared__ __attribute__((aligned(16))) char rx_smem[];
+    using L = RxTile<RX_THREADS, RX_ITEMS>;
+    u32 *stage32 = (u32 *)L::stage(rx_smem);
+    u32 *dbase = L::dbase(rx_smem), *gbase = L::gbase(rx_smem), *scan_sm = L::scan_sm(rx_smem);
+    u16 (*whist)[256] = L::whist(rx_smem);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const u64 tile = rx_tile_of_block((m + RX_TILE - 1) / RX_TILE);
+    const u64 tile_base = tile * RX_TILE;
+    if (tile_base >= m) return;                                   // padding block of the grid
+    const u64 wave_base = tile_base + (u64)w * (64 * RX_ITEMS);
+    const u64 remain = m - tile_base;
+    const u32 tile_count = remain < RX_TILE ? (u32)remain : (u32)RX_TILE;
+
+    for (int i = tid; i < RX_WAVES * 128; i += RX_THREADS) ((u32 *)whist)[i] = 0;
+
+    const u64 i0 = wave_base + (u64)lane;
+    u32 vmask = 0;
+#pragma unroll
+    for (int j = 0; j < RX_ITEMS; j++) vmask |= (i0 + (u64)j * 64 < m ? 1u : 0u) << j;
+#define PK_VALID(j) ((vmask >> (j)) & 1u)
+
+    // Both streams are loaded before the ranking: with nothing but the byte to write there is one LDS trip, not two, and lo has to
+    // be there for it.  In wave 0 also the LEAN_SEAM elements on either side of the tile.
+    u32 dsrc[RX_ITEMS], lo[RX_ITEMS];
+    Pos16<RX_ITEMS> pos;
+    {
+        const u16 *c16 = io.c_in + i0;
+        const u32 *lop = io.lo_in + i0;
+#pragma unroll
+        for (int j = 0; j < RX_ITEMS; j++) dsrc[j] = PK_VALID(j) ? (u32)c16[j * 64] : 0xffffu;
+#pragma unroll
+        for (int j = 0; j < RX_ITEMS; j++) lo[j] = PK_VALID(j) ? lop[j * 64] : 0u;
+    }
+    // (a tile that does not start the array has 8192 elements before it; one that is not full has none behind it)
+    const bool has_before = tile_base > 0, has_after = tile_base + RX_TILE + (u64)lane < m;
+    u32 b_lo = 0, b_c = 0, a_lo = 0, a_c = 0;
+    if (w == 0) {
+        if (has_before) { const u64 i = tile_base - 1 - (u64)lane; b_lo = io.lo_in[i]; b_c = io.c_in[i]; }
+        if (has_after) { const u64 i = tile_base + RX_TILE + (u64)lane; a_lo = io.lo_in[i]; a_c = io.c_in[i]; }
+    }
+    const u32 lo_first = io.lo_in[tile_base], lo_last = io.lo_in[tile_base + tile_count - 1];       // (uniform addresses: scalar loads)
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < RX_ITEMS; j++) {
+        const bool valid = PK_VALID(j);
+        wave_rank_step(whist[w], dsrc[j] & 255u, valid, [&](u32 r) { pos.init(j, r); });
+    }
+    __syncthreads();
+    {
+        const u32 exc = digit_bases<RX_WAVES>(whist, scan_sm);
+        if (tid < 256) {
+            dbase[tid] = exc;
+            gbase[tid] = tile_off[tile * 256 + tid] - exc;
+        }
+    }
+    __syncthreads();
+
+    // the trip: a slot holds its lo in the stage's first half and, in the second, c | the element's place in the tile << 16 (the
+    // digit is c's low byte: the byte table is not used)
+    constexpr int HB = 8;
+    u32 *lo_s = stage32, *cx_s = stage32 + RX_TILE;
+#pragma unroll
+    for (int j0 = 0; j0 < RX_ITEMS; j0 += HB) {
+        u32 add[HB];
+#pragma unroll
+        for (int jj = 0; jj < HB; jj++) {
+            const u32 d = dsrc[j0 + jj] & 255u;
+            add[jj] = dbase[d] + whist[w][d];
+        }
+#pragma unroll
+        for (int jj = 0; jj < HB; jj++) {
+            const int j = j0 + jj;
+            const u32 p = pos.get(j) + add[jj];
+            if (PK_VALID(j)) {
+                lo_s[p] = lo[j];
+                cx_s[p] = dsrc[j] | ((u32)w * (64u * RX_ITEMS) + (u32)j * 64u + (u32)lane) << 16;
+            }
+        }
+    }
+    // the seams.  Wave 0 has read its row of the digit counters for the last time just above (nobody else reads that row): the row's
+    // first 16 words hold the two sets
+    u32 *seam = (u32 *)whist;
+    if (w == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if (lane < 16) seam[lane] = 0;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        // lanes of a window that belong to the run: those in front of the first that does not match
+        const auto in_run = [](u64 match) { return ~match ? (u32)__ffsll((unsigned long long)~match) - 1u : (u32)LEAN_SEAM; };
+        u32 run_b = in_run(__ballot(has_before && b_lo == lo_first)), run_a = in_run(__ballot(has_after && a_lo == lo_last));
+        if ((u32)lane < run_b) atomicOr(&seam[(b_c & 255u) >> 5], 1u << (b_c & 31u));
+        if ((u32)lane < run_a) atomicOr(&seam[8 + ((a_c & 255u) >> 5)], 1u << (a_c & 31u));
+        for (u32 off = LEAN_SEAM; run_b == off && off < LEAN_REACH; off += LEAN_SEAM) {
+            const u64 i = tile_base - 1 - off - (u64)lane;
+            const u32 l = io.lo_in[i], c = io.c_in[i];
+            const u32 r = in_run(__ballot(l == lo_first));
+            if ((u32)lane < r) atomicOr(&seam[(c & 255u) >> 5], 1u << (c & 31u));
+            run_b += r;
+        }
+        for (u32 off = LEAN_SEAM; run_a == off && off < LEAN_REACH; off += LEAN_SEAM) {
+            const u64 i = tile_base + RX_TILE + off + (u64)lane;
+            const bool there = i < m;
+            const u32 l = there ? io.lo_in[i] : 0u, c = there ? (u32)io.c_in[i] : 0u;
+            const u32 r = in_run(__ballot(there && l == lo_last));
+            if ((u32)lane < r) atomicOr(&seam[8 + ((c & 255u) >> 5)], 1u << (c & 31u));
+            run_a += r;
+        }
+        const bool undecided = run_b == LEAN_REACH || (run_a == LEAN_REACH && tile_base + RX_TILE + LEAN_REACH < m);
+        if (undecided && lane == 0) __hip_atomic_store(io.giveup, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    // every slot: the byte out; equal to a neighbour in the tile's order, or to the lo a seam run has?
+#pragma unroll
+    for (int j0 = 0; j0 < RX_ITEMS; j0 += HB) {
+        u32 cx[HB], x[HB], xp[HB], xn[HB], g[HB];
+#pragma unroll
+        for (int jj = 0; jj < HB; jj++) {
+            const u32 s = (u32)(j0 + jj) * RX_THREADS + tid;
+            const u32 sc = s < tile_count ? s : 0u;
+            cx[jj] = cx_s[sc];
+            x[jj] = lo_s[sc];
+            xp[jj] = lo_s[sc ? sc - 1u : 0u];
+            xn[jj] = lo_s[sc + 1u < tile_count ? sc + 1u : sc];
+        }
+#pragma unroll
+        for (int jj = 0; jj < HB; jj++) g[jj] = gbase[cx[jj] & 255u];
+#pragma unroll
+        for (int jj = 0; jj < HB; jj++) {
+            const u32 s = (u32)(j0 + jj) * RX_THREADS + tid;
+            if (s >= tile_count) continue;
+            const u32 dst = g[jj] + s;
+            io.sym_out[dst] = (u8)(cx[jj] >> 8);
+            const bool eq_p = s > 0 && xp[jj] == x[jj], eq_n = s + 1u < tile_count && xn[jj] == x[jj];
+            // (random keys: one slot in a few hundred gets past this line)
+            if (!(eq_p || eq_n || x[jj] == lo_first || x[jj] == lo_last)) continue;
+            const u32 d = cx[jj] & 255u;
+            const bool run_first = s == 0 || (cx_s[s - 1u] & 255u) != d, run_last = s + 1u == tile_count || (cx_s[s + 1u] & 255u) != d;
+            const bool same_p = run_first ? x[jj] == lo_first && ((seam[d >> 5] >> (d & 31u)) & 1u) : eq_p;
+            const bool same_n = run_last ? x[jj] == lo_last && ((seam[8 + (d >> 5)] >> (d & 31u)) & 1u) : eq_n;
+            if (!(same_p || same_n)) continue;
+            io.val_out[dst] = io.val_in[tile_base + (cx[jj] >> 16)];
+            __hip_atomic_fetch_or(&io.keepw[dst >> 6], 1ull << (dst & 63u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (same_p) __hip_atomic_fetch_and(&io.headw[dst >> 6], ~(1ull << (dst & 63u)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+#undef PK_VALID
+}
+
 // ------------------------------------------------------------------------------------
 // host side of a pass
 // ------------------------------------------------------------------------------------
@@ -549,35 +735,57 @@ static int launch_scatter(bwts_ctx *ctx, void (*kernel)(P...), u64 m, u64 alg_by
     return BWTS_OK;
 }
 
+// pass p of `passes` over the packed streams, from keys[cur] / vals[cur] into the other pair.  lean: the last of five passes in its
+// lean form (radix_scatter_lean_last_kernel), which writes neither of them
+template <bool HI16>
+static int radix_packed_pass(bwts_ctx *ctx, const SortPlan &plan, u64 m, int p, int passes, int cur, bool lean)
+{
+    const size_t lo_bytes = align_up((size_t)m * 4, 256);
+    const u64 pass_bytes = HI16 ? 20 : 18;
+    const int shift = 8 * p;
+    const bool first = p == 0, last = p == passes - 1;
+    char *src = (char *)plan.keys[cur], *dst = (char *)plan.keys[cur ^ 1];
+    PackedIO io{};
+    io.lo_in = (const u32 *)src; io.c_in = src + lo_bytes; io.val_in = plan.vals[cur];
+    io.lo_out = (u32 *)dst; io.c_out = dst + lo_bytes; io.val_out = plan.vals[cur ^ 1];
+    io.hi_out = (u8 *)dst + lo_bytes; io.sym_out = plan.sym_final;
+    // the first pass's table may have been counted already (the key builder's)
+    u32 *tile_hist = first && plan.first_hist ? plan.first_hist : plan.tile_hist;
+    const bool counted = tile_hist != plan.tile_hist;
+    if (HI16 && shift >= 32) BWTS_TRY(radix_pass_offsets(ctx, (const u16 *)io.c_in, m, 0, tile_hist, counted, plan.scan_temp));
+    else BWTS_TRY(radix_pass_offsets(ctx, io.lo_in, m, shift, tile_hist, counted, plan.scan_temp));
+    if (lean) {
+        if (!HI16 || !last || !plan.headw || !plan.keepw || !plan.seam_giveup) return BWTS_E_INTERNAL;
+        // c and lo in, the byte out; what the tied slots add is booked with the tied list
+        const LeanIO lio{io.lo_in, (const u16 *)io.c_in, io.val_in, io.sym_out, io.val_out, plan.headw, plan.keepw, plan.seam_giveup};
+        return launch_scatter(ctx, radix_scatter_lean_last_kernel, m, 7 * m, false, lio, tile_hist, m);
+    }
+    // the first pass reads no values; the last writes the keys split and the byte alone
+    const u64 bytes = first ? pass_bytes - 4 : last ? pass_bytes / 2 + (HI16 ? 10 : 9) : pass_bytes;
+    const auto kernel = first ? radix_scatter_packed_kernel<true, false, HI16>
+                      : last  ? radix_scatter_packed_kernel<false, true, HI16> : radix_scatter_packed_kernel<false, false, HI16>;
+    return launch_scatter(ctx, kernel, m, bytes * m, !first && !last, io, tile_hist, m, shift);
+}
+
 // round 0 with the byte stream and identity values, keys of 17..40 bits: split -> packed ... packed -> split
 template <bool HI16>
 static int radix_sort_packed(bwts_ctx *ctx, const SortPlan &plan, u64 m, int passes, int *result_buf)
 {
-    const size_t lo_bytes = align_up((size_t)m * 4, 256);
-    const u64 pass_bytes = HI16 ? 20 : 18;
+    if (plan.lean_last && passes != 5) return BWTS_E_INTERNAL;
     int cur = 0;
     for (int p = 0; p < passes; p++) {
-        const int shift = 8 * p;
-        const bool first = p == 0, last = p == passes - 1;
-        char *src = (char *)plan.keys[cur], *dst = (char *)plan.keys[cur ^ 1];
-        PackedIO io{};
-        io.lo_in = (const u32 *)src; io.c_in = src + lo_bytes; io.val_in = plan.vals[cur];
-        io.lo_out = (u32 *)dst; io.c_out = dst + lo_bytes; io.val_out = plan.vals[cur ^ 1];
-        io.hi_out = (u8 *)dst + lo_bytes; io.sym_out = plan.sym_final;
-        // the first pass's table may have been counted already (the key builder's)
-        u32 *tile_hist = first && plan.first_hist ? plan.first_hist : plan.tile_hist;
-        const bool counted = tile_hist != plan.tile_hist;
-        if (HI16 && shift >= 32) BWTS_TRY(radix_pass_offsets(ctx, (const u16 *)io.c_in, m, 0, tile_hist, counted, plan.scan_temp));
-        else BWTS_TRY(radix_pass_offsets(ctx, io.lo_in, m, shift, tile_hist, counted, plan.scan_temp));
-        // the first pass reads no values; the last writes the keys split and the byte alone
-        const u64 bytes = first ? pass_bytes - 4 : last ? pass_bytes / 2 + (HI16 ? 10 : 9) : pass_bytes;
-        const auto kernel = first ? radix_scatter_packed_kernel<true, false, HI16>
-                          : last  ? radix_scatter_packed_kernel<false, true, HI16> : radix_scatter_packed_kernel<false, false, HI16>;
-        BWTS_TRY(launch_scatter(ctx, kernel, m, bytes * m, !first && !last, io, tile_hist, m, shift));
+        BWTS_TRY(radix_packed_pass<HI16>(ctx, plan, m, p, passes, cur, plan.lean_last && p == passes - 1));
         cur ^= 1;
     }
     *result_buf = cur;
     return BWTS_OK;
+}
+
+// After a lean last pass that could not stand: the classic fifth pass, from the fourth pass's output, which the lean pass left as it was
+int radix_packed_last_pass(bwts_ctx *ctx, const SortPlan &plan, u64 m)
+{
+    if (!plan.keys_split || !plan.sym_final) return BWTS_E_INTERNAL;
+    return radix_packed_pass<true>(ctx, plan, m, 4, 5, 0, false);
 }
 
 // ------------------------------------------------------------------------------------
@@ -778,6 +986,7 @@ int radix_sort_pairs(bwts_ctx *ctx, const SortPlan &plan, u64 m, int key_bits, i
     if (key_bits < 1) key_bits = 1;
     if (key_bits > 64) key_bits = 64;
     const int passes = (key_bits + 7) / 8;
+    if (plan.lean_last && !plan.keys_split) return BWTS_E_INTERNAL;
 
     if (!knob_off(ctx, "BWTS_RX_SMALL") && m <= RS_MAX && !plan.sym_src && !plan.vals_identity && !plan.keys_split) {
         SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, 24 * m);

@@ -97,7 +97,11 @@ int bwts_debug_segments_report(bwts_ctx *ctx, uint64_t out[8]);
  * starts in LDS (1) or the general instantiation (0); 33 compactions done; 34 compactions chunk_recut_plan refused; 35 a round was
  * enqueued behind the last one.  All of 24..35 stay 0 when the chunk form did not run to its end (form 3 after a hand-over included).
  * 36 the direct form: 0 not tried, 1 all groups settled (form 4), 2 fell back to the sparse rounds on a group above its cap, 3 fell
- * back on two rotations equal beyond its depth.  Words 37..47 stay 0.
+ * back on two rotations equal beyond its depth.  37 (BWTS_FWD_LEAN_WORD) the lean last pass of round 0, which leaves the group flags
+ * and the tied positions instead of the sorted keys and the suffix array: 0 not tried, 1 held, 2 gave up on a run of equal low key
+ * words too long across a tile seam, 3 gave up on the tied count (above n / 32), 4 the direct form gave up behind it; after 2, 3 and 4
+ * the classic last pass ran from the same input and words 0..36 and the rounds are what they are without the lean pass.
+ * Words 38..47 stay 0.
  * Rounds, BWTS_FWD_ROUND_WORDS words each, the first BWTS_MAX_ROUND_STATS rounds after round 0 (those past that are counted in word 20
  * and leave no record): 0 form, as header word 13; 1 h; 2 list going in; 3 list coming out; 4 a group split in this round (1) or none did (0; direct: always 1); then sparse: 5 probe: 0 list of at most 4096, 1 ran, 2 skipped after skip_next; 6 m_big; 7 whole; 8 skip_next;
  * chunks: 5, 6 elements in chunks before and after; 7, 8, 9 big list before, stays, leaves; 10 chunks in the tables;
@@ -105,6 +109,7 @@ int bwts_debug_segments_report(bwts_ctx *ctx, uint64_t out[8]);
  * out receives whole records while they fit into cap_words; *sorts = sorts the call made.  Returns the records written, < 0 on a
  * bad argument. */
 #define BWTS_FWD_HEADER_WORDS 48
+#define BWTS_FWD_LEAN_WORD 37
 #define BWTS_FWD_ROUND_WORDS 12
 #define BWTS_FWD_SORT_WORDS (BWTS_FWD_HEADER_WORDS + BWTS_MAX_ROUND_STATS * BWTS_FWD_ROUND_WORDS)
 int bwts_debug_forward_report(bwts_ctx *ctx, uint64_t *out, uint64_t cap_words, uint64_t *sorts);

@@ -55,11 +55,17 @@ ZRL_EXPORTS = [
     "bwts_zrl_bound", "bwts_zrl_encode_device", "bwts_zrl_decode_device", "bwts_zrl_encode", "bwts_zrl_decode",
     "bwts_zrl_encode_segments_device", "bwts_zrl_decode_segments_device",
 ]
+# ... include/bwts_planes.h (byte-plane split of typed arrays, the stage in front of the transform) ...
+PLANES_EXPORTS = [
+    "bwts_planes_split_device", "bwts_planes_join_device", "bwts_planes_split_segments_device", "bwts_planes_join_segments_device",
+    "bwts_planes_split", "bwts_planes_join",
+]
 # ... include/bwts_pack.h (the chain as one call: a checksummed frame) ...
 PACK_EXPORTS = [
     "bwts_crc32_device", "bwts_crc32_segments_device", "bwts_pack_bound", "bwts_unpack_size",
     "bwts_pack_device", "bwts_unpack_device", "bwts_pack", "bwts_unpack",
     "bwts_pack_bound_v", "bwts_pack_device_v", "bwts_pack_v",
+    "bwts_pack_planes_bound", "bwts_pack_planes_device", "bwts_pack_planes",
 ]
 E_CHECKSUM = -10
 # ... and include/bwts_test.h (harness and unit-test hooks)
@@ -69,7 +75,7 @@ TEST_EXPORTS = [
     "bwts_debug_chunk_plan", "bwts_debug_inverse_arena", "bwts_debug_forward_arena", "bwts_debug_wide_forward_arena", "bwts_debug_inverse_report",
     "bwts_debug_forward_report", "bwts_debug_segments_plan", "bwts_debug_segments_report",
     "bwts_debug_mtf_plan", "bwts_debug_last_spans", "bwts_debug_ec_plan", "bwts_debug_crc_plan",
-    "bwts_debug_zrl_plan",
+    "bwts_debug_zrl_plan", "bwts_debug_planes_plan",
 ]
 # bwts_debug_inverse_report: the words of one attempt's record, and what marks, outcomes and forms are called
 INV_REPORT_FIELDS = ["g", "mark", "outcome", "s", "virtual", "node_cap", "nu", "nu2", "ucap_first", "second_collect",
@@ -195,6 +201,12 @@ def lib():
         L.bwts_zrl_encode_segments_device.argtypes = [vp, vp, vp, u64, vp, u64, vp]
         L.bwts_zrl_decode_segments_device.argtypes = [vp, vp, vp, vp, u64, vp]
         L.bwts_debug_zrl_plan.argtypes = [u64, ctypes.POINTER(u64)]
+        u32 = ctypes.c_uint32
+        for name in ("bwts_planes_split_device", "bwts_planes_join_device", "bwts_planes_split", "bwts_planes_join"):
+            getattr(L, name).argtypes = [vp, vp, u64, u32, vp]
+        for name in ("bwts_planes_split_segments_device", "bwts_planes_join_segments_device"):
+            getattr(L, name).argtypes = [vp, vp, vp, u64, u32, vp]
+        L.bwts_debug_planes_plan.argtypes = [u64, u32, ctypes.POINTER(u64)]
         L.bwts_crc32_device.argtypes = [vp, vp, u64, ctypes.POINTER(ctypes.c_uint32)]
         L.bwts_crc32_segments_device.argtypes = [vp, vp, vp, u64, vp]
         L.bwts_pack_bound.argtypes = [u64, u64]
@@ -202,10 +214,13 @@ def lib():
         L.bwts_unpack_size.argtypes = [vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]
         for name in ("bwts_pack_device", "bwts_pack"):
             getattr(L, name).argtypes = [vp, vp, u64, u64, vp, u64, ctypes.POINTER(u64)]
-        u32 = ctypes.c_uint32
         L.bwts_pack_bound_v.argtypes = [u32, u64, u64]
         L.bwts_pack_bound_v.restype = u64
         for name in ("bwts_pack_device_v", "bwts_pack_v"):
+            getattr(L, name).argtypes = [vp, u32, vp, u64, u64, vp, u64, ctypes.POINTER(u64)]
+        L.bwts_pack_planes_bound.argtypes = [u32, u64, u64]
+        L.bwts_pack_planes_bound.restype = u64
+        for name in ("bwts_pack_planes_device", "bwts_pack_planes"):
             getattr(L, name).argtypes = [vp, u32, vp, u64, u64, vp, u64, ctypes.POINTER(u64)]
         for name in ("bwts_unpack_device", "bwts_unpack"):
             getattr(L, name).argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
@@ -523,6 +538,38 @@ class Context:
             raise BwtsError(-1, "one coded length per segment")
         self._check(lib().bwts_zrl_decode_segments_device(self._h, _ptr(d_in), il.ctypes.data, ls.ctypes.data, ls.size, _ptr(d_out)))
 
+    # -- byte-plane split in front of the transform (include/bwts_planes.h) -------------------------------
+    def _planes_host(self, fn, data, width):
+        a = _u8(data)
+        if a.size == 0:
+            raise BwtsError(-1, "empty input")
+        out = np.empty_like(a)
+        self._check(fn(self._h, a.ctypes.data, a.size, int(width), out.ctypes.data))
+        return out
+
+    def planes_split(self, data, width):
+        """bwts_planes_split: byte k of every `width`-byte element gathered into plane k, the tail copied (host buffers)."""
+        return self._planes_host(lib().bwts_planes_split, data, width)
+
+    def planes_join(self, data, width):
+        """bwts_planes_join: the inverse of planes_split (host buffers)."""
+        return self._planes_host(lib().bwts_planes_join, data, width)
+
+    def planes_split_device(self, d_in, n, width, d_out):
+        self._check(lib().bwts_planes_split_device(self._h, _ptr(d_in), int(n), int(width), _ptr(d_out)))
+
+    def planes_join_device(self, d_in, n, width, d_out):
+        self._check(lib().bwts_planes_join_device(self._h, _ptr(d_in), int(n), int(width), _ptr(d_out)))
+
+    def planes_split_segments_device(self, d_in, lengths, width, d_out):
+        """bwts_planes_split_segments_device: every segment split on its own, where it lies."""
+        ls = np.ascontiguousarray(lengths, dtype=np.uint64)
+        self._check(lib().bwts_planes_split_segments_device(self._h, _ptr(d_in), ls.ctypes.data, ls.size, int(width), _ptr(d_out)))
+
+    def planes_join_segments_device(self, d_in, lengths, width, d_out):
+        ls = np.ascontiguousarray(lengths, dtype=np.uint64)
+        self._check(lib().bwts_planes_join_segments_device(self._h, _ptr(d_in), ls.ctypes.data, ls.size, int(width), _ptr(d_out)))
+
     # -- the chain as one call: a checksummed frame (include/bwts_pack.h) -----------------------------
     def crc32_device(self, d_in, n):
         """bwts_crc32_device: zlib's CRC-32 of n device bytes."""
@@ -537,15 +584,20 @@ class Context:
         self._check(lib().bwts_crc32_segments_device(self._h, _ptr(d_in), ls.ctypes.data, ls.size, crcs.ctypes.data))
         return crcs
 
-    def pack(self, data, block_bytes=0, out_cap=None, version=1):
+    def pack(self, data, block_bytes=0, out_cap=None, version=None, planes=None):
         """bwts_pack_v: the frame of a byte string (host buffers); out_cap defaults to the bound; version 2: zero-run coding in front
-        of the coder."""
+        of the coder.  planes=2, 4 or 8 (bwts_pack_planes): a frame of version 3, the byte-plane split at that width in front of the
+        transform."""
         a = _u8(data)
         if a.size == 0:
             raise BwtsError(-1, "empty input")
-        out = np.empty(pack_bound(a.size, block_bytes, version) if out_cap is None else int(out_cap), dtype=np.uint8)
+        version = _pack_version(version, planes)
+        out = np.empty(pack_bound(a.size, block_bytes, version, planes) if out_cap is None else int(out_cap), dtype=np.uint8)
         got = ctypes.c_uint64(0)
-        self._check(lib().bwts_pack_v(self._h, int(version), a.ctypes.data, a.size, int(block_bytes), out.ctypes.data, out.size, ctypes.byref(got)))
+        if planes is None:
+            self._check(lib().bwts_pack_v(self._h, version, a.ctypes.data, a.size, int(block_bytes), out.ctypes.data, out.size, ctypes.byref(got)))
+        else:
+            self._check(lib().bwts_pack_planes(self._h, int(planes), a.ctypes.data, a.size, int(block_bytes), out.ctypes.data, out.size, ctypes.byref(got)))
         return out[:got.value].copy()
 
     def unpack(self, frame, out=None):
@@ -557,10 +609,14 @@ class Context:
         self._check(lib().bwts_unpack(self._h, a.ctypes.data, a.size, out.ctypes.data, out.size, ctypes.byref(got)))
         return out[:got.value]
 
-    def pack_device(self, d_in, n, block_bytes, d_out, out_cap, version=1):
-        """bwts_pack_device_v: returns the frame's size in bytes."""
+    def pack_device(self, d_in, n, block_bytes, d_out, out_cap, version=None, planes=None):
+        """bwts_pack_device_v, or with planes=2, 4 or 8 bwts_pack_planes_device (version 3): returns the frame's size in bytes."""
         got = ctypes.c_uint64(0)
-        self._check(lib().bwts_pack_device_v(self._h, int(version), _ptr(d_in), int(n), int(block_bytes), _ptr(d_out), int(out_cap), ctypes.byref(got)))
+        version = _pack_version(version, planes)
+        if planes is None:
+            self._check(lib().bwts_pack_device_v(self._h, version, _ptr(d_in), int(n), int(block_bytes), _ptr(d_out), int(out_cap), ctypes.byref(got)))
+        else:
+            self._check(lib().bwts_pack_planes_device(self._h, int(planes), _ptr(d_in), int(n), int(block_bytes), _ptr(d_out), int(out_cap), ctypes.byref(got)))
         return int(got.value)
 
     def unpack_device(self, d_in, in_bytes, d_out, out_cap):
@@ -739,6 +795,14 @@ def debug_zrl_plan(n):
     return {"T": int(buf[0]), "tiles": int(buf[1])}
 
 
+def debug_planes_plan(n, width):
+    """How the byte-plane split cuts one input of n bytes at a width (bwts_debug_planes_plan: host arithmetic, no context, no device)."""
+    buf = (ctypes.c_uint64 * 4)()
+    if lib().bwts_debug_planes_plan(int(n), int(width), buf) < 0:
+        raise BwtsError(-1, "bad length or width")
+    return {"T": int(buf[0]), "tiles": int(buf[1]), "q": int(buf[2]), "tail": int(buf[3])}
+
+
 def zrl_bound(n):
     """bwts_zrl_bound: the most bytes the zero-run stage writes for an input of n bytes: n."""
     b = int(lib().bwts_zrl_bound(int(n)))
@@ -747,9 +811,23 @@ def zrl_bound(n):
     return b
 
 
-def pack_bound(n, block_bytes=0, version=1):
-    """bwts_pack_bound_v: the largest frame of the given version an input of n bytes cut at block_bytes can have."""
-    b = int(lib().bwts_pack_bound_v(int(version), int(n), int(block_bytes)))
+def _pack_version(version, planes):
+    """The frame version a pack is asked for: 1 unless named; planes alone means 3, and goes with no other version."""
+    if planes is None:
+        return 1 if version is None else int(version)
+    if version is not None and int(version) != 3:
+        raise BwtsError(-1, "planes asks for a frame of version 3")
+    return 3
+
+
+def pack_bound(n, block_bytes=0, version=None, planes=None):
+    """bwts_pack_bound_v: the largest frame of the given version an input of n bytes cut at block_bytes can have; with planes=2, 4 or 8
+    bwts_pack_planes_bound (version 3)."""
+    version = _pack_version(version, planes)
+    if planes is None:
+        b = int(lib().bwts_pack_bound_v(version, int(n), int(block_bytes)))
+    else:
+        b = int(lib().bwts_pack_planes_bound(int(planes), int(n), int(block_bytes)))
     if b == 0:
         raise BwtsError(-5 if int(n) > (1 << 32) else -1, "no bound for these arguments")
     return b

@@ -2,9 +2,12 @@
  * bwts_pack -- compress a file on the GPU: bijective BWT, move-to-front and rANS over blocks, one checksummed frame
  * (include/bwts_pack.h) per 2^32 input bytes.
  *
- *   bwts_pack [-z] [-b <KiB>] <infile> [<outfile>]
+ *   bwts_pack [-z] [-p <2|4|8>] [-b <KiB>] <infile> [<outfile>]
  *   -b <KiB>: block size in KiB, at least 4 (default: every frame is one block)
- *   -z: frames of version 2, zero-run coding between move-to-front and the coder (before or behind -b)
+ *   -z: frames of version 2, zero-run coding between move-to-front and the coder
+ *   -p <width>: frames of version 3 for arrays of 2-, 4- or 8-byte numbers: every block split into byte planes in front of the
+ *      transform; implies -z
+ *   the options come in any order
  *   no outfile: the frames go to standard output
  *   any error: a message on stderr, exit 1
  * The output is opened once the first frame exists, so a failing run leaves no truncated destination behind.
@@ -23,9 +26,10 @@
 
 static void usage(void)
 {
-	fprintf(stderr, "Usage: bwts_pack [-z] [-b <KiB>] <infile> [<outfile>]\n");
+	fprintf(stderr, "Usage: bwts_pack [-z] [-p <2|4|8>] [-b <KiB>] <infile> [<outfile>]\n");
 	fprintf(stderr, "-b: block size in KiB, at least 4 (default: one block per frame)\n");
 	fprintf(stderr, "-z: zero-run coding in front of the coder (frame version 2)\n");
+	fprintf(stderr, "-p: byte planes of 2-, 4- or 8-byte numbers in front of the transform (frame version 3; implies -z)\n");
 	fprintf(stderr, "If unspecified, output is written to standard output\n");
 	exit(1);
 }
@@ -45,7 +49,7 @@ int main(int argc, char **argv)
 	FILE *fp = NULL;
 	int rc, arg = 1;
 	uint64_t block_bytes = 0, at, in_total, out_total = 0, cap;
-	uint32_t version = 1;
+	uint32_t version = 1, width = 0;
 	double device_ms = 0.0;
 	const char *dev = getenv("BWTS_DEVICE"), *show_env = getenv("BWTS_TIMINGS"), *out_name;
 	const int show = show_env && show_env[0] == '1';
@@ -53,7 +57,7 @@ int main(int argc, char **argv)
 
 	marks.main_start = cli_now_s();
 	marks.write_s = 0.0;
-	while (arg < argc && (strcmp(argv[arg], "-b") == 0 || strcmp(argv[arg], "-z") == 0)) {
+	while (arg < argc && (strcmp(argv[arg], "-b") == 0 || strcmp(argv[arg], "-z") == 0 || strcmp(argv[arg], "-p") == 0)) {
 		char *end = NULL;
 		unsigned long long kib;
 
@@ -64,6 +68,16 @@ int main(int argc, char **argv)
 		}
 		if (argc < arg + 2)
 			usage();
+		if (argv[arg][1] == 'p') {
+			kib = strtoull(argv[arg + 1], &end, 10);
+			if (!end || *end || (kib != 2 && kib != 4 && kib != 8)) {
+				fprintf(stderr, "bwts_pack: the width of a number must be 2, 4 or 8 bytes\n");
+				exit(1);
+			}
+			width = (uint32_t)kib;
+			arg += 2;
+			continue;
+		}
 		kib = strtoull(argv[arg + 1], &end, 10);
 		if (!end || *end || kib < 4 || kib > (1ull << 22)) {
 			fprintf(stderr, "bwts_pack: block size must be 4 .. 4194304 KiB\n");
@@ -82,7 +96,8 @@ int main(int argc, char **argv)
 	if ((rc = bwts_ctx_create(&ctx, dev ? atoi(dev) : 0)) != BWTS_OK)
 		fail("cannot open GPU context", rc);
 	marks.ctx_ready = cli_now_s();
-	cap = bwts_pack_bound_v(version, in_total < FRAME_INPUT_MAX ? in_total : FRAME_INPUT_MAX, block_bytes);
+	cap = width ? bwts_pack_planes_bound(width, in_total < FRAME_INPUT_MAX ? in_total : FRAME_INPUT_MAX, block_bytes)
+		    : bwts_pack_bound_v(version, in_total < FRAME_INPUT_MAX ? in_total : FRAME_INPUT_MAX, block_bytes);
 	out = cap ? malloc(cap) : NULL;
 	if (!out) {
 		fprintf(stderr, "bwts_pack: no memory for a frame of up to %llu bytes\n", (unsigned long long)cap);
@@ -93,7 +108,9 @@ int main(int argc, char **argv)
 		uint64_t bytes = 0;
 		double t0;
 
-		if ((rc = bwts_pack_v(ctx, version, text + at, n, block_bytes, out, cap, &bytes)) != BWTS_OK)
+		rc = width ? bwts_pack_planes(ctx, width, text + at, n, block_bytes, out, cap, &bytes)
+			   : bwts_pack_v(ctx, version, text + at, n, block_bytes, out, cap, &bytes);
+		if (rc != BWTS_OK)
 			fail("packing failed", rc);
 		bwts_last_timings(ctx, &t);
 		device_ms += t.total_ms;

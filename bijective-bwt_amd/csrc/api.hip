@@ -4,9 +4,11 @@
 #include "../../include/bwts_mtf.h"
 #include "../../include/bwts_ec.h"
 #include "../../include/bwts_zrl.h"
+#include "../../include/bwts_planes.h"
 #include "../../include/bwts_pack.h"
 #include "ec_plan.h"
 #include "zrl_plan.h"
+#include "planes_plan.h"
 #include "pack_plan.h"
 
 #include <new>
@@ -563,6 +565,65 @@ extern "C" int bwts_zrl_decode(bwts_ctx *ctx, const uint8_t *in, uint64_t in_byt
 }
 
 // ------------------------------------------------------------------------------------
+// byte-plane split in front of the transform (include/bwts_planes.h): n bytes to n bytes at a width, the kernels in planes.hip
+// ------------------------------------------------------------------------------------
+static int planes_device(bwts_ctx *ctx, const void *d_in, uint64_t n, uint32_t width, void *d_out, bool join)
+{
+    if (!ctx || !d_in || !d_out || n == 0 || !planes_width_ok(width)) return BWTS_E_ARG;
+    if (n > PLANES_MAX_N) return BWTS_E_RANGE;
+    if (ranges_overlap(d_in, n, d_out, n)) return BWTS_E_ARG;
+    return run_sized(ctx, n, join ? "planes join" : "planes split", [&] { return planes_impl(ctx, (const u8 *)d_in, n, width, (u8 *)d_out, join, SEG_SINGLE); });
+}
+
+static int planes_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, uint32_t width, void *d_out, bool join)
+{
+    if (!ctx || !d_in || !d_out || !planes_width_ok(width)) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(seg_table_set(ctx, lengths, count, &n));
+    if (ranges_overlap(d_in, n, d_out, n)) return BWTS_E_ARG;
+    return run_sized(ctx, n, join ? "planes join" : "planes split", [&] { return planes_impl(ctx, (const u8 *)d_in, n, width, (u8 *)d_out, join, seg_mode(ctx)); });
+}
+
+static int planes_host(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint32_t width, uint8_t *out, bool join)
+{
+    if (!ctx || !in || !out || n == 0 || !planes_width_ok(width)) return BWTS_E_ARG;
+    if (n > PLANES_MAX_N) return BWTS_E_RANGE;
+    u64 made = 0;
+    const HostTrip trip = {in, n, n, out, &made};
+    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *got) { *got = n; return planes_device(ctx, d_in, n, width, d_out, join); });
+}
+
+extern "C" int bwts_planes_split_device(bwts_ctx *ctx, const void *d_in, uint64_t n, uint32_t width, void *d_out)
+{
+    return planes_device(ctx, d_in, n, width, d_out, false);
+}
+
+extern "C" int bwts_planes_join_device(bwts_ctx *ctx, const void *d_in, uint64_t n, uint32_t width, void *d_out)
+{
+    return planes_device(ctx, d_in, n, width, d_out, true);
+}
+
+extern "C" int bwts_planes_split_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, uint32_t width, void *d_out)
+{
+    return planes_segments_device(ctx, d_in, lengths, count, width, d_out, false);
+}
+
+extern "C" int bwts_planes_join_segments_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, uint64_t count, uint32_t width, void *d_out)
+{
+    return planes_segments_device(ctx, d_in, lengths, count, width, d_out, true);
+}
+
+extern "C" int bwts_planes_split(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint32_t width, uint8_t *out)
+{
+    return planes_host(ctx, in, n, width, out, false);
+}
+
+extern "C" int bwts_planes_join(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint32_t width, uint8_t *out)
+{
+    return planes_host(ctx, in, n, width, out, true);
+}
+
+// ------------------------------------------------------------------------------------
 // checksum and the packed frame (include/bwts_pack.h): the chain of the three stages as one call, the kernel in crc.hip, the drivers
 // in pack.hip
 // ------------------------------------------------------------------------------------
@@ -584,8 +645,14 @@ extern "C" int bwts_crc32_segments_device(bwts_ctx *ctx, const void *d_in, const
 extern "C" uint64_t bwts_pack_bound_v(uint32_t version, uint64_t n, uint64_t block_bytes)
 {
     const u64 B = pack_block_len(n, block_bytes);
-    if (!B || !pack_version_ok(version)) return 0;
+    if (!B || !pack_version_asked_ok(version)) return 0;
     return version == PACK_VERSION_2 ? pack_bound_bytes_v2(n, B) : pack_bound_bytes(n, B);
+}
+
+extern "C" uint64_t bwts_pack_planes_bound(uint32_t width, uint64_t n, uint64_t block_bytes)
+{
+    const u64 B = pack_block_len(n, block_bytes);
+    return B && planes_width_ok(width) ? pack_bound_bytes_v2(n, B) : 0;
 }
 
 extern "C" uint64_t bwts_pack_bound(uint64_t n, uint64_t block_bytes)
@@ -603,14 +670,45 @@ extern "C" int bwts_unpack_size(const uint8_t *frame, uint64_t in_bytes, uint64_
     return BWTS_OK;
 }
 
-extern "C" int bwts_pack_device_v(bwts_ctx *ctx, uint32_t version, const void *d_in, uint64_t n, uint64_t block_bytes, void *d_out, uint64_t out_cap,
-                                  uint64_t *out_bytes)
+// the device form of every version (width: 0 but for version 3)
+static int pack_device_any(bwts_ctx *ctx, uint32_t version, uint32_t width, const void *d_in, uint64_t n, uint64_t block_bytes, void *d_out, uint64_t out_cap,
+                           uint64_t *out_bytes)
 {
-    if (!ctx || !d_in || !d_out || !out_bytes || n == 0 || ((uintptr_t)d_out & 15) || !pack_version_ok(version)) return BWTS_E_ARG;
+    if (!ctx || !d_in || !d_out || !out_bytes || n == 0 || ((uintptr_t)d_out & 15)) return BWTS_E_ARG;
     if (n > PACK_MAX_N) return BWTS_E_RANGE;
     const u64 B = pack_block_len(n, block_bytes);
     if (B == 0 || ranges_overlap(d_in, n, d_out, out_cap)) return BWTS_E_ARG;
-    return run_sized(ctx, n, "pack", [&] { return pack_device_impl(ctx, version, (const u8 *)d_in, n, B, (u8 *)d_out, out_cap, out_bytes); });
+    return run_sized(ctx, n, "pack", [&] { return pack_device_impl(ctx, version, width, (const u8 *)d_in, n, B, (u8 *)d_out, out_cap, out_bytes); });
+}
+
+// the host form of every version
+static int pack_host_any(bwts_ctx *ctx, uint32_t version, uint32_t width, const uint8_t *in, uint64_t n, uint64_t block_bytes, uint8_t *out, uint64_t out_cap,
+                         uint64_t *out_bytes)
+{
+    if (!ctx || !in || !out || !out_bytes || n == 0) return BWTS_E_ARG;
+    if (n > PACK_MAX_N) return BWTS_E_RANGE;
+    const u64 B = pack_block_len(n, block_bytes);
+    if (B == 0) return BWTS_E_ARG;
+    const bool v1 = version == PACK_VERSION;
+    const u64 bound = v1 ? pack_bound_bytes(n, B) : pack_bound_bytes_v2(n, B);
+    const u64 cap = out_cap < bound ? out_cap : bound;
+    if (cap < (v1 ? pack_least_bytes(n, B) : pack_least_bytes_v2(n, B))) return BWTS_E_SPACE;
+    const HostTrip trip = {in, n, n > cap ? n : cap, out, out_bytes};
+    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *bytes) { return pack_device_any(ctx, version, width, d_in, n, block_bytes, d_out, cap, bytes); });
+}
+
+extern "C" int bwts_pack_device_v(bwts_ctx *ctx, uint32_t version, const void *d_in, uint64_t n, uint64_t block_bytes, void *d_out, uint64_t out_cap,
+                                  uint64_t *out_bytes)
+{
+    if (!pack_version_asked_ok(version)) return BWTS_E_ARG;
+    return pack_device_any(ctx, version, 0, d_in, n, block_bytes, d_out, out_cap, out_bytes);
+}
+
+extern "C" int bwts_pack_planes_device(bwts_ctx *ctx, uint32_t width, const void *d_in, uint64_t n, uint64_t block_bytes, void *d_out, uint64_t out_cap,
+                                       uint64_t *out_bytes)
+{
+    if (!planes_width_ok(width)) return BWTS_E_ARG;
+    return pack_device_any(ctx, PACK_VERSION_3, width, d_in, n, block_bytes, d_out, out_cap, out_bytes);
 }
 
 extern "C" int bwts_pack_device(bwts_ctx *ctx, const void *d_in, uint64_t n, uint64_t block_bytes, void *d_out, uint64_t out_cap, uint64_t *out_bytes)
@@ -628,16 +726,15 @@ extern "C" int bwts_unpack_device(bwts_ctx *ctx, const void *d_in, uint64_t in_b
 extern "C" int bwts_pack_v(bwts_ctx *ctx, uint32_t version, const uint8_t *in, uint64_t n, uint64_t block_bytes, uint8_t *out, uint64_t out_cap,
                            uint64_t *out_bytes)
 {
-    if (!ctx || !in || !out || !out_bytes || n == 0 || !pack_version_ok(version)) return BWTS_E_ARG;
-    if (n > PACK_MAX_N) return BWTS_E_RANGE;
-    const u64 B = pack_block_len(n, block_bytes);
-    if (B == 0) return BWTS_E_ARG;
-    const bool v2 = version == PACK_VERSION_2;
-    const u64 bound = v2 ? pack_bound_bytes_v2(n, B) : pack_bound_bytes(n, B);
-    const u64 cap = out_cap < bound ? out_cap : bound;
-    if (cap < (v2 ? pack_least_bytes_v2(n, B) : pack_least_bytes(n, B))) return BWTS_E_SPACE;
-    const HostTrip trip = {in, n, n > cap ? n : cap, out, out_bytes};
-    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *bytes) { return bwts_pack_device_v(ctx, version, d_in, n, block_bytes, d_out, cap, bytes); });
+    if (!pack_version_asked_ok(version)) return BWTS_E_ARG;
+    return pack_host_any(ctx, version, 0, in, n, block_bytes, out, out_cap, out_bytes);
+}
+
+extern "C" int bwts_pack_planes(bwts_ctx *ctx, uint32_t width, const uint8_t *in, uint64_t n, uint64_t block_bytes, uint8_t *out, uint64_t out_cap,
+                                uint64_t *out_bytes)
+{
+    if (!planes_width_ok(width)) return BWTS_E_ARG;
+    return pack_host_any(ctx, PACK_VERSION_3, width, in, n, block_bytes, out, out_cap, out_bytes);
 }
 
 extern "C" int bwts_pack(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint64_t block_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes)

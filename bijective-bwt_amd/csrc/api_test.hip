@@ -4,6 +4,7 @@
 #include "../../include/bwts_test.h"
 #include "ec_plan.h"
 #include "zrl_plan.h"
+#include "planes_plan.h"
 #include "pack_plan.h"
 
 #include <stdlib.h>
@@ -126,6 +127,14 @@ extern "C" int bwts_debug_zrl_plan(uint64_t n, uint64_t out[2])
 {
     if (n == 0 || n > ZRL_MAX_N || !out) return -1;
     bwts_zrl_plan(n, out);
+    return 0;
+}
+
+// the byte-plane split's cut of one input of n bytes at a width: tile bytes, tiles, elements, tail bytes.  No context, no device
+extern "C" int bwts_debug_planes_plan(uint64_t n, uint32_t width, uint64_t out[4])
+{
+    if (n == 0 || n > PLANES_MAX_N || !planes_width_ok(width) || !out) return -1;
+    bwts_planes_plan(n, width, out);
     return 0;
 }
 

@@ -341,11 +341,15 @@ int zrl_encode_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u8 *d_out, u64 out_cap
 int zrl_decode_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 n, SegMode segs, const u64 *in_lengths);
 void bwts_zrl_plan(u64 n, u64 out[2]);                                  // tile size and tiles of one input of n bytes
 
+// ---- byte-plane split in front of the transform (planes.hip; include/bwts_planes.h) ----
+int planes_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u32 w, u8 *d_out, bool join, SegMode segs);
+void bwts_planes_plan(u64 n, u32 w, u64 out[4]);                        // tile bytes, tiles, elements and tail bytes of one input of n bytes
+
 // ---- checksum and the packed frame (crc.hip, pack.hip; include/bwts_pack.h) ------------
 // one value for the input of n bytes, or one per segment, to the host
 int crc_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, SegMode segs, u32 *crcs);
 void bwts_crc_plan(u64 n, u64 out[4]);                                  // tile size, tiles per fold group, tiles and groups of one input
-int pack_device_impl(bwts_ctx *ctx, u32 version, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes);
+int pack_device_impl(bwts_ctx *ctx, u32 version, u32 width, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes);   // width: version 3 only
 int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out);
 
 // chunk tables of the forward's later rounds (chunk_rounds.h) as plain arithmetic: nominal chunk size of a list, the tables' capacity

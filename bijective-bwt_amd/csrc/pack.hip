@@ -1,5 +1,5 @@
-// pack.hip -- the chain as one call (include/bwts_pack.h): checksums, transform, move-to-front, zero-run coding (frame version 2) and
-// entropy coder over the blocks of a frame, and the way back.  No kernel of its own: the stages are the ones behind the single calls, run one after the other inside
+// pack.hip -- the chain as one call (include/bwts_pack.h): checksums, byte-plane split (frame version 3), transform, move-to-front,
+// zero-run coding (frame versions 2 and 3) and entropy coder over the blocks of a frame, and the way back.  No kernel of its own: the stages are the ones behind the single calls, run one after the other inside
 // one call bracket; the frame's arithmetic and the checks of an untrusted frame are in pack_plan.h.
 //
 // A frame of one block goes through the single-input stages, one of several blocks through the segment forms (the bytes are the
@@ -8,13 +8,16 @@
 // writes its own (seg_layout.h: the regions, and who overlaps whom).  Header and directory travel through pinned memory too: the
 // small block, and for several blocks the directory region behind the segment table (version 1; the 32-byte entries of version 2 do
 // not fit that region and travel through a host block of the call's own).
-// Version 2 changes the segment table on the way: the coder's segments are the blocks' zero-run coded bytes, every other stage's
-// the blocks themselves.
+// Versions 2 and 3 change the segment table on the way: the coder's segments are the blocks' zero-run coded bytes, every other
+// stage's the blocks themselves.
+// The bytes between two stages go to and fro between two blocks (pack) or between one block and d_out (unpack); where a version has
+// a stage more, the directions swap, so that the last stage of an unpack always lands in d_out.
 #include "internal.h"
 #include "pack_plan.h"
 #include "../../include/bwts_pack.h"
 
 #include <string.h>
+#include <utility>
 
 static_assert(PACK_OK == BWTS_OK && PACK_RANGE == BWTS_E_RANGE && PACK_FORMAT == BWTS_E_FORMAT, "pack_plan.h answers in the library's codes");
 
@@ -38,11 +41,11 @@ static int pack_blocks_set(bwts_ctx *ctx, u64 n, u64 B, u64 nblk)
 }
 
 // room on the host for a directory of nblk entries: the small block behind the header, or for several blocks the directory region
-// behind the segment table (pinned; version 1) or `own` (version 2)
+// behind the segment table (pinned; version 1) or `own` (versions 2 and 3)
 static int pack_dir_staging(bwts_ctx *ctx, u32 version, u64 nblk, std::vector<u8> &own, u8 **dir)
 {
     if (nblk == 1) { *dir = (u8 *)(ctx->h_small + SM_PACK_HEAD) + PACK_HEADER_BYTES; return BWTS_OK; }
-    if (version == PACK_VERSION_2) {
+    if (version != PACK_VERSION) {
         own.resize((size_t)(PACK_ENTRY_BYTES_V2 * nblk));
         *dir = own.data();
         return BWTS_OK;
@@ -57,43 +60,50 @@ static int pack_coded_set(bwts_ctx *ctx, const std::vector<u64> &coded, u64 *tot
     return seg_table_set(ctx, coded.data(), coded.size(), total);
 }
 
-int pack_device_impl(bwts_ctx *ctx, u32 version, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes)
+int pack_device_impl(bwts_ctx *ctx, u32 version, u32 width, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes)
 {
-    const bool v2 = version == PACK_VERSION_2;
+    const bool zrl = version != PACK_VERSION, planes = version == PACK_VERSION_3;
     const u64 nblk = pack_blocks(n, B), fixed = pack_fixed_bytes_v(version, nblk), entry = pack_entry_bytes(version);
     const bool seg = nblk > 1;
-    if (out_cap < (v2 ? pack_least_bytes_v2(n, B) : pack_least_bytes(n, B))) return BWTS_E_SPACE;
+    if (out_cap < (zrl ? pack_least_bytes_v2(n, B) : pack_least_bytes(n, B))) return BWTS_E_SPACE;
     BWTS_TRY(pack_blocks_set(ctx, n, B, nblk));
     SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
     std::vector<u32> crcs((size_t)nblk);
     std::vector<u64> sizes((size_t)nblk), coded((size_t)nblk);
     BWTS_TRY(crc_impl(ctx, d_in, n, segs, crcs.data()));
-    u8 *a = nullptr, *b = nullptr;
-    BWTS_TRY(pack_stage(ctx, 0, n, &a));
-    BWTS_TRY(pack_stage(ctx, 1, n, &b));
-    BWTS_TRY(seg ? forward_segments_impl(ctx, d_in, n, a) : forward_device_impl(ctx, d_in, n, a));
-    HIPC(hipStreamSynchronize(ctx->stream));
-    BWTS_TRY(mtf_impl(ctx, a, n, b, false, segs));
-    HIPC(hipStreamSynchronize(ctx->stream));
-    const u8 *ranks = b;
+    // a stage reads `from` and writes `to`; the two blocks swap behind it
+    u8 *to = nullptr, *other = nullptr;
+    BWTS_TRY(pack_stage(ctx, 0, n, &to));
+    BWTS_TRY(pack_stage(ctx, 1, n, &other));
+    const u8 *from = d_in;
+    auto done = [&] { from = to; std::swap(to, other); return hipStreamSynchronize(ctx->stream); };
+    if (planes) {
+        // every block split on its own; the checksums above are the original bytes'
+        BWTS_TRY(planes_impl(ctx, from, n, width, to, false, segs));
+        HIPC(done());
+    }
+    BWTS_TRY(seg ? forward_segments_impl(ctx, from, n, to) : forward_device_impl(ctx, from, n, to));
+    HIPC(done());
+    BWTS_TRY(mtf_impl(ctx, from, n, to, false, segs));
+    HIPC(done());
     u64 m = n;
-    if (v2) {
-        // the ranks' coded bytes go back into the first block, one block's behind the other's: the coder's segments
-        BWTS_TRY(zrl_encode_impl(ctx, b, n, a, n, segs, coded.data()));
-        HIPC(hipStreamSynchronize(ctx->stream));
+    if (zrl) {
+        // the ranks' coded bytes, one block's behind the other's: the coder's segments
+        BWTS_TRY(zrl_encode_impl(ctx, from, n, to, n, segs, coded.data()));
+        HIPC(done());
         BWTS_TRY(pack_coded_set(ctx, coded, &m));
         if (seg) segs = seg_mode(ctx);
-        ranks = a;
     }
     // the streams go straight to their place; a frame that does not fit is refused by the coder before it writes anything
-    BWTS_TRY(ec_encode_impl(ctx, ranks, m, d_out + fixed, out_cap - fixed, segs, sizes.data()));
+    BWTS_TRY(ec_encode_impl(ctx, from, m, d_out + fixed, out_cap - fixed, segs, sizes.data()));
     HIPC(hipStreamSynchronize(ctx->stream));
     u8 *head = (u8 *)(ctx->h_small + SM_PACK_HEAD), *dir = nullptr;
     std::vector<u8> own;
     BWTS_TRY(pack_dir_staging(ctx, version, nblk, own, &dir));
     u64 total = fixed;
     for (u64 k = 0; k < nblk; k++) {
-        if (v2) pack_entry_write_v2(dir + entry * k, sizes[(size_t)k], crcs[(size_t)k], coded[(size_t)k]);
+        if (planes) pack_entry_write_v3(dir + entry * k, sizes[(size_t)k], crcs[(size_t)k], coded[(size_t)k], width);
+        else if (zrl) pack_entry_write_v2(dir + entry * k, sizes[(size_t)k], crcs[(size_t)k], coded[(size_t)k]);
         else pack_entry_write(dir + entry * k, sizes[(size_t)k], crcs[(size_t)k]);
         total += sizes[(size_t)k];
     }
@@ -117,7 +127,7 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
     HIPC(hipStreamSynchronize(ctx->stream));
     PackHeader H;
     BWTS_TRY(pack_header_check(head, in_bytes, &H));
-    const bool seg = H.nblk > 1, v2 = H.version == PACK_VERSION_2;
+    const bool seg = H.nblk > 1, zrl = H.version != PACK_VERSION, planes = H.version == PACK_VERSION_3;
     const u64 fixed = pack_fixed_bytes_v(H.version, H.nblk), entry = pack_entry_bytes(H.version);
     BWTS_TRY(pack_blocks_set(ctx, H.n, H.B, H.nblk));
     const SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
@@ -137,39 +147,50 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
     for (u64 k = 0; k < H.nblk; k++) {
         sizes[(size_t)k] = pack_le64(dir + entry * k);
         want[(size_t)k] = ec_le32(dir + entry * k + 8);
-        coded[(size_t)k] = v2 ? pack_le64(dir + entry * k + 16) : pack_block_at(H.n, H.B, k);
+        coded[(size_t)k] = zrl ? pack_le64(dir + entry * k + 16) : pack_block_at(H.n, H.B, k);
     }
-    // version 1: ranks into d_out, bytes of the transform into the stage block, the input's bytes into d_out.  Version 2: the ranks'
-    // coded bytes into the stage block first, and from there the ranks into d_out.
-    u8 *a = nullptr;
-    BWTS_TRY(pack_stage(ctx, 0, H.n, &a));
-    u8 *ranks = v2 ? a : d_out;
+    // The stages go to and fro between d_out and the stage block, and the last one lands in d_out.  Version 1, three stages: ranks
+    // into d_out, bytes of the transform into the block, the input's bytes into d_out.  Version 2, four: the ranks' coded bytes into
+    // the block first.  Version 3, five: the coded bytes into d_out first (they are no more than the H.n bytes it holds), the ranks
+    // into the block, and at the end the join from the block into d_out.
+    u8 *block = nullptr;
+    BWTS_TRY(pack_stage(ctx, 0, H.n, &block));
+    const bool odd = !zrl || planes;        // an odd number of stages: the first one writes d_out
+    u8 *to = odd ? d_out : block, *other = odd ? block : d_out;
+    const u8 *from = nullptr;
+    auto done = [&] { from = to; std::swap(to, other); return hipStreamSynchronize(ctx->stream); };
     u64 m = H.n;
     SegMode csegs = segs;
-    if (v2) {
+    if (zrl) {
         BWTS_TRY(pack_coded_set(ctx, coded, &m));
         if (seg) csegs = seg_mode(ctx);
     }
     if (seg) {
-        BWTS_TRY(ec_decode_impl(ctx, d_in + fixed, m, ranks, m, nullptr, csegs, sizes.data()));
+        BWTS_TRY(ec_decode_impl(ctx, d_in + fixed, m, to, m, nullptr, csegs, sizes.data()));
     } else {
         u64 named = 0;
-        const int rc = ec_decode_impl(ctx, d_in + fixed, sizes[0], ranks, m, &named, csegs, nullptr);
+        const int rc = ec_decode_impl(ctx, d_in + fixed, sizes[0], to, m, &named, csegs, nullptr);
         // (room for the bytes the directory names is what the coder was given: a stream that names more, or less, is not this frame's)
         if (rc == BWTS_E_SPACE || (rc == BWTS_OK && named != m)) return BWTS_E_FORMAT;
         BWTS_TRY(rc);
     }
-    if (v2) {
+    from = to; std::swap(to, other);
+    if (zrl) {
         HIPC(hipStreamSynchronize(ctx->stream));
         ctx->tm.n = H.n;        // (the coder has put its own n there: the coded bytes)
         BWTS_TRY(pack_blocks_set(ctx, H.n, H.B, H.nblk));
-        BWTS_TRY(zrl_decode_impl(ctx, a, m, d_out, H.n, segs, coded.data()));
-        HIPC(hipStreamSynchronize(ctx->stream));
+        BWTS_TRY(zrl_decode_impl(ctx, from, m, to, H.n, segs, coded.data()));
+        HIPC(done());
     }
-    BWTS_TRY(mtf_impl(ctx, d_out, H.n, a, true, segs));
-    HIPC(hipStreamSynchronize(ctx->stream));
-    BWTS_TRY(seg ? inverse_segments_impl(ctx, a, H.n, d_out) : inverse_device_impl(ctx, a, H.n, d_out));
-    HIPC(hipStreamSynchronize(ctx->stream));
+    BWTS_TRY(mtf_impl(ctx, from, H.n, to, true, segs));
+    HIPC(done());
+    BWTS_TRY(seg ? inverse_segments_impl(ctx, from, H.n, to) : inverse_device_impl(ctx, from, H.n, to));
+    HIPC(done());
+    if (planes) {
+        BWTS_TRY(planes_impl(ctx, from, H.n, H.width, to, true, segs));
+        HIPC(done());
+    }
+    if (from != d_out) return BWTS_E_INTERNAL;
     BWTS_TRY(crc_impl(ctx, d_out, H.n, segs, got.data()));
     if (memcmp(got.data(), want.data(), (size_t)H.nblk * sizeof(u32)) != 0) return BWTS_E_CHECKSUM;
     *n_out = H.n;

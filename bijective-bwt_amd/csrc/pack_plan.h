@@ -1,14 +1,16 @@
-// pack_plan.h -- the arithmetic of the packed frame (include/bwts_pack.h, versions 1 and 2) and of its checksum that host and device share:
+// pack_plan.h -- the arithmetic of the packed frame (include/bwts_pack.h, versions 1 to 3) and of its checksum that host and device share:
 // CRC-32 as polynomial arithmetic over GF(2), how an input is cut into blocks, the bound, and what makes a header and a directory
-// valid.  Plain C++ with no dependency but ec_plan.h: crc.hip, pack.hip, the host side of the calls and a stand-alone host program
+// valid.  Plain C++ with no dependency but ec_plan.h and planes_plan.h: crc.hip, pack.hip, the host side of the calls and a stand-alone host program
 // (tests/pack_plan_check.cc, built with the sanitizers) all compile this file.
 #pragma once
 #include <stdint.h>
 #include "ec_plan.h"
+#include "planes_plan.h"
 
 #define PACK_MAGIC 0x5A545742u           // "BWTZ"
 #define PACK_VERSION 1u
 #define PACK_VERSION_2 2u                // zero-run coding between the ranks and the coder: a directory entry names the coded bytes too
+#define PACK_VERSION_3 3u                // version 2 with the byte-plane split in front of the transform: an entry names the width too
 #define PACK_HEADER_BYTES 32u
 #define PACK_ENTRY_BYTES 16u
 #define PACK_ENTRY_BYTES_V2 32u
@@ -109,8 +111,14 @@ EC_HD uint64_t pack_least_bytes(uint64_t n, uint64_t B)
 }
 
 // ---- version 2: the same header with version = 2, entries of 32 bytes, the coder's streams over the zero-run coded bytes ----
-EC_HD bool pack_version_ok(uint32_t version) { return version == PACK_VERSION || version == PACK_VERSION_2; }
-EC_HD uint32_t pack_entry_bytes(uint32_t version) { return version == PACK_VERSION_2 ? PACK_ENTRY_BYTES_V2 : PACK_ENTRY_BYTES; }
+// ---- version 3: version 2 with version = 3 and the width of the split in the word at entry offset 12; bound and least size are version 2's ----
+// what a frame may say ...
+EC_HD bool pack_version_ok(uint32_t version) { return version == PACK_VERSION || version == PACK_VERSION_2 || version == PACK_VERSION_3; }
+// ... and what the _v calls may be asked for: version 3 has calls of its own, which take the width
+EC_HD bool pack_version_asked_ok(uint32_t version) { return version == PACK_VERSION || version == PACK_VERSION_2; }
+EC_HD uint32_t pack_entry_bytes(uint32_t version) { return version == PACK_VERSION ? PACK_ENTRY_BYTES : PACK_ENTRY_BYTES_V2; }
+// the word at entry offset 12: zero in versions 1 and 2, the width in version 3
+EC_HD bool pack_width_word_ok(uint32_t version, uint32_t word) { return version == PACK_VERSION_3 ? planes_width_ok(word) : word == 0u; }
 EC_HD uint64_t pack_fixed_bytes_v(uint32_t version, uint64_t nblk) { return PACK_HEADER_BYTES + (uint64_t)pack_entry_bytes(version) * nblk; }
 // the zero-run stage never expands, and the coder's bound grows with its input: the version-1 streams' bound holds
 EC_HD uint64_t pack_bound_bytes_v2(uint64_t n, uint64_t B)
@@ -134,6 +142,11 @@ EC_HD void pack_entry_write_v2(uint8_t e[32], uint64_t stream_bytes, uint32_t cr
     pack_entry_write(e, stream_bytes, crc);
     pack_put64(e + 16, coded_bytes); pack_put64(e + 24, 0u);
 }
+EC_HD void pack_entry_write_v3(uint8_t e[32], uint64_t stream_bytes, uint32_t crc, uint64_t coded_bytes, uint32_t width)
+{
+    pack_entry_write_v2(e, stream_bytes, crc, coded_bytes);
+    ec_put32(e + 12, width);
+}
 // the header of a frame whose directory (nblk entries) is complete
 EC_HD void pack_header_write_v(uint8_t h[32], uint32_t version, uint64_t n, uint64_t B, const uint8_t *dir)
 {
@@ -143,7 +156,7 @@ EC_HD void pack_header_write_v(uint8_t h[32], uint32_t version, uint64_t n, uint
 }
 EC_HD void pack_header_write(uint8_t h[32], uint64_t n, uint64_t B, const uint8_t *dir) { pack_header_write_v(h, PACK_VERSION, n, B, dir); }
 
-struct PackHeader { uint64_t n, B, nblk; uint32_t dir_crc, version; };
+struct PackHeader { uint64_t n, B, nblk; uint32_t dir_crc, version, width; };      // width: 0 until the directory has been judged, and in versions 1 and 2
 
 // The header of a frame of which in_bytes bytes are at hand (h: the first 32 of them, read only when in_bytes allows a frame at all).
 // PACK_OK and *H, PACK_FORMAT, or PACK_RANGE for a sound header that names more than 2^32 bytes.
@@ -156,24 +169,25 @@ EC_HD int pack_header_check(const uint8_t *h, uint64_t in_bytes, PackHeader *H)
     if (n == 0) return PACK_FORMAT;
     if (n > PACK_MAX_N) return PACK_RANGE;
     if (B == 0 || B > n || (B < PACK_MIN_BLOCK && B != n)) return PACK_FORMAT;
-    H->n = n; H->B = B; H->nblk = pack_blocks(n, B); H->dir_crc = ec_le32(h + 24); H->version = ec_le32(h + 4);
+    H->n = n; H->B = B; H->nblk = pack_blocks(n, B); H->dir_crc = ec_le32(h + 24); H->version = ec_le32(h + 4); H->width = 0u;
     if (pack_fixed_bytes_v(H->version, H->nblk) > in_bytes) return PACK_FORMAT;      // (judged with the version's entry size, before the directory is read)
     return PACK_OK;
 }
 
 // The directory behind a header that passed (dir: H.nblk entries, which in_bytes holds).  exact: the frame must be all of in_bytes
-// (an unpack), else it may end earlier (stepping through concatenated frames).  PACK_OK and *frame_bytes, or PACK_FORMAT.
-EC_HD int pack_directory_check(const uint8_t *dir, const PackHeader &H, uint64_t in_bytes, bool exact, uint64_t *frame_bytes)
+// (an unpack), else it may end earlier (stepping through concatenated frames).  PACK_OK, *frame_bytes and H.width, or PACK_FORMAT.
+EC_HD int pack_directory_check(const uint8_t *dir, PackHeader &H, uint64_t in_bytes, bool exact, uint64_t *frame_bytes)
 {
     const uint64_t entry = pack_entry_bytes(H.version);
     if (crc32_bytes(dir, entry * H.nblk) != H.dir_crc) return PACK_FORMAT;
+    const uint32_t width = ec_le32(dir + 12);       // (every entry must say what the first one says)
     uint64_t total = pack_fixed_bytes_v(H.version, H.nblk);
     for (uint64_t b = 0; b < H.nblk; b++) {
         const uint8_t *e = dir + entry * b;
         const uint64_t sb = pack_le64(e);
         uint64_t len = pack_block_at(H.n, H.B, b);
-        if (ec_le32(e + 12) != 0u || (sb & 15u)) return PACK_FORMAT;
-        if (H.version == PACK_VERSION_2) {
+        if (ec_le32(e + 12) != width || !pack_width_word_ok(H.version, width) || (sb & 15u)) return PACK_FORMAT;
+        if (H.version != PACK_VERSION) {
             // the stream is the coder's over the zero-run coded bytes: 1 <= coded_bytes <= the block's length
             const uint64_t coded = pack_le64(e + 16);
             if (pack_le64(e + 24) != 0u || coded == 0u || coded > len) return PACK_FORMAT;
@@ -184,5 +198,6 @@ EC_HD int pack_directory_check(const uint8_t *dir, const PackHeader &H, uint64_t
     }
     if (exact ? total != in_bytes : total > in_bytes) return PACK_FORMAT;
     *frame_bytes = total;
+    H.width = width;
     return PACK_OK;
 }

@@ -1,0 +1,247 @@
+// planes.hip -- the byte-plane split of typed arrays and its inverse, the stage in front of the transform (include/bwts_planes.h; the
+// definition is stated there and in DESIGN section 16, tests/planes_model.py is its executable form; the arithmetic shared with the
+// host is in planes_plan.h).
+//
+// A streaming transpose: one read and one write of n bytes, no working memory.  A string is cut into tiles of E = 4096 elements of w
+// bytes, no tile across a segment start; a workgroup of 256 threads works on one tile, every thread on 16 consecutive elements.
+//   split: the thread takes its 16 w interleaved bytes as w 16-byte loads, regroups them with byte permutes into one 16-byte unit per
+//          plane, and puts unit and plane into LDS; the tile's w plane pieces go out from there.
+//   join:  the thread takes one 16-byte unit per plane, regroups them into its 16 w interleaved bytes and puts them into LDS; the
+//          tile's interleaved bytes go out from there.
+// Neither side of either direction is aligned but by luck (a plane starts at base + k q, a segment anywhere), and no access wider than
+// a byte is ever made at an address that is not a multiple of its width:
+//   reading  planes_load16 reads the two aligned 16-byte pieces around an address and shifts the bytes into place in registers; a
+//            piece that does not lie inside the call's input is put together from the single bytes that do (the first and the last
+//            piece of the whole input at most), so nothing outside the input is read.
+//   writing  planes_stream_store sends a piece of len bytes from LDS: single bytes up to the destination's first 16-byte boundary (at
+//            most 15), aligned 16-byte stores behind them, each shifted into place from two aligned LDS units, and single bytes for
+//            what is left (at most 15).  At most 30 bytes of a piece of 4096 or more leave as single bytes.
+// The tail of a string (its last L mod w bytes) is copied by the workgroup of its last tile.
+#include "internal.h"
+#include "device_utils.h"
+#include "planes_plan.h"
+#include "../../include/bwts_planes.h"
+
+// The LDS unit (16 bytes) of unit u of a stream: one unit of padding behind every eight, so that the eight lanes whose 16-byte stores
+// the LDS takes together (units w apart in a join) fall on different banks.
+#define PLANES_SLOT(u) ((u) + ((u) >> 3))
+#define PLANES_PLANE_SLOTS (PLANES_SLOT(PLANES_E / 16u) + 2u)           // a plane's piece of a split, and the unit behind it that a shift reads
+
+// The segments of a call as the kernels see them.  off == null: one input of n bytes.
+struct PlanesSegs {
+    const u64 *off;         // [count + 1] where every segment starts
+    const u64 *first;       // [count + 1] the segment's first tile, counted over the call
+    u64 count, n;
+};
+
+struct PlanesTile {
+    u64 seg, len, q, e0;    // the segment's start and length, its elements, the tile's first element
+    u32 elems;              // the tile's elements (0: the tile is there for the tail alone)
+    bool last;
+};
+
+template <int W>
+__device__ __forceinline__ PlanesTile planes_tile(const PlanesSegs &S, u64 t)
+{
+    PlanesTile R;
+    u64 first = 0;
+    R.seg = 0; R.len = S.n;
+    if (S.off) {
+        // the segment of tile t: the last one whose first tile is not behind t (every segment has a tile, so the firsts differ)
+        u64 lo = 0, hi = S.count;
+        while (hi - lo > 1) {
+            const u64 mid = lo + (hi - lo) / 2;
+            if (S.first[mid] <= t) lo = mid;
+            else hi = mid;
+        }
+        first = S.first[lo];
+        R.seg = S.off[lo]; R.len = S.off[lo + 1] - R.seg;
+    }
+    const u64 j = t - first;
+    R.q = planes_q(R.len, W);
+    R.e0 = j << PLANES_LOG_E;
+    R.elems = planes_tile_elems(R.len, W, j);
+    R.last = j + 1 == planes_tiles(R.len, W);
+    return R;
+}
+
+// the 16 bytes at byte sh (0 .. 15) of the 32 bytes a, b
+__device__ __forceinline__ uint4 planes_funnel(uint4 a, uint4 b, u32 sh)
+{
+    const u32 D[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    const u32 bytes = sh & 3u, words = sh >> 2;
+    u32 e[7], o[4];
+#pragma unroll
+    for (int j = 0; j < 7; j++) e[j] = __builtin_amdgcn_alignbyte(D[j + 1], D[j], bytes);
+#pragma unroll
+    for (int j = 0; j < 4; j++) o[j] = words == 0 ? e[j] : (words == 1 ? e[j + 1] : (words == 2 ? e[j + 2] : e[j + 3]));
+    return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+// the aligned 16-byte piece at a, of which only bytes inside [lo, hi) are read (the others are 0)
+__device__ __forceinline__ uint4 planes_piece(const u8 *a, const u8 *lo, const u8 *hi)
+{
+    const uintptr_t x = (uintptr_t)a, l = (uintptr_t)lo, h = (uintptr_t)hi;
+    if (x >= l && x + 16 <= h) return *(const uint4 *)a;
+    u32 w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 16; i++)
+        if (x + i >= l && x + i < h) w[i >> 2] |= (u32)a[i] << (8 * (i & 3));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// the 16 bytes at p, at any alignment; what lies outside [lo, hi) reads as 0
+__device__ __forceinline__ uint4 planes_load16(const u8 *p, const u8 *lo, const u8 *hi)
+{
+    const u32 sh = (u32)((uintptr_t)p & 15);
+    const u8 *a = p - sh;
+    const uint4 x = planes_piece(a, lo, hi);
+    if (sh == 0) return x;
+    return planes_funnel(x, planes_piece(a + 16, lo, hi), sh);
+}
+
+// one word from byte ba of a, byte bb of b, byte bc of c and byte bd of d (constants after unrolling): three byte permutes
+__device__ __forceinline__ u32 planes_pick4(u32 a, int ba, u32 b, int bb, u32 c, int bc, u32 d, int bd)
+{
+    const u32 lo = __builtin_amdgcn_perm(b, a, 0x0c0c0000u | (u32)ba | ((u32)(4 + bb) << 8));
+    const u32 hi = __builtin_amdgcn_perm(d, c, 0x0c0c0000u | (u32)bc | ((u32)(4 + bd) << 8));
+    return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+}
+
+// byte i of a stream in LDS
+__device__ __forceinline__ u32 planes_lds_byte(u32 i) { return 16u * PLANES_SLOT(i >> 4) + (i & 15u); }
+
+// len bytes of a stream in LDS (unit u at PLANES_SLOT(u), one more unit readable behind the last) to dst, the whole workgroup
+__device__ __forceinline__ void planes_stream_store(const uint4 *lds, u8 *dst, u32 len)
+{
+    const u32 tid = threadIdx.x;
+    const u8 *bytes = (const u8 *)lds;
+    u32 head = (16u - (u32)((uintptr_t)dst & 15)) & 15u;
+    if (head > len) head = len;
+    const u32 vecs = (len - head) / 16u, done = head + 16u * vecs;
+    if (tid < head) dst[tid] = bytes[planes_lds_byte(tid)];
+    // store v holds the stream's bytes [head + 16 v, head + 16 v + 16): from the units v and v + 1
+    for (u32 v = tid; v < vecs; v += 256) {
+        uint4 x = lds[PLANES_SLOT(v)];
+        if (head) x = planes_funnel(x, lds[PLANES_SLOT(v + 1u)], head);
+        ((uint4 *)(dst + head))[v] = x;
+    }
+    if (tid < len - done) dst[done + tid] = bytes[planes_lds_byte(done + tid)];
+}
+
+// the tail of the tile's string: fewer than w bytes, copied
+template <int W>
+__device__ __forceinline__ void planes_copy_tail(const u8 *in, const PlanesTile &R, u8 *out)
+{
+    const u64 at = planes_tail_at(R.len, W);
+    if (threadIdx.x < R.len - at) out[R.seg + at + threadIdx.x] = in[R.seg + at + threadIdx.x];
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void planes_split_kernel(const u8 *__restrict__ in, PlanesSegs S, u8 *__restrict__ out)
+{
+    __shared__ uint4 lds[W * PLANES_PLANE_SLOTS];
+    const u32 tid = threadIdx.x, at = 16u * tid;
+    const PlanesTile R = planes_tile<W>(S, blockIdx.x);
+    if (R.elems) {
+        if (at < R.elems) {
+            // (a tile's last thread may hold fewer than 16 elements: what it reads behind them lies in the input or reads as 0, and no
+            // byte of it leaves the LDS)
+            const u8 *p = in + R.seg + (R.e0 + at) * W;
+            u32 D[4 * W];
+#pragma unroll
+            for (int v = 0; v < W; v++) {
+                const uint4 x = planes_load16(p + 16 * v, in, in + S.n);
+                D[4 * v] = x.x; D[4 * v + 1] = x.y; D[4 * v + 2] = x.z; D[4 * v + 3] = x.w;
+            }
+            // word j of plane k: byte k of the elements 4 j .. 4 j + 3
+#pragma unroll
+            for (int k = 0; k < W; k++) {
+                u32 o[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const int b0 = (4 * j) * W + k, b1 = b0 + W, b2 = b1 + W, b3 = b2 + W;
+                    o[j] = planes_pick4(D[b0 >> 2], b0 & 3, D[b1 >> 2], b1 & 3, D[b2 >> 2], b2 & 3, D[b3 >> 2], b3 & 3);
+                }
+                lds[k * PLANES_PLANE_SLOTS + PLANES_SLOT(tid)] = make_uint4(o[0], o[1], o[2], o[3]);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < W; k++) planes_stream_store(lds + k * PLANES_PLANE_SLOTS, out + R.seg + (u64)k * R.q + R.e0, R.elems);
+    }
+    if (R.last) planes_copy_tail<W>(in, R, out);
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void planes_join_kernel(const u8 *__restrict__ in, PlanesSegs S, u8 *__restrict__ out)
+{
+    __shared__ uint4 lds[PLANES_SLOT(W * (PLANES_E / 16u)) + 2u];
+    const u32 tid = threadIdx.x, at = 16u * tid;
+    const PlanesTile R = planes_tile<W>(S, blockIdx.x);
+    if (R.elems) {
+        if (at < R.elems) {
+            const u8 *p = in + R.seg + R.e0 + at;
+            u32 P[4 * W];
+#pragma unroll
+            for (int k = 0; k < W; k++) {
+                const uint4 x = planes_load16(p + (u64)k * R.q, in, in + S.n);
+                P[4 * k] = x.x; P[4 * k + 1] = x.y; P[4 * k + 2] = x.z; P[4 * k + 3] = x.w;
+            }
+            // interleaved byte b of the thread: byte b / w of plane b mod w
+#pragma unroll
+            for (int v = 0; v < W; v++) {
+                u32 o[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const int b0 = 16 * v + 4 * j, b1 = b0 + 1, b2 = b0 + 2, b3 = b0 + 3;
+                    o[j] = planes_pick4(P[4 * (b0 % W) + ((b0 / W) >> 2)], (b0 / W) & 3, P[4 * (b1 % W) + ((b1 / W) >> 2)], (b1 / W) & 3,
+                                        P[4 * (b2 % W) + ((b2 / W) >> 2)], (b2 / W) & 3, P[4 * (b3 % W) + ((b3 / W) >> 2)], (b3 / W) & 3);
+                }
+                lds[PLANES_SLOT((u32)W * tid + (u32)v)] = make_uint4(o[0], o[1], o[2], o[3]);
+            }
+        }
+        __syncthreads();
+        planes_stream_store(lds, out + R.seg + R.e0 * W, R.elems * W);
+    }
+    if (R.last) planes_copy_tail<W>(in, R, out);
+}
+
+// ------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------
+void bwts_planes_plan(u64 n, u32 w, u64 out[4])
+{
+    out[0] = planes_tile_bytes(w); out[1] = planes_tiles(n, w); out[2] = planes_q(n, w); out[3] = n - planes_tail_at(n, w);
+}
+
+template <int W>
+static void planes_launch(hipStream_t stream, bool join, unsigned grid, const u8 *d_in, const PlanesSegs &S, u8 *d_out)
+{
+    if (join) planes_join_kernel<W><<<dim3(grid), dim3(256), 0, stream>>>(d_in, S, d_out);
+    else planes_split_kernel<W><<<dim3(grid), dim3(256), 0, stream>>>(d_in, S, d_out);
+}
+
+// one input of n bytes, or every segment of the context's table on its own
+int planes_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u32 w, u8 *d_out, bool join, SegMode segs)
+{
+    if (!planes_width_ok(w)) return BWTS_E_ARG;
+    const StageCut cut = stage_cut_call(ctx, segs, n, planes_tile_bytes(w));
+    const u64 tiles = cut.units[0];
+    if (tiles >= (1ull << 31)) return BWTS_E_RANGE;
+    PlanesSegs S = {nullptr, nullptr, 0, n};
+    if (segs.table()) {
+        // behind the context's table: every segment's first tile and the total
+        u64 *d_first = nullptr;
+        BWTS_TRY(seg_upload_extra(ctx, cut.first[0].data(), cut.count + 1, &d_first));
+        S.off = d_seg_off(ctx); S.first = d_first; S.count = cut.count;
+    }
+    {
+        SpanGuard sp(ctx, BWTS_K_OTHER, n, 2 * n);
+        if (w == 2) planes_launch<2>(ctx->stream, join, (unsigned)tiles, d_in, S, d_out);
+        else if (w == 4) planes_launch<4>(ctx->stream, join, (unsigned)tiles, d_in, S, d_out);
+        else planes_launch<8>(ctx->stream, join, (unsigned)tiles, d_in, S, d_out);
+    }
+    HIPC(hipGetLastError());
+    return BWTS_OK;
+}

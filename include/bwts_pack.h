@@ -31,8 +31,25 @@
  *      together exactly what bwts_ec_encode_segments_device writes for the coded_bytes lengths.
  * Bound: 32 + 32 nblk + the sum of bwts_ec_bound over the blocks' lengths (the zero-run stage never expands).
  *
+ * The frame, version 3: version 2 with the byte-plane split (bwts_planes.h) in front of the transform, at a width w in {2, 4, 8}
+ * that the caller names.  Asked for with the _planes calls (the _v calls keep to versions 1 and 2); unpack takes all three.
+ *   1. Header: as above, with version = 3.
+ *   2. Directory, nblk x 32 bytes: u64 stream_bytes, u32 CRC-32 of the block's original bytes (before the split), u32 w (the reserved
+ *      word of versions 1 and 2; the same in every entry), u64 coded_bytes, u64 zero.
+ *   3. Streams: the version-1 stream of bwts_ec.h of ZRL(MTF(BWTS(SPLIT_w(block)))) for every block, in order; every block is split
+ *      on its own (a block whose length is no multiple of w keeps its tail, bwts_planes.h); otherwise as in version 2.
+ * Bound: version 2's (the split never changes a length).
+ * Unpack keeps version 2's order; the word at entry offset 12 is judged where versions 1 and 2 demand zero: a width that is not 2, 4
+ * or 8, or that differs from the first entry's, is BWTS_E_FORMAT (so is a version-2 body under a version word of 3: its width is 0).
+ * After the inverse transform every block is joined at w, and the CRC-32 of the result is held against the directory: a frame whose
+ * width words name another of the three widths decodes in bounds and fails with BWTS_E_CHECKSUM.
+ * A limit of the transform that version 3 meets: the planes of a long smooth field are deeply repetitive, and from 2^29 bytes of such
+ * a field on (2^28 bytes pack) bwts_forward_device refuses the split bytes with BWTS_E_INTERNAL, in one block and in blocks alike,
+ * before anything is written; the _planes calls pass that code on.  Pack such an input in frames of at most 2^28 bytes (DESIGN
+ * section 16).  Versions 1 and 2 of the same bytes are not affected.
+ *
  * A frame is not trusted.  Unpack refuses with BWTS_E_FORMAT, in this order: in_bytes < 48 or not a multiple of 16; wrong magic, or
- * a version that is neither 1 nor 2; a wrong header CRC; n = 0 (n > 2^32 is BWTS_E_RANGE); B = 0, B > n, or B < 4096 with B != n; a directory longer than the
+ * a version that is not 1, 2 or 3; a wrong header CRC; n = 0 (n > 2^32 is BWTS_E_RANGE); B = 0, B > n, or B < 4096 with B != n; a directory longer than the
  * frame; a wrong directory CRC; an entry with a nonzero reserved word, or a stream_bytes that is not a multiple of 16 or outside
  * what the coder can make of the block's length; 32 + 16 nblk + the sum of stream_bytes != in_bytes.  Then a header n > out_cap is
  * BWTS_E_SPACE.  After the checks: decode (the coder's own BWTS_E_FORMAT passes through, and a stream whose header names another
@@ -51,15 +68,16 @@
  * Pack never fails with BWTS_E_SPACE for out_cap >= bwts_pack_bound; with less it returns BWTS_E_SPACE as soon as the frame is known
  * not to fit, and has then written nothing at all (header and directory are written last).  A device unpack that fails may have
  * written part of d_out; the host forms leave out as it was after any failure.
- * Cost: pack is one checksum pass and the three stages (version 2: four); between them the bytes stay in two n-byte blocks that the
- * context keeps (unpack: one; it decodes into d_out, version 2 into the block and from there into d_out), counted in bwts_timings::device_bytes and given up by bwts_ctx_release_memory.  The checksum
+ * Cost: pack is one checksum pass and the three stages (version 2: four, version 3: five); between them the bytes stay in two n-byte
+ * blocks that the context keeps (unpack: one; it decodes into d_out, version 2 into the block and from there into d_out, version 3
+ * into d_out, from there into the block, and so on: the last stage always lands in d_out), counted in bwts_timings::device_bytes and given up by bwts_ctx_release_memory.  The checksum
  * takes four bytes per 64 KiB tile from the context's arena.  bwts_last_timings: n (the unpacked bytes) and total_ms are filled,
  * the kernels are accounted under BWTS_K_OTHER.
  */
 #ifndef BWTS_PACK_H
 #define BWTS_PACK_H
 
-#include "bwts_zrl.h"
+#include "bwts_planes.h"
 
 #define BWTS_E_CHECKSUM -10   /* a block decoded in bounds but its bytes are not the ones that were packed */
 
@@ -89,6 +107,14 @@ int bwts_pack_device_v(bwts_ctx *ctx, uint32_t version, const void *d_in, uint64
                        uint64_t *out_bytes);
 int bwts_pack_v(bwts_ctx *ctx, uint32_t version, const uint8_t *in, uint64_t n, uint64_t block_bytes, uint8_t *out, uint64_t out_cap,
                 uint64_t *out_bytes);
+
+/* frames of version 3: the byte-plane split at `width` (2, 4 or 8; anything else: BWTS_E_ARG, the bound: 0) in front of the
+ * transform, zero-run coding in front of the coder; otherwise the calls above */
+uint64_t bwts_pack_planes_bound(uint32_t width, uint64_t n, uint64_t block_bytes);
+int bwts_pack_planes_device(bwts_ctx *ctx, uint32_t width, const void *d_in, uint64_t n, uint64_t block_bytes, void *d_out, uint64_t out_cap,
+                            uint64_t *out_bytes);
+int bwts_pack_planes(bwts_ctx *ctx, uint32_t width, const uint8_t *in, uint64_t n, uint64_t block_bytes, uint8_t *out, uint64_t out_cap,
+                     uint64_t *out_bytes);
 
 #ifdef __cplusplus
 }

@@ -125,6 +125,10 @@ int bwts_debug_crc_plan(uint64_t n, uint64_t out[4]);
 /* Pure arithmetic, no context and no device: how the zero-run stage (bwts_zrl.h) cuts one input of 1 <= n <= 2^36 bytes.  out = {T, the
  * tile size in bytes the kernels use; tiles = ceil(n / T)}.  Returns 0, -1 on a bad argument. */
 int bwts_debug_zrl_plan(uint64_t n, uint64_t out[2]);
+/* Pure arithmetic, no context and no device: how the byte-plane split (bwts_planes.h) cuts one input of 1 <= n <= 2^36 bytes at a width
+ * of 2, 4 or 8.  out = {T, the tile size in bytes (4096 elements); tiles = ceil(n / T); q, the whole elements; the bytes of the tail}.
+ * Returns 0, -1 on a bad argument. */
+int bwts_debug_planes_plan(uint64_t n, uint32_t width, uint64_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -72,7 +72,7 @@ E_CHECKSUM = -10
 TEST_EXPORTS = [
     "bwts_generate_device", "bwts_device_alloc", "bwts_device_free", "bwts_copy_to_device", "bwts_copy_to_host",
     "bwts_device_equal", "bwts_debug_sort_pairs", "bwts_debug_suffix_array", "bwts_debug_lyndon",
-    "bwts_debug_chunk_plan", "bwts_debug_inverse_arena", "bwts_debug_forward_arena", "bwts_debug_wide_forward_arena", "bwts_debug_inverse_report",
+    "bwts_debug_chunk_plan", "bwts_debug_chunk_plan_target", "bwts_debug_inverse_arena", "bwts_debug_forward_arena", "bwts_debug_wide_forward_arena", "bwts_debug_inverse_report",
     "bwts_debug_forward_report", "bwts_debug_segments_plan", "bwts_debug_segments_report",
     "bwts_debug_mtf_plan", "bwts_debug_last_spans", "bwts_debug_ec_plan", "bwts_debug_crc_plan",
     "bwts_debug_zrl_plan", "bwts_debug_planes_plan",
@@ -99,6 +99,11 @@ FWD_LEAN_WORD = 37              # header word: what became of round 0's lean las
 FWD_LEAN = {0: "not_tried", 1: "held", 2: "gave_up_seam", 3: "gave_up_count", 4: "gave_up_direct"}
 FWD_CHUNK_FIELDS = ["S", "maxchunks", "a_small", "big0", "m_exit", "m_stay", "groups", "wide_possible", "fsl", "compactions",
                     "compactions_skipped", "enqueued_behind_last"]
+# Later additions live beside the dicts above, whose keys are compared whole by the exact tests: header word 38, the nominal chunk size
+# after the last compaction (0 without one), is "chunk_S_recut"; word 11 of a chunk round, the nominal size as the round ran, goes to
+# the list "chunk_round_S" (one entry per recorded round)
+FWD_CHUNK_S_RECUT_WORD = 38
+FWD_ROUND_CHUNK_S_WORD = 11
 FWD_ROUND_FIELDS = {"sparse": ["form", "h", "in", "out", "splits", "probe", "m_big", "whole", "skip_next"],
                     "chunks": ["form", "h", "in", "out", "splits", "chunks_in", "chunks_out", "big_in", "big_stays", "big_leaves", "nchunks"],
                     "tiles": ["form", "h", "in", "out", "splits", "m_big"],
@@ -237,6 +242,7 @@ def lib():
         L.bwts_debug_suffix_array.argtypes = [vp, vp, u64, vp]
         L.bwts_debug_lyndon.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
         L.bwts_debug_chunk_plan.argtypes = [u64, u64, ctypes.POINTER(u64)]
+        L.bwts_debug_chunk_plan_target.argtypes = [u64, u64, ctypes.c_uint32, ctypes.POINTER(u64)]
         L.bwts_debug_inverse_arena.argtypes = [u64, i32, i32, ctypes.POINTER(u64)]
         L.bwts_debug_forward_arena.argtypes = [u64, ctypes.POINTER(u64)]
         L.bwts_debug_wide_forward_arena.argtypes = [u64, i32, i32, u64, ctypes.POINTER(u64)]
@@ -708,7 +714,7 @@ class Context:
     def debug_forward_report(self):
         """One dict per doubling sort of the most recent forward call on this context (also debug_suffix_array / debug_lyndon), in the
         order they ran: the header (FWD_HEADER_FIELDS; form, keys, no_chunks and end by name, flags as bool; "direct" / "direct_word": header
-        word 36 by name and as the number; "lean" / "lean_word": likewise header word 37), "chunks" (FWD_CHUNK_FIELDS)
+        word 36 by name and as the number; "lean" / "lean_word": likewise header word 37), "chunks" (FWD_CHUNK_FIELDS), "chunk_S_recut" and "chunk_round_S"
         when the chunk form ran, and "round": one dict per recorded round after round 0 (FWD_ROUND_FIELDS of its form)."""
         buf = (ctypes.c_uint64 * (2 * FWD_SORT_WORDS))()
         made = ctypes.c_uint64(0)
@@ -726,6 +732,7 @@ class Context:
                 d[f] = bool(d[f])
             if d["form"] == "chunks":
                 d["chunks"] = {f: w[24 + i] for i, f in enumerate(FWD_CHUNK_FIELDS)}
+                d["chunk_S_recut"], d["chunk_round_S"] = w[FWD_CHUNK_S_RECUT_WORD], []
                 for f in ("wide_possible", "fsl", "enqueued_behind_last"):
                     d["chunks"][f] = bool(d["chunks"][f])
             d["round"] = []
@@ -737,6 +744,8 @@ class Context:
                 if form == "sparse":
                     rd["probe"], rd["whole"], rd["skip_next"] = FWD_PROBES[rd["probe"]], bool(rd["whole"]), bool(rd["skip_next"])
                 d["round"].append(rd)
+                if d["form"] == "chunks":
+                    d["chunk_round_S"].append(rw[FWD_ROUND_CHUNK_S_WORD])
             out.append(d)
         return out
 

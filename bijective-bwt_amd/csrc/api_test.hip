@@ -90,12 +90,18 @@ static int upload_text(bwts_ctx *ctx, const uint8_t *in, uint64_t n, u8 **d_T)
     return BWTS_OK;
 }
 
-// the chunk tables' arithmetic for a tied list of a0 elements of which a_chunks are left at a compaction: no context, no device
+// the chunk tables' arithmetic for a tied list of a0 elements of which a_chunks are left at a compaction, with cuts that aim at
+// `target` chunks: no context, no device.  The re-cut always fits (chunk_table_capacity): the return value says so
+extern "C" int bwts_debug_chunk_plan_target(uint64_t a0, uint64_t a_chunks, uint32_t target, uint64_t out[4])
+{
+    if (!out || target < 16 || target > CH_CHUNK_TARGET) return -1;
+    const ChunkRecut re = chunk_recut_plan(a_chunks, target);
+    out[0] = chunk_nominal_size(a0, target); out[1] = chunk_table_capacity(a0); out[2] = re.S; out[3] = re.nc;
+    return re.nc <= out[1] ? 1 : 0;
+}
 extern "C" int bwts_debug_chunk_plan(uint64_t a0, uint64_t a_chunks, uint64_t out[4])
 {
-    const ChunkRecut re = chunk_recut_plan(a0, a_chunks);
-    out[0] = chunk_nominal_size(a0); out[1] = chunk_table_capacity(a0); out[2] = re.S; out[3] = re.nc;
-    return re.allowed ? 1 : 0;
+    return bwts_debug_chunk_plan_target(a0, a_chunks, CH_CHUNK_TARGET, out);
 }
 
 // the move-to-front stage's cut of one input of n bytes: tile size, tiles per group, tiles, groups.  No context, no device

@@ -41,6 +41,7 @@
 // (factors whose data a workgroup keeps in LDS: natural data has a dozen or two)
 #define CH_GROUP_MAX CH_TILE             // largest group a chunk may hold (a tile of its own in a WIDE chunk)
 #define CH_MIN_LIST 65536ull            // shorter lists keep the tile form (dense_rounds)
+#define CH_CUT_SLACK 128                // table entries beyond a0 / CH_TILE: one ragged chunk per cut (chunk_table_capacity)
 #define CH_SLOTS   4                    // result slots of rounds in flight
 #define CH_SLOT_WORDS 16
 #define SM_CHSLOT  (SM_DGCNT + 16)      // CH_SLOTS x CH_SLOT_WORDS words inside the dense rounds' counter block
@@ -518,8 +519,8 @@ __global__ __launch_bounds__(256) void chunk_apply_records_kernel(u64 *__restric
     }
 }
 
-// elements still tied over all chunks; with off, also the exclusive sums of ccount for chunk_compact_kernel (one workgroup: at most a
-// few 10^4 chunks)
+// elements still tied over all chunks; with off, also the exclusive sums of ccount for chunk_compact_kernel.  One workgroup loops over
+// the tables: up to a0 / CH_TILE + CH_CUT_SLACK chunks, 1024 per step (nothing here is indexed by chunk but the global tables)
 __global__ __launch_bounds__(1024) void chunk_total_kernel(const u32 *__restrict__ ccount, u32 nchunks, unsigned long long *__restrict__ result,
                                                            u32 *__restrict__ off)
 {
@@ -958,26 +959,34 @@ static void chunk_diag_sizes(bwts_ctx *ctx, const u32 *head, const u32 *cstart, 
 }
 
 // ---- the chunk tables as plain arithmetic (declared in internal.h: the bwts_debug_chunk_plan test hook asks them too) ----
-u32 chunk_nominal_size(u64 a)
+u32 chunk_nominal_size(u64 a, u32 target)
 {
-    // about 16 K chunks, between one and eight tiles each
-    u64 s = (a / 16384 + 1023) / 1024 * 1024;
+    // about `target` chunks (CH_CHUNK_TARGET = 16 K unless the test switch BWTS_CHUNK_TARGET says otherwise), between one and eight tiles each
+    u64 s = (a / target + 1023) / 1024 * 1024;
     if (s < CH_TILE) s = CH_TILE;
     if (s > 8 * CH_TILE) s = 8 * CH_TILE;
     return (u32)s;
 }
-// Entries of cstart/ccount/mvcount/cwide/coff, fixed when their block is reserved: the first cut's chunks, and one ragged chunk per
-// append (rounds are capped at 80).  After a compaction the nominal size is up to 8x smaller, so a list that the big list dominates
-// may append more chunks than this budgets: that ends in "chunk table full" (BWTS_E_INTERNAL), a clean failure and never an overrun.
-u64 chunk_table_capacity(u64 a0) { return a0 / chunk_nominal_size(a0) + 1024; }
-// A compaction re-cuts the a_chunks elements left by their own nominal size, which is allowed only when the new chunks fit the tables
-// (S is rounded up to whole K, so a0 / S(a0) can fall to about 14 K while the re-cut makes up to 16 K chunks).
-ChunkRecut chunk_recut_plan(u64 a0, u64 a_chunks)
+// Entries of cstart/ccount/mvcount/cwide/coff, fixed when their block is reserved.  They hold every run the driver can make:
+//   * the store has tail <= a0 slots in use (the driver fails on c.tail + m_exit > a0), and every cut_chunks(lo, hi) adds
+//     ceil((hi - lo) / S) chunks over slots of its own;
+//   * S changes only at a compaction, which starts the tables over at 0 with tail = a_chunks; between two compactions nchunks never
+//     falls, and S >= CH_TILE always.  So between compactions nchunks <= tail / S + cuts <= a0 / CH_TILE + cuts;
+//   * the cuts between two compactions are at most one first cut or re-cut, one first split of the big list and one append per round,
+//     and the rounds are capped (more than 80 fails): fewer than CH_CUT_SLACK.
+// A capacity sized by the FIRST cut's S (a0 / S(a0) + 1024, what this was) does not: after a re-cut at a nominal size up to 8x
+// smaller, a list that the big list still dominates appends more chunks than that held.  "chunk table full" on the byte planes of a
+// smooth float32 field from 2^29 bytes on was this: a0 = 254 419 860 cut at S = 16 384, 16 552 entries; 5 887 411 elements left of
+// 85 722 238 slots re-cut into 2875 chunks of 2048; then 11.2 M and 18.4 M elements left the big list in two rounds, 17 328 chunks.
+// 17 bytes per entry: ~35 MB at a0 = 2^32, beside a store of more than 100 GB.
+u64 chunk_table_capacity(u64 a0) { return a0 / CH_TILE + CH_CUT_SLACK; }
+// A compaction re-cuts the a_chunks <= a0 elements left by their own nominal size S' >= CH_TILE: ceil(a_chunks / S') <= a0 / CH_TILE + 1
+// chunks, which always fit.
+ChunkRecut chunk_recut_plan(u64 a_chunks, u32 target)
 {
     ChunkRecut r;
-    r.S = chunk_nominal_size(a_chunks);
+    r.S = chunk_nominal_size(a_chunks, target);
     r.nc = (a_chunks + r.S - 1) / r.S;
-    r.allowed = r.nc <= chunk_table_capacity(a0);
     return r;
 }
 
@@ -1002,6 +1011,7 @@ struct ChunkRun {
     u32 *cstart, *ccount, *mvcount, *coff;          // (coff: the chunks' offsets in the dense list of a compaction)
     u8 *cwide;
     u32 S, nchunks = 0;             // nominal chunk size; chunks in the tables
+    u32 target = CH_CHUNK_TARGET;   // chunks a cut aims at (test switch BWTS_CHUNK_TARGET)
     u64 maxchunks, tail = 0;        // chunk_table_capacity(); slots of the store in use: chunks leaving the big list are appended there
     bool wide_possible = false;     // some chunk may be flagged WIDE: the second instantiation is launched as well
     BigList b;
@@ -1178,16 +1188,10 @@ static int big_list_sort_split(bwts_ctx *ctx, ChunkRun &c, SortSpace &sp, unsign
 }
 
 // The chunks are two thirds empty: a dense list in the store's other pair of arrays, cut into new chunks (chunk_compact_kernel).
-// Skipped, as whenever the chunks are fuller than that, when the new chunks would not fit the tables.
-static int compact_chunks(bwts_ctx *ctx, ChunkRun &c, u64 a0, u64 a_chunks)
+// The new chunks always fit the tables (chunk_table_capacity).
+static int compact_chunks(bwts_ctx *ctx, ChunkRun &c, u64 a_chunks)
 {
-    const ChunkRecut re = chunk_recut_plan(a0, a_chunks);
-    if (!re.allowed) {
-        if (c.trace) fprintf(stderr, "[chunks] list not compacted: %llu elements would make %llu chunks (nominal chunk %u), the tables hold %llu\n",
-                             (unsigned long long)a_chunks, (unsigned long long)re.nc, re.S, (unsigned long long)c.maxchunks);
-        fwd_report_of(ctx)[FC_COMPACTIONS_SKIPPED]++;
-        return BWTS_OK;
-    }
+    const ChunkRecut re = chunk_recut_plan(a_chunks, c.target);
     fwd_report_of(ctx)[FC_COMPACTIONS]++;
     SpanGuard g(ctx, BWTS_K_ROUND, 0, 0);
     chunk_total_kernel<<<dim3(1), dim3(1024), 0, ctx->stream>>>(c.ccount, c.nchunks, (unsigned long long *)(c.slots + 3 * CH_SLOT_WORDS), c.coff);
@@ -1196,6 +1200,7 @@ static int compact_chunks(bwts_ctx *ctx, ChunkRun &c, u64 a0, u64 a_chunks)
     if (c.trace) fprintf(stderr, "[chunks] list compacted: %llu elements of %llu slots, %u chunks -> %u (nominal chunk %u)\n", (unsigned long long)a_chunks,
                          (unsigned long long)c.tail, c.nchunks, (u32)re.nc, re.S);
     c.S = re.S;
+    fwd_report_of(ctx)[FC_S_RECUT] = re.S;
     return cut_chunks(ctx, c, 0, a_chunks, 0, c.wide_possible);
 }
 
@@ -1235,7 +1240,8 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
                CYCLIC ? bitlen_u64(n - 1) : bitlen_u64(n), PrevSym{sp.carry_src, d_T, n, d_fstart, k}, CYCLIC ? sp.carry_out : nullptr,
                ctx->d_small + SM_CHSLOT};
     BigList &b = c.b;
-    c.S = chunk_nominal_size(a0);
+    if (const char *e = bwts_knob(ctx, "BWTS_CHUNK_TARGET")) { const int v = atoi(e); if (v >= 16 && v <= CH_CHUNK_TARGET) c.target = (u32)v; }      // (test switch)
+    c.S = chunk_nominal_size(a0, c.target);
     c.maxchunks = chunk_table_capacity(a0);
     char *base = nullptr, *ob = nullptr;
     BlockLayout L;
@@ -1355,7 +1361,7 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
             if (u64 *rr = fwd_report_round(ctx, c.rounds)) {
                 rr[FRR_FORM] = FR_FORM_CHUNKS; rr[FRR_H] = hs[q]; rr[FRR_IN] = a_chunks + b.m; rr[FRR_OUT] = in_chunks + m_exit + (b.m ? m_stay : 0);
                 rr[FRR_SPLITS] = r[CHS_SPLIT]; rr[FRR_CHUNKS_IN] = a_chunks; rr[FRR_CHUNKS_OUT] = in_chunks; rr[FRR_BIG_IN] = b.m;
-                rr[FRR_BIG_STAYS] = m_stay; rr[FRR_BIG_LEAVES] = m_exit; rr[FRR_NCHUNKS] = c.nchunks;
+                rr[FRR_BIG_STAYS] = m_stay; rr[FRR_BIG_LEAVES] = m_exit; rr[FRR_NCHUNKS] = c.nchunks; rr[FRR_CHUNK_S] = c.S;
             }
             if (m_exit) CH_TRY(cut_chunks(ctx, c, c.tail, c.tail + m_exit, c.nchunks, true));
             if (b.m) { b.cur ^= 1; b.m = m_stay; }
@@ -1373,7 +1379,7 @@ static int chunk_rounds(bwts_ctx *ctx, const u8 *d_T, u64 n, const Alphabet &al,
             if (!CYCLIC && hs[q] >= n) CH_FAIL("suffixes still tied at h >= n");      // suffixes are distinct; cannot happen
             if (c.rounds > 80) CH_FAIL("more than 80 rounds");
         }
-        if (!finished && c.nchunks >= 64 && a_chunks > 0 && a_chunks * 3 < c.tail) CH_TRY(compact_chunks(ctx, c, a0, a_chunks));
+        if (!finished && c.nchunks >= 64 && a_chunks > 0 && a_chunks * 3 < c.tail) CH_TRY(compact_chunks(ctx, c, a_chunks));
     }
     rep[FC_WIDE_POSSIBLE] = c.wide_possible;
     CH_TRY(chunk_finish(ctx, c, sp, n, SA, need_sa, stable, a_chunks));

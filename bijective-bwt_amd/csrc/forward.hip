@@ -1368,15 +1368,16 @@ enum FwdReportWord { FR_CYCLIC, FR_N, FR_K, FR_SIGMA, FR_BITS, FR_MSYM, FR_KEY_B
                      FC_S = 24, FC_MAXCHUNKS, FC_A_SMALL, FC_BIG0, FC_M_EXIT, FC_M_STAY, FC_GROUPS, FC_WIDE_POSSIBLE, FC_FSL, FC_COMPACTIONS,
                      FC_COMPACTIONS_SKIPPED, FC_ENQUEUED_BEHIND_LAST,
                      FR_DIRECT = 36 /* FwdDirect: what became of the direct form */,
-                     FR_LEAN = 37 /* FwdLean: what became of the lean last pass of round 0 */ };
+                     FR_LEAN = 37 /* FwdLean: what became of the lean last pass of round 0 */,
+                     FC_S_RECUT = 38 /* chunks: the nominal size after the last compaction, 0 without one */ };
 enum FwdRoundWord { FRR_FORM, FRR_H, FRR_IN, FRR_OUT, FRR_SPLITS, FRR_PROBE = 5, FRR_MBIG, FRR_WHOLE, FRR_SKIP_NEXT,
-                    FRR_CHUNKS_IN = 5, FRR_CHUNKS_OUT, FRR_BIG_IN, FRR_BIG_STAYS, FRR_BIG_LEAVES, FRR_NCHUNKS, FRR_TILE_MBIG = 5 };
+                    FRR_CHUNKS_IN = 5, FRR_CHUNKS_OUT, FRR_BIG_IN, FRR_BIG_STAYS, FRR_BIG_LEAVES, FRR_NCHUNKS, FRR_CHUNK_S, FRR_TILE_MBIG = 5 };
 enum FwdForm { FR_FORM_NONE, FR_FORM_SPARSE, FR_FORM_CHUNKS, FR_FORM_TILES, FR_FORM_DIRECT };
 enum FwdNoChunks { FR_NC_NA, FR_NC_SHORT, FR_NC_KNOB, FR_NC_STORE, FR_NC_ORDER, FR_NC_BIGLIST };
 enum FwdEnd { FR_END_NONE, FR_END_EMPTY, FR_END_STABLE };
 enum FwdLean { FR_LEAN_NONE, FR_LEAN_HELD, FR_LEAN_SEAM, FR_LEAN_COUNT, FR_LEAN_DIRECT };
 static_assert(FR_LEAN == BWTS_FWD_LEAN_WORD, "include/bwts_test.h names the word");
-static_assert(FC_ENQUEUED_BEHIND_LAST < FR_DIRECT && FR_LEAN < FWD_HEADER_WORDS && FRR_NCHUNKS < FWD_ROUND_WORDS && FR_LEFT < FC_S, "the forward report's layout");
+static_assert(FC_ENQUEUED_BEHIND_LAST < FR_DIRECT && FC_S_RECUT < FWD_HEADER_WORDS && FRR_CHUNK_S < FWD_ROUND_WORDS && FR_LEFT < FC_S, "the forward report's layout");
 static u64 *fwd_report_open(bwts_ctx *ctx)
 {
     u64 *w = ctx->fwd_report[ctx->fwd_sorts_made < FWD_REPORT_SORTS ? ctx->fwd_sorts_made : FWD_REPORT_SORTS - 1];

@@ -353,11 +353,13 @@ int pack_device_impl(bwts_ctx *ctx, u32 version, u32 width, const u8 *d_in, u64 
 int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out);
 
 // chunk tables of the forward's later rounds (chunk_rounds.h) as plain arithmetic: nominal chunk size of a list, the tables' capacity
-// for a tied list of a0, and the re-cut of the a_chunks elements left at a compaction (allowed = the new chunks fit the tables)
-struct ChunkRecut { u32 S; u64 nc; bool allowed; };
-u32 chunk_nominal_size(u64 a);
+// for a tied list of a0 (which holds every run: the derivation stands at chunk_table_capacity), and the re-cut of the a_chunks elements
+// left at a compaction.  target: the chunks a cut aims at, CH_CHUNK_TARGET unless the test switch BWTS_CHUNK_TARGET (16 .. 16384) is set
+#define CH_CHUNK_TARGET 16384
+struct ChunkRecut { u32 S; u64 nc; };
+u32 chunk_nominal_size(u64 a, u32 target);
 u64 chunk_table_capacity(u64 a0);
-ChunkRecut chunk_recut_plan(u64 a0, u64 a_chunks);
+ChunkRecut chunk_recut_plan(u64 a_chunks, u32 target);
 
 // non-cyclic suffix sort: leaves the suffix array in *d_sa (arena memory) and ranks in *d_rank
 int suffix_sort_device(bwts_ctx *ctx, const u8 *d_T, u64 n, u32 **d_sa, u32 **d_rank, u32 *rounds);

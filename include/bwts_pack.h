@@ -43,10 +43,8 @@
  * or 8, or that differs from the first entry's, is BWTS_E_FORMAT (so is a version-2 body under a version word of 3: its width is 0).
  * After the inverse transform every block is joined at w, and the CRC-32 of the result is held against the directory: a frame whose
  * width words name another of the three widths decodes in bounds and fails with BWTS_E_CHECKSUM.
- * A limit of the transform that version 3 meets: the planes of a long smooth field are deeply repetitive, and from 2^29 bytes of such
- * a field on (2^28 bytes pack) bwts_forward_device refuses the split bytes with BWTS_E_INTERNAL, in one block and in blocks alike,
- * before anything is written; the _planes calls pass that code on.  Pack such an input in frames of at most 2^28 bytes (DESIGN
- * section 16).  Versions 1 and 2 of the same bytes are not affected.
+ * The planes of a long smooth field are deeply repetitive, the transform's dear case: such a field packs at every size (2^30 bytes of
+ * float32 run, in one block and in blocks of 1 MiB), but its pack takes several times as long as version 2's.
  *
  * A frame is not trusted.  Unpack refuses with BWTS_E_FORMAT, in this order: in_bytes < 48 or not a multiple of 16; wrong magic, or
  * a version that is not 1, 2 or 3; a wrong header CRC; n = 0 (n > 2^32 is BWTS_E_RANGE); B = 0, B > n, or B < 4096 with B != n; a directory longer than the

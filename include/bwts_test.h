@@ -30,9 +30,13 @@ int bwts_debug_sort_pairs(bwts_ctx *ctx, uint64_t *h_keys, uint32_t *h_vals, uin
 int bwts_debug_suffix_array(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint32_t *h_sa);
 int bwts_debug_lyndon(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint64_t *h_starts, uint64_t cap, uint64_t *count);
 /* Pure arithmetic, no context and no device: the chunk tables of the forward's later rounds for a tied list of a0 elements, and the
- * re-cut of the a_chunks elements left at a compaction.  out = {nominal chunk size of a0, table capacity, nominal size of a_chunks,
- * chunks of the re-cut}; returns 1 when the compaction is allowed (the re-cut fits the tables), else 0. */
+ * re-cut of the a_chunks <= a0 elements left at a compaction.  out = {nominal chunk size of a0, table capacity = a0 / 2048 + 128,
+ * nominal size of a_chunks, chunks of the re-cut}; returns 1 when the re-cut fits the tables, which it always does (the capacity
+ * holds every run the driver can make: csrc/chunk_rounds.h, chunk_table_capacity), else 0.
+ * _target: the same with cuts that aim at `target` chunks (16 .. 16384; the engine's own 16384 unless the test switch
+ * BWTS_CHUNK_TARGET is set); -1 on a target outside that range.  bwts_debug_chunk_plan is the call with 16384. */
 int bwts_debug_chunk_plan(uint64_t a0, uint64_t a_chunks, uint64_t out[4]);
+int bwts_debug_chunk_plan_target(uint64_t a0, uint64_t a_chunks, uint32_t target, uint64_t out[4]);
 /* Pure arithmetic, no context and no device: how the move-to-front stage (bwts_mtf.h) cuts one input of n >= 1 bytes.  out = {T, the
  * tile size in bytes; G, the tiles one wave composes in the scan's first level; tiles = ceil(n / T); groups = ceil(tiles / G)}.
  * Returns 0, -1 on a bad argument. */
@@ -94,17 +98,19 @@ int bwts_debug_segments_report(bwts_ctx *ctx, uint64_t out[8]);
  * log2 of the key directory's size, 0 without one; 22 tiles: the one-off order sort ran; 23 tied when the rounds ended.
  * Chunks, words 24..35: 24 S, the nominal chunk size at the start; 25 maxchunks; 26 a_small, elements of groups of at most 256;
  * 27 the big list's first size; 28, 29, 30 m_exit, m_stay and groups staying of the first split; 31 wide_possible; 32 factor
- * starts in LDS (1) or the general instantiation (0); 33 compactions done; 34 compactions chunk_recut_plan refused; 35 a round was
+ * starts in LDS (1) or the general instantiation (0); 33 compactions done; 34 always 0 (it counted refused compactions while the tables could be too small for a re-cut); 35 a round was
  * enqueued behind the last one.  All of 24..35 stay 0 when the chunk form did not run to its end (form 3 after a hand-over included).
  * 36 the direct form: 0 not tried, 1 all groups settled (form 4), 2 fell back to the sparse rounds on a group above its cap, 3 fell
  * back on two rotations equal beyond its depth.  37 (BWTS_FWD_LEAN_WORD) the lean last pass of round 0, which leaves the group flags
  * and the tied positions instead of the sorted keys and the suffix array: 0 not tried, 1 held, 2 gave up on a run of equal low key
  * words too long across a tile seam, 3 gave up on the tied count (above n / 32), 4 the direct form gave up behind it; after 2, 3 and 4
  * the classic last pass ran from the same input and words 0..36 and the rounds are what they are without the lean pass.
- * Words 38..47 stay 0.
+ * 38 chunks: the nominal chunk size after the last compaction, 0 without one (it is below word 24 when the list had shrunk enough;
+ * 0 as words 24..35 when the chunk form did not run to its end).  Words 39..47 stay 0.
  * Rounds, BWTS_FWD_ROUND_WORDS words each, the first BWTS_MAX_ROUND_STATS rounds after round 0 (those past that are counted in word 20
  * and leave no record): 0 form, as header word 13; 1 h; 2 list going in; 3 list coming out; 4 a group split in this round (1) or none did (0; direct: always 1); then sparse: 5 probe: 0 list of at most 4096, 1 ran, 2 skipped after skip_next; 6 m_big; 7 whole; 8 skip_next;
- * chunks: 5, 6 elements in chunks before and after; 7, 8, 9 big list before, stays, leaves; 10 chunks in the tables;
+ * chunks: 5, 6 elements in chunks before and after; 7, 8, 9 big list before, stays, leaves; 10 chunks in the tables; 11 the nominal
+ * chunk size, both as the round ran (what leaves is appended behind, cut by that size);
  * tiles: 5 m_big.
  * out receives whole records while they fit into cap_words; *sorts = sorts the call made.  Returns the records written, < 0 on a
  * bad argument. */

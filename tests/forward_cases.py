@@ -30,7 +30,10 @@ COVERAGE: what each name means.
   chunks.ends_empty
   chunks.two_rounds_per_trip        a round was enqueued behind the last one
   chunks.compaction_done
-  chunks.compaction_skipped         NOT REACHABLE AT TEST SIZE, see COMPACTION_SKIPPED below; tests/test_chunk_plan.py keeps the arithmetic
+  chunks.recut_smaller              a compaction re-cut the list at a nominal chunk size below the first cut's
+  chunks.appends_after_recut        ... and a later round appended what left the big list, cut by that smaller size
+  chunks.outgrows_first_cut         ... until the tables held more chunks than the first cut and first split made plus one per cut since:
+                                    impossible at one nominal size, so the tables grew past what the first cut sizes
   handover.short_list / knob / no_room_biglist    why the tile form ran instead of chunks
   tiles.no_order_sort / order_sort  list below / from 65 536 elements
   tiles.big_groups / small_only     a round saw groups of more than 256 / none did
@@ -42,11 +45,13 @@ Out of scope, kept by the 1 GiB goldens and the wide tests: n > 2^30 (sbits = 24
 "no room for the store" and "no room for the order block" need the device to be out of memory and stay out as well."""
 import numpy as np
 
-# A compaction is skipped when the re-cut of a_chunks < tail / 3 <= a0 / 3 elements makes more chunks than the tables hold.  The re-cut
-# makes at most ceil((a0 / 3) / 2048) = a0 / 6144 chunks (2048 is the smallest nominal size); the tables hold a0 / S(a0) + 1024 with
-# S(a0) <= 4096 for every a0 <= 2^26 (S = a0 / 16384 rounded up to whole K).  a0 / 6144 < a0 / 4096 + 1024: no input of at most 64 MiB
-# reaches it (tests/test_forward_model.py::test_skipped_compaction_is_out_of_reach asks bwts_debug_chunk_plan).
-COMPACTION_SKIPPED = "chunks.compaction_skipped"
+# The three names above need a nominal size that falls, and chunk_nominal_size is 2048 (its floor) from the start for every list below
+# about 32 Mi elements.  BWTS_CHUNK_TARGET=64 (cuts aim at 64 chunks instead of 16 384) brings that arithmetic to test size: a list of
+# 1 Mi elements or more starts at 16 384 and a re-cut of what is left lands lower.  This is the shape of the list that used to end in
+# "chunk table full" (254 M elements cut at 16 384, re-cut at 2048, then 30 M elements leaving the big list); that input itself is
+# tests/test_chunk_tables_gpu.py.  The chunk count of every round is part of the report that each cell holds against the model, and
+# the model holds it against the tables' capacity (forward_model.predict).
+CHUNK_TARGET_64 = {"BWTS_CHUNK_TARGET": "64"}
 
 
 def noise(n, sigma, seed, base=0):
@@ -110,6 +115,24 @@ def variants(n, sigma, seed, lp, lq, kinds, times):
     return x
 
 
+def two_level(n, seed, n_noise, lp, lq, kinds, times):
+    """Noise over four letters; behind the first n_noise positions a phrase P of lp letters followed by one of `kinds` tails of lq
+    letters, pasted `times` times.  With times > 2048 >= times / kinds the positions of P sit in the big list until the depth reaches
+    their tail, and then leave it in groups of times / kinds that stay tied while the depth stays inside the tail: a round of depth d
+    moves about min(lq, 3 d / 4) * times elements from the big list to the chunks, round after round, while the noise in front (tied
+    in small groups at first, settled one round later) has emptied the chunks it was cut into."""
+    rng = np.random.default_rng(seed)
+    x = rng.integers(0, 4, size=n, dtype=np.uint8)
+    P = rng.integers(0, 4, size=lp, dtype=np.uint8)
+    Q = [rng.integers(0, 4, size=lq, dtype=np.uint8) for _ in range(kinds)]
+    slot = lp + lq + 8
+    slots = n_noise + rng.permutation((n - n_noise) // slot)[:times] * slot
+    for i, at in enumerate(slots):
+        ph = np.concatenate([P, Q[i % kinds]])
+        x[at:at + ph.size] = ph
+    return x
+
+
 def one_pair(n):
     x = np.arange(n, dtype=np.uint8)[::-1].copy()
     x[n // 2] = x[5]
@@ -128,6 +151,11 @@ _dense4 = lambda: np.concatenate([noise(1 << 20, 4, 11), twice(noise(1 << 14, 4,
 _hundreds = lambda: np.concatenate([twice(noise(1 << 16, 256, 21)), pasted(1 << 17, 4, 22, [(48, 1000), (40, 700)])])
 _drain = lambda: variants(1 << 20, 4, 31, 40, 40, 4, 6000)
 _early = lambda n: pasted(n, 4, 41, [(64, 4096)])
+# target 64: a0 = 2 097 152 cut at 16 384 (75 chunks), re-cut after round 1 at 3072 (46 chunks), 2218 elements appended in round 2
+_recut = lambda: variants(1 << 21, 4, 31, 40, 40, 4, 12000)
+# target 64: a0 = 2 621 440 cut at 16 384 (64 chunks, 70 with the first split), re-cut after round 1 at 2048 (56 chunks), then 103 352 and
+# 116 024 elements appended in rounds 2 and 3: 164 chunks in round 4, 2.3 times what the first cut and split made
+_recut_drain = lambda: two_level(5 << 19, 32, 1000000, 660, 40, 2, 2250)
 
 CASES = [
     Case("noise256-m8", lambda: noise(1 << 17, 256, 1), 8, ["round0.wide", "round0.nothing_tied", "round0.flags_carry"]),
@@ -154,6 +182,10 @@ CASES = [
     Case("drain-nomem", _drain, 8, ["handover.no_room_biglist", "tiles.big_groups"], env={"BWTS_BIGLIST_NOMEM": "1"}),
     Case("dense4-wide-keys", _dense4, 8, ["round0.wide"], env={"BWTS_RX_PACK": "0"}),
     Case("dense4-gather", _dense4, 8, ["round0.flags_rank"], env={"BWTS_EMIT": "gather"}),
+    Case("recut", _recut, 8, ["chunks.recut_smaller", "chunks.appends_after_recut"], env=CHUNK_TARGET_64),
+    Case("recut-drain", _recut_drain, 8, ["chunks.recut_smaller", "chunks.appends_after_recut", "chunks.outgrows_first_cut"], env=CHUNK_TARGET_64),
+    Case("suffix-recut", _recut, 8, ["suffix.chunks_biglist", "chunks.recut_smaller", "chunks.appends_after_recut"], sort="suffix", env=CHUNK_TARGET_64),
+    Case("general-recut", _recut, 8, ["general.chunks", "chunks.recut_smaller", "chunks.appends_after_recut"], sort="general", env=CHUNK_TARGET_64),
     Case("suffix-sparse", lambda: pasted(1 << 20, 4, 5, [(40, 200)]), 13, ["suffix.sparse"], sort="suffix"),
     Case("suffix-chunks", _drain, 8, ["suffix.chunks_biglist"], sort="suffix"),
     Case("suffix-tiles", lambda: np.concatenate([noise(1 << 18, 200, 13), twice(noise(1 << 13, 200, 14))]), 4, ["suffix.tiles"], sort="suffix"),
@@ -170,13 +202,13 @@ COVERAGE = [
     "early_ranks.on", "early_ranks.off",
     "chunks.fsl", "chunks.general", "chunks.small_only", "chunks.biglist_leaves_at_once", "chunks.biglist_drains",
     "chunks.biglist_at_stable_end", "chunks.wide", "chunks.stable_rest", "chunks.ends_empty", "chunks.two_rounds_per_trip",
-    "chunks.compaction_done",
+    "chunks.compaction_done", "chunks.recut_smaller", "chunks.appends_after_recut", "chunks.outgrows_first_cut",
     "handover.short_list", "handover.knob", "handover.no_room_biglist",
     "tiles.no_order_sort", "tiles.order_sort", "tiles.big_groups", "tiles.small_only", "tiles.stable_rest", "tiles.ends_empty",
     "suffix.sparse", "suffix.chunks_biglist", "suffix.tiles", "general.sparse", "general.chunks", "general.tiles",
 ]
 assert not {t for c in CASES for t in c.tags} - set(COVERAGE), "a case names a path the list does not have"
-NOT_REACHABLE = [COMPACTION_SKIPPED]
+NOT_REACHABLE = []
 DEFAULT_KEY_CASES = [c for c in CASES if c.sort == "cyclic" and not c.env]       # these run once more with no key knob
 
 
@@ -205,13 +237,20 @@ def tag_holds(tag, rep):
                 "directory": rep.get("directory", 8) >= 8, "no_directory": rep.get("directory", 0) == 0,
                 "ends_empty": rep["end"] == "empty", "ends_stable": rep["end"] == "stable"}[name]
     if fam == "chunks":
-        return {"fsl": ch["fsl"], "general": not ch["fsl"], "small_only": ch["big0"] == 0,
+        # rounds that ran behind a re-cut to a smaller size (the nominal sizes stand beside the dicts that older tests compare whole)
+        smaller = [i for i, S in enumerate(rep["chunk_round_S"]) if S < ch["S"]]
+        first = -(-ch["a_small"] // ch["S"]) + -(-ch["m_exit"] // ch["S"])          # chunks of the first cut and the first split
+        return {"recut_smaller": ch["compactions"] > 0 and 0 < rep["chunk_S_recut"] < ch["S"] and len(smaller) > 0,
+                "appends_after_recut": any(rounds[i]["big_leaves"] > 0 for i in smaller),
+                # (cuts before round i: the first cut, the first split, one append per earlier round at most, the re-cuts)
+                "outgrows_first_cut": any(rounds[i]["nchunks"] > first + 2 + i + ch["compactions"] for i in smaller),
+                "fsl": ch["fsl"], "general": not ch["fsl"], "small_only": ch["big0"] == 0,
                 "biglist_leaves_at_once": ch["big0"] > 0 and ch["m_stay"] == 0 and ch["m_exit"] == ch["big0"],
                 "biglist_drains": ch["m_stay"] > 0 and sum(1 for r in rounds if r["big_leaves"] > 0) >= 2,
                 "biglist_at_stable_end": rep["end"] == "stable" and rep["rest_big"] > 0,
                 "wide": ch["wide_possible"], "stable_rest": rep["end"] == "stable" and rep["rest_chunks"] > 0,
                 "ends_empty": rep["end"] == "empty", "two_rounds_per_trip": ch["enqueued_behind_last"],
-                "compaction_done": ch["compactions"] > 0, "compaction_skipped": ch["compactions_skipped"] > 0}[name]
+                "compaction_done": ch["compactions"] > 0}[name]
     if fam == "tiles":
         return {"no_order_sort": not rep["order_sort"], "order_sort": rep["order_sort"],
                 "big_groups": any(r["m_big"] > 0 for r in rounds), "small_only": all(r["m_big"] == 0 for r in rounds),

@@ -24,6 +24,7 @@ SEG_MIN_LIST = 4096       # sparse form: lists of at most this are sorted whole,
 RANK_EARLY_N = 1 << 22
 FLAGS_OUTSIDE_N = 4096
 MAX_ROUNDS = 80
+CHUNK_TARGET = 16384      # chunks a cut aims at (the test switch BWTS_CHUNK_TARGET lowers it)
 
 
 class Model:
@@ -124,9 +125,11 @@ def key_form(key_bits, n, carry, pack=True):
     return "split40" if key_bits > 32 else "split32"
 
 
-def predict(mod, m, plan, tiles_knob=False, biglist_nomem=False, gather=False, pack=True):
-    """What a fresh context reports for fixed-width keys of m symbols (tests/forward_cases.py: the exact cells).  plan(a0, a_chunks) is
-    bwts_debug_chunk_plan: ([S(a0), capacity, S(a_chunks), chunks of the re-cut], allowed)."""
+def predict(mod, m, plan, tiles_knob=False, biglist_nomem=False, gather=False, pack=True, target=CHUNK_TARGET):
+    """What a fresh context reports for fixed-width keys of m symbols (tests/forward_cases.py: the exact cells).  plan(a0, a_chunks, target)
+    is bwts_debug_chunk_plan_target: ([S(a0), capacity, S(a_chunks), chunks of the re-cut], the re-cut fits); target is what
+    BWTS_CHUNK_TARGET says.  The chunk count is held against the capacity wherever it grows: a run that the engine would end with
+    "chunk table full" fails here first."""
     n = mod.n
     carry = mod.cyclic and not gather
     p = {"cyclic": mod.cyclic, "n": n, "k": mod.k, "need_sa": (not mod.cyclic) or gather, "flags_outside_rank": carry and n >= FLAGS_OUTSIDE_N}
@@ -183,10 +186,12 @@ def predict(mod, m, plan, tiles_knob=False, biglist_nomem=False, gather=False, p
         p["rest_tiles"] = st[-1]["tied"] if end == "stable" else 0
     else:
         s0 = st[0]
-        (S, cap, _, _), _ = plan(a0, a0)
+        (S, cap, _, _), _ = plan(a0, a0, target)
         ch = {"S": S, "maxchunks": cap, "a_small": s0["le_cap"], "big0": s0["mid"] + s0["huge"], "fsl": mod.cyclic and mod.k <= CH_FS,
               "m_exit": 0, "m_stay": 0, "groups": 0, "compactions": 0, "compactions_skipped": 0, "enqueued_behind_last": False}
+        S_recut, round_S = 0, []              # the nominal size after the last compaction, and as each round ran
         nchunks = -(-s0["le_cap"] // S)
+        assert nchunks <= cap, ("the first cut", nchunks, cap)
         tail = a_chunks = s0["le_cap"]
         big = 0
         wide = False
@@ -194,6 +199,7 @@ def predict(mod, m, plan, tiles_knob=False, biglist_nomem=False, gather=False, p
             ch.update(m_exit=s0["mid"], m_stay=s0["huge"], groups=s0["huge_groups"])
             if s0["mid"]:
                 nchunks += -(-s0["mid"] // S); tail += s0["mid"]; a_chunks += s0["mid"]; wide = True
+                assert nchunks <= cap, ("the first split", nchunks, cap)
             big = s0["huge"]
         r, finished = 1, False
         while not finished:
@@ -210,22 +216,24 @@ def predict(mod, m, plan, tiles_knob=False, biglist_nomem=False, gather=False, p
                 rounds.append({"form": "chunks", "h": st[r - 1]["depth"], "in": a_chunks + big, "out": new["tied"],
                                "split": new["classes"] > st[r - 1]["classes"], "chunks_in": a_chunks, "chunks_out": in_chunks, "big_in": big,
                                "big_stays": stays, "big_leaves": leaves, "nchunks": nchunks})
+                round_S.append(S)
                 if leaves:
                     nchunks += -(-leaves // S); tail += leaves; wide = True
+                    assert nchunks <= cap and tail <= a0, ("an append", len(rounds), nchunks, cap, tail, a0)
                 big = stays
                 a_chunks = in_chunks + leaves
                 r += 1
                 if r == len(st):
                     finished = True
             if not finished and nchunks >= 64 and a_chunks > 0 and a_chunks * 3 < tail:
-                (_, _, S2, nc), allowed = plan(a0, a_chunks)
-                if allowed:
-                    ch["compactions"] += 1
-                    S, nchunks, tail = S2, nc, a_chunks
-                else:
-                    ch["compactions_skipped"] += 1
+                (_, _, S2, nc), fits = plan(a0, a_chunks, target)
+                assert fits and nc <= cap, ("a re-cut", a0, a_chunks, nc, cap)
+                ch["compactions"] += 1
+                S_recut = S2
+                S, nchunks, tail = S2, nc, a_chunks
         ch["wide_possible"] = wide
         p["chunks"] = ch
+        p["chunk_S_recut"], p["chunk_round_S"] = S_recut, round_S
         p["rest_chunks"] = a_chunks if end == "stable" and nchunks else 0
         p["rest_big"] = big if end == "stable" else 0
     p["round"] = rounds

@@ -11,10 +11,11 @@ import oracle_lib as O
 
 
 def chunk_plan(pkg):
-    def plan(a0, a_chunks):
+    def plan(a0, a_chunks, target=M.CHUNK_TARGET):
         out = (ctypes.c_uint64 * 4)()
-        allowed = pkg.lib().bwts_debug_chunk_plan(a0, a_chunks, out)
-        return [int(v) for v in out], bool(allowed)
+        fits = pkg.lib().bwts_debug_chunk_plan_target(a0, a_chunks, target, out)
+        assert fits in (0, 1)
+        return [int(v) for v in out], bool(fits)
     return plan
 
 
@@ -84,15 +85,6 @@ def test_hand_worked_cases():
     assert (s["tied"], s["huge"], s["huge_groups"], s["le_cap"], s["mid"]) == (90000, 90000, 30, 0, 0)
 
 
-def test_skipped_compaction_is_out_of_reach(pkg):
-    """forward_cases.COMPACTION_SKIPPED: no tied list of at most 64 Mi elements has a compaction refused (a_chunks < a0 / 3 when it triggers)."""
-    plan = chunk_plan(pkg)
-    rng = np.random.default_rng(1)
-    for a0 in [65536, 1 << 20, (1 << 24) + 1, (1 << 25) - 1, 1 << 26] + [int(v) for v in rng.integers(65536, 1 << 26, 300)]:
-        for a_chunks in (1, a0 // 6, (a0 - 1) // 3):
-            assert plan(a0, a_chunks)[1], (a0, a_chunks)
-
-
 _pred = {}
 
 
@@ -102,7 +94,7 @@ def prediction(case, plan):
         if case.sort == "general":
             mod = M.Model(mod.x, cyclic=False)
         _pred[case.name] = M.predict(mod, case.m, plan, tiles_knob=case.env.get("BWTS_DENSE") == "tiles", biglist_nomem="BWTS_BIGLIST_NOMEM" in case.env,
-                                     gather=case.env.get("BWTS_EMIT") == "gather", pack=case.env.get("BWTS_RX_PACK") != "0")
+                                     gather=case.env.get("BWTS_EMIT") == "gather", pack=case.env.get("BWTS_RX_PACK") != "0", target=int(case.env.get("BWTS_CHUNK_TARGET", M.CHUNK_TARGET)))
     return _pred[case.name]
 
 
@@ -117,4 +109,4 @@ def test_every_path_is_predicted(pkg):
     plan = chunk_plan(pkg)
     seen = {t for c in FC.CASES for t in c.tags if FC.tag_holds(t, prediction(c, plan))}
     assert not [t for t in FC.COVERAGE if t not in seen]
-    assert FC.COMPACTION_SKIPPED not in FC.COVERAGE and FC.NOT_REACHABLE == [FC.COMPACTION_SKIPPED]
+    assert FC.NOT_REACHABLE == []

@@ -19,7 +19,7 @@ import oracle_lib as O
 pytestmark = pytest.mark.gpu
 
 _KNOBS = ("BWTS_TEST_KNOBS", "BWTS_POISON", "BWTS_VARLEN", "BWTS_KEY_SYMBOLS", "BWTS_KEY_BITS", "BWTS_DENSE", "BWTS_BIGLIST_NOMEM", "BWTS_RX_PACK",
-          "BWTS_EMIT", "BWTS_LYNDON", "BWTS_ROUND_TRACE", "BWTS_FORCE_WIDE")
+          "BWTS_EMIT", "BWTS_LYNDON", "BWTS_ROUND_TRACE", "BWTS_FORCE_WIDE", "BWTS_CHUNK_TARGET")
 
 
 @contextlib.contextmanager
@@ -40,10 +40,11 @@ def fresh_context(pkg, env):
 
 
 def chunk_plan(pkg):
-    def plan(a0, a_chunks):
+    def plan(a0, a_chunks, target=M.CHUNK_TARGET):
         out = (ctypes.c_uint64 * 4)()
-        allowed = pkg.lib().bwts_debug_chunk_plan(a0, a_chunks, out)
-        return [int(v) for v in out], bool(allowed)
+        fits = pkg.lib().bwts_debug_chunk_plan_target(a0, a_chunks, target, out)
+        assert fits in (0, 1)
+        return [int(v) for v in out], bool(fits)
     return plan
 
 
@@ -76,6 +77,7 @@ def check_exact(rep, p, t=None):
         assert (rep["order_sort"], rep["rest_tiles"], rep["rest_chunks"], rep["rest_big"]) == (p["order_sort"], p["rest_tiles"], 0, 0), rep
     if p["form"] == "chunks":
         assert rep["chunks"] == p["chunks"], (rep["chunks"], p["chunks"])
+        assert (rep["chunk_S_recut"], rep["chunk_round_S"]) == (p["chunk_S_recut"], p["chunk_round_S"]), (rep["chunk_S_recut"], rep["chunk_round_S"])
         assert (rep["rest_chunks"], rep["rest_big"], rep["rest_tiles"]) == (p["rest_chunks"], p["rest_big"], 0), rep
     assert len(rep["round"]) == len(p["round"]) == rep["rounds"] - 1
     for r, pr in zip(rep["round"], p["round"]):
@@ -110,7 +112,7 @@ def test_forward_path(pkg, case):
     if case.sort == "general":
         env["BWTS_LYNDON"] = "general"
     knobs = dict(tiles_knob=env.get("BWTS_DENSE") == "tiles", biglist_nomem="BWTS_BIGLIST_NOMEM" in env, gather=env.get("BWTS_EMIT") == "gather",
-                 pack=env.get("BWTS_RX_PACK") != "0")
+                 pack=env.get("BWTS_RX_PACK") != "0", target=int(env.get("BWTS_CHUNK_TARGET", M.CHUNK_TARGET)))
     with fresh_context(pkg, env) as ctx:
         if case.sort == "suffix":
             sa = ctx.debug_suffix_array(x)
@@ -135,7 +137,8 @@ def test_forward_path(pkg, case):
         check_exact(reps[-1], M.predict(pre["cyclic"], case.m, plan, **knobs), t)
         home = reps[-1]
         if case.sort == "general":                  # the suffix sort first; both sorts see the same key knob
-            check_exact(reps[0], M.predict(pre["suffix"], case.m, plan, tiles_knob=knobs["tiles_knob"], biglist_nomem=knobs["biglist_nomem"]))
+            check_exact(reps[0], M.predict(pre["suffix"], case.m, plan, tiles_knob=knobs["tiles_knob"], biglist_nomem=knobs["biglist_nomem"],
+                                              target=knobs["target"]))
             home = reps[0]
     for tag in case.tags:
         assert FC.tag_holds(tag, home), (tag, home)

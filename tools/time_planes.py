@@ -5,8 +5,7 @@ rounds each.  The bar, both sides from this run, no further margin; exit code 1 
           zrl_encode_device on the move-to-front ranks of the bench default zipf(2^30, seed 1).
 For the record, with no bar: a plain device-to-device copy of the same bytes; packed size / n of the device's frames of versions 2 and
 3 for typed inputs of 1 MiB (one block) beside bz2 -9, the rows that gain nothing included; pack_device and unpack_device of versions
-2 and 3 on a float32 field of 2^30 bytes, in one block and in blocks of 1 MiB (of its first 2^28 bytes, and the output says so, where
-the transform refuses the split bytes with BWTS_E_INTERNAL: DESIGN section 16; any other error ends the run).
+2 and 3 on a float32 field of 2^30 bytes, in one block and in blocks of 1 MiB.
     python tools/time_planes.py [--log2n 30] [--reps 6] > profiles/planes_stage.txt"""
 import argparse
 import bz2
@@ -143,16 +142,7 @@ def main():
                      ("pack_device v3 w=4", lambda: size.update(v3=ctx.pack_device(x, m, b, g, cap, planes=4))),
                      ("unpack_device v2", lambda: ctx.unpack_device(f, size["v2"], back, m)),
                      ("unpack_device v3 w=4", lambda: ctx.unpack_device(g, size["v3"], back, m))]
-            try:
-                rounds(ctx, calls, 1)
-            except pkg.BwtsError as e:
-                # the transform's own limit on deeply repetitive bytes, which the planes of a long smooth field are (DESIGN section
-                # 16): BWTS_E_INTERNAL from its chunk form, and nothing else, makes the record fall back to a quarter of the field
-                if e.code != -6 or m != n:
-                    raise
-                m = n // 4
-                print("float32 field of 2^%d bytes, %s: a call fails (%s); the first %d bytes instead" % (args.log2n, what, e, m), flush=True)
-                rounds(ctx, calls, 1)
+            rounds(ctx, calls, 1)
             assert ctx.device_equal(back, x, m), "unpack(pack(x)) != x"
             print("float32 field, %d bytes, %s (no bar): %d rounds, the four calls alternated" % (m, what, reps))
             report(rounds(ctx, calls, reps))

@@ -66,6 +66,7 @@ PACK_EXPORTS = [
     "bwts_pack_device", "bwts_unpack_device", "bwts_pack", "bwts_unpack",
     "bwts_pack_bound_v", "bwts_pack_device_v", "bwts_pack_v",
     "bwts_pack_planes_bound", "bwts_pack_planes_device", "bwts_pack_planes",
+    "bwts_unpack_ranges_device", "bwts_unpack_ranges",
 ]
 E_CHECKSUM = -10
 # ... and include/bwts_test.h (harness and unit-test hooks)
@@ -76,7 +77,11 @@ TEST_EXPORTS = [
     "bwts_debug_forward_report", "bwts_debug_segments_plan", "bwts_debug_segments_report",
     "bwts_debug_mtf_plan", "bwts_debug_last_spans", "bwts_debug_ec_plan", "bwts_debug_crc_plan",
     "bwts_debug_zrl_plan", "bwts_debug_planes_plan",
+    "bwts_debug_unpack_ranges_plan", "bwts_debug_unpack_ranges_report", "bwts_debug_copy_pieces",
 ]
+# bwts_debug_unpack_ranges_report: the words of the record, and the stages by their bits
+RANGES_REPORT_FIELDS = ["blocks", "runs", "covered_bytes", "stream_bytes", "gathered", "pieces", "stages", "single"]
+RANGES_STAGES = {1: "gather", 2: "decode", 4: "zrl", 8: "mtf", 16: "inverse", 32: "join", 64: "crc", 128: "cut"}
 # bwts_debug_inverse_report: the words of one attempt's record, and what marks, outcomes and forms are called
 INV_REPORT_FIELDS = ["g", "mark", "outcome", "s", "virtual", "node_cap", "nu", "nu2", "ucap_first", "second_collect",
                      "listed_classes", "mom_fallback", "unit_rank", "kc", "kt", "form"]
@@ -230,6 +235,11 @@ def lib():
         for name in ("bwts_unpack_device", "bwts_unpack"):
             getattr(L, name).argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
         L.bwts_debug_crc_plan.argtypes = [u64, ctypes.POINTER(u64)]
+        for name in ("bwts_unpack_ranges_device", "bwts_unpack_ranges"):
+            getattr(L, name).argtypes = [vp, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64)]
+        L.bwts_debug_unpack_ranges_plan.argtypes = [vp, u64, vp, u64, u64, ctypes.POINTER(u64), vp, u64]
+        L.bwts_debug_unpack_ranges_report.argtypes = [vp, ctypes.POINTER(u64)]
+        L.bwts_debug_copy_pieces.argtypes = [vp, vp, u64, vp, u64, vp, u64]
         for name in ("bwts_forward_sink", "bwts_inverse_sink"):
             getattr(L, name).argtypes = [vp, vp, u64, SINK_FN, vp]
         L.bwts_generate_device.argtypes = [vp, i32, u64, u64, vp]
@@ -631,6 +641,47 @@ class Context:
         self._check(lib().bwts_unpack_device(self._h, _ptr(d_in), int(in_bytes), _ptr(d_out), int(out_cap), ctypes.byref(got)))
         return int(got.value)
 
+    def unpack_ranges(self, frame, ranges):
+        """bwts_unpack_ranges: the bytes of every (offset, nbytes) range of the unpacked input, one uint8 array per range, in the
+        order given (host buffers).  Only the blocks the ranges touch are decoded, and only their checksums are held against the
+        frame's: damage in a block no range touches goes unnoticed."""
+        a, rs = _u8(frame), _ranges(ranges)
+        total = sum(int(b) for _, b in rs.tolist())
+        out = np.empty(max(total, 1), dtype=np.uint8)[:total]       # (never a null pointer: the library judges the ranges itself)
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_unpack_ranges(self._h, a.ctypes.data, a.size, rs.ctypes.data if rs.size else None, len(rs), out.ctypes.data, total,
+                                             ctypes.byref(got)))
+        ends = np.cumsum(rs[:, 1], dtype=np.uint64).tolist()
+        return [out[e - int(b):e] for e, b in zip(ends, rs[:, 1].tolist())]
+
+    def unpack_range(self, frame, offset, nbytes):
+        """unpack_ranges with one range."""
+        return self.unpack_ranges(frame, [(offset, nbytes)])[0]
+
+    def unpack_ranges_device(self, d_in, in_bytes, ranges, d_out, out_cap):
+        """bwts_unpack_ranges_device: the ranges' bytes back to back in d_out; returns their sum."""
+        rs = _ranges(ranges)
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_unpack_ranges_device(self._h, _ptr(d_in), int(in_bytes), rs.ctypes.data if rs.size else None, len(rs), _ptr(d_out),
+                                                    int(out_cap), ctypes.byref(got)))
+        return int(got.value)
+
+    def debug_unpack_ranges_report(self):
+        """What the most recent unpack_ranges / unpack_ranges_device on this context did (RANGES_REPORT_FIELDS; "stages": the names
+        of the stages that ran, "stage_bits": the word itself; "gathered" and "single" as bool)."""
+        buf = (ctypes.c_uint64 * 8)()
+        self._check(lib().bwts_debug_unpack_ranges_report(self._h, buf))
+        d = {f: int(buf[i]) for i, f in enumerate(RANGES_REPORT_FIELDS)}
+        d["stage_bits"], d["stages"] = d["stages"], [name for bit, name in RANGES_STAGES.items() if d["stages"] & bit]
+        d["gathered"], d["single"] = bool(d["gathered"]), bool(d["single"])
+        return d
+
+    def debug_copy_pieces(self, d_src, src_bytes, pieces, d_dst, dst_bytes):
+        """bwts_debug_copy_pieces: copy_pieces_kernel alone over (src offset, dst offset, bytes) triples."""
+        ps = np.ascontiguousarray(pieces, dtype=np.uint64).reshape(-1, 3)
+        self._check(lib().bwts_debug_copy_pieces(self._h, _ptr(d_src), int(src_bytes), ps.ctypes.data if ps.size else None, len(ps), _ptr(d_dst),
+                                                 int(dst_bytes)))
+
     def forward_into(self, a, out):
         """bwts_forward on caller-provided numpy buffers (no allocation inside the call)."""
         self._check(lib().bwts_forward(self._h, a.ctypes.data, a.size, out.ctypes.data))
@@ -840,6 +891,35 @@ def pack_bound(n, block_bytes=0, version=None, planes=None):
     if b == 0:
         raise BwtsError(-5 if int(n) > (1 << 32) else -1, "no bound for these arguments")
     return b
+
+
+def _ranges(ranges):
+    """(offset, nbytes) pairs as the uint64 array that is a bwts_range list."""
+    return np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 2)
+
+
+def debug_unpack_ranges_plan(frame, ranges, out_cap=None, in_bytes=None):
+    """What a range read of this frame would decode and move (bwts_debug_unpack_ranges_plan: host arithmetic over the frame's header
+    and directory, no context, no device): blocks, runs [(first block, blocks)], covered_bytes, stream_bytes, coded_bytes, out_bytes,
+    T, streams and out [(src, dst, bytes)].  Refusals raise BwtsError with the call's code.  in_bytes: the frame's length where `frame`
+    holds its header and directory alone."""
+    a, rs = _u8(frame), _ranges(ranges)
+    nbytes = a.size if in_bytes is None else int(in_bytes)
+    cap = (1 << 64) - 1 if out_cap is None else int(out_cap)
+    head = (ctypes.c_uint64 * 8)()
+    rp = rs.ctypes.data if rs.size else None
+    rc = lib().bwts_debug_unpack_ranges_plan(a.ctypes.data, nbytes, rp, len(rs), cap, head, None, 0)
+    if rc != 0:
+        raise BwtsError(rc, lib().bwts_strerror(rc).decode())
+    lists = np.zeros(int(head[7]), dtype=np.uint64)
+    rc = lib().bwts_debug_unpack_ranges_plan(a.ctypes.data, nbytes, rp, len(rs), cap, head, lists.ctypes.data, lists.size)
+    if rc != 0:
+        raise BwtsError(rc, lib().bwts_strerror(rc).decode())
+    runs, w = int(head[1]), lists.tolist()
+    triples = [tuple(w[2 * runs + 3 * i:2 * runs + 3 * i + 3]) for i in range(runs + len(rs))]
+    return {"blocks": int(head[0]), "runs": [tuple(w[2 * i:2 * i + 2]) for i in range(runs)], "covered_bytes": int(head[2]),
+            "stream_bytes": int(head[3]), "coded_bytes": int(head[4]), "out_bytes": int(head[5]), "T": int(head[6]),
+            "streams": triples[:runs], "out": triples[runs:]}
 
 
 def unpack_size(frame):

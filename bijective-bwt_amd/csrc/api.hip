@@ -11,6 +11,7 @@
 #include "planes_plan.h"
 #include "pack_plan.h"
 
+#include <algorithm>
 #include <new>
 #include <stdio.h>
 #include <time.h>
@@ -751,6 +752,66 @@ extern "C" int bwts_unpack(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, 
     if (v > out_cap) return BWTS_E_SPACE;
     const HostTrip trip = {in, in_bytes, in_bytes > v ? in_bytes : v, out, n};
     return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *got) { return bwts_unpack_device(ctx, d_in, in_bytes, d_out, v, got); });
+}
+
+// ranges of a frame (include/bwts_pack.h, "Ranges"): the driver in pack.hip, the plan in pack_plan.h
+static_assert(sizeof(bwts_range) == sizeof(PackRange) && offsetof(bwts_range, bytes) == offsetof(PackRange, bytes), "bwts_range is pack_plan.h's PackRange");
+
+extern "C" int bwts_unpack_ranges_device(bwts_ctx *ctx, const void *d_in, uint64_t in_bytes, const bwts_range *ranges, uint64_t count,
+                                         void *d_out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!ctx || !d_in || !d_out || !out_bytes || in_bytes == 0 || ((uintptr_t)d_in & 15)) return BWTS_E_ARG;
+    if (ranges_overlap(d_in, in_bytes, d_out, out_cap)) return BWTS_E_ARG;
+    return run_sized(ctx, 0, "unpack ranges", [&] {
+        return unpack_ranges_device_impl(ctx, (const u8 *)d_in, in_bytes, false, (const PackRange *)ranges, count, (u8 *)d_out, out_cap, out_bytes);
+    });
+}
+
+// The host form judges frame and ranges itself, in the device form's order, and sends header, directory and the covered blocks'
+// streams alone, back to back: the device form finds them gathered.
+extern "C" int bwts_unpack_ranges(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const bwts_range *ranges, uint64_t count,
+                                  uint8_t *out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!ctx || !in || !out || !out_bytes || in_bytes == 0) return BWTS_E_ARG;
+    PackHeader H;
+    u64 frame = 0, sum = 0;
+    BWTS_TRY(pack_header_check(in, in_bytes, &H));
+    BWTS_TRY(pack_directory_check(in + PACK_HEADER_BYTES, H, in_bytes, true, &frame));
+    BWTS_TRY(pack_ranges_check(H, (const PackRange *)ranges, count, out_cap, &sum));
+    PackRangesPlan P;
+    pack_ranges_plan(H, in + PACK_HEADER_BYTES, (const PackRange *)ranges, count, &P);
+    const u64 fixed = pack_fixed_bytes_v(H.version, H.nblk);
+    std::vector<u8> sent((size_t)(fixed + P.stream_bytes));
+    memcpy(sent.data(), in, (size_t)fixed);
+    for (const PackPiece &s : P.streams) memcpy(sent.data() + fixed + s.dst, in + s.src, (size_t)s.bytes);
+    const HostTrip trip = {sent.data(), sent.size(), sent.size() > sum ? sent.size() : sum, out, out_bytes};
+    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *got) {
+        return run_sized(ctx, 0, "unpack ranges", [&] {
+            return unpack_ranges_device_impl(ctx, d_in, in_bytes, true, (const PackRange *)ranges, count, d_out, sum, got);
+        });
+    });
+}
+
+// copy_pieces_kernel alone (include/bwts_test.h; here for the call bracket): refuses, before anything is launched, what the driver's
+// plan cannot make -- a piece that leaves either buffer, or two that share a destination byte
+extern "C" int bwts_debug_copy_pieces(bwts_ctx *ctx, const void *d_src, uint64_t src_bytes, const uint64_t *pieces, uint64_t count, void *d_dst,
+                                      uint64_t dst_bytes)
+{
+    if (!ctx || !d_src || !d_dst || !pieces || count == 0 || count > PACK_MAX_RANGES) return BWTS_E_ARG;
+    std::vector<PackPiece> ps((size_t)count);
+    std::vector<std::pair<u64, u64>> dsts((size_t)count);
+    u64 total = 0;
+    for (u64 i = 0; i < count; i++) {
+        const PackPiece p = {pieces[3 * i], pieces[3 * i + 1], pieces[3 * i + 2]};
+        if (p.bytes == 0 || p.bytes > src_bytes || p.src > src_bytes - p.bytes || p.bytes > dst_bytes || p.dst > dst_bytes - p.bytes) return BWTS_E_ARG;
+        ps[(size_t)i] = p;
+        dsts[(size_t)i] = {p.dst, p.bytes};
+        total += p.bytes;
+    }
+    std::sort(dsts.begin(), dsts.end());
+    for (u64 i = 1; i < count; i++)
+        if (dsts[(size_t)i].first - dsts[(size_t)i - 1].first < dsts[(size_t)i - 1].second) return BWTS_E_ARG;
+    return run_sized(ctx, total, "copy pieces", [&] { return copy_pieces_impl(ctx, (const u8 *)d_src, src_bytes, ps.data(), count, (u8 *)d_dst); });
 }
 
 extern "C" int bwts_host_alloc(bwts_ctx *ctx, uint64_t bytes, void **h_ptr)

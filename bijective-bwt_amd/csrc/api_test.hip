@@ -144,6 +144,36 @@ extern "C" int bwts_debug_planes_plan(uint64_t n, uint32_t width, uint64_t out[4
     return 0;
 }
 
+// what a range read of a frame would decode and move (pack_plan.h): the frame's header and directory alone are read.  No context, no device
+extern "C" int bwts_debug_unpack_ranges_plan(const uint8_t *frame, uint64_t in_bytes, const uint64_t *ranges, uint64_t count, uint64_t out_cap,
+                                             uint64_t out[8], uint64_t *lists, uint64_t cap_words)
+{
+    if (!frame || !out || (!lists && cap_words)) return -1;
+    PackHeader H;
+    u64 total = 0, sum = 0;
+    BWTS_TRY(pack_header_check(frame, in_bytes, &H));
+    BWTS_TRY(pack_directory_check(frame + PACK_HEADER_BYTES, H, in_bytes, true, &total));
+    BWTS_TRY(pack_ranges_check(H, (const PackRange *)ranges, count, out_cap, &sum));
+    PackRangesPlan P;
+    pack_ranges_plan(H, frame + PACK_HEADER_BYTES, (const PackRange *)ranges, count, &P);
+    const u64 runs = P.runs.size(), words = 5 * runs + 3 * count;
+    const u64 head[8] = {(u64)P.blocks.size(), runs, P.covered_bytes, P.stream_bytes, P.coded_bytes, P.out_bytes, PIECES_T, words};
+    memcpy(out, head, sizeof head);
+    if (words > cap_words) return 0;
+    for (const PackRun &r : P.runs) { *lists++ = r.first; *lists++ = r.blocks; }
+    for (const PackPiece &s : P.streams) { *lists++ = s.src; *lists++ = s.dst; *lists++ = s.bytes; }
+    for (const PackPiece &o : P.out) { *lists++ = o.src; *lists++ = o.dst; *lists++ = o.bytes; }
+    return 0;
+}
+
+// what the most recent range read on this context did: no device, the record is host memory
+extern "C" int bwts_debug_unpack_ranges_report(bwts_ctx *ctx, uint64_t out[8])
+{
+    if (!ctx || !out) return BWTS_E_ARG;
+    memcpy(out, ctx->ranges_report, sizeof ctx->ranges_report);
+    return BWTS_OK;
+}
+
 // the device time of every timed launch of the most recent call, in launch order (timing level 2: every launch has a span; the events
 // stay with the context until the next call)
 extern "C" int bwts_debug_last_spans(bwts_ctx *ctx, double *ms, uint64_t cap)

@@ -134,6 +134,8 @@ struct bwts_ctx {
     // inverse: what the most recent segmented inverse did (bwts_debug_segments_report; include/bwts_test.h names the words)
     u64 seg_report[SEG_REPORT_WORDS] = {0};
     bool crc_tables = false;            // the checksum's tables (crc.hip) have been made on this context's device
+    // ranges of a frame: what the most recent call did (bwts_debug_unpack_ranges_report; include/bwts_test.h names the words)
+    u64 ranges_report[8] = {0};
 
     bwts_timings tm;
     double host_ms[BWTS_H_COUNT];   // cumulative host-side costs (BWTS_H_*)
@@ -351,6 +353,13 @@ int crc_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, SegMode segs, u32 *crcs);
 void bwts_crc_plan(u64 n, u64 out[4]);                                  // tile size, tiles per fold group, tiles and groups of one input
 int pack_device_impl(bwts_ctx *ctx, u32 version, u32 width, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes);   // width: version 3 only
 int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out);
+// ranges of a frame (pack_plan.h names the three types).  packed: d_in holds header, directory and behind them the covered blocks'
+// streams alone, back to back (the host form); in_bytes stays the whole frame's length
+struct PackRange;
+struct PackPiece;
+int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool packed, const PackRange *ranges, u64 count, u8 *d_out, u64 out_cap, u64 *out_bytes);
+// pieces of one device buffer to another, at any alignment (pieces.hip); every piece inside both buffers, by the caller's check
+int copy_pieces_impl(bwts_ctx *ctx, const u8 *d_src, u64 src_bytes, const PackPiece *pieces, u64 count, u8 *d_dst);
 
 // chunk tables of the forward's later rounds (chunk_rounds.h) as plain arithmetic: nominal chunk size of a list, the tables' capacity
 // for a tied list of a0 (which holds every run: the derivation stands at chunk_table_capacity), and the re-cut of the a_chunks elements

@@ -12,6 +12,8 @@
 // stage's the blocks themselves.
 // The bytes between two stages go to and fro between two blocks (pack) or between one block and d_out (unpack); where a version has
 // a stage more, the directions swap, so that the last stage of an unpack always lands in d_out.
+// A range read (unpack_ranges_device_impl, at the end) runs the same stages over the blocks its ranges touch, between the two blocks,
+// and cuts the ranges out with pieces.hip's copy kernel.
 #include "internal.h"
 #include "pack_plan.h"
 #include "../../include/bwts_pack.h"
@@ -19,7 +21,8 @@
 #include <string.h>
 #include <utility>
 
-static_assert(PACK_OK == BWTS_OK && PACK_RANGE == BWTS_E_RANGE && PACK_FORMAT == BWTS_E_FORMAT, "pack_plan.h answers in the library's codes");
+static_assert(PACK_OK == BWTS_OK && PACK_RANGE == BWTS_E_RANGE && PACK_FORMAT == BWTS_E_FORMAT && PACK_ARG == BWTS_E_ARG && PACK_SPACE == BWTS_E_SPACE,
+              "pack_plan.h answers in the library's codes");
 
 // the n-byte block between two stages
 static int pack_stage(bwts_ctx *ctx, int i, u64 n, u8 **p)
@@ -118,27 +121,45 @@ int pack_device_impl(bwts_ctx *ctx, u32 version, u32 width, const u8 *d_in, u64 
 
 // The frame is not trusted: header, then directory, are brought to the host and judged by the predicates of pack_plan.h before
 // anything is made of them; the coder and the zero-run decoder judge their inputs themselves.
-int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out)
+// What both unpacks know of a frame before a stream is touched.  The segment table is the frame's blocks when this returns; dir is
+// staging that the next stage writes over (seg_layout.h): what the directory says is copied out at once.
+struct FrameHead {
+    PackHeader H;
+    std::vector<u8> own;
+    u8 *dir;
+    u64 fixed, entry;
+};
+
+static int unpack_frame_head(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, FrameHead &F)
 {
     if (in_bytes < PACK_LEAST_FRAME || (in_bytes & 15u)) return BWTS_E_FORMAT;
-    u8 *head = (u8 *)(ctx->h_small + SM_PACK_HEAD), *dir = nullptr;
+    u8 *head = (u8 *)(ctx->h_small + SM_PACK_HEAD);
     const u64 first = in_bytes < PACK_HEADER_BYTES + PACK_ENTRY_BYTES_V2 ? in_bytes : PACK_HEADER_BYTES + PACK_ENTRY_BYTES_V2;
     HIPC(hipMemcpyAsync(head, d_in, first, hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
-    PackHeader H;
+    PackHeader &H = F.H;
     BWTS_TRY(pack_header_check(head, in_bytes, &H));
-    const bool seg = H.nblk > 1, zrl = H.version != PACK_VERSION, planes = H.version == PACK_VERSION_3;
-    const u64 fixed = pack_fixed_bytes_v(H.version, H.nblk), entry = pack_entry_bytes(H.version);
+    F.fixed = pack_fixed_bytes_v(H.version, H.nblk);
+    F.entry = pack_entry_bytes(H.version);
     BWTS_TRY(pack_blocks_set(ctx, H.n, H.B, H.nblk));
-    const SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
-    std::vector<u8> own;
-    BWTS_TRY(pack_dir_staging(ctx, H.version, H.nblk, own, &dir));
-    if (seg) {
-        HIPC(hipMemcpyAsync(dir, d_in + PACK_HEADER_BYTES, entry * H.nblk, hipMemcpyDeviceToHost, ctx->stream));
+    BWTS_TRY(pack_dir_staging(ctx, H.version, H.nblk, F.own, &F.dir));
+    if (H.nblk > 1) {
+        HIPC(hipMemcpyAsync(F.dir, d_in + PACK_HEADER_BYTES, F.entry * H.nblk, hipMemcpyDeviceToHost, ctx->stream));
         HIPC(hipStreamSynchronize(ctx->stream));
     }
     u64 frame = 0;
-    BWTS_TRY(pack_directory_check(dir, H, in_bytes, true, &frame));
+    return pack_directory_check(F.dir, H, in_bytes, true, &frame);
+}
+
+int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out)
+{
+    FrameHead F;
+    BWTS_TRY(unpack_frame_head(ctx, d_in, in_bytes, F));
+    const PackHeader &H = F.H;
+    const u8 *dir = F.dir;
+    const bool seg = H.nblk > 1, zrl = H.version != PACK_VERSION, planes = H.version == PACK_VERSION_3;
+    const u64 fixed = F.fixed, entry = F.entry;
+    const SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
     if (H.n > out_cap) return BWTS_E_SPACE;
     ctx->tm.n = H.n;
     // (the staging is the next stage's: what the directory says is kept here)
@@ -194,5 +215,91 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
     BWTS_TRY(crc_impl(ctx, d_out, H.n, segs, got.data()));
     if (memcmp(got.data(), want.data(), (size_t)H.nblk * sizeof(u32)) != 0) return BWTS_E_CHECKSUM;
     *n_out = H.n;
+    return BWTS_OK;
+}
+
+// Ranges of a frame (include/bwts_pack.h, "Ranges"): the frame is judged as above, then the ranges; the plan of pack_plan.h names the
+// covered blocks, and only their streams are decoded, through the same stages over a segment table of the covered blocks alone.  The
+// bytes go to and fro between the two stage blocks (neither is d_out here); the covered blocks' checksums are held against the
+// directory, and only then are the ranges cut out of the last stage's block into d_out.
+enum { RG_GATHER = 1, RG_DECODE = 2, RG_ZRL = 4, RG_MTF = 8, RG_INVERSE = 16, RG_JOIN = 32, RG_CRC = 64, RG_CUT = 128 };
+
+int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool packed, const PackRange *ranges, u64 count, u8 *d_out, u64 out_cap, u64 *out_bytes)
+{
+    u64 *rep = ctx->ranges_report;
+    memset(rep, 0, sizeof ctx->ranges_report);
+    FrameHead F;
+    BWTS_TRY(unpack_frame_head(ctx, d_in, in_bytes, F));
+    const PackHeader &H = F.H;
+    const bool zrl = H.version != PACK_VERSION, planes = H.version == PACK_VERSION_3;
+    u64 sum = 0;
+    BWTS_TRY(pack_ranges_check(H, ranges, count, out_cap, &sum));
+    PackRangesPlan P;
+    pack_ranges_plan(H, F.dir, ranges, count, &P);
+    const u64 C = P.covered_bytes, nb = P.blocks.size();
+    const bool seg = nb > 1, gather = !packed && P.runs.size() > 1;
+    // (the staging is the next stage's: what the directory says of the covered blocks is kept here)
+    std::vector<u64> lengths((size_t)nb), sizes((size_t)nb), coded((size_t)nb);
+    std::vector<u32> want((size_t)nb), got((size_t)nb);
+    for (u64 k = 0; k < nb; k++) {
+        const u8 *e = F.dir + F.entry * P.blocks[(size_t)k];
+        lengths[(size_t)k] = pack_block_at(H.n, H.B, P.blocks[(size_t)k]);
+        sizes[(size_t)k] = pack_le64(e);
+        want[(size_t)k] = ec_le32(e + 8);
+        coded[(size_t)k] = zrl ? pack_le64(e + 16) : lengths[(size_t)k];
+    }
+    ctx->tm.n = C;
+    rep[0] = nb; rep[1] = P.runs.size(); rep[2] = C; rep[3] = P.stream_bytes; rep[4] = gather; rep[5] = P.out.size(); rep[7] = !seg;
+    // one covered block: no table, the single-input stages, as a frame of one block
+    auto blocks_set = [&] { u64 total = 0; return seg ? seg_table_set(ctx, lengths.data(), nb, &total) : BWTS_OK; };
+    BWTS_TRY(blocks_set());
+    const SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
+    // the stage blocks hold the covered bytes, and the gathered streams where there are any (a stream may be longer than its block)
+    const u64 room = gather && P.stream_bytes > C ? P.stream_bytes : C;
+    u8 *to = nullptr, *other = nullptr;
+    BWTS_TRY(pack_stage(ctx, 0, room, &to));
+    BWTS_TRY(pack_stage(ctx, 1, room, &other));
+    // the covered streams, back to back: behind the directory (host form), gathered, or where the one run lies in the frame
+    const u8 *from = packed ? d_in + F.fixed : d_in + P.streams[0].src;
+    auto done = [&](u64 bit) { rep[6] |= bit; from = to; std::swap(to, other); return hipStreamSynchronize(ctx->stream); };
+    if (gather) {
+        BWTS_TRY(copy_pieces_impl(ctx, d_in, in_bytes, P.streams.data(), P.streams.size(), to));
+        HIPC(done(RG_GATHER));
+    }
+    u64 m = C;
+    SegMode csegs = segs;
+    if (zrl) {
+        BWTS_TRY(pack_coded_set(ctx, coded, &m));
+        if (seg) csegs = seg_mode(ctx);
+    }
+    if (seg) {
+        BWTS_TRY(ec_decode_impl(ctx, from, m, to, m, nullptr, csegs, sizes.data()));
+    } else {
+        u64 named = 0;
+        const int rc = ec_decode_impl(ctx, from, sizes[0], to, m, &named, csegs, nullptr);
+        if (rc == BWTS_E_SPACE || (rc == BWTS_OK && named != m)) return BWTS_E_FORMAT;
+        BWTS_TRY(rc);
+    }
+    HIPC(done(RG_DECODE));
+    ctx->tm.n = C;        // (the coder has put its own n there)
+    if (zrl) {
+        BWTS_TRY(blocks_set());
+        BWTS_TRY(zrl_decode_impl(ctx, from, m, to, C, segs, coded.data()));
+        HIPC(done(RG_ZRL));
+    }
+    BWTS_TRY(mtf_impl(ctx, from, C, to, true, segs));
+    HIPC(done(RG_MTF));
+    BWTS_TRY(seg ? inverse_segments_impl(ctx, from, C, to) : inverse_device_impl(ctx, from, C, to));
+    HIPC(done(RG_INVERSE));
+    if (planes) {
+        BWTS_TRY(planes_impl(ctx, from, C, H.width, to, true, segs));
+        HIPC(done(RG_JOIN));
+    }
+    BWTS_TRY(crc_impl(ctx, from, C, segs, got.data()));
+    rep[6] |= RG_CRC;
+    if (memcmp(got.data(), want.data(), (size_t)nb * sizeof(u32)) != 0) return BWTS_E_CHECKSUM;
+    BWTS_TRY(copy_pieces_impl(ctx, from, C, P.out.data(), P.out.size(), d_out));
+    rep[6] |= RG_CUT;
+    *out_bytes = sum;
     return BWTS_OK;
 }

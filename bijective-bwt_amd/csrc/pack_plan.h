@@ -3,6 +3,7 @@
 // valid.  Plain C++ with no dependency but ec_plan.h and planes_plan.h: crc.hip, pack.hip, the host side of the calls and a stand-alone host program
 // (tests/pack_plan_check.cc, built with the sanitizers) all compile this file.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include "ec_plan.h"
 #include "planes_plan.h"
@@ -200,4 +201,101 @@ EC_HD int pack_directory_check(const uint8_t *dir, PackHeader &H, uint64_t in_by
     *frame_bytes = total;
     H.width = width;
     return PACK_OK;
+}
+
+// ---- ranges: which blocks a list of byte ranges touches, and what is moved for them (bwts_unpack_ranges) ----
+#include <vector>
+
+#define PACK_ARG -1                      // (the values of BWTS_E_ARG and BWTS_E_SPACE; pack.hip asserts that they are)
+#define PACK_SPACE -9
+#define PACK_MAX_RANGES (1ull << 20)
+#define PACK_MAX_RANGE_BYTES (1ull << 32)
+// copy_pieces_kernel (pieces.hip) cuts a piece into tiles of T = 16 KiB, no tile across a piece: a workgroup of 256 threads makes four
+// aligned 16-byte stores per thread and tile.  The first tile of a piece is shorter by `lead`, its destination address modulo
+// PIECES_LINE, so that every later tile begins on such a boundary of the destination and no store of a wave straddles a line.
+#define PIECES_LOG_T 14u
+#define PIECES_T (1u << PIECES_LOG_T)
+#define PIECES_LINE 256u
+EC_HD uint64_t pieces_first_bytes(uint64_t lead) { return PIECES_T - lead; }
+EC_HD uint64_t pieces_tiles(uint64_t bytes, uint64_t lead)
+{
+    const uint64_t f = pieces_first_bytes(lead);
+    return bytes <= f ? 1u : 1u + ((bytes - f + PIECES_T - 1u) >> PIECES_LOG_T);
+}
+
+struct PackRange { uint64_t offset, bytes; };           // bwts_range: bytes [offset, offset + bytes) of the unpacked input
+struct PackPiece { uint64_t src, dst, bytes; };         // bytes [src, src + bytes) of one buffer to [dst, dst + bytes) of another
+struct PackRun { uint64_t first, blocks; };             // blocks [first, first + blocks) of the frame
+
+// The ranges of a call against a judged header: PACK_ARG, PACK_RANGE, PACK_SPACE in this order, else PACK_OK and *sum, the bytes of all
+// ranges.  No sum can overflow: at most 2^20 ranges count, each of at most n <= 2^32 bytes.
+static inline int pack_ranges_check(const PackHeader &H, const PackRange *r, uint64_t count, uint64_t out_cap, uint64_t *sum)
+{
+    if (!r || count == 0) return PACK_ARG;
+    if (count > PACK_MAX_RANGES) return PACK_RANGE;
+    for (uint64_t i = 0; i < count; i++)
+        if (r[i].bytes == 0) return PACK_ARG;
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < count; i++) {
+        if (r[i].bytes > H.n || r[i].offset > H.n - r[i].bytes) return PACK_RANGE;      // (by subtraction: offset + bytes may wrap)
+        total += r[i].bytes;
+    }
+    if (total > PACK_MAX_RANGE_BYTES) return PACK_RANGE;
+    if (total > out_cap) return PACK_SPACE;
+    *sum = total;
+    return PACK_OK;
+}
+
+// What a call with these ranges decodes and moves.  The covered blocks are those a range touches, as sorted maximal runs; they are
+// decoded into one buffer, block behind block in the frame's order (covered bytes in all), so every range is one piece of that buffer.
+struct PackRangesPlan {
+    std::vector<PackRun> runs;
+    std::vector<PackPiece> streams;     // one per run: src in the frame, dst in the gathered streams
+    std::vector<PackPiece> out;         // one per range: src in the covered-block buffer, dst in the call's output
+    std::vector<uint64_t> blocks;       // the covered blocks, ascending
+    uint64_t covered_bytes, stream_bytes, coded_bytes, out_bytes;
+};
+
+// H and dir have passed pack_header_check and pack_directory_check, the ranges pack_ranges_check.  Nothing here can overflow: the
+// directory check has held the sum of all stream_bytes against the frame's length, coded_bytes against the blocks' lengths, and the
+// blocks' lengths add up to n <= 2^32; the ranges' sum is bounded by their check.
+static inline void pack_ranges_plan(const PackHeader &H, const uint8_t *dir, const PackRange *r, uint64_t count, PackRangesPlan *P)
+{
+    const uint64_t entry = pack_entry_bytes(H.version);
+    // how many ranges begin in a block minus how many end in the one before: a running sum above zero marks a covered block
+    std::vector<int32_t> step((size_t)H.nblk + 1, 0);
+    for (uint64_t i = 0; i < count; i++) {
+        step[(size_t)(r[i].offset / H.B)]++;
+        step[(size_t)((r[i].offset + r[i].bytes - 1u) / H.B) + 1]--;
+    }
+    std::vector<uint64_t> at((size_t)H.nblk, 0);         // where a covered block begins in the covered-block buffer
+    P->runs.clear(); P->streams.clear(); P->out.clear(); P->blocks.clear();
+    P->covered_bytes = P->stream_bytes = P->coded_bytes = P->out_bytes = 0;
+    uint64_t frame_at = pack_fixed_bytes_v(H.version, H.nblk);
+    int64_t open = 0;
+    bool in_run = false;
+    for (uint64_t b = 0; b < H.nblk; b++) {
+        const uint64_t sb = pack_le64(dir + entry * b), len = pack_block_at(H.n, H.B, b);
+        open += step[(size_t)b];
+        if (open > 0) {
+            if (!in_run) {
+                P->runs.push_back(PackRun{b, 0});
+                P->streams.push_back(PackPiece{frame_at, P->stream_bytes, 0});
+            }
+            P->runs.back().blocks++;
+            P->streams.back().bytes += sb;
+            P->blocks.push_back(b);
+            at[(size_t)b] = P->covered_bytes;
+            P->covered_bytes += len;
+            P->stream_bytes += sb;
+            P->coded_bytes += H.version != PACK_VERSION ? pack_le64(dir + entry * b + 16) : len;
+        }
+        in_run = open > 0;
+        frame_at += sb;
+    }
+    for (uint64_t i = 0; i < count; i++) {
+        const uint64_t b = r[i].offset / H.B;
+        P->out.push_back(PackPiece{at[(size_t)b] + (r[i].offset - b * H.B), P->out_bytes, r[i].bytes});
+        P->out_bytes += r[i].bytes;
+    }
 }

@@ -10,7 +10,7 @@
 //          tile's interleaved bytes go out from there.
 // Neither side of either direction is aligned but by luck (a plane starts at base + k q, a segment anywhere), and no access wider than
 // a byte is ever made at an address that is not a multiple of its width:
-//   reading  planes_load16 reads the two aligned 16-byte pieces around an address and shifts the bytes into place in registers; a
+//   reading  planes_load16 (load16.h) reads the two aligned 16-byte pieces around an address and shifts the bytes into place in registers; a
 //            piece that does not lie inside the call's input is put together from the single bytes that do (the first and the last
 //            piece of the whole input at most), so nothing outside the input is read.
 //   writing  planes_stream_store sends a piece of len bytes from LDS: single bytes up to the destination's first 16-byte boundary (at
@@ -19,6 +19,7 @@
 // The tail of a string (its last L mod w bytes) is copied by the workgroup of its last tile.
 #include "internal.h"
 #include "device_utils.h"
+#include "load16.h"
 #include "planes_plan.h"
 #include "../../include/bwts_planes.h"
 
@@ -63,41 +64,6 @@ __device__ __forceinline__ PlanesTile planes_tile(const PlanesSegs &S, u64 t)
     R.elems = planes_tile_elems(R.len, W, j);
     R.last = j + 1 == planes_tiles(R.len, W);
     return R;
-}
-
-// the 16 bytes at byte sh (0 .. 15) of the 32 bytes a, b
-__device__ __forceinline__ uint4 planes_funnel(uint4 a, uint4 b, u32 sh)
-{
-    const u32 D[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    const u32 bytes = sh & 3u, words = sh >> 2;
-    u32 e[7], o[4];
-#pragma unroll
-    for (int j = 0; j < 7; j++) e[j] = __builtin_amdgcn_alignbyte(D[j + 1], D[j], bytes);
-#pragma unroll
-    for (int j = 0; j < 4; j++) o[j] = words == 0 ? e[j] : (words == 1 ? e[j + 1] : (words == 2 ? e[j + 2] : e[j + 3]));
-    return make_uint4(o[0], o[1], o[2], o[3]);
-}
-
-// the aligned 16-byte piece at a, of which only bytes inside [lo, hi) are read (the others are 0)
-__device__ __forceinline__ uint4 planes_piece(const u8 *a, const u8 *lo, const u8 *hi)
-{
-    const uintptr_t x = (uintptr_t)a, l = (uintptr_t)lo, h = (uintptr_t)hi;
-    if (x >= l && x + 16 <= h) return *(const uint4 *)a;
-    u32 w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int i = 0; i < 16; i++)
-        if (x + i >= l && x + i < h) w[i >> 2] |= (u32)a[i] << (8 * (i & 3));
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// the 16 bytes at p, at any alignment; what lies outside [lo, hi) reads as 0
-__device__ __forceinline__ uint4 planes_load16(const u8 *p, const u8 *lo, const u8 *hi)
-{
-    const u32 sh = (u32)((uintptr_t)p & 15);
-    const u8 *a = p - sh;
-    const uint4 x = planes_piece(a, lo, hi);
-    if (sh == 0) return x;
-    return planes_funnel(x, planes_piece(a + 16, lo, hi), sh);
 }
 
 // one word from byte ba of a, byte bb of b, byte bc of c and byte bd of d (constants after unrolling): three byte permutes

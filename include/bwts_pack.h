@@ -114,6 +114,38 @@ int bwts_pack_planes_device(bwts_ctx *ctx, uint32_t width, const void *d_in, uin
 int bwts_pack_planes(bwts_ctx *ctx, uint32_t width, const uint8_t *in, uint64_t n, uint64_t block_bytes, uint8_t *out, uint64_t out_cap,
                      uint64_t *out_bytes);
 
+/*
+ * Ranges: bytes [offset, offset + bytes) of the unpacked input, read by decoding only the blocks they touch.
+ *
+ * Results.  They lie back to back in d_out (out) in the order the ranges were given; *out_bytes is their sum.  Ranges may overlap,
+ * repeat and come in any order; a block that several ranges touch is decoded once.
+ * Versions.  All three frame versions are taken; a version-3 block is joined at its width before anything is cut out of it.  A frame
+ * of one block (B = n) is covered whole by any range: the call then costs a full unpack minus the n-byte output.
+ * Frame checks.  Header and the whole directory are judged exactly as bwts_unpack_device judges them, in the same order and with the
+ * same codes (every block's entry, touched or not), and the frame must end at in_bytes.
+ * Range checks.  Only after the frame checks are the ranges judged, in this order: BWTS_E_ARG for ranges == NULL, count == 0 or a
+ * range with bytes == 0 (count > 2^20 is BWTS_E_RANGE, decided before the ranges are read); BWTS_E_RANGE for a range whose
+ * offset + bytes overflows or exceeds n, or a sum of bytes above 2^32; BWTS_E_SPACE for a sum above out_cap.  All of these are
+ * decided before the device touches a stream or d_out.
+ * What is read.  Only the streams of covered blocks.  Every covered block's CRC-32 is held against the directory before the ranges
+ * are cut out: a mismatch is BWTS_E_CHECKSUM; the coder's and the zero-run decoder's BWTS_E_FORMAT pass through, and a covered
+ * stream whose header names another length than the directory's is BWTS_E_FORMAT.  Damage inside a block that no range touches
+ * goes unnoticed: that is the point of the call, and a caller who wants the whole frame vouched for unpacks it.
+ * Device form.  BWTS_E_ARG on NULL pointers, in_bytes == 0, a d_in that is not 16-byte aligned, or d_in and d_out that overlap; d_out
+ * may have any alignment.  d_out is written by the last step alone, the cut-out behind the checksums: a call that fails has written
+ * nothing to d_out.
+ * Host form.  It leaves out as it was after any failure.  Only header, directory and the covered blocks' streams cross to the device.
+ * Memory.  The bytes between the stages live in the two blocks that pack keeps with the context, sized for the covered bytes C (the
+ * sum of the covered blocks' lengths; the gathered streams where those are longer), not for n.  bwts_last_timings: n holds C, total_ms
+ * is filled, the kernels are accounted under BWTS_K_OTHER.
+ */
+typedef struct { uint64_t offset, bytes; } bwts_range;      /* bytes [offset, offset + bytes) of the unpacked input */
+
+int bwts_unpack_ranges_device(bwts_ctx *ctx, const void *d_in, uint64_t in_bytes, const bwts_range *ranges, uint64_t count,
+                              void *d_out, uint64_t out_cap, uint64_t *out_bytes);
+int bwts_unpack_ranges(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const bwts_range *ranges, uint64_t count,
+                       uint8_t *out, uint64_t out_cap, uint64_t *out_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,26 @@ int bwts_debug_zrl_plan(uint64_t n, uint64_t out[2]);
  * of 2, 4 or 8.  out = {T, the tile size in bytes (4096 elements); tiles = ceil(n / T); q, the whole elements; the bytes of the tail}.
  * Returns 0, -1 on a bad argument. */
 int bwts_debug_planes_plan(uint64_t n, uint32_t width, uint64_t out[4]);
+/* Pure arithmetic, no context and no device: what a range read of a frame (bwts_pack.h: bwts_unpack_ranges) would decode and move for `count` ranges
+ * (offset, bytes pairs, as bwts_range) of the frame of in_bytes bytes whose first 32 + entry x nblk bytes are at `frame` (nothing
+ * behind them is read) into an output of out_cap bytes.  Returns the call's code for frame and ranges (0, or the negative code of
+ * the first check that refuses), -1 also for NULL pointers.  On 0, out = {0 covered blocks, 1 runs, 2 C: the covered bytes, 3 the
+ * covered streams' bytes, 4 the covered coded_bytes (version 1: C), 5 the output's bytes, 6 T: the tile of copy_pieces_kernel in
+ * bytes, 7 the words the lists take: 2 runs + 3 runs + 3 count}, and, where cap_words holds them, lists = the runs as (first block,
+ * blocks), then one stream piece per run as (offset in the frame, offset in the gathered streams, bytes), then one output piece per
+ * range as (offset in the covered-block buffer, offset in the output, bytes). */
+int bwts_debug_unpack_ranges_plan(const uint8_t *frame, uint64_t in_bytes, const uint64_t *ranges, uint64_t count, uint64_t out_cap,
+                                  uint64_t out[8], uint64_t *lists, uint64_t cap_words);
+/* What the most recent bwts_unpack_ranges / _device on the context did (host memory, no device work; all 0 before any call and
+ * after one that was refused by the frame checks).  out = {0 covered blocks, 1 runs, 2 C, 3 stream bytes read, 4 the stream gather
+ * ran, 5 output pieces, 6 stages run, a bit each: 1 gather, 2 decode, 4 zero-run decode, 8 inverse move-to-front, 16 inverse
+ * transform, 32 join, 64 checksums, 128 cut-out; 7 the single-input stages were used (one covered block)}. */
+int bwts_debug_unpack_ranges_report(bwts_ctx *ctx, uint64_t out[8]);
+/* copy_pieces_kernel alone: `count` pieces as (offset in d_src, offset in d_dst, bytes) triples.  BWTS_E_ARG, before anything is
+ * launched, for NULL pointers, count == 0, a piece of no bytes, a piece that leaves either buffer, or two pieces that share a
+ * destination byte. */
+int bwts_debug_copy_pieces(bwts_ctx *ctx, const void *d_src, uint64_t src_bytes, const uint64_t *pieces, uint64_t count, void *d_dst,
+                           uint64_t dst_bytes);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,7 @@ repo-root ``__graft_entry__`` or ``importlib`` (see ``tests/conftest.py``).
 """
 import ctypes
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -76,7 +77,7 @@ TEST_EXPORTS = [
     "bwts_debug_chunk_plan", "bwts_debug_chunk_plan_target", "bwts_debug_inverse_arena", "bwts_debug_forward_arena", "bwts_debug_wide_forward_arena", "bwts_debug_inverse_report",
     "bwts_debug_forward_report", "bwts_debug_segments_plan", "bwts_debug_segments_report",
     "bwts_debug_mtf_plan", "bwts_debug_last_spans", "bwts_debug_ec_plan", "bwts_debug_crc_plan",
-    "bwts_debug_zrl_plan", "bwts_debug_planes_plan",
+    "bwts_debug_zrl_plan", "bwts_debug_planes_plan", "bwts_debug_key_plan",
     "bwts_debug_unpack_ranges_plan", "bwts_debug_unpack_ranges_report", "bwts_debug_copy_pieces",
 ]
 # bwts_debug_unpack_ranges_report: the words of the record, and the stages by their bits
@@ -253,6 +254,7 @@ def lib():
         L.bwts_debug_lyndon.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
         L.bwts_debug_chunk_plan.argtypes = [u64, u64, ctypes.POINTER(u64)]
         L.bwts_debug_chunk_plan_target.argtypes = [u64, u64, ctypes.c_uint32, ctypes.POINTER(u64)]
+        L.bwts_debug_key_plan.argtypes = [vp, u64, i32, i32, i32, i32, i32, vp, ctypes.POINTER(u64), vp, vp]
         L.bwts_debug_inverse_arena.argtypes = [u64, i32, i32, ctypes.POINTER(u64)]
         L.bwts_debug_forward_arena.argtypes = [u64, ctypes.POINTER(u64)]
         L.bwts_debug_wide_forward_arena.argtypes = [u64, i32, i32, u64, ctypes.POINTER(u64)]
@@ -820,6 +822,54 @@ def debug_segments_plan(lengths):
         raise BwtsError(-1, "bad segment lengths")
     d = _segments_words(buf)
     d["arena_bytes"] = int(buf[7])
+    return d
+
+
+# bwts_debug_key_plan: the words of the answer ("avg" is a double's bit pattern), and the value of a knob that is not set
+KEY_PLAN_FIELDS = ["sigma", "bits", "pad_add", "msym", "key_bits", "varlen", "hstep", "patch_span", "few_ties", "lmax", "kb_iid",
+                   "passes_fixed", "passes_var", "avg", "code_built", "kb_var"]
+KEY_KNOB_ABSENT = -2 ** 31
+
+
+def debug_key_plan(hist, n=None, reserve_pad=False, key_symbols=None, varlen=None, key_bits=None, kb_emp=0, partners_of=None):
+    """The round-0 key layout a sort picks for a text with this byte histogram (bwts_debug_key_plan: csrc/key_plan.h as host arithmetic,
+    no context, no device).  hist: 256 counts, n their sum (the default).  key_symbols, varlen, key_bits: the knobs BWTS_KEY_SYMBOLS,
+    BWTS_VARLEN and BWTS_KEY_BITS as numbers or as the text the environment would hold, None for one that is not set.  kb_emp and
+    partners_of (65 numbers, negative where the sample has no say): what the key sample found.  Without them the answer is the engine's
+    for n < 2^22; from there on the engine may widen the key by its sample.  Returns the dict of KEY_PLAN_FIELDS (flags as bool, "avg"
+    as a float) with "codes": the byte -> fixed-width code table, "vlen" and "vcode": length and bits of every byte's code word (all 0
+    when no alphabetic code was built)."""
+    h = np.ascontiguousarray(hist, dtype=np.uint64)
+    if h.size != 256:
+        raise BwtsError(-1, "a histogram has 256 counts")
+
+    def knob(v, is_varlen=False):
+        if v is None:
+            return KEY_KNOB_ABSENT
+        if isinstance(v, str):                     # what atoi makes of the text; BWTS_VARLEN looks at the first character alone
+            if is_varlen:
+                return {"0": 0, "1": 1}.get(v[:1], 2)
+            m = re.match(r"\s*[+-]?\d+", v)
+            return int(m.group()) if m else 0
+        return int(v)
+
+    pp = None
+    if partners_of is not None:
+        pp = np.ascontiguousarray(partners_of, dtype=np.float64)
+        if pp.size != 65:
+            raise BwtsError(-1, "partners_of has 65 entries")
+    out = (ctypes.c_uint64 * len(KEY_PLAN_FIELDS))()
+    codes, vtab = np.zeros(256, dtype=np.uint8), np.zeros(256, dtype=np.uint64)
+    rc = lib().bwts_debug_key_plan(h.ctypes.data, int(h.sum()) if n is None else int(n), int(bool(reserve_pad)), knob(key_symbols),
+                                   knob(varlen, True), knob(key_bits), int(kb_emp), pp.ctypes.data if pp is not None else None, out,
+                                   codes.ctypes.data, vtab.ctypes.data)
+    if rc < 0:
+        raise BwtsError(-1, "bad histogram or length")
+    d = {f: int(out[i]) for i, f in enumerate(KEY_PLAN_FIELDS)}
+    d["avg"] = float(np.array([d["avg"]], dtype=np.uint64).view(np.float64)[0])
+    for f in ("varlen", "few_ties", "code_built"):
+        d[f] = bool(d[f])
+    d["codes"], d["vlen"], d["vcode"] = codes, (vtab >> np.uint64(32)).astype(np.int64), (vtab & np.uint64(0xffffffff)).astype(np.int64)
     return d
 
 

@@ -6,6 +6,7 @@
 #include "zrl_plan.h"
 #include "planes_plan.h"
 #include "pack_plan.h"
+#include "key_plan.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -102,6 +103,38 @@ extern "C" int bwts_debug_chunk_plan_target(uint64_t a0, uint64_t a_chunks, uint
 extern "C" int bwts_debug_chunk_plan(uint64_t a0, uint64_t a_chunks, uint64_t out[4])
 {
     return bwts_debug_chunk_plan_target(a0, a_chunks, CH_CHUNK_TARGET, out);
+}
+
+// the round-0 key layout of a sort from its byte histogram (key_plan.h): no context, no device
+extern "C" int bwts_debug_key_plan(const uint64_t hist[256], uint64_t n, int reserve_pad, int key_symbols, int varlen, int key_bits,
+                                   int kb_emp, const double *partners_of, uint64_t out[BWTS_KEY_PLAN_WORDS], uint8_t codes[256],
+                                   uint64_t vtab[256])
+{
+    static_assert(BWTS_KEY_KNOB_ABSENT == KEY_KNOB_ABSENT, "the value bwts_test.h states");
+    if (!hist || !out || !codes || !vtab || n == 0) return -1;
+    u64 sum = 0;
+    for (int c = 0; c < 256; c++) {
+        if (hist[c] > n - sum) return -1;
+        sum += hist[c];
+    }
+    if (sum != n) return -1;
+    KeyKnobs knobs;
+    knobs.key_symbols = key_symbols; knobs.varlen = varlen; knobs.key_bits = key_bits;
+    KeySample sample;
+    sample.kb_emp = kb_emp;
+    if (partners_of) memcpy(sample.partners_of, partners_of, sizeof sample.partners_of);
+    KeyPlan P;
+    key_plan(hist, n, reserve_pad != 0, knobs, sample, &P);
+    const Alphabet &al = P.al;
+    u64 avg_bits;
+    memcpy(&avg_bits, &P.avg, 8);
+    const u64 words[BWTS_KEY_PLAN_WORDS] = {(u64)al.sigma, (u64)al.bits, (u64)al.pad_add, (u64)al.msym, (u64)al.key_bits, al.varlen ? 1u : 0u,
+                                            (u64)al.hstep, (u64)al.patch_span, al.few_ties ? 1u : 0u, (u64)P.lmax, (u64)P.kb_iid,
+                                            (u64)P.passes_fixed, (u64)P.passes_var, avg_bits, P.code_built ? 1u : 0u, (u64)P.kb};
+    memcpy(out, words, sizeof words);
+    memcpy(codes, P.codes, 256);
+    memcpy(vtab, P.vtab, sizeof P.vtab);
+    return 0;
 }
 
 // the move-to-front stage's cut of one input of n bytes: tile size, tiles per group, tiles, groups.  No context, no device

@@ -15,6 +15,7 @@
 #include "internal.h"
 #include "device_utils.h"
 #include "scan_templ.h"
+#include "key_plan.h"
 #include "../../include/bwts_test.h"
 
 #include <math.h>
@@ -36,23 +37,9 @@
 #define   CNT_LYN_K    (SM_COUNTERS + 5)
 #define   CNT_LYN_OVF  (SM_COUNTERS + 6)
 
-struct Alphabet {
-    int sigma;      // distinct byte values present
-    int bits;       // bits per symbol code
-    int msym;       // symbols packed into a round-0 key
-    int key_bits;   // bits * msym (fixed-width codes) or the chosen key width (variable-length codes)
-    int pad_add;    // added to a table code by the kernels (9-bit padded alphabet only)
-    bool varlen;    // order-preserving variable-length codes (optimal alphabetic tree) instead of fixed-width ones
-    int hstep;      // symbols every key is guaranteed to cover: the step of round 1 (msym, or key_bits / longest code)
-    int patch_span; // positions in front of a factor's end whose key wraps around (msym - 1, or 64)
-    bool few_ties;  // the model of this key, and the key sample where one was taken, expect at most n / 64 positions tied after round 0
-};
 #define SM_DGCNT  2816      // 8 + 1024 words: counters of the group-local dense rounds (dense_round_kernel)
 #define SM_SEGCNT 2560      // 256 words: large-group element counts of seg_small_sort_kernel (spread: one address would serialise)
 #define SM_VTAB 2048        // 256 words: (length << 32) | code of each byte value (variable-length codes)
-#define VL_MAXLEN 24        // longest code the variable-length key builder accepts
-
-static int bitlen_u64(u64 x) { int b = 0; while (x) { b++; x >>= 1; } return b; }
 
 // ------------------------------------------------------------------------------------
 // byte histogram (also used by the inverse: unbwts.c:34-36)
@@ -111,140 +98,10 @@ static int read_histogram(bwts_ctx *ctx, const u8 *d_T, u64 n)
     return read_small(ctx, SM_HIST, 256);
 }
 
-// Symbols per round-0 key.  A key only has to separate most positions: for an i.i.d. source with collision entropy
-// H2 bits per symbol, about n * 2^(log2 n - m * H2) positions stay tied after m symbols.  Taking the smallest m that
-// keeps that below ~0.4 % of n saves whole radix passes on high-entropy inputs (uniform bytes: 40 instead of 64 key
-// bits at 2^28); a wrong guess (real text is not i.i.d.) only moves work into the later rounds, never changes the result.
-static int pick_key_symbols(const u64 *hist, u64 n, int bits, int max_sym)
-{
-    double sum2 = 0.0;
-    for (int c = 0; c < 256; c++) { const double p = (double)hist[c] / (double)n; sum2 += p * p; }
-    if (sum2 >= 1.0) return max_sym;                            // one symbol: nothing separates
-    const double H2 = -log2(sum2);
-    const double need = log2((double)n) + 8.0;                  // bits of collision entropy wanted in a key
-    int m = (int)ceil(need / H2 - 0.05);                        // a hair of slack: exactly-uniform alphabets land on the boundary
-    // whole passes are what counts: use every symbol that fits in the same number of 8-bit passes
-    if (m < 1) m = 1;
-    if (m > max_sym) return max_sym;
-    const int passes = (m * bits + 7) / 8;
-    while (m < max_sym && ((m + 1) * bits + 7) / 8 <= passes) m++;
-    return m;
-}
-
 #define KEY_SAMPLES (1u << 17)
 #define CNT_SAMPLE (SM_COUNTERS + 16)      // 5 words: adjacent sample keys agreeing on their first 24/32/40/48/56 bits
 __global__ void sample_keys_kernel(const u8 *T, u64 n, const u64 *vtab, u32 samples, u64 *out);
 __global__ void count_prefix_matches_kernel(const u64 *keys, u32 samples, unsigned long long *counters);
-
-// Optimal alphabetic (order-preserving prefix) code for the byte histogram: the classic interval DP with Knuth's
-// monotone-root bound, O(sigma^2).  Order-preserving means that comparing concatenated code words bit by bit is
-// comparing the symbol strings, so packed code bits sort like the text does -- but frequent symbols take fewer bits,
-// so a key of B bits separates positions about as well as B bits of entropy would.  Returns the longest code length.
-static int build_alphabetic_code(const u64 *hist, u64 n, u32 *code, u8 *len, double *avg_len, double *entropy, double smooth_scale = 1.0)
-{
-    // (heap, not static: contexts on different host threads may be here at the same time)
-    std::vector<double> Cv(256 * 256);
-    std::vector<u16> Rv(256 * 256);
-    double (*C)[256] = (double (*)[256])Cv.data();
-    u16 (*R)[256] = (u16 (*)[256])Rv.data();
-    int sym[256], sigma = 0;
-    double w[256], pre[257];
-    for (int c = 0; c < 256; c++) { code[c] = 0; len[c] = 0; if (hist[c]) sym[sigma++] = c; }
-    // keeps rare symbols' codes short enough for the key builder; a larger scale flattens the tree (shorter longest code)
-    const double smooth = ((double)(n >> 14) + 1.0) * smooth_scale;
-    pre[0] = 0;
-    for (int i = 0; i < sigma; i++) { w[i] = (double)hist[sym[i]] + smooth; pre[i + 1] = pre[i] + w[i]; }
-    if (sigma == 1) { len[sym[0]] = 1; *avg_len = 1; *entropy = 0; return 1; }
-    for (int i = 0; i < sigma; i++) { C[i][i] = 0; R[i][i] = (u16)i; }
-    for (int L = 2; L <= sigma; L++) {
-        for (int i = 0; i + L - 1 < sigma; i++) {
-            const int j = i + L - 1;
-            int lo = R[i][j - 1], hi = R[i + 1][j];
-            if (lo < i) lo = i;
-            if (hi > j - 1) hi = j - 1;
-            if (hi < lo) hi = lo;
-            double best = 1e300; int arg = lo;
-            for (int k = lo; k <= hi; k++) {
-                const double v = C[i][k] + C[k + 1][j];
-                if (v < best) { best = v; arg = k; }
-            }
-            C[i][j] = best + (pre[j + 1] - pre[i]);
-            R[i][j] = (u16)arg;
-        }
-    }
-    // walk the tree: left = 0, right = 1
-    struct Item { int i, j, depth; u32 prefix; } stack[512];
-    int sp = 0, lmax = 0;
-    stack[sp++] = Item{0, sigma - 1, 0, 0u};
-    while (sp) {
-        const Item it = stack[--sp];
-        if (it.i == it.j) {
-            len[sym[it.i]] = (u8)it.depth; code[sym[it.i]] = it.prefix;
-            if (it.depth > lmax) lmax = it.depth;
-            continue;
-        }
-        if (it.depth >= 31) return 99;
-        const int k = R[it.i][it.j];
-        stack[sp++] = Item{k + 1, it.j, it.depth + 1, (it.prefix << 1) | 1u};
-        stack[sp++] = Item{it.i, k, it.depth + 1, it.prefix << 1};
-    }
-    double al = 0, h = 0;
-    for (int i = 0; i < sigma; i++) {
-        const double p = (double)hist[sym[i]] / (double)n;
-        al += p * len[sym[i]];
-        h -= p * log2(p);
-    }
-    *avg_len = al; *entropy = h;
-    return lmax;
-}
-
-// Fixed-width codes: the byte -> code table, sigma, bits per code.  The cyclic sort uses codes 0..sigma-1; the suffix (non-cyclic)
-// sort reserves code 0 for "past the end" and uses 1..sigma (reserve_pad).
-static void fixed_codes(const u64 *hist, bool reserve_pad, u8 codes[256], Alphabet *al)
-{
-    int sigma = 0;
-    for (int c = 0; c < 256; c++) codes[c] = hist[c] ? (u8)(sigma++ + (reserve_pad ? 1 : 0)) : (u8)0;   // sigma == 256 with pad handled below
-    const int ncodes = sigma + (reserve_pad ? 1 : 0);
-    al->sigma = sigma;
-    al->bits = bitlen_u64((u64)(ncodes > 1 ? ncodes - 1 : 1));
-    al->pad_add = 0;
-    if (al->bits > 8) {
-        // 256 symbols + pad: 9-bit codes; the u8 table cannot hold code 256, so the kernels add
-        // the +1 themselves (the table then holds 0..255)
-        for (int c = 0, s = 0; c < 256; c++) if (hist[c]) codes[c] = (u8)(s++);
-        al->pad_add = 1;
-    }
-}
-
-// Width of a variable-length key: the smallest whole number of bytes B for which an i.i.d. source with this histogram leaves at most
-// ~0.8 % of the positions tied.  share[b] = probability that two independent positions agree on the first b
-// bits of their code streams: both start with the same symbol and agree on the rest, or their first code
-// words are both longer than b bits and agree on those b bits.  Host arithmetic only; share[0..64] is left for the caller.
-static int iid_key_bits(const u64 *hist, const u8 *vlen, const u32 *vcode, u64 n, double share[65])
-{
-    double p[256];
-    for (int c = 0; c < 256; c++) p[c] = (double)hist[c] / (double)n;
-    share[0] = 1.0;
-    for (int b = 1; b <= 64; b++) {
-        double s = 0.0;
-        for (int c = 0; c < 256; c++)
-            if (vlen[c] && vlen[c] <= b) s += p[c] * p[c] * share[b - vlen[c]];
-        // code words longer than b bits that share their first b bits are neighbours in symbol order
-        // (alphabetic and prefix-free), so the partial term is a sum of squared run masses
-        double mass = 0.0; u32 cur = 0; bool open = false;
-        for (int c = 0; c < 256; c++) {
-            if (!vlen[c] || vlen[c] <= b) continue;
-            const u32 pc = vcode[c] >> (vlen[c] - b);
-            if (open && pc == cur) mass += p[c];
-            else { s += mass * mass; mass = p[c]; cur = pc; open = true; }
-        }
-        s += mass * mass;
-        share[b] = s;
-    }
-    for (int b = 32; b <= 64; b += 8)
-        if ((double)n * share[b] <= 1.0 / 128.0) return b;
-    return 64;
-}
 
 // The model knows nothing about repeated phrases.  Where the input is large enough to matter, sort the keys
 // of 2^17 sampled positions and count neighbours that agree on their first B bits: if the sample shows
@@ -270,74 +127,32 @@ static int sampled_key_bits(bwts_ctx *ctx, const u8 *d_T, u64 n, const SortBufs 
         const double m = (double)ctx->h_small[CNT_SAMPLE + w];
         const double partners = m >= 8.0 ? (double)n * m / pairs : (double)n * share[b];   // few hits: trust the model
         partners_of[b] = partners;
-        if (*kb_emp == 64 && 1.0 - exp(-partners) <= 1.0 / 64.0) *kb_emp = b;
+        if (*kb_emp == 64 && key_few_ties(partners)) *kb_emp = b;
     }
     return BWTS_OK;
 }
 
-// The alphabet and the round-0 key of a sort, from the histogram in h_small.  The sampled measurement needs both d_T and scratch.
+// The alphabet and the round-0 key of a sort, from the histogram in h_small: key_plan.h decides, this adds the sampled measurement
+// (it needs both d_T and scratch) and the copies to the device.
 static int set_alphabet(bwts_ctx *ctx, bool reserve_pad, u64 n, Alphabet *al, const u8 *d_T = nullptr, const SortBufs *scratch = nullptr)
 {
     const u64 *hist = ctx->h_small + SM_HIST;
-    u8 codes[256];
-    fixed_codes(hist, reserve_pad, codes, al);
-    const int bits = al->bits;
-    int msym = pick_key_symbols(hist, n, bits, 64 / bits);
-    const char *env = bwts_knob(ctx, "BWTS_KEY_SYMBOLS");              // tuning / test knob: force the symbol count (0 = maximum)
-    if (env) { int v = atoi(env); if (v >= 1 && v <= 64 / bits) msym = v; else if (v == 0) msym = 64 / bits; }
-    al->msym = al->hstep = msym; al->key_bits = bits * msym; al->varlen = false; al->patch_span = msym - 1;
-    // tied after round 0, as pick_key_symbols models it: a position meets n * (sum of p^2)^msym others with its key
-    const auto few = [](double partners) { return 1.0 - exp(-partners) <= 1.0 / 64.0; };
-    const auto fixed_partners = [&](int m) {
-        double sum2 = 0.0;
-        for (int c = 0; c < 256; c++) { const double p = (double)hist[c] / (double)n; sum2 += p * p; }
-        return (double)n * pow(sum2, (double)m);
-    };
-    al->few_ties = few(fixed_partners(msym));
-    // variable-length codes when they save whole radix passes (skewed alphabets: text); the suffix sort of the general
-    // Lyndon path keeps fixed-width codes with the pad symbol
-    const char *vl = bwts_knob(ctx, "BWTS_VARLEN");                    // 0 = never, 1 = always (tests), unset = when it pays
-    u32 vcode[256]; u8 vlen[256];
-    double avg = 0, ent = 0;
-    const bool try_vl = !reserve_pad && al->sigma > 1 && !(vl && vl[0] == '0') && !(env && !vl);
-    const int lmax = try_vl ? build_alphabetic_code(hist, n, vcode, vlen, &avg, &ent) : 0;
-    if (try_vl && lmax <= VL_MAXLEN) {
-        u64 *vtab = ctx->h_small + SM_VTAB;          // (length << 32) | code of each byte value
-        for (int c = 0; c < 256; c++) vtab[c] = ((u64)vlen[c] << 32) | vcode[c];
-        double share[65], partners_of[65];
-        for (int b = 0; b <= 64; b++) partners_of[b] = -1.0;              // (no sample, or none at this width: the model)
-        int kb = iid_key_bits(hist, vlen, vcode, n, share), kb_emp = 0;
-        if (d_T && scratch && n >= (1ull << 22)) BWTS_TRY(sampled_key_bits(ctx, d_T, n, *scratch, vtab, share, &kb_emp, partners_of));
-        if (kb_emp > kb) {
-            // Repeats, not entropy, tie these positions, and no key width separates the copies of a long repeat: the
-            // rounds on the tied list will.  Wider keys then only pay where they lengthen the first step (key bits /
-            // longest code word) -- with short code words five digits (the packed passes) already give a step
-            // of four symbols, and three fewer n-sized passes beat the few per cent of extra list elements (text 2^30,
-            // longest code 9 bits: 64 / 48 / 40 / 32 key bits = 169 / 160 / 143 / 159 ms); with long code words (real
-            // text: 205 symbols, 16 bits) every key bit counts (53.6 MiB: 16.1 / 18.5 / 20.6 / 23.3 ms).
-            // (five packed digits whatever the model asks for at this n: text 2^31 / 2^32 with 48 against 40 bits = 334 / 660
-            // against 295 / 590 ms)
-            const int keep = 40;
-            if (keep / lmax >= 4) kb = keep;
-            else {
-                kb = kb_emp;
-                // the fixed-width alternative was sized by the same model: let it use every symbol that fits
-                al->msym = al->hstep = 64 / bits; al->key_bits = bits * al->msym; al->patch_span = al->msym - 1;
-                al->few_ties = few(fixed_partners(al->msym));
-            }
-        }
-        const char *kbe = bwts_knob(ctx, "BWTS_KEY_BITS");
-        if (kbe) { int v = atoi(kbe); if (v >= 8 && v >= lmax && v <= 64) kb = v; }       // (a key must hold its first symbol whole: the first step is >= 1)
-        const int passes_fixed = (al->key_bits + 7) / 8, passes_var = (kb + 7) / 8;
-        // equal pass counts: the variable-length key still holds more symbols when its words are shorter on average
-        if ((vl && vl[0] == '1') || passes_var < passes_fixed || (passes_var == passes_fixed && avg < (double)bits - 0.25)) {
-            al->varlen = true; al->key_bits = kb; al->patch_span = 64;
-            al->few_ties = few(partners_of[kb] >= 0.0 ? partners_of[kb] : (double)n * share[kb]);
-            al->msym = al->hstep = kb / lmax < 1 ? 1 : kb / lmax;
-            HIPC(hipMemcpyAsync(ctx->d_small + SM_VTAB, vtab, 256 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-        }
+    KeyKnobs knobs;
+    knobs.key_symbols = key_knob_int(bwts_knob(ctx, "BWTS_KEY_SYMBOLS"));
+    knobs.varlen = key_knob_varlen(bwts_knob(ctx, "BWTS_VARLEN"));
+    knobs.key_bits = key_knob_int(bwts_knob(ctx, "BWTS_KEY_BITS"));
+    KeyPlan P;
+    key_plan_begin(hist, n, reserve_pad, knobs, &P);
+    KeySample sample;
+    u64 *vtab = ctx->h_small + SM_VTAB;          // (length << 32) | code of each byte value
+    if (P.code_built) {
+        memcpy(vtab, P.vtab, sizeof P.vtab);
+        if (d_T && scratch && n >= (1ull << 22)) BWTS_TRY(sampled_key_bits(ctx, d_T, n, *scratch, vtab, P.share, &sample.kb_emp, sample.partners_of));
     }
-    memcpy(ctx->h_small + SM_CODES, codes, 256);
+    key_plan_finish(&P, sample);
+    *al = P.al;
+    if (al->varlen) HIPC(hipMemcpyAsync(ctx->d_small + SM_VTAB, vtab, 256 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    memcpy(ctx->h_small + SM_CODES, P.codes, 256);
     HIPC(hipMemcpyAsync(ctx->d_small + SM_CODES, ctx->h_small + SM_CODES, 256, hipMemcpyHostToDevice, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));   // h_small is reused by later read-backs
     return BWTS_OK;

@@ -37,6 +37,24 @@ int bwts_debug_lyndon(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint64_t *h_
  * BWTS_CHUNK_TARGET is set); -1 on a target outside that range.  bwts_debug_chunk_plan is the call with 16384. */
 int bwts_debug_chunk_plan(uint64_t a0, uint64_t a_chunks, uint64_t out[4]);
 int bwts_debug_chunk_plan_target(uint64_t a0, uint64_t a_chunks, uint32_t target, uint64_t out[4]);
+/* Pure arithmetic, no context and no device: the round-0 key layout a sort picks for a text of n >= 1 bytes with this byte histogram
+ * (csrc/key_plan.h, the single statement of the rules).  reserve_pad: 0 the cyclic sort, 1 the suffix form (code 0 is "past the end").
+ * key_symbols, varlen, key_bits: the knobs BWTS_KEY_SYMBOLS, BWTS_VARLEN and BWTS_KEY_BITS as numbers, BWTS_KEY_KNOB_ABSENT for one
+ * that is not set (key_symbols and key_bits: atoi of the text; varlen: 0 never, 1 always, any other value: set and neither).  kb_emp
+ * and partners_of (65 doubles, < 0 where the sample has no say; may be NULL): what the key sample of a cyclic sort of n >= 2^22
+ * found, kb_emp = 0 for no sample.  Without a sample the answer is the engine's for n < 2^22 (and for every suffix sort); from 2^22 on
+ * the engine may widen the key by its sample.
+ * out: 0 sigma; 1 bits per fixed-width code; 2 pad_add; 3 msym; 4 key_bits; 5 varlen; 6 hstep; 7 patch_span; 8 few_ties; 9 lmax, the
+ * longest word of the alphabetic code (0: none was built; 99: built and refused); 10 the model's own key width (iid_key_bits; 0
+ * without a code); 11, 12 radix passes of the fixed-width and of the variable-length alternative (12 is 0 where there is none);
+ * 13 the mean code length in bits per symbol, a double's bit pattern; 14 an alphabetic code was built and accepted; 15 the
+ * variable-length alternative's key width after sample and knob.  codes: byte -> fixed-width code.  vtab: (length << 32) | code of
+ * each byte value's word, all 0 when word 14 is 0.
+ * Returns 0; -1 on a NULL pointer (partners_of excepted), n = 0, or a histogram that does not sum to n. */
+#define BWTS_KEY_PLAN_WORDS 16
+#define BWTS_KEY_KNOB_ABSENT (-2147483647 - 1)
+int bwts_debug_key_plan(const uint64_t hist[256], uint64_t n, int reserve_pad, int key_symbols, int varlen, int key_bits, int kb_emp,
+                        const double *partners_of, uint64_t out[BWTS_KEY_PLAN_WORDS], uint8_t codes[256], uint64_t vtab[256]);
 /* Pure arithmetic, no context and no device: how the move-to-front stage (bwts_mtf.h) cuts one input of n >= 1 bytes.  out = {T, the
  * tile size in bytes; G, the tiles one wave composes in the scan's first level; tiles = ceil(n / T); groups = ceil(tiles / G)}.
  * Returns 0, -1 on a bad argument. */

@@ -14,6 +14,7 @@ import pytest
 
 import forward_cases as FC
 import forward_model as M
+import key_model as KM
 import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
@@ -91,10 +92,17 @@ def check_exact(rep, p, t=None):
         assert [int(v) for v in t.round_active[:t.rounds]] == p["round_active"], ([int(v) for v in t.round_active[:t.rounds]], p["round_active"])
 
 
-def check_any_key(rep, mod, t):
-    """No key knob: the heuristics pick the key.  Fixed-width keys are still exact (the caller does that); for variable-length keys
-    the model does not rebuild the code and asserts what holds for any key whose first step is hstep symbols."""
+def check_any_key(rep, mod, t, pkg):
+    """No key knob: the heuristics pick the key.  Fixed-width keys are still exact (the caller does that).  For variable-length keys
+    the model builds every position's key from the code table of the input's histogram (debug_key_plan: csrc/key_plan.h) at the
+    width the engine reports (from 2^22 positions on its key sample may have widened it) and the tied count after round 0 is exact
+    too (tests/key_model.py); the rest is what holds for any key whose first step is hstep symbols."""
     final = mod.final_tied()
+    if rep["varlen"]:
+        plan = pkg.debug_key_plan(np.bincount(mod.x, minlength=256), varlen=1, key_bits=rep["key_bits"])
+        assert (plan["key_bits"], plan["hstep"], plan["msym"], plan["bits"]) == (rep["key_bits"], rep["hstep"], rep["msym"], rep["bits"]), rep
+        assert rep["hstep"] == max(1, rep["key_bits"] // plan["lmax"])
+        assert rep["tied0"] == KM.tied(KM.keys_of_plan(mod.x, mod.starts, plan)), rep["tied0"]
     assert mod.stats(rep["hstep"])["tied"] >= rep["tied0"] >= final, (rep["tied0"], final)
     active = [int(v) for v in t.round_active[:t.rounds]]
     assert active == [rep["tied0"]] + [r["out"] for r in rep["round"]] and t.rounds == rep["rounds"]
@@ -158,7 +166,7 @@ def test_forward_default_key(pkg, case):
     assert len(reps) in (1, 2) and reps[-1]["cyclic"] and not any(r["cyclic"] for r in reps[:-1]), reps
     rep = reps[-1]
     assert t.key_bits == rep["key_bits"] and t.key_symbols == rep["msym"]
-    check_any_key(rep, mod, t)
+    check_any_key(rep, mod, t, pkg)
     if not rep["varlen"]:
         check_exact(rep, M.predict(mod, rep["msym"], chunk_plan(pkg)), t)
     _seen[case.name + "/default"] = rep

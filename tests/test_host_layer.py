@@ -48,6 +48,6 @@ def test_stage_cut_under_sanitizers(tmp_path, pkg):
 
 def test_headers_are_plain_cxx():
     """None of the headers may pull in the device runtime: the programs above have to build with a host compiler alone."""
-    for h in ("copy_pool.h", "seg_layout.h", "stage_cut.h"):
+    for h in ("copy_pool.h", "seg_layout.h", "stage_cut.h", "key_plan.h"):
         includes = [line for line in open(os.path.join(CSRC, h)).read().splitlines() if line.startswith("#include")]
         assert includes and not [line for line in includes if "hip" in line or "internal.h" in line], h

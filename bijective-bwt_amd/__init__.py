@@ -70,6 +70,11 @@ PACK_EXPORTS = [
     "bwts_unpack_ranges_device", "bwts_unpack_ranges",
 ]
 E_CHECKSUM = -10
+# ... include/bwts_members.h (the member frame: arrays of any lengths and widths in one frame) ...
+MEMBERS_EXPORTS = [
+    "bwts_planes_split_segments_w_device", "bwts_planes_join_segments_w_device", "bwts_pack_members_bound",
+    "bwts_pack_members_device", "bwts_pack_members", "bwts_frame_members", "bwts_unpack_members_device", "bwts_unpack_members",
+]
 # ... and include/bwts_test.h (harness and unit-test hooks)
 TEST_EXPORTS = [
     "bwts_generate_device", "bwts_device_alloc", "bwts_device_free", "bwts_copy_to_device", "bwts_copy_to_host",
@@ -241,6 +246,15 @@ def lib():
         L.bwts_debug_unpack_ranges_plan.argtypes = [vp, u64, vp, u64, u64, ctypes.POINTER(u64), vp, u64]
         L.bwts_debug_unpack_ranges_report.argtypes = [vp, ctypes.POINTER(u64)]
         L.bwts_debug_copy_pieces.argtypes = [vp, vp, u64, vp, u64, vp, u64]
+        for name in ("bwts_planes_split_segments_w_device", "bwts_planes_join_segments_w_device"):
+            getattr(L, name).argtypes = [vp, vp, vp, vp, u64, vp]
+        L.bwts_pack_members_bound.argtypes = [vp, u64]
+        L.bwts_pack_members_bound.restype = u64
+        for name in ("bwts_pack_members_device", "bwts_pack_members"):
+            getattr(L, name).argtypes = [vp, vp, vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
+        L.bwts_frame_members.argtypes = [vp, u64, vp, vp, u64, ctypes.POINTER(u64)]
+        for name in ("bwts_unpack_members_device", "bwts_unpack_members"):
+            getattr(L, name).argtypes = [vp, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64)]
         for name in ("bwts_forward_sink", "bwts_inverse_sink"):
             getattr(L, name).argtypes = [vp, vp, u64, SINK_FN, vp]
         L.bwts_generate_device.argtypes = [vp, i32, u64, u64, vp]
@@ -678,6 +692,61 @@ class Context:
         d["gathered"], d["single"] = bool(d["gathered"]), bool(d["single"])
         return d
 
+    # -- the member frame: arrays of any lengths and widths in one frame (include/bwts_members.h) ---------
+    def planes_split_segments_w_device(self, d_in, lengths, widths, d_out):
+        """bwts_planes_split_segments_w_device: every segment split at its own width (1: copied), where it lies, in one launch."""
+        ls, ws = _members(lengths, widths)
+        self._check(lib().bwts_planes_split_segments_w_device(self._h, _ptr(d_in), ls.ctypes.data, ws.ctypes.data, ls.size, _ptr(d_out)))
+
+    def planes_join_segments_w_device(self, d_in, lengths, widths, d_out):
+        ls, ws = _members(lengths, widths)
+        self._check(lib().bwts_planes_join_segments_w_device(self._h, _ptr(d_in), ls.ctypes.data, ws.ctypes.data, ls.size, _ptr(d_out)))
+
+    def pack_members(self, arrays, widths=None, out_cap=None):
+        """bwts_pack_members: one member frame of the arrays (bytes-like, or numpy arrays of any dtype, taken as their bytes); widths: one
+        of 1, 2, 4, 8 per array, None for no split at all -- named by the caller, never guessed from a dtype (host buffers)."""
+        parts = [_bytes_of(a) for a in arrays]
+        ls, ws = _members([p.size for p in parts], widths)
+        a = np.concatenate(parts) if parts else np.empty(0, dtype=np.uint8)
+        out = np.empty(pack_members_bound(ls) if out_cap is None else int(out_cap), dtype=np.uint8)
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_pack_members(self._h, a.ctypes.data, ls.ctypes.data, None if ws is None else ws.ctypes.data, ls.size,
+                                            out.ctypes.data, out.size, ctypes.byref(got)))
+        return out[:got.value].copy()
+
+    def pack_members_device(self, d_in, lengths, widths, d_out, out_cap):
+        """bwts_pack_members_device: the members lie back to back in d_in; returns the frame's size in bytes."""
+        ls, ws = _members(lengths, widths)
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_pack_members_device(self._h, _ptr(d_in), ls.ctypes.data, None if ws is None else ws.ctypes.data, ls.size,
+                                                   _ptr(d_out), int(out_cap), ctypes.byref(got)))
+        return int(got.value)
+
+    def unpack_members(self, frame, indices=None):
+        """bwts_unpack_members: the members named, as a list of bytes, in the order asked (None: all of them); only these are decoded."""
+        a = _u8(frame)
+        lengths, _ = frame_members(a)
+        idx = np.arange(len(lengths), dtype=np.uint64) if indices is None else np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        sizes = [lengths[int(i)] if int(i) < len(lengths) else 0 for i in idx.tolist()]
+        total = sum(sizes)
+        out = np.empty(max(total, 1), dtype=np.uint8)[:total]       # (never a null pointer: the library judges the indices itself)
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_unpack_members(self._h, a.ctypes.data, a.size, idx.ctypes.data if idx.size else None, idx.size, out.ctypes.data, total,
+                                              ctypes.byref(got)))
+        res, at = [], 0
+        for b in sizes:
+            res.append(out[at:at + b].tobytes())
+            at += b
+        return res
+
+    def unpack_members_device(self, d_in, in_bytes, indices, d_out, out_cap):
+        """bwts_unpack_members_device: the members named back to back in d_out; returns their sum."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_unpack_members_device(self._h, _ptr(d_in), int(in_bytes), idx.ctypes.data if idx.size else None, idx.size, _ptr(d_out),
+                                                     int(out_cap), ctypes.byref(got)))
+        return int(got.value)
+
     def debug_copy_pieces(self, d_src, src_bytes, pieces, d_dst, dst_bytes):
         """bwts_debug_copy_pieces: copy_pieces_kernel alone over (src offset, dst offset, bytes) triples."""
         ps = np.ascontiguousarray(pieces, dtype=np.uint64).reshape(-1, 3)
@@ -941,6 +1010,48 @@ def pack_bound(n, block_bytes=0, version=None, planes=None):
     if b == 0:
         raise BwtsError(-5 if int(n) > (1 << 32) else -1, "no bound for these arguments")
     return b
+
+
+def _bytes_of(a):
+    """A member as its bytes: a numpy array of any dtype is viewed, not converted."""
+    if isinstance(a, np.ndarray):
+        return np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    return np.frombuffer(bytes(a), dtype=np.uint8)
+
+
+def _members(lengths, widths):
+    """Lengths and widths of a member call as the arrays the library takes; widths None stays None (all 1)."""
+    ls = np.ascontiguousarray(lengths, dtype=np.uint64).reshape(-1)
+    if widths is None:
+        return ls, None
+    ws = np.ascontiguousarray(widths, dtype=np.uint32).reshape(-1)
+    if ws.size != ls.size:
+        raise BwtsError(-1, "one width per member")
+    return ls, ws
+
+
+def pack_members_bound(lengths):
+    """bwts_pack_members_bound: the largest member frame of members of these lengths."""
+    ls = np.ascontiguousarray(lengths, dtype=np.uint64).reshape(-1)
+    b = int(lib().bwts_pack_members_bound(ls.ctypes.data if ls.size else None, ls.size))
+    if b == 0:
+        bad = ls.size == 0 or bool((ls == 0).any())
+        raise BwtsError(-1 if bad else -5, "no bound for these lengths")
+    return b
+
+
+def frame_members(frame):
+    """bwts_frame_members: (lengths, widths) of a member frame, two lists, from its header and directory (host arithmetic)."""
+    a = _u8(frame)
+    count = ctypes.c_uint64(0)
+    rc = lib().bwts_frame_members(a.ctypes.data, a.size, None, None, 0, ctypes.byref(count))
+    if rc != 0:
+        raise BwtsError(rc, lib().bwts_strerror(rc).decode())
+    ls, ws = np.zeros(count.value, dtype=np.uint64), np.zeros(count.value, dtype=np.uint32)
+    rc = lib().bwts_frame_members(a.ctypes.data, a.size, ls.ctypes.data, ws.ctypes.data, ls.size, ctypes.byref(count))
+    if rc != 0:
+        raise BwtsError(rc, lib().bwts_strerror(rc).decode())
+    return ls.tolist(), ws.tolist()
 
 
 def _ranges(ranges):

@@ -10,6 +10,8 @@
 #include "zrl_plan.h"
 #include "planes_plan.h"
 #include "pack_plan.h"
+#include "members_plan.h"
+#include "../../include/bwts_members.h"
 
 #include <algorithm>
 #include <new>
@@ -664,6 +666,13 @@ extern "C" uint64_t bwts_pack_bound(uint64_t n, uint64_t block_bytes)
 extern "C" int bwts_unpack_size(const uint8_t *frame, uint64_t in_bytes, uint64_t *n, uint64_t *frame_bytes)
 {
     if (!frame || !n || !frame_bytes) return BWTS_E_ARG;
+    if (in_bytes >= PACK_HEADER_BYTES && members_magic(frame)) {
+        MembersHeader M;
+        BWTS_TRY(members_header_check(frame, in_bytes, &M));
+        BWTS_TRY(members_directory_check(frame + MEMBERS_HEADER_BYTES, M, in_bytes, false, frame_bytes));
+        *n = M.n;
+        return BWTS_OK;
+    }
     PackHeader H;
     BWTS_TRY(pack_header_check(frame, in_bytes, &H));
     BWTS_TRY(pack_directory_check(frame + PACK_HEADER_BYTES, H, in_bytes, false, frame_bytes));
@@ -769,27 +778,117 @@ extern "C" int bwts_unpack_ranges_device(bwts_ctx *ctx, const void *d_in, uint64
 
 // The host form judges frame and ranges itself, in the device form's order, and sends header, directory and the covered blocks'
 // streams alone, back to back: the device form finds them gathered.
-extern "C" int bwts_unpack_ranges(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const bwts_range *ranges, uint64_t count,
-                                  uint8_t *out, uint64_t out_cap, uint64_t *out_bytes)
+// by_index: whole members of a member frame as the ranges (bwts_unpack_members); `ranges` is then not read.
+static int unpack_ranges_host(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const PackRange *ranges, const uint64_t *indices, uint64_t count,
+                              uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, bool by_index = false)
 {
-    if (!ctx || !in || !out || !out_bytes || in_bytes == 0) return BWTS_E_ARG;
     PackHeader H;
-    u64 frame = 0, sum = 0;
-    BWTS_TRY(pack_header_check(in, in_bytes, &H));
-    BWTS_TRY(pack_directory_check(in + PACK_HEADER_BYTES, H, in_bytes, true, &frame));
-    BWTS_TRY(pack_ranges_check(H, (const PackRange *)ranges, count, out_cap, &sum));
+    u64 sum = 0, fixed = 0;
     PackRangesPlan P;
-    pack_ranges_plan(H, in + PACK_HEADER_BYTES, (const PackRange *)ranges, count, &P);
-    const u64 fixed = pack_fixed_bytes_v(H.version, H.nblk);
+    std::vector<PackRange> whole;
+    BWTS_TRY(frame_ranges_plan(in, in_bytes, ranges, by_index ? indices : nullptr, count, out_cap, &H, &fixed, &sum, &whole, &ranges, &P));
     std::vector<u8> sent((size_t)(fixed + P.stream_bytes));
     memcpy(sent.data(), in, (size_t)fixed);
     for (const PackPiece &s : P.streams) memcpy(sent.data() + fixed + s.dst, in + s.src, (size_t)s.bytes);
     const HostTrip trip = {sent.data(), sent.size(), sent.size() > sum ? sent.size() : sum, out, out_bytes};
     return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *got) {
         return run_sized(ctx, 0, "unpack ranges", [&] {
-            return unpack_ranges_device_impl(ctx, d_in, in_bytes, true, (const PackRange *)ranges, count, d_out, sum, got);
+            return unpack_ranges_device_impl(ctx, d_in, in_bytes, true, ranges, count, d_out, sum, got, by_index ? indices : nullptr);
         });
     });
+}
+
+extern "C" int bwts_unpack_ranges(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const bwts_range *ranges, uint64_t count,
+                                  uint8_t *out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!ctx || !in || !out || !out_bytes || in_bytes == 0) return BWTS_E_ARG;
+    return unpack_ranges_host(ctx, in, in_bytes, (const PackRange *)ranges, nullptr, count, out, out_cap, out_bytes);
+}
+
+// ------------------------------------------------------------------------------------
+// the member frame (include/bwts_members.h): the drivers in pack.hip, the arithmetic in members_plan.h, the mixed-width kernels in
+// planes.hip
+// ------------------------------------------------------------------------------------
+static int planes_segments_w_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, uint64_t count, void *d_out, bool join)
+{
+    if (!ctx || !d_in || !d_out || !widths) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(seg_table_set(ctx, lengths, count, &n));
+    for (u64 s = 0; s < count; s++)
+        if (!planes_width_w_ok(widths[s])) return BWTS_E_ARG;
+    if (ranges_overlap(d_in, n, d_out, n)) return BWTS_E_ARG;
+    return run_sized(ctx, n, join ? "planes join" : "planes split", [&] { return planes_w_impl(ctx, (const u8 *)d_in, n, widths, (u8 *)d_out, join); });
+}
+
+extern "C" int bwts_planes_split_segments_w_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, uint64_t count, void *d_out)
+{
+    return planes_segments_w_device(ctx, d_in, lengths, widths, count, d_out, false);
+}
+
+extern "C" int bwts_planes_join_segments_w_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, uint64_t count, void *d_out)
+{
+    return planes_segments_w_device(ctx, d_in, lengths, widths, count, d_out, true);
+}
+
+extern "C" uint64_t bwts_pack_members_bound(const uint64_t *lengths, uint64_t count)
+{
+    return members_bound_bytes(lengths, count);
+}
+
+extern "C" int bwts_pack_members_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, uint64_t count, void *d_out,
+                                        uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!ctx || !d_in || !d_out || !out_bytes || ((uintptr_t)d_out & 15)) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(members_args_check(lengths, widths, count, &n));
+    if (ranges_overlap(d_in, n, d_out, out_cap)) return BWTS_E_ARG;
+    return run_sized(ctx, n, "pack members", [&] { return pack_members_device_impl(ctx, (const u8 *)d_in, lengths, widths, count, n, (u8 *)d_out, out_cap, out_bytes); });
+}
+
+extern "C" int bwts_pack_members(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, const uint32_t *widths, uint64_t count, uint8_t *out,
+                                 uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!ctx || !in || !out || !out_bytes) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(members_args_check(lengths, widths, count, &n));
+    const u64 bound = members_bound_bytes(lengths, count);
+    const u64 cap = out_cap < bound ? out_cap : bound;
+    if (cap < members_least_bytes(count)) return BWTS_E_SPACE;
+    const HostTrip trip = {in, n, n > cap ? n : cap, out, out_bytes};
+    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *bytes) { return bwts_pack_members_device(ctx, d_in, lengths, widths, count, d_out, cap, bytes); });
+}
+
+extern "C" int bwts_frame_members(const uint8_t *frame, uint64_t in_bytes, uint64_t *lengths_out, uint32_t *widths_out, uint64_t cap, uint64_t *count)
+{
+    if (!frame || !count || in_bytes == 0) return BWTS_E_ARG;
+    MembersHeader M;
+    u64 frame_bytes = 0;
+    BWTS_TRY(members_header_check(frame, in_bytes, &M));
+    BWTS_TRY(members_directory_check(frame + MEMBERS_HEADER_BYTES, M, in_bytes, true, &frame_bytes));
+    if ((lengths_out || widths_out) && cap < M.count) return BWTS_E_SPACE;
+    for (u64 k = 0; k < M.count; k++) {
+        if (lengths_out) lengths_out[k] = members_entry_len(frame + MEMBERS_HEADER_BYTES, k);
+        if (widths_out) widths_out[k] = members_entry_width(frame + MEMBERS_HEADER_BYTES, k);
+    }
+    *count = M.count;
+    return BWTS_OK;
+}
+
+extern "C" int bwts_unpack_members_device(bwts_ctx *ctx, const void *d_in, uint64_t in_bytes, const uint64_t *indices, uint64_t icount, void *d_out,
+                                          uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!ctx || !d_in || !d_out || !out_bytes || !indices || in_bytes == 0 || ((uintptr_t)d_in & 15)) return BWTS_E_ARG;
+    if (ranges_overlap(d_in, in_bytes, d_out, out_cap)) return BWTS_E_ARG;
+    return run_sized(ctx, 0, "unpack members", [&] {
+        return unpack_ranges_device_impl(ctx, (const u8 *)d_in, in_bytes, false, nullptr, icount, (u8 *)d_out, out_cap, out_bytes, indices);
+    });
+}
+
+extern "C" int bwts_unpack_members(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const uint64_t *indices, uint64_t icount, uint8_t *out,
+                                   uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!ctx || !in || !out || !out_bytes || !indices || in_bytes == 0) return BWTS_E_ARG;
+    return unpack_ranges_host(ctx, in, in_bytes, nullptr, indices, icount, out, out_cap, out_bytes, true);
 }
 
 // copy_pieces_kernel alone (include/bwts_test.h; here for the call bracket): refuses, before anything is launched, what the driver's

@@ -345,6 +345,7 @@ void bwts_zrl_plan(u64 n, u64 out[2]);                                  // tile 
 
 // ---- byte-plane split in front of the transform (planes.hip; include/bwts_planes.h) ----
 int planes_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u32 w, u8 *d_out, bool join, SegMode segs);
+int planes_w_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, const u32 *widths, u8 *d_out, bool join);     // the context's table, a width (1, 2, 4, 8) per segment
 void bwts_planes_plan(u64 n, u32 w, u64 out[4]);                        // tile bytes, tiles, elements and tail bytes of one input of n bytes
 
 // ---- checksum and the packed frame (crc.hip, pack.hip; include/bwts_pack.h) ------------
@@ -357,7 +358,11 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
 // streams alone, back to back (the host form); in_bytes stays the whole frame's length
 struct PackRange;
 struct PackPiece;
-int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool packed, const PackRange *ranges, u64 count, u8 *d_out, u64 out_cap, u64 *out_bytes);
+// indices: not null for whole members of a member frame as the ranges (ranges is then not read; count indices)
+int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool packed, const PackRange *ranges, u64 count, u8 *d_out, u64 out_cap, u64 *out_bytes,
+                              const u64 *indices = nullptr);
+// the member frame (include/bwts_members.h); lengths and widths have passed members_args_check, n is their sum
+int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, u64 count, u64 n, u8 *d_out, u64 out_cap, u64 *out_bytes);
 // pieces of one device buffer to another, at any alignment (pieces.hip); every piece inside both buffers, by the caller's check
 int copy_pieces_impl(bwts_ctx *ctx, const u8 *d_src, u64 src_bytes, const PackPiece *pieces, u64 count, u8 *d_dst);
 

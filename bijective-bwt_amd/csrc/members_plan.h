@@ -1,0 +1,215 @@
+// members_plan.h -- the arithmetic of the member frame (include/bwts_members.h): members of any lengths and widths in one frame, its
+// bound, what makes its header and directory valid, and which members a list of byte ranges touches.  In the style of pack_plan.h,
+// whose codes, CRC-32 and range types it uses: pack.hip, the host side of the calls and a stand-alone host program
+// (tests/members_plan_check.cc, built with the sanitizers) all compile this file.
+#pragma once
+#include "pack_plan.h"
+
+#define MEMBERS_MAGIC 0x4D545742u        // "BWTM"
+#define MEMBERS_VERSION 1u
+#define MEMBERS_HEADER_BYTES 32u
+#define MEMBERS_ENTRY_BYTES 32u
+#define MEMBERS_MAX_COUNT (1ull << 20)   // the largest directory a "BWTZ" frame can have: 2^32 / 4096
+#define MEMBERS_LEAST_FRAME 64u          // header and one directory entry
+
+EC_HD bool members_magic(const uint8_t *h) { return ec_le32(h) == MEMBERS_MAGIC; }
+EC_HD uint64_t members_fixed_bytes(uint64_t count) { return MEMBERS_HEADER_BYTES + (uint64_t)MEMBERS_ENTRY_BYTES * count; }
+
+// What a pack is asked for: PACK_ARG for no members, a zero length or a bad width (widths == NULL: all 1), PACK_RANGE for more than
+// 2^20 members or more than 2^32 bytes, else PACK_OK and *n.  The sum cannot wrap: it is held against 2^32 after every member.
+static inline int members_args_check(const uint64_t *lengths, const uint32_t *widths, uint64_t count, uint64_t *n)
+{
+    if (!lengths || count == 0) return PACK_ARG;
+    if (count > MEMBERS_MAX_COUNT) return PACK_RANGE;
+    for (uint64_t k = 0; k < count; k++)
+        if (lengths[k] == 0 || (widths && !planes_width_w_ok(widths[k]))) return PACK_ARG;
+    uint64_t sum = 0;
+    for (uint64_t k = 0; k < count; k++) {
+        if (lengths[k] > PACK_MAX_N - sum) return PACK_RANGE;
+        sum += lengths[k];
+    }
+    *n = sum;
+    return PACK_OK;
+}
+
+// 32 + 32 count + the coder's bound of every member (the split never changes a length, the zero-run stage never expands); 0 on
+// arguments that members_args_check refuses
+static inline uint64_t members_bound_bytes(const uint64_t *lengths, uint64_t count)
+{
+    uint64_t n = 0;
+    if (members_args_check(lengths, nullptr, count, &n) != PACK_OK) return 0;
+    uint64_t total = members_fixed_bytes(count);
+    for (uint64_t k = 0; k < count; k++) total += ec_bound_bytes(lengths[k]);
+    return total;
+}
+// every member at least one coded byte
+EC_HD uint64_t members_least_bytes(uint64_t count) { return members_fixed_bytes(count) + count * ec_least_bytes(1u); }
+
+EC_HD void members_entry_write(uint8_t e[32], uint64_t stream_bytes, uint32_t crc, uint32_t width, uint64_t coded_bytes, uint64_t len)
+{
+    pack_put64(e, stream_bytes); ec_put32(e + 8, crc); ec_put32(e + 12, width); pack_put64(e + 16, coded_bytes); pack_put64(e + 24, len);
+}
+// the header of a frame whose directory (count entries) is complete
+EC_HD void members_header_write(uint8_t h[32], uint64_t n, uint64_t count, const uint8_t *dir)
+{
+    ec_put32(h, MEMBERS_MAGIC); ec_put32(h + 4, MEMBERS_VERSION); pack_put64(h + 8, n); pack_put64(h + 16, count);
+    ec_put32(h + 24, crc32_bytes(dir, (uint64_t)MEMBERS_ENTRY_BYTES * count));
+    ec_put32(h + 28, crc32_bytes(h, 28));
+}
+
+struct MembersHeader { uint64_t n, count; uint32_t dir_crc; };
+
+// The header of a frame of which in_bytes bytes are at hand (h: the first 32 of them, read only when in_bytes allows a frame at all).
+// PACK_OK and *H, PACK_FORMAT, or PACK_RANGE for a sound header that names more than 2^32 bytes or more than 2^20 members.
+EC_HD int members_header_check(const uint8_t *h, uint64_t in_bytes, MembersHeader *H)
+{
+    if (in_bytes < MEMBERS_LEAST_FRAME || (in_bytes & 15u)) return PACK_FORMAT;
+    if (ec_le32(h) != MEMBERS_MAGIC || ec_le32(h + 4) != MEMBERS_VERSION) return PACK_FORMAT;
+    if (ec_le32(h + 28) != crc32_bytes(h, 28)) return PACK_FORMAT;
+    const uint64_t n = pack_le64(h + 8), count = pack_le64(h + 16);
+    if (n == 0) return PACK_FORMAT;
+    if (n > PACK_MAX_N) return PACK_RANGE;
+    if (count == 0 || count > n) return PACK_FORMAT;
+    if (count > MEMBERS_MAX_COUNT) return PACK_RANGE;
+    H->n = n; H->count = count; H->dir_crc = ec_le32(h + 24);
+    if (members_fixed_bytes(count) > in_bytes) return PACK_FORMAT;
+    return PACK_OK;
+}
+
+// The directory behind a header that passed (dir: H.count entries, which in_bytes holds).  exact: the frame must be all of in_bytes
+// (an unpack), else it may end earlier (stepping through concatenated frames).  PACK_OK and *frame_bytes, or PACK_FORMAT.
+EC_HD int members_directory_check(const uint8_t *dir, const MembersHeader &H, uint64_t in_bytes, bool exact, uint64_t *frame_bytes)
+{
+    if (crc32_bytes(dir, (uint64_t)MEMBERS_ENTRY_BYTES * H.count) != H.dir_crc) return PACK_FORMAT;
+    uint64_t total = members_fixed_bytes(H.count), sum = 0;
+    for (uint64_t k = 0; k < H.count; k++) {
+        const uint8_t *e = dir + (uint64_t)MEMBERS_ENTRY_BYTES * k;
+        const uint64_t sb = pack_le64(e), coded = pack_le64(e + 16), len = pack_le64(e + 24);
+        if (!planes_width_w_ok(ec_le32(e + 12))) return PACK_FORMAT;
+        if (len == 0 || len > H.n - sum) return PACK_FORMAT;       // (by subtraction: the running sum stays within n <= 2^32)
+        sum += len;
+        if (coded == 0 || coded > len) return PACK_FORMAT;
+        if ((sb & 15u) || sb < ec_least_bytes(coded) || sb > ec_bound_bytes(coded)) return PACK_FORMAT;      // (so the sum cannot overflow)
+        total += sb;
+    }
+    if (sum != H.n) return PACK_FORMAT;
+    if (exact ? total != in_bytes : total > in_bytes) return PACK_FORMAT;
+    *frame_bytes = total;
+    return PACK_OK;
+}
+
+EC_HD uint64_t members_entry_len(const uint8_t *dir, uint64_t k) { return pack_le64(dir + (uint64_t)MEMBERS_ENTRY_BYTES * k + 24); }
+EC_HD uint32_t members_entry_width(const uint8_t *dir, uint64_t k) { return ec_le32(dir + (uint64_t)MEMBERS_ENTRY_BYTES * k + 12); }
+
+// where every member begins in the concatenation: count + 1 offsets, off[count] = n (a directory that passed its check)
+static inline std::vector<uint64_t> members_offsets(const uint8_t *dir, uint64_t count)
+{
+    std::vector<uint64_t> off((size_t)count + 1, 0);
+    for (uint64_t k = 0; k < count; k++) off[(size_t)k + 1] = off[(size_t)k] + members_entry_len(dir, k);
+    return off;
+}
+
+// the member that holds byte `at` of the concatenation (at < off[count]): the last one that does not begin behind it
+static inline uint64_t members_find(const std::vector<uint64_t> &off, uint64_t at)
+{
+    uint64_t lo = 0, hi = off.size() - 1;
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (off[(size_t)mid] <= at) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The indices of a bwts_unpack_members call against a judged directory, as the ranges they stand for: PACK_ARG, then PACK_RANGE for
+// more than 2^20 indices or one that names no member; else PACK_OK and one range per index, in the order asked.
+static inline int members_index_ranges(const std::vector<uint64_t> &off, const uint64_t *indices, uint64_t icount, std::vector<PackRange> *r)
+{
+    if (!indices || icount == 0) return PACK_ARG;
+    if (icount > PACK_MAX_RANGES) return PACK_RANGE;
+    const uint64_t count = off.size() - 1;
+    r->clear();
+    for (uint64_t i = 0; i < icount; i++) {
+        if (indices[i] >= count) return PACK_RANGE;
+        r->push_back(PackRange{off[(size_t)indices[i]], off[(size_t)indices[i] + 1] - off[(size_t)indices[i]]});
+    }
+    return PACK_OK;
+}
+
+// pack_ranges_plan for a member frame: the covered members are found by bisecting the offsets where that one divides by B.  dir has
+// passed members_directory_check and off is its members_offsets, the ranges pack_ranges_check against n = off[count].
+static inline void members_ranges_plan(const std::vector<uint64_t> &off, const uint8_t *dir, const PackRange *r, uint64_t count, PackRangesPlan *P)
+{
+    const uint64_t members = off.size() - 1, entry = MEMBERS_ENTRY_BYTES;
+    std::vector<int32_t> step((size_t)members + 1, 0);
+    for (uint64_t i = 0; i < count; i++) {
+        step[(size_t)members_find(off, r[i].offset)]++;
+        step[(size_t)members_find(off, r[i].offset + r[i].bytes - 1u) + 1]--;
+    }
+    std::vector<uint64_t> at((size_t)members, 0);        // where a covered member begins in the covered-member buffer
+    P->runs.clear(); P->streams.clear(); P->out.clear(); P->blocks.clear();
+    P->covered_bytes = P->stream_bytes = P->coded_bytes = P->out_bytes = 0;
+    uint64_t frame_at = members_fixed_bytes(members);
+    int64_t open = 0;
+    bool in_run = false;
+    for (uint64_t b = 0; b < members; b++) {
+        const uint64_t sb = pack_le64(dir + entry * b);
+        open += step[(size_t)b];
+        if (open > 0) {
+            if (!in_run) {
+                P->runs.push_back(PackRun{b, 0});
+                P->streams.push_back(PackPiece{frame_at, P->stream_bytes, 0});
+            }
+            P->runs.back().blocks++;
+            P->streams.back().bytes += sb;
+            P->blocks.push_back(b);
+            at[(size_t)b] = P->covered_bytes;
+            P->covered_bytes += off[(size_t)b + 1] - off[(size_t)b];
+            P->stream_bytes += sb;
+            P->coded_bytes += pack_le64(dir + entry * b + 16);
+        }
+        in_run = open > 0;
+        frame_at += sb;
+    }
+    for (uint64_t i = 0; i < count; i++) {
+        const uint64_t b = members_find(off, r[i].offset);
+        P->out.push_back(PackPiece{at[(size_t)b] + (r[i].offset - off[(size_t)b]), P->out_bytes, r[i].bytes});
+        P->out_bytes += r[i].bytes;
+    }
+}
+
+// A frame of either magic that the host holds whole, and the ranges asked of it: header, directory and ranges judged in unpack's order
+// with unpack's codes, then the plan.  indices: not null for whole members as the ranges (`ranges` is then not read, a "BWTZ" frame
+// is PACK_FORMAT, and *ranges_out points into *whole).  H: the frame as the drivers carry it (a member frame: version 3, nblk
+// members, B unused).
+static inline int frame_ranges_plan(const uint8_t *frame, uint64_t in_bytes, const PackRange *ranges, const uint64_t *indices, uint64_t count,
+                                    uint64_t out_cap, PackHeader *H, uint64_t *fixed, uint64_t *sum, std::vector<PackRange> *whole,
+                                    const PackRange **ranges_out, PackRangesPlan *P)
+{
+    uint64_t frame_bytes = 0;
+    int rc;
+    if (in_bytes >= MEMBERS_HEADER_BYTES && members_magic(frame)) {
+        MembersHeader M;
+        const uint8_t *dir = frame + MEMBERS_HEADER_BYTES;
+        if ((rc = members_header_check(frame, in_bytes, &M)) != PACK_OK) return rc;
+        if ((rc = members_directory_check(dir, M, in_bytes, true, &frame_bytes)) != PACK_OK) return rc;
+        const std::vector<uint64_t> off = members_offsets(dir, M.count);
+        if (indices) {
+            if ((rc = members_index_ranges(off, indices, count, whole)) != PACK_OK) return rc;
+            ranges = whole->data();
+        }
+        *H = PackHeader{M.n, 0, M.count, M.dir_crc, PACK_VERSION_3, 0u};
+        if ((rc = pack_ranges_check(*H, ranges, count, out_cap, sum)) != PACK_OK) return rc;
+        members_ranges_plan(off, dir, ranges, count, P);
+        *fixed = members_fixed_bytes(M.count);
+    } else {
+        if ((rc = pack_header_check(frame, in_bytes, H)) != PACK_OK) return rc;
+        if ((rc = pack_directory_check(frame + PACK_HEADER_BYTES, *H, in_bytes, true, &frame_bytes)) != PACK_OK) return rc;
+        if (indices) return PACK_FORMAT;
+        if ((rc = pack_ranges_check(*H, ranges, count, out_cap, sum)) != PACK_OK) return rc;
+        pack_ranges_plan(*H, frame + PACK_HEADER_BYTES, ranges, count, P);
+        *fixed = pack_fixed_bytes_v(H->version, H->nblk);
+    }
+    *ranges_out = ranges;
+    return PACK_OK;
+}

@@ -15,8 +15,8 @@
 // A range read (unpack_ranges_device_impl, at the end) runs the same stages over the blocks its ranges touch, between the two blocks,
 // and cuts the ranges out with pieces.hip's copy kernel.
 #include "internal.h"
-#include "pack_plan.h"
-#include "../../include/bwts_pack.h"
+#include "members_plan.h"
+#include "../../include/bwts_members.h"
 
 #include <string.h>
 #include <utility>
@@ -119,16 +119,129 @@ int pack_device_impl(bwts_ctx *ctx, u32 version, u32 width, const u8 *d_in, u64 
     return BWTS_OK;
 }
 
+// is any block split at all?  (none in versions 1 and 2, whose list of widths is empty, nor where every member has width 1)
+static bool widths_split(const std::vector<u32> &widths)
+{
+    for (u32 w : widths) if (w != 1u) return true;
+    return false;
+}
+
+// A member frame: pack_device_impl's chain over members of any lengths, each split at its own width (1: not at all), with the entries
+// and the header of include/bwts_members.h.  One member goes through the single-input stages.
+int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, u64 count, u64 n, u8 *d_out, u64 out_cap, u64 *out_bytes)
+{
+    const u64 fixed = members_fixed_bytes(count);
+    const bool seg = count > 1;
+    if (out_cap < members_least_bytes(count)) return BWTS_E_SPACE;
+    std::vector<u32> ws((size_t)count, 1u);
+    if (widths) ws.assign(widths, widths + count);
+    auto members_set = [&] { u64 total = 0; return seg ? seg_table_set(ctx, lengths, count, &total) : BWTS_OK; };
+    BWTS_TRY(members_set());
+    SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
+    std::vector<u32> crcs((size_t)count);
+    std::vector<u64> sizes((size_t)count), coded((size_t)count);
+    BWTS_TRY(crc_impl(ctx, d_in, n, segs, crcs.data()));
+    u8 *to = nullptr, *other = nullptr;
+    BWTS_TRY(pack_stage(ctx, 0, n, &to));
+    BWTS_TRY(pack_stage(ctx, 1, n, &other));
+    const u8 *from = d_in;
+    auto done = [&] { from = to; std::swap(to, other); return hipStreamSynchronize(ctx->stream); };
+    if (widths_split(ws)) {
+        bool alike = true;
+        for (u32 w : ws) alike = alike && w == ws[0];
+        BWTS_TRY(alike ? planes_impl(ctx, from, n, ws[0], to, false, segs) : planes_w_impl(ctx, from, n, ws.data(), to, false));
+        HIPC(done());
+    }
+    BWTS_TRY(seg ? forward_segments_impl(ctx, from, n, to) : forward_device_impl(ctx, from, n, to));
+    HIPC(done());
+    BWTS_TRY(mtf_impl(ctx, from, n, to, false, segs));
+    HIPC(done());
+    BWTS_TRY(zrl_encode_impl(ctx, from, n, to, n, segs, coded.data()));
+    HIPC(done());
+    u64 m = 0;
+    BWTS_TRY(pack_coded_set(ctx, coded, &m));
+    if (seg) segs = seg_mode(ctx);
+    BWTS_TRY(ec_encode_impl(ctx, from, m, d_out + fixed, out_cap - fixed, segs, sizes.data()));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    u8 *head = (u8 *)(ctx->h_small + SM_PACK_HEAD), *dir = nullptr;
+    std::vector<u8> own;
+    BWTS_TRY(pack_dir_staging(ctx, PACK_VERSION_3, count, own, &dir));
+    u64 total = fixed;
+    for (u64 k = 0; k < count; k++) {
+        members_entry_write(dir + (u64)MEMBERS_ENTRY_BYTES * k, sizes[(size_t)k], crcs[(size_t)k], ws[(size_t)k], coded[(size_t)k], lengths[k]);
+        total += sizes[(size_t)k];
+    }
+    if (total > out_cap) return BWTS_E_INTERNAL;
+    members_header_write(head, n, count, dir);
+    HIPC(hipMemcpyAsync(d_out + MEMBERS_HEADER_BYTES, dir, (u64)MEMBERS_ENTRY_BYTES * count, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(hipMemcpyAsync(d_out, head, MEMBERS_HEADER_BYTES, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    *out_bytes = total;
+    return BWTS_OK;
+}
+
 // The frame is not trusted: header, then directory, are brought to the host and judged by the predicates of pack_plan.h before
 // anything is made of them; the coder and the zero-run decoder judge their inputs themselves.
 // What both unpacks know of a frame before a stream is touched.  The segment table is the frame's blocks when this returns; dir is
 // staging that the next stage writes over (seg_layout.h): what the directory says is copied out at once.
+// A member frame ("BWTM", include/bwts_members.h) is carried as a version-3 frame whose blocks are the members: H.nblk members,
+// H.B unused, every block with a length and a width of its own.
 struct FrameHead {
     PackHeader H;
     std::vector<u8> own;
     u8 *dir;
     u64 fixed, entry;
+    bool members = false;
+    std::vector<u64> off;       // members: where every member begins in the concatenation (count + 1)
+    u64 len_at(u64 k) const { return members ? off[(size_t)k + 1] - off[(size_t)k] : pack_block_at(H.n, H.B, k); }
+    u32 width_at(u64 k) const { return members ? members_entry_width(dir, k) : H.width; }
 };
+
+// the blocks of a judged frame as the segment table of the stages
+static int frame_blocks_set(bwts_ctx *ctx, const FrameHead &F)
+{
+    if (!F.members) return pack_blocks_set(ctx, F.H.n, F.H.B, F.H.nblk);
+    if (F.H.nblk == 1) return BWTS_OK;
+    std::vector<u64> lengths((size_t)F.H.nblk);
+    for (u64 k = 0; k < F.H.nblk; k++) lengths[(size_t)k] = F.len_at(k);
+    u64 total = 0;
+    BWTS_TRY(seg_table_set(ctx, lengths.data(), F.H.nblk, &total));
+    return total == F.H.n ? BWTS_OK : BWTS_E_INTERNAL;
+}
+
+// the join behind the inverse transform: blocks of `total` bytes in all at the widths given (one block, or all widths alike: the
+// uniform kernels; else one launch at mixed widths)
+static int frame_join(bwts_ctx *ctx, const u8 *from, u64 total, const std::vector<u32> &widths, u8 *to, SegMode segs)
+{
+    bool alike = true;
+    for (u32 w : widths) alike = alike && w == widths[0];
+    if (alike) return planes_impl(ctx, from, total, widths[0], to, true, segs);
+    return planes_w_impl(ctx, from, total, widths.data(), to, true);
+}
+
+static int unpack_members_head(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, const u8 *head, FrameHead &F)
+{
+    MembersHeader M;
+    BWTS_TRY(members_header_check(head, in_bytes, &M));
+    F.members = true;
+    F.H = PackHeader{M.n, 0, M.count, M.dir_crc, PACK_VERSION_3, 0u};
+    F.fixed = members_fixed_bytes(M.count);
+    F.entry = MEMBERS_ENTRY_BYTES;
+    BWTS_TRY(pack_dir_staging(ctx, PACK_VERSION_3, M.count, F.own, &F.dir));
+    if (M.count > 1) {
+        HIPC(hipMemcpyAsync(F.dir, d_in + MEMBERS_HEADER_BYTES, F.entry * M.count, hipMemcpyDeviceToHost, ctx->stream));
+        HIPC(hipStreamSynchronize(ctx->stream));
+    }
+    u64 frame = 0;
+    BWTS_TRY(members_directory_check(F.dir, M, in_bytes, true, &frame));
+    F.off = members_offsets(F.dir, M.count);
+    if (M.count == 1) {
+        // (the small block is the stages' too: the one entry is kept here)
+        F.own.assign(F.dir, F.dir + MEMBERS_ENTRY_BYTES);
+        F.dir = F.own.data();
+    }
+    return frame_blocks_set(ctx, F);
+}
 
 static int unpack_frame_head(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, FrameHead &F)
 {
@@ -137,6 +250,7 @@ static int unpack_frame_head(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, FrameH
     const u64 first = in_bytes < PACK_HEADER_BYTES + PACK_ENTRY_BYTES_V2 ? in_bytes : PACK_HEADER_BYTES + PACK_ENTRY_BYTES_V2;
     HIPC(hipMemcpyAsync(head, d_in, first, hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
+    if (members_magic(head)) return unpack_members_head(ctx, d_in, in_bytes, head, F);
     PackHeader &H = F.H;
     BWTS_TRY(pack_header_check(head, in_bytes, &H));
     F.fixed = pack_fixed_bytes_v(H.version, H.nblk);
@@ -157,7 +271,10 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
     BWTS_TRY(unpack_frame_head(ctx, d_in, in_bytes, F));
     const PackHeader &H = F.H;
     const u8 *dir = F.dir;
-    const bool seg = H.nblk > 1, zrl = H.version != PACK_VERSION, planes = H.version == PACK_VERSION_3;
+    std::vector<u32> widths;
+    if (H.version == PACK_VERSION_3)
+        for (u64 k = 0; k < H.nblk; k++) widths.push_back(F.width_at(k));
+    const bool seg = H.nblk > 1, zrl = H.version != PACK_VERSION, planes = widths_split(widths);
     const u64 fixed = F.fixed, entry = F.entry;
     const SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
     if (H.n > out_cap) return BWTS_E_SPACE;
@@ -168,7 +285,7 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
     for (u64 k = 0; k < H.nblk; k++) {
         sizes[(size_t)k] = pack_le64(dir + entry * k);
         want[(size_t)k] = ec_le32(dir + entry * k + 8);
-        coded[(size_t)k] = zrl ? pack_le64(dir + entry * k + 16) : pack_block_at(H.n, H.B, k);
+        coded[(size_t)k] = zrl ? pack_le64(dir + entry * k + 16) : F.len_at(k);
     }
     // The stages go to and fro between d_out and the stage block, and the last one lands in d_out.  Version 1, three stages: ranks
     // into d_out, bytes of the transform into the block, the input's bytes into d_out.  Version 2, four: the ranks' coded bytes into
@@ -199,7 +316,7 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
     if (zrl) {
         HIPC(hipStreamSynchronize(ctx->stream));
         ctx->tm.n = H.n;        // (the coder has put its own n there: the coded bytes)
-        BWTS_TRY(pack_blocks_set(ctx, H.n, H.B, H.nblk));
+        BWTS_TRY(frame_blocks_set(ctx, F));
         BWTS_TRY(zrl_decode_impl(ctx, from, m, to, H.n, segs, coded.data()));
         HIPC(done());
     }
@@ -208,7 +325,7 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
     BWTS_TRY(seg ? inverse_segments_impl(ctx, from, H.n, to) : inverse_device_impl(ctx, from, H.n, to));
     HIPC(done());
     if (planes) {
-        BWTS_TRY(planes_impl(ctx, from, H.n, H.width, to, true, segs));
+        BWTS_TRY(frame_join(ctx, from, H.n, widths, to, segs));
         HIPC(done());
     }
     if (from != d_out) return BWTS_E_INTERNAL;
@@ -224,26 +341,36 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
 // directory, and only then are the ranges cut out of the last stage's block into d_out.
 enum { RG_GATHER = 1, RG_DECODE = 2, RG_ZRL = 4, RG_MTF = 8, RG_INVERSE = 16, RG_JOIN = 32, RG_CRC = 64, RG_CUT = 128 };
 
-int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool packed, const PackRange *ranges, u64 count, u8 *d_out, u64 out_cap, u64 *out_bytes)
+int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool packed, const PackRange *ranges, u64 count, u8 *d_out, u64 out_cap, u64 *out_bytes,
+                              const u64 *indices)
 {
     u64 *rep = ctx->ranges_report;
     memset(rep, 0, sizeof ctx->ranges_report);
     FrameHead F;
     BWTS_TRY(unpack_frame_head(ctx, d_in, in_bytes, F));
     const PackHeader &H = F.H;
-    const bool zrl = H.version != PACK_VERSION, planes = H.version == PACK_VERSION_3;
+    const bool zrl = H.version != PACK_VERSION;
     u64 sum = 0;
+    // whole members as ranges (bwts_unpack_members_device): a member frame alone has them
+    std::vector<PackRange> whole;
+    if (indices) {
+        if (!F.members) return BWTS_E_FORMAT;
+        BWTS_TRY(members_index_ranges(F.off, indices, count, &whole));
+        ranges = whole.data();
+    }
     BWTS_TRY(pack_ranges_check(H, ranges, count, out_cap, &sum));
     PackRangesPlan P;
-    pack_ranges_plan(H, F.dir, ranges, count, &P);
+    if (F.members) members_ranges_plan(F.off, F.dir, ranges, count, &P);
+    else pack_ranges_plan(H, F.dir, ranges, count, &P);
     const u64 C = P.covered_bytes, nb = P.blocks.size();
     const bool seg = nb > 1, gather = !packed && P.runs.size() > 1;
     // (the staging is the next stage's: what the directory says of the covered blocks is kept here)
     std::vector<u64> lengths((size_t)nb), sizes((size_t)nb), coded((size_t)nb);
-    std::vector<u32> want((size_t)nb), got((size_t)nb);
+    std::vector<u32> want((size_t)nb), got((size_t)nb), widths;
     for (u64 k = 0; k < nb; k++) {
         const u8 *e = F.dir + F.entry * P.blocks[(size_t)k];
-        lengths[(size_t)k] = pack_block_at(H.n, H.B, P.blocks[(size_t)k]);
+        lengths[(size_t)k] = F.len_at(P.blocks[(size_t)k]);
+        if (H.version == PACK_VERSION_3) widths.push_back(F.width_at(P.blocks[(size_t)k]));
         sizes[(size_t)k] = pack_le64(e);
         want[(size_t)k] = ec_le32(e + 8);
         coded[(size_t)k] = zrl ? pack_le64(e + 16) : lengths[(size_t)k];
@@ -291,8 +418,8 @@ int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool 
     HIPC(done(RG_MTF));
     BWTS_TRY(seg ? inverse_segments_impl(ctx, from, C, to) : inverse_device_impl(ctx, from, C, to));
     HIPC(done(RG_INVERSE));
-    if (planes) {
-        BWTS_TRY(planes_impl(ctx, from, C, H.width, to, true, segs));
+    if (widths_split(widths)) {
+        BWTS_TRY(frame_join(ctx, from, C, widths, to, segs));
         HIPC(done(RG_JOIN));
     }
     BWTS_TRY(crc_impl(ctx, from, C, segs, got.data()));

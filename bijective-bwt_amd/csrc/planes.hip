@@ -41,29 +41,37 @@ struct PlanesTile {
     bool last;
 };
 
+// tile j of the string of len bytes at seg
 template <int W>
-__device__ __forceinline__ PlanesTile planes_tile(const PlanesSegs &S, u64 t)
+__device__ __forceinline__ PlanesTile planes_tile_at(u64 seg, u64 len, u64 j)
 {
     PlanesTile R;
-    u64 first = 0;
-    R.seg = 0; R.len = S.n;
-    if (S.off) {
-        // the segment of tile t: the last one whose first tile is not behind t (every segment has a tile, so the firsts differ)
-        u64 lo = 0, hi = S.count;
-        while (hi - lo > 1) {
-            const u64 mid = lo + (hi - lo) / 2;
-            if (S.first[mid] <= t) lo = mid;
-            else hi = mid;
-        }
-        first = S.first[lo];
-        R.seg = S.off[lo]; R.len = S.off[lo + 1] - R.seg;
-    }
-    const u64 j = t - first;
+    R.seg = seg; R.len = len;
     R.q = planes_q(R.len, W);
     R.e0 = j << PLANES_LOG_E;
     R.elems = planes_tile_elems(R.len, W, j);
     R.last = j + 1 == planes_tiles(R.len, W);
     return R;
+}
+
+// the segment of tile t: the last one whose first tile is not behind t (every segment has a tile, so the firsts differ)
+__device__ __forceinline__ u64 planes_tile_segment(const u64 *first, u64 count, u64 t)
+{
+    u64 lo = 0, hi = count;
+    while (hi - lo > 1) {
+        const u64 mid = lo + (hi - lo) / 2;
+        if (first[mid] <= t) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+template <int W>
+__device__ __forceinline__ PlanesTile planes_tile(const PlanesSegs &S, u64 t)
+{
+    if (!S.off) return planes_tile_at<W>(0, S.n, t);
+    const u64 lo = planes_tile_segment(S.first, S.count, t);
+    return planes_tile_at<W>(S.off[lo], S.off[lo + 1] - S.off[lo], t - S.first[lo]);
 }
 
 // one word from byte ba of a, byte bb of b, byte bc of c and byte bd of d (constants after unrolling): three byte permutes
@@ -103,12 +111,11 @@ __device__ __forceinline__ void planes_copy_tail(const u8 *in, const PlanesTile 
     if (threadIdx.x < R.len - at) out[R.seg + at + threadIdx.x] = in[R.seg + at + threadIdx.x];
 }
 
+// one tile of a split; lds: W * PLANES_PLANE_SLOTS units; n: the bytes of the call's input
 template <int W>
-__global__ __launch_bounds__(256) void planes_split_kernel(const u8 *__restrict__ in, PlanesSegs S, u8 *__restrict__ out)
+__device__ __forceinline__ void planes_split_tile(const u8 *__restrict__ in, u64 n, const PlanesTile &R, uint4 *lds, u8 *__restrict__ out)
 {
-    __shared__ uint4 lds[W * PLANES_PLANE_SLOTS];
     const u32 tid = threadIdx.x, at = 16u * tid;
-    const PlanesTile R = planes_tile<W>(S, blockIdx.x);
     if (R.elems) {
         if (at < R.elems) {
             // (a tile's last thread may hold fewer than 16 elements: what it reads behind them lies in the input or reads as 0, and no
@@ -117,7 +124,7 @@ __global__ __launch_bounds__(256) void planes_split_kernel(const u8 *__restrict_
             u32 D[4 * W];
 #pragma unroll
             for (int v = 0; v < W; v++) {
-                const uint4 x = planes_load16(p + 16 * v, in, in + S.n);
+                const uint4 x = planes_load16(p + 16 * v, in, in + n);
                 D[4 * v] = x.x; D[4 * v + 1] = x.y; D[4 * v + 2] = x.z; D[4 * v + 3] = x.w;
             }
             // word j of plane k: byte k of the elements 4 j .. 4 j + 3
@@ -140,18 +147,26 @@ __global__ __launch_bounds__(256) void planes_split_kernel(const u8 *__restrict_
 }
 
 template <int W>
-__global__ __launch_bounds__(256) void planes_join_kernel(const u8 *__restrict__ in, PlanesSegs S, u8 *__restrict__ out)
+__global__ __launch_bounds__(256) void planes_split_kernel(const u8 *__restrict__ in, PlanesSegs S, u8 *__restrict__ out)
 {
-    __shared__ uint4 lds[PLANES_SLOT(W * (PLANES_E / 16u)) + 2u];
+    __shared__ uint4 lds[W * PLANES_PLANE_SLOTS];
+    planes_split_tile<W>(in, S.n, planes_tile<W>(S, blockIdx.x), lds, out);
+}
+
+#define PLANES_JOIN_SLOTS(w) (PLANES_SLOT((w) * (PLANES_E / 16u)) + 2u)
+
+// one tile of a join; lds: PLANES_JOIN_SLOTS(W) units
+template <int W>
+__device__ __forceinline__ void planes_join_tile(const u8 *__restrict__ in, u64 n, const PlanesTile &R, uint4 *lds, u8 *__restrict__ out)
+{
     const u32 tid = threadIdx.x, at = 16u * tid;
-    const PlanesTile R = planes_tile<W>(S, blockIdx.x);
     if (R.elems) {
         if (at < R.elems) {
             const u8 *p = in + R.seg + R.e0 + at;
             u32 P[4 * W];
 #pragma unroll
             for (int k = 0; k < W; k++) {
-                const uint4 x = planes_load16(p + (u64)k * R.q, in, in + S.n);
+                const uint4 x = planes_load16(p + (u64)k * R.q, in, in + n);
                 P[4 * k] = x.x; P[4 * k + 1] = x.y; P[4 * k + 2] = x.z; P[4 * k + 3] = x.w;
             }
             // interleaved byte b of the thread: byte b / w of plane b mod w
@@ -171,6 +186,50 @@ __global__ __launch_bounds__(256) void planes_join_kernel(const u8 *__restrict__
         planes_stream_store(lds, out + R.seg + R.e0 * W, R.elems * W);
     }
     if (R.last) planes_copy_tail<W>(in, R, out);
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void planes_join_kernel(const u8 *__restrict__ in, PlanesSegs S, u8 *__restrict__ out)
+{
+    __shared__ uint4 lds[PLANES_JOIN_SLOTS(W)];
+    planes_join_tile<W>(in, S.n, planes_tile<W>(S, blockIdx.x), lds, out);
+}
+
+// ---- a width per segment: one launch for all of them ----
+// The segments of such a call: first and width lie behind the context's table, first[count + 1] and then one word per segment.
+struct PlanesSegsW {
+    const u64 *off, *first, *width;
+    u64 count, n;
+};
+
+// tile j of a segment of width 1: PLANES_COPY_T bytes at most, copied through the LDS under the same discipline (planes_load16 in,
+// planes_stream_store out); a thread takes every 256th unit of 16 bytes
+__device__ __forceinline__ void planes_copy_tile(const u8 *__restrict__ in, u64 n, u64 seg, u64 len, u64 j, uint4 *lds, u8 *__restrict__ out)
+{
+    const u32 bytes = planes_copy_bytes(len, j), units = (bytes + 15u) / 16u;
+    const u64 at = seg + j * PLANES_COPY_T;
+    for (u32 u = threadIdx.x; u < units; u += 256) lds[PLANES_SLOT(u)] = planes_load16(in + at + 16u * u, in, in + n);
+    __syncthreads();
+    planes_stream_store(lds, out + at, bytes);
+}
+
+// LDS for the widest tile of either direction
+#define PLANES_W_SLOTS (PLANES_MAX_W * PLANES_PLANE_SLOTS > PLANES_JOIN_SLOTS(PLANES_MAX_W) ? PLANES_MAX_W * PLANES_PLANE_SLOTS : PLANES_JOIN_SLOTS(PLANES_MAX_W))
+static_assert(PLANES_JOIN_SLOTS(PLANES_MAX_W) >= PLANES_SLOT(PLANES_COPY_T / 16u) + 2u, "a copied tile fits the LDS of a join at the largest width");
+
+template <bool JOIN>
+__global__ __launch_bounds__(256) void planes_w_kernel(const u8 *__restrict__ in, PlanesSegsW S, u8 *__restrict__ out)
+{
+    __shared__ uint4 lds[PLANES_W_SLOTS];
+    const u64 t = blockIdx.x, lo = planes_tile_segment(S.first, S.count, t);
+    const u64 seg = S.off[lo], len = S.off[lo + 1] - seg, j = t - S.first[lo];
+    // (the width is the same for the whole workgroup: one branch, taken together)
+    switch ((u32)S.width[lo]) {
+    case 1: planes_copy_tile(in, S.n, seg, len, j, lds, out); break;
+    case 2: JOIN ? planes_join_tile<2>(in, S.n, planes_tile_at<2>(seg, len, j), lds, out) : planes_split_tile<2>(in, S.n, planes_tile_at<2>(seg, len, j), lds, out); break;
+    case 4: JOIN ? planes_join_tile<4>(in, S.n, planes_tile_at<4>(seg, len, j), lds, out) : planes_split_tile<4>(in, S.n, planes_tile_at<4>(seg, len, j), lds, out); break;
+    default: JOIN ? planes_join_tile<8>(in, S.n, planes_tile_at<8>(seg, len, j), lds, out) : planes_split_tile<8>(in, S.n, planes_tile_at<8>(seg, len, j), lds, out); break;
+    }
 }
 
 // ------------------------------------------------------------------------------------
@@ -207,6 +266,27 @@ int planes_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u32 w, u8 *d_out, bool joi
         if (w == 2) planes_launch<2>(ctx->stream, join, (unsigned)tiles, d_in, S, d_out);
         else if (w == 4) planes_launch<4>(ctx->stream, join, (unsigned)tiles, d_in, S, d_out);
         else planes_launch<8>(ctx->stream, join, (unsigned)tiles, d_in, S, d_out);
+    }
+    HIPC(hipGetLastError());
+    return BWTS_OK;
+}
+
+// every segment of the context's table at its own width (1: copied), in one launch; widths: one per segment, judged by the caller
+int planes_w_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, const u32 *widths, u8 *d_out, bool join)
+{
+    const u64 count = ctx->seg_off.size() - 1;
+    // behind the context's table: every segment's first tile and the total, then every segment's width
+    std::vector<u64> words((size_t)(2 * count + 1));
+    const u64 tiles = planes_cut_w(ctx->seg_off.data(), widths, count, words.data());
+    if (tiles >= (1ull << 31)) return BWTS_E_RANGE;
+    for (u64 s = 0; s < count; s++) words[(size_t)(count + 1 + s)] = widths[s];
+    u64 *d_words = nullptr;
+    BWTS_TRY(seg_upload_extra(ctx, words.data(), 2 * count + 1, &d_words));
+    const PlanesSegsW S = {d_seg_off(ctx), d_words, d_words + count + 1, count, n};
+    {
+        SpanGuard sp(ctx, BWTS_K_OTHER, n, 2 * n);
+        if (join) planes_w_kernel<true><<<dim3((unsigned)tiles), dim3(256), 0, ctx->stream>>>(d_in, S, d_out);
+        else planes_w_kernel<false><<<dim3((unsigned)tiles), dim3(256), 0, ctx->stream>>>(d_in, S, d_out);
     }
     HIPC(hipGetLastError());
     return BWTS_OK;

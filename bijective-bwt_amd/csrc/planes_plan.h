@@ -32,6 +32,32 @@ PLANES_HD uint32_t planes_tile_elems(uint64_t L, uint32_t w, uint64_t j)
     return e0 >= q ? 0u : (q - e0 < PLANES_E ? (uint32_t)(q - e0) : PLANES_E);
 }
 
+// ---- a width per segment (bwts_planes_*_segments_w_device, the member frame of include/bwts_members.h) ----
+// Width 1 joins the three: such a segment is copied.  Its tile is PLANES_COPY_T bytes, the interleaved side of a tile at the largest
+// width, so that one LDS footprint (that of w = 8) serves every tile of a mixed call: 16 bytes to a thread, eight times over.
+#define PLANES_COPY_T (PLANES_E * PLANES_MAX_W)
+PLANES_HD bool planes_width_w_ok(uint64_t w) { return w == 1u || planes_width_ok(w); }
+PLANES_HD uint64_t planes_tile_bytes_w(uint32_t w) { return w == 1u ? (uint64_t)PLANES_COPY_T : planes_tile_bytes(w); }
+PLANES_HD uint64_t planes_tiles_w(uint64_t L, uint32_t w) { return (L + planes_tile_bytes_w(w) - 1u) / planes_tile_bytes_w(w); }
+// the bytes of tile j of a copied segment
+PLANES_HD uint32_t planes_copy_bytes(uint64_t L, uint64_t j)
+{
+    const uint64_t at = j * PLANES_COPY_T;
+    return at >= L ? 0u : (L - at < PLANES_COPY_T ? (uint32_t)(L - at) : PLANES_COPY_T);
+}
+// first[s]: the first tile of segment s over the call, count + 1 entries (stage_cut.h's cut, with a unit per segment); the total is
+// first[count]
+PLANES_HD uint64_t planes_cut_w(const uint64_t *off, const uint32_t *widths, uint64_t count, uint64_t *first)
+{
+    uint64_t tiles = 0;
+    for (uint64_t s = 0; s < count; s++) {
+        first[s] = tiles;
+        tiles += planes_tiles_w(off[s + 1] - off[s], widths[s]);
+    }
+    first[count] = tiles;
+    return tiles;
+}
+
 // where byte i of the interleaved string lies in the split string
 PLANES_HD uint64_t planes_split_index(uint64_t L, uint32_t w, uint64_t i)
 {

@@ -74,7 +74,14 @@ E_CHECKSUM = -10
 MEMBERS_EXPORTS = [
     "bwts_planes_split_segments_w_device", "bwts_planes_join_segments_w_device", "bwts_pack_members_bound",
     "bwts_pack_members_device", "bwts_pack_members", "bwts_frame_members", "bwts_unpack_members_device", "bwts_unpack_members",
+    "bwts_pack_members_f_device", "bwts_pack_members_f", "bwts_frame_members_f",
 ]
+# ... include/bwts_delta.h (delta filter of integer arrays, the stage in front of the byte-plane split) ...
+DELTA_EXPORTS = [
+    "bwts_delta_encode_device", "bwts_delta_decode_device", "bwts_delta_encode_segments_f_device", "bwts_delta_decode_segments_f_device",
+    "bwts_delta_encode", "bwts_delta_decode",
+]
+FILTER_NONE, FILTER_DELTA = 0, 1
 # ... and include/bwts_test.h (harness and unit-test hooks)
 TEST_EXPORTS = [
     "bwts_generate_device", "bwts_device_alloc", "bwts_device_free", "bwts_copy_to_device", "bwts_copy_to_host",
@@ -87,7 +94,7 @@ TEST_EXPORTS = [
 ]
 # bwts_debug_unpack_ranges_report: the words of the record, and the stages by their bits
 RANGES_REPORT_FIELDS = ["blocks", "runs", "covered_bytes", "stream_bytes", "gathered", "pieces", "stages", "single"]
-RANGES_STAGES = {1: "gather", 2: "decode", 4: "zrl", 8: "mtf", 16: "inverse", 32: "join", 64: "crc", 128: "cut"}
+RANGES_STAGES = {1: "gather", 2: "decode", 4: "zrl", 8: "mtf", 16: "inverse", 32: "join", 64: "crc", 128: "cut", 256: "delta"}
 # bwts_debug_inverse_report: the words of one attempt's record, and what marks, outcomes and forms are called
 INV_REPORT_FIELDS = ["g", "mark", "outcome", "s", "virtual", "node_cap", "nu", "nu2", "ucap_first", "second_collect",
                      "listed_classes", "mom_fallback", "unit_rank", "kc", "kt", "form"]
@@ -255,6 +262,13 @@ def lib():
         L.bwts_frame_members.argtypes = [vp, u64, vp, vp, u64, ctypes.POINTER(u64)]
         for name in ("bwts_unpack_members_device", "bwts_unpack_members"):
             getattr(L, name).argtypes = [vp, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64)]
+        for name in ("bwts_pack_members_f_device", "bwts_pack_members_f"):
+            getattr(L, name).argtypes = [vp, vp, vp, vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
+        L.bwts_frame_members_f.argtypes = [vp, u64, vp, vp, vp, u64, ctypes.POINTER(u64)]
+        for name in ("bwts_delta_encode_device", "bwts_delta_decode_device", "bwts_delta_encode", "bwts_delta_decode"):
+            getattr(L, name).argtypes = [vp, vp, u64, u32, vp]
+        for name in ("bwts_delta_encode_segments_f_device", "bwts_delta_decode_segments_f_device"):
+            getattr(L, name).argtypes = [vp, vp, vp, vp, vp, u64, vp]
         for name in ("bwts_forward_sink", "bwts_inverse_sink"):
             getattr(L, name).argtypes = [vp, vp, u64, SINK_FN, vp]
         L.bwts_generate_device.argtypes = [vp, i32, u64, u64, vp]
@@ -602,6 +616,31 @@ class Context:
         ls = np.ascontiguousarray(lengths, dtype=np.uint64)
         self._check(lib().bwts_planes_join_segments_device(self._h, _ptr(d_in), ls.ctypes.data, ls.size, int(width), _ptr(d_out)))
 
+    # -- delta filter in front of the byte-plane split (include/bwts_delta.h) -------------------------------
+    def delta_encode(self, data, width):
+        """bwts_delta_encode: every `width`-byte element replaced by the zigzag of its difference to the one before, the tail copied
+        (host buffers)."""
+        return self._planes_host(lib().bwts_delta_encode, data, width)
+
+    def delta_decode(self, data, width):
+        """bwts_delta_decode: the inverse of delta_encode (host buffers)."""
+        return self._planes_host(lib().bwts_delta_decode, data, width)
+
+    def delta_encode_device(self, d_in, n, width, d_out):
+        self._check(lib().bwts_delta_encode_device(self._h, _ptr(d_in), int(n), int(width), _ptr(d_out)))
+
+    def delta_decode_device(self, d_in, n, width, d_out):
+        self._check(lib().bwts_delta_decode_device(self._h, _ptr(d_in), int(n), int(width), _ptr(d_out)))
+
+    def delta_encode_segments_f_device(self, d_in, lengths, widths, filters, d_out):
+        """bwts_delta_encode_segments_f_device: every segment at its own width, encoded (filter 1) or copied (filter 0), where it lies."""
+        ls, ws, fs = _members_f(lengths, widths, filters)
+        self._check(lib().bwts_delta_encode_segments_f_device(self._h, _ptr(d_in), ls.ctypes.data, ws.ctypes.data, fs.ctypes.data, ls.size, _ptr(d_out)))
+
+    def delta_decode_segments_f_device(self, d_in, lengths, widths, filters, d_out):
+        ls, ws, fs = _members_f(lengths, widths, filters)
+        self._check(lib().bwts_delta_decode_segments_f_device(self._h, _ptr(d_in), ls.ctypes.data, ws.ctypes.data, fs.ctypes.data, ls.size, _ptr(d_out)))
+
     # -- the chain as one call: a checksummed frame (include/bwts_pack.h) -----------------------------
     def crc32_device(self, d_in, n):
         """bwts_crc32_device: zlib's CRC-32 of n device bytes."""
@@ -702,24 +741,27 @@ class Context:
         ls, ws = _members(lengths, widths)
         self._check(lib().bwts_planes_join_segments_w_device(self._h, _ptr(d_in), ls.ctypes.data, ws.ctypes.data, ls.size, _ptr(d_out)))
 
-    def pack_members(self, arrays, widths=None, out_cap=None):
-        """bwts_pack_members: one member frame of the arrays (bytes-like, or numpy arrays of any dtype, taken as their bytes); widths: one
-        of 1, 2, 4, 8 per array, None for no split at all -- named by the caller, never guessed from a dtype (host buffers)."""
+    def pack_members(self, arrays, widths=None, filters=None, out_cap=None):
+        """bwts_pack_members_f: one member frame of the arrays (bytes-like, or numpy arrays of any dtype, taken as their bytes); widths: one
+        of 1, 2, 4, 8 per array, None for no split at all; filters: 0 or 1 (FILTER_DELTA: the delta filter of include/bwts_delta.h at the
+        array's width) per array, None for none -- both named by the caller, never guessed from a dtype (host buffers)."""
         parts = [_bytes_of(a) for a in arrays]
         ls, ws = _members([p.size for p in parts], widths)
+        fs = _filters(ls, filters)
         a = np.concatenate(parts) if parts else np.empty(0, dtype=np.uint8)
         out = np.empty(pack_members_bound(ls) if out_cap is None else int(out_cap), dtype=np.uint8)
         got = ctypes.c_uint64(0)
-        self._check(lib().bwts_pack_members(self._h, a.ctypes.data, ls.ctypes.data, None if ws is None else ws.ctypes.data, ls.size,
-                                            out.ctypes.data, out.size, ctypes.byref(got)))
+        self._check(lib().bwts_pack_members_f(self._h, a.ctypes.data, ls.ctypes.data, None if ws is None else ws.ctypes.data,
+                                              None if fs is None else fs.ctypes.data, ls.size, out.ctypes.data, out.size, ctypes.byref(got)))
         return out[:got.value].copy()
 
-    def pack_members_device(self, d_in, lengths, widths, d_out, out_cap):
-        """bwts_pack_members_device: the members lie back to back in d_in; returns the frame's size in bytes."""
+    def pack_members_device(self, d_in, lengths, widths, d_out, out_cap, filters=None):
+        """bwts_pack_members_f_device: the members lie back to back in d_in; returns the frame's size in bytes."""
         ls, ws = _members(lengths, widths)
+        fs = _filters(ls, filters)
         got = ctypes.c_uint64(0)
-        self._check(lib().bwts_pack_members_device(self._h, _ptr(d_in), ls.ctypes.data, None if ws is None else ws.ctypes.data, ls.size,
-                                                   _ptr(d_out), int(out_cap), ctypes.byref(got)))
+        self._check(lib().bwts_pack_members_f_device(self._h, _ptr(d_in), ls.ctypes.data, None if ws is None else ws.ctypes.data,
+                                                     None if fs is None else fs.ctypes.data, ls.size, _ptr(d_out), int(out_cap), ctypes.byref(got)))
         return int(got.value)
 
     def unpack_members(self, frame, indices=None):
@@ -1030,6 +1072,24 @@ def _members(lengths, widths):
     return ls, ws
 
 
+def _filters(ls, filters):
+    """The filters of a member call as the array the library takes; None stays None (no filter)."""
+    if filters is None:
+        return None
+    fs = np.ascontiguousarray(filters, dtype=np.uint32).reshape(-1)
+    if fs.size != ls.size:
+        raise BwtsError(-1, "one filter per member")
+    return fs
+
+
+def _members_f(lengths, widths, filters):
+    """Lengths, widths and filters of a segment call of the delta filter: all three named."""
+    if widths is None or filters is None:
+        raise BwtsError(-1, "a width and a filter per segment")
+    ls, ws = _members(lengths, widths)
+    return ls, ws, _filters(ls, filters)
+
+
 def pack_members_bound(lengths):
     """bwts_pack_members_bound: the largest member frame of members of these lengths."""
     ls = np.ascontiguousarray(lengths, dtype=np.uint64).reshape(-1)
@@ -1052,6 +1112,20 @@ def frame_members(frame):
     if rc != 0:
         raise BwtsError(rc, lib().bwts_strerror(rc).decode())
     return ls.tolist(), ws.tolist()
+
+
+def frame_member_filters(frame):
+    """bwts_frame_members_f: the members' filters, a list (all 0 for a version-1 frame), from header and directory (host arithmetic)."""
+    a = _u8(frame)
+    count = ctypes.c_uint64(0)
+    rc = lib().bwts_frame_members_f(a.ctypes.data, a.size, None, None, None, 0, ctypes.byref(count))
+    if rc != 0:
+        raise BwtsError(rc, lib().bwts_strerror(rc).decode())
+    fs = np.zeros(count.value, dtype=np.uint32)
+    rc = lib().bwts_frame_members_f(a.ctypes.data, a.size, None, None, fs.ctypes.data, fs.size, ctypes.byref(count))
+    if rc != 0:
+        raise BwtsError(rc, lib().bwts_strerror(rc).decode())
+    return fs.tolist()
 
 
 def _ranges(ranges):

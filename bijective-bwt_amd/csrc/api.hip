@@ -12,6 +12,7 @@
 #include "pack_plan.h"
 #include "members_plan.h"
 #include "../../include/bwts_members.h"
+#include "../../include/bwts_delta.h"
 
 #include <algorithm>
 #include <new>
@@ -627,6 +628,70 @@ extern "C" int bwts_planes_join(bwts_ctx *ctx, const uint8_t *in, uint64_t n, ui
 }
 
 // ------------------------------------------------------------------------------------
+// delta filter in front of the byte-plane split (include/bwts_delta.h): n bytes to n bytes at a width, the kernels in delta.hip
+// ------------------------------------------------------------------------------------
+static int delta_device(bwts_ctx *ctx, const void *d_in, uint64_t n, uint32_t width, void *d_out, bool decode)
+{
+    if (!ctx || !d_in || !d_out || n == 0 || !delta_width_ok(width)) return BWTS_E_ARG;
+    if (n > DELTA_MAX_N) return BWTS_E_RANGE;
+    if (ranges_overlap(d_in, n, d_out, n)) return BWTS_E_ARG;
+    return run_sized(ctx, n, decode ? "delta decode" : "delta encode", [&] { return delta_impl(ctx, (const u8 *)d_in, n, width, (u8 *)d_out, decode); });
+}
+
+static int delta_segments_f_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters, uint64_t count,
+                                   void *d_out, bool decode)
+{
+    if (!ctx || !d_in || !d_out || !widths || !filters) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(seg_table_set(ctx, lengths, count, &n));
+    for (u64 s = 0; s < count; s++)
+        if (!delta_width_ok(widths[s]) || !delta_filter_ok(filters[s])) return BWTS_E_ARG;
+    if (ranges_overlap(d_in, n, d_out, n)) return BWTS_E_ARG;
+    return run_sized(ctx, n, decode ? "delta decode" : "delta encode", [&] { return delta_f_impl(ctx, (const u8 *)d_in, n, widths, filters, (u8 *)d_out, decode); });
+}
+
+static int delta_host(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint32_t width, uint8_t *out, bool decode)
+{
+    if (!ctx || !in || !out || n == 0 || !delta_width_ok(width)) return BWTS_E_ARG;
+    if (n > DELTA_MAX_N) return BWTS_E_RANGE;
+    u64 made = 0;
+    const HostTrip trip = {in, n, n, out, &made};
+    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *got) { *got = n; return delta_device(ctx, d_in, n, width, d_out, decode); });
+}
+
+extern "C" int bwts_delta_encode_device(bwts_ctx *ctx, const void *d_in, uint64_t n, uint32_t width, void *d_out)
+{
+    return delta_device(ctx, d_in, n, width, d_out, false);
+}
+
+extern "C" int bwts_delta_decode_device(bwts_ctx *ctx, const void *d_in, uint64_t n, uint32_t width, void *d_out)
+{
+    return delta_device(ctx, d_in, n, width, d_out, true);
+}
+
+extern "C" int bwts_delta_encode_segments_f_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters,
+                                                   uint64_t count, void *d_out)
+{
+    return delta_segments_f_device(ctx, d_in, lengths, widths, filters, count, d_out, false);
+}
+
+extern "C" int bwts_delta_decode_segments_f_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters,
+                                                   uint64_t count, void *d_out)
+{
+    return delta_segments_f_device(ctx, d_in, lengths, widths, filters, count, d_out, true);
+}
+
+extern "C" int bwts_delta_encode(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint32_t width, uint8_t *out)
+{
+    return delta_host(ctx, in, n, width, out, false);
+}
+
+extern "C" int bwts_delta_decode(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint32_t width, uint8_t *out)
+{
+    return delta_host(ctx, in, n, width, out, true);
+}
+
+// ------------------------------------------------------------------------------------
 // checksum and the packed frame (include/bwts_pack.h): the chain of the three stages as one call, the kernel in crc.hip, the drivers
 // in pack.hip
 // ------------------------------------------------------------------------------------
@@ -835,43 +900,66 @@ extern "C" uint64_t bwts_pack_members_bound(const uint64_t *lengths, uint64_t co
     return members_bound_bytes(lengths, count);
 }
 
-extern "C" int bwts_pack_members_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, uint64_t count, void *d_out,
-                                        uint64_t out_cap, uint64_t *out_bytes)
+extern "C" int bwts_pack_members_f_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters, uint64_t count,
+                                          void *d_out, uint64_t out_cap, uint64_t *out_bytes)
 {
     if (!ctx || !d_in || !d_out || !out_bytes || ((uintptr_t)d_out & 15)) return BWTS_E_ARG;
     u64 n = 0;
-    BWTS_TRY(members_args_check(lengths, widths, count, &n));
+    BWTS_TRY(members_args_check_f(lengths, widths, filters, count, &n));
     if (ranges_overlap(d_in, n, d_out, out_cap)) return BWTS_E_ARG;
-    return run_sized(ctx, n, "pack members", [&] { return pack_members_device_impl(ctx, (const u8 *)d_in, lengths, widths, count, n, (u8 *)d_out, out_cap, out_bytes); });
+    return run_sized(ctx, n, "pack members", [&] {
+        return pack_members_device_impl(ctx, (const u8 *)d_in, lengths, widths, filters, count, n, (u8 *)d_out, out_cap, out_bytes);
+    });
+}
+
+extern "C" int bwts_pack_members_f(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters, uint64_t count,
+                                   uint8_t *out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!ctx || !in || !out || !out_bytes) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(members_args_check_f(lengths, widths, filters, count, &n));
+    const u64 bound = members_bound_bytes(lengths, count);
+    const u64 cap = out_cap < bound ? out_cap : bound;
+    if (cap < members_least_bytes(count)) return BWTS_E_SPACE;
+    const HostTrip trip = {in, n, n > cap ? n : cap, out, out_bytes};
+    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *bytes) {
+        return bwts_pack_members_f_device(ctx, d_in, lengths, widths, filters, count, d_out, cap, bytes);
+    });
+}
+
+extern "C" int bwts_pack_members_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, uint64_t count, void *d_out,
+                                        uint64_t out_cap, uint64_t *out_bytes)
+{
+    return bwts_pack_members_f_device(ctx, d_in, lengths, widths, nullptr, count, d_out, out_cap, out_bytes);
 }
 
 extern "C" int bwts_pack_members(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, const uint32_t *widths, uint64_t count, uint8_t *out,
                                  uint64_t out_cap, uint64_t *out_bytes)
 {
-    if (!ctx || !in || !out || !out_bytes) return BWTS_E_ARG;
-    u64 n = 0;
-    BWTS_TRY(members_args_check(lengths, widths, count, &n));
-    const u64 bound = members_bound_bytes(lengths, count);
-    const u64 cap = out_cap < bound ? out_cap : bound;
-    if (cap < members_least_bytes(count)) return BWTS_E_SPACE;
-    const HostTrip trip = {in, n, n > cap ? n : cap, out, out_bytes};
-    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *bytes) { return bwts_pack_members_device(ctx, d_in, lengths, widths, count, d_out, cap, bytes); });
+    return bwts_pack_members_f(ctx, in, lengths, widths, nullptr, count, out, out_cap, out_bytes);
 }
 
-extern "C" int bwts_frame_members(const uint8_t *frame, uint64_t in_bytes, uint64_t *lengths_out, uint32_t *widths_out, uint64_t cap, uint64_t *count)
+extern "C" int bwts_frame_members_f(const uint8_t *frame, uint64_t in_bytes, uint64_t *lengths_out, uint32_t *widths_out, uint32_t *filters_out, uint64_t cap,
+                                    uint64_t *count)
 {
     if (!frame || !count || in_bytes == 0) return BWTS_E_ARG;
     MembersHeader M;
     u64 frame_bytes = 0;
     BWTS_TRY(members_header_check(frame, in_bytes, &M));
     BWTS_TRY(members_directory_check(frame + MEMBERS_HEADER_BYTES, M, in_bytes, true, &frame_bytes));
-    if ((lengths_out || widths_out) && cap < M.count) return BWTS_E_SPACE;
+    if ((lengths_out || widths_out || filters_out) && cap < M.count) return BWTS_E_SPACE;
     for (u64 k = 0; k < M.count; k++) {
         if (lengths_out) lengths_out[k] = members_entry_len(frame + MEMBERS_HEADER_BYTES, k);
         if (widths_out) widths_out[k] = members_entry_width(frame + MEMBERS_HEADER_BYTES, k);
+        if (filters_out) filters_out[k] = members_entry_filter(frame + MEMBERS_HEADER_BYTES, k);
     }
     *count = M.count;
     return BWTS_OK;
+}
+
+extern "C" int bwts_frame_members(const uint8_t *frame, uint64_t in_bytes, uint64_t *lengths_out, uint32_t *widths_out, uint64_t cap, uint64_t *count)
+{
+    return bwts_frame_members_f(frame, in_bytes, lengths_out, widths_out, nullptr, cap, count);
 }
 
 extern "C" int bwts_unpack_members_device(bwts_ctx *ctx, const void *d_in, uint64_t in_bytes, const uint64_t *indices, uint64_t icount, void *d_out,

@@ -348,6 +348,10 @@ int planes_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u32 w, u8 *d_out, bool joi
 int planes_w_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, const u32 *widths, u8 *d_out, bool join);     // the context's table, a width (1, 2, 4, 8) per segment
 void bwts_planes_plan(u64 n, u32 w, u64 out[4]);                        // tile bytes, tiles, elements and tail bytes of one input of n bytes
 
+// ---- delta filter in front of the byte-plane split (delta.hip; include/bwts_delta.h) ----
+int delta_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u32 w, u8 *d_out, bool decode);                 // one input of n bytes at width 1, 2, 4 or 8
+int delta_f_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, const u32 *widths, const u32 *filters, u8 *d_out, bool decode);   // the context's table, a width and a filter per segment
+
 // ---- checksum and the packed frame (crc.hip, pack.hip; include/bwts_pack.h) ------------
 // one value for the input of n bytes, or one per segment, to the host
 int crc_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, SegMode segs, u32 *crcs);
@@ -361,8 +365,9 @@ struct PackPiece;
 // indices: not null for whole members of a member frame as the ranges (ranges is then not read; count indices)
 int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool packed, const PackRange *ranges, u64 count, u8 *d_out, u64 out_cap, u64 *out_bytes,
                               const u64 *indices = nullptr);
-// the member frame (include/bwts_members.h); lengths and widths have passed members_args_check, n is their sum
-int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, u64 count, u64 n, u8 *d_out, u64 out_cap, u64 *out_bytes);
+// the member frame (include/bwts_members.h); lengths, widths and filters (null: none) have passed members_args_check_f, n is the lengths' sum
+int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, const u32 *filters, u64 count, u64 n, u8 *d_out, u64 out_cap,
+                             u64 *out_bytes);
 // pieces of one device buffer to another, at any alignment (pieces.hip); every piece inside both buffers, by the caller's check
 int copy_pieces_impl(bwts_ctx *ctx, const u8 *d_src, u64 src_bytes, const PackPiece *pieces, u64 count, u8 *d_dst);
 

@@ -2,11 +2,14 @@
 // bound, what makes its header and directory valid, and which members a list of byte ranges touches.  In the style of pack_plan.h,
 // whose codes, CRC-32 and range types it uses: pack.hip, the host side of the calls and a stand-alone host program
 // (tests/members_plan_check.cc, built with the sanitizers) all compile this file.
+// Version 2 of the frame names a filter (delta_plan.h) beside a member's width; tests/delta_plan_check.cc holds its predicates.
 #pragma once
 #include "pack_plan.h"
+#include "delta_plan.h"
 
 #define MEMBERS_MAGIC 0x4D545742u        // "BWTM"
 #define MEMBERS_VERSION 1u
+#define MEMBERS_VERSION_2 2u             // entries may name a filter (delta_plan.h) beside the width; written only where one does
 #define MEMBERS_HEADER_BYTES 32u
 #define MEMBERS_ENTRY_BYTES 32u
 #define MEMBERS_MAX_COUNT (1ull << 20)   // the largest directory a "BWTZ" frame can have: 2^32 / 4096
@@ -15,14 +18,30 @@
 EC_HD bool members_magic(const uint8_t *h) { return ec_le32(h) == MEMBERS_MAGIC; }
 EC_HD uint64_t members_fixed_bytes(uint64_t count) { return MEMBERS_HEADER_BYTES + (uint64_t)MEMBERS_ENTRY_BYTES * count; }
 
-// What a pack is asked for: PACK_ARG for no members, a zero length or a bad width (widths == NULL: all 1), PACK_RANGE for more than
-// 2^20 members or more than 2^32 bytes, else PACK_OK and *n.  The sum cannot wrap: it is held against 2^32 after every member.
-static inline int members_args_check(const uint64_t *lengths, const uint32_t *widths, uint64_t count, uint64_t *n)
+// The word at offset 12 of an entry: the width in bits 0-7, in a version-2 frame the filter in bits 8-15, nothing above.  In a
+// version-1 frame the whole word is the width, as it always was.
+EC_HD bool members_word_ok(uint32_t word, uint32_t version)
+{
+    if (version != MEMBERS_VERSION_2) return planes_width_w_ok(word);
+    return planes_width_w_ok(word & 0xffu) && delta_filter_ok((word >> 8) & 0xffu) && (word >> 16) == 0;
+}
+// does any member name a filter?  (filters == NULL: none does.)  Such a pack writes a version-2 frame, every other one version 1.
+static inline bool members_any_filter(const uint32_t *filters, uint64_t count)
+{
+    for (uint64_t k = 0; filters && k < count; k++)
+        if (filters[k] != DELTA_FILTER_NONE) return true;
+    return false;
+}
+
+// What a pack is asked for: PACK_ARG for no members, a zero length, a bad width (widths == NULL: all 1) or a bad filter (filters ==
+// NULL: none), PACK_RANGE for more than 2^20 members or more than 2^32 bytes, else PACK_OK and *n.  The sum cannot wrap: it is held
+// against 2^32 after every member.
+static inline int members_args_check_f(const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters, uint64_t count, uint64_t *n)
 {
     if (!lengths || count == 0) return PACK_ARG;
     if (count > MEMBERS_MAX_COUNT) return PACK_RANGE;
     for (uint64_t k = 0; k < count; k++)
-        if (lengths[k] == 0 || (widths && !planes_width_w_ok(widths[k]))) return PACK_ARG;
+        if (lengths[k] == 0 || (widths && !planes_width_w_ok(widths[k])) || (filters && !delta_filter_ok(filters[k]))) return PACK_ARG;
     uint64_t sum = 0;
     for (uint64_t k = 0; k < count; k++) {
         if (lengths[k] > PACK_MAX_N - sum) return PACK_RANGE;
@@ -30,6 +49,10 @@ static inline int members_args_check(const uint64_t *lengths, const uint32_t *wi
     }
     *n = sum;
     return PACK_OK;
+}
+static inline int members_args_check(const uint64_t *lengths, const uint32_t *widths, uint64_t count, uint64_t *n)
+{
+    return members_args_check_f(lengths, widths, nullptr, count, n);
 }
 
 // 32 + 32 count + the coder's bound of every member (the split never changes a length, the zero-run stage never expands); 0 on
@@ -50,28 +73,32 @@ EC_HD void members_entry_write(uint8_t e[32], uint64_t stream_bytes, uint32_t cr
     pack_put64(e, stream_bytes); ec_put32(e + 8, crc); ec_put32(e + 12, width); pack_put64(e + 16, coded_bytes); pack_put64(e + 24, len);
 }
 // the header of a frame whose directory (count entries) is complete
-EC_HD void members_header_write(uint8_t h[32], uint64_t n, uint64_t count, const uint8_t *dir)
+EC_HD void members_header_write_v(uint8_t h[32], uint32_t version, uint64_t n, uint64_t count, const uint8_t *dir)
 {
-    ec_put32(h, MEMBERS_MAGIC); ec_put32(h + 4, MEMBERS_VERSION); pack_put64(h + 8, n); pack_put64(h + 16, count);
+    ec_put32(h, MEMBERS_MAGIC); ec_put32(h + 4, version); pack_put64(h + 8, n); pack_put64(h + 16, count);
     ec_put32(h + 24, crc32_bytes(dir, (uint64_t)MEMBERS_ENTRY_BYTES * count));
     ec_put32(h + 28, crc32_bytes(h, 28));
 }
+EC_HD void members_header_write(uint8_t h[32], uint64_t n, uint64_t count, const uint8_t *dir)
+{
+    members_header_write_v(h, MEMBERS_VERSION, n, count, dir);
+}
 
-struct MembersHeader { uint64_t n, count; uint32_t dir_crc; };
+struct MembersHeader { uint64_t n, count; uint32_t dir_crc, version; };
 
 // The header of a frame of which in_bytes bytes are at hand (h: the first 32 of them, read only when in_bytes allows a frame at all).
 // PACK_OK and *H, PACK_FORMAT, or PACK_RANGE for a sound header that names more than 2^32 bytes or more than 2^20 members.
 EC_HD int members_header_check(const uint8_t *h, uint64_t in_bytes, MembersHeader *H)
 {
     if (in_bytes < MEMBERS_LEAST_FRAME || (in_bytes & 15u)) return PACK_FORMAT;
-    if (ec_le32(h) != MEMBERS_MAGIC || ec_le32(h + 4) != MEMBERS_VERSION) return PACK_FORMAT;
+    if (ec_le32(h) != MEMBERS_MAGIC || (ec_le32(h + 4) != MEMBERS_VERSION && ec_le32(h + 4) != MEMBERS_VERSION_2)) return PACK_FORMAT;
     if (ec_le32(h + 28) != crc32_bytes(h, 28)) return PACK_FORMAT;
     const uint64_t n = pack_le64(h + 8), count = pack_le64(h + 16);
     if (n == 0) return PACK_FORMAT;
     if (n > PACK_MAX_N) return PACK_RANGE;
     if (count == 0 || count > n) return PACK_FORMAT;
     if (count > MEMBERS_MAX_COUNT) return PACK_RANGE;
-    H->n = n; H->count = count; H->dir_crc = ec_le32(h + 24);
+    H->n = n; H->count = count; H->dir_crc = ec_le32(h + 24); H->version = ec_le32(h + 4);
     if (members_fixed_bytes(count) > in_bytes) return PACK_FORMAT;
     return PACK_OK;
 }
@@ -82,16 +109,20 @@ EC_HD int members_directory_check(const uint8_t *dir, const MembersHeader &H, ui
 {
     if (crc32_bytes(dir, (uint64_t)MEMBERS_ENTRY_BYTES * H.count) != H.dir_crc) return PACK_FORMAT;
     uint64_t total = members_fixed_bytes(H.count), sum = 0;
+    bool filtered = false;
     for (uint64_t k = 0; k < H.count; k++) {
         const uint8_t *e = dir + (uint64_t)MEMBERS_ENTRY_BYTES * k;
         const uint64_t sb = pack_le64(e), coded = pack_le64(e + 16), len = pack_le64(e + 24);
-        if (!planes_width_w_ok(ec_le32(e + 12))) return PACK_FORMAT;
+        if (!members_word_ok(ec_le32(e + 12), H.version)) return PACK_FORMAT;
+        filtered = filtered || (ec_le32(e + 12) >> 8) != 0;
         if (len == 0 || len > H.n - sum) return PACK_FORMAT;       // (by subtraction: the running sum stays within n <= 2^32)
         sum += len;
         if (coded == 0 || coded > len) return PACK_FORMAT;
         if ((sb & 15u) || sb < ec_least_bytes(coded) || sb > ec_bound_bytes(coded)) return PACK_FORMAT;      // (so the sum cannot overflow)
         total += sb;
     }
+    // the frame is canonical: version 2 is written only where an entry names a filter
+    if (H.version == MEMBERS_VERSION_2 && !filtered) return PACK_FORMAT;
     if (sum != H.n) return PACK_FORMAT;
     if (exact ? total != in_bytes : total > in_bytes) return PACK_FORMAT;
     *frame_bytes = total;
@@ -99,7 +130,9 @@ EC_HD int members_directory_check(const uint8_t *dir, const MembersHeader &H, ui
 }
 
 EC_HD uint64_t members_entry_len(const uint8_t *dir, uint64_t k) { return pack_le64(dir + (uint64_t)MEMBERS_ENTRY_BYTES * k + 24); }
-EC_HD uint32_t members_entry_width(const uint8_t *dir, uint64_t k) { return ec_le32(dir + (uint64_t)MEMBERS_ENTRY_BYTES * k + 12); }
+// width and filter of an entry of a directory that passed its check
+EC_HD uint32_t members_entry_width(const uint8_t *dir, uint64_t k) { return ec_le32(dir + (uint64_t)MEMBERS_ENTRY_BYTES * k + 12) & 0xffu; }
+EC_HD uint32_t members_entry_filter(const uint8_t *dir, uint64_t k) { return (ec_le32(dir + (uint64_t)MEMBERS_ENTRY_BYTES * k + 12) >> 8) & 0xffu; }
 
 // where every member begins in the concatenation: count + 1 offsets, off[count] = n (a directory that passed its check)
 static inline std::vector<uint64_t> members_offsets(const uint8_t *dir, uint64_t count)

@@ -1,5 +1,6 @@
-// pack.hip -- the chain as one call (include/bwts_pack.h): checksums, byte-plane split (frame version 3), transform, move-to-front,
-// zero-run coding (frame versions 2 and 3) and entropy coder over the blocks of a frame, and the way back.  No kernel of its own: the stages are the ones behind the single calls, run one after the other inside
+// pack.hip -- the chain as one call (include/bwts_pack.h): checksums, delta filter (member frame version 2), byte-plane split (frame
+// version 3), transform, move-to-front, zero-run coding (frame versions 2 and 3) and entropy coder over the blocks of a frame, and the
+// way back.  No kernel of its own: the stages are the ones behind the single calls, run one after the other inside
 // one call bracket; the frame's arithmetic and the checks of an untrusted frame are in pack_plan.h.
 //
 // A frame of one block goes through the single-input stages, one of several blocks through the segment forms (the bytes are the
@@ -126,15 +127,36 @@ static bool widths_split(const std::vector<u32> &widths)
     return false;
 }
 
-// A member frame: pack_device_impl's chain over members of any lengths, each split at its own width (1: not at all), with the entries
-// and the header of include/bwts_members.h.  One member goes through the single-input stages.
-int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, u64 count, u64 n, u8 *d_out, u64 out_cap, u64 *out_bytes)
+// is any block filtered?  (none outside a version-2 member frame, whose list alone is not empty)
+static bool filters_named(const std::vector<u32> &filters)
+{
+    for (u32 f : filters) if (f != DELTA_FILTER_NONE) return true;
+    return false;
+}
+
+// the delta filter (delta.hip) over blocks of `total` bytes in all: one block through the single-input stage, several in one launch
+// per sweep at the widths and filters given
+static int frame_delta(bwts_ctx *ctx, const u8 *from, u64 total, const std::vector<u32> &widths, const std::vector<u32> &filters, u8 *to, bool decode,
+                       SegMode segs)
+{
+    if (!segs.table()) return delta_impl(ctx, from, total, widths[0], to, decode);
+    return delta_f_impl(ctx, from, total, widths.data(), filters.data(), to, decode);
+}
+
+// A member frame: pack_device_impl's chain over members of any lengths, each filtered if asked (filters: null for none) and split at
+// its own width (1: not at all), with the entries and the header of include/bwts_members.h.  One member goes through the single-input
+// stages.  A pack in which no member names a filter writes the version-1 frame.
+int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, const u32 *filters, u64 count, u64 n, u8 *d_out, u64 out_cap,
+                             u64 *out_bytes)
 {
     const u64 fixed = members_fixed_bytes(count);
     const bool seg = count > 1;
     if (out_cap < members_least_bytes(count)) return BWTS_E_SPACE;
     std::vector<u32> ws((size_t)count, 1u);
     if (widths) ws.assign(widths, widths + count);
+    std::vector<u32> fs((size_t)count, DELTA_FILTER_NONE);
+    if (filters) fs.assign(filters, filters + count);
+    const bool delta = filters_named(fs);
     auto members_set = [&] { u64 total = 0; return seg ? seg_table_set(ctx, lengths, count, &total) : BWTS_OK; };
     BWTS_TRY(members_set());
     SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
@@ -146,6 +168,11 @@ int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, 
     BWTS_TRY(pack_stage(ctx, 1, n, &other));
     const u8 *from = d_in;
     auto done = [&] { from = to; std::swap(to, other); return hipStreamSynchronize(ctx->stream); };
+    if (delta) {
+        // every filtered member on its own; the checksums above are the original bytes'
+        BWTS_TRY(frame_delta(ctx, from, n, ws, fs, to, false, segs));
+        HIPC(done());
+    }
     if (widths_split(ws)) {
         bool alike = true;
         for (u32 w : ws) alike = alike && w == ws[0];
@@ -168,11 +195,11 @@ int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, 
     BWTS_TRY(pack_dir_staging(ctx, PACK_VERSION_3, count, own, &dir));
     u64 total = fixed;
     for (u64 k = 0; k < count; k++) {
-        members_entry_write(dir + (u64)MEMBERS_ENTRY_BYTES * k, sizes[(size_t)k], crcs[(size_t)k], ws[(size_t)k], coded[(size_t)k], lengths[k]);
+        members_entry_write(dir + (u64)MEMBERS_ENTRY_BYTES * k, sizes[(size_t)k], crcs[(size_t)k], delta_word(ws[(size_t)k], fs[(size_t)k]), coded[(size_t)k], lengths[k]);
         total += sizes[(size_t)k];
     }
     if (total > out_cap) return BWTS_E_INTERNAL;
-    members_header_write(head, n, count, dir);
+    members_header_write_v(head, delta ? MEMBERS_VERSION_2 : MEMBERS_VERSION, n, count, dir);
     HIPC(hipMemcpyAsync(d_out + MEMBERS_HEADER_BYTES, dir, (u64)MEMBERS_ENTRY_BYTES * count, hipMemcpyHostToDevice, ctx->stream));
     HIPC(hipMemcpyAsync(d_out, head, MEMBERS_HEADER_BYTES, hipMemcpyHostToDevice, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
@@ -195,6 +222,7 @@ struct FrameHead {
     std::vector<u64> off;       // members: where every member begins in the concatenation (count + 1)
     u64 len_at(u64 k) const { return members ? off[(size_t)k + 1] - off[(size_t)k] : pack_block_at(H.n, H.B, k); }
     u32 width_at(u64 k) const { return members ? members_entry_width(dir, k) : H.width; }
+    u32 filter_at(u64 k) const { return members ? members_entry_filter(dir, k) : DELTA_FILTER_NONE; }
 };
 
 // the blocks of a judged frame as the segment table of the stages
@@ -224,7 +252,7 @@ static int unpack_members_head(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, cons
     MembersHeader M;
     BWTS_TRY(members_header_check(head, in_bytes, &M));
     F.members = true;
-    F.H = PackHeader{M.n, 0, M.count, M.dir_crc, PACK_VERSION_3, 0u};
+    F.H = PackHeader{M.n, 0, M.count, M.dir_crc, PACK_VERSION_3, 0u};      // (either version of the member frame)
     F.fixed = members_fixed_bytes(M.count);
     F.entry = MEMBERS_ENTRY_BYTES;
     BWTS_TRY(pack_dir_staging(ctx, PACK_VERSION_3, M.count, F.own, &F.dir));
@@ -271,10 +299,10 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
     BWTS_TRY(unpack_frame_head(ctx, d_in, in_bytes, F));
     const PackHeader &H = F.H;
     const u8 *dir = F.dir;
-    std::vector<u32> widths;
+    std::vector<u32> widths, filters;
     if (H.version == PACK_VERSION_3)
-        for (u64 k = 0; k < H.nblk; k++) widths.push_back(F.width_at(k));
-    const bool seg = H.nblk > 1, zrl = H.version != PACK_VERSION, planes = widths_split(widths);
+        for (u64 k = 0; k < H.nblk; k++) { widths.push_back(F.width_at(k)); filters.push_back(F.filter_at(k)); }
+    const bool seg = H.nblk > 1, zrl = H.version != PACK_VERSION, planes = widths_split(widths), delta = filters_named(filters);
     const u64 fixed = F.fixed, entry = F.entry;
     const SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
     if (H.n > out_cap) return BWTS_E_SPACE;
@@ -290,10 +318,11 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
     // The stages go to and fro between d_out and the stage block, and the last one lands in d_out.  Version 1, three stages: ranks
     // into d_out, bytes of the transform into the block, the input's bytes into d_out.  Version 2, four: the ranks' coded bytes into
     // the block first.  Version 3, five: the coded bytes into d_out first (they are no more than the H.n bytes it holds), the ranks
-    // into the block, and at the end the join from the block into d_out.
+    // into the block, and at the end the join from the block into d_out.  A member frame with filters has the delta decode behind the
+    // join (or in its place): one stage more, and the first one writes the other buffer.
     u8 *block = nullptr;
     BWTS_TRY(pack_stage(ctx, 0, H.n, &block));
-    const bool odd = !zrl || planes;        // an odd number of stages: the first one writes d_out
+    const bool odd = (3 + zrl + planes + delta) % 2 != 0;        // an odd number of stages: the first one writes d_out
     u8 *to = odd ? d_out : block, *other = odd ? block : d_out;
     const u8 *from = nullptr;
     auto done = [&] { from = to; std::swap(to, other); return hipStreamSynchronize(ctx->stream); };
@@ -328,6 +357,10 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
         BWTS_TRY(frame_join(ctx, from, H.n, widths, to, segs));
         HIPC(done());
     }
+    if (delta) {
+        BWTS_TRY(frame_delta(ctx, from, H.n, widths, filters, to, true, segs));
+        HIPC(done());
+    }
     if (from != d_out) return BWTS_E_INTERNAL;
     BWTS_TRY(crc_impl(ctx, d_out, H.n, segs, got.data()));
     if (memcmp(got.data(), want.data(), (size_t)H.nblk * sizeof(u32)) != 0) return BWTS_E_CHECKSUM;
@@ -339,7 +372,7 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
 // covered blocks, and only their streams are decoded, through the same stages over a segment table of the covered blocks alone.  The
 // bytes go to and fro between the two stage blocks (neither is d_out here); the covered blocks' checksums are held against the
 // directory, and only then are the ranges cut out of the last stage's block into d_out.
-enum { RG_GATHER = 1, RG_DECODE = 2, RG_ZRL = 4, RG_MTF = 8, RG_INVERSE = 16, RG_JOIN = 32, RG_CRC = 64, RG_CUT = 128 };
+enum { RG_GATHER = 1, RG_DECODE = 2, RG_ZRL = 4, RG_MTF = 8, RG_INVERSE = 16, RG_JOIN = 32, RG_CRC = 64, RG_CUT = 128, RG_DELTA = 256 };
 
 int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool packed, const PackRange *ranges, u64 count, u8 *d_out, u64 out_cap, u64 *out_bytes,
                               const u64 *indices)
@@ -366,11 +399,11 @@ int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool 
     const bool seg = nb > 1, gather = !packed && P.runs.size() > 1;
     // (the staging is the next stage's: what the directory says of the covered blocks is kept here)
     std::vector<u64> lengths((size_t)nb), sizes((size_t)nb), coded((size_t)nb);
-    std::vector<u32> want((size_t)nb), got((size_t)nb), widths;
+    std::vector<u32> want((size_t)nb), got((size_t)nb), widths, filters;
     for (u64 k = 0; k < nb; k++) {
         const u8 *e = F.dir + F.entry * P.blocks[(size_t)k];
         lengths[(size_t)k] = F.len_at(P.blocks[(size_t)k]);
-        if (H.version == PACK_VERSION_3) widths.push_back(F.width_at(P.blocks[(size_t)k]));
+        if (H.version == PACK_VERSION_3) { widths.push_back(F.width_at(P.blocks[(size_t)k])); filters.push_back(F.filter_at(P.blocks[(size_t)k])); }
         sizes[(size_t)k] = pack_le64(e);
         want[(size_t)k] = ec_le32(e + 8);
         coded[(size_t)k] = zrl ? pack_le64(e + 16) : lengths[(size_t)k];
@@ -421,6 +454,11 @@ int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool 
     if (widths_split(widths)) {
         BWTS_TRY(frame_join(ctx, from, C, widths, to, segs));
         HIPC(done(RG_JOIN));
+    }
+    if (filters_named(filters)) {
+        // a touched member is decoded whole, filter included
+        BWTS_TRY(frame_delta(ctx, from, C, widths, filters, to, true, segs));
+        HIPC(done(RG_DELTA));
     }
     BWTS_TRY(crc_impl(ctx, from, C, segs, got.data()));
     rep[6] |= RG_CRC;

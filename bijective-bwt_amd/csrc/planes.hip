@@ -13,7 +13,7 @@
 //   reading  planes_load16 (load16.h) reads the two aligned 16-byte pieces around an address and shifts the bytes into place in registers; a
 //            piece that does not lie inside the call's input is put together from the single bytes that do (the first and the last
 //            piece of the whole input at most), so nothing outside the input is read.
-//   writing  planes_stream_store sends a piece of len bytes from LDS: single bytes up to the destination's first 16-byte boundary (at
+//   writing  planes_stream_store (load16.h) sends a piece of len bytes from LDS: single bytes up to the destination's first 16-byte boundary (at
 //            most 15), aligned 16-byte stores behind them, each shifted into place from two aligned LDS units, and single bytes for
 //            what is left (at most 15).  At most 30 bytes of a piece of 4096 or more leave as single bytes.
 // The tail of a string (its last L mod w bytes) is copied by the workgroup of its last tile.
@@ -23,9 +23,6 @@
 #include "planes_plan.h"
 #include "../../include/bwts_planes.h"
 
-// The LDS unit (16 bytes) of unit u of a stream: one unit of padding behind every eight, so that the eight lanes whose 16-byte stores
-// the LDS takes together (units w apart in a join) fall on different banks.
-#define PLANES_SLOT(u) ((u) + ((u) >> 3))
 #define PLANES_PLANE_SLOTS (PLANES_SLOT(PLANES_E / 16u) + 2u)           // a plane's piece of a split, and the unit behind it that a shift reads
 
 // The segments of a call as the kernels see them.  off == null: one input of n bytes.
@@ -54,18 +51,6 @@ __device__ __forceinline__ PlanesTile planes_tile_at(u64 seg, u64 len, u64 j)
     return R;
 }
 
-// the segment of tile t: the last one whose first tile is not behind t (every segment has a tile, so the firsts differ)
-__device__ __forceinline__ u64 planes_tile_segment(const u64 *first, u64 count, u64 t)
-{
-    u64 lo = 0, hi = count;
-    while (hi - lo > 1) {
-        const u64 mid = lo + (hi - lo) / 2;
-        if (first[mid] <= t) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 template <int W>
 __device__ __forceinline__ PlanesTile planes_tile(const PlanesSegs &S, u64 t)
 {
@@ -80,27 +65,6 @@ __device__ __forceinline__ u32 planes_pick4(u32 a, int ba, u32 b, int bb, u32 c,
     const u32 lo = __builtin_amdgcn_perm(b, a, 0x0c0c0000u | (u32)ba | ((u32)(4 + bb) << 8));
     const u32 hi = __builtin_amdgcn_perm(d, c, 0x0c0c0000u | (u32)bc | ((u32)(4 + bd) << 8));
     return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
-}
-
-// byte i of a stream in LDS
-__device__ __forceinline__ u32 planes_lds_byte(u32 i) { return 16u * PLANES_SLOT(i >> 4) + (i & 15u); }
-
-// len bytes of a stream in LDS (unit u at PLANES_SLOT(u), one more unit readable behind the last) to dst, the whole workgroup
-__device__ __forceinline__ void planes_stream_store(const uint4 *lds, u8 *dst, u32 len)
-{
-    const u32 tid = threadIdx.x;
-    const u8 *bytes = (const u8 *)lds;
-    u32 head = (16u - (u32)((uintptr_t)dst & 15)) & 15u;
-    if (head > len) head = len;
-    const u32 vecs = (len - head) / 16u, done = head + 16u * vecs;
-    if (tid < head) dst[tid] = bytes[planes_lds_byte(tid)];
-    // store v holds the stream's bytes [head + 16 v, head + 16 v + 16): from the units v and v + 1
-    for (u32 v = tid; v < vecs; v += 256) {
-        uint4 x = lds[PLANES_SLOT(v)];
-        if (head) x = planes_funnel(x, lds[PLANES_SLOT(v + 1u)], head);
-        ((uint4 *)(dst + head))[v] = x;
-    }
-    if (tid < len - done) dst[done + tid] = bytes[planes_lds_byte(done + tid)];
 }
 
 // the tail of the tile's string: fewer than w bytes, copied
@@ -201,17 +165,6 @@ struct PlanesSegsW {
     const u64 *off, *first, *width;
     u64 count, n;
 };
-
-// tile j of a segment of width 1: PLANES_COPY_T bytes at most, copied through the LDS under the same discipline (planes_load16 in,
-// planes_stream_store out); a thread takes every 256th unit of 16 bytes
-__device__ __forceinline__ void planes_copy_tile(const u8 *__restrict__ in, u64 n, u64 seg, u64 len, u64 j, uint4 *lds, u8 *__restrict__ out)
-{
-    const u32 bytes = planes_copy_bytes(len, j), units = (bytes + 15u) / 16u;
-    const u64 at = seg + j * PLANES_COPY_T;
-    for (u32 u = threadIdx.x; u < units; u += 256) lds[PLANES_SLOT(u)] = planes_load16(in + at + 16u * u, in, in + n);
-    __syncthreads();
-    planes_stream_store(lds, out + at, bytes);
-}
 
 // LDS for the widest tile of either direction
 #define PLANES_W_SLOTS (PLANES_MAX_W * PLANES_PLANE_SLOTS > PLANES_JOIN_SLOTS(PLANES_MAX_W) ? PLANES_MAX_W * PLANES_PLANE_SLOTS : PLANES_JOIN_SLOTS(PLANES_MAX_W))

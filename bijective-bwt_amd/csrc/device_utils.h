@@ -175,6 +175,34 @@ __device__ __forceinline__ u32 digit_bases(C (*whist)[256], u32 *scan_sm)
     return block_scan_exclusive<u32, OpAdd, NWAVES>(run, OpAdd(), 0u, scan_sm, &total);
 }
 
+// The same, with the digit's base folded into the waves' starts: whist[ww][d] comes out as the first slot, in the tile, of wave ww's
+// elements with digit d, so a kernel that stages an item reads one word for it, not base and start.  The starts wait in registers
+// for the scan (the column is read once and written once, as above; the sums are those of the plain form, C holds them when it
+// holds a tile position).
+template <int NWAVES, typename C>
+__device__ __forceinline__ u32 digit_bases_folded(C (*whist)[256], u32 *scan_sm)
+{
+    const int tid = threadIdx.x;
+    u32 start[NWAVES], run = 0;
+    if (tid < 256) {
+#pragma unroll
+        for (int ww = 0; ww < NWAVES; ww++) start[ww] = whist[ww][tid];
+#pragma unroll
+        for (int ww = 0; ww < NWAVES; ww++) {
+            const u32 c = start[ww];
+            start[ww] = run;
+            run += c;
+        }
+    }
+    u32 total;
+    const u32 exc = block_scan_exclusive<u32, OpAdd, NWAVES>(run, OpAdd(), 0u, scan_sm, &total);
+    if (tid < 256) {
+#pragma unroll
+        for (int ww = 0; ww < NWAVES; ww++) whist[ww][tid] = (C)(start[ww] + exc);
+    }
+    return exc;
+}
+
 // One wave's 64 consecutive digits into its LDS bins.  Sorted and repetitive input (every pass but the first of a sort over text or
 // over ranks with many equal values) puts runs of equal digits into neighbouring lanes, and same-address LDS atomics are served one
 // lane at a time: a pass over such keys ran at 2.4 TB/s where unsorted keys reach 5.6.  So the lanes of a run elect their first one, and

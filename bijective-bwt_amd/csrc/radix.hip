@@ -13,7 +13,7 @@
 //                                 (see "packed streams" below).
 //   radix_scatter_lean_last_kernel  the last of five packed passes when few positions are expected to stay tied: the byte out,
 //                                 and the group flags of its own output instead of sorted keys and values; 7 bytes per element.
-// All are built from the same blocks: RxTile (the tile's place and its LDS), wave_rank_step and digit_bases (device_utils.h),
+// All are built from the same blocks: RxTile (the tile's place and its LDS), wave_rank_step and digit_bases / digit_bases_folded (device_utils.h),
 // Pos16; radix_hist_kernel<T> counts the digits of whichever stream holds them.
 #include "internal.h"
 #include "device_utils.h"
@@ -132,16 +132,21 @@ __global__ __launch_bounds__(256) void radix_chunk_apply_kernel(u32 *__restrict_
 // instantiations a VGPR more or less.)  The LDS tile holds the keys first and is then
 // reused for the values (and, optionally, a third one-byte stream), the per-wave digit counters are 16-bit and each slot's digit is
 // kept in a byte table, so the destination of a slot is re-derived instead of living in a register: 9 B of LDS per element instead
-// of 12, two 8192-element tiles fit a CU and one tile's loads overlap the other's ranking.
+// of 12, two 8192-element tiles fit a CU and one tile's loads overlap the other's ranking.  That is the wide kernel
+// (radix_scatter2_kernel), whose registers are full.  The packed kernels have sixteen to spare: both their write-outs give a thread
+// the same slots, so it keeps each slot's destination base from the first to the second and has no byte table (bytes_no_sdig).
 template <int THREADS, int ITEMS>
 struct RxTile {
     static constexpr int WAVES = THREADS / 64, TILE = THREADS * ITEMS;
     static constexpr size_t off_dbase = (size_t)TILE * sizeof(u64), off_gbase = off_dbase + 256 * sizeof(u32),
                             off_scan = off_gbase + 256 * sizeof(u32), off_whist = off_scan + 16 * sizeof(u32),
                             off_sdig = off_whist + (size_t)WAVES * 256 * sizeof(u16), bytes = off_sdig + TILE;
+    // what a kernel without the byte table asks for (the packed passes, the lean last pass): everything in front of it
+    static constexpr size_t bytes_no_sdig = off_sdig;
     // TILE slots: the first stream (keys; the packed passes' u32 digit stream), then the others (values; uint2 pairs)
     static __device__ __forceinline__ u64 *stage(char *smem) { return (u64 *)smem; }
-    // 256 each: the digit's first slot in the tile; its run's global start minus that slot
+    // 256 each: the digit's first slot in the tile (not used where digit_bases_folded has put it into the waves' starts); its run's
+    // global start minus that slot
     static __device__ __forceinline__ u32 *dbase(char *smem) { return (u32 *)(smem + off_dbase); }
     static __device__ __forceinline__ u32 *gbase(char *smem) { return (u32 *)(smem + off_gbase); }
     // WAVES words (padded to 16) for block_scan_exclusive
@@ -152,6 +157,17 @@ struct RxTile {
     static __device__ __forceinline__ u8 *sdig(char *smem) { return (u8 *)(smem + off_sdig); }
 };
 static_assert(RxTile<RX_THREADS, RX_ITEMS>::bytes == 79936, "9 B per element + 6208: two tiles per CU");
+static_assert(RxTile<RX_THREADS, RX_ITEMS>::bytes_no_sdig == 71744, "8 B per element + 6208");
+
+// one byte per item, four to a register (the key bytes that the last pass over 40-bit keys holds back for the second write-out)
+template <int ITEMS>
+struct Dig8 {
+    static_assert(ITEMS % 4 == 0, "packed as bytes");
+    u32 p[ITEMS / 4];
+    __device__ __forceinline__ u32 get(int j) const { return (p[j >> 2] >> (8 * (j & 3))) & 255u; }
+    // the first write of a quad: its first item sets the register, the others join it (d < 256)
+    __device__ __forceinline__ void init(int j, u32 d) { if (j & 3) p[j >> 2] |= d << (8 * (j & 3)); else p[j >> 2] = d; }
+};
 
 // the items' 16-bit tile positions, two per register
 template <int ITEMS>
@@ -345,9 +361,8 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_packed_kern
     extern __shared__ __attribute__((aligned(16))) char rx_smem[];
     using L = RxTile<RX_THREADS, RX_ITEMS>;
     u64 *stage = L::stage(rx_smem);
-    u32 *dbase = L::dbase(rx_smem), *gbase = L::gbase(rx_smem), *scan_sm = L::scan_sm(rx_smem);
+    u32 *gbase = L::gbase(rx_smem), *scan_sm = L::scan_sm(rx_smem);
     u16 (*whist)[256] = L::whist(rx_smem);
-    u8 *sdig = L::sdig(rx_smem);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const u64 tile = rx_tile_of_block((m + RX_TILE - 1) / RX_TILE);
     const u64 tile_base = tile * RX_TILE;
@@ -392,24 +407,20 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_packed_kern
     }
     __syncthreads();
     {
-        const u32 exc = digit_bases<RX_WAVES>(whist, scan_sm);
-        if (tid < 256) {
-            dbase[tid] = exc;
-            gbase[tid] = tile_off[tile * 256 + tid] - exc;
-        }
+        const u32 exc = digit_bases_folded<RX_WAVES>(whist, scan_sm);        // whist[w][d]: the slot of wave w's first element with digit d
+        if (tid < 256) gbase[tid] = tile_off[tile * 256 + tid] - exc;
     }
     __syncthreads();
 
     constexpr int HB = 8;
     u32 *stage32 = (u32 *)stage;
-    // first trip: the digit's stream into its slot, the slot's digit into the byte table
+    // first trip: the digit's stream into its slot
 #pragma unroll
     for (int j0 = 0; j0 < RX_ITEMS; j0 += HB) {
         u32 add[HB];
 #pragma unroll
         for (int jj = 0; jj < HB; jj++) {
-            const u32 d = PK_DIGIT(j0 + jj);
-            add[jj] = dbase[d] + whist[w][d];
+            add[jj] = whist[w][PK_DIGIT(j0 + jj)];
         }
 #pragma unroll
         for (int jj = 0; jj < HB; jj++) {
@@ -417,7 +428,7 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_packed_kern
             const bool valid = PK_VALID(j);
             const u32 p = pos.get(j) + add[jj];
             pos.set(j, p);
-            if (valid) { stage32[p] = dsrc[j]; sdig[p] = (u8)PK_DIGIT(j); }
+            if (valid) stage32[p] = dsrc[j];
         }
     }
     // the other two streams: (lo, val) on the pass that sorts by c, else (val, c); their loads overlap the write-out below
@@ -439,7 +450,14 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_packed_kern
         }
     }
     __syncthreads();
-    u32 hi_s[DIG_C ? RX_ITEMS : 1];                                // last 40-bit pass: the slot's key byte waits for its lo
+    // Both write-outs hand slot (j0 + jj) * RX_THREADS + tid to this thread, and the slot's digit is a field of the word it reads in
+    // the first: no table of the slots' digits, and the digit's base (gbase) is looked up once and waits in gs[] for the second
+    // write-out.  On the last 40-bit pass the digit is also the key byte that waits for its lo (hi_s, four to a register).  A slot
+    // past the tile's end reads slot 0 and is not written.  (The bases pass through g[] on their way into gs[] and out of it again:
+    // written straight into gs[] and used from there, the same loops compiled to 100 VGPRs instead of 107 and to passes that ran
+    // 0.15 ms per forward slower at 2^30 than the parent's, where this form runs faster: profiles/history/packed_lds_dropped.md.)
+    Dig8<DIG_C ? RX_ITEMS : 4> hi_s;
+    u32 gs[RX_ITEMS];
 #pragma unroll
     for (int j0 = 0; j0 < RX_ITEMS; j0 += HB) {
         u32 x[HB], g[HB];
@@ -448,14 +466,18 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_packed_kern
             const u32 s = (u32)(j0 + jj) * RX_THREADS + tid;
             const u32 sc = s < tile_count ? s : 0u;
             x[jj] = stage32[sc];
-            g[jj] = sdig[sc];
         }
 #pragma unroll
-        for (int jj = 0; jj < HB; jj++) g[jj] = gbase[g[jj]];
+        for (int jj = 0; jj < HB; jj++) {
+            const u32 d = DIG_C ? x[jj] & 255u : (x[jj] >> shift) & 255u;
+            if (DIG_C) hi_s.init(j0 + jj, d);
+            g[jj] = gbase[d];
+        }
+#pragma unroll
+        for (int jj = 0; jj < HB; jj++) gs[j0 + jj] = g[jj];
 #pragma unroll
         for (int jj = 0; jj < HB; jj++) {
             const u32 s = (u32)(j0 + jj) * RX_THREADS + tid;
-            if (DIG_C) hi_s[j0 + jj] = x[jj] & 255u;
             if (s < tile_count) {
                 const u32 dst = g[jj] + s;
                 if (DIG_C) io.sym_out[dst] = (u8)(x[jj] >> 8);
@@ -485,10 +507,8 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_packed_kern
             const u32 s = (u32)(j0 + jj) * RX_THREADS + tid;
             const u32 sc = s < tile_count ? s : 0u;
             e[jj] = ((const uint2 *)stage)[sc];
-            g[jj] = sdig[sc];
+            g[jj] = gs[j0 + jj];
         }
-#pragma unroll
-        for (int jj = 0; jj < HB; jj++) g[jj] = gbase[g[jj]];
 #pragma unroll
         for (int jj = 0; jj < HB; jj++) {
             const u32 s = (u32)(j0 + jj) * RX_THREADS + tid;
@@ -496,7 +516,7 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_packed_kern
                 const u32 dst = g[jj] + s;
                 if (DIG_C) {
                     io.lo_out[dst] = e[jj].x;
-                    io.hi_out[dst] = (u8)hi_s[j0 + jj];
+                    io.hi_out[dst] = (u8)hi_s.get(j0 + jj);
                     io.val_out[dst] = e[jj].y;
                 } else {
                     io.val_out[dst] = e[jj].x;
@@ -534,8 +554,7 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_packed_kern
 // With only the byte to write the tile makes one LDS trip where the other passes make two: c and lo are both loaded before the
 // ranking and staged together (lo | c with the element's place in the tile, 8 B per slot as ever), and one sweep over the slots
 // writes the bytes and looks for equal neighbours: two barriers and a write-out loop fewer (zipf 2^30: 4.10 -> 3.60 ms).  The
-// slots' byte table, 8 KB of RxTile, is not used (the digit is c's low byte); the layout is kept whole: it is what fits two
-// tiles on a CU.
+// slots' byte table, 8 KB of RxTile, is not used (the digit is c's low byte) and not asked for: bytes_no_sdig, as the packed passes.
 #define LEAN_SEAM 64
 #define LEAN_REACH 1024
 static_assert(LEAN_REACH % LEAN_SEAM == 0 && LEAN_REACH <= RX_TILE, "the elements before a tile that is not the first are all there");
@@ -551,7 +570,7 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_lean_last_k
     extern __shared__ __attribute__((aligned(16))) char rx_smem[];
     using L = RxTile<RX_THREADS, RX_ITEMS>;
     u32 *stage32 = (u32 *)L::stage(rx_smem);
-    u32 *dbase = L::dbase(rx_smem), *gbase = L::gbase(rx_smem), *scan_sm = L::scan_sm(rx_smem);
+    u32 *gbase = L::gbase(rx_smem), *scan_sm = L::scan_sm(rx_smem);
     u16 (*whist)[256] = L::whist(rx_smem);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const u64 tile = rx_tile_of_block((m + RX_TILE - 1) / RX_TILE);
@@ -597,11 +616,8 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_lean_last_k
     }
     __syncthreads();
     {
-        const u32 exc = digit_bases<RX_WAVES>(whist, scan_sm);
-        if (tid < 256) {
-            dbase[tid] = exc;
-            gbase[tid] = tile_off[tile * 256 + tid] - exc;
-        }
+        const u32 exc = digit_bases_folded<RX_WAVES>(whist, scan_sm);
+        if (tid < 256) gbase[tid] = tile_off[tile * 256 + tid] - exc;
     }
     __syncthreads();
 
@@ -614,8 +630,7 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_lean_last_k
         u32 add[HB];
 #pragma unroll
         for (int jj = 0; jj < HB; jj++) {
-            const u32 d = dsrc[j0 + jj] & 255u;
-            add[jj] = dbase[d] + whist[w][d];
+            add[jj] = whist[w][dsrc[j0 + jj] & 255u];
         }
 #pragma unroll
         for (int jj = 0; jj < HB; jj++) {
@@ -717,11 +732,11 @@ static int radix_pass_offsets(bwts_ctx *ctx, const T *src, u64 m, int shift, u32
 }
 
 // One scatter launch of either family; `kernel` is the instantiation its caller picked.  roofline: the launch is timed a second time
-// under its own class -- the roofline kernel (one template variant, n-sized launches).
+// under its own class -- the roofline kernel (one template variant, n-sized launches).  lds: RX_LDS, or RX_LDS_PACKED for the kernels without the slots' byte table.
+constexpr size_t RX_LDS = RxTile<RX_THREADS, RX_ITEMS>::bytes, RX_LDS_PACKED = RxTile<RX_THREADS, RX_ITEMS>::bytes_no_sdig;
 template <typename... P, typename... A>
-static int launch_scatter(bwts_ctx *ctx, void (*kernel)(P...), u64 m, u64 alg_bytes, bool roofline, A... args)
+static int launch_scatter(bwts_ctx *ctx, void (*kernel)(P...), size_t lds, u64 m, u64 alg_bytes, bool roofline, A... args)
 {
-    constexpr size_t lds = RxTile<RX_THREADS, RX_ITEMS>::bytes;
     {
         SpanGuard g(ctx, BWTS_K_RADIX_SCATTER, m, alg_bytes);
         const int gm = roofline ? span_begin(ctx, BWTS_K_RADIX_SCATTER_MAIN, m, alg_bytes) : -1;
@@ -758,13 +773,13 @@ static int radix_packed_pass(bwts_ctx *ctx, const SortPlan &plan, u64 m, int p, 
         if (!HI16 || !last || !plan.headw || !plan.keepw || !plan.seam_giveup) return BWTS_E_INTERNAL;
         // c and lo in, the byte out; what the tied slots add is booked with the tied list
         const LeanIO lio{io.lo_in, (const u16 *)io.c_in, io.val_in, io.sym_out, io.val_out, plan.headw, plan.keepw, plan.seam_giveup};
-        return launch_scatter(ctx, radix_scatter_lean_last_kernel, m, 7 * m, false, lio, tile_hist, m);
+        return launch_scatter(ctx, radix_scatter_lean_last_kernel, RX_LDS_PACKED, m, 7 * m, false, lio, tile_hist, m);
     }
     // the first pass reads no values; the last writes the keys split and the byte alone
     const u64 bytes = first ? pass_bytes - 4 : last ? pass_bytes / 2 + (HI16 ? 10 : 9) : pass_bytes;
     const auto kernel = first ? radix_scatter_packed_kernel<true, false, HI16>
                       : last  ? radix_scatter_packed_kernel<false, true, HI16> : radix_scatter_packed_kernel<false, false, HI16>;
-    return launch_scatter(ctx, kernel, m, bytes * m, !first && !last, io, tile_hist, m, shift);
+    return launch_scatter(ctx, kernel, RX_LDS_PACKED, m, bytes * m, !first && !last, io, tile_hist, m, shift);
 }
 
 // round 0 with the byte stream and identity values, keys of 17..40 bits: split -> packed ... packed -> split
@@ -964,7 +979,7 @@ int radix_sort_keys(bwts_ctx *ctx, u64 *keys[2], u32 *tile_hist, void *scan_temp
     int cur = 0;
     for (int shift = lo_bit; shift < lo_bit + bits; shift += 8) {
         BWTS_TRY(radix_pass_offsets(ctx, keys[cur], m, shift, tile_hist, false, scan_temp));
-        BWTS_TRY(launch_scatter(ctx, radix_scatter2_kernel<RX_THREADS, RX_ITEMS, RX_MINW, false, false, true>, m, 16 * m, false,
+        BWTS_TRY(launch_scatter(ctx, radix_scatter2_kernel<RX_THREADS, RX_ITEMS, RX_MINW, false, false, true>, RX_LDS, m, 16 * m, false,
                                 keys[cur], nullptr, keys[cur ^ 1], nullptr, tile_hist, m, shift,
                                 nullptr, nullptr));
         cur ^= 1;
@@ -1012,7 +1027,7 @@ int radix_sort_pairs(bwts_ctx *ctx, const SortPlan &plan, u64 m, int key_bits, i
                                              : radix_scatter2_kernel<RX_THREADS, RX_ITEMS, RX_MINW, true, false>)
                                     : (ident ? radix_scatter2_kernel<RX_THREADS, RX_ITEMS, RX_MINW, false, true>
                                              : radix_scatter2_kernel<RX_THREADS, RX_ITEMS, RX_MINW, false, false>);
-        BWTS_TRY(launch_scatter(ctx, kernel, m, ((has_sym ? 26 : 24) - (ident ? 4 : 0)) * m, has_sym && !ident,
+        BWTS_TRY(launch_scatter(ctx, kernel, RX_LDS, m, ((has_sym ? 26 : 24) - (ident ? 4 : 0)) * m, has_sym && !ident,
                                 plan.keys[cur], plan.vals[cur], plan.keys[cur ^ 1], plan.vals[cur ^ 1],
                                 plan.tile_hist, m, shift, sin, sout));
         cur ^= 1;

@@ -714,13 +714,13 @@ extern "C" uint64_t bwts_pack_bound_v(uint32_t version, uint64_t n, uint64_t blo
 {
     const u64 B = pack_block_len(n, block_bytes);
     if (!B || !pack_version_asked_ok(version)) return 0;
-    return version == PACK_VERSION_2 ? pack_bound_bytes_v2(n, B) : pack_bound_bytes(n, B);
+    return pack_bound_bytes_of(version, n, B);
 }
 
 extern "C" uint64_t bwts_pack_planes_bound(uint32_t width, uint64_t n, uint64_t block_bytes)
 {
     const u64 B = pack_block_len(n, block_bytes);
-    return B && planes_width_ok(width) ? pack_bound_bytes_v2(n, B) : 0;
+    return B && planes_width_ok(width) ? pack_bound_bytes_of(PACK_VERSION_3, n, B) : 0;
 }
 
 extern "C" uint64_t bwts_pack_bound(uint64_t n, uint64_t block_bytes)
@@ -731,17 +731,10 @@ extern "C" uint64_t bwts_pack_bound(uint64_t n, uint64_t block_bytes)
 extern "C" int bwts_unpack_size(const uint8_t *frame, uint64_t in_bytes, uint64_t *n, uint64_t *frame_bytes)
 {
     if (!frame || !n || !frame_bytes) return BWTS_E_ARG;
-    if (in_bytes >= PACK_HEADER_BYTES && members_magic(frame)) {
-        MembersHeader M;
-        BWTS_TRY(members_header_check(frame, in_bytes, &M));
-        BWTS_TRY(members_directory_check(frame + MEMBERS_HEADER_BYTES, M, in_bytes, false, frame_bytes));
-        *n = M.n;
-        return BWTS_OK;
-    }
-    PackHeader H;
-    BWTS_TRY(pack_header_check(frame, in_bytes, &H));
-    BWTS_TRY(pack_directory_check(frame + PACK_HEADER_BYTES, H, in_bytes, false, frame_bytes));
-    *n = H.n;
+    Frame F;
+    BWTS_TRY(frame_head_check(frame, in_bytes, &F));
+    BWTS_TRY(frame_dir_check(frame + PACK_HEADER_BYTES, F, in_bytes, false, frame_bytes));
+    *n = F.n;
     return BWTS_OK;
 }
 
@@ -764,10 +757,9 @@ static int pack_host_any(bwts_ctx *ctx, uint32_t version, uint32_t width, const 
     if (n > PACK_MAX_N) return BWTS_E_RANGE;
     const u64 B = pack_block_len(n, block_bytes);
     if (B == 0) return BWTS_E_ARG;
-    const bool v1 = version == PACK_VERSION;
-    const u64 bound = v1 ? pack_bound_bytes(n, B) : pack_bound_bytes_v2(n, B);
+    const u64 bound = pack_bound_bytes_of(version, n, B);
     const u64 cap = out_cap < bound ? out_cap : bound;
-    if (cap < (v1 ? pack_least_bytes(n, B) : pack_least_bytes_v2(n, B))) return BWTS_E_SPACE;
+    if (cap < pack_least_bytes_of(version, n, B)) return BWTS_E_SPACE;
     const HostTrip trip = {in, n, n > cap ? n : cap, out, out_bytes};
     return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *bytes) { return pack_device_any(ctx, version, width, d_in, n, block_bytes, d_out, cap, bytes); });
 }
@@ -828,7 +820,7 @@ extern "C" int bwts_unpack(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, 
     return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *got) { return bwts_unpack_device(ctx, d_in, in_bytes, d_out, v, got); });
 }
 
-// ranges of a frame (include/bwts_pack.h, "Ranges"): the driver in pack.hip, the plan in pack_plan.h
+// ranges of a frame (include/bwts_pack.h, "Ranges"): the driver in pack.hip, the plan in members_plan.h
 static_assert(sizeof(bwts_range) == sizeof(PackRange) && offsetof(bwts_range, bytes) == offsetof(PackRange, bytes), "bwts_range is pack_plan.h's PackRange");
 
 extern "C" int bwts_unpack_ranges_device(bwts_ctx *ctx, const void *d_in, uint64_t in_bytes, const bwts_range *ranges, uint64_t count,
@@ -847,11 +839,12 @@ extern "C" int bwts_unpack_ranges_device(bwts_ctx *ctx, const void *d_in, uint64
 static int unpack_ranges_host(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const PackRange *ranges, const uint64_t *indices, uint64_t count,
                               uint8_t *out, uint64_t out_cap, uint64_t *out_bytes, bool by_index = false)
 {
-    PackHeader H;
-    u64 sum = 0, fixed = 0;
+    Frame F;
+    u64 sum = 0;
     PackRangesPlan P;
     std::vector<PackRange> whole;
-    BWTS_TRY(frame_ranges_plan(in, in_bytes, ranges, by_index ? indices : nullptr, count, out_cap, &H, &fixed, &sum, &whole, &ranges, &P));
+    BWTS_TRY(frame_ranges_plan(in, in_bytes, ranges, by_index ? indices : nullptr, count, out_cap, &F, &sum, &whole, &ranges, &P));
+    const u64 fixed = F.fixed;
     std::vector<u8> sent((size_t)(fixed + P.stream_bytes));
     memcpy(sent.data(), in, (size_t)fixed);
     for (const PackPiece &s : P.streams) memcpy(sent.data() + fixed + s.dst, in + s.src, (size_t)s.bytes);
@@ -943,17 +936,19 @@ extern "C" int bwts_frame_members_f(const uint8_t *frame, uint64_t in_bytes, uin
                                     uint64_t *count)
 {
     if (!frame || !count || in_bytes == 0) return BWTS_E_ARG;
-    MembersHeader M;
+    Frame F;
     u64 frame_bytes = 0;
-    BWTS_TRY(members_header_check(frame, in_bytes, &M));
-    BWTS_TRY(members_directory_check(frame + MEMBERS_HEADER_BYTES, M, in_bytes, true, &frame_bytes));
-    if ((lengths_out || widths_out || filters_out) && cap < M.count) return BWTS_E_SPACE;
-    for (u64 k = 0; k < M.count; k++) {
-        if (lengths_out) lengths_out[k] = members_entry_len(frame + MEMBERS_HEADER_BYTES, k);
-        if (widths_out) widths_out[k] = members_entry_width(frame + MEMBERS_HEADER_BYTES, k);
-        if (filters_out) filters_out[k] = members_entry_filter(frame + MEMBERS_HEADER_BYTES, k);
+    const int rc = frame_head_check(frame, in_bytes, &F);
+    if (!F.members) return BWTS_E_FORMAT;       // (a "BWTZ" frame, whatever its own header check says, has no members)
+    BWTS_TRY(rc);
+    BWTS_TRY(frame_dir_check(frame + MEMBERS_HEADER_BYTES, F, in_bytes, true, &frame_bytes));
+    if ((lengths_out || widths_out || filters_out) && cap < F.count) return BWTS_E_SPACE;
+    for (u64 k = 0; k < F.count; k++) {
+        if (lengths_out) lengths_out[k] = F.len(k);
+        if (widths_out) widths_out[k] = F.width[(size_t)k];
+        if (filters_out) filters_out[k] = F.filter[(size_t)k];
     }
-    *count = M.count;
+    *count = F.count;
     return BWTS_OK;
 }
 

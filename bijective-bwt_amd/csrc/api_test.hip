@@ -178,17 +178,17 @@ extern "C" int bwts_debug_planes_plan(uint64_t n, uint32_t width, uint64_t out[4
     return 0;
 }
 
-// what a range read of a frame would decode and move (pack_plan.h; a member frame: members_plan.h): the frame's header and directory alone are read.  No context, no device
+// what a range read of a frame would decode and move (ranges_plan in members_plan.h): the frame's header and directory alone are read.  No context, no device
 extern "C" int bwts_debug_unpack_ranges_plan(const uint8_t *frame, uint64_t in_bytes, const uint64_t *ranges, uint64_t count, uint64_t out_cap,
                                              uint64_t out[8], uint64_t *lists, uint64_t cap_words)
 {
     if (!frame || !out || (!lists && cap_words)) return -1;
-    PackHeader H;
-    u64 fixed = 0, sum = 0;
+    Frame F;
+    u64 sum = 0;
     PackRangesPlan P;
     std::vector<PackRange> whole;
     const PackRange *rs = nullptr;
-    BWTS_TRY(frame_ranges_plan(frame, in_bytes, (const PackRange *)ranges, nullptr, count, out_cap, &H, &fixed, &sum, &whole, &rs, &P));
+    BWTS_TRY(frame_ranges_plan(frame, in_bytes, (const PackRange *)ranges, nullptr, count, out_cap, &F, &sum, &whole, &rs, &P));
     const u64 runs = P.runs.size(), words = 5 * runs + 3 * count;
     const u64 head[8] = {(u64)P.blocks.size(), runs, P.covered_bytes, P.stream_bytes, P.coded_bytes, P.out_bytes, PIECES_T, words};
     memcpy(out, head, sizeof head);

@@ -1,5 +1,6 @@
 // members_plan.h -- the arithmetic of the member frame (include/bwts_members.h): members of any lengths and widths in one frame, its
-// bound, what makes its header and directory valid, and which members a list of byte ranges touches.  In the style of pack_plan.h,
+// bound, what makes its header and directory valid; and, for a frame of either magic, the judged Frame that every reader fills and
+// the plan of a range read: which blocks a list of byte ranges touches.  In the style of pack_plan.h,
 // whose codes, CRC-32 and range types it uses: pack.hip, the host side of the calls and a stand-alone host program
 // (tests/members_plan_check.cc, built with the sanitizers) all compile this file.
 // Version 2 of the frame names a filter (delta_plan.h) beside a member's width; tests/delta_plan_check.cc holds its predicates.
@@ -129,64 +130,114 @@ EC_HD int members_directory_check(const uint8_t *dir, const MembersHeader &H, ui
     return PACK_OK;
 }
 
-EC_HD uint64_t members_entry_len(const uint8_t *dir, uint64_t k) { return pack_le64(dir + (uint64_t)MEMBERS_ENTRY_BYTES * k + 24); }
 // width and filter of an entry of a directory that passed its check
 EC_HD uint32_t members_entry_width(const uint8_t *dir, uint64_t k) { return ec_le32(dir + (uint64_t)MEMBERS_ENTRY_BYTES * k + 12) & 0xffu; }
 EC_HD uint32_t members_entry_filter(const uint8_t *dir, uint64_t k) { return (ec_le32(dir + (uint64_t)MEMBERS_ENTRY_BYTES * k + 12) >> 8) & 0xffu; }
 
-// where every member begins in the concatenation: count + 1 offsets, off[count] = n (a directory that passed its check)
-static inline std::vector<uint64_t> members_offsets(const uint8_t *dir, uint64_t count)
+// ---- a judged frame of either magic ----
+// What every user of a frame needs of its header and directory, so that nobody reads either again: the device forms' directory lies
+// in staging that the first stage writes over.  A reader fills it in two steps, frame_head_check and frame_dir_check, because the
+// device form reads the header before it can fetch the directory.  "BWTZ": the blocks are min(k B, n), the width is the directory's
+// one (version 3; else 1, no split) and no block is filtered.  "BWTM": every member is a block, and its entry says all of it.
+struct Frame {
+    bool members = false;                       // "BWTM"
+    PackHeader z;                               // the judged header: "BWTZ" ...
+    MembersHeader m;                            // ... or "BWTM"
+    uint64_t n = 0, count = 0;                  // bytes and blocks
+    uint64_t B = 0;                             // the uniform block length ("BWTZ"); 0: the block of a byte is found by bisecting off
+    uint64_t entry = 0, fixed = 0;              // bytes of a directory entry, and of header and directory
+    bool zrl = false;                           // the streams are the coder's over zero-run coded bytes
+    std::vector<uint64_t> off, stream, coded;   // per block: where it begins (count + 1), stream bytes, coded bytes (not zrl: its length)
+    std::vector<uint32_t> crc, width, filter;
+    uint64_t len(uint64_t k) const { return off[(size_t)k + 1] - off[(size_t)k]; }
+};
+
+static_assert(MEMBERS_HEADER_BYTES == PACK_HEADER_BYTES, "the directory of either frame begins behind 32 bytes");
+
+// The header of a frame of which in_bytes bytes are at hand (h: the first 32 of them, read only when in_bytes allows them): the magic
+// chooses the predicate, whose code this returns.  PACK_OK: everything of *F that needs no directory.
+static inline int frame_head_check(const uint8_t *h, uint64_t in_bytes, Frame *F)
 {
-    std::vector<uint64_t> off((size_t)count + 1, 0);
-    for (uint64_t k = 0; k < count; k++) off[(size_t)k + 1] = off[(size_t)k] + members_entry_len(dir, k);
-    return off;
+    int rc;
+    F->members = in_bytes >= MEMBERS_HEADER_BYTES && members_magic(h);
+    if (F->members) {
+        if ((rc = members_header_check(h, in_bytes, &F->m)) != PACK_OK) return rc;
+        F->n = F->m.n; F->count = F->m.count; F->B = 0; F->entry = MEMBERS_ENTRY_BYTES; F->zrl = true;
+    } else {
+        if ((rc = pack_header_check(h, in_bytes, &F->z)) != PACK_OK) return rc;
+        F->n = F->z.n; F->count = F->z.nblk; F->B = F->z.B; F->entry = pack_entry_bytes(F->z.version); F->zrl = F->z.version != PACK_VERSION;
+    }
+    F->fixed = PACK_HEADER_BYTES + F->entry * F->count;
+    return PACK_OK;
 }
 
-// the member that holds byte `at` of the concatenation (at < off[count]): the last one that does not begin behind it
-static inline uint64_t members_find(const std::vector<uint64_t> &off, uint64_t at)
+// The directory behind a header that passed (dir: F.count entries, which in_bytes holds; exact: as the predicates take it).  PACK_OK,
+// *frame_bytes and the rest of F, or the predicate's code.
+static inline int frame_dir_check(const uint8_t *dir, Frame &F, uint64_t in_bytes, bool exact, uint64_t *frame_bytes)
 {
-    uint64_t lo = 0, hi = off.size() - 1;
+    const int rc = F.members ? members_directory_check(dir, F.m, in_bytes, exact, frame_bytes) : pack_directory_check(dir, F.z, in_bytes, exact, frame_bytes);
+    if (rc != PACK_OK) return rc;
+    const size_t c = (size_t)F.count;
+    F.off.assign(c + 1, 0); F.stream.resize(c); F.coded.resize(c); F.crc.resize(c); F.width.resize(c); F.filter.resize(c);
+    for (size_t k = 0; k < c; k++) {
+        const uint8_t *e = dir + F.entry * k;
+        const uint64_t len = F.members ? pack_le64(e + 24) : pack_block_at(F.n, F.B, k);
+        F.off[k + 1] = F.off[k] + len;
+        F.stream[k] = pack_le64(e);
+        F.crc[k] = ec_le32(e + 8);
+        F.coded[k] = F.zrl ? pack_le64(e + 16) : len;
+        F.width[k] = F.members ? members_entry_width(dir, k) : F.z.version == PACK_VERSION_3 ? F.z.width : 1u;
+        F.filter[k] = F.members ? members_entry_filter(dir, k) : DELTA_FILTER_NONE;
+    }
+    return PACK_OK;
+}
+
+// the block that holds byte `at` (at < n): a division where the blocks are uniform, else the last one that does not begin behind it
+static inline uint64_t frame_block_of(const Frame &F, uint64_t at)
+{
+    if (F.B) return at / F.B;
+    uint64_t lo = 0, hi = F.count;
     while (hi - lo > 1) {
         const uint64_t mid = lo + (hi - lo) / 2;
-        if (off[(size_t)mid] <= at) lo = mid;
+        if (F.off[(size_t)mid] <= at) lo = mid;
         else hi = mid;
     }
     return lo;
 }
 
-// The indices of a bwts_unpack_members call against a judged directory, as the ranges they stand for: PACK_ARG, then PACK_RANGE for
+// The indices of a bwts_unpack_members call against a judged member frame, as the ranges they stand for: PACK_ARG, then PACK_RANGE for
 // more than 2^20 indices or one that names no member; else PACK_OK and one range per index, in the order asked.
-static inline int members_index_ranges(const std::vector<uint64_t> &off, const uint64_t *indices, uint64_t icount, std::vector<PackRange> *r)
+static inline int members_index_ranges(const Frame &F, const uint64_t *indices, uint64_t icount, std::vector<PackRange> *r)
 {
     if (!indices || icount == 0) return PACK_ARG;
     if (icount > PACK_MAX_RANGES) return PACK_RANGE;
-    const uint64_t count = off.size() - 1;
     r->clear();
     for (uint64_t i = 0; i < icount; i++) {
-        if (indices[i] >= count) return PACK_RANGE;
-        r->push_back(PackRange{off[(size_t)indices[i]], off[(size_t)indices[i] + 1] - off[(size_t)indices[i]]});
+        if (indices[i] >= F.count) return PACK_RANGE;
+        r->push_back(PackRange{F.off[(size_t)indices[i]], F.len(indices[i])});
     }
     return PACK_OK;
 }
 
-// pack_ranges_plan for a member frame: the covered members are found by bisecting the offsets where that one divides by B.  dir has
-// passed members_directory_check and off is its members_offsets, the ranges pack_ranges_check against n = off[count].
-static inline void members_ranges_plan(const std::vector<uint64_t> &off, const uint8_t *dir, const PackRange *r, uint64_t count, PackRangesPlan *P)
+// The plan of a range read (pack_plan.h: PackRangesPlan).  F has passed both checks, the ranges pack_ranges_check against F.n.  Nothing
+// here can overflow: the directory check has held the sum of all stream bytes against the frame's length, the coded bytes against the
+// blocks' lengths, and the blocks' lengths add up to n <= 2^32; the ranges' sum is bounded by their check.
+static inline void ranges_plan(const Frame &F, const PackRange *r, uint64_t count, PackRangesPlan *P)
 {
-    const uint64_t members = off.size() - 1, entry = MEMBERS_ENTRY_BYTES;
-    std::vector<int32_t> step((size_t)members + 1, 0);
+    // how many ranges begin in a block minus how many end in the one before: a running sum above zero marks a covered block
+    std::vector<int32_t> step((size_t)F.count + 1, 0);
     for (uint64_t i = 0; i < count; i++) {
-        step[(size_t)members_find(off, r[i].offset)]++;
-        step[(size_t)members_find(off, r[i].offset + r[i].bytes - 1u) + 1]--;
+        step[(size_t)frame_block_of(F, r[i].offset)]++;
+        step[(size_t)frame_block_of(F, r[i].offset + r[i].bytes - 1u) + 1]--;
     }
-    std::vector<uint64_t> at((size_t)members, 0);        // where a covered member begins in the covered-member buffer
+    std::vector<uint64_t> at((size_t)F.count, 0);        // where a covered block begins in the covered-block buffer
     P->runs.clear(); P->streams.clear(); P->out.clear(); P->blocks.clear();
     P->covered_bytes = P->stream_bytes = P->coded_bytes = P->out_bytes = 0;
-    uint64_t frame_at = members_fixed_bytes(members);
+    uint64_t frame_at = F.fixed;
     int64_t open = 0;
     bool in_run = false;
-    for (uint64_t b = 0; b < members; b++) {
-        const uint64_t sb = pack_le64(dir + entry * b);
+    for (uint64_t b = 0; b < F.count; b++) {
+        const uint64_t sb = F.stream[(size_t)b];
         open += step[(size_t)b];
         if (open > 0) {
             if (!in_run) {
@@ -197,52 +248,38 @@ static inline void members_ranges_plan(const std::vector<uint64_t> &off, const u
             P->streams.back().bytes += sb;
             P->blocks.push_back(b);
             at[(size_t)b] = P->covered_bytes;
-            P->covered_bytes += off[(size_t)b + 1] - off[(size_t)b];
+            P->covered_bytes += F.len(b);
             P->stream_bytes += sb;
-            P->coded_bytes += pack_le64(dir + entry * b + 16);
+            P->coded_bytes += F.coded[(size_t)b];
         }
         in_run = open > 0;
         frame_at += sb;
     }
     for (uint64_t i = 0; i < count; i++) {
-        const uint64_t b = members_find(off, r[i].offset);
-        P->out.push_back(PackPiece{at[(size_t)b] + (r[i].offset - off[(size_t)b]), P->out_bytes, r[i].bytes});
+        const uint64_t b = frame_block_of(F, r[i].offset);
+        P->out.push_back(PackPiece{at[(size_t)b] + (r[i].offset - F.off[(size_t)b]), P->out_bytes, r[i].bytes});
         P->out_bytes += r[i].bytes;
     }
 }
 
-// A frame of either magic that the host holds whole, and the ranges asked of it: header, directory and ranges judged in unpack's order
-// with unpack's codes, then the plan.  indices: not null for whole members as the ranges (`ranges` is then not read, a "BWTZ" frame
-// is PACK_FORMAT, and *ranges_out points into *whole).  H: the frame as the drivers carry it (a member frame: version 3, nblk
-// members, B unused).
+// A frame that the host holds whole, and the ranges asked of it: header, directory and ranges judged in unpack's order with unpack's
+// codes, then the plan.  indices: not null for whole members as the ranges (`ranges` is then not read, a "BWTZ" frame is PACK_FORMAT,
+// and *ranges_out points into *whole).
 static inline int frame_ranges_plan(const uint8_t *frame, uint64_t in_bytes, const PackRange *ranges, const uint64_t *indices, uint64_t count,
-                                    uint64_t out_cap, PackHeader *H, uint64_t *fixed, uint64_t *sum, std::vector<PackRange> *whole,
-                                    const PackRange **ranges_out, PackRangesPlan *P)
+                                    uint64_t out_cap, Frame *F, uint64_t *sum, std::vector<PackRange> *whole, const PackRange **ranges_out,
+                                    PackRangesPlan *P)
 {
     uint64_t frame_bytes = 0;
     int rc;
-    if (in_bytes >= MEMBERS_HEADER_BYTES && members_magic(frame)) {
-        MembersHeader M;
-        const uint8_t *dir = frame + MEMBERS_HEADER_BYTES;
-        if ((rc = members_header_check(frame, in_bytes, &M)) != PACK_OK) return rc;
-        if ((rc = members_directory_check(dir, M, in_bytes, true, &frame_bytes)) != PACK_OK) return rc;
-        const std::vector<uint64_t> off = members_offsets(dir, M.count);
-        if (indices) {
-            if ((rc = members_index_ranges(off, indices, count, whole)) != PACK_OK) return rc;
-            ranges = whole->data();
-        }
-        *H = PackHeader{M.n, 0, M.count, M.dir_crc, PACK_VERSION_3, 0u};
-        if ((rc = pack_ranges_check(*H, ranges, count, out_cap, sum)) != PACK_OK) return rc;
-        members_ranges_plan(off, dir, ranges, count, P);
-        *fixed = members_fixed_bytes(M.count);
-    } else {
-        if ((rc = pack_header_check(frame, in_bytes, H)) != PACK_OK) return rc;
-        if ((rc = pack_directory_check(frame + PACK_HEADER_BYTES, *H, in_bytes, true, &frame_bytes)) != PACK_OK) return rc;
-        if (indices) return PACK_FORMAT;
-        if ((rc = pack_ranges_check(*H, ranges, count, out_cap, sum)) != PACK_OK) return rc;
-        pack_ranges_plan(*H, frame + PACK_HEADER_BYTES, ranges, count, P);
-        *fixed = pack_fixed_bytes_v(H->version, H->nblk);
+    if ((rc = frame_head_check(frame, in_bytes, F)) != PACK_OK) return rc;
+    if ((rc = frame_dir_check(frame + PACK_HEADER_BYTES, *F, in_bytes, true, &frame_bytes)) != PACK_OK) return rc;
+    if (indices) {
+        if (!F->members) return PACK_FORMAT;
+        if ((rc = members_index_ranges(*F, indices, count, whole)) != PACK_OK) return rc;
+        ranges = whole->data();
     }
+    if ((rc = pack_ranges_check(F->n, ranges, count, out_cap, sum)) != PACK_OK) return rc;
+    ranges_plan(*F, ranges, count, P);
     *ranges_out = ranges;
     return PACK_OK;
 }

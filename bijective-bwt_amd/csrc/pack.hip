@@ -1,20 +1,25 @@
-// pack.hip -- the chain as one call (include/bwts_pack.h): checksums, delta filter (member frame version 2), byte-plane split (frame
-// version 3), transform, move-to-front, zero-run coding (frame versions 2 and 3) and entropy coder over the blocks of a frame, and the
-// way back.  No kernel of its own: the stages are the ones behind the single calls, run one after the other inside
-// one call bracket; the frame's arithmetic and the checks of an untrusted frame are in pack_plan.h.
+// pack.hip -- the packed frames as one call each way (include/bwts_pack.h, include/bwts_members.h).  No kernel of its own: the stages
+// are the ones behind the single calls, run one after the other inside one call bracket; the frames' arithmetic, the checks of an
+// untrusted frame and the plan of a range read are in pack_plan.h and members_plan.h.
 //
-// A frame of one block goes through the single-input stages, one of several blocks through the segment forms (the bytes are the
-// same by the segment forms' contract).  The stages share the context's arena, and the segment forms the pinned staging of their
-// tables: the stream is drained between two stages, so that no table copy of the stage before is still to come when the next stage
-// writes its own (seg_layout.h: the regions, and who overlaps whom).  Header and directory travel through pinned memory too: the
-// small block, and for several blocks the directory region behind the segment table (version 1; the 32-byte entries of version 2 do
-// not fit that region and travel through a host block of the call's own).
-// Versions 2 and 3 change the segment table on the way: the coder's segments are the blocks' zero-run coded bytes, every other
-// stage's the blocks themselves.
-// The bytes between two stages go to and fro between two blocks (pack) or between one block and d_out (unpack); where a version has
-// a stage more, the directions swap, so that the last stage of an unpack always lands in d_out.
-// A range read (unpack_ranges_device_impl, at the end) runs the same stages over the blocks its ranges touch, between the two blocks,
-// and cuts the ranges out with pieces.hip's copy kernel.
+// Two chains, each written once:
+//   encode_chain: crc, (delta), (split), transform, move-to-front, (zero-run coding), coder.  pack_device_impl ("BWTZ", versions 1 to
+//     3) and pack_members_device_impl ("BWTM") say in an EncodeSet what the blocks are and which stages apply to them, and write their
+//     own directory entries and header around the streams.
+//   decode_chain: coder, (zero-run decoding), inverse move-to-front, inverse transform, (join), (delta), crc compare.  The reader
+//     judges the frame into a Frame (members_plan.h); unpack_device_impl runs the chain over all its blocks, unpack_ranges_device_impl
+//     over the blocks its ranges touch, and cuts the ranges out with pieces.hip's copy kernel.
+//
+// One block goes through the single-input stages, several through the segment forms (the bytes are the same by the segment forms'
+// contract).  The stages share the context's arena, and the segment forms the pinned staging of their tables: the stream is drained
+// between two stages, so that no table copy of the stage before is still to come when the next stage writes its own (seg_layout.h:
+// the regions, and who overlaps whom).  The context's table changes hands inside a chain: the coder's segments are the blocks'
+// zero-run coded bytes where that stage runs, every other stage's the blocks themselves.
+// Header and directory travel through pinned memory too: the small block, and for several blocks the directory region behind the
+// segment table (16-byte entries, "BWTZ" version 1; the 32-byte entries do not fit that region and travel through a host block of the
+// call's own).  Either is staging that the next stage writes over: a Frame holds everything the directory says.
+// The bytes between two stages go to and fro between two blocks; in a whole unpack one of the two is d_out, and the first stage
+// writes the one that makes the last stage land in d_out (decode_stages).
 #include "internal.h"
 #include "members_plan.h"
 #include "../../include/bwts_members.h"
@@ -33,109 +38,54 @@ static int pack_stage(bwts_ctx *ctx, int i, u64 n, u8 **p)
     return BWTS_OK;
 }
 
-// the blocks of a frame as the segment table of the stages; one block: no table, the single-input stages
-static int pack_blocks_set(bwts_ctx *ctx, u64 n, u64 B, u64 nblk)
+// blocks of n bytes in all as the segment table of the stages; one block: no table, the single-input stages
+static int blocks_set(bwts_ctx *ctx, const std::vector<u64> &lengths, u64 n)
 {
-    if (nblk == 1) return BWTS_OK;
-    std::vector<u64> lengths((size_t)nblk, B);
-    lengths[(size_t)nblk - 1] = pack_block_at(n, B, nblk - 1);
+    if (lengths.size() == 1) return BWTS_OK;
     u64 total = 0;
-    BWTS_TRY(seg_table_set(ctx, lengths.data(), nblk, &total));
+    BWTS_TRY(seg_table_set(ctx, lengths.data(), lengths.size(), &total));
     return total == n ? BWTS_OK : BWTS_E_INTERNAL;
 }
 
-// room on the host for a directory of nblk entries: the small block behind the header, or for several blocks the directory region
-// behind the segment table (pinned; version 1) or `own` (versions 2 and 3)
-static int pack_dir_staging(bwts_ctx *ctx, u32 version, u64 nblk, std::vector<u8> &own, u8 **dir)
-{
-    if (nblk == 1) { *dir = (u8 *)(ctx->h_small + SM_PACK_HEAD) + PACK_HEADER_BYTES; return BWTS_OK; }
-    if (version != PACK_VERSION) {
-        own.resize((size_t)(PACK_ENTRY_BYTES_V2 * nblk));
-        *dir = own.data();
-        return BWTS_OK;
-    }
-    return seg_pinned_region(ctx, seg_dir_at(nblk), seg_dir_words(nblk), (void **)dir);
-}
-
-// the coder's segments of a version-2 frame of several blocks: the blocks' coded bytes
+// the coder's segments where the zero-run stage runs: the blocks' coded bytes
 static int pack_coded_set(bwts_ctx *ctx, const std::vector<u64> &coded, u64 *total)
 {
     if (coded.size() == 1) { *total = coded[0]; return BWTS_OK; }
     return seg_table_set(ctx, coded.data(), coded.size(), total);
 }
 
-int pack_device_impl(bwts_ctx *ctx, u32 version, u32 width, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes)
+// the blocks of a "BWTZ" frame: all B long but the last
+static std::vector<u64> uniform_lengths(u64 n, u64 B)
 {
-    const bool zrl = version != PACK_VERSION, planes = version == PACK_VERSION_3;
-    const u64 nblk = pack_blocks(n, B), fixed = pack_fixed_bytes_v(version, nblk), entry = pack_entry_bytes(version);
-    const bool seg = nblk > 1;
-    if (out_cap < (zrl ? pack_least_bytes_v2(n, B) : pack_least_bytes(n, B))) return BWTS_E_SPACE;
-    BWTS_TRY(pack_blocks_set(ctx, n, B, nblk));
-    SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
-    std::vector<u32> crcs((size_t)nblk);
-    std::vector<u64> sizes((size_t)nblk), coded((size_t)nblk);
-    BWTS_TRY(crc_impl(ctx, d_in, n, segs, crcs.data()));
-    // a stage reads `from` and writes `to`; the two blocks swap behind it
-    u8 *to = nullptr, *other = nullptr;
-    BWTS_TRY(pack_stage(ctx, 0, n, &to));
-    BWTS_TRY(pack_stage(ctx, 1, n, &other));
-    const u8 *from = d_in;
-    auto done = [&] { from = to; std::swap(to, other); return hipStreamSynchronize(ctx->stream); };
-    if (planes) {
-        // every block split on its own; the checksums above are the original bytes'
-        BWTS_TRY(planes_impl(ctx, from, n, width, to, false, segs));
-        HIPC(done());
-    }
-    BWTS_TRY(seg ? forward_segments_impl(ctx, from, n, to) : forward_device_impl(ctx, from, n, to));
-    HIPC(done());
-    BWTS_TRY(mtf_impl(ctx, from, n, to, false, segs));
-    HIPC(done());
-    u64 m = n;
-    if (zrl) {
-        // the ranks' coded bytes, one block's behind the other's: the coder's segments
-        BWTS_TRY(zrl_encode_impl(ctx, from, n, to, n, segs, coded.data()));
-        HIPC(done());
-        BWTS_TRY(pack_coded_set(ctx, coded, &m));
-        if (seg) segs = seg_mode(ctx);
-    }
-    // the streams go straight to their place; a frame that does not fit is refused by the coder before it writes anything
-    BWTS_TRY(ec_encode_impl(ctx, from, m, d_out + fixed, out_cap - fixed, segs, sizes.data()));
-    HIPC(hipStreamSynchronize(ctx->stream));
-    u8 *head = (u8 *)(ctx->h_small + SM_PACK_HEAD), *dir = nullptr;
-    std::vector<u8> own;
-    BWTS_TRY(pack_dir_staging(ctx, version, nblk, own, &dir));
-    u64 total = fixed;
-    for (u64 k = 0; k < nblk; k++) {
-        if (planes) pack_entry_write_v3(dir + entry * k, sizes[(size_t)k], crcs[(size_t)k], coded[(size_t)k], width);
-        else if (zrl) pack_entry_write_v2(dir + entry * k, sizes[(size_t)k], crcs[(size_t)k], coded[(size_t)k]);
-        else pack_entry_write(dir + entry * k, sizes[(size_t)k], crcs[(size_t)k]);
-        total += sizes[(size_t)k];
-    }
-    if (total > out_cap) return BWTS_E_INTERNAL;
-    pack_header_write_v(head, version, n, B, dir);
-    HIPC(hipMemcpyAsync(d_out + PACK_HEADER_BYTES, dir, entry * nblk, hipMemcpyHostToDevice, ctx->stream));
-    HIPC(hipMemcpyAsync(d_out, head, PACK_HEADER_BYTES, hipMemcpyHostToDevice, ctx->stream));
-    HIPC(hipStreamSynchronize(ctx->stream));
-    *out_bytes = total;
-    return BWTS_OK;
+    std::vector<u64> lengths((size_t)pack_blocks(n, B), B);
+    lengths.back() = pack_block_at(n, B, lengths.size() - 1);
+    return lengths;
 }
 
-// is any block split at all?  (none in versions 1 and 2, whose list of widths is empty, nor where every member has width 1)
-static bool widths_split(const std::vector<u32> &widths)
+// room on the host for a directory of nblk entries: the small block behind the header, or for several blocks the directory region
+// behind the segment table (pinned; 16-byte entries, and the table is nblk segments when this is called) or `own` (32-byte entries)
+static int pack_dir_staging(bwts_ctx *ctx, u64 entry, u64 nblk, std::vector<u8> &own, u8 **dir)
 {
-    for (u32 w : widths) if (w != 1u) return true;
-    return false;
+    if (nblk == 1) { *dir = (u8 *)(ctx->h_small + SM_PACK_HEAD) + PACK_HEADER_BYTES; return BWTS_OK; }
+    if (entry != PACK_ENTRY_BYTES) {
+        own.resize((size_t)(entry * nblk));
+        *dir = own.data();
+        return BWTS_OK;
+    }
+    return seg_pinned_region(ctx, seg_dir_at(nblk), seg_dir_words(nblk), (void **)dir);
 }
 
-// is any block filtered?  (none outside a version-2 member frame, whose list alone is not empty)
-static bool filters_named(const std::vector<u32> &filters)
+// split or join (planes.hip) of blocks of `total` bytes in all at the widths given: one block, or all widths alike, through the
+// uniform kernels; else one launch at mixed widths
+static int frame_planes(bwts_ctx *ctx, const u8 *from, u64 total, const std::vector<u32> &widths, u8 *to, bool join, SegMode segs)
 {
-    for (u32 f : filters) if (f != DELTA_FILTER_NONE) return true;
-    return false;
+    bool alike = true;
+    for (u32 w : widths) alike = alike && w == widths[0];
+    if (alike) return planes_impl(ctx, from, total, widths[0], to, join, segs);
+    return planes_w_impl(ctx, from, total, widths.data(), to, join);
 }
 
-// the delta filter (delta.hip) over blocks of `total` bytes in all: one block through the single-input stage, several in one launch
-// per sweep at the widths and filters given
+// the delta filter (delta.hip) likewise: one block through the single-input stage, several in one launch per sweep
 static int frame_delta(bwts_ctx *ctx, const u8 *from, u64 total, const std::vector<u32> &widths, const std::vector<u32> &filters, u8 *to, bool decode,
                        SegMode segs)
 {
@@ -143,277 +93,284 @@ static int frame_delta(bwts_ctx *ctx, const u8 *from, u64 total, const std::vect
     return delta_f_impl(ctx, from, total, widths.data(), filters.data(), to, decode);
 }
 
-// A member frame: pack_device_impl's chain over members of any lengths, each filtered if asked (filters: null for none) and split at
-// its own width (1: not at all), with the entries and the header of include/bwts_members.h.  One member goes through the single-input
-// stages.  A pack in which no member names a filter writes the version-1 frame.
-int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, const u32 *filters, u64 count, u64 n, u8 *d_out, u64 out_cap,
-                             u64 *out_bytes)
+static bool any_split(const std::vector<u32> &widths)
 {
-    const u64 fixed = members_fixed_bytes(count);
+    for (u32 w : widths) if (w != 1u) return true;
+    return false;
+}
+
+static bool any_filter(const std::vector<u32> &filters)
+{
+    for (u32 f : filters) if (f != DELTA_FILTER_NONE) return true;
+    return false;
+}
+
+// ---- encoding ----
+// What a pack is asked for: the blocks, each with its width (1: not split) and filter, whether the zero-run stage runs, and the room
+// the frame needs at least (`fixed` of it header and directory).
+struct EncodeSet {
+    std::vector<u64> lengths;
+    std::vector<u32> widths, filters;
+    bool zrl;
+    u64 n, fixed, least;
+};
+struct Encoded {
+    std::vector<u64> sizes, coded;      // per block: stream bytes; zero-run coded bytes (where that stage ran)
+    std::vector<u32> crcs;
+};
+
+// From d_in to the streams behind d_out + S.fixed.  A stage reads `from` and writes `to`; the two stage blocks swap behind it.
+static int encode_chain(bwts_ctx *ctx, const EncodeSet &S, const u8 *d_in, u8 *d_out, u64 out_cap, Encoded &E)
+{
+    const size_t count = S.lengths.size();
+    const u64 n = S.n;
     const bool seg = count > 1;
-    if (out_cap < members_least_bytes(count)) return BWTS_E_SPACE;
-    std::vector<u32> ws((size_t)count, 1u);
-    if (widths) ws.assign(widths, widths + count);
-    std::vector<u32> fs((size_t)count, DELTA_FILTER_NONE);
-    if (filters) fs.assign(filters, filters + count);
-    const bool delta = filters_named(fs);
-    auto members_set = [&] { u64 total = 0; return seg ? seg_table_set(ctx, lengths, count, &total) : BWTS_OK; };
-    BWTS_TRY(members_set());
-    SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
-    std::vector<u32> crcs((size_t)count);
-    std::vector<u64> sizes((size_t)count), coded((size_t)count);
-    BWTS_TRY(crc_impl(ctx, d_in, n, segs, crcs.data()));
+    if (out_cap < S.least) return BWTS_E_SPACE;
+    BWTS_TRY(blocks_set(ctx, S.lengths, n));
+    const SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;       // (of the blocks, and of their coded bytes: as many segments)
+    E.crcs.resize(count); E.sizes.resize(count); E.coded.resize(count);
+    BWTS_TRY(crc_impl(ctx, d_in, n, segs, E.crcs.data()));
     u8 *to = nullptr, *other = nullptr;
     BWTS_TRY(pack_stage(ctx, 0, n, &to));
     BWTS_TRY(pack_stage(ctx, 1, n, &other));
     const u8 *from = d_in;
     auto done = [&] { from = to; std::swap(to, other); return hipStreamSynchronize(ctx->stream); };
-    if (delta) {
-        // every filtered member on its own; the checksums above are the original bytes'
-        BWTS_TRY(frame_delta(ctx, from, n, ws, fs, to, false, segs));
+    if (any_filter(S.filters)) {
+        // every filtered block on its own; the checksums above are the original bytes'
+        BWTS_TRY(frame_delta(ctx, from, n, S.widths, S.filters, to, false, segs));
         HIPC(done());
     }
-    if (widths_split(ws)) {
-        bool alike = true;
-        for (u32 w : ws) alike = alike && w == ws[0];
-        BWTS_TRY(alike ? planes_impl(ctx, from, n, ws[0], to, false, segs) : planes_w_impl(ctx, from, n, ws.data(), to, false));
+    if (any_split(S.widths)) {
+        BWTS_TRY(frame_planes(ctx, from, n, S.widths, to, false, segs));
         HIPC(done());
     }
     BWTS_TRY(seg ? forward_segments_impl(ctx, from, n, to) : forward_device_impl(ctx, from, n, to));
     HIPC(done());
     BWTS_TRY(mtf_impl(ctx, from, n, to, false, segs));
     HIPC(done());
-    BWTS_TRY(zrl_encode_impl(ctx, from, n, to, n, segs, coded.data()));
-    HIPC(done());
-    u64 m = 0;
-    BWTS_TRY(pack_coded_set(ctx, coded, &m));
-    if (seg) segs = seg_mode(ctx);
-    BWTS_TRY(ec_encode_impl(ctx, from, m, d_out + fixed, out_cap - fixed, segs, sizes.data()));
-    HIPC(hipStreamSynchronize(ctx->stream));
-    u8 *head = (u8 *)(ctx->h_small + SM_PACK_HEAD), *dir = nullptr;
-    std::vector<u8> own;
-    BWTS_TRY(pack_dir_staging(ctx, PACK_VERSION_3, count, own, &dir));
-    u64 total = fixed;
-    for (u64 k = 0; k < count; k++) {
-        members_entry_write(dir + (u64)MEMBERS_ENTRY_BYTES * k, sizes[(size_t)k], crcs[(size_t)k], delta_word(ws[(size_t)k], fs[(size_t)k]), coded[(size_t)k], lengths[k]);
-        total += sizes[(size_t)k];
+    u64 m = n;
+    if (S.zrl) {
+        // the ranks' coded bytes, one block's behind the other's: the coder's segments
+        BWTS_TRY(zrl_encode_impl(ctx, from, n, to, n, segs, E.coded.data()));
+        HIPC(done());
+        BWTS_TRY(pack_coded_set(ctx, E.coded, &m));
     }
+    // the streams go straight to their place; a frame that does not fit is refused by the coder before it writes anything
+    BWTS_TRY(ec_encode_impl(ctx, from, m, d_out + S.fixed, out_cap - S.fixed, segs, E.sizes.data()));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    return BWTS_OK;
+}
+
+// where a pack writes header and directory before they go to the front of the frame
+struct FrameStaging { u8 *head, *dir; std::vector<u8> own; };
+static int encode_staging(bwts_ctx *ctx, u64 entry, u64 count, FrameStaging &T)
+{
+    T.head = (u8 *)(ctx->h_small + SM_PACK_HEAD);
+    return pack_dir_staging(ctx, entry, count, T.own, &T.dir);
+}
+static int encode_finish(bwts_ctx *ctx, const EncodeSet &S, const Encoded &E, const FrameStaging &T, u8 *d_out, u64 out_cap, u64 *out_bytes)
+{
+    u64 total = S.fixed;
+    for (u64 sb : E.sizes) total += sb;
     if (total > out_cap) return BWTS_E_INTERNAL;
-    members_header_write_v(head, delta ? MEMBERS_VERSION_2 : MEMBERS_VERSION, n, count, dir);
-    HIPC(hipMemcpyAsync(d_out + MEMBERS_HEADER_BYTES, dir, (u64)MEMBERS_ENTRY_BYTES * count, hipMemcpyHostToDevice, ctx->stream));
-    HIPC(hipMemcpyAsync(d_out, head, MEMBERS_HEADER_BYTES, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(hipMemcpyAsync(d_out + PACK_HEADER_BYTES, T.dir, S.fixed - PACK_HEADER_BYTES, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(hipMemcpyAsync(d_out, T.head, PACK_HEADER_BYTES, hipMemcpyHostToDevice, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
     *out_bytes = total;
     return BWTS_OK;
 }
 
-// The frame is not trusted: header, then directory, are brought to the host and judged by the predicates of pack_plan.h before
-// anything is made of them; the coder and the zero-run decoder judge their inputs themselves.
-// What both unpacks know of a frame before a stream is touched.  The segment table is the frame's blocks when this returns; dir is
-// staging that the next stage writes over (seg_layout.h): what the directory says is copied out at once.
-// A member frame ("BWTM", include/bwts_members.h) is carried as a version-3 frame whose blocks are the members: H.nblk members,
-// H.B unused, every block with a length and a width of its own.
-struct FrameHead {
-    PackHeader H;
-    std::vector<u8> own;
-    u8 *dir;
-    u64 fixed, entry;
-    bool members = false;
-    std::vector<u64> off;       // members: where every member begins in the concatenation (count + 1)
-    u64 len_at(u64 k) const { return members ? off[(size_t)k + 1] - off[(size_t)k] : pack_block_at(H.n, H.B, k); }
-    u32 width_at(u64 k) const { return members ? members_entry_width(dir, k) : H.width; }
-    u32 filter_at(u64 k) const { return members ? members_entry_filter(dir, k) : DELTA_FILTER_NONE; }
-};
-
-// the blocks of a judged frame as the segment table of the stages
-static int frame_blocks_set(bwts_ctx *ctx, const FrameHead &F)
+// "BWTZ": blocks of B bytes; version 2 adds the zero-run stage, version 3 the split at one width from {2, 4, 8} (so it always runs)
+int pack_device_impl(bwts_ctx *ctx, u32 version, u32 width, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes)
 {
-    if (!F.members) return pack_blocks_set(ctx, F.H.n, F.H.B, F.H.nblk);
-    if (F.H.nblk == 1) return BWTS_OK;
-    std::vector<u64> lengths((size_t)F.H.nblk);
-    for (u64 k = 0; k < F.H.nblk; k++) lengths[(size_t)k] = F.len_at(k);
-    u64 total = 0;
-    BWTS_TRY(seg_table_set(ctx, lengths.data(), F.H.nblk, &total));
-    return total == F.H.n ? BWTS_OK : BWTS_E_INTERNAL;
-}
-
-// the join behind the inverse transform: blocks of `total` bytes in all at the widths given (one block, or all widths alike: the
-// uniform kernels; else one launch at mixed widths)
-static int frame_join(bwts_ctx *ctx, const u8 *from, u64 total, const std::vector<u32> &widths, u8 *to, SegMode segs)
-{
-    bool alike = true;
-    for (u32 w : widths) alike = alike && w == widths[0];
-    if (alike) return planes_impl(ctx, from, total, widths[0], to, true, segs);
-    return planes_w_impl(ctx, from, total, widths.data(), to, true);
-}
-
-static int unpack_members_head(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, const u8 *head, FrameHead &F)
-{
-    MembersHeader M;
-    BWTS_TRY(members_header_check(head, in_bytes, &M));
-    F.members = true;
-    F.H = PackHeader{M.n, 0, M.count, M.dir_crc, PACK_VERSION_3, 0u};      // (either version of the member frame)
-    F.fixed = members_fixed_bytes(M.count);
-    F.entry = MEMBERS_ENTRY_BYTES;
-    BWTS_TRY(pack_dir_staging(ctx, PACK_VERSION_3, M.count, F.own, &F.dir));
-    if (M.count > 1) {
-        HIPC(hipMemcpyAsync(F.dir, d_in + MEMBERS_HEADER_BYTES, F.entry * M.count, hipMemcpyDeviceToHost, ctx->stream));
-        HIPC(hipStreamSynchronize(ctx->stream));
+    const u64 nblk = pack_blocks(n, B), entry = pack_entry_bytes(version);
+    EncodeSet S{uniform_lengths(n, B), {}, {}, version != PACK_VERSION, n, pack_fixed_bytes_v(version, nblk), pack_least_bytes_of(version, n, B)};
+    S.widths.assign((size_t)nblk, version == PACK_VERSION_3 ? width : 1u);
+    S.filters.assign((size_t)nblk, DELTA_FILTER_NONE);
+    Encoded E;
+    BWTS_TRY(encode_chain(ctx, S, d_in, d_out, out_cap, E));
+    FrameStaging T;
+    BWTS_TRY(encode_staging(ctx, entry, nblk, T));
+    for (size_t k = 0; k < (size_t)nblk; k++) {
+        if (version == PACK_VERSION_3) pack_entry_write_v3(T.dir + entry * k, E.sizes[k], E.crcs[k], E.coded[k], width);
+        else if (S.zrl) pack_entry_write_v2(T.dir + entry * k, E.sizes[k], E.crcs[k], E.coded[k]);
+        else pack_entry_write(T.dir + entry * k, E.sizes[k], E.crcs[k]);
     }
-    u64 frame = 0;
-    BWTS_TRY(members_directory_check(F.dir, M, in_bytes, true, &frame));
-    F.off = members_offsets(F.dir, M.count);
-    if (M.count == 1) {
-        // (the small block is the stages' too: the one entry is kept here)
-        F.own.assign(F.dir, F.dir + MEMBERS_ENTRY_BYTES);
-        F.dir = F.own.data();
-    }
-    return frame_blocks_set(ctx, F);
+    pack_header_write_v(T.head, version, n, B, T.dir);
+    return encode_finish(ctx, S, E, T, d_out, out_cap, out_bytes);
 }
 
-static int unpack_frame_head(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, FrameHead &F)
+// "BWTM": members of any lengths, each filtered if asked (filters: null for none) and split at its own width (widths: null for 1, not
+// at all), with the entries and the header of include/bwts_members.h.  A pack in which no member names a filter writes version 1.
+int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, const u32 *filters, u64 count, u64 n, u8 *d_out, u64 out_cap,
+                             u64 *out_bytes)
+{
+    EncodeSet S{std::vector<u64>(lengths, lengths + count), {}, {}, true, n, members_fixed_bytes(count), members_least_bytes(count)};
+    S.widths.assign((size_t)count, 1u);
+    if (widths) S.widths.assign(widths, widths + count);
+    S.filters.assign((size_t)count, DELTA_FILTER_NONE);
+    if (filters) S.filters.assign(filters, filters + count);
+    Encoded E;
+    BWTS_TRY(encode_chain(ctx, S, d_in, d_out, out_cap, E));
+    FrameStaging T;
+    BWTS_TRY(encode_staging(ctx, MEMBERS_ENTRY_BYTES, count, T));
+    for (size_t k = 0; k < (size_t)count; k++)
+        members_entry_write(T.dir + (u64)MEMBERS_ENTRY_BYTES * k, E.sizes[k], E.crcs[k], delta_word(S.widths[k], S.filters[k]), E.coded[k], lengths[k]);
+    members_header_write_v(T.head, any_filter(S.filters) ? MEMBERS_VERSION_2 : MEMBERS_VERSION, n, count, T.dir);
+    return encode_finish(ctx, S, E, T, d_out, out_cap, out_bytes);
+}
+
+// ---- decoding ----
+// The frame is not trusted: header, then directory, are brought to the host and judged (frame_head_check, frame_dir_check) before
+// anything is made of them; the coder and the zero-run decoder judge their inputs themselves.  The segment table is the frame's
+// blocks when this returns.
+static int unpack_frame_head(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, Frame &F)
 {
     if (in_bytes < PACK_LEAST_FRAME || (in_bytes & 15u)) return BWTS_E_FORMAT;
-    u8 *head = (u8 *)(ctx->h_small + SM_PACK_HEAD);
+    u8 *head = (u8 *)(ctx->h_small + SM_PACK_HEAD), *dir = nullptr;
     const u64 first = in_bytes < PACK_HEADER_BYTES + PACK_ENTRY_BYTES_V2 ? in_bytes : PACK_HEADER_BYTES + PACK_ENTRY_BYTES_V2;
     HIPC(hipMemcpyAsync(head, d_in, first, hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
-    if (members_magic(head)) return unpack_members_head(ctx, d_in, in_bytes, head, F);
-    PackHeader &H = F.H;
-    BWTS_TRY(pack_header_check(head, in_bytes, &H));
-    F.fixed = pack_fixed_bytes_v(H.version, H.nblk);
-    F.entry = pack_entry_bytes(H.version);
-    BWTS_TRY(pack_blocks_set(ctx, H.n, H.B, H.nblk));
-    BWTS_TRY(pack_dir_staging(ctx, H.version, H.nblk, F.own, &F.dir));
-    if (H.nblk > 1) {
-        HIPC(hipMemcpyAsync(F.dir, d_in + PACK_HEADER_BYTES, F.entry * H.nblk, hipMemcpyDeviceToHost, ctx->stream));
+    BWTS_TRY(frame_head_check(head, in_bytes, &F));
+    // a "BWTZ" frame's blocks are known from the header, and the directory region lies behind their table; a member frame's blocks
+    // come with the directory
+    if (!F.members) BWTS_TRY(blocks_set(ctx, uniform_lengths(F.n, F.B), F.n));
+    std::vector<u8> own;
+    BWTS_TRY(pack_dir_staging(ctx, F.entry, F.count, own, &dir));
+    if (F.count > 1) {
+        HIPC(hipMemcpyAsync(dir, d_in + PACK_HEADER_BYTES, F.entry * F.count, hipMemcpyDeviceToHost, ctx->stream));
         HIPC(hipStreamSynchronize(ctx->stream));
     }
     u64 frame = 0;
-    return pack_directory_check(F.dir, H, in_bytes, true, &frame);
+    BWTS_TRY(frame_dir_check(dir, F, in_bytes, true, &frame));
+    if (!F.members) return BWTS_OK;
+    std::vector<u64> lengths((size_t)F.count);
+    for (size_t k = 0; k < lengths.size(); k++) lengths[k] = F.len(k);
+    return blocks_set(ctx, lengths, F.n);
 }
 
-int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out)
+// The blocks of a judged frame that a call decodes: all of them, or the covered blocks of a plan.
+struct DecodeSet {
+    u64 total = 0;                              // the blocks' bytes
+    std::vector<u64> lengths, sizes, coded;     // per block: bytes, stream bytes, coded bytes
+    std::vector<u32> want, widths, filters;     // ... checksum, width, filter
+    bool zrl = false, split = false, delta = false;
+};
+static DecodeSet decode_set(const Frame &F, const std::vector<u64> *blocks)
 {
-    FrameHead F;
-    BWTS_TRY(unpack_frame_head(ctx, d_in, in_bytes, F));
-    const PackHeader &H = F.H;
-    const u8 *dir = F.dir;
-    std::vector<u32> widths, filters;
-    if (H.version == PACK_VERSION_3)
-        for (u64 k = 0; k < H.nblk; k++) { widths.push_back(F.width_at(k)); filters.push_back(F.filter_at(k)); }
-    const bool seg = H.nblk > 1, zrl = H.version != PACK_VERSION, planes = widths_split(widths), delta = filters_named(filters);
-    const u64 fixed = F.fixed, entry = F.entry;
-    const SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
-    if (H.n > out_cap) return BWTS_E_SPACE;
-    ctx->tm.n = H.n;
-    // (the staging is the next stage's: what the directory says is kept here)
-    std::vector<u64> sizes((size_t)H.nblk), coded((size_t)H.nblk);
-    std::vector<u32> want((size_t)H.nblk), got((size_t)H.nblk);
-    for (u64 k = 0; k < H.nblk; k++) {
-        sizes[(size_t)k] = pack_le64(dir + entry * k);
-        want[(size_t)k] = ec_le32(dir + entry * k + 8);
-        coded[(size_t)k] = zrl ? pack_le64(dir + entry * k + 16) : F.len_at(k);
+    DecodeSet S;
+    const size_t nb = blocks ? blocks->size() : (size_t)F.count;
+    S.lengths.resize(nb); S.sizes.resize(nb); S.coded.resize(nb); S.want.resize(nb); S.widths.resize(nb); S.filters.resize(nb);
+    for (size_t i = 0; i < nb; i++) {
+        const size_t k = blocks ? (size_t)(*blocks)[i] : i;
+        S.lengths[i] = F.len(k); S.sizes[i] = F.stream[k]; S.coded[i] = F.coded[k];
+        S.want[i] = F.crc[k]; S.widths[i] = F.width[k]; S.filters[i] = F.filter[k];
+        S.total += F.len(k);
     }
-    // The stages go to and fro between d_out and the stage block, and the last one lands in d_out.  Version 1, three stages: ranks
-    // into d_out, bytes of the transform into the block, the input's bytes into d_out.  Version 2, four: the ranks' coded bytes into
-    // the block first.  Version 3, five: the coded bytes into d_out first (they are no more than the H.n bytes it holds), the ranks
-    // into the block, and at the end the join from the block into d_out.  A member frame with filters has the delta decode behind the
-    // join (or in its place): one stage more, and the first one writes the other buffer.
-    u8 *block = nullptr;
-    BWTS_TRY(pack_stage(ctx, 0, H.n, &block));
-    const bool odd = (3 + zrl + planes + delta) % 2 != 0;        // an odd number of stages: the first one writes d_out
-    u8 *to = odd ? d_out : block, *other = odd ? block : d_out;
-    const u8 *from = nullptr;
-    auto done = [&] { from = to; std::swap(to, other); return hipStreamSynchronize(ctx->stream); };
-    u64 m = H.n;
-    SegMode csegs = segs;
-    if (zrl) {
-        BWTS_TRY(pack_coded_set(ctx, coded, &m));
-        if (seg) csegs = seg_mode(ctx);
-    }
+    S.zrl = F.zrl; S.split = any_split(S.widths); S.delta = any_filter(S.filters);
+    return S;
+}
+// how many stages write a buffer: coder, inverse move-to-front and inverse transform always
+static int decode_stages(const DecodeSet &S) { return 3 + S.zrl + S.split + S.delta; }
+
+// the stages of a range read, as the bits of its report (include/bwts_test.h)
+enum { RG_GATHER = 1, RG_DECODE = 2, RG_ZRL = 4, RG_MTF = 8, RG_INVERSE = 16, RG_JOIN = 32, RG_CRC = 64, RG_CUT = 128, RG_DELTA = 256 };
+
+// From the streams at `from`, back to back, to the blocks' bytes with their checksums held against the directory: `from` is where
+// they are when this returns.  The context's table is S's blocks on entry; the first stage writes `to`, the next one `other`, and so
+// on.  stages: not null to have the bit of every stage that ran ORed in.
+static int decode_chain(bwts_ctx *ctx, const DecodeSet &S, const u8 *&from, u8 *to, u8 *other, u64 *stages)
+{
+    const bool seg = S.lengths.size() > 1;
+    const SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;       // (of the blocks, and of their coded bytes: as many segments)
+    const u64 n = S.total;
+    auto next = [&](u64 bit) { if (stages) *stages |= bit; from = to; std::swap(to, other); };
+    auto done = [&](u64 bit) { next(bit); return hipStreamSynchronize(ctx->stream); };
+    u64 m = n;
+    if (S.zrl) BWTS_TRY(pack_coded_set(ctx, S.coded, &m));
     if (seg) {
-        BWTS_TRY(ec_decode_impl(ctx, d_in + fixed, m, to, m, nullptr, csegs, sizes.data()));
+        BWTS_TRY(ec_decode_impl(ctx, from, m, to, m, nullptr, segs, S.sizes.data()));
     } else {
         u64 named = 0;
-        const int rc = ec_decode_impl(ctx, d_in + fixed, sizes[0], to, m, &named, csegs, nullptr);
+        const int rc = ec_decode_impl(ctx, from, S.sizes[0], to, m, &named, segs, nullptr);
         // (room for the bytes the directory names is what the coder was given: a stream that names more, or less, is not this frame's)
         if (rc == BWTS_E_SPACE || (rc == BWTS_OK && named != m)) return BWTS_E_FORMAT;
         BWTS_TRY(rc);
     }
-    from = to; std::swap(to, other);
-    if (zrl) {
-        HIPC(hipStreamSynchronize(ctx->stream));
-        ctx->tm.n = H.n;        // (the coder has put its own n there: the coded bytes)
-        BWTS_TRY(frame_blocks_set(ctx, F));
-        BWTS_TRY(zrl_decode_impl(ctx, from, m, to, H.n, segs, coded.data()));
-        HIPC(done());
+    next(RG_DECODE);        // (the coder has drained the stream itself: it reads its verdict back)
+    ctx->tm.n = n;          // (... and has put its own n there: the coded bytes)
+    if (S.zrl) {
+        BWTS_TRY(blocks_set(ctx, S.lengths, n));
+        BWTS_TRY(zrl_decode_impl(ctx, from, m, to, n, segs, S.coded.data()));
+        HIPC(done(RG_ZRL));
     }
-    BWTS_TRY(mtf_impl(ctx, from, H.n, to, true, segs));
-    HIPC(done());
-    BWTS_TRY(seg ? inverse_segments_impl(ctx, from, H.n, to) : inverse_device_impl(ctx, from, H.n, to));
-    HIPC(done());
-    if (planes) {
-        BWTS_TRY(frame_join(ctx, from, H.n, widths, to, segs));
-        HIPC(done());
+    BWTS_TRY(mtf_impl(ctx, from, n, to, true, segs));
+    HIPC(done(RG_MTF));
+    BWTS_TRY(seg ? inverse_segments_impl(ctx, from, n, to) : inverse_device_impl(ctx, from, n, to));
+    HIPC(done(RG_INVERSE));
+    if (S.split) {
+        BWTS_TRY(frame_planes(ctx, from, n, S.widths, to, true, segs));
+        HIPC(done(RG_JOIN));
     }
-    if (delta) {
-        BWTS_TRY(frame_delta(ctx, from, H.n, widths, filters, to, true, segs));
-        HIPC(done());
+    if (S.delta) {
+        // a touched member is decoded whole, filter included
+        BWTS_TRY(frame_delta(ctx, from, n, S.widths, S.filters, to, true, segs));
+        HIPC(done(RG_DELTA));
     }
+    std::vector<u32> got(S.want.size());
+    BWTS_TRY(crc_impl(ctx, from, n, segs, got.data()));
+    if (stages) *stages |= RG_CRC;
+    return got == S.want ? BWTS_OK : BWTS_E_CHECKSUM;
+}
+
+// The stages go to and fro between d_out and the stage block (d_out holds n bytes, and no stage's output is more), and the first one
+// writes the buffer that makes the last one land in d_out.
+int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u64 out_cap, u64 *n_out)
+{
+    Frame F;
+    BWTS_TRY(unpack_frame_head(ctx, d_in, in_bytes, F));
+    if (F.n > out_cap) return BWTS_E_SPACE;
+    ctx->tm.n = F.n;
+    const DecodeSet S = decode_set(F, nullptr);
+    u8 *block = nullptr;
+    BWTS_TRY(pack_stage(ctx, 0, F.n, &block));
+    const bool odd = decode_stages(S) % 2 != 0;
+    const u8 *from = d_in + F.fixed;
+    BWTS_TRY(decode_chain(ctx, S, from, odd ? d_out : block, odd ? block : d_out, nullptr));
     if (from != d_out) return BWTS_E_INTERNAL;
-    BWTS_TRY(crc_impl(ctx, d_out, H.n, segs, got.data()));
-    if (memcmp(got.data(), want.data(), (size_t)H.nblk * sizeof(u32)) != 0) return BWTS_E_CHECKSUM;
-    *n_out = H.n;
+    *n_out = F.n;
     return BWTS_OK;
 }
 
-// Ranges of a frame (include/bwts_pack.h, "Ranges"): the frame is judged as above, then the ranges; the plan of pack_plan.h names the
-// covered blocks, and only their streams are decoded, through the same stages over a segment table of the covered blocks alone.  The
-// bytes go to and fro between the two stage blocks (neither is d_out here); the covered blocks' checksums are held against the
-// directory, and only then are the ranges cut out of the last stage's block into d_out.
-enum { RG_GATHER = 1, RG_DECODE = 2, RG_ZRL = 4, RG_MTF = 8, RG_INVERSE = 16, RG_JOIN = 32, RG_CRC = 64, RG_CUT = 128, RG_DELTA = 256 };
-
+// Ranges of a frame (include/bwts_pack.h, "Ranges"): the frame is judged as above, then the ranges; the plan names the covered blocks,
+// and only their streams are decoded, over a segment table of the covered blocks alone.  The bytes go to and fro between the two
+// stage blocks (neither is d_out here); only when the covered blocks' checksums agree are the ranges cut out of the last stage's
+// block into d_out.
 int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool packed, const PackRange *ranges, u64 count, u8 *d_out, u64 out_cap, u64 *out_bytes,
                               const u64 *indices)
 {
     u64 *rep = ctx->ranges_report;
     memset(rep, 0, sizeof ctx->ranges_report);
-    FrameHead F;
+    Frame F;
     BWTS_TRY(unpack_frame_head(ctx, d_in, in_bytes, F));
-    const PackHeader &H = F.H;
-    const bool zrl = H.version != PACK_VERSION;
     u64 sum = 0;
     // whole members as ranges (bwts_unpack_members_device): a member frame alone has them
     std::vector<PackRange> whole;
     if (indices) {
         if (!F.members) return BWTS_E_FORMAT;
-        BWTS_TRY(members_index_ranges(F.off, indices, count, &whole));
+        BWTS_TRY(members_index_ranges(F, indices, count, &whole));
         ranges = whole.data();
     }
-    BWTS_TRY(pack_ranges_check(H, ranges, count, out_cap, &sum));
+    BWTS_TRY(pack_ranges_check(F.n, ranges, count, out_cap, &sum));
     PackRangesPlan P;
-    if (F.members) members_ranges_plan(F.off, F.dir, ranges, count, &P);
-    else pack_ranges_plan(H, F.dir, ranges, count, &P);
+    ranges_plan(F, ranges, count, &P);
+    const DecodeSet S = decode_set(F, &P.blocks);
     const u64 C = P.covered_bytes, nb = P.blocks.size();
-    const bool seg = nb > 1, gather = !packed && P.runs.size() > 1;
-    // (the staging is the next stage's: what the directory says of the covered blocks is kept here)
-    std::vector<u64> lengths((size_t)nb), sizes((size_t)nb), coded((size_t)nb);
-    std::vector<u32> want((size_t)nb), got((size_t)nb), widths, filters;
-    for (u64 k = 0; k < nb; k++) {
-        const u8 *e = F.dir + F.entry * P.blocks[(size_t)k];
-        lengths[(size_t)k] = F.len_at(P.blocks[(size_t)k]);
-        if (H.version == PACK_VERSION_3) { widths.push_back(F.width_at(P.blocks[(size_t)k])); filters.push_back(F.filter_at(P.blocks[(size_t)k])); }
-        sizes[(size_t)k] = pack_le64(e);
-        want[(size_t)k] = ec_le32(e + 8);
-        coded[(size_t)k] = zrl ? pack_le64(e + 16) : lengths[(size_t)k];
-    }
+    const bool gather = !packed && P.runs.size() > 1;
     ctx->tm.n = C;
-    rep[0] = nb; rep[1] = P.runs.size(); rep[2] = C; rep[3] = P.stream_bytes; rep[4] = gather; rep[5] = P.out.size(); rep[7] = !seg;
+    rep[0] = nb; rep[1] = P.runs.size(); rep[2] = C; rep[3] = P.stream_bytes; rep[4] = gather; rep[5] = P.out.size(); rep[7] = nb == 1;
     // one covered block: no table, the single-input stages, as a frame of one block
-    auto blocks_set = [&] { u64 total = 0; return seg ? seg_table_set(ctx, lengths.data(), nb, &total) : BWTS_OK; };
-    BWTS_TRY(blocks_set());
-    const SegMode segs = seg ? seg_mode(ctx) : SEG_SINGLE;
+    BWTS_TRY(blocks_set(ctx, S.lengths, C));
     // the stage blocks hold the covered bytes, and the gathered streams where there are any (a stream may be longer than its block)
     const u64 room = gather && P.stream_bytes > C ? P.stream_bytes : C;
     u8 *to = nullptr, *other = nullptr;
@@ -421,48 +378,14 @@ int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool 
     BWTS_TRY(pack_stage(ctx, 1, room, &other));
     // the covered streams, back to back: behind the directory (host form), gathered, or where the one run lies in the frame
     const u8 *from = packed ? d_in + F.fixed : d_in + P.streams[0].src;
-    auto done = [&](u64 bit) { rep[6] |= bit; from = to; std::swap(to, other); return hipStreamSynchronize(ctx->stream); };
     if (gather) {
         BWTS_TRY(copy_pieces_impl(ctx, d_in, in_bytes, P.streams.data(), P.streams.size(), to));
-        HIPC(done(RG_GATHER));
+        HIPC(hipStreamSynchronize(ctx->stream));
+        rep[6] |= RG_GATHER;
+        from = to;
+        std::swap(to, other);
     }
-    u64 m = C;
-    SegMode csegs = segs;
-    if (zrl) {
-        BWTS_TRY(pack_coded_set(ctx, coded, &m));
-        if (seg) csegs = seg_mode(ctx);
-    }
-    if (seg) {
-        BWTS_TRY(ec_decode_impl(ctx, from, m, to, m, nullptr, csegs, sizes.data()));
-    } else {
-        u64 named = 0;
-        const int rc = ec_decode_impl(ctx, from, sizes[0], to, m, &named, csegs, nullptr);
-        if (rc == BWTS_E_SPACE || (rc == BWTS_OK && named != m)) return BWTS_E_FORMAT;
-        BWTS_TRY(rc);
-    }
-    HIPC(done(RG_DECODE));
-    ctx->tm.n = C;        // (the coder has put its own n there)
-    if (zrl) {
-        BWTS_TRY(blocks_set());
-        BWTS_TRY(zrl_decode_impl(ctx, from, m, to, C, segs, coded.data()));
-        HIPC(done(RG_ZRL));
-    }
-    BWTS_TRY(mtf_impl(ctx, from, C, to, true, segs));
-    HIPC(done(RG_MTF));
-    BWTS_TRY(seg ? inverse_segments_impl(ctx, from, C, to) : inverse_device_impl(ctx, from, C, to));
-    HIPC(done(RG_INVERSE));
-    if (widths_split(widths)) {
-        BWTS_TRY(frame_join(ctx, from, C, widths, to, segs));
-        HIPC(done(RG_JOIN));
-    }
-    if (filters_named(filters)) {
-        // a touched member is decoded whole, filter included
-        BWTS_TRY(frame_delta(ctx, from, C, widths, filters, to, true, segs));
-        HIPC(done(RG_DELTA));
-    }
-    BWTS_TRY(crc_impl(ctx, from, C, segs, got.data()));
-    rep[6] |= RG_CRC;
-    if (memcmp(got.data(), want.data(), (size_t)nb * sizeof(u32)) != 0) return BWTS_E_CHECKSUM;
+    BWTS_TRY(decode_chain(ctx, S, from, to, other, &rep[6]));
     BWTS_TRY(copy_pieces_impl(ctx, from, C, P.out.data(), P.out.size(), d_out));
     rep[6] |= RG_CUT;
     *out_bytes = sum;

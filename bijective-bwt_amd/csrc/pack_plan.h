@@ -133,6 +133,9 @@ EC_HD uint64_t pack_least_bytes_v2(uint64_t n, uint64_t B)
     const uint64_t nblk = pack_blocks(n, B);
     return pack_fixed_bytes_v(PACK_VERSION_2, nblk) + nblk * ec_least_bytes(1u);
 }
+// either, by the version
+EC_HD uint64_t pack_bound_bytes_of(uint32_t version, uint64_t n, uint64_t B) { return version == PACK_VERSION ? pack_bound_bytes(n, B) : pack_bound_bytes_v2(n, B); }
+EC_HD uint64_t pack_least_bytes_of(uint32_t version, uint64_t n, uint64_t B) { return version == PACK_VERSION ? pack_least_bytes(n, B) : pack_least_bytes_v2(n, B); }
 
 EC_HD void pack_entry_write(uint8_t e[16], uint64_t stream_bytes, uint32_t crc)
 {
@@ -227,9 +230,9 @@ struct PackRange { uint64_t offset, bytes; };           // bwts_range: bytes [of
 struct PackPiece { uint64_t src, dst, bytes; };         // bytes [src, src + bytes) of one buffer to [dst, dst + bytes) of another
 struct PackRun { uint64_t first, blocks; };             // blocks [first, first + blocks) of the frame
 
-// The ranges of a call against a judged header: PACK_ARG, PACK_RANGE, PACK_SPACE in this order, else PACK_OK and *sum, the bytes of all
-// ranges.  No sum can overflow: at most 2^20 ranges count, each of at most n <= 2^32 bytes.
-static inline int pack_ranges_check(const PackHeader &H, const PackRange *r, uint64_t count, uint64_t out_cap, uint64_t *sum)
+// The ranges of a call against the n bytes of a judged frame: PACK_ARG, PACK_RANGE, PACK_SPACE in this order, else PACK_OK and *sum,
+// the bytes of all ranges.  No sum can overflow: at most 2^20 ranges count, each of at most n <= 2^32 bytes.
+static inline int pack_ranges_check(uint64_t n, const PackRange *r, uint64_t count, uint64_t out_cap, uint64_t *sum)
 {
     if (!r || count == 0) return PACK_ARG;
     if (count > PACK_MAX_RANGES) return PACK_RANGE;
@@ -237,7 +240,7 @@ static inline int pack_ranges_check(const PackHeader &H, const PackRange *r, uin
         if (r[i].bytes == 0) return PACK_ARG;
     uint64_t total = 0;
     for (uint64_t i = 0; i < count; i++) {
-        if (r[i].bytes > H.n || r[i].offset > H.n - r[i].bytes) return PACK_RANGE;      // (by subtraction: offset + bytes may wrap)
+        if (r[i].bytes > n || r[i].offset > n - r[i].bytes) return PACK_RANGE;      // (by subtraction: offset + bytes may wrap)
         total += r[i].bytes;
     }
     if (total > PACK_MAX_RANGE_BYTES) return PACK_RANGE;
@@ -246,8 +249,9 @@ static inline int pack_ranges_check(const PackHeader &H, const PackRange *r, uin
     return PACK_OK;
 }
 
-// What a call with these ranges decodes and moves.  The covered blocks are those a range touches, as sorted maximal runs; they are
-// decoded into one buffer, block behind block in the frame's order (covered bytes in all), so every range is one piece of that buffer.
+// What a call with these ranges decodes and moves (ranges_plan in members_plan.h fills it, for a frame of either magic).  The covered
+// blocks are those a range touches, as sorted maximal runs; they are decoded into one buffer, block behind block in the frame's order
+// (covered bytes in all), so every range is one piece of that buffer.
 struct PackRangesPlan {
     std::vector<PackRun> runs;
     std::vector<PackPiece> streams;     // one per run: src in the frame, dst in the gathered streams
@@ -255,47 +259,3 @@ struct PackRangesPlan {
     std::vector<uint64_t> blocks;       // the covered blocks, ascending
     uint64_t covered_bytes, stream_bytes, coded_bytes, out_bytes;
 };
-
-// H and dir have passed pack_header_check and pack_directory_check, the ranges pack_ranges_check.  Nothing here can overflow: the
-// directory check has held the sum of all stream_bytes against the frame's length, coded_bytes against the blocks' lengths, and the
-// blocks' lengths add up to n <= 2^32; the ranges' sum is bounded by their check.
-static inline void pack_ranges_plan(const PackHeader &H, const uint8_t *dir, const PackRange *r, uint64_t count, PackRangesPlan *P)
-{
-    const uint64_t entry = pack_entry_bytes(H.version);
-    // how many ranges begin in a block minus how many end in the one before: a running sum above zero marks a covered block
-    std::vector<int32_t> step((size_t)H.nblk + 1, 0);
-    for (uint64_t i = 0; i < count; i++) {
-        step[(size_t)(r[i].offset / H.B)]++;
-        step[(size_t)((r[i].offset + r[i].bytes - 1u) / H.B) + 1]--;
-    }
-    std::vector<uint64_t> at((size_t)H.nblk, 0);         // where a covered block begins in the covered-block buffer
-    P->runs.clear(); P->streams.clear(); P->out.clear(); P->blocks.clear();
-    P->covered_bytes = P->stream_bytes = P->coded_bytes = P->out_bytes = 0;
-    uint64_t frame_at = pack_fixed_bytes_v(H.version, H.nblk);
-    int64_t open = 0;
-    bool in_run = false;
-    for (uint64_t b = 0; b < H.nblk; b++) {
-        const uint64_t sb = pack_le64(dir + entry * b), len = pack_block_at(H.n, H.B, b);
-        open += step[(size_t)b];
-        if (open > 0) {
-            if (!in_run) {
-                P->runs.push_back(PackRun{b, 0});
-                P->streams.push_back(PackPiece{frame_at, P->stream_bytes, 0});
-            }
-            P->runs.back().blocks++;
-            P->streams.back().bytes += sb;
-            P->blocks.push_back(b);
-            at[(size_t)b] = P->covered_bytes;
-            P->covered_bytes += len;
-            P->stream_bytes += sb;
-            P->coded_bytes += H.version != PACK_VERSION ? pack_le64(dir + entry * b + 16) : len;
-        }
-        in_run = open > 0;
-        frame_at += sb;
-    }
-    for (uint64_t i = 0; i < count; i++) {
-        const uint64_t b = r[i].offset / H.B;
-        P->out.push_back(PackPiece{at[(size_t)b] + (r[i].offset - b * H.B), P->out_bytes, r[i].bytes});
-        P->out_bytes += r[i].bytes;
-    }
-}

@@ -6,6 +6,7 @@
 // count (offset, bytes) pairs of u64, `words` u64 the model's plan }.  Frame head and ranges are judged from heap blocks of exactly
 // their length, so a read past either is caught.  The first case is a valid member frame of several members; it is cut here at every
 // length below 128 and paired with hostile ranges and indices.
+// argv[2]: the cases file of pack_range_check.cc ("BWTZ" frames), each planned by division and by bisection (both_ways_cases).
 #include "members_plan.h"
 
 #include <stdio.h>
@@ -14,23 +15,41 @@
 #include <vector>
 
 static int failures = 0;
+static size_t both_ways = 0;        // plans of "BWTZ" frames made by division and by bisection, and compared
 #define CHECK(cond, ...) do { if (!(cond)) { failures++; printf("FAILED %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } while (0)
 
 // the library's order: header, directory, ranges (or indices), plan; the plan as the words of the cases file
 static int judge(const uint8_t *head, uint64_t in_bytes, const PackRange *r, const uint64_t *indices, uint64_t count, uint64_t out_cap,
                  std::vector<uint64_t> *words)
 {
-    PackHeader H;
-    uint64_t fixed = 0, sum = 0;
+    Frame H;
+    uint64_t sum = 0;
     PackRangesPlan P;
     std::vector<PackRange> whole;
     const PackRange *rs = nullptr;
-    const int rc = frame_ranges_plan(head, in_bytes, r, indices, count, out_cap, &H, &fixed, &sum, &whole, &rs, &P);
+    const int rc = frame_ranges_plan(head, in_bytes, r, indices, count, out_cap, &H, &sum, &whole, &rs, &P);
     if (rc != PACK_OK) return rc;
+    const uint64_t fixed = H.fixed;
+    // the same ranges through the other way of finding a byte's block: the bisection of the offsets where the frame's blocks are
+    // uniform (B switched off); for a member frame there is no other way, and the plan must simply repeat
+    {
+        Frame G = H;
+        G.B = 0;
+        PackRangesPlan Q;
+        ranges_plan(G, rs, count, &Q);
+        bool same = Q.covered_bytes == P.covered_bytes && Q.stream_bytes == P.stream_bytes && Q.coded_bytes == P.coded_bytes && Q.out_bytes == P.out_bytes &&
+                    Q.blocks == P.blocks && Q.runs.size() == P.runs.size() && Q.streams.size() == P.streams.size() && Q.out.size() == P.out.size();
+        for (size_t i = 0; same && i < P.runs.size(); i++)
+            same = Q.runs[i].first == P.runs[i].first && Q.runs[i].blocks == P.runs[i].blocks && Q.streams[i].src == P.streams[i].src &&
+                   Q.streams[i].dst == P.streams[i].dst && Q.streams[i].bytes == P.streams[i].bytes;
+        for (size_t i = 0; same && i < P.out.size(); i++) same = Q.out[i].src == P.out[i].src && Q.out[i].dst == P.out[i].dst && Q.out[i].bytes == P.out[i].bytes;
+        CHECK(same, "the plan by division and the plan by bisection differ");
+        if (!H.members) both_ways++;
+    }
     CHECK(P.out_bytes == sum && P.out.size() == count && P.runs.size() == P.streams.size(), "the plan's own sums");
     uint64_t blocks = 0, gathered = 0;
     for (size_t i = 0; i < P.runs.size(); i++) {
-        CHECK(P.runs[i].blocks >= 1 && P.runs[i].first + P.runs[i].blocks <= H.nblk, "run %zu inside the frame", i);
+        CHECK(P.runs[i].blocks >= 1 && P.runs[i].first + P.runs[i].blocks <= H.count, "run %zu inside the frame", i);
         if (i) CHECK(P.runs[i - 1].first + P.runs[i - 1].blocks < P.runs[i].first, "runs %zu and %zu sorted and maximal", i - 1, i);
         CHECK(P.streams[i].dst == gathered && P.streams[i].src >= fixed && P.streams[i].src + P.streams[i].bytes <= in_bytes, "stream piece %zu", i);
         blocks += P.runs[i].blocks;
@@ -65,17 +84,53 @@ static int judge_copy(const uint8_t *head, uint64_t head_bytes, uint64_t in_byte
     return rc;
 }
 
+static bool read_file(const char *path, std::vector<uint8_t> *file)
+{
+    FILE *fp = fopen(path, "rb");
+    if (!fp) { printf("cannot open %s\n", path); return false; }
+    uint8_t buf[65536];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof buf, fp)) > 0) file->insert(file->end(), buf, buf + got);
+    fclose(fp);
+    return true;
+}
+
+// The cases of pack_range_check.cc ("BWTZ" frames, the same layout): every one judged and planned here too, where judge() plans it
+// a second time through the offsets path and holds the two plans against each other word for word.  The merged loop can be wrong
+// there without a frame test noticing: no "BWTZ" call ever bisects.
+static int both_ways_cases(const std::vector<uint8_t> &file)
+{
+    size_t at = 0, cases = 0;
+    while (at + 32 <= file.size()) {
+        int32_t want;
+        uint32_t head_bytes, count, nwords;
+        uint64_t in_bytes, out_cap;
+        memcpy(&want, file.data() + at, 4); memcpy(&head_bytes, file.data() + at + 4, 4);
+        memcpy(&in_bytes, file.data() + at + 8, 8); memcpy(&out_cap, file.data() + at + 16, 8);
+        memcpy(&count, file.data() + at + 24, 4); memcpy(&nwords, file.data() + at + 28, 4);
+        at += 32;
+        if (at + head_bytes + 16ull * count + 8ull * nwords > file.size()) { printf("cases file cut short\n"); return 2; }
+        const uint8_t *head = file.data() + at;
+        std::vector<uint64_t> pairs(2 * (size_t)count + 1), model((size_t)nwords), words;
+        if (count) memcpy(pairs.data(), head + head_bytes, 16 * (size_t)count);
+        if (nwords) memcpy(model.data(), head + head_bytes + 16 * (size_t)count, 8 * (size_t)nwords);
+        const int rc = judge_copy(head, head_bytes, in_bytes, pairs.data(), count, false, out_cap, &words);
+        CHECK(rc == want, "\"BWTZ\" case %zu: %d, the model says %d", cases, rc, (int)want);
+        if (rc == PACK_OK && want == PACK_OK) CHECK(words == model, "\"BWTZ\" case %zu: the plan is not the model's", cases);
+        at += head_bytes + 16 * (size_t)count + 8 * (size_t)nwords;
+        cases++;
+    }
+    CHECK(cases >= 160 && both_ways >= 100, "%zu \"BWTZ\" cases, %zu planned both ways", cases, both_ways);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     static_assert(sizeof(PackRange) == 16, "two words");
-    if (argc != 2) { printf("usage: members_plan_check <cases>\n"); return 2; }
-    FILE *fp = fopen(argv[1], "rb");
-    if (!fp) { printf("cannot open %s\n", argv[1]); return 2; }
-    std::vector<uint8_t> file;
-    uint8_t buf[65536];
-    size_t got;
-    while ((got = fread(buf, 1, sizeof buf, fp)) > 0) file.insert(file.end(), buf, buf + got);
-    fclose(fp);
+    if (argc != 3) { printf("usage: members_plan_check <cases> <cases of pack_range_check>\n"); return 2; }
+    std::vector<uint8_t> file, bwtz;
+    if (!read_file(argv[1], &file) || !read_file(argv[2], &bwtz)) return 2;
+    if (both_ways_cases(bwtz) != 0) return 2;
 
     // the cut of a call at mixed widths (planes_plan.h)
     CHECK(planes_tiles_w(1, 1) == 1 && planes_tiles_w(PLANES_COPY_T, 1) == 1 && planes_tiles_w(PLANES_COPY_T + 1, 1) == 2, "tiles of a copied segment");
@@ -154,7 +209,10 @@ int main(int argc, char **argv)
         CHECK(judge_copy(valid.data(), valid.size(), valid_in_bytes, zero[0], 2, false, big, nullptr) == PACK_ARG, "a range of no bytes comes before one that leaves the input");
         CHECK(judge_copy(valid.data(), valid.size(), valid_in_bytes, nullptr, 0, false, big, nullptr) == PACK_ARG, "no ranges");
         // indices: any order, repeats; one that names no member; too many
-        const std::vector<uint64_t> off = members_offsets(valid.data() + MEMBERS_HEADER_BYTES, M.count);
+        Frame V;
+        CHECK(frame_head_check(valid.data(), valid_in_bytes, &V) == PACK_OK && frame_dir_check(valid.data() + MEMBERS_HEADER_BYTES, V, valid_in_bytes, true, &frame) == PACK_OK &&
+              V.members && V.count == M.count && V.off.size() == M.count + 1 && V.off[M.count] == n, "the judged frame");
+        const std::vector<uint64_t> &off = V.off;
         const uint64_t idx[4] = {M.count - 1, 0, M.count - 1, 1};
         std::vector<uint64_t> words;
         CHECK(judge_copy(valid.data(), valid.size(), valid_in_bytes, idx, 4, true, big, &words) == PACK_OK && words[0] == (M.count > 3 ? 3u : M.count), "indices");

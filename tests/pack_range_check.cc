@@ -1,12 +1,12 @@
-// pack_range_check.cc -- the range plan of pack_plan.h (pack_ranges_check, pack_ranges_plan) as a host program of its own, for the
-// sanitizers (tests/test_pack_range_model.py builds it with -fsanitize=address,undefined and runs it as a child process).
+// pack_range_check.cc -- the range plan of a "BWTZ" frame (pack_ranges_check, and ranges_plan over a judged Frame: members_plan.h) as
+// a host program of its own, for the sanitizers (tests/test_pack_range_model.py builds it with -fsanitize=address,undefined and runs it as a child process).
 //
 // argv[1]: a file of cases, each { i32 the code the checks must give, u32 head_bytes, u64 in_bytes, u64 out_cap, u32 count, u32 words,
 // head_bytes bytes: the frame's header and directory (all of the frame where those are refused), count (offset, bytes) pairs of u64,
 // `words` u64 the model's plan: covered blocks, runs, covered bytes, stream bytes, coded bytes, output bytes, then the runs, the
 // stream pieces and the output pieces }.  Frame head and ranges are judged from heap blocks of exactly their length, so a read past
 // either is caught.  The first case is a valid frame of several blocks; it is paired here with ranges no model run could afford.
-#include "pack_plan.h"
+#include "members_plan.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,26 +19,27 @@ static int failures = 0;
 // the library's order: header, directory, ranges, plan; the plan as the words of the cases file
 static int judge(const uint8_t *head, uint64_t in_bytes, const PackRange *r, uint64_t count, uint64_t out_cap, std::vector<uint64_t> *words)
 {
-    PackHeader H;
+    Frame F;
     uint64_t frame = 0, sum = 0;
-    int rc = pack_header_check(head, in_bytes, &H);
+    int rc = frame_head_check(head, in_bytes, &F);
     if (rc != PACK_OK) return rc;
-    rc = pack_directory_check(head + PACK_HEADER_BYTES, H, in_bytes, true, &frame);
+    rc = frame_dir_check(head + PACK_HEADER_BYTES, F, in_bytes, true, &frame);
     if (rc != PACK_OK) return rc;
-    rc = pack_ranges_check(H, r, count, out_cap, &sum);
+    CHECK(!F.members && F.B == F.z.B && F.count == F.z.nblk, "a \"BWTZ\" frame, planned by dividing by B");
+    rc = pack_ranges_check(F.n, r, count, out_cap, &sum);
     if (rc != PACK_OK) return rc;
     PackRangesPlan P;
-    pack_ranges_plan(H, head + PACK_HEADER_BYTES, r, count, &P);
+    ranges_plan(F, r, count, &P);
     CHECK(P.out_bytes == sum && P.out.size() == count && P.runs.size() == P.streams.size(), "the plan's own sums");
     uint64_t blocks = 0, gathered = 0;
     for (size_t i = 0; i < P.runs.size(); i++) {
-        CHECK(P.runs[i].blocks >= 1 && P.runs[i].first + P.runs[i].blocks <= H.nblk, "run %zu inside the frame", i);
+        CHECK(P.runs[i].blocks >= 1 && P.runs[i].first + P.runs[i].blocks <= F.count, "run %zu inside the frame", i);
         if (i) CHECK(P.runs[i - 1].first + P.runs[i - 1].blocks < P.runs[i].first, "runs %zu and %zu sorted and maximal", i - 1, i);
         CHECK(P.streams[i].dst == gathered && P.streams[i].src + P.streams[i].bytes <= in_bytes, "stream piece %zu", i);
         blocks += P.runs[i].blocks;
         gathered += P.streams[i].bytes;
     }
-    CHECK(blocks == P.blocks.size() && gathered == P.stream_bytes && P.covered_bytes <= H.n && P.coded_bytes <= P.covered_bytes, "covered sums");
+    CHECK(blocks == P.blocks.size() && gathered == P.stream_bytes && P.covered_bytes <= F.n && P.coded_bytes <= P.covered_bytes, "covered sums");
     for (size_t i = 0; i < P.out.size(); i++)
         CHECK(P.out[i].bytes == r[i].bytes && P.out[i].src + P.out[i].bytes <= P.covered_bytes && P.out[i].dst + P.out[i].bytes <= sum, "output piece %zu", i);
     if (words) {

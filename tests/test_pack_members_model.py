@@ -13,6 +13,7 @@ import pack_members_model as MM
 import pack_v2_model as P2
 import pack_v3_model as P3
 from test_pack_model import _put, fixture_input
+from test_pack_range_model import write_cases_file as write_bwtz_cases_file
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -270,7 +271,8 @@ def test_library_host_arithmetic_against_the_model(pkg):
 def test_plan_under_sanitizers(tmp_path):
     """tests/members_plan_check.cc drives the header and directory predicates and the range plan of members_plan.h over every case
     above, each from heap blocks of exactly the header's, directory's and ranges' length, over the valid frame cut at every length
-    below 128, and over a valid directory with hostile ranges and indices."""
+    below 128, and over a valid directory with hostile ranges and indices.  It also plans every "BWTZ" case of test_pack_range_model
+    twice, by division by B and by bisection of the same blocks' offsets, and holds the two plans against each other."""
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     assert cxx, "no host C++ compiler"
     path = str(tmp_path / "cases.bin")
@@ -284,9 +286,11 @@ def test_plan_under_sanitizers(tmp_path):
             head = frame_head(f)
             out.write(struct.pack("<iIQQII", want, len(head), len(f), BIG if cap is None else cap, len(rs), len(words)) + head)
             out.write(b"".join(struct.pack("<QQ", o, b) for o, b in rs) + b"".join(struct.pack("<Q", v) for v in words))
+    bwtz = str(tmp_path / "bwtz_cases.bin")
+    write_bwtz_cases_file(bwtz)
     exe = str(tmp_path / "members_plan_check")
     subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-I", os.path.join(ROOT, "bijective-bwt_amd", "csrc"), os.path.join(ROOT, "tests", "members_plan_check.cc"), "-o", exe])
-    r = subprocess.run([exe, path], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env={"PATH": os.environ.get("PATH", "")})
+    r = subprocess.run([exe, path, bwtz], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env={"PATH": os.environ.get("PATH", "")})
     assert r.returncode == 0, (r.stdout.decode(errors="replace")[-1000:], r.stderr.decode(errors="replace")[-2000:])
     assert r.stdout.decode().strip().endswith("checks ok")

@@ -247,13 +247,8 @@ def test_plan_hook_arguments(pkg):
 
 
 # -- the plan under the sanitizers, as a program of its own ---------------------------------------------------------------
-def test_plan_under_sanitizers(tmp_path):
-    """tests/pack_range_check.cc drives pack_ranges_check and pack_ranges_plan over every case above, each from heap blocks of exactly
-    the header's, directory's and ranges' length, and over a valid directory with hostile ranges: overflowing sums, 2^20 one-byte
-    ranges in one block."""
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    path = str(tmp_path / "cases.bin")
+def write_cases_file(path):
+    """plan_cases() with the model's answers, in the layout that tests/pack_range_check.cc reads (tests/members_plan_check.cc too)."""
     with open(path, "wb") as out:
         for name, f, rs, cap in plan_cases():
             want, p = model_plan_or_code(f, rs, cap)
@@ -264,6 +259,16 @@ def test_plan_under_sanitizers(tmp_path):
             head = frame_head(f)
             out.write(struct.pack("<iIQQII", want, len(head), len(f), BIG if cap is None else cap, len(rs), len(words)) + head)
             out.write(b"".join(struct.pack("<QQ", o, b) for o, b in rs) + b"".join(struct.pack("<Q", v) for v in words))
+
+
+def test_plan_under_sanitizers(tmp_path):
+    """tests/pack_range_check.cc drives pack_ranges_check and the range plan over every case above, each from heap blocks of exactly
+    the header's, directory's and ranges' length, and over a valid directory with hostile ranges: overflowing sums, 2^20 one-byte
+    ranges in one block."""
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    path = str(tmp_path / "cases.bin")
+    write_cases_file(path)
     exe = str(tmp_path / "pack_range_check")
     subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-I", os.path.join(ROOT, "bijective-bwt_amd", "csrc"), os.path.join(ROOT, "tests", "pack_range_check.cc"), "-o", exe])

@@ -75,6 +75,7 @@ MEMBERS_EXPORTS = [
     "bwts_planes_split_segments_w_device", "bwts_planes_join_segments_w_device", "bwts_pack_members_bound",
     "bwts_pack_members_device", "bwts_pack_members", "bwts_frame_members", "bwts_unpack_members_device", "bwts_unpack_members",
     "bwts_pack_members_f_device", "bwts_pack_members_f", "bwts_frame_members_f",
+    "bwts_pack_members_bound_m", "bwts_pack_members_m_device", "bwts_pack_members_m", "bwts_frame_members_m",
 ]
 # ... include/bwts_delta.h (delta filter of integer arrays, the stage in front of the byte-plane split) ...
 DELTA_EXPORTS = [
@@ -82,6 +83,7 @@ DELTA_EXPORTS = [
     "bwts_delta_encode", "bwts_delta_decode",
 ]
 FILTER_NONE, FILTER_DELTA = 0, 1
+METHOD_CHAIN, METHOD_ORDER0 = 0, 1      # a member's method (member frame version 3): the whole chain, or its planes coded directly
 # ... and include/bwts_test.h (harness and unit-test hooks)
 TEST_EXPORTS = [
     "bwts_generate_device", "bwts_device_alloc", "bwts_device_free", "bwts_copy_to_device", "bwts_copy_to_host",
@@ -94,7 +96,7 @@ TEST_EXPORTS = [
 ]
 # bwts_debug_unpack_ranges_report: the words of the record, and the stages by their bits
 RANGES_REPORT_FIELDS = ["blocks", "runs", "covered_bytes", "stream_bytes", "gathered", "pieces", "stages", "single"]
-RANGES_STAGES = {1: "gather", 2: "decode", 4: "zrl", 8: "mtf", 16: "inverse", 32: "join", 64: "crc", 128: "cut", 256: "delta"}
+RANGES_STAGES = {1: "gather", 2: "decode", 4: "zrl", 8: "mtf", 16: "inverse", 32: "join", 64: "crc", 128: "cut", 256: "delta", 512: "regroup"}
 # bwts_debug_inverse_report: the words of one attempt's record, and what marks, outcomes and forms are called
 INV_REPORT_FIELDS = ["g", "mark", "outcome", "s", "virtual", "node_cap", "nu", "nu2", "ucap_first", "second_collect",
                      "listed_classes", "mom_fallback", "unit_rank", "kc", "kt", "form"]
@@ -265,6 +267,11 @@ def lib():
         for name in ("bwts_pack_members_f_device", "bwts_pack_members_f"):
             getattr(L, name).argtypes = [vp, vp, vp, vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
         L.bwts_frame_members_f.argtypes = [vp, u64, vp, vp, vp, u64, ctypes.POINTER(u64)]
+        L.bwts_pack_members_bound_m.argtypes = [vp, vp, vp, u64]
+        L.bwts_pack_members_bound_m.restype = u64
+        for name in ("bwts_pack_members_m_device", "bwts_pack_members_m"):
+            getattr(L, name).argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
+        L.bwts_frame_members_m.argtypes = [vp, u64, vp, vp, vp, vp, u64, ctypes.POINTER(u64)]
         for name in ("bwts_delta_encode_device", "bwts_delta_decode_device", "bwts_delta_encode", "bwts_delta_decode"):
             getattr(L, name).argtypes = [vp, vp, u64, u32, vp]
         for name in ("bwts_delta_encode_segments_f_device", "bwts_delta_decode_segments_f_device"):
@@ -741,27 +748,31 @@ class Context:
         ls, ws = _members(lengths, widths)
         self._check(lib().bwts_planes_join_segments_w_device(self._h, _ptr(d_in), ls.ctypes.data, ws.ctypes.data, ls.size, _ptr(d_out)))
 
-    def pack_members(self, arrays, widths=None, filters=None, out_cap=None):
-        """bwts_pack_members_f: one member frame of the arrays (bytes-like, or numpy arrays of any dtype, taken as their bytes); widths: one
+    def pack_members(self, arrays, widths=None, filters=None, out_cap=None, methods=None):
+        """bwts_pack_members_m: one member frame of the arrays (bytes-like, or numpy arrays of any dtype, taken as their bytes); widths: one
         of 1, 2, 4, 8 per array, None for no split at all; filters: 0 or 1 (FILTER_DELTA: the delta filter of include/bwts_delta.h at the
-        array's width) per array, None for none -- both named by the caller, never guessed from a dtype (host buffers)."""
+        array's width) per array, None for none; methods: 0 or 1 (METHOD_ORDER0: the array's byte planes coded directly, for weights,
+        noise and hashes) per array, None for the whole chain everywhere -- all named by the caller, never guessed from a dtype (host
+        buffers)."""
         parts = [_bytes_of(a) for a in arrays]
         ls, ws = _members([p.size for p in parts], widths)
-        fs = _filters(ls, filters)
+        fs, ms = _filters(ls, filters), _methods(ls, methods)
         a = np.concatenate(parts) if parts else np.empty(0, dtype=np.uint8)
-        out = np.empty(pack_members_bound(ls) if out_cap is None else int(out_cap), dtype=np.uint8)
+        out = np.empty(pack_members_bound(ls, ws, ms) if out_cap is None else int(out_cap), dtype=np.uint8)
         got = ctypes.c_uint64(0)
-        self._check(lib().bwts_pack_members_f(self._h, a.ctypes.data, ls.ctypes.data, None if ws is None else ws.ctypes.data,
-                                              None if fs is None else fs.ctypes.data, ls.size, out.ctypes.data, out.size, ctypes.byref(got)))
+        self._check(lib().bwts_pack_members_m(self._h, a.ctypes.data, ls.ctypes.data, None if ws is None else ws.ctypes.data,
+                                              None if fs is None else fs.ctypes.data, None if ms is None else ms.ctypes.data, ls.size,
+                                              out.ctypes.data, out.size, ctypes.byref(got)))
         return out[:got.value].copy()
 
-    def pack_members_device(self, d_in, lengths, widths, d_out, out_cap, filters=None):
-        """bwts_pack_members_f_device: the members lie back to back in d_in; returns the frame's size in bytes."""
+    def pack_members_device(self, d_in, lengths, widths, d_out, out_cap, filters=None, methods=None):
+        """bwts_pack_members_m_device: the members lie back to back in d_in; returns the frame's size in bytes."""
         ls, ws = _members(lengths, widths)
-        fs = _filters(ls, filters)
+        fs, ms = _filters(ls, filters), _methods(ls, methods)
         got = ctypes.c_uint64(0)
-        self._check(lib().bwts_pack_members_f_device(self._h, _ptr(d_in), ls.ctypes.data, None if ws is None else ws.ctypes.data,
-                                                     None if fs is None else fs.ctypes.data, ls.size, _ptr(d_out), int(out_cap), ctypes.byref(got)))
+        self._check(lib().bwts_pack_members_m_device(self._h, _ptr(d_in), ls.ctypes.data, None if ws is None else ws.ctypes.data,
+                                                     None if fs is None else fs.ctypes.data, None if ms is None else ms.ctypes.data, ls.size,
+                                                     _ptr(d_out), int(out_cap), ctypes.byref(got)))
         return int(got.value)
 
     def unpack_members(self, frame, indices=None):
@@ -1090,12 +1101,26 @@ def _members_f(lengths, widths, filters):
     return ls, ws, _filters(ls, filters)
 
 
-def pack_members_bound(lengths):
-    """bwts_pack_members_bound: the largest member frame of members of these lengths."""
-    ls = np.ascontiguousarray(lengths, dtype=np.uint64).reshape(-1)
-    b = int(lib().bwts_pack_members_bound(ls.ctypes.data if ls.size else None, ls.size))
+def _methods(ls, methods):
+    """The methods of a member call as the array the library takes; None stays None (the whole chain)."""
+    if methods is None:
+        return None
+    ms = np.ascontiguousarray(methods, dtype=np.uint32).reshape(-1)
+    if ms.size != ls.size:
+        raise BwtsError(-1, "one method per member")
+    return ms
+
+
+def pack_members_bound(lengths, widths=None, methods=None):
+    """bwts_pack_members_bound_m: the largest member frame of members of these lengths (and, where methods are named, widths)."""
+    ls, ws = _members(lengths, widths)
+    ms = _methods(ls, methods)
+    if ms is None:
+        b = int(lib().bwts_pack_members_bound(ls.ctypes.data if ls.size else None, ls.size))
+    else:
+        b = int(lib().bwts_pack_members_bound_m(ls.ctypes.data if ls.size else None, None if ws is None else ws.ctypes.data, ms.ctypes.data, ls.size))
     if b == 0:
-        bad = ls.size == 0 or bool((ls == 0).any())
+        bad = ls.size == 0 or bool((ls == 0).any()) or (ms is not None and (bool((ms > 1).any()) or (ws is not None and not bool(np.isin(ws, (1, 2, 4, 8)).all()))))
         raise BwtsError(-1 if bad else -5, "no bound for these lengths")
     return b
 
@@ -1126,6 +1151,20 @@ def frame_member_filters(frame):
     if rc != 0:
         raise BwtsError(rc, lib().bwts_strerror(rc).decode())
     return fs.tolist()
+
+
+def frame_member_methods(frame):
+    """bwts_frame_members_m: the members' methods, a list (all 0 below version 3), from header and directory (host arithmetic)."""
+    a = _u8(frame)
+    count = ctypes.c_uint64(0)
+    rc = lib().bwts_frame_members_m(a.ctypes.data, a.size, None, None, None, None, 0, ctypes.byref(count))
+    if rc != 0:
+        raise BwtsError(rc, lib().bwts_strerror(rc).decode())
+    ms = np.zeros(count.value, dtype=np.uint32)
+    rc = lib().bwts_frame_members_m(a.ctypes.data, a.size, None, None, None, ms.ctypes.data, ms.size, ctypes.byref(count))
+    if rc != 0:
+        raise BwtsError(rc, lib().bwts_strerror(rc).decode())
+    return ms.tolist()
 
 
 def _ranges(ranges):

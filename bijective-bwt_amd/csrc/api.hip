@@ -893,31 +893,49 @@ extern "C" uint64_t bwts_pack_members_bound(const uint64_t *lengths, uint64_t co
     return members_bound_bytes(lengths, count);
 }
 
-extern "C" int bwts_pack_members_f_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters, uint64_t count,
-                                          void *d_out, uint64_t out_cap, uint64_t *out_bytes)
+extern "C" uint64_t bwts_pack_members_bound_m(const uint64_t *lengths, const uint32_t *widths, const uint32_t *methods, uint64_t count)
+{
+    return members_bound_bytes_m(lengths, widths, methods, count);
+}
+
+extern "C" int bwts_pack_members_m_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters,
+                                          const uint32_t *methods, uint64_t count, void *d_out, uint64_t out_cap, uint64_t *out_bytes)
 {
     if (!ctx || !d_in || !d_out || !out_bytes || ((uintptr_t)d_out & 15)) return BWTS_E_ARG;
     u64 n = 0;
-    BWTS_TRY(members_args_check_f(lengths, widths, filters, count, &n));
+    BWTS_TRY(members_args_check_m(lengths, widths, filters, methods, count, &n));
     if (ranges_overlap(d_in, n, d_out, out_cap)) return BWTS_E_ARG;
     return run_sized(ctx, n, "pack members", [&] {
-        return pack_members_device_impl(ctx, (const u8 *)d_in, lengths, widths, filters, count, n, (u8 *)d_out, out_cap, out_bytes);
+        return pack_members_device_impl(ctx, (const u8 *)d_in, lengths, widths, filters, methods, count, n, (u8 *)d_out, out_cap, out_bytes);
     });
+}
+
+extern "C" int bwts_pack_members_m(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters,
+                                   const uint32_t *methods, uint64_t count, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    if (!ctx || !in || !out || !out_bytes) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(members_args_check_m(lengths, widths, filters, methods, count, &n));
+    // (without a method both are what they were: members_bound_bytes and members_least_bytes)
+    const u64 bound = members_bound_bytes_m(lengths, widths, methods, count);
+    const u64 cap = out_cap < bound ? out_cap : bound;
+    if (cap < members_least_bytes_m(lengths, widths, methods, count)) return BWTS_E_SPACE;
+    const HostTrip trip = {in, n, n > cap ? n : cap, out, out_bytes};
+    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *bytes) {
+        return bwts_pack_members_m_device(ctx, d_in, lengths, widths, filters, methods, count, d_out, cap, bytes);
+    });
+}
+
+extern "C" int bwts_pack_members_f_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters, uint64_t count,
+                                          void *d_out, uint64_t out_cap, uint64_t *out_bytes)
+{
+    return bwts_pack_members_m_device(ctx, d_in, lengths, widths, filters, nullptr, count, d_out, out_cap, out_bytes);
 }
 
 extern "C" int bwts_pack_members_f(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters, uint64_t count,
                                    uint8_t *out, uint64_t out_cap, uint64_t *out_bytes)
 {
-    if (!ctx || !in || !out || !out_bytes) return BWTS_E_ARG;
-    u64 n = 0;
-    BWTS_TRY(members_args_check_f(lengths, widths, filters, count, &n));
-    const u64 bound = members_bound_bytes(lengths, count);
-    const u64 cap = out_cap < bound ? out_cap : bound;
-    if (cap < members_least_bytes(count)) return BWTS_E_SPACE;
-    const HostTrip trip = {in, n, n > cap ? n : cap, out, out_bytes};
-    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *bytes) {
-        return bwts_pack_members_f_device(ctx, d_in, lengths, widths, filters, count, d_out, cap, bytes);
-    });
+    return bwts_pack_members_m(ctx, in, lengths, widths, filters, nullptr, count, out, out_cap, out_bytes);
 }
 
 extern "C" int bwts_pack_members_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, uint64_t count, void *d_out,
@@ -932,8 +950,8 @@ extern "C" int bwts_pack_members(bwts_ctx *ctx, const uint8_t *in, const uint64_
     return bwts_pack_members_f(ctx, in, lengths, widths, nullptr, count, out, out_cap, out_bytes);
 }
 
-extern "C" int bwts_frame_members_f(const uint8_t *frame, uint64_t in_bytes, uint64_t *lengths_out, uint32_t *widths_out, uint32_t *filters_out, uint64_t cap,
-                                    uint64_t *count)
+extern "C" int bwts_frame_members_m(const uint8_t *frame, uint64_t in_bytes, uint64_t *lengths_out, uint32_t *widths_out, uint32_t *filters_out,
+                                    uint32_t *methods_out, uint64_t cap, uint64_t *count)
 {
     if (!frame || !count || in_bytes == 0) return BWTS_E_ARG;
     Frame F;
@@ -942,14 +960,21 @@ extern "C" int bwts_frame_members_f(const uint8_t *frame, uint64_t in_bytes, uin
     if (!F.members) return BWTS_E_FORMAT;       // (a "BWTZ" frame, whatever its own header check says, has no members)
     BWTS_TRY(rc);
     BWTS_TRY(frame_dir_check(frame + MEMBERS_HEADER_BYTES, F, in_bytes, true, &frame_bytes));
-    if ((lengths_out || widths_out || filters_out) && cap < F.count) return BWTS_E_SPACE;
+    if ((lengths_out || widths_out || filters_out || methods_out) && cap < F.count) return BWTS_E_SPACE;
     for (u64 k = 0; k < F.count; k++) {
         if (lengths_out) lengths_out[k] = F.len(k);
         if (widths_out) widths_out[k] = F.width[(size_t)k];
         if (filters_out) filters_out[k] = F.filter[(size_t)k];
+        if (methods_out) methods_out[k] = F.direct(k) ? MEMBERS_METHOD_ORDER0 : MEMBERS_METHOD_CHAIN;
     }
     *count = F.count;
     return BWTS_OK;
+}
+
+extern "C" int bwts_frame_members_f(const uint8_t *frame, uint64_t in_bytes, uint64_t *lengths_out, uint32_t *widths_out, uint32_t *filters_out, uint64_t cap,
+                                    uint64_t *count)
+{
+    return bwts_frame_members_m(frame, in_bytes, lengths_out, widths_out, filters_out, nullptr, cap, count);
 }
 
 extern "C" int bwts_frame_members(const uint8_t *frame, uint64_t in_bytes, uint64_t *lengths_out, uint32_t *widths_out, uint64_t cap, uint64_t *count)

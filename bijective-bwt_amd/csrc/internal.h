@@ -365,9 +365,10 @@ struct PackPiece;
 // indices: not null for whole members of a member frame as the ranges (ranges is then not read; count indices)
 int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool packed, const PackRange *ranges, u64 count, u8 *d_out, u64 out_cap, u64 *out_bytes,
                               const u64 *indices = nullptr);
-// the member frame (include/bwts_members.h); lengths, widths and filters (null: none) have passed members_args_check_f, n is the lengths' sum
-int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, const u32 *filters, u64 count, u64 n, u8 *d_out, u64 out_cap,
-                             u64 *out_bytes);
+// the member frame (include/bwts_members.h); lengths, widths, filters (null: none) and methods (null: the whole chain) have passed
+// members_args_check_m, n is the lengths' sum
+int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, const u32 *filters, const u32 *methods, u64 count, u64 n,
+                             u8 *d_out, u64 out_cap, u64 *out_bytes);
 // pieces of one device buffer to another, at any alignment (pieces.hip); every piece inside both buffers, by the caller's check
 int copy_pieces_impl(bwts_ctx *ctx, const u8 *d_src, u64 src_bytes, const PackPiece *pieces, u64 count, u8 *d_dst);
 

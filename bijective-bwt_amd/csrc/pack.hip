@@ -15,6 +15,11 @@
 // between two stages, so that no table copy of the stage before is still to come when the next stage writes its own (seg_layout.h:
 // the regions, and who overlaps whom).  The context's table changes hands inside a chain: the coder's segments are the blocks'
 // zero-run coded bytes where that stage runs, every other stage's the blocks themselves.
+// A member of a version-3 member frame may skip the middle of either chain (its method, include/bwts_members.h): such direct members
+// go from the split straight to the coder, every plane of a long one as a coder segment of its own (members_plan.h: the cut rule).
+// The chain stages then run over the chain members alone, gathered to the front of a stage block with pieces.hip's copy kernel, and
+// the coder runs once over all coder segments in member order; where either set is empty nothing is gathered and the calls are those
+// of the other kind alone.
 // Header and directory travel through pinned memory too: the small block, and for several blocks the directory region behind the
 // segment table (16-byte entries, "BWTZ" version 1; the 32-byte entries do not fit that region and travel through a host block of the
 // call's own).  Either is staging that the next stage writes over: a Frame holds everything the directory says.
@@ -27,6 +32,7 @@
 #include <string.h>
 #include <utility>
 
+static_assert(MEMBERS_METHOD_CHAIN == BWTS_METHOD_CHAIN && MEMBERS_METHOD_ORDER0 == BWTS_METHOD_ORDER0, "members_plan.h names the header's methods");
 static_assert(PACK_OK == BWTS_OK && PACK_RANGE == BWTS_E_RANGE && PACK_FORMAT == BWTS_E_FORMAT && PACK_ARG == BWTS_E_ARG && PACK_SPACE == BWTS_E_SPACE,
               "pack_plan.h answers in the library's codes");
 
@@ -63,12 +69,13 @@ static std::vector<u64> uniform_lengths(u64 n, u64 B)
 }
 
 // room on the host for a directory of nblk entries: the small block behind the header, or for several blocks the directory region
-// behind the segment table (pinned; 16-byte entries, and the table is nblk segments when this is called) or `own` (32-byte entries)
-static int pack_dir_staging(bwts_ctx *ctx, u64 entry, u64 nblk, std::vector<u8> &own, u8 **dir)
+// behind the segment table (pinned; 16-byte entries, and the table is nblk segments when this is called) or `own` (32-byte entries,
+// and behind them the ext words of a member frame's extension table, with which one block's directory goes there too)
+static int pack_dir_staging(bwts_ctx *ctx, u64 entry, u64 nblk, u64 ext, std::vector<u8> &own, u8 **dir)
 {
-    if (nblk == 1) { *dir = (u8 *)(ctx->h_small + SM_PACK_HEAD) + PACK_HEADER_BYTES; return BWTS_OK; }
+    if (nblk == 1 && ext == 0) { *dir = (u8 *)(ctx->h_small + SM_PACK_HEAD) + PACK_HEADER_BYTES; return BWTS_OK; }
     if (entry != PACK_ENTRY_BYTES) {
-        own.resize((size_t)(entry * nblk));
+        own.resize((size_t)(entry * nblk + 8u * ext));
         *dir = own.data();
         return BWTS_OK;
     }
@@ -105,6 +112,71 @@ static bool any_filter(const std::vector<u32> &filters)
     return false;
 }
 
+// ---- the two sets of a call whose blocks name methods ----
+// The chain set (method 0) and the direct set (method 1) of the blocks of a call, and the coder's segments over both, in block order:
+// a chain block's one segment is its (zero-run) coded bytes, a direct block's segments are its split bytes by the cut rule.
+struct MethodSets {
+    size_t chain = 0, direct = 0;               // blocks of either set
+    u64 chain_bytes = 0, direct_bytes = 0;      // their bytes
+    std::vector<u64> chain_lengths;             // the chain set's segment table
+    std::vector<u32> segs;                      // per block: its coder segments
+    bool mixed() const { return chain && direct; }
+};
+static bool is_direct(const std::vector<u32> &methods, size_t k) { return !methods.empty() && methods[k] == MEMBERS_METHOD_ORDER0; }
+static MethodSets method_sets(const std::vector<u64> &lengths, const std::vector<u32> &widths, const std::vector<u32> &methods)
+{
+    MethodSets M;
+    M.segs.assign(lengths.size(), 1u);
+    for (size_t k = 0; k < lengths.size(); k++) {
+        if (is_direct(methods, k)) {
+            M.direct++; M.direct_bytes += lengths[k];
+            M.segs[k] = members_direct_segments(lengths[k], widths[k]);
+        } else {
+            M.chain++; M.chain_bytes += lengths[k];
+            M.chain_lengths.push_back(lengths[k]);
+        }
+    }
+    return M;
+}
+// The coder's segment lengths: `coded` per chain block, the cut rule's per direct block.
+static std::vector<u64> coder_lengths(const MethodSets &M, const std::vector<u64> &lengths, const std::vector<u32> &widths, const std::vector<u32> &methods,
+                                      const std::vector<u64> &coded)
+{
+    std::vector<u64> cl;
+    for (size_t k = 0; k < lengths.size(); k++) {
+        if (!is_direct(methods, k)) { cl.push_back(coded[k]); continue; }
+        for (u32 i = 0; i < M.segs[k]; i++) cl.push_back(members_direct_segment_bytes(lengths[k], widths[k], i));
+    }
+    return cl;
+}
+// The pieces that regroup a buffer of blocks in order (sizes `in_order`: chain blocks at their coded or plain size, direct blocks at
+// their length) into the chain blocks back to back from 0 and the direct blocks back to back from `direct_at`; neighbouring blocks of
+// one set are one piece.  back: the other way round.  At most one piece per block: 2^20, what pieces.hip takes.
+static std::vector<PackPiece> regroup_pieces(const std::vector<u32> &methods, const std::vector<u64> &in_order, u64 direct_at, bool back)
+{
+    std::vector<PackPiece> ps;
+    u64 at = 0, chain_at = 0, dir_at = direct_at;
+    for (size_t k = 0; k < in_order.size(); k++) {
+        const bool d = is_direct(methods, k);
+        u64 &set_at = d ? dir_at : chain_at;
+        if (k > 0 && is_direct(methods, k - 1) == d) ps.back().bytes += in_order[k];
+        else ps.push_back(back ? PackPiece{set_at, at, in_order[k]} : PackPiece{at, set_at, in_order[k]});
+        at += in_order[k];
+        set_at += in_order[k];
+    }
+    return ps;
+}
+// a table of these lengths for the stages that follow (one length: none, the single-input stages)
+static int table_set(bwts_ctx *ctx, const std::vector<u64> &lengths, SegMode *segs)
+{
+    *segs = SEG_SINGLE;
+    if (lengths.size() == 1) return BWTS_OK;
+    u64 total = 0;
+    BWTS_TRY(seg_table_set(ctx, lengths.data(), lengths.size(), &total));
+    *segs = seg_mode(ctx);
+    return BWTS_OK;
+}
+
 // ---- encoding ----
 // What a pack is asked for: the blocks, each with its width (1: not split) and filter, whether the zero-run stage runs, and the room
 // the frame needs at least (`fixed` of it header and directory).
@@ -113,11 +185,58 @@ struct EncodeSet {
     std::vector<u32> widths, filters;
     bool zrl;
     u64 n, fixed, least;
+    std::vector<u32> methods;           // empty: every block through the whole chain
 };
 struct Encoded {
-    std::vector<u64> sizes, coded;      // per block: stream bytes; zero-run coded bytes (where that stage ran)
+    std::vector<u64> sizes, coded;      // per block: stream bytes; zero-run coded bytes (where that stage ran; a direct block: its length)
     std::vector<u32> crcs;
+    std::vector<u64> seg_sizes;         // per coder segment, where a block is direct: stream bytes
 };
+
+// The middle of the encode chain where blocks are direct: the chain set's split bytes through transform, move-to-front and zero-run
+// coding, the direct set's kept, and the coder's input put together in block order.  On entry `from` holds all blocks' split bytes;
+// when this returns it holds the coder's input, E.coded says how much of it every block has, and the context's table is the
+// coder's segments (*segs).  The two stage blocks hold n bytes each, and `from` may be the call's input, which is only read.
+//   all direct: nothing moves.
+//   mixed: a gather puts the chain set at [0, chain bytes) and the direct set at [chain bytes, n) of `to`; the three stages go to and
+//     fro in [0, chain bytes) of both blocks and leave the coded bytes in the block that does not hold the direct set, so a plain copy
+//     takes them over (they are the small side) before the second gather writes that block in block order.
+static int encode_middle(bwts_ctx *ctx, const EncodeSet &S, const MethodSets &M, const u8 *&from, u8 *&to, u8 *&other, Encoded &E, u64 *m, SegMode *segs)
+{
+    const size_t count = S.lengths.size();
+    for (size_t k = 0; k < count; k++) E.coded[k] = S.lengths[k];
+    if (M.mixed()) {
+        const u64 nc = M.chain_bytes;
+        auto done = [&] { from = to; std::swap(to, other); return hipStreamSynchronize(ctx->stream); };
+        const std::vector<PackPiece> apart = regroup_pieces(S.methods, S.lengths, nc, false);
+        BWTS_TRY(copy_pieces_impl(ctx, from, S.n, apart.data(), apart.size(), to));
+        HIPC(done());
+        u8 *const sets = (u8 *)from;        // (a stage block: chain set, then direct set)
+        SegMode cs;
+        BWTS_TRY(table_set(ctx, M.chain_lengths, &cs));
+        BWTS_TRY(cs.table() ? forward_segments_impl(ctx, from, nc, to) : forward_device_impl(ctx, from, nc, to));
+        HIPC(done());
+        BWTS_TRY(mtf_impl(ctx, from, nc, to, false, cs));
+        HIPC(done());
+        std::vector<u64> chain_coded(M.chain);
+        BWTS_TRY(zrl_encode_impl(ctx, from, nc, to, nc, cs, chain_coded.data()));
+        HIPC(done());
+        u64 mc = 0;
+        for (size_t k = 0, c = 0; k < count; k++)
+            if (!is_direct(S.methods, k)) { E.coded[k] = chain_coded[c++]; mc += E.coded[k]; }
+        HIPC(hipMemcpyAsync(sets, from, mc, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPC(hipStreamSynchronize(ctx->stream));
+        u8 *const order = (u8 *)from;       // (the other stage block: its coded bytes are taken over)
+        const std::vector<PackPiece> back = regroup_pieces(S.methods, E.coded, nc, true);
+        BWTS_TRY(copy_pieces_impl(ctx, sets, S.n, back.data(), back.size(), order));
+        HIPC(hipStreamSynchronize(ctx->stream));
+        from = order;
+    }
+    const std::vector<u64> cl = coder_lengths(M, S.lengths, S.widths, S.methods, E.coded);
+    *m = 0;
+    for (u64 l : cl) *m += l;
+    return table_set(ctx, cl, segs);
+}
 
 // From d_in to the streams behind d_out + S.fixed.  A stage reads `from` and writes `to`; the two stage blocks swap behind it.
 static int encode_chain(bwts_ctx *ctx, const EncodeSet &S, const u8 *d_in, u8 *d_out, u64 out_cap, Encoded &E)
@@ -144,6 +263,22 @@ static int encode_chain(bwts_ctx *ctx, const EncodeSet &S, const u8 *d_in, u8 *d
         BWTS_TRY(frame_planes(ctx, from, n, S.widths, to, false, segs));
         HIPC(done());
     }
+    const MethodSets M = method_sets(S.lengths, S.widths, S.methods);
+    if (M.direct) {
+        // the coder's segments are no longer the blocks: one table entry per plane of a long direct block
+        u64 m = 0;
+        SegMode cs;
+        BWTS_TRY(encode_middle(ctx, S, M, from, to, other, E, &m, &cs));
+        E.seg_sizes.resize(cs.table() ? (size_t)cs.count : 1);
+        BWTS_TRY(ec_encode_impl(ctx, from, m, d_out + S.fixed, out_cap - S.fixed, cs, E.seg_sizes.data()));
+        HIPC(hipStreamSynchronize(ctx->stream));
+        for (size_t k = 0, at = 0; k < count; at += M.segs[k], k++) {
+            E.sizes[k] = 0;
+            for (u32 i = 0; i < M.segs[k]; i++) E.sizes[k] += E.seg_sizes[at + i];
+        }
+        ctx->tm.n = n;
+        return BWTS_OK;
+    }
     BWTS_TRY(seg ? forward_segments_impl(ctx, from, n, to) : forward_device_impl(ctx, from, n, to));
     HIPC(done());
     BWTS_TRY(mtf_impl(ctx, from, n, to, false, segs));
@@ -163,10 +298,10 @@ static int encode_chain(bwts_ctx *ctx, const EncodeSet &S, const u8 *d_in, u8 *d
 
 // where a pack writes header and directory before they go to the front of the frame
 struct FrameStaging { u8 *head, *dir; std::vector<u8> own; };
-static int encode_staging(bwts_ctx *ctx, u64 entry, u64 count, FrameStaging &T)
+static int encode_staging(bwts_ctx *ctx, u64 entry, u64 count, u64 ext, FrameStaging &T)
 {
     T.head = (u8 *)(ctx->h_small + SM_PACK_HEAD);
-    return pack_dir_staging(ctx, entry, count, T.own, &T.dir);
+    return pack_dir_staging(ctx, entry, count, ext, T.own, &T.dir);
 }
 static int encode_finish(bwts_ctx *ctx, const EncodeSet &S, const Encoded &E, const FrameStaging &T, u8 *d_out, u64 out_cap, u64 *out_bytes)
 {
@@ -184,13 +319,13 @@ static int encode_finish(bwts_ctx *ctx, const EncodeSet &S, const Encoded &E, co
 int pack_device_impl(bwts_ctx *ctx, u32 version, u32 width, const u8 *d_in, u64 n, u64 B, u8 *d_out, u64 out_cap, u64 *out_bytes)
 {
     const u64 nblk = pack_blocks(n, B), entry = pack_entry_bytes(version);
-    EncodeSet S{uniform_lengths(n, B), {}, {}, version != PACK_VERSION, n, pack_fixed_bytes_v(version, nblk), pack_least_bytes_of(version, n, B)};
+    EncodeSet S{uniform_lengths(n, B), {}, {}, version != PACK_VERSION, n, pack_fixed_bytes_v(version, nblk), pack_least_bytes_of(version, n, B), {}};
     S.widths.assign((size_t)nblk, version == PACK_VERSION_3 ? width : 1u);
     S.filters.assign((size_t)nblk, DELTA_FILTER_NONE);
     Encoded E;
     BWTS_TRY(encode_chain(ctx, S, d_in, d_out, out_cap, E));
     FrameStaging T;
-    BWTS_TRY(encode_staging(ctx, entry, nblk, T));
+    BWTS_TRY(encode_staging(ctx, entry, nblk, 0, T));
     for (size_t k = 0; k < (size_t)nblk; k++) {
         if (version == PACK_VERSION_3) pack_entry_write_v3(T.dir + entry * k, E.sizes[k], E.crcs[k], E.coded[k], width);
         else if (S.zrl) pack_entry_write_v2(T.dir + entry * k, E.sizes[k], E.crcs[k], E.coded[k]);
@@ -201,22 +336,34 @@ int pack_device_impl(bwts_ctx *ctx, u32 version, u32 width, const u8 *d_in, u64 
 }
 
 // "BWTM": members of any lengths, each filtered if asked (filters: null for none) and split at its own width (widths: null for 1, not
-// at all), with the entries and the header of include/bwts_members.h.  A pack in which no member names a filter writes version 1.
-int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, const u32 *filters, u64 count, u64 n, u8 *d_out, u64 out_cap,
-                             u64 *out_bytes)
+// at all), with the entries and the header of include/bwts_members.h.  methods: null for the whole chain everywhere; a member of
+// method 1 is coded directly.  A pack in which no member names a method writes version 2 where one names a filter, else version 1;
+// one that does writes version 3, with the stream sizes of every member that has several in the table behind the entries.
+int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, const u32 *filters, const u32 *methods, u64 count, u64 n,
+                             u8 *d_out, u64 out_cap, u64 *out_bytes)
 {
-    EncodeSet S{std::vector<u64>(lengths, lengths + count), {}, {}, true, n, members_fixed_bytes(count), members_least_bytes(count)};
+    const bool v3 = members_any_method(methods, count);
+    const u64 ext = v3 ? members_ext_words(lengths, widths, methods, count) : 0;
+    EncodeSet S{std::vector<u64>(lengths, lengths + count), {}, {}, true, n, members_fixed_bytes_x(count, ext),
+                v3 ? members_least_bytes_m(lengths, widths, methods, count) : members_least_bytes(count), {}};
     S.widths.assign((size_t)count, 1u);
     if (widths) S.widths.assign(widths, widths + count);
     S.filters.assign((size_t)count, DELTA_FILTER_NONE);
     if (filters) S.filters.assign(filters, filters + count);
+    if (v3) S.methods.assign(methods, methods + count);
     Encoded E;
     BWTS_TRY(encode_chain(ctx, S, d_in, d_out, out_cap, E));
     FrameStaging T;
-    BWTS_TRY(encode_staging(ctx, MEMBERS_ENTRY_BYTES, count, T));
-    for (size_t k = 0; k < (size_t)count; k++)
-        members_entry_write(T.dir + (u64)MEMBERS_ENTRY_BYTES * k, E.sizes[k], E.crcs[k], delta_word(S.widths[k], S.filters[k]), E.coded[k], lengths[k]);
-    members_header_write_v(T.head, any_filter(S.filters) ? MEMBERS_VERSION_2 : MEMBERS_VERSION, n, count, T.dir);
+    BWTS_TRY(encode_staging(ctx, MEMBERS_ENTRY_BYTES, count, ext, T));
+    u8 *table = T.dir + (u64)MEMBERS_ENTRY_BYTES * count;
+    if (ext) memset(table, 0, (size_t)(8u * ext));
+    for (size_t k = 0, seg = 0; k < (size_t)count; k++) {
+        const u32 method = v3 ? methods[k] : MEMBERS_METHOD_CHAIN, words = members_table_words(lengths[k], S.widths[k], method);
+        members_entry_write(T.dir + (u64)MEMBERS_ENTRY_BYTES * k, E.sizes[k], E.crcs[k], members_word(S.widths[k], S.filters[k], method), E.coded[k], lengths[k]);
+        for (u32 i = 0; i < words; i++, table += 8) pack_put64(table, E.seg_sizes[seg + i]);
+        seg += words ? words : 1u;
+    }
+    members_header_write_x(T.head, v3 ? MEMBERS_VERSION_3 : any_filter(S.filters) ? MEMBERS_VERSION_2 : MEMBERS_VERSION, n, count, ext, T.dir);
     return encode_finish(ctx, S, E, T, d_out, out_cap, out_bytes);
 }
 
@@ -236,9 +383,10 @@ static int unpack_frame_head(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, Frame 
     // come with the directory
     if (!F.members) BWTS_TRY(blocks_set(ctx, uniform_lengths(F.n, F.B), F.n));
     std::vector<u8> own;
-    BWTS_TRY(pack_dir_staging(ctx, F.entry, F.count, own, &dir));
-    if (F.count > 1) {
-        HIPC(hipMemcpyAsync(dir, d_in + PACK_HEADER_BYTES, F.entry * F.count, hipMemcpyDeviceToHost, ctx->stream));
+    BWTS_TRY(pack_dir_staging(ctx, F.entry, F.count, F.ext, own, &dir));
+    if (F.count > 1 || F.ext) {
+        // (the extension table of a version-3 member frame comes with the entries: the header check has held both against in_bytes)
+        HIPC(hipMemcpyAsync(dir, d_in + PACK_HEADER_BYTES, F.fixed - PACK_HEADER_BYTES, hipMemcpyDeviceToHost, ctx->stream));
         HIPC(hipStreamSynchronize(ctx->stream));
     }
     u64 frame = 0;
@@ -254,6 +402,9 @@ struct DecodeSet {
     u64 total = 0;                              // the blocks' bytes
     std::vector<u64> lengths, sizes, coded;     // per block: bytes, stream bytes, coded bytes
     std::vector<u32> want, widths, filters;     // ... checksum, width, filter
+    std::vector<u32> methods;                   // ... method; empty where no block is direct
+    std::vector<u64> seg_sizes;                 // per coder segment, where a block is direct: stream bytes
+    MethodSets M;
     bool zrl = false, split = false, delta = false;
 };
 static DecodeSet decode_set(const Frame &F, const std::vector<u64> *blocks)
@@ -268,13 +419,84 @@ static DecodeSet decode_set(const Frame &F, const std::vector<u64> *blocks)
         S.total += F.len(k);
     }
     S.zrl = F.zrl; S.split = any_split(S.widths); S.delta = any_filter(S.filters);
+    bool direct = false;
+    for (size_t i = 0; i < nb; i++) direct = direct || F.direct(blocks ? (*blocks)[i] : i);
+    if (direct) {
+        S.methods.resize(nb);
+        for (size_t i = 0; i < nb; i++) {
+            const size_t k = blocks ? (size_t)(*blocks)[i] : i;
+            S.methods[i] = F.method[k];
+            if (F.table_at[k + 1] == F.table_at[k]) S.seg_sizes.push_back(F.stream[k]);
+            else S.seg_sizes.insert(S.seg_sizes.end(), F.table.begin() + (ptrdiff_t)F.table_at[k], F.table.begin() + (ptrdiff_t)F.table_at[k + 1]);
+        }
+    }
+    S.M = method_sets(S.lengths, S.widths, S.methods);
     return S;
 }
-// how many stages write a buffer: coder, inverse move-to-front and inverse transform always
-static int decode_stages(const DecodeSet &S) { return 3 + S.zrl + S.split + S.delta; }
+// how many stages write a buffer: coder, inverse move-to-front and inverse transform always; where every block is direct the coder
+// alone, and in a mixed set the two gathers and the copy between them besides (decode_middle)
+static int decode_stages(const DecodeSet &S)
+{
+    if (S.M.direct) return (S.M.chain ? 7 : 1) + S.split + S.delta;
+    return 3 + S.zrl + S.split + S.delta;
+}
 
 // the stages of a range read, as the bits of its report (include/bwts_test.h)
-enum { RG_GATHER = 1, RG_DECODE = 2, RG_ZRL = 4, RG_MTF = 8, RG_INVERSE = 16, RG_JOIN = 32, RG_CRC = 64, RG_CUT = 128, RG_DELTA = 256 };
+enum { RG_GATHER = 1, RG_DECODE = 2, RG_ZRL = 4, RG_MTF = 8, RG_INVERSE = 16, RG_JOIN = 32, RG_CRC = 64, RG_CUT = 128, RG_DELTA = 256, RG_REGROUP = 512 };
+
+static int decode_tail(bwts_ctx *ctx, const DecodeSet &S, const u8 *&from, u8 *to, u8 *other, u64 *stages);
+
+// The front of the decode chain where blocks are direct: one coder decode over all coder segments, the cut rule's for a direct block;
+// then, where chain blocks are among them, their coded bytes through zero-run decoding, inverse move-to-front and the inverse
+// transform under a table of the chain set alone.  When this returns, `from` holds every block's split bytes in block order, and
+// to / other are the buffers the next two stages write.  Both buffers hold S.total bytes.
+//   all direct: the coder's output is that already.
+//   mixed: a gather puts the chain set's coded bytes at the front and the direct set at [chain bytes, total) of the second buffer; a
+//     plain copy takes the coded bytes (the small side) back to the first, so that the three stages, which go to and fro in [0, chain
+//     bytes) of both, end in the buffer that holds the direct set; a second gather restores block order.  Seven writes of a buffer.
+static int decode_middle(bwts_ctx *ctx, const DecodeSet &S, const u8 *&from, u8 *&to, u8 *&other, u64 *stages)
+{
+    const MethodSets &M = S.M;
+    auto next = [&](u64 bit) { if (stages) *stages |= bit; from = to; std::swap(to, other); };
+    auto done = [&](u64 bit) { next(bit); return hipStreamSynchronize(ctx->stream); };
+    const std::vector<u64> cl = coder_lengths(M, S.lengths, S.widths, S.methods, S.coded);
+    u64 m = 0;
+    for (u64 l : cl) m += l;
+    SegMode cs;
+    BWTS_TRY(table_set(ctx, cl, &cs));
+    if (cs.table()) {
+        BWTS_TRY(ec_decode_impl(ctx, from, m, to, m, nullptr, cs, S.seg_sizes.data()));
+    } else {
+        u64 named = 0;
+        const int rc = ec_decode_impl(ctx, from, S.seg_sizes[0], to, m, &named, cs, nullptr);
+        if (rc == BWTS_E_SPACE || (rc == BWTS_OK && named != m)) return BWTS_E_FORMAT;
+        BWTS_TRY(rc);
+    }
+    next(RG_DECODE);
+    if (!M.chain) return BWTS_OK;
+    const u64 nc = M.chain_bytes;
+    std::vector<u64> in_order(S.lengths), chain_coded;
+    u64 mc = 0;
+    for (size_t k = 0; k < in_order.size(); k++)
+        if (!is_direct(S.methods, k)) { in_order[k] = S.coded[k]; chain_coded.push_back(S.coded[k]); mc += S.coded[k]; }
+    const std::vector<PackPiece> apart = regroup_pieces(S.methods, in_order, nc, false);
+    BWTS_TRY(copy_pieces_impl(ctx, from, m, apart.data(), apart.size(), to));
+    HIPC(done(RG_REGROUP));
+    HIPC(hipMemcpyAsync(to, from, mc, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPC(done(0));
+    SegMode chain;
+    BWTS_TRY(table_set(ctx, M.chain_lengths, &chain));
+    BWTS_TRY(zrl_decode_impl(ctx, from, mc, to, nc, chain, chain_coded.data()));
+    HIPC(done(RG_ZRL));
+    BWTS_TRY(mtf_impl(ctx, from, nc, to, true, chain));
+    HIPC(done(RG_MTF));
+    BWTS_TRY(chain.table() ? inverse_segments_impl(ctx, from, nc, to) : inverse_device_impl(ctx, from, nc, to));
+    HIPC(done(RG_INVERSE));
+    const std::vector<PackPiece> back = regroup_pieces(S.methods, S.lengths, nc, true);
+    BWTS_TRY(copy_pieces_impl(ctx, from, S.total, back.data(), back.size(), to));
+    HIPC(done(0));
+    return BWTS_OK;
+}
 
 // From the streams at `from`, back to back, to the blocks' bytes with their checksums held against the directory: `from` is where
 // they are when this returns.  The context's table is S's blocks on entry; the first stage writes `to`, the next one `other`, and so
@@ -287,6 +509,12 @@ static int decode_chain(bwts_ctx *ctx, const DecodeSet &S, const u8 *&from, u8 *
     auto next = [&](u64 bit) { if (stages) *stages |= bit; from = to; std::swap(to, other); };
     auto done = [&](u64 bit) { next(bit); return hipStreamSynchronize(ctx->stream); };
     u64 m = n;
+    if (S.M.direct) {
+        BWTS_TRY(decode_middle(ctx, S, from, to, other, stages));
+        ctx->tm.n = n;
+        BWTS_TRY(blocks_set(ctx, S.lengths, n));
+        return decode_tail(ctx, S, from, to, other, stages);
+    }
     if (S.zrl) BWTS_TRY(pack_coded_set(ctx, S.coded, &m));
     if (seg) {
         BWTS_TRY(ec_decode_impl(ctx, from, m, to, m, nullptr, segs, S.sizes.data()));
@@ -308,6 +536,15 @@ static int decode_chain(bwts_ctx *ctx, const DecodeSet &S, const u8 *&from, u8 *
     HIPC(done(RG_MTF));
     BWTS_TRY(seg ? inverse_segments_impl(ctx, from, n, to) : inverse_device_impl(ctx, from, n, to));
     HIPC(done(RG_INVERSE));
+    return decode_tail(ctx, S, from, to, other, stages);
+}
+
+// The end of the decode chain, over all blocks of S (the context's table): join, delta decode, and the checksums against the directory.
+static int decode_tail(bwts_ctx *ctx, const DecodeSet &S, const u8 *&from, u8 *to, u8 *other, u64 *stages)
+{
+    const SegMode segs = S.lengths.size() > 1 ? seg_mode(ctx) : SEG_SINGLE;
+    const u64 n = S.total;
+    auto done = [&](u64 bit) { if (stages) *stages |= bit; from = to; std::swap(to, other); return hipStreamSynchronize(ctx->stream); };
     if (S.split) {
         BWTS_TRY(frame_planes(ctx, from, n, S.widths, to, true, segs));
         HIPC(done(RG_JOIN));

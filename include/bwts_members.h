@@ -10,15 +10,17 @@
  * len_k, 1 <= n <= 2^32, 1 <= count <= 2^20 (the largest directory a "BWTZ" frame can have: 2^32 / 4096).
  *   1. Header, 32 bytes:
  *        offset  0  u32 magic 0x4D545742 ("BWTM")
- *        offset  4  u32 version = 1, or 2 where a member names a filter (below)
+ *        offset  4  u32 version = 1, or 2 where a member names a filter, or 3 where one names a method (below)
  *        offset  8  u64 n
- *        offset 16  u64 count
- *        offset 24  u32 CRC-32 of the directory bytes
+ *        offset 16  u64 count; version 3: u32 count and, at offset 20, u32 ext, the 8-byte words of the extension table (below);
+ *                   versions 1 and 2 have the upper half zero, and count <= 2^20 always fits
+ *        offset 24  u32 CRC-32 of the directory bytes (version 3: the entries and the extension table)
  *        offset 28  u32 CRC-32 of header bytes 0 .. 27
  *   2. Directory, count x 32 bytes:
  *        offset  0  u64 stream_bytes
  *        offset  8  u32 CRC-32 of the member's original bytes (before the split)
- *        offset 12  u32 w; version 2: bits 0-7 w, bits 8-15 the member's filter f (bwts_delta.h: 0 none, 1 delta), bits 16-31 zero
+ *        offset 12  u32 w; version 2: bits 0-7 w, bits 8-15 the member's filter f (bwts_delta.h: 0 none, 1 delta), bits 16-31 zero;
+ *                   version 3: bits 16-23 the member's method (0 or 1, below), bits 24-31 zero
  *        offset 16  u64 coded_bytes (the zero-run stage's out_bytes for the member: 1 <= coded_bytes <= len)
  *        offset 24  u64 len (the slot that versions 2 and 3 of the "BWTZ" frame keep zero)
  *   3. Streams: for every member in order the version-1 stream of bwts_ec.h of ZRL(MTF(BWTS(SPLIT_w(member)))); w = 1 means no
@@ -28,7 +30,28 @@
  *      original bytes.
  * The frame is canonical: only a version-2 frame may name a filter, and a version-2 frame in which no entry names one does not
  * exist.  A pack without a filter writes the version-1 frame, byte for byte.
- * Bound: 32 + 32 count + the sum of bwts_ec_bound(len_k).  Header and directory are written last: a pack that fails with
+ *
+ * Version 3: a method per member.  BWTS_METHOD_CHAIN = 0 is the chain above.  BWTS_METHOD_ORDER0 = 1 codes the member's planes
+ * directly: (DELTA_w if asked,) SPLIT_w, coder -- no transform, no move-to-front, no zero-run stage.  That is the right method for
+ * weights, noise and hashes, whose bytes are close to independent (the transform and move-to-front make the coder's input less
+ * skewed than the plain planes, at forty times the cost), and the wrong one for text, integer walks and smooth fields: it is asked
+ * for per member, like the width and the filter, and is never a default.
+ *   The cut of a method-1 member of len bytes and width w into coder segments, with q = floor(len / w):
+ *     w > 1 and q >= 8192: w segments, planes 0 .. w-2 of q bytes each, and plane w-1 followed by the tail, q + (len - q w) bytes
+ *       (the planes as bwts_planes.h lays them out);
+ *     otherwise (w = 1 and len < w among it): one segment of len bytes.
+ *   The member's stream is its segments' version-1 streams of bwts_ec.h, one behind the other: every plane of a long member has
+ *   tables of its own, which is where the gain lies (a coder block across a plane boundary mixes an exponent plane with a mantissa
+ *   plane).  A stream of its own costs 800 bytes before its first symbol, which planes of 8192 bytes repay.
+ *   Entries: coded_bytes = len; stream_bytes = the sum of the member's segment streams.
+ *   Extension table, behind the count entries: for every method-1 member that has w > 1 segments, in member order, w x u64, the
+ *   segments' stream sizes; the whole table zero-padded to a multiple of 16 bytes; ext counts its 8-byte words, the pad word among
+ *   them.  Fixed bytes: 32 + 32 count + 8 ext; the streams begin behind them.
+ *   Canonical again: the version is 3 where any member names method 1, else 2 where any names a filter, else 1; a pack that names
+ *   no method writes the frame it always wrote, byte for byte, and a version-3 frame in which no entry names a method does not exist.
+ *   "BWTZ" frames have no method.
+ * Bound: 32 + 32 count + the sum of bwts_ec_bound(len_k); with methods, bwts_pack_members_bound_m: 32 + 32 count + 8 ext + the sum of
+ * bwts_ec_bound over all coder segments (a chain member's one of len_k bytes, a direct member's by the cut).  Header and directory are written last: a pack that fails with
  * BWTS_E_SPACE has written nothing at all.
  * Members of width 1 and one length B >= 4096 make the streams of the version-2 "BWTZ" frame of the same bytes at block_bytes = B,
  * byte for byte; only the header and the entries' width and length words differ.
@@ -39,14 +62,19 @@
  *    3. a wrong header CRC;
  *    4. n = 0 (n > 2^32: BWTS_E_RANGE);
  *    5. count = 0 or count > n (count > 2^20: BWTS_E_RANGE);
- *    6. a directory longer than the frame;
+ *    6. a directory (version 3: with its extension table) longer than the frame;
  *    7. a wrong directory CRC;
  *    8. per entry, in order: w not in {1, 2, 4, 8} (version 1: the whole word is w; version 2: a filter above 1 or a nonzero bit
  *       16-31 is refused here too); len = 0, or a running sum of the lengths above n; coded_bytes outside [1, len]; stream_bytes not a
  *       multiple of 16, or outside what the coder can make of coded_bytes;
- *    9. version 2 and no entry names a filter;
+ *       version 3, in the same place: a method above 1 or a nonzero bit 24-31 with the bad width; behind coded_bytes, for a member of
+ *       method 1, coded_bytes != len; for a member with several segments, instead of the bounds on stream_bytes: its table words
+ *       reaching beyond ext, a table word that is not a multiple of 16 or lies outside what the coder can make of its segment's
+ *       length, or a sum of the words that is not stream_bytes (a member of one segment is held to the bounds on stream_bytes itself);
+ *    9. version 2 and no entry names a filter; version 3 and no entry names a method, an ext that is not exactly what the entries
+ *       demand, or a pad word that is not zero;
  *   10. a sum of the lengths that is not n;
- *   11. 32 + 32 count + the sum of stream_bytes != in_bytes;
+ *   11. 32 + 32 count + 8 ext + the sum of stream_bytes != in_bytes;
  *   12. n > out_cap: BWTS_E_SPACE.
  * After the checks unpack runs version 3's order: decode against coded_bytes (a stream whose header names another length is
  * BWTS_E_FORMAT), zero-run decode, inverse move-to-front, inverse transform, the join of every member at its own width, and the
@@ -55,6 +83,12 @@
  * ones (one launch per sweep), then the CRCs; a rewritten filter bit that leaves the frame canonical decodes in bounds and fails
  * with BWTS_E_CHECKSUM.  Unpack still holds one block of n bytes beside d_out: with a stage more, the first stage writes the
  * other buffer, and the last one lands in d_out.
+ * Version 3: one coder decode over all coder segments; the chain members' coded bytes are gathered and go through zero-run decode,
+ * inverse move-to-front and the inverse transform under a segment table of their own; the split bytes are gathered back into member
+ * order; join, delta decode and the CRCs run over all members.  Where every member is direct, no stage between coder and join is
+ * entered, nothing is gathered and the transform's arena is not taken; where none is, the calls are those of version 2.  A
+ * rewritten method bit that leaves the frame canonical decodes in bounds and fails with BWTS_E_FORMAT (the streams do not fit the
+ * other cut) or BWTS_E_CHECKSUM; so do two table words exchanged.
  *
  * bwts_unpack, bwts_unpack_device, bwts_unpack_size, bwts_unpack_ranges and bwts_unpack_ranges_device (bwts_pack.h) take member
  * frames as they take "BWTZ" frames: unpack gives the concatenation of the members, and a range's offset is counted in that
@@ -69,6 +103,11 @@
  * bytes are the same by the segment forms' contract.
  * bwts_pack_members_f* are the same calls with a filter per member (bwts_delta.h; filters == NULL: none; a filter other than 0 or 1
  * is BWTS_E_ARG with the bad widths); the bound is bwts_pack_members_bound, the filter never changes a length.
+ * bwts_pack_members_m* are the same calls with a method per member besides (methods == NULL: all 0; a method other than 0 or 1 is
+ * BWTS_E_ARG with the bad widths and filters); the bound is bwts_pack_members_bound_m, which without a method is
+ * bwts_pack_members_bound.  Every reader above, bwts_unpack_members* and bwts_frame_members* take version 3 as they take the others;
+ * a touched direct member is decoded whole, with all its streams, its join and its filter.  bwts_frame_members_m gives the methods too
+ * (all 0 below version 3).
  * bwts_frame_members is host arithmetic: it judges header and directory of a frame that is all of in_bytes (checks 1 to 11) and
  * gives the members' lengths and widths (of a version-2 entry the low byte); with both arrays NULL the count alone, else BWTS_E_SPACE
  * where cap < count.  bwts_frame_members_f gives the filters too (all 0 for a version-1 frame).  A "BWTZ" frame is BWTS_E_FORMAT here.
@@ -79,6 +118,8 @@
  * Cost: that of a version-3 pack or unpack of n bytes in `count` blocks; the split and the join are one launch each whatever the
  * mix of widths, and are left out where every width is 1; the delta stage is one launch per sweep whatever the mix of filters, and is
  * left out where there is none.  bwts_timings::device_bytes after a version-2 call is what the version-1 frame of the same lengths leaves.
+ * A direct member costs a checksum, a split and the coder; in a mixed frame two gathers (a copy each) besides, and the transform's
+ * arena is sized for the chain members alone.
  */
 #ifndef BWTS_MEMBERS_H
 #define BWTS_MEMBERS_H
@@ -94,7 +135,17 @@ extern "C" {
 int bwts_planes_split_segments_w_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, uint64_t count, void *d_out);
 int bwts_planes_join_segments_w_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, uint64_t count, void *d_out);
 
+#define BWTS_METHOD_CHAIN  0
+#define BWTS_METHOD_ORDER0 1
+
 uint64_t bwts_pack_members_bound(const uint64_t *lengths, uint64_t count);      /* 0 on bad arguments */
+uint64_t bwts_pack_members_bound_m(const uint64_t *lengths, const uint32_t *widths, const uint32_t *methods, uint64_t count);    /* likewise */
+int bwts_pack_members_m_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters,
+                               const uint32_t *methods, uint64_t count, void *d_out, uint64_t out_cap, uint64_t *out_bytes);
+int bwts_pack_members_m(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters,
+                        const uint32_t *methods, uint64_t count, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes);
+int bwts_frame_members_m(const uint8_t *frame, uint64_t in_bytes, uint64_t *lengths_out, uint32_t *widths_out, uint32_t *filters_out,
+                         uint32_t *methods_out, uint64_t cap, uint64_t *count);
 int bwts_pack_members_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, uint64_t count, void *d_out,
                              uint64_t out_cap, uint64_t *out_bytes);
 int bwts_pack_members(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, const uint32_t *widths, uint64_t count, uint8_t *out,

@@ -166,7 +166,9 @@ int bwts_debug_unpack_ranges_plan(const uint8_t *frame, uint64_t in_bytes, const
 /* What the most recent bwts_unpack_ranges / _device on the context did (host memory, no device work; all 0 before any call and
  * after one that was refused by the frame checks).  out = {0 covered blocks, 1 runs, 2 C, 3 stream bytes read, 4 the stream gather
  * ran, 5 output pieces, 6 stages run, a bit each: 1 gather, 2 decode, 4 zero-run decode, 8 inverse move-to-front, 16 inverse
- * transform, 32 join, 64 checksums, 128 cut-out; 7 the single-input stages were used (one covered block)}. */
+ * transform, 32 join, 64 checksums, 128 cut-out, 256 delta decode, 512 the regrouping of a covered set that holds both chain and
+ * direct members (bwts_members.h, version 3; where every covered member is direct, none of 4, 8, 16 and 512); 7 the single-input
+ * stages were used (one covered block)}. */
 int bwts_debug_unpack_ranges_report(bwts_ctx *ctx, uint64_t out[8]);
 /* copy_pieces_kernel alone: `count` pieces as (offset in d_src, offset in d_dst, bytes) triples.  BWTS_E_ARG, before anything is
  * launched, for NULL pointers, count == 0, a piece of no bytes, a piece that leaves either buffer, or two pieces that share a

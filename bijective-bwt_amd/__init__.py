@@ -76,6 +76,7 @@ MEMBERS_EXPORTS = [
     "bwts_pack_members_device", "bwts_pack_members", "bwts_frame_members", "bwts_unpack_members_device", "bwts_unpack_members",
     "bwts_pack_members_f_device", "bwts_pack_members_f", "bwts_frame_members_f",
     "bwts_pack_members_bound_m", "bwts_pack_members_m_device", "bwts_pack_members_m", "bwts_frame_members_m",
+    "bwts_members_estimate_device", "bwts_members_estimate", "bwts_pack_members_bound_a", "bwts_pack_members_a_device", "bwts_pack_members_a",
 ]
 # ... include/bwts_delta.h (delta filter of integer arrays, the stage in front of the byte-plane split) ...
 DELTA_EXPORTS = [
@@ -84,6 +85,7 @@ DELTA_EXPORTS = [
 ]
 FILTER_NONE, FILTER_DELTA = 0, 1
 METHOD_CHAIN, METHOD_ORDER0 = 0, 1      # a member's method (member frame version 3): the whole chain, or its planes coded directly
+FILTER_AUTO = METHOD_AUTO = 255         # pack_members_auto alone: the pack chooses (include/bwts_members.h, "AUTO")
 # ... and include/bwts_test.h (harness and unit-test hooks)
 TEST_EXPORTS = [
     "bwts_generate_device", "bwts_device_alloc", "bwts_device_free", "bwts_copy_to_device", "bwts_copy_to_host",
@@ -272,6 +274,12 @@ def lib():
         for name in ("bwts_pack_members_m_device", "bwts_pack_members_m"):
             getattr(L, name).argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
         L.bwts_frame_members_m.argtypes = [vp, u64, vp, vp, vp, vp, u64, ctypes.POINTER(u64)]
+        for name in ("bwts_members_estimate_device", "bwts_members_estimate"):
+            getattr(L, name).argtypes = [vp, vp, vp, vp, u64, vp, vp]
+        L.bwts_pack_members_bound_a.argtypes = [vp, vp, vp, u64]
+        L.bwts_pack_members_bound_a.restype = u64
+        for name in ("bwts_pack_members_a_device", "bwts_pack_members_a"):
+            getattr(L, name).argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, u64, ctypes.POINTER(u64), vp, vp]
         for name in ("bwts_delta_encode_device", "bwts_delta_decode_device", "bwts_delta_encode", "bwts_delta_decode"):
             getattr(L, name).argtypes = [vp, vp, u64, u32, vp]
         for name in ("bwts_delta_encode_segments_f_device", "bwts_delta_decode_segments_f_device"):
@@ -775,6 +783,48 @@ class Context:
                                                      _ptr(d_out), int(out_cap), ctypes.byref(got)))
         return int(got.value)
 
+    def members_estimate(self, arrays, widths=None):
+        """bwts_members_estimate: what the order-0 coder would make of every array's byte planes without a filter and with the delta
+        filter, two lists of bytes (host buffers); widths as in pack_members."""
+        parts = [_bytes_of(a) for a in arrays]
+        ls, ws = _members([p.size for p in parts], widths)
+        a = np.concatenate(parts) if parts else np.empty(0, dtype=np.uint8)
+        e0, e1 = np.zeros(ls.size, dtype=np.uint64), np.zeros(ls.size, dtype=np.uint64)
+        self._check(lib().bwts_members_estimate(self._h, a.ctypes.data, ls.ctypes.data if ls.size else None, None if ws is None else ws.ctypes.data, ls.size,
+                                                e0.ctypes.data, e1.ctypes.data))
+        return e0.tolist(), e1.tolist()
+
+    def members_estimate_device(self, d_in, lengths, widths=None):
+        """bwts_members_estimate_device: the members lie back to back in d_in."""
+        ls, ws = _members(lengths, widths)
+        e0, e1 = np.zeros(ls.size, dtype=np.uint64), np.zeros(ls.size, dtype=np.uint64)
+        self._check(lib().bwts_members_estimate_device(self._h, _ptr(d_in), ls.ctypes.data if ls.size else None, None if ws is None else ws.ctypes.data, ls.size,
+                                                       e0.ctypes.data, e1.ctypes.data))
+        return e0.tolist(), e1.tolist()
+
+    def pack_members_auto(self, arrays, widths=None, filters=FILTER_AUTO, methods=METHOD_AUTO, out_cap=None):
+        """bwts_pack_members_a: pack_members with FILTER_AUTO and METHOD_AUTO allowed, each a scalar for all arrays or a list; the pack
+        resolves them by the rules of include/bwts_members.h, and frame_member_filters / frame_member_methods read the choices back."""
+        parts = [_bytes_of(a) for a in arrays]
+        ls, ws = _members([p.size for p in parts], widths)
+        fs, ms = _per_member(ls, filters, "filter"), _per_member(ls, methods, "method")
+        a = np.concatenate(parts) if parts else np.empty(0, dtype=np.uint8)
+        out = np.empty(pack_members_bound_auto(ls, ws, ms) if out_cap is None else int(out_cap), dtype=np.uint8)
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_pack_members_a(self._h, a.ctypes.data, ls.ctypes.data, None if ws is None else ws.ctypes.data, fs.ctypes.data, ms.ctypes.data,
+                                              ls.size, out.ctypes.data, out.size, ctypes.byref(got), None, None))
+        return out[:got.value].copy()
+
+    def pack_members_auto_device(self, d_in, lengths, widths, d_out, out_cap, filters=FILTER_AUTO, methods=METHOD_AUTO):
+        """bwts_pack_members_a_device: (the frame's size in bytes, the resolved filters, the resolved methods)."""
+        ls, ws = _members(lengths, widths)
+        fs, ms = _per_member(ls, filters, "filter"), _per_member(ls, methods, "method")
+        fo, mo = np.zeros(ls.size, dtype=np.uint32), np.zeros(ls.size, dtype=np.uint32)
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_pack_members_a_device(self._h, _ptr(d_in), ls.ctypes.data, None if ws is None else ws.ctypes.data, fs.ctypes.data,
+                                                     ms.ctypes.data, ls.size, _ptr(d_out), int(out_cap), ctypes.byref(got), fo.ctypes.data, mo.ctypes.data))
+        return int(got.value), fo.tolist(), mo.tolist()
+
     def unpack_members(self, frame, indices=None):
         """bwts_unpack_members: the members named, as a list of bytes, in the order asked (None: all of them); only these are decoded."""
         a = _u8(frame)
@@ -1121,6 +1171,28 @@ def pack_members_bound(lengths, widths=None, methods=None):
         b = int(lib().bwts_pack_members_bound_m(ls.ctypes.data if ls.size else None, None if ws is None else ws.ctypes.data, ms.ctypes.data, ls.size))
     if b == 0:
         bad = ls.size == 0 or bool((ls == 0).any()) or (ms is not None and (bool((ms > 1).any()) or (ws is not None and not bool(np.isin(ws, (1, 2, 4, 8)).all()))))
+        raise BwtsError(-1 if bad else -5, "no bound for these lengths")
+    return b
+
+
+def _per_member(ls, value, what):
+    """A filter or a method of an auto pack as the array the library takes: a scalar for all members, or one per member."""
+    if np.ndim(value) == 0:
+        return np.full(ls.size, int(value), dtype=np.uint32)
+    vs = np.ascontiguousarray(value, dtype=np.uint32).reshape(-1)
+    if vs.size != ls.size:
+        raise BwtsError(-1, "one %s per member" % what)
+    return vs
+
+
+def pack_members_bound_auto(lengths, widths=None, methods=METHOD_AUTO):
+    """bwts_pack_members_bound_a: the largest frame an auto pack of these members can make: a METHOD_AUTO member counts with the larger
+    of its two bounds."""
+    ls, ws = _members(lengths, widths)
+    ms = _per_member(ls, methods, "method")
+    b = int(lib().bwts_pack_members_bound_a(ls.ctypes.data if ls.size else None, None if ws is None else ws.ctypes.data, ms.ctypes.data, ls.size))
+    if b == 0:
+        bad = ls.size == 0 or bool((ls == 0).any()) or bool(((ms > 1) & (ms != METHOD_AUTO)).any()) or (ws is not None and not bool(np.isin(ws, (1, 2, 4, 8)).all()))
         raise BwtsError(-1 if bad else -5, "no bound for these lengths")
     return b
 

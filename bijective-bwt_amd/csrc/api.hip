@@ -11,6 +11,7 @@
 #include "planes_plan.h"
 #include "pack_plan.h"
 #include "members_plan.h"
+#include "estimate_plan.h"
 #include "../../include/bwts_members.h"
 #include "../../include/bwts_delta.h"
 
@@ -948,6 +949,70 @@ extern "C" int bwts_pack_members(bwts_ctx *ctx, const uint8_t *in, const uint64_
                                  uint64_t out_cap, uint64_t *out_bytes)
 {
     return bwts_pack_members_f(ctx, in, lengths, widths, nullptr, count, out, out_cap, out_bytes);
+}
+
+// the estimate and the pack that chooses (include/bwts_members.h, "The estimate", "AUTO"): the kernel in estimate.hip, the driver in pack.hip
+static_assert(MEMBERS_AUTO == BWTS_FILTER_AUTO && MEMBERS_AUTO == BWTS_METHOD_AUTO, "members_plan.h names the header's AUTO");
+
+extern "C" int bwts_members_estimate_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, uint64_t count,
+                                            uint64_t *est_none, uint64_t *est_delta)
+{
+    if (!ctx || !d_in || !est_none || !est_delta) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(members_args_check(lengths, widths, count, &n));
+    BWTS_TRY(seg_table_set(ctx, lengths, count, &n));
+    std::vector<u32> ws((size_t)count, 1u);
+    if (widths) ws.assign(widths, widths + count);
+    return run_sized(ctx, n, "members estimate", [&] { return estimate_impl(ctx, (const u8 *)d_in, n, ws.data(), nullptr, est_none, est_delta); });
+}
+
+extern "C" int bwts_members_estimate(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, const uint32_t *widths, uint64_t count,
+                                     uint64_t *est_none, uint64_t *est_delta)
+{
+    if (!ctx || !in || !est_none || !est_delta) return BWTS_E_ARG;
+    u64 n = 0, made = 0;
+    BWTS_TRY(members_args_check(lengths, widths, count, &n));
+    u8 nothing = 0;
+    const HostTrip trip = {in, n, n, &nothing, &made};
+    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *, u64 *got) {
+        *got = 0;
+        return bwts_members_estimate_device(ctx, d_in, lengths, widths, count, est_none, est_delta);
+    });
+}
+
+extern "C" uint64_t bwts_pack_members_bound_a(const uint64_t *lengths, const uint32_t *widths, const uint32_t *methods, uint64_t count)
+{
+    return members_bound_bytes_a(lengths, widths, methods, count);
+}
+
+extern "C" int bwts_pack_members_a_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters,
+                                          const uint32_t *methods, uint64_t count, void *d_out, uint64_t out_cap, uint64_t *out_bytes,
+                                          uint32_t *filters_out, uint32_t *methods_out)
+{
+    if (!ctx || !d_in || !d_out || !out_bytes || ((uintptr_t)d_out & 15)) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(members_args_check_a(lengths, widths, filters, methods, count, &n));
+    if (ranges_overlap(d_in, n, d_out, out_cap)) return BWTS_E_ARG;
+    return run_sized(ctx, n, "pack members", [&] {
+        return pack_members_auto_device_impl(ctx, (const u8 *)d_in, lengths, widths, filters, methods, count, n, (u8 *)d_out, out_cap, out_bytes, filters_out,
+                                             methods_out);
+    });
+}
+
+extern "C" int bwts_pack_members_a(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters,
+                                   const uint32_t *methods, uint64_t count, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
+                                   uint32_t *filters_out, uint32_t *methods_out)
+{
+    if (!ctx || !in || !out || !out_bytes) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(members_args_check_a(lengths, widths, filters, methods, count, &n));
+    // (the frame's size is known only when the choices are: the device form refuses what does not fit, before it writes)
+    const u64 bound = members_bound_bytes_a(lengths, widths, methods, count);
+    const u64 cap = out_cap < bound ? out_cap : bound;
+    const HostTrip trip = {in, n, n > cap ? n : cap, out, out_bytes};
+    return host_round_trip(ctx, trip, [&](const u8 *d_in, u8 *d_out, u64 *bytes) {
+        return bwts_pack_members_a_device(ctx, d_in, lengths, widths, filters, methods, count, d_out, cap, bytes, filters_out, methods_out);
+    });
 }
 
 extern "C" int bwts_frame_members_m(const uint8_t *frame, uint64_t in_bytes, uint64_t *lengths_out, uint32_t *widths_out, uint32_t *filters_out,

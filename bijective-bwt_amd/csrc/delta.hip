@@ -13,6 +13,8 @@
 //              tile's carry is added and the elements go out.
 //           Addition mod 2^64 is a group: the carry of tile t is scanned[t] - scanned[first tile of its segment], taken mod 2^{8w}.
 //           The scan stays plain addition, and what a copied segment's tiles put into it (zeros) cancels.
+// A thread's elements in registers (the word they are worked on in, element i of the loaded words, the zigzag at a constant width) are
+// in delta_words.h, which estimate.hip shares.
 // Reading and writing follow planes.hip (load16.h): planes_load16 reads the two aligned 16-byte pieces around an address, and nothing
 // outside the call's input; planes_stream_store sends a tile from LDS with aligned 16-byte stores and at most 30 single bytes.  No
 // access wider than a byte is made at an address that is not a multiple of its width.
@@ -23,6 +25,7 @@
 #include "load16.h"
 #include "scan_templ.h"
 #include "delta_plan.h"
+#include "delta_words.h"
 #include "../../include/bwts_delta.h"
 
 static_assert(DELTA_FILTER_NONE == BWTS_FILTER_NONE && DELTA_FILTER_DELTA == BWTS_FILTER_DELTA, "delta_plan.h names the header's filters");
@@ -30,52 +33,6 @@ static_assert(DELTA_FILTER_NONE == BWTS_FILTER_NONE && DELTA_FILTER_DELTA == BWT
 // LDS units of a tile at width w (the interleaved side of a join at that width), and of the widest tile of a mixed call, copied ones included
 #define DELTA_SLOTS(w) (PLANES_SLOT((w) * (PLANES_E / 16u)) + 2u)
 static_assert(DELTA_SLOTS(PLANES_MAX_W) >= PLANES_SLOT(PLANES_COPY_T / 16u) + 2u, "a copied tile fits the LDS of a tile at the largest width");
-
-// elements are worked on in 32 bits, 8-byte ones in 64
-template <int W> struct DeltaWord { typedef u32 T; };
-template <> struct DeltaWord<8> { typedef u64 T; };
-
-template <int W>
-__device__ __forceinline__ typename DeltaWord<W>::T delta_mask_t()
-{
-    if constexpr (W == 8) return ~0ull;
-    else if constexpr (W == 4) return ~0u;
-    else return (1u << (8 * W)) - 1u;
-}
-
-// element i of the little-endian words D (i a constant after unrolling), and its place in words that were zero
-template <int W>
-__device__ __forceinline__ typename DeltaWord<W>::T delta_get(const u32 *D, int i)
-{
-    if constexpr (W == 8) return (u64)D[2 * i] | ((u64)D[2 * i + 1] << 32);
-    else if constexpr (W == 4) return D[i];
-    else if constexpr (W == 2) return (D[i >> 1] >> (16 * (i & 1))) & 0xffffu;
-    else return (D[i >> 2] >> (8 * (i & 3))) & 0xffu;
-}
-
-template <int W>
-__device__ __forceinline__ void delta_put(u32 *O, int i, typename DeltaWord<W>::T v)
-{
-    if constexpr (W == 8) { O[2 * i] = (u32)v; O[2 * i + 1] = (u32)(v >> 32); }
-    else if constexpr (W == 4) O[i] = v;
-    else if constexpr (W == 2) O[i >> 1] |= v << (16 * (i & 1));
-    else O[i >> 2] |= v << (8 * (i & 3));
-}
-
-// delta_plan.h's delta_zigzag and delta_unzigzag at a constant width
-template <int W>
-__device__ __forceinline__ typename DeltaWord<W>::T delta_zig(typename DeltaWord<W>::T d)
-{
-    typedef typename DeltaWord<W>::T T;
-    return ((T)(d << 1) ^ (T)(0 - ((d >> (8 * W - 1)) & 1u))) & delta_mask_t<W>();
-}
-
-template <int W>
-__device__ __forceinline__ typename DeltaWord<W>::T delta_unzig(typename DeltaWord<W>::T z)
-{
-    typedef typename DeltaWord<W>::T T;
-    return ((z >> 1) ^ (T)(0 - (z & 1u))) & delta_mask_t<W>();
-}
 
 struct DeltaTile {
     u64 seg, len, e0;       // the segment's start and length, the tile's first element
@@ -108,12 +65,7 @@ __device__ __forceinline__ void delta_copy_tail(const u8 *in, const DeltaTile &R
 template <int W>
 __device__ __forceinline__ void delta_load_thread(const u8 *__restrict__ in, u64 n, const DeltaTile &R, u32 at, u32 *D)
 {
-    const u8 *p = in + R.seg + (R.e0 + at) * W;
-#pragma unroll
-    for (int v = 0; v < W; v++) {
-        const uint4 x = planes_load16(p + 16 * v, in, in + n);
-        D[4 * v] = x.x; D[4 * v + 1] = x.y; D[4 * v + 2] = x.z; D[4 * v + 3] = x.w;
-    }
+    delta_load16<W>(in + R.seg + (R.e0 + at) * W, in, n, D);
 }
 
 // the thread's 16 elements into the tile's stream in LDS

@@ -41,7 +41,7 @@ enum SegReportWord { SR_PLAN, SR_BIG, SR_RUNS, SR_OWN_SEGS, SR_OWN_BYTES, SR_SIN
 // bwts_ctx_destroy (ctx_memory.hip).  name: what the allocation trace and the guard report call it.
 struct KeptBlock { char *p; size_t cap; const char *name; };
 // every kept block of a context, in bwts_ctx::kept
-enum { KB_ARENA, KB_AUX, KB_IO = KB_AUX + BWTS_AUX_SLOTS, KB_SEG_TABLE = KB_IO + 4, KB_SEG_SCRATCH, KB_PACK, KB_COUNT = KB_PACK + 2 };
+enum { KB_ARENA, KB_AUX, KB_IO = KB_AUX + BWTS_AUX_SLOTS, KB_SEG_TABLE = KB_IO + 4, KB_SEG_SCRATCH, KB_PACK, KB_COUNT = KB_PACK + 3 };
 
 #define SM_RX_SYNC 4090          // d_small word holding the two 32-bit counters of radix_column_scan_fused_kernel (zero between launches)
 #define SM_EC_TOTAL 4020         // entropy coder (ec.hip): d_small word for the bytes of all payloads of an encode
@@ -72,14 +72,15 @@ struct bwts_ctx {
     // list of the general Lyndon path.  3: previous-symbol array + carried-byte buffers (rounds-0 sorts on wide keys).  4: dense rank array.
     // (What the headline path does not touch is not allocated: the driver clears device memory it hands out, ~27 ms per GiB.)
     // KB_IO + i: the host-buffer entry points' device-side in/out buffers (below).  KB_SEG_TABLE: the device copy of the segment table.
-    // KB_SEG_SCRATCH: segmented forward: factor-start flags.  KB_PACK + i: pack / unpack: the bytes between two stages of the chain.
+    // KB_SEG_SCRATCH: segmented forward: factor-start flags.  KB_PACK + 0, 1: pack / unpack: the bytes between two stages of the chain; + 2: a pack
+    // that chooses methods: both candidates' streams.
     KeptBlock kept[KB_COUNT] = {{nullptr, 0, "arena"},
                                 {nullptr, 0, "side block 0"}, {nullptr, 0, "side block 1"}, {nullptr, 0, "side block 2"},
                                 {nullptr, 0, "side block 3"}, {nullptr, 0, "side block 4"},
                                 {nullptr, 0, "device input 0"}, {nullptr, 0, "device input 1"},
                                 {nullptr, 0, "device output 0"}, {nullptr, 0, "device output 1"},
                                 {nullptr, 0, "segment table"}, {nullptr, 0, "segment scratch"},
-                                {nullptr, 0, "pack stage 0"}, {nullptr, 0, "pack stage 1"}};
+                                {nullptr, 0, "pack stage 0"}, {nullptr, 0, "pack stage 1"}, {nullptr, 0, "pack candidates"}};
     size_t arena_off;
     size_t unv_hint;       // inverse: unreached elements seen by the previous call (sizes the first collection pass)
     // inverse: one record per attempt of the most recent call, from values its stages hold on the host anyway (a few stores per
@@ -352,6 +353,10 @@ void bwts_planes_plan(u64 n, u32 w, u64 out[4]);                        // tile 
 int delta_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, u32 w, u8 *d_out, bool decode);                 // one input of n bytes at width 1, 2, 4 or 8
 int delta_f_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, const u32 *widths, const u32 *filters, u8 *d_out, bool decode);   // the context's table, a width and a filter per segment
 
+// ---- plane costs of the members of the context's table under both filters (estimate.hip; include/bwts_members.h) ----
+// take: null for every member, or a byte per member (zero: left out, its estimates are 0)
+int estimate_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, const u32 *widths, const u8 *take, u64 *est_none, u64 *est_delta);
+
 // ---- checksum and the packed frame (crc.hip, pack.hip; include/bwts_pack.h) ------------
 // one value for the input of n bytes, or one per segment, to the host
 int crc_impl(bwts_ctx *ctx, const u8 *d_in, u64 n, SegMode segs, u32 *crcs);
@@ -369,6 +374,10 @@ int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool 
 // members_args_check_m, n is the lengths' sum
 int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, const u32 *filters, const u32 *methods, u64 count, u64 n,
                              u8 *d_out, u64 out_cap, u64 *out_bytes);
+// the same with MEMBERS_AUTO among filters and methods, resolved by the rules of include/bwts_members.h ("AUTO"); arguments that have
+// passed members_args_check_a; filters_out, methods_out: null, or room for the resolved values
+int pack_members_auto_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, const u32 *filters, const u32 *methods, u64 count, u64 n,
+                                  u8 *d_out, u64 out_cap, u64 *out_bytes, u32 *filters_out, u32 *methods_out);
 // pieces of one device buffer to another, at any alignment (pieces.hip); every piece inside both buffers, by the caller's check
 int copy_pieces_impl(bwts_ctx *ctx, const u8 *d_src, u64 src_bytes, const PackPiece *pieces, u64 count, u8 *d_dst);
 

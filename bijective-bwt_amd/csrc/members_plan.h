@@ -148,6 +148,56 @@ static inline uint64_t members_least_bytes_m(const uint64_t *lengths, const uint
     return total;
 }
 
+// ---- a filter or a method left to the pack (bwts_pack_members_a*; the rules: include/bwts_members.h, "AUTO") ----
+#define MEMBERS_AUTO 255u                // BWTS_FILTER_AUTO, BWTS_METHOD_AUTO
+// members_args_check_m with MEMBERS_AUTO among the filters and the methods
+static inline int members_args_check_a(const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters, const uint32_t *methods, uint64_t count,
+                                       uint64_t *n)
+{
+    const int rc = members_args_check_m(lengths, widths, nullptr, nullptr, count, n);
+    if (rc != PACK_OK) return rc;
+    for (uint64_t k = 0; k < count; k++)
+        if ((filters && filters[k] != MEMBERS_AUTO && !delta_filter_ok(filters[k])) || (methods && methods[k] != MEMBERS_AUTO && !members_method_ok(methods[k])))
+            return PACK_ARG;
+    return PACK_OK;
+}
+static inline bool members_any_auto(const uint32_t *values, uint64_t count)
+{
+    for (uint64_t k = 0; values && k < count; k++)
+        if (values[k] == MEMBERS_AUTO) return true;
+    return false;
+}
+// the coder's bound of a member's streams under a method that is 0 or 1
+static inline uint64_t members_streams_bound(uint64_t len, uint32_t w, uint32_t method)
+{
+    const uint32_t segs = method == MEMBERS_METHOD_ORDER0 ? members_direct_segments(len, w) : 1u;
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < segs; i++) total += ec_bound_bytes(segs > 1u ? members_direct_segment_bytes(len, w, i) : len);
+    return total;
+}
+// What a method's encoding of a member costs the frame: its streams and its words of the extension table.  The smaller cost wins an
+// AUTO, and a tie goes to the chain.
+EC_HD uint64_t members_method_cost(uint64_t stream_bytes, uint64_t len, uint32_t w, uint32_t method)
+{
+    return stream_bytes + 8u * members_table_words(len, w, method);
+}
+EC_HD uint32_t members_method_choice(uint64_t chain_cost, uint64_t direct_cost) { return direct_cost < chain_cost ? MEMBERS_METHOD_ORDER0 : MEMBERS_METHOD_CHAIN; }
+// The bound with AUTO among the methods: the extension table with every AUTO member's words, and an AUTO member's streams at the
+// larger of its two bounds; without AUTO it is members_bound_bytes_m.  0 on arguments that members_args_check_a refuses.
+static inline uint64_t members_bound_bytes_a(const uint64_t *lengths, const uint32_t *widths, const uint32_t *methods, uint64_t count)
+{
+    uint64_t n = 0, words = 0;
+    if (members_args_check_a(lengths, widths, nullptr, methods, count, &n) != PACK_OK) return 0;
+    uint64_t total = 0;
+    for (uint64_t k = 0; k < count; k++) {
+        const uint32_t w = widths ? widths[k] : 1u, m = methods ? methods[k] : MEMBERS_METHOD_CHAIN;
+        const uint64_t chain = members_streams_bound(lengths[k], w, MEMBERS_METHOD_CHAIN), direct = members_streams_bound(lengths[k], w, MEMBERS_METHOD_ORDER0);
+        if (m != MEMBERS_METHOD_CHAIN) words += members_table_words(lengths[k], w, MEMBERS_METHOD_ORDER0);
+        total += m == MEMBERS_METHOD_CHAIN ? chain : (m == MEMBERS_METHOD_ORDER0 ? direct : (chain > direct ? chain : direct));
+    }
+    return total + members_fixed_bytes_x(count, words + (words & 1u));
+}
+
 EC_HD void members_entry_write(uint8_t e[32], uint64_t stream_bytes, uint32_t crc, uint32_t width, uint64_t coded_bytes, uint64_t len)
 {
     pack_put64(e, stream_bytes); ec_put32(e + 8, crc); ec_put32(e + 12, width); pack_put64(e + 16, coded_bytes); pack_put64(e + 24, len);

@@ -15,6 +15,8 @@
 // between two stages, so that no table copy of the stage before is still to come when the next stage writes its own (seg_layout.h:
 // the regions, and who overlaps whom).  The context's table changes hands inside a chain: the coder's segments are the blocks'
 // zero-run coded bytes where that stage runs, every other stage's the blocks themselves.
+// bwts_pack_members_a* leave filters and methods to the pack: the estimator (estimate.hip) in front of the chain resolves the filters,
+// and encode_candidates, a second arrangement of the same stages, encodes the members whose method is open both ways.
 // A member of a version-3 member frame may skip the middle of either chain (its method, include/bwts_members.h): such direct members
 // go from the split straight to the coder, every plane of a long one as a coder segment of its own (members_plan.h: the cut rule).
 // The chain stages then run over the chain members alone, gathered to the front of a stage block with pieces.hip's copy kernel, and
@@ -27,6 +29,7 @@
 // writes the one that makes the last stage land in d_out (decode_stages).
 #include "internal.h"
 #include "members_plan.h"
+#include "estimate_plan.h"
 #include "../../include/bwts_members.h"
 
 #include <string.h>
@@ -335,6 +338,26 @@ int pack_device_impl(bwts_ctx *ctx, u32 version, u32 width, const u8 *d_in, u64 
     return encode_finish(ctx, S, E, T, d_out, out_cap, out_bytes);
 }
 
+// Entries, extension table and header of a member frame whose streams lie behind d_out + S.fixed; S.methods is empty where no member
+// names a method.  E.seg_sizes: one word per member, and per stream of a member that has several.
+static int members_finish(bwts_ctx *ctx, const EncodeSet &S, const Encoded &E, u64 ext, u8 *d_out, u64 out_cap, u64 *out_bytes)
+{
+    const u64 count = S.lengths.size();
+    const bool v3 = !S.methods.empty();
+    FrameStaging T;
+    BWTS_TRY(encode_staging(ctx, MEMBERS_ENTRY_BYTES, count, ext, T));
+    u8 *table = T.dir + (u64)MEMBERS_ENTRY_BYTES * count;
+    if (ext) memset(table, 0, (size_t)(8u * ext));
+    for (size_t k = 0, seg = 0; k < (size_t)count; k++) {
+        const u32 method = v3 ? S.methods[k] : MEMBERS_METHOD_CHAIN, words = members_table_words(S.lengths[k], S.widths[k], method);
+        members_entry_write(T.dir + (u64)MEMBERS_ENTRY_BYTES * k, E.sizes[k], E.crcs[k], members_word(S.widths[k], S.filters[k], method), E.coded[k], S.lengths[k]);
+        for (u32 i = 0; i < words; i++, table += 8) pack_put64(table, E.seg_sizes[seg + i]);
+        seg += words ? words : 1u;
+    }
+    members_header_write_x(T.head, v3 ? MEMBERS_VERSION_3 : any_filter(S.filters) ? MEMBERS_VERSION_2 : MEMBERS_VERSION, S.n, count, ext, T.dir);
+    return encode_finish(ctx, S, E, T, d_out, out_cap, out_bytes);
+}
+
 // "BWTM": members of any lengths, each filtered if asked (filters: null for none) and split at its own width (widths: null for 1, not
 // at all), with the entries and the header of include/bwts_members.h.  methods: null for the whole chain everywhere; a member of
 // method 1 is coded directly.  A pack in which no member names a method writes version 2 where one names a filter, else version 1;
@@ -353,18 +376,176 @@ int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, 
     if (v3) S.methods.assign(methods, methods + count);
     Encoded E;
     BWTS_TRY(encode_chain(ctx, S, d_in, d_out, out_cap, E));
-    FrameStaging T;
-    BWTS_TRY(encode_staging(ctx, MEMBERS_ENTRY_BYTES, count, ext, T));
-    u8 *table = T.dir + (u64)MEMBERS_ENTRY_BYTES * count;
-    if (ext) memset(table, 0, (size_t)(8u * ext));
-    for (size_t k = 0, seg = 0; k < (size_t)count; k++) {
-        const u32 method = v3 ? methods[k] : MEMBERS_METHOD_CHAIN, words = members_table_words(lengths[k], S.widths[k], method);
-        members_entry_write(T.dir + (u64)MEMBERS_ENTRY_BYTES * k, E.sizes[k], E.crcs[k], members_word(S.widths[k], S.filters[k], method), E.coded[k], lengths[k]);
-        for (u32 i = 0; i < words; i++, table += 8) pack_put64(table, E.seg_sizes[seg + i]);
-        seg += words ? words : 1u;
+    return members_finish(ctx, S, E, ext, d_out, out_cap, out_bytes);
+}
+
+// ---- a pack that chooses filters and methods (include/bwts_members.h, "AUTO") ----
+// the pieces that gather the blocks a set names (a byte per block) from a buffer of all blocks in order to the front of another;
+// neighbouring blocks are one piece
+static std::vector<PackPiece> set_pieces(const std::vector<u64> &lengths, const std::vector<u8> &in_set)
+{
+    std::vector<PackPiece> ps;
+    u64 at = 0, to = 0;
+    for (size_t k = 0; k < lengths.size(); at += lengths[k], k++) {
+        if (!in_set[k]) continue;
+        if (!ps.empty() && ps.back().src + ps.back().bytes == at) ps.back().bytes += lengths[k];
+        else ps.push_back(PackPiece{at, to, lengths[k]});
+        to += lengths[k];
     }
-    members_header_write_x(T.head, v3 ? MEMBERS_VERSION_3 : any_filter(S.filters) ? MEMBERS_VERSION_2 : MEMBERS_VERSION, n, count, ext, T.dir);
-    return encode_finish(ctx, S, E, T, d_out, out_cap, out_bytes);
+    return ps;
+}
+
+// Both encodings of the members whose method is open, and the winners' streams to their places.  S holds the resolved filters and, in
+// S.methods, what was asked (MEMBERS_AUTO among it); the direct candidates are the members that name method 1 or AUTO, the chain
+// candidates those that name method 0 or AUTO, and there is one of either.  Checksum, filter and split run once over all members;
+// the coder runs over the direct candidates' split bytes, then the chain stages and the coder over the chain candidates' -- both into
+// the context's candidates block, which the bounds size, so that nothing is written to d_out before the frame is known to fit.  On
+// return S.methods are the resolved ones (empty where none is direct), E says what members_finish needs, and *ext the table's words.
+static int encode_candidates(bwts_ctx *ctx, EncodeSet &S, const u8 *d_in, u8 *d_out, u64 out_cap, Encoded &E, u64 *ext)
+{
+    const size_t count = S.lengths.size();
+    const u64 n = S.n;
+    std::vector<u8> chain(count), direct(count);
+    std::vector<u64> chain_lengths, direct_lengths;         // the chain candidates; the direct candidates' coder segments
+    std::vector<u32> dsegs(count, 0u);
+    u64 nc = 0, nd = 0, bound_c = 0, bound_d = 0;
+    size_t chains = 0, directs = 0;
+    for (size_t k = 0; k < count; k++) {
+        chain[k] = S.methods[k] != MEMBERS_METHOD_ORDER0;
+        direct[k] = S.methods[k] != MEMBERS_METHOD_CHAIN;
+        if (chain[k]) { chains++; nc += S.lengths[k]; chain_lengths.push_back(S.lengths[k]); bound_c += ec_bound_bytes(S.lengths[k]); }
+        if (direct[k]) {
+            directs++; nd += S.lengths[k]; bound_d += members_streams_bound(S.lengths[k], S.widths[k], MEMBERS_METHOD_ORDER0);
+            dsegs[k] = members_direct_segments(S.lengths[k], S.widths[k]);
+            for (u32 i = 0; i < dsegs[k]; i++) direct_lengths.push_back(members_direct_segment_bytes(S.lengths[k], S.widths[k], i));
+        }
+    }
+    BWTS_TRY(blocks_set(ctx, S.lengths, n));
+    const SegMode segs = count > 1 ? seg_mode(ctx) : SEG_SINGLE;
+    E.crcs.resize(count); E.sizes.resize(count); E.coded.resize(count);
+    BWTS_TRY(crc_impl(ctx, d_in, n, segs, E.crcs.data()));
+    u8 *to = nullptr, *other = nullptr;
+    BWTS_TRY(pack_stage(ctx, 0, n, &to));
+    BWTS_TRY(pack_stage(ctx, 1, n, &other));
+    const u64 direct_at = 0, chain_at = align_up(bound_d, 256), cand_bytes = chain_at + bound_c;
+    BWTS_TRY(kept_grow(ctx, ctx->kept[KB_PACK + 2], cand_bytes, 1 << 16, -1));
+    u8 *const cand = (u8 *)ctx->kept[KB_PACK + 2].p;
+    const u8 *from = d_in;
+    auto done = [&] { from = to; std::swap(to, other); return hipStreamSynchronize(ctx->stream); };
+    if (any_filter(S.filters)) {
+        BWTS_TRY(frame_delta(ctx, from, n, S.widths, S.filters, to, false, segs));
+        HIPC(done());
+    }
+    if (any_split(S.widths)) {
+        BWTS_TRY(frame_planes(ctx, from, n, S.widths, to, false, segs));
+        HIPC(done());
+    }
+    // `from` holds every member's split bytes, and `to` is free.  The direct candidates: gathered there unless they are all members
+    std::vector<u64> dsizes(direct_lengths.size()), csizes(chains), ccoded(chains);
+    {
+        const u8 *dfrom = from;
+        if (directs != count) {
+            const std::vector<PackPiece> ps = set_pieces(S.lengths, direct);
+            BWTS_TRY(copy_pieces_impl(ctx, from, n, ps.data(), ps.size(), to));
+            dfrom = to;
+        }
+        SegMode ds;
+        BWTS_TRY(table_set(ctx, direct_lengths, &ds));
+        BWTS_TRY(ec_encode_impl(ctx, dfrom, nd, cand + direct_at, bound_d, ds, dsizes.data()));
+        HIPC(hipStreamSynchronize(ctx->stream));
+    }
+    // The chain candidates: gathered likewise, after which the split bytes are no longer needed and their block (where it is a stage
+    // block: `other`) is the second one of the to and fro
+    if (chains != count) {
+        const std::vector<PackPiece> ps = set_pieces(S.lengths, chain);
+        BWTS_TRY(copy_pieces_impl(ctx, from, n, ps.data(), ps.size(), to));
+        HIPC(done());
+    }
+    SegMode cs;
+    BWTS_TRY(table_set(ctx, chain_lengths, &cs));
+    BWTS_TRY(cs.table() ? forward_segments_impl(ctx, from, nc, to) : forward_device_impl(ctx, from, nc, to));
+    HIPC(done());
+    BWTS_TRY(mtf_impl(ctx, from, nc, to, false, cs));
+    HIPC(done());
+    BWTS_TRY(zrl_encode_impl(ctx, from, nc, to, nc, cs, ccoded.data()));
+    HIPC(done());
+    u64 mc = 0;
+    BWTS_TRY(pack_coded_set(ctx, ccoded, &mc));
+    BWTS_TRY(ec_encode_impl(ctx, from, mc, cand + chain_at, bound_c, cs, csizes.data()));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    // the choice, and where every winner's streams lie in the candidates block
+    std::vector<PackPiece> win;
+    std::vector<u32> resolved(count);
+    bool v3 = false;
+    u64 d_at = direct_at, c_at = chain_at, total = 0;
+    for (size_t k = 0, di = 0, ci = 0; k < count; k++) {
+        u64 dsb = 0, csb = chain[k] ? csizes[ci] : 0;
+        for (u32 i = 0; i < dsegs[k]; i++) dsb += dsizes[di + i];
+        u32 m = S.methods[k];
+        if (m == MEMBERS_AUTO)
+            m = members_method_choice(members_method_cost(csb, S.lengths[k], S.widths[k], MEMBERS_METHOD_CHAIN),
+                                      members_method_cost(dsb, S.lengths[k], S.widths[k], MEMBERS_METHOD_ORDER0));
+        resolved[k] = m;
+        const bool d = m == MEMBERS_METHOD_ORDER0;
+        v3 = v3 || d;
+        E.sizes[k] = d ? dsb : csb;
+        E.coded[k] = d ? S.lengths[k] : ccoded[ci];
+        if (d) E.seg_sizes.insert(E.seg_sizes.end(), dsizes.begin() + (long)di, dsizes.begin() + (long)(di + dsegs[k]));
+        else E.seg_sizes.push_back(csb);
+        const u64 src = d ? d_at : c_at;
+        if (!win.empty() && win.back().src + win.back().bytes == src) win.back().bytes += E.sizes[k];
+        else win.push_back(PackPiece{src, total, E.sizes[k]});
+        total += E.sizes[k];
+        if (direct[k]) { d_at += dsb; di += dsegs[k]; }
+        if (chain[k]) { c_at += csb; ci++; }
+    }
+    S.methods = resolved;
+    *ext = v3 ? members_ext_words(S.lengths.data(), S.widths.data(), S.methods.data(), count) : 0;
+    S.fixed = members_fixed_bytes_x(count, *ext);
+    if (S.fixed + total > out_cap) return BWTS_E_SPACE;
+    BWTS_TRY(copy_pieces_impl(ctx, cand, cand_bytes, win.data(), win.size(), d_out + S.fixed));
+    if (!v3) S.methods.clear();
+    ctx->tm.n = n;
+    return BWTS_OK;
+}
+
+// lengths, widths (null: 1), filters (null: none) and methods (null: the chain), MEMBERS_AUTO among the last two, have passed
+// members_args_check_a; n is the lengths' sum.  filters_out, methods_out: null, or room for the resolved values.
+int pack_members_auto_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, const u32 *filters, const u32 *methods, u64 count, u64 n,
+                                  u8 *d_out, u64 out_cap, u64 *out_bytes, u32 *filters_out, u32 *methods_out)
+{
+    EncodeSet S{std::vector<u64>(lengths, lengths + count), {}, {}, true, n, 0, 0, {}};
+    S.widths.assign((size_t)count, 1u);
+    if (widths) S.widths.assign(widths, widths + count);
+    S.filters.assign((size_t)count, DELTA_FILTER_NONE);
+    if (filters) S.filters.assign(filters, filters + count);
+    S.methods.assign((size_t)count, MEMBERS_METHOD_CHAIN);
+    if (methods) S.methods.assign(methods, methods + count);
+    if (members_any_auto(S.filters.data(), count)) {
+        // the estimate of the members whose filter is open, and the rule of estimate_plan.h
+        std::vector<u8> take((size_t)count);
+        std::vector<u64> none((size_t)count), delta((size_t)count);
+        for (size_t k = 0; k < (size_t)count; k++) take[k] = S.filters[k] == MEMBERS_AUTO;
+        u64 total = 0;
+        BWTS_TRY(seg_table_set(ctx, lengths, count, &total));
+        BWTS_TRY(estimate_impl(ctx, d_in, n, S.widths.data(), take.data(), none.data(), delta.data()));
+        for (size_t k = 0; k < (size_t)count; k++)
+            if (take[k]) S.filters[k] = estimate_filter(none[k], delta[k]);
+    }
+    if (!members_any_auto(S.methods.data(), count)) {
+        BWTS_TRY(pack_members_device_impl(ctx, d_in, lengths, S.widths.data(), S.filters.data(), S.methods.data(), count, n, d_out, out_cap, out_bytes));
+    } else {
+        Encoded E;
+        u64 ext = 0;
+        BWTS_TRY(encode_candidates(ctx, S, d_in, d_out, out_cap, E, &ext));
+        BWTS_TRY(members_finish(ctx, S, E, ext, d_out, out_cap, out_bytes));
+        if (S.methods.empty()) S.methods.assign((size_t)count, MEMBERS_METHOD_CHAIN);
+    }
+    for (size_t k = 0; k < (size_t)count; k++) {
+        if (filters_out) filters_out[k] = S.filters[k];
+        if (methods_out) methods_out[k] = S.methods[k];
+    }
+    return BWTS_OK;
 }
 
 // ---- decoding ----

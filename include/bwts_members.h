@@ -120,6 +120,40 @@
  * left out where there is none.  bwts_timings::device_bytes after a version-2 call is what the version-1 frame of the same lengths leaves.
  * A direct member costs a checksum, a split and the coder; in a mixed frame two gathers (a copy each) besides, and the transform's
  * arena is sized for the chain members alone.
+ *
+ * The estimate.  bwts_members_estimate* give, for every member, what the order-0 coder would make of its byte planes as they are
+ * (est_none) and of the planes of its delta-filtered elements (est_delta), in bytes, from one read of the input.  Exact integer
+ * arithmetic, the same on the device, on the host and in tests/estimate_model.py:
+ *   a member of len bytes and width w has q = floor(len / w) elements; its tail of len - q w bytes is copied under either filter and
+ *   is not counted.  The member is cut into units of 2^18 elements (what one 256 KiB coder block of a plane spans).  For every unit,
+ *   every plane p < w and both filters, c[0..255] is the histogram of byte p of the unit's elements: filter 0 takes the element
+ *   itself, filter 1 zigzag(element - predecessor) at width w as bwts_delta.h defines it, with 0 in front of the member's first
+ *   element and the last element of the unit before in front of a unit's first.  With N the sum of c,
+ *       bits = N lg(N) - sum over s of c[s] lg(c[s]), 0 where that would be negative;  a unit's plane costs ceil(bits / (8 * 2^16)) bytes,
+ *   and the estimate is the sum over the member's units and planes; q = 0 gives 0 and 0.
+ *   lg(x), 1 <= x < 2^32, is a fixed-point log2 with 16 fraction bits: k = the place of x's highest bit, y = x * 2^(31 - k), and
+ *   sixteen times: y = floor(y * y / 2^31); the next fraction bit is 1, and y = floor(y / 2), where y >= 2^32, else 0.  lg(x) = k * 2^16 + the
+ *   fraction bits, first one highest.  No floating point is used anywhere.
+ * The estimate is a statement about planes, not a promise of a frame size; a member that the coder would code as one stream is
+ * estimated by the same definition.  Refusals are those of bwts_pack_members (est_none or est_delta NULL: BWTS_E_ARG); working
+ * memory is 16 bytes per unit.  bwts_last_timings: n and total_ms are filled, the kernel is accounted under BWTS_K_OTHER, as one
+ * launch more in a pack that leaves a filter open.
+ *
+ * AUTO.  bwts_pack_members_a* take BWTS_FILTER_AUTO and BWTS_METHOD_AUTO (255) beside the values above, per member, and resolve them
+ * by the rules of this writer; the frame is, byte for byte, what bwts_pack_members_m* writes for the resolved arrays (its canonical
+ * version 1, 2 or 3 among it), which filters_out and methods_out give where they are not NULL, and which every reader takes as it
+ * takes any other: the choice stands in the directory.  bwts_pack_members_m* refuse 255 as they always did.
+ *   A filter AUTO becomes delta iff est_delta + (est_none >> 6) < est_none, else none: a filter must save more than 1/64 of the
+ *   estimate, since one that buys nothing costs a decode sweep.  The filter is chosen by the estimate whatever the member's method.
+ *   A method AUTO: the member is encoded both ways at its resolved filter; a way's cost is its stream_bytes + 8 x its extension-table
+ *   words (none for the chain); the smaller cost wins, and a tie goes to the chain (method 0).
+ *   The estimator runs only where some filter is AUTO, and over those members alone.  Checksum, filter and split run once; the
+ *   chain stages run once, over the members that name the chain or AUTO; the coder runs over both sets of candidates into a block the
+ *   context keeps for such calls, sized by the candidates' bounds, and the winners' streams are copied to their places.  A call whose
+ *   arrays name no AUTO launches exactly what bwts_pack_members_m* launches; so does one with filters AUTO alone, behind the estimator.
+ *   Bound: bwts_pack_members_bound_a: an AUTO member counts with the larger of its two bounds, and the extension table with every AUTO
+ *   member's words; without AUTO it is bwts_pack_members_bound_m.  No BWTS_E_SPACE for out_cap >= that bound; header and directory are
+ *   written last, behind the streams, and a call that fails with BWTS_E_SPACE has written nothing.
  */
 #ifndef BWTS_MEMBERS_H
 #define BWTS_MEMBERS_H
@@ -161,6 +195,25 @@ int bwts_unpack_members_device(bwts_ctx *ctx, const void *d_in, uint64_t in_byte
                                uint64_t out_cap, uint64_t *out_bytes);
 int bwts_unpack_members(bwts_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const uint64_t *indices, uint64_t icount, uint8_t *out,
                         uint64_t out_cap, uint64_t *out_bytes);
+
+/* the estimate: est_none and est_delta are host arrays of count */
+int bwts_members_estimate_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, uint64_t count,
+                                 uint64_t *est_none, uint64_t *est_delta);
+int bwts_members_estimate(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, const uint32_t *widths, uint64_t count,
+                          uint64_t *est_none, uint64_t *est_delta);
+
+/* a filter or a method that the pack chooses (bwts_pack_members_a* alone take them) */
+#define BWTS_FILTER_AUTO 255u
+#define BWTS_METHOD_AUTO 255u
+
+uint64_t bwts_pack_members_bound_a(const uint64_t *lengths, const uint32_t *widths, const uint32_t *methods, uint64_t count);    /* 0 on bad arguments */
+/* filters_out, methods_out: host arrays of count for the resolved values, or NULL */
+int bwts_pack_members_a_device(bwts_ctx *ctx, const void *d_in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters,
+                               const uint32_t *methods, uint64_t count, void *d_out, uint64_t out_cap, uint64_t *out_bytes,
+                               uint32_t *filters_out, uint32_t *methods_out);
+int bwts_pack_members_a(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters,
+                        const uint32_t *methods, uint64_t count, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
+                        uint32_t *filters_out, uint32_t *methods_out);
 
 #ifdef __cplusplus
 }

@@ -94,7 +94,7 @@ TEST_EXPORTS = [
     "bwts_debug_forward_report", "bwts_debug_segments_plan", "bwts_debug_segments_report",
     "bwts_debug_mtf_plan", "bwts_debug_last_spans", "bwts_debug_ec_plan", "bwts_debug_crc_plan",
     "bwts_debug_zrl_plan", "bwts_debug_planes_plan", "bwts_debug_key_plan",
-    "bwts_debug_unpack_ranges_plan", "bwts_debug_unpack_ranges_report", "bwts_debug_copy_pieces",
+    "bwts_debug_unpack_ranges_plan", "bwts_debug_unpack_ranges_report", "bwts_debug_copy_pieces", "bwts_debug_rank_steps",
 ]
 # bwts_debug_unpack_ranges_report: the words of the record, and the stages by their bits
 RANGES_REPORT_FIELDS = ["blocks", "runs", "covered_bytes", "stream_bytes", "gathered", "pieces", "stages", "single"]
@@ -293,6 +293,7 @@ def lib():
         L.bwts_copy_to_host.argtypes = [vp, vp, vp, u64]
         L.bwts_device_equal.argtypes = [vp, vp, vp, u64, ctypes.POINTER(i32)]
         L.bwts_debug_sort_pairs.argtypes = [vp, vp, vp, u64, i32]
+        L.bwts_debug_rank_steps.argtypes = [vp, vp, vp, i32, vp, vp]
         L.bwts_debug_suffix_array.argtypes = [vp, vp, u64, vp]
         L.bwts_debug_lyndon.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
         L.bwts_debug_chunk_plan.argtypes = [u64, u64, ctypes.POINTER(u64)]
@@ -886,6 +887,15 @@ class Context:
         v = np.ascontiguousarray(vals, dtype=np.uint32).copy()
         self._check(lib().bwts_debug_sort_pairs(self._h, k.ctypes.data, v.ctypes.data, k.size, int(key_bits)))
         return k, v
+
+    def debug_rank_steps(self, digits, valid, atomic_items):
+        """bwts_debug_rank_steps: (ranks[8][16][64] with 0xffffffff at invalid items, the passes' shipped atomic items)."""
+        d = np.ascontiguousarray(digits, dtype=np.uint8).reshape(8, 16, 64)
+        v = np.ascontiguousarray(valid, dtype=np.uint8).reshape(8, 16, 64)
+        ranks = np.empty((8, 16, 64), dtype=np.uint32)
+        shipped = np.zeros(4, dtype=np.uint32)
+        self._check(lib().bwts_debug_rank_steps(self._h, d.ctypes.data, v.ctypes.data, int(atomic_items), ranks.ctypes.data, shipped.ctypes.data))
+        return ranks, [int(k) for k in shipped]
 
     def debug_suffix_array(self, data):
         a = _u8(data)

@@ -82,6 +82,26 @@ extern "C" int bwts_debug_sort_pairs(bwts_ctx *ctx, uint64_t *h_keys, uint32_t *
     return BWTS_OK;
 }
 
+// the packed passes' ranking of one tile alone (radix.hip, rank_split): 8192 digits and validity bytes in, 8192 ranks out
+extern "C" int bwts_debug_rank_steps(bwts_ctx *ctx, const uint8_t *digits, const uint8_t *valid, int atomic_items, uint32_t *ranks,
+                                     uint32_t shipped[4])
+{
+    if (!ctx || !digits || !valid || !ranks || !shipped) return BWTS_E_ARG;
+    HIPC(hipSetDevice(ctx->device));
+    const size_t tile = 8192;
+    u8 *d_in = nullptr;
+    if (hipMalloc((void **)&d_in, 2 * tile + tile * sizeof(u32)) != hipSuccess) { (void)hipGetLastError(); return BWTS_E_NOMEM; }
+    u32 *d_ranks = (u32 *)(d_in + 2 * tile);
+    int rc = BWTS_OK;
+    if (hipMemcpyAsync(d_in, digits, tile, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(d_in + tile, valid, tile, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = BWTS_E_HIP;
+    if (rc == BWTS_OK) rc = radix_debug_rank_steps(ctx, d_in, d_in + tile, atomic_items, d_ranks, shipped);
+    if (rc == BWTS_OK && hipMemcpyAsync(ranks, d_ranks, tile * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = BWTS_E_HIP;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == BWTS_OK) rc = BWTS_E_HIP;
+    (void)hipFree(d_in);
+    return rc;
+}
+
 static int upload_text(bwts_ctx *ctx, const uint8_t *in, uint64_t n, u8 **d_T)
 {
     void *p = nullptr;

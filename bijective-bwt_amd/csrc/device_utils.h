@@ -118,7 +118,9 @@ __device__ __forceinline__ T block_scan_exclusive(T v, Op op, T identity, T *sme
 }
 
 // lanes of the wave whose 8-bit digit equals the caller's (restricted to `valid` lanes).
-// The radix kernels are VALU-bound and most of their VALU work is this function, so it is written for instruction
+// The radix kernels are VALU-bound, and in the kernels that rank every item with wave_rank_step (the wide passes, the small sort, the
+// LF kernels) most of their VALU work is this function -- 52 of a middle pass's 84 VALU instructions per item; the packed round-0
+// passes give some of a tile's items to the LDS atomic unit instead (wave_rank_atomic_step).  It is written for instruction
 // count: per digit bit, t = 0 / -1 from a sign-extended one-bit field, one compare for the ballot, and on each
 // 32-bit half an XNOR with the ballot (lanes whose bit equals mine) folded in with an AND -- six instructions.
 __device__ __forceinline__ u64 match_digit8(u32 digit, bool valid)
@@ -154,6 +156,25 @@ __device__ __forceinline__ void wave_rank_step(C *wave_hist, u32 d, bool valid, 
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 }
 
+// The same step on the other unit: one returning LDS add of 1 on the wave's u32 counter of the digit, no ballots -- 4 VALU
+// instructions an item where wave_rank_step takes 52, and the LDS atomic unit works while the VALU ranks other items.  Lanes with
+// one digit are served one by one, so a wave full of equal digits (sorted, repetitive keys) is where the ballot step is the
+// faster of the two.  Invalid lanes issue nothing.
+// Why the ranks are the ones wave_rank_step gives, so that a tile may rank any of its items with either step on the same
+// counters: (1) inside one instruction the lanes that add to the same address are served in lane order (a property of this
+// chip's LDS, pinned by tests/test_rank_atomic_gpu.py), so a lane gets the counter's value plus the number of lower lanes with its
+// digit -- prev + before; (2) a wave's LDS instructions execute in program order, so the counter holds the number of the wave's
+// elements with digit d in items 0 .. j-1 when item j's instruction -- atomic, or the read of a ballot step -- reaches it, and a
+// ballot step's plain write of prev + cnt is the value 64 atomic lanes would have left.  Both kinds of rank are therefore "the
+// wave's earlier elements with my digit, in element order", the ranking is stable, and the counter ends as the digit's count.
+// rank(r) is handed the returned register and nothing here reads it: a caller that only keeps it (no arithmetic on it inside
+// rank) lets the compiler issue the atomics of several items back to back and wait once, where they are first used.
+template <typename Rank>
+__device__ __forceinline__ void wave_rank_atomic_step(u32 *wave_cnt, u32 d, bool valid, Rank rank)
+{
+    if (valid) rank(__hip_atomic_fetch_add(&wave_cnt[d], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+}
+
 // After the ranking: thread d < 256 turns column d of the waves' counters into each wave's start inside the digit (exclusive, in
 // wave order), and the column totals are scanned over the workgroup.  Returns the calling thread's exclusive base: for d < 256 the
 // number of the tile's elements with a smaller digit.  Contains block_scan_exclusive's two barriers; the caller stores the base
@@ -178,15 +199,17 @@ __device__ __forceinline__ u32 digit_bases(C (*whist)[256], u32 *scan_sm)
 // The same, with the digit's base folded into the waves' starts: whist[ww][d] comes out as the first slot, in the tile, of wave ww's
 // elements with digit d, so a kernel that stages an item reads one word for it, not base and start.  The starts wait in registers
 // for the scan (the column is read once and written once, as above; the sums are those of the plain form, C holds them when it
-// holds a tile position).
+// holds a tile position).  The counts are read from cnt, which may be another array than whist (the u32 counters the atomic step
+// needs, in memory that is reused once the starts are out): every read of cnt lies before the scan's barriers, every write of
+// whist behind them, and all of whist is written.
 template <int NWAVES, typename C>
-__device__ __forceinline__ u32 digit_bases_folded(C (*whist)[256], u32 *scan_sm)
+__device__ __forceinline__ u32 digit_bases_folded(const u32 (*cnt)[256], C (*whist)[256], u32 *scan_sm)
 {
     const int tid = threadIdx.x;
     u32 start[NWAVES], run = 0;
     if (tid < 256) {
 #pragma unroll
-        for (int ww = 0; ww < NWAVES; ww++) start[ww] = whist[ww][tid];
+        for (int ww = 0; ww < NWAVES; ww++) start[ww] = cnt[ww][tid];
 #pragma unroll
         for (int ww = 0; ww < NWAVES; ww++) {
             const u32 c = start[ww];

@@ -14,7 +14,8 @@
 //   radix_scatter_lean_last_kernel  the last of five packed passes when few positions are expected to stay tied: the byte out,
 //                                 and the group flags of its own output instead of sorted keys and values; 7 bytes per element.
 // All are built from the same blocks: RxTile (the tile's place and its LDS), wave_rank_step and digit_bases / digit_bases_folded (device_utils.h),
-// Pos16; radix_hist_kernel<T> counts the digits of whichever stream holds them.
+// Pos16; radix_hist_kernel<T> counts the digits of whichever stream holds them.  The packed and the lean kernels rank part of a
+// thread's items with one returning LDS add each instead of the ballots (rank_split, wave_rank_atomic_step).
 #include "internal.h"
 #include "device_utils.h"
 #include "scan_templ.h"
@@ -145,6 +146,10 @@ struct RxTile {
     static constexpr size_t bytes_no_sdig = off_sdig;
     // TILE slots: the first stream (keys; the packed passes' u32 digit stream), then the others (values; uint2 pairs)
     static __device__ __forceinline__ u64 *stage(char *smem) { return (u64 *)smem; }
+    // WAVES x 256 u32 in the front of the stage area, which is idle until the first staging trip: the counters of a ranking that
+    // takes the atomic step (rank_split); digit_bases_folded reads them for the last time before the barriers of its scan
+    static_assert((size_t)WAVES * 256 * sizeof(u32) <= off_dbase, "the counters fit the stage area");
+    static __device__ __forceinline__ u32 (*cnt(char *smem))[256] { return (u32 (*)[256])smem; }
     // 256 each: the digit's first slot in the tile (not used where digit_bases_folded has put it into the waves' starts); its run's
     // global start minus that slot
     static __device__ __forceinline__ u32 *dbase(char *smem) { return (u32 *)(smem + off_dbase); }
@@ -182,6 +187,30 @@ struct Pos16 {
     // the first write of a pair: the even item sets the register, the odd one joins it
     __device__ __forceinline__ void init(int j, u32 v) { if (j & 1) p[j >> 1] |= v << 16; else p[j >> 1] = v; }
 };
+
+// The ranking of a packed tile, split between two units (device_utils.h): the wave's first K items take wave_rank_atomic_step, the
+// others wave_rank_step, in the order of j and on the same u32 counters, so the ranks are those of sixteen ballot steps.  The
+// atomics go out back to back -- their returns wait in ra[] -- and the LDS unit serves them while the VALU works on the
+// ballots of the items behind them.  digit(j), valid(j): item j's.  K is even: positions are packed in pairs.
+// K = 12 in every pass: measured over K = 0 .. 16 (profiles/history/rank_split.md).  All sixteen atomic is
+// faster still on random digits and loses 5 % of a middle pass on text, whose sorted keys put runs of one digit into a wave:
+// a same-address atomic serves its lanes one by one, the ballot step does not care.
+constexpr int RX_ATOMIC_FIRST = 12, RX_ATOMIC_MIDDLE = 12, RX_ATOMIC_LAST = 12, RX_ATOMIC_LEAN = 12;
+template <int K, typename D, typename V>
+__device__ __forceinline__ void rank_split(u32 *wave_cnt, Pos16<RX_ITEMS> &pos, D digit, V valid)
+{
+    static_assert(K >= 0 && K <= RX_ITEMS && K % 2 == 0, "whole pairs of items");
+    u32 ra[K ? K : 1];
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        ra[j] = 0;
+        wave_rank_atomic_step(wave_cnt, digit(j), valid(j), [&](u32 r) { ra[j] = r; });
+    }
+#pragma unroll
+    for (int j = K; j < RX_ITEMS; j++) wave_rank_step(wave_cnt, digit(j), valid(j), [&](u32 r) { pos.init(j, r); });
+#pragma unroll
+    for (int j = 0; j < K; j++) pos.init(j, ra[j]);
+}
 
 template <int TH, int IT, int MINW, bool HAS_SYM, bool IDENT, bool KEYS_ONLY = false>
 __global__ __launch_bounds__(TH, MINW) void radix_scatter2_kernel(const u64 *__restrict__ kin, const u32 *__restrict__ vin,
@@ -363,6 +392,7 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_packed_kern
     u64 *stage = L::stage(rx_smem);
     u32 *gbase = L::gbase(rx_smem), *scan_sm = L::scan_sm(rx_smem);
     u16 (*whist)[256] = L::whist(rx_smem);
+    u32 (*cnt)[256] = L::cnt(rx_smem);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const u64 tile = rx_tile_of_block((m + RX_TILE - 1) / RX_TILE);
     const u64 tile_base = tile * RX_TILE;
@@ -371,7 +401,7 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_packed_kern
     const u64 remain = m - tile_base;
     const u32 tile_count = remain < RX_TILE ? (u32)remain : (u32)RX_TILE;
 
-    for (int i = tid; i < RX_WAVES * 128; i += RX_THREADS) ((u32 *)whist)[i] = 0;
+    for (int i = tid; i < RX_WAVES * 256; i += RX_THREADS) ((u32 *)cnt)[i] = 0;
 
     // element j of this lane is i0 + 64 j; which of the sixteen exist is decided once (bit j of vmask), so that no
     // 64-bit index has to stay alive for the bounds checks further down
@@ -399,15 +429,11 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_packed_kern
 #define PK_DIGIT(j) (DIG_C ? (dsrc[j] & 255u) : ((dsrc[j] >> shift) & 255u))
     __syncthreads();
 
-#pragma unroll
-    for (int j = 0; j < RX_ITEMS; j++) {
-        const bool valid = PK_VALID(j);
-        const u32 d = PK_DIGIT(j);
-        wave_rank_step(whist[w], d, valid, [&](u32 r) { pos.init(j, r); });
-    }
+    rank_split<FIRST ? RX_ATOMIC_FIRST : LAST ? RX_ATOMIC_LAST : RX_ATOMIC_MIDDLE>(
+        cnt[w], pos, [&](int j) { return PK_DIGIT(j); }, [&](int j) { return (bool)PK_VALID(j); });
     __syncthreads();
     {
-        const u32 exc = digit_bases_folded<RX_WAVES>(whist, scan_sm);        // whist[w][d]: the slot of wave w's first element with digit d
+        const u32 exc = digit_bases_folded<RX_WAVES>(cnt, whist, scan_sm);   // whist[w][d]: the slot of wave w's first element with digit d
         if (tid < 256) gbase[tid] = tile_off[tile * 256 + tid] - exc;
     }
     __syncthreads();
@@ -572,6 +598,7 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_lean_last_k
     u32 *stage32 = (u32 *)L::stage(rx_smem);
     u32 *gbase = L::gbase(rx_smem), *scan_sm = L::scan_sm(rx_smem);
     u16 (*whist)[256] = L::whist(rx_smem);
+    u32 (*cnt)[256] = L::cnt(rx_smem);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const u64 tile = rx_tile_of_block((m + RX_TILE - 1) / RX_TILE);
     const u64 tile_base = tile * RX_TILE;
@@ -580,7 +607,7 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_lean_last_k
     const u64 remain = m - tile_base;
     const u32 tile_count = remain < RX_TILE ? (u32)remain : (u32)RX_TILE;
 
-    for (int i = tid; i < RX_WAVES * 128; i += RX_THREADS) ((u32 *)whist)[i] = 0;
+    for (int i = tid; i < RX_WAVES * 256; i += RX_THREADS) ((u32 *)cnt)[i] = 0;
 
     const u64 i0 = wave_base + (u64)lane;
     u32 vmask = 0;
@@ -609,14 +636,10 @@ __global__ __launch_bounds__(RX_THREADS, RX_MINW) void radix_scatter_lean_last_k
     }
     const u32 lo_first = io.lo_in[tile_base], lo_last = io.lo_in[tile_base + tile_count - 1];       // (uniform addresses: scalar loads)
     __syncthreads();
-#pragma unroll
-    for (int j = 0; j < RX_ITEMS; j++) {
-        const bool valid = PK_VALID(j);
-        wave_rank_step(whist[w], dsrc[j] & 255u, valid, [&](u32 r) { pos.init(j, r); });
-    }
+    rank_split<RX_ATOMIC_LEAN>(cnt[w], pos, [&](int j) { return dsrc[j] & 255u; }, [&](int j) { return (bool)PK_VALID(j); });
     __syncthreads();
     {
-        const u32 exc = digit_bases_folded<RX_WAVES>(whist, scan_sm);
+        const u32 exc = digit_bases_folded<RX_WAVES>(cnt, whist, scan_sm);
         if (tid < 256) gbase[tid] = tile_off[tile * 256 + tid] - exc;
     }
     __syncthreads();
@@ -1033,5 +1056,52 @@ int radix_sort_pairs(bwts_ctx *ctx, const SortPlan &plan, u64 m, int key_bits, i
         cur ^= 1;
     }
     *result_buf = cur;
+    return BWTS_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// test hook: the ranking of one tile alone (bwts_debug_rank_steps)
+// ------------------------------------------------------------------------------------
+// One workgroup ranks RX_TILE caller-given digits, item j of lane l of wave w at [w][j][l], with rank_split<K> on counters of its
+// own, and writes every valid item's rank among its wave's earlier elements with its digit (~0 for an invalid item).
+template <int K>
+__global__ __launch_bounds__(RX_THREADS) void rank_steps_kernel(const u8 *__restrict__ digits, const u8 *__restrict__ valid, u32 *__restrict__ ranks)
+{
+    __shared__ u32 cnt[RX_WAVES][256];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int i = tid; i < RX_WAVES * 256; i += RX_THREADS) ((u32 *)cnt)[i] = 0;
+    u32 d[RX_ITEMS], vmask = 0;
+#pragma unroll
+    for (int j = 0; j < RX_ITEMS; j++) {
+        const u32 i = ((u32)w * RX_ITEMS + (u32)j) * 64u + (u32)lane;
+        d[j] = digits[i];
+        vmask |= (valid[i] ? 1u : 0u) << j;
+    }
+    __syncthreads();
+    Pos16<RX_ITEMS> pos;
+    rank_split<K>(cnt[w], pos, [&](int j) { return d[j]; }, [&](int j) { return (bool)((vmask >> j) & 1u); });
+#pragma unroll
+    for (int j = 0; j < RX_ITEMS; j++)
+        ranks[((u32)w * RX_ITEMS + (u32)j) * 64u + (u32)lane] = (vmask >> j) & 1u ? pos.get(j) : ~0u;
+}
+
+int radix_debug_rank_steps(bwts_ctx *ctx, const u8 *d_digits, const u8 *d_valid, int atomic_items, u32 *d_ranks, u32 shipped[4])
+{
+    shipped[0] = RX_ATOMIC_FIRST; shipped[1] = RX_ATOMIC_MIDDLE; shipped[2] = RX_ATOMIC_LAST; shipped[3] = RX_ATOMIC_LEAN;
+    void (*kernel)(const u8 *, const u8 *, u32 *) = nullptr;
+    switch (atomic_items) {
+    case 0: kernel = rank_steps_kernel<0>; break;
+    case 2: kernel = rank_steps_kernel<2>; break;
+    case 4: kernel = rank_steps_kernel<4>; break;
+    case 6: kernel = rank_steps_kernel<6>; break;
+    case 8: kernel = rank_steps_kernel<8>; break;
+    case 10: kernel = rank_steps_kernel<10>; break;
+    case 12: kernel = rank_steps_kernel<12>; break;
+    case 14: kernel = rank_steps_kernel<14>; break;
+    case 16: kernel = rank_steps_kernel<16>; break;
+    default: return BWTS_E_ARG;
+    }
+    kernel<<<dim3(1), dim3(RX_THREADS), 0, ctx->stream>>>(d_digits, d_valid, d_ranks);
+    HIPC(hipGetLastError());
     return BWTS_OK;
 }

@@ -28,6 +28,13 @@ int bwts_device_equal(bwts_ctx *ctx, const void *d_a, const void *d_b, uint64_t 
  * value) pairs on the low key_bits bits; suffix array via the non-cyclic sort). */
 int bwts_debug_sort_pairs(bwts_ctx *ctx, uint64_t *h_keys, uint32_t *h_vals, uint64_t m, int key_bits);
 int bwts_debug_suffix_array(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint32_t *h_sa);
+/* The ranking of one tile of the packed round-0 radix passes alone, in one workgroup of 8 waves: 8192 digits and 8192 validity bytes
+ * (0: the item does not exist) in host memory, item j (0 .. 15) of lane l of wave w at [(w * 16 + j) * 64 + l].  A wave ranks its
+ * items in the order of j on one set of counters, the first atomic_items (even, 0 .. 16) of them with one returning LDS add each,
+ * the others by ballots.  ranks: every valid item's number of earlier (item, lane) pairs of its wave with its digit, ~0 for an
+ * invalid item.  shipped: the atomic_items of the first, middle, classic last and lean last pass as built.  BWTS_E_ARG for a NULL
+ * pointer or an atomic_items outside that set. */
+int bwts_debug_rank_steps(bwts_ctx *ctx, const uint8_t *digits, const uint8_t *valid, int atomic_items, uint32_t *ranks, uint32_t shipped[4]);
 int bwts_debug_lyndon(bwts_ctx *ctx, const uint8_t *in, uint64_t n, uint64_t *h_starts, uint64_t cap, uint64_t *count);
 /* Pure arithmetic, no context and no device: the chunk tables of the forward's later rounds for a tied list of a0 elements, and the
  * re-cut of the a_chunks <= a0 elements left at a compaction.  out = {nominal chunk size of a0, table capacity = a0 / 2048 + 128,

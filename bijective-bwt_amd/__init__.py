@@ -77,6 +77,7 @@ MEMBERS_EXPORTS = [
     "bwts_pack_members_f_device", "bwts_pack_members_f", "bwts_frame_members_f",
     "bwts_pack_members_bound_m", "bwts_pack_members_m_device", "bwts_pack_members_m", "bwts_frame_members_m",
     "bwts_members_estimate_device", "bwts_members_estimate", "bwts_pack_members_bound_a", "bwts_pack_members_a_device", "bwts_pack_members_a",
+    "bwts_gather_device", "bwts_scatter_device", "bwts_pack_members_p_device", "bwts_unpack_members_p_device",
 ]
 # ... include/bwts_delta.h (delta filter of integer arrays, the stage in front of the byte-plane split) ...
 DELTA_EXPORTS = [
@@ -280,6 +281,10 @@ def lib():
         L.bwts_pack_members_bound_a.restype = u64
         for name in ("bwts_pack_members_a_device", "bwts_pack_members_a"):
             getattr(L, name).argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, u64, ctypes.POINTER(u64), vp, vp]
+        L.bwts_gather_device.argtypes = [vp, vp, vp, u64, vp]
+        L.bwts_scatter_device.argtypes = [vp, vp, vp, vp, u64]
+        L.bwts_pack_members_p_device.argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, u64, ctypes.POINTER(u64), vp, vp]
+        L.bwts_unpack_members_p_device.argtypes = [vp, vp, u64, vp, u64, vp, vp]
         for name in ("bwts_delta_encode_device", "bwts_delta_decode_device", "bwts_delta_encode", "bwts_delta_decode"):
             getattr(L, name).argtypes = [vp, vp, u64, u32, vp]
         for name in ("bwts_delta_encode_segments_f_device", "bwts_delta_decode_segments_f_device"):
@@ -851,6 +856,97 @@ class Context:
                                                      int(out_cap), ctypes.byref(got)))
         return int(got.value)
 
+    # -- members where they lie: tables of device pointers (include/bwts_members.h, "Pointers") ---------
+    def gather_device(self, members, lengths, d_out):
+        """bwts_gather_device: member k, lengths[k] bytes at members[k] (an int address, a DeviceBuffer, or anything with data_ptr()),
+        to d_out, the members back to back."""
+        ls, _ = _members(lengths, None)
+        ps = _ptrs(members, ls.size)
+        self._check(lib().bwts_gather_device(self._h, ps.ctypes.data if ps.size else None, ls.ctypes.data if ls.size else None, ls.size, _ptr(d_out)))
+
+    def scatter_device(self, d_in, members, lengths):
+        """bwts_scatter_device: the members that lie back to back in d_in, each to members[k]."""
+        ls, _ = _members(lengths, None)
+        ps = _ptrs(members, ls.size)
+        self._check(lib().bwts_scatter_device(self._h, _ptr(d_in), ps.ctypes.data if ps.size else None, ls.ctypes.data if ls.size else None, ls.size))
+
+    def pack_members_ptrs_device(self, members, lengths, widths, d_out, out_cap, filters=FILTER_AUTO, methods=METHOD_AUTO):
+        """bwts_pack_members_p_device: pack_members_auto_device over members where they lie: (the frame's size in bytes, the resolved
+        filters, the resolved methods).  The frame is what pack_members_auto_device writes for the same members back to back."""
+        ls, ws = _members(lengths, widths)
+        ps = _ptrs(members, ls.size)
+        fs, ms = _per_member(ls, filters, "filter"), _per_member(ls, methods, "method")
+        fo, mo = np.zeros(ls.size, dtype=np.uint32), np.zeros(ls.size, dtype=np.uint32)
+        got = ctypes.c_uint64(0)
+        self._check(lib().bwts_pack_members_p_device(self._h, ps.ctypes.data if ps.size else None, ls.ctypes.data if ls.size else None,
+                                                     None if ws is None else ws.ctypes.data, fs.ctypes.data, ms.ctypes.data, ls.size, _ptr(d_out), int(out_cap),
+                                                     ctypes.byref(got), fo.ctypes.data, mo.ctypes.data))
+        return int(got.value), fo.tolist(), mo.tolist()
+
+    def unpack_members_ptrs_device(self, d_in, in_bytes, indices, members, dst_bytes):
+        """bwts_unpack_members_p_device: member indices[j] of the frame to members[j], of which dst_bytes[j] bytes may be written (only
+        the member's own are); indices None: every member in order."""
+        room = np.ascontiguousarray(dst_bytes, dtype=np.uint64).reshape(-1)
+        ps = _ptrs(members, room.size)
+        idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        if idx is not None and idx.size != room.size:
+            raise BwtsError(-1, "one destination per index")
+        self._check(lib().bwts_unpack_members_p_device(self._h, _ptr(d_in), int(in_bytes), None if idx is None or not idx.size else idx.ctypes.data, room.size,
+                                                       ps.ctypes.data if ps.size else None, room.ctypes.data if room.size else None))
+
+    def pack_tensors(self, tensors, widths=None, filters=FILTER_AUTO, methods=METHOD_AUTO, frame_bytes=1 << 32):
+        """A set of device tensors of any sizes as member frames: the set is cut by tensor_frames(sizes, frame_bytes), and every frame
+        of the cut is one pack_members_ptrs_device over its pieces where they lie (data_ptr() + offset); returns the frames, one numpy
+        uint8 array each, which every reader of member frames takes.  A tensor is anything with data_ptr(), element_size(), numel()
+        and is_contiguous(); one that is not contiguous is refused.  widths None takes every tensor's element_size() where that is 1,
+        2, 4 or 8, and 1 otherwise: the caller's own dtype, not a guess from the bytes.  filters and methods: a scalar, or one value
+        per tensor, carried to all of a tensor's pieces.  One frame buffer on the device, sized for the largest bound, serves all frames."""
+        tensors = list(tensors)
+        for t in tensors:
+            if not t.is_contiguous():
+                raise BwtsError(-1, "a tensor that is not contiguous")
+        sizes = [int(t.numel()) * int(t.element_size()) for t in tensors]
+        ls = np.asarray(sizes, dtype=np.uint64)
+        if widths is None:
+            widths = [int(t.element_size()) if int(t.element_size()) in (1, 2, 4, 8) else 1 for t in tensors]
+        _, ws = _members(ls, widths)
+        fs, ms = _per_member(ls, filters, "filter"), _per_member(ls, methods, "method")
+        cut = tensor_frames(sizes, frame_bytes)
+        sets = [([tensors[k].data_ptr() + off for k, off, _ in fr], [b for _, _, b in fr], [int(ws[k]) for k, _, _ in fr], [int(fs[k]) for k, _, _ in fr],
+                 [int(ms[k]) for k, _, _ in fr]) for fr in cut]
+        if not sets:
+            return []
+        cap = max(pack_members_bound_auto(s[1], s[2], s[4]) for s in sets)
+        buf = self.alloc(cap)
+        try:
+            frames = []
+            for ptrs, lens, w, f, m in sets:
+                got, _, _ = self.pack_members_ptrs_device(ptrs, lens, w, buf, cap, f, m)
+                frames.append(buf.download(got))
+            return frames
+        finally:
+            buf.free()
+
+    def unpack_tensors(self, frames, tensors):
+        """What pack_tensors made, decoded in place: the frames' own directories (frame_members) are walked against the tensors in
+        order, so frame_bytes need not be known.  Every member must lie inside the current tensor's remaining bytes and the members
+        must tile the tensors exactly, else BwtsError(-1) before any device call."""
+        tensors = list(tensors)
+        for t in tensors:
+            if not t.is_contiguous():
+                raise BwtsError(-1, "a tensor that is not contiguous")
+        frames = [_u8(f) for f in frames]
+        places = tensor_places([frame_members(f)[0] for f in frames], [int(t.numel()) * int(t.element_size()) for t in tensors])
+        if not frames:
+            return
+        buf = self.alloc(max(f.size for f in frames))
+        try:
+            for f, pl in zip(frames, places):
+                buf.upload(f)
+                self.unpack_members_ptrs_device(buf, f.size, None, [tensors[k].data_ptr() + off for k, off, _ in pl], [b for _, _, b in pl])
+        finally:
+            buf.free()
+
     def debug_copy_pieces(self, d_src, src_bytes, pieces, d_dst, dst_bytes):
         """bwts_debug_copy_pieces: copy_pieces_kernel alone over (src offset, dst offset, bytes) triples."""
         ps = np.ascontiguousarray(pieces, dtype=np.uint64).reshape(-1, 3)
@@ -1247,6 +1343,79 @@ def frame_member_methods(frame):
     if rc != 0:
         raise BwtsError(rc, lib().bwts_strerror(rc).decode())
     return ms.tolist()
+
+
+MAX_MEMBERS = 1 << 20           # the most members of one frame (include/bwts_members.h)
+
+
+def _ptrs(members, count):
+    """Members where they lie, as the uint64 array that is a table of device pointers: int addresses, DeviceBuffers, or anything with data_ptr()."""
+    ps = np.asarray([_ptr(m) for m in members], dtype=np.uint64).reshape(-1)
+    if ps.size != count:
+        raise BwtsError(-1, "one pointer per member")
+    return ps
+
+
+def tensor_frames(lengths, frame_bytes=1 << 32):
+    """The cut of a set of tensors of these byte lengths into member frames, as pure arithmetic: a list of frames, each a list of
+    (tensor index, byte offset, bytes) in order.  A zero-length tensor is in no frame.  A tensor of at most frame_bytes bytes joins the
+    current frame if the frame's sum stays <= frame_bytes and its member count <= 2^20, else it opens a new one.  A longer tensor
+    closes the current frame and is cut into pieces of frame_bytes rounded down to a multiple of 8, each a frame of its own; the
+    last, shorter piece opens a frame that later tensors may join."""
+    fb = int(frame_bytes)
+    if fb < 8 or fb > 1 << 32:
+        raise BwtsError(-1, "frame_bytes outside [8, 2^32]")
+    piece = fb // 8 * 8
+    frames, cur, total = [], [], 0
+    for k, n in enumerate(lengths):
+        n = int(n)
+        if n < 0:
+            raise BwtsError(-1, "a negative length")
+        if n == 0:
+            continue
+        if n > fb:
+            if cur:
+                frames.append(cur)
+            cur, total, at = [], 0, 0
+            while n - at > piece:
+                frames.append([(k, at, piece)])
+                at += piece
+            cur, total = [(k, at, n - at)], n - at
+            continue
+        if cur and (total + n > fb or len(cur) >= MAX_MEMBERS):
+            frames.append(cur)
+            cur, total = [], 0
+        cur.append((k, 0, n))
+        total += n
+    if cur:
+        frames.append(cur)
+    return frames
+
+
+def tensor_places(frame_lengths, tensor_bytes):
+    """The members of frames (frame_lengths: a list of member lengths per frame) laid over tensors of tensor_bytes bytes in order: per
+    frame a list of (tensor index, byte offset, bytes).  BwtsError(-1) unless every member lies inside the current tensor's remaining
+    bytes and the members tile the tensors exactly (zero-length tensors are passed over)."""
+    k, at, out = 0, 0, []
+    sizes = [int(b) for b in tensor_bytes]
+    for lens in frame_lengths:
+        places = []
+        for n in lens:
+            n = int(n)
+            while k < len(sizes) and at == sizes[k]:
+                k, at = k + 1, 0
+            if k == len(sizes):
+                raise BwtsError(-1, "more members than the tensors hold")
+            if n > sizes[k] - at:
+                raise BwtsError(-1, "a member of %d bytes straddles the end of tensor %d" % (n, k))
+            places.append((k, at, n))
+            at += n
+        out.append(places)
+    while k < len(sizes) and at == sizes[k]:
+        k, at = k + 1, 0
+    if k != len(sizes):
+        raise BwtsError(-1, "the members end inside tensor %d" % k)
+    return out
 
 
 def _ranges(ranges):

@@ -1064,6 +1064,92 @@ extern "C" int bwts_unpack_members(bwts_ctx *ctx, const uint8_t *in, uint64_t in
     return unpack_ranges_host(ctx, in, in_bytes, nullptr, indices, icount, out, out_cap, out_bytes, true);
 }
 
+// ---- scattered members (include/bwts_members.h, "Pointers"): the copy kernel between scattered buffers as calls of its own, and
+// ---- the member calls over tables of device pointers
+// the scattered side of a call, ptrs[k] of lengths[k] >= 1 bytes, against its contiguous side [d_flat, d_flat + flat_bytes): no entry
+// NULL, none that shares a byte with the contiguous side, and, where the scattered side is written, no two that share a byte
+static int member_ptrs_check(const void *const *ptrs, const uint64_t *lengths, uint64_t count, const void *d_flat, u64 flat_bytes, bool written)
+{
+    if (!ptrs) return BWTS_E_ARG;
+    for (u64 k = 0; k < count; k++)
+        if (!ptrs[k]) return BWTS_E_ARG;
+    std::vector<std::pair<u64, u64>> spans((size_t)count);
+    for (u64 k = 0; k < count; k++) {
+        if (ranges_overlap(d_flat, flat_bytes, ptrs[k], lengths[k])) return BWTS_E_ARG;
+        spans[(size_t)k] = {(u64)(uintptr_t)ptrs[k], lengths[k]};
+    }
+    return !written || spans_disjoint(spans) ? BWTS_OK : BWTS_E_ARG;
+}
+
+// the members' pieces with the contiguous side at d_flat, members back to back
+static std::vector<PackPiece> member_pieces(const void *const *ptrs, const uint64_t *lengths, uint64_t count, const void *d_flat, bool gather)
+{
+    std::vector<PackPiece> ps((size_t)count);
+    u64 at = (u64)(uintptr_t)d_flat;
+    for (u64 k = 0; k < count; k++) {
+        const u64 m = (u64)(uintptr_t)ptrs[k];
+        ps[(size_t)k] = gather ? PackPiece{m, at, lengths[k]} : PackPiece{at, m, lengths[k]};
+        at += lengths[k];
+    }
+    return ps;
+}
+
+extern "C" int bwts_gather_device(bwts_ctx *ctx, const void *const *d_srcs, const uint64_t *lengths, uint64_t count, void *d_out)
+{
+    if (!ctx || !d_out) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(members_args_check(lengths, nullptr, count, &n));
+    BWTS_TRY(member_ptrs_check(d_srcs, lengths, count, d_out, n, false));
+    const std::vector<PackPiece> ps = member_pieces(d_srcs, lengths, count, d_out, true);
+    return run_sized(ctx, n, "gather", [&] { return scatter_pieces_impl(ctx, ps.data(), count); });
+}
+
+extern "C" int bwts_scatter_device(bwts_ctx *ctx, const void *d_in, void *const *d_dsts, const uint64_t *lengths, uint64_t count)
+{
+    if (!ctx || !d_in) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(members_args_check(lengths, nullptr, count, &n));
+    BWTS_TRY(member_ptrs_check(d_dsts, lengths, count, d_in, n, true));
+    const std::vector<PackPiece> ps = member_pieces(d_dsts, lengths, count, d_in, false);
+    return run_sized(ctx, n, "scatter", [&] { return scatter_pieces_impl(ctx, ps.data(), count); });
+}
+
+// A set that lies back to back already is the contiguous call's input as it is; any other is gathered into the block the context keeps
+// for it, and packed from there.
+extern "C" int bwts_pack_members_p_device(bwts_ctx *ctx, const void *const *d_members, const uint64_t *lengths, const uint32_t *widths,
+                                          const uint32_t *filters, const uint32_t *methods, uint64_t count, void *d_out, uint64_t out_cap,
+                                          uint64_t *out_bytes, uint32_t *filters_out, uint32_t *methods_out)
+{
+    if (!ctx || !d_out || !out_bytes || ((uintptr_t)d_out & 15)) return BWTS_E_ARG;
+    u64 n = 0;
+    BWTS_TRY(members_args_check_a(lengths, widths, filters, methods, count, &n));
+    BWTS_TRY(member_ptrs_check(d_members, lengths, count, d_out, out_cap, false));
+    bool flat = true;
+    for (u64 k = 0; k + 1 < count && flat; k++) flat = (const u8 *)d_members[k + 1] == (const u8 *)d_members[k] + lengths[k];
+    return run_sized(ctx, n, "pack members", [&] {
+        const u8 *d_in = (const u8 *)d_members[0];
+        if (!flat) {
+            BWTS_TRY(kept_grow(ctx, ctx->kept[KB_MEMBER_SET], n, 1 << 16, -1));
+            u8 *set = (u8 *)ctx->kept[KB_MEMBER_SET].p;
+            const std::vector<PackPiece> ps = member_pieces(d_members, lengths, count, set, true);
+            BWTS_TRY(scatter_pieces_impl(ctx, ps.data(), count));
+            d_in = set;
+        }
+        return pack_members_auto_device_impl(ctx, d_in, lengths, widths, filters, methods, count, n, (u8 *)d_out, out_cap, out_bytes, filters_out, methods_out);
+    });
+}
+
+extern "C" int bwts_unpack_members_p_device(bwts_ctx *ctx, const void *d_in, uint64_t in_bytes, const uint64_t *indices, uint64_t icount,
+                                            void *const *d_dsts, const uint64_t *dst_bytes)
+{
+    if (!ctx || !d_in || in_bytes == 0 || ((uintptr_t)d_in & 15)) return BWTS_E_ARG;
+    const MemberDsts dsts = {d_dsts, dst_bytes};
+    u64 made = 0;
+    return run_sized(ctx, 0, "unpack members", [&] {
+        return unpack_ranges_device_impl(ctx, (const u8 *)d_in, in_bytes, false, nullptr, icount, nullptr, ~0ull, &made, indices, &dsts);
+    });
+}
+
 // copy_pieces_kernel alone (include/bwts_test.h; here for the call bracket): refuses, before anything is launched, what the driver's
 // plan cannot make -- a piece that leaves either buffer, or two that share a destination byte
 extern "C" int bwts_debug_copy_pieces(bwts_ctx *ctx, const void *d_src, uint64_t src_bytes, const uint64_t *pieces, uint64_t count, void *d_dst,

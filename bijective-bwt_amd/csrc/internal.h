@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <assert.h>
+#include <algorithm>
+#include <utility>
 #include <string>
 #include <vector>
 #include <functional>
@@ -41,7 +43,7 @@ enum SegReportWord { SR_PLAN, SR_BIG, SR_RUNS, SR_OWN_SEGS, SR_OWN_BYTES, SR_SIN
 // bwts_ctx_destroy (ctx_memory.hip).  name: what the allocation trace and the guard report call it.
 struct KeptBlock { char *p; size_t cap; const char *name; };
 // every kept block of a context, in bwts_ctx::kept
-enum { KB_ARENA, KB_AUX, KB_IO = KB_AUX + BWTS_AUX_SLOTS, KB_SEG_TABLE = KB_IO + 4, KB_SEG_SCRATCH, KB_PACK, KB_COUNT = KB_PACK + 3 };
+enum { KB_ARENA, KB_AUX, KB_IO = KB_AUX + BWTS_AUX_SLOTS, KB_SEG_TABLE = KB_IO + 4, KB_SEG_SCRATCH, KB_PACK, KB_MEMBER_SET = KB_PACK + 3, KB_COUNT };
 
 #define SM_RX_SYNC 4090          // d_small word holding the two 32-bit counters of radix_column_scan_fused_kernel (zero between launches)
 #define SM_EC_TOTAL 4020         // entropy coder (ec.hip): d_small word for the bytes of all payloads of an encode
@@ -73,14 +75,16 @@ struct bwts_ctx {
     // (What the headline path does not touch is not allocated: the driver clears device memory it hands out, ~27 ms per GiB.)
     // KB_IO + i: the host-buffer entry points' device-side in/out buffers (below).  KB_SEG_TABLE: the device copy of the segment table.
     // KB_SEG_SCRATCH: segmented forward: factor-start flags.  KB_PACK + 0, 1: pack / unpack: the bytes between two stages of the chain; + 2: a pack
-    // that chooses methods: both candidates' streams.
+    // that chooses methods: both candidates' streams.  KB_MEMBER_SET: a pack of scattered members (bwts_pack_members_p_device): the members
+    // gathered back to back.
     KeptBlock kept[KB_COUNT] = {{nullptr, 0, "arena"},
                                 {nullptr, 0, "side block 0"}, {nullptr, 0, "side block 1"}, {nullptr, 0, "side block 2"},
                                 {nullptr, 0, "side block 3"}, {nullptr, 0, "side block 4"},
                                 {nullptr, 0, "device input 0"}, {nullptr, 0, "device input 1"},
                                 {nullptr, 0, "device output 0"}, {nullptr, 0, "device output 1"},
                                 {nullptr, 0, "segment table"}, {nullptr, 0, "segment scratch"},
-                                {nullptr, 0, "pack stage 0"}, {nullptr, 0, "pack stage 1"}, {nullptr, 0, "pack candidates"}};
+                                {nullptr, 0, "pack stage 0"}, {nullptr, 0, "pack stage 1"}, {nullptr, 0, "pack candidates"},
+                                {nullptr, 0, "member set"}};
     size_t arena_off;
     size_t unv_hint;       // inverse: unreached elements seen by the previous call (sizes the first collection pass)
     // inverse: one record per attempt of the most recent call, from values its stages hold on the host anyway (a few stores per
@@ -172,6 +176,15 @@ static inline bool ranges_overlap(const void *a, u64 na, const void *b, u64 nb)
 {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x <= y ? y - x < na : x - y < nb;
+}
+
+// do no two of the spans (address, bytes >= 1) share a byte?  Sorts them.  An address space ends below 2^64: no sum wraps for spans that exist
+static inline bool spans_disjoint(std::vector<std::pair<u64, u64>> &spans)
+{
+    std::sort(spans.begin(), spans.end());
+    for (size_t i = 1; i < spans.size(); i++)
+        if (spans[i].first - spans[i - 1].first < spans[i - 1].second) return false;
+    return true;
 }
 
 // ---- the call bracket and the transform table (api.hip) ---------------------------
@@ -368,9 +381,10 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
 // streams alone, back to back (the host form); in_bytes stays the whole frame's length
 struct PackRange;
 struct PackPiece;
+struct MemberDsts;
 // indices: not null for whole members of a member frame as the ranges (ranges is then not read; count indices)
 int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool packed, const PackRange *ranges, u64 count, u8 *d_out, u64 out_cap, u64 *out_bytes,
-                              const u64 *indices = nullptr);
+                              const u64 *indices = nullptr, const MemberDsts *ptrs = nullptr);
 // the member frame (include/bwts_members.h); lengths, widths, filters (null: none) and methods (null: the whole chain) have passed
 // members_args_check_m, n is the lengths' sum
 int pack_members_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *lengths, const u32 *widths, const u32 *filters, const u32 *methods, u64 count, u64 n,
@@ -381,6 +395,10 @@ int pack_members_auto_device_impl(bwts_ctx *ctx, const u8 *d_in, const u64 *leng
                                   u8 *d_out, u64 out_cap, u64 *out_bytes, u32 *filters_out, u32 *methods_out);
 // pieces of one device buffer to another, at any alignment (pieces.hip); every piece inside both buffers, by the caller's check
 int copy_pieces_impl(bwts_ctx *ctx, const u8 *d_src, u64 src_bytes, const PackPiece *pieces, u64 count, u8 *d_dst);
+// the same between scattered buffers: src and dst of a piece are absolute device addresses, and every piece is a buffer of its own
+int scatter_pieces_impl(bwts_ctx *ctx, const PackPiece *pieces, u64 count);
+// the destinations of bwts_unpack_members_p_device: one per index, with its room
+struct MemberDsts { void *const *dsts; const u64 *dst_bytes; };
 
 // chunk tables of the forward's later rounds (chunk_rounds.h) as plain arithmetic: nominal chunk size of a list, the tables' capacity
 // for a tied list of a0 (which holds every run: the derivation stands at chunk_table_capacity), and the re-cut of the a_chunks elements

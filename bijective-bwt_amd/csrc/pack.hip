@@ -760,12 +760,31 @@ int unpack_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, u8 *d_out, u
     return BWTS_OK;
 }
 
+// The destinations of bwts_unpack_members_p_device against the members asked for (r: one per destination): a NULL table or entry,
+// then room, then two destinations that share a byte or one that overlaps the frame -- only the member's bytes of a destination count.
+static int member_dsts_check(const MemberDsts &D, const PackRange *r, u64 count, const u8 *d_in, u64 in_bytes)
+{
+    if (!D.dsts || !D.dst_bytes) return BWTS_E_ARG;
+    for (u64 j = 0; j < count; j++)
+        if (!D.dsts[j]) return BWTS_E_ARG;
+    for (u64 j = 0; j < count; j++)
+        if (D.dst_bytes[j] < r[j].bytes) return BWTS_E_SPACE;
+    std::vector<std::pair<u64, u64>> spans((size_t)count);
+    for (u64 j = 0; j < count; j++) {
+        if (ranges_overlap(d_in, in_bytes, D.dsts[j], r[j].bytes)) return BWTS_E_ARG;
+        spans[(size_t)j] = {(u64)(uintptr_t)D.dsts[j], r[j].bytes};
+    }
+    return spans_disjoint(spans) ? BWTS_OK : BWTS_E_ARG;
+}
+
 // Ranges of a frame (include/bwts_pack.h, "Ranges"): the frame is judged as above, then the ranges; the plan names the covered blocks,
 // and only their streams are decoded, over a segment table of the covered blocks alone.  The bytes go to and fro between the two
 // stage blocks (neither is d_out here); only when the covered blocks' checksums agree are the ranges cut out of the last stage's
 // block into d_out.
+// With ptrs (bwts_unpack_members_p_device: whole members, each into a buffer of its own) the cut is pieces.hip's copy between scattered
+// buffers, d_out is not read, and the destinations are judged behind the frame and the indices (include/bwts_members.h, "Pointers").
 int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool packed, const PackRange *ranges, u64 count, u8 *d_out, u64 out_cap, u64 *out_bytes,
-                              const u64 *indices)
+                              const u64 *indices, const MemberDsts *ptrs)
 {
     u64 *rep = ctx->ranges_report;
     memset(rep, 0, sizeof ctx->ranges_report);
@@ -774,12 +793,22 @@ int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool 
     u64 sum = 0;
     // whole members as ranges (bwts_unpack_members_device): a member frame alone has them
     std::vector<PackRange> whole;
+    std::vector<u64> all;
+    if (ptrs && !indices) {
+        // every member in order: the count must be the frame's
+        if (!F.members) return BWTS_E_FORMAT;
+        if (count != F.count) return BWTS_E_ARG;
+        all.resize((size_t)count);
+        for (u64 k = 0; k < count; k++) all[(size_t)k] = k;
+        indices = all.data();
+    }
     if (indices) {
         if (!F.members) return BWTS_E_FORMAT;
         BWTS_TRY(members_index_ranges(F, indices, count, &whole));
         ranges = whole.data();
     }
     BWTS_TRY(pack_ranges_check(F.n, ranges, count, out_cap, &sum));
+    if (ptrs) BWTS_TRY(member_dsts_check(*ptrs, ranges, count, d_in, in_bytes));
     PackRangesPlan P;
     ranges_plan(F, ranges, count, &P);
     const DecodeSet S = decode_set(F, &P.blocks);
@@ -804,7 +833,14 @@ int unpack_ranges_device_impl(bwts_ctx *ctx, const u8 *d_in, u64 in_bytes, bool 
         std::swap(to, other);
     }
     BWTS_TRY(decode_chain(ctx, S, from, to, other, &rep[6]));
-    BWTS_TRY(copy_pieces_impl(ctx, from, C, P.out.data(), P.out.size(), d_out));
+    if (ptrs) {
+        // (one piece per range, in the ranges' order: its place in the covered bytes to the destination that asked for it)
+        std::vector<PackPiece> apart(P.out);
+        for (size_t j = 0; j < apart.size(); j++) apart[j] = PackPiece{(u64)(uintptr_t)from + P.out[j].src, (u64)(uintptr_t)ptrs->dsts[j], P.out[j].bytes};
+        BWTS_TRY(scatter_pieces_impl(ctx, apart.data(), apart.size()));
+    } else {
+        BWTS_TRY(copy_pieces_impl(ctx, from, C, P.out.data(), P.out.size(), d_out));
+    }
     rep[6] |= RG_CUT;
     *out_bytes = sum;
     return BWTS_OK;

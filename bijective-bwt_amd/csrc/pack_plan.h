@@ -226,6 +226,50 @@ EC_HD uint64_t pieces_tiles(uint64_t bytes, uint64_t lead)
     return bytes <= f ? 1u : 1u + ((bytes - f + PIECES_T - 1u) >> PIECES_LOG_T);
 }
 
+// tile j of a piece of `bytes` bytes whose destination begins `lead` bytes into a line: where it begins in the piece, and its bytes
+EC_HD uint32_t pieces_tile_at(uint64_t bytes, uint64_t lead, uint64_t j, uint64_t *at)
+{
+    const uint64_t f = pieces_first_bytes(lead);
+    *at = j ? f + ((j - 1u) << PIECES_LOG_T) : 0u;
+    const uint64_t left = bytes - *at, most = j ? (uint64_t)PIECES_T : f;
+    return (uint32_t)(left < most ? left : most);
+}
+
+// scatter_pieces_kernel (pieces.hip) copies between buffers of which every piece is one of its own: the readable bytes of a piece are
+// [ps, pe) and nothing else.  A tile of len bytes at source address s and destination address d is stored as copy_pieces_kernel stores
+// it: `head` single bytes up to the destination's next 16-byte boundary, `vecs` aligned 16-byte stores, single bytes for the rest.
+// Store v is put together from the aligned 16-byte source pieces at a + 16 v and, where sh != 0, a + 16 v + 16, a = s + head - sh.
+// Those pieces lie inside the tile's own piece for every store but, at most, the first (a < ps) and the last (a + 16 vecs + 16 > pe,
+// with sh != 0): stores [v_lo, v_hi) are made from aligned pieces, stores [0, v_lo) and [v_hi, vecs) in single bytes, and
+// v_lo <= 1, vecs - v_hi <= 1.  A tile inside its piece, with bytes of the piece on both sides, loses nothing.
+struct ScatterTile { uint32_t head, vecs, sh, v_lo, v_hi; };
+EC_HD ScatterTile scatter_tile_plan(uint64_t s, uint64_t d, uint32_t len, uint64_t ps, uint64_t pe)
+{
+    ScatterTile t;
+    t.head = (16u - (uint32_t)(d & 15u)) & 15u;
+    if (t.head > len) t.head = len;
+    t.vecs = (len - t.head) / 16u;
+    t.sh = (uint32_t)((s + t.head) & 15u);
+    const uint64_t a = s + t.head - t.sh;
+    t.v_lo = t.vecs && a < ps ? 1u : 0u;
+    t.v_hi = t.vecs - (t.vecs && t.sh && a + 16u * ((uint64_t)t.vecs + 1u) > pe ? 1u : 0u);
+    if (t.v_hi < t.v_lo) t.v_hi = t.v_lo;
+    return t;
+}
+// The single bytes of such a tile, one per lane of the workgroup's first wave: lanes 0 .. 15 the head, 16 .. 31 what is left behind the
+// last store, 32 .. 47 store 0 where it is below v_lo, 48 .. 63 store vecs - 1 where it is not below v_hi.  *i: the byte's place in the tile.
+EC_HD bool scatter_edge_byte(const ScatterTile &t, uint32_t len, uint32_t lane, uint32_t *i)
+{
+    const uint32_t k = lane & 15u, done = t.head + 16u * t.vecs;
+    switch (lane >> 4) {
+    case 0: *i = k; return k < t.head;
+    case 1: *i = done + k; return k < len - done;
+    case 2: *i = t.head + k; return t.v_lo != 0u;
+    case 3: *i = t.head + 16u * t.v_hi + k; return t.v_hi < t.vecs;
+    default: return false;
+    }
+}
+
 struct PackRange { uint64_t offset, bytes; };           // bwts_range: bytes [offset, offset + bytes) of the unpacked input
 struct PackPiece { uint64_t src, dst, bytes; };         // bytes [src, src + bytes) of one buffer to [dst, dst + bytes) of another
 struct PackRun { uint64_t first, blocks; };             // blocks [first, first + blocks) of the frame

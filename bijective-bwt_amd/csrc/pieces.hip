@@ -113,6 +113,60 @@ __global__ __launch_bounds__(256, 8) void copy_pieces_kernel(const u8 *__restric
     }
 }
 
+// The piece of tile t, as the bisection above finds it, by sections of 64: every lane of a wave reads one of 64 evenly spaced first
+// tiles of the range, and a ballot says in which 64th t lies.  Two dependent reads for 4096 pieces where the bisection makes twelve: a
+// workgroup has nothing else in flight while it looks for its tile's piece, and with a shifted source those reads showed in the time
+// of the whole copy.  Every wave of the workgroup finds the same piece for itself; nothing is shared.
+__device__ __forceinline__ u64 pieces_find(const u64 *__restrict__ first, u64 count, u64 t)
+{
+    const u32 lane = threadIdx.x & 63u;
+    u64 lo = 0, hi = count;         // first[lo] <= t < first[hi]
+    while (hi - lo > 1) {
+        const u64 step = (hi - lo + 63u) >> 6;
+        const u64 i = lo + lane * step;
+        const bool below = i < hi && first[i] <= t;
+        const u32 k = (u32)__popcll(__ballot(below));       // the lanes below are a prefix of the wave, lane 0 among them
+        lo += (u64)(k - 1u) * step;
+        hi = lo + step < hi ? lo + step : hi;
+    }
+    return lo;
+}
+
+// scatter_pieces_kernel: the same copy between buffers of which every piece is one of its own (include/bwts_members.h, "Pointers";
+// DESIGN section 23): P.src and P.dst hold absolute device addresses, and the readable bytes of a piece are its own and nothing
+// else.  Tile cut and stores are those above; the tile's piece is found by pieces_find.  The guard of the aligned over-read is the piece's, not a buffer's, and it
+// costs a store, not the tile (pack_plan.h, scatter_tile_plan): the first store of a tile where its lower aligned source piece begins
+// in front of the piece, and the last one where its upper piece ends behind it, are made of single bytes by lanes 32 .. 63, which
+// read and write them with the head and tail bytes of lanes 0 .. 31.  A tile that has bytes of its piece on both sides loses nothing.
+__global__ __launch_bounds__(256, 8) void scatter_pieces_kernel(PiecesTable P)
+{
+    const u32 tid = threadIdx.x;
+    for (u64 t = blockIdx.x; t < P.tiles; t += gridDim.x) {
+        u64 first = 0;
+        PackPiece p = P.one;
+        if (P.count > 1) {
+            const u64 lo = pieces_find(P.first, P.count, t);
+            first = P.first[lo];
+            p = PackPiece{P.src[lo], P.dst[lo], P.bytes[lo]};
+        }
+        u64 at = 0;
+        const u32 len = pieces_tile_at(p.bytes, p.dst & (PIECES_LINE - 1u), t - first, &at);
+        const ScatterTile k = scatter_tile_plan(p.src + at, p.dst + at, len, p.src, p.src + p.bytes);
+        const u8 *s = (const u8 *)(uintptr_t)(p.src + at);
+        u8 *d = (u8 *)(uintptr_t)(p.dst + at);
+        // the single bytes: read first and written last, so that the wait for them is not in front of the tile's loads
+        u32 ei = 0;
+        const bool edge = tid < 64u && scatter_edge_byte(k, len, tid, &ei);
+        u8 eb = 0;
+        if (edge) eb = s[ei];
+        const uint4 *av = (const uint4 *)(s + k.head - k.sh) + k.v_lo;
+        uint4 *dv = (uint4 *)(d + k.head) + k.v_lo;
+        if (k.sh) pieces_stores<2, true>(av, dv, k.v_hi - k.v_lo, k.sh);
+        else pieces_stores<4, false>(av, dv, k.v_hi - k.v_lo, 0);
+        if (edge) d[ei] = eb;
+    }
+}
+
 // ------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------
@@ -144,6 +198,38 @@ int copy_pieces_impl(bwts_ctx *ctx, const u8 *d_src, u64 src_bytes, const PackPi
     {
         SpanGuard sp(ctx, BWTS_K_OTHER, total, 2 * total);
         copy_pieces_kernel<<<dim3((unsigned)(tiles < PIECES_GRID ? tiles : PIECES_GRID)), dim3(256), 0, ctx->stream>>>(d_src, src_bytes, P, d_dst);
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(ctx->stream));
+    return BWTS_OK;
+}
+
+// The same for scatter_pieces_kernel: src and dst of a piece are absolute device addresses, every piece a buffer of its own (the
+// callers have seen to it that no destination shares a byte with another or with a source: the checks of api.hip).
+int scatter_pieces_impl(bwts_ctx *ctx, const PackPiece *pieces, u64 count)
+{
+    std::vector<u64> h((size_t)(4 * count + 1));
+    u64 *src = h.data(), *dst = src + count, *bytes = dst + count, *first = bytes + count;
+    u64 tiles = 0, total = 0;
+    for (u64 i = 0; i < count; i++) {
+        src[i] = pieces[i].src; dst[i] = pieces[i].dst; bytes[i] = pieces[i].bytes;
+        first[i] = tiles;
+        tiles += pieces_tiles(pieces[i].bytes, pieces[i].dst & (PIECES_LINE - 1u));
+        total += pieces[i].bytes;
+    }
+    first[count] = tiles;
+    PiecesTable P = {nullptr, nullptr, nullptr, nullptr, count, tiles, pieces[0]};
+    if (count > 1) {
+        u64 *d = nullptr;
+        BlockLayout L;
+        L.array(&d, h.size());
+        BWTS_TRY(arena_take(ctx, L));
+        HIPC(hipMemcpyAsync(d, h.data(), h.size() * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+        P.src = d; P.dst = d + count; P.bytes = d + 2 * count; P.first = d + 3 * count;
+    }
+    {
+        SpanGuard sp(ctx, BWTS_K_OTHER, total, 2 * total);
+        scatter_pieces_kernel<<<dim3((unsigned)(tiles < PIECES_GRID ? tiles : PIECES_GRID)), dim3(256), 0, ctx->stream>>>(P);
     }
     HIPC(hipGetLastError());
     HIPC(hipStreamSynchronize(ctx->stream));

@@ -154,6 +154,32 @@
  *   Bound: bwts_pack_members_bound_a: an AUTO member counts with the larger of its two bounds, and the extension table with every AUTO
  *   member's words; without AUTO it is bwts_pack_members_bound_m.  No BWTS_E_SPACE for out_cap >= that bound; header and directory are
  *   written last, behind the streams, and a call that fails with BWTS_E_SPACE has written nothing.
+ *
+ * Pointers.  Tensors do not lie back to back: the _p calls take every member where it is.  d_srcs, d_dsts and d_members are host
+ * arrays of `count` device pointers; no alignment is asked of a member, and none need be a whole allocation.
+ *   bwts_gather_device copies member k, lengths[k] >= 1 bytes at d_srcs[k], to d_out, the members back to back in order;
+ *   bwts_scatter_device copies them from d_in, back to back, to d_dsts[k].  One launch of the copy kernel between scattered buffers
+ *   (csrc/pieces.hip): it reads nothing but a source member's own bytes, writes nothing but a destination's, and makes no access wider
+ *   than a byte at an address that is not a multiple of its width.  Refusals: BWTS_E_ARG for NULL pointers, count == 0 or a zero
+ *   length, BWTS_E_RANGE for count > 2^20 or a sum above 2^32; then BWTS_E_ARG for a NULL entry, for a member that shares a byte with
+ *   the contiguous side, and on scatter for two destinations that share a byte.  Sources of a gather may overlap or repeat.
+ *   bwts_pack_members_p_device is bwts_pack_members_a_device over such a table (AUTO values, NULL widths, filters and methods, the
+ *   bound and filters_out / methods_out with that call's meaning): the frame is, byte for byte, what that call writes for the same
+ *   members back to back, so no reader and no version changes.  The set is gathered into a block of n bytes that the context keeps
+ *   for this purpose (counted in bwts_timings::device_bytes, given up by bwts_ctx_release_memory); a set that lies back to back already,
+ *   d_members[k + 1] == d_members[k] + lengths[k] for all k, is passed on as it is and launches what the contiguous call launches.
+ *   Refusals, in this order: those of bwts_pack_members_a_device; a NULL table or entry, BWTS_E_ARG; a member that shares a byte with
+ *   [d_out, d_out + out_cap), BWTS_E_ARG.  Members may overlap one another or repeat.
+ *   bwts_unpack_members_p_device is bwts_unpack_members_device with a destination per index: member indices[j] goes to d_dsts[j], of
+ *   which dst_bytes[j] bytes may be written and only the member's len are.  indices == NULL means every member in order, and icount
+ *   must then be the frame's count (BWTS_E_ARG).  Indices may come in any order and may repeat; a member is decoded once and written to
+ *   every destination that names it.  Refusals, in this order: NULL ctx or d_in, in_bytes == 0, d_in not 16-byte aligned, BWTS_E_ARG;
+ *   the frame checks and the index checks of bwts_unpack_members_device, with their codes; a NULL table or entry, BWTS_E_ARG;
+ *   dst_bytes[j] below the member's length, BWTS_E_SPACE; two destinations that share a byte (of their members' len bytes), or one
+ *   that overlaps the frame, BWTS_E_ARG.  The decode ends in a block the context keeps, every member's CRC-32 is compared there, and
+ *   only then is anything scattered: a call that fails, BWTS_E_CHECKSUM and the coder's BWTS_E_FORMAT among it, has written nothing
+ *   to any destination.
+ *   The range readers have no pointer form.
  */
 #ifndef BWTS_MEMBERS_H
 #define BWTS_MEMBERS_H
@@ -214,6 +240,15 @@ int bwts_pack_members_a_device(bwts_ctx *ctx, const void *d_in, const uint64_t *
 int bwts_pack_members_a(bwts_ctx *ctx, const uint8_t *in, const uint64_t *lengths, const uint32_t *widths, const uint32_t *filters,
                         const uint32_t *methods, uint64_t count, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
                         uint32_t *filters_out, uint32_t *methods_out);
+
+/* members where they lie ("Pointers"): d_srcs, d_dsts, d_members are host arrays of device pointers */
+int bwts_gather_device(bwts_ctx *ctx, const void *const *d_srcs, const uint64_t *lengths, uint64_t count, void *d_out);
+int bwts_scatter_device(bwts_ctx *ctx, const void *d_in, void *const *d_dsts, const uint64_t *lengths, uint64_t count);
+int bwts_pack_members_p_device(bwts_ctx *ctx, const void *const *d_members, const uint64_t *lengths, const uint32_t *widths,
+                               const uint32_t *filters, const uint32_t *methods, uint64_t count, void *d_out, uint64_t out_cap,
+                               uint64_t *out_bytes, uint32_t *filters_out, uint32_t *methods_out);
+int bwts_unpack_members_p_device(bwts_ctx *ctx, const void *d_in, uint64_t in_bytes, const uint64_t *indices, uint64_t icount,
+                                 void *const *d_dsts, const uint64_t *dst_bytes);
 
 #ifdef __cplusplus
 }
